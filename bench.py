@@ -21,12 +21,19 @@ flux_pipeline.py:197-212): 13 calibrating steps that freeze the F8Linear input s
 N GPUs = N batch-sharded replicas (weak scaling); collectives: one RCCL broadcast of the T5/CLIP embeddings + noise before the
 loop and, during calibration only, the per-layer amax MAX-reduction.
 
-Prints ONE JSON line (rank 0).  `roofline` prices the dominant kernel of the configuration (the fp8 MX-MFMA GEMM; for config 1
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the --steps steps once (`ms_per_step` = that time / steps) and
+prints the line; `roofline`, `cpu_baseline` and the clock / power samples are null there.
+  python bench.py --full                                 also measures everything below: the median of --requests (default 3) timed
+                                                         repeats, the sustained clock and board power, the kernel probes, the in-step
+                                                         trace, the PMC passes and the CPU baseline
+  python bench.py --dump-outputs DIR                     after the timed steps, writes the latents the last request returned (all images
+                                                         of the job, gathered on rank 0) as DIR/latents.npy in float32
+With --full, `roofline` prices the dominant kernel of the configuration (the fp8 MX-MFMA GEMM; for config 1
 the bf16 GEMM's weight stream) from HIP-event timings taken live in this process on the launch stream; `cpu_baseline` times the
 reference's CPU flow path on the host cores for a bounded sample: the UNMODIFIED reference when /root/reference is present
 (build container), otherwise the oracle port that is pinned bit-for-bit to it (oracle/gen_golden*.py).
   python bench.py --cpu-baseline-only [--config C]      runs only that leg (no GPU needed)
-  python bench.py --no-pmc                               skips the live rocprofv3 PMC passes (HBM traffic, MFMA busy; default at N = 1 when
+  python bench.py --full --no-pmc                        skips the live rocprofv3 PMC passes (HBM traffic, MFMA busy; default at N = 1 when
                                                          rocprofv3 is on PATH, ~2 min); `roofline.source` says where each number came from
   python bench.py --gpus 2 --backend gloo --dry-run      no GPU: the multi-rank control flow (rendezvous, broadcast, sharding, in-step amax
                                                          exchange, barriers, max-over-ranks timing, one JSON line) on a stub engine
@@ -34,7 +41,7 @@ reference's CPU flow path on the host cores for a bounded sample: the UNMODIFIED
                                                          all-reduce, ONE broadcast of a request-sized payload, the latent gather; one JSON line;
                                                          exit codes 10 rendezvous / 11 all-reduce / 12 broadcast / 13 gather (works with
                                                          --backend gloo --dry-run on CPU and with --single-rank-group on a one-GPU box)
-`roofline.frac` is the IN-STEP figure: the same command runs one more graph-replayed request under `rocprofv3 --kernel-trace` (a child
+`roofline.frac` is the IN-STEP figure: the --full command runs one more graph-replayed request under `rocprofv3 --kernel-trace` (a child
 process of this script, after the timed region) and prices the GEMM family by its kernel time inside the steady steps; `roofline.step`
 splits the step into GEMM / attention / LayerNorm / other / gaps.  The isolated back-to-back probe of rounds 1 - 4 stays as
 `roofline.probe_frac` (it flatters a kernel: warm Infinity Cache, lower clock).  --no-step-trace skips the child.
@@ -234,11 +241,13 @@ def pmc_file(kind, cfg_id):
     return os.path.join(ROOT, "profiles", f"r06_{kind}_config{cfg_id}.json")
 
 
-def read_pmc(kind, cfg_id):
+def read_pmc(kind, cfg_id, d=None):
     """Counter values collected by `bench.py --pmc` (rocprofv3 PMC passes over tools/gemm_probe.py); null when the kernel sources
-    changed since (the file is keyed by a content hash of csrc/gemm*, attention*, common.h, api.cpp)."""
+    changed since (the file is keyed by a content hash of csrc/gemm*, attention*, common.h, api.cpp).  d = the directory of this run's
+    live summary; default: the committed file under profiles/."""
+    path = os.path.join(d, os.path.basename(pmc_file(kind, cfg_id))) if d else pmc_file(kind, cfg_id)
     try:
-        with open(pmc_file(kind, cfg_id)) as f:
+        with open(path) as f:
             d = json.load(f)
         return d if d.get("source_key") == kernel_source_key() else None
     except Exception:
@@ -273,8 +282,9 @@ def collect_pmc(cfg_id, Li, Lt):
                 pass
 
 
-def summarize_pmc(cfg_id, Li, Lt):
-    """raw CSVs -> profiles/r06_{traffic,mfma}_config<id>.json, keyed by the kernel-source hash.  HBM bytes per launch =
+def summarize_pmc(cfg_id, Li, Lt, dest=None):
+    """raw CSVs -> r06_{traffic,mfma}_config<id>.json in `dest` (default: the committed files under profiles/, what --pmc-summarize
+    rebuilds), keyed by the kernel-source hash.  HBM bytes per launch =
     (2 x FETCH_SIZE + WRITE_SIZE) KiB (gfx950 tallies a 128-B fabric read at 64 B: MI355X_MICROARCH.md 'HBM'); matrix-pipe busy fraction =
     SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE / 8 XCDs x 1024 SIMDs).  The first dispatch of every kernel (cold caches, lazy init) is
     dropped; the 256x256 kernels of a launch are summed with its 128x128 peel."""
@@ -308,12 +318,13 @@ def summarize_pmc(cfg_id, Li, Lt):
     key = kernel_source_key()
     w = {name: cnt for name, _m, _n, _k, cnt, _e in gemm_shapes(Li, Lt)}
     how = "bench.py --pmc: rocprofv3 --kernel-trace --pmc <counters> -- python tools/gemm_probe.py --shape M,N,K --cfg -1 (one pass per counter set)"
+    path = lambda kind: os.path.join(dest, os.path.basename(pmc_file(kind, cfg_id))) if dest else pmc_file(kind, cfg_id)
     if per_traffic:
         tot_b = sum(per_traffic[n] * w[n] for n in per_traffic) / sum(w[n] for n in per_traffic)
-        with open(pmc_file("traffic", cfg_id), "w") as f:
+        with open(path("traffic"), "w") as f:
             json.dump({"source_key": key, "bytes_per_launch": tot_b, "per_launch": per_traffic, "formula": "(2*FETCH_SIZE + WRITE_SIZE) KiB", "how": how}, f, indent=1)
     if per_busy:
-        with open(pmc_file("mfma", cfg_id), "w") as f:
+        with open(path("mfma"), "w") as f:
             json.dump({"source_key": key, "per_launch": per_busy,
                        "formula": "SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE / 8 * 1024)", "how": how}, f, indent=1)
     return per_traffic, per_busy
@@ -468,11 +479,11 @@ def collect_step_pmc(args, timeout_s=300.0):
     return root
 
 
-def summarize_step_pmc(root, cfg_id, ms_per_step=None):
+def summarize_step_pmc(root, cfg_id, ms_per_step=None, dest=None):
     """counter_collection.csv of the three passes -> per kernel family, per steady step of the last request: HBM-side bytes
     ((2 x FETCH_SIZE + WRITE_SIZE) KiB: gfx950 tallies a 128-byte fabric read at 64 B, MI355X_MICROARCH.md 'HBM'; Infinity-Cache hits count)
-    and the matrix-pipe busy fraction SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE / 8 XCDs x 1024 SIMDs).  Written to profiles/ with the
-    kernel-source hash."""
+    and the matrix-pipe busy fraction SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE / 8 XCDs x 1024 SIMDs).  Written with the kernel-source
+    hash to `dest` (default: the committed file under profiles/)."""
     import csv
     import glob
 
@@ -525,7 +536,7 @@ def summarize_step_pmc(root, cfg_id, ms_per_step=None):
     if ms_per_step:
         out["hbm_gbs_at_timed_ms_per_step"] = round(all_b / (ms_per_step * 1e-3) / 1e9, 1)
         out["ms_per_step_timed"] = ms_per_step
-    with open(step_pmc_file(cfg_id), "w") as f:
+    with open(os.path.join(dest, os.path.basename(step_pmc_file(cfg_id))) if dest else step_pmc_file(cfg_id), "w") as f:
         json.dump(out, f, indent=1)
     return out
 
@@ -833,18 +844,23 @@ def main():
     ap.add_argument("--config", type=int, default=2, choices=sorted(CONFIGS))
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-baseline-only", action="store_true")
-    ap.add_argument("--pmc", action="store_true", help="force the live rocprofv3 PMC passes (default: on at N = 1 when rocprofv3 is on PATH)")
+    ap.add_argument("--pmc", action="store_true", help="force the live rocprofv3 PMC passes (with --full they are on by default at N = 1 when rocprofv3 is on PATH)")
     ap.add_argument("--no-pmc", action="store_true", help="skip the live rocprofv3 PMC passes (~2 min)")
     ap.add_argument("--pmc-summarize", action="store_true", help="no GPU: rebuild profiles/r06_*_config<id>.json from gpurun_out/pmc_config<id>/")
-    ap.add_argument("--requests", type=int, default=3, help="timed repeats of the K steps (each bracketed and timed on its own; the median is reported)")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need: repeats, clock and power, kernel probes, "
+                    "in-step trace, PMC passes, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the latents the last request returned as DIR/latents.npy (float32)")
+    ap.add_argument("--requests", type=int, default=None, help="timed repeats of the K steps (each bracketed and timed on its own; the median is reported); "
+                    "default 1, with --full 3")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="process-group backend for N > 1 (nccl = RCCL over xGMI)")
     ap.add_argument("--dry-run", action="store_true", help="no GPU: run the multi-rank control flow on a stub engine (CPU tensors)")
     ap.add_argument("--depth", type=int, default=None, help="debug only: fewer blocks (the result is then flagged invalid)")
     ap.add_argument("--preflight", action="store_true", help="check the N-rank plumbing (group, all-reduce, request broadcast, latent gather) and exit; no model")
     ap.add_argument("--no-step-trace", action="store_true", help="skip the extra request under rocprofv3 --kernel-trace (roofline.frac is then the isolated probe's)")
-    ap.add_argument("--pmc-step", action="store_true", help="also collect hardware counters of the kernels INSIDE the step (HBM-side bytes, matrix-pipe busy): three more "
-                    "child runs under rocprofv3 --pmc, ~1 min each; the result is kept in profiles/r06_step_pmc_config<id>.json and reported while the kernel sources match")
+    ap.add_argument("--pmc-step", action="store_true", help="with --full: also collect hardware counters of the kernels INSIDE the step (HBM-side bytes, matrix-pipe "
+                    "busy): three more child runs under rocprofv3 --pmc, ~1 min each; the summary is written beside the raw counters, and a copy committed as "
+                    "profiles/r06_step_pmc_config<id>.json is reported while the kernel sources match")
     ap.add_argument("--keep-trace", action="store_true", help="keep the raw rocprofv3 CSVs of the step trace under gpurun_out/step_trace_config<id>/")
     ap.add_argument("--no-probe", action="store_true", help="skip the isolated GEMM / attention probe loops (used by the step-trace child)")
     ap.add_argument("--single-rank-group", action="store_true",
@@ -855,6 +871,12 @@ def main():
                          "request broadcast, in-step amax exchange from the engine's hook, barriers, max-over-ranks timing, one JSON line.  The ranks share "
                          "the chip, so the line is flagged `share_device` and is NOT a scaling measurement")
     args = ap.parse_args()
+    if (args.pmc or args.pmc_step or args.keep_trace) and not args.full:
+        ap.error("--pmc, --pmc-step and --keep-trace are parts of --full")
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.requests is None:
+        args.requests = 3 if args.full else 1
     C = CONFIGS[args.config]
     if args.share_device and (args.backend != "gloo" or args.gpus < 2):
         raise SystemExit("--share-device needs --gpus N >= 2 and --backend gloo (RCCL refuses two ranks on one device)")
@@ -1015,8 +1037,8 @@ def main():
         # (fluxmi_clock_sample): their ratio is the clock the chip SUSTAINED over that repeat -- this workload is power-limited, and a
         # slow box or a throttling one shows up here instead of as unexplained spread.  Board power / sclk from hwmon, when readable.
         R = max(1, args.requests)
-        clk = None if dry else torch.zeros((R + 1) * 8 * 3, dtype=torch.int64, device=dev)
-        power = _PowerSampler(_pci_bdf(torch, dev)) if (not dry and rank == 0) else None
+        clk = None if (dry or not args.full) else torch.zeros((R + 1) * 8 * 3, dtype=torch.int64, device=dev)
+        power = _PowerSampler(_pci_bdf(torch, dev)) if (args.full and not dry and rank == 0) else None
         elapsed_each, finite = [], True
         out = None
         for rep in range(R):
@@ -1065,6 +1087,14 @@ def main():
                       file=sys.stderr, flush=True)
                 os._exit(4)
             nranks = nranks_seen
+        if args.dump_outputs:
+            # what a caller of the timed path receives from its last request: the latents of every image of the job, gathered on rank 0
+            lat = fdist.gather_latents(out, world * ipg, dst=0)
+            if rank == 0:
+                import numpy as np
+
+                os.makedirs(args.dump_outputs, exist_ok=True)
+                np.save(os.path.join(args.dump_outputs, "latents.npy"), lat.float().cpu().numpy())
 
         result = None
         if rank == 0:
@@ -1072,7 +1102,7 @@ def main():
             ms_per_step = elapsed / steps_done * 1e3
             loop_its = steps_done / elapsed                 # loop iterations per second on one GPU (what the reference's tqdm prints)
             its = world * ipg * loop_its                    # whole job: every image of every GPU advances one step per loop iteration
-            ms_each = [round(e / steps_done * 1e3, 3) for e in elapsed_each]
+            ms_each = [round(e / steps_done * 1e3, 6) for e in elapsed_each]
             fp8 = C["quant"] is not None
             cfg_block = {"workload": f"BASELINE.json configs[{args.config - 1}]: {C['name']}; batch {ipg} per GPU, Li={Li}+Lt={Lt} tokens, "
                                      f"{p.depth} double + {p.depth_single_blocks} single blocks, {spr} step(s) per request x {n_req} request(s) = {steps_done} "
@@ -1084,7 +1114,7 @@ def main():
             result = {
                 "metric": "denoise it/s, " + C["name"] + (" (image-steps per second: every loop iteration advances all images of the batch by one step)" if ipg > 1 else ""),
                 "value": round(its, 4), "unit": "it/s", "n_gpus": world, "steps": steps_done, "warmup": args.warmup,
-                "ms_per_step": round(ms_per_step, 3), "requests": R, "ms_per_step_each": ms_each,
+                "ms_per_step": round(ms_per_step, 6), "requests": R, "ms_per_step_each": ms_each,
                 "value_range": [round(world * ipg * steps_done / max(elapsed_each), 4), round(world * ipg * steps_done / min(elapsed_each), 4)],
                 "loop_its_per_gpu": round(loop_its, 4), "image_steps_per_s": round(its, 4),
                 "sustained_shader_clock_ghz_each": clock_each, "board_power": power.summary() if power else None,
@@ -1102,6 +1132,15 @@ def main():
                                "amax_exchanges": model.exchanges})
             else:
                 lin_flops = linear_flops_per_step(Li, Lt, batch=ipg)
+                result.update({
+                    "reference_h100_compiled_its": H100_COMPILED.get(args.config),
+                    "vs_h100_compiled": round(its / world / H100_COMPILED[args.config], 3) if args.config in H100_COMPILED else None,
+                    "fp8_mfma_fraction_whole_step": round(lin_flops / (ms_per_step * 1e-3) / (FP8_PEAK_TFLOPS * 1e12), 4) if fp8 else None,
+                    "ms_per_step_hipevent": round(ms_ev_v / n_ev_v, 3) if n_ev_v else None,
+                    "setup_s": round(setup_s, 1),
+                    "roofline": None,
+                })
+            if args.full and not dry:
                 attn_flops = 4.0 * (Li + Lt) ** 2 * 128 * p.num_heads * ipg
                 n_lin = sum(cnt for *_x, cnt, _e in gemm_shapes(Li, Lt))  # grouped Linear launches per step (152)
                 n_attn = p.depth + p.depth_single_blocks
@@ -1147,20 +1186,24 @@ def main():
                     src["achieved"] = "isolated probe loop (HIP events on the launch stream, this process): no step trace (rocprofv3 not on PATH, N > 1, or --no-step-trace)"
                     avg_us = probe["probe_avg_launch_us"]
                 peak = FP8_PEAK_TFLOPS if fp8 else HBM_PEAK_GBS
+                live_pmc = {"traffic": None, "mfma": None}  # this run's summaries stay beside its raw counters: the committed files are not rewritten
                 if world == 1 and fp8 and ipg == 1 and not args.no_probe and (args.pmc or (have_prof and not args.no_pmc)):
                     try:
                         collect_pmc(args.config, Li, Lt)
-                        per_t, per_b = summarize_pmc(args.config, Li, Lt)
+                        per_t, per_b = summarize_pmc(args.config, Li, Lt, dest=pmc_dir(args.config))
                         if per_t:
                             src["traffic"] = "live (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes run by this command)"
+                            live_pmc["traffic"] = pmc_dir(args.config)
                         if per_b:
                             src["mfma_busy"] = "live (rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES / GRBM_GUI_ACTIVE pass run by this command)"
+                            live_pmc["mfma"] = pmc_dir(args.config)
                     except Exception as ex:  # the counters must never take the measurement down
                         print(f"bench: PMC collection failed: {ex}", file=sys.stderr)
                 step_pmc = None
                 if world == 1 and have_prof and args.pmc_step:
                     try:
-                        step_pmc = summarize_step_pmc(collect_step_pmc(args), args.config, ms_per_step=round(ms_per_step, 3))
+                        pmc_root = collect_step_pmc(args)
+                        step_pmc = summarize_step_pmc(pmc_root, args.config, ms_per_step=round(ms_per_step, 3), dest=pmc_root)
                     except Exception as ex:  # noqa
                         print(f"bench: step PMC failed: {ex}", file=sys.stderr)
                 if step_pmc is None:
@@ -1169,7 +1212,7 @@ def main():
                         step_pmc = dict(step_pmc, source="committed file profiles/" + os.path.basename(step_pmc_file(args.config)) + " (same kernel sources, earlier run)")
                 else:
                     step_pmc = dict(step_pmc, source="live (bench.py --pmc-step)")
-                traffic, busy = (read_pmc("traffic", args.config), read_pmc("mfma", args.config)) if ipg == 1 else (None, None)
+                traffic, busy = (read_pmc("traffic", args.config, live_pmc["traffic"]), read_pmc("mfma", args.config, live_pmc["mfma"])) if ipg == 1 else (None, None)
                 if traffic and src["traffic"] is None:
                     src["traffic"] = "committed file profiles/" + os.path.basename(pmc_file("traffic", args.config)) + " (same kernel sources, earlier run)"
                 if busy and src["mfma_busy"] is None:
@@ -1204,16 +1247,9 @@ def main():
                                      "frac": round(attn_flops * n_attn / a_s / 1e12 / BF16_PEAK_TFLOPS, 4), "source": "in-step (the same kernel trace)"})
                 elif attn_row is not None:
                     attn_row.update({"us": attn_row["probe_us"], "achieved": attn_row["probe_achieved"], "frac": attn_row["probe_frac"], "source": "isolated probe loop"})
-                result.update({
-                    "reference_h100_compiled_its": H100_COMPILED.get(args.config),
-                    "vs_h100_compiled": round(its / world / H100_COMPILED[args.config], 3) if args.config in H100_COMPILED else None,
-                    "fp8_mfma_fraction_whole_step": round(lin_flops / (ms_per_step * 1e-3) / (FP8_PEAK_TFLOPS * 1e12), 4) if fp8 else None,
-                    "ms_per_step_hipevent": round(ms_ev_v / n_ev_v, 3) if n_ev_v else None,
-                    "setup_s": round(setup_s, 1),
-                    "roofline": roof,
-                })
+                result["roofline"] = roof
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline and not dry:
+        if world == 1 and args.full and not args.no_cpu_baseline and not dry:
             try:
                 result["cpu_baseline"] = cpu_baseline(args.config)
             except Exception as ex:  # the baseline must never take the measurement down

@@ -182,7 +182,7 @@ def test_config_jsons_load(tmp_path):
     import util
 
     files = sorted(glob.glob(os.path.join(ROOT, "flux-fp8-api_amd", "configs", "*.json")))
-    files += sorted(glob.glob("/root/reference/configs/*.json"))  # present in the build container only
+    files += sorted(glob.glob(os.path.join(ROOT, "tests", "golden", "configs", "*.json")))  # the reference's own shipped JSONs
     assert files
     for f in files:
         cfg = util.load_config_from_path(f)

@@ -241,10 +241,23 @@ def test_bench_multi_rank_launch_paths(launcher):
     assert abs(d["value"] - 2 * d["steps"] / (d["ms_per_step"] * d["steps"] * 1e-3)) / d["value"] < 1e-2  # whole-job aggregate
 
 
-def test_bench_single_rank_dry_run_and_failed_exchange():
-    r, out = _run_bench(["--gpus", "1"])
+def test_bench_single_rank_dry_run_and_failed_exchange(tmp_path):
+    import numpy as np
+
+    # a plain run times the --steps steps ONCE; --dump-outputs writes the latents its last request returned, identical from run to run
+    dumps = []
+    for i in range(2):
+        r, out = _run_bench(["--gpus", "1", "--dump-outputs", str(tmp_path / str(i))])
+        assert r.returncode == 0 and len(out) == 1, r.stderr[-2000:]
+        d = out[0]
+        assert d["steps"] == 6 and d["requests"] == 1 and d["ms_per_step_each"] == [d["ms_per_step"]] and d["cpu_baseline"] is None
+        assert abs(d["value"] - 1e3 / d["ms_per_step"]) / d["value"] <= 1e-3
+        dumps.append(np.load(tmp_path / str(i) / "latents.npy"))
+    assert dumps[0].dtype == np.float32 and dumps[0].shape == (1, 16, 64) and np.isfinite(dumps[0]).all()
+    assert np.array_equal(dumps[0], dumps[1])
+    r, out = _run_bench(["--gpus", "1", "--full"])
     assert r.returncode == 0 and len(out) == 1 and out[0]["n_gpus"] == 1 and out[0]["config"]["backend"] is None, r.stderr[-2000:]
-    # the headline is the MEDIAN of `requests` timed repeats of `steps` steps each; every repeat and the range are in the line
+    # with --full the headline is the MEDIAN of `requests` timed repeats of `steps` steps each; every repeat and the range are in the line
     d = out[0]
     each = d["ms_per_step_each"]
     assert d["requests"] == len(each) == 3 and d["ms_per_step"] == sorted(each)[1]
@@ -257,7 +270,7 @@ def test_bench_single_rank_dry_run_and_failed_exchange():
     assert "injected exchange failure" in r.stderr
 
 
-def test_bench_preflight_and_batched_config():
+def test_bench_preflight_and_batched_config(tmp_path):
     """`bench.py --gpus N --preflight`: the first contact of the N-rank plumbing without a model -- process group, rank-id
     all-reduce, ONE broadcast of a request-sized payload (T5 states + CLIP vector + packed noise of every image), the latent gather -- one JSON
     line from rank 0, and a DISTINCT exit status per failing stage (10 rendezvous, 11 all-reduce, 12 broadcast, 13 gather).  And `--config 4`
@@ -273,11 +286,15 @@ def test_bench_preflight_and_batched_config():
         assert str(code) in r.stderr or r.returncode in (code, 1), (stage, r.returncode)  # torch.distributed.run reports the failing rank's exit code
     r, out = _run_bench(["--gpus", "1", "--preflight", "--single-rank-group"])
     assert r.returncode == 0 and out[0]["preflight"] == "ok" and out[0]["nranks"] == 1
-    r, out = _run_bench(["--gpus", "2", "--config", "4"])
+    r, out = _run_bench(["--gpus", "2", "--config", "4", "--dump-outputs", str(tmp_path)])
     assert r.returncode == 0 and len(out) == 1, r.stderr[-1500:]
     d = out[0]
     assert d["config"]["images_per_gpu"] == 4 and d["config"]["global_batch"] == 8 and d["n_gpus"] == 2
     assert abs(d["value"] - 8 * d["loop_its_per_gpu"]) / d["value"] < 1e-3 and d["image_steps_per_s"] == d["value"]
+    import numpy as np
+
+    lat = np.load(tmp_path / "latents.npy")  # the whole job's latents: both ranks' shards, gathered on rank 0
+    assert lat.dtype == np.float32 and lat.shape == (8, 16, 64) and np.isfinite(lat).all()
 
 
 def test_bench_step_trace_and_step_pmc_summaries(tmp_path, monkeypatch):

@@ -4,8 +4,8 @@
 # Every recipe writes under gpurun_out/<tag>/<n>_* and prints a short tail; summaries worth judging are copied to profiles/ afterwards.
 #   suite            the driver's command: pytest -x -q -m gpu (+ durations), then smoke()
 #   suite_hog        the same with a CPU hog on half of the host's hardware threads beside it (a "busy box")
-#   bench            the driver's bench command (python bench.py --gpus 1, defaults) with its in-step trace
-#   bench_pmc        bench.py --gpus 1 --pmc-step (separate counter passes)
+#   bench            python bench.py --gpus 1 --full: the headline run with its in-step trace, probes, PMC passes and CPU baseline
+#   bench_pmc        bench.py --gpus 1 --full --pmc-step (separate counter passes)
 #   bench:<args>     bench.py with explicit arguments:  bench:--config_3_--steps_20     ('_' -> space, '%' -> '_')
 #   py:<script+args> python <script> <args>:            py:tools/attn%probe.py_--L_4608  ('_' -> space, '%' -> '_')
 #   pytest:<k-expr>  pytest -m gpu -x -q -s -k <expr>:  pytest:attention+or+qkv_rope     ('+' -> space)
@@ -40,8 +40,8 @@ for r in "$@"; do
       ( time python -c "import __graft_entry__ as g; g.smoke()" ) > "$out/${n}_smoke.log" 2>&1; echo "smoke rc=$?" >> "$out/${n}_smoke.log"
       grep -E "passed|failed|rc=|real" "$log" | tail -n 4; grep -E "smoke|rc=" "$out/${n}_smoke.log" | tail -n 3 ;;
     bench|bench_pmc|bench:*)
-      args="--gpus 1"
-      [ "$r" = bench_pmc ] && args="--gpus 1 --pmc-step"
+      args="--gpus 1 --full"
+      [ "$r" = bench_pmc ] && args="--gpus 1 --full --pmc-step"
       case "$r" in bench:*) args=$(words "${r#bench:}") ;; esac
       ( time python bench.py $args ) > "$out/${n}_bench.json" 2> "$out/${n}_bench.err"; echo "bench rc=$?" >> "$out/${n}_bench.err"
       keep_traces "$n"

@@ -652,12 +652,15 @@ int fluxmi_k_axpy_f32(float* w, const float* d, float alpha, long long n, hipStr
   return 0;
 }
 
+// the row-pair output layout (out_pairs) is written by the streaming kernel only: it serves hidden sizes whose four fp32 vectors fit its LDS
+// (H * 16 <= 48 KiB: H <= 3072) and runs when fluxmi_tuning_t.ln_variant >= 2; the engine asks before it keeps its activations in pairs
+int fluxmi_ln_pairs_ok(int H) { return H % 64 == 0 && (size_t)H * 16 <= 49152 && fluxmi_tuning().ln_variant >= 2; }
+
 int fluxmi_k_ln_modulate(const void* x, long long ldx, long long x_bstride, void* out, long long ldo, long long out_bstride,
                          const void* shift0, const void* scale0, const void* shift1, const void* scale1, long long mod_bstride,
                          const float* q0, const float* q1, int B, int L, int split, int H, int out_fp8, int fmt, hipStream_t s, int out_pairs) {
   FLUXMI_REQUIRE(H % 8 == 0 && H <= 4096, "ln_modulate: hidden size %d unsupported (need %%8==0, <=4096)", H);
-  FLUXMI_REQUIRE(!out_pairs || (out_fp8 && ldo == H && out_bstride == (long long)L * ldo && H % 64 == 0 && ((long long)B * L) % 2 == 0 &&
-                                fluxmi_tuning().ln_variant >= 2 && (size_t)H * 16 <= 49152),
+  FLUXMI_REQUIRE(!out_pairs || (out_fp8 && ldo == H && out_bstride == (long long)L * ldo && ((long long)B * L) % 2 == 0 && fluxmi_ln_pairs_ok(H)),
                  "ln_modulate: the row-pair output layout needs fp8 output, dense rows, an even row count and the streaming kernel");
   FLUXMI_REQUIRE(!out_fp8 || (q0 && q1), "ln_modulate: fp8 output needs q_scale pointers");
   if (B * L == 0) return 0;

@@ -18,6 +18,7 @@
 //   attn8  fp8  [B, L, H];  h8 fp8 [B, L, 4H];  cat8 fp8 [B, L, 5H]  (single block: attn | gelu(mlp))
 //   mod    bf16 [B, 12H*depth + 3H*single + 2H]   all modulation vectors of the step
 #include <dlfcn.h>
+#include <limits.h>
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
@@ -77,6 +78,9 @@ struct fluxmi_engine {
   bool pairs_skipped = false;      // the copies were wanted and did not fit (ensure_pairs): retried at the next prepare
   unsigned pairs_gen = 0;          // fluxmi_tuning_generation() the copies were built under (fluxmi_tuning_t.w_pairs may have changed)
   int* d_step0 = nullptr;          // first step of the modulation table (device scalar: the captured graph reads it)
+  // the layout each fp8 activation buffer (ACT_A8 .. ACT_CAT8) was last written in: true = row pairs (fused mode, act_pairs), false = plain
+  // rows.  Set by the stages that write them (and by a replayed step graph); fluxmi_engine_copy_buffer converts by it
+  bool act_in_pairs[4] = {false, false, false, false};
   int mods_rows_cap = 0;           // rows (steps x B) the table holds; sized in engine_prepare, never inside denoise
   // pinned host staging for the per-request schedule (ts | dts), guarded by an event so that engine_denoise never waits on the stream
   float* h_sched = nullptr;
@@ -162,9 +166,15 @@ const void* pairs_of(E* e, int li) {
 // the block linears -- keep the 64-byte K-steps of rows 2r and 2r + 1 in one 128-byte line, so an A panel's lines cross L2 -> CU once per
 // tile instead of twice (what W_pairs does for the weights).  Needs every row offset of a group to be even: L and Lt even, hidden % 64 == 0.
 // The unfused / calibrating modes keep plain rows (their producers are the standalone quantise kernels).
+// Every producer and consumer of the step must handle the layout: the LayerNorm kernel writes it only from its streaming form (hidden <= 3072,
+// ln_variant >= 2: fluxmi_ln_pairs_ok), and the generic GEMM kernel -- the fallback of a launch no tile config fits, e.g. a single block's
+// split column 3H that is no multiple of a 256-column tile -- reads and writes plain rows only; otherwise the step keeps plain rows (same bits).
 bool act_pairs(const E* e, bool fused) {
-  return fused && fluxmi_tuning().a_pairs && e->L % 2 == 0 && e->Lt % 2 == 0 && e->d.hidden % 64 == 0 && e->d.mlp_hidden % 64 == 0;
+  const int H = e->d.hidden, Hm = e->d.mlp_hidden;
+  return fused && fluxmi_tuning().a_pairs && e->L % 2 == 0 && e->Lt % 2 == 0 && fluxmi_ln_pairs_ok(H) && Hm % 128 == 0 && (3 * H) % 256 == 0;
 }
+// fp8 activation buffers whose layout is recorded (fluxmi_engine::act_in_pairs)
+enum { ACT_A8 = 0, ACT_ATTN8 = 1, ACT_H8 = 2, ACT_CAT8 = 3 };
 // Linears whose launches go through the kernels that honour W_pairs at Flux geometry: the persistent kernel (double blocks' qkv and mlp.0,
 // single blocks' linear1) and the one-wave-per-SIMD kernel (mlp.2, linear2).  +8 GB at Flux-dev.  Built lazily on the caller's stream:
 // create / rebind have none, and a rebind follows weight surgery.
@@ -588,6 +598,7 @@ int double_block(E* e, const Ctx& c, int i, int mode, int trial, int s0, int s1,
     const int so = half * 3;  // offset of (shift, scale, gate) triple inside the 6H chunk
     const int* li_in = half == 0 ? li_q : li_m0;
     if (on(half == 0 ? 0 : 5)) {
+      e->act_in_pairs[ACT_A8] = ap;
       if (fused) {
         FLUXMI_TRY(fluxmi_k_ln_modulate(x, H, XB, a8, H, XB, mt + so * H, mt + (so + 1) * H, mi + so * H, mi + (so + 1) * H, MC,
                                         e->lin[li_in[0]].in_scale, e->lin[li_in[1]].in_scale, B, L, Lt, H, 1, e->lin[li_in[0]].in_fmt, s, ap));
@@ -625,6 +636,7 @@ int double_block(E* e, const Ctx& c, int i, int mode, int trial, int s0, int s1,
       if (on(2) && !fuse_k)
         FLUXMI_TRY(fluxmi_k_qkv_rope(qkv, 3 * H, pe, ns[2], ns[3], ns[0], ns[1], nullptr, K, fuse_v ? nullptr : VT, B, L, e->Lp, heads, Lt, attn_f16k(), s));
       if (on(3)) {
+        e->act_in_pairs[ACT_ATTN8] = ap;
         if (fused) {
           // attention's last round leaves CUs idle (432 workgroups = 1.69 rounds at L = 4608): they pull in the weights this block needs
           // next -- proj and mlp.0 (94 MB); fluxmi_tuning_t.prefetch = 2: mlp.2 as well (170 MB, as much as the idle CUs read in that time)
@@ -658,6 +670,7 @@ int double_block(E* e, const Ctx& c, int i, int mode, int trial, int s0, int s1,
       }
     } else {
       if (on(6)) {  // mlp.0 (+GELU, + quantise for mlp.2)
+        e->act_in_pairs[ACT_H8] = ap;
         std::vector<FluxmiGemmGroup> gs;
         for (int b = 0; b < B; ++b)
           for (int st = 0; st < 2; ++st) {
@@ -722,6 +735,8 @@ int single_block(E* e, const Ctx& c, int i, int mode, int trial, int s0, int s1,
   const int l1 = SLi(e, i, S_LIN1), l2 = SLi(e, i, S_LIN2);
   const fluxmi_linear_t &L1 = e->lin[l1], &L2 = e->lin[l2];
   const void* const* ns = &e->norm[e->d.depth * 4 + i * 2];
+  if (on(0)) e->act_in_pairs[ACT_A8] = ap;
+  if ((fused && on(1)) || on(3)) e->act_in_pairs[ACT_CAT8] = ap;  // fused: linear1 writes the GELU part, attention the rest
   if (fused) {
     const bool fuse_v = fuse_kv_level() >= 1 && fluxmi_gemm_tile_ok(3 * H + Hm, H, 1, 13);
     const bool fuse_k = fuse_kv_level() >= 2 && fuse_v && H % 256 == 0 && L >= 2048;  // short sequences: one launch of the relayout kernel is cheaper
@@ -941,6 +956,8 @@ int fluxmi_engine_create(const fluxmi_model_desc_t* desc, const fluxmi_linear_t*
   FLUXMI_REQUIRE(desc && linears && norm_scales && out, "engine_create: NULL argument");
   fluxmi_log_tuning("engine_create");  // the kernel choices this engine will run with (FLUXMI_LOG=1)
   FLUXMI_REQUIRE(desc->hidden == desc->heads * 128, "engine_create: head_dim must be 128 (hidden %d, heads %d)", desc->hidden, desc->heads);
+  // the LayerNorm + modulate kernels hold a row (wave per row) or four fp32 vectors of it (streaming) on chip: refused here, not mid-step
+  FLUXMI_REQUIRE(desc->hidden <= 4096, "engine_create: hidden %d > 4096, the widest row the LayerNorm kernels take", desc->hidden);
   FLUXMI_REQUIRE(desc->axes_dim[0] + desc->axes_dim[1] + desc->axes_dim[2] == 128, "engine_create: sum(axes_dim) must be 128");
   FLUXMI_REQUIRE(n_linears == lin_count(*desc), "engine_create: expected %d linears, got %d", lin_count(*desc), n_linears);
   FLUXMI_REQUIRE(n_norm_scales == desc->depth * 4 + desc->depth_single * 2, "engine_create: expected %d norm scales, got %d",
@@ -1247,6 +1264,10 @@ int fluxmi_engine_denoise(fluxmi_engine_t* e, void* img, const void* txt, const 
       }
       if (use_graph && e->graph_ok) {
         for (; step < win_end; ++step) FLUXMI_CHECK_HIP(hipGraphLaunch(e->exec, s));
+        // the host code of the step ran at capture only: the replayed graph wrote the activation buffers in the layout it was captured with
+        // (a tuning change since the capture re-captures above)
+        const bool ap = act_pairs(e, mode == 1);
+        for (bool& b : e->act_in_pairs) b = ap;
       } else {
         for (; step < win_end; ++step) FLUXMI_TRY(one_step(s));
       }
@@ -1315,16 +1336,18 @@ int fluxmi_engine_copy_buffer(fluxmi_engine_t* e, const char* name, long long of
   FLUXMI_REQUIRE(offset >= 0 && bytes >= 0 && (size_t)(offset + bytes) <= it->second.n, "engine_copy_buffer: [%lld, +%lld) outside '%s' (%zu bytes)",
                  offset, bytes, name, it->second.n);
   char* p = (char*)it->second.p + offset;
-  // the fp8 activation buffers are exchanged as PLAIN rows; the FUSED path keeps them in the row-pair layout (act_pairs): convert on the way
-  // (whole row pairs only).  The unfused / calibrating modes use plain rows -- this hook serves the fused teacher-forced tests.
-  long long ld = 0;
+  // the fp8 activation buffers are exchanged as PLAIN rows.  Inside the engine each is in the layout its last writer used (act_in_pairs: row
+  // pairs from a fused step, plain rows from the unfused / calibrating modes): a read converts from that layout, a write stores in it -- the
+  // stage that reads the buffer next is expected to run in the mode that wrote it (the teacher-forced tests: run a stage, replace its
+  // output with the oracle's, run the next stage in the same mode).  Whole row pairs only.
   const std::string nm(name);
-  if (nm == "a8" || nm == "attn8") ld = e->d.hidden;
-  else if (nm == "h8") ld = e->d.mlp_hidden;
-  else if (nm == "cat8") ld = (long long)e->d.hidden + e->d.mlp_hidden;
-  if (ld > 0 && act_pairs(e, true)) {
+  const int slot = nm == "a8" ? ACT_A8 : nm == "attn8" ? ACT_ATTN8 : nm == "h8" ? ACT_H8 : nm == "cat8" ? ACT_CAT8 : -1;
+  const long long ld = slot == ACT_A8 || slot == ACT_ATTN8 ? e->d.hidden : slot == ACT_H8 ? e->d.mlp_hidden
+                                                                          : (long long)e->d.hidden + e->d.mlp_hidden;
+  if (slot >= 0 && e->act_in_pairs[slot]) {
     FLUXMI_REQUIRE(offset % (2 * ld) == 0 && bytes % (2 * ld) == 0, "engine_copy_buffer: '%s' is kept in row pairs: offset / size must cover whole pairs of %lld-byte rows",
                    name, ld);
+    FLUXMI_REQUIRE(bytes / ld <= INT_MAX, "engine_copy_buffer: %lld rows of '%s' in one copy exceed the pair kernels' int row count", bytes / ld, name);
     return to_engine ? fluxmi_k_pair_rows(dev_ptr, p, (int)(bytes / ld), ld, (hipStream_t)stream)
                      : fluxmi_k_unpair_rows(p, dev_ptr, (int)(bytes / ld), ld, (hipStream_t)stream);
   }

@@ -98,7 +98,8 @@ int fluxmi_launch_gemm(FluxmiGemmParams& p, int is_fp8, int act_fmt, int tile_cf
 int fluxmi_launch_gemm_generic(FluxmiGemmParams& p, int is_fp8, int act_fmt, hipStream_t s);
 const void* fluxmi_zero_page();  // 256 zero bytes on the current device (vae.hip; allocated once per device, never under stream capture)
 int fluxmi_launch_gemm_conv(FluxmiGemmParams& p, hipStream_t s);  // bf16, tile config 2 with the implicit 3x3 gather (p.conv filled by the caller)
-int fluxmi_gemm_auto_cfg(const FluxmiGemmParams& p, int is_fp8);
+int fluxmi_gemm_auto_cfg(const FluxmiGemmParams& p, int is_fp8, int act_fmt);
+int fluxmi_gemm_cfg_supports(const FluxmiGemmParams& p, int is_fp8, int act_fmt, int cfg);  // gemm.hip: launch p runs on tile config cfg
 // persistent 256x256 ping-pong kernel (gemm_persist.hip, tile config 18; 19 = with per-tile timestamps)
 int fluxmi_gemm_persist_ok(const FluxmiGemmParams& p, int is_fp8, int act_fmt);
 int fluxmi_launch_gemm_persist(FluxmiGemmParams& p, int is_fp8, int act_fmt, int timing, hipStream_t s);
@@ -136,6 +137,7 @@ int fluxmi_k_dequant(const void* q, float* out, const float* recip, long long n,
 int fluxmi_k_requantize_f32(const float* w32, void* q, float* amax_tmp, float* scale, float* recip, long long n, int fmt, hipStream_t s);
 int fluxmi_k_lora_delta(const float* Bm, const float* A, float* delta, int N, int K, int R, float scale, int accumulate, hipStream_t s);
 int fluxmi_k_axpy_f32(float* w, const float* d, float alpha, long long n, hipStream_t s);
+int fluxmi_ln_pairs_ok(int H);  // elementwise.hip: fluxmi_k_ln_modulate can write the row-pair layout at this hidden size / ln_variant
 int fluxmi_k_ln_modulate(const void* x, long long ldx, long long x_bstride, void* out, long long ldo, long long out_bstride,
                          const void* shift0, const void* scale0, const void* shift1, const void* scale1, long long mod_bstride,
                          const float* q0, const float* q1, int B, int L, int split, int H, int out_fp8, int fmt, hipStream_t s, int out_pairs = 0);

@@ -379,6 +379,22 @@ int fluxmi_gemm_tile_ok(int N, int K, int is_fp8, int cfg) {
   return (N % bn == 0) && (kb % kstep == 0) && kb >= kstep;
 }
 
+// Whether tile config `cfg` runs launch `p` as it stands: the conditions fluxmi_launch_gemm and the per-config launchers REQUIRE (tiling, the
+// split column, fused K / V^T outputs, operand format and epilogue of configs 17 / 20 / 21, the persistent kernel's conditions for 18 / 19).
+// A forced tile config (fluxmi_tuning_t.gemm_cfg) is taken only where this holds; every other launch keeps the automatic choice.
+int fluxmi_gemm_cfg_supports(const FluxmiGemmParams& p, int is_fp8, int act_fmt, int cfg) {
+  if (!fluxmi_gemm_tile_ok(p.N, p.K, is_fp8, cfg)) return 0;
+  if (p.epi == FLUXMI_EPI_SPLIT && p.g[0].split_n % fluxmi_gemm_tile_bn(cfg) != 0) return 0;
+  bool fused_out = false;
+  for (int i = 0; i < p.n_groups; ++i) fused_out |= (p.g[i].vt_out != nullptr || p.g[i].k_out != nullptr);
+  if (fused_out && cfg != 13 && cfg != 16 && cfg != 18 && cfg != 19) return 0;
+  if (cfg == 18 || cfg == 19) return fluxmi_gemm_persist_ok(p, is_fp8, act_fmt);
+  const bool f8_gate = is_fp8 && act_fmt == FLUXMI_FMT_E5M2 && p.epi == FLUXMI_EPI_GATE_RESID;
+  if (cfg == 17) return f8_gate || (!is_fp8 && (p.epi == FLUXMI_EPI_BF16 || p.epi == FLUXMI_EPI_GATE_RESID));
+  if (cfg == 20 || cfg == 21) return f8_gate;
+  return 1;
+}
+
 int fluxmi_launch_gemm(FluxmiGemmParams& p, int is_fp8, int act_fmt, int cfg, hipStream_t s) {
   FLUXMI_REQUIRE(p.n_groups >= 1 && p.n_groups <= FLUXMI_MAX_GROUPS, "gemm: n_groups=%d out of range", p.n_groups);
   FLUXMI_REQUIRE(fluxmi_gemm_tile_ok(p.N, p.K, is_fp8, cfg), "gemm: shape N=%d K=%d not tileable with cfg %d", p.N, p.K, cfg);

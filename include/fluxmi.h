@@ -113,24 +113,35 @@ int fluxmi_abi_version(void);
 
 /* ---- kernel-selection knobs (ABI 3; attn_split: ABI 4; a_pairs: ABI 5) --------------------------------------------------------------------------------------------
  * The reference has no counterpart (its only switches are the ModelSpec flags of util.py:40-77); these choose between kernels /
- * fusion levels that compute the same results.  They are resolved ONCE: the first call that needs a knob parses the FLUXMI_*
+ * fusion levels.  What each VALUE promises about the model's output -- bit-identical to the defaults, or within a stated rel-L2 of them
+ * (another summation order or rounding grid: split-K, the attention arithmetic knobs, the one-wave-per-row LayerNorm), or excluded (timing
+ * builds) -- is the table of tests/knob_contract.py, which the test suite checks against fluxmi_set_tuning and runs at model level.  They
+ * are resolved ONCE: the first call that needs a knob parses the FLUXMI_*
  * environment variables named below into this struct (csrc/tuning.cpp -- the only getenv site of the library);
  * fluxmi_set_tuning replaces it at run time (A/B probes, tests).  An engine re-captures its step graph when the struct changed
  * since the capture, and fluxmi_engine_create logs it once under FLUXMI_LOG=1. */
 typedef struct fluxmi_tuning {
   int struct_size;       /* sizeof(fluxmi_tuning_t): filled by fluxmi_get_tuning, checked by fluxmi_set_tuning */
-  int gemm_cfg;          /* FLUXMI_GEMM_CFG     -1 = cost model (default), else force this tile config where it applies */
+  int gemm_cfg;          /* FLUXMI_GEMM_CFG     -1 = cost model (default), else force this tile config (2, 13, 15..21; nothing else is
+                                                 accepted) on the launches it runs -- shape, split column, fused K / V^T outputs, operand
+                                                 format and epilogue (17: fp8 x e5m2 gate*y+x or bf16 plain / gate*y+x; 20, 21: fp8 x e5m2
+                                                 gate*y+x) -- every other launch keeps the cost model.  Turns split-K, the 128x128 peel, the
+                                                 persistent kernel and the lower tiles off */
   int gemm_splitk;       /* FLUXMI_GEMM_SPLITK   1: small-M bf16 launches split K over several workgroups per tile */
   int gemm_hybrid;       /* FLUXMI_GEMM_HYBRID   1: peel the thin groups of a grouped launch into a 128x128 launch */
   int gemm_esel;         /* FLUXMI_GEMM_ESEL     1: one kernel instantiation per hot epilogue (0 = run-time switch, A/B) */
   int gemm_persist;      /* FLUXMI_GEMM_PERSIST  1: multi-round fp8 launches on the persistent kernel (tile config 18); 2 = its timing build (probes) */
-  int attn_var;          /* FLUXMI_ATTN_VAR      bit 1: exact instead of deferred running max */
-  int attn_abl;          /* FLUXMI_ATTN_ABL      ablation bits of the 8-wave kernel (probes) */
+  int attn_var;          /* FLUXMI_ATTN_VAR      bit 1: exact instead of deferred running max (other bits); bit 0 selects nothing */
+  int attn_abl;          /* FLUXMI_ATTN_ABL      ablation bits of the 8-wave kernel (probes): bit 1 drops a barrier (timing only, results
+                                                 undefined), bit 3 stores the fp8 output as 4-byte words (the same bytes; also taken for
+                                                 rows that are not 16-byte aligned); bits 0 and 2 select nothing */
   float attn_defer_log2; /* FLUXMI_ATTN_THR      rescale threshold of the deferred running max, log2; [0, 16], default 8 */
   int attn_f16k;         /* FLUXMI_ATTN_F16K     1: the engine stores K as fp16 and runs the folded attention arithmetic */
   int fuse_kv;           /* FLUXMI_FUSE_KV       0 / 1 / 2 (default): K, V^T by the relayout kernel / V^T from the qkv GEMM epilogue / both */
   int qlut;              /* FLUXMI_QLUT          1: table-driven GELU -> fp8 epilogues */
-  int ln_variant;        /* FLUXMI_LN_V          2 = streaming LayerNorm kernel (default), 3 = the same at two workgroups per CU, 1 = one wave per row */
+  int ln_variant;        /* FLUXMI_LN_V          2 = streaming LayerNorm kernel (default; hidden <= 3072), 3 = the same at two workgroups
+                                                 per CU (same bits), 1 = one wave per row (mean / variance in another order; the fused step
+                                                 then keeps plain activation rows, as it does at hidden > 3072) */
   int roctx;             /* FLUXMI_ROCTX         1: roctx ranges around the phases of a denoise call */
   int prefetch;          /* FLUXMI_PREFETCH      1: launches with idle CUs (attention, the 216-tile GEMMs) carry extra workgroups that read the
                                                  weights of the following launches into the memory-side cache (engine, fused mode); 2: a double
@@ -151,7 +162,9 @@ typedef struct fluxmi_tuning {
                                                  rounds: measured not to pay, Flux-dev 1024^2 +3.4 % per step), 0 = one workgroup per task */
   int a_pairs;           /* FLUXMI_A_PAIRS       1 (default): in fused mode the engine keeps its fp8 ACTIVATION buffers (LayerNorm / attention /
                                                  GELU outputs = the A operands of the block linears) in the row-pair layout
-                                                 (fluxmi_gemm_group_t.a_pairs / c8_pairs; even L and Lt only) -- same bits, fewer L2 lines */
+                                                 (fluxmi_gemm_group_t.a_pairs / c8_pairs) -- same bits, fewer L2 lines.  Only where every
+                                                 producer takes it: even L and Lt, the streaming LayerNorm (ln_variant >= 2, hidden <= 3072),
+                                                 3 x hidden % 256 == 0, mlp_hidden % 128 == 0 */
 } fluxmi_tuning_t;
 int fluxmi_get_tuning(fluxmi_tuning_t* out);
 int fluxmi_set_tuning(const fluxmi_tuning_t* in); /* validates every field (non-zero + fluxmi_last_error on a bad value) */
@@ -406,9 +419,10 @@ int fluxmi_engine_get_buffer(fluxmi_engine_t* e, const char* name, void** ptr, l
  * stages 0 LN+modulate of the img rows of x -> "fin", 1 bf16 Linear -> buffer "pred_s" [B, Li, in_channels]; flux_model.py:499-503).
  * mode 1 = fused kernels, 2 = unfused with frozen scales.
  * copy_buffer: device-to-device copy between a named workspace buffer and a caller buffer (to_engine != 0 writes the workspace).  The fp8
- * activation buffers "a8", "attn8", "h8", "cat8" are exchanged as PLAIN rows: while the engine keeps them in row pairs (fused mode,
- * fluxmi_tuning_t.a_pairs, even L and Lt) the copy converts, and offset / bytes must then cover whole pairs of rows.  (The unfused modes
- * stage plain rows into the same buffers: this hook serves mode-1 teacher forcing.) */
+ * activation buffers "a8", "attn8", "h8", "cat8" are exchanged as PLAIN rows.  Inside the engine each one is in the layout of its last
+ * writer -- row pairs after a fused step or stage (fluxmi_tuning_t.a_pairs, even L and Lt), plain rows after an unfused / calibrating one --
+ * and the copy converts from (reading) or into (writing) that layout; offset / bytes must then cover whole pairs of rows.  A buffer written
+ * here is read correctly by a stage that runs in the mode of that last writer (teacher forcing in mode 1 or 2). */
 int fluxmi_engine_run_block(fluxmi_engine_t* e, int kind, int index, int mode, int stage_from, int stage_to, void* stream);
 int fluxmi_engine_copy_buffer(fluxmi_engine_t* e, const char* name, long long offset, void* dev_ptr, long long bytes, int to_engine,
                               void* stream);

@@ -146,6 +146,53 @@ def test_tuning_struct_round_trip_and_validation(monkeypatch):
         _lib.set_tuning(no_such_knob=1)
 
 
+def test_knob_contract_covers_every_tuning_field():
+    """tests/knob_contract.py states, for every value of every fluxmi_tuning_t knob, what it promises about the model's output (bit-identical
+    or within a stated rel-L2 of the defaults, or excluded with a reason); the GPU sweeps run that table.  Here: the table has an entry for
+    every field of the struct, and its ranges are exactly what fluxmi_set_tuning accepts -- a knob added (or widened) later without a
+    contract fails on the CPU."""
+    import knob_contract as kc
+    from fluxmi import _lib
+
+    fields = [f[0] for f in _lib.Tuning._fields_ if f[0] != "struct_size"]
+    assert sorted(kc.KNOBS) == sorted(fields), f"knobs without a contract: {sorted(set(fields) - set(kc.KNOBS))}; stale entries: {sorted(set(kc.KNOBS) - set(fields))}"
+    t = _lib.get_tuning()
+    for name, k in kc.KNOBS.items():
+        ctype = dict(_lib.Tuning._fields_)[name]
+        default = getattr(t, name)
+        assert default == k.default or (ctype is C.c_float and abs(default - k.default) < 1e-6), f"{name}: library default {default} vs table {k.default}"
+        assert k.default in k.values and kc.contract(name, k.default, "fp8").kind == "bit", f"{name}: the default itself must be listed, BIT"
+        for v, c in k.values.items():
+            for flow in ("fp8", "bf16"):
+                cc = kc.contract(name, v, flow)
+                assert cc.kind in ("bit", "tol", "excluded") and (cc.kind != "excluded" or cc.reason), f"{name}={v}: contract {cc}"
+                assert cc.kind != "tol" or 0.0 < cc.tol <= kc.FP8_TOL, f"{name}={v}: tolerance {cc.tol}"
+                assert set(cc.knobs_with) <= set(fields) and name not in cc.knobs_with, f"{name}={v}: companion knobs {cc.knobs_with}"
+            _lib.set_tuning(**{name: v})  # every listed value is accepted (raises otherwise)
+        _lib.set_tuning(**{name: k.default})
+        accepts = lambda v: _lib.lib.fluxmi_set_tuning(C.byref(_with(name, v))) == 0
+        if ctype is C.c_float:
+            assert min(k.values) == k.lo and max(k.values) == k.hi, f"{name}: the values under test must include both ends of [{k.lo}, {k.hi}]"
+            assert accepts(k.lo) and accepts(k.hi) and not accepts(k.lo - 0.01) and not accepts(k.hi + 0.01), f"{name}: accepted range != [{k.lo}, {k.hi}]"
+        elif name == "gemm_cfg":
+            # a set, not a range: -1 and every tile config the launchers know, nothing else
+            got = {v for v in range(-3, 260) if accepts(v)}
+            assert got == set(k.values), f"gemm_cfg: library accepts {sorted(got)}, table lists {sorted(k.values)}"
+        else:
+            assert set(k.values) == set(range(k.lo, k.hi + 1)), f"{name}: every value in [{k.lo}, {k.hi}] needs a contract"
+            assert accepts(k.lo) and accepts(k.hi) and not accepts(k.lo - 1) and not accepts(k.hi + 1), f"{name}: accepted range != [{k.lo}, {k.hi}]"
+        _lib.set_tuning(**{name: k.default})
+    final = _lib.get_tuning()
+    assert all(getattr(final, f) == getattr(t, f) for f in fields)
+
+
+def _with(name, v):
+    from fluxmi import _lib
+
+    t = _lib.get_tuning()
+    setattr(t, name, v)
+    return t
+
 def test_struct_layouts_match_the_header():
     from fluxmi import _lib
 

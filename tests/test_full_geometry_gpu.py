@@ -28,6 +28,7 @@ from safetensors.torch import load_file
 
 import flux_oracle as fo
 import full_geometry as fg
+import knob_contract as kc
 from parity_util import assert_close_mag, f8_ulp_diff, round_fp64_to_bf16, ulp_diff
 
 pytestmark = pytest.mark.gpu
@@ -153,7 +154,16 @@ class Eng:
         torch.cuda.synchronize()
         return t.cpu()
 
-    def run(self, kind, idx, s0, s1, mode=1):
+    mode = 1  # the mode run() uses when none is given
+
+    def in_mode(self, mode):
+        """the same handle, running its blocks in `mode` (1 fused, 2 unfused-frozen) unless told otherwise"""
+        e = Eng(self.m)
+        e.mode = mode
+        return e
+
+    def run(self, kind, idx, s0, s1, mode=None):
+        mode = self.mode if mode is None else mode
         self.lib.call("fluxmi_engine_run_block", self.m._engine, kind, idx, mode, s0, s1, self.ops._stream())
 
 
@@ -247,8 +257,49 @@ def end_to_end(ck, name, model, inp, o1, dev, tol):
     return e
 
 
-def teacher_forced_double(ck, E, orc, tr, i, H, Lt, L, prev_img, prev_txt):
+# cases whose frozen forward is re-run under every knob value of tests/knob_contract.py: 1024^2 (fused K / V^T in the persistent kernel, tile
+# configs 18 and 20), 768^2 (configs 17 and 21, the balanced attention grid of a thin last round), Flux-schnell bf16 at 1024^2 (bf16 GEMMs)
+KNOB_SWEEP_CASES = ("c2_2p2_L4608", "c3_2p2_L2816", "c1_schnell_bf16_1p1_L4352")
+# the teacher-forced stage checks run in mode 2 (unfused, frozen scales) as well: plain-row fp8 buffers read back through copy_buffer
+MODE2_STAGE_CASES = ("tiny_2p2_L96", "c2_2p2_L4608")
+
+
+def knob_sweep_forward(ck, fwd, o1, flow, oracle_tol):
+    """one frozen forward per knob value (tests/knob_contract.py, `flow` = "fp8" / "bf16") against the default forward under the value's
+    contract (bit-identical, or within its rel-L2), and against the oracle's frozen prediction at the case's own gate"""
+    from fluxmi import _lib
+
+    base = fwd()
+    torch.cuda.synchronize()
+    bits = lambda a, b: torch.equal(a.view(torch.int16), b.view(torch.int16))
+    for knob, value, c in kc.sweep(flow):
+        tag = f"knob {knob}={value}" + (f" (with {c.knobs_with})" if c.with_ else "")
+        try:
+            with _lib.tuning(**kc.knobs_of(knob, value, c)):
+                got = fwd()
+                torch.cuda.synchronize()
+        except RuntimeError as ex:
+            ck.rows.append(f"  BAD {tag:58s} refused: {str(ex).splitlines()[0][:160]}")
+            ck.fail.append(tag)
+            continue
+        same = bits(got, base)
+        e, eo = rel_l2(got, base), rel_l2(got, o1)
+        ok = bool(torch.isfinite(got).all()) and eo <= oracle_tol and (same if c.kind == "bit" else e <= c.tol)
+        what = ("BIT held" if same else f"BIT broken: rel-L2 {e:.3e}") if c.kind == "bit" else f"rel-L2 {e:.3e} vs defaults (<= {c.tol:g})"
+        ck.rows.append(f"  {'ok ' if ok else 'BAD'} {tag:58s} {what}; vs oracle {eo:.3e} (<= {oracle_tol:g})")
+        if not ok:
+            ck.fail.append(tag)
+    # back at the defaults
+    same = bits(fwd(), base)
+    ck.rows.append(f"  {'ok ' if same else 'BAD'} {'knob sweep: defaults again == the first default forward':58s}")
+    if not same:
+        ck.fail.append("defaults after the knob sweep")
+
+
+def teacher_forced_double(ck, E, orc, tr, i, H, Lt, L, prev_img, prev_txt, mode=1):
     pre = f"double_blocks.{i}"
+    if mode != 1:
+        E = E.in_mode(mode)
     cat = lambda a, b: torch.cat((tr[a].reshape(Lt, -1), tr[b].reshape(L - Lt, -1)), 0)
     x_in = torch.cat((prev_txt[0], prev_img[0]), 0).cuda()                    # [L, H] txt rows first
     mods = torch.cat((tr[pre + ".img_mod.lin.out"][0], tr[pre + ".txt_mod.lin.out"][0])).cuda()
@@ -309,9 +360,11 @@ class _q2:
         self.input_scale_reciprocal, self.scale_reciprocal = st.input_scale_reciprocal, st.scale_reciprocal
 
 
-def teacher_forced_single(ck, E, orc, tr, i, depth, H, L, x_prev):
+def teacher_forced_single(ck, E, orc, tr, i, depth, H, L, x_prev, mode=1):
     pre = f"single_blocks.{i}"
     Hm, HC = 4 * H, 5 * H
+    if mode != 1:
+        E = E.in_mode(mode)
     x_in = x_prev[0].cuda()
     E.put("mod", tr[pre + ".modulation.lin.out"][0].cuda(), offset=(depth * 12 * H + i * 3 * H) * 2)
     E.put("x", x_in); E.run(1, i, 0, 0)
@@ -323,7 +376,7 @@ def teacher_forced_single(ck, E, orc, tr, i, depth, H, L, x_prev):
     with _tuning(fuse_kv=1):  # k columns through the qkv buffer for the GEMM check (see the double block)
         E.run(1, i, 1, 1)
     lin1 = tr[pre + ".linear1.out"]
-    qkv = E.get("qkv", (L, 3 * H), torch.bfloat16)
+    qkv = E.get("qkv", (L, 3 * H), torch.bfloat16) if E.mode == 1 else E.get("lin1", (L, 3 * H + Hm), torch.bfloat16)[:, :3 * H]
     ck.bf16(f"{pre} linear1 GEMM (q,k columns)", qkv[:, :2 * H], lin1[:, :2 * H], 0.980, 0.997, 2e-3)
     rows = torch.arange(0, L, max(1, L // 48))[:48]
     sampled_fp64_gemm(ck, f"{pre} linear1 GEMM", qkv[rows][:, :2 * H], x8, _q2(orc.lin[pre + ".linear1"], 2 * H), rows)
@@ -389,6 +442,19 @@ def test_teacher_forced_blocks_at_real_geometry(dev, name):
     for i in range(p.depth_single_blocks):
         x = teacher_forced_single(ck, E, orc, tr, i, p.depth, H, L, x)
     teacher_forced_last_layer(ck, E, orc, tr, p, H, Lt, L, x, o1)
+    if name in MODE2_STAGE_CASES:  # the same stage checks on the unfused-frozen path (plain-row fp8 buffers)
+        ck2 = Checks(name)
+        img, txt = tr["img_in.out"], tr["txt_in.out"]
+        for i in range(p.depth):
+            img, txt = teacher_forced_double(ck2, E, orc, tr, i, H, Lt, L, img, txt, mode=2)
+        x = torch.cat((txt, img), 1)
+        for i in range(p.depth_single_blocks):
+            x = teacher_forced_single(ck2, E, orc, tr, i, p.depth, H, L, x, mode=2)
+        ck.rows += ["  -- the same stage checks in mode 2 (unfused, frozen scales):"] + ck2.rows
+        ck.fail += [f"mode 2: {f}" for f in ck2.fail]
+    if name in KNOB_SWEEP_CASES:
+        args = tuple(a.to(dev) for a in fg.call_args(d, fg.T_FROZEN))
+        knob_sweep_forward(ck, lambda: model(*args, mode=1), o1, "fp8", 7e-2)
     ck.done()
 
 
@@ -565,6 +631,8 @@ def test_schnell_bf16_flow_at_full_depth(dev, name):
     ck.rows.append(f"  {'ok ' if same else 'BAD'} 4-step bf16 denoise loop: graph replay == eager, bit for bit")
     if not same:
         ck.fail.append("bf16 graph vs eager")
+    if name in KNOB_SWEEP_CASES:
+        knob_sweep_forward(ck, lambda: model(*args[:6], None), o1, "bf16", 3.5e-2)
     ck.done()
     if p.depth >= 19:
         fg.drop_sd_cache()  # 24 GB of synthetic checkpoint shared with test_full_depth_19_38

@@ -833,7 +833,7 @@ def test_gemv(ops, dev, B):
 
 
 # ------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("variant", ["stream", "row_per_wave"])
+@pytest.mark.parametrize("variant", ["stream", "stream_2wg", "row_per_wave"])
 @pytest.mark.parametrize("L,Lt", [(40, 12), (42, 13), (1300, 500)])
 @pytest.mark.parametrize("H", [256, 3072])
 def test_ln_modulate(ops, dev, H, L, Lt, variant):
@@ -841,10 +841,11 @@ def test_ln_modulate(ops, dev, H, L, Lt, variant):
     (42, 13): a workgroup's rows straddle the txt|img split and the batch boundary (the rows that do not belong to the
     workgroup's LDS-staged table take their modulation vectors from global memory); (1300, 500): 256 workgroups with 10-11 rows each,
     i.e. the streaming kernel's prefetch loop runs (every wave owns two rows, some a single one).
-    Both kernels: the streaming one (default, fluxmi_tuning_t.ln_variant = 2) and the one-wave-per-row one (1)."""
+    Both kernels: the streaming one (default, fluxmi_tuning_t.ln_variant = 2; 3 = its grid at two workgroups per CU) and the
+    one-wave-per-row one (1)."""
     from fluxmi import _lib
 
-    with _lib.tuning(ln_variant=2 if variant == "stream" else 1):
+    with _lib.tuning(ln_variant={"stream": 2, "stream_2wg": 3, "row_per_wave": 1}[variant]):
         _ln_modulate_body(ops, dev, H, L, Lt)
 
 

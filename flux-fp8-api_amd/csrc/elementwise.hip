@@ -519,6 +519,23 @@ __global__ void __launch_bounds__(256) euler_kernel(u16* __restrict__ img, const
     *(uint4*)(img + i) = pack8(fi);
   }
 }
+// The Euler step of an image stream LONGER than the prediction (FLUX.1 Kontext: the reference-image rows ride behind the noisy rows of each
+// sample and are never stepped): rows [0, pred_rows) of every sample of img [B, img_rows, C] += bf16(dt * pred), pred [B, pred_rows, C].
+// Same arithmetic as euler_kernel, 16-byte accesses (C % 8 == 0: a vector never straddles a row); the reference rows are not touched.
+__global__ void __launch_bounds__(256) euler_rows_kernel(u16* __restrict__ img, const u16* __restrict__ pred, const float* __restrict__ dts,
+                                                         const int* __restrict__ step, long long n, long long pred_bstride, long long img_bstride) {
+  const float dt = dts[*step];
+  for (long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 8; i < n; i += (long long)gridDim.x * blockDim.x * 8) {
+    const long long b = i / pred_bstride;
+    u16* x = img + b * img_bstride + (i - b * pred_bstride);
+    float fi[8], fp[8];
+    unpack8(*(const uint4*)x, fi);
+    unpack8(*(const uint4*)(pred + i), fp);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) fi[j] += rbf(dt * fp[j]);
+    *(uint4*)x = pack8(fi);
+  }
+}
 // per-step scalars kept on the device so that one captured graph serves every step:
 //   t_vec[b] = bf16(ts[*step]),  then ++*step happens in advance_step_kernel at the end of the step.
 __global__ void set_timestep_kernel(u16* __restrict__ t_vec, const float* __restrict__ ts, const int* __restrict__ step, int B) {
@@ -814,6 +831,17 @@ int fluxmi_k_euler(void* img, const void* pred, const float* dts, const int* ste
   FLUXMI_REQUIRE(n % 8 == 0, "euler: n must be a multiple of 8");
   if (n == 0) return 0;
   hipLaunchKernelGGL(euler_kernel, dim3(grid_for(n / 8)), dim3(256), 0, s, (u16*)img, (const u16*)pred, dts, step, n);
+  FLUXMI_LAUNCH_CHECK();
+  return 0;
+}
+int fluxmi_k_euler_rows(void* img, const void* pred, const float* dts, const int* step, int B, long long img_rows, long long pred_rows, int C,
+                        hipStream_t s) {
+  FLUXMI_REQUIRE(step && B >= 0 && C > 0 && C % 8 == 0 && pred_rows >= 0 && pred_rows <= img_rows,
+                 "euler_rows: bad shape B=%d img_rows=%lld pred_rows=%lld C=%d (C %% 8 == 0, pred_rows <= img_rows)", B, img_rows, pred_rows, C);
+  const long long n = (long long)B * pred_rows * C;
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(euler_rows_kernel, dim3(grid_for(n / 8)), dim3(256), 0, s, (u16*)img, (const u16*)pred, dts, step, n, pred_rows * C,
+                     img_rows * C);
   FLUXMI_LAUNCH_CHECK();
   return 0;
 }

@@ -10,7 +10,9 @@
 // Because every fused kernel re-applies the reference's bf16 rounding points, both modes produce the same bits
 // for the same scales (tests/test_engine.py checks this on the GPU).
 //
-// HBM layout (per request shape B, Li, Lt; L = Lt + Li, txt rows first so torch.cat is free):
+// HBM layout (per request shape B, Li, Lt; L = Lt + Li, txt rows first so torch.cat is free).  Li is the whole IMAGE STREAM: with a FLUX.1
+// Kontext reference (fluxmi_engine_prepare_cond) the Lc reference rows follow the Lpred noisy rows of each sample (Li = Lpred + Lc); every
+// block runs over all of them, and only the final layer and the Euler update are restricted to the leading Lpred rows:
 //   x      bf16 [B, L, H]        residual stream (img = rows Lt.., txt = rows ..Lt)
 //   a8     fp8  [B, L, H]        quantised LN+modulate output (GEMM A operand)
 //   qkv    bf16 [B, L, 3H]       qkv GEMM output
@@ -43,6 +45,7 @@ struct fluxmi_engine {
   std::vector<const void*> norm;
   int i_img_in, i_time_in, i_vec_in, i_guid_in, i_txt_in, i_double0, i_single0, i_final_mod, i_final_lin;
   int B = 0, Li = 0, Lt = 0, L = 0, Lp = 0;
+  int Lpred = 0;  // predicted (and stepped) rows per sample: the leading rows of the image stream; Li - Lpred = Lc reference rows (Kontext)
   long long mod_cols = 0;
   char* ws = nullptr;
   size_t ws_bytes = 0;
@@ -811,21 +814,22 @@ int single_block(E* e, const Ctx& c, int i, int mode, int trial, int s0, int s1,
   return 0;
 }
 
-// LastLayer.forward (flux_model.py:499-503) on the img rows of x: stage 0 = (1 + scale) * LayerNorm(x) + shift -> fin (bf16; the adaLN
+// LastLayer.forward (flux_model.py:499-503) on the predicted img rows of x (the leading Lpred of the Li image rows; Kontext's reference rows
+// are not predicted): stage 0 = (1 + scale) * LayerNorm(x) + shift -> fin (bf16; the adaLN
 // vectors are the last 2H entries of `mod`, shift first), stage 1 = the bf16 Linear hidden -> patch channels -> pred.  Never fp8
 // (float8_quantize.py:476).
 int final_layer(E* e, u16* pred, int s0, int s1, hipStream_t s) {
-  const int H = e->d.hidden, B = e->B, L = e->L, Lt = e->Lt, Li = e->Li;
+  const int H = e->d.hidden, B = e->B, L = e->L, Lt = e->Lt, Lo = e->Lpred;
   const long long XB = (long long)L * H, MC = e->mod_cols;
   u16 *x = buf<u16>(e, "x"), *mod = buf<u16>(e, "mod"), *fin = buf<u16>(e, "fin");
   const u16* mf = mod + (long long)e->d.depth * 12 * H + (long long)e->d.depth_single * 3 * H;  // shift | scale
   if (s0 <= 0 && s1 >= 0)
-    FLUXMI_TRY(fluxmi_k_ln_modulate(x + (long long)Lt * H, H, XB, fin, H, (long long)Li * H, mf, mf + H, mf, mf + H, MC, nullptr, nullptr, B,
-                                    Li, Li, H, 0, 0, s));
+    FLUXMI_TRY(fluxmi_k_ln_modulate(x + (long long)Lt * H, H, XB, fin, H, (long long)Lo * H, mf, mf + H, mf, mf + H, MC, nullptr, nullptr, B,
+                                    Lo, Lo, H, 0, 0, s));
   if (s0 <= 1 && s1 >= 1) {
     const fluxmi_linear_t& l = e->lin[e->i_final_lin];
     std::vector<FluxmiGemmGroup> gs;
-    gs.push_back(mk_group(l, fin, H, pred, l.N, B * Li));
+    gs.push_back(mk_group(l, fin, H, pred, l.N, B * Lo));
     FLUXMI_TRY(run_gemm_fixed_cfg(gs, l.N, H, 0, 0, FLUXMI_EPI_BF16, s));
   }
   return 0;
@@ -1051,23 +1055,31 @@ int fluxmi_engine_set_tables(fluxmi_engine_t* e, const float* freqs128, const fl
 }
 
 int fluxmi_engine_prepare(fluxmi_engine_t* e, int B, int Li, int Lt, const void* img_ids, const void* txt_ids, void* stream) {
+  return fluxmi_engine_prepare_cond(e, B, Li, 0, Lt, img_ids, txt_ids, stream);
+}
+
+// Li_pred noisy rows + Lc reference rows per sample (FLUX.1 Kontext): the engine's image stream is Li = Li_pred + Lc rows long.  The split is
+// part of the workspace key: the same (B, Li, Lt) with another split re-allocates, which drops the captured step graph (its final layer and
+// Euler update are sized by the split).
+int fluxmi_engine_prepare_cond(fluxmi_engine_t* e, int B, int Li_pred, int Lc, int Lt, const void* img_ids, const void* txt_ids, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  FLUXMI_REQUIRE(e && B >= 1 && B <= FLUXMI_ENGINE_MAX_BATCH && Li >= 1 && Lt >= 0, "engine_prepare: bad shape B=%d Li=%d Lt=%d (B must be 1..%d)", B, Li,
-                 Lt, FLUXMI_ENGINE_MAX_BATCH);
+  FLUXMI_REQUIRE(e && B >= 1 && B <= FLUXMI_ENGINE_MAX_BATCH && Li_pred >= 1 && Lc >= 0 && Lt >= 0,
+                 "engine_prepare: bad shape B=%d Li=%d Lc=%d Lt=%d (B must be 1..%d)", B, Li_pred, Lc, Lt, FLUXMI_ENGINE_MAX_BATCH);
   FLUXMI_REQUIRE(img_ids && (Lt == 0 || txt_ids), "engine_prepare: NULL ids");
+  const int Li = Li_pred + Lc;
   const int H = e->d.hidden, Hm = e->d.mlp_hidden, L = Li + Lt, Lp = ((L + 63) / 64) * 64;
   if (e->pairs_skipped) e->pairs_dirty = true;  // the row-pair copies did not fit last time: try again with this request
-  if (B != e->B || Li != e->Li || Lt != e->Lt || !e->ws) {
+  if (B != e->B || Li != e->Li || Li_pred != e->Lpred || Lt != e->Lt || !e->ws) {
     FLUXMI_CHECK_HIP(hipStreamSynchronize(s));
     free_ws(e);
-    e->B = B; e->Li = Li; e->Lt = Lt; e->L = L; e->Lp = Lp;
+    e->B = B; e->Li = Li; e->Lpred = Li_pred; e->Lt = Lt; e->L = L; e->Lp = Lp;
     struct Item { const char* name; size_t bytes; };
     const size_t BL = (size_t)B * L;
     const size_t in8 = std::max((size_t)B * Li * e->d.in_channels, (size_t)B * Lt * e->d.ctx_in);
     std::vector<Item> items = {
         {"x", BL * H * 2}, {"a8", BL * H}, {"attn8", BL * H}, {"qkv", BL * 3 * H * 2}, {"Q", BL * H * 2}, {"K", BL * H * 2},
         {"VT", (size_t)B * H * Lp * 2}, {"h8", BL * Hm}, {"cat8", BL * (H + Hm)}, {"pe", BL * 64 * 2 * 2},
-        {"mod", (size_t)B * e->mod_cols * 2}, {"fin", (size_t)B * Li * H * 2},
+        {"mod", (size_t)B * e->mod_cols * 2}, {"fin", (size_t)B * Li_pred * H * 2},
         // unfused-path temporaries
         {"abf", BL * H * 2}, {"attnbf", BL * H * 2}, {"hbf", BL * Hm * 2}, {"catbf", BL * (H + Hm) * 2}, {"lin1", BL * (3 * H + Hm) * 2},
         {"in8", in8},
@@ -1079,7 +1091,7 @@ int fluxmi_engine_prepare(fluxmi_engine_t* e, int B, int Li, int Lt, const void*
         {"mods_a8", (size_t)FLUXMI_MAX_GROUPS * (((size_t)B * std::max(H, 4096) + 255) & ~(size_t)255)},
         // static request buffers (make the captured graph independent of caller pointers)
         {"img_s", (size_t)B * Li * e->d.in_channels * 2}, {"txt_s", (size_t)B * Lt * e->d.ctx_in * 2}, {"y_s", (size_t)B * e->d.vec_in * 2},
-        {"pred_s", (size_t)B * Li * e->d.in_channels * 2}, {"txt_emb", (size_t)B * Lt * H * 2},
+        {"pred_s", (size_t)B * Li_pred * e->d.in_channels * 2}, {"txt_emb", (size_t)B * Lt * H * 2},
         // split-K partial tiles of the bf16 small-M launches (api.cpp: bf16 operands, >= 192 K-steps): owned by the engine, because its step
         // graph is captured on a private stream and replayed on the caller's -- a scratch keyed by stream would be nobody's
         {"splitk", needs_splitk(e) ? FLUXMI_SPLITK_WS_BYTES : 256},
@@ -1147,6 +1159,11 @@ int fluxmi_engine_denoise(fluxmi_engine_t* e, void* img, const void* txt, const 
   SplitkScope splitk(e);
   FLUXMI_TRY(ensure_pairs(e, s));
   const int B = e->B, Li = e->Li, Lt = e->Lt, C = e->d.in_channels;
+  // the Euler update: the whole stream, or (Kontext) the leading Lpred rows of each sample -- the reference rows never move
+  auto euler = [&](hipStream_t st) -> int {
+    if (e->Lpred == Li) return fluxmi_k_euler(buf<u16>(e, "img_s"), buf<u16>(e, "pred_s"), e->d_dts, e->d_step, (long long)B * Li * C, st);
+    return fluxmi_k_euler_rows(buf<u16>(e, "img_s"), buf<u16>(e, "pred_s"), e->d_dts, e->d_step, B, Li, e->Lpred, C, st);
+  };
   // any bf16 block linear -> the fused path is unavailable, run unfused-frozen (mode 2)
   bool all_f8 = true;
   for (int i = e->i_double0; i < e->i_final_mod; ++i) {
@@ -1187,7 +1204,7 @@ int fluxmi_engine_denoise(fluxmi_engine_t* e, void* img, const void* txt, const 
       FLUXMI_TRY(fluxmi_k_set_timestep(tvec, e->d_ts, e->d_step, B, s));
       e->qlut_valid = false;
       FLUXMI_TRY(forward_impl(e, img_s, txt_s, y_s, tvec, g_arg, pred_s, 0, trial, false, s));
-      FLUXMI_TRY(fluxmi_k_euler(img_s, pred_s, e->d_dts, e->d_step, n_img, s));
+      FLUXMI_TRY(euler(s));
       FLUXMI_TRY(fluxmi_k_advance_step(e->d_step, s));
       ++trial; ++step;
     }
@@ -1206,7 +1223,7 @@ int fluxmi_engine_denoise(fluxmi_engine_t* e, void* img, const void* txt, const 
       int rc = forward_impl(e, img_s, txt_s, y_s, tvec, g_arg, pred_s, mode, 0, mode == 1, st);
       e->mods_table = false;
       FLUXMI_TRY(rc);
-      FLUXMI_TRY(fluxmi_k_euler(img_s, pred_s, e->d_dts, e->d_step, n_img, st));
+      FLUXMI_TRY(euler(st));
       return fluxmi_k_advance_step(e->d_step, st);
     };
     // ev_t0 .. ev_t1 (fluxmi_engine_last_timing) brackets frozen STEPS only: recorded behind the first window's modulation table, the eager

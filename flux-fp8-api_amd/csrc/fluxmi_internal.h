@@ -155,6 +155,9 @@ int fluxmi_k_fill_bf16(void* dst, float v, int n, hipStream_t s);
 int fluxmi_k_timestep_embedding(const void* t, const float* freqs, void* out, int B, int half, float time_factor, hipStream_t s);
 int fluxmi_k_rope_table(const void* ids, const float* omega, const int* axis, void* pe, long long rows, int n_axes, int pairs, hipStream_t s);
 int fluxmi_k_euler(void* img, const void* pred, const float* dts, const int* step, long long n, hipStream_t s);
+// rows [0, pred_rows) of each sample of img [B, img_rows, C] += bf16(dts[*step] * pred [B, pred_rows, C]) (FLUX.1 Kontext: the reference rows stay)
+int fluxmi_k_euler_rows(void* img, const void* pred, const float* dts, const int* step, int B, long long img_rows, long long pred_rows, int C,
+                        hipStream_t s);
 int fluxmi_k_set_timestep(void* t_vec, const float* ts, const int* step, int B, hipStream_t s);
 int fluxmi_k_advance_step(int* step, hipStream_t s);
 int fluxmi_k_clock_sample(unsigned long long* out2, hipStream_t s);

@@ -30,6 +30,28 @@ from util import ModelSpec, ModelVersion, engine_flow_dtype, into_device, into_d
 
 MAX_RAND = 2**32 - 1
 
+# FLUX.1 Kontext's preferred reference resolutions, (width, height) (BFL flux, src/flux/sampling.py)
+KONTEXT_PREFERRED_RESOLUTIONS = [
+    (672, 1568), (688, 1504), (720, 1456), (752, 1392), (800, 1328), (832, 1248), (880, 1184), (944, 1104), (1024, 1024),
+    (1104, 944), (1184, 880), (1248, 832), (1328, 800), (1392, 752), (1456, 720), (1504, 688), (1568, 672),
+]
+
+
+def kontext_reference_size(width: int, height: int):
+    """-> (w, h, w_l, h_l): the preferred Kontext resolution closest in aspect ratio to a `width` x `height` image, and its latent size
+    (w_l = 2 * int(w / 16), h_l = 2 * int(h / 16)).  Ties go to the smaller (width, height) pair, as min() over tuples does."""
+    a = width / height
+    _, w, h = min((abs(a - w / h), w, h) for (w, h) in KONTEXT_PREFERRED_RESOLUTIONS)
+    return w, h, 2 * int(w / 16), 2 * int(h / 16)
+
+
+def kontext_reference_ids(bs: int, h_l: int, w_l: int, device=None, dtype=torch.bfloat16) -> torch.Tensor:
+    """Position ids of the reference tokens, [bs, (h_l/2) * (w_l/2), 3]: make_img_ids over the (h_l/2) x (w_l/2) grid (axis 1 the row, axis 2
+    the column) with axis 0 set to 1, which tells the model these tokens are the reference, not the image being generated."""
+    ids = FluxPipeline.make_img_ids(bs, h_l // 2, w_l // 2, device, dtype)
+    ids[..., 0] = 1
+    return ids
+
 
 class FluxPipeline:
     def __init__(self, name: str, offload: bool = False, clip=None, t5=None, model=None, ae=None,
@@ -159,6 +181,48 @@ class FluxPipeline:
             x = t * x + (1.0 - t) * init_image
         return x, timesteps
 
+    # ---- FLUX.1 Kontext reference image ------------------------------------------------------------------------------------------------
+    @torch.inference_mode()
+    def prepare_kontext_reference(self, reference_image, num_images: int = 1, generator: torch.Generator = None):
+        """The reference image of an instruction edit (FLUX.1 Kontext [dev]) -> (img_cond_seq [num_images, Lc, 64], img_cond_seq_ids
+        [num_images, Lc, 3]) in the flow dtype on the flow device.  The semantics of BFL's prepare_kontext / denoise (src/flux/sampling.py),
+        kept here in one place:
+          1. preprocessing: a = W / H of the input image picks (w, h) = min((|a - w/h|, w, h)) over KONTEXT_PREFERRED_RESOLUTIONS; the
+             latent size is w_l = 2 * int(w / 16), h_l = 2 * int(h / 16); the RGB image is resized to (8 w_l, 8 h_l) with PIL LANCZOS, scaled
+             to [-1, 1], VAE-encoded (the native encoder img2img uses) and packed 2x2 like the noise: Lc = (h_l / 2) * (w_l / 2);
+          2. position ids: make_img_ids over the (h_l / 2) x (w_l / 2) grid with axis 0 set to 1;
+          3. forward: the reference tokens are appended to the image stream of every step; only the noisy tokens are predicted and stepped
+             (img = img + (t_prev - t_curr) * pred[:, :Li]); the reference tokens never change;
+          4. schedule: get_schedule(num_steps, Li) counts the noisy tokens only (generate() does);
+          5. the output size is the requested width / height, independent of the reference's snapped size.
+        The encoder's Gaussian sample is drawn from `generator` ([1, z_channels, h_l, w_l], one draw shared by the num_images copies);
+        generate() passes the request's seeded generator AFTER the noise has been drawn from it, so one seed gives one result.
+        `reference_image`: anything load_init_image_if_needed takes (path, base64 / data-URL, PIL image, HWC uint8 array or tensor)."""
+        from PIL import Image
+
+        if self.ae is None:
+            raise RuntimeError("fluxmi: a Kontext reference image needs an autoencoder (config.ae_path) -- none is attached")
+        ref = self.load_init_image_if_needed(reference_image)
+        if isinstance(ref, torch.Tensor):
+            ref = ref.detach().cpu()
+            if ref.dtype != torch.uint8:
+                raise TypeError(f"fluxmi: a reference image tensor must be uint8 HWC, got {ref.dtype}")
+            ref = ref.numpy()
+        pil = Image.fromarray(np.asarray(ref)).convert("RGB")
+        width, height = pil.size
+        _, _, w_l, h_l = kontext_reference_size(width, height)
+        pil = pil.resize((8 * w_l, 8 * h_l), Image.LANCZOS)
+        x = torch.from_numpy(np.array(pil)).permute(2, 0, 1).float().div(127.5).sub(1.0)[None]
+        x = x.to(self.device_ae, dtype=self.ae_dtype)
+        f = 1 << (self.ae.encoder.num_resolutions - 1)  # the encoder's downsampling (8 for every Flux autoencoder)
+        z_ch = self.ae.encoder.conv_out.out_channels // 2
+        gen_dev = generator.device if generator is not None else self.device_ae
+        eps = torch.randn(1, z_ch, 8 * h_l // f, 8 * w_l // f, generator=generator, device=gen_dev, dtype=torch.float32)
+        z = self.ae.encode(x, noise=eps.to(self.device_ae))
+        cond = self.pack(z.to(device=self.device_flux, dtype=self.dtype)).repeat(num_images, 1, 1)
+        ids = kontext_reference_ids(num_images, h_l, w_l, self.device_flux, self.dtype)
+        return cond.contiguous(), ids
+
     # ---- packing / ids (reference flux_pipeline.py:267-292, 440-448) ----------------------------------------------
     @staticmethod
     def pack(img: torch.Tensor) -> torch.Tensor:
@@ -269,7 +333,9 @@ class FluxPipeline:
     def generate(self, prompt, width: int = 720, height: int = 1024, num_steps: int = 24, guidance: float = 3.5,
                  seed: int | None = None, init_image=None, strength: float = 1.0, silent: bool = False, num_images: int = 1,
                  return_seed: bool = False, jpeg_quality: int = 99, output_type: str = "jpeg", noise: Optional[torch.Tensor] = None,
-                 use_graph: bool = True):
+                 use_graph: bool = True, reference_image=None):
+        """`reference_image` (FLUX.1 Kontext [dev] instruction editing): an image the prompt describes an edit of, in any form `init_image`
+        takes; see prepare_kontext_reference.  Composes with `init_image` / `strength` unchanged."""
         num_steps = 4 if self.name == "flux-schnell" else num_steps
         init_image = self.load_init_image_if_needed(init_image) if init_image is not None else None
         height, width = 16 * (height // 16), 16 * (width // 16)
@@ -290,16 +356,26 @@ class FluxPipeline:
                                                   generator=generator, num_images=num_images, noise=noise)
         img, img_ids, vec, txt, txt_ids = map(lambda x: x.contiguous(), self.prepare(noise, prompt))
         num_images = img.shape[0]  # a list prompt with num_images == 1 sizes the batch (prepare)
+        cond = {}
+        if reference_image is not None:
+            # drawn from the request's generator after the noise (the order is part of what a seed reproduces)
+            c_seq, c_ids = self.prepare_kontext_reference(reference_image, num_images=num_images, generator=generator)
+            cond = dict(img_cond_seq=c_seq, img_cond_seq_ids=c_ids)
         if world > 1:
-            txt, vec, img = fdist.broadcast_request(txt, vec, img, src=0)
+            if cond:
+                # every rank steps rank 0's reference latents (the VAE sample differs between ranks' generators on other devices)
+                txt, vec, img, cond["img_cond_seq"] = fdist.broadcast_request(txt, vec, img, src=0, extra=cond["img_cond_seq"])
+            else:
+                txt, vec, img = fdist.broadcast_request(txt, vec, img, src=0)
             lo, hi = fdist.shard_bounds(img.shape[0], rank, world)
             img, img_ids, vec, txt, txt_ids = (t[lo:hi].contiguous() for t in (img, img_ids, vec, txt, txt_ids))
+            cond = {k: v[lo:hi].contiguous() for k, v in cond.items()}
         if img.shape[0] == 0:
             # more ranks than images (frozen scales only, see above): this rank has nothing to denoise but still takes part in the gather
             # below (an exception or an early return here would leave the other ranks blocked in the collective)
             latents = img.new_empty((0,) + tuple(img.shape[1:]))
         else:
-            latents = self.model.denoise(img, img_ids, txt, txt_ids, vec, timesteps, guidance=guidance, use_graph=use_graph)
+            latents = self.model.denoise(img, img_ids, txt, txt_ids, vec, timesteps, guidance=guidance, use_graph=use_graph, **cond)
         if world > 1:
             latents = fdist.gather_latents(latents, num_images, dst=0)
             if latents is None:  # only the gather rank decodes / returns the images

@@ -104,6 +104,7 @@ _SIGS = {
     "fluxmi_engine_rebind": ([vp, C.POINTER(Linear), i32], i32),
     "fluxmi_engine_set_tables": ([vp, C.POINTER(f32), C.POINTER(f32), C.POINTER(i32)], i32),
     "fluxmi_engine_prepare": ([vp, i32, i32, i32, vp, vp, vp], i32),
+    "fluxmi_engine_prepare_cond": ([vp, i32, i32, i32, i32, vp, vp, vp], i32),
     "fluxmi_engine_forward": ([vp, vp, vp, vp, vp, vp, vp, i32, i32, vp], i32),
     "fluxmi_engine_denoise": ([vp, vp, vp, vp, f32, C.POINTER(C.c_double), i32, C.POINTER(i32), i32, vp], i32),
     "fluxmi_engine_workspace_bytes": ([vp, C.POINTER(i64)], i32),

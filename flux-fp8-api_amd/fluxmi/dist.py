@@ -5,6 +5,7 @@ sample i of a request on rank floor(i*world/B)... exactly one exchange before th
                       CLIP pooled `vec` [B,768] -- plus the packed request noise [B,Li,64] so that a batch of 8 on
                       8 GPUs reproduces the same batch on 1 GPU; ONE flat broadcast (payload <= 34 MB: latency-,
                       not bandwidth-bound, so no ring/bucketing)
+                      (+ the packed Kontext reference latents [B,Lc,64] when the request has a reference image)
   gather_latents    : final latents [B_local,Li,64] back to the VAE rank
 
 There is no per-step collective: batch elements never interact inside Flux.forward.  During the 12 calibration
@@ -39,11 +40,13 @@ def shard_bounds(batch: int, rank_: int, world: int) -> Tuple[int, int]:
     return lo, lo + base + (1 if rank_ < rem else 0)
 
 
-def broadcast_request(txt: torch.Tensor, vec: torch.Tensor, noise: torch.Tensor, src: int = 0):
-    """One flat buffer = [txt | vec | noise] (same dtype) broadcast from `src`; shapes must already agree on all ranks."""
+def broadcast_request(txt: torch.Tensor, vec: torch.Tensor, noise: torch.Tensor, src: int = 0, extra: Optional[torch.Tensor] = None):
+    """One flat buffer = [txt | vec | noise (| extra)] (same dtype) broadcast from `src`; shapes must already agree on all ranks.
+    `extra`: an optional further tensor in the same payload -- the packed FLUX.1 Kontext reference latents [B, Lc, 64], so that every rank
+    steps the same reference.  Returns (txt, vec, noise) or, with `extra`, (txt, vec, noise, extra)."""
     if not is_dist():
-        return txt, vec, noise
-    parts = [txt, vec, noise]
+        return (txt, vec, noise) if extra is None else (txt, vec, noise, extra)
+    parts = [txt, vec, noise] + ([] if extra is None else [extra])
     flat = torch.cat([p.reshape(-1) for p in parts])
     td.broadcast(flat, src=src)
     out, off = [], 0

@@ -236,16 +236,24 @@ class AutoEncoder(nn.Module):
         from fluxmi import ops
 
         B, H, W, C = x.shape
-        hn = self._norm(x, blk.norm, False).view(B, H * W, C)
+        P = H * W
+        hn = self._norm(x, blk.norm, False).view(B, P, C)
         wv, bv, _ = self._w(blk.v)
         out = torch.empty_like(hn)
+        # a pixel count that is no multiple of 8 (the softmax kernel's 16-byte rows; e.g. the 174 x 94 latent of a 1392 x 752 FLUX.1 Kontext
+        # reference) runs on Pp = P rounded up to 64: zero pixel rows, whose key columns are masked to -inf before the softmax (weight exactly
+        # 0) and whose V^T columns are Wv . 0 = 0; their output rows are dropped.  Other sizes take the unpadded path unchanged.
+        Pp = P if P % 8 == 0 else -(-P // 64) * 64
         for b in range(B):
-            q = self._conv1(hn[b], blk.q)                       # [P, C]
-            k = self._conv1(hn[b], blk.k)
-            vt = ops.linear(wv, hn[b].contiguous(), None)       # [C, P] = Wv . Xn^T = V^T (bias added after P V)
+            xb = hn[b] if Pp == P else torch.cat((hn[b], hn.new_zeros(Pp - P, C)), 0)
+            q = self._conv1(xb, blk.q)                          # [P, C]
+            k = self._conv1(xb, blk.k)
+            vt = ops.linear(wv, xb.contiguous(), None)          # [C, P] = Wv . Xn^T = V^T (bias added after P V)
             S = ops.linear(q, k, None)                          # [P, P] = Q K^T
+            if Pp != P:
+                S[:, P:] = float("-inf")
             Pm = ops.softmax_rows(S, float(C) ** -0.5)
-            out[b] = ops.linear(Pm, vt, bv)                     # [P, C] = P V + b_v
+            out[b] = ops.linear(Pm, vt, bv)[:P]                 # [P, C] = P V + b_v
         return self._conv1(out.view(B, H, W, C), blk.proj_out, resid=x)
 
     @torch.inference_mode()

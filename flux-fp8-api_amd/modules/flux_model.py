@@ -309,13 +309,35 @@ class Flux(nn.Module):
             _lib.call("fluxmi_engine_rebind", self._engine, lin, len(lin))
             self._engine_keep = (keep_l, self._engine_keep[1], lin, self._engine_keep[3])
 
-    def _prepare(self, img, img_ids, txt_ids, txt):
-        B, Li, _ = img.shape
+    def _prepare(self, img, img_ids, txt_ids, txt, Lc: int = 0):
+        """`img` / `img_ids` hold the whole image stream; with a Kontext reference its last `Lc` rows of each sample are the reference tokens."""
+        B, L_img, _ = img.shape
         Lt = txt.shape[1]
         # cheap (two small copies + one table kernel; the workspace is only re-allocated when the shape changes)
         ii = img_ids.to(torch.bfloat16).contiguous()
         ti = txt_ids.to(torch.bfloat16).contiguous()
-        _lib.call("fluxmi_engine_prepare", self._engine, B, Li, Lt, ops._p(ii), ops._p(ti), ops._stream())
+        if Lc:
+            _lib.call("fluxmi_engine_prepare_cond", self._engine, B, L_img - Lc, Lc, Lt, ops._p(ii), ops._p(ti), ops._stream())
+        else:
+            _lib.call("fluxmi_engine_prepare", self._engine, B, L_img, Lt, ops._p(ii), ops._p(ti), ops._stream())
+
+    @staticmethod
+    def _with_reference(img, img_ids, img_cond_seq, img_cond_seq_ids):
+        """FLUX.1 Kontext: the reference tokens ride behind the noisy tokens of each sample -> (stream, stream ids, Lc).  Both None: unchanged."""
+        if img_cond_seq is None and img_cond_seq_ids is None:
+            return img, img_ids, 0
+        if img_cond_seq is None or img_cond_seq_ids is None:
+            raise ValueError("img_cond_seq and img_cond_seq_ids go together")
+        if img_cond_seq.ndim != 3 or img_cond_seq.shape[0] != img.shape[0] or img_cond_seq.shape[2] != img.shape[2]:
+            raise ValueError(f"img_cond_seq {tuple(img_cond_seq.shape)} does not match img {tuple(img.shape)}")
+        if tuple(img_cond_seq_ids.shape) != (img_cond_seq.shape[0], img_cond_seq.shape[1], 3):
+            raise ValueError(f"img_cond_seq_ids {tuple(img_cond_seq_ids.shape)} != {(img_cond_seq.shape[0], img_cond_seq.shape[1], 3)}")
+        Lc = img_cond_seq.shape[1]
+        if Lc == 0:
+            return img, img_ids, 0
+        img = torch.cat((img.to(torch.bfloat16), img_cond_seq.to(device=img.device, dtype=torch.bfloat16)), 1)
+        img_ids = torch.cat((img_ids, img_cond_seq_ids.to(device=img_ids.device, dtype=img_ids.dtype)), 1)
+        return img, img_ids, Lc
 
     # ---- batch-sharded calibration (SURVEY.md 8e-3) ------------------------------------------------------------------
     def enable_amax_exchange(self, reduce_fn=None):
@@ -413,19 +435,24 @@ class Flux(nn.Module):
     # ---- forward / denoise ---------------------------------------------------------------------------------------
     @torch.inference_mode()
     def forward(self, img: Tensor, img_ids: Tensor, txt: Tensor, txt_ids: Tensor, timesteps: Tensor, y: Tensor,
-                guidance: Tensor | None = None, mode: Optional[int] = None) -> Tensor:
+                guidance: Tensor | None = None, mode: Optional[int] = None, img_cond_seq: Tensor | None = None,
+                img_cond_seq_ids: Tensor | None = None) -> Tensor:
         """One denoise-step evaluation (reference flux_model.py:672-716).  mode=None picks what the reference would do:
-        calibrating (unfused) while any F8Linear still has trials to record, fused once frozen."""
+        calibrating (unfused) while any F8Linear still has trials to record, fused once frozen.
+        FLUX.1 Kontext: `img_cond_seq` [B, Lc, C] / `img_cond_seq_ids` [B, Lc, 3] (flux_pipeline.prepare_kontext_reference) run through every
+        block behind the noisy tokens; the prediction covers the `img.shape[1]` noisy tokens only."""
         if img.ndim != 3 or txt.ndim != 3:
             raise ValueError("Input img and txt tensors must have 3 dimensions.")
         if self.params.guidance_embed and guidance is None:
             raise ValueError("Didn't get guidance strength for guidance distilled model.")
         bf = lambda t: t.to(torch.bfloat16).contiguous()
+        Li = img.shape[1]
+        img, img_ids, Lc = self._with_reference(img, img_ids, img_cond_seq, img_cond_seq_ids)
         img, txt, y, timesteps = bf(img), bf(txt), bf(y), bf(timesteps)
         guidance = bf(guidance) if guidance is not None else None
         self._ensure_engine(img.device)
         with self._lock:
-            self._prepare(img, img_ids, txt_ids, txt)
+            self._prepare(img, img_ids, txt_ids, txt, Lc)
             trial = self._trial_counter()
             if mode is None:
                 if trial is None:
@@ -434,7 +461,7 @@ class Flux(nn.Module):
                     mode = 0
                 else:
                     mode = 1 if self._all_block_linears_f8() else 2
-            pred = torch.empty(img.shape[0], img.shape[1], self.out_channels, dtype=torch.bfloat16, device=img.device)
+            pred = torch.empty(img.shape[0], Li, self.out_channels, dtype=torch.bfloat16, device=img.device)
             _lib.call("fluxmi_engine_forward", self._engine, ops._p(img), ops._p(txt), ops._p(y), ops._p(timesteps), ops._p(guidance),
                       ops._p(pred), mode, trial if mode == 0 else 0, ops._stream())
             if mode == 0:
@@ -452,10 +479,14 @@ class Flux(nn.Module):
 
     @torch.inference_mode()
     def denoise(self, img: Tensor, img_ids: Tensor, txt: Tensor, txt_ids: Tensor, y: Tensor, timesteps: List[float],
-                guidance: float = 3.5, use_graph: bool = True) -> Tensor:
+                guidance: float = 3.5, use_graph: bool = True, img_cond_seq: Tensor | None = None,
+                img_cond_seq_ids: Tensor | None = None) -> Tensor:
         """The Euler loop of FluxPipeline.generate (reference flux_pipeline.py:619-651) run natively: calibrating
-        steps unfused, every later step one replay of a captured hipGraph.  Returns the final latent tokens."""
+        steps unfused, every later step one replay of a captured hipGraph.  Returns the final latent tokens.
+        FLUX.1 Kontext: with `img_cond_seq` / `img_cond_seq_ids` the reference tokens join every step's forward and are never stepped; the
+        return value is the `img.shape[1]` noisy tokens only."""
         bf = lambda t: t.to(torch.bfloat16).contiguous()
+        kontext = img_cond_seq is not None or img_cond_seq_ids is not None
         if img.shape[0] > self.MAX_ENGINE_BATCH:
             # the engine takes at most 32 samples per pass (workspace / modulation-table size); the reference has no num_images limit, so
             # larger batches run as consecutive passes (samples never interact).  EQUAL passes: the engine re-allocates its workspace and
@@ -471,14 +502,18 @@ class Flux(nn.Module):
                 sl = slice(i, min(i + per, B))
                 pad = per - (sl.stop - sl.start)  # a short last pass is padded with copies of its last sample (same B -> same graph)
                 pick = lambda t: torch.cat([t[sl], t[sl.stop - 1:sl.stop].expand(pad, *t.shape[1:])], 0) if pad else t[sl]
-                o = self.denoise(pick(img), pick(img_ids), pick(txt), pick(txt_ids), pick(y), timesteps, guidance=guidance, use_graph=use_graph)
+                cond = dict(img_cond_seq=pick(img_cond_seq), img_cond_seq_ids=pick(img_cond_seq_ids)) if kontext else {}
+                o = self.denoise(pick(img), pick(img_ids), pick(txt), pick(txt_ids), pick(y), timesteps, guidance=guidance, use_graph=use_graph,
+                                 **cond)
                 outs.append(o[:per - pad])
             return torch.cat(outs, 0)
+        Li = img.shape[1]
+        img, img_ids, Lc = self._with_reference(img, img_ids, img_cond_seq, img_cond_seq_ids)
         img = bf(img).clone()
         txt, y = bf(txt), bf(y)
         self._ensure_engine(img.device)
         with self._lock:
-            self._prepare(img, img_ids, txt_ids, txt)
+            self._prepare(img, img_ids, txt_ids, txt, Lc)
             trial = self._trial_counter()
             t_io = C.c_int(trial if trial is not None else 0)
             ts = (C.c_double * len(timesteps))(*[float(t) for t in timesteps])
@@ -486,7 +521,7 @@ class Flux(nn.Module):
                       len(timesteps) - 1, C.byref(t_io), int(use_graph), ops._stream())
             if trial is not None:
                 self._advance_calibration(t_io.value)
-        return img
+        return img[:, :Li].contiguous() if Lc else img
 
     @classmethod
     def from_pretrained(cls, path: str, dtype: torch.dtype = torch.float16) -> "Flux":

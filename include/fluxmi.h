@@ -383,6 +383,13 @@ int fluxmi_engine_rebind(fluxmi_engine_t* e, const fluxmi_linear_t* linears, int
 /* per-request setup: (re)allocates the workspace for (B, Li, Lt), builds the RoPE table from the position ids
  * (step-invariant: flux_model.py:701-702) */
 int fluxmi_engine_prepare(fluxmi_engine_t* e, int B, int Li, int Lt, const void* img_ids, const void* txt_ids, void* stream);
+/* FLUX.1 Kontext (reference-image editing): the same setup for an image stream of Li predicted + Lc reference rows per sample.
+ * img_ids: [B, Li+Lc, 3], the reference rows last in each sample (their axis 0 = 1).  fluxmi_engine_prepare == this with Lc = 0.  After a
+ * prepare with Lc > 0, fluxmi_engine_forward / fluxmi_engine_denoise take img as [B, Li+Lc, in_channels]; forward writes pred as
+ * [B, Li, in_channels] (the reference rows run through every block, only the leading Li rows are predicted); denoise steps rows [0, Li) of
+ * each sample in place and leaves the reference rows bit-for-bit as they were.  The split (Li, Lc) is part of the workspace key: another
+ * split of the same Li+Lc re-allocates and re-captures the step graph. */
+int fluxmi_engine_prepare_cond(fluxmi_engine_t* e, int B, int Li, int Lc, int Lt, const void* img_ids, const void* txt_ids, void* stream);
 /* one Flux.forward (flux_model.py:672-716).  mode 0 = calibrating/unfused (advances the F8Linear trial state
  * machine exactly like the reference's first 13 calls), 1 = frozen/fused.  pred: bf16 [B,Li,in_channels]. */
 int fluxmi_engine_forward(fluxmi_engine_t* e, const void* img, const void* txt, const void* y, const void* timesteps,

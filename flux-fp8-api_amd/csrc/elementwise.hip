@@ -536,6 +536,25 @@ __global__ void __launch_bounds__(256) euler_rows_kernel(u16* __restrict__ img, 
     *(uint4*)x = pack8(fi);
   }
 }
+// The Euler step of an image stream WIDER than the prediction (FLUX.1 Fill / Depth / Canny: step-invariant conditioning channels ride behind
+// the noisy channels of every token and are never stepped): channels [0, c_out) of every row of img [rows, c_in] += bf16(dt * pred),
+// pred [rows, c_out].  Same arithmetic as euler_kernel.  One thread per 16-byte vector, vectors numbered along pred (dense): the c_out / 8
+// lanes of one row read one contiguous c_out * 2-byte segment of img (128 B at c_out = 64) and the next row's segment starts c_in * 2 bytes
+// further on, so every wave touches 8 full segments and pred in one contiguous KiB.  The conditioning channels are neither read nor written.
+__global__ void __launch_bounds__(256) euler_cols_kernel(u16* __restrict__ img, const u16* __restrict__ pred, const float* __restrict__ dts,
+                                                         const int* __restrict__ step, long long n_vec, int vec_per_row, int c_in) {
+  const float dt = dts[*step];
+  for (long long v = (long long)blockIdx.x * blockDim.x + threadIdx.x; v < n_vec; v += (long long)gridDim.x * blockDim.x) {
+    const long long r = v / vec_per_row;
+    u16* x = img + r * c_in + (v - r * vec_per_row) * 8;
+    float fi[8], fp[8];
+    unpack8(*(const uint4*)x, fi);
+    unpack8(*(const uint4*)(pred + v * 8), fp);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) fi[j] += rbf(dt * fp[j]);
+    *(uint4*)x = pack8(fi);
+  }
+}
 // per-step scalars kept on the device so that one captured graph serves every step:
 //   t_vec[b] = bf16(ts[*step]),  then ++*step happens in advance_step_kernel at the end of the step.
 __global__ void set_timestep_kernel(u16* __restrict__ t_vec, const float* __restrict__ ts, const int* __restrict__ step, int B) {
@@ -842,6 +861,15 @@ int fluxmi_k_euler_rows(void* img, const void* pred, const float* dts, const int
   if (n == 0) return 0;
   hipLaunchKernelGGL(euler_rows_kernel, dim3(grid_for(n / 8)), dim3(256), 0, s, (u16*)img, (const u16*)pred, dts, step, n, pred_rows * C,
                      img_rows * C);
+  FLUXMI_LAUNCH_CHECK();
+  return 0;
+}
+int fluxmi_k_euler_cols(void* img, const void* pred, const float* dts, const int* step, long long rows, int c_in, int c_out, hipStream_t s) {
+  FLUXMI_REQUIRE(step && rows >= 0 && c_out > 0 && c_out % 8 == 0 && c_in % 8 == 0 && c_out <= c_in,
+                 "euler_cols: bad shape rows=%lld c_in=%d c_out=%d (multiples of 8, c_out <= c_in)", rows, c_in, c_out);
+  const long long n_vec = rows * (c_out / 8);
+  if (n_vec == 0) return 0;
+  hipLaunchKernelGGL(euler_cols_kernel, dim3(grid_for(n_vec)), dim3(256), 0, s, (u16*)img, (const u16*)pred, dts, step, n_vec, c_out / 8, c_in);
   FLUXMI_LAUNCH_CHECK();
   return 0;
 }

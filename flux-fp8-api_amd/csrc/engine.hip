@@ -12,7 +12,9 @@
 //
 // HBM layout (per request shape B, Li, Lt; L = Lt + Li, txt rows first so torch.cat is free).  Li is the whole IMAGE STREAM: with a FLUX.1
 // Kontext reference (fluxmi_engine_prepare_cond) the Lc reference rows follow the Lpred noisy rows of each sample (Li = Lpred + Lc); every
-// block runs over all of them, and only the final layer and the Euler update are restricted to the leading Lpred rows:
+// block runs over all of them, and only the final layer and the Euler update are restricted to the leading Lpred rows.  The image stream's
+// rows are C_in = in_channels wide (img_in's K); the model predicts C_out = final_layer.linear's N of them.  C_out < C_in for FLUX.1 Fill /
+// Depth / Canny: the trailing C_in - C_out channels are step-invariant conditioning that img_in reads and the Euler update never writes:
 //   x      bf16 [B, L, H]        residual stream (img = rows Lt.., txt = rows ..Lt)
 //   a8     fp8  [B, L, H]        quantised LN+modulate output (GEMM A operand)
 //   qkv    bf16 [B, L, 3H]       qkv GEMM output
@@ -835,6 +837,9 @@ int final_layer(E* e, u16* pred, int s0, int s1, hipStream_t s) {
   return 0;
 }
 
+// the channels the model predicts: final_layer.linear's N (== in_channels but for channel-conditioned models, see fluxmi_engine_create)
+int c_out(const E* e) { return e->lin[e->i_final_lin].N; }
+
 int require_all_f8(E* e) {
   for (int i = 0; i < e->d.depth; ++i)
     for (int sl : {D_IMG_QKV, D_IMG_PROJ, D_IMG_MLP0, D_IMG_MLP2, D_TXT_QKV, D_TXT_PROJ, D_TXT_MLP0, D_TXT_MLP2})
@@ -967,6 +972,11 @@ int fluxmi_engine_create(const fluxmi_model_desc_t* desc, const fluxmi_linear_t*
   FLUXMI_REQUIRE(n_norm_scales == desc->depth * 4 + desc->depth_single * 2, "engine_create: expected %d norm scales, got %d",
                  desc->depth * 4 + desc->depth_single * 2, n_norm_scales);
   FLUXMI_REQUIRE(desc->num_trials >= 1 && desc->num_trials <= 64, "engine_create: num_trials out of range");
+  // C_in = img_in's width, C_out = final_layer.linear's N (the last linear): FLUX.1 Fill / Depth / Canny append C_in - C_out step-invariant
+  // conditioning channels to every token; the 16-byte Euler kernels need both widths in whole 8-channel vectors
+  const int C_in = desc->in_channels, C_out = linears[n_linears - 1].N;
+  FLUXMI_REQUIRE(C_out >= 8 && C_out <= C_in && C_out % 8 == 0 && C_in % 8 == 0,
+                 "engine_create: in_channels %d / final_layer out_channels %d: need out <= in, both multiples of 8", C_in, C_out);
   E* e = new E();
   e->d = *desc;
   e->lin.assign(linears, linears + n_linears);
@@ -1066,6 +1076,9 @@ int fluxmi_engine_prepare_cond(fluxmi_engine_t* e, int B, int Li_pred, int Lc, i
   FLUXMI_REQUIRE(e && B >= 1 && B <= FLUXMI_ENGINE_MAX_BATCH && Li_pred >= 1 && Lc >= 0 && Lt >= 0,
                  "engine_prepare: bad shape B=%d Li=%d Lc=%d Lt=%d (B must be 1..%d)", B, Li_pred, Lc, Lt, FLUXMI_ENGINE_MAX_BATCH);
   FLUXMI_REQUIRE(img_ids && (Lt == 0 || txt_ids), "engine_prepare: NULL ids");
+  FLUXMI_REQUIRE(Lc == 0 || c_out(e) == e->d.in_channels,
+                 "engine_prepare: a reference-image row split (Lc = %d) needs in_channels == out_channels (this model: %d / %d, channel "
+                 "conditioning); no released model takes both", Lc, e->d.in_channels, c_out(e));
   const int Li = Li_pred + Lc;
   const int H = e->d.hidden, Hm = e->d.mlp_hidden, L = Li + Lt, Lp = ((L + 63) / 64) * 64;
   if (e->pairs_skipped) e->pairs_dirty = true;  // the row-pair copies did not fit last time: try again with this request
@@ -1091,7 +1104,7 @@ int fluxmi_engine_prepare_cond(fluxmi_engine_t* e, int B, int Li_pred, int Lc, i
         {"mods_a8", (size_t)FLUXMI_MAX_GROUPS * (((size_t)B * std::max(H, 4096) + 255) & ~(size_t)255)},
         // static request buffers (make the captured graph independent of caller pointers)
         {"img_s", (size_t)B * Li * e->d.in_channels * 2}, {"txt_s", (size_t)B * Lt * e->d.ctx_in * 2}, {"y_s", (size_t)B * e->d.vec_in * 2},
-        {"pred_s", (size_t)B * Li_pred * e->d.in_channels * 2}, {"txt_emb", (size_t)B * Lt * H * 2},
+        {"pred_s", (size_t)B * Li_pred * c_out(e) * 2}, {"txt_emb", (size_t)B * Lt * H * 2},
         // split-K partial tiles of the bf16 small-M launches (api.cpp: bf16 operands, >= 192 K-steps): owned by the engine, because its step
         // graph is captured on a private stream and replayed on the caller's -- a scratch keyed by stream would be nobody's
         {"splitk", needs_splitk(e) ? FLUXMI_SPLITK_WS_BYTES : 256},
@@ -1159,8 +1172,11 @@ int fluxmi_engine_denoise(fluxmi_engine_t* e, void* img, const void* txt, const 
   SplitkScope splitk(e);
   FLUXMI_TRY(ensure_pairs(e, s));
   const int B = e->B, Li = e->Li, Lt = e->Lt, C = e->d.in_channels;
-  // the Euler update: the whole stream, or (Kontext) the leading Lpred rows of each sample -- the reference rows never move
+  // the Euler update: the whole stream, or (Kontext) the leading Lpred rows of each sample -- the reference rows never move -- or (Fill /
+  // Depth / Canny) the leading C_out channels of every row -- the conditioning channels never move (no row split then: prepare_cond)
   auto euler = [&](hipStream_t st) -> int {
+    if (c_out(e) != C)
+      return fluxmi_k_euler_cols(buf<u16>(e, "img_s"), buf<u16>(e, "pred_s"), e->d_dts, e->d_step, (long long)B * Li, C, c_out(e), st);
     if (e->Lpred == Li) return fluxmi_k_euler(buf<u16>(e, "img_s"), buf<u16>(e, "pred_s"), e->d_dts, e->d_step, (long long)B * Li * C, st);
     return fluxmi_k_euler_rows(buf<u16>(e, "img_s"), buf<u16>(e, "pred_s"), e->d_dts, e->d_step, B, Li, e->Lpred, C, st);
   };

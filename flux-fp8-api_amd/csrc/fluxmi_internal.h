@@ -158,6 +158,9 @@ int fluxmi_k_euler(void* img, const void* pred, const float* dts, const int* ste
 // rows [0, pred_rows) of each sample of img [B, img_rows, C] += bf16(dts[*step] * pred [B, pred_rows, C]) (FLUX.1 Kontext: the reference rows stay)
 int fluxmi_k_euler_rows(void* img, const void* pred, const float* dts, const int* step, int B, long long img_rows, long long pred_rows, int C,
                         hipStream_t s);
+// channels [0, c_out) of every row of img [rows, c_in] += bf16(dts[*step] * pred [rows, c_out]) (FLUX.1 Fill / Depth / Canny: the conditioning
+// channels stay)
+int fluxmi_k_euler_cols(void* img, const void* pred, const float* dts, const int* step, long long rows, int c_in, int c_out, hipStream_t s);
 int fluxmi_k_set_timestep(void* t_vec, const float* ts, const int* step, int B, hipStream_t s);
 int fluxmi_k_advance_step(int* step, hipStream_t s);
 int fluxmi_k_clock_sample(unsigned long long* out2, hipStream_t s);

@@ -223,6 +223,92 @@ class FluxPipeline:
         ids = kontext_reference_ids(num_images, h_l, w_l, self.device_flux, self.dtype)
         return cond.contiguous(), ids
 
+    # ---- FLUX.1 Fill / Depth / Canny channel conditioning ------------------------------------------------------------------------------
+    def conditioning_kind(self) -> Optional[str]:
+        """None (text-to-image: in_channels == out_channels), "fill" (FLUX.1 Fill [dev]: 320 conditioning channels) or "control" (FLUX.1
+        Depth / Canny [dev]: 64).  Any other split is refused."""
+        extra = getattr(self.model, "in_channels", 64) - getattr(self.model, "out_channels", getattr(self.model, "in_channels", 64))
+        if extra == 0:
+            return None
+        kind = {320: "fill", 64: "control"}.get(extra)
+        if kind is None:
+            raise ValueError(f"fluxmi: a model with {extra} conditioning channels per token is neither FLUX.1 Fill (320) nor Depth / Canny (64)")
+        return kind
+
+    def _rgb_uint8(self, image) -> torch.Tensor:
+        """any form load_init_image_if_needed takes -> PIL image (uint8 tensors only, like a Kontext reference)"""
+        from PIL import Image
+
+        im = self.load_init_image_if_needed(image)
+        if isinstance(im, torch.Tensor):
+            im = im.detach().cpu()
+            if im.dtype != torch.uint8:
+                raise TypeError(f"fluxmi: a conditioning image tensor must be uint8 HWC, got {im.dtype}")
+            im = im.numpy()
+        return im if isinstance(im, Image.Image) else Image.fromarray(np.asarray(im))
+
+    def _encode_sampled(self, x: torch.Tensor, generator: torch.Generator = None) -> torch.Tensor:
+        """VAE-encode x [1, 3, H, W] in [-1, 1] with the Gaussian sample [1, z_channels, H/8, W/8] drawn from `generator` -> bf16 latents"""
+        f = 1 << (self.ae.encoder.num_resolutions - 1)  # the encoder's downsampling (8 for every Flux autoencoder)
+        z_ch = self.ae.encoder.conv_out.out_channels // 2
+        gen_dev = generator.device if generator is not None else self.device_ae
+        eps = torch.randn(1, z_ch, x.shape[-2] // f, x.shape[-1] // f, generator=generator, device=gen_dev, dtype=torch.float32)
+        return self.ae.encode(x.to(self.device_ae, dtype=self.ae_dtype), noise=eps.to(self.device_ae)).to(torch.bfloat16)
+
+    @staticmethod
+    def pack_fill_mask(mask: torch.Tensor) -> torch.Tensor:
+        """mask [B, 1, H, W] in [0, 1] -> bf16 [B, (H/16) * (W/16), 256]: each 8 x 8 pixel block of a latent pixel becomes 64 channels (BFL:
+        rearrange(mask[:, 0], "b (h ph) (w pw) -> b (ph pw) h w", ph=8, pw=8)), then packed 2 x 2 like the latents."""
+        m = mask[:, 0].to(torch.bfloat16)
+        b, H, W = m.shape
+        m = m.reshape(b, H // 8, 8, W // 8, 8).permute(0, 2, 4, 1, 3).reshape(b, 64, H // 8, W // 8)
+        return FluxPipeline.pack(m)
+
+    @torch.inference_mode()
+    def prepare_fill_conditioning(self, image, mask, height: int, width: int, num_images: int = 1,
+                                  generator: torch.Generator = None) -> torch.Tensor:
+        """FLUX.1 Fill [dev] (inpainting / outpainting) -> img_cond bf16 [num_images, Li, 320] on the flow device.  The semantics of BFL's
+        prepare_fill / denoise (src/flux/sampling.py), kept here in one place:
+          1. the RGB image goes to float / 127.5 - 1, [1, 3, H, W]; the mask is converted to single-channel "L" as PIL does, then
+             float / 255, [1, 1, H, W].  White (1) means "regenerate", black (0) "keep";
+          2. masked = image * (1 - mask), VAE-encoded with its Gaussian sample, cast to bf16 and packed 2 x 2: [1, Li, 64];
+          3. bf16(mask[:, 0]) is rearranged "b (h ph) (w pw) -> b (ph pw) h w" (ph = pw = 8) and packed 2 x 2: [1, Li, 256]
+             (pack_fill_mask);
+          4. img_cond = cat(latents, mask, -1), [1, Li, 320], repeated over the batch; it is appended to the channels of every token of every
+             step, the model predicts the 64 noisy channels and only they are stepped.
+        Ours, not BFL's: image and mask are brought to (width, height) with img2img's resize_center_crop (skipped when the size already
+        matches, so a correctly sized input passes unchanged).  The encoder's sample is drawn from `generator` ([1, 16, H/8, W/8], one draw
+        shared by the copies); generate() passes the request's generator AFTER the noise, so one seed gives one image.  Outpainting is the same
+        call on an image padded to the new size, with a mask that is white over the padding.  BFL recommends guidance 30 and about 50 steps.
+        `image` / `mask`: anything load_init_image_if_needed takes (path, base64 / data-URL, PIL image, uint8 array or tensor)."""
+        if self.ae is None:
+            raise RuntimeError("fluxmi: FLUX.1 Fill conditioning needs an autoencoder (config.ae_path) -- none is attached")
+        img = torch.from_numpy(np.array(self._rgb_uint8(image).convert("RGB"))).float().div(127.5).sub(1.0).permute(2, 0, 1)[None]
+        m = torch.from_numpy(np.array(self._rgb_uint8(mask).convert("L"))).float().div(255.0)[None, None]
+        if tuple(img.shape[-2:]) != (height, width):
+            img = self.resize_center_crop(img, height, width)
+        if tuple(m.shape[-2:]) != (height, width):
+            m = self.resize_center_crop(m, height, width)
+        z = self._encode_sampled(img * (1.0 - m), generator)
+        cond = torch.cat((self.pack(z), self.pack_fill_mask(m).to(z.device)), -1)
+        return cond.to(self.device_flux).repeat(num_images, 1, 1).contiguous()
+
+    @torch.inference_mode()
+    def prepare_control_conditioning(self, control_image, height: int, width: int, num_images: int = 1,
+                                     generator: torch.Generator = None) -> torch.Tensor:
+        """FLUX.1 Depth / Canny [dev] -> img_cond bf16 [num_images, Li, 64] on the flow device (BFL's prepare_control, src/flux/sampling.py):
+        the RGB control image is resized to (width, height) with PIL LANCZOS, goes to float / 127.5 - 1, is VAE-encoded with its Gaussian
+        sample (drawn from `generator` after the noise, as in prepare_fill_conditioning), cast to bf16 and packed 2 x 2.  The caller passes the
+        depth map or edge map itself: BFL's preprocessors (Depth Anything, OpenCV Canny) are not part of this project."""
+        from PIL import Image
+
+        if self.ae is None:
+            raise RuntimeError("fluxmi: FLUX.1 Depth / Canny conditioning needs an autoencoder (config.ae_path) -- none is attached")
+        pil = self._rgb_uint8(control_image).convert("RGB").resize((width, height), Image.LANCZOS)
+        x = torch.from_numpy(np.array(pil)).float().div(127.5).sub(1.0).permute(2, 0, 1)[None]
+        cond = self.pack(self._encode_sampled(x, generator))
+        return cond.to(self.device_flux).repeat(num_images, 1, 1).contiguous()
+
     # ---- packing / ids (reference flux_pipeline.py:267-292, 440-448) ----------------------------------------------
     @staticmethod
     def pack(img: torch.Tensor) -> torch.Tensor:
@@ -318,6 +404,7 @@ class FluxPipeline:
             self.model.enable_amax_exchange()
         kw = dict(prompt=prompt, height=768, width=768, num_steps=12, guidance=3.5, seed=10, silent=True, output_type="latent",
                   num_images=max(1, world))
+        kw.update(self._warmup_conditioning(768, 768))
         if self.name == ModelVersion.flux_schnell.value or self.name == "flux-schnell":
             kw["num_steps"] = 4
             for _ in range(3):
@@ -328,16 +415,61 @@ class FluxPipeline:
         if world > 1:
             self.model.enable_amax_exchange(False)
 
+    def _warmup_conditioning(self, height: int, width: int) -> dict:
+        """compile()'s conditioning for a Fill / Depth / Canny model, so that img_in sees its real width and (fp8 embedders) its input scale
+        covers the conditioning channels: a mid-grey image and a centred rectangular mask (Fill) or a mid-grey control image through the
+        autoencoder; without one, N(0, 1) latents and the same mask, packed.  Nothing for a text-to-image model."""
+        kind = self.conditioning_kind()
+        if kind is None:
+            return {}
+        mask = np.zeros((height, width), dtype=np.uint8)
+        mask[height // 4:height - height // 4, width // 4:width - width // 4] = 255
+        grey = np.full((height, width, 3), 128, dtype=np.uint8)
+        if self.ae is not None:
+            return dict(init_image=grey, mask_image=mask) if kind == "fill" else dict(control_image=grey)
+        z = torch.randn(1, 16, height // 8, width // 8, generator=torch.Generator().manual_seed(11)).to(torch.bfloat16)
+        cond = self.pack(z)
+        if kind == "fill":
+            cond = torch.cat((cond, self.pack_fill_mask(torch.from_numpy(mask).float().div(255.0)[None, None])), -1)
+        return dict(img_cond=cond)
+
     # ---- the request (reference flux_pipeline.py:526-663) ---------------------------------------------------------------
     @torch.inference_mode()
     def generate(self, prompt, width: int = 720, height: int = 1024, num_steps: int = 24, guidance: float = 3.5,
                  seed: int | None = None, init_image=None, strength: float = 1.0, silent: bool = False, num_images: int = 1,
                  return_seed: bool = False, jpeg_quality: int = 99, output_type: str = "jpeg", noise: Optional[torch.Tensor] = None,
-                 use_graph: bool = True, reference_image=None):
+                 use_graph: bool = True, reference_image=None, mask_image=None, control_image=None,
+                 img_cond: Optional[torch.Tensor] = None):
         """`reference_image` (FLUX.1 Kontext [dev] instruction editing): an image the prompt describes an edit of, in any form `init_image`
-        takes; see prepare_kontext_reference.  Composes with `init_image` / `strength` unchanged."""
+        takes; see prepare_kontext_reference.  Composes with `init_image` / `strength` unchanged.
+        FLUX.1 Fill [dev] (a model with 320 conditioning channels): `init_image` is the image to inpaint and `mask_image` (white =
+        regenerate) is required; see prepare_fill_conditioning.  At strength 1.0 (BFL's only mode) the generation starts from pure noise;
+        strength < 1 also blends the VAE latents of `init_image` into the start as img2img does.  BFL recommends guidance 30, ~50 steps.
+        FLUX.1 Depth / Canny [dev] (64 conditioning channels): `control_image` (the depth map or edge map) is required; see
+        prepare_control_conditioning.  Both take any form `init_image` takes.  `img_cond`: the conditioning tokens [1 or num_images, Li,
+        in_channels - out_channels] already prepared (instead of `mask_image` / `control_image`).  A text-to-image model refuses all three."""
+        kind = self.conditioning_kind()
+        if kind is None and (mask_image is not None or control_image is not None or img_cond is not None):
+            raise ValueError("fluxmi: mask_image / control_image / img_cond need a FLUX.1 Fill or Depth / Canny model (this one has no "
+                             "conditioning channels)")
+        if kind is not None:
+            if reference_image is not None:
+                raise ValueError("fluxmi: a Fill / Depth / Canny model takes no Kontext reference_image")
+            if kind == "fill" and control_image is not None:
+                raise ValueError("fluxmi: control_image is for FLUX.1 Depth / Canny; a Fill model takes init_image + mask_image")
+            if kind == "control" and mask_image is not None:
+                raise ValueError("fluxmi: mask_image is for FLUX.1 Fill; a Depth / Canny model takes control_image")
+            if img_cond is not None and (mask_image is not None or control_image is not None):
+                raise ValueError("fluxmi: pass img_cond or mask_image / control_image, not both")
+            if img_cond is None and kind == "fill" and (mask_image is None or init_image is None):
+                raise ValueError("fluxmi: FLUX.1 Fill needs init_image (the image to inpaint) and mask_image (white = regenerate)")
+            if img_cond is None and kind == "control" and control_image is None:
+                raise ValueError("fluxmi: FLUX.1 Depth / Canny needs control_image (the depth map or edge map)")
         num_steps = 4 if self.name == "flux-schnell" else num_steps
         init_image = self.load_init_image_if_needed(init_image) if init_image is not None else None
+        fill_image = init_image if kind == "fill" else None
+        if fill_image is not None and strength == 1.0:
+            init_image = None  # the img2img blend is the identity at strength 1: BFL's Fill starts from pure noise, no encode
         height, width = 16 * (height // 16), 16 * (width // 16)
         generator, seed = self.set_seed(seed)
         world, rank = fdist.world_size(), fdist.rank()
@@ -361,8 +493,23 @@ class FluxPipeline:
             # drawn from the request's generator after the noise (the order is part of what a seed reproduces)
             c_seq, c_ids = self.prepare_kontext_reference(reference_image, num_images=num_images, generator=generator)
             cond = dict(img_cond_seq=c_seq, img_cond_seq_ids=c_ids)
+        if kind is not None:
+            # drawn from the request's generator after the noise, like a Kontext reference
+            if img_cond is None and kind == "fill":
+                img_cond = self.prepare_fill_conditioning(fill_image, mask_image, height, width, num_images=1, generator=generator)
+            elif img_cond is None:
+                img_cond = self.prepare_control_conditioning(control_image, height, width, num_images=1, generator=generator)
+            img_cond = img_cond.to(device=self.device_flux, dtype=torch.bfloat16)
+            if img_cond.shape[0] == 1 and num_images > 1:
+                img_cond = img_cond.repeat(num_images, 1, 1)
+            cond = dict(img_cond=img_cond.contiguous())
         if world > 1:
-            if cond:
+            if "img_cond" in cond:
+                # every rank steps rank 0's conditioning (the VAE sample differs between ranks' generators); its bf16 bits ride in the
+                # payload's dtype and come back unchanged
+                txt, vec, img, c = fdist.broadcast_request(txt, vec, img, src=0, extra=cond["img_cond"].view(img.dtype))
+                cond["img_cond"] = c.view(torch.bfloat16)
+            elif cond:
                 # every rank steps rank 0's reference latents (the VAE sample differs between ranks' generators on other devices)
                 txt, vec, img, cond["img_cond_seq"] = fdist.broadcast_request(txt, vec, img, src=0, extra=cond["img_cond_seq"])
             else:

@@ -5,7 +5,8 @@ sample i of a request on rank floor(i*world/B)... exactly one exchange before th
                       CLIP pooled `vec` [B,768] -- plus the packed request noise [B,Li,64] so that a batch of 8 on
                       8 GPUs reproduces the same batch on 1 GPU; ONE flat broadcast (payload <= 34 MB: latency-,
                       not bandwidth-bound, so no ring/bucketing)
-                      (+ the packed Kontext reference latents [B,Lc,64] when the request has a reference image)
+                      (+ the packed Kontext reference latents [B,Lc,64] when the request has a reference image, or the
+                      Fill / Depth / Canny conditioning [B,Li,320|64] as bf16 bits in the payload's dtype)
   gather_latents    : final latents [B_local,Li,64] back to the VAE rank
 
 There is no per-step collective: batch elements never interact inside Flux.forward.  During the 12 calibration
@@ -42,8 +43,8 @@ def shard_bounds(batch: int, rank_: int, world: int) -> Tuple[int, int]:
 
 def broadcast_request(txt: torch.Tensor, vec: torch.Tensor, noise: torch.Tensor, src: int = 0, extra: Optional[torch.Tensor] = None):
     """One flat buffer = [txt | vec | noise (| extra)] (same dtype) broadcast from `src`; shapes must already agree on all ranks.
-    `extra`: an optional further tensor in the same payload -- the packed FLUX.1 Kontext reference latents [B, Lc, 64], so that every rank
-    steps the same reference.  Returns (txt, vec, noise) or, with `extra`, (txt, vec, noise, extra)."""
+    `extra`: an optional further tensor in the same payload -- the packed FLUX.1 Kontext reference latents [B, Lc, 64] or the FLUX.1 Fill /
+    Depth / Canny conditioning [B, Li, 320 | 64], so that every rank steps the same conditioning.  Returns (txt, vec, noise) or, with `extra`, (txt, vec, noise, extra)."""
     if not is_dist():
         return (txt, vec, noise) if extra is None else (txt, vec, noise, extra)
     parts = [txt, vec, noise] + ([] if extra is None else [extra])

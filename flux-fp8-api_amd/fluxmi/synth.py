@@ -28,6 +28,12 @@ def _linear(sd, name, n_out, n_in, gen, device, dtype, gain=1.0, bias=True, outl
         sd[name + ".bias"] = b.to(dtype)
 
 
+def _out_channels(params) -> int:
+    """the predicted (noisy) channels: params.out_channels when set (FLUX.1 Fill / Depth / Canny), else in_channels"""
+    out = getattr(params, "out_channels", None)
+    return params.in_channels if out is None else out
+
+
 def make_state_dict(params, seed: int = 0, dtype=torch.bfloat16, device="cpu") -> Dict[str, torch.Tensor]:
     """params: anything with the FluxParams fields (modules.flux_model.FluxParams)."""
     gen = torch.Generator(device=device).manual_seed(seed)
@@ -64,19 +70,19 @@ def make_state_dict(params, seed: int = 0, dtype=torch.bfloat16, device="cpu") -
         L(f"{p}.linear2", H, H + mlp)
         qk_scales(f"{p}.norm")
         L(f"{p}.modulation.lin", 3 * H, H, gain=0.5)
-    L("final_layer.linear", params.in_channels, H)
+    L("final_layer.linear", _out_channels(params), H)
     L("final_layer.adaLN_modulation.1", 2 * H, H, gain=0.5)
     return sd
 
 
 def make_inputs(params, height: int, width: int, txt_len: int, batch: int = 1, seed: int = 0,
                 dtype=torch.bfloat16, real_tokens: int = 32):
-    """Seeded request tensors: packed N(0,1) latent noise, T5-like `txt` whose rows
+    """Seeded request tensors: packed N(0,1) latent noise (the predicted channels only), T5-like `txt` whose rows
     >= real_tokens repeat one "pad" row, CLIP-like pooled `y`, position ids per
     flux_pipeline.py:280-292 / flux_emphasis.py:433-439.  All on CPU in the flow dtype."""
     gen = torch.Generator().manual_seed(1000 + seed)
     h2, w2 = math.ceil(height / 16), math.ceil(width / 16)
-    img = torch.randn(batch, h2 * w2, params.in_channels, generator=gen).to(dtype)
+    img = torch.randn(batch, h2 * w2, _out_channels(params), generator=gen).to(dtype)
     txt = 0.1 * torch.randn(batch, txt_len, params.context_in_dim, generator=gen)
     if txt_len > real_tokens:
         txt[:, real_tokens:] = txt[:, real_tokens:real_tokens + 1]

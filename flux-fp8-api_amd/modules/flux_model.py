@@ -22,7 +22,7 @@ from collections import namedtuple
 from typing import TYPE_CHECKING, List, Optional
 
 import torch
-from pydantic import BaseModel
+from pydantic import BaseModel, Field
 from torch import Tensor, nn
 
 from fluxmi import _lib, ops
@@ -44,6 +44,10 @@ class FluxParams(BaseModel):  # reference flux_model.py:24-36
     theta: int
     qkv_bias: bool
     guidance_embed: bool
+    # BFL's name: the channels the model predicts.  None = in_channels (every text-to-image model).  FLUX.1 Fill [dev] (384 -> 64) and
+    # Depth / Canny [dev] (128 -> 64) feed step-invariant conditioning channels behind the 64 noisy ones through img_in.  Not part of
+    # model_dump(): the oracle's FluxParams dataclass has no such field.
+    out_channels: Optional[int] = Field(default=None, exclude=True)
 
 
 ModulationOut = namedtuple("ModulationOut", ["shift", "scale", "gate"])
@@ -162,7 +166,10 @@ class Flux(nn.Module):
         super().__init__()
         self.dtype = dtype
         self.params = p = config.params
-        self.in_channels = self.out_channels = p.in_channels
+        self.in_channels = p.in_channels
+        self.out_channels = p.in_channels if p.out_channels is None else p.out_channels
+        if not 0 < self.out_channels <= self.in_channels:
+            raise ValueError(f"out_channels {self.out_channels} must be in 1..in_channels ({self.in_channels})")
         self.loras: List = []
         preq = config.prequantized_flow
         q_emb = config.quantize_flow_embedder_layers and preq
@@ -339,6 +346,26 @@ class Flux(nn.Module):
         img_ids = torch.cat((img_ids, img_cond_seq_ids.to(device=img_ids.device, dtype=img_ids.dtype)), 1)
         return img, img_ids, Lc
 
+    def _with_channels(self, img, img_cond, img_cond_seq):
+        """FLUX.1 Fill / Depth / Canny: the conditioning channels ride behind the noisy channels of every token -> [B, Li, in_channels].
+        `img_cond` [B, Li, in_channels - out_channels] is required exactly when the two differ; no released model takes it together with
+        a Kontext `img_cond_seq` (the engine refuses the combination).  Checked before any device work."""
+        extra = self.in_channels - self.out_channels
+        if img_cond is None:
+            if extra:
+                raise ValueError(f"this model takes {extra} conditioning channels per token (in_channels {self.in_channels}, out_channels "
+                                 f"{self.out_channels}): pass img_cond [B, Li, {extra}]")
+            return img
+        if not extra:
+            raise ValueError(f"img_cond given, but this model has no conditioning channels (in_channels == out_channels == {self.in_channels})")
+        if img_cond_seq is not None:
+            raise ValueError("img_cond (channel conditioning) and img_cond_seq (a Kontext reference) cannot be combined")
+        if img.shape[2] != self.out_channels:
+            raise ValueError(f"img {tuple(img.shape)}: expected {self.out_channels} noisy channels per token")
+        if img_cond.ndim != 3 or tuple(img_cond.shape) != (img.shape[0], img.shape[1], extra):
+            raise ValueError(f"img_cond {tuple(img_cond.shape)} != {(img.shape[0], img.shape[1], extra)}")
+        return torch.cat((img.to(torch.bfloat16), img_cond.to(device=img.device, dtype=torch.bfloat16)), 2)
+
     # ---- batch-sharded calibration (SURVEY.md 8e-3) ------------------------------------------------------------------
     def enable_amax_exchange(self, reduce_fn=None):
         """Keep the F8Linear input scales of batch-sharded replicas IDENTICAL to those of the whole batch on one GPU: the reference
@@ -436,17 +463,20 @@ class Flux(nn.Module):
     @torch.inference_mode()
     def forward(self, img: Tensor, img_ids: Tensor, txt: Tensor, txt_ids: Tensor, timesteps: Tensor, y: Tensor,
                 guidance: Tensor | None = None, mode: Optional[int] = None, img_cond_seq: Tensor | None = None,
-                img_cond_seq_ids: Tensor | None = None) -> Tensor:
+                img_cond_seq_ids: Tensor | None = None, img_cond: Tensor | None = None) -> Tensor:
         """One denoise-step evaluation (reference flux_model.py:672-716).  mode=None picks what the reference would do:
         calibrating (unfused) while any F8Linear still has trials to record, fused once frozen.
         FLUX.1 Kontext: `img_cond_seq` [B, Lc, C] / `img_cond_seq_ids` [B, Lc, 3] (flux_pipeline.prepare_kontext_reference) run through every
-        block behind the noisy tokens; the prediction covers the `img.shape[1]` noisy tokens only."""
+        block behind the noisy tokens; the prediction covers the `img.shape[1]` noisy tokens only.
+        FLUX.1 Fill / Depth / Canny: `img_cond` [B, Li, in_channels - out_channels] (flux_pipeline.prepare_fill_conditioning /
+        prepare_control_conditioning) is appended to the channels of every token; the prediction is [B, Li, out_channels]."""
         if img.ndim != 3 or txt.ndim != 3:
             raise ValueError("Input img and txt tensors must have 3 dimensions.")
         if self.params.guidance_embed and guidance is None:
             raise ValueError("Didn't get guidance strength for guidance distilled model.")
         bf = lambda t: t.to(torch.bfloat16).contiguous()
         Li = img.shape[1]
+        img = self._with_channels(img, img_cond, img_cond_seq)
         img, img_ids, Lc = self._with_reference(img, img_ids, img_cond_seq, img_cond_seq_ids)
         img, txt, y, timesteps = bf(img), bf(txt), bf(y), bf(timesteps)
         guidance = bf(guidance) if guidance is not None else None
@@ -480,13 +510,16 @@ class Flux(nn.Module):
     @torch.inference_mode()
     def denoise(self, img: Tensor, img_ids: Tensor, txt: Tensor, txt_ids: Tensor, y: Tensor, timesteps: List[float],
                 guidance: float = 3.5, use_graph: bool = True, img_cond_seq: Tensor | None = None,
-                img_cond_seq_ids: Tensor | None = None) -> Tensor:
+                img_cond_seq_ids: Tensor | None = None, img_cond: Tensor | None = None) -> Tensor:
         """The Euler loop of FluxPipeline.generate (reference flux_pipeline.py:619-651) run natively: calibrating
         steps unfused, every later step one replay of a captured hipGraph.  Returns the final latent tokens.
         FLUX.1 Kontext: with `img_cond_seq` / `img_cond_seq_ids` the reference tokens join every step's forward and are never stepped; the
-        return value is the `img.shape[1]` noisy tokens only."""
+        return value is the `img.shape[1]` noisy tokens only.
+        FLUX.1 Fill / Depth / Canny: `img_cond` [B, Li, in_channels - out_channels] joins every step's forward as further channels of each
+        token and is never stepped; the return value is the stepped [B, Li, out_channels] tokens."""
         bf = lambda t: t.to(torch.bfloat16).contiguous()
         kontext = img_cond_seq is not None or img_cond_seq_ids is not None
+        stream = self._with_channels(img, img_cond, img_cond_seq) if img.shape[0] <= self.MAX_ENGINE_BATCH else None
         if img.shape[0] > self.MAX_ENGINE_BATCH:
             # the engine takes at most 32 samples per pass (workspace / modulation-table size); the reference has no num_images limit, so
             # larger batches run as consecutive passes (samples never interact).  EQUAL passes: the engine re-allocates its workspace and
@@ -503,12 +536,14 @@ class Flux(nn.Module):
                 pad = per - (sl.stop - sl.start)  # a short last pass is padded with copies of its last sample (same B -> same graph)
                 pick = lambda t: torch.cat([t[sl], t[sl.stop - 1:sl.stop].expand(pad, *t.shape[1:])], 0) if pad else t[sl]
                 cond = dict(img_cond_seq=pick(img_cond_seq), img_cond_seq_ids=pick(img_cond_seq_ids)) if kontext else {}
+                if img_cond is not None:
+                    cond["img_cond"] = pick(img_cond)
                 o = self.denoise(pick(img), pick(img_ids), pick(txt), pick(txt_ids), pick(y), timesteps, guidance=guidance, use_graph=use_graph,
                                  **cond)
                 outs.append(o[:per - pad])
             return torch.cat(outs, 0)
         Li = img.shape[1]
-        img, img_ids, Lc = self._with_reference(img, img_ids, img_cond_seq, img_cond_seq_ids)
+        img, img_ids, Lc = self._with_reference(stream, img_ids, img_cond_seq, img_cond_seq_ids)
         img = bf(img).clone()
         txt, y = bf(txt), bf(y)
         self._ensure_engine(img.device)
@@ -521,6 +556,8 @@ class Flux(nn.Module):
                       len(timesteps) - 1, C.byref(t_io), int(use_graph), ops._stream())
             if trial is not None:
                 self._advance_calibration(t_io.value)
+        if self.in_channels != self.out_channels:
+            return img[..., :self.out_channels].contiguous()
         return img[:, :Li].contiguous() if Lc else img
 
     @classmethod

@@ -182,6 +182,25 @@ def load_config_from_path(path: str) -> ModelSpec:
     return ModelSpec(**json.loads(path_path.read_text()))
 
 
+_CHANNEL_CONFIGS = {(64, 64): "config-dev-mi355x.json (or the schnell one)", (384, 64): "config-fill-dev-mi355x.json",
+                    (128, 64): "config-depth-dev-mi355x.json"}
+
+
+def _check_channels(config: ModelSpec, state_dict) -> None:
+    """A checkpoint whose img_in / final_layer widths disagree with the config (a FLUX.1 Fill or Depth / Canny checkpoint under the
+    text-to-image config, or the reverse) names the config to use instead of failing on a bare shape mismatch."""
+    w_in, w_out = state_dict.get("img_in.weight"), state_dict.get("final_layer.linear.weight")
+    if w_in is None or w_out is None or w_in.ndim != 2 or w_out.ndim != 2:
+        return
+    p = config.params
+    have = (int(w_in.shape[1]), int(w_out.shape[0]))
+    want = (p.in_channels, p.in_channels if p.out_channels is None else p.out_channels)
+    if have != want:
+        hint = _CHANNEL_CONFIGS.get(have)
+        raise ValueError(f"the checkpoint has in_channels {have[0]} / out_channels {have[1]}, the config {want[0]} / {want[1]}"
+                         + (f": load it with configs/{hint}" if hint else ""))
+
+
 def load_flow_model(config: ModelSpec, state_dict=None) -> Flux:
     """reference util.py:240-256.  `state_dict` lets tests / the bench inject a synthetic BFL checkpoint."""
     dtype = into_dtype(config.flow_dtype)          # what callers see (Flux.dtype: forward() returns this)
@@ -195,6 +214,7 @@ def load_flow_model(config: ModelSpec, state_dict=None) -> Flux:
 
         state_dict = load_sft(config.ckpt_path, device="cpu")
     if state_dict is not None:
+        _check_channels(config, state_dict)
         model.load_state_dict(state_dict, strict=False, assign=True)
         if not config.prequantized_flow:
             model.type(pdtype)

@@ -363,7 +363,10 @@ typedef struct fluxmi_model_desc {
  *                       txt_mod.lin, txt_attn.qkv, txt_attn.proj, txt_mlp.0, txt_mlp.2
  *   per single block i: modulation.lin, linear1, linear2
  *   final_layer.adaLN_modulation.1, final_layer.linear
- * `norm_scales`: bf16 [128] pointers, per double block: img q, img k, txt q, txt k; per single block: q, k. */
+ * `norm_scales`: bf16 [128] pointers, per double block: img q, img k, txt q, txt k; per single block: q, k.
+ * Channels: C_in = desc->in_channels is img_in's K, the width of the image stream; C_out = final_layer.linear's N is what the model predicts.
+ * create requires C_out <= C_in, both multiples of 8.  C_out < C_in (FLUX.1 Fill [dev]: 384 / 64, Depth / Canny [dev]: 128 / 64): the trailing
+ * C_in - C_out channels of every image row are step-invariant conditioning that img_in reads and the Euler update never writes. */
 typedef struct fluxmi_engine fluxmi_engine_t;
 int fluxmi_engine_num_linears(const fluxmi_model_desc_t* desc);
 int fluxmi_engine_create(const fluxmi_model_desc_t* desc, const fluxmi_linear_t* linears, int n_linears,
@@ -388,13 +391,15 @@ int fluxmi_engine_prepare(fluxmi_engine_t* e, int B, int Li, int Lt, const void*
  * prepare with Lc > 0, fluxmi_engine_forward / fluxmi_engine_denoise take img as [B, Li+Lc, in_channels]; forward writes pred as
  * [B, Li, in_channels] (the reference rows run through every block, only the leading Li rows are predicted); denoise steps rows [0, Li) of
  * each sample in place and leaves the reference rows bit-for-bit as they were.  The split (Li, Lc) is part of the workspace key: another
- * split of the same Li+Lc re-allocates and re-captures the step graph. */
+ * split of the same Li+Lc re-allocates and re-captures the step graph.  Lc > 0 is refused on a model with C_in != C_out (see create). */
 int fluxmi_engine_prepare_cond(fluxmi_engine_t* e, int B, int Li, int Lc, int Lt, const void* img_ids, const void* txt_ids, void* stream);
 /* one Flux.forward (flux_model.py:672-716).  mode 0 = calibrating/unfused (advances the F8Linear trial state
- * machine exactly like the reference's first 13 calls), 1 = frozen/fused.  pred: bf16 [B,Li,in_channels]. */
+ * machine exactly like the reference's first 13 calls), 1 = frozen/fused.  img: bf16 [B, Li(+Lc), C_in], the conditioning channels (if any)
+ * behind the noisy ones of every row; pred: bf16 [B, Li, C_out]. */
 int fluxmi_engine_forward(fluxmi_engine_t* e, const void* img, const void* txt, const void* y, const void* timesteps,
                           const void* guidance, void* pred, int mode, int trial_index, void* stream);
-/* the denoise loop (flux_pipeline.py:619-651): timesteps_host[n_steps+1]; img updated in place.
+/* the denoise loop (flux_pipeline.py:619-651): timesteps_host[n_steps+1]; img bf16 [B, Li(+Lc), C_in] updated in place: channels
+ * [0, C_out) of the predicted rows are stepped, the conditioning channels [C_out, C_in) (and Kontext's reference rows) stay bit for bit.
  * Steps with trial_index <= num_trials run unfused; the remainder replays ONE captured hipGraph per step. */
 int fluxmi_engine_denoise(fluxmi_engine_t* e, void* img, const void* txt, const void* y, float guidance,
                           const double* timesteps_host, int n_steps, int* trial_index_inout, int use_graph, void* stream);
@@ -423,7 +428,7 @@ int fluxmi_engine_get_buffer(fluxmi_engine_t* e, const char* name, void** ptr, l
  * on the engine's own workspace: the residual stream is buffer "x" ([B, Lt+Li, H], txt rows first), the modulation vectors are read
  * from buffer "mod" (per batch row: double block i at [i*12H, +12H) = img shift1|scale1|gate1|shift2|scale2|gate2 then txt, single
  * block i at depth*12H + i*3H = shift|scale|gate, LastLayer.adaLN at depth*12H + single*3H = shift|scale).  kind 2 = LastLayer (index 0;
- * stages 0 LN+modulate of the img rows of x -> "fin", 1 bf16 Linear -> buffer "pred_s" [B, Li, in_channels]; flux_model.py:499-503).
+ * stages 0 LN+modulate of the img rows of x -> "fin", 1 bf16 Linear -> buffer "pred_s" [B, Li, C_out = out_channels]; flux_model.py:499-503).
  * mode 1 = fused kernels, 2 = unfused with frozen scales.
  * copy_buffer: device-to-device copy between a named workspace buffer and a caller buffer (to_engine != 0 writes the workspace).  The fp8
  * activation buffers "a8", "attn8", "h8", "cat8" are exchanged as PLAIN rows.  Inside the engine each one is in the layout of its last

@@ -3,8 +3,9 @@
 Same two POST endpoints, request fields, defaults and status codes:
   /generate  GenerateArgs{prompt, width=720, height=1024, num_steps=24, guidance=3.5, seed=random in (0, MAX_RAND), strength=1.0,
              init_image=None (path or base64), reference_image=None (FLUX.1 Kontext edit; path or base64, passed on only when set),
-             mask_image=None (FLUX.1 Fill: white = regenerate), control_image=None (FLUX.1 Depth / Canny: the depth or edge map) -- path or
-             base64, each passed on only when set}  ->  image/jpeg stream of FluxPipeline.generate(**args)          (reference api.py:54-86)
+             mask_image=None (FLUX.1 Fill: white = regenerate), control_image=None (FLUX.1 Depth / Canny: the depth or edge map),
+             redux_image=None (FLUX.1 Redux image prompt) -- path or base64, each passed on only when set}
+             ->  image/jpeg stream of FluxPipeline.generate(**args)                                               (reference api.py:54-86)
   /lora      LoraArgs{scale=1.0, path, name, action="load"|"unload"}  ->  {"status": "success"} | 400 invalid action | 500 with the
              exception text; unload uses `name` when given, else `path`                                         (reference api.py:89-122)
 The app holds one pipeline in `app.state.model`; FastAPI runs these sync handlers on its threadpool, and the pipeline serialises
@@ -46,6 +47,7 @@ class GenerateArgs(BaseModel):
     reference_image: Optional[str] = None  # FLUX.1 Kontext instruction editing: the image to edit (path or base64, like init_image)
     mask_image: Optional[str] = None  # FLUX.1 Fill inpainting / outpainting: the mask of init_image to regenerate (white), path or base64
     control_image: Optional[str] = None  # FLUX.1 Depth / Canny: the depth map or edge map to follow, path or base64
+    redux_image: Optional[str] = None  # FLUX.1 Redux: an image prompt (needs config redux_path / siglip_path), path or base64
 
 
 app = FastAPI(title="fluxmi")
@@ -55,9 +57,9 @@ app = FastAPI(title="fluxmi")
 def generate(args: GenerateArgs):
     """JPEG bytes of one image; `init_image` + `strength` select img2img (flux_pipeline.py:399-420,459-523 of the reference);
     `reference_image` selects a FLUX.1 Kontext edit of that image, `mask_image` a FLUX.1 Fill inpainting of `init_image`, `control_image` a
-    FLUX.1 Depth / Canny generation.  Without them the call is exactly the reference's."""
+    FLUX.1 Depth / Canny generation, `redux_image` a FLUX.1 Redux image prompt.  Without them the call is exactly the reference's."""
     kwargs = args.model_dump()
-    for k in ("reference_image", "mask_image", "control_image"):
+    for k in ("reference_image", "mask_image", "control_image", "redux_image"):
         if kwargs.get(k) is None:
             kwargs.pop(k, None)
     result = app.state.model.generate(**kwargs)

@@ -449,6 +449,14 @@ int fluxmi_text_attention(const void* q, const void* k, long long ld_qk, const v
                           const float* rel_bias, int bias_ld, const void* v_bias, float scale, int causal, int L, int Lp, int H, void* stream) {
   return fluxmi_k_text_attention(q, k, ld_qk, vt, ld_vt, out, ld_out, rel_bias, bias_ld, v_bias, scale, causal, L, Lp, H, (hipStream_t)stream);
 }
+int fluxmi_vision_attention(const void* q, const void* k, long long ld_qk, long long bs_qk, const void* vt, long long ld_vt, long long bs_vt,
+                            void* out, long long ld_out, long long bs_out, const void* v_bias, float scale, int head_dim, int L, int Lp, int H, int B,
+                            void* stream) {
+  return fluxmi_k_vision_attention(q, k, ld_qk, bs_qk, vt, ld_vt, bs_vt, out, ld_out, bs_out, v_bias, scale, head_dim, L, Lp, H, B, (hipStream_t)stream);
+}
+int fluxmi_patchify(const void* pix, void* out, int B, int C, int H, int W, int patch, int grid, int Kp, void* stream) {
+  return fluxmi_k_patchify(pix, out, B, C, H, W, patch, grid, Kp, (hipStream_t)stream);
+}
 int fluxmi_build_quant_lut(const float* scale, int fmt, int act, void* lut, void* stream) {
   return fluxmi_k_build_qlut(scale, fmt, act, lut, (hipStream_t)stream);
 }

@@ -10,7 +10,9 @@ get_noise / prepare / unpack / vae_decode / into_bytes / load_init_image_if_need
 SURVEY.md §8f rows 1-2 are built around it: the native VAE decoder (latents -> JPEG) and encoder (img2img: `init_image`, `strength`),
 and the text conditioning (flux_emphasis.py prompt weighting over the native T5 / CLIP encoders of modules/conditioner.py) when
 `config.text_enc_path` / `clip_path` point at local HF-layout directories.  Without them `generate()` takes the conditioning as
-pre-computed embeddings (`prompt={"txt": [B,Lt,4096], "vec": [B,768]}`); it returns latents when no autoencoder is attached.  CPU-offload flags are accepted
+pre-computed embeddings (`prompt={"txt": [B,Lt,4096], "vec": [B,768]}`); it returns latents when no autoencoder is attached.
+FLUX.1 Redux image prompts (`redux_image`) run through the native SigLIP + projector of modules/image_embedders.py when
+`config.redux_path` / `siglip_path` point at local files.  CPU-offload flags are accepted
 and ignored (meaningless with 288 GB of HBM).  `compile()` keeps the reference's warm-up/calibration protocol
 (flux_pipeline.py:197-212) but never calls torch.compile: the fused kernels + hipGraph replace it.
 """
@@ -56,7 +58,7 @@ def kontext_reference_ids(bs: int, h_l: int, w_l: int, device=None, dtype=torch.
 class FluxPipeline:
     def __init__(self, name: str, offload: bool = False, clip=None, t5=None, model=None, ae=None,
                  dtype: torch.dtype = torch.float16, verbose: bool = False, flux_device="cuda:0", ae_device="cuda:1",
-                 clip_device="cuda:1", t5_device="cuda:1", config: ModelSpec = None, debug: bool = False):
+                 clip_device="cuda:1", t5_device="cuda:1", config: ModelSpec = None, debug: bool = False, redux=None):
         if config is None:
             raise ValueError("ModelSpec config is required!")
         self.debug, self.name, self.verbose, self.offload = debug, name, verbose, offload
@@ -64,6 +66,7 @@ class FluxPipeline:
         self.device_ae, self.device_clip, self.device_t5 = into_device(ae_device), into_device(clip_device), into_device(t5_device)
         self.dtype = into_dtype(dtype)
         self.clip, self.t5, self.model, self.ae = clip, t5, model, ae
+        self.redux = redux  # FLUX.1 Redux image encoder (modules/image_embedders.ReduxImageEncoder) or None
         self.rng = torch.Generator(device="cpu")
         self.ae_dtype = torch.bfloat16
         self.config = config
@@ -309,6 +312,30 @@ class FluxPipeline:
         cond = self.pack(self._encode_sampled(x, generator))
         return cond.to(self.device_flux).repeat(num_images, 1, 1).contiguous()
 
+    # ---- FLUX.1 Redux image prompts ------------------------------------------------------------------------------------------------------
+    def _require_redux(self):
+        if self.redux is None:
+            raise ValueError("fluxmi: redux_image needs the FLUX.1 Redux image encoder: set config.redux_path (flux1-redux-dev.safetensors) and "
+                             "config.siglip_path (the SigLIP vision tower, a local HF directory or .safetensors file)")
+
+    @staticmethod
+    def _redux_list(redux_image) -> list:
+        return list(redux_image) if isinstance(redux_image, (list, tuple)) else [redux_image]
+
+    @torch.inference_mode()
+    def prepare_redux_tokens(self, images, num_images: int = 1, txt: Optional[torch.Tensor] = None):
+        """FLUX.1 Redux [dev]: steps 1-4 of modules/image_embedders.py's docstring.  `images`: one image in any form `init_image` takes,
+        or a list of them (729 tokens per image, in list order).  Returns the Redux tokens [num_images, 729 n, 4096] in the flow dtype on
+        the flow device; with `txt` [num_images, Lt5, 4096] (the T5 states), returns (txt, txt_ids) with the tokens appended behind the T5
+        tokens and txt_ids = zeros [num_images, Lt5 + 729 n, 3], as BFL's prepare_redux builds them."""
+        self._require_redux()
+        tok = self.redux(self._redux_list(images)).to(device=self.device_flux, dtype=torch.bfloat16)
+        tok = tok.reshape(1, -1, tok.shape[-1]).to(self.dtype).repeat(num_images, 1, 1)
+        if txt is None:
+            return tok
+        txt = torch.cat((txt, tok.to(txt)), dim=-2)
+        return txt, torch.zeros(txt.shape[0], txt.shape[1], 3, device=txt.device, dtype=txt.dtype)
+
     # ---- packing / ids (reference flux_pipeline.py:267-292, 440-448) ----------------------------------------------
     @staticmethod
     def pack(img: torch.Tensor) -> torch.Tensor:
@@ -414,6 +441,9 @@ class FluxPipeline:
             self.generate(**{**kw, "num_steps": 1})  # 13th call: freezes the input scales
         if world > 1:
             self.model.enable_amax_exchange(False)
+        if self.redux is not None:
+            # one Redux request on the frozen scales, so that the encoder and the longer text stream have run before serving
+            self.generate(**{**kw, "num_steps": 1, "redux_image": np.full((384, 384, 3), 128, dtype=np.uint8)})
 
     def _warmup_conditioning(self, height: int, width: int) -> dict:
         """compile()'s conditioning for a Fill / Depth / Canny model, so that img_in sees its real width and (fp8 embedders) its input scale
@@ -439,7 +469,7 @@ class FluxPipeline:
                  seed: int | None = None, init_image=None, strength: float = 1.0, silent: bool = False, num_images: int = 1,
                  return_seed: bool = False, jpeg_quality: int = 99, output_type: str = "jpeg", noise: Optional[torch.Tensor] = None,
                  use_graph: bool = True, reference_image=None, mask_image=None, control_image=None,
-                 img_cond: Optional[torch.Tensor] = None):
+                 img_cond: Optional[torch.Tensor] = None, redux_image=None):
         """`reference_image` (FLUX.1 Kontext [dev] instruction editing): an image the prompt describes an edit of, in any form `init_image`
         takes; see prepare_kontext_reference.  Composes with `init_image` / `strength` unchanged.
         FLUX.1 Fill [dev] (a model with 320 conditioning channels): `init_image` is the image to inpaint and `mask_image` (white =
@@ -447,7 +477,12 @@ class FluxPipeline:
         strength < 1 also blends the VAE latents of `init_image` into the start as img2img does.  BFL recommends guidance 30, ~50 steps.
         FLUX.1 Depth / Canny [dev] (64 conditioning channels): `control_image` (the depth map or edge map) is required; see
         prepare_control_conditioning.  Both take any form `init_image` takes.  `img_cond`: the conditioning tokens [1 or num_images, Li,
-        in_channels - out_channels] already prepared (instead of `mask_image` / `control_image`).  A text-to-image model refuses all three."""
+        in_channels - out_channels] already prepared (instead of `mask_image` / `control_image`).  A text-to-image model refuses all three.
+        `redux_image` (FLUX.1 Redux [dev] image prompt; needs config.redux_path / siglip_path): an image in any form `init_image` takes, or a
+        list; 729 SigLIP-derived tokens per image are appended to the T5 tokens (see prepare_redux_tokens).  It only lengthens the text
+        stream, so it composes with everything above."""
+        if redux_image is not None:
+            self._require_redux()
         kind = self.conditioning_kind()
         if kind is None and (mask_image is not None or control_image is not None or img_cond is not None):
             raise ValueError("fluxmi: mask_image / control_image / img_cond need a FLUX.1 Fill or Depth / Canny model (this one has no "
@@ -488,6 +523,15 @@ class FluxPipeline:
                                                   generator=generator, num_images=num_images, noise=noise)
         img, img_ids, vec, txt, txt_ids = map(lambda x: x.contiguous(), self.prepare(noise, prompt))
         num_images = img.shape[0]  # a list prompt with num_images == 1 sizes the batch (prepare)
+        if redux_image is not None:
+            if world > 1 and rank != 0:
+                # the broadcast below carries rank 0's tokens; this rank only needs the same text length
+                n_tok = len(self._redux_list(redux_image)) * self.redux.num_tokens
+                txt = torch.cat((txt, txt.new_zeros(txt.shape[0], n_tok, txt.shape[2])), dim=-2)
+                txt_ids = txt_ids.new_zeros(txt.shape[0], txt.shape[1], 3)
+            else:
+                txt, txt_ids = self.prepare_redux_tokens(redux_image, num_images=num_images, txt=txt)
+            txt, txt_ids = txt.contiguous(), txt_ids.contiguous()
         cond = {}
         if reference_image is not None:
             # drawn from the request's generator after the noise (the order is part of what a seed reproduces)
@@ -579,6 +623,7 @@ class FluxPipeline:
         with torch.inference_mode():
             models = load_models_from_config(config, state_dict=state_dict, ae_state_dict=ae_state_dict, clip_kwargs=clip_kwargs,
                                              t5_kwargs=t5_kwargs)
+            redux = models.redux
             config = models.config
             flux_device = into_device(config.flux_device)
             # every shipped reference JSON says flow_dtype float16: accepted -- the engine computes in bf16 and the pipeline keeps the
@@ -594,4 +639,4 @@ class FluxPipeline:
                 flow_model.eval().requires_grad_(False)
         return cls(name=config.version, clip=models.clip, t5=models.t5, model=flow_model, ae=models.ae, dtype=flux_dtype, verbose=False,
                    flux_device=flux_device, ae_device=into_device(config.ae_device), clip_device=into_device(config.text_enc_device),
-                   t5_device=into_device(config.text_enc_device), config=config, debug=debug)
+                   t5_device=into_device(config.text_enc_device), config=config, debug=debug, redux=redux)

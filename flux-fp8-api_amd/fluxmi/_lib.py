@@ -92,6 +92,8 @@ _SIGS = {
     "fluxmi_row_norm": ([vp, vp, vp, vp, i32, i32, i64, i64, C.c_float, i32, vp], i32),
     "fluxmi_act_mul": ([vp, vp, i32, i32, i64, i64, i32, vp], i32),
     "fluxmi_text_attention": ([vp, vp, i64, vp, i64, vp, i64, vp, i32, vp, C.c_float, i32, i32, i32, i32, vp], i32),
+    "fluxmi_vision_attention": ([vp, vp, i64, i64, vp, i64, i64, vp, i64, i64, vp, C.c_float, i32, i32, i32, i32, i32, vp], i32),
+    "fluxmi_patchify": ([vp, vp, i32, i32, i32, i32, i32, i32, i32, vp], i32),
     "fluxmi_attention": ([vp, vp, vp, vp, i64, i32, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp], i32),
     "fluxmi_attention_debug_buffer": ([vp], i32),
     "fluxmi_attention_plan": ([i32, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(C.c_ulonglong)], i32),

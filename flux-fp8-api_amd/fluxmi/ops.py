@@ -417,3 +417,39 @@ def text_attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, L: int, h
          _p(rel_bias) if rel_bias is not None else None, rel_bias.shape[1] if rel_bias is not None else 0,
          _p(v_bias) if v_bias is not None else None, float(scale), int(causal), int(L), Lp, heads, _stream())
     return out
+
+
+# ---- vision-encoder pieces (bf16) --------------------------------------------------------------------------------------------
+def vision_attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, L: int, heads: int, head_dim: int, scale: float,
+                     v_bias: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """q, k [B, Lp, >= heads*head_dim] (views with the same strides), vt [B, heads*head_dim, Lp] -> out [B, Lp, heads*head_dim] (rows < L
+    written): non-causal self-attention of B sequences in one launch, head width head_dim = 64 or 96 (zero-padded heads; see include/fluxmi.h)."""
+    _req(q, torch.bfloat16, "q")
+    _req(k, torch.bfloat16, "k")
+    _req(vt, torch.bfloat16, "vt")
+    B, Lp = q.shape[0], q.shape[1]
+    if q.stride() != k.stride() or q.stride(2) != 1 or vt.stride(2) != 1 or tuple(k.shape[:2]) != (B, Lp):
+        raise ValueError("vision_attention: q and k must share shape and strides; innermost strides must be 1")
+    if vt.shape[0] != B or vt.shape[1] < heads * head_dim or vt.shape[2] < Lp:
+        raise ValueError(f"vision_attention: vt must be [B, heads*head_dim, >= Lp], got {tuple(vt.shape)}")
+    if q.shape[2] < heads * head_dim:
+        raise ValueError(f"vision_attention: q must have >= heads*head_dim = {heads * head_dim} columns, got {q.shape[2]}")
+    if out is None:
+        out = torch.zeros((B, Lp, heads * head_dim), dtype=torch.bfloat16, device=q.device)
+    if v_bias is not None:
+        _req(v_bias, torch.bfloat16, "v_bias")
+        if v_bias.numel() < heads * head_dim:
+            raise ValueError("vision_attention: v_bias needs heads*head_dim entries")
+    call("fluxmi_vision_attention", _p(q), _p(k), q.stride(1), q.stride(0), _p(vt), vt.stride(1), vt.stride(0), _p(out), out.stride(1),
+         out.stride(0), _p(v_bias), float(scale), int(head_dim), int(L), Lp, int(heads), B, _stream())
+    return out
+
+
+def patchify(pix: torch.Tensor, patch: int, grid: int, k_pad: int) -> torch.Tensor:
+    """pix bf16 [B, C, H, W] -> patch rows [B*grid*grid, k_pad], column order (c, ky, kx), zero past C*patch*patch (fluxmi_patchify)."""
+    _req(pix, torch.bfloat16, "pix")
+    pix = pix.contiguous()
+    B, Cc, H, W = pix.shape
+    out = torch.empty((B * grid * grid, k_pad), dtype=torch.bfloat16, device=pix.device)
+    call("fluxmi_patchify", _p(pix), _p(out), B, Cc, H, W, int(patch), int(grid), int(k_pad), _stream())
+    return out

@@ -1,0 +1,356 @@
+"""Image conditioning on MI355X -- FLUX.1 Redux [dev]: BFL's `ReduxImageEncoder` (src/flux/modules/image_embedders.py) over a native SigLIP.
+
+What Redux computes (BFL `ReduxImageEncoder.__call__` + `prepare_redux`, src/flux/sampling.py), kept here in one place:
+  1. preprocessing = transformers' SiglipImageProcessor of google/siglip-so400m-patch14-384: convert to RGB, PIL bicubic resize to
+     384 x 384, x / 255 (in float64, then float32), normalise with mean = std = 0.5 -> pixel_values fp32 [1, 3, 384, 384], cast to bf16;
+  2. SiglipVisionModel(...).last_hidden_state in bf16: a stride-14 "valid" Conv2d(3, 1152, 14) (a 27 x 27 grid = 729 tokens; the last 6
+     pixel rows and columns are never read) + position embedding [729, 1152]; 27 pre-LN encoder layers (LayerNorm eps 1e-6 with bias;
+     q/k/v/out projections with bias, 16 heads of 72, non-causal, scale 72^-1/2; LayerNorm; fc1 1152 -> 4304, gelu_pytorch_tanh, fc2
+     4304 -> 1152; both residual adds in bf16); post_layernorm.  The pooling head (vision_model.head.*) is not used;
+  3. projector: redux_down(silu(redux_up(x))), Linear(1152, 12288) and Linear(12288, 4096) with bias, bf16 -> [1, 729, 4096] bf16;
+  4. txt = cat(t5_embedding, redux_tokens, dim=-2), repeated over the batch; txt_ids = zeros(bs, Lt, 3); vec (CLIP) unchanged.  The flow
+     model is plain Flux-dev / Flux-schnell; schedule, noise draw and guidance do not change (FluxPipeline.prepare_redux_tokens).
+
+The encoder runs on libfluxmi: every Linear on the bf16 MFMA GEMM (residual adds and the position embedding in its gate*y+x epilogue
+with a ones gate), LayerNorm = `fluxmi_row_norm`, gelu_tanh / silu = `fluxmi_act`, attention = `fluxmi_vision_attention` (all images of a
+call in one launch), the patch embedding = `fluxmi_patchify` + the GEMM.  So that every GEMM takes a tiled config, weights are padded
+once at load time (exact: the pads are zeros):
+  * heads of 72 -> 96: q / k / v weight rows and biases per head, out_proj's columns per head.  Zero q / k columns add nothing to q.k,
+    zero V^T rows and v_bias entries give zero output columns, and out_proj's zero columns drop them;
+  * fc1 rows / bias and fc2 columns to a multiple of 256 (4304 -> 4352): gelu_tanh(0) = 0;
+  * the patch matrix's K from 3 * 14 * 14 = 588 to 640 (1280 bytes per row).
+q | k run as one GEMM; V^T comes from the v-projection GEMM with its operands swapped (the text encoders' scheme), its bias added after
+P V (rows of P sum to 1).  A sequence is padded to Lp = 768 rows (729 -> a multiple of 256: the GEMM tiles' and V^T's column count).
+"""
+from __future__ import annotations
+
+import io
+import json
+import os
+from typing import Optional
+
+import numpy as np
+import torch
+from torch import Tensor, nn
+
+from modules.conditioner import _bf, _Cache, _lin, _read_dir_weights, _Weight
+
+# google/siglip-so400m-patch14-384 (the vision tower FLUX.1 Redux was trained on); keys left out of a config mean SiglipVisionConfig's
+# defaults, as transformers reads them
+SIGLIP_SO400M_384 = dict(hidden_size=1152, intermediate_size=4304, num_hidden_layers=27, num_attention_heads=16, num_channels=3,
+                         image_size=384, patch_size=14, hidden_act="gelu_pytorch_tanh", layer_norm_eps=1e-6)
+_SIGLIP_DEFAULTS = dict(hidden_size=768, intermediate_size=3072, num_hidden_layers=12, num_attention_heads=12, num_channels=3,
+                        image_size=224, patch_size=16, hidden_act="gelu_pytorch_tanh", layer_norm_eps=1e-6)
+
+
+def _round_up(n: int, m: int) -> int:
+    return (n + m - 1) // m * m
+
+
+def padded_head_dim(head_dim: int) -> int:
+    """the head width fluxmi_vision_attention runs a head of `head_dim` at (64 or 96; SigLIP-so400m's 72 -> 96)"""
+    if head_dim <= 64:
+        return 64
+    if head_dim <= 96:
+        return 96
+    raise ValueError(f"fluxmi: vision attention covers head_dim <= 96, got {head_dim}")
+
+
+def pad_heads(t: Tensor, heads: int, hd: int, hp: int, dim: int = 0) -> Tensor:
+    """rows (dim 0) or columns (dim 1) of H heads of hd -> H heads of hp, zero-filled per head"""
+    if dim == 0:
+        x = t.reshape(heads, hd, *t.shape[1:])
+        out = x.new_zeros((heads, hp) + tuple(x.shape[2:]))
+        out[:, :hd] = x
+        return out.reshape(heads * hp, *t.shape[1:])
+    x = t.reshape(t.shape[0], heads, hd)
+    out = x.new_zeros(t.shape[0], heads, hp)
+    out[:, :, :hd] = x
+    return out.reshape(t.shape[0], heads * hp)
+
+
+def unpad_heads(t: Tensor, heads: int, hd: int, hp: int, dim: int = 0) -> Tensor:
+    if dim == 0:
+        return t.reshape(heads, hp, *t.shape[1:])[:, :hd].reshape(heads * hd, *t.shape[1:])
+    return t.reshape(t.shape[0], heads, hp)[:, :, :hd].reshape(t.shape[0], heads * hd)
+
+
+def _pad_to(t: Tensor, n: int, dim: int = 0) -> Tensor:
+    if t.shape[dim] == n:
+        return t
+    shape = list(t.shape)
+    shape[dim] = n
+    out = t.new_zeros(shape)
+    out.narrow(dim, 0, t.shape[dim]).copy_(t)
+    return out
+
+
+def _linear_groups(rows_a, w, out_rows, bias=None, resid_rows=None, ones=None):
+    """One GEMM launch over groups (<= 16 per launch): out_rows[i] = rows_a[i] . w^T (+ bias) (+ resid_rows[i], through the gate*y+x
+    epilogue with a ones gate).  Each item is a 2-D view with unit column stride."""
+    from fluxmi import _lib, ops
+
+    N, K = w.shape
+    epi = _lib.EPI_BF16 if resid_rows is None else _lib.EPI_GATE_RESID
+    for i0 in range(0, len(rows_a), 16):
+        gs = []
+        for i in range(i0, min(i0 + 16, len(rows_a))):
+            a, c = rows_a[i], out_rows[i]
+            r = None if resid_rows is None else resid_rows[i]
+            gs.append(ops.make_group(ops._p(a), ops._p(w), ops._p(bias), None, None, ops._p(c), a.shape[0], a.stride(0), c.stride(0),
+                                     gate=ops._p(ones), resid=ops._p(r), ldr=r.stride(0) if r is not None else 0))
+        ops.gemm_grouped(gs, N, K, False, _lib.E5M2, epi)
+
+
+# ---- SigLIP vision tower ------------------------------------------------------------------------------------------------------------
+class _SiglipVisionTransformer(nn.Module):
+    def __init__(self, c):
+        super().__init__()
+        D, Fd, C, P = c["hidden_size"], c["intermediate_size"], c["num_channels"], c["patch_size"]
+        self.embeddings = nn.Module()
+        self.embeddings.patch_embedding = nn.Conv2d(C, D, kernel_size=P, stride=P)
+        self.embeddings.position_embedding = _Weight((c["image_size"] // P) ** 2, D)
+        self.encoder = nn.Module()
+        self.encoder.layers = nn.ModuleList()
+        for _ in range(c["num_hidden_layers"]):
+            lay = nn.Module()
+            lay.self_attn = nn.Module()
+            for n in ("q_proj", "k_proj", "v_proj", "out_proj"):
+                setattr(lay.self_attn, n, _lin(D, D, True))
+            lay.layer_norm1, lay.layer_norm2 = nn.LayerNorm(D, eps=c["layer_norm_eps"]), nn.LayerNorm(D, eps=c["layer_norm_eps"])
+            lay.mlp = nn.Module()
+            lay.mlp.fc1, lay.mlp.fc2 = _lin(D, Fd, True), _lin(Fd, D, True)
+            self.encoder.layers.append(lay)
+        self.post_layernorm = nn.LayerNorm(D, eps=c["layer_norm_eps"])
+        self.requires_grad_(False)
+
+
+class SiglipVisionNative(nn.Module):
+    """State-dict keys of transformers' SiglipVisionModel: vision_model.embeddings.{patch_embedding, position_embedding},
+    vision_model.encoder.layers.{i}.{self_attn.{q,k,v,out}_proj, layer_norm1, layer_norm2, mlp.fc1, mlp.fc2}, vision_model.post_layernorm.
+    A full SiglipModel checkpoint loads too: text_model.*, logit_scale, logit_bias and the pooling head vision_model.head.* are ignored.
+    `config`: a SiglipVisionConfig dict, or a SiglipModel config.json (its `vision_config`); None = google/siglip-so400m-patch14-384."""
+
+    def __init__(self, config: Optional[dict] = None):
+        super().__init__()
+        c = dict(_SIGLIP_DEFAULTS)
+        if config is None:
+            c.update(SIGLIP_SO400M_384)
+        elif "vision_config" in config:
+            c.update(config.get("vision_config") or {})
+        else:
+            c.update(config)
+        if c["hidden_act"] not in ("gelu_pytorch_tanh", "gelu_new"):
+            raise ValueError(f"fluxmi: the native SigLIP covers gelu_pytorch_tanh MLPs, got {c['hidden_act']!r}")
+        D, H = c["hidden_size"], c["num_attention_heads"]
+        if D % H or D % 8:
+            raise ValueError(f"fluxmi: hidden_size {D} must be a multiple of the head count {H} and of 8")
+        self.cfg = c
+        self.head_dim = D // H
+        self.head_pad = padded_head_dim(self.head_dim)
+        self.grid = c["image_size"] // c["patch_size"]
+        self.num_tokens = self.grid ** 2
+        self.vision_model = _SiglipVisionTransformer(c)
+        self._cache = _Cache()
+
+    def load_state_dict(self, sd, strict=True, assign=False):
+        sd = {k: v for k, v in sd.items() if not k.startswith(("text_model.", "logit_scale", "logit_bias")) and not k.endswith("position_ids")}
+        # keys without the `vision_model.` prefix (how transformers 5.x saves a bare SiglipVisionModel) are accepted too
+        sd = {(k if k.startswith("vision_model.") else "vision_model." + k): v for k, v in sd.items()}
+        return super().load_state_dict({k: v for k, v in sd.items() if not k.startswith("vision_model.head.")}, strict=strict, assign=assign)
+
+    @property
+    def device(self):
+        return self.vision_model.post_layernorm.weight.device
+
+    @property
+    def seq_pad(self) -> int:
+        """rows a sequence is padded to: a multiple of 256 (the GEMM tile height; also V^T's column count, which the swapped v-projection
+        GEMM needs as a multiple of its 256-column tile)"""
+        return _round_up(self.num_tokens, 256)
+
+    @property
+    def mlp_pad(self) -> int:
+        return _round_up(self.cfg["intermediate_size"], 256)
+
+    @property
+    def patch_k(self) -> int:
+        c = self.cfg
+        return _round_up(c["num_channels"] * c["patch_size"] ** 2, 64)
+
+    def padded_weights(self, i) -> dict:
+        """bf16 weights of layer i (or i = "embed") as the kernels take them, built once (see the module docstring for the padding)"""
+        vm, ck = self.vision_model, self._cache
+        H, hd, hp = self.cfg["num_attention_heads"], self.head_dim, self.head_pad
+        if i == "embed":
+            pe = vm.embeddings.patch_embedding
+            return dict(
+                w=ck.get("patch_w", [pe.weight], lambda: _pad_to(_bf(pe.weight).reshape(pe.weight.shape[0], -1), self.patch_k, 1).contiguous()),
+                b=ck.get("patch_b", [pe.bias], lambda: _bf(pe.bias)),
+                pos=ck.get("pos", [vm.embeddings.position_embedding.weight], lambda: _bf(vm.embeddings.position_embedding.weight)))
+        lay = vm.encoder.layers[i]
+        sa, mlp = lay.self_attn, lay.mlp
+        ph = lambda t, dim=0: pad_heads(_bf(t), H, hd, hp, dim).contiguous()  # noqa: E731
+        p = dict(
+            wqk=ck.get(("wqk", i), [sa.q_proj.weight, sa.k_proj.weight], lambda: torch.cat([ph(sa.q_proj.weight), ph(sa.k_proj.weight)], 0)),
+            bqk=ck.get(("bqk", i), [sa.q_proj.bias, sa.k_proj.bias], lambda: torch.cat([ph(sa.q_proj.bias), ph(sa.k_proj.bias)], 0)),
+            wv=ck.get(("wv", i), [sa.v_proj.weight], lambda: ph(sa.v_proj.weight)),
+            bv=ck.get(("bv", i), [sa.v_proj.bias], lambda: ph(sa.v_proj.bias)),
+            wo=ck.get(("wo", i), [sa.out_proj.weight], lambda: ph(sa.out_proj.weight, 1)),
+            bo=ck.get(("bo", i), [sa.out_proj.bias], lambda: _bf(sa.out_proj.bias)),
+            w1=ck.get(("w1", i), [mlp.fc1.weight], lambda: _pad_to(_bf(mlp.fc1.weight), self.mlp_pad, 0).contiguous()),
+            b1=ck.get(("b1", i), [mlp.fc1.bias], lambda: _pad_to(_bf(mlp.fc1.bias), self.mlp_pad, 0).contiguous()),
+            w2=ck.get(("w2", i), [mlp.fc2.weight], lambda: _pad_to(_bf(mlp.fc2.weight), self.mlp_pad, 1).contiguous()),
+            b2=ck.get(("b2", i), [mlp.fc2.bias], lambda: _bf(mlp.fc2.bias)))
+        for name, t in (("g1", lay.layer_norm1.weight), ("e1", lay.layer_norm1.bias), ("g2", lay.layer_norm2.weight), ("e2", lay.layer_norm2.bias)):
+            p[name] = ck.get((name, i), [t], lambda t=t: _bf(t))
+        return p
+
+    @torch.inference_mode()
+    def forward(self, pixel_values: Tensor, **_) -> dict:
+        """pixel_values [B, C, image_size, image_size] -> {"last_hidden_state": bf16 [B, grid^2, hidden]}"""
+        from fluxmi import _lib, ops
+
+        dev = self.device
+        if dev.type != "cuda":
+            raise RuntimeError("fluxmi: the SigLIP vision encoder needs the GPU (libfluxmi has no CPU path)")
+        c, ck, vm = self.cfg, self._cache, self.vision_model
+        D, H, eps, P, S = c["hidden_size"], c["num_attention_heads"], c["layer_norm_eps"], c["patch_size"], c["image_size"]
+        pix = pixel_values.to(device=dev, dtype=torch.bfloat16)
+        if pix.dim() != 4 or pix.shape[1] != c["num_channels"] or tuple(pix.shape[-2:]) != (S, S):
+            raise ValueError(f"fluxmi: SigLIP takes pixel_values [B, {c['num_channels']}, {S}, {S}], got {tuple(pix.shape)}")
+        B, L, Lp, hp = pix.shape[0], self.num_tokens, self.seq_pad, self.head_pad
+        ones = ck.get("ones", [vm.post_layernorm.weight], lambda: torch.ones(D, dtype=torch.bfloat16, device=dev))
+        # patch embedding + position embedding: bf16(pos + bf16(conv)), written into the first L rows of each image's Lp-row slab
+        e = self.padded_weights("embed")
+        patches = ops.patchify(pix, P, self.grid, self.patch_k)
+        x = torch.zeros(B, Lp, D, dtype=torch.bfloat16, device=dev)
+        _linear_groups([patches[b * L:(b + 1) * L] for b in range(B)], e["w"], [x[b, :L] for b in range(B)], e["b"],
+                       resid_rows=[e["pos"]] * B, ones=ones)
+        x = x.view(B * Lp, D)
+        for i in range(len(vm.encoder.layers)):
+            p = self.padded_weights(i)
+            h = ops.row_norm(x, p["g1"], p["e1"], eps=eps, rms=False)
+            qk = ops.linear(h, p["wqk"], p["bqk"]).view(B, Lp, 2 * H * hp)
+            vt = torch.empty(B, H * hp, Lp, dtype=torch.bfloat16, device=dev)
+            # V^T = W_v . h_b^T per image: the weight is the "A" operand, the image's rows the "W" operand (one launch per image)
+            for b in range(B):
+                ops.linear(p["wv"], h[b * Lp:(b + 1) * Lp], out=vt[b])
+            o = ops.vision_attention(qk[:, :, : H * hp], qk[:, :, H * hp:], vt, L, H, hp, self.head_dim ** -0.5, v_bias=p["bv"])
+            x = ops.linear(o.view(B * Lp, H * hp), p["wo"], p["bo"], epilogue=_lib.EPI_GATE_RESID, gate=ones, resid=x, out=torch.empty_like(x))
+            h = ops.row_norm(x, p["g2"], p["e2"], eps=eps, rms=False)
+            f = ops.act(ops.linear(h, p["w1"], p["b1"]), 0)
+            x = ops.linear(f, p["w2"], p["b2"], epilogue=_lib.EPI_GATE_RESID, gate=ones, resid=x, out=torch.empty_like(x))
+        g, e2 = (ck.get((n, "post"), [t], lambda t=t: _bf(t)) for n, t in (("g", vm.post_layernorm.weight), ("e", vm.post_layernorm.bias)))
+        y = ops.row_norm(x, g, e2, eps=eps, rms=False).view(B, Lp, D)[:, :L]
+        return {"last_hidden_state": y.contiguous()}
+
+
+# ---- FLUX.1 Redux ------------------------------------------------------------------------------------------------------------------
+def to_pil(image):
+    """str (path, or base64 / data-URL) | PIL.Image | np.ndarray (uint8 HW / HWC) | torch.Tensor (uint8 HW / HWC) -> PIL.Image"""
+    from base64 import standard_b64decode
+
+    from PIL import Image
+
+    if isinstance(image, Image.Image):
+        return image
+    if isinstance(image, str):
+        try:
+            return Image.open(image)
+        except Exception:
+            return Image.open(io.BytesIO(standard_b64decode(image.split(",")[-1])))
+    if isinstance(image, torch.Tensor):
+        image = image.detach().cpu()
+        if image.dtype != torch.uint8:
+            raise TypeError(f"fluxmi: an image tensor must be uint8 HW / HWC, got {image.dtype}")
+        image = image.numpy()
+    if isinstance(image, np.ndarray):
+        if image.dtype != np.uint8:
+            raise TypeError(f"fluxmi: an image array must be uint8 HW / HWC, got {image.dtype}")
+        return Image.fromarray(image)
+    raise TypeError(f"fluxmi: cannot read an image from {type(image).__name__}")
+
+
+class ReduxImageEncoder(nn.Module):
+    """BFL's ReduxImageEncoder (src/flux/modules/image_embedders.py): keys redux_up.{weight,bias} / redux_down.{weight,bias} of
+    flux1-redux-dev.safetensors; `siglip` is the vision tower (SiglipVisionNative, loaded from its own checkpoint)."""
+
+    def __init__(self, siglip: SiglipVisionNative, txt_in_features: int = 4096):
+        super().__init__()
+        d = siglip.cfg["hidden_size"]
+        self.siglip = siglip
+        self.redux_up = _lin(d, 3 * txt_in_features, True)
+        self.redux_down = _lin(3 * txt_in_features, txt_in_features, True)
+        self.image_size = siglip.cfg["image_size"]
+        self._cache = _Cache()
+
+    def load_state_dict(self, sd, strict=True, assign=False):
+        """the projector's own keys (a Redux checkpoint); the SigLIP tower loads through self.siglip"""
+        sd = {k: v for k, v in sd.items() if k.startswith(("redux_up.", "redux_down."))}
+        missing = [k for k in ("redux_up.weight", "redux_up.bias", "redux_down.weight", "redux_down.bias") if k not in sd]
+        if missing and strict:
+            raise RuntimeError(f"fluxmi: Redux checkpoint is missing {missing}")
+        self.redux_up.load_state_dict({k[len("redux_up."):]: v for k, v in sd.items() if k.startswith("redux_up.")}, strict=strict, assign=assign)
+        self.redux_down.load_state_dict({k[len("redux_down."):]: v for k, v in sd.items() if k.startswith("redux_down.")}, strict=strict,
+                                        assign=assign)
+        return nn.modules.module._IncompatibleKeys(missing, [])
+
+    @property
+    def device(self):
+        return self.redux_up.weight.device
+
+    @property
+    def num_tokens(self) -> int:
+        return self.siglip.num_tokens
+
+    def preprocess(self, image) -> Tensor:
+        """step 1 of the module docstring -> fp32 [1, 3, S, S] on the host (S = 384), bit-identical to transformers'
+        SiglipImageProcessor(size={"height": S, "width": S}).  `image`: anything to_pil takes."""
+        from PIL import Image
+
+        pil = to_pil(image).convert("RGB").resize((self.image_size, self.image_size), resample=Image.BICUBIC)
+        a = (np.asarray(pil).astype(np.float64) * (1 / 255)).astype(np.float32)
+        a = (a - np.float32(0.5)) / np.float32(0.5)
+        return torch.from_numpy(np.ascontiguousarray(a.transpose(2, 0, 1)))[None]
+
+    @torch.inference_mode()
+    def project(self, hidden: Tensor) -> Tensor:
+        """step 3: [n, T, 1152] bf16 -> redux_down(silu(redux_up(x))) [n, T, 4096] bf16"""
+        from fluxmi import ops
+
+        n, T, d = hidden.shape
+        ck = self._cache
+        wu, bu, wd, bd = (ck.get(k, [t], lambda t=t: _bf(t)) for k, t in (("wu", self.redux_up.weight), ("bu", self.redux_up.bias),
+                                                                            ("wd", self.redux_down.weight), ("bd", self.redux_down.bias)))
+        up = ops.act(ops.linear(hidden.reshape(n * T, d).contiguous(), wu, bu), 1)
+        return ops.linear(up, wd, bd).view(n, T, -1)
+
+    @torch.inference_mode()
+    def __call__(self, images) -> Tensor:
+        """one image or a list -> Redux tokens bf16 [n, 729, 4096] on the encoder's device, in list order"""
+        if not isinstance(images, (list, tuple)):
+            images = [images]
+        pix = torch.cat([self.preprocess(im) for im in images], 0).to(self.device)
+        return self.project(self.siglip(pix)["last_hidden_state"])
+
+
+def read_siglip(path: str) -> SiglipVisionNative:
+    """a local HF directory (config.json + *.safetensors of SiglipVisionModel or SiglipModel) or one .safetensors file (the
+    so400m-patch14-384 geometry) -> SiglipVisionNative with its weights (host memory)"""
+    from safetensors.torch import load_file
+
+    if os.path.isdir(path):
+        cfg = None
+        cj = os.path.join(path, "config.json")
+        if os.path.exists(cj):
+            with open(cj) as f:
+                cfg = json.load(f)
+        sd = _read_dir_weights(path)
+    else:
+        cfg, sd = None, load_file(path, device="cpu")
+    m = SiglipVisionNative(cfg)
+    missing, _ = m.load_state_dict(sd, strict=False)
+    if missing:
+        raise RuntimeError(f"fluxmi: SigLIP checkpoint is missing weights: {missing[:4]} ...")
+    return m

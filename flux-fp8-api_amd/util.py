@@ -67,6 +67,9 @@ class ModelSpec(BaseModel):  # reference util.py:38-79 (unknown JSON keys are ig
     prequantized_flow: bool = False
     quantize_modulation: bool = True
     quantize_flow_embedder_layers: bool = False
+    # FLUX.1 Redux: BFL's flux1-redux-dev.safetensors (the projector) and the SigLIP vision tower (a local HF directory or .safetensors file)
+    redux_path: str | None = None
+    siglip_path: str | None = None
 
     model_config: ConfigDict = {"arbitrary_types_allowed": True, "use_enum_values": True}
 
@@ -227,6 +230,7 @@ class LoadedModels(BaseModel):
     ae: object = None
     clip: object = None
     t5: object = None
+    redux: object = None
     config: ModelSpec
 
     model_config = {"arbitrary_types_allowed": True, "use_enum_values": True}
@@ -277,10 +281,31 @@ def load_text_encoders(config: ModelSpec, clip_kwargs=None, t5_kwargs=None):
     return clip, t5
 
 
+def load_redux(config: ModelSpec):
+    """FLUX.1 Redux's image encoder (modules/image_embedders.py) on config.text_enc_device in bf16, or None unless config.redux_path is a
+    local file and config.siglip_path a local directory or file.  Nothing is downloaded."""
+    import os
+
+    from modules.image_embedders import ReduxImageEncoder, read_siglip
+
+    redux, siglip = getattr(config, "redux_path", None), getattr(config, "siglip_path", None)
+    if not (isinstance(redux, str) and os.path.isfile(redux) and isinstance(siglip, str) and os.path.exists(siglip)):
+        return None
+    from safetensors.torch import load_file as load_sft
+
+    sd = load_sft(redux, device="cpu")
+    if "redux_down.weight" not in sd:
+        raise RuntimeError(f"fluxmi: {redux} is not a FLUX.1 Redux checkpoint (no redux_down.weight)")
+    enc = ReduxImageEncoder(read_siglip(siglip), txt_in_features=sd["redux_down.weight"].shape[0])
+    enc.load_state_dict(sd)
+    return enc.to(device=into_device(config.text_enc_device), dtype=torch.bfloat16)
+
+
 def load_models_from_config(config: ModelSpec, state_dict=None, ae_state_dict=None, clip_kwargs=None, t5_kwargs=None) -> LoadedModels:
-    """reference util.py:325-333."""
+    """reference util.py:325-333 (+ the FLUX.1 Redux encoder when configured)."""
     clip, t5 = load_text_encoders(config, clip_kwargs, t5_kwargs)
-    return LoadedModels(flow=load_flow_model(config, state_dict), ae=load_autoencoder(config, ae_state_dict), clip=clip, t5=t5, config=config)
+    return LoadedModels(flow=load_flow_model(config, state_dict), ae=load_autoencoder(config, ae_state_dict), clip=clip, t5=t5,
+                        redux=load_redux(config), config=config)
 
 
 def load_models_from_config_path(path: str) -> LoadedModels:

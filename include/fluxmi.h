@@ -330,6 +330,18 @@ int fluxmi_act_mul(const void* in, void* out, int rows, int F, long long ld_in, 
  * masked when causal (CLIP); fp32 softmax, P rounded to bf16, out = P V + v_bias (bf16 [H*64] or NULL).  Lp %% 32 == 0. */
 int fluxmi_text_attention(const void* q, const void* k, long long ld_qk, const void* vt, long long ld_vt, void* out, long long ld_out,
                           const float* rel_bias, int bias_ld, const void* v_bias, float scale, int causal, int L, int Lp, int H, void* stream);
+/* fluxmi_text_attention's kernel over B sequences in one launch (B images of a vision encoder), non-causal, no position bias, at a padded head
+ * width head_dim = 64 or 96: head h at columns h*head_dim.. of q / k / out and rows h*head_dim.. of vt.  A head narrower than head_dim (SigLIP-so400m:
+ * 72 in 96) is zero-padded by the caller in q, k, vt and v_bias; the padded output columns then come out zero.  Sequence b is at
+ * q + b*bs_qk, k + b*bs_qk, vt + b*bs_vt, out + b*bs_out (element strides); q / k / vt hold Lp rows (columns) of finite values per sequence,
+ * keys >= L are ignored, out rows < L are written.  Lp %% 32 == 0; ld_qk, bs_qk %% 8 == 0; ld_vt, bs_vt, ld_out, bs_out %% 4 == 0. */
+int fluxmi_vision_attention(const void* q, const void* k, long long ld_qk, long long bs_qk, const void* vt, long long ld_vt, long long bs_vt,
+                            void* out, long long ld_out, long long bs_out, const void* v_bias, float scale, int head_dim, int L, int Lp, int H, int B,
+                            void* stream);
+/* Patch rows of a stride-`patch` "valid" convolution: pix bf16 [B, C, H, W] (NCHW, contiguous) -> out bf16 [B*grid*grid, Kp], row
+ * (b, gy, gx), column c*patch*patch + ky*patch + kx (the order of a Conv2d weight [N, C, patch, patch] flattened), columns >= C*patch*patch
+ * zero.  Pixels past grid*patch are not read.  Kp %% 8 == 0; grid*patch <= H, W.  SigLIP-so400m: C 3, patch 14, grid 27, Kp 640. */
+int fluxmi_patchify(const void* pix, void* out, int B, int C, int H, int W, int patch, int grid, int Kp, void* stream);
 
 /* ---- step scalars -------------------------------------------------------------------------------------- */
 /* timestep_embedding(t, 2*half) with host-provided frequency table                 flux_model.py:95-116 */

@@ -4,7 +4,9 @@ Same two POST endpoints, request fields, defaults and status codes:
   /generate  GenerateArgs{prompt, width=720, height=1024, num_steps=24, guidance=3.5, seed=random in (0, MAX_RAND), strength=1.0,
              init_image=None (path or base64), reference_image=None (FLUX.1 Kontext edit; path or base64, passed on only when set),
              mask_image=None (FLUX.1 Fill: white = regenerate), control_image=None (FLUX.1 Depth / Canny: the depth or edge map),
-             redux_image=None (FLUX.1 Redux image prompt) -- path or base64, each passed on only when set}
+             redux_image=None (FLUX.1 Redux image prompt) -- path or base64, each passed on only when set;
+             negative_prompt=None, true_cfg_scale=None, true_cfg_interval=None ([lo, hi]) -- true classifier-free guidance
+             (FluxPipeline.generate), each passed on only when set}
              ->  image/jpeg stream of FluxPipeline.generate(**args)                                               (reference api.py:54-86)
   /lora      LoraArgs{scale=1.0, path, name, action="load"|"unload"}  ->  {"status": "success"} | 400 invalid action | 500 with the
              exception text; unload uses `name` when given, else `path`                                         (reference api.py:89-122)
@@ -14,7 +16,7 @@ engine access with its own lock (modules/flux_model.py), so concurrent requests 
 from __future__ import annotations
 
 import random
-from typing import Literal, Optional
+from typing import Literal, Optional, Tuple
 
 from fastapi import FastAPI
 from fastapi.responses import JSONResponse, StreamingResponse
@@ -48,6 +50,9 @@ class GenerateArgs(BaseModel):
     mask_image: Optional[str] = None  # FLUX.1 Fill inpainting / outpainting: the mask of init_image to regenerate (white), path or base64
     control_image: Optional[str] = None  # FLUX.1 Depth / Canny: the depth map or edge map to follow, path or base64
     redux_image: Optional[str] = None  # FLUX.1 Redux: an image prompt (needs config redux_path / siglip_path), path or base64
+    negative_prompt: Optional[str] = None  # true classifier-free guidance: what to steer away from ("" is valid); needs true_cfg_scale > 1
+    true_cfg_scale: Optional[float] = None  # its scale (diffusers' name); guidance runs iff negative_prompt is set and this is > 1
+    true_cfg_interval: Optional[Tuple[float, float]] = None  # [lo, hi], fractions of the steps that are guided (default: all)
 
 
 app = FastAPI(title="fluxmi")
@@ -57,9 +62,10 @@ app = FastAPI(title="fluxmi")
 def generate(args: GenerateArgs):
     """JPEG bytes of one image; `init_image` + `strength` select img2img (flux_pipeline.py:399-420,459-523 of the reference);
     `reference_image` selects a FLUX.1 Kontext edit of that image, `mask_image` a FLUX.1 Fill inpainting of `init_image`, `control_image` a
-    FLUX.1 Depth / Canny generation, `redux_image` a FLUX.1 Redux image prompt.  Without them the call is exactly the reference's."""
+    FLUX.1 Depth / Canny generation, `redux_image` a FLUX.1 Redux image prompt; `negative_prompt` + `true_cfg_scale` (+ `true_cfg_interval`)
+    select true classifier-free guidance.  Without them the call is exactly the reference's."""
     kwargs = args.model_dump()
-    for k in ("reference_image", "mask_image", "control_image", "redux_image"):
+    for k in ("reference_image", "mask_image", "control_image", "redux_image", "negative_prompt", "true_cfg_scale", "true_cfg_interval"):
         if kwargs.get(k) is None:
             kwargs.pop(k, None)
     result = app.state.model.generate(**kwargs)

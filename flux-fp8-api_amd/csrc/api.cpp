@@ -488,5 +488,9 @@ int fluxmi_clock_sample(void* out2_dev_u64, void* stream) {
 int fluxmi_euler(void* img, const void* pred, const float* dts, const int* step, long long n, void* stream) {
   return fluxmi_k_euler(img, pred, dts, step, n, (hipStream_t)stream);
 }
+int fluxmi_cfg_euler(void* img, const void* pred, const float* dts, const int* step, const float* scale, int B, long long img_rows,
+                     long long pred_rows, int c_in, int c_out, void* stream) {
+  return fluxmi_k_cfg_euler(img, pred, dts, step, scale, B, img_rows, pred_rows, c_in, c_out, (hipStream_t)stream);
+}
 
 }  // extern "C"

@@ -555,6 +555,40 @@ __global__ void __launch_bounds__(256) euler_cols_kernel(u16* __restrict__ img, 
     *(uint4*)x = pack8(fi);
   }
 }
+// The guided Euler step (true classifier-free guidance): the image stream holds 2B samples, sample b the prompt branch and sample B + b the
+// negative branch of the same image.  With c = pred[b], u = pred[B + b], x = img[b], s = *scale, dt = dts[*step]:
+//   d = bf16(c - u);  m = bf16(s * d);  p = bf16(u + m);  x' = bf16(x + bf16(dt * p));  img[b] = img[B + b] = x'
+// -- the torch expression x + dt * (u + s * (c - u)) on bf16 tensors, one rounding per operation; the last operation is euler_kernel's.  x is
+// read from the prompt half only and x' is written to both, so the halves stay bit-identical.  One thread per 16-byte vector, vectors numbered
+// along the prompt half of pred (dense).  PLAIN: the prediction is as long and as wide as the stream and the vector index is the offset; else
+// (Kontext: img_bstride > vec_per_sample rows' worth; Fill / Depth / Canny: c_in > 8 * vec_per_row) the sample and the row are divided out
+// in 32 bits, and neither the reference rows nor the conditioning channels are read or written.
+template <bool PLAIN>
+__global__ void __launch_bounds__(256) cfg_euler_kernel(u16* __restrict__ img, const u16* __restrict__ pred, const float* __restrict__ dts,
+                                                        const int* __restrict__ step, const float* __restrict__ scale, unsigned n_vec,
+                                                        unsigned vec_per_sample, unsigned vec_per_row, long long img_bstride, int c_in,
+                                                        long long img_half, long long pred_half) {
+  const float dt = dts[step ? *step : 0], sc = *scale;
+  for (unsigned v = blockIdx.x * blockDim.x + threadIdx.x; v < n_vec; v += gridDim.x * blockDim.x) {
+    long long xo = (long long)v * 8;
+    if (!PLAIN) {
+      const unsigned b = v / vec_per_sample, w = v - b * vec_per_sample, r = w / vec_per_row;
+      xo = b * img_bstride + (long long)r * c_in + (w - r * vec_per_row) * 8;
+    }
+    float fx[8], fc[8], fu[8];
+    unpack8(*(const uint4*)(img + xo), fx);
+    unpack8(*(const uint4*)(pred + (long long)v * 8), fc);
+    unpack8(*(const uint4*)(pred + pred_half + (long long)v * 8), fu);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float m = rbf(sc * rbf(fc[j] - fu[j]));
+      fx[j] += rbf(dt * rbf(fu[j] + m));
+    }
+    const uint4 o = pack8(fx);
+    *(uint4*)(img + xo) = o;
+    *(uint4*)(img + img_half + xo) = o;
+  }
+}
 // per-step scalars kept on the device so that one captured graph serves every step:
 //   t_vec[b] = bf16(ts[*step]),  then ++*step happens in advance_step_kernel at the end of the step.
 __global__ void set_timestep_kernel(u16* __restrict__ t_vec, const float* __restrict__ ts, const int* __restrict__ step, int B) {
@@ -870,6 +904,27 @@ int fluxmi_k_euler_cols(void* img, const void* pred, const float* dts, const int
   const long long n_vec = rows * (c_out / 8);
   if (n_vec == 0) return 0;
   hipLaunchKernelGGL(euler_cols_kernel, dim3(grid_for(n_vec)), dim3(256), 0, s, (u16*)img, (const u16*)pred, dts, step, n_vec, c_out / 8, c_in);
+  FLUXMI_LAUNCH_CHECK();
+  return 0;
+}
+int fluxmi_k_cfg_euler(void* img, const void* pred, const float* dts, const int* step, const float* scale, int B, long long img_rows,
+                       long long pred_rows, int c_in, int c_out, hipStream_t s) {
+  FLUXMI_REQUIRE(img && pred && dts && scale, "cfg_euler: NULL argument");
+  FLUXMI_REQUIRE(B >= 0 && c_out > 0 && c_out % 8 == 0 && c_in % 8 == 0 && c_out <= c_in && pred_rows >= 0 && pred_rows <= img_rows &&
+                     (c_in == c_out || pred_rows == img_rows),
+                 "cfg_euler: bad shape B=%d img_rows=%lld pred_rows=%lld c_in=%d c_out=%d (channels multiples of 8, c_out <= c_in, pred_rows <= "
+                 "img_rows, not both shorter and narrower)", B, img_rows, pred_rows, c_in, c_out);
+  const long long n_vec = (long long)B * pred_rows * (c_out / 8);
+  FLUXMI_REQUIRE(n_vec <= 0x7fffffffLL, "cfg_euler: %lld vectors exceed the kernel's 32-bit index", n_vec);
+  if (n_vec == 0) return 0;
+  const long long img_bstride = img_rows * c_in, img_half = (long long)B * img_bstride, pred_half = n_vec * 8;
+  const unsigned vps = (unsigned)(pred_rows * (c_out / 8));
+  if (c_in == c_out && pred_rows == img_rows)
+    hipLaunchKernelGGL(cfg_euler_kernel<true>, dim3(grid_for(n_vec)), dim3(256), 0, s, (u16*)img, (const u16*)pred, dts, step, scale,
+                       (unsigned)n_vec, vps, (unsigned)(c_out / 8), img_bstride, c_in, img_half, pred_half);
+  else
+    hipLaunchKernelGGL(cfg_euler_kernel<false>, dim3(grid_for(n_vec)), dim3(256), 0, s, (u16*)img, (const u16*)pred, dts, step, scale,
+                       (unsigned)n_vec, vps, (unsigned)(c_out / 8), img_bstride, c_in, img_half, pred_half);
   FLUXMI_LAUNCH_CHECK();
   return 0;
 }

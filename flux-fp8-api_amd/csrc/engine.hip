@@ -71,6 +71,7 @@ struct fluxmi_engine {
   bool qlut_valid = false;  // the quantising-epilogue tables reflect the current input scales
   hipGraphExec_t exec = nullptr;
   bool graph_ok = false;
+  bool graph_cfg = false;           // the captured step graph (and `warmed`) is the guided one: plain and guided steps of one shape differ
   unsigned graph_gen = 0;          // fluxmi_tuning_generation() the step graph was captured under: a changed tuning struct re-captures
   bool warmed = false;             // one frozen step of this shape has run eagerly (lazy one-time inits done): later calls may capture at once
   bool txt_emb_valid = false;
@@ -82,6 +83,7 @@ struct fluxmi_engine {
   bool pairs_dirty = true;
   bool pairs_skipped = false;      // the copies were wanted and did not fit (ensure_pairs): retried at the next prepare
   unsigned pairs_gen = 0;          // fluxmi_tuning_generation() the copies were built under (fluxmi_tuning_t.w_pairs may have changed)
+  float* d_cfg = nullptr;          // true-CFG scale (device scalar, like d_dts: one guided graph serves every scale)
   int* d_step0 = nullptr;          // first step of the modulation table (device scalar: the captured graph reads it)
   // the layout each fp8 activation buffer (ACT_A8 .. ACT_CAT8) was last written in: true = row pairs (fused mode, act_pairs), false = plain
   // rows.  Set by the stages that write them (and by a replayed step graph); fluxmi_engine_copy_buffer converts by it
@@ -996,7 +998,7 @@ int fluxmi_engine_create(const fluxmi_model_desc_t* desc, const fluxmi_linear_t*
   size_t off = 0;
   auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
   const size_t o_freqs = carve(128 * 4), o_omega = carve(64 * 4), o_axis = carve(64 * 4), o_ts = carve((MAX_STEPS + 1) * 4),
-               o_dts = carve((MAX_STEPS + 1) * 4), o_step = carve(4), o_step0 = carve(4), o_amax = carve((size_t)n_linears * 4),
+               o_dts = carve((MAX_STEPS + 1) * 4), o_step = carve(4), o_step0 = carve(4), o_cfg = carve(4), o_amax = carve((size_t)n_linears * 4),
                o_gemv = carve(sizeof(FluxmiGemvLayer) * n_mod), o_cm = carve(sizeof(FluxmiCalibLayer) * n_mod);
   if (hipMalloc((void**)&e->consts, off) != hipSuccess) { delete e; fluxmi_set_error("engine_create: hipMalloc(%zu) failed", off); return 2; }
   e->d_freqs = (float*)(e->consts + o_freqs); e->d_omega = (float*)(e->consts + o_omega); e->d_axis = (int*)(e->consts + o_axis);
@@ -1004,6 +1006,7 @@ int fluxmi_engine_create(const fluxmi_model_desc_t* desc, const fluxmi_linear_t*
   e->d_amax = e->d_amax_own = (float*)(e->consts + o_amax); e->d_gemv = (FluxmiGemvLayer*)(e->consts + o_gemv);
   e->d_calib_mod = (FluxmiCalibLayer*)(e->consts + o_cm);
   e->d_step0 = (int*)(e->consts + o_step0);
+  e->d_cfg = (float*)(e->consts + o_cfg);
   hipMemset(e->consts, 0, off);
   // pinned staging for the schedule + the events (guard of the staging buffer, timing of the frozen steps)
   if (hipHostMalloc((void**)&e->h_sched, 2 * (MAX_STEPS + 1) * sizeof(float), hipHostMallocDefault) != hipSuccess ||
@@ -1162,10 +1165,15 @@ int fluxmi_engine_forward(fluxmi_engine_t* e, const void* img, const void* txt, 
 }
 
 
-int fluxmi_engine_denoise(fluxmi_engine_t* e, void* img, const void* txt, const void* y, float guidance,
-                          const double* timesteps_host, int n_steps, int* trial_index_inout, int use_graph, void* stream) {
+// the denoise loop, plain or guided (cfg: true classifier-free guidance).  Guided: the prepared batch B is 2 Bh, samples [0, Bh) the prompt
+// branch and [Bh, B) the negative branch of the caller's Bh images; the caller's img [Bh, ...] is copied into both halves of the stream, every
+// forward runs on the B samples, and the update is fluxmi_k_cfg_euler, which keeps the halves bit-identical.
+static int denoise_impl(fluxmi_engine_t* e, void* img, const void* txt, const void* y, float guidance, bool cfg, float cfg_scale,
+                        const double* timesteps_host, int n_steps, int* trial_index_inout, int use_graph, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   FLUXMI_REQUIRE(e && e->ws, "engine_denoise: call fluxmi_engine_prepare first");
+  FLUXMI_REQUIRE(!cfg || e->B % 2 == 0, "engine_denoise_cfg: the prepared batch (%d) must be even: prompt branches first, then the negative "
+                 "branches of the same images (2B <= %d)", e->B, FLUXMI_ENGINE_MAX_BATCH);
   FLUXMI_REQUIRE(img && txt && y && timesteps_host && trial_index_inout, "engine_denoise: NULL argument");
   FLUXMI_REQUIRE(n_steps >= 0 && n_steps <= MAX_STEPS, "engine_denoise: n_steps=%d out of range", n_steps);
   Range whole("fluxmi_engine_denoise");
@@ -1175,6 +1183,8 @@ int fluxmi_engine_denoise(fluxmi_engine_t* e, void* img, const void* txt, const 
   // the Euler update: the whole stream, or (Kontext) the leading Lpred rows of each sample -- the reference rows never move -- or (Fill /
   // Depth / Canny) the leading C_out channels of every row -- the conditioning channels never move (no row split then: prepare_cond)
   auto euler = [&](hipStream_t st) -> int {
+    if (cfg)
+      return fluxmi_k_cfg_euler(buf<u16>(e, "img_s"), buf<u16>(e, "pred_s"), e->d_dts, e->d_step, e->d_cfg, B / 2, Li, e->Lpred, C, c_out(e), st);
     if (c_out(e) != C)
       return fluxmi_k_euler_cols(buf<u16>(e, "img_s"), buf<u16>(e, "pred_s"), e->d_dts, e->d_step, (long long)B * Li, C, c_out(e), st);
     if (e->Lpred == Li) return fluxmi_k_euler(buf<u16>(e, "img_s"), buf<u16>(e, "pred_s"), e->d_dts, e->d_step, (long long)B * Li * C, st);
@@ -1205,8 +1215,14 @@ int fluxmi_engine_denoise(fluxmi_engine_t* e, void* img, const void* txt, const 
   FLUXMI_TRY(fluxmi_k_fill_bf16(gvec, guidance, B, s));  // guidance arrives in the flow dtype (flux_pipeline.py:619-623)
   FLUXMI_CHECK_HIP(hipMemsetAsync(e->d_step, 0, 4, s));
   u16 *img_s = buf<u16>(e, "img_s"), *txt_s = buf<u16>(e, "txt_s"), *y_s = buf<u16>(e, "y_s"), *pred_s = buf<u16>(e, "pred_s");
-  const long long n_img = (long long)B * Li * C;
+  const long long n_img = (long long)(cfg ? B / 2 : B) * Li * C;  // the caller's samples
   FLUXMI_CHECK_HIP(hipMemcpyAsync(img_s, img, n_img * 2, hipMemcpyDeviceToDevice, s));
+  if (cfg) {
+    FLUXMI_CHECK_HIP(hipMemcpyAsync(img_s + n_img, img, n_img * 2, hipMemcpyDeviceToDevice, s));
+    unsigned bits;
+    memcpy(&bits, &cfg_scale, 4);
+    FLUXMI_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)e->d_cfg, (int)bits, 1, s));
+  }
   FLUXMI_CHECK_HIP(hipMemcpyAsync(txt_s, txt, (size_t)B * Lt * e->d.ctx_in * 2, hipMemcpyDeviceToDevice, s));
   FLUXMI_CHECK_HIP(hipMemcpyAsync(y_s, y, (size_t)B * e->d.vec_in * 2, hipMemcpyDeviceToDevice, s));
 
@@ -1258,6 +1274,11 @@ int fluxmi_engine_denoise(fluxmi_engine_t* e, void* img, const void* txt, const 
         e->graph_ok = false;  // kernel choices are baked into a captured graph: never replay one captured under other knobs
         e->warmed = false;
         e->qlut_valid = false;
+      }
+      if (e->graph_cfg != cfg) {
+        e->graph_ok = false;  // the update kernel is baked in too: a plain and a guided request of one shape never share a graph
+        e->warmed = false;
+        e->graph_cfg = cfg;
       }
       if (use_graph && !e->graph_ok) {
         // the first frozen step of a shape runs eagerly so that every lazy one-time init (function attributes) happens outside capture
@@ -1311,6 +1332,16 @@ int fluxmi_engine_denoise(fluxmi_engine_t* e, void* img, const void* txt, const 
   FLUXMI_CHECK_HIP(hipMemcpyAsync(img, img_s, n_img * 2, hipMemcpyDeviceToDevice, s));
   *trial_index_inout = trial;
   return 0;
+}
+
+int fluxmi_engine_denoise(fluxmi_engine_t* e, void* img, const void* txt, const void* y, float guidance,
+                          const double* timesteps_host, int n_steps, int* trial_index_inout, int use_graph, void* stream) {
+  return denoise_impl(e, img, txt, y, guidance, false, 1.f, timesteps_host, n_steps, trial_index_inout, use_graph, stream);
+}
+
+int fluxmi_engine_denoise_cfg(fluxmi_engine_t* e, void* img, const void* txt, const void* y, float guidance, float cfg_scale,
+                              const double* timesteps_host, int n_steps, int* trial_index_inout, int use_graph, void* stream) {
+  return denoise_impl(e, img, txt, y, guidance, true, cfg_scale, timesteps_host, n_steps, trial_index_inout, use_graph, stream);
 }
 
 int fluxmi_engine_last_timing(fluxmi_engine_t* e, float* ms, int* steps) {

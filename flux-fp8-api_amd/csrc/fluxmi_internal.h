@@ -161,6 +161,10 @@ int fluxmi_k_euler_rows(void* img, const void* pred, const float* dts, const int
 // channels [0, c_out) of every row of img [rows, c_in] += bf16(dts[*step] * pred [rows, c_out]) (FLUX.1 Fill / Depth / Canny: the conditioning
 // channels stay)
 int fluxmi_k_euler_cols(void* img, const void* pred, const float* dts, const int* step, long long rows, int c_in, int c_out, hipStream_t s);
+// the guided Euler step (true CFG): img [2B, img_rows, c_in], pred [2B, pred_rows, c_out], prompt branch first; both halves of img get
+// x + bf16(dt * (u + s (c - u))) with one bf16 rounding per operation, s = *scale (device), dt = dts[*step]
+int fluxmi_k_cfg_euler(void* img, const void* pred, const float* dts, const int* step, const float* scale, int B, long long img_rows,
+                       long long pred_rows, int c_in, int c_out, hipStream_t s);
 int fluxmi_k_set_timestep(void* t_vec, const float* ts, const int* step, int B, hipStream_t s);
 int fluxmi_k_advance_step(int* step, hipStream_t s);
 int fluxmi_k_clock_sample(unsigned long long* out2, hipStream_t s);

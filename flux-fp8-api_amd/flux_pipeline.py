@@ -401,6 +401,17 @@ class FluxPipeline:
         txt_ids = torch.zeros(bs, txt.shape[1], 3, device=target_device, dtype=target_dtype)
         return tokens, img_ids, vec, txt, txt_ids
 
+    def _prepare_negative(self, negative_prompt, noise: torch.Tensor, num_images: int, txt: torch.Tensor):
+        """The negative prompt through prepare()'s text path (prompt weighting syntax included) -> (vec, txt) [num_images, ...] matching the
+        prompt's `txt`.  Checked here, before any collective: every rank sees the same shapes, so every rank raises."""
+        if isinstance(negative_prompt, (list, tuple)) and len(negative_prompt) not in (1, num_images):
+            raise ValueError(f"fluxmi: {len(negative_prompt)} negative prompts for a batch of {num_images} images (one, or one per image)")
+        _, _, neg_vec, neg_txt, _ = self.prepare(noise[:1].expand(num_images, -1, -1, -1), negative_prompt)
+        if tuple(neg_txt.shape[1:]) != tuple(txt.shape[1:]) or neg_txt.shape[0] not in (1, num_images):
+            raise ValueError(f"fluxmi: negative_prompt embeddings {tuple(neg_txt.shape)} do not match the prompt's {tuple(txt.shape)}: both branches "
+                             "run in one batch and need the same sequence length")
+        return neg_vec.expand(num_images, -1).contiguous(), neg_txt.expand(num_images, -1, -1).contiguous()
+
     # ---- LoRA (reference flux_pipeline.py:151-177) -------------------------------------------------------------------
     def load_lora(self, lora_path, scale: float, name: Optional[str] = None):
         self.model.load_lora(path=lora_path, scale=scale, name=name)
@@ -469,7 +480,8 @@ class FluxPipeline:
                  seed: int | None = None, init_image=None, strength: float = 1.0, silent: bool = False, num_images: int = 1,
                  return_seed: bool = False, jpeg_quality: int = 99, output_type: str = "jpeg", noise: Optional[torch.Tensor] = None,
                  use_graph: bool = True, reference_image=None, mask_image=None, control_image=None,
-                 img_cond: Optional[torch.Tensor] = None, redux_image=None):
+                 img_cond: Optional[torch.Tensor] = None, redux_image=None, negative_prompt=None, true_cfg_scale: float = 1.0,
+                 true_cfg_interval=(0.0, 1.0)):
         """`reference_image` (FLUX.1 Kontext [dev] instruction editing): an image the prompt describes an edit of, in any form `init_image`
         takes; see prepare_kontext_reference.  Composes with `init_image` / `strength` unchanged.
         FLUX.1 Fill [dev] (a model with 320 conditioning channels): `init_image` is the image to inpaint and `mask_image` (white =
@@ -480,9 +492,30 @@ class FluxPipeline:
         in_channels - out_channels] already prepared (instead of `mask_image` / `control_image`).  A text-to-image model refuses all three.
         `redux_image` (FLUX.1 Redux [dev] image prompt; needs config.redux_path / siglip_path): an image in any form `init_image` takes, or a
         list; 729 SigLIP-derived tokens per image are appended to the T5 tokens (see prepare_redux_tokens).  It only lengthens the text
-        stream, so it composes with everything above."""
+        stream, so it composes with everything above.
+        `negative_prompt` + `true_cfg_scale` (the names of diffusers' FluxPipeline): true classifier-free guidance.  It runs iff
+        `negative_prompt is not None and true_cfg_scale > 1`: every guided step predicts the prompt and the negative prompt in one forward
+        on twice the batch and steps the latent with `neg + true_cfg_scale * (pos - neg)` (Flux.denoise), which costs about what twice
+        the images cost.  A negative prompt with a scale <= 1 is ignored (not even encoded); a scale > 1 without one is refused.
+        `negative_prompt` takes what `prompt` takes: a str ("" is valid), a list of one entry or one per image, or a dict of embeddings
+        with the prompt's sequence length.  `guidance` (the distilled embedding) is independent of it and goes to both branches, as do a
+        Kontext reference, Fill / Depth / Canny conditioning and `init_image` / `strength`; Redux tokens are appended to BOTH branches,
+        so the guidance then acts on the text alone.  A seed draws the same noise with and without a negative prompt.
+        `true_cfg_interval=(lo, hi)`, fractions of the request's n steps: step i (0-based) is guided iff lo n <= i < hi n, the others run
+        the prompt alone.  Run as up to three consecutive denoise calls on slices of the schedule; the engine keeps one workspace and one
+        graph, so every switch re-allocates and re-captures (README: measured)."""
         if redux_image is not None:
             self._require_redux()
+        if negative_prompt is None and true_cfg_scale > 1:
+            raise ValueError(f"fluxmi: true_cfg_scale={true_cfg_scale} needs a negative_prompt (\"\" for the unconditional branch); without "
+                             "one the request would pay for two branches and guide nothing")
+        try:
+            cfg_lo, cfg_hi = (float(v) for v in true_cfg_interval)
+        except (TypeError, ValueError):
+            raise ValueError(f"fluxmi: true_cfg_interval={true_cfg_interval!r}: expected (lo, hi)") from None
+        if not 0.0 <= cfg_lo <= cfg_hi <= 1.0:
+            raise ValueError(f"fluxmi: true_cfg_interval={true_cfg_interval!r}: expected 0 <= lo <= hi <= 1")
+        guided = negative_prompt is not None and true_cfg_scale > 1
         kind = self.conditioning_kind()
         if kind is None and (mask_image is not None or control_image is not None or img_cond is not None):
             raise ValueError("fluxmi: mask_image / control_image / img_cond need a FLUX.1 Fill or Depth / Canny model (this one has no "
@@ -523,6 +556,9 @@ class FluxPipeline:
                                                   generator=generator, num_images=num_images, noise=noise)
         img, img_ids, vec, txt, txt_ids = map(lambda x: x.contiguous(), self.prepare(noise, prompt))
         num_images = img.shape[0]  # a list prompt with num_images == 1 sizes the batch (prepare)
+        neg_txt = neg_vec = None
+        if guided:
+            neg_vec, neg_txt = self._prepare_negative(negative_prompt, noise, num_images, txt)
         if redux_image is not None:
             if world > 1 and rank != 0:
                 # the broadcast below carries rank 0's tokens; this rank only needs the same text length
@@ -532,6 +568,8 @@ class FluxPipeline:
             else:
                 txt, txt_ids = self.prepare_redux_tokens(redux_image, num_images=num_images, txt=txt)
             txt, txt_ids = txt.contiguous(), txt_ids.contiguous()
+            if guided:  # the same image tokens behind the negative prompt's T5 tokens
+                neg_txt = torch.cat((neg_txt, txt[:, neg_txt.shape[1]:]), dim=-2).contiguous()
         cond = {}
         if reference_image is not None:
             # drawn from the request's generator after the noise (the order is part of what a seed reproduces)
@@ -548,6 +586,8 @@ class FluxPipeline:
                 img_cond = img_cond.repeat(num_images, 1, 1)
             cond = dict(img_cond=img_cond.contiguous())
         if world > 1:
+            if guided:  # the negative embeddings ride in the one broadcast, behind the prompt's
+                txt, vec = torch.cat((txt, neg_txt), 0), torch.cat((vec, neg_vec), 0)
             if "img_cond" in cond:
                 # every rank steps rank 0's conditioning (the VAE sample differs between ranks' generators); its bf16 bits ride in the
                 # payload's dtype and come back unchanged
@@ -558,15 +598,28 @@ class FluxPipeline:
                 txt, vec, img, cond["img_cond_seq"] = fdist.broadcast_request(txt, vec, img, src=0, extra=cond["img_cond_seq"])
             else:
                 txt, vec, img = fdist.broadcast_request(txt, vec, img, src=0)
+            if guided:
+                (txt, neg_txt), (vec, neg_vec) = txt.chunk(2, 0), vec.chunk(2, 0)
+            # images are sharded, not branches: both branches of an image run on the rank that owns it
             lo, hi = fdist.shard_bounds(img.shape[0], rank, world)
             img, img_ids, vec, txt, txt_ids = (t[lo:hi].contiguous() for t in (img, img_ids, vec, txt, txt_ids))
+            if guided:
+                neg_txt, neg_vec = neg_txt[lo:hi].contiguous(), neg_vec[lo:hi].contiguous()
             cond = {k: v[lo:hi].contiguous() for k, v in cond.items()}
         if img.shape[0] == 0:
             # more ranks than images (frozen scales only, see above): this rank has nothing to denoise but still takes part in the gather
             # below (an exception or an early return here would leave the other ranks blocked in the collective)
             latents = img.new_empty((0,) + tuple(img.shape[1:]))
         else:
-            latents = self.model.denoise(img, img_ids, txt, txt_ids, vec, timesteps, guidance=guidance, use_graph=use_graph, **cond)
+            n = len(timesteps) - 1
+            # step i is guided iff cfg_lo n <= i < cfg_hi n, i.e. ceil(cfg_lo n) <= i < ceil(cfg_hi n)
+            g0, g1 = (min(n, math.ceil(cfg_lo * n)), min(n, math.ceil(cfg_hi * n))) if guided else (n, n)
+            neg = dict(neg_txt=neg_txt, neg_y=neg_vec, cfg_scale=true_cfg_scale)
+            latents = img
+            for a, b, kw in ((0, g0, {}), (g0, g1, neg), (g1, n, {})) if g0 < g1 else ((0, n, {}),):
+                if a < b or n == 0:
+                    latents = self.model.denoise(latents, img_ids, txt, txt_ids, vec, timesteps[a:b + 1], guidance=guidance, use_graph=use_graph,
+                                                 **cond, **kw)
         if world > 1:
             latents = fdist.gather_latents(latents, num_images, dst=0)
             if latents is None:  # only the gather rank decodes / returns the images

@@ -100,6 +100,7 @@ _SIGS = {
     "fluxmi_attention_rawq": ([vp, i64, vp, vp, vp, vp, vp, vp, i64, i32, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp], i32),
     "fluxmi_timestep_embedding": ([vp, vp, vp, i32, i32, f32, vp], i32),
     "fluxmi_euler": ([vp, vp, vp, vp, i64, vp], i32),
+    "fluxmi_cfg_euler": ([vp, vp, vp, vp, vp, i32, i64, i64, i32, i32, vp], i32),
     "fluxmi_engine_num_linears": ([C.POINTER(ModelDesc)], i32),
     "fluxmi_engine_create": ([C.POINTER(ModelDesc), C.POINTER(Linear), i32, C.POINTER(vp), i32, C.POINTER(vp)], i32),
     "fluxmi_engine_destroy": ([vp], i32),
@@ -109,6 +110,7 @@ _SIGS = {
     "fluxmi_engine_prepare_cond": ([vp, i32, i32, i32, i32, vp, vp, vp], i32),
     "fluxmi_engine_forward": ([vp, vp, vp, vp, vp, vp, vp, i32, i32, vp], i32),
     "fluxmi_engine_denoise": ([vp, vp, vp, vp, f32, C.POINTER(C.c_double), i32, C.POINTER(i32), i32, vp], i32),
+    "fluxmi_engine_denoise_cfg": ([vp, vp, vp, vp, f32, f32, C.POINTER(C.c_double), i32, C.POINTER(i32), i32, vp], i32),
     "fluxmi_engine_workspace_bytes": ([vp, C.POINTER(i64)], i32),
     "fluxmi_engine_get_buffer": ([vp, C.c_char_p, C.POINTER(vp), C.POINTER(i64)], i32),
     "fluxmi_engine_last_timing": ([vp, C.POINTER(f32), C.POINTER(i32)], i32),

@@ -317,8 +317,9 @@ class Flux(nn.Module):
             self._engine_keep = (keep_l, self._engine_keep[1], lin, self._engine_keep[3])
 
     def _prepare(self, img, img_ids, txt_ids, txt, Lc: int = 0):
-        """`img` / `img_ids` hold the whole image stream; with a Kontext reference its last `Lc` rows of each sample are the reference tokens."""
-        B, L_img, _ = img.shape
+        """`img` / `img_ids` hold the whole image stream; with a Kontext reference its last `Lc` rows of each sample are the reference tokens.
+        The batch is that of the ids and `txt` (a guided request: twice `img`'s, the negative branches behind the prompt branches)."""
+        B, L_img = txt.shape[0], img.shape[1]
         Lt = txt.shape[1]
         # cheap (two small copies + one table kernel; the workspace is only re-allocated when the shape changes)
         ii = img_ids.to(torch.bfloat16).contiguous()
@@ -510,25 +511,43 @@ class Flux(nn.Module):
     @torch.inference_mode()
     def denoise(self, img: Tensor, img_ids: Tensor, txt: Tensor, txt_ids: Tensor, y: Tensor, timesteps: List[float],
                 guidance: float = 3.5, use_graph: bool = True, img_cond_seq: Tensor | None = None,
-                img_cond_seq_ids: Tensor | None = None, img_cond: Tensor | None = None) -> Tensor:
+                img_cond_seq_ids: Tensor | None = None, img_cond: Tensor | None = None, neg_txt: Tensor | None = None,
+                neg_y: Tensor | None = None, cfg_scale: float = 1.0) -> Tensor:
         """The Euler loop of FluxPipeline.generate (reference flux_pipeline.py:619-651) run natively: calibrating
         steps unfused, every later step one replay of a captured hipGraph.  Returns the final latent tokens.
         FLUX.1 Kontext: with `img_cond_seq` / `img_cond_seq_ids` the reference tokens join every step's forward and are never stepped; the
         return value is the `img.shape[1]` noisy tokens only.
         FLUX.1 Fill / Depth / Canny: `img_cond` [B, Li, in_channels - out_channels] joins every step's forward as further channels of each
-        token and is never stepped; the return value is the stepped [B, Li, out_channels] tokens."""
+        token and is never stepped; the return value is the stepped [B, Li, out_channels] tokens.
+        True classifier-free guidance: with `neg_txt` [1 or B, Lt, ctx] / `neg_y` [1 or B, vec] (both or neither; the prompt's Lt) every step
+        predicts both branches in ONE forward on 2B samples (prompt branches first, ids and conditioning duplicated) and steps the shared
+        latent with `u + cfg_scale * (c - u)` (csrc/elementwise.hip, cfg_euler_kernel); any `cfg_scale` is taken as given.  At most 16 images
+        per pass then, more run as equal passes (frozen scales only); the two branches of an image always share a pass."""
         bf = lambda t: t.to(torch.bfloat16).contiguous()
         kontext = img_cond_seq is not None or img_cond_seq_ids is not None
-        stream = self._with_channels(img, img_cond, img_cond_seq) if img.shape[0] <= self.MAX_ENGINE_BATCH else None
-        if img.shape[0] > self.MAX_ENGINE_BATCH:
+        guided = neg_txt is not None or neg_y is not None
+        if guided:
+            if neg_txt is None or neg_y is None:
+                raise ValueError("neg_txt and neg_y go together (the negative prompt's T5 sequence and pooled CLIP vector)")
+            B = img.shape[0]
+            if neg_txt.ndim != 3 or neg_txt.shape[0] not in (1, B) or tuple(neg_txt.shape[1:]) != tuple(txt.shape[1:]):
+                raise ValueError(f"neg_txt {tuple(neg_txt.shape)}: expected [1 or {B}, {txt.shape[1]}, {txt.shape[2]}] (the prompt's sequence length: both "
+                                 f"branches run in one batch)")
+            if neg_y.ndim != 2 or neg_y.shape[0] not in (1, B) or neg_y.shape[1] != y.shape[1]:
+                raise ValueError(f"neg_y {tuple(neg_y.shape)}: expected [1 or {B}, {y.shape[1]}]")
+            neg_txt = neg_txt.to(device=txt.device).expand(B, -1, -1)
+            neg_y = neg_y.to(device=y.device).expand(B, -1)
+        cap = self.MAX_ENGINE_BATCH // 2 if guided else self.MAX_ENGINE_BATCH
+        stream = self._with_channels(img, img_cond, img_cond_seq) if img.shape[0] <= cap else None
+        if img.shape[0] > cap:
             # the engine takes at most 32 samples per pass (workspace / modulation-table size); the reference has no num_images limit, so
             # larger batches run as consecutive passes (samples never interact).  EQUAL passes: the engine re-allocates its workspace and
             # re-captures its graph whenever the batch size changes, so 40 = 20 + 20, not 32 + 8.  Only frozen models: a calibrating pass
             # per chunk would advance the F8Linear trial counters once per chunk instead of once per step.
             if self.calibration_state()[0] is False:
-                raise ValueError(f"fluxmi: batches larger than {self.MAX_ENGINE_BATCH} need frozen F8Linear input scales (run the calibration warm-up first)")
+                raise ValueError(f"fluxmi: batches larger than {cap} need frozen F8Linear input scales (run the calibration warm-up first)")
             B = img.shape[0]
-            n_pass = -(-B // self.MAX_ENGINE_BATCH)
+            n_pass = -(-B // cap)
             per = -(-B // n_pass)
             outs = []
             for i in range(0, B, per):
@@ -538,6 +557,8 @@ class Flux(nn.Module):
                 cond = dict(img_cond_seq=pick(img_cond_seq), img_cond_seq_ids=pick(img_cond_seq_ids)) if kontext else {}
                 if img_cond is not None:
                     cond["img_cond"] = pick(img_cond)
+                if guided:
+                    cond.update(neg_txt=pick(neg_txt), neg_y=pick(neg_y), cfg_scale=cfg_scale)
                 o = self.denoise(pick(img), pick(img_ids), pick(txt), pick(txt_ids), pick(y), timesteps, guidance=guidance, use_graph=use_graph,
                                  **cond)
                 outs.append(o[:per - pad])
@@ -545,6 +566,9 @@ class Flux(nn.Module):
         Li = img.shape[1]
         img, img_ids, Lc = self._with_reference(stream, img_ids, img_cond_seq, img_cond_seq_ids)
         img = bf(img).clone()
+        if guided:  # the negative branches ride behind the prompt branches: same position ids, the negative prompt's text
+            txt, y = torch.cat((txt, neg_txt.to(txt.dtype)), 0), torch.cat((y, neg_y.to(y.dtype)), 0)
+            img_ids, txt_ids = torch.cat((img_ids, img_ids), 0), torch.cat((txt_ids, txt_ids), 0)
         txt, y = bf(txt), bf(y)
         self._ensure_engine(img.device)
         with self._lock:
@@ -552,8 +576,12 @@ class Flux(nn.Module):
             trial = self._trial_counter()
             t_io = C.c_int(trial if trial is not None else 0)
             ts = (C.c_double * len(timesteps))(*[float(t) for t in timesteps])
-            _lib.call("fluxmi_engine_denoise", self._engine, ops._p(img), ops._p(txt), ops._p(y), float(guidance), ts,
-                      len(timesteps) - 1, C.byref(t_io), int(use_graph), ops._stream())
+            if guided:
+                _lib.call("fluxmi_engine_denoise_cfg", self._engine, ops._p(img), ops._p(txt), ops._p(y), float(guidance), float(cfg_scale), ts,
+                          len(timesteps) - 1, C.byref(t_io), int(use_graph), ops._stream())
+            else:
+                _lib.call("fluxmi_engine_denoise", self._engine, ops._p(img), ops._p(txt), ops._p(y), float(guidance), ts,
+                          len(timesteps) - 1, C.byref(t_io), int(use_graph), ops._stream())
             if trial is not None:
                 self._advance_calibration(t_io.value)
         if self.in_channels != self.out_channels:

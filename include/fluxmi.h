@@ -348,6 +348,15 @@ int fluxmi_patchify(const void* pix, void* out, int B, int C, int H, int W, int 
 int fluxmi_timestep_embedding(const void* t, const float* freqs, void* out, int B, int half, float time_factor, void* stream);
 /* img += dts[*step] * pred                                                          flux_pipeline.py:651 */
 int fluxmi_euler(void* img, const void* pred, const float* dts, const int* step, long long n, void* stream);
+/* The guided Euler update (true classifier-free guidance).  img bf16 [2B, img_rows, c_in], pred bf16 [2B, pred_rows, c_out]: sample b is the
+ * prompt branch, sample B + b the negative branch of the same image.  For every predicted element (rows [0, pred_rows), channels
+ * [0, c_out) of a sample), with c = pred[b], u = pred[B + b], x = img[b], s = *scale, dt = dts[*step] (step NULL: dts[0]):
+ *   d = bf16(c - u);  m = bf16(s * d);  p = bf16(u + m);  x' = bf16(x + bf16(dt * p));  img[b] = img[B + b] = x'
+ * i.e. the torch expression x + dt * (u + s * (c - u)) on bf16 tensors.  x is read from the prompt half only, so the halves are
+ * bit-identical afterwards.  pred_rows < img_rows (Kontext reference rows) or c_out < c_in (Fill / Depth / Canny conditioning channels),
+ * not both: those rows / channels are neither read nor written.  dts, step, scale are DEVICE pointers; c_in, c_out multiples of 8. */
+int fluxmi_cfg_euler(void* img, const void* pred, const float* dts, const int* step, const float* scale, int B, long long img_rows,
+                     long long pred_rows, int c_in, int c_out, void* stream);
 
 /* ---- whole-model engine ------------------------------------------------------------------------------- */
 typedef struct fluxmi_linear {
@@ -415,7 +424,17 @@ int fluxmi_engine_forward(fluxmi_engine_t* e, const void* img, const void* txt, 
  * Steps with trial_index <= num_trials run unfused; the remainder replays ONE captured hipGraph per step. */
 int fluxmi_engine_denoise(fluxmi_engine_t* e, void* img, const void* txt, const void* y, float guidance,
                           const double* timesteps_host, int n_steps, int* trial_index_inout, int use_graph, void* stream);
-/* hipEvent timing of the frozen STEPS of the last fluxmi_engine_denoise call: the first event is recorded on the caller's stream behind
+/* The same loop with true classifier-free guidance (a negative prompt).  The engine has been prepared for a batch of 2B whose halves
+ * carry the same position ids; img is the caller's B samples [B, Li(+Lc), C_in], stepped in place exactly as above; txt [2B, Lt, ctx] and
+ * y [2B, vec] hold the prompt branch first, then the negative branch of the same images.  img is copied into both halves of the engine's
+ * stream, every step is ONE forward on the 2B samples followed by fluxmi_cfg_euler with scale = cfg_scale (any value; 1 reproduces the
+ * prompt branch up to the roundings of the formula), in the calibrating and in the graph-replayed steps alike.  One trial per step, as in
+ * a whole-batch calibration.  cfg_scale is device data of the captured graph: another scale replays the same graph; a plain and a guided
+ * request of the same prepared shape never share one (each switch re-captures).  An odd prepared batch is refused (2B <=
+ * FLUXMI_ENGINE_MAX_BATCH follows from prepare).  Timing, the amax-exchange hook and use_graph as for fluxmi_engine_denoise. */
+int fluxmi_engine_denoise_cfg(fluxmi_engine_t* e, void* img, const void* txt, const void* y, float guidance, float cfg_scale,
+                              const double* timesteps_host, int n_steps, int* trial_index_inout, int use_graph, void* stream);
+/* hipEvent timing of the frozen STEPS of the last fluxmi_engine_denoise / _denoise_cfg call: the first event is recorded on the caller's stream behind
  * the step-ahead modulation table, the eager warm step and the graph capture of a new shape (none of them is inside the window), the
  * second behind the last step (the reference's only meter is tqdm's it/s, flux_pipeline.py:628-630).  A request longer than 64 steps
  * includes the table builds of its later windows.  Blocks until the second event has completed.  steps = number of steps between the

@@ -6,7 +6,8 @@ Same two POST endpoints, request fields, defaults and status codes:
              mask_image=None (FLUX.1 Fill: white = regenerate), control_image=None (FLUX.1 Depth / Canny: the depth or edge map),
              redux_image=None (FLUX.1 Redux image prompt) -- path or base64, each passed on only when set;
              negative_prompt=None, true_cfg_scale=None, true_cfg_interval=None ([lo, hi]) -- true classifier-free guidance
-             (FluxPipeline.generate), each passed on only when set}
+             (FluxPipeline.generate), each passed on only when set;
+             cache_threshold=None, cache_max_hits=None -- first-block step caching (FluxPipeline.generate), each passed on only when set}
              ->  image/jpeg stream of FluxPipeline.generate(**args)                                               (reference api.py:54-86)
   /lora      LoraArgs{scale=1.0, path, name, action="load"|"unload"}  ->  {"status": "success"} | 400 invalid action | 500 with the
              exception text; unload uses `name` when given, else `path`                                         (reference api.py:89-122)
@@ -53,6 +54,8 @@ class GenerateArgs(BaseModel):
     negative_prompt: Optional[str] = None  # true classifier-free guidance: what to steer away from ("" is valid); needs true_cfg_scale > 1
     true_cfg_scale: Optional[float] = None  # its scale (diffusers' name); guidance runs iff negative_prompt is set and this is > 1
     true_cfg_interval: Optional[Tuple[float, float]] = None  # [lo, hi], fractions of the steps that are guided (default: all)
+    cache_threshold: Optional[float] = None  # first-block step caching: relative-L1 threshold of the first block's residual (off unless > 0)
+    cache_max_hits: Optional[int] = None  # ... and the most cached steps in a row (0 = no bound)
 
 
 app = FastAPI(title="fluxmi")
@@ -63,9 +66,10 @@ def generate(args: GenerateArgs):
     """JPEG bytes of one image; `init_image` + `strength` select img2img (flux_pipeline.py:399-420,459-523 of the reference);
     `reference_image` selects a FLUX.1 Kontext edit of that image, `mask_image` a FLUX.1 Fill inpainting of `init_image`, `control_image` a
     FLUX.1 Depth / Canny generation, `redux_image` a FLUX.1 Redux image prompt; `negative_prompt` + `true_cfg_scale` (+ `true_cfg_interval`)
-    select true classifier-free guidance.  Without them the call is exactly the reference's."""
+    select true classifier-free guidance, `cache_threshold` (+ `cache_max_hits`) first-block step caching.  Without them the call is exactly the reference's."""
     kwargs = args.model_dump()
-    for k in ("reference_image", "mask_image", "control_image", "redux_image", "negative_prompt", "true_cfg_scale", "true_cfg_interval"):
+    for k in ("reference_image", "mask_image", "control_image", "redux_image", "negative_prompt", "true_cfg_scale", "true_cfg_interval",
+              "cache_threshold", "cache_max_hits"):
         if kwargs.get(k) is None:
             kwargs.pop(k, None)
     result = app.state.model.generate(**kwargs)

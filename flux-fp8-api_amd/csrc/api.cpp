@@ -493,4 +493,21 @@ int fluxmi_cfg_euler(void* img, const void* pred, const float* dts, const int* s
   return fluxmi_k_cfg_euler(img, pred, dts, step, scale, B, img_rows, pred_rows, c_in, c_out, (hipStream_t)stream);
 }
 
+int fluxmi_fb_snapshot(const void* x, long long x_bstride, void* dst, int B, long long n, void* stream) {
+  return fluxmi_k_fb_snapshot(x, x_bstride, dst, B, n, (hipStream_t)stream);
+}
+int fluxmi_fb_commit(const void* x, long long x_bstride, const void* r, void* r_ref, void* h1, int B, long long n, void* stream) {
+  return fluxmi_k_fb_commit(x, x_bstride, r, r_ref, h1, B, n, (hipStream_t)stream);
+}
+int fluxmi_fb_metric(const void* x, long long x_bstride, const void* h0, void* r, const void* r_ref, float* part, float* ratio, float* numden,
+                     int B, long long n, void* stream) {
+  return fluxmi_k_fb_metric(x, x_bstride, h0, r, r_ref, part, ratio, numden, B, n, (hipStream_t)stream);
+}
+int fluxmi_fb_store(const void* x, long long x_bstride, const void* h1, void* R, int B, long long n, void* stream) {
+  return fluxmi_k_fb_store(x, x_bstride, h1, R, B, n, (hipStream_t)stream);
+}
+int fluxmi_fb_apply(void* x, long long x_bstride, const void* h1, long long h1_bstride, const void* R, int B, long long n, void* stream) {
+  return fluxmi_k_fb_apply(x, x_bstride, h1, h1_bstride, R, B, n, (hipStream_t)stream);
+}
+
 }  // extern "C"

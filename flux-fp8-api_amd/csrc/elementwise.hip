@@ -965,3 +965,181 @@ int fluxmi_k_fill_bf16(void* dst, float v, int n, hipStream_t s) {
   FLUXMI_LAUNCH_CHECK();
   return 0;
 }
+
+// ---------------------------------------------------------------------------------------------
+// First-block step cache.  All passes stream B samples of n = rows * H bf16 elements: the `x` side is the residual
+// stream (the caller's pointer is the first cached row of sample 0, batch stride x_bstride elements), the cache side is dense [B, n].
+// 16-byte accesses; workgroup c of sample b owns vectors [c * FB_CHUNK, (c + 1) * FB_CHUNK) of that sample -- a split that depends on n
+// alone, so whatever is summed per workgroup has one order whatever B is and wherever the workgroup runs.
+// ---------------------------------------------------------------------------------------------
+namespace {
+constexpr unsigned FB_VPT = 8;                // 16-byte vectors per thread
+constexpr unsigned FB_CHUNK = 256 * FB_VPT;   // vectors per workgroup (32 KiB of each stream)
+
+// dst = x (h0 snapshot); with dst2 / src2: dst2 = src2 as well (the miss path's commit: h1 <- x, r_ref <- r in one pass)
+__global__ void __launch_bounds__(256) fb_copy_kernel(const u16* __restrict__ x, long long x_bstride, u16* __restrict__ dst,
+                                                      const u16* __restrict__ src2, u16* __restrict__ dst2, unsigned n_vec) {
+  const unsigned b = blockIdx.y;
+  const u16* xb = x + b * x_bstride;
+  const long long cb = (long long)b * n_vec * 8;
+#pragma unroll
+  for (unsigned j = 0; j < FB_VPT; ++j) {
+    const unsigned v = blockIdx.x * FB_CHUNK + j * 256 + threadIdx.x;
+    if (v < n_vec) {
+      *(uint4*)(dst + cb + (long long)v * 8) = *(const uint4*)(xb + (long long)v * 8);
+      if (src2) *(uint4*)(dst2 + cb + (long long)v * 8) = *(const uint4*)(src2 + cb + (long long)v * 8);
+    }
+  }
+}
+
+// fixed-order sum of one value per thread over the 256 threads of a workgroup: xor-butterfly inside each wave, then waves 0..3 in order
+__device__ __forceinline__ float2 fb_block_sum(float a, float c, float2* lds) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    a += __shfl_xor(a, off, 64);
+    c += __shfl_xor(c, off, 64);
+  }
+  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = make_float2(a, c);
+  __syncthreads();
+  float2 t = lds[0];
+#pragma unroll
+  for (int w = 1; w < 4; ++w) { t.x += lds[w].x; t.y += lds[w].y; }
+  return t;
+}
+
+// r = bf16(x - h0) (fp32 subtract of the bf16 values, one rounding); part[b][c] = (sum |r - r_ref|, sum |r_ref|) over workgroup c's vectors.
+// h0 and r may be the same buffer (each element is read, then written, by one thread).
+__global__ void __launch_bounds__(256) fb_metric_kernel(const u16* __restrict__ x, long long x_bstride, const u16* h0, u16* r,
+                                                        const u16* __restrict__ r_ref, float2* __restrict__ part, unsigned n_vec) {
+  __shared__ float2 lds[4];
+  const unsigned b = blockIdx.y;
+  const u16* xb = x + b * x_bstride;
+  const long long cb = (long long)b * n_vec * 8;
+  float num = 0.f, den = 0.f;
+#pragma unroll
+  for (unsigned j = 0; j < FB_VPT; ++j) {
+    const unsigned v = blockIdx.x * FB_CHUNK + j * 256 + threadIdx.x;
+    if (v < n_vec) {
+      const long long o = cb + (long long)v * 8;
+      float fx[8], fh[8], fr[8];
+      unpack8(*(const uint4*)(xb + (long long)v * 8), fx);
+      unpack8(*(const uint4*)(h0 + o), fh);
+      unpack8(*(const uint4*)(r_ref + o), fr);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        fx[k] = rbf(fx[k] - fh[k]);
+        num += fabsf(fx[k] - fr[k]);
+        den += fabsf(fr[k]);
+      }
+      *(uint4*)(r + o) = pack8(fx);
+    }
+  }
+  const float2 t = fb_block_sum(num, den, lds);
+  if (threadIdx.x == 0) part[(long long)b * gridDim.x + blockIdx.x] = t;
+}
+// one workgroup per sample: thread t sums partials t, t + 256, ... in order, then the same fixed tree; ratio = num / den (den == 0: +inf,
+// which no threshold admits)
+__global__ void __launch_bounds__(256) fb_finalise_kernel(const float2* __restrict__ part, unsigned chunks, float* __restrict__ ratio,
+                                                          float* __restrict__ numden) {
+  __shared__ float2 lds[4];
+  const unsigned b = blockIdx.x;
+  float num = 0.f, den = 0.f;
+  for (unsigned c = threadIdx.x; c < chunks; c += 256) {
+    const float2 p = part[(long long)b * chunks + c];
+    num += p.x;
+    den += p.y;
+  }
+  const float2 t = fb_block_sum(num, den, lds);
+  if (threadIdx.x == 0) {
+    ratio[b] = t.y > 0.f ? t.x / t.y : __builtin_inff();
+    if (numden) { numden[2 * b] = t.x; numden[2 * b + 1] = t.y; }
+  }
+}
+// STORE: R = bf16(x - h1)  |  !STORE: x = bf16(h1 + R), h1 may be x itself (the hit path applies in place: x still holds this step's h1)
+template <bool STORE>
+__global__ void __launch_bounds__(256) fb_resid_kernel(u16* x, long long x_bstride, const u16* h1, long long h1_bstride, u16* R, unsigned n_vec) {
+  const unsigned b = blockIdx.y;
+  u16* xb = x + b * x_bstride;
+  const u16* hb = h1 + b * h1_bstride;
+  const long long cb = (long long)b * n_vec * 8;
+#pragma unroll
+  for (unsigned j = 0; j < FB_VPT; ++j) {
+    const unsigned v = blockIdx.x * FB_CHUNK + j * 256 + threadIdx.x;
+    if (v < n_vec) {
+      float fa[8], fb[8];
+      unpack8(*(const uint4*)(hb + (long long)v * 8), fb);
+      if (STORE) {
+        unpack8(*(const uint4*)(xb + (long long)v * 8), fa);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) fa[k] -= fb[k];
+        *(uint4*)(R + cb + (long long)v * 8) = pack8(fa);
+      } else {
+        unpack8(*(const uint4*)(R + cb + (long long)v * 8), fa);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) fa[k] += fb[k];
+        *(uint4*)(xb + (long long)v * 8) = pack8(fa);
+      }
+    }
+  }
+}
+
+}  // namespace
+
+static int fb_shape(const char* who, int B, long long n, long long x_bstride, unsigned* n_vec, unsigned* chunks) {
+  FLUXMI_REQUIRE(B >= 0 && B <= 65535 && n >= 0 && n % 8 == 0 && x_bstride % 8 == 0 && x_bstride >= n && n / 8 <= 0x7fffffffLL,
+                 "%s: bad shape B=%d n=%lld x_bstride=%lld (n and the stride multiples of 8, stride >= n, n / 8 < 2^31)", who, B, n, x_bstride);
+  *n_vec = (unsigned)(n / 8);
+  *chunks = (*n_vec + FB_CHUNK - 1) / FB_CHUNK;
+  return 0;
+}
+
+int fluxmi_k_fb_snapshot(const void* x, long long x_bstride, void* dst, int B, long long n, hipStream_t s) {
+  unsigned nv, ch;
+  FLUXMI_REQUIRE(x && dst, "fb_snapshot: NULL argument");
+  FLUXMI_TRY(fb_shape("fb_snapshot", B, n, x_bstride, &nv, &ch));
+  if (!B || !nv) return 0;
+  hipLaunchKernelGGL(fb_copy_kernel, dim3(ch, B), dim3(256), 0, s, (const u16*)x, x_bstride, (u16*)dst, (const u16*)nullptr, (u16*)nullptr, nv);
+  FLUXMI_LAUNCH_CHECK();
+  return 0;
+}
+int fluxmi_k_fb_commit(const void* x, long long x_bstride, const void* r, void* r_ref, void* h1, int B, long long n, hipStream_t s) {
+  unsigned nv, ch;
+  FLUXMI_REQUIRE(x && r && r_ref && h1, "fb_commit: NULL argument");
+  FLUXMI_TRY(fb_shape("fb_commit", B, n, x_bstride, &nv, &ch));
+  if (!B || !nv) return 0;
+  hipLaunchKernelGGL(fb_copy_kernel, dim3(ch, B), dim3(256), 0, s, (const u16*)x, x_bstride, (u16*)h1, (const u16*)r, (u16*)r_ref, nv);
+  FLUXMI_LAUNCH_CHECK();
+  return 0;
+}
+int fluxmi_k_fb_metric(const void* x, long long x_bstride, const void* h0, void* r, const void* r_ref, float* part, float* ratio,
+                       float* numden, int B, long long n, hipStream_t s) {
+  unsigned nv, ch;
+  FLUXMI_REQUIRE(x && h0 && r && r_ref && part && ratio, "fb_metric: NULL argument");
+  FLUXMI_TRY(fb_shape("fb_metric", B, n, x_bstride, &nv, &ch));
+  FLUXMI_REQUIRE(B >= 1 && nv >= 1, "fb_metric: empty input");
+  hipLaunchKernelGGL(fb_metric_kernel, dim3(ch, B), dim3(256), 0, s, (const u16*)x, x_bstride, (const u16*)h0, (u16*)r, (const u16*)r_ref,
+                     (float2*)part, nv);
+  FLUXMI_LAUNCH_CHECK();
+  hipLaunchKernelGGL(fb_finalise_kernel, dim3(B), dim3(256), 0, s, (const float2*)part, ch, ratio, numden);
+  FLUXMI_LAUNCH_CHECK();
+  return 0;
+}
+int fluxmi_k_fb_store(const void* x, long long x_bstride, const void* h1, void* R, int B, long long n, hipStream_t s) {
+  unsigned nv, ch;
+  FLUXMI_REQUIRE(x && h1 && R, "fb_store: NULL argument");
+  FLUXMI_TRY(fb_shape("fb_store", B, n, x_bstride, &nv, &ch));
+  if (!B || !nv) return 0;
+  hipLaunchKernelGGL(fb_resid_kernel<true>, dim3(ch, B), dim3(256), 0, s, (u16*)x, x_bstride, (const u16*)h1, (long long)n, (u16*)R, nv);
+  FLUXMI_LAUNCH_CHECK();
+  return 0;
+}
+int fluxmi_k_fb_apply(void* x, long long x_bstride, const void* h1, long long h1_bstride, const void* R, int B, long long n, hipStream_t s) {
+  unsigned nv, ch;
+  FLUXMI_REQUIRE(x && h1 && R, "fb_apply: NULL argument");
+  FLUXMI_TRY(fb_shape("fb_apply", B, n, x_bstride, &nv, &ch));
+  FLUXMI_REQUIRE(h1_bstride % 8 == 0 && h1_bstride >= n, "fb_apply: bad h1 stride %lld", h1_bstride);
+  if (!B || !nv) return 0;
+  hipLaunchKernelGGL(fb_resid_kernel<false>, dim3(ch, B), dim3(256), 0, s, (u16*)x, x_bstride, (const u16*)h1, h1_bstride, (u16*)R, nv);
+  FLUXMI_LAUNCH_CHECK();
+  return 0;
+}

@@ -25,7 +25,9 @@
 #include <limits.h>
 #include <stdlib.h>
 #include <string.h>
+#include <math.h>
 #include <algorithm>
+#include <functional>
 #include <map>
 #include <string>
 #include <vector>
@@ -100,6 +102,21 @@ struct fluxmi_engine {
   float* amax_ext = nullptr;
   fluxmi_amax_hook_t amax_hook = nullptr;
   void* amax_user = nullptr;
+  // first-block step cache (fluxmi_engine_set_step_cache).  Threshold, hit counter and log are HOST state: one set of
+  // graphs serves every threshold.  The buffers (h0 | r, h1, r_ref, R, partial sums, ratios) are one allocation made at the first cached
+  // call of a prepared shape and dropped with the workspace; a plain request never allocates, captures or launches any of this.
+  float fb_threshold = 0.f;
+  int fb_max_hits = 0;
+  char* fb_mem = nullptr;
+  size_t fb_bytes = 0;
+  float* h_ratio = nullptr;        // pinned: the B ratios of the step, copied out behind the head piece
+  hipEvent_t ev_fb = nullptr;      // ... and the event the host waits on before it decides
+  hipGraphExec_t fb_exec[3] = {nullptr, nullptr, nullptr};  // head, body (miss), skip (hit)
+  bool fb_graph_ok = false, fb_graph_cfg = false, fb_warmed = false;
+  unsigned fb_graph_gen = 0;
+  int fb_log_B = 0;
+  std::vector<float> fb_log_ratio;          // [frozen steps of the last call][B]
+  std::vector<unsigned char> fb_log_hit;    // [frozen steps of the last call]
 };
 
 namespace {
@@ -852,8 +869,11 @@ int require_all_f8(E* e) {
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// Phases [p0, p1] of the forward: 0 = embedders + modulation vectors, 1 = double block 0, 2 = every later block, 3 = final layer.  The step
+// cache cuts the frozen step between them (head = 0..1, body = 2..3, skip = 3); every other caller runs 0..3, the launches it always ran.
+enum { PH_EMBED = 0, PH_BLOCK0 = 1, PH_BLOCKS = 2, PH_FINAL = 3 };
 int forward_impl(E* e, const u16* img, const u16* txt, const u16* y, const u16* t_vec, const u16* g_vec, u16* pred, int mode,
-                 int trial, bool txt_cached, hipStream_t s) {
+                 int trial, bool txt_cached, hipStream_t s, int p0 = PH_EMBED, int p1 = PH_FINAL) {
   const int H = e->d.hidden, Hm = e->d.mlp_hidden, B = e->B, L = e->L, Lt = e->Lt, Li = e->Li, heads = e->d.heads;
   const bool fused = mode == 1, calib = mode == 0;
   const long long XB = (long long)L * H;  // batch stride of x
@@ -869,7 +889,7 @@ int forward_impl(E* e, const u16* img, const u16* txt, const u16* y, const u16* 
   const Ctx ctx = make_ctx(e);
 
   // ---- img_in / txt_in                                                             flux_model.py:686,699
-  {
+  if (p0 <= PH_EMBED) {
     const fluxmi_linear_t& l = e->lin[e->i_img_in];
     const int C = e->d.in_channels;
     FLUXMI_TRY(stage_input(e, e->i_img_in, calib, trial, img, C, 0, in8, C, 0, 1, B * Li, C, s));
@@ -879,22 +899,28 @@ int forward_impl(E* e, const u16* img, const u16* txt, const u16* y, const u16* 
                             x + b * XB + (long long)Lt * H, H, Li));
     FLUXMI_TRY(run_gemm_fixed_cfg(gs, H, C, l.kind, l.in_fmt, FLUXMI_EPI_BF16, s));
   }
-  if (txt_cached) {
-    FLUXMI_CHECK_HIP(hipMemcpy2DAsync(x, XB * 2, buf<u16>(e, "txt_emb"), (size_t)Lt * H * 2, (size_t)Lt * H * 2, B, hipMemcpyDeviceToDevice, s));
-  } else {
-    FLUXMI_TRY(embed_txt(e, txt, calib, trial, x, XB, s));
-  }
-  if (e->mods_table) {
-    FLUXMI_TRY(fluxmi_k_select_step(e->mods_all, e->d_step, e->d_step0, mod, (long long)B * MC * 2, s));
-  } else {
-    FLUXMI_TRY(compute_vec_and_mods(e, t_vec, g_vec, y, calib, trial, s));
+  if (p0 <= PH_EMBED) {
+    if (txt_cached) {
+      FLUXMI_CHECK_HIP(hipMemcpy2DAsync(x, XB * 2, buf<u16>(e, "txt_emb"), (size_t)Lt * H * 2, (size_t)Lt * H * 2, B, hipMemcpyDeviceToDevice, s));
+    } else {
+      FLUXMI_TRY(embed_txt(e, txt, calib, trial, x, XB, s));
+    }
+    if (e->mods_table) {
+      FLUXMI_TRY(fluxmi_k_select_step(e->mods_all, e->d_step, e->d_step0, mod, (long long)B * MC * 2, s));
+    } else {
+      FLUXMI_TRY(compute_vec_and_mods(e, t_vec, g_vec, y, calib, trial, s));
+    }
   }
 
-  for (int i = 0; i < e->d.depth; ++i) FLUXMI_TRY(double_block(e, ctx, i, mode, trial, 0, DOUBLE_STAGES - 1, s));
-  for (int i = 0; i < e->d.depth_single; ++i) FLUXMI_TRY(single_block(e, ctx, i, mode, trial, 0, SINGLE_STAGES - 1, s));
+  for (int i = 0; i < e->d.depth; ++i) {
+    const int ph = i == 0 ? PH_BLOCK0 : PH_BLOCKS;
+    if (ph >= p0 && ph <= p1) FLUXMI_TRY(double_block(e, ctx, i, mode, trial, 0, DOUBLE_STAGES - 1, s));
+  }
+  if (p0 <= PH_BLOCKS && p1 >= PH_BLOCKS)
+    for (int i = 0; i < e->d.depth_single; ++i) FLUXMI_TRY(single_block(e, ctx, i, mode, trial, 0, SINGLE_STAGES - 1, s));
 
   // ---- final layer                                                                flux_model.py:499-503, 714-715
-  FLUXMI_TRY(final_layer(e, pred, 0, 1, s));
+  if (p1 >= PH_FINAL) FLUXMI_TRY(final_layer(e, pred, 0, 1, s));
   return 0;
 }
 
@@ -925,12 +951,46 @@ struct SplitkScope {
 
 void free_ws(E* e) {
   if (e->exec) { hipGraphExecDestroy(e->exec); e->exec = nullptr; }
+  for (hipGraphExec_t& g : e->fb_exec)
+    if (g) { hipGraphExecDestroy(g); g = nullptr; }
   e->graph_ok = false;
   e->warmed = false;
+  e->fb_graph_ok = false;
+  e->fb_warmed = false;
   e->qlut_valid = false;
+  if (e->fb_mem) { hipFree(e->fb_mem); e->fb_mem = nullptr; e->fb_bytes = 0; }
   if (e->ws) { hipFree(e->ws); e->ws = nullptr; }
   e->bufs.clear();
   e->ws_bytes = 0;
+}
+
+// the step cache's buffers for the prepared shape, made once a cached request arrives (a plain request's workspace stays what it was)
+constexpr long long FB_CHUNK_ELEMS = 16384;  // elements per workgroup of the metric pass (elementwise.hip, FB_CHUNK vectors)
+int ensure_fb(E* e, hipStream_t s) {
+  if (!e->h_ratio) FLUXMI_CHECK_HIP(hipHostMalloc((void**)&e->h_ratio, FLUXMI_ENGINE_MAX_BATCH * sizeof(float), hipHostMallocDefault));
+  if (!e->ev_fb) FLUXMI_CHECK_HIP(hipEventCreateWithFlags(&e->ev_fb, hipEventDisableTiming));
+  if (e->fb_mem) return 0;
+  const size_t n = (size_t)e->Lpred * e->d.hidden, rows = (size_t)e->B * n * 2;
+  const size_t chunks = (n + FB_CHUNK_ELEMS - 1) / FB_CHUNK_ELEMS;
+  struct Item { const char* name; size_t bytes; };
+  const Item items[] = {{"fb_h0", rows}, {"fb_h1", rows}, {"fb_rref", rows}, {"fb_R", rows}, {"fb_part", (size_t)e->B * chunks * 8},
+                        {"fb_ratio", (size_t)e->B * 3 * 4}};
+  size_t total = 0;
+  for (auto& it : items) total += (it.bytes + 255) & ~(size_t)255;
+  if (hipMalloc((void**)&e->fb_mem, total) != hipSuccess) {
+    (void)hipGetLastError();
+    e->fb_mem = nullptr;
+    fluxmi_set_error("engine_denoise: hipMalloc(%zu bytes) failed (step cache)", total);
+    return 2;
+  }
+  e->fb_bytes = total;
+  FLUXMI_CHECK_HIP(hipMemsetAsync(e->fb_mem, 0, total, s));
+  size_t off = 0;
+  for (auto& it : items) {
+    e->bufs[it.name] = Buf{e->fb_mem + off, it.bytes};
+    off += (it.bytes + 255) & ~(size_t)255;
+  }
+  return 0;
 }
 
 }  // namespace
@@ -1030,6 +1090,8 @@ int fluxmi_engine_destroy(fluxmi_engine_t* e) {
   if (e->ev_sched) hipEventDestroy(e->ev_sched);
   if (e->ev_t0) hipEventDestroy(e->ev_t0);
   if (e->ev_t1) hipEventDestroy(e->ev_t1);
+  if (e->h_ratio) hipHostFree(e->h_ratio);
+  if (e->ev_fb) hipEventDestroy(e->ev_fb);
   delete e;
   return 0;
 }
@@ -1039,6 +1101,8 @@ int fluxmi_engine_rebind(fluxmi_engine_t* e, const fluxmi_linear_t* linears, int
   e->lin.assign(linears, linears + n_linears);
   e->graph_ok = false;
   e->warmed = false;
+  e->fb_graph_ok = false;
+  e->fb_warmed = false;
   e->txt_emb_valid = false;
   e->pairs_dirty = true;
   e->qlut_valid = false;
@@ -1165,6 +1229,140 @@ int fluxmi_engine_forward(fluxmi_engine_t* e, const void* img, const void* txt, 
 }
 
 
+// ---------------------------------------------------------------------------------------------------------
+// The frozen steps [step, n_steps) with first-block step caching (fluxmi.h, fluxmi_engine_set_step_cache).
+//   head: img_in, txt rows, select_step | h0 = x rows | double block 0 | r = bf16(x - h0) over h0, ratios -> pinned host
+//   host: waits for the head, reads the B ratios, decides
+//   body (miss): r_ref = r, h1 = x | blocks 1 .. | R = bf16(x - h1) | final layer, update, advance
+//   skip (hit):  x = bf16(x + R) (x still holds this step's h1) | final layer, update, advance
+// on the rows the final layer reads.  Each piece is one captured graph (first step of a shape eager, re-captured with the tuning generation
+// and the update kind, like the plain step's graph); use_graph = 0 runs the same pieces eagerly.
+// ---------------------------------------------------------------------------------------------------------
+static int denoise_cached(fluxmi_engine_t* e, int mode, bool cfg, int step, int n_steps, const u16* g_arg, int use_graph,
+                          const std::function<int(hipStream_t)>& euler, int* first_timed, hipStream_t s) {
+  FLUXMI_REQUIRE(e->d.depth >= 1, "engine_denoise: step caching needs at least one double block");
+  FLUXMI_TRY(ensure_fb(e, s));
+  const int B = e->B, H = e->d.hidden;
+  const long long XB = (long long)e->L * H, n = (long long)e->Lpred * H;
+  u16 *img_s = buf<u16>(e, "img_s"), *txt_s = buf<u16>(e, "txt_s"), *y_s = buf<u16>(e, "y_s"), *pred_s = buf<u16>(e, "pred_s");
+  u16* tvec = buf<u16>(e, "tvec");
+  u16* xr = buf<u16>(e, "x") + (long long)e->Lt * H;  // the rows the final layer reads: Lpred rows behind the text rows of each sample
+  u16 *h0 = buf<u16>(e, "fb_h0"), *h1 = buf<u16>(e, "fb_h1"), *rref = buf<u16>(e, "fb_rref"), *R = buf<u16>(e, "fb_R");
+  float *part = buf<float>(e, "fb_part"), *ratio = buf<float>(e, "fb_ratio");
+  auto fwd = [&](int p0, int p1, hipStream_t st) -> int {
+    e->mods_table = true;
+    const int rc = forward_impl(e, img_s, txt_s, y_s, tvec, g_arg, pred_s, mode, 0, mode == 1, st, p0, p1);
+    e->mods_table = false;
+    return rc;
+  };
+  auto head = [&](hipStream_t st) -> int {
+    FLUXMI_TRY(fwd(PH_EMBED, PH_EMBED, st));
+    FLUXMI_TRY(fluxmi_k_fb_snapshot(xr, XB, h0, B, n, st));
+    FLUXMI_TRY(fwd(PH_BLOCK0, PH_BLOCK0, st));
+    FLUXMI_TRY(fluxmi_k_fb_metric(xr, XB, h0, h0, rref, part, ratio, ratio + B, B, n, st));
+    FLUXMI_CHECK_HIP(hipMemcpyAsync(e->h_ratio, ratio, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+    return 0;
+  };
+  auto tail = [&](hipStream_t st) -> int {
+    FLUXMI_TRY(fwd(PH_FINAL, PH_FINAL, st));
+    FLUXMI_TRY(euler(st));
+    return fluxmi_k_advance_step(e->d_step, st);
+  };
+  auto body = [&](hipStream_t st) -> int {
+    FLUXMI_TRY(fluxmi_k_fb_commit(xr, XB, h0, rref, h1, B, n, st));
+    FLUXMI_TRY(fwd(PH_BLOCKS, PH_BLOCKS, st));
+    FLUXMI_TRY(fluxmi_k_fb_store(xr, XB, h1, R, B, n, st));
+    return tail(st);
+  };
+  auto skip = [&](hipStream_t st) -> int {
+    FLUXMI_TRY(fluxmi_k_fb_apply(xr, XB, xr, XB, R, B, n, st));
+    return tail(st);
+  };
+  const std::function<int(hipStream_t)> pieces[3] = {head, body, skip};
+  // host state of the rule
+  bool have_full = false;  // a full step has run in THIS call: every call starts with an empty cache
+  int consec = 0;
+  e->fb_log_B = B;
+  auto one_step = [&](bool graph) -> int {
+    if (graph) FLUXMI_CHECK_HIP(hipGraphLaunch(e->fb_exec[0], s));
+    else FLUXMI_TRY(head(s));
+    FLUXMI_CHECK_HIP(hipEventRecord(e->ev_fb, s));
+    FLUXMI_CHECK_HIP(hipEventSynchronize(e->ev_fb));
+    bool hit = have_full && (e->fb_max_hits <= 0 || consec < e->fb_max_hits);
+    for (int b = 0; b < B; ++b) {
+      const float r = have_full ? e->h_ratio[b] : INFINITY;  // no reference yet: the step misses whatever r_ref still holds
+      e->fb_log_ratio.push_back(r);
+      hit = hit && r < e->fb_threshold;  // NaN and +inf (den == 0) are misses
+    }
+    e->fb_log_hit.push_back(hit ? 1 : 0);
+    consec = hit ? consec + 1 : 0;
+    have_full = have_full || !hit;
+    if (graph) FLUXMI_CHECK_HIP(hipGraphLaunch(e->fb_exec[hit ? 2 : 1], s));
+    else FLUXMI_TRY(hit ? skip(s) : body(s));
+    return 0;
+  };
+  bool t0 = false;
+  while (step < n_steps) {
+    const int win_end = std::min(n_steps, step + MODS_STEPS);
+    {
+      Range r("step-ahead modulation table");
+      FLUXMI_TRY(precompute_mods(e, step, win_end, g_arg, y_s, s));
+    }
+    if (e->fb_graph_ok && (e->fb_graph_gen != fluxmi_tuning_generation() || e->fb_graph_cfg != cfg)) {
+      e->fb_graph_ok = false;  // kernel choices and the update kernel are baked into the captured pieces
+      e->fb_warmed = false;
+      e->qlut_valid = false;
+    }
+    if (use_graph && !e->fb_graph_ok) {
+      if (!e->fb_warmed) {
+        // lazy one-time inits happen outside capture: this step runs eagerly -- head and body, it is the first frozen step of a call and
+        // misses -- and the skip piece's own kernel is launched once on x's image rows, which are dead here (img_in rewrites them next)
+        FLUXMI_REQUIRE(!have_full, "engine_denoise: step-cache warm-up behind a full step");
+        FLUXMI_TRY(fluxmi_k_fb_apply(xr, XB, xr, XB, R, B, n, s));
+        FLUXMI_TRY(one_step(false));
+        ++step;
+        e->fb_warmed = true;
+      }
+      if (step < win_end) {
+        hipStream_t cs;
+        FLUXMI_CHECK_HIP(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
+        FLUXMI_CHECK_HIP(hipStreamSynchronize(s));  // one-time, at graph capture only
+        for (int p = 0; p < 3; ++p) {
+          hipGraph_t graph = nullptr;
+          hipError_t ce = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal);
+          const int rc = ce == hipSuccess ? pieces[p](cs) : 0;
+          if (ce == hipSuccess) ce = hipStreamEndCapture(cs, &graph);
+          if (e->fb_exec[p]) { hipGraphExecDestroy(e->fb_exec[p]); e->fb_exec[p] = nullptr; }
+          if (!rc && ce == hipSuccess) ce = hipGraphInstantiate(&e->fb_exec[p], graph, nullptr, nullptr, 0);
+          if (graph) hipGraphDestroy(graph);
+          if (rc || ce != hipSuccess) {
+            hipStreamDestroy(cs);
+            if (!rc) fluxmi_set_error("engine_denoise: capturing step-cache piece %d failed: %s", p, hipGetErrorString(ce));
+            return rc ? rc : 2;
+          }
+        }
+        hipStreamDestroy(cs);
+        e->fb_graph_ok = true;
+        e->fb_graph_gen = fluxmi_tuning_generation();
+        e->fb_graph_cfg = cfg;
+      }
+    }
+    Range r("frozen steps (step cache)");
+    if (!t0) {
+      FLUXMI_CHECK_HIP(hipEventRecord(e->ev_t0, s));
+      *first_timed = step;
+      t0 = true;
+    }
+    const bool graph = use_graph && e->fb_graph_ok;
+    for (; step < win_end; ++step) FLUXMI_TRY(one_step(graph));
+    if (graph) {  // the replayed pieces wrote the activation buffers in the layout they were captured with
+      const bool ap = act_pairs(e, mode == 1);
+      for (bool& b : e->act_in_pairs) b = ap;
+    }
+  }
+  return 0;
+}
+
 // the denoise loop, plain or guided (cfg: true classifier-free guidance).  Guided: the prepared batch B is 2 Bh, samples [0, Bh) the prompt
 // branch and [Bh, B) the negative branch of the caller's Bh images; the caller's img [Bh, ...] is copied into both halves of the stream, every
 // forward runs on the B samples, and the update is fluxmi_k_cfg_euler, which keeps the halves bit-identical.
@@ -1243,6 +1441,8 @@ static int denoise_impl(fluxmi_engine_t* e, void* img, const void* txt, const vo
   }
   // -- frozen steps -------------------------------------------------------------------------------------------
   e->timed_steps = 0;
+  e->fb_log_ratio.clear();
+  e->fb_log_hit.clear();
   if (step < n_steps) {
     const int mode = all_f8 ? 1 : 2;
     if (mode == 1) {
@@ -1262,6 +1462,11 @@ static int denoise_impl(fluxmi_engine_t* e, void* img, const void* txt, const vo
     // warm step and the graph capture of a new shape (a request longer than MODS_STEPS steps includes its later table builds)
     bool t0_recorded = false;
     int first_timed = step;
+    if (e->fb_threshold > 0.f) {  // first-block step caching: the same steps as head / body / skip pieces with a host decision in between
+      FLUXMI_TRY(denoise_cached(e, mode, cfg, step, n_steps, g_arg, use_graph, euler, &first_timed, s));
+      t0_recorded = true;
+      step = n_steps;
+    }
     // the modulation vectors of up to MODS_STEPS steps are produced ahead (one pass over the 3.2 GB of modulation weights per window);
     // the table address and the device-side window origin never change, so ONE captured graph serves every step of every request
     while (step < n_steps) {
@@ -1344,6 +1549,48 @@ int fluxmi_engine_denoise_cfg(fluxmi_engine_t* e, void* img, const void* txt, co
   return denoise_impl(e, img, txt, y, guidance, true, cfg_scale, timesteps_host, n_steps, trial_index_inout, use_graph, stream);
 }
 
+int fluxmi_engine_set_step_cache(fluxmi_engine_t* e, float threshold, int max_consecutive_hits) {
+  FLUXMI_REQUIRE(e, "engine_set_step_cache: NULL engine");
+  FLUXMI_REQUIRE(threshold >= 0.f, "engine_set_step_cache: threshold %g must be >= 0 and not NaN (0 = off)", (double)threshold);
+  FLUXMI_REQUIRE(max_consecutive_hits >= 0, "engine_set_step_cache: max_consecutive_hits %d must be >= 0 (0 = unbounded)", max_consecutive_hits);
+  e->fb_threshold = threshold;
+  e->fb_max_hits = max_consecutive_hits;
+  return 0;
+}
+
+int fluxmi_engine_step_cache_log(fluxmi_engine_t* e, int* n, int* batch, float* ratios, unsigned char* hit, int cap) {
+  FLUXMI_REQUIRE(e && n && batch && cap >= 0 && (cap == 0 || (ratios && hit)), "engine_step_cache_log: bad arguments");
+  const int steps = (int)e->fb_log_hit.size(), m = std::min(steps, cap);
+  *n = steps;
+  *batch = steps ? e->fb_log_B : 0;
+  for (int i = 0; i < m; ++i) hit[i] = e->fb_log_hit[i];
+  for (long long i = 0; i < (long long)m * e->fb_log_B; ++i) ratios[i] = e->fb_log_ratio[i];
+  return 0;
+}
+
+int fluxmi_engine_run_phase(fluxmi_engine_t* e, int mode, int phase_from, int phase_to, int step, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  FLUXMI_REQUIRE(e && e->ws, "engine_run_phase: call fluxmi_engine_prepare first");
+  FLUXMI_REQUIRE(mode == 1 || mode == 2, "engine_run_phase: mode must be 1 (fused) or 2 (unfused, frozen scales)");
+  FLUXMI_REQUIRE(phase_from >= PH_EMBED && phase_to <= PH_FINAL && phase_from <= phase_to, "engine_run_phase: phases [%d, %d] out of range (0..3)",
+                 phase_from, phase_to);
+  FLUXMI_REQUIRE(step < 0 || (e->mods_all && step >= e->mods_step0 && step < e->mods_step0 + MODS_STEPS),
+                 "engine_run_phase: step %d is outside the modulation table of the last denoise call (from step %d)", step, e->mods_step0);
+  FLUXMI_REQUIRE(mode == 2 || phase_from > PH_EMBED || e->txt_emb_valid, "engine_run_phase: no embedded text from a denoise call on this shape");
+  SplitkScope splitk(e);
+  FLUXMI_TRY(ensure_pairs(e, s));
+  if (mode == 1) {
+    FLUXMI_TRY(require_all_f8(e));
+    FLUXMI_TRY(build_qluts(e, s));
+  }
+  if (step >= 0) FLUXMI_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)e->d_step, step, 1, s));
+  e->mods_table = true;
+  const int rc = forward_impl(e, buf<u16>(e, "img_s"), buf<u16>(e, "txt_s"), buf<u16>(e, "y_s"), buf<u16>(e, "tvec"), buf<u16>(e, "gvec"),
+                              buf<u16>(e, "pred_s"), mode, 0, mode == 1, s, phase_from, phase_to);
+  e->mods_table = false;
+  return rc;
+}
+
 int fluxmi_engine_last_timing(fluxmi_engine_t* e, float* ms, int* steps) {
   FLUXMI_REQUIRE(e && ms && steps, "engine_last_timing: NULL argument");
   *ms = 0.f; *steps = e->timed_steps;
@@ -1422,7 +1669,7 @@ int fluxmi_engine_copy_buffer(fluxmi_engine_t* e, const char* name, long long of
 
 int fluxmi_engine_workspace_bytes(fluxmi_engine_t* e, long long* bytes) {
   FLUXMI_REQUIRE(e && bytes, "engine_workspace_bytes: NULL argument");
-  *bytes = (long long)(e->ws_bytes + e->pairs_bytes + e->mods_all_bytes);  // workspace + row-pair weight copies + modulation table
+  *bytes = (long long)(e->ws_bytes + e->pairs_bytes + e->mods_all_bytes + e->fb_bytes);  // workspace + row-pair weight copies + modulation table + step cache
   return 0;
 }
 

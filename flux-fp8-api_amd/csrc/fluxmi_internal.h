@@ -165,6 +165,13 @@ int fluxmi_k_euler_cols(void* img, const void* pred, const float* dts, const int
 // x + bf16(dt * (u + s (c - u))) with one bf16 rounding per operation, s = *scale (device), dt = dts[*step]
 int fluxmi_k_cfg_euler(void* img, const void* pred, const float* dts, const int* step, const float* scale, int B, long long img_rows,
                        long long pred_rows, int c_in, int c_out, hipStream_t s);
+// first-block step cache (elementwise.hip): streaming passes over B samples of n bf16 elements, x side strided, cache side dense
+int fluxmi_k_fb_snapshot(const void* x, long long x_bstride, void* dst, int B, long long n, hipStream_t s);
+int fluxmi_k_fb_commit(const void* x, long long x_bstride, const void* r, void* r_ref, void* h1, int B, long long n, hipStream_t s);
+int fluxmi_k_fb_metric(const void* x, long long x_bstride, const void* h0, void* r, const void* r_ref, float* part, float* ratio,
+                       float* numden, int B, long long n, hipStream_t s);
+int fluxmi_k_fb_store(const void* x, long long x_bstride, const void* h1, void* R, int B, long long n, hipStream_t s);
+int fluxmi_k_fb_apply(void* x, long long x_bstride, const void* h1, long long h1_bstride, const void* R, int B, long long n, hipStream_t s);
 int fluxmi_k_set_timestep(void* t_vec, const float* ts, const int* step, int B, hipStream_t s);
 int fluxmi_k_advance_step(int* step, hipStream_t s);
 int fluxmi_k_clock_sample(unsigned long long* out2, hipStream_t s);

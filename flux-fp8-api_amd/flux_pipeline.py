@@ -481,7 +481,7 @@ class FluxPipeline:
                  return_seed: bool = False, jpeg_quality: int = 99, output_type: str = "jpeg", noise: Optional[torch.Tensor] = None,
                  use_graph: bool = True, reference_image=None, mask_image=None, control_image=None,
                  img_cond: Optional[torch.Tensor] = None, redux_image=None, negative_prompt=None, true_cfg_scale: float = 1.0,
-                 true_cfg_interval=(0.0, 1.0)):
+                 true_cfg_interval=(0.0, 1.0), cache_threshold: float = 0.0, cache_max_hits: int = 0):
         """`reference_image` (FLUX.1 Kontext [dev] instruction editing): an image the prompt describes an edit of, in any form `init_image`
         takes; see prepare_kontext_reference.  Composes with `init_image` / `strength` unchanged.
         FLUX.1 Fill [dev] (a model with 320 conditioning channels): `init_image` is the image to inpaint and `mask_image` (white =
@@ -503,7 +503,20 @@ class FluxPipeline:
         so the guidance then acts on the text alone.  A seed draws the same noise with and without a negative prompt.
         `true_cfg_interval=(lo, hi)`, fractions of the request's n steps: step i (0-based) is guided iff lo n <= i < hi n, the others run
         the prompt alone.  Run as up to three consecutive denoise calls on slices of the schedule; the engine keeps one workspace and one
-        graph, so every switch re-allocates and re-captures (README: measured)."""
+        graph, so every switch re-allocates and re-captures (README: measured).
+        `cache_threshold` > 0 (+ `cache_max_hits`): first-block step caching (Flux.denoise; diffusers' FirstBlockCacheConfig): a frozen step
+        whose first double block's residual moved by less than the threshold since the last full step skips every later block and reuses
+        that step's residual.  Off by default; an approximation when on -- no threshold is recommended here (README).  Each of the up to
+        three denoise calls of a `true_cfg_interval` request starts with an empty cache."""
+        try:
+            cache_threshold, cache_max_hits = float(cache_threshold), int(cache_max_hits)
+        except (TypeError, ValueError):
+            raise ValueError(f"fluxmi: cache_threshold={cache_threshold!r} / cache_max_hits={cache_max_hits!r}: expected a number and an integer") from None
+        if not (math.isfinite(cache_threshold) and cache_threshold >= 0.0):
+            raise ValueError(f"fluxmi: cache_threshold={cache_threshold}: expected a finite value >= 0 (0 = off)")
+        if cache_max_hits < 0:
+            raise ValueError(f"fluxmi: cache_max_hits={cache_max_hits}: expected >= 0 (0 = no bound)")
+        cache = dict(cache_threshold=cache_threshold, cache_max_hits=cache_max_hits) if cache_threshold > 0 else {}
         if redux_image is not None:
             self._require_redux()
         if negative_prompt is None and true_cfg_scale > 1:
@@ -619,7 +632,7 @@ class FluxPipeline:
             for a, b, kw in ((0, g0, {}), (g0, g1, neg), (g1, n, {})) if g0 < g1 else ((0, n, {}),):
                 if a < b or n == 0:
                     latents = self.model.denoise(latents, img_ids, txt, txt_ids, vec, timesteps[a:b + 1], guidance=guidance, use_graph=use_graph,
-                                                 **cond, **kw)
+                                                 **cond, **kw, **cache)
         if world > 1:
             latents = fdist.gather_latents(latents, num_images, dst=0)
             if latents is None:  # only the gather rank decodes / returns the images

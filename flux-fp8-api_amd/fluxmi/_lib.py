@@ -101,6 +101,11 @@ _SIGS = {
     "fluxmi_timestep_embedding": ([vp, vp, vp, i32, i32, f32, vp], i32),
     "fluxmi_euler": ([vp, vp, vp, vp, i64, vp], i32),
     "fluxmi_cfg_euler": ([vp, vp, vp, vp, vp, i32, i64, i64, i32, i32, vp], i32),
+    "fluxmi_fb_snapshot": ([vp, i64, vp, i32, i64, vp], i32),
+    "fluxmi_fb_metric": ([vp, i64, vp, vp, vp, vp, vp, vp, i32, i64, vp], i32),
+    "fluxmi_fb_commit": ([vp, i64, vp, vp, vp, i32, i64, vp], i32),
+    "fluxmi_fb_store": ([vp, i64, vp, vp, i32, i64, vp], i32),
+    "fluxmi_fb_apply": ([vp, i64, vp, i64, vp, i32, i64, vp], i32),
     "fluxmi_engine_num_linears": ([C.POINTER(ModelDesc)], i32),
     "fluxmi_engine_create": ([C.POINTER(ModelDesc), C.POINTER(Linear), i32, C.POINTER(vp), i32, C.POINTER(vp)], i32),
     "fluxmi_engine_destroy": ([vp], i32),
@@ -117,6 +122,9 @@ _SIGS = {
     "fluxmi_engine_set_amax_exchange": ([vp, vp, i32, vp, vp], i32),
     "fluxmi_engine_run_block": ([vp, i32, i32, i32, i32, i32, vp], i32),
     "fluxmi_engine_copy_buffer": ([vp, C.c_char_p, i64, vp, i64, i32, vp], i32),
+    "fluxmi_engine_set_step_cache": ([vp, f32, i32], i32),
+    "fluxmi_engine_step_cache_log": ([vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(f32), C.POINTER(C.c_ubyte), i32], i32),
+    "fluxmi_engine_run_phase": ([vp, i32, i32, i32, i32, vp], i32),
 }
 AMAX_HOOK = C.CFUNCTYPE(i32, vp, i32, i32, vp)
 EXPORTS = sorted(list(_SIGS) + ["fluxmi_last_error"])

@@ -512,7 +512,7 @@ class Flux(nn.Module):
     def denoise(self, img: Tensor, img_ids: Tensor, txt: Tensor, txt_ids: Tensor, y: Tensor, timesteps: List[float],
                 guidance: float = 3.5, use_graph: bool = True, img_cond_seq: Tensor | None = None,
                 img_cond_seq_ids: Tensor | None = None, img_cond: Tensor | None = None, neg_txt: Tensor | None = None,
-                neg_y: Tensor | None = None, cfg_scale: float = 1.0) -> Tensor:
+                neg_y: Tensor | None = None, cfg_scale: float = 1.0, cache_threshold: float = 0.0, cache_max_hits: int = 0) -> Tensor:
         """The Euler loop of FluxPipeline.generate (reference flux_pipeline.py:619-651) run natively: calibrating
         steps unfused, every later step one replay of a captured hipGraph.  Returns the final latent tokens.
         FLUX.1 Kontext: with `img_cond_seq` / `img_cond_seq_ids` the reference tokens join every step's forward and are never stepped; the
@@ -522,7 +522,14 @@ class Flux(nn.Module):
         True classifier-free guidance: with `neg_txt` [1 or B, Lt, ctx] / `neg_y` [1 or B, vec] (both or neither; the prompt's Lt) every step
         predicts both branches in ONE forward on 2B samples (prompt branches first, ids and conditioning duplicated) and steps the shared
         latent with `u + cfg_scale * (c - u)` (csrc/elementwise.hip, cfg_euler_kernel); any `cfg_scale` is taken as given.  At most 16 images
-        per pass then, more run as equal passes (frozen scales only); the two branches of an image always share a pass."""
+        per pass then, more run as equal passes (frozen scales only); the two branches of an image always share a pass.
+        First-block step caching: `cache_threshold` > 0 lets a frozen step whose first double block's residual moved by less than that
+        (relative L1, per sample; every sample of the pass must agree) reuse the remaining blocks' residual of the last full step instead of
+        running them; at most `cache_max_hits` such steps in a row (0 = no bound).  0 (the default) = off: the call is today's, bit for bit.
+        Every call starts with an empty cache; `step_cache_log()` tells what the last call did."""
+        cache_threshold, cache_max_hits = float(cache_threshold), int(cache_max_hits)
+        if not (math.isfinite(cache_threshold) and cache_threshold >= 0.0) or cache_max_hits < 0:
+            raise ValueError(f"cache_threshold {cache_threshold} must be finite and >= 0 (0 = off), cache_max_hits {cache_max_hits} >= 0 (0 = no bound)")
         bf = lambda t: t.to(torch.bfloat16).contiguous()
         kontext = img_cond_seq is not None or img_cond_seq_ids is not None
         guided = neg_txt is not None or neg_y is not None
@@ -560,7 +567,7 @@ class Flux(nn.Module):
                 if guided:
                     cond.update(neg_txt=pick(neg_txt), neg_y=pick(neg_y), cfg_scale=cfg_scale)
                 o = self.denoise(pick(img), pick(img_ids), pick(txt), pick(txt_ids), pick(y), timesteps, guidance=guidance, use_graph=use_graph,
-                                 **cond)
+                                 cache_threshold=cache_threshold, cache_max_hits=cache_max_hits, **cond)
                 outs.append(o[:per - pad])
             return torch.cat(outs, 0)
         Li = img.shape[1]
@@ -576,6 +583,7 @@ class Flux(nn.Module):
             trial = self._trial_counter()
             t_io = C.c_int(trial if trial is not None else 0)
             ts = (C.c_double * len(timesteps))(*[float(t) for t in timesteps])
+            _lib.call("fluxmi_engine_set_step_cache", self._engine, cache_threshold, cache_max_hits)
             if guided:
                 _lib.call("fluxmi_engine_denoise_cfg", self._engine, ops._p(img), ops._p(txt), ops._p(y), float(guidance), float(cfg_scale), ts,
                           len(timesteps) - 1, C.byref(t_io), int(use_graph), ops._stream())
@@ -587,6 +595,22 @@ class Flux(nn.Module):
         if self.in_channels != self.out_channels:
             return img[..., :self.out_channels].contiguous()
         return img[:, :Li].contiguous() if Lc else img
+
+    def step_cache_log(self):
+        """What first-block step caching did in the last `denoise` call (the last pass of a chunked batch): `(ratios, hits)` with
+        `ratios` a float32 tensor [frozen steps, samples of the pass] (inf where no reference existed yet: the first frozen step) and `hits` a
+        list of bools, one per frozen step.  Empty after a call with `cache_threshold=0`."""
+        if self._engine is None:
+            return torch.zeros(0, 0), []
+        with self._lock:
+            n, B = C.c_int(0), C.c_int(0)
+            _lib.call("fluxmi_engine_step_cache_log", self._engine, C.byref(n), C.byref(B), None, None, 0)
+            if n.value == 0:
+                return torch.zeros(0, 0), []
+            r = (C.c_float * (n.value * B.value))()
+            h = (C.c_ubyte * n.value)()
+            _lib.call("fluxmi_engine_step_cache_log", self._engine, C.byref(n), C.byref(B), r, h, n.value)
+        return torch.tensor(list(r), dtype=torch.float32).reshape(n.value, B.value), [bool(v) for v in h]
 
     @classmethod
     def from_pretrained(cls, path: str, dtype: torch.dtype = torch.float16) -> "Flux":

@@ -358,6 +358,25 @@ int fluxmi_euler(void* img, const void* pred, const float* dts, const int* step,
 int fluxmi_cfg_euler(void* img, const void* pred, const float* dts, const int* step, const float* scale, int B, long long img_rows,
                      long long pred_rows, int c_in, int c_out, void* stream);
 
+/* ---- first-block step cache: the streaming passes --------------------------------------
+ * B samples of n bf16 elements each (n = cached rows x hidden, n %% 8 == 0).  The `x` side is the residual stream: the pointer is the first
+ * cached row of sample 0, x_bstride the batch stride in elements; every other tensor is dense [B, n].  16-byte accesses; workgroup c of a
+ * sample owns its elements [c * 16384, (c + 1) * 16384).
+ *   snapshot: dst = x                                              (h0, before double block 0)
+ *   metric:   r = bf16(x - h0)  (fp32 subtract, one rounding; r may be h0's buffer);  num_b = sum |r - r_ref|, den_b = sum |r_ref| in fp32,
+ *             ratio[b] = num_b / den_b (+inf when den_b == 0), numden[2b], numden[2b + 1] = num_b, den_b (numden may be NULL).  Two stages, no
+ *             atomics: per-workgroup partials into `part` (float [B][ceil(n / 16384)][2], scratch), then one workgroup per sample adds them
+ *             in a fixed order.  A sample's three numbers depend on its own n elements only: same bits alone, in any batch, at every launch.
+ *   commit:   r_ref = r, h1 = x                                    (a miss, before the remaining blocks run)
+ *   store:    R = bf16(x - h1)                                     (a miss, after the last single block)
+ *   apply:    x = bf16(h1 + R); h1 strided like x (h1_bstride) and allowed to be x itself  (a hit) */
+int fluxmi_fb_snapshot(const void* x, long long x_bstride, void* dst, int B, long long n, void* stream);
+int fluxmi_fb_metric(const void* x, long long x_bstride, const void* h0, void* r, const void* r_ref, float* part, float* ratio, float* numden,
+                     int B, long long n, void* stream);
+int fluxmi_fb_commit(const void* x, long long x_bstride, const void* r, void* r_ref, void* h1, int B, long long n, void* stream);
+int fluxmi_fb_store(const void* x, long long x_bstride, const void* h1, void* R, int B, long long n, void* stream);
+int fluxmi_fb_apply(void* x, long long x_bstride, const void* h1, long long h1_bstride, const void* R, int B, long long n, void* stream);
+
 /* ---- whole-model engine ------------------------------------------------------------------------------- */
 typedef struct fluxmi_linear {
   const void* weight;      /* fp8 float8_data [N,K] (kind 1) or bf16 weight [N,K] (kind 0) */
@@ -469,6 +488,29 @@ int fluxmi_engine_get_buffer(fluxmi_engine_t* e, const char* name, void** ptr, l
 int fluxmi_engine_run_block(fluxmi_engine_t* e, int kind, int index, int mode, int stage_from, int stage_to, void* stream);
 int fluxmi_engine_copy_buffer(fluxmi_engine_t* e, const char* name, long long offset, void* dev_ptr, long long bytes, int to_engine,
                               void* stream);
+
+/* First-block step caching (off by default).  set_step_cache applies to the following fluxmi_engine_denoise /
+ * _denoise_cfg calls: threshold <= 0 = off (those calls launch exactly what they launch without this entry point), negative / NaN refused,
+ * max_consecutive_hits 0 = unbounded, negative refused.  On: every FROZEN step runs embedders + double block 0 ("head"), measures per sample
+ *   ratio_b = sum |r - r_ref| / sum |r_ref|,  r = bf16(h1 - h0) on the rows the final layer reads, r_ref = the r of the last full step,
+ * and the host reads the B ratios (one event wait per step).  HIT iff a full step has run in this call, every ratio_b < threshold and fewer
+ * than max_consecutive_hits hits precede it in a row: x = bf16(h1 + R) on those rows, final layer, update ("skip").  Otherwise MISS: r_ref = r,
+ * the remaining blocks run, R = bf16(x - h1) is stored, final layer, update ("body").  One decision per pass (all samples, both branches of a
+ * guided request).  head / body / skip are three captured graphs sharing the plain step's device-side step counter; use_graph = 0 runs the
+ * same pieces eagerly.  Calibrating steps never touch the cache.  The cache buffers ("fb_h0" = h0, overwritten by r; "fb_h1"; "fb_rref";
+ * "fb_R"; all bf16 [B, Lpred, hidden]; "fb_ratio" = float ratio[B] | (num, den)[B]) are allocated at the first cached call of a prepared shape
+ * and are readable through fluxmi_engine_copy_buffer.
+ * step_cache_log: the frozen steps of the last denoise call, cached or not (a plain call: *n = 0): *n = their number, *batch = B of that pass, ratios[i * B + b]
+ * and hit[i] for the first min(*n, cap) of them; a step with no reference yet (the first) logs +inf.  ratios / hit may be NULL with cap = 0. */
+int fluxmi_engine_set_step_cache(fluxmi_engine_t* e, float threshold, int max_consecutive_hits);
+int fluxmi_engine_step_cache_log(fluxmi_engine_t* e, int* n, int* batch, float* ratios, unsigned char* hit, int cap);
+/* Test hook: phases [phase_from, phase_to] of ONE frozen forward on the engine's own buffers, mode 1 (fused) or 2 (unfused, frozen scales):
+ *   0 img_in + txt_in on the request buffers "img_s" / "txt_s" (mode 1: the cached "txt_emb" of the last denoise call) + this step's
+ *     modulation vectors out of the step-ahead table the last denoise call left (step = the request's step index, written to the device-side
+ *     step counter first; step < 0 keeps the counter)
+ *   1 double block 0 | 2 every later block | 3 the final layer -> "pred_s".
+ * The counterpart of fluxmi_engine_run_block for what that cannot reach; needs a finished fluxmi_engine_denoise call on this shape. */
+int fluxmi_engine_run_phase(fluxmi_engine_t* e, int mode, int phase_from, int phase_to, int step, void* stream);
 
 #ifdef __cplusplus
 }

@@ -41,6 +41,20 @@ constexpr int MAX_STEPS = 1024;
 // sample); the host wrapper runs larger batches as equal consecutive passes
 constexpr int FLUXMI_ENGINE_MAX_BATCH = 32;
 struct Buf { void* p; size_t n; };
+// The captured pieces of one kind of frozen step (plain: the whole step; cached: head, body, skip) and what they were captured for.  Kernel
+// choices and the update kernel are baked into a captured piece, so the set is keyed on the tuning generation and the update kind.
+struct StepGraphs {
+  hipGraphExec_t exec[3] = {nullptr, nullptr, nullptr};
+  bool ok = false;      // exec[] is instantiated and replayable
+  bool warmed = false;  // one frozen step of this kind, shape and update kind has run eagerly (lazy one-time inits done): the next call may capture at once
+  bool cfg = false;     // the update kind (`warmed` and the pieces): guided or plain -- the two never share a graph
+  unsigned gen = 0;     // fluxmi_tuning_generation() the pieces were captured under
+  void drop() {
+    for (hipGraphExec_t& g : exec)
+      if (g) { hipGraphExecDestroy(g); g = nullptr; }
+    ok = warmed = false;
+  }
+};
 }  // namespace
 
 struct fluxmi_engine {
@@ -71,11 +85,9 @@ struct fluxmi_engine {
   int mods_step0 = 0;
   bool mods_table = false;  // the step being sequenced takes its modulations from the table
   bool qlut_valid = false;  // the quantising-epilogue tables reflect the current input scales
-  hipGraphExec_t exec = nullptr;
-  bool graph_ok = false;
-  bool graph_cfg = false;           // the captured step graph (and `warmed`) is the guided one: plain and guided steps of one shape differ
-  unsigned graph_gen = 0;          // fluxmi_tuning_generation() the step graph was captured under: a changed tuning struct re-captures
-  bool warmed = false;             // one frozen step of this shape has run eagerly (lazy one-time inits done): later calls may capture at once
+  // the frozen step's graphs: the plain step (one piece) and the step-cache step (head, body, skip).  Separate sets, so that plain and cached
+  // requests alternating on one shape never re-capture; both go stale by ONE rule (graphs_stale) and run through ONE loop (frozen_steps)
+  StepGraphs step_graphs, fb_graphs;
   bool txt_emb_valid = false;
   // row-pair copies of the F8Linear weights the persistent GEMM launches read (fluxmi_gemm_group_t.W_pairs): one allocation, offsets per linear
   // (-1 = none); rebuilt on the first launch after create / rebind (the weights may have been rewritten: LoRA fuse)
@@ -103,7 +115,7 @@ struct fluxmi_engine {
   fluxmi_amax_hook_t amax_hook = nullptr;
   void* amax_user = nullptr;
   // first-block step cache (fluxmi_engine_set_step_cache).  Threshold, hit counter and log are HOST state: one set of
-  // graphs serves every threshold.  The buffers (h0 | r, h1, r_ref, R, partial sums, ratios) are one allocation made at the first cached
+  // graphs (fb_graphs) serves every threshold.  The buffers (h0 | r, h1, r_ref, R, partial sums, ratios) are one allocation made at the first cached
   // call of a prepared shape and dropped with the workspace; a plain request never allocates, captures or launches any of this.
   float fb_threshold = 0.f;
   int fb_max_hits = 0;
@@ -111,9 +123,6 @@ struct fluxmi_engine {
   size_t fb_bytes = 0;
   float* h_ratio = nullptr;        // pinned: the B ratios of the step, copied out behind the head piece
   hipEvent_t ev_fb = nullptr;      // ... and the event the host waits on before it decides
-  hipGraphExec_t fb_exec[3] = {nullptr, nullptr, nullptr};  // head, body (miss), skip (hit)
-  bool fb_graph_ok = false, fb_graph_cfg = false, fb_warmed = false;
-  unsigned fb_graph_gen = 0;
   int fb_log_B = 0;
   std::vector<float> fb_log_ratio;          // [frozen steps of the last call][B]
   std::vector<unsigned char> fb_log_hit;    // [frozen steps of the last call]
@@ -859,13 +868,24 @@ int final_layer(E* e, u16* pred, int s0, int s1, hipStream_t s) {
 // the channels the model predicts: final_layer.linear's N (== in_channels but for channel-conditioned models, see fluxmi_engine_create)
 int c_out(const E* e) { return e->lin[e->i_final_lin].N; }
 
-int require_all_f8(E* e) {
-  for (int i = 0; i < e->d.depth; ++i)
+// Every block linear (the modulation linears apart) is F8Linear: what the fused path needs.  Otherwise *blk is the first block that has a
+// bf16 one: double block *blk, or single block *blk - depth.
+bool all_block_linears_f8(E* e, int* blk = nullptr) {
+  int bad = -1;
+  for (int i = 0; i < e->d.depth && bad < 0; ++i)
     for (int sl : {D_IMG_QKV, D_IMG_PROJ, D_IMG_MLP0, D_IMG_MLP2, D_TXT_QKV, D_TXT_PROJ, D_TXT_MLP0, D_TXT_MLP2})
-      FLUXMI_REQUIRE(DL(e, i, sl).kind == 1, "fused mode needs every block linear to be F8Linear (double block %d)", i);
-  for (int i = 0; i < e->d.depth_single; ++i)
-    FLUXMI_REQUIRE(SL(e, i, S_LIN1).kind == 1 && SL(e, i, S_LIN2).kind == 1, "fused mode needs F8Linear in single block %d", i);
-  return 0;
+      if (DL(e, i, sl).kind != 1) bad = i;
+  for (int i = 0; i < e->d.depth_single && bad < 0; ++i)
+    if (SL(e, i, S_LIN1).kind != 1 || SL(e, i, S_LIN2).kind != 1) bad = e->d.depth + i;
+  if (blk) *blk = bad;
+  return bad < 0;
+}
+int require_all_f8(E* e) {
+  int blk;
+  if (all_block_linears_f8(e, &blk)) return 0;
+  if (blk < e->d.depth) fluxmi_set_error("fused mode needs every block linear to be F8Linear (double block %d)", blk);
+  else fluxmi_set_error("fused mode needs F8Linear in single block %d", blk - e->d.depth);
+  return 1;
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -924,6 +944,15 @@ int forward_impl(E* e, const u16* img, const u16* txt, const u16* y, const u16* 
   return 0;
 }
 
+// Phases [p0, p1] of a frozen step's forward: the engine's static request buffers, the modulations from the step-ahead table
+int frozen_forward(E* e, int mode, const u16* g_arg, int p0, int p1, hipStream_t s) {
+  e->mods_table = true;
+  const int rc = forward_impl(e, buf<u16>(e, "img_s"), buf<u16>(e, "txt_s"), buf<u16>(e, "y_s"), buf<u16>(e, "tvec"), g_arg, buf<u16>(e, "pred_s"),
+                              mode, 0, mode == 1, s, p0, p1);
+  e->mods_table = false;
+  return rc;
+}
+
 bool needs_splitk(E* e) {
   for (const fluxmi_linear_t& l : e->lin)
     if (!l.kind && (long long)l.K * 2 / 64 >= 192) return true;
@@ -950,13 +979,8 @@ struct SplitkScope {
 };
 
 void free_ws(E* e) {
-  if (e->exec) { hipGraphExecDestroy(e->exec); e->exec = nullptr; }
-  for (hipGraphExec_t& g : e->fb_exec)
-    if (g) { hipGraphExecDestroy(g); g = nullptr; }
-  e->graph_ok = false;
-  e->warmed = false;
-  e->fb_graph_ok = false;
-  e->fb_warmed = false;
+  e->step_graphs.drop();
+  e->fb_graphs.drop();
   e->qlut_valid = false;
   if (e->fb_mem) { hipFree(e->fb_mem); e->fb_mem = nullptr; e->fb_bytes = 0; }
   if (e->ws) { hipFree(e->ws); e->ws = nullptr; }
@@ -1099,10 +1123,8 @@ int fluxmi_engine_destroy(fluxmi_engine_t* e) {
 int fluxmi_engine_rebind(fluxmi_engine_t* e, const fluxmi_linear_t* linears, int n_linears) {
   FLUXMI_REQUIRE(e && linears && n_linears == (int)e->lin.size(), "engine_rebind: bad arguments");
   e->lin.assign(linears, linears + n_linears);
-  e->graph_ok = false;
-  e->warmed = false;
-  e->fb_graph_ok = false;
-  e->fb_warmed = false;
+  e->step_graphs.drop();
+  e->fb_graphs.drop();
   e->txt_emb_valid = false;
   e->pairs_dirty = true;
   e->qlut_valid = false;
@@ -1230,62 +1252,176 @@ int fluxmi_engine_forward(fluxmi_engine_t* e, const void* img, const void* txt, 
 
 
 // ---------------------------------------------------------------------------------------------------------
-// The frozen steps [step, n_steps) with first-block step caching (fluxmi.h, fluxmi_engine_set_step_cache).
+// The frozen steps [step, n_steps) of a request: ONE loop (frozen_steps) for the plain step and for the step with first-block caching.  The
+// two differ only in their Stepper: the pieces a step is cut into -- each piece is one captured graph -- and how a step is sequenced from them.
+// ---------------------------------------------------------------------------------------------------------
+typedef std::function<int(hipStream_t)> StepFn;
+struct StepPiece { const char* name; StepFn run; };
+struct Stepper {
+  StepGraphs* g;
+  const char* range;                    // roctx range around the steps
+  int n_pieces;
+  StepPiece piece[3];
+  std::function<int(bool graph)> step;  // one step on the caller's stream: the pieces replayed (graph) or run eagerly
+  std::function<int()> pre_warm;        // what precedes the eager warm step (may be empty)
+};
+
+// The ONE staleness rule of both graph sets.  Kernel choices are baked into a captured piece: never replay one captured under other knobs
+// (the quantising-epilogue tables follow the knobs too).  The update kernel is baked in as well, and `warmed` speaks of one update kind: a
+// plain and a guided request of one shape never share a graph or a warm step, whether or not a graph exists yet.  The old pieces stay
+// allocated until the re-capture replaces them (behind its stream synchronisation).
+static void graphs_stale(fluxmi_engine_t* e, StepGraphs& g, bool cfg) {
+  if (g.ok && g.gen != fluxmi_tuning_generation()) g.ok = g.warmed = e->qlut_valid = false;
+  if (g.cfg != cfg) g.ok = g.warmed = false;
+  g.cfg = cfg;
+}
+
+// Captures pieces[0 .. n) into g.exec[0 .. n) on a private non-blocking stream (the caller has synchronised its own).  The only place that
+// captures and instantiates; the stream sits behind a guard, so that no error path keeps it.
+static int capture_pieces(StepGraphs& g, const StepPiece* pieces, int n) {
+  struct CaptureStream {
+    hipStream_t s = nullptr;
+    ~CaptureStream() { if (s) hipStreamDestroy(s); }
+  } cs;
+  FLUXMI_CHECK_HIP(hipStreamCreateWithFlags(&cs.s, hipStreamNonBlocking));
+  for (int p = 0; p < n; ++p) {
+    hipGraph_t graph = nullptr;
+    hipError_t ce = hipStreamBeginCapture(cs.s, hipStreamCaptureModeThreadLocal);
+    const int rc = ce == hipSuccess ? pieces[p].run(cs.s) : 0;
+    if (ce == hipSuccess) ce = hipStreamEndCapture(cs.s, &graph);  // ends the capture of a failed piece as well
+    if (g.exec[p]) { hipGraphExecDestroy(g.exec[p]); g.exec[p] = nullptr; }
+    if (!rc && ce == hipSuccess) ce = hipGraphInstantiate(&g.exec[p], graph, nullptr, nullptr, 0);
+    if (graph) hipGraphDestroy(graph);
+    if (!rc && ce != hipSuccess) fluxmi_set_error("engine_denoise: capturing %s failed: %s", pieces[p].name, hipGetErrorString(ce));
+    if (rc || ce != hipSuccess) return rc ? rc : 2;
+  }
+  g.ok = true;
+  g.gen = fluxmi_tuning_generation();
+  return 0;
+}
+
+// The modulation vectors of up to MODS_STEPS steps are produced ahead (one pass over the 3.2 GB of modulation weights per window); the table
+// address and the device-side window origin never change, so ONE set of captured pieces serves every step of every request.  The first frozen
+// step of a shape and update kind runs eagerly, so that every lazy one-time init (function attributes) happens outside capture; the steps
+// behind it are replayed (use_graph) or run eagerly.  *first_timed = the first step behind ev_t0.
+static int frozen_steps(fluxmi_engine_t* e, const Stepper& st, int mode, bool cfg, int step, int n_steps, const u16* g_arg, int use_graph,
+                        int* first_timed, hipStream_t s) {
+  StepGraphs& g = *st.g;
+  bool t0 = false;
+  while (step < n_steps) {
+    const int win_end = std::min(n_steps, step + MODS_STEPS);
+    {
+      Range r("step-ahead modulation table");
+      FLUXMI_TRY(precompute_mods(e, step, win_end, g_arg, buf<u16>(e, "y_s"), s));
+    }
+    graphs_stale(e, g, cfg);
+    if (use_graph && !g.ok) {
+      if (!g.warmed) {
+        if (st.pre_warm) FLUXMI_TRY(st.pre_warm());
+        FLUXMI_TRY(st.step(false));
+        ++step;
+        g.warmed = true;
+      }
+      if (step < win_end) {
+        FLUXMI_CHECK_HIP(hipStreamSynchronize(s));  // one-time, at graph capture only
+        FLUXMI_TRY(capture_pieces(g, st.piece, st.n_pieces));
+      }
+    }
+    Range r(st.range);
+    // ev_t0 .. ev_t1 (fluxmi_engine_last_timing) brackets frozen STEPS only: recorded behind the first window's modulation table, the eager
+    // warm step and the graph capture of a new shape (a request longer than MODS_STEPS steps includes its later table builds)
+    if (!t0) {
+      FLUXMI_CHECK_HIP(hipEventRecord(e->ev_t0, s));
+      *first_timed = step;
+      t0 = true;
+    }
+    const bool graph = use_graph && g.ok;
+    for (; step < win_end; ++step) FLUXMI_TRY(st.step(graph));
+    if (graph) {
+      // the host code of the step ran at capture only: the replayed pieces wrote the activation buffers in the layout they were captured
+      // with (a tuning change since the capture re-captures above)
+      const bool ap = act_pairs(e, mode == 1);
+      for (bool& b : e->act_in_pairs) b = ap;
+    }
+  }
+  return 0;
+}
+
+// The plain step: one piece -- the forward, the update, the step counter -- and one hipGraphLaunch per replayed step.
+static int plain_steps(fluxmi_engine_t* e, int mode, bool cfg, int step, int n_steps, const u16* g_arg, int use_graph, const StepFn& euler,
+                       int* first_timed, hipStream_t s) {
+  Stepper st;
+  st.g = &e->step_graphs;
+  st.range = "frozen steps (hipGraph replay)";
+  st.n_pieces = 1;
+  st.piece[0] = {"the step", [&](hipStream_t t) -> int {
+                   FLUXMI_TRY(frozen_forward(e, mode, g_arg, PH_EMBED, PH_FINAL, t));
+                   FLUXMI_TRY(euler(t));
+                   return fluxmi_k_advance_step(e->d_step, t);
+                 }};
+  st.step = [&](bool graph) -> int {
+    if (!graph) return st.piece[0].run(s);
+    FLUXMI_CHECK_HIP(hipGraphLaunch(st.g->exec[0], s));
+    return 0;
+  };
+  return frozen_steps(e, st, mode, cfg, step, n_steps, g_arg, use_graph, first_timed, s);
+}
+
+// The step with first-block caching (fluxmi.h, fluxmi_engine_set_step_cache): three pieces with a host decision between them
 //   head: img_in, txt rows, select_step | h0 = x rows | double block 0 | r = bf16(x - h0) over h0, ratios -> pinned host
 //   host: waits for the head, reads the B ratios, decides
 //   body (miss): r_ref = r, h1 = x | blocks 1 .. | R = bf16(x - h1) | final layer, update, advance
 //   skip (hit):  x = bf16(x + R) (x still holds this step's h1) | final layer, update, advance
-// on the rows the final layer reads.  Each piece is one captured graph (first step of a shape eager, re-captured with the tuning generation
-// and the update kind, like the plain step's graph); use_graph = 0 runs the same pieces eagerly.
-// ---------------------------------------------------------------------------------------------------------
-static int denoise_cached(fluxmi_engine_t* e, int mode, bool cfg, int step, int n_steps, const u16* g_arg, int use_graph,
-                          const std::function<int(hipStream_t)>& euler, int* first_timed, hipStream_t s) {
+// on the rows the final layer reads.  The rule's host state (have_full, consec) and the log live here; a plain request never comes here, so it
+// never allocates, captures or launches anything of the cache.
+static int cached_steps(fluxmi_engine_t* e, int mode, bool cfg, int step, int n_steps, const u16* g_arg, int use_graph, const StepFn& euler,
+                        int* first_timed, hipStream_t s) {
   FLUXMI_REQUIRE(e->d.depth >= 1, "engine_denoise: step caching needs at least one double block");
   FLUXMI_TRY(ensure_fb(e, s));
   const int B = e->B, H = e->d.hidden;
   const long long XB = (long long)e->L * H, n = (long long)e->Lpred * H;
-  u16 *img_s = buf<u16>(e, "img_s"), *txt_s = buf<u16>(e, "txt_s"), *y_s = buf<u16>(e, "y_s"), *pred_s = buf<u16>(e, "pred_s");
-  u16* tvec = buf<u16>(e, "tvec");
   u16* xr = buf<u16>(e, "x") + (long long)e->Lt * H;  // the rows the final layer reads: Lpred rows behind the text rows of each sample
   u16 *h0 = buf<u16>(e, "fb_h0"), *h1 = buf<u16>(e, "fb_h1"), *rref = buf<u16>(e, "fb_rref"), *R = buf<u16>(e, "fb_R");
   float *part = buf<float>(e, "fb_part"), *ratio = buf<float>(e, "fb_ratio");
-  auto fwd = [&](int p0, int p1, hipStream_t st) -> int {
-    e->mods_table = true;
-    const int rc = forward_impl(e, img_s, txt_s, y_s, tvec, g_arg, pred_s, mode, 0, mode == 1, st, p0, p1);
-    e->mods_table = false;
-    return rc;
+  auto fwd = [&](int p0, int p1, hipStream_t t) -> int { return frozen_forward(e, mode, g_arg, p0, p1, t); };
+  auto tail = [&](hipStream_t t) -> int {
+    FLUXMI_TRY(fwd(PH_FINAL, PH_FINAL, t));
+    FLUXMI_TRY(euler(t));
+    return fluxmi_k_advance_step(e->d_step, t);
   };
-  auto head = [&](hipStream_t st) -> int {
-    FLUXMI_TRY(fwd(PH_EMBED, PH_EMBED, st));
-    FLUXMI_TRY(fluxmi_k_fb_snapshot(xr, XB, h0, B, n, st));
-    FLUXMI_TRY(fwd(PH_BLOCK0, PH_BLOCK0, st));
-    FLUXMI_TRY(fluxmi_k_fb_metric(xr, XB, h0, h0, rref, part, ratio, ratio + B, B, n, st));
-    FLUXMI_CHECK_HIP(hipMemcpyAsync(e->h_ratio, ratio, (size_t)B * 4, hipMemcpyDeviceToHost, st));
-    return 0;
-  };
-  auto tail = [&](hipStream_t st) -> int {
-    FLUXMI_TRY(fwd(PH_FINAL, PH_FINAL, st));
-    FLUXMI_TRY(euler(st));
-    return fluxmi_k_advance_step(e->d_step, st);
-  };
-  auto body = [&](hipStream_t st) -> int {
-    FLUXMI_TRY(fluxmi_k_fb_commit(xr, XB, h0, rref, h1, B, n, st));
-    FLUXMI_TRY(fwd(PH_BLOCKS, PH_BLOCKS, st));
-    FLUXMI_TRY(fluxmi_k_fb_store(xr, XB, h1, R, B, n, st));
-    return tail(st);
-  };
-  auto skip = [&](hipStream_t st) -> int {
-    FLUXMI_TRY(fluxmi_k_fb_apply(xr, XB, xr, XB, R, B, n, st));
-    return tail(st);
-  };
-  const std::function<int(hipStream_t)> pieces[3] = {head, body, skip};
+  Stepper st;
+  st.g = &e->fb_graphs;
+  st.range = "frozen steps (step cache)";
+  st.n_pieces = 3;
+  st.piece[0] = {"step-cache piece 0 (head)", [&](hipStream_t t) -> int {
+                   FLUXMI_TRY(fwd(PH_EMBED, PH_EMBED, t));
+                   FLUXMI_TRY(fluxmi_k_fb_snapshot(xr, XB, h0, B, n, t));
+                   FLUXMI_TRY(fwd(PH_BLOCK0, PH_BLOCK0, t));
+                   FLUXMI_TRY(fluxmi_k_fb_metric(xr, XB, h0, h0, rref, part, ratio, ratio + B, B, n, t));
+                   FLUXMI_CHECK_HIP(hipMemcpyAsync(e->h_ratio, ratio, (size_t)B * 4, hipMemcpyDeviceToHost, t));
+                   return 0;
+                 }};
+  st.piece[1] = {"step-cache piece 1 (body)", [&](hipStream_t t) -> int {
+                   FLUXMI_TRY(fluxmi_k_fb_commit(xr, XB, h0, rref, h1, B, n, t));
+                   FLUXMI_TRY(fwd(PH_BLOCKS, PH_BLOCKS, t));
+                   FLUXMI_TRY(fluxmi_k_fb_store(xr, XB, h1, R, B, n, t));
+                   return tail(t);
+                 }};
+  st.piece[2] = {"step-cache piece 2 (skip)", [&](hipStream_t t) -> int {
+                   FLUXMI_TRY(fluxmi_k_fb_apply(xr, XB, xr, XB, R, B, n, t));
+                   return tail(t);
+                 }};
   // host state of the rule
   bool have_full = false;  // a full step has run in THIS call: every call starts with an empty cache
   int consec = 0;
   e->fb_log_B = B;
-  auto one_step = [&](bool graph) -> int {
-    if (graph) FLUXMI_CHECK_HIP(hipGraphLaunch(e->fb_exec[0], s));
-    else FLUXMI_TRY(head(s));
+  auto run = [&](int p, bool graph) -> int {
+    if (!graph) return st.piece[p].run(s);
+    FLUXMI_CHECK_HIP(hipGraphLaunch(st.g->exec[p], s));
+    return 0;
+  };
+  st.step = [&](bool graph) -> int {
+    FLUXMI_TRY(run(0, graph));
     FLUXMI_CHECK_HIP(hipEventRecord(e->ev_fb, s));
     FLUXMI_CHECK_HIP(hipEventSynchronize(e->ev_fb));
     bool hit = have_full && (e->fb_max_hits <= 0 || consec < e->fb_max_hits);
@@ -1297,70 +1433,15 @@ static int denoise_cached(fluxmi_engine_t* e, int mode, bool cfg, int step, int 
     e->fb_log_hit.push_back(hit ? 1 : 0);
     consec = hit ? consec + 1 : 0;
     have_full = have_full || !hit;
-    if (graph) FLUXMI_CHECK_HIP(hipGraphLaunch(e->fb_exec[hit ? 2 : 1], s));
-    else FLUXMI_TRY(hit ? skip(s) : body(s));
-    return 0;
+    return run(hit ? 2 : 1, graph);
   };
-  bool t0 = false;
-  while (step < n_steps) {
-    const int win_end = std::min(n_steps, step + MODS_STEPS);
-    {
-      Range r("step-ahead modulation table");
-      FLUXMI_TRY(precompute_mods(e, step, win_end, g_arg, y_s, s));
-    }
-    if (e->fb_graph_ok && (e->fb_graph_gen != fluxmi_tuning_generation() || e->fb_graph_cfg != cfg)) {
-      e->fb_graph_ok = false;  // kernel choices and the update kernel are baked into the captured pieces
-      e->fb_warmed = false;
-      e->qlut_valid = false;
-    }
-    if (use_graph && !e->fb_graph_ok) {
-      if (!e->fb_warmed) {
-        // lazy one-time inits happen outside capture: this step runs eagerly -- head and body, it is the first frozen step of a call and
-        // misses -- and the skip piece's own kernel is launched once on x's image rows, which are dead here (img_in rewrites them next)
-        FLUXMI_REQUIRE(!have_full, "engine_denoise: step-cache warm-up behind a full step");
-        FLUXMI_TRY(fluxmi_k_fb_apply(xr, XB, xr, XB, R, B, n, s));
-        FLUXMI_TRY(one_step(false));
-        ++step;
-        e->fb_warmed = true;
-      }
-      if (step < win_end) {
-        hipStream_t cs;
-        FLUXMI_CHECK_HIP(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
-        FLUXMI_CHECK_HIP(hipStreamSynchronize(s));  // one-time, at graph capture only
-        for (int p = 0; p < 3; ++p) {
-          hipGraph_t graph = nullptr;
-          hipError_t ce = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal);
-          const int rc = ce == hipSuccess ? pieces[p](cs) : 0;
-          if (ce == hipSuccess) ce = hipStreamEndCapture(cs, &graph);
-          if (e->fb_exec[p]) { hipGraphExecDestroy(e->fb_exec[p]); e->fb_exec[p] = nullptr; }
-          if (!rc && ce == hipSuccess) ce = hipGraphInstantiate(&e->fb_exec[p], graph, nullptr, nullptr, 0);
-          if (graph) hipGraphDestroy(graph);
-          if (rc || ce != hipSuccess) {
-            hipStreamDestroy(cs);
-            if (!rc) fluxmi_set_error("engine_denoise: capturing step-cache piece %d failed: %s", p, hipGetErrorString(ce));
-            return rc ? rc : 2;
-          }
-        }
-        hipStreamDestroy(cs);
-        e->fb_graph_ok = true;
-        e->fb_graph_gen = fluxmi_tuning_generation();
-        e->fb_graph_cfg = cfg;
-      }
-    }
-    Range r("frozen steps (step cache)");
-    if (!t0) {
-      FLUXMI_CHECK_HIP(hipEventRecord(e->ev_t0, s));
-      *first_timed = step;
-      t0 = true;
-    }
-    const bool graph = use_graph && e->fb_graph_ok;
-    for (; step < win_end; ++step) FLUXMI_TRY(one_step(graph));
-    if (graph) {  // the replayed pieces wrote the activation buffers in the layout they were captured with
-      const bool ap = act_pairs(e, mode == 1);
-      for (bool& b : e->act_in_pairs) b = ap;
-    }
-  }
-  return 0;
+  // lazy one-time inits happen outside capture: the warm step runs head and body eagerly -- it is the first frozen step of a call and
+  // misses -- and the skip piece's own kernel is launched once before it on x's image rows, which are dead here (img_in rewrites them next)
+  st.pre_warm = [&]() -> int {
+    FLUXMI_REQUIRE(!have_full, "engine_denoise: step-cache warm-up behind a full step");
+    return fluxmi_k_fb_apply(xr, XB, xr, XB, R, B, n, s);
+  };
+  return frozen_steps(e, st, mode, cfg, step, n_steps, g_arg, use_graph, first_timed, s);
 }
 
 // the denoise loop, plain or guided (cfg: true classifier-free guidance).  Guided: the prepared batch B is 2 Bh, samples [0, Bh) the prompt
@@ -1388,13 +1469,6 @@ static int denoise_impl(fluxmi_engine_t* e, void* img, const void* txt, const vo
     if (e->Lpred == Li) return fluxmi_k_euler(buf<u16>(e, "img_s"), buf<u16>(e, "pred_s"), e->d_dts, e->d_step, (long long)B * Li * C, st);
     return fluxmi_k_euler_rows(buf<u16>(e, "img_s"), buf<u16>(e, "pred_s"), e->d_dts, e->d_step, B, Li, e->Lpred, C, st);
   };
-  // any bf16 block linear -> the fused path is unavailable, run unfused-frozen (mode 2)
-  bool all_f8 = true;
-  for (int i = e->i_double0; i < e->i_final_mod; ++i) {
-    const int rel = i < e->i_single0 ? (i - e->i_double0) % 10 : -1;
-    const bool is_mod = (i < e->i_single0) ? (rel == D_IMG_MOD || rel == D_TXT_MOD) : ((i - e->i_single0) % 3 == S_MOD);
-    if (!is_mod && !e->lin[i].kind) all_f8 = false;
-  }
   bool any_f8 = false;
   for (auto& l : e->lin) any_f8 |= (l.kind != 0);
 
@@ -1444,95 +1518,17 @@ static int denoise_impl(fluxmi_engine_t* e, void* img, const void* txt, const vo
   e->fb_log_ratio.clear();
   e->fb_log_hit.clear();
   if (step < n_steps) {
-    const int mode = all_f8 ? 1 : 2;
+    const int mode = all_block_linears_f8(e) ? 1 : 2;  // any bf16 block linear -> the fused path is unavailable, run unfused-frozen
     if (mode == 1) {
       FLUXMI_TRY(embed_txt(e, txt_s, false, 0, buf<u16>(e, "txt_emb"), (long long)Lt * e->d.hidden, s));
       e->txt_emb_valid = true;
       FLUXMI_TRY(build_qluts(e, s));
     }
-    auto one_step = [&](hipStream_t st) -> int {
-      e->mods_table = true;
-      int rc = forward_impl(e, img_s, txt_s, y_s, tvec, g_arg, pred_s, mode, 0, mode == 1, st);
-      e->mods_table = false;
-      FLUXMI_TRY(rc);
-      FLUXMI_TRY(euler(st));
-      return fluxmi_k_advance_step(e->d_step, st);
-    };
-    // ev_t0 .. ev_t1 (fluxmi_engine_last_timing) brackets frozen STEPS only: recorded behind the first window's modulation table, the eager
-    // warm step and the graph capture of a new shape (a request longer than MODS_STEPS steps includes its later table builds)
-    bool t0_recorded = false;
-    int first_timed = step;
-    if (e->fb_threshold > 0.f) {  // first-block step caching: the same steps as head / body / skip pieces with a host decision in between
-      FLUXMI_TRY(denoise_cached(e, mode, cfg, step, n_steps, g_arg, use_graph, euler, &first_timed, s));
-      t0_recorded = true;
-      step = n_steps;
-    }
-    // the modulation vectors of up to MODS_STEPS steps are produced ahead (one pass over the 3.2 GB of modulation weights per window);
-    // the table address and the device-side window origin never change, so ONE captured graph serves every step of every request
-    while (step < n_steps) {
-      const int win_end = std::min(n_steps, step + MODS_STEPS);
-      {
-        Range r("step-ahead modulation table");
-        FLUXMI_TRY(precompute_mods(e, step, win_end, g_arg, y_s, s));
-      }
-      if (e->graph_ok && e->graph_gen != fluxmi_tuning_generation()) {
-        e->graph_ok = false;  // kernel choices are baked into a captured graph: never replay one captured under other knobs
-        e->warmed = false;
-        e->qlut_valid = false;
-      }
-      if (e->graph_cfg != cfg) {
-        e->graph_ok = false;  // the update kernel is baked in too: a plain and a guided request of one shape never share a graph
-        e->warmed = false;
-        e->graph_cfg = cfg;
-      }
-      if (use_graph && !e->graph_ok) {
-        // the first frozen step of a shape runs eagerly so that every lazy one-time init (function attributes) happens outside capture
-        if (!e->warmed) {
-          FLUXMI_TRY(one_step(s));
-          ++step;
-          e->warmed = true;
-        }
-        if (step < win_end) {
-          hipStream_t cs;
-          FLUXMI_CHECK_HIP(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
-          FLUXMI_CHECK_HIP(hipStreamSynchronize(s));  // one-time, at graph capture only
-          hipGraph_t graph = nullptr;
-          FLUXMI_CHECK_HIP(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
-          int rc = one_step(cs);
-          hipError_t ce = hipStreamEndCapture(cs, &graph);
-          if (rc || ce != hipSuccess) {
-            if (graph) hipGraphDestroy(graph);
-            hipStreamDestroy(cs);
-            if (!rc) fluxmi_set_error("engine_denoise: hipStreamEndCapture failed: %s", hipGetErrorString(ce));
-            return rc ? rc : 2;
-          }
-          if (e->exec) { hipGraphExecDestroy(e->exec); e->exec = nullptr; }
-          hipError_t ie = hipGraphInstantiate(&e->exec, graph, nullptr, nullptr, 0);
-          hipGraphDestroy(graph);
-          hipStreamDestroy(cs);
-          if (ie != hipSuccess) { fluxmi_set_error("engine_denoise: hipGraphInstantiate failed: %s", hipGetErrorString(ie)); return 2; }
-          e->graph_ok = true;
-          e->graph_gen = fluxmi_tuning_generation();
-        }
-      }
-      Range r("frozen steps (hipGraph replay)");
-      if (!t0_recorded) {
-        FLUXMI_CHECK_HIP(hipEventRecord(e->ev_t0, s));
-        first_timed = step;
-        t0_recorded = true;
-      }
-      if (use_graph && e->graph_ok) {
-        for (; step < win_end; ++step) FLUXMI_CHECK_HIP(hipGraphLaunch(e->exec, s));
-        // the host code of the step ran at capture only: the replayed graph wrote the activation buffers in the layout it was captured with
-        // (a tuning change since the capture re-captures above)
-        const bool ap = act_pairs(e, mode == 1);
-        for (bool& b : e->act_in_pairs) b = ap;
-      } else {
-        for (; step < win_end; ++step) FLUXMI_TRY(one_step(s));
-      }
-    }
+    // plain, or with first-block step caching: the same steps cut into head / body / skip pieces with a host decision in between
+    int first_timed = n_steps;  // the first step behind ev_t0, which the loop records: ev_t0 .. ev_t1 brackets steps [first_timed, n_steps)
+    FLUXMI_TRY((e->fb_threshold > 0.f ? cached_steps : plain_steps)(e, mode, cfg, step, n_steps, g_arg, use_graph, euler, &first_timed, s));
     FLUXMI_CHECK_HIP(hipEventRecord(e->ev_t1, s));
-    e->timed_steps = t0_recorded ? n_steps - first_timed : 0;
+    e->timed_steps = n_steps - first_timed;
   }
   FLUXMI_CHECK_HIP(hipMemcpyAsync(img, img_s, n_img * 2, hipMemcpyDeviceToDevice, s));
   *trial_index_inout = trial;
@@ -1584,11 +1580,7 @@ int fluxmi_engine_run_phase(fluxmi_engine_t* e, int mode, int phase_from, int ph
     FLUXMI_TRY(build_qluts(e, s));
   }
   if (step >= 0) FLUXMI_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)e->d_step, step, 1, s));
-  e->mods_table = true;
-  const int rc = forward_impl(e, buf<u16>(e, "img_s"), buf<u16>(e, "txt_s"), buf<u16>(e, "y_s"), buf<u16>(e, "tvec"), buf<u16>(e, "gvec"),
-                              buf<u16>(e, "pred_s"), mode, 0, mode == 1, s, phase_from, phase_to);
-  e->mods_table = false;
-  return rc;
+  return frozen_forward(e, mode, buf<u16>(e, "gvec"), phase_from, phase_to, s);
 }
 
 int fluxmi_engine_last_timing(fluxmi_engine_t* e, float* ms, int* steps) {

@@ -156,6 +156,61 @@ def test_off_is_off(dev, qname):
             assert ws_bytes(model) == ws
 
 
+# ---- 2b. one engine, both graph sets, both update kinds ------------------------------------------------------------------------------------
+def _halves(d2):
+    return {k: v[:1] for k, v in d2.items()}
+
+
+@pytest.mark.parametrize("qname", ["fp8", "bf16"])
+def test_cached_plain_and_cached_guided_never_share_graphs(dev, qname):
+    """The prepared shape (2 samples) five times on ONE engine -- cached plain B = 2, cached guided B = 1, cached plain B = 2, plain B = 2,
+    guided B = 1, 8 frozen steps each -- equals each request on a fresh engine: latents bit for bit, and the hit log."""
+    model, d2, ts, lat = frozen_request(dev, qname, "plain")
+    d1 = _halves(d2)
+    ckw = dict(cache_threshold=1e30, cache_max_hits=2)  # miss, hit, hit, miss, ... whatever the ratios
+    runs = [lambda: denoise(model, d2, ts, img=lat, **ckw), lambda: denoise(model, d1, ts, img=lat[:1], guided=True, **ckw),
+            lambda: denoise(model, d2, ts, img=lat, **ckw), lambda: denoise(model, d2, ts, img=lat),
+            lambda: denoise(model, d1, ts, img=lat[:1], guided=True)]
+
+    def logged(r):
+        out = r()
+        return out, model.step_cache_log()[1]
+
+    got = [logged(r) for r in runs]
+    n = len(ts) - 1
+    assert n == 8 and [h for _, h in got] == [[i % 3 != 0 for i in range(n)]] * 3 + [[], []]
+    assert torch.equal(got[0][0], got[2][0]), f"requests 1 and 3 differ: rel-L2 {rel_l2(got[0][0], got[2][0]):.3e}"
+    for i, r in enumerate(runs):
+        model._invalidate_engine()
+        fresh, hits = logged(r)
+        assert torch.equal(got[i][0], fresh), f"request {i} on the shared engine differs from a fresh engine: rel-L2 {rel_l2(got[i][0], fresh):.3e}"
+        assert got[i][1] == hits, f"request {i}: hits {got[i][1]} on the shared engine, {hits} on a fresh one"
+
+
+@pytest.mark.parametrize("qname", ["fp8", "bf16"])
+def test_single_frozen_step_then_other_update_kind(dev, qname):
+    """A request of ONE frozen step leaves its step kind warmed with nothing captured; the next request on the shape has the other update
+    kind.  With the cache: guided, then plain; without: plain, then guided.  The second request equals itself on a fresh engine and its
+    eager run."""
+    model, d2, ts, lat = frozen_request(dev, qname, "plain")
+    d1 = _halves(d2)
+    ckw = dict(cache_threshold=1e30)
+    pairs = {"cached": (lambda: denoise(model, d1, ts[:2], img=lat[:1], guided=True, **ckw), lambda **kw: denoise(model, d2, ts, img=lat, **ckw, **kw)),
+             "plain": (lambda: denoise(model, d2, ts[:2], img=lat), lambda **kw: denoise(model, d1, ts, img=lat[:1], guided=True, **kw))}
+    for name, (short, long) in pairs.items():
+        model._invalidate_engine()
+        assert torch.isfinite(short()).all()
+        got, hits = long(), model.step_cache_log()[1]
+        assert hits == ([False] + [True] * (len(ts) - 2) if name == "cached" else [])
+        model._invalidate_engine()
+        fresh = long()
+        assert torch.equal(got, fresh), f"{name}: behind a one-step request of the other kind vs a fresh engine: rel-L2 {rel_l2(got, fresh):.3e}"
+        assert model.step_cache_log()[1] == hits
+        eager = long(use_graph=False)
+        assert torch.equal(got, eager), f"{name}: graph vs eager: rel-L2 {rel_l2(got, eager):.3e}"
+        assert model.step_cache_log()[1] == hits
+
+
 # ---- 3. extremes -------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("qname", ["fp8", "bf16"])
 def test_extremes(dev, qname):

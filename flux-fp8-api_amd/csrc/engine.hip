@@ -34,6 +34,7 @@
 
 #include "common.h"
 #include "fluxmi_internal.h"
+#include "gemm_cfg.h"
 
 namespace {
 constexpr int MAX_STEPS = 1024;
@@ -289,11 +290,11 @@ int run_gemm(std::vector<FluxmiGemmGroup>& gs, int N, int K, int is_fp8, int act
 // count -- through img_in a sample's latents depended on the batch it rode in from B = 4 on (B x 4096 rows: config 13 instead of 2;
 // tests/test_engine_gpu.py::test_maximum_batch_at_real_width).  Config 2 (128x128 tiles; 15 = its 128x64 form) is the choice at B = 1 for all
 // three and costs nothing at larger B (K = 64 / one launch per request / N = 64: output-bound launches of tens of microseconds).
-// Round 6: every bf16 tile config sums K in one order now (gemm.hip) and the split-K slices follow ONE sample's groups (api.cpp,
+// Round 6: every bf16 tile config sums K in one order now (gemm.hip) and the split-K slices follow ONE sample's groups (gemm_dispatch.cpp,
 // fluxmi_gemm_set_batch), so the bf16 FLOW is batch-invariant as well; the pin stays (it is the B = 1 choice and keeps these three launches
 // off the split-K path whatever the tuning says).
 int run_gemm_fixed_cfg(std::vector<FluxmiGemmGroup>& gs, int N, int K, int is_fp8, int act_fmt, int epi, hipStream_t s) {
-  const int cfg = fluxmi_gemm_tile_ok(N, K, 0, 2) ? 2 : (fluxmi_gemm_tile_ok(N, K, 0, 15) ? 15 : -1);
+  const int cfg = fluxmi_gemm_tile_ok(N, K, 0, GEMM_CFG_T128) ? GEMM_CFG_T128 : (fluxmi_gemm_tile_ok(N, K, 0, GEMM_CFG_T128x64) ? GEMM_CFG_T128x64 : -1);
   if (is_fp8 || cfg < 0 || fluxmi_tuning().gemm_cfg >= 0) return run_gemm(gs, N, K, is_fp8, act_fmt, epi, s);
   for (size_t off = 0; off < gs.size(); off += FLUXMI_MAX_GROUPS) {
     FluxmiGemmParams p;
@@ -623,7 +624,7 @@ int double_block(E* e, const Ctx& c, int i, int mode, int trial, int s0, int s1,
   // kernels, and a launch that small runs 1.7x faster on 128x128 tiles at two workgroups per CU, profiles/r03_small_m.txt).  The threshold
   // is on ONE sample's rows, not on B x L: the fused K of tile config 13 and the relayout kernel's K agree on 99.9 % of the elements, not on
   // all, so a choice that followed the batch made a sample's bits follow it (round 6: schnell 256^2 at B = 4 crossed 2048 rows)
-  const bool fuse_v = fuse_kv_level() >= 1 && fluxmi_gemm_tile_ok(3 * H, H, e->lin[li_q[0]].kind, 13) && Lt % 16 == 0 && L >= 2048;
+  const bool fuse_v = fuse_kv_level() >= 1 && fluxmi_gemm_tile_ok(3 * H, H, e->lin[li_q[0]].kind, GEMM_CFG_PP) && Lt % 16 == 0 && L >= 2048;
   const bool fuse_k = fuse_kv_level() >= 2 && fuse_v && H % 256 == 0;  // a 256-column tile must not straddle the q|k|v boundaries
   const int ap = act_pairs(e, fused) ? 1 : 0;  // fp8 activation buffers in the row-pair layout (see act_pairs)
 
@@ -771,7 +772,7 @@ int single_block(E* e, const Ctx& c, int i, int mode, int trial, int s0, int s1,
   if (on(0)) e->act_in_pairs[ACT_A8] = ap;
   if ((fused && on(1)) || on(3)) e->act_in_pairs[ACT_CAT8] = ap;  // fused: linear1 writes the GELU part, attention the rest
   if (fused) {
-    const bool fuse_v = fuse_kv_level() >= 1 && fluxmi_gemm_tile_ok(3 * H + Hm, H, 1, 13);
+    const bool fuse_v = fuse_kv_level() >= 1 && fluxmi_gemm_tile_ok(3 * H + Hm, H, 1, GEMM_CFG_PP);
     const bool fuse_k = fuse_kv_level() >= 2 && fuse_v && H % 256 == 0 && L >= 2048;  // short sequences: one launch of the relayout kernel is cheaper
     if (on(0))
       FLUXMI_TRY(fluxmi_k_ln_modulate(x, H, XB, a8, H, XB, ms, ms + H, ms, ms + H, MC, L1.in_scale, L1.in_scale, B, L, L, H, 1, L1.in_fmt, s, ap));
@@ -1194,7 +1195,7 @@ int fluxmi_engine_prepare_cond(fluxmi_engine_t* e, int B, int Li_pred, int Lc, i
         // static request buffers (make the captured graph independent of caller pointers)
         {"img_s", (size_t)B * Li * e->d.in_channels * 2}, {"txt_s", (size_t)B * Lt * e->d.ctx_in * 2}, {"y_s", (size_t)B * e->d.vec_in * 2},
         {"pred_s", (size_t)B * Li_pred * c_out(e) * 2}, {"txt_emb", (size_t)B * Lt * H * 2},
-        // split-K partial tiles of the bf16 small-M launches (api.cpp: bf16 operands, >= 192 K-steps): owned by the engine, because its step
+        // split-K partial tiles of the bf16 small-M launches (gemm_dispatch.cpp: bf16 operands, >= 192 K-steps): owned by the engine, because its step
         // graph is captured on a private stream and replayed on the caller's -- a scratch keyed by stream would be nobody's
         {"splitk", needs_splitk(e) ? FLUXMI_SPLITK_WS_BYTES : 256},
         // partial softmax states + arrival counters of attention's balanced grid (attention2.hip, AttnSplit; 69 MB), when this shape uses it.

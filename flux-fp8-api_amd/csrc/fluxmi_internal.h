@@ -88,18 +88,13 @@ unsigned fluxmi_tuning_generation();
 void fluxmi_log_tuning(const char* why);
 
 // ---- internal launchers (defined in the .hip files) --------------------------------------------
-int fluxmi_gemm_tile_ok(int N, int K, int is_fp8, int cfg);
-int fluxmi_launch_gemm_w1_192(FluxmiGemmParams& p, int is_fp8, int act_fmt, hipStream_t s);  // tile config 17 (gemm_w1.hip)
-int fluxmi_launch_gemm_w1_224(FluxmiGemmParams& p, int is_fp8, int act_fmt, hipStream_t s);  // tile config 20 (gemm_w1.hip)
-int fluxmi_launch_gemm_w1_160(FluxmiGemmParams& p, int is_fp8, int act_fmt, hipStream_t s);  // tile config 21 (gemm_w1.hip)
-int fluxmi_gemm_tile_bn(int cfg);
-int fluxmi_gemm_tile_bm(int cfg);
-int fluxmi_launch_gemm(FluxmiGemmParams& p, int is_fp8, int act_fmt, int tile_cfg, hipStream_t s);
+int fluxmi_gemm_tile_ok(int N, int K, int is_fp8, int cfg);  // gemm_dispatch.cpp: config cfg of the table (gemm_cfg.h) tiles this shape
+int fluxmi_launch_gemm(FluxmiGemmParams& p, int is_fp8, int act_fmt, int tile_cfg, hipStream_t s);  // gemm.hip: validates, then the family's launcher:
+int fluxmi_launch_gemm_pp(FluxmiGemmParams& p, int is_fp8, int act_fmt, hipStream_t s);           // ping-pong ring (gemm_pp.hip)
+int fluxmi_launch_gemm_w1(FluxmiGemmParams& p, int is_fp8, int act_fmt, int cfg, hipStream_t s);  // one wave per SIMD, every height (gemm_w1.hip)
 int fluxmi_launch_gemm_generic(FluxmiGemmParams& p, int is_fp8, int act_fmt, hipStream_t s);
 const void* fluxmi_zero_page();  // 256 zero bytes on the current device (vae.hip; allocated once per device, never under stream capture)
 int fluxmi_launch_gemm_conv(FluxmiGemmParams& p, hipStream_t s);  // bf16, tile config 2 with the implicit 3x3 gather (p.conv filled by the caller)
-int fluxmi_gemm_auto_cfg(const FluxmiGemmParams& p, int is_fp8, int act_fmt);
-int fluxmi_gemm_cfg_supports(const FluxmiGemmParams& p, int is_fp8, int act_fmt, int cfg);  // gemm.hip: launch p runs on tile config cfg
 // persistent 256x256 ping-pong kernel (gemm_persist.hip, tile config 18; 19 = with per-tile timestamps)
 int fluxmi_gemm_persist_ok(const FluxmiGemmParams& p, int is_fp8, int act_fmt);
 int fluxmi_launch_gemm_persist(FluxmiGemmParams& p, int is_fp8, int act_fmt, int timing, hipStream_t s);
@@ -112,7 +107,7 @@ int fluxmi_launch_gemm_splitk(FluxmiGemmParams& p, int is_fp8, int act_fmt, int 
 constexpr size_t FLUXMI_SPLITK_WS_BYTES = (size_t)256 << 20;
 void fluxmi_set_splitk_scratch(float* p);
 // the batch of the calling thread's engine (1 = none): bf16 launches take the split-K decision of ONE sample's groups, so a sample's bits do not
-// follow the batch it rides in (api.cpp)
+// follow the batch it rides in (gemm_dispatch.cpp)
 void fluxmi_gemm_set_batch(int B);
 // scratch of attention's balanced grid (attention2.hip, AttnSplit: partial softmax states of the key bins + arrival counters, which must be
 // ZERO when handed over and are left zero by every launch): thread-local like the split-K scratch, an engine owns one; nullptr = the library's own
@@ -122,8 +117,11 @@ void fluxmi_set_attn_scratch(void* p);
 int fluxmi_attn_plan_any(int B, int L, int H);
 int fluxmi_attn_debug_buffer(void* dev_u64);  // fluxmi_attention_debug_buffer
 int fluxmi_attn_plan_export(int B, int L, int H, int* n_per_x, int* full_per_x, int* npieces, unsigned long long* pieces);  // fluxmi_attention_plan  // the same for ANY tuning (what an engine sizes its workspace by: the knob may change later)
-// tile choice + (when it pays) the split of a grouped launch into a 256x256 and a 128x128 launch; any number of groups
+// gemm_dispatch.cpp: plan the launches of a grouped GEMM of any number of groups (tile choice, peel, split-K, chunks of FLUXMI_MAX_GROUPS), then
+// issue them; fluxmi_gemm_plan_export = the plan alone (fluxmi_gemm_plan)
 int fluxmi_gemm_dispatch(const FluxmiGemmGroup* gs, int n, int N, int K, int is_fp8, int act_fmt, int epi, hipStream_t s);
+int fluxmi_gemm_plan_export(const FluxmiGemmGroup* gs, int n, int N, int K, int is_fp8, int act_fmt, int epi, int batch, int* plan, int plan_cap,
+                            int* plan_len);
 int fluxmi_launch_gemv(const FluxmiGemvLayer* layers_dev, FluxmiGemvLayer* layers_host, int n_layers, int B, int total_blocks,
                        int max_K, hipStream_t s, int row0 = 0);
 int fluxmi_gemv_blocks(const FluxmiGemvLayer* layers_host, int n_layers);

@@ -304,22 +304,14 @@ __global__ void __launch_bounds__(256) gemm_generic_kernel(const FluxmiGemmParam
   }
 }
 
-template <int BM, int BN, int WM, int WN, bool FP8, int ACT>
+// the double-buffered kernel of this file on BM x BN tiles (CONV: the implicit 3x3 gather, one group)
+template <int BM, int BN, int WM, int WN, bool FP8, int ACT, bool CONV = false>
 int launch_tile(FluxmiGemmParams& p, hipStream_t s) {
-  int t = 0;
-  for (int i = 0; i < p.n_groups; ++i) {
-    p.g[i].m_tile_start = t;
-    t += (p.g[i].M + BM - 1) / BM;
-  }
-  p.tiles_m_total = t;
+  const int t = assign_m_tiles(p, BM);
   p.group_m = 8;
   constexpr int SMEM = 2 * (BM + BN) * 128;
-  auto kern = gemm_tile_kernel<BM, BN, WM, WN, FP8, ACT>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    FLUXMI_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM));
-    attr_set = true;
-  }
+  constexpr auto kern = gemm_tile_kernel<BM, BN, WM, WN, FP8, ACT, CONV>;
+  FLUXMI_TRY(set_smem_once<kern>(SMEM));
   const int nblk = t * (p.N / BN);
   if (nblk == 0) return 0;
   hipLaunchKernelGGL(kern, dim3(nblk), dim3(WM * WN * 64), SMEM, s, p);
@@ -327,82 +319,24 @@ int launch_tile(FluxmiGemmParams& p, hipStream_t s) {
   return 0;
 }
 
-template <bool FP8, int ACT>
-int launch_cfg(FluxmiGemmParams& p, int cfg, hipStream_t s);
-
-int launch_conv_tile(FluxmiGemmParams& p, hipStream_t s) {
-  constexpr int BM = 128, BN = 128;
-  p.g[0].m_tile_start = 0;
-  p.tiles_m_total = (p.g[0].M + BM - 1) / BM;
-  p.group_m = 8;
-  constexpr int SMEM = 2 * (BM + BN) * 128;
-  auto kern = gemm_tile_kernel<BM, BN, 2, 2, false, FLUXMI_FMT_E5M2, true>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    FLUXMI_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM));
-    attr_set = true;
-  }
-  const int nblk = p.tiles_m_total * (p.N / BN);
-  if (nblk == 0) return 0;
-  hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), SMEM, s, p);
-  FLUXMI_LAUNCH_CHECK();
-  return 0;
-}
-
+// the two tile shapes of the GEMM_FAMILY_TILE configs
 template <bool FP8, int ACT>
 int launch_cfg(FluxmiGemmParams& p, int cfg, hipStream_t s) {
-  switch (cfg) {
-    case 2: return launch_tile<128, 128, 2, 2, FP8, ACT>(p, s);  // two workgroups per CU: thin launches, N % 256 != 0
-    case 15: return launch_tile<128, 64, 4, 1, FP8, ACT>(p, s);  // narrow outputs (LastLayer.linear: N = 64)
-    default: fluxmi_set_error("gemm: unknown tile config %d", cfg); return 1;
-  }
+  return cfg == GEMM_CFG_T128 ? launch_tile<128, 128, 2, 2, FP8, ACT>(p, s) : launch_tile<128, 64, 4, 1, FP8, ACT>(p, s);
 }
 
 }  // namespace
 
-// tile configs (the numbers are part of the C ABI, fluxmi_gemm_grouped): 2 = 128x128 and 15 = 128x64 double-buffered kernels of this
-// file, 13 = 256x256 ping-pong ring (gemm_pp.hip), 16 = 256x256 one wave per SIMD (gemm_w1.hip), 18 = persistent ping-pong
-// (gemm_persist.hip; 19 = its timing build), 100 = generic.  The other numbers
-// belonged to kernel generations that were measured slower and removed in round 3 (profiles/r01_kernel_sweep.txt, r02_gemm_ab.txt).
-int fluxmi_launch_gemm_pp(FluxmiGemmParams& p, int is_fp8, int act_fmt, int cfg, hipStream_t s);
-int fluxmi_launch_gemm_w1(FluxmiGemmParams& p, int is_fp8, int act_fmt, hipStream_t s);
-
-int fluxmi_gemm_tile_bn(int cfg) { return cfg == 2 ? 128 : cfg == 15 ? 64 : (cfg == 13 || cfg == 16 || cfg == 17 || cfg == 18 || cfg == 19 || cfg == 20 || cfg == 21) ? 256 : 0; }
-int fluxmi_gemm_tile_bm(int cfg) { return (cfg == 2 || cfg == 15) ? 128 : cfg == 17 ? 192 : cfg == 20 ? 224 : cfg == 21 ? 160 : (cfg == 13 || cfg == 16 || cfg == 18 || cfg == 19) ? 256 : 0; }
-
-int fluxmi_gemm_tile_ok(int N, int K, int is_fp8, int cfg) {
-  const int bn = fluxmi_gemm_tile_bn(cfg);
-  if (!bn) return 0;
-  const int kb = K * (is_fp8 ? 1 : 2);
-  const int kstep = (cfg == 16 || cfg == 17 || cfg == 18 || cfg == 19 || cfg == 20 || cfg == 21) ? 256 : cfg == 13 ? 64 : 128;
-  if ((cfg == 18 || cfg == 19) && kb < 512) return 0;
-  return (N % bn == 0) && (kb % kstep == 0) && kb >= kstep;
-}
-
-// Whether tile config `cfg` runs launch `p` as it stands: the conditions fluxmi_launch_gemm and the per-config launchers REQUIRE (tiling, the
-// split column, fused K / V^T outputs, operand format and epilogue of configs 17 / 20 / 21, the persistent kernel's conditions for 18 / 19).
-// A forced tile config (fluxmi_tuning_t.gemm_cfg) is taken only where this holds; every other launch keeps the automatic choice.
-int fluxmi_gemm_cfg_supports(const FluxmiGemmParams& p, int is_fp8, int act_fmt, int cfg) {
-  if (!fluxmi_gemm_tile_ok(p.N, p.K, is_fp8, cfg)) return 0;
-  if (p.epi == FLUXMI_EPI_SPLIT && p.g[0].split_n % fluxmi_gemm_tile_bn(cfg) != 0) return 0;
-  bool fused_out = false;
-  for (int i = 0; i < p.n_groups; ++i) fused_out |= (p.g[i].vt_out != nullptr || p.g[i].k_out != nullptr);
-  if (fused_out && cfg != 13 && cfg != 16 && cfg != 18 && cfg != 19) return 0;
-  if (cfg == 18 || cfg == 19) return fluxmi_gemm_persist_ok(p, is_fp8, act_fmt);
-  const bool f8_gate = is_fp8 && act_fmt == FLUXMI_FMT_E5M2 && p.epi == FLUXMI_EPI_GATE_RESID;
-  if (cfg == 17) return f8_gate || (!is_fp8 && (p.epi == FLUXMI_EPI_BF16 || p.epi == FLUXMI_EPI_GATE_RESID));
-  if (cfg == 20 || cfg == 21) return f8_gate;
-  return 1;
-}
-
+// One launch on tile config `cfg` (gemm_cfg.h: what each number means): the checks every config shares, then the launcher of its family.
 int fluxmi_launch_gemm(FluxmiGemmParams& p, int is_fp8, int act_fmt, int cfg, hipStream_t s) {
   FLUXMI_REQUIRE(p.n_groups >= 1 && p.n_groups <= FLUXMI_MAX_GROUPS, "gemm: n_groups=%d out of range", p.n_groups);
   FLUXMI_REQUIRE(fluxmi_gemm_tile_ok(p.N, p.K, is_fp8, cfg), "gemm: shape N=%d K=%d not tileable with cfg %d", p.N, p.K, cfg);
+  const GemmTileCfg& c = *gemm_cfg(cfg);
   if (p.epi == FLUXMI_EPI_SPLIT)
-    FLUXMI_REQUIRE(p.g[0].split_n % fluxmi_gemm_tile_bn(cfg) == 0, "gemm: split_n=%d must be a multiple of the N tile", p.g[0].split_n);
+    FLUXMI_REQUIRE(p.g[0].split_n % c.bn == 0, "gemm: split_n=%d must be a multiple of the N tile", p.g[0].split_n);
   for (int i = 0; i < p.n_groups; ++i)
     if (p.g[i].vt_out || p.g[i].k_out)
-      FLUXMI_REQUIRE(cfg == 13 || cfg == 16 || cfg == 18 || cfg == 19, "gemm: fused K / V^T outputs exist only in the 256x256 tile configs (got %d)", cfg);
+      FLUXMI_REQUIRE(c.fused_kv, "gemm: fused K / V^T outputs exist only in the 256x256 tile configs (got %d)", cfg);
   // activations in the row-pair layout (fluxmi_gemm_group_t.a_pairs / c8_pairs): every group of a launch or none; fp8, dense even rows
   for (int i = 0; i < p.n_groups; ++i) {
     const FluxmiGemmGroup& g = p.g[i];
@@ -419,12 +353,12 @@ int fluxmi_launch_gemm(FluxmiGemmParams& p, int is_fp8, int act_fmt, int cfg, hi
                      "gemm: c8_pairs needs an even M and 64-byte aligned rows / column offsets (group %d)", i);
     }
   }
-  if (cfg == 18 || cfg == 19) return fluxmi_launch_gemm_persist(p, is_fp8, act_fmt, cfg == 19, s);
-  if (cfg == 16) return fluxmi_launch_gemm_w1(p, is_fp8, act_fmt, s);
-  if (cfg == 17) return fluxmi_launch_gemm_w1_192(p, is_fp8, act_fmt, s);
-  if (cfg == 20) return fluxmi_launch_gemm_w1_224(p, is_fp8, act_fmt, s);
-  if (cfg == 21) return fluxmi_launch_gemm_w1_160(p, is_fp8, act_fmt, s);
-  if (cfg == 13) return fluxmi_launch_gemm_pp(p, is_fp8, act_fmt, cfg, s);
+  switch (c.family) {
+    case GEMM_FAMILY_PERSISTENT: return fluxmi_launch_gemm_persist(p, is_fp8, act_fmt, cfg == GEMM_CFG_PERSIST_TIMING, s);
+    case GEMM_FAMILY_ONEWAVE: return fluxmi_launch_gemm_w1(p, is_fp8, act_fmt, cfg, s);
+    case GEMM_FAMILY_PINGPONG: return fluxmi_launch_gemm_pp(p, is_fp8, act_fmt, s);
+    case GEMM_FAMILY_TILE: break;
+  }
   if (is_fp8) {
     if (act_fmt == FLUXMI_FMT_E5M2) return launch_cfg<true, FLUXMI_FMT_E5M2>(p, cfg, s);
     return launch_cfg<true, FLUXMI_FMT_E4M3>(p, cfg, s);
@@ -439,7 +373,7 @@ int fluxmi_launch_gemm_conv(FluxmiGemmParams& p, hipStream_t s) {
                  "conv3x3 (implicit): one group, C %% 64 == 0, K == 9 C, N %% 128 == 0 (C=%d N=%d K=%d)", p.conv.C, p.N, p.K);
   FLUXMI_REQUIRE(p.epi == FLUXMI_EPI_BF16 || p.epi == FLUXMI_EPI_GATE_RESID, "conv3x3 (implicit): plain or residual epilogue");
   FLUXMI_REQUIRE(!p.g[0].a_pairs && !p.g[0].c8_pairs && !p.g[0].vt_out && !p.g[0].k_out, "conv3x3 (implicit): no fused layouts");
-  return launch_conv_tile(p, s);
+  return launch_tile<128, 128, 2, 2, false, FLUXMI_FMT_E5M2, true>(p, s);
 }
 
 int fluxmi_launch_gemm_generic(FluxmiGemmParams& p, int is_fp8, int act_fmt, hipStream_t s) {

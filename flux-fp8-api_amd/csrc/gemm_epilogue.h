@@ -1,7 +1,8 @@
-// fluxmi -- GEMM epilogue helpers shared by the tile kernels (gemm.hip, gemm_pp.hip).
+// fluxmi -- GEMM epilogue and launch helpers shared by the kernel files (gemm.hip, gemm_pp.hip, gemm_w1.hip, gemm_persist.hip).
 #pragma once
 #include "common.h"
 #include "fluxmi_internal.h"
+#include "gemm_cfg.h"
 
 namespace {
 
@@ -463,6 +464,36 @@ __device__ __forceinline__ void lds_epilogue(const FluxmiGemmGroup& G, v16f (&ac
   }
 }
 
+// ---- host-side launch glue: ONE copy for the four kernel files -------------------------------------------------------------------
+// (The device side keeps its copies -- block -> (group, tile) mapping, the switch over the six epilogues: as shared __forceinline__ helpers
+// they changed the register allocation of the kernels, which depend on it: Makefile header, profiles/r07_gemm_refactor_device_code.txt.)
+// every group's first row tile on BM-row tiles (FluxmiGemmGroup.m_tile_start) and their total, which is returned
+inline int assign_m_tiles(FluxmiGemmParams& p, int BM) {
+  int t = 0;
+  for (int i = 0; i < p.n_groups; ++i) { p.g[i].m_tile_start = t; t += (p.g[i].M + BM - 1) / BM; }
+  return p.tiles_m_total = t;
+}
 
+// hipFuncAttributeMaxDynamicSharedMemorySize, set once per kernel (KERN = the instantiation: one flag each)
+template <auto KERN> int set_smem_once(int bytes) {
+  static bool attr_set = false;
+  if (!attr_set) FLUXMI_CHECK_HIP(hipFuncSetAttribute((const void*)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+  attr_set = true;
+  return 0;
+}
+
+// the pending weight prefetch (FluxmiPrefetch) for a launch that can carry it, unless fluxmi_tuning_t.prefetch is off; consumed either way
+inline FluxmiPrefetch take_prefetch() {
+  FluxmiPrefetch pf = fluxmi_take_prefetch();
+  if (!fluxmi_tuning().prefetch) pf.n = 0;
+  return pf;
+}
+
+// buffer descriptors address 4 GiB per operand: every A panel and the weight stay below (eb = bytes per element)
+inline bool operands_below_4gib(const FluxmiGemmParams& p, int eb) {
+  for (int i = 0; i < p.n_groups; ++i)
+    if ((long long)p.g[i].M * p.g[i].lda * eb >= (1LL << 32)) return false;
+  return (long long)p.N * p.K * eb < (1LL << 32);
+}
 
 }  // namespace

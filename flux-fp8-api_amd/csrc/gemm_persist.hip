@@ -800,12 +800,7 @@ __global__ void __launch_bounds__(512, 2) gemm_ps_kernel(const FluxmiGemmParams 
 template <bool FP8, int ACT, int ESEL, bool TIMING>
 int launch_ps(FluxmiGemmParams& p, hipStream_t s) {
   constexpr int BM = 256, BN = 256;
-  int t = 0;
-  for (int i = 0; i < p.n_groups; ++i) {
-    p.g[i].m_tile_start = t;
-    t += (p.g[i].M + BM - 1) / BM;
-  }
-  p.tiles_m_total = t;
+  const int t = assign_m_tiles(p, BM);
   // bands of FOUR row tiles (the one-tile-per-workgroup kernels use 8): an XCD's 32 concurrent tiles are 4 rows x 8 columns, the four A
   // panels of a band (3.1 MB at K = 3072) stay in its 4 MiB L2 while the band's columns stream by, and the fused-K / V^T tiles of a
   // launch spread more evenly over the workgroups.  Measured: qkv 145.2 -> 136.5 us, linear1 296.9 -> 292.7 us, step 41.64 -> 41.30 ms
@@ -815,12 +810,8 @@ int launch_ps(FluxmiGemmParams& p, hipStream_t s) {
 #endif
   p.group_m = PS_GROUP_M;
   constexpr int SMEM = 5 * (BM + BN) * 64;  // five ring slots = all 160 KiB (the epilogue borrows the dead ones)
-  auto kern = gemm_ps_kernel<FP8, ACT, ESEL, TIMING>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    FLUXMI_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM));
-    attr_set = true;
-  }
+  constexpr auto kern = gemm_ps_kernel<FP8, ACT, ESEL, TIMING>;
+  FLUXMI_TRY(set_smem_once<kern>(SMEM));
   const int nblk = t * (p.N / BN);
   if (nblk == 0) return 0;
   static int n_cu = 0;
@@ -852,6 +843,7 @@ int fluxmi_gemm_persist_ok(const FluxmiGemmParams& p, int is_fp8, int act_fmt) {
   if (!is_fp8 || act_fmt != FLUXMI_FMT_E5M2) return 0;
   if (p.N % 256 != 0 || p.K % 256 != 0 || p.K < 512) return 0;
   if (p.epi != FLUXMI_EPI_BF16 && p.epi != FLUXMI_EPI_GATE_RESID && p.epi != FLUXMI_EPI_SPLIT && p.epi != FLUXMI_EPI_GELU_QUANT) return 0;
+  if (!operands_below_4gib(p, 1)) return 0;
   for (int i = 0; i < p.n_groups; ++i) {
     const FluxmiGemmGroup& g = p.g[i];
     if (g.lda != p.g[0].lda || (g.W_pairs != nullptr) != (p.g[0].W_pairs != nullptr) || (g.a_pairs != 0) != (p.g[0].a_pairs != 0)) return 0;
@@ -859,7 +851,6 @@ int fluxmi_gemm_persist_ok(const FluxmiGemmParams& p, int is_fp8, int act_fmt) {
     if (g.k_out && (g.kv_col0 % 256 != 0 || (g.heads * 128) % 256 != 0 || !g.pe || !g.k_norm || g.k_rows <= 0 ||
                     (long long)g.heads * g.k_rows * 256 >= (1LL << 32) || (p.epi != FLUXMI_EPI_BF16 && p.epi != FLUXMI_EPI_SPLIT)))
       return 0;
-    if ((long long)g.M * g.lda >= (1LL << 32) || (long long)p.N * p.K >= (1LL << 32)) return 0;
     if ((p.epi == FLUXMI_EPI_SPLIT || p.epi == FLUXMI_EPI_GELU_QUANT) && !g.q_lut) return 0;
     if (p.epi == FLUXMI_EPI_SPLIT && (g.split_n % 256 != 0 || g.split_n != p.g[0].split_n)) return 0;
   }
@@ -872,18 +863,14 @@ int fluxmi_launch_gemm_persist(FluxmiGemmParams& p, int is_fp8, int act_fmt, int
                  "gemm_persist: needs fp8 x e5m2 operands, N %% 256 == 0, K %% 256 == 0, K >= 512, a bf16 / gate_resid / split / gelu_quant "
                  "epilogue (the quantising ones with a table), one lda (N=%d K=%d epi=%d)", p.N, p.K, p.epi);
   p.dbg = timing ? g_ps_dbg : nullptr;
-  if (timing) {
+  auto launch = [&](auto TIMING) {
+    constexpr bool T = decltype(TIMING)::value;
     switch (p.epi) {
-      case FLUXMI_EPI_BF16: return launch_ps<true, FLUXMI_FMT_E5M2, FLUXMI_EPI_BF16, true>(p, s);
-      case FLUXMI_EPI_GATE_RESID: return launch_ps<true, FLUXMI_FMT_E5M2, FLUXMI_EPI_GATE_RESID, true>(p, s);
-      case FLUXMI_EPI_SPLIT: return launch_ps<true, FLUXMI_FMT_E5M2, FLUXMI_EPI_SPLIT, true>(p, s);
-      default: return launch_ps<true, FLUXMI_FMT_E5M2, FLUXMI_EPI_GELU_QUANT, true>(p, s);
+      case FLUXMI_EPI_BF16: return launch_ps<true, FLUXMI_FMT_E5M2, FLUXMI_EPI_BF16, T>(p, s);
+      case FLUXMI_EPI_GATE_RESID: return launch_ps<true, FLUXMI_FMT_E5M2, FLUXMI_EPI_GATE_RESID, T>(p, s);
+      case FLUXMI_EPI_SPLIT: return launch_ps<true, FLUXMI_FMT_E5M2, FLUXMI_EPI_SPLIT, T>(p, s);
+      default: return launch_ps<true, FLUXMI_FMT_E5M2, FLUXMI_EPI_GELU_QUANT, T>(p, s);
     }
-  }
-  switch (p.epi) {
-    case FLUXMI_EPI_BF16: return launch_ps<true, FLUXMI_FMT_E5M2, FLUXMI_EPI_BF16, false>(p, s);
-    case FLUXMI_EPI_GATE_RESID: return launch_ps<true, FLUXMI_FMT_E5M2, FLUXMI_EPI_GATE_RESID, false>(p, s);
-    case FLUXMI_EPI_SPLIT: return launch_ps<true, FLUXMI_FMT_E5M2, FLUXMI_EPI_SPLIT, false>(p, s);
-    default: return launch_ps<true, FLUXMI_FMT_E5M2, FLUXMI_EPI_GELU_QUANT, false>(p, s);
-  }
+  };
+  return timing ? launch(std::true_type{}) : launch(std::false_type{});
 }

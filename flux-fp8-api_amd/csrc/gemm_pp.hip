@@ -36,7 +36,7 @@ namespace {
 // SPLITK: blockIdx.x = split * tiles + tile; the workgroup accumulates K-steps [split * nk / S, (split + 1) * nk / S) of its tile and
 // stores the raw fp32 accumulators (no scale, no bias) into P.partial -- the small-M launches (M <= 512: schnell 256x256, the text
 // encoders) have 24-96 tiles for 256 CUs and are weight-stream bound: a tile per workgroup leaves the stream to a tenth of the chip.
-template <bool FP8, int ACT_FMT, int VAR, int ESEL, bool SPLITK = false>
+template <bool FP8, int ACT_FMT, int ESEL, bool SPLITK = false>
 __global__ void __launch_bounds__(512, 2) gemm_pp_kernel(const FluxmiGemmParams P) {
   constexpr int BM = 256, BN = 256, WM = 2, WN = 4, NT = 512, TM = 4, TN = 2, NS = 4, D = 3;
   constexpr int WTM = 128, WTN = 64;
@@ -75,9 +75,8 @@ __global__ void __launch_bounds__(512, 2) gemm_pp_kernel(const FluxmiGemmParams 
   const int k_begin = SPLITK ? (int)(((long long)split * nk_all) / P.split_k) : 0;
   const int nk = SPLITK ? (int)(((long long)(split + 1) * nk_all) / P.split_k) - k_begin : nk_all;
 
-  // VAR & 4: LDS-DMA through buffer descriptors (SGPR tile / K offsets, rows past M read as zero) instead of per-lane 64-bit
-  // addresses (4 v_lshl_add_u64 per K-step and a clamped row index)
-  constexpr bool BUF = (VAR & 4) != 0;
+  // LDS-DMA from per-lane 64-bit addresses, rows clamped to M - 1.  (Nothing reads a_voff / w_voff / ars / wrs / *_soff0, the operands of a removed
+  // descriptor staging path: without them hipcc orders the fp8 kernels' prologue differently -- profiles/r07_gemm_refactor_device_code.txt.)
   const unsigned char* srcA[IA];
   const unsigned char* srcW[IW];
   unsigned a_voff[IA], w_voff[IW];
@@ -85,7 +84,7 @@ __global__ void __launch_bounds__(512, 2) gemm_pp_kernel(const FluxmiGemmParams 
   const bool a_pairs = FP8 && !SPLITK && G.a_pairs != 0;
   const int a_kstep = a_pairs ? 128 : 64;
   // W in the row-pair layout when the caller has one (fluxmi_gemm_group_t.W_pairs, as in the persistent and the one-wave kernels)
-  const bool w_pairs = G.W_pairs != nullptr;  // fp8 or bf16 (row bytes K * EB), split-K or not (this launch uses per-lane pointers: VAR 2)
+  const bool w_pairs = G.W_pairs != nullptr;  // fp8 or bf16 (row bytes K * EB), split-K or not
   const int w_kstep = w_pairs ? 128 : 64;
   const unsigned char* w_base = (const unsigned char*)(w_pairs ? G.W_pairs : G.W);
 #pragma unroll
@@ -110,18 +109,10 @@ __global__ void __launch_bounds__(512, 2) gemm_pp_kernel(const FluxmiGemmParams 
   auto stage = [&](int kt, int slot) {
     unsigned char* dA = smem + slot * STAGE + wave * 1024;
     unsigned char* dW = dA + A_BYTES;
-    if constexpr (BUF) {
 #pragma unroll
-      for (int i = 0; i < IA; ++i) dma16_buf(ars, dA + NT * 16 * i, a_voff[i], a_soff0 + kt * a_kstep);
+    for (int i = 0; i < IA; ++i) glds16(srcA[i] + (long long)kt * a_kstep, dA + NT * 16 * i);
 #pragma unroll
-      for (int i = 0; i < IW; ++i) dma16_buf(wrs, dW + NT * 16 * i, w_voff[i], w_soff0 + kt * w_kstep);
-    } else {
-      const long long koff = (long long)kt * 64;
-#pragma unroll
-      for (int i = 0; i < IA; ++i) glds16(srcA[i] + (long long)kt * a_kstep, dA + NT * 16 * i);
-#pragma unroll
-      for (int i = 0; i < IW; ++i) glds16(srcW[i] + (long long)kt * w_kstep, dW + NT * 16 * i);
-    }
+    for (int i = 0; i < IW; ++i) glds16(srcW[i] + (long long)kt * w_kstep, dW + NT * 16 * i);
   };
 
   v16f acc[TM][TN];
@@ -190,9 +181,7 @@ __global__ void __launch_bounds__(512, 2) gemm_pp_kernel(const FluxmiGemmParams 
       if (kt + 2 < nk) wait_vmcnt<LPT>(); else wait_vmcnt<0>();
       __builtin_amdgcn_s_barrier();
       fence();
-      if (VAR & 1) __builtin_amdgcn_s_setprio(1);
       mma_all();
-      if (VAR & 1) __builtin_amdgcn_s_setprio(0);
       fence();
       const int rslot = slot == 0 ? NS - 1 : slot - 1;
       if (kt + D < nk) stage(kt + D, rslot);
@@ -208,26 +197,12 @@ __global__ void __launch_bounds__(512, 2) gemm_pp_kernel(const FluxmiGemmParams 
       __builtin_amdgcn_s_barrier();
       fence();
       const int rslot = slot == 0 ? NS - 1 : slot - 1;
-      if (VAR & 8) {
-        read_frags(slot);
-      } else if (VAR & 2) {
-        read_frags(slot);
-        fence();
-        if (kt + D < nk) stage(kt + D, rslot);
-      } else {
-        if (kt + D < nk) stage(kt + D, rslot);
-        fence();
-        read_frags(slot);
-      }
+      read_frags(slot);
       fence();
-      if (VAR & 1) __builtin_amdgcn_s_setprio(1);
+      if (kt + D < nk) stage(kt + D, rslot);
+      fence();
       mma_all();
-      if (VAR & 1) __builtin_amdgcn_s_setprio(0);
       fence();
-      if (VAR & 8) {  // refill behind this wave's own MFMA block (an LDS-DMA piece issues in 60 cycles there, 100-185 beside ds_reads)
-        if (kt + D < nk) stage(kt + D, rslot);
-        fence();
-      }
       slot = slot + 1 == NS ? 0 : slot + 1;
     }
   }
@@ -260,41 +235,33 @@ __global__ void __launch_bounds__(512, 2) gemm_pp_kernel(const FluxmiGemmParams 
   if constexpr (ESEL >= 0) {
     lds_epilogue<ESEL, ACT_FMT, TM, TN>(G, acc, s, qs, wbuf, mw, nw, M, lane, xchg, wave, smem);
   } else {
-    switch (P.epi) {
-      case FLUXMI_EPI_BF16: lds_epilogue<FLUXMI_EPI_BF16, ACT_FMT, TM, TN>(G, acc, s, qs, wbuf, mw, nw, M, lane, xchg, wave, smem); break;
-      case FLUXMI_EPI_GELU_QUANT: lds_epilogue<FLUXMI_EPI_GELU_QUANT, ACT_FMT, TM, TN>(G, acc, s, qs, wbuf, mw, nw, M, lane, xchg, wave, smem); break;
-      case FLUXMI_EPI_GATE_RESID: lds_epilogue<FLUXMI_EPI_GATE_RESID, ACT_FMT, TM, TN>(G, acc, s, qs, wbuf, mw, nw, M, lane, xchg, wave, smem); break;
-      case FLUXMI_EPI_SPLIT: lds_epilogue<FLUXMI_EPI_SPLIT, ACT_FMT, TM, TN>(G, acc, s, qs, wbuf, mw, nw, M, lane, xchg, wave, smem); break;
-      case FLUXMI_EPI_QUANT: lds_epilogue<FLUXMI_EPI_QUANT, ACT_FMT, TM, TN>(G, acc, s, qs, wbuf, mw, nw, M, lane, xchg, wave, smem); break;
-      case FLUXMI_EPI_SILU_QUANT: lds_epilogue<FLUXMI_EPI_SILU_QUANT, ACT_FMT, TM, TN>(G, acc, s, qs, wbuf, mw, nw, M, lane, xchg, wave, smem); break;
-      default: break;
-    }
+  switch (P.epi) {
+    case FLUXMI_EPI_BF16: lds_epilogue<FLUXMI_EPI_BF16, ACT_FMT, TM, TN>(G, acc, s, qs, wbuf, mw, nw, M, lane, xchg, wave, smem); break;
+    case FLUXMI_EPI_GELU_QUANT: lds_epilogue<FLUXMI_EPI_GELU_QUANT, ACT_FMT, TM, TN>(G, acc, s, qs, wbuf, mw, nw, M, lane, xchg, wave, smem); break;
+    case FLUXMI_EPI_GATE_RESID: lds_epilogue<FLUXMI_EPI_GATE_RESID, ACT_FMT, TM, TN>(G, acc, s, qs, wbuf, mw, nw, M, lane, xchg, wave, smem); break;
+    case FLUXMI_EPI_SPLIT: lds_epilogue<FLUXMI_EPI_SPLIT, ACT_FMT, TM, TN>(G, acc, s, qs, wbuf, mw, nw, M, lane, xchg, wave, smem); break;
+    case FLUXMI_EPI_QUANT: lds_epilogue<FLUXMI_EPI_QUANT, ACT_FMT, TM, TN>(G, acc, s, qs, wbuf, mw, nw, M, lane, xchg, wave, smem); break;
+    case FLUXMI_EPI_SILU_QUANT: lds_epilogue<FLUXMI_EPI_SILU_QUANT, ACT_FMT, TM, TN>(G, acc, s, qs, wbuf, mw, nw, M, lane, xchg, wave, smem); break;
+    default: break;
+  }
   }
 }
 
-template <bool FP8, int ACT, int VAR, int ESEL = -1>
+constexpr int PP_BM = 256, PP_BN = 256;
+constexpr int PP_SMEM = 4 * (PP_BM + PP_BN) * 64 + 8 * 128 * 4;  // ring + the K-epilogue's row-sum exchange (8 waves x 128 rows)
+
+template <bool FP8, int ACT, int ESEL = -1>
 int launch_pp(FluxmiGemmParams& p, hipStream_t s) {
-  constexpr int BM = 256, BN = 256;
-  int t = 0;
-  for (int i = 0; i < p.n_groups; ++i) {
-    p.g[i].m_tile_start = t;
-    t += (p.g[i].M + BM - 1) / BM;
-  }
-  p.tiles_m_total = t;
+  const int t = assign_m_tiles(p, PP_BM);
   p.group_m = 8;
-  constexpr int SMEM = 4 * (BM + BN) * 64 + 8 * 128 * 4;  // ring + the K-epilogue's row-sum exchange (8 waves x 128 rows)
-  auto kern = gemm_pp_kernel<FP8, ACT, VAR, ESEL>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    FLUXMI_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM));
-    attr_set = true;
-  }
-  const int nblk = t * (p.N / BN);
+  constexpr auto kern = gemm_pp_kernel<FP8, ACT, ESEL>;
+  FLUXMI_TRY(set_smem_once<kern>(PP_SMEM));
+  const int nblk = t * (p.N / PP_BN);
   if (nblk == 0) return 0;
   const int idle = (256 - nblk % 256) % 256;
   const int extra = p.pf.n > 0 ? std::min(p.pf.wgs, idle) : 0;
   if (!extra) p.pf.n = 0;
-  hipLaunchKernelGGL(kern, dim3(nblk + extra), dim3(512), SMEM, s, p);
+  hipLaunchKernelGGL(kern, dim3(nblk + extra), dim3(512), PP_SMEM, s, p);
   FLUXMI_LAUNCH_CHECK();
   return 0;
 }
@@ -368,13 +335,8 @@ int splitk_workspace(hipStream_t s, float** out) {
 
 template <bool FP8, int ACT>
 int launch_pp_splitk(FluxmiGemmParams& p, int split_k, hipStream_t s) {
-  constexpr int BM = 256, BN = 256;
-  int t = 0;
-  for (int i = 0; i < p.n_groups; ++i) {
-    p.g[i].m_tile_start = t;
-    t += (p.g[i].M + BM - 1) / BM;
-  }
-  p.tiles_m_total = t;
+  constexpr int BM = PP_BM, BN = PP_BN;
+  const int t = assign_m_tiles(p, BM);
   p.group_m = 8;
   const int nblk = t * (p.N / BN);
   if (nblk == 0) return 0;
@@ -388,14 +350,9 @@ int launch_pp_splitk(FluxmiGemmParams& p, int split_k, hipStream_t s) {
   p.split_k = split_k;
   p.partial = ws;
   p.pf.n = 0;
-  constexpr int SMEM = 4 * (BM + BN) * 64 + 8 * 128 * 4;
-  auto kern = gemm_pp_kernel<FP8, ACT, 2, -1, true>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    FLUXMI_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM));
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(nblk * split_k), dim3(512), SMEM, s, p);
+  constexpr auto kern = gemm_pp_kernel<FP8, ACT, -1, true>;
+  FLUXMI_TRY(set_smem_once<kern>(PP_SMEM));
+  hipLaunchKernelGGL(kern, dim3(nblk * split_k), dim3(512), PP_SMEM, s, p);
   FLUXMI_LAUNCH_CHECK();
   if (p.epi == FLUXMI_EPI_GATE_RESID) hipLaunchKernelGGL(splitk_reduce_kernel<FLUXMI_EPI_GATE_RESID>, dim3(t * BM), dim3(256), 0, s, p);
   else hipLaunchKernelGGL(splitk_reduce_kernel<FLUXMI_EPI_BF16>, dim3(t * BM), dim3(256), 0, s, p);
@@ -409,14 +366,14 @@ int launch_pp_cfg(FluxmiGemmParams& p, hipStream_t s) {
   if constexpr (ACT == FLUXMI_FMT_E5M2) {
     const int esel = fluxmi_tuning().gemm_esel;  // 0: the run-time-switch kernel for every epilogue (A/B)
     if (esel) switch (p.epi) {
-      case FLUXMI_EPI_BF16: return launch_pp<FP8, ACT, 2, FLUXMI_EPI_BF16>(p, s);
-      case FLUXMI_EPI_GATE_RESID: return launch_pp<FP8, ACT, 2, FLUXMI_EPI_GATE_RESID>(p, s);
-      case FLUXMI_EPI_SPLIT: if constexpr (FP8) return launch_pp<FP8, ACT, 2, FLUXMI_EPI_SPLIT>(p, s); else break;
-      case FLUXMI_EPI_GELU_QUANT: if constexpr (FP8) return launch_pp<FP8, ACT, 2, FLUXMI_EPI_GELU_QUANT>(p, s); else break;
+      case FLUXMI_EPI_BF16: return launch_pp<FP8, ACT, FLUXMI_EPI_BF16>(p, s);
+      case FLUXMI_EPI_GATE_RESID: return launch_pp<FP8, ACT, FLUXMI_EPI_GATE_RESID>(p, s);
+      case FLUXMI_EPI_SPLIT: if constexpr (FP8) return launch_pp<FP8, ACT, FLUXMI_EPI_SPLIT>(p, s); else break;
+      case FLUXMI_EPI_GELU_QUANT: if constexpr (FP8) return launch_pp<FP8, ACT, FLUXMI_EPI_GELU_QUANT>(p, s); else break;
       default: break;
     }
   }
-  return launch_pp<FP8, ACT, 2>(p, s);
+  return launch_pp<FP8, ACT>(p, s);
 }
 
 }  // namespace
@@ -424,7 +381,7 @@ int launch_pp_cfg(FluxmiGemmParams& p, hipStream_t s) {
 void fluxmi_set_splitk_scratch(float* p) { t_splitk_override = p; }
 
 int fluxmi_launch_gemm_splitk(FluxmiGemmParams& p, int is_fp8, int act_fmt, int split_k, hipStream_t s) {
-  FLUXMI_REQUIRE(fluxmi_gemm_tile_ok(p.N, p.K, is_fp8, 13), "gemm split-K: shape N=%d K=%d not tileable", p.N, p.K);
+  FLUXMI_REQUIRE(fluxmi_gemm_tile_ok(p.N, p.K, is_fp8, GEMM_CFG_PP), "gemm split-K: shape N=%d K=%d not tileable", p.N, p.K);
   for (int i = 0; i < p.n_groups; ++i)
     FLUXMI_REQUIRE(!p.g[i].vt_out && !p.g[i].k_out && !p.g[i].a_pairs && !p.g[i].c8_pairs, "gemm split-K: no fused K / V^T outputs, no row-pair activation layout");
   if (is_fp8) {
@@ -434,11 +391,9 @@ int fluxmi_launch_gemm_splitk(FluxmiGemmParams& p, int is_fp8, int act_fmt, int 
   return launch_pp_splitk<false, FLUXMI_FMT_E5M2>(p, split_k, s);
 }
 
-// config 13 = 256x256 ping-pong ring (8 waves)
-int fluxmi_launch_gemm_pp(FluxmiGemmParams& p, int is_fp8, int act_fmt, int cfg, hipStream_t s) {
-  p.pf = fluxmi_take_prefetch();
-  if (!fluxmi_tuning().prefetch) p.pf.n = 0;
-  FLUXMI_REQUIRE(cfg == 13, "gemm_pp: unknown tile config %d", cfg);
+// GEMM_CFG_PP = 256x256 ping-pong ring (8 waves)
+int fluxmi_launch_gemm_pp(FluxmiGemmParams& p, int is_fp8, int act_fmt, hipStream_t s) {
+  p.pf = take_prefetch();
   if (is_fp8) {
     if (act_fmt == FLUXMI_FMT_E5M2) return launch_pp_cfg<true, FLUXMI_FMT_E5M2>(p, s);
     return launch_pp_cfg<true, FLUXMI_FMT_E4M3>(p, s);

@@ -205,27 +205,22 @@ __global__ void __launch_bounds__(256, 1) gemm_w1_kernel(const FluxmiGemmParams 
   if constexpr (ESEL >= 0) {
     lds_epilogue<ESEL, ACT_FMT, TM, TN>(G, acc, s, qs, wbuf, mw, nw, M, lane);
   } else {
-    switch (P.epi) {
-      case FLUXMI_EPI_BF16: lds_epilogue<FLUXMI_EPI_BF16, ACT_FMT, TM, TN>(G, acc, s, qs, wbuf, mw, nw, M, lane); break;
-      case FLUXMI_EPI_GELU_QUANT: lds_epilogue<FLUXMI_EPI_GELU_QUANT, ACT_FMT, TM, TN>(G, acc, s, qs, wbuf, mw, nw, M, lane); break;
-      case FLUXMI_EPI_GATE_RESID: lds_epilogue<FLUXMI_EPI_GATE_RESID, ACT_FMT, TM, TN>(G, acc, s, qs, wbuf, mw, nw, M, lane); break;
-      case FLUXMI_EPI_SPLIT: lds_epilogue<FLUXMI_EPI_SPLIT, ACT_FMT, TM, TN>(G, acc, s, qs, wbuf, mw, nw, M, lane); break;
-      case FLUXMI_EPI_QUANT: lds_epilogue<FLUXMI_EPI_QUANT, ACT_FMT, TM, TN>(G, acc, s, qs, wbuf, mw, nw, M, lane); break;
-      case FLUXMI_EPI_SILU_QUANT: lds_epilogue<FLUXMI_EPI_SILU_QUANT, ACT_FMT, TM, TN>(G, acc, s, qs, wbuf, mw, nw, M, lane); break;
-      default: break;
-    }
+  switch (P.epi) {
+    case FLUXMI_EPI_BF16: lds_epilogue<FLUXMI_EPI_BF16, ACT_FMT, TM, TN>(G, acc, s, qs, wbuf, mw, nw, M, lane); break;
+    case FLUXMI_EPI_GELU_QUANT: lds_epilogue<FLUXMI_EPI_GELU_QUANT, ACT_FMT, TM, TN>(G, acc, s, qs, wbuf, mw, nw, M, lane); break;
+    case FLUXMI_EPI_GATE_RESID: lds_epilogue<FLUXMI_EPI_GATE_RESID, ACT_FMT, TM, TN>(G, acc, s, qs, wbuf, mw, nw, M, lane); break;
+    case FLUXMI_EPI_SPLIT: lds_epilogue<FLUXMI_EPI_SPLIT, ACT_FMT, TM, TN>(G, acc, s, qs, wbuf, mw, nw, M, lane); break;
+    case FLUXMI_EPI_QUANT: lds_epilogue<FLUXMI_EPI_QUANT, ACT_FMT, TM, TN>(G, acc, s, qs, wbuf, mw, nw, M, lane); break;
+    case FLUXMI_EPI_SILU_QUANT: lds_epilogue<FLUXMI_EPI_SILU_QUANT, ACT_FMT, TM, TN>(G, acc, s, qs, wbuf, mw, nw, M, lane); break;
+    default: break;
+  }
   }
 }
 
 template <bool FP8, int ACT, int ESEL = -1, int TM_ = 4, int WM_ = 2>
 int launch_w1(FluxmiGemmParams& p, hipStream_t s) {
   constexpr int BM = 32 * WM_ * TM_, BN = 256, A_ROWS = ((BM + 63) / 64) * 64;
-  int t = 0;
-  for (int i = 0; i < p.n_groups; ++i) {
-    p.g[i].m_tile_start = t;
-    t += (p.g[i].M + BM - 1) / BM;
-  }
-  p.tiles_m_total = t;
+  const int t = assign_m_tiles(p, BM);
   // bands of six row tiles: the step's launches of this kernel have 18 (three equal bands instead of 8 + 8 + 2); in-step A/B of 8 / 4 / 6:
   // 40.93 / 40.85 / 40.77 ms per step (profiles/r04_gemm_persist.txt section 11)
 #ifndef W1_GROUP_M
@@ -233,12 +228,8 @@ int launch_w1(FluxmiGemmParams& p, hipStream_t s) {
 #endif
   p.group_m = W1_GROUP_M;
   constexpr int SMEM = 4 * (A_ROWS + BN) * 64;
-  auto kern = gemm_w1_kernel<FP8, ACT, ESEL, TM_, WM_>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    FLUXMI_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM));
-    attr_set = true;
-  }
+  constexpr auto kern = gemm_w1_kernel<FP8, ACT, ESEL, TM_, WM_>;
+  FLUXMI_TRY(set_smem_once<kern>(SMEM));
   const int nblk = t * (p.N / BN);
   if (nblk == 0) return 0;
   // a launch that leaves CUs idle in its last round carries the pending weight prefetch on them (fluxmi_internal.h, FluxmiPrefetch)
@@ -254,72 +245,39 @@ int launch_w1(FluxmiGemmParams& p, hipStream_t s) {
 
 }  // namespace
 
-// config 17 = the same kernel on 192 x 256 tiles, for the launches it exists for: fp8 x e5m2 operands with the gate*y+x epilogue (Flux-dev
-// 768^2 mlp.2 / linear2) and bf16 operands with the plain or the gate*y+x epilogue (M = 512: Flux-schnell 256^2 linear1 runs 3 x 84 = 252
-// tiles instead of 2 x 84 = 168 for 256 CUs; the text encoders)
-int fluxmi_launch_gemm_w1_192(FluxmiGemmParams& p, int is_fp8, int act_fmt, hipStream_t s) {
-  const bool f8_ok = is_fp8 && act_fmt == FLUXMI_FMT_E5M2 && p.epi == FLUXMI_EPI_GATE_RESID;
-  const bool bf_ok = !is_fp8 && (p.epi == FLUXMI_EPI_BF16 || p.epi == FLUXMI_EPI_GATE_RESID);
-  FLUXMI_REQUIRE(f8_ok || bf_ok, "gemm tile config 17 (192x256 one-wave-per-SIMD tiles): fp8 x e5m2 operands with the gate*y+x epilogue, or bf16 operands "
-                 "with the plain / gate*y+x epilogue (fp8 %d, epi %d)", is_fp8, p.epi);
-  for (int i = 0; i < p.n_groups; ++i)
-    FLUXMI_REQUIRE(!p.g[i].vt_out && !p.g[i].k_out, "gemm tile config 17: no fused K / V^T outputs");
-  p.pf = fluxmi_take_prefetch();
-  if (!fluxmi_tuning().prefetch) p.pf.n = 0;
-  const int eb = is_fp8 ? 1 : 2;
-  for (int i = 0; i < p.n_groups; ++i)
-    FLUXMI_REQUIRE((long long)p.g[i].M * p.g[i].lda * eb < (1LL << 32) && (long long)p.N * p.K * eb < (1LL << 32), "gemm_w1: operand larger than 4 GiB");
-  if (is_fp8) return launch_w1<true, FLUXMI_FMT_E5M2, FLUXMI_EPI_GATE_RESID, 3>(p, s);
-  if (p.epi == FLUXMI_EPI_GATE_RESID) return launch_w1<false, FLUXMI_FMT_E5M2, FLUXMI_EPI_GATE_RESID, 3>(p, s);
-  return launch_w1<false, FLUXMI_FMT_E5M2, FLUXMI_EPI_BF16, 3>(p, s);
-}
-
-// config 20 (round 6) = 224 x 256 tiles, the four waves side by side along N (wave tile 224 x 64): fp8 x e5m2 operands with the gate*y+x epilogue
-// -- the exact fit of Flux-dev 1024^2 linear2 (21 x 12 = 252 tiles for 256 CUs)
-int fluxmi_launch_gemm_w1_224(FluxmiGemmParams& p, int is_fp8, int act_fmt, hipStream_t s) {
-  FLUXMI_REQUIRE(is_fp8 && act_fmt == FLUXMI_FMT_E5M2 && p.epi == FLUXMI_EPI_GATE_RESID,
-                 "gemm tile config 20 (224x256 one-wave-per-SIMD tiles): fp8 x e5m2 operands with the gate*y+x epilogue (fp8 %d, epi %d)", is_fp8, p.epi);
-  for (int i = 0; i < p.n_groups; ++i) {
-    FLUXMI_REQUIRE(!p.g[i].vt_out && !p.g[i].k_out, "gemm tile config 20: no fused K / V^T outputs");
-    FLUXMI_REQUIRE((long long)p.g[i].M * p.g[i].lda < (1LL << 32) && (long long)p.N * p.K < (1LL << 32), "gemm_w1: operand larger than 4 GiB");
+// The one-wave-per-SIMD family: height, wave grid and what a height is compiled for come from the table (gemm_cfg.h).  The lower tiles exist for the
+// launches they fit: 192 rows -- Flux-dev 768^2 mlp.2 / linear2, and bf16 at M = 512 (Flux-schnell 256^2 linear1: 3 x 84 = 252 tiles instead of 168; the
+// text encoders); 224 rows -- Flux-dev 1024^2 linear2 (21 x 12 = 252 tiles for 256 CUs); 160 rows -- 768^2 again (M = 2816: 216 tiles of 5/8 the work).
+int fluxmi_launch_gemm_w1(FluxmiGemmParams& p, int is_fp8, int act_fmt, int cfg, hipStream_t s) {
+  const GemmTileCfg* c = gemm_cfg(cfg);
+  FLUXMI_REQUIRE(c && c->family == GEMM_FAMILY_ONEWAVE, "gemm_w1: unknown tile config %d", cfg);
+  FLUXMI_REQUIRE(gemm_cfg_takes(*c, is_fp8, act_fmt, p.epi), "gemm tile config %d (%dx%d one-wave-per-SIMD tiles): fp8 x e5m2 operands with the gate*y+x epilogue%s (fp8 %d, epi %d)",
+                 cfg, c->bm, c->bn, c->takes == GEMM_TAKES_F8_GATE ? "" : ", or bf16 operands with the plain / gate*y+x epilogue", is_fp8, p.epi);
+  if (!c->fused_kv)
+    for (int i = 0; i < p.n_groups; ++i) FLUXMI_REQUIRE(!p.g[i].vt_out && !p.g[i].k_out, "gemm tile config %d: no fused K / V^T outputs", cfg);
+  FLUXMI_REQUIRE(operands_below_4gib(p, is_fp8 ? 1 : 2), "gemm_w1: operand larger than 4 GiB");  // buffer descriptors address 4 GiB per operand
+  p.pf = take_prefetch();
+  const bool gate = p.epi == FLUXMI_EPI_GATE_RESID;
+  switch (c->bm) {  // (the table's restriction was checked above: the lower tiles exist for these instantiations only)
+    case 192:
+      if (is_fp8) return launch_w1<true, FLUXMI_FMT_E5M2, FLUXMI_EPI_GATE_RESID, 3>(p, s);
+      if (gate) return launch_w1<false, FLUXMI_FMT_E5M2, FLUXMI_EPI_GATE_RESID, 3>(p, s);
+      return launch_w1<false, FLUXMI_FMT_E5M2, FLUXMI_EPI_BF16, 3>(p, s);
+    case 224: return launch_w1<true, FLUXMI_FMT_E5M2, FLUXMI_EPI_GATE_RESID, 7, 1>(p, s);
+    case 160: return launch_w1<true, FLUXMI_FMT_E5M2, FLUXMI_EPI_GATE_RESID, 5, 1>(p, s);
+    default: break;
   }
-  p.pf = fluxmi_take_prefetch();
-  if (!fluxmi_tuning().prefetch) p.pf.n = 0;
-  return launch_w1<true, FLUXMI_FMT_E5M2, FLUXMI_EPI_GATE_RESID, 7, 1>(p, s);
-}
-// config 21 = the same wave layout on 160 x 256 tiles (wave tile 160 x 64): Flux-dev 768^2 mlp.2 / linear2 (M = 2816: 18 x 12 = 216 tiles of 5/8 of the
-// work instead of config 17's 180 tiles of 6/8)
-int fluxmi_launch_gemm_w1_160(FluxmiGemmParams& p, int is_fp8, int act_fmt, hipStream_t s) {
-  FLUXMI_REQUIRE(is_fp8 && act_fmt == FLUXMI_FMT_E5M2 && p.epi == FLUXMI_EPI_GATE_RESID,
-                 "gemm tile config 21 (160x256 one-wave-per-SIMD tiles): fp8 x e5m2 operands with the gate*y+x epilogue (fp8 %d, epi %d)", is_fp8, p.epi);
-  for (int i = 0; i < p.n_groups; ++i) {
-    FLUXMI_REQUIRE(!p.g[i].vt_out && !p.g[i].k_out, "gemm tile config 21: no fused K / V^T outputs");
-    FLUXMI_REQUIRE((long long)p.g[i].M * p.g[i].lda < (1LL << 32) && (long long)p.N * p.K < (1LL << 32), "gemm_w1: operand larger than 4 GiB");
-  }
-  p.pf = fluxmi_take_prefetch();
-  if (!fluxmi_tuning().prefetch) p.pf.n = 0;
-  return launch_w1<true, FLUXMI_FMT_E5M2, FLUXMI_EPI_GATE_RESID, 5, 1>(p, s);
-}
-
-// config 16 = 256x256, one wave per SIMD
-int fluxmi_launch_gemm_w1(FluxmiGemmParams& p, int is_fp8, int act_fmt, hipStream_t s) {
-  p.pf = fluxmi_take_prefetch();
-  if (!fluxmi_tuning().prefetch) p.pf.n = 0;
-  // buffer descriptors address 4 GiB per operand
-  for (int i = 0; i < p.n_groups; ++i)
-    FLUXMI_REQUIRE((long long)p.g[i].M * p.g[i].lda * (is_fp8 ? 1 : 2) < (1LL << 32) && (long long)p.N * p.K * (is_fp8 ? 1 : 2) < (1LL << 32),
-                   "gemm_w1: operand larger than 4 GiB");
   if (is_fp8) {
     if (act_fmt == FLUXMI_FMT_E5M2) {
       // the step's K >= 8192 launches (mlp.2, linear2) all end in gate*y + x
       const int esel = fluxmi_tuning().gemm_esel;  // 0: the run-time-switch kernel for every epilogue (A/B)
-      if (esel && p.epi == FLUXMI_EPI_GATE_RESID) return launch_w1<true, FLUXMI_FMT_E5M2, FLUXMI_EPI_GATE_RESID>(p, s);
+      if (esel && gate) return launch_w1<true, FLUXMI_FMT_E5M2, FLUXMI_EPI_GATE_RESID>(p, s);
       return launch_w1<true, FLUXMI_FMT_E5M2>(p, s);
     }
     return launch_w1<true, FLUXMI_FMT_E4M3>(p, s);
   }
   if (act_fmt == FLUXMI_FMT_E5M2) {  // bf16 operands (VAE convolutions, text encoders, bf16 flow): plain and residual epilogues specialised
-    if (p.epi == FLUXMI_EPI_GATE_RESID) return launch_w1<false, FLUXMI_FMT_E5M2, FLUXMI_EPI_GATE_RESID>(p, s);
+    if (gate) return launch_w1<false, FLUXMI_FMT_E5M2, FLUXMI_EPI_GATE_RESID>(p, s);
     if (p.epi == FLUXMI_EPI_BF16) return launch_w1<false, FLUXMI_FMT_E5M2, FLUXMI_EPI_BF16>(p, s);
     return launch_w1<false, FLUXMI_FMT_E5M2>(p, s);
   }

@@ -13,6 +13,7 @@
 #include <mutex>
 
 #include "fluxmi_internal.h"
+#include "gemm_cfg.h"
 
 namespace {
 
@@ -28,9 +29,9 @@ int env_int(const char* name, int dflt) {
 
 int validate(const fluxmi_tuning_t& t) {
   FLUXMI_REQUIRE(t.struct_size == (int)sizeof(fluxmi_tuning_t), "tuning: struct_size %d != %d (ABI mismatch)", t.struct_size, (int)sizeof(fluxmi_tuning_t));
-  // -1 (cost model) or a tile config the launchers know (fluxmi_gemm_tile_bn: 2, 13, 15..21); tests/knob_contract.py lists them with what each
+  // -1 (cost model) or a tile config of the table (gemm_cfg.h); tests/knob_contract.py lists them with what each
   // promises, and the CPU suite checks that this function accepts exactly those
-  FLUXMI_REQUIRE(t.gemm_cfg == -1 || (t.gemm_cfg >= 0 && fluxmi_gemm_tile_bn(t.gemm_cfg) != 0), "tuning: gemm_cfg %d is neither -1 nor a tile config", t.gemm_cfg);
+  FLUXMI_REQUIRE(t.gemm_cfg == -1 || gemm_cfg(t.gemm_cfg), "tuning: gemm_cfg %d is neither -1 nor a tile config", t.gemm_cfg);
   // P is bounded by 2^defer_log2, O and l carry the same factor: beyond 2^16 the fp32 sums of 4608 keys lose their headroom, and a
   // negative or non-finite threshold makes the rescale test meaningless (inf / NaN images with no error otherwise)
   FLUXMI_REQUIRE(isfinite(t.attn_defer_log2) && t.attn_defer_log2 >= 0.f && t.attn_defer_log2 <= 16.f,
@@ -86,7 +87,7 @@ void init_from_env() {
     if (!(isfinite(t.attn_defer_log2) && t.attn_defer_log2 >= 0.f && t.attn_defer_log2 <= 16.f)) t.attn_defer_log2 = 8.0f;
     if (t.fuse_kv < 0 || t.fuse_kv > 2) t.fuse_kv = 2;
     if (t.ln_variant < 1 || t.ln_variant > 3) t.ln_variant = 2;
-    if (t.gemm_cfg != -1 && (t.gemm_cfg < 0 || fluxmi_gemm_tile_bn(t.gemm_cfg) == 0)) t.gemm_cfg = -1;
+    if (t.gemm_cfg != -1 && !gemm_cfg(t.gemm_cfg)) t.gemm_cfg = -1;
     auto fix = [](int& v, int lo, int hi, int dflt) { if (v < lo || v > hi) v = dflt; };
     fix(t.gemm_splitk, 0, 1, 1); fix(t.gemm_hybrid, 0, 1, 1); fix(t.gemm_esel, 0, 1, 1); fix(t.gemm_persist, 0, 2, 1);
     fix(t.attn_var, 0, 3, 0); fix(t.attn_abl, 0, 15, 0); fix(t.attn_f16k, 0, 1, 1); fix(t.qlut, 0, 1, 1); fix(t.roctx, 0, 1, 0);

@@ -68,6 +68,7 @@ _SIGS = {
     "fluxmi_gemm_debug_buffer": ([vp], i32),
     "fluxmi_clock_sample": ([vp, vp], i32),
     "fluxmi_gemm_grouped": ([C.POINTER(GemmGroup), i32, i32, i32, i32, i32, i32, i32, vp], i32),
+    "fluxmi_gemm_plan": ([C.POINTER(GemmGroup), i32, i32, i32, i32, i32, i32, i32, C.POINTER(i32), i32, C.POINTER(i32)], i32),
     "fluxmi_f8_gemm": ([vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp], i32),
     "fluxmi_gemv": ([vp, i64, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, vp], i32),
     "fluxmi_quantize_act": ([vp, vp, vp, i32, i32, i64, i64, i32, vp], i32),

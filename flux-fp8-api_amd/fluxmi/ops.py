@@ -120,6 +120,22 @@ def gemm_grouped(groups: Sequence[GemmGroup], N: int, K: int, is_fp8: bool, act_
     call("fluxmi_gemm_grouped", arr, len(groups), N, K, int(is_fp8), act_fmt, epilogue, tile_cfg, _stream())
 
 
+def gemm_plan(groups: Sequence[GemmGroup], N: int, K: int, is_fp8: bool, act_fmt: int, epilogue: int, batch: int = 1):
+    """fluxmi_gemm_plan: the launches gemm_grouped(tile_cfg=-1) would issue for these groups under the current tuning, as a list of dicts
+    with kind ("tile", "generic", "splitk"), cfg (tile config or -1), S (split-K slices or 0) and groups (indices into `groups`, in
+    launch order).  Host arithmetic only -- works without a GPU, the groups' pointers are never followed."""
+    arr = (GemmGroup * len(groups))(*groups)
+    cap = 5 * len(groups)
+    raw, n = (C.c_int * cap)(), C.c_int()
+    call("fluxmi_gemm_plan", arr, len(groups), N, K, int(is_fp8), act_fmt, epilogue, batch, raw, cap, C.byref(n))
+    v, i, launches = list(raw[: n.value]), 0, []
+    while i < len(v):
+        kind, cfg, S, ng = v[i:i + 4]
+        launches.append(dict(kind=("tile", "generic", "splitk")[kind], cfg=cfg, S=S, groups=v[i + 4:i + 4 + ng]))
+        i += 4 + ng
+    return launches
+
+
 def pair_rows(w: torch.Tensor) -> torch.Tensor:
     """[R, C] (1-byte or 2-byte elements, row bytes % 64 == 0, R even) -> the same bytes in the row-pair layout [R/2][row_bytes/64][2][64]
     (fluxmi_gemm_group_t.W_pairs), as a tensor of w's shape and dtype."""

@@ -199,7 +199,18 @@ int fluxmi_clock_sample(void* out24_dev_u64, void* stream);
  * blocks the choice) or set fluxmi_tuning_t.gemm_splitk = 0. */
 int fluxmi_gemm_grouped(const fluxmi_gemm_group_t* groups, int n_groups, int N, int K, int is_fp8, int act_fmt,
                         int epilogue, int tile_cfg, void* stream);
-/* single-problem convenience form of the above (F8Linear.forward after quantisation) */
+/* The launches fluxmi_gemm_grouped(tile_cfg = -1) would issue for these groups under the process-wide tuning, WITHOUT issuing them: host
+ * arithmetic only, works without a GPU (added within ABI 5: no struct or existing entry point changed).  Of a group it reads M, the layout
+ * fields and whether its pointers are NULL, never through them; any n_groups >= 1 (launches carry at most 16 groups each).  `batch`: what an
+ * engine would announce for its bf16 launches (1 = none): the decisions of ONE sample's share of the groups are replayed on all of them.
+ * plan[0 .. *plan_len) receives one record per launch, in launch order:
+ *     kind, cfg, S, n, g_0 .. g_(n-1)
+ * kind 0 = tile config `cfg` (csrc/gemm_cfg.h), 1 = the generic kernel (cfg = -1), 2 = split-K with S slices on 256x256 tiles (cfg = -1);
+ * S = 0 unless kind 2; g_i = indices into `groups`, in the order the launch carries them.  Every group appears in exactly one record.
+ * When plan_cap is too small the call fails with *plan_len set to the length needed (n_groups + 4 x launches <= 5 x n_groups). */
+int fluxmi_gemm_plan(const fluxmi_gemm_group_t* groups, int n_groups, int N, int K, int is_fp8, int act_fmt, int epilogue, int batch,
+                     int* plan, int plan_cap, int* plan_len);
+/* single-problem convenience form of fluxmi_gemm_grouped (F8Linear.forward after quantisation) */
 int fluxmi_f8_gemm(const void* a_fp8, const void* w_e4m3, const float* sa_recip, const float* sb_recip, const void* bias,
                    void* out, int M, int N, int K, int act_fmt, int epilogue, const void* gate, const void* resid,
                    const float* q_scale, int tile_cfg, void* stream);

@@ -4,8 +4,9 @@ this pool (boxes differ by 5 %, and an isolated probe loop flatters a kernel: DE
     python tools/ab_step.py --variant base: --variant nosplit:attn_split=0 [--variant name:knob=v,knob=v ...] [--steps 20] [--rounds 3]
                             [--height 1024 --width 1024] [--batch 1] [--check]
 Prints ms/step per variant and round, the median, the sustained shader clock, and (--check) whether the latents of every variant are
-bit-identical to the first variant's."""
+bit-identical to the first variant's, with a sha256 of the first variant's latents (to compare two libraries: one process each, FLUXMI_LIB)."""
 import argparse
+import hashlib
 import os
 import sys
 import time
@@ -77,6 +78,8 @@ def main():
                 if r == 0:
                     lat[name] = out.clone()
         base = variants[0][0]
+        if a.check:  # a fingerprint to compare across processes (another library through FLUXMI_LIB)
+            print(f"latents sha256 ({base}): {hashlib.sha256(lat[base].cpu().view(torch.int16).numpy().tobytes()).hexdigest()}", flush=True)
         for name, knobs in variants:
             v = sorted(res[name])
             med = v[len(v) // 2]

@@ -7,7 +7,9 @@ Same two POST endpoints, request fields, defaults and status codes:
              redux_image=None (FLUX.1 Redux image prompt) -- path or base64, each passed on only when set;
              negative_prompt=None, true_cfg_scale=None, true_cfg_interval=None ([lo, hi]) -- true classifier-free guidance
              (FluxPipeline.generate), each passed on only when set;
-             cache_threshold=None, cache_max_hits=None -- first-block step caching (FluxPipeline.generate), each passed on only when set}
+             cache_threshold=None, cache_max_hits=None -- first-block step caching (FluxPipeline.generate), each passed on only when set;
+             regions=None ([{prompt, box=[x0, y0, x1, y1] | mask}], regional prompts), regional_tokens=None -- each passed on only when
+             set; a region with both or neither of box / mask, or a box outside 0 <= x0 < x1 <= 1, is a 422}
              ->  image/jpeg stream of FluxPipeline.generate(**args)                                               (reference api.py:54-86)
   /lora      LoraArgs{scale=1.0, path, name, action="load"|"unload"}  ->  {"status": "success"} | 400 invalid action | 500 with the
              exception text; unload uses `name` when given, else `path`                                         (reference api.py:89-122)
@@ -17,7 +19,7 @@ engine access with its own lock (modules/flux_model.py), so concurrent requests 
 from __future__ import annotations
 
 import random
-from typing import Literal, Optional, Tuple
+from typing import List, Literal, Optional, Tuple
 
 from fastapi import FastAPI
 from fastapi.responses import JSONResponse, StreamingResponse
@@ -38,6 +40,13 @@ class LoraLoadResponse(BaseModel):
     message: Optional[str] = None
 
 
+class RegionArgs(BaseModel):
+    """one regional prompt: `prompt` holds inside `box` (x0, y0, x1, y1 in 0..1 of the image) or inside the white part of `mask` (path or base64)"""
+    prompt: str
+    box: Optional[Tuple[float, float, float, float]] = None
+    mask: Optional[str] = None
+
+
 class GenerateArgs(BaseModel):
     prompt: str
     width: Optional[int] = Field(default=720)
@@ -56,6 +65,8 @@ class GenerateArgs(BaseModel):
     true_cfg_interval: Optional[Tuple[float, float]] = None  # [lo, hi], fractions of the steps that are guided (default: all)
     cache_threshold: Optional[float] = None  # first-block step caching: relative-L1 threshold of the first block's residual (off unless > 0)
     cache_max_hits: Optional[int] = None  # ... and the most cached steps in a row (0 = no bound)
+    regions: Optional[List[RegionArgs]] = Field(default=None, min_length=1)  # regional prompts (FluxPipeline.generate)
+    regional_tokens: Optional[int] = Field(default=None, gt=0, multiple_of=16)  # T5 rows kept per region prompt (default 128)
 
 
 app = FastAPI(title="fluxmi")
@@ -69,9 +80,22 @@ def generate(args: GenerateArgs):
     select true classifier-free guidance, `cache_threshold` (+ `cache_max_hits`) first-block step caching.  Without them the call is exactly the reference's."""
     kwargs = args.model_dump()
     for k in ("reference_image", "mask_image", "control_image", "redux_image", "negative_prompt", "true_cfg_scale", "true_cfg_interval",
-              "cache_threshold", "cache_max_hits"):
+              "cache_threshold", "cache_max_hits", "regions", "regional_tokens"):
         if kwargs.get(k) is None:
             kwargs.pop(k, None)
+    if "regions" in kwargs:
+        regs = []
+        for r in kwargs["regions"]:
+            if (r.get("box") is None) == (r.get("mask") is None):
+                return JSONResponse(status_code=422, content={"status": "error", "message": "a region takes exactly one of box and mask"})
+            if r.get("box") is not None:
+                x0, y0, x1, y1 = r["box"]
+                if not (0.0 <= x0 < x1 <= 1.0 and 0.0 <= y0 < y1 <= 1.0):
+                    return JSONResponse(status_code=422, content={"status": "error", "message": "a region box needs 0 <= x0 < x1 <= 1 and 0 <= y0 < y1 <= 1"})
+                regs.append({"prompt": r["prompt"], "box": tuple(r["box"])})
+            else:
+                regs.append({"prompt": r["prompt"], "mask": r["mask"]})
+        kwargs["regions"] = regs
     result = app.state.model.generate(**kwargs)
     return StreamingResponse(result, media_type="image/jpeg")
 

@@ -9,12 +9,13 @@
 //  * the P^T operand of O^T += V^T . P^T is the S^T accumulator itself, converted to bf16 in place: the k-slot <-> key mapping that
 //    results (key = (e & 3) + 8 (e >> 2) + 4 hi inside each 16-key group) is pre-applied to V by qkv_rope.hip, so no cross-lane traffic
 //    and no transpose read is needed;
-//  * online softmax in the exp2 domain with a deferred running max, fp32 accumulators, P rounded to bf16 for the PV MFMA.
+//  * online softmax in the exp2 domain with a deferred running max, fp32 accumulators, P rounded to bf16 for the PV MFMA;
+//  * `groups` (fluxmi_attention_grouped): a per-token descriptor table restricts who attends to whom; the MASKED instantiations.
 #include "attention_common.h"
 
 int fluxmi_k_attention(const void* Q, const void* K, const void* VT, void* out, long long ld_out, int col_off, int out_fp8,
                        const float* q_scale0, const float* q_scale1, int split, int B, int L, int Lp, int H, int fmt,
-                       hipStream_t s, const void* qraw, long long ldq, const void* pe, const void* qn0, const void* qn1, int k_f16, int out_pairs) {
+                       hipStream_t s, const void* qraw, long long ldq, const void* pe, const void* qn0, const void* qn1, int k_f16, int out_pairs, const void* groups) {
   FLUXMI_REQUIRE(Q || (qraw && pe && qn0 && qn1 && ldq % 8 == 0), "attention: need Q, or raw q + pe + both q-norm scales (ld %% 8 == 0)");
   FLUXMI_REQUIRE(Lp % 64 == 0 && Lp >= L, "attention: Lp=%d must be a multiple of 64 and >= L=%d", Lp, L);
   FLUXMI_REQUIRE(!out_fp8 || (q_scale0 && q_scale1), "attention: fp8 output needs q_scale pointers");
@@ -31,6 +32,7 @@ int fluxmi_k_attention(const void* Q, const void* K, const void* VT, void* out, 
   a.scale_log2 = 0.08838834764831845f * 1.4426950408889634f;  // 128^-0.5 * log2(e)
   a.k_f16 = k_f16;
   a.dbg = nullptr;
+  a.groups = (const unsigned*)groups;
   const fluxmi_tuning_t tun = fluxmi_tuning();
   a.pf = fluxmi_take_prefetch();
   if (!tun.prefetch) a.pf.n = 0;

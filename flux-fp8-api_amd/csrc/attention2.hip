@@ -66,7 +66,19 @@ constexpr int VRING2 = RD2 * K_BYTES;
 // MFMAs (with the barrier in front, all eight waves leave it in lockstep and both waves of every SIMD wait out the LDS latency of their
 // first fragments with the matrix pipe idle).  Refill order K0 K1 K2 V0 K3 | step j: V_{j+1} (QK^T half), K_{j+4} (PV half, behind
 // the barrier of step j, where K_j is dead); the barrier of step j waits for K_{j+2} and V_j (two younger groups stay in flight).
-template <int FMT, bool FOLD, bool EXACT, bool MIDBAR = false>
+// MASKED (token-group masks, AttnArgs.groups): the mask rides on the MATRIX pipe.  Per 32-key half of a tile one more QK^T MFMA whose
+// K-side fragment is the one-hot code of the keys' groups (k = group) and whose Q-side fragment holds, per group, 0 where the row admits it
+// and -32768 where it does not (exact in fp16 and bf16): an admitted score receives +0 in the fp32 accumulator and keeps its bits -- a table
+// that admits everything gives the dense result bit for bit -- and a masked one drops to exp2(..) = 0.  No VALU work and no branch enter
+// the step's softmax: both sides are staged in the LDS the rings leave free.  The prologue builds the Q-side fragment of every lane once
+// (16 B per thread) and writes, per key of the sample, the byte offset of its fragment in a 16-entry table (one-hot halves 0..7, then
+// zeros; one byte array per lane half, since the upper lanes hold k = 8..15); a step reads two bytes and three 16-byte fragments per lane.
+// The running max of a MASKED row starts from a FLOOR (-1024 in the exp2 domain) instead of from tile 0's maximum: a row whose first tiles
+// are all masked then carries the state (O, l) = 0 rather than weights relative to a maximum near -32768, and -- what decides it -- the
+// folded kernel's accumulator init -M stays small: with M ~ -32768 the first admitted tile would be summed on a 2^-8 grid (fp32 ulp at
+// 2^15) and its weights carry ~1 % error; at 1024 the grid is 2^-13.  The price: a row whose admitted scores ALL lie below
+// -1024 + 126 (exp2 domain; |q . k| / sqrt(128) ~ 620) has l = 0.  QK-normed operands are two orders of magnitude away from that.
+template <int FMT, bool FOLD, bool EXACT, bool MIDBAR = false, bool MASKED = false>
 __global__ void __launch_bounds__(NW2 * 64, 2) attention2_kernel(const AttnArgs a) {
   constexpr int QB = NW2 * 32;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -123,6 +135,45 @@ __global__ void __launch_bounds__(NW2 * 64, 2) attention2_kernel(const AttnArgs 
     else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfr, qfr, acc, 0, 0, 0);
   };
 
+  // MASKED: permission fragment of this lane's query row, key-side staging (see the head of the kernel)
+  constexpr int M_LUT = 4 * A_STAGE, M_QM = M_LUT + 256, M_IDX = M_QM + NW2 * 64 * 16;
+  constexpr float M_FLOOR = -1024.f;  // exp2 domain
+  v8bf qmask;
+  unsigned midx = 0;
+  if constexpr (MASKED) {
+    const unsigned* gt = a.groups + (long long)b * a.L;
+    const int nk_pad = (ntiles_all + 1) * KT;  // the last step's S_{j+1} reads one tile past the end
+    for (int key = tid; key < nk_pad; key += NW2 * 64) {
+      const unsigned g = key < a.L ? (gt[key] & 15u) : 8u;  // keys past the end: a zero fragment in both halves (mask_tile removes them)
+      smem[M_IDX + key] = (unsigned char)(g << 4);
+      smem[M_IDX + nk_pad + key] = (unsigned char)(key < a.L ? ((g ^ 8u) << 4) : 0x80u);
+    }
+    if (tid < 16) {
+      const unsigned one = FOLD ? 0x3C00u : 0x3F80u;
+      uint4 e = {0u, 0u, 0u, 0u};
+      const unsigned w = one << (16 * (tid & 1));
+      if (tid < 8) { if ((tid >> 1) == 0) e.x = w; else if ((tid >> 1) == 1) e.y = w; else if ((tid >> 1) == 2) e.z = w; else e.w = w; }
+      *(uint4*)(smem + M_LUT + tid * 16) = e;
+    }
+    const unsigned perm = (gt[qld] >> 16) >> (hi * 8);
+    const unsigned neg = FOLD ? 0xF800u : 0xC700u;  // -32768
+    uint4 qm;
+    qm.x = ((perm & 1u) ? 0u : neg) | ((perm & 2u) ? 0u : neg << 16);
+    qm.y = ((perm & 4u) ? 0u : neg) | ((perm & 8u) ? 0u : neg << 16);
+    qm.z = ((perm & 16u) ? 0u : neg) | ((perm & 32u) ? 0u : neg << 16);
+    qm.w = ((perm & 64u) ? 0u : neg) | ((perm & 128u) ? 0u : neg << 16);
+    qmask = __builtin_bit_cast(v8bf, qm);
+    *(uint4*)(smem + M_QM + tid * 16) = qm;
+    midx = (unsigned)(M_IDX + hi * nk_pad + l31 + tb * KT);
+  }
+  // the two table offsets of this lane's keys in tile `t_rel` of the piece, and the mask MFMAs on the tile's two accumulators
+  auto mask_off = [&](int t_rel, unsigned (&mo)[2]) {
+    mo[0] = smem[midx + t_rel * KT];
+    mo[1] = smem[midx + t_rel * KT + 32];
+  };
+  auto mask_frag = [&](unsigned off) -> v8bf { return *(const v8bf*)(smem + M_LUT + off); };
+  auto mask_q = [&]() -> v8bf { return *(const v8bf*)(smem + M_QM + tid * 16); };
+
   const auto krsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(a.K + bh * a.L * 128), 0, a.L * 256, 0x00020000);
   const auto vrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(a.VT + bh * 128 * a.Lp), 0, 128 * a.Lp * 2, 0x00020000);
   unsigned k_off[LPW2], v_off[LPW2];
@@ -141,7 +192,7 @@ __global__ void __launch_bounds__(NW2 * 64, 2) attention2_kernel(const AttnArgs 
   for (int i = 0; i < 4; ++i)
 #pragma unroll
     for (int r = 0; r < 16; ++r) o[i][r] = 0.f;
-  float m_run = -1e30f;
+  float m_run = MASKED ? M_FLOOR / a.scale_log2 : -1e30f;  // MASKED: the floor in the raw-score domain
   float l4[4] = {0.f, 0.f, 0.f, 0.f};
   // FOLD: M = deferred running max in the exp2 domain; ninit = sixteen copies of -M, the C operand of the first QK^T MFMAs
   float m_cur = 0.f;
@@ -190,6 +241,7 @@ __global__ void __launch_bounds__(NW2 * 64, 2) attention2_kernel(const AttnArgs 
   }
   if constexpr (MIDBAR) wait_vm<3 * LPW2>();  // K0 and K1 (step 0 reads K1 before its barrier)
   else wait_vm<5 * LPW2>();
+  if constexpr (MASKED) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the staging writes above
   __builtin_amdgcn_s_barrier();
   stamp(5);
   v16f sa[2], sb[2];
@@ -208,6 +260,12 @@ __global__ void __launch_bounds__(NW2 * 64, 2) attention2_kernel(const AttnArgs 
       sa[0] = mfma_qk(k_frag(0, cc, 0), qf[cc], sa[0]);
       sa[1] = mfma_qk(k_frag(0, cc, 1), qf[cc], sa[1]);
     }
+    if constexpr (MASKED) {
+      unsigned mo[2];
+      mask_off(0, mo);
+      sa[0] = mfma_qk(mask_frag(mo[0]), qmask, sa[0]);
+      sa[1] = mfma_qk(mask_frag(mo[1]), qmask, sa[1]);
+    }
   }
   if (ragged && ntiles == 1) {
     asm volatile("" ::: "memory");
@@ -223,7 +281,7 @@ __global__ void __launch_bounds__(NW2 * 64, 2) attention2_kernel(const AttnArgs 
     mx = finish_max(m0);
   }
   if constexpr (FOLD) {  // M = exact max of tile 0; S_0 -> S_0 - M; nothing to rescale in step 0
-    m_cur = mx;
+    m_cur = MASKED ? fmaxf(mx, M_FLOOR) : mx;
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -384,12 +442,45 @@ __global__ void __launch_bounds__(NW2 * 64, 2) attention2_kernel(const AttnArgs 
     };
     // -- C: O^T += V_{j-1}^T P_{j-1}^T, four independent accumulators; V fragments two ahead; the other 16 scores of P_j and the
     //       row max of S_{j+1} (two scores per gap, v_max3)
-    float m0 = nxt[0][0];
+    // MASKED: the two mask MFMAs of S_{j+1} ride in the first PV gaps (the softmax of P_j has freed registers by then; the QK^T half has
+    // none to spare: behind the sixteen QK^T MFMAs they cost 11 spill reloads per four tiles, each with an s_waitcnt vmcnt(0) that drains
+    // the DMA rings): table offsets in gap MK_O, fragments in gaps MK_L / MK_L + 1, MFMAs behind gaps MK_M / MK_M + 1; the row max of
+    // S_{j+1} then takes four scores per gap in gaps 8..15 instead of two in every gap.  The permission fragment is re-read from LDS
+    // per tile (four registers held across the step spill three more values)
+    constexpr int MK_O = 0, MK_L = 2, MK_M = 4;
+    unsigned mo[2];
+    v8bf mf[2], mq;
+    auto mask_gap = [&](auto SC) {
+      constexpr int s = decltype(SC)::value;
+      if constexpr (MASKED) {
+        if constexpr (s == MK_O) mask_off(j + 1, mo);
+        if constexpr (s == MK_L) { mf[0] = mask_frag(mo[0]); mq = mask_q(); }
+        if constexpr (s == MK_L + 1) mf[1] = mask_frag(mo[1]);
+      }
+    };
+    auto mask_mfma = [&](auto SC) {
+      constexpr int s = decltype(SC)::value;
+      if constexpr (MASKED && (s == MK_M || s == MK_M + 1)) {
+        nxt[s - MK_M] = mfma_qk(mf[s - MK_M], mq, nxt[s - MK_M]);
+        fence();
+      }
+    };
+    float m0 = MASKED ? -3.0e38f : nxt[0][0];
     auto rmax = [&](auto SC) {  // two scores of S_{j+1} per gap (v_max3), pinned like the softmax work
       constexpr int s = decltype(SC)::value;
-      asm volatile("" : "+v"(m0));
-      m0 = fmaxf(fmaxf(m0, nxt[s >> 3][(2 * s) & 15]), nxt[s >> 3][((2 * s) & 15) + 1]);
-      asm volatile("" : "+v"(m0));
+      if constexpr (MASKED) {
+        if constexpr (s >= 8) {
+          constexpr int e = (s - 8) * 4, t = e >> 4, r = e & 15;
+          asm volatile("" : "+v"(m0));
+          m0 = fmaxf(fmaxf(m0, nxt[t][r]), nxt[t][r + 1]);
+          m0 = fmaxf(fmaxf(m0, nxt[t][r + 2]), nxt[t][r + 3]);
+          asm volatile("" : "+v"(m0));
+        }
+      } else {
+        asm volatile("" : "+v"(m0));
+        m0 = fmaxf(fmaxf(m0, nxt[s >> 3][(2 * s) & 15]), nxt[s >> 3][((2 * s) & 15) + 1]);
+        asm volatile("" : "+v"(m0));
+      }
     };
     if constexpr (!FIRST) {
       // V fragments VPF MFMAs ahead (PMC of the 2-ahead version: the waves sat a third of their cycles in s_waitcnt / s_barrier)
@@ -403,17 +494,21 @@ __global__ void __launch_bounds__(NW2 * 64, 2) attention2_kernel(const AttnArgs 
         o[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[s % (VPF + 1)], __builtin_bit_cast(v8bf, pp[ch4]), o[db], 0, 0, 0);
         fence();
         if constexpr (s + VPF < 16) vf[(s + VPF) % (VPF + 1)] = v_frag(VS, (s + VPF) >> 2, (s + VPF) & 3);
+        mask_gap(SC);
         gapwork(std::integral_constant<int, 16 + s>{});
         rmax(SC);
         midbar_pv_gap(SC);
         fence();
+        mask_mfma(SC);
       });
     } else {
       static_for<16>([&](auto SC) {
         constexpr int s = decltype(SC)::value;
+        mask_gap(SC);
         gapwork(std::integral_constant<int, 16 + s>{});
         rmax(SC);
         midbar_pv_gap(SC);
+        mask_mfma(SC);
       });
     }
     mx = m0;
@@ -692,23 +787,26 @@ int fluxmi_attn_plan_export(int B, int L, int H, int* n_per_x, int* full_per_x, 
   return sp.thin ? 1 : 2;
 }
 
-template <bool FOLD, bool EXACT, bool MIDBAR = false> static int launch2(AttnArgs a, int fmt, hipStream_t s) {
+template <bool FOLD, bool EXACT, bool MIDBAR = false, bool MASKED = false> static int launch2(AttnArgs a, int fmt, hipStream_t s) {
   static bool attr = false;
   if (!attr) {
-    FLUXMI_CHECK_HIP(hipFuncSetAttribute((const void*)attention2_kernel<FLUXMI_FMT_E5M2, FOLD, EXACT, MIDBAR>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * A_STAGE));
-    FLUXMI_CHECK_HIP(hipFuncSetAttribute((const void*)attention2_kernel<FLUXMI_FMT_E4M3, FOLD, EXACT, MIDBAR>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * A_STAGE));
+    const int lds_max = MASKED ? ATTN_LDS_MAX : 4 * A_STAGE;
+    FLUXMI_CHECK_HIP(hipFuncSetAttribute((const void*)attention2_kernel<FLUXMI_FMT_E5M2, FOLD, EXACT, MIDBAR, MASKED>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
+    FLUXMI_CHECK_HIP(hipFuncSetAttribute((const void*)attention2_kernel<FLUXMI_FMT_E4M3, FOLD, EXACT, MIDBAR, MASKED>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
     attr = true;
   }
+  const int lds = 4 * A_STAGE + (MASKED ? attn_mask_lds_bytes(a.L) : 0);
   memset(&a.sp, 0, sizeof(a.sp));
   a.dbg = g_attn_dbg;
   const int tasks1 = ((a.L + 255) / 256) * a.H;  // of one sample
   const fluxmi_tuning_t tun = fluxmi_tuning();
   auto launch = [&](const AttnArgs& aa, int wgs) {
     const dim3 grid(wgs);
-    if (fmt == FLUXMI_FMT_E5M2) hipLaunchKernelGGL((attention2_kernel<FLUXMI_FMT_E5M2, FOLD, EXACT, MIDBAR>), grid, dim3(512), 4 * A_STAGE, s, aa);
-    else hipLaunchKernelGGL((attention2_kernel<FLUXMI_FMT_E4M3, FOLD, EXACT, MIDBAR>), grid, dim3(512), 4 * A_STAGE, s, aa);
+    if (fmt == FLUXMI_FMT_E5M2) hipLaunchKernelGGL((attention2_kernel<FLUXMI_FMT_E5M2, FOLD, EXACT, MIDBAR, MASKED>), grid, dim3(512), lds, s, aa);
+    else hipLaunchKernelGGL((attention2_kernel<FLUXMI_FMT_E4M3, FOLD, EXACT, MIDBAR, MASKED>), grid, dim3(512), lds, s, aa);
   };
-  if (FOLD && tun.attn_split && fluxmi_xcd_mapping_ok(s) == 1) {
+  // MASKED launches take no plan: one workgroup per task under every attn_split (the balanced grid's scratch and merge stay dense-only)
+  if (FOLD && !MASKED && tun.attn_split && fluxmi_xcd_mapping_ok(s) == 1) {
     AttnSplit sp = fluxmi_attn_plan(tasks1, (a.L + KT - 1) / KT, 256);  // per SAMPLE: see fluxmi_attn_plan_any
     // attn_split = 1: only THIN last rounds (at most 8 of an XCD's 32 CUs busy, folded into the round in front of them; or a single partial
     // round).  Fuller ones were measured not to pay on this chip -- Flux-dev 1024^2, 22 of 32: 236 vs 223 - 235 us isolated, +3.4 % per
@@ -747,6 +845,14 @@ template <bool FOLD, bool EXACT, bool MIDBAR = false> static int launch2(AttnArg
 // MFMAs of the current one; bit-identical to the barrier-at-step-start build it replaced, -1.6 %), bf16 K -> the unfolded kernel.
 // `exact` (fluxmi_tuning_t.attn_var bit 1) selects exact instead of deferred max tracking (tests).
 int fluxmi_launch_attention2(const AttnArgs& a, int fmt, hipStream_t s, bool exact) {
+  if (a.groups) {
+    // the staging behind the rings: 8448 B + 128 B per (key tile + 1) within ATTN_LDS_MAX -> 189 tiles (include/fluxmi.h states the number)
+    constexpr int MASK_L_MAX = ((ATTN_LDS_MAX - 4 * A_STAGE - 256 - 512 * 16) / 128 - 1) * 64;
+    static_assert(MASK_L_MAX == 12096, "include/fluxmi.h and DESIGN.md document L <= 12096 for masked launches");
+    FLUXMI_REQUIRE(4 * A_STAGE + attn_mask_lds_bytes(a.L) <= ATTN_LDS_MAX, "attention: a token-group mask needs L <= %d (key staging in LDS), got L=%d", MASK_L_MAX, a.L);
+    if (a.k_f16) return exact ? launch2<true, true, true, true>(a, fmt, s) : launch2<true, false, true, true>(a, fmt, s);
+    return exact ? launch2<false, true, false, true>(a, fmt, s) : launch2<false, false, false, true>(a, fmt, s);
+  }
   if (a.k_f16) return exact ? launch2<true, true, true>(a, fmt, s) : launch2<true, false, true>(a, fmt, s);
   return exact ? launch2<false, true>(a, fmt, s) : launch2<false, false>(a, fmt, s);
 }

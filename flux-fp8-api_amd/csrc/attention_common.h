@@ -59,7 +59,14 @@ struct AttnArgs {
   int out_pairs;  // fp8 output rows in the row-pair layout (fluxmi_gemm_group_t.a_pairs: the next F8Linear's A operand; dense rows, even B * L)
   int abl;  // A/B knobs (FLUXMI_ATTN_ABL, read per call): 2 = no barrier in the 8-wave kernel (timing only), 8 = fp8 output through 16 x 4 B
             // stores per lane (also taken when the output rows are not 16-byte aligned)
+  // token-group mask (fluxmi_attention_grouped): [B, L] descriptors, bits 0-3 = key group g of the token, bits 16-31 = the groups its
+  // query admits; query i attends key j iff bit g_j of P_i is set.  null = dense (the instantiations without MASKED)
+  const unsigned* groups;
 };
+// dynamic LDS of a MASKED launch behind the K / V^T rings: a 16-entry table of one-hot key fragments (256 B) and, per half of the MFMA's
+// k range, one byte per key of (tiles + 1) x 64 keys (the byte offset of the key's fragment in that table)
+constexpr int ATTN_LDS_MAX = 160 * 1024;
+inline int attn_mask_lds_bytes(int L) { return 256 + 512 * 16 + 2 * (((L + 63) / 64 + 1) * 64); }
 
 namespace {
 

@@ -49,6 +49,7 @@ struct StepGraphs {
   bool ok = false;      // exec[] is instantiated and replayable
   bool warmed = false;  // one frozen step of this kind, shape and update kind has run eagerly (lazy one-time inits done): the next call may capture at once
   bool cfg = false;     // the update kind (`warmed` and the pieces): guided or plain -- the two never share a graph
+  bool masked = false;  // the attention kind: token-group masked or dense launches are baked into the pieces like the update kernel
   unsigned gen = 0;     // fluxmi_tuning_generation() the pieces were captured under
   void drop() {
     for (hipGraphExec_t& g : exec)
@@ -99,6 +100,10 @@ struct fluxmi_engine {
   bool pairs_skipped = false;      // the copies were wanted and did not fit (ensure_pairs): retried at the next prepare
   unsigned pairs_gen = 0;          // fluxmi_tuning_generation() the copies were built under (fluxmi_tuning_t.w_pairs may have changed)
   float* d_cfg = nullptr;          // true-CFG scale (device scalar, like d_dts: one guided graph serves every scale)
+  // token-group attention mask (fluxmi_engine_set_attn_groups): every attention launch of a forward reads the [B, L] descriptors in the
+  // workspace buffer "attn_groups".  The CONTENTS are device data -- one set of graphs serves every table of a prepared shape -- masked
+  // versus dense is a graph kind (graphs_stale).  Cleared when the workspace is re-allocated: a table belongs to a shape
+  bool masked = false;
   int* d_step0 = nullptr;          // first step of the modulation table (device scalar: the captured graph reads it)
   // the layout each fp8 activation buffer (ACT_A8 .. ACT_CAT8) was last written in: true = row pairs (fused mode, act_pairs), false = plain
   // rows.  Set by the stages that write them (and by a replayed step graph); fluxmi_engine_copy_buffer converts by it
@@ -151,6 +156,9 @@ static u16 host_f2bf(double v) {
 // norm + RoPE behind guarded stores with the pe load inside each guard; the persistent kernel's K path (gemm_persist.hip) prefetches pe,
 // normalises on the accumulators and stores unguarded (profiles/r04_fused_k.txt).
 int fuse_kv_level() { return fluxmi_tuning().fuse_kv; }
+
+// the descriptor table every attention launch of a forward reads, or null (dense)
+const void* attn_groups(E* e) { return e->masked ? buf<void>(e, "attn_groups") : nullptr; }
 
 // fluxmi_tuning_t.attn_f16k (FLUXMI_ATTN_F16K, default 1): K is stored as fp16 (by the relayout kernel or the fused-K GEMM epilogue) and attention runs the
 // folded arithmetic (softmax scale in Q, running max in the accumulator init; include/fluxmi.h, fluxmi_attention).  0 = bf16 K, the unfolded kernel.
@@ -678,11 +686,11 @@ int double_block(E* e, const Ctx& c, int i, int mode, int trial, int s0, int s1,
             set_pf(e, {li_p[0], li_p[1], li_m0[0], li_m0[1], li_m2[0], li_m2[1]}, idle_cus((long long)B * heads * ((L + 255) / 256)));
           else set_pf(e, {li_p[0], li_p[1], li_m0[0], li_m0[1]}, idle_cus((long long)B * heads * ((L + 255) / 256)));
           FLUXMI_TRY(fluxmi_k_attention(nullptr, K, VT, attn8, H, 0, 1, e->lin[li_p[0]].in_scale, e->lin[li_p[1]].in_scale, Lt, B, L, e->Lp,
-                                        heads, e->lin[li_p[0]].in_fmt, s, qkv, 3 * H, pe, ns[2], ns[0], attn_f16k(), ap));
+                                        heads, e->lin[li_p[0]].in_fmt, s, qkv, 3 * H, pe, ns[2], ns[0], attn_f16k(), ap, attn_groups(e)));
           fluxmi_set_prefetch(nullptr);
         } else {
           FLUXMI_TRY(fluxmi_k_attention(nullptr, K, VT, attnbf, H, 0, 0, nullptr, nullptr, Lt, B, L, e->Lp, heads, 0, s, qkv, 3 * H, pe,
-                                        ns[2], ns[0], attn_f16k()));
+                                        ns[2], ns[0], attn_f16k(), 0, attn_groups(e)));
           for (int st = 0; st < 2; ++st)
             FLUXMI_TRY(stage_input(e, li_p[st], calib, trial, attnbf + (long long)roff[st] * H, H, XB, attn8 + (long long)roff[st] * H, H,
                                    XB, B, rows[st], H, s));
@@ -802,7 +810,7 @@ int single_block(E* e, const Ctx& c, int i, int mode, int trial, int s0, int s1,
       if (fluxmi_tuning().prefetch >= 3 && i + 1 < e->d.depth_single) set_pf(e, {l2, SLi(e, i + 1, S_LIN1)}, idle_cus((long long)B * heads * ((L + 255) / 256)));
       else set_pf(e, {l2}, idle_cus((long long)B * heads * ((L + 255) / 256)));
       FLUXMI_TRY(fluxmi_k_attention(nullptr, K, VT, cat8, HC, 0, 1, L2.in_scale, L2.in_scale, L, B, L, e->Lp, heads, L2.in_fmt, s, qkv,
-                                    3 * H, pe, ns[0], ns[0], attn_f16k(), ap));
+                                    3 * H, pe, ns[0], ns[0], attn_f16k(), ap, attn_groups(e)));
       fluxmi_set_prefetch(nullptr);
     }
   } else {
@@ -819,7 +827,7 @@ int single_block(E* e, const Ctx& c, int i, int mode, int trial, int s0, int s1,
     if (on(2)) FLUXMI_TRY(fluxmi_k_qkv_rope(lin1, 3 * H + Hm, pe, ns[0], ns[1], ns[0], ns[1], nullptr, K, VT, B, L, e->Lp, heads, L, attn_f16k(), s));
     if (on(3)) {
       FLUXMI_TRY(fluxmi_k_attention(nullptr, K, VT, catbf, HC, 0, 0, nullptr, nullptr, L, B, L, e->Lp, heads, 0, s, lin1, 3 * H + Hm, pe,
-                                    ns[0], ns[0], attn_f16k()));
+                                    ns[0], ns[0], attn_f16k(), 0, attn_groups(e)));
       FLUXMI_TRY(fluxmi_k_act(lin1 + 3 * H, catbf + H, B * L, Hm, 3 * H + Hm, HC, 0, s));
       FLUXMI_TRY(stage_input(e, l2, calib, trial, catbf, HC, 0, cat8, HC, 0, 1, B * L, HC, s));
     }
@@ -987,6 +995,7 @@ void free_ws(E* e) {
   if (e->ws) { hipFree(e->ws); e->ws = nullptr; }
   e->bufs.clear();
   e->ws_bytes = 0;
+  e->masked = false;
 }
 
 // the step cache's buffers for the prepared shape, made once a cached request arrives (a plain request's workspace stays what it was)
@@ -1201,6 +1210,8 @@ int fluxmi_engine_prepare_cond(fluxmi_engine_t* e, int B, int Li_pred, int Lc, i
         // partial softmax states + arrival counters of attention's balanced grid (attention2.hip, AttnSplit; 69 MB), when this shape uses it.
         // Zeroed with the rest of the workspace below; the kernel leaves the counters at zero.
         {"attn_part", fluxmi_attn_plan_any(B, L, e->d.heads) ? FLUXMI_ATTN_SPLIT_WS_BYTES : 256},
+        // token-group mask descriptors [B, L] (fluxmi_engine_set_attn_groups)
+        {"attn_groups", BL * 4},
     };
     size_t total = 0;
     for (auto& it : items) total += (it.bytes + 255) & ~(size_t)255;
@@ -1273,8 +1284,9 @@ struct Stepper {
 // allocated until the re-capture replaces them (behind its stream synchronisation).
 static void graphs_stale(fluxmi_engine_t* e, StepGraphs& g, bool cfg) {
   if (g.ok && g.gen != fluxmi_tuning_generation()) g.ok = g.warmed = e->qlut_valid = false;
-  if (g.cfg != cfg) g.ok = g.warmed = false;
+  if (g.cfg != cfg || g.masked != e->masked) g.ok = g.warmed = false;  // masked versus dense attention is a kind like guided versus plain
   g.cfg = cfg;
+  g.masked = e->masked;
 }
 
 // Captures pieces[0 .. n) into g.exec[0 .. n) on a private non-blocking stream (the caller has synchronised its own).  The only place that
@@ -1544,6 +1556,31 @@ int fluxmi_engine_denoise(fluxmi_engine_t* e, void* img, const void* txt, const 
 int fluxmi_engine_denoise_cfg(fluxmi_engine_t* e, void* img, const void* txt, const void* y, float guidance, float cfg_scale,
                               const double* timesteps_host, int n_steps, int* trial_index_inout, int use_graph, void* stream) {
   return denoise_impl(e, img, txt, y, guidance, true, cfg_scale, timesteps_host, n_steps, trial_index_inout, use_graph, stream);
+}
+
+// Token-group attention mask of the prepared shape: `table` = [B, L] descriptors on the device (L = Lt + Li: text rows, then image rows, as
+// the joint sequence is laid out), copied into the engine's own buffer; NULL = dense.  Self-admission is checked here on a host copy (one
+// stream synchronisation per call, none per step).
+int fluxmi_engine_set_attn_groups(fluxmi_engine_t* e, const unsigned* table, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  FLUXMI_REQUIRE(e, "engine_set_attn_groups: NULL engine");
+  if (!table) {
+    e->masked = false;
+    return 0;
+  }
+  FLUXMI_REQUIRE(e->ws, "engine_set_attn_groups: call fluxmi_engine_prepare first (the table is [B, L] of the prepared shape)");
+  const size_t n = (size_t)e->B * e->L;
+  std::vector<unsigned> h(n);
+  FLUXMI_CHECK_HIP(hipMemcpyAsync(h.data(), table, n * 4, hipMemcpyDeviceToHost, s));
+  FLUXMI_CHECK_HIP(hipStreamSynchronize(s));
+  for (size_t i = 0; i < n; ++i) {
+    FLUXMI_REQUIRE((h[i] & 0xFFF0u) == 0, "engine_set_attn_groups: descriptor %zu = 0x%08x has bits 4-15 set", i, h[i]);
+    FLUXMI_REQUIRE((h[i] >> (16 + (h[i] & 15u))) & 1u, "engine_set_attn_groups: token %zu (sample %zu, row %zu) does not admit its own key group %u: "
+                   "its softmax row would be empty", i, i / e->L, i % e->L, h[i] & 15u);
+  }
+  FLUXMI_CHECK_HIP(hipMemcpyAsync(buf<unsigned>(e, "attn_groups"), table, n * 4, hipMemcpyDeviceToDevice, s));
+  e->masked = true;
+  return 0;
 }
 
 int fluxmi_engine_set_step_cache(fluxmi_engine_t* e, float threshold, int max_consecutive_hits) {

@@ -192,4 +192,4 @@ int fluxmi_k_qkv_rope(const void* qkv, long long ld, const void* pe, const void*
 int fluxmi_k_attention(const void* Q, const void* K, const void* VT, void* out, long long ld_out, int col_off, int out_fp8,
                        const float* q_scale0, const float* q_scale1, int split, int B, int L, int Lp, int H, int fmt, hipStream_t s,
                        const void* qraw = nullptr, long long ldq = 0, const void* pe = nullptr, const void* qn0 = nullptr,
-                       const void* qn1 = nullptr, int k_f16 = 0, int out_pairs = 0);
+                       const void* qn1 = nullptr, int k_f16 = 0, int out_pairs = 0, const void* groups = nullptr);

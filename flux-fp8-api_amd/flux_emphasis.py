@@ -187,8 +187,9 @@ def _flatten(groups):
 @torch.inference_mode()
 def get_weighted_text_embeddings_flux(pipe: "FluxPipeline", prompt: str = "", num_images_per_prompt: int = 1,
                                       device: Optional[torch.device] = None, target_device: Optional[torch.device] = torch.device("cuda:0"),
-                                      target_dtype: Optional[torch.dtype] = torch.bfloat16, debug: bool = False):
+                                      target_dtype: Optional[torch.dtype] = torch.bfloat16, debug: bool = False, need_clip: bool = True):
     """-> (clip pooled [bs, 768], weighted T5 states [bs, t5_length, 4096], txt_ids zeros [bs, t5_length, 3]).
+    need_clip=False (a region prompt of a regional request, whose pooled vector nobody reads) skips the CLIP encoder: the first result is None.
 
     The reference's pipeline: weighted token lists from both tokenizers -> grouped / padded -> DECODED back to text and re-tokenised
     with special tokens at the fixed lengths (CLIP 77; T5 512 for flux-dev, 256 otherwise) -> encoders (attention_mask=None) -> the
@@ -214,9 +215,11 @@ def get_weighted_text_embeddings_flux(pipe: "FluxPipeline", prompt: str = "", nu
     w = torch.tensor(_flatten(g_w_t5), dtype=torch.float32)
     weights_t5 = torch.cat([w, torch.full((t5_length - w.numel(),), 1.0, dtype=torch.float32)], dim=0).to(device)
 
-    clip_embeds = clip(tokens_clip, output_hidden_states=True, attention_mask=None)["pooler_output"]
-    if clip_embeds.shape[0] == 1 and num_images_per_prompt > 1:
-        clip_embeds = clip_embeds.expand(num_images_per_prompt, *clip_embeds.shape[1:])
+    clip_embeds = None
+    if need_clip:
+        clip_embeds = clip(tokens_clip, output_hidden_states=True, attention_mask=None)["pooler_output"]
+        if clip_embeds.shape[0] == 1 and num_images_per_prompt > 1:
+            clip_embeds = clip_embeds.expand(num_images_per_prompt, *clip_embeds.shape[1:])
     t5_embeds = t5(tokens_t5, output_hidden_states=True, attention_mask=None)["last_hidden_state"]
     t5_embeds = apply_weights(tokens_t5, weights_t5, t5_embeds, t5_tok.eos_token_id)
     if debug:
@@ -224,4 +227,6 @@ def get_weighted_text_embeddings_flux(pipe: "FluxPipeline", prompt: str = "", nu
     if t5_embeds.shape[0] == 1 and num_images_per_prompt > 1:
         t5_embeds = t5_embeds.expand(num_images_per_prompt, *t5_embeds.shape[1:])
     txt_ids = torch.zeros(num_images_per_prompt, t5_embeds.shape[1], 3, device=target_device, dtype=target_dtype)
-    return clip_embeds.to(target_device, dtype=target_dtype).contiguous(), t5_embeds.to(target_device, dtype=target_dtype).contiguous(), txt_ids
+    if clip_embeds is not None:
+        clip_embeds = clip_embeds.to(target_device, dtype=target_dtype).contiguous()
+    return clip_embeds, t5_embeds.to(target_device, dtype=target_dtype).contiguous(), txt_ids

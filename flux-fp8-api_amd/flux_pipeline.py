@@ -55,6 +55,97 @@ def kontext_reference_ids(bs: int, h_l: int, w_l: int, device=None, dtype=torch.
     return ids
 
 
+# ---- regional prompts: token-group attention masks (include/fluxmi.h, fluxmi_attention_grouped) --------------------------------------
+ATTN_GROUPS = 16  # key groups of a descriptor table
+
+
+def region_token_grid(region: dict, height: int, width: int) -> torch.Tensor:
+    """One entry of generate(regions=...) -> bool [height/16, width/16]: which image tokens the region covers.  `box` = (x0, y0, x1, y1)
+    in 0..1 of the image, or `mask` = an image / array / tensor (white = inside; any size, resized by area averaging).  Both are
+    area-averaged to the token grid and thresholded at 0.5.  A region that covers no token is refused."""
+    h, w = height // 16, width // 16
+    if not isinstance(region, dict) or ("box" in region) == ("mask" in region):
+        raise ValueError("fluxmi: a region needs a 'prompt' and exactly one of 'box' (x0, y0, x1, y1 in 0..1) and 'mask'")
+    if "box" in region:
+        try:
+            x0, y0, x1, y1 = (float(v) for v in region["box"])
+        except (TypeError, ValueError):
+            raise ValueError(f"fluxmi: region box {region['box']!r}: expected (x0, y0, x1, y1)") from None
+        if not (0.0 <= x0 < x1 <= 1.0 and 0.0 <= y0 < y1 <= 1.0):
+            raise ValueError(f"fluxmi: region box {region['box']!r}: expected 0 <= x0 < x1 <= 1 and 0 <= y0 < y1 <= 1")
+        # covered fraction of every token cell = (overlap of [x0 w, x1 w] with [j, j + 1]) x (the same in y)
+        cov = lambda a, b, n: (torch.minimum(torch.arange(1, n + 1, dtype=torch.float64), torch.tensor(b * n, dtype=torch.float64))
+                               - torch.maximum(torch.arange(0, n, dtype=torch.float64), torch.tensor(a * n, dtype=torch.float64))).clamp_(min=0)
+        frac = cov(y0, y1, h)[:, None] * cov(x0, x1, w)[None, :]
+    else:
+        m = region["mask"]
+        if hasattr(m, "convert"):  # PIL
+            m = np.array(m.convert("L"))
+        m = torch.as_tensor(np.asarray(m) if not isinstance(m, torch.Tensor) else m)
+        # 8-bit images are 0..255; bool masks and the 0 / 1 bytes of a bilevel ('1') image are 0..1 already, like float masks
+        scale = 255.0 if m.dtype == torch.uint8 and m.numel() and int(m.max()) > 1 else 1.0
+        m = m.to(torch.float64) / scale
+        if m.dim() == 3:
+            m = m.mean(-1) if m.shape[-1] in (1, 3, 4) else m.mean(0)
+        if m.dim() != 2 or m.numel() == 0:
+            raise ValueError(f"fluxmi: region mask of shape {tuple(m.shape)}: expected [H, W] (or an image)")
+        frac = torch.nn.functional.adaptive_avg_pool2d(m[None, None], (h, w))[0, 0]
+    grid = frac >= 0.5
+    if not bool(grid.any()):
+        raise ValueError("fluxmi: a region covers no image token (16 x 16 pixels each) at this size")
+    return grid
+
+
+def build_region_groups(n_base: int, regional_tokens: int, region_grids: torch.Tensor, n_ref: int = 0, negative: bool = False) -> torch.Tensor:
+    """The descriptor table of ONE sample of a regional request, int32 [L] (include/fluxmi.h: g | P << 16; query i attends key j iff bit
+    g_j of P_i), for the joint sequence
+        [ base text (n_base rows: T5 + Redux tokens) | region 1 text | .. | region R text (regional_tokens rows each) | image tokens
+          (h w, row-major) | n_ref Kontext reference rows ].
+    region_grids: bool [R, h, w], which image tokens each region covers (region_token_grid).
+    Key groups: 0 = base text; r = 1..R the text of region r; then one group per distinct COVERAGE PATTERN of the image tokens (the set
+    of regions that cover a token), in ascending order of the pattern read as a bit set -- uncovered tokens and reference rows have the
+    pattern "none".  More than 16 groups are refused.
+    Permissions: a base-text query sees group 0 and every image group; a text query of region r sees group r and the image groups whose
+    pattern contains r; an image query of pattern S sees group 0, the text groups of S and EVERY image group (image-to-image attention
+    stays dense).  negative=True (the negative branch of true classifier-free guidance): every query loses the region text groups and a
+    region's text rows see only themselves, so their content is inert.  Every query admits its own group."""
+    grids = torch.as_tensor(region_grids).bool()
+    if grids.dim() != 3 or grids.shape[0] < 1:
+        raise ValueError(f"fluxmi: region grids of shape {tuple(grids.shape)}: expected [R >= 1, h, w]")
+    R = grids.shape[0]
+    if n_base < 0 or n_ref < 0 or regional_tokens < 1:
+        raise ValueError("fluxmi: n_base, n_ref >= 0 and regional_tokens >= 1 expected")
+    if R + 2 > ATTN_GROUPS:
+        raise ValueError(f"fluxmi: {R} regions need {R + 2} or more attention groups; at most {ATTN_GROUPS} exist (base text + one per region "
+                         "text + one per distinct overlap pattern)")
+    for r in range(R):
+        if not bool(grids[r].any()):
+            raise ValueError(f"fluxmi: region {r} covers no image token")
+    pattern = (grids.flatten(1).long() << torch.arange(R)[:, None]).sum(0)  # [h w] bit r = region r + 1 covers the token
+    if n_ref:
+        pattern = torch.cat((pattern, torch.zeros(n_ref, dtype=torch.long)))
+    pats = torch.unique(pattern)  # ascending
+    n_groups = 1 + R + pats.numel()
+    if n_groups > ATTN_GROUPS:
+        raise ValueError(f"fluxmi: the regions need {n_groups} attention groups (1 base text + {R} region texts + {pats.numel()} distinct "
+                         f"overlap patterns of the image tokens); at most {ATTN_GROUPS} exist -- use fewer or less overlapping regions")
+    img_group = 1 + R + torch.searchsorted(pats, pattern)
+    img_bits = sum(1 << (1 + R + i) for i in range(pats.numel()))
+    txt_of = lambda p: (int(p) << 1)  # pattern bit r -> text group r + 1
+    group = torch.cat((torch.zeros(n_base, dtype=torch.long), torch.arange(1, R + 1).repeat_interleave(regional_tokens), img_group))
+    if negative:
+        perm_region = [1 << r for r in range(1, R + 1)]
+        perm_img = torch.full_like(pattern, 1 | img_bits)
+    else:
+        perm_region = [(1 << r) | sum(1 << (1 + R + i) for i, p in enumerate(pats.tolist()) if (p >> (r - 1)) & 1) for r in range(1, R + 1)]
+        perm_img = (pattern << 1) | 1 | img_bits
+    perm = torch.cat((torch.full((n_base,), 1 | img_bits, dtype=torch.long),
+                      torch.tensor(perm_region, dtype=torch.long).repeat_interleave(regional_tokens), perm_img))
+    d = group | (perm << 16)
+    assert bool(((perm >> group) & 1).all())
+    return torch.where(d >= 1 << 31, d - (1 << 32), d).to(torch.int32)
+
+
 class FluxPipeline:
     def __init__(self, name: str, offload: bool = False, clip=None, t5=None, model=None, ae=None,
                  dtype: torch.dtype = torch.float16, verbose: bool = False, flux_device="cuda:0", ae_device="cuda:1",
@@ -401,6 +492,20 @@ class FluxPipeline:
         txt_ids = torch.zeros(bs, txt.shape[1], 3, device=target_device, dtype=target_dtype)
         return tokens, img_ids, vec, txt, txt_ids
 
+    def _region_text(self, prompt) -> torch.Tensor:
+        """T5 states [1, Lt, C] of one region prompt (prompt weighting syntax included), or the `txt` of pre-computed embeddings.  Only the
+        text stream of a region is used (y and guidance come from the base prompt), so CLIP does not run and no image ids are built."""
+        if isinstance(prompt, dict):
+            return prompt["txt"].to(device=self.device_flux, dtype=self.dtype)
+        if not isinstance(prompt, str):
+            raise TypeError("fluxmi: a region prompt must be a str or a dict of pre-computed embeddings")
+        if self.t5 is None or self.clip is None:
+            raise RuntimeError("fluxmi: no text encoders attached; pass region prompts as {'txt': T5 states [1, Lt, C]}")
+        from flux_emphasis import get_weighted_text_embeddings_flux
+
+        return get_weighted_text_embeddings_flux(self, prompt, num_images_per_prompt=1, device=self.device_clip, target_device=self.device_flux,
+                                                 target_dtype=self.dtype, debug=self.debug, need_clip=False)[1]
+
     def _prepare_negative(self, negative_prompt, noise: torch.Tensor, num_images: int, txt: torch.Tensor):
         """The negative prompt through prepare()'s text path (prompt weighting syntax included) -> (vec, txt) [num_images, ...] matching the
         prompt's `txt`.  Checked here, before any collective: every rank sees the same shapes, so every rank raises."""
@@ -481,7 +586,8 @@ class FluxPipeline:
                  return_seed: bool = False, jpeg_quality: int = 99, output_type: str = "jpeg", noise: Optional[torch.Tensor] = None,
                  use_graph: bool = True, reference_image=None, mask_image=None, control_image=None,
                  img_cond: Optional[torch.Tensor] = None, redux_image=None, negative_prompt=None, true_cfg_scale: float = 1.0,
-                 true_cfg_interval=(0.0, 1.0), cache_threshold: float = 0.0, cache_max_hits: int = 0):
+                 true_cfg_interval=(0.0, 1.0), cache_threshold: float = 0.0, cache_max_hits: int = 0, regions=None,
+                 regional_tokens: int = 128):
         """`reference_image` (FLUX.1 Kontext [dev] instruction editing): an image the prompt describes an edit of, in any form `init_image`
         takes; see prepare_kontext_reference.  Composes with `init_image` / `strength` unchanged.
         FLUX.1 Fill [dev] (a model with 320 conditioning channels): `init_image` is the image to inpaint and `mask_image` (white =
@@ -507,7 +613,30 @@ class FluxPipeline:
         `cache_threshold` > 0 (+ `cache_max_hits`): first-block step caching (Flux.denoise; diffusers' FirstBlockCacheConfig): a frozen step
         whose first double block's residual moved by less than the threshold since the last full step skips every later block and reuses
         that step's residual.  Off by default; an approximation when on -- no threshold is recommended here (README).  Each of the up to
-        three denoise calls of a `true_cfg_interval` request starts with an empty cache."""
+        three denoise calls of a `true_cfg_interval` request starts with an empty cache.
+        `regions` (regional prompts): a list of {"prompt": ..., "box": (x0, y0, x1, y1)} (0..1 of the image) or {"prompt": ..., "mask": image}
+        entries.  Rows [0, regional_tokens) of each region prompt's T5 states are appended to the text stream (behind the prompt's and any
+        Redux tokens; `y` and `guidance` stay the base prompt's, txt_ids stay zero) and every attention runs under the token-group mask of
+        build_region_groups: a region's text and the image tokens it covers see each other, the base prompt sees and is seen by every
+        image token, image tokens see all image tokens.  `regional_tokens` is a multiple of 16.  Composes with img2img, a Kontext
+        reference (its rows count as uncovered), Fill / Depth / Canny, Redux, LoRA, step caching and a negative prompt (the negative
+        branch carries the same rows, masked out of every other token's view).  Under a process group the region text rides in the one
+        request broadcast; the table is a pure function of the request's arguments, the same on every rank.  Without `regions` nothing
+        changes, the text-encoder calls included."""
+        region_grids = None
+        if regions is not None:
+            if not isinstance(regions, (list, tuple)) or not regions:
+                raise ValueError("fluxmi: regions must be a non-empty list of {'prompt', 'box' | 'mask'} entries")
+            if not isinstance(regional_tokens, int) or regional_tokens < 16 or regional_tokens % 16:
+                raise ValueError(f"fluxmi: regional_tokens={regional_tokens!r}: expected a positive multiple of 16")
+            for r in regions:
+                if not isinstance(r, dict) or "prompt" not in r:
+                    raise ValueError("fluxmi: every region needs a 'prompt'")
+            # a mask given as a path / base64 string is loaded like init_image
+            regions = [{**r, "mask": self.load_init_image_if_needed(r["mask"])} if isinstance(r.get("mask"), str) else r for r in regions]
+            region_grids = torch.stack([region_token_grid(r, 16 * (height // 16), 16 * (width // 16)) for r in regions])
+            if len(regions) + 2 > ATTN_GROUPS:
+                raise ValueError(f"fluxmi: {len(regions)} regions: at most {ATTN_GROUPS - 2} fit the {ATTN_GROUPS} attention groups")
         try:
             cache_threshold, cache_max_hits = float(cache_threshold), int(cache_max_hits)
         except (TypeError, ValueError):
@@ -583,6 +712,19 @@ class FluxPipeline:
             txt, txt_ids = txt.contiguous(), txt_ids.contiguous()
             if guided:  # the same image tokens behind the negative prompt's T5 tokens
                 neg_txt = torch.cat((neg_txt, txt[:, neg_txt.shape[1]:]), dim=-2).contiguous()
+        n_base = txt.shape[1]
+        if regions is not None:
+            rows = []
+            for r in regions:
+                r_txt = self._region_text(r["prompt"])
+                if r_txt.shape[0] != 1 or r_txt.shape[1] < regional_tokens or r_txt.shape[2] != txt.shape[2]:
+                    raise ValueError(f"fluxmi: a region prompt's T5 states {tuple(r_txt.shape)} hold fewer than regional_tokens={regional_tokens} rows")
+                rows.append(r_txt[:, :regional_tokens].to(txt))
+            rows = torch.cat(rows, 1).expand(txt.shape[0], -1, -1)
+            txt = torch.cat((txt, rows), 1).contiguous()
+            txt_ids = txt_ids.new_zeros(txt.shape[0], txt.shape[1], 3)
+            if guided:  # the same rows in the negative branch, where the table hides them from every other token
+                neg_txt = torch.cat((neg_txt, rows), 1).contiguous()
         cond = {}
         if reference_image is not None:
             # drawn from the request's generator after the noise (the order is part of what a seed reproduces)
@@ -628,8 +770,14 @@ class FluxPipeline:
             # step i is guided iff cfg_lo n <= i < cfg_hi n, i.e. ceil(cfg_lo n) <= i < ceil(cfg_hi n)
             g0, g1 = (min(n, math.ceil(cfg_lo * n)), min(n, math.ceil(cfg_hi * n))) if guided else (n, n)
             neg = dict(neg_txt=neg_txt, neg_y=neg_vec, cfg_scale=true_cfg_scale)
+            plain_kw = {}
+            if regions is not None:
+                n_ref = cond["img_cond_seq"].shape[1] if "img_cond_seq" in cond else 0
+                tab = [build_region_groups(n_base, regional_tokens, region_grids, n_ref=n_ref, negative=ng) for ng in ((False, True) if guided else (False,))]
+                plain_kw = dict(attn_groups=tab[0][None].to(self.device_flux))
+                neg["attn_groups"] = torch.stack(tab).to(self.device_flux)
             latents = img
-            for a, b, kw in ((0, g0, {}), (g0, g1, neg), (g1, n, {})) if g0 < g1 else ((0, n, {}),):
+            for a, b, kw in ((0, g0, plain_kw), (g0, g1, neg), (g1, n, plain_kw)) if g0 < g1 else ((0, n, plain_kw),):
                 if a < b or n == 0:
                     latents = self.model.denoise(latents, img_ids, txt, txt_ids, vec, timesteps[a:b + 1], guidance=guidance, use_graph=use_graph,
                                                  **cond, **kw, **cache)

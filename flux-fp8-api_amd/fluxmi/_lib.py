@@ -96,6 +96,8 @@ _SIGS = {
     "fluxmi_vision_attention": ([vp, vp, i64, i64, vp, i64, i64, vp, i64, i64, vp, C.c_float, i32, i32, i32, i32, i32, vp], i32),
     "fluxmi_patchify": ([vp, vp, i32, i32, i32, i32, i32, i32, i32, vp], i32),
     "fluxmi_attention": ([vp, vp, vp, vp, i64, i32, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp], i32),
+    "fluxmi_attention_grouped": ([vp, vp, vp, vp, i64, i32, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp], i32),
+    "fluxmi_attention_rawq_grouped": ([vp, i64, vp, vp, vp, vp, vp, vp, i64, i32, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp], i32),
     "fluxmi_attention_debug_buffer": ([vp], i32),
     "fluxmi_attention_plan": ([i32, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(C.c_ulonglong)], i32),
     "fluxmi_attention_rawq": ([vp, i64, vp, vp, vp, vp, vp, vp, i64, i32, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp], i32),
@@ -124,6 +126,7 @@ _SIGS = {
     "fluxmi_engine_run_block": ([vp, i32, i32, i32, i32, i32, vp], i32),
     "fluxmi_engine_copy_buffer": ([vp, C.c_char_p, i64, vp, i64, i32, vp], i32),
     "fluxmi_engine_set_step_cache": ([vp, f32, i32], i32),
+    "fluxmi_engine_set_attn_groups": ([vp, vp, vp], i32),
     "fluxmi_engine_step_cache_log": ([vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(f32), C.POINTER(C.c_ubyte), i32], i32),
     "fluxmi_engine_run_phase": ([vp, i32, i32, i32, i32, vp], i32),
 }

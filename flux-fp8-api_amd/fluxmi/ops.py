@@ -258,8 +258,48 @@ def qkv_rope(qkv, pe, q_scale0, k_scale0, q_scale1=None, k_scale1=None, split=No
     return Q, K, VT
 
 
-def attention(Q, K, VT, q_scale0=None, q_scale1=None, split=None, fmt=E5M2, out=None, col_off=0):
-    """K may be bfloat16 or float16 (float16 selects the folded kernel, see include/fluxmi.h)."""
+ATTN_GROUPS = 16  # key groups of a token-group mask (include/fluxmi.h, fluxmi_attention_grouped)
+ATTN_MASK_FLOOR = -1024.0  # exp2 domain: where a masked row's running maximum starts (M_FLOOR of csrc/attention2.hip)
+ATTN_MASK_L_MAX = 12096  # the keys' group codes are staged in LDS behind the K / V^T rings
+
+
+def attn_descriptors(group: torch.Tensor, perm: torch.Tensor) -> torch.Tensor:
+    """Per-token descriptors of a token-group mask: group [.., L] in [0, 16) = the token's key group, perm [.., L] = bit set of the groups
+    its query admits -> int32 [.., L] holding the bits of FLUXMI_ATTN_DESC(group, perm).  Query i attends key j iff bit group[j] of perm[i]."""
+    g, p = group.to(torch.int64), perm.to(torch.int64)
+    if g.numel() and (int(g.min()) < 0 or int(g.max()) >= ATTN_GROUPS or int(p.min()) < 0 or int(p.max()) >= 1 << ATTN_GROUPS):
+        raise ValueError(f"attn_descriptors: groups must lie in [0, {ATTN_GROUPS}) and permission sets in [0, 2^{ATTN_GROUPS})")
+    d = g | (p << 16)
+    return torch.where(d >= 1 << 31, d - (1 << 32), d).to(torch.int32)
+
+
+def attn_groups_allowed(groups: torch.Tensor) -> torch.Tensor:
+    """descriptors [B, L] -> bool [B, L, L]: allowed[b, i, j] = query i attends key j (the attn_mask of F.scaled_dot_product_attention)"""
+    d = groups.to(torch.int64) & 0xFFFFFFFF
+    g, p = d & 15, d >> 16
+    return ((p[:, :, None] >> g[:, None, :]) & 1).bool()
+
+
+def check_attn_groups(groups: torch.Tensor, B: int, L: int) -> torch.Tensor:
+    """Shape, dtype and SELF-ADMISSION of a descriptor table (every query admits its own group: no softmax row is empty)."""
+    if groups.dtype not in (torch.int32, torch.uint32) or tuple(groups.shape) != (B, L) or not groups.is_contiguous():
+        raise ValueError(f"attention groups: need a contiguous int32 / uint32 [B={B}, L={L}] table, got {groups.dtype} {tuple(groups.shape)}")
+    d = groups.view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    g, p = d & 15, d >> 16
+    if bool((d & 0xFFF0).any()):
+        raise ValueError("attention groups: bits 4-15 of a descriptor must be zero")
+    if not bool(((p >> g) & 1).all()):
+        raise ValueError("attention groups: every query must admit its own key group (an empty softmax row otherwise)")
+    return groups
+
+
+def attention(Q, K, VT, q_scale0=None, q_scale1=None, split=None, fmt=E5M2, out=None, col_off=0, groups=None, out_pairs=False):
+    """K may be bfloat16 or float16 (float16 selects the folded kernel, see include/fluxmi.h).
+    groups: a token-group mask, int32 [B, L] descriptors on the device (attn_descriptors); out_pairs (with groups, fp8 output): rows in
+    the row-pair layout (pair_rows).  With groups, L <= 12096, and a row's admitted scores must not all lie below ATTN_MASK_FLOOR + 126
+    in the exp2 domain (q . k / sqrt(128) * log2 e; about |q . k| / sqrt(128) < 620): the masked rows' running maximum starts from that
+    floor, below it a row sums to l = 0 and comes out inf / nan.  Nothing checks this per call (Q is device data); QK-normed operands
+    are two orders of magnitude inside it."""
     B, H, L, _ = Q.shape
     Lp = VT.shape[-1]
     split = L if split is None else split
@@ -267,6 +307,13 @@ def attention(Q, K, VT, q_scale0=None, q_scale1=None, split=None, fmt=E5M2, out=
     q_scale1 = q_scale0 if q_scale1 is None else q_scale1
     if out is None:
         out = torch.empty((B, L, H * 128), dtype=dtype_of(fmt) if out_fp8 else torch.bfloat16, device=Q.device)
+    if groups is not None:
+        check_attn_groups(groups, B, L)
+        call("fluxmi_attention_grouped", _p(Q), _p(K), _p(VT), _p(out), out.stride(1), col_off, int(out_fp8), _p(q_scale0), _p(q_scale1), split,
+             B, L, Lp, H, fmt, int(K.dtype == torch.float16), _p(groups), int(out_pairs), _stream())
+        return out
+    if out_pairs:
+        raise ValueError("attention: out_pairs is an argument of the grouped entry (pass groups)")
     call("fluxmi_attention", _p(Q), _p(K), _p(VT), _p(out), out.stride(1), col_off, int(out_fp8), _p(q_scale0), _p(q_scale1), split,
          B, L, Lp, H, fmt, int(K.dtype == torch.float16), _stream())
     return out
@@ -296,8 +343,10 @@ def attention_plan(B: int, L: int, H: int):
     return dict(n_per_x=n.value, full_per_x=f.value, pieces=pieces, thin=kind == 1)  # thin: what fluxmi_tuning_t.attn_split = 1 takes
 
 
-def attention_rawq(qkv, pe, qn_scale0, K, VT, qn_scale1=None, q_scale0=None, q_scale1=None, split=None, fmt=E5M2, out=None, col_off=0):
-    """Attention with Q read raw from the qkv GEMM output [B,L,>=H*128] (QKNorm + RoPE applied on load); K, VT from qkv_rope."""
+def attention_rawq(qkv, pe, qn_scale0, K, VT, qn_scale1=None, q_scale0=None, q_scale1=None, split=None, fmt=E5M2, out=None, col_off=0,
+                   groups=None, out_pairs=False):
+    """Attention with Q read raw from the qkv GEMM output [B,L,>=H*128] (QKNorm + RoPE applied on load); K, VT from qkv_rope.
+    groups / out_pairs: as in attention."""
     B, H, L, _ = K.shape
     Lp = VT.shape[-1]
     split = L if split is None else split
@@ -306,6 +355,14 @@ def attention_rawq(qkv, pe, qn_scale0, K, VT, qn_scale1=None, q_scale0=None, q_s
     q_scale1 = q_scale0 if q_scale1 is None else q_scale1
     if out is None:
         out = torch.empty((B, L, H * 128), dtype=dtype_of(fmt) if out_fp8 else torch.bfloat16, device=K.device)
+    if groups is not None:
+        check_attn_groups(groups, B, L)
+        call("fluxmi_attention_rawq_grouped", _p(qkv), qkv.stride(1), _p(pe), _p(qn_scale0), _p(qn_scale1), _p(K), _p(VT), _p(out),
+             out.stride(1), col_off, int(out_fp8), _p(q_scale0), _p(q_scale1), split, B, L, Lp, H, fmt, int(K.dtype == torch.float16),
+             _p(groups), int(out_pairs), _stream())
+        return out
+    if out_pairs:
+        raise ValueError("attention_rawq: out_pairs is an argument of the grouped entry (pass groups)")
     call("fluxmi_attention_rawq", _p(qkv), qkv.stride(1), _p(pe), _p(qn_scale0), _p(qn_scale1), _p(K), _p(VT), _p(out), out.stride(1),
          col_off, int(out_fp8), _p(q_scale0), _p(q_scale1), split, B, L, Lp, H, fmt, int(K.dtype == torch.float16), _stream())
     return out

@@ -329,6 +329,19 @@ class Flux(nn.Module):
         else:
             _lib.call("fluxmi_engine_prepare", self._engine, B, L_img, Lt, ops._p(ii), ops._p(ti), ops._stream())
 
+    def _set_attn_groups(self, attn_groups, B: int, L: int, device):
+        """after _prepare, under the lock: the token-group attention mask of this call (int32 [B, L] descriptors; fluxmi.ops.attn_descriptors,
+        flux_pipeline.build_region_groups), or None = dense.  The engine copies the table and checks self-admission."""
+        if attn_groups is None:
+            _lib.call("fluxmi_engine_set_attn_groups", self._engine, None, ops._stream())
+            return
+        g = attn_groups
+        if g.dtype not in (torch.int32, torch.uint32) or g.ndim != 2 or g.shape[0] not in (1, B) or g.shape[1] != L:
+            raise ValueError(f"attn_groups {g.dtype} {tuple(g.shape)}: expected int32 [1 or {B}, {L}] (one descriptor per token of the joint "
+                             f"sequence: text rows, image rows, reference rows)")
+        g = g.to(device).expand(B, L).contiguous()
+        _lib.call("fluxmi_engine_set_attn_groups", self._engine, ops._p(g), ops._stream())
+
     @staticmethod
     def _with_reference(img, img_ids, img_cond_seq, img_cond_seq_ids):
         """FLUX.1 Kontext: the reference tokens ride behind the noisy tokens of each sample -> (stream, stream ids, Lc).  Both None: unchanged."""
@@ -464,13 +477,15 @@ class Flux(nn.Module):
     @torch.inference_mode()
     def forward(self, img: Tensor, img_ids: Tensor, txt: Tensor, txt_ids: Tensor, timesteps: Tensor, y: Tensor,
                 guidance: Tensor | None = None, mode: Optional[int] = None, img_cond_seq: Tensor | None = None,
-                img_cond_seq_ids: Tensor | None = None, img_cond: Tensor | None = None) -> Tensor:
+                img_cond_seq_ids: Tensor | None = None, img_cond: Tensor | None = None, attn_groups: Tensor | None = None) -> Tensor:
         """One denoise-step evaluation (reference flux_model.py:672-716).  mode=None picks what the reference would do:
         calibrating (unfused) while any F8Linear still has trials to record, fused once frozen.
         FLUX.1 Kontext: `img_cond_seq` [B, Lc, C] / `img_cond_seq_ids` [B, Lc, 3] (flux_pipeline.prepare_kontext_reference) run through every
         block behind the noisy tokens; the prediction covers the `img.shape[1]` noisy tokens only.
         FLUX.1 Fill / Depth / Canny: `img_cond` [B, Li, in_channels - out_channels] (flux_pipeline.prepare_fill_conditioning /
-        prepare_control_conditioning) is appended to the channels of every token; the prediction is [B, Li, out_channels]."""
+        prepare_control_conditioning) is appended to the channels of every token; the prediction is [B, Li, out_channels].
+        `attn_groups`: a token-group attention mask, int32 [1 or B, Lt + Li + Lc] descriptors (include/fluxmi.h, fluxmi_attention_grouped):
+        every attention of the forward then runs F.scaled_dot_product_attention(q, k, v, attn_mask=allowed) instead of the dense one."""
         if img.ndim != 3 or txt.ndim != 3:
             raise ValueError("Input img and txt tensors must have 3 dimensions.")
         if self.params.guidance_embed and guidance is None:
@@ -484,6 +499,7 @@ class Flux(nn.Module):
         self._ensure_engine(img.device)
         with self._lock:
             self._prepare(img, img_ids, txt_ids, txt, Lc)
+            self._set_attn_groups(attn_groups, img.shape[0], txt.shape[1] + img.shape[1], img.device)
             trial = self._trial_counter()
             if mode is None:
                 if trial is None:
@@ -512,7 +528,8 @@ class Flux(nn.Module):
     def denoise(self, img: Tensor, img_ids: Tensor, txt: Tensor, txt_ids: Tensor, y: Tensor, timesteps: List[float],
                 guidance: float = 3.5, use_graph: bool = True, img_cond_seq: Tensor | None = None,
                 img_cond_seq_ids: Tensor | None = None, img_cond: Tensor | None = None, neg_txt: Tensor | None = None,
-                neg_y: Tensor | None = None, cfg_scale: float = 1.0, cache_threshold: float = 0.0, cache_max_hits: int = 0) -> Tensor:
+                neg_y: Tensor | None = None, cfg_scale: float = 1.0, cache_threshold: float = 0.0, cache_max_hits: int = 0,
+                attn_groups: Tensor | None = None) -> Tensor:
         """The Euler loop of FluxPipeline.generate (reference flux_pipeline.py:619-651) run natively: calibrating
         steps unfused, every later step one replay of a captured hipGraph.  Returns the final latent tokens.
         FLUX.1 Kontext: with `img_cond_seq` / `img_cond_seq_ids` the reference tokens join every step's forward and are never stepped; the
@@ -526,7 +543,9 @@ class Flux(nn.Module):
         First-block step caching: `cache_threshold` > 0 lets a frozen step whose first double block's residual moved by less than that
         (relative L1, per sample; every sample of the pass must agree) reuse the remaining blocks' residual of the last full step instead of
         running them; at most `cache_max_hits` such steps in a row (0 = no bound).  0 (the default) = off: the call is today's, bit for bit.
-        Every call starts with an empty cache; `step_cache_log()` tells what the last call did."""
+        Every call starts with an empty cache; `step_cache_log()` tells what the last call did.
+        `attn_groups`: a token-group attention mask for every attention of every step (Flux.forward), int32 [1 or B, Lt + Li + Lc]; a guided
+        call takes [2 or 2B, ...]: the tables of the prompt branches, then those of the negative branches.  None = dense, today's call."""
         cache_threshold, cache_max_hits = float(cache_threshold), int(cache_max_hits)
         if not (math.isfinite(cache_threshold) and cache_threshold >= 0.0) or cache_max_hits < 0:
             raise ValueError(f"cache_threshold {cache_threshold} must be finite and >= 0 (0 = off), cache_max_hits {cache_max_hits} >= 0 (0 = no bound)")
@@ -566,6 +585,9 @@ class Flux(nn.Module):
                     cond["img_cond"] = pick(img_cond)
                 if guided:
                     cond.update(neg_txt=pick(neg_txt), neg_y=pick(neg_y), cfg_scale=cfg_scale)
+                if attn_groups is not None:
+                    halves = attn_groups.chunk(2, 0) if guided else (attn_groups,)
+                    cond["attn_groups"] = torch.cat([h if h.shape[0] == 1 else pick(h) for h in halves], 0)
                 o = self.denoise(pick(img), pick(img_ids), pick(txt), pick(txt_ids), pick(y), timesteps, guidance=guidance, use_graph=use_graph,
                                  cache_threshold=cache_threshold, cache_max_hits=cache_max_hits, **cond)
                 outs.append(o[:per - pad])
@@ -580,6 +602,9 @@ class Flux(nn.Module):
         self._ensure_engine(img.device)
         with self._lock:
             self._prepare(img, img_ids, txt_ids, txt, Lc)
+            if attn_groups is not None and guided and attn_groups.shape[0] == 2 and txt.shape[0] > 2:
+                attn_groups = attn_groups.repeat_interleave(txt.shape[0] // 2, 0)  # [pos, neg] -> B x pos, B x neg
+            self._set_attn_groups(attn_groups, txt.shape[0], txt.shape[1] + img.shape[1], img.device)
             trial = self._trial_counter()
             t_io = C.c_int(trial if trial is not None else 0)
             ts = (C.c_double * len(timesteps))(*[float(t) for t in timesteps])

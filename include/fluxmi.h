@@ -304,6 +304,25 @@ int fluxmi_attention_rawq(const void* qkv, long long ld_qkv, const void* pe, con
                           const void* VT, void* out, long long ld_out, int col_off, int out_fp8, const float* q_scale0,
                           const float* q_scale1, int split, int B, int L, int Lp, int H, int fmt, int k_f16, void* stream);
 
+/* Token-group masks (regional prompts, key-masked padding): the two entries above plus `groups`, a DEVICE table [B, L] of one 32-bit
+ * descriptor per token of the joint sequence, and `out_pairs` (fp8 output rows in the row-pair layout of fluxmi_gemm_group_t.a_pairs).
+ *   descriptor = g | P << 16:  g (bits 0-3) the token's KEY GROUP, P (bits 16-31) the groups its QUERY admits; bits 4-15 are zero.
+ *   Query i attends key j iff bit g_j of P_i is set: F.scaled_dot_product_attention(q, k, v, attn_mask=allowed).
+ * Every query must admit its own group (no empty softmax row); the CALLER checks that (FLUXMI_ATTN_DESC and ops.attention do; the table is
+ * device data and this call does not read it back).  groups = NULL is the dense call.  A table that admits everything gives the dense
+ * result bit for bit.  The mask costs two more QK^T MFMAs per 64-key tile (one-hot group code x permission row; csrc/attention2.hip) and
+ * L <= 12096 (the keys' group codes are staged in LDS).  Masked launches take no balanced-grid plan: one workgroup per task under every
+ * attn_split.  Scores of admitted keys must stay above -1024 + 126 in the exp2 domain (|q . k| / sqrt(128) < ~620: the masked rows' running
+ * maximum starts from that floor, see the kernel). */
+#define FLUXMI_ATTN_DESC(group, perm) ((unsigned)(group) | ((unsigned)(perm) << 16))
+int fluxmi_attention_grouped(const void* Q, const void* K, const void* VT, void* out, long long ld_out, int col_off, int out_fp8,
+                             const float* q_scale0, const float* q_scale1, int split, int B, int L, int Lp, int H, int fmt, int k_f16,
+                             const unsigned* groups, int out_pairs, void* stream);
+int fluxmi_attention_rawq_grouped(const void* qkv, long long ld_qkv, const void* pe, const void* qn_scale0, const void* qn_scale1,
+                                  const void* K, const void* VT, void* out, long long ld_out, int col_off, int out_fp8,
+                                  const float* q_scale0, const float* q_scale1, int split, int B, int L, int Lp, int H, int fmt, int k_f16,
+                                  const unsigned* groups, int out_pairs, void* stream);
+
 /* ---- VAE pieces (NHWC bf16) -------------------------------------------------------------------- */
 /* 3x3 patch matrix: x [B, Hi, Wi, C] -> col [B*H*W, 9*C], column (dy*3+dx)*C + c, (H, W) = the OUTPUT grid.  `upsample`:
  *   1  stride 1 / pad 1 (Hi = H);   2  nearest 2x upsample folded into the gather (Hi = H/2; Upsample.forward);
@@ -514,6 +533,13 @@ int fluxmi_engine_copy_buffer(fluxmi_engine_t* e, const char* name, long long of
  * step_cache_log: the frozen steps of the last denoise call, cached or not (a plain call: *n = 0): *n = their number, *batch = B of that pass, ratios[i * B + b]
  * and hit[i] for the first min(*n, cap) of them; a step with no reference yet (the first) logs +inf.  ratios / hit may be NULL with cap = 0. */
 int fluxmi_engine_set_step_cache(fluxmi_engine_t* e, float threshold, int max_consecutive_hits);
+/* Token-group attention mask (fluxmi_attention_grouped) for every attention launch of the PREPARED shape: `table` = [B, L] descriptors on
+ * the device, L = Lt + Li in the order of the joint sequence (text rows, image rows, reference rows).  The engine copies them into its own
+ * buffer (counted in fluxmi_engine_workspace_bytes) and checks on the host that every token admits its own group.  NULL turns masking off.
+ * Masked versus dense is a kind of step graph like guided versus plain: a change re-captures; the table's CONTENTS are device data, so
+ * one set of graphs serves every layout of a prepared shape.  A prepare that re-allocates the workspace clears the table.  Call it after
+ * fluxmi_engine_prepare* and before forward / denoise. */
+int fluxmi_engine_set_attn_groups(fluxmi_engine_t* e, const unsigned* table, void* stream);
 int fluxmi_engine_step_cache_log(fluxmi_engine_t* e, int* n, int* batch, float* ratios, unsigned char* hit, int cap);
 /* Test hook: phases [phase_from, phase_to] of ONE frozen forward on the engine's own buffers, mode 1 (fused) or 2 (unfused, frozen scales):
  *   0 img_in + txt_in on the request buffers "img_s" / "txt_s" (mode 1: the cached "txt_emb" of the last denoise call) + this step's

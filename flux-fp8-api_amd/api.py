@@ -9,7 +9,10 @@ Same two POST endpoints, request fields, defaults and status codes:
              (FluxPipeline.generate), each passed on only when set;
              cache_threshold=None, cache_max_hits=None -- first-block step caching (FluxPipeline.generate), each passed on only when set;
              regions=None ([{prompt, box=[x0, y0, x1, y1] | mask}], regional prompts), regional_tokens=None -- each passed on only when
-             set; a region with both or neither of box / mask, or a box outside 0 <= x0 < x1 <= 1, is a 422}
+             set;
+             inpaint_mask=None (path or base64; white = regenerate: masked-latent inpainting of init_image on any model),
+             inpaint_differential=None (differential diffusion: the mask is a grey change map) -- each passed on only when set;
+             a region with both or neither of box / mask, or a box outside 0 <= x0 < x1 <= 1, is a 422}
              ->  image/jpeg stream of FluxPipeline.generate(**args)                                               (reference api.py:54-86)
   /lora      LoraArgs{scale=1.0, path, name, action="load"|"unload"}  ->  {"status": "success"} | 400 invalid action | 500 with the
              exception text; unload uses `name` when given, else `path`                                         (reference api.py:89-122)
@@ -67,6 +70,8 @@ class GenerateArgs(BaseModel):
     cache_max_hits: Optional[int] = None  # ... and the most cached steps in a row (0 = no bound)
     regions: Optional[List[RegionArgs]] = Field(default=None, min_length=1)  # regional prompts (FluxPipeline.generate)
     regional_tokens: Optional[int] = Field(default=None, gt=0, multiple_of=16)  # T5 rows kept per region prompt (default 128)
+    inpaint_mask: Optional[str] = None  # masked-latent inpainting of init_image on any model: white = regenerate, path or base64
+    inpaint_differential: Optional[bool] = None  # differential diffusion: inpaint_mask is a grey change map (lighter = changed more)
 
 
 app = FastAPI(title="fluxmi")
@@ -80,7 +85,7 @@ def generate(args: GenerateArgs):
     select true classifier-free guidance, `cache_threshold` (+ `cache_max_hits`) first-block step caching.  Without them the call is exactly the reference's."""
     kwargs = args.model_dump()
     for k in ("reference_image", "mask_image", "control_image", "redux_image", "negative_prompt", "true_cfg_scale", "true_cfg_interval",
-              "cache_threshold", "cache_max_hits", "regions", "regional_tokens"):
+              "cache_threshold", "cache_max_hits", "regions", "regional_tokens", "inpaint_mask", "inpaint_differential"):
         if kwargs.get(k) is None:
             kwargs.pop(k, None)
     if "regions" in kwargs:

@@ -589,6 +589,62 @@ __global__ void __launch_bounds__(256) cfg_euler_kernel(u16* __restrict__ img, c
     *(uint4*)(img + img_half + xo) = o;
   }
 }
+// The masked-latent (inpainting) update: the Euler step (CFG: the guided one, cfg_euler_kernel's arithmetic) followed by the blend with the
+// init latent re-noised to the NEXT time.  With i = *step, dt = dts[i], tn = tnext[i], om = one_minus_tnext[i]:
+//   x1 = bf16(x + bf16(dt * v))                                      (CFG: v = bf16(u + bf16(s * bf16(c - u))))
+//   p  = bf16(bf16(tn * noise) + bf16(om * x0))
+//   x' = bf16(bf16(bf16(1 - m) * p) + bf16(m * x1))
+// -- the torch expressions x + dt * v; tn * noise + om * x0; (1 - m) * p + m * x1 on bf16 tensors, one rounding per operation, scalars fp32.
+// thr != nullptr (differential diffusion): m is replaced by (float(m) > thr[i] ? 1 : 0), compared in fp32.  x0 / noise / mask are dense like
+// the prompt half of pred; the indexing is cfg_euler_kernel's (one thread per 16-byte vector numbered along pred; PLAIN: the vector index is
+// the stream offset).  CFG: x is read from the prompt half and x' written to both; reference rows and conditioning channels are never touched.
+template <bool CFG, bool PLAIN>
+__global__ void __launch_bounds__(256) blend_euler_kernel(u16* __restrict__ img, const u16* __restrict__ pred, const u16* __restrict__ x0,
+                                                          const u16* __restrict__ noise, const u16* __restrict__ mask,
+                                                          const float* __restrict__ dts, const float* __restrict__ tnext,
+                                                          const float* __restrict__ one_minus_tnext, const float* __restrict__ thr,
+                                                          const int* __restrict__ step, const float* __restrict__ scale, unsigned n_vec,
+                                                          unsigned vec_per_sample, unsigned vec_per_row, long long img_bstride, int c_in,
+                                                          long long img_half, long long pred_half) {
+  // Every product below is rounded to bf16 BEFORE it is added.  Two of them have two bf16-valued factors (m * x1, (1 - m) * p), which the
+  // compiler may narrow to a bf16 multiply and then, contracting, fuse into the following add as an fma on the unrounded product (it did:
+  // one operand of the last sum lost its rounding).  No contraction in this kernel.
+#pragma clang fp contract(off)
+  const int i = step ? *step : 0;
+  const float dt = dts[i], tn = tnext[i], om = one_minus_tnext[i], sc = CFG ? *scale : 0.f;
+  const bool diff = thr != nullptr;
+  const float th = diff ? thr[i] : 0.f;
+  for (unsigned v = blockIdx.x * blockDim.x + threadIdx.x; v < n_vec; v += gridDim.x * blockDim.x) {
+    long long xo = (long long)v * 8;
+    if (!PLAIN) {
+      const unsigned b = v / vec_per_sample, w = v - b * vec_per_sample, r = w / vec_per_row;
+      xo = b * img_bstride + (long long)r * c_in + (w - r * vec_per_row) * 8;
+    }
+    const long long po = (long long)v * 8;
+    float fx[8], fc[8], fz[8], fn[8], fm[8];
+    unpack8(*(const uint4*)(img + xo), fx);
+    unpack8(*(const uint4*)(pred + po), fc);
+    unpack8(*(const uint4*)(x0 + po), fz);
+    unpack8(*(const uint4*)(noise + po), fn);
+    unpack8(*(const uint4*)(mask + po), fm);
+    if (CFG) {
+      float fu[8];
+      unpack8(*(const uint4*)(pred + pred_half + po), fu);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) fc[j] = rbf(fu[j] + rbf(sc * rbf(fc[j] - fu[j])));
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float x1 = rbf(fx[j] + rbf(dt * fc[j]));
+      const float p = rbf(rbf(tn * fn[j]) + rbf(om * fz[j]));
+      const float m = diff ? (fm[j] > th ? 1.f : 0.f) : fm[j];
+      fx[j] = rbf(rbf(m * x1) + rbf(rbf(1.f - m) * p));
+    }
+    const uint4 o = pack8(fx);
+    *(uint4*)(img + xo) = o;
+    if (CFG) *(uint4*)(img + img_half + xo) = o;
+  }
+}
 // per-step scalars kept on the device so that one captured graph serves every step:
 //   t_vec[b] = bf16(ts[*step]),  then ++*step happens in advance_step_kernel at the end of the step.
 __global__ void set_timestep_kernel(u16* __restrict__ t_vec, const float* __restrict__ ts, const int* __restrict__ step, int B) {
@@ -925,6 +981,33 @@ int fluxmi_k_cfg_euler(void* img, const void* pred, const float* dts, const int*
   else
     hipLaunchKernelGGL(cfg_euler_kernel<false>, dim3(grid_for(n_vec)), dim3(256), 0, s, (u16*)img, (const u16*)pred, dts, step, scale,
                        (unsigned)n_vec, vps, (unsigned)(c_out / 8), img_bstride, c_in, img_half, pred_half);
+  FLUXMI_LAUNCH_CHECK();
+  return 0;
+}
+int fluxmi_k_blend_euler(void* img, const void* pred, const void* x0, const void* noise, const void* mask, const float* dts, const float* tnext,
+                         const float* one_minus_tnext, const float* thr, const int* step, const float* scale, int B, long long img_rows,
+                         long long pred_rows, int c_in, int c_out, hipStream_t s) {
+  FLUXMI_REQUIRE(img && pred && x0 && noise && mask && dts && tnext && one_minus_tnext, "blend_euler: NULL argument");
+  FLUXMI_REQUIRE(B >= 0 && c_out > 0 && c_out % 8 == 0 && c_in % 8 == 0 && c_out <= c_in && pred_rows >= 0 && pred_rows <= img_rows &&
+                     (c_in == c_out || pred_rows == img_rows),
+                 "blend_euler: bad shape B=%d img_rows=%lld pred_rows=%lld c_in=%d c_out=%d (channels multiples of 8, c_out <= c_in, pred_rows <= "
+                 "img_rows, not both shorter and narrower)", B, img_rows, pred_rows, c_in, c_out);
+  const long long n_vec = (long long)B * pred_rows * (c_out / 8);
+  FLUXMI_REQUIRE(n_vec <= 0x7fffffffLL, "blend_euler: %lld vectors exceed the kernel's 32-bit index", n_vec);
+  if (n_vec == 0) return 0;
+  const long long img_bstride = img_rows * c_in, img_half = (long long)B * img_bstride, pred_half = n_vec * 8;
+  const unsigned vps = (unsigned)(pred_rows * (c_out / 8));
+  const bool plain = c_in == c_out && pred_rows == img_rows;
+#define FLUXMI_BLEND_LAUNCH(CFG, PLAIN)                                                                                                       \
+  hipLaunchKernelGGL((blend_euler_kernel<CFG, PLAIN>), dim3(grid_for(n_vec)), dim3(256), 0, s, (u16*)img, (const u16*)pred, (const u16*)x0, \
+                     (const u16*)noise, (const u16*)mask, dts, tnext, one_minus_tnext, thr, step, scale, (unsigned)n_vec, vps,                \
+                     (unsigned)(c_out / 8), img_bstride, c_in, img_half, pred_half)
+  if (scale) {
+    if (plain) FLUXMI_BLEND_LAUNCH(true, true); else FLUXMI_BLEND_LAUNCH(true, false);
+  } else {
+    if (plain) FLUXMI_BLEND_LAUNCH(false, true); else FLUXMI_BLEND_LAUNCH(false, false);
+  }
+#undef FLUXMI_BLEND_LAUNCH
   FLUXMI_LAUNCH_CHECK();
   return 0;
 }

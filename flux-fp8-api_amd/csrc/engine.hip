@@ -50,6 +50,8 @@ struct StepGraphs {
   bool warmed = false;  // one frozen step of this kind, shape and update kind has run eagerly (lazy one-time inits done): the next call may capture at once
   bool cfg = false;     // the update kind (`warmed` and the pieces): guided or plain -- the two never share a graph
   bool masked = false;  // the attention kind: token-group masked or dense launches are baked into the pieces like the update kernel
+  bool blend = false;   // the update kind, continued: the masked-latent blend kernel instead of the (guided) Euler kernel ...
+  bool diff = false;    // ... and its differential form (the threshold table is a launch argument)
   unsigned gen = 0;     // fluxmi_tuning_generation() the pieces were captured under
   void drop() {
     for (hipGraphExec_t& g : exec)
@@ -132,6 +134,15 @@ struct fluxmi_engine {
   int fb_log_B = 0;
   std::vector<float> fb_log_ratio;          // [frozen steps of the last call][B]
   std::vector<unsigned char> fb_log_hit;    // [frozen steps of the last call]
+  // masked-latent inpainting (fluxmi_engine_set_inpaint).  The buffers (x0 | noise | mask, each bf16 [B, Lpred, C_out]: room
+  // for a plain call's B images) are one allocation made at the first masked call of a prepared shape and dropped with the workspace; the
+  // per-step tables ride in the constants block and the pinned schedule staging.  A request without a mask allocates and launches none of it.
+  bool inp_on = false, inp_diff = false;
+  int inp_B = 0;                   // the caller's images the buffers hold
+  std::vector<double> inp_thr;     // differential thresholds, one per step of the following denoise call
+  char* inp_mem = nullptr;
+  size_t inp_bytes = 0;
+  float *d_tnext = nullptr, *d_omt = nullptr, *d_thr = nullptr;
 };
 
 namespace {
@@ -992,6 +1003,8 @@ void free_ws(E* e) {
   e->fb_graphs.drop();
   e->qlut_valid = false;
   if (e->fb_mem) { hipFree(e->fb_mem); e->fb_mem = nullptr; e->fb_bytes = 0; }
+  if (e->inp_mem) { hipFree(e->inp_mem); e->inp_mem = nullptr; e->inp_bytes = 0; }
+  e->inp_on = e->inp_diff = false;
   if (e->ws) { hipFree(e->ws); e->ws = nullptr; }
   e->bufs.clear();
   e->ws_bytes = 0;
@@ -1024,6 +1037,22 @@ int ensure_fb(E* e, hipStream_t s) {
     e->bufs[it.name] = Buf{e->fb_mem + off, it.bytes};
     off += (it.bytes + 255) & ~(size_t)255;
   }
+  return 0;
+}
+
+// the inpainting buffers of the prepared shape, made once a masked request arrives (like ensure_fb)
+int ensure_inp(E* e) {
+  if (e->inp_mem) return 0;
+  const size_t one = ((size_t)e->B * e->Lpred * c_out(e) * 2 + 255) & ~(size_t)255;
+  if (hipMalloc((void**)&e->inp_mem, 3 * one) != hipSuccess) {
+    (void)hipGetLastError();
+    e->inp_mem = nullptr;
+    fluxmi_set_error("engine_set_inpaint: hipMalloc(%zu bytes) failed", 3 * one);
+    return 2;
+  }
+  e->inp_bytes = 3 * one;
+  const char* names[3] = {"inp_x0", "inp_noise", "inp_mask"};
+  for (int i = 0; i < 3; ++i) e->bufs[names[i]] = Buf{e->inp_mem + i * one, one};
   return 0;
 }
 
@@ -1092,7 +1121,8 @@ int fluxmi_engine_create(const fluxmi_model_desc_t* desc, const fluxmi_linear_t*
   size_t off = 0;
   auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
   const size_t o_freqs = carve(128 * 4), o_omega = carve(64 * 4), o_axis = carve(64 * 4), o_ts = carve((MAX_STEPS + 1) * 4),
-               o_dts = carve((MAX_STEPS + 1) * 4), o_step = carve(4), o_step0 = carve(4), o_cfg = carve(4), o_amax = carve((size_t)n_linears * 4),
+               o_dts = carve((MAX_STEPS + 1) * 4), o_step = carve(4), o_step0 = carve(4), o_cfg = carve(4), o_tnext = carve((MAX_STEPS + 1) * 4),
+               o_omt = carve((MAX_STEPS + 1) * 4), o_thr = carve((MAX_STEPS + 1) * 4), o_amax = carve((size_t)n_linears * 4),
                o_gemv = carve(sizeof(FluxmiGemvLayer) * n_mod), o_cm = carve(sizeof(FluxmiCalibLayer) * n_mod);
   if (hipMalloc((void**)&e->consts, off) != hipSuccess) { delete e; fluxmi_set_error("engine_create: hipMalloc(%zu) failed", off); return 2; }
   e->d_freqs = (float*)(e->consts + o_freqs); e->d_omega = (float*)(e->consts + o_omega); e->d_axis = (int*)(e->consts + o_axis);
@@ -1101,9 +1131,10 @@ int fluxmi_engine_create(const fluxmi_model_desc_t* desc, const fluxmi_linear_t*
   e->d_calib_mod = (FluxmiCalibLayer*)(e->consts + o_cm);
   e->d_step0 = (int*)(e->consts + o_step0);
   e->d_cfg = (float*)(e->consts + o_cfg);
+  e->d_tnext = (float*)(e->consts + o_tnext); e->d_omt = (float*)(e->consts + o_omt); e->d_thr = (float*)(e->consts + o_thr);
   hipMemset(e->consts, 0, off);
-  // pinned staging for the schedule + the events (guard of the staging buffer, timing of the frozen steps)
-  if (hipHostMalloc((void**)&e->h_sched, 2 * (MAX_STEPS + 1) * sizeof(float), hipHostMallocDefault) != hipSuccess ||
+  // pinned staging for the schedule (ts | dts | tnext | 1 - tnext | thresholds) + the events (guard of the staging buffer, timing of the frozen steps)
+  if (hipHostMalloc((void**)&e->h_sched, 5 * (MAX_STEPS + 1) * sizeof(float), hipHostMallocDefault) != hipSuccess ||
       hipEventCreateWithFlags(&e->ev_sched, hipEventDisableTiming) != hipSuccess || hipEventCreate(&e->ev_t0) != hipSuccess ||
       hipEventCreate(&e->ev_t1) != hipSuccess) {
     fluxmi_engine_destroy(e);
@@ -1284,9 +1315,13 @@ struct Stepper {
 // allocated until the re-capture replaces them (behind its stream synchronisation).
 static void graphs_stale(fluxmi_engine_t* e, StepGraphs& g, bool cfg) {
   if (g.ok && g.gen != fluxmi_tuning_generation()) g.ok = g.warmed = e->qlut_valid = false;
-  if (g.cfg != cfg || g.masked != e->masked) g.ok = g.warmed = false;  // masked versus dense attention is a kind like guided versus plain
+  const bool diff = e->inp_on && e->inp_diff;
+  // masked versus dense attention is a kind like guided versus plain, and so are the blend update and its differential form
+  if (g.cfg != cfg || g.masked != e->masked || g.blend != e->inp_on || g.diff != diff) g.ok = g.warmed = false;
   g.cfg = cfg;
   g.masked = e->masked;
+  g.blend = e->inp_on;
+  g.diff = diff;
 }
 
 // Captures pieces[0 .. n) into g.exec[0 .. n) on a private non-blocking stream (the caller has synchronised its own).  The only place that
@@ -1474,7 +1509,16 @@ static int denoise_impl(fluxmi_engine_t* e, void* img, const void* txt, const vo
   const int B = e->B, Li = e->Li, Lt = e->Lt, C = e->d.in_channels;
   // the Euler update: the whole stream, or (Kontext) the leading Lpred rows of each sample -- the reference rows never move -- or (Fill /
   // Depth / Canny) the leading C_out channels of every row -- the conditioning channels never move (no row split then: prepare_cond)
+  // With an inpainting state set (fluxmi_engine_set_inpaint) the ONE blend kernel replaces whichever of them it would have been.
+  FLUXMI_REQUIRE(!e->inp_on || e->inp_B == (cfg ? B / 2 : B), "engine_denoise: the inpainting state holds %d images, this call steps %d "
+                 "(fluxmi_engine_set_inpaint takes the caller's images: the prepared batch, half of it for a guided call)", e->inp_B, cfg ? B / 2 : B);
+  FLUXMI_REQUIRE(!e->inp_on || !e->inp_diff || (int)e->inp_thr.size() == n_steps, "engine_denoise: %d differential thresholds for a call of %d "
+                 "steps (fluxmi_engine_set_inpaint takes one per step)", (int)e->inp_thr.size(), n_steps);
   auto euler = [&](hipStream_t st) -> int {
+    if (e->inp_on)
+      return fluxmi_k_blend_euler(buf<u16>(e, "img_s"), buf<u16>(e, "pred_s"), buf<u16>(e, "inp_x0"), buf<u16>(e, "inp_noise"),
+                                  buf<u16>(e, "inp_mask"), e->d_dts, e->d_tnext, e->d_omt, e->inp_diff ? e->d_thr : nullptr, e->d_step,
+                                  cfg ? e->d_cfg : nullptr, cfg ? B / 2 : B, Li, e->Lpred, C, c_out(e), st);
     if (cfg)
       return fluxmi_k_cfg_euler(buf<u16>(e, "img_s"), buf<u16>(e, "pred_s"), e->d_dts, e->d_step, e->d_cfg, B / 2, Li, e->Lpred, C, c_out(e), st);
     if (c_out(e) != C)
@@ -1494,6 +1538,18 @@ static int denoise_impl(fluxmi_engine_t* e, void* img, const void* txt, const vo
   h_dts[n_steps] = 0.f;
   FLUXMI_CHECK_HIP(hipMemcpyAsync(e->d_ts, h_ts, (n_steps + 1) * 4, hipMemcpyHostToDevice, s));
   FLUXMI_CHECK_HIP(hipMemcpyAsync(e->d_dts, h_dts, (n_steps + 1) * 4, hipMemcpyHostToDevice, s));
+  if (e->inp_on) {  // the blend's tables: the NEXT time of every step and its complement (subtracted in double), the thresholds
+    float *h_tn = e->h_sched + 2 * (MAX_STEPS + 1), *h_om = e->h_sched + 3 * (MAX_STEPS + 1), *h_th = e->h_sched + 4 * (MAX_STEPS + 1);
+    for (int i = 0; i < n_steps; ++i) {
+      h_tn[i] = (float)timesteps_host[i + 1];
+      h_om[i] = (float)(1.0 - timesteps_host[i + 1]);
+      h_th[i] = e->inp_diff ? (float)e->inp_thr[i] : 0.f;
+    }
+    h_tn[n_steps] = h_om[n_steps] = h_th[n_steps] = 0.f;
+    FLUXMI_CHECK_HIP(hipMemcpyAsync(e->d_tnext, h_tn, (n_steps + 1) * 4, hipMemcpyHostToDevice, s));
+    FLUXMI_CHECK_HIP(hipMemcpyAsync(e->d_omt, h_om, (n_steps + 1) * 4, hipMemcpyHostToDevice, s));
+    if (e->inp_diff) FLUXMI_CHECK_HIP(hipMemcpyAsync(e->d_thr, h_th, (n_steps + 1) * 4, hipMemcpyHostToDevice, s));
+  }
   FLUXMI_CHECK_HIP(hipEventRecord(e->ev_sched, s));
   e->sched_pending = true;
   u16 *gvec = buf<u16>(e, "gvec"), *tvec = buf<u16>(e, "tvec");
@@ -1580,6 +1636,36 @@ int fluxmi_engine_set_attn_groups(fluxmi_engine_t* e, const unsigned* table, voi
   }
   FLUXMI_CHECK_HIP(hipMemcpyAsync(buf<unsigned>(e, "attn_groups"), table, n * 4, hipMemcpyDeviceToDevice, s));
   e->masked = true;
+  return 0;
+}
+
+// Masked-latent inpainting state of the prepared shape (fluxmi.h): the caller's tensors are copied into the engine's own buffers on `stream`,
+// in order with the denoise call that follows on it.
+int fluxmi_engine_set_inpaint(fluxmi_engine_t* e, const void* x0, const void* noise, const void* mask, int batch, const double* thresholds_host,
+                              int n_thresholds, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  FLUXMI_REQUIRE(e, "engine_set_inpaint: NULL engine");
+  if (!x0) {
+    e->inp_on = e->inp_diff = false;
+    e->inp_thr.clear();
+    return 0;
+  }
+  FLUXMI_REQUIRE(e->ws, "engine_set_inpaint: call fluxmi_engine_prepare first (the tensors are [batch, Li, C_out] of the prepared shape)");
+  FLUXMI_REQUIRE(noise && mask, "engine_set_inpaint: x0, noise and mask go together");
+  FLUXMI_REQUIRE(batch >= 1 && batch <= e->B, "engine_set_inpaint: batch %d outside 1..%d (the prepared batch)", batch, e->B);
+  FLUXMI_REQUIRE(!thresholds_host ? n_thresholds == 0 : (n_thresholds >= 0 && n_thresholds <= MAX_STEPS),
+                 "engine_set_inpaint: n_thresholds %d (0 without a table, at most %d with one)", n_thresholds, MAX_STEPS);
+  for (int i = 0; i < n_thresholds; ++i)
+    FLUXMI_REQUIRE(thresholds_host[i] == thresholds_host[i], "engine_set_inpaint: threshold %d is NaN", i);
+  FLUXMI_TRY(ensure_inp(e));
+  const size_t bytes = (size_t)batch * e->Lpred * c_out(e) * 2;
+  FLUXMI_CHECK_HIP(hipMemcpyAsync(buf<void>(e, "inp_x0"), x0, bytes, hipMemcpyDeviceToDevice, s));
+  FLUXMI_CHECK_HIP(hipMemcpyAsync(buf<void>(e, "inp_noise"), noise, bytes, hipMemcpyDeviceToDevice, s));
+  FLUXMI_CHECK_HIP(hipMemcpyAsync(buf<void>(e, "inp_mask"), mask, bytes, hipMemcpyDeviceToDevice, s));
+  e->inp_on = true;
+  e->inp_diff = thresholds_host != nullptr;
+  e->inp_B = batch;
+  e->inp_thr.assign(thresholds_host, thresholds_host + (thresholds_host ? n_thresholds : 0));
   return 0;
 }
 
@@ -1699,7 +1785,7 @@ int fluxmi_engine_copy_buffer(fluxmi_engine_t* e, const char* name, long long of
 
 int fluxmi_engine_workspace_bytes(fluxmi_engine_t* e, long long* bytes) {
   FLUXMI_REQUIRE(e && bytes, "engine_workspace_bytes: NULL argument");
-  *bytes = (long long)(e->ws_bytes + e->pairs_bytes + e->mods_all_bytes + e->fb_bytes);  // workspace + row-pair weight copies + modulation table + step cache
+  *bytes = (long long)(e->ws_bytes + e->pairs_bytes + e->mods_all_bytes + e->fb_bytes + e->inp_bytes);  // workspace + row-pair weight copies + modulation table + step cache + inpainting
   return 0;
 }
 

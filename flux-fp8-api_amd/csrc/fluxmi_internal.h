@@ -163,6 +163,12 @@ int fluxmi_k_euler_cols(void* img, const void* pred, const float* dts, const int
 // x + bf16(dt * (u + s (c - u))) with one bf16 rounding per operation, s = *scale (device), dt = dts[*step]
 int fluxmi_k_cfg_euler(void* img, const void* pred, const float* dts, const int* step, const float* scale, int B, long long img_rows,
                        long long pred_rows, int c_in, int c_out, hipStream_t s);
+// the masked-latent update: the Euler step (scale != NULL: the guided one, img / pred [2B, ...]) then the blend with x0 re-noised to the next
+// time; x0 / noise / mask dense bf16 [B, pred_rows, c_out], tnext / one_minus_tnext / thr fp32 tables indexed by *step like dts; thr != NULL
+// replaces mask by (float(mask) > thr[*step])
+int fluxmi_k_blend_euler(void* img, const void* pred, const void* x0, const void* noise, const void* mask, const float* dts, const float* tnext,
+                         const float* one_minus_tnext, const float* thr, const int* step, const float* scale, int B, long long img_rows,
+                         long long pred_rows, int c_in, int c_out, hipStream_t s);
 // first-block step cache (elementwise.hip): streaming passes over B samples of n bf16 elements, x side strided, cache side dense
 int fluxmi_k_fb_snapshot(const void* x, long long x_bstride, void* dst, int B, long long n, hipStream_t s);
 int fluxmi_k_fb_commit(const void* x, long long x_bstride, const void* r, void* r_ref, void* h1, int B, long long n, hipStream_t s);

@@ -257,6 +257,14 @@ class FluxPipeline:
                           generator: torch.Generator = None, num_images: int = 1, noise: Optional[torch.Tensor] = None):
         """reference flux_pipeline.py:459-523: noise + schedule; with an init image: VAE-encode it, start the schedule at
         t_idx = int((1 - strength) * num_steps) and blend x = t * noise + (1 - t) * latent."""
+        return self.preprocess_latent_parts(init_image, height, width, num_steps, strength, generator, num_images, noise)[:2]
+
+    @torch.inference_mode()
+    def preprocess_latent_parts(self, init_image=None, height: int = 720, width: int = 1024, num_steps: int = 20, strength: float = 1.0,
+                                generator: torch.Generator = None, num_images: int = 1, noise: Optional[torch.Tensor] = None):
+        """preprocess_latent, with what it blends: -> (x, timesteps, latent, noise).  `latent` = the VAE latent of `init_image` [num_images,
+        16, H/8, W/8] in the flow dtype (None without an init image: one encode per request), `noise` = the pure draw before the blend.
+        Masked-latent inpainting re-blends these two at every step (Flux.denoise)."""
         if init_image is not None:
             if self.ae is None:
                 raise RuntimeError("fluxmi: img2img needs an autoencoder (config.ae_path) -- none is attached")
@@ -272,8 +280,39 @@ class FluxPipeline:
             t_idx = int((1 - strength) * num_steps)
             t = timesteps[t_idx]
             timesteps = timesteps[t_idx:]
-            x = t * x + (1.0 - t) * init_image
-        return x, timesteps
+            pure, x = x, t * x + (1.0 - t) * init_image
+            return x, timesteps, init_image, pure
+        return x, timesteps, None, x
+
+    @torch.inference_mode()
+    def prepare_inpaint_mask(self, inpaint_mask, height: int, width: int, differential: bool = False) -> torch.Tensor:
+        """The mask of a masked-latent inpainting request -> bf16 [1, Li, 64] on the flow device, one value per element of the packed latent
+        (1 = regenerate, 0 = keep; Flux.denoise's `inpaint_mask`):
+          1. `inpaint_mask` in any form load_init_image_if_needed takes (path, base64 / data-URL, PIL image, uint8 array or tensor) is
+             converted to single-channel "L" as PIL does, then float / 255: [1, 1, H, W].  White = regenerate, black = keep;
+          2. brought to (height, width) with img2img's resize_center_crop when its size differs;
+          3. the mean over each 8 x 8 pixel block gives one value per latent pixel: [1, 1, H/8, W/8];
+          4. binarised at >= 0.5 (a latent pixel is regenerated when at least half of its block is white); with `differential` the means
+             are kept as the grey change map of differential diffusion;
+          5. repeated over the 16 latent channels and packed 2 x 2 like the latents."""
+        if isinstance(inpaint_mask, torch.Tensor) and inpaint_mask.dtype != torch.uint8:
+            raise TypeError(f"fluxmi: an inpaint_mask tensor must be uint8 (HW or HWC), got {inpaint_mask.dtype}")
+        if not isinstance(inpaint_mask, (str, np.ndarray, torch.Tensor)) and not hasattr(inpaint_mask, "convert"):
+            raise TypeError(f"fluxmi: inpaint_mask must be a path / base64 string, a PIL image or a uint8 array / tensor, got {type(inpaint_mask).__name__}")
+        m = torch.from_numpy(np.array(self._rgb_uint8(inpaint_mask).convert("L"))).float().div(255.0)[None, None]
+        if tuple(m.shape[-2:]) != (height, width):
+            m = self.resize_center_crop(m, height, width)
+        m = m.reshape(1, 1, height // 8, 8, width // 8, 8).mean(dim=(3, 5))
+        if not differential:
+            m = (m >= 0.5).float()
+        return self.pack(m.repeat(1, 16, 1, 1)).to(device=self.device_flux, dtype=torch.bfloat16).contiguous()
+
+    @staticmethod
+    def inpaint_thresholds(n_steps: int) -> list:
+        """Differential diffusion's schedule over the n steps a request really runs: step i regenerates what is lighter than
+        thr_i = 1 - (i + 1) / n.  White (1) is free from the first step, black (0) is kept to the end (thr_{n-1} = 0, strict compare), a
+        grey g is released for roughly the last fraction g of the steps."""
+        return [1.0 - (i + 1) / n_steps for i in range(n_steps)]
 
     # ---- FLUX.1 Kontext reference image ------------------------------------------------------------------------------------------------
     @torch.inference_mode()
@@ -587,7 +626,7 @@ class FluxPipeline:
                  use_graph: bool = True, reference_image=None, mask_image=None, control_image=None,
                  img_cond: Optional[torch.Tensor] = None, redux_image=None, negative_prompt=None, true_cfg_scale: float = 1.0,
                  true_cfg_interval=(0.0, 1.0), cache_threshold: float = 0.0, cache_max_hits: int = 0, regions=None,
-                 regional_tokens: int = 128):
+                 regional_tokens: int = 128, inpaint_mask=None, inpaint_differential: bool = False):
         """`reference_image` (FLUX.1 Kontext [dev] instruction editing): an image the prompt describes an edit of, in any form `init_image`
         takes; see prepare_kontext_reference.  Composes with `init_image` / `strength` unchanged.
         FLUX.1 Fill [dev] (a model with 320 conditioning channels): `init_image` is the image to inpaint and `mask_image` (white =
@@ -622,7 +661,19 @@ class FluxPipeline:
         reference (its rows count as uncovered), Fill / Depth / Canny, Redux, LoRA, step caching and a negative prompt (the negative
         branch carries the same rows, masked out of every other token's view).  Under a process group the region text rides in the one
         request broadcast; the table is a pure function of the request's arguments, the same on every rank.  Without `regions` nothing
-        changes, the text-encoder calls included."""
+        changes, the text-encoder calls included.
+        `inpaint_mask` (masked-latent inpainting; diffusers' FluxInpaintPipeline, on a Kontext / Depth / Canny model its Kontext / Control
+        counterparts): white = regenerate, black = keep `init_image`, which is required; see prepare_inpaint_mask.  Works with the model
+        that is loaded, no Fill checkpoint needed: after every step the kept part of the latent is replaced by the init latent noised to
+        the step's time (Flux.denoise), so the kept latent pixels of the result are the encoded `init_image` exactly.  A new keyword on
+        purpose: `mask_image` stays FLUX.1 Fill's conditioning; on a Fill model `inpaint_mask` is a hard composite on top of it.
+        `inpaint_differential=True` (differential diffusion): the mask is a grey change map, released step by step (inpaint_thresholds).
+        Composes with strength, `noise=`, num_images, a Kontext reference (noisy rows only), Depth / Canny, Redux, regions, step caching, a
+        negative prompt and LoRA.  Image quality on real FLUX weights is not established here."""
+        if inpaint_mask is None and inpaint_differential:
+            raise ValueError("fluxmi: inpaint_differential needs an inpaint_mask (the change map)")
+        if inpaint_mask is not None and init_image is None:
+            raise ValueError("fluxmi: inpaint_mask needs init_image (the image whose black-masked part is kept)")
         region_grids = None
         if regions is not None:
             if not isinstance(regions, (list, tuple)) or not regions:
@@ -678,7 +729,7 @@ class FluxPipeline:
         num_steps = 4 if self.name == "flux-schnell" else num_steps
         init_image = self.load_init_image_if_needed(init_image) if init_image is not None else None
         fill_image = init_image if kind == "fill" else None
-        if fill_image is not None and strength == 1.0:
+        if fill_image is not None and strength == 1.0 and inpaint_mask is None:
             init_image = None  # the img2img blend is the identity at strength 1: BFL's Fill starts from pure noise, no encode
         height, width = 16 * (height // 16), 16 * (width // 16)
         generator, seed = self.set_seed(seed)
@@ -694,10 +745,20 @@ class FluxPipeline:
                                "until the F8Linear input scales are frozen (FluxPipeline.compile() does)")
         # batch-sharded replicas: every rank denoises its own slice of the batch (rank 0's noise / init latent is
         # what the broadcast below distributes)
-        noise, timesteps = self.preprocess_latent(init_image=init_image, height=height, width=width, num_steps=num_steps, strength=strength,
-                                                  generator=generator, num_images=num_images, noise=noise)
+        inp_mask = self.prepare_inpaint_mask(inpaint_mask, height, width, bool(inpaint_differential)) if inpaint_mask is not None else None
+        if inp_mask is None:
+            noise, timesteps = self.preprocess_latent(init_image=init_image, height=height, width=width, num_steps=num_steps, strength=strength,
+                                                      generator=generator, num_images=num_images, noise=noise)
+        else:
+            noise, timesteps, inp_x0, inp_noise = self.preprocess_latent_parts(init_image=init_image, height=height, width=width, num_steps=num_steps,
+                                                                               strength=strength, generator=generator, num_images=num_images, noise=noise)
         img, img_ids, vec, txt, txt_ids = map(lambda x: x.contiguous(), self.prepare(noise, prompt))
         num_images = img.shape[0]  # a list prompt with num_images == 1 sizes the batch (prepare)
+        inpaint = None
+        if inp_mask is not None:
+            # [x0 | noise | mask] per token, in the flow dtype (the mask's 0 / 1 / block means are what the engine's bf16 copy holds too)
+            rep = lambda t: t.repeat_interleave(num_images // t.shape[0], dim=0) if t.shape[0] != num_images else t
+            inpaint = torch.cat((rep(self.pack(inp_x0)), rep(self.pack(inp_noise)), inp_mask.to(img.dtype).expand(num_images, -1, -1)), -1).contiguous()
         neg_txt = neg_vec = None
         if guided:
             neg_vec, neg_txt = self._prepare_negative(negative_prompt, noise, num_images, txt)
@@ -743,16 +804,19 @@ class FluxPipeline:
         if world > 1:
             if guided:  # the negative embeddings ride in the one broadcast, behind the prompt's
                 txt, vec = torch.cat((txt, neg_txt), 0), torch.cat((vec, neg_vec), 0)
+            inp_kw = {} if inpaint is None else dict(inpaint=inpaint)  # rank 0's [x0 | noise | mask] rides in the same broadcast
             if "img_cond" in cond:
                 # every rank steps rank 0's conditioning (the VAE sample differs between ranks' generators); its bf16 bits ride in the
                 # payload's dtype and come back unchanged
-                txt, vec, img, c = fdist.broadcast_request(txt, vec, img, src=0, extra=cond["img_cond"].view(img.dtype))
+                txt, vec, img, c, *got = fdist.broadcast_request(txt, vec, img, src=0, extra=cond["img_cond"].view(img.dtype), **inp_kw)
                 cond["img_cond"] = c.view(torch.bfloat16)
             elif cond:
                 # every rank steps rank 0's reference latents (the VAE sample differs between ranks' generators on other devices)
-                txt, vec, img, cond["img_cond_seq"] = fdist.broadcast_request(txt, vec, img, src=0, extra=cond["img_cond_seq"])
+                txt, vec, img, cond["img_cond_seq"], *got = fdist.broadcast_request(txt, vec, img, src=0, extra=cond["img_cond_seq"], **inp_kw)
             else:
-                txt, vec, img = fdist.broadcast_request(txt, vec, img, src=0)
+                txt, vec, img, *got = fdist.broadcast_request(txt, vec, img, src=0, **inp_kw)
+            if inpaint is not None:
+                inpaint = got[0]
             if guided:
                 (txt, neg_txt), (vec, neg_vec) = txt.chunk(2, 0), vec.chunk(2, 0)
             # images are sharded, not branches: both branches of an image run on the rank that owns it
@@ -761,6 +825,8 @@ class FluxPipeline:
             if guided:
                 neg_txt, neg_vec = neg_txt[lo:hi].contiguous(), neg_vec[lo:hi].contiguous()
             cond = {k: v[lo:hi].contiguous() for k, v in cond.items()}
+            if inpaint is not None:
+                inpaint = inpaint[lo:hi].contiguous()
         if img.shape[0] == 0:
             # more ranks than images (frozen scales only, see above): this rank has nothing to denoise but still takes part in the gather
             # below (an exception or an early return here would leave the other ranks blocked in the collective)
@@ -776,9 +842,15 @@ class FluxPipeline:
                 tab = [build_region_groups(n_base, regional_tokens, region_grids, n_ref=n_ref, negative=ng) for ng in ((False, True) if guided else (False,))]
                 plain_kw = dict(attn_groups=tab[0][None].to(self.device_flux))
                 neg["attn_groups"] = torch.stack(tab).to(self.device_flux)
+            thr = self.inpaint_thresholds(n) if inpaint is not None and inpaint_differential else None
             latents = img
             for a, b, kw in ((0, g0, plain_kw), (g0, g1, neg), (g1, n, plain_kw)) if g0 < g1 else ((0, n, plain_kw),):
                 if a < b or n == 0:
+                    if inpaint is not None:
+                        x0_, noise_, mask_ = inpaint.chunk(3, -1)
+                        kw = dict(kw, inpaint_x0=x0_, inpaint_noise=noise_, inpaint_mask=mask_)
+                        if thr is not None:
+                            kw["inpaint_thresholds"] = thr[a:b]  # each denoise call gets its slice of the request's table
                     latents = self.model.denoise(latents, img_ids, txt, txt_ids, vec, timesteps[a:b + 1], guidance=guidance, use_graph=use_graph,
                                                  **cond, **kw, **cache)
         if world > 1:

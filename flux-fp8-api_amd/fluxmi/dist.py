@@ -6,7 +6,8 @@ sample i of a request on rank floor(i*world/B)... exactly one exchange before th
                       8 GPUs reproduces the same batch on 1 GPU; ONE flat broadcast (payload <= 34 MB: latency-,
                       not bandwidth-bound, so no ring/bucketing)
                       (+ the packed Kontext reference latents [B,Lc,64] when the request has a reference image, or the
-                      Fill / Depth / Canny conditioning [B,Li,320|64] as bf16 bits in the payload's dtype)
+                      Fill / Depth / Canny conditioning [B,Li,320|64] as bf16 bits in the payload's dtype;
+                      + the inpainting state [x0 | noise | mask] [B,Li,192] of a masked-latent request)
   gather_latents    : final latents [B_local,Li,64] back to the VAE rank
 
 There is no per-step collective: batch elements never interact inside Flux.forward.  During the 12 calibration
@@ -41,13 +42,16 @@ def shard_bounds(batch: int, rank_: int, world: int) -> Tuple[int, int]:
     return lo, lo + base + (1 if rank_ < rem else 0)
 
 
-def broadcast_request(txt: torch.Tensor, vec: torch.Tensor, noise: torch.Tensor, src: int = 0, extra: Optional[torch.Tensor] = None):
+def broadcast_request(txt: torch.Tensor, vec: torch.Tensor, noise: torch.Tensor, src: int = 0, extra: Optional[torch.Tensor] = None,
+                      inpaint: Optional[torch.Tensor] = None):
     """One flat buffer = [txt | vec | noise (| extra)] (same dtype) broadcast from `src`; shapes must already agree on all ranks.
     `extra`: an optional further tensor in the same payload -- the packed FLUX.1 Kontext reference latents [B, Lc, 64] or the FLUX.1 Fill /
-    Depth / Canny conditioning [B, Li, 320 | 64], so that every rank steps the same conditioning.  Returns (txt, vec, noise) or, with `extra`, (txt, vec, noise, extra)."""
+    Depth / Canny conditioning [B, Li, 320 | 64], so that every rank steps the same conditioning.  `inpaint`: a further optional
+    tensor behind it -- the masked-latent inpainting state [x0 | noise | mask] as [B, Li, 3 * 64], sharded like `noise` by the caller; absent,
+    the buffer is today's, byte for byte.  Returns (txt, vec, noise), then `extra` and `inpaint` in this order, each only when given."""
+    parts = [txt, vec, noise] + [p for p in (extra, inpaint) if p is not None]
     if not is_dist():
-        return (txt, vec, noise) if extra is None else (txt, vec, noise, extra)
-    parts = [txt, vec, noise] + ([] if extra is None else [extra])
+        return tuple(parts)
     flat = torch.cat([p.reshape(-1) for p in parts])
     td.broadcast(flat, src=src)
     out, off = [], 0

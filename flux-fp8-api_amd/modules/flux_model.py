@@ -342,6 +342,44 @@ class Flux(nn.Module):
         g = g.to(device).expand(B, L).contiguous()
         _lib.call("fluxmi_engine_set_attn_groups", self._engine, ops._p(g), ops._stream())
 
+    def _check_inpaint(self, img, x0, noise, mask, thresholds, n_steps: int):
+        """the masked-latent inpainting arguments of a denoise call, validated before any device work -> None (no mask) or (x0, noise, mask
+        expanded over the batch, thresholds as a list or None)"""
+        given = [t is not None for t in (x0, noise, mask)]
+        if not any(given):
+            if thresholds is not None:
+                raise ValueError("inpaint_thresholds without inpaint_x0 / inpaint_noise / inpaint_mask")
+            return None
+        if not all(given):
+            raise ValueError("inpaint_x0, inpaint_noise and inpaint_mask go together (all three or none)")
+        want = (img.shape[0], img.shape[1], self.out_channels)
+        for name, t in (("inpaint_x0", x0), ("inpaint_noise", noise)):
+            if not isinstance(t, torch.Tensor) or tuple(t.shape) != want:
+                raise ValueError(f"{name} {tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}: expected a tensor {want} (the "
+                                 f"stepped channels of img's noisy tokens)")
+        if not isinstance(mask, torch.Tensor) or mask.ndim != 3 or mask.shape[0] not in (1, want[0]) or tuple(mask.shape[1:]) != want[1:]:
+            raise ValueError(f"inpaint_mask {tuple(mask.shape) if isinstance(mask, torch.Tensor) else type(mask).__name__}: expected a tensor "
+                             f"[1 or {want[0]}, {want[1]}, {want[2]}]")
+        if thresholds is not None:
+            thresholds = [float(t) for t in thresholds]
+            if len(thresholds) != n_steps or any(math.isnan(t) for t in thresholds):
+                raise ValueError(f"inpaint_thresholds: {len(thresholds)} values for {n_steps} steps (one per step of this call, none NaN)")
+        return x0, noise, mask.expand(want[0], -1, -1), thresholds
+
+    def _set_inpaint(self, inpaint, device):
+        """after _prepare, under the lock: the masked-latent inpainting state of this call (the engine copies the tensors), or None = off.  Set
+        on every call, so nothing is left over from an earlier request."""
+        if inpaint is None:
+            _lib.call("fluxmi_engine_set_inpaint", self._engine, None, None, None, 0, None, 0, ops._stream())
+            return
+        x0, noise, mask, thr = inpaint
+        x0, noise, mask = (t.to(device=device, dtype=torch.bfloat16).contiguous() for t in (x0, noise, mask))
+        table = (C.c_double * len(thr))(*thr) if thr is not None else None
+        if thr is not None and not thr:
+            table = (C.c_double * 1)()  # a non-NULL table of zero entries: a differential call of zero steps
+        _lib.call("fluxmi_engine_set_inpaint", self._engine, ops._p(x0), ops._p(noise), ops._p(mask), x0.shape[0], table,
+                  len(thr) if thr is not None else 0, ops._stream())
+
     @staticmethod
     def _with_reference(img, img_ids, img_cond_seq, img_cond_seq_ids):
         """FLUX.1 Kontext: the reference tokens ride behind the noisy tokens of each sample -> (stream, stream ids, Lc).  Both None: unchanged."""
@@ -529,7 +567,8 @@ class Flux(nn.Module):
                 guidance: float = 3.5, use_graph: bool = True, img_cond_seq: Tensor | None = None,
                 img_cond_seq_ids: Tensor | None = None, img_cond: Tensor | None = None, neg_txt: Tensor | None = None,
                 neg_y: Tensor | None = None, cfg_scale: float = 1.0, cache_threshold: float = 0.0, cache_max_hits: int = 0,
-                attn_groups: Tensor | None = None) -> Tensor:
+                attn_groups: Tensor | None = None, inpaint_x0: Tensor | None = None, inpaint_noise: Tensor | None = None,
+                inpaint_mask: Tensor | None = None, inpaint_thresholds=None) -> Tensor:
         """The Euler loop of FluxPipeline.generate (reference flux_pipeline.py:619-651) run natively: calibrating
         steps unfused, every later step one replay of a captured hipGraph.  Returns the final latent tokens.
         FLUX.1 Kontext: with `img_cond_seq` / `img_cond_seq_ids` the reference tokens join every step's forward and are never stepped; the
@@ -545,7 +584,15 @@ class Flux(nn.Module):
         running them; at most `cache_max_hits` such steps in a row (0 = no bound).  0 (the default) = off: the call is today's, bit for bit.
         Every call starts with an empty cache; `step_cache_log()` tells what the last call did.
         `attn_groups`: a token-group attention mask for every attention of every step (Flux.forward), int32 [1 or B, Lt + Li + Lc]; a guided
-        call takes [2 or 2B, ...]: the tables of the prompt branches, then those of the negative branches.  None = dense, today's call."""
+        call takes [2 or 2B, ...]: the tables of the prompt branches, then those of the negative branches.  None = dense, today's call.
+        Masked-latent inpainting: `inpaint_x0` (the init image's latent tokens) and `inpaint_noise` (the request's pure noise draw), both
+        [B, Li, out_channels], and `inpaint_mask` [1 or B, Li, out_channels] (1 = regenerate, 0 = keep), all three or none.  Every step's
+        update -- calibrating, replayed, cached, guided -- is then followed, in the same kernel (csrc/elementwise.hip, blend_euler_kernel), by
+            p = t_next * noise + (1.0 - t_next) * x0;  x' = (1 - m) * p + m * x1
+        on bf16 tensors, t_next = timesteps[i + 1]: with a schedule that ends at 0 the kept elements of the result are x0 bit for bit.
+        `inpaint_thresholds` (differential diffusion): one float per step of THIS call; step i blends with the binary mask
+        float32(m) > float32(thresholds[i]) instead of m.  The caller's tensors are not modified."""
+        inpaint = self._check_inpaint(img, inpaint_x0, inpaint_noise, inpaint_mask, inpaint_thresholds, len(timesteps) - 1)
         cache_threshold, cache_max_hits = float(cache_threshold), int(cache_max_hits)
         if not (math.isfinite(cache_threshold) and cache_threshold >= 0.0) or cache_max_hits < 0:
             raise ValueError(f"cache_threshold {cache_threshold} must be finite and >= 0 (0 = off), cache_max_hits {cache_max_hits} >= 0 (0 = no bound)")
@@ -588,6 +635,9 @@ class Flux(nn.Module):
                 if attn_groups is not None:
                     halves = attn_groups.chunk(2, 0) if guided else (attn_groups,)
                     cond["attn_groups"] = torch.cat([h if h.shape[0] == 1 else pick(h) for h in halves], 0)
+                if inpaint is not None:
+                    cond.update(inpaint_x0=pick(inpaint[0]), inpaint_noise=pick(inpaint[1]), inpaint_mask=pick(inpaint[2]),
+                                inpaint_thresholds=inpaint[3])
                 o = self.denoise(pick(img), pick(img_ids), pick(txt), pick(txt_ids), pick(y), timesteps, guidance=guidance, use_graph=use_graph,
                                  cache_threshold=cache_threshold, cache_max_hits=cache_max_hits, **cond)
                 outs.append(o[:per - pad])
@@ -609,6 +659,7 @@ class Flux(nn.Module):
             t_io = C.c_int(trial if trial is not None else 0)
             ts = (C.c_double * len(timesteps))(*[float(t) for t in timesteps])
             _lib.call("fluxmi_engine_set_step_cache", self._engine, cache_threshold, cache_max_hits)
+            self._set_inpaint(inpaint, img.device)
             if guided:
                 _lib.call("fluxmi_engine_denoise_cfg", self._engine, ops._p(img), ops._p(txt), ops._p(y), float(guidance), float(cfg_scale), ts,
                           len(timesteps) - 1, C.byref(t_io), int(use_graph), ops._stream())

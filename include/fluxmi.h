@@ -387,6 +387,18 @@ int fluxmi_euler(void* img, const void* pred, const float* dts, const int* step,
  * not both: those rows / channels are neither read nor written.  dts, step, scale are DEVICE pointers; c_in, c_out multiples of 8. */
 int fluxmi_cfg_euler(void* img, const void* pred, const float* dts, const int* step, const float* scale, int B, long long img_rows,
                      long long pred_rows, int c_in, int c_out, void* stream);
+/* The masked-latent (inpainting) update: the Euler step, then the blend with the init latent re-noised to the NEXT time.  img, pred, dts,
+ * step, B, img_rows, pred_rows, c_in, c_out as for fluxmi_cfg_euler; scale == NULL: the unguided update on img [B, ...] / pred [B, ...], else
+ * the guided one on [2B, ...] (x read from the prompt half, x' written to both).  x0, noise, mask: dense bf16 [B, pred_rows, c_out];
+ * tnext, one_minus_tnext (and thr): DEVICE fp32 tables indexed by *step like dts.  Per predicted element, one bf16 rounding per operation:
+ *   x1 = x + dt * v                (guided: v = u + s * (c - u))
+ *   p  = tnext * noise + one_minus_tnext * x0
+ *   x' = (1 - m) * p + m * x1      (m = 1: regenerate, m = 0: keep)
+ * i.e. those torch expressions on bf16 tensors.  thr == NULL: m = mask (a linear blend).  Else (differential diffusion) m = 1 where
+ * float(mask) > thr[*step], compared in fp32, and 0 elsewhere.  Reference rows and conditioning channels are neither read nor written. */
+int fluxmi_blend_euler(void* img, const void* pred, const void* x0, const void* noise, const void* mask, const float* dts, const float* tnext,
+                       const float* one_minus_tnext, const float* thr, const int* step, const float* scale, int B, long long img_rows,
+                       long long pred_rows, int c_in, int c_out, void* stream);
 
 /* ---- first-block step cache: the streaming passes --------------------------------------
  * B samples of n bf16 elements each (n = cached rows x hidden, n %% 8 == 0).  The `x` side is the residual stream: the pointer is the first
@@ -541,6 +553,20 @@ int fluxmi_engine_set_step_cache(fluxmi_engine_t* e, float threshold, int max_co
  * fluxmi_engine_prepare* and before forward / denoise. */
 int fluxmi_engine_set_attn_groups(fluxmi_engine_t* e, const unsigned* table, void* stream);
 int fluxmi_engine_step_cache_log(fluxmi_engine_t* e, int* n, int* batch, float* ratios, unsigned char* hit, int cap);
+/* Masked-latent inpainting (and differential diffusion) for the following fluxmi_engine_denoise / _denoise_cfg calls on the PREPARED shape:
+ * every update of those calls -- calibrating, graph-replayed, both tails of a step-cached step, guided -- is fluxmi_blend_euler instead of
+ * the Euler / guided Euler kernel (as many launches per step as without a mask), with tnext[i] = (float)timesteps[i + 1] and
+ * one_minus_tnext[i] = (float)(1.0 - timesteps[i + 1]) built from the call's schedule.  x0, noise, mask: device bf16 [batch, Li, C_out] for the
+ * caller's `batch` images (the prepared B of a plain call, B / 2 of a guided one: checked by the denoise call), copied into the engine's own
+ * buffers "inp_x0", "inp_noise", "inp_mask" (allocated at the first masked call of a prepared shape, dropped with the workspace, counted
+ * in fluxmi_engine_workspace_bytes), so the caller's tensors are free again when this returns and a captured graph never holds their
+ * pointers.  thresholds_host == NULL: the linear blend with the mask as given.  Else differential diffusion: n_thresholds doubles, one per
+ * step of the denoise call -- a call with another n_steps is refused -- and step i blends with (float(mask) > (float)thresholds_host[i]).
+ * x0 == NULL switches the feature off (the other arguments are ignored); a prepare that re-allocates the workspace does too.  Blend on / off
+ * and differential on / off are kinds of step graph like guided versus plain: requests of different kinds alternating on one shape re-capture,
+ * never replay each other's graph.  A request without a mask allocates and launches nothing of this.  Call it after fluxmi_engine_prepare*. */
+int fluxmi_engine_set_inpaint(fluxmi_engine_t* e, const void* x0, const void* noise, const void* mask, int batch, const double* thresholds_host,
+                              int n_thresholds, void* stream);
 /* Test hook: phases [phase_from, phase_to] of ONE frozen forward on the engine's own buffers, mode 1 (fused) or 2 (unfused, frozen scales):
  *   0 img_in + txt_in on the request buffers "img_s" / "txt_s" (mode 1: the cached "txt_emb" of the last denoise call) + this step's
  *     modulation vectors out of the step-ahead table the last denoise call left (step = the request's step index, written to the device-side

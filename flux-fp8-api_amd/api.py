@@ -72,6 +72,11 @@ class GenerateArgs(BaseModel):
     regional_tokens: Optional[int] = Field(default=None, gt=0, multiple_of=16)  # T5 rows kept per region prompt (default 128)
     inpaint_mask: Optional[str] = None  # masked-latent inpainting of init_image on any model: white = regenerate, path or base64
     inpaint_differential: Optional[bool] = None  # differential diffusion: inpaint_mask is a grey change map (lighter = changed more)
+    controlnet_image: Optional[str] = None  # FLUX ControlNet (config controlnet_path): the edge map / depth map / pose to follow, path or base64
+    controlnet_conditioning_scale: Optional[float] = None  # ... the strength of its residuals (default 1.0)
+    control_mode: Optional[int] = Field(default=None, ge=0)  # ... the control mode of a Union net
+    control_guidance_start: Optional[float] = Field(default=None, ge=0.0, le=1.0)  # ... the fraction of the steps at which it switches on
+    control_guidance_end: Optional[float] = Field(default=None, ge=0.0, le=1.0)  # ... and off (diffusers' names)
 
 
 app = FastAPI(title="fluxmi")
@@ -82,10 +87,12 @@ def generate(args: GenerateArgs):
     """JPEG bytes of one image; `init_image` + `strength` select img2img (flux_pipeline.py:399-420,459-523 of the reference);
     `reference_image` selects a FLUX.1 Kontext edit of that image, `mask_image` a FLUX.1 Fill inpainting of `init_image`, `control_image` a
     FLUX.1 Depth / Canny generation, `redux_image` a FLUX.1 Redux image prompt; `negative_prompt` + `true_cfg_scale` (+ `true_cfg_interval`)
-    select true classifier-free guidance, `cache_threshold` (+ `cache_max_hits`) first-block step caching.  Without them the call is exactly the reference's."""
+    select true classifier-free guidance, `cache_threshold` (+ `cache_max_hits`) first-block step caching, `controlnet_image` (+ `controlnet_conditioning_scale`,
+    `control_mode`, `control_guidance_start` / `_end`) a FLUX ControlNet.  Without them the call is exactly the reference's."""
     kwargs = args.model_dump()
     for k in ("reference_image", "mask_image", "control_image", "redux_image", "negative_prompt", "true_cfg_scale", "true_cfg_interval",
-              "cache_threshold", "cache_max_hits", "regions", "regional_tokens", "inpaint_mask", "inpaint_differential"):
+              "cache_threshold", "cache_max_hits", "regions", "regional_tokens", "inpaint_mask", "inpaint_differential", "controlnet_image",
+              "controlnet_conditioning_scale", "control_mode", "control_guidance_start", "control_guidance_end"):
         if kwargs.get(k) is None:
             kwargs.pop(k, None)
     if "regions" in kwargs:

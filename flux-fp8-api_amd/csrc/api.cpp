@@ -251,5 +251,8 @@ int fluxmi_fb_store(const void* x, long long x_bstride, const void* h1, void* R,
 int fluxmi_fb_apply(void* x, long long x_bstride, const void* h1, long long h1_bstride, const void* R, int B, long long n, void* stream) {
   return fluxmi_k_fb_apply(x, x_bstride, h1, h1_bstride, R, B, n, (hipStream_t)stream);
 }
+int fluxmi_add_scaled(void* x, long long x_bstride, const void* r, long long r_bstride, const float* scale, int B, long long n, void* stream) {
+  return fluxmi_k_add_scaled(x, x_bstride, r, r_bstride, scale, B, n, (hipStream_t)stream);
+}
 
 }  // extern "C"

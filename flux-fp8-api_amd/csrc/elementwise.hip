@@ -1226,3 +1226,59 @@ int fluxmi_k_fb_apply(void* x, long long x_bstride, const void* h1, long long h1
   FLUXMI_LAUNCH_CHECK();
   return 0;
 }
+
+// ---------------------------------------------------------------------------------------------
+// ControlNet residual hand-over:  x[b, j] = bf16(x[b, j] + bf16(r[b, j] * *s))  over B samples of n bf16 elements with
+// separate batch strides -- the torch expression  x + r * s  on bf16 tensors with s a Python float.  s is DEVICE data (fp32, never rounded to
+// bf16): one captured graph serves every conditioning scale.  Workgroup c of a sample owns its elements [c * 16384, (c + 1) * 16384): 16-byte
+// accesses when both pointers and both strides allow them (the engine's case), with the n % 8 tail elements on the last workgroup; any other
+// alignment runs the same arithmetic element by element.
+// ---------------------------------------------------------------------------------------------
+namespace {
+template <bool VEC>
+__global__ void __launch_bounds__(256) add_scaled_kernel(u16* x, long long x_bstride, const u16* __restrict__ r, long long r_bstride,
+                                                         const float* __restrict__ sp, long long n) {
+  // the product is rounded to bf16 BEFORE it is added (the contract of fluxmi_add_scaled): no contraction in this kernel
+#pragma clang fp contract(off)
+  const float s = *sp;
+  u16* xb = x + (long long)blockIdx.y * x_bstride;
+  const u16* rb = r + (long long)blockIdx.y * r_bstride;
+  if (VEC) {
+    const long long n_vec = n >> 3;
+#pragma unroll
+    for (unsigned j = 0; j < FB_VPT; ++j) {
+      const long long v = (long long)blockIdx.x * FB_CHUNK + j * 256 + threadIdx.x;
+      if (v < n_vec) {
+        float fx[8], fr[8];
+        unpack8(*(const uint4*)(xb + v * 8), fx);
+        unpack8(*(const uint4*)(rb + v * 8), fr);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) fx[k] += rbf(fr[k] * s);
+        *(uint4*)(xb + v * 8) = pack8(fx);
+      }
+    }
+    const long long t = n_vec * 8 + threadIdx.x;  // the n % 8 elements behind the last whole vector
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x < 8 && t < n) xb[t] = f2bf(bf2f(xb[t]) + rbf(bf2f(rb[t]) * s));
+  } else {
+    for (unsigned j = 0; j < FB_VPT * 8; ++j) {
+      const long long i = ((long long)blockIdx.x * FB_CHUNK * 8) + j * 256 + threadIdx.x;
+      if (i < n) xb[i] = f2bf(bf2f(xb[i]) + rbf(bf2f(rb[i]) * s));
+    }
+  }
+}
+}  // namespace
+
+int fluxmi_k_add_scaled(void* x, long long x_bstride, const void* r, long long r_bstride, const float* s_dev, int B, long long n, hipStream_t s) {
+  FLUXMI_REQUIRE(x && r && s_dev, "add_scaled: NULL argument");
+  FLUXMI_REQUIRE(B >= 0 && B <= 65535 && n >= 0 && n <= 0x7fffffffLL * 8 && (B <= 1 || (x_bstride >= n && r_bstride >= n)),
+                 "add_scaled: bad shape B=%d n=%lld x_bstride=%lld r_bstride=%lld (strides >= n)", B, n, x_bstride, r_bstride);
+  if (!B || !n) return 0;
+  const unsigned chunks = (unsigned)((n + FB_CHUNK * 8 - 1) / (FB_CHUNK * 8));
+  const bool vec = ((uintptr_t)x % 16 == 0) && ((uintptr_t)r % 16 == 0) && (B == 1 || (x_bstride % 8 == 0 && r_bstride % 8 == 0));
+  if (vec)
+    hipLaunchKernelGGL(add_scaled_kernel<true>, dim3(chunks, B), dim3(256), 0, s, (u16*)x, x_bstride, (const u16*)r, r_bstride, s_dev, n);
+  else
+    hipLaunchKernelGGL(add_scaled_kernel<false>, dim3(chunks, B), dim3(256), 0, s, (u16*)x, x_bstride, (const u16*)r, r_bstride, s_dev, n);
+  FLUXMI_LAUNCH_CHECK();
+  return 0;
+}

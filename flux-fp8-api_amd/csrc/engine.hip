@@ -27,6 +27,7 @@
 #include <string.h>
 #include <math.h>
 #include <algorithm>
+#include <atomic>
 #include <functional>
 #include <map>
 #include <string>
@@ -53,6 +54,8 @@ struct StepGraphs {
   bool blend = false;   // the update kind, continued: the masked-latent blend kernel instead of the (guided) Euler kernel ...
   bool diff = false;    // ... and its differential form (the threshold table is a launch argument)
   unsigned gen = 0;     // fluxmi_tuning_generation() the pieces were captured under
+  const void* cn = nullptr;  // the attached ControlNet whose launches (and workspace pointers) are baked into the pieces, or none ...
+  unsigned long long cn_gen = 0;  // ... and the generation of its workspace / weight binding: process-wide unique, so a net created at a freed net's address never matches
   void drop() {
     for (hipGraphExec_t& g : exec)
       if (g) { hipGraphExecDestroy(g); g = nullptr; }
@@ -143,6 +146,22 @@ struct fluxmi_engine {
   char* inp_mem = nullptr;
   size_t inp_bytes = 0;
   float *d_tnext = nullptr, *d_omt = nullptr, *d_thr = nullptr;
+  // ControlNet (fluxmi_controlnet_create / fluxmi_engine_attach_controlnet).  A net is an engine of its own kind
+  // (is_cn): no final layer, the controlnet_* projections behind the trunk's linears, the residuals of a forward in its workspace buffer
+  // "cn_res" [Nd + Ns][B, Li, H].  The main engine holds the attached net (cn) and the conditioning scale (d_cn_scale, device data).
+  bool is_cn = false;
+  int i_cn_x = -1, i_cn_d0 = -1, i_cn_s0 = -1;   // controlnet_x_embedder, controlnet_blocks[0], controlnet_single_blocks[0]
+  const void* cn_mode_table = nullptr;           // controlnet_mode_embedder.weight bf16 [cn_num_mode, H] (Union), or none
+  int cn_num_mode = 0;
+  int txt_extra = 0;               // 1: row 0 of the text stream is the mode embedding (Lt = the request's text rows + 1)
+  int cn_trial = 0;                // the net's own calibration counter
+  // a number no other engine state of this process ever had (next_generation): renewed at create, when the workspace is dropped and when the
+  // weights are re-bound.  Step graphs that baked a net in are keyed on it, never on the net's address alone (the allocator reuses addresses)
+  unsigned long long ws_gen = 0;
+  fluxmi_engine* cn = nullptr;        // main: the attached net
+  fluxmi_engine* cn_owner = nullptr;  // net: the main engine it is attached to
+  int cn_batch = 0;                // main: the caller's images the attached cond holds
+  float* d_cn_scale = nullptr;
 };
 
 namespace {
@@ -181,6 +200,12 @@ void set_pf(fluxmi_engine* e, std::initializer_list<int> lins, int wgs);
 const void* pairs_of(fluxmi_engine* e, int li);
 
 int lin_count(const fluxmi_model_desc_t& d) { return 6 + (d.guidance_embed ? 2 : 0) + d.depth * 10 + d.depth_single * 3 + 2; }
+// a ControlNet: the trunk without its final layer + controlnet_x_embedder + one projection per block
+unsigned long long next_generation() {
+  static std::atomic<unsigned long long> g{0};
+  return ++g;
+}
+int cn_lin_count(const fluxmi_model_desc_t& d) { return lin_count(d) - 2 + 1 + d.depth + d.depth_single; }
 
 // double-block linear slots / single-block linear slots
 enum { D_IMG_MOD = 0, D_IMG_QKV, D_IMG_PROJ, D_IMG_MLP0, D_IMG_MLP2, D_TXT_MOD, D_TXT_QKV, D_TXT_PROJ, D_TXT_MLP0, D_TXT_MLP2 };
@@ -399,7 +424,7 @@ int build_gemv_table(E* e, hipStream_t s) {
     add(DLi(e, i, D_TXT_MOD), (long long)i * 12 * H + 6 * H);
   }
   for (int i = 0; i < e->d.depth_single; ++i) add(SLi(e, i, S_MOD), (long long)e->d.depth * 12 * H + (long long)i * 3 * H);
-  add(e->i_final_mod, (long long)e->d.depth * 12 * H + (long long)e->d.depth_single * 3 * H);
+  if (e->i_final_mod >= 0) add(e->i_final_mod, (long long)e->d.depth * 12 * H + (long long)e->d.depth_single * 3 * H);
   int blk = 0, maxK = 0;
   for (auto& g : e->h_gemv) {
     g.blk_start = blk;
@@ -492,15 +517,25 @@ int compute_vec_and_mods(E* e, const u16* t_vec, const u16* g_vec, const u16* y,
 }
 
 int embed_txt(E* e, const u16* txt, bool calib, int trial, u16* dst, long long dst_bstride, hipStream_t s) {
-  const int H = e->d.hidden, B = e->B, Lt = e->Lt, C = e->d.ctx_in;
+  // (a Union ControlNet: row 0 of the text stream is the mode embedding, put_mode_row; txt_in's rows follow it)
+  const int H = e->d.hidden, B = e->B, Lt = e->Lt - e->txt_extra, C = e->d.ctx_in;
   const fluxmi_linear_t& l = e->lin[e->i_txt_in];
   uint8_t* in8 = buf<uint8_t>(e, "in8");
+  dst += (long long)e->txt_extra * H;
   FLUXMI_TRY(stage_input(e, e->i_txt_in, calib, trial, txt, C, 0, in8, C, 0, 1, B * Lt, C, s));
   std::vector<FluxmiGemmGroup> gs;
   for (int b = 0; b < B; ++b)
     gs.push_back(mk_group(l, l.kind ? (const void*)(in8 + (long long)b * Lt * C) : (const void*)(txt + (long long)b * Lt * C), C,
                           dst + b * dst_bstride, H, Lt));
   return run_gemm_fixed_cfg(gs, H, C, l.kind, l.in_fmt, FLUXMI_EPI_BF16, s);
+}
+
+// Union ControlNet: the request's row of controlnet_mode_embedder (copied into "cn_mode_row" at attach) in front of every sample's text rows
+int put_mode_row(E* e, u16* dst, long long dst_bstride, hipStream_t s) {
+  if (!e->txt_extra) return 0;
+  for (int b = 0; b < e->B; ++b)
+    FLUXMI_CHECK_HIP(hipMemcpyAsync(dst + b * dst_bstride, buf<u16>(e, "cn_mode_row"), (size_t)e->d.hidden * 2, hipMemcpyDeviceToDevice, s));
+  return 0;
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -886,7 +921,27 @@ int final_layer(E* e, u16* pred, int s0, int s1, hipStream_t s) {
 }
 
 // the channels the model predicts: final_layer.linear's N (== in_channels but for channel-conditioned models, see fluxmi_engine_create)
-int c_out(const E* e) { return e->lin[e->i_final_lin].N; }
+int c_out(const E* e) { return e->is_cn ? e->d.in_channels : e->lin[e->i_final_lin].N; }
+
+// ControlNet: r_k = bf16(proj(x_img)) of the image rows of the stream after block k (slot k < Nd: double, Nd + k: single) -> "cn_res"[slot]
+int cn_project(E* e, int li, int slot, hipStream_t s) {
+  const int H = e->d.hidden, B = e->B, Li = e->Li;
+  const long long XB = (long long)e->L * H;
+  u16* x = buf<u16>(e, "x") + (long long)e->Lt * H;
+  u16* res = buf<u16>(e, "cn_res") + (long long)slot * B * Li * H;
+  const fluxmi_linear_t& l = e->lin[li];
+  std::vector<FluxmiGemmGroup> gs;
+  for (int b = 0; b < B; ++b) gs.push_back(mk_group(l, x + b * XB, H, res + (long long)b * Li * H, H, Li));
+  return run_gemm(gs, H, H, 0, 0, FLUXMI_EPI_BF16, s);
+}
+// main engine with a net attached: x_img = bf16(x_img + bf16(r_slot * scale)) after a controlled block
+int cn_add(E* e, int slot, hipStream_t s) {
+  const E* n = e->cn;
+  const int H = e->d.hidden;
+  const long long one = (long long)e->Li * H;
+  return fluxmi_k_add_scaled(buf<u16>(e, "x") + (long long)e->Lt * H, (long long)e->L * H, buf<u16>(const_cast<E*>(n), "cn_res") + slot * e->B * one, one,
+                             e->d_cn_scale, e->B, one, s);
+}
 
 // Every block linear (the modulation linears apart) is F8Linear: what the fused path needs.  Otherwise *blk is the first block that has a
 // bf16 one: double block *blk, or single block *blk - depth.
@@ -938,12 +993,16 @@ int forward_impl(E* e, const u16* img, const u16* txt, const u16* y, const u16* 
       gs.push_back(mk_group(l, l.kind ? (const void*)(in8 + (long long)b * Li * C) : (const void*)(img + (long long)b * Li * C), C,
                             x + b * XB + (long long)Lt * H, H, Li));
     FLUXMI_TRY(run_gemm_fixed_cfg(gs, H, C, l.kind, l.in_fmt, FLUXMI_EPI_BF16, s));
+    // ControlNet: bf16(img_in(img) + controlnet_x_embedder(cond)), the second term projected once per request ("cn_cproj")
+    if (e->is_cn)
+      FLUXMI_TRY(fluxmi_k_fb_apply(x + (long long)Lt * H, XB, x + (long long)Lt * H, XB, buf<u16>(e, "cn_cproj"), B, (long long)Li * H, s));
   }
   if (p0 <= PH_EMBED) {
     if (txt_cached) {
       FLUXMI_CHECK_HIP(hipMemcpy2DAsync(x, XB * 2, buf<u16>(e, "txt_emb"), (size_t)Lt * H * 2, (size_t)Lt * H * 2, B, hipMemcpyDeviceToDevice, s));
     } else {
       FLUXMI_TRY(embed_txt(e, txt, calib, trial, x, XB, s));
+      FLUXMI_TRY(put_mode_row(e, x, XB, s));
     }
     if (e->mods_table) {
       FLUXMI_TRY(fluxmi_k_select_step(e->mods_all, e->d_step, e->d_step0, mod, (long long)B * MC * 2, s));
@@ -954,18 +1013,32 @@ int forward_impl(E* e, const u16* img, const u16* txt, const u16* y, const u16* 
 
   for (int i = 0; i < e->d.depth; ++i) {
     const int ph = i == 0 ? PH_BLOCK0 : PH_BLOCKS;
-    if (ph >= p0 && ph <= p1) FLUXMI_TRY(double_block(e, ctx, i, mode, trial, 0, DOUBLE_STAGES - 1, s));
+    if (ph >= p0 && ph <= p1) {
+      FLUXMI_TRY(double_block(e, ctx, i, mode, trial, 0, DOUBLE_STAGES - 1, s));
+      if (e->is_cn) FLUXMI_TRY(cn_project(e, e->i_cn_d0 + i, i, s));
+      if (e->cn) FLUXMI_TRY(cn_add(e, i / ((e->d.depth + e->cn->d.depth - 1) / e->cn->d.depth), s));
+    }
   }
   if (p0 <= PH_BLOCKS && p1 >= PH_BLOCKS)
-    for (int i = 0; i < e->d.depth_single; ++i) FLUXMI_TRY(single_block(e, ctx, i, mode, trial, 0, SINGLE_STAGES - 1, s));
+    for (int i = 0; i < e->d.depth_single; ++i) {
+      FLUXMI_TRY(single_block(e, ctx, i, mode, trial, 0, SINGLE_STAGES - 1, s));
+      if (e->is_cn) FLUXMI_TRY(cn_project(e, e->i_cn_s0 + i, e->d.depth + i, s));
+      if (e->cn && e->cn->d.depth_single > 0)
+        FLUXMI_TRY(cn_add(e, e->cn->d.depth + i / ((e->d.depth_single + e->cn->d.depth_single - 1) / e->cn->d.depth_single), s));
+    }
 
   // ---- final layer                                                                flux_model.py:499-503, 714-715
   if (p1 >= PH_FINAL) FLUXMI_TRY(final_layer(e, pred, 0, 1, s));
   return 0;
 }
 
+int cn_forward(E* e, const u16* img, const u16* txt, const u16* y, const u16* t_vec, const u16* g_vec, int mode, int trial, bool table,
+               hipStream_t s);
 // Phases [p0, p1] of a frozen step's forward: the engine's static request buffers, the modulations from the step-ahead table
 int frozen_forward(E* e, int mode, const u16* g_arg, int p0, int p1, hipStream_t s) {
+  if (e->cn && p0 <= PH_EMBED)
+    FLUXMI_TRY(cn_forward(e, buf<u16>(e, "img_s"), buf<u16>(e, "txt_s"), buf<u16>(e, "y_s"), buf<u16>(e, "tvec"), buf<u16>(e, "gvec"),
+                          all_block_linears_f8(e->cn) ? 1 : 2, 0, true, s));
   e->mods_table = true;
   const int rc = forward_impl(e, buf<u16>(e, "img_s"), buf<u16>(e, "txt_s"), buf<u16>(e, "y_s"), buf<u16>(e, "tvec"), g_arg, buf<u16>(e, "pred_s"),
                               mode, 0, mode == 1, s, p0, p1);
@@ -981,15 +1054,16 @@ bool needs_splitk(E* e) {
 // the engine's split-K scratch for every launch of this thread while an engine entry point runs
 // ... and its scratch for attention's balanced grid; a prefetch left pending by an error return between set_pf and the launch that
 // would have consumed it is dropped here, on entry and on exit (it points into weights the caller may free afterwards)
+void scope_set(E* e) {
+  auto it = e->bufs.find("splitk");
+  fluxmi_set_splitk_scratch(it != e->bufs.end() && it->second.n >= FLUXMI_SPLITK_WS_BYTES ? (float*)it->second.p : nullptr);
+  auto ia = e->bufs.find("attn_part");
+  fluxmi_set_attn_scratch(ia != e->bufs.end() && ia->second.n >= FLUXMI_ATTN_SPLIT_WS_BYTES ? ia->second.p : nullptr);
+  fluxmi_set_prefetch(nullptr);
+  fluxmi_gemm_set_batch(e->B);
+}
 struct SplitkScope {
-  explicit SplitkScope(E* e) {
-    auto it = e->bufs.find("splitk");
-    fluxmi_set_splitk_scratch(it != e->bufs.end() && it->second.n >= FLUXMI_SPLITK_WS_BYTES ? (float*)it->second.p : nullptr);
-    auto ia = e->bufs.find("attn_part");
-    fluxmi_set_attn_scratch(ia != e->bufs.end() && ia->second.n >= FLUXMI_ATTN_SPLIT_WS_BYTES ? ia->second.p : nullptr);
-    fluxmi_set_prefetch(nullptr);
-    fluxmi_gemm_set_batch(e->B);
-  }
+  explicit SplitkScope(E* e) { scope_set(e); }
   ~SplitkScope() {
     fluxmi_gemm_set_batch(1);
     fluxmi_set_splitk_scratch(nullptr);
@@ -998,7 +1072,29 @@ struct SplitkScope {
   }
 };
 
+// One forward of the ControlNet attached to `e` (no final layer: phases 0 .. 2) on the buffers given -- the residuals land in the net's
+// "cn_res" -- under the net's own scratch scope; e's scope is restored behind it.  table: modulations from the net's step-ahead table.
+int cn_forward(E* e, const u16* img, const u16* txt, const u16* y, const u16* t_vec, const u16* g_vec, int mode, int trial, bool table,
+               hipStream_t s) {
+  E* n = e->cn;
+  scope_set(n);
+  n->mods_table = table;
+  const int rc = forward_impl(n, img, txt, y, t_vec, n->d.guidance_embed ? g_vec : nullptr, nullptr, mode, trial, table && mode == 1, s, PH_EMBED, PH_BLOCKS);
+  n->mods_table = false;
+  scope_set(e);
+  return rc;
+}
+bool any_f8(const E* e) {
+  for (auto& l : e->lin)
+    if (l.kind != 0) return true;
+  return false;
+}
+
 void free_ws(E* e) {
+  e->ws_gen = next_generation();
+  // an attachment belongs to a prepared shape: dropped with the workspace of either side
+  if (e->cn) { e->cn->cn_owner = nullptr; e->cn = nullptr; }
+  if (e->cn_owner) { e->cn_owner->cn = nullptr; e->cn_owner = nullptr; }
   e->step_graphs.drop();
   e->fb_graphs.drop();
   e->qlut_valid = false;
@@ -1085,24 +1181,52 @@ extern "C" {
 
 int fluxmi_engine_num_linears(const fluxmi_model_desc_t* desc) { return desc ? lin_count(*desc) : -1; }
 
+static int create_impl(const fluxmi_model_desc_t* desc, const fluxmi_linear_t* linears, int n_linears, const void* const* norm_scales,
+                       int n_norm_scales, bool cn, const void* mode_table, int num_mode, fluxmi_engine_t** out);
 int fluxmi_engine_create(const fluxmi_model_desc_t* desc, const fluxmi_linear_t* linears, int n_linears,
                          const void* const* norm_scales, int n_norm_scales, fluxmi_engine_t** out) {
+  return create_impl(desc, linears, n_linears, norm_scales, n_norm_scales, false, nullptr, 0, out);
+}
+
+int fluxmi_controlnet_num_linears(const fluxmi_model_desc_t* desc) { return desc ? cn_lin_count(*desc) : -1; }
+
+int fluxmi_controlnet_create(const fluxmi_model_desc_t* desc, const fluxmi_linear_t* linears, int n_linears, const void* const* norm_scales,
+                             int n_norm_scales, const void* mode_table, int num_mode, fluxmi_engine_t** out) {
+  FLUXMI_REQUIRE(desc && linears, "controlnet_create: NULL argument");
+  FLUXMI_REQUIRE(desc->depth >= 1 && desc->depth_single >= 0, "controlnet_create: a ControlNet has at least one double block (got %d + %d)",
+                 desc->depth, desc->depth_single);
+  FLUXMI_REQUIRE((mode_table != nullptr) == (num_mode > 0) && num_mode >= 0, "controlnet_create: mode_table and num_mode (%d) go together", num_mode);
+  FLUXMI_REQUIRE(n_linears == cn_lin_count(*desc), "controlnet_create: expected %d linears, got %d", cn_lin_count(*desc), n_linears);
+  const int first = lin_count(*desc) - 2, H = desc->hidden;
+  for (int i = first; i < n_linears; ++i) {
+    const int K = i == first ? desc->in_channels : H;
+    FLUXMI_REQUIRE(linears[i].kind == 0 && linears[i].weight && linears[i].N == H && linears[i].K == K,
+                   "controlnet_create: linear %d (controlnet_%s) must be a bf16 nn.Linear [%d, %d] (kind %d, [%d, %d])", i,
+                   i == first ? "x_embedder" : "blocks / controlnet_single_blocks", H, K, linears[i].kind, linears[i].N, linears[i].K);
+  }
+  return create_impl(desc, linears, n_linears, norm_scales, n_norm_scales, true, mode_table, num_mode, out);
+}
+
+static int create_impl(const fluxmi_model_desc_t* desc, const fluxmi_linear_t* linears, int n_linears, const void* const* norm_scales,
+                       int n_norm_scales, bool cn, const void* mode_table, int num_mode, fluxmi_engine_t** out) {
   FLUXMI_REQUIRE(desc && linears && norm_scales && out, "engine_create: NULL argument");
   fluxmi_log_tuning("engine_create");  // the kernel choices this engine will run with (FLUXMI_LOG=1)
   FLUXMI_REQUIRE(desc->hidden == desc->heads * 128, "engine_create: head_dim must be 128 (hidden %d, heads %d)", desc->hidden, desc->heads);
   // the LayerNorm + modulate kernels hold a row (wave per row) or four fp32 vectors of it (streaming) on chip: refused here, not mid-step
   FLUXMI_REQUIRE(desc->hidden <= 4096, "engine_create: hidden %d > 4096, the widest row the LayerNorm kernels take", desc->hidden);
   FLUXMI_REQUIRE(desc->axes_dim[0] + desc->axes_dim[1] + desc->axes_dim[2] == 128, "engine_create: sum(axes_dim) must be 128");
-  FLUXMI_REQUIRE(n_linears == lin_count(*desc), "engine_create: expected %d linears, got %d", lin_count(*desc), n_linears);
+  FLUXMI_REQUIRE(n_linears == (cn ? cn_lin_count(*desc) : lin_count(*desc)), "engine_create: expected %d linears, got %d",
+                 cn ? cn_lin_count(*desc) : lin_count(*desc), n_linears);
   FLUXMI_REQUIRE(n_norm_scales == desc->depth * 4 + desc->depth_single * 2, "engine_create: expected %d norm scales, got %d",
                  desc->depth * 4 + desc->depth_single * 2, n_norm_scales);
   FLUXMI_REQUIRE(desc->num_trials >= 1 && desc->num_trials <= 64, "engine_create: num_trials out of range");
   // C_in = img_in's width, C_out = final_layer.linear's N (the last linear): FLUX.1 Fill / Depth / Canny append C_in - C_out step-invariant
   // conditioning channels to every token; the 16-byte Euler kernels need both widths in whole 8-channel vectors
-  const int C_in = desc->in_channels, C_out = linears[n_linears - 1].N;
+  const int C_in = desc->in_channels, C_out = cn ? desc->in_channels : linears[n_linears - 1].N;  // (a ControlNet predicts nothing)
   FLUXMI_REQUIRE(C_out >= 8 && C_out <= C_in && C_out % 8 == 0 && C_in % 8 == 0,
                  "engine_create: in_channels %d / final_layer out_channels %d: need out <= in, both multiples of 8", C_in, C_out);
   E* e = new E();
+  e->ws_gen = next_generation();
   e->d = *desc;
   e->lin.assign(linears, linears + n_linears);
   e->norm.assign(norm_scales, norm_scales + n_norm_scales);
@@ -1113,15 +1237,26 @@ int fluxmi_engine_create(const fluxmi_model_desc_t* desc, const fluxmi_linear_t*
   e->i_txt_in = i++;
   e->i_double0 = i; i += desc->depth * 10;
   e->i_single0 = i; i += desc->depth_single * 3;
-  e->i_final_mod = i++; e->i_final_lin = i++;
+  if (cn) {
+    e->is_cn = true;
+    e->i_final_mod = e->i_final_lin = -1;
+    e->i_cn_x = i++;
+    e->i_cn_d0 = i; i += desc->depth;
+    e->i_cn_s0 = i; i += desc->depth_single;
+    e->cn_mode_table = mode_table;
+    e->cn_num_mode = num_mode;
+    e->txt_extra = mode_table ? 1 : 0;
+  } else {
+    e->i_final_mod = i++; e->i_final_lin = i++;
+  }
   const int H = desc->hidden;
-  e->mod_cols = (long long)desc->depth * 12 * H + (long long)desc->depth_single * 3 * H + 2 * H;
+  e->mod_cols = (long long)desc->depth * 12 * H + (long long)desc->depth_single * 3 * H + (cn ? 0 : 2 * H);
   // constants block
   const int n_mod = desc->depth * 2 + desc->depth_single + 1;
   size_t off = 0;
   auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
   const size_t o_freqs = carve(128 * 4), o_omega = carve(64 * 4), o_axis = carve(64 * 4), o_ts = carve((MAX_STEPS + 1) * 4),
-               o_dts = carve((MAX_STEPS + 1) * 4), o_step = carve(4), o_step0 = carve(4), o_cfg = carve(4), o_tnext = carve((MAX_STEPS + 1) * 4),
+               o_dts = carve((MAX_STEPS + 1) * 4), o_step = carve(4), o_step0 = carve(4), o_cfg = carve(4), o_cns = carve(4), o_tnext = carve((MAX_STEPS + 1) * 4),
                o_omt = carve((MAX_STEPS + 1) * 4), o_thr = carve((MAX_STEPS + 1) * 4), o_amax = carve((size_t)n_linears * 4),
                o_gemv = carve(sizeof(FluxmiGemvLayer) * n_mod), o_cm = carve(sizeof(FluxmiCalibLayer) * n_mod);
   if (hipMalloc((void**)&e->consts, off) != hipSuccess) { delete e; fluxmi_set_error("engine_create: hipMalloc(%zu) failed", off); return 2; }
@@ -1131,6 +1266,7 @@ int fluxmi_engine_create(const fluxmi_model_desc_t* desc, const fluxmi_linear_t*
   e->d_calib_mod = (FluxmiCalibLayer*)(e->consts + o_cm);
   e->d_step0 = (int*)(e->consts + o_step0);
   e->d_cfg = (float*)(e->consts + o_cfg);
+  e->d_cn_scale = (float*)(e->consts + o_cns);
   e->d_tnext = (float*)(e->consts + o_tnext); e->d_omt = (float*)(e->consts + o_omt); e->d_thr = (float*)(e->consts + o_thr);
   hipMemset(e->consts, 0, off);
   // pinned staging for the schedule (ts | dts | tnext | 1 - tnext | thresholds) + the events (guard of the staging buffer, timing of the frozen steps)
@@ -1147,7 +1283,7 @@ int fluxmi_engine_create(const fluxmi_model_desc_t* desc, const fluxmi_linear_t*
 
 int fluxmi_engine_destroy(fluxmi_engine_t* e) {
   if (!e) return 0;
-  free_ws(e);
+  free_ws(e);  // (drops an attachment on either side)
   if (e->mods_all) hipFree(e->mods_all);
   if (e->pairs) hipFree(e->pairs);
   if (e->consts) hipFree(e->consts);
@@ -1164,6 +1300,7 @@ int fluxmi_engine_destroy(fluxmi_engine_t* e) {
 int fluxmi_engine_rebind(fluxmi_engine_t* e, const fluxmi_linear_t* linears, int n_linears) {
   FLUXMI_REQUIRE(e && linears && n_linears == (int)e->lin.size(), "engine_rebind: bad arguments");
   e->lin.assign(linears, linears + n_linears);
+  e->ws_gen = next_generation();  // a main engine's graphs that baked this net's weights in go stale
   e->step_graphs.drop();
   e->fb_graphs.drop();
   e->txt_emb_valid = false;
@@ -1201,11 +1338,19 @@ int fluxmi_engine_prepare(fluxmi_engine_t* e, int B, int Li, int Lt, const void*
 // Li_pred noisy rows + Lc reference rows per sample (FLUX.1 Kontext): the engine's image stream is Li = Li_pred + Lc rows long.  The split is
 // part of the workspace key: the same (B, Li, Lt) with another split re-allocates, which drops the captured step graph (its final layer and
 // Euler update are sized by the split).
+static int prepare_impl(fluxmi_engine_t* e, int B, int Li_pred, int Lc, int Lt, const void* img_ids, const void* txt_ids, const fluxmi_engine_t* ids_from,
+                        hipStream_t s);
 int fluxmi_engine_prepare_cond(fluxmi_engine_t* e, int B, int Li_pred, int Lc, int Lt, const void* img_ids, const void* txt_ids, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
+  FLUXMI_REQUIRE(e && !e->is_cn, "engine_prepare: a ControlNet engine is prepared by fluxmi_engine_attach_controlnet");
+  FLUXMI_REQUIRE(img_ids && (Lt == 0 || txt_ids), "engine_prepare: NULL ids");
+  return prepare_impl(e, B, Li_pred, Lc, Lt, img_ids, txt_ids, nullptr, (hipStream_t)stream);
+}
+// ids_from: (a ControlNet) the main engine whose position ids this shape shares -- its text rows (behind a copy of the first of them for the
+// mode row of a Union net: Lt counts that row), then its image rows
+static int prepare_impl(fluxmi_engine_t* e, int B, int Li_pred, int Lc, int Lt, const void* img_ids, const void* txt_ids, const fluxmi_engine_t* ids_from,
+                        hipStream_t s) {
   FLUXMI_REQUIRE(e && B >= 1 && B <= FLUXMI_ENGINE_MAX_BATCH && Li_pred >= 1 && Lc >= 0 && Lt >= 0,
                  "engine_prepare: bad shape B=%d Li=%d Lc=%d Lt=%d (B must be 1..%d)", B, Li_pred, Lc, Lt, FLUXMI_ENGINE_MAX_BATCH);
-  FLUXMI_REQUIRE(img_ids && (Lt == 0 || txt_ids), "engine_prepare: NULL ids");
   FLUXMI_REQUIRE(Lc == 0 || c_out(e) == e->d.in_channels,
                  "engine_prepare: a reference-image row split (Lc = %d) needs in_channels == out_channels (this model: %d / %d, channel "
                  "conditioning); no released model takes both", Lc, e->d.in_channels, c_out(e));
@@ -1222,7 +1367,7 @@ int fluxmi_engine_prepare_cond(fluxmi_engine_t* e, int B, int Li_pred, int Lc, i
     std::vector<Item> items = {
         {"x", BL * H * 2}, {"a8", BL * H}, {"attn8", BL * H}, {"qkv", BL * 3 * H * 2}, {"Q", BL * H * 2}, {"K", BL * H * 2},
         {"VT", (size_t)B * H * Lp * 2}, {"h8", BL * Hm}, {"cat8", BL * (H + Hm)}, {"pe", BL * 64 * 2 * 2},
-        {"mod", (size_t)B * e->mod_cols * 2}, {"fin", (size_t)B * Li_pred * H * 2},
+        {"mod", (size_t)B * e->mod_cols * 2}, {"fin", e->is_cn ? 256 : (size_t)B * Li_pred * H * 2},
         // unfused-path temporaries
         {"abf", BL * H * 2}, {"attnbf", BL * H * 2}, {"hbf", BL * Hm * 2}, {"catbf", BL * (H + Hm) * 2}, {"lin1", BL * (3 * H + Hm) * 2},
         {"in8", in8},
@@ -1244,6 +1389,12 @@ int fluxmi_engine_prepare_cond(fluxmi_engine_t* e, int B, int Li_pred, int Lc, i
         // token-group mask descriptors [B, L] (fluxmi_engine_set_attn_groups)
         {"attn_groups", BL * 4},
     };
+    if (e->is_cn) {  // the request's cond, controlnet_x_embedder(cond), the residuals of a forward, the request's mode embedding
+      items.push_back({"cn_cond", (size_t)B * Li * e->d.in_channels * 2});
+      items.push_back({"cn_cproj", (size_t)B * Li * H * 2});
+      items.push_back({"cn_res", (size_t)(e->d.depth + e->d.depth_single) * B * Li * H * 2});
+      items.push_back({"cn_mode_row", (size_t)H * 2});
+    }
     size_t total = 0;
     for (auto& it : items) total += (it.bytes + 255) & ~(size_t)255;
     if (hipMalloc((void**)&e->ws, total) != hipSuccess) {
@@ -1271,17 +1422,34 @@ int fluxmi_engine_prepare_cond(fluxmi_engine_t* e, int B, int Li_pred, int Lc, i
   }
   // ids = cat(txt_ids, img_ids) per batch element; pe table                              flux_model.py:701-702
   u16* ids = buf<u16>(e, "ids");
-  if (Lt > 0)
-    FLUXMI_CHECK_HIP(hipMemcpy2DAsync(ids, (size_t)L * 6, txt_ids, (size_t)Lt * 6, (size_t)Lt * 6, B, hipMemcpyDeviceToDevice, s));
-  FLUXMI_CHECK_HIP(hipMemcpy2DAsync(ids + (size_t)Lt * 3, (size_t)L * 6, img_ids, (size_t)Li * 6, (size_t)Li * 6, B, hipMemcpyDeviceToDevice, s));
+  if (ids_from) {
+    const u16* src = buf<u16>(const_cast<fluxmi_engine_t*>(ids_from), "ids");
+    const size_t sp = (size_t)ids_from->L * 6, X = (size_t)e->txt_extra;
+    if (X) FLUXMI_CHECK_HIP(hipMemcpy2DAsync(ids, (size_t)L * 6, src, sp, 6, B, hipMemcpyDeviceToDevice, s));
+    FLUXMI_CHECK_HIP(hipMemcpy2DAsync(ids + X * 3, (size_t)L * 6, src, sp, sp, B, hipMemcpyDeviceToDevice, s));
+  } else {
+    if (Lt > 0)
+      FLUXMI_CHECK_HIP(hipMemcpy2DAsync(ids, (size_t)L * 6, txt_ids, (size_t)Lt * 6, (size_t)Lt * 6, B, hipMemcpyDeviceToDevice, s));
+    FLUXMI_CHECK_HIP(hipMemcpy2DAsync(ids + (size_t)Lt * 3, (size_t)L * 6, img_ids, (size_t)Li * 6, (size_t)Li * 6, B, hipMemcpyDeviceToDevice, s));
+  }
   FLUXMI_TRY(fluxmi_k_rope_table(ids, e->d_omega, e->d_axis, buf<u16>(e, "pe"), (long long)B * L, 3, 64, s));
   e->txt_emb_valid = false;
+  return 0;
+}
+
+// what an attached ControlNet excludes, checked again by every call that runs it (the state may have been set after the attach)
+static int cn_usable(fluxmi_engine_t* e) {
+  FLUXMI_REQUIRE(!e->masked, "ControlNet: a token-group attention table is set on this engine (regional prompts do not combine with a ControlNet)");
+  FLUXMI_REQUIRE(!(e->fb_threshold > 0.f), "ControlNet: step caching is on (it does not combine with a ControlNet)");
+  FLUXMI_REQUIRE(e->cn->ws && e->cn->B == e->B && e->cn->Li == e->Li && e->cn->Lt == e->Lt + e->cn->txt_extra,
+                 "ControlNet: the attached net is not prepared for this engine's shape (attach it after fluxmi_engine_prepare)");
   return 0;
 }
 
 int fluxmi_engine_forward(fluxmi_engine_t* e, const void* img, const void* txt, const void* y, const void* timesteps,
                           const void* guidance, void* pred, int mode, int trial_index, void* stream) {
   FLUXMI_REQUIRE(e && e->ws, "engine_forward: call fluxmi_engine_prepare first");
+  FLUXMI_REQUIRE(!e->is_cn, "engine_forward: a ControlNet engine runs attached to a main engine (fluxmi_engine_attach_controlnet)");
   FLUXMI_REQUIRE(img && txt && y && timesteps && pred, "engine_forward: NULL tensor");
   FLUXMI_REQUIRE(mode >= 0 && mode <= 2, "engine_forward: bad mode %d", mode);
   if (mode == 0) FLUXMI_REQUIRE(trial_index >= 0 && trial_index <= e->d.num_trials, "engine_forward: trial_index %d out of range", trial_index);
@@ -1289,6 +1457,17 @@ int fluxmi_engine_forward(fluxmi_engine_t* e, const void* img, const void* txt, 
   if (mode == 1) FLUXMI_TRY(build_qluts(e, (hipStream_t)stream));
   SplitkScope splitk(e);
   FLUXMI_TRY(ensure_pairs(e, (hipStream_t)stream));
+  if (fluxmi_engine_t* n = e->cn) {  // the attached ControlNet first: calibrating on its own counter, else frozen like the main model
+    FLUXMI_TRY(cn_usable(e));
+    const bool ncal = any_f8(n) && n->cn_trial <= n->d.num_trials;
+    const int nmode = ncal ? 0 : (mode != 2 && all_block_linears_f8(n) ? 1 : 2);
+    FLUXMI_TRY(ensure_pairs(n, (hipStream_t)stream));
+    if (nmode == 0) n->qlut_valid = false;
+    if (nmode == 1) FLUXMI_TRY(build_qluts(n, (hipStream_t)stream));
+    FLUXMI_TRY(cn_forward(e, (const u16*)img, (const u16*)txt, (const u16*)y, (const u16*)timesteps, (const u16*)guidance, nmode, n->cn_trial, false,
+                          (hipStream_t)stream));
+    if (ncal) ++n->cn_trial;
+  }
   return forward_impl(e, (const u16*)img, (const u16*)txt, (const u16*)y, (const u16*)timesteps, (const u16*)guidance, (u16*)pred,
                       mode, trial_index, false, (hipStream_t)stream);
 }
@@ -1318,6 +1497,10 @@ static void graphs_stale(fluxmi_engine_t* e, StepGraphs& g, bool cfg) {
   const bool diff = e->inp_on && e->inp_diff;
   // masked versus dense attention is a kind like guided versus plain, and so are the blend update and its differential form
   if (g.cfg != cfg || g.masked != e->masked || g.blend != e->inp_on || g.diff != diff) g.ok = g.warmed = false;
+  // ... and so is the attached ControlNet: its launches, weights and workspace pointers are baked into the pieces
+  if (g.cn != e->cn || (e->cn && g.cn_gen != e->cn->ws_gen)) g.ok = g.warmed = false;
+  g.cn = e->cn;
+  g.cn_gen = e->cn ? e->cn->ws_gen : 0;
   g.cfg = cfg;
   g.masked = e->masked;
   g.blend = e->inp_on;
@@ -1361,6 +1544,12 @@ static int frozen_steps(fluxmi_engine_t* e, const Stepper& st, int mode, bool cf
     {
       Range r("step-ahead modulation table");
       FLUXMI_TRY(precompute_mods(e, step, win_end, g_arg, buf<u16>(e, "y_s"), s));
+      if (e->cn) {  // the attached ControlNet's own table, from the same schedule, guidance and y
+        scope_set(e->cn);
+        const int rc = precompute_mods(e->cn, step, win_end, e->cn->d.guidance_embed ? buf<u16>(e, "gvec") : nullptr, buf<u16>(e, "y_s"), s);
+        scope_set(e);
+        FLUXMI_TRY(rc);
+      }
     }
     graphs_stale(e, g, cfg);
     if (use_graph && !g.ok) {
@@ -1499,6 +1688,7 @@ static int denoise_impl(fluxmi_engine_t* e, void* img, const void* txt, const vo
                         const double* timesteps_host, int n_steps, int* trial_index_inout, int use_graph, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   FLUXMI_REQUIRE(e && e->ws, "engine_denoise: call fluxmi_engine_prepare first");
+  FLUXMI_REQUIRE(!e->is_cn, "engine_denoise: a ControlNet engine runs attached to a main engine (fluxmi_engine_attach_controlnet)");
   FLUXMI_REQUIRE(!cfg || e->B % 2 == 0, "engine_denoise_cfg: the prepared batch (%d) must be even: prompt branches first, then the negative "
                  "branches of the same images (2B <= %d)", e->B, FLUXMI_ENGINE_MAX_BATCH);
   FLUXMI_REQUIRE(img && txt && y && timesteps_host && trial_index_inout, "engine_denoise: NULL argument");
@@ -1526,8 +1716,29 @@ static int denoise_impl(fluxmi_engine_t* e, void* img, const void* txt, const vo
     if (e->Lpred == Li) return fluxmi_k_euler(buf<u16>(e, "img_s"), buf<u16>(e, "pred_s"), e->d_dts, e->d_step, (long long)B * Li * C, st);
     return fluxmi_k_euler_rows(buf<u16>(e, "img_s"), buf<u16>(e, "pred_s"), e->d_dts, e->d_step, B, Li, e->Lpred, C, st);
   };
-  bool any_f8 = false;
-  for (auto& l : e->lin) any_f8 |= (l.kind != 0);
+  const bool main_f8 = any_f8(e);
+  // the attached ControlNet: its own scratch / weight copies, the request's schedule and step counter shared with the main engine
+  fluxmi_engine_t* const cn = e->cn;
+  if (cn) {
+    FLUXMI_TRY(cn_usable(e));
+    FLUXMI_REQUIRE(e->cn_batch == (cfg ? e->B / 2 : e->B), "engine_denoise: the attached ControlNet's cond holds %d images, this call steps %d",
+                   e->cn_batch, cfg ? e->B / 2 : e->B);
+    FLUXMI_TRY(ensure_pairs(cn, s));
+  }
+  // for the length of this call the net reads the request's schedule and step counter from the main engine's constants; its own pointers
+  // are back on every way out
+  struct SharedSchedule {
+    fluxmi_engine_t* n;
+    float* ts;
+    int* step;
+    SharedSchedule(fluxmi_engine_t* n_, fluxmi_engine_t* m) : n(n_), ts(n_ ? n_->d_ts : nullptr), step(n_ ? n_->d_step : nullptr) {
+      if (n) { n->d_ts = m->d_ts; n->d_step = m->d_step; }
+    }
+    ~SharedSchedule() {
+      if (n) { n->d_ts = ts; n->d_step = step; }
+    }
+  } shared_schedule(cn, e);
+  const bool cn_f8 = cn && any_f8(cn);
 
   // schedule -> device through the engine's pinned staging buffer.  The buffer may still be the source of the previous request's
   // (long finished) copy: wait on that copy's event, never on the stream.
@@ -1573,13 +1784,26 @@ static int denoise_impl(fluxmi_engine_t* e, void* img, const void* txt, const vo
   // -- calibrating steps: the reference's first num_trials+1 calls of every F8Linear ----------------------
   {
     Range r("calibrating steps (unfused)");
-    while (step < n_steps && any_f8 && trial <= e->d.num_trials) {
+    // (with a ControlNet attached: while EITHER net has trials left -- that net in mode 0, the other in its frozen mode, eagerly)
+    auto main_cal = [&]() { return main_f8 && trial <= e->d.num_trials; };
+    auto cn_cal = [&]() { return cn_f8 && cn->cn_trial <= cn->d.num_trials; };
+    while (step < n_steps && (main_cal() || cn_cal())) {
       FLUXMI_TRY(fluxmi_k_set_timestep(tvec, e->d_ts, e->d_step, B, s));
-      e->qlut_valid = false;
-      FLUXMI_TRY(forward_impl(e, img_s, txt_s, y_s, tvec, g_arg, pred_s, 0, trial, false, s));
+      if (cn) {
+        const int nmode = cn_cal() ? 0 : (all_block_linears_f8(cn) ? 1 : 2);
+        if (nmode == 0) cn->qlut_valid = false;
+        if (nmode == 1) FLUXMI_TRY(build_qluts(cn, s));
+        FLUXMI_TRY(cn_forward(e, img_s, txt_s, y_s, tvec, gvec, nmode, cn->cn_trial, false, s));
+        if (nmode == 0) ++cn->cn_trial;
+      }
+      const int mmode = main_cal() ? 0 : (all_block_linears_f8(e) ? 1 : 2);
+      if (mmode == 0) e->qlut_valid = false;
+      if (mmode == 1) FLUXMI_TRY(build_qluts(e, s));
+      FLUXMI_TRY(forward_impl(e, img_s, txt_s, y_s, tvec, g_arg, pred_s, mmode, trial, false, s));
       FLUXMI_TRY(euler(s));
       FLUXMI_TRY(fluxmi_k_advance_step(e->d_step, s));
-      ++trial; ++step;
+      if (mmode == 0) ++trial;
+      ++step;
     }
   }
   // -- frozen steps -------------------------------------------------------------------------------------------
@@ -1592,6 +1816,16 @@ static int denoise_impl(fluxmi_engine_t* e, void* img, const void* txt, const vo
       FLUXMI_TRY(embed_txt(e, txt_s, false, 0, buf<u16>(e, "txt_emb"), (long long)Lt * e->d.hidden, s));
       e->txt_emb_valid = true;
       FLUXMI_TRY(build_qluts(e, s));
+    }
+    if (cn && all_block_linears_f8(cn)) {  // the net's embedded text (behind its mode row) and quantising tables, once per request
+      scope_set(cn);
+      u16* te = buf<u16>(cn, "txt_emb");
+      int rc = embed_txt(cn, txt_s, false, 0, te, (long long)cn->Lt * cn->d.hidden, s);
+      if (!rc) rc = put_mode_row(cn, te, (long long)cn->Lt * cn->d.hidden, s);
+      if (!rc) rc = build_qluts(cn, s);
+      scope_set(e);
+      FLUXMI_TRY(rc);
+      cn->txt_emb_valid = true;
     }
     // plain, or with first-block step caching: the same steps cut into head / body / skip pieces with a host decision in between
     int first_timed = n_steps;  // the first step behind ev_t0, which the loop records: ev_t0 .. ev_t1 brackets steps [first_timed, n_steps)
@@ -1669,6 +1903,74 @@ int fluxmi_engine_set_inpaint(fluxmi_engine_t* e, const void* x0, const void* no
   return 0;
 }
 
+// Attach a ControlNet to the prepared shape of `e` (fluxmi.h): prepares the net for that shape (its own workspace; the position ids come from
+// e's), copies the caller's cond -- replicated to both halves of a guided batch -- and the request's mode row, writes the scale, and projects
+// controlnet_x_embedder(cond) once.  Everything is enqueued on `stream`, in order with the forward / denoise call that follows on it.
+int fluxmi_engine_attach_controlnet(fluxmi_engine_t* e, fluxmi_engine_t* cn, const void* cond, int batch, int mode, float scale, int trial_index,
+                                    void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  FLUXMI_REQUIRE(e && !e->is_cn, "engine_attach_controlnet: the first argument is the main engine");
+  if (!cn) {
+    if (e->cn) { e->cn->cn_owner = nullptr; e->cn = nullptr; }
+    return 0;
+  }
+  FLUXMI_REQUIRE(cn->is_cn, "engine_attach_controlnet: the second argument is not a ControlNet engine (fluxmi_controlnet_create)");
+  FLUXMI_REQUIRE(e->ws, "engine_attach_controlnet: call fluxmi_engine_prepare first (the net is attached to the prepared shape)");
+  FLUXMI_REQUIRE(cond, "engine_attach_controlnet: NULL cond");
+  FLUXMI_REQUIRE(cn->d.hidden == e->d.hidden && cn->d.heads == e->d.heads && cn->d.in_channels == e->d.in_channels,
+                 "engine_attach_controlnet: the net's hidden / heads / in_channels (%d / %d / %d) differ from the main model's (%d / %d / %d)",
+                 cn->d.hidden, cn->d.heads, cn->d.in_channels, e->d.hidden, e->d.heads, e->d.in_channels);
+  FLUXMI_REQUIRE(!cn->d.guidance_embed || e->d.guidance_embed, "engine_attach_controlnet: the net has a guidance embedder, the main model has none "
+                 "(no guidance value reaches the step)");
+  FLUXMI_REQUIRE(c_out(e) == e->d.in_channels, "engine_attach_controlnet: the main model reads %d channels and predicts %d (FLUX.1 Fill, Depth / "
+                 "Canny [dev]): channel-conditioned models take no ControlNet", e->d.in_channels, c_out(e));
+  FLUXMI_REQUIRE(e->Lpred == e->Li, "engine_attach_controlnet: the prepared shape has %d Kontext reference rows: they do not combine with a "
+                 "ControlNet", e->Li - e->Lpred);
+  FLUXMI_REQUIRE(!e->masked, "engine_attach_controlnet: a token-group attention table is set (regional prompts do not combine with a ControlNet)");
+  FLUXMI_REQUIRE(!(e->fb_threshold > 0.f), "engine_attach_controlnet: step caching is on (it does not combine with a ControlNet)");
+  if (cn->cn_mode_table) {
+    FLUXMI_REQUIRE(mode >= 0 && mode < cn->cn_num_mode, "engine_attach_controlnet: control mode %d outside 0..%d (a Union net needs one)", mode,
+                   cn->cn_num_mode - 1);
+    FLUXMI_REQUIRE(e->Lt >= 1, "engine_attach_controlnet: a Union net needs at least one text row (the mode row takes its position id)");
+  } else {
+    FLUXMI_REQUIRE(mode == -1, "engine_attach_controlnet: control mode %d given to a net without a mode embedding (pass -1)", mode);
+  }
+  FLUXMI_REQUIRE(batch >= 1 && (batch == e->B || (e->B % 2 == 0 && batch == e->B / 2)),
+                 "engine_attach_controlnet: cond for %d images on a prepared batch of %d (the batch, or half of it for a guided request)", batch, e->B);
+  FLUXMI_REQUIRE(!cn->cn_owner || cn->cn_owner == e, "engine_attach_controlnet: the net is attached to another engine");
+  FLUXMI_REQUIRE(trial_index >= 0, "engine_attach_controlnet: trial_index %d", trial_index);
+  if (e->cn && e->cn != cn) { e->cn->cn_owner = nullptr; e->cn = nullptr; }
+  FLUXMI_TRY(prepare_impl(cn, e->B, e->Li, 0, e->Lt + cn->txt_extra, nullptr, nullptr, e, s));
+  const int H = cn->d.hidden, C = cn->d.in_channels, B = e->B, Li = e->Li;
+  const size_t nb = (size_t)batch * Li * C * 2;
+  u16 *cc = buf<u16>(cn, "cn_cond"), *cp = buf<u16>(cn, "cn_cproj");
+  FLUXMI_CHECK_HIP(hipMemcpyAsync(cc, cond, nb, hipMemcpyDeviceToDevice, s));
+  if (batch < B) FLUXMI_CHECK_HIP(hipMemcpyAsync((char*)cc + nb, cond, nb, hipMemcpyDeviceToDevice, s));
+  if (cn->cn_mode_table)
+    FLUXMI_CHECK_HIP(hipMemcpyAsync(buf<u16>(cn, "cn_mode_row"), (const u16*)cn->cn_mode_table + (size_t)mode * H, (size_t)H * 2, hipMemcpyDeviceToDevice, s));
+  unsigned bits;
+  memcpy(&bits, &scale, 4);
+  FLUXMI_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)e->d_cn_scale, (int)bits, 1, s));
+  {
+    SplitkScope scope(cn);
+    const fluxmi_linear_t& l = cn->lin[cn->i_cn_x];
+    std::vector<FluxmiGemmGroup> gs;
+    for (int b = 0; b < B; ++b) gs.push_back(mk_group(l, cc + (long long)b * Li * C, C, cp + (long long)b * Li * H, H, Li));
+    FLUXMI_TRY(run_gemm_fixed_cfg(gs, H, C, 0, 0, FLUXMI_EPI_BF16, s));
+  }
+  cn->cn_trial = trial_index;
+  cn->cn_owner = e;
+  e->cn = cn;
+  e->cn_batch = batch;
+  return 0;
+}
+
+int fluxmi_controlnet_trial(fluxmi_engine_t* cn, int* trial_index) {
+  FLUXMI_REQUIRE(cn && cn->is_cn && trial_index, "controlnet_trial: not a ControlNet engine / NULL argument");
+  *trial_index = cn->cn_trial;
+  return 0;
+}
+
 int fluxmi_engine_set_step_cache(fluxmi_engine_t* e, float threshold, int max_consecutive_hits) {
   FLUXMI_REQUIRE(e, "engine_set_step_cache: NULL engine");
   FLUXMI_REQUIRE(threshold >= 0.f, "engine_set_step_cache: threshold %g must be >= 0 and not NaN (0 = off)", (double)threshold);
@@ -1697,6 +1999,7 @@ int fluxmi_engine_run_phase(fluxmi_engine_t* e, int mode, int phase_from, int ph
   FLUXMI_REQUIRE(step < 0 || (e->mods_all && step >= e->mods_step0 && step < e->mods_step0 + MODS_STEPS),
                  "engine_run_phase: step %d is outside the modulation table of the last denoise call (from step %d)", step, e->mods_step0);
   FLUXMI_REQUIRE(mode == 2 || phase_from > PH_EMBED || e->txt_emb_valid, "engine_run_phase: no embedded text from a denoise call on this shape");
+  FLUXMI_REQUIRE(!e->cn && !e->is_cn, "engine_run_phase: a ControlNet is attached (the phases are the main model's alone: detach it first)");
   SplitkScope splitk(e);
   FLUXMI_TRY(ensure_pairs(e, s));
   if (mode == 1) {

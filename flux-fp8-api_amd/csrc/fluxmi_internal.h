@@ -176,6 +176,8 @@ int fluxmi_k_fb_metric(const void* x, long long x_bstride, const void* h0, void*
                        float* numden, int B, long long n, hipStream_t s);
 int fluxmi_k_fb_store(const void* x, long long x_bstride, const void* h1, void* R, int B, long long n, hipStream_t s);
 int fluxmi_k_fb_apply(void* x, long long x_bstride, const void* h1, long long h1_bstride, const void* R, int B, long long n, hipStream_t s);
+// ControlNet residual hand-over: x[b, j] = bf16(x[b, j] + bf16(r[b, j] * *s_dev)), B samples of n elements, batch strides in elements
+int fluxmi_k_add_scaled(void* x, long long x_bstride, const void* r, long long r_bstride, const float* s_dev, int B, long long n, hipStream_t s);
 int fluxmi_k_set_timestep(void* t_vec, const float* ts, const int* step, int B, hipStream_t s);
 int fluxmi_k_advance_step(int* step, hipStream_t s);
 int fluxmi_k_clock_sample(unsigned long long* out2, hipStream_t s);

@@ -28,7 +28,8 @@ import torch
 
 import lora_loading  # noqa: F401  (same import side as the reference)
 from fluxmi import dist as fdist
-from util import ModelSpec, ModelVersion, engine_flow_dtype, into_device, into_dtype, load_config_from_path, load_models_from_config
+from util import (ModelSpec, ModelVersion, engine_flow_dtype, into_device, into_dtype, load_config_from_path, load_controlnet,
+                  load_models_from_config)
 
 MAX_RAND = 2**32 - 1
 
@@ -149,7 +150,8 @@ def build_region_groups(n_base: int, regional_tokens: int, region_grids: torch.T
 class FluxPipeline:
     def __init__(self, name: str, offload: bool = False, clip=None, t5=None, model=None, ae=None,
                  dtype: torch.dtype = torch.float16, verbose: bool = False, flux_device="cuda:0", ae_device="cuda:1",
-                 clip_device="cuda:1", t5_device="cuda:1", config: ModelSpec = None, debug: bool = False, redux=None):
+                 clip_device="cuda:1", t5_device="cuda:1", config: ModelSpec = None, debug: bool = False, redux=None,
+                 controlnet=None):
         if config is None:
             raise ValueError("ModelSpec config is required!")
         self.debug, self.name, self.verbose, self.offload = debug, name, verbose, offload
@@ -158,6 +160,7 @@ class FluxPipeline:
         self.dtype = into_dtype(dtype)
         self.clip, self.t5, self.model, self.ae = clip, t5, model, ae
         self.redux = redux  # FLUX.1 Redux image encoder (modules/image_embedders.ReduxImageEncoder) or None
+        self.controlnet = controlnet  # FLUX ControlNet (modules/controlnet.FluxControlNet, config.controlnet_path) or None
         self.rng = torch.Generator(device="cpu")
         self.ae_dtype = torch.bfloat16
         self.config = config
@@ -442,6 +445,17 @@ class FluxPipeline:
         cond = self.pack(self._encode_sampled(x, generator))
         return cond.to(self.device_flux).repeat(num_images, 1, 1).contiguous()
 
+    @torch.inference_mode()
+    def prepare_controlnet_conditioning(self, controlnet_image, height: int, width: int, num_images: int = 1,
+                                        generator: torch.Generator = None) -> torch.Tensor:
+        """A ControlNet's `cond` bf16 [num_images, Li, 64] on the flow device (diffusers' FluxControlNetPipeline.prepare_image + the latent
+        handling of its __call__): the control image, in any form `init_image` takes, is resized like `control_image`, VAE-encoded (its
+        Gaussian sample drawn from `generator` after the noise), shifted and scaled, cast to bf16 and packed 2 x 2.  The caller passes the
+        edge map / depth map / pose itself; no preprocessor is part of this project."""
+        if self.ae is None:
+            raise RuntimeError("fluxmi: controlnet_image needs an autoencoder (config.ae_path) -- none is attached; pass controlnet_cond")
+        return self.prepare_control_conditioning(controlnet_image, height, width, num_images=num_images, generator=generator)
+
     # ---- FLUX.1 Redux image prompts ------------------------------------------------------------------------------------------------------
     def _require_redux(self):
         if self.redux is None:
@@ -596,6 +610,17 @@ class FluxPipeline:
             self.generate(**{**kw, "num_steps": 1})  # 13th call: freezes the input scales
         if world > 1:
             self.model.enable_amax_exchange(False)
+        if getattr(self, "controlnet", None) is not None:
+            # the ControlNet calibrates on its own counter (the main model's scales are frozen by now): the same 13 calls with a mid-grey
+            # control image through the autoencoder, or N(0, 1) control latents without one
+            ckw = dict(control_mode=0) if self.controlnet.is_union else {}
+            if self.ae is not None and getattr(self.ae, "encoder_loaded", True):
+                ckw["controlnet_image"] = np.full((kw["height"], kw["width"], 3), 128, dtype=np.uint8)
+            else:
+                g = torch.Generator().manual_seed(11)
+                ckw["controlnet_cond"] = torch.randn(1, (kw["height"] // 16) * (kw["width"] // 16), p.in_channels, generator=g)
+            for n in ((4, 4, 4, 1) if kw["num_steps"] == 4 else (12, 1)):
+                self.generate(**{**kw, **ckw, "num_steps": n})
         if self.redux is not None:
             # one Redux request on the frozen scales, so that the encoder and the longer text stream have run before serving
             self.generate(**{**kw, "num_steps": 1, "redux_image": np.full((384, 384, 3), 128, dtype=np.uint8)})
@@ -626,7 +651,9 @@ class FluxPipeline:
                  use_graph: bool = True, reference_image=None, mask_image=None, control_image=None,
                  img_cond: Optional[torch.Tensor] = None, redux_image=None, negative_prompt=None, true_cfg_scale: float = 1.0,
                  true_cfg_interval=(0.0, 1.0), cache_threshold: float = 0.0, cache_max_hits: int = 0, regions=None,
-                 regional_tokens: int = 128, inpaint_mask=None, inpaint_differential: bool = False):
+                 regional_tokens: int = 128, inpaint_mask=None, inpaint_differential: bool = False, controlnet_image=None,
+                 controlnet_conditioning_scale: float = 1.0, control_mode: Optional[int] = None, control_guidance_start: float = 0.0,
+                 control_guidance_end: float = 1.0, controlnet_cond: Optional[torch.Tensor] = None):
         """`reference_image` (FLUX.1 Kontext [dev] instruction editing): an image the prompt describes an edit of, in any form `init_image`
         takes; see prepare_kontext_reference.  Composes with `init_image` / `strength` unchanged.
         FLUX.1 Fill [dev] (a model with 320 conditioning channels): `init_image` is the image to inpaint and `mask_image` (white =
@@ -669,7 +696,46 @@ class FluxPipeline:
         purpose: `mask_image` stays FLUX.1 Fill's conditioning; on a Fill model `inpaint_mask` is a hard composite on top of it.
         `inpaint_differential=True` (differential diffusion): the mask is a grey change map, released step by step (inpaint_thresholds).
         Composes with strength, `noise=`, num_images, a Kontext reference (noisy rows only), Depth / Canny, Redux, regions, step caching, a
-        negative prompt and LoRA.  Image quality on real FLUX weights is not established here."""
+        negative prompt and LoRA.  Image quality on real FLUX weights is not established here.
+        `controlnet_image` (a FLUX ControlNet, config.controlnet_path: a diffusers-format FluxControlNetModel checkpoint): the edge map, depth
+        map, pose ... to follow, in any form `init_image` takes (prepare_controlnet_conditioning), or `controlnet_cond`, its packed latents
+        [1 or num_images, Li, 64] already prepared.  `controlnet_conditioning_scale` (any float) scales the net's residuals; a Union net needs
+        `control_mode`; `control_guidance_start` / `control_guidance_end` follow diffusers: step i of n is controlled iff not (i / n < start
+        or (i + 1) / n > end) -- run as consecutive denoise calls on slices of the schedule, like `true_cfg_interval`.  Composes with img2img,
+        num_images, `noise=`, LoRA on the main model, Redux (the net sees the same text rows), a negative prompt (both branches are
+        controlled) and `inpaint_mask`; refused with `regions`, `cache_threshold` > 0, `reference_image` and a Fill / Depth / Canny model.
+        Without it the request is today's, launch for launch."""
+        cn_on = controlnet_image is not None or controlnet_cond is not None
+        if cn_on:
+            if getattr(self, "controlnet", None) is None:
+                raise ValueError("fluxmi: controlnet_image needs a ControlNet: set config.controlnet_path (a local diffusers-format "
+                                 "FluxControlNetModel checkpoint)")
+            if controlnet_image is not None and controlnet_cond is not None:
+                raise ValueError("fluxmi: pass controlnet_image or controlnet_cond, not both")
+            if regions is not None:
+                raise ValueError("fluxmi: regions do not combine with a ControlNet")
+            if float(cache_threshold) > 0:
+                raise ValueError("fluxmi: cache_threshold > 0 (step caching) does not combine with a ControlNet")
+            if reference_image is not None:
+                raise ValueError("fluxmi: a Kontext reference_image does not combine with a ControlNet")
+            if self.conditioning_kind() is not None:
+                raise ValueError("fluxmi: a FLUX.1 Fill / Depth / Canny model takes no ControlNet")
+            if self.controlnet.is_union and control_mode is None:
+                raise ValueError(f"fluxmi: a Union ControlNet needs control_mode (0..{self.controlnet.num_mode - 1})")
+            if self.controlnet.is_union and not 0 <= int(control_mode) < self.controlnet.num_mode:
+                raise ValueError(f"fluxmi: control_mode={control_mode}: expected 0..{self.controlnet.num_mode - 1}")
+            if not self.controlnet.is_union and control_mode is not None:
+                raise ValueError("fluxmi: control_mode is for Union ControlNets; this net has no mode embedding")
+            try:
+                cg0, cg1 = float(control_guidance_start), float(control_guidance_end)
+                cn_scale = float(controlnet_conditioning_scale)
+            except (TypeError, ValueError):
+                raise ValueError("fluxmi: controlnet_conditioning_scale / control_guidance_start / control_guidance_end: expected numbers") from None
+            if not (0.0 <= cg0 <= 1.0 and 0.0 <= cg1 <= 1.0 and cg0 <= cg1 and math.isfinite(cn_scale)):
+                raise ValueError(f"fluxmi: control_guidance_start={control_guidance_start} / end={control_guidance_end}: expected 0 <= start <= "
+                                 f"end <= 1 and a finite controlnet_conditioning_scale")
+            if fdist.world_size() > 1:
+                raise ValueError("fluxmi: a ControlNet request under a process group is not supported")
         if inpaint_mask is None and inpaint_differential:
             raise ValueError("fluxmi: inpaint_differential needs an inpaint_mask (the change map)")
         if inpaint_mask is not None and init_image is None:
@@ -801,6 +867,15 @@ class FluxPipeline:
             if img_cond.shape[0] == 1 and num_images > 1:
                 img_cond = img_cond.repeat(num_images, 1, 1)
             cond = dict(img_cond=img_cond.contiguous())
+        cn_cond = None
+        if cn_on:
+            # drawn from the request's generator after the noise, like a Kontext reference
+            if controlnet_cond is None:
+                controlnet_cond = self.prepare_controlnet_conditioning(controlnet_image, height, width, num_images=1, generator=generator)
+            cn_cond = controlnet_cond.to(device=self.device_flux, dtype=torch.bfloat16)
+            if cn_cond.ndim != 3 or cn_cond.shape[0] not in (1, num_images) or tuple(cn_cond.shape[1:]) != tuple(img.shape[1:]):
+                raise ValueError(f"fluxmi: controlnet_cond {tuple(cn_cond.shape)}: expected [1 or {num_images}, {img.shape[1]}, {img.shape[2]}]")
+            cn_cond = cn_cond.expand(num_images, -1, -1).contiguous()
         if world > 1:
             if guided:  # the negative embeddings ride in the one broadcast, behind the prompt's
                 txt, vec = torch.cat((txt, neg_txt), 0), torch.cat((vec, neg_vec), 0)
@@ -844,7 +919,24 @@ class FluxPipeline:
                 neg["attn_groups"] = torch.stack(tab).to(self.device_flux)
             thr = self.inpaint_thresholds(n) if inpaint is not None and inpaint_differential else None
             latents = img
-            for a, b, kw in ((0, g0, plain_kw), (g0, g1, neg), (g1, n, plain_kw)) if g0 < g1 else ((0, n, plain_kw),):
+            segs = list(((0, g0, plain_kw), (g0, g1, neg), (g1, n, plain_kw)) if g0 < g1 else ((0, n, plain_kw),))
+            if cn_cond is not None and n > 0:
+                # cut every segment where the ControlNet switches on or off (diffusers' controlnet_keep): consecutive denoise calls
+                from modules.controlnet import ControlNetCall, control_steps
+
+                keep = control_steps(n, cg0, cg1)
+                call = ControlNetCall(self.controlnet, cn_cond, cn_scale, None if control_mode is None else int(control_mode))
+                cut = []
+                for a, b, kw in segs:
+                    i = a
+                    while i < b:
+                        j = i
+                        while j < b and keep[j] == keep[i]:
+                            j += 1
+                        cut.append((i, j, dict(kw, controlnet=call) if keep[i] else kw))
+                        i = j
+                segs = cut
+            for a, b, kw in segs:
                 if a < b or n == 0:
                     if inpaint is not None:
                         x0_, noise_, mask_ = inpaint.chunk(3, -1)
@@ -925,4 +1017,5 @@ class FluxPipeline:
                 flow_model.eval().requires_grad_(False)
         return cls(name=config.version, clip=models.clip, t5=models.t5, model=flow_model, ae=models.ae, dtype=flux_dtype, verbose=False,
                    flux_device=flux_device, ae_device=into_device(config.ae_device), clip_device=into_device(config.text_enc_device),
-                   t5_device=into_device(config.text_enc_device), config=config, debug=debug, redux=redux)
+                   t5_device=into_device(config.text_enc_device), config=config, debug=debug, redux=redux,
+                   controlnet=load_controlnet(config, device=flux_device))

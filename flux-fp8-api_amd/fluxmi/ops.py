@@ -526,3 +526,23 @@ def patchify(pix: torch.Tensor, patch: int, grid: int, k_pad: int) -> torch.Tens
     out = torch.empty((B * grid * grid, k_pad), dtype=torch.bfloat16, device=pix.device)
     call("fluxmi_patchify", _p(pix), _p(out), B, Cc, H, W, int(patch), int(grid), int(k_pad), _stream())
     return out
+
+
+def add_scaled(x: torch.Tensor, r: torch.Tensor, scale) -> torch.Tensor:
+    """In place x[b] = bf16(x[b] + bf16(r[b] * scale)) (fluxmi_add_scaled: the ControlNet residual hand-over).  x, r: bf16 [B, ...] whose
+    samples are contiguous (the batch stride may exceed a sample's size); scale: a float or an fp32 device scalar, never rounded to bf16."""
+    _req(x, torch.bfloat16, "x")
+    _req(r, torch.bfloat16, "r")
+    if x.shape != r.shape or x.ndim < 1:
+        raise ValueError(f"add_scaled: x {tuple(x.shape)} vs r {tuple(r.shape)}")
+    B = x.shape[0]
+    n = x[0].numel() if B else 0
+    for t in (x, r):
+        if B and not t[0].is_contiguous():
+            raise ValueError("add_scaled: the samples must be contiguous")
+    s = scale if isinstance(scale, torch.Tensor) else torch.tensor([float(scale)], dtype=torch.float32, device=x.device)
+    _req(s, torch.float32, "scale")
+    xs = x.stride(0) if B > 1 else n
+    rs = r.stride(0) if B > 1 else n
+    _lib.call("fluxmi_add_scaled", _p(x), xs, _p(r), rs, _p(s), B, n, _stream())
+    return x

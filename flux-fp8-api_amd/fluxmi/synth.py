@@ -94,3 +94,30 @@ def make_inputs(params, height: int, width: int, txt_len: int, batch: int = 1, s
     img_ids = img_ids[None].repeat(batch, 1, 1, 1).flatten(1, 2)
     txt_ids = torch.zeros(batch, txt_len, 3, dtype=dtype)
     return dict(img=img, img_ids=img_ids, txt=txt, txt_ids=txt_ids, y=y)
+
+
+def make_controlnet_state_dict(params, num_double: int, num_single: int, num_mode: int = 0, seed: int = 0, guidance_embed=None,
+                               dtype=torch.bfloat16, device="cpu", proj_gain: float = 1.0) -> Dict[str, torch.Tensor]:
+    """A synthetic FLUX ControlNet for the main model of `params` under modules.controlnet.FluxControlNet's (BFL-style) key names: a trunk of
+    `num_double` + `num_single` blocks like make_state_dict's (no final layer), controlnet_x_embedder, one controlnet_blocks /
+    controlnet_single_blocks projection per block and, with `num_mode`, the controlnet_mode_embedder table.  Real checkpoints zero-initialise the
+    projections before training; these are drawn like every other linear (`proj_gain`), so that the net's residuals are as large as the stream
+    they join and a parity test cannot pass by ignoring them."""
+    import copy
+
+    p = copy.copy(params)
+    p.depth, p.depth_single_blocks = int(num_double), int(num_single)
+    if guidance_embed is not None:
+        p.guidance_embed = bool(guidance_embed)
+    sd = {k: v for k, v in make_state_dict(p, seed=seed + 7919, dtype=dtype, device=device).items() if not k.startswith("final_layer.")}
+    gen = torch.Generator(device=device).manual_seed(seed + 104729)
+    H = params.hidden_size
+    L = lambda *a, **k: _linear(sd, *a, gen=gen, device=device, dtype=dtype, **k)
+    L("controlnet_x_embedder", H, params.in_channels, gain=proj_gain)
+    for i in range(num_double):
+        L(f"controlnet_blocks.{i}", H, H, gain=proj_gain)
+    for i in range(num_single):
+        L(f"controlnet_single_blocks.{i}", H, H, gain=proj_gain)
+    if num_mode:
+        sd["controlnet_mode_embedder.weight"] = torch.randn(num_mode, H, generator=gen, device=device, dtype=torch.float32).to(dtype)
+    return sd

@@ -418,6 +418,50 @@ class Flux(nn.Module):
             raise ValueError(f"img_cond {tuple(img_cond.shape)} != {(img.shape[0], img.shape[1], extra)}")
         return torch.cat((img.to(torch.bfloat16), img_cond.to(device=img.device, dtype=torch.bfloat16)), 2)
 
+    def _check_controlnet(self, controlnet, img, B_cond: int, kontext: bool, attn_groups, cache_threshold: float = 0.0):
+        """the `controlnet=` argument (modules.controlnet.ControlNetCall) validated before any device work -> None or (net, cond, mode, scale)"""
+        if controlnet is None:
+            return None
+        net, cond, scale, mode = controlnet.net, controlnet.cond, float(controlnet.scale), controlnet.mode
+        if self.in_channels != self.out_channels:
+            raise ValueError("controlnet: FLUX.1 Fill / Depth / Canny [dev] models (in_channels != out_channels) take no ControlNet")
+        if kontext:
+            raise ValueError("controlnet: a Kontext reference (img_cond_seq) does not combine with a ControlNet")
+        if attn_groups is not None:
+            raise ValueError("controlnet: regional prompts (attn_groups) do not combine with a ControlNet")
+        if cache_threshold > 0.0:
+            raise ValueError("controlnet: step caching (cache_threshold > 0) does not combine with a ControlNet")
+        if net.hidden_size != self.hidden_size or net.num_heads != self.num_heads or net.in_channels != self.in_channels:
+            raise ValueError(f"controlnet: the net's hidden / heads / in_channels ({net.hidden_size} / {net.num_heads} / {net.in_channels}) differ "
+                             f"from the main model's ({self.hidden_size} / {self.num_heads} / {self.in_channels})")
+        if net.params.guidance_embed and not self.params.guidance_embed:
+            raise ValueError("controlnet: the net has a guidance embedder, the main model has none")
+        if net.is_union:
+            if mode is None or not 0 <= int(mode) < net.num_mode:
+                raise ValueError(f"controlnet: a Union net needs control_mode in 0..{net.num_mode - 1} (got {mode})")
+        elif mode is not None:
+            raise ValueError("controlnet: control_mode given to a net without a mode embedding")
+        if not math.isfinite(scale):
+            raise ValueError(f"controlnet: conditioning scale {scale} is not finite")
+        want = (B_cond, img.shape[1], self.in_channels)
+        if not isinstance(cond, torch.Tensor) or cond.ndim != 3 or cond.shape[0] not in (1, B_cond) or tuple(cond.shape[1:]) != want[1:]:
+            raise ValueError(f"controlnet: cond {tuple(cond.shape) if isinstance(cond, torch.Tensor) else type(cond).__name__}: expected a tensor "
+                             f"[1 or {want[0]}, {want[1]}, {want[2]}] (the packed control latent)")
+        return net, cond.expand(B_cond, -1, -1), None if mode is None else int(mode), scale
+
+    def _attach_controlnet(self, cn, device):
+        """after _prepare, under the lock: attach the call's ControlNet (the engine copies cond), or detach; returns the net to hand to
+        _release_controlnet behind the call"""
+        if cn is None:
+            return None  # nothing is attached between calls (_release_controlnet): a plain call makes the host calls it always made
+        net, cond, mode, scale = cn
+        net._attach(self._engine, cond.to(device=device, dtype=torch.bfloat16).contiguous(), mode, scale)
+        return net
+
+    def _release_controlnet(self, net):
+        if net is not None:
+            net._detach(self._engine)
+
     # ---- batch-sharded calibration (SURVEY.md 8e-3) ------------------------------------------------------------------
     def enable_amax_exchange(self, reduce_fn=None):
         """Keep the F8Linear input scales of batch-sharded replicas IDENTICAL to those of the whole batch on one GPU: the reference
@@ -515,7 +559,8 @@ class Flux(nn.Module):
     @torch.inference_mode()
     def forward(self, img: Tensor, img_ids: Tensor, txt: Tensor, txt_ids: Tensor, timesteps: Tensor, y: Tensor,
                 guidance: Tensor | None = None, mode: Optional[int] = None, img_cond_seq: Tensor | None = None,
-                img_cond_seq_ids: Tensor | None = None, img_cond: Tensor | None = None, attn_groups: Tensor | None = None) -> Tensor:
+                img_cond_seq_ids: Tensor | None = None, img_cond: Tensor | None = None, attn_groups: Tensor | None = None,
+                controlnet=None) -> Tensor:
         """One denoise-step evaluation (reference flux_model.py:672-716).  mode=None picks what the reference would do:
         calibrating (unfused) while any F8Linear still has trials to record, fused once frozen.
         FLUX.1 Kontext: `img_cond_seq` [B, Lc, C] / `img_cond_seq_ids` [B, Lc, 3] (flux_pipeline.prepare_kontext_reference) run through every
@@ -523,13 +568,17 @@ class Flux(nn.Module):
         FLUX.1 Fill / Depth / Canny: `img_cond` [B, Li, in_channels - out_channels] (flux_pipeline.prepare_fill_conditioning /
         prepare_control_conditioning) is appended to the channels of every token; the prediction is [B, Li, out_channels].
         `attn_groups`: a token-group attention mask, int32 [1 or B, Lt + Li + Lc] descriptors (include/fluxmi.h, fluxmi_attention_grouped):
-        every attention of the forward then runs F.scaled_dot_product_attention(q, k, v, attn_mask=allowed) instead of the dense one."""
+        every attention of the forward then runs F.scaled_dot_product_attention(q, k, v, attn_mask=allowed) instead of the dense one.
+        `controlnet`: a modules.controlnet.ControlNetCall -- the ControlNet runs first on the same inputs and its per-block residuals, times
+        the conditioning scale, are added to the image stream behind the main blocks (diffusers' FluxControlNetModel / FluxTransformer2DModel);
+        it calibrates on its own counter.  None = today's call."""
         if img.ndim != 3 or txt.ndim != 3:
             raise ValueError("Input img and txt tensors must have 3 dimensions.")
         if self.params.guidance_embed and guidance is None:
             raise ValueError("Didn't get guidance strength for guidance distilled model.")
         bf = lambda t: t.to(torch.bfloat16).contiguous()
         Li = img.shape[1]
+        cn = self._check_controlnet(controlnet, img, img.shape[0], img_cond_seq is not None or img_cond_seq_ids is not None, attn_groups)
         img = self._with_channels(img, img_cond, img_cond_seq)
         img, img_ids, Lc = self._with_reference(img, img_ids, img_cond_seq, img_cond_seq_ids)
         img, txt, y, timesteps = bf(img), bf(txt), bf(y), bf(timesteps)
@@ -547,8 +596,12 @@ class Flux(nn.Module):
                 else:
                     mode = 1 if self._all_block_linears_f8() else 2
             pred = torch.empty(img.shape[0], Li, self.out_channels, dtype=torch.bfloat16, device=img.device)
-            _lib.call("fluxmi_engine_forward", self._engine, ops._p(img), ops._p(txt), ops._p(y), ops._p(timesteps), ops._p(guidance),
-                      ops._p(pred), mode, trial if mode == 0 else 0, ops._stream())
+            net = self._attach_controlnet(cn, img.device)
+            try:
+                _lib.call("fluxmi_engine_forward", self._engine, ops._p(img), ops._p(txt), ops._p(y), ops._p(timesteps), ops._p(guidance),
+                          ops._p(pred), mode, trial if mode == 0 else 0, ops._stream())
+            finally:
+                self._release_controlnet(net)
             if mode == 0:
                 self._advance_calibration(trial + 1)
         return pred if self.dtype == torch.bfloat16 else pred.to(self.dtype)
@@ -568,7 +621,7 @@ class Flux(nn.Module):
                 img_cond_seq_ids: Tensor | None = None, img_cond: Tensor | None = None, neg_txt: Tensor | None = None,
                 neg_y: Tensor | None = None, cfg_scale: float = 1.0, cache_threshold: float = 0.0, cache_max_hits: int = 0,
                 attn_groups: Tensor | None = None, inpaint_x0: Tensor | None = None, inpaint_noise: Tensor | None = None,
-                inpaint_mask: Tensor | None = None, inpaint_thresholds=None) -> Tensor:
+                inpaint_mask: Tensor | None = None, inpaint_thresholds=None, controlnet=None) -> Tensor:
         """The Euler loop of FluxPipeline.generate (reference flux_pipeline.py:619-651) run natively: calibrating
         steps unfused, every later step one replay of a captured hipGraph.  Returns the final latent tokens.
         FLUX.1 Kontext: with `img_cond_seq` / `img_cond_seq_ids` the reference tokens join every step's forward and are never stepped; the
@@ -591,7 +644,10 @@ class Flux(nn.Module):
             p = t_next * noise + (1.0 - t_next) * x0;  x' = (1 - m) * p + m * x1
         on bf16 tensors, t_next = timesteps[i + 1]: with a schedule that ends at 0 the kept elements of the result are x0 bit for bit.
         `inpaint_thresholds` (differential diffusion): one float per step of THIS call; step i blends with the binary mask
-        float32(m) > float32(thresholds[i]) instead of m.  The caller's tensors are not modified."""
+        float32(m) > float32(thresholds[i]) instead of m.  The caller's tensors are not modified.
+        `controlnet`: a modules.controlnet.ControlNetCall (Flux.forward): every step runs the ControlNet, then the main model with the
+        residual adds, then the update the request already had -- one captured graph per frozen step once BOTH nets are calibrated; a guided
+        request controls both branches.  Refused with a Kontext reference, attn_groups, cache_threshold > 0 and channel-conditioned models."""
         inpaint = self._check_inpaint(img, inpaint_x0, inpaint_noise, inpaint_mask, inpaint_thresholds, len(timesteps) - 1)
         cache_threshold, cache_max_hits = float(cache_threshold), int(cache_max_hits)
         if not (math.isfinite(cache_threshold) and cache_threshold >= 0.0) or cache_max_hits < 0:
@@ -599,6 +655,7 @@ class Flux(nn.Module):
         bf = lambda t: t.to(torch.bfloat16).contiguous()
         kontext = img_cond_seq is not None or img_cond_seq_ids is not None
         guided = neg_txt is not None or neg_y is not None
+        cn = self._check_controlnet(controlnet, img, img.shape[0], kontext, attn_groups, cache_threshold)
         if guided:
             if neg_txt is None or neg_y is None:
                 raise ValueError("neg_txt and neg_y go together (the negative prompt's T5 sequence and pooled CLIP vector)")
@@ -617,7 +674,7 @@ class Flux(nn.Module):
             # larger batches run as consecutive passes (samples never interact).  EQUAL passes: the engine re-allocates its workspace and
             # re-captures its graph whenever the batch size changes, so 40 = 20 + 20, not 32 + 8.  Only frozen models: a calibrating pass
             # per chunk would advance the F8Linear trial counters once per chunk instead of once per step.
-            if self.calibration_state()[0] is False:
+            if self.calibration_state()[0] is False or (cn is not None and cn[0].calibration_state()[0] is False):
                 raise ValueError(f"fluxmi: batches larger than {cap} need frozen F8Linear input scales (run the calibration warm-up first)")
             B = img.shape[0]
             n_pass = -(-B // cap)
@@ -638,6 +695,8 @@ class Flux(nn.Module):
                 if inpaint is not None:
                     cond.update(inpaint_x0=pick(inpaint[0]), inpaint_noise=pick(inpaint[1]), inpaint_mask=pick(inpaint[2]),
                                 inpaint_thresholds=inpaint[3])
+                if cn is not None:
+                    cond["controlnet"] = type(controlnet)(cn[0], pick(cn[1]), cn[3], cn[2])
                 o = self.denoise(pick(img), pick(img_ids), pick(txt), pick(txt_ids), pick(y), timesteps, guidance=guidance, use_graph=use_graph,
                                  cache_threshold=cache_threshold, cache_max_hits=cache_max_hits, **cond)
                 outs.append(o[:per - pad])
@@ -660,12 +719,16 @@ class Flux(nn.Module):
             ts = (C.c_double * len(timesteps))(*[float(t) for t in timesteps])
             _lib.call("fluxmi_engine_set_step_cache", self._engine, cache_threshold, cache_max_hits)
             self._set_inpaint(inpaint, img.device)
-            if guided:
-                _lib.call("fluxmi_engine_denoise_cfg", self._engine, ops._p(img), ops._p(txt), ops._p(y), float(guidance), float(cfg_scale), ts,
-                          len(timesteps) - 1, C.byref(t_io), int(use_graph), ops._stream())
-            else:
-                _lib.call("fluxmi_engine_denoise", self._engine, ops._p(img), ops._p(txt), ops._p(y), float(guidance), ts,
-                          len(timesteps) - 1, C.byref(t_io), int(use_graph), ops._stream())
+            net = self._attach_controlnet(cn, img.device)
+            try:
+                if guided:
+                    _lib.call("fluxmi_engine_denoise_cfg", self._engine, ops._p(img), ops._p(txt), ops._p(y), float(guidance), float(cfg_scale), ts,
+                              len(timesteps) - 1, C.byref(t_io), int(use_graph), ops._stream())
+                else:
+                    _lib.call("fluxmi_engine_denoise", self._engine, ops._p(img), ops._p(txt), ops._p(y), float(guidance), ts,
+                              len(timesteps) - 1, C.byref(t_io), int(use_graph), ops._stream())
+            finally:
+                self._release_controlnet(net)
             if trial is not None:
                 self._advance_calibration(t_io.value)
         if self.in_channels != self.out_channels:

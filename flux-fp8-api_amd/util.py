@@ -70,6 +70,9 @@ class ModelSpec(BaseModel):  # reference util.py:38-79 (unknown JSON keys are ig
     # FLUX.1 Redux: BFL's flux1-redux-dev.safetensors (the projector) and the SigLIP vision tower (a local HF directory or .safetensors file)
     redux_path: str | None = None
     siglip_path: str | None = None
+    # FLUX ControlNet: a LOCAL diffusers-format FluxControlNetModel checkpoint (InstantX / Shakker-Labs Canny, Depth, Union ...), a
+    # .safetensors file or a directory holding diffusion_pytorch_model.safetensors.  Nothing is downloaded.
+    controlnet_path: str | None = None
 
     model_config: ConfigDict = {"arbitrary_types_allowed": True, "use_enum_values": True}
 
@@ -299,6 +302,38 @@ def load_redux(config: ModelSpec):
     enc = ReduxImageEncoder(read_siglip(siglip), txt_in_features=sd["redux_down.weight"].shape[0])
     enc.load_state_dict(sd)
     return enc.to(device=into_device(config.text_enc_device), dtype=torch.bfloat16)
+
+
+def load_controlnet(config: ModelSpec, device=None, state_dict=None):
+    """The FLUX ControlNet of config.controlnet_path (modules/controlnet.FluxControlNet) for the main model of `config`, quantised by the flow
+    model's flags, or None unless the path is a local file or directory (`state_dict`: the offline hook, diffusers- or BFL-named keys).
+    Nothing is downloaded.  XLabs-format checkpoints (input_hint_block) are refused by name."""
+    import os
+
+    from modules.controlnet import FluxControlNet
+
+    if state_dict is None:
+        path = getattr(config, "controlnet_path", None)
+        if not isinstance(path, str) or not os.path.exists(path):
+            return None
+        if os.path.isdir(path):
+            path = os.path.join(path, "diffusion_pytorch_model.safetensors")
+            if not os.path.isfile(path):
+                return None
+        from safetensors.torch import load_file as load_sft
+
+        state_dict = load_sft(path, device="cpu")
+    net = FluxControlNet.from_state_dict(config, state_dict)
+    if device is not None:
+        from float8_quantize import quantize_flow_transformer_and_dispatch_float8
+
+        device = into_device(device)
+        net.to(device)
+        if not config.prequantized_flow:
+            quantize_flow_transformer_and_dispatch_float8(net, device, swap_linears_with_cublaslinear=False, flow_dtype=torch.bfloat16,
+                                                          quantize_modulation=config.quantize_modulation,
+                                                          quantize_flow_embedder_layers=config.quantize_flow_embedder_layers)
+    return net
 
 
 def load_models_from_config(config: ModelSpec, state_dict=None, ae_state_dict=None, clip_kwargs=None, t5_kwargs=None) -> LoadedModels:

@@ -419,6 +419,14 @@ int fluxmi_fb_commit(const void* x, long long x_bstride, const void* r, void* r_
 int fluxmi_fb_store(const void* x, long long x_bstride, const void* h1, void* R, int B, long long n, void* stream);
 int fluxmi_fb_apply(void* x, long long x_bstride, const void* h1, long long h1_bstride, const void* R, int B, long long n, void* stream);
 
+/* ---- ControlNet residual hand-over ---------------------------------------------------
+ *   x[b, j] = bf16(x[b, j] + bf16(r[b, j] * *scale))     for b < B, j < n
+ * i.e. the torch expression x + r * s on bf16 tensors with s a Python float (diffusers' FluxControlNetModel scales its block samples by
+ * conditioning_scale, FluxTransformer2DModel adds them to the image stream).  x, r: bf16 with batch strides x_bstride / r_bstride in elements
+ * (>= n); scale: DEVICE fp32 scalar, used as it is -- never rounded to bf16 -- so one captured graph serves every scale.  Any n; 16-byte
+ * accesses when both pointers are 16-byte aligned and both strides are multiples of 8, element accesses otherwise (same arithmetic). */
+int fluxmi_add_scaled(void* x, long long x_bstride, const void* r, long long r_bstride, const float* scale, int B, long long n, void* stream);
+
 /* ---- whole-model engine ------------------------------------------------------------------------------- */
 typedef struct fluxmi_linear {
   const void* weight;      /* fp8 float8_data [N,K] (kind 1) or bf16 weight [N,K] (kind 0) */
@@ -574,6 +582,48 @@ int fluxmi_engine_set_inpaint(fluxmi_engine_t* e, const void* x0, const void* no
  *   1 double block 0 | 2 every later block | 3 the final layer -> "pred_s".
  * The counterpart of fluxmi_engine_run_block for what that cannot reach; needs a finished fluxmi_engine_denoise call on this shape. */
 int fluxmi_engine_run_phase(fluxmi_engine_t* e, int mode, int phase_from, int phase_to, int step, void* stream);
+
+/* ---- FLUX ControlNet (diffusers' FluxControlNetModel) -----------------------------------------------------------------
+ * A ControlNet is an engine of its own kind: a Flux trunk of desc->depth (= Nd >= 1) double and desc->depth_single (= Ns >= 0) single blocks
+ * with its own embedders and NO final layer, plus the bf16 nn.Linear projections controlnet_x_embedder [hidden, in_channels] and one
+ * [hidden, hidden] per block.  Layer order in `linears` (count = fluxmi_controlnet_num_linears(desc), host arithmetic only):
+ *   the trunk's list (fluxmi_engine_create) WITHOUT its two final-layer entries, then
+ *   controlnet_x_embedder, controlnet_blocks[0 .. Nd), controlnet_single_blocks[0 .. Ns)          -- all kind 0 (bf16), refused otherwise
+ * norm_scales as for fluxmi_engine_create.  mode_table: bf16 [num_mode, hidden] = controlnet_mode_embedder.weight of a Union net, or NULL
+ * (num_mode 0).  The handle is a fluxmi_engine_t: fluxmi_engine_set_tables, _rebind, _set_amax_exchange, _workspace_bytes, _get_buffer,
+ * _copy_buffer and _destroy apply; it keeps its own workspace, step-ahead modulation table, quantising tables and row-pair weight copies.  It
+ * is prepared and run only through fluxmi_engine_attach_controlnet: prepare / forward / denoise on the handle itself are refused. */
+int fluxmi_controlnet_num_linears(const fluxmi_model_desc_t* desc);
+int fluxmi_controlnet_create(const fluxmi_model_desc_t* desc, const fluxmi_linear_t* linears, int n_linears, const void* const* norm_scales,
+                             int n_norm_scales, const void* mode_table, int num_mode, fluxmi_engine_t** out);
+/* Attach `cn` to the main engine `e` for the following fluxmi_engine_forward / _denoise / _denoise_cfg calls on e's PREPARED shape (call it
+ * after fluxmi_engine_prepare, like fluxmi_engine_set_inpaint); cn == NULL detaches, and so does a prepare that re-allocates e's workspace.
+ * A detached engine launches exactly what it launched before this entry point existed.
+ *   cond   device bf16 [batch, Li, in_channels]: the VAE-encoded, shifted, scaled and packed control image of the caller's `batch` images;
+ *          batch = the prepared B, or B / 2 (a guided request: replicated to both halves).  The engine copies it: a captured graph never
+ *          holds the caller's pointer.  controlnet_x_embedder(cond) is step-invariant and computed here, once per request
+ *   mode   row of mode_table (a Union net: required, 0 <= mode < num_mode), -1 for a net without one (anything else is refused)
+ *   scale  the conditioning scale: device data of the captured graph (any value, another scale replays the same graph)
+ *   trial_index  the ControlNet's OWN calibration counter (its F8Linears' trial_index), read back with fluxmi_controlnet_trial
+ * With a net attached every forward is
+ *   ControlNet: x_img = bf16(img_in(img) + controlnet_x_embedder(cond)); x_txt = [mode_table[mode] ;] txt_in(txt) (the mode row's position
+ *               id is txt_ids[:1], the net's text length Lt + 1); vec from its own embedders; after double block k: r_k = bf16(
+ *               controlnet_blocks[k](x_img)), after single block k: r_(Nd + k) = bf16(controlnet_single_blocks[k](x_img rows))
+ *   main:       after double block i  x_img = bf16(x_img + bf16(r_(i / ceil(depth / Nd)) * scale))          (fluxmi_add_scaled, one launch)
+ *               after single block i  x_img rows = bf16(x_img + bf16(r_(Nd + i / ceil(depth_single / Ns)) * scale))
+ * on the same img / txt / y / timestep buffers, and a denoise step is ControlNet forward, main forward, the update kernel the request
+ * already had (plain, guided, blend): ONE captured graph per frozen step.  ControlNet on / off (and which net) is a kind of step graph like
+ * guided or masked.  Calibration: a step is graph-replayed only when BOTH nets are frozen; while either has trials left the steps run
+ * eagerly, that net in mode 0 and the other in its frozen mode.  fluxmi_engine_forward's mode / trial_index speak of the main model; the
+ * ControlNet runs mode 0 while its own counter has trials left (and advances it), else fused when the main runs fused, else unfused-frozen.
+ * Refused (fluxmi_last_error says which): hidden / heads / in_channels differ from e's; e predicts fewer channels than it reads (Fill, Depth /
+ * Canny [dev]); Kontext reference rows (Lc > 0); a token-group attention table; step caching on (also refused by the denoise call if it is
+ * switched on afterwards); a mode out of range, missing for a Union net or given to a net without a table; a net with a guidance embedder on a main model without
+ * one; a net attached elsewhere.  fluxmi_engine_run_phase is refused while a net is attached.  A captured step is keyed on a process-wide unique
+ * generation number of the net's workspace and weight binding, not on its address: a net created where a destroyed one lived re-captures. */
+int fluxmi_engine_attach_controlnet(fluxmi_engine_t* e, fluxmi_engine_t* cn, const void* cond, int batch, int mode, float scale, int trial_index,
+                                    void* stream);
+int fluxmi_controlnet_trial(fluxmi_engine_t* cn, int* trial_index);
 
 #ifdef __cplusplus
 }

@@ -234,6 +234,12 @@ int fluxmi_blend_euler(void* img, const void* pred, const void* x0, const void* 
   return fluxmi_k_blend_euler(img, pred, x0, noise, mask, dts, tnext, one_minus_tnext, thr, step, scale, B, img_rows, pred_rows, c_in, c_out,
                               (hipStream_t)stream);
 }
+int fluxmi_solver_step(void* img, const void* pred, void* xs, float* hist, const float* coef, const int* ctl, const void* x0, const void* noise,
+                       const void* mask, const float* tnext, const float* one_minus_tnext, const float* thr, const int* step, const float* scale,
+                       int B, long long img_rows, long long pred_rows, int c_in, int c_out, void* stream) {
+  return fluxmi_k_solver_step(img, pred, xs, hist, coef, ctl, x0, noise, mask, tnext, one_minus_tnext, thr, step, scale, B, img_rows, pred_rows,
+                              c_in, c_out, (hipStream_t)stream);
+}
 
 int fluxmi_fb_snapshot(const void* x, long long x_bstride, void* dst, int B, long long n, void* stream) {
   return fluxmi_k_fb_snapshot(x, x_bstride, dst, B, n, (hipStream_t)stream);

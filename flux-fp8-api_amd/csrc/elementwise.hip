@@ -645,6 +645,107 @@ __global__ void __launch_bounds__(256) blend_euler_kernel(u16* __restrict__ img,
     if (CFG) *(uint4*)(img + img_half + xo) = o;
   }
 }
+// The table-driven solver update (higher-order samplers): ONE linear update whose coefficients are device data, so the
+// engine never knows which solver runs.  Row j = *step of coef [n][8] = {cx, cs, c0, c1, c2, ga, gb, 0} and ctl [n][4] = {save_xs, w_slot,
+// h1_slot, h2_slot}; per predicted element, v = pred (CFG: cfg_euler_kernel's bf16 chain),
+//   g   = ga * x + gb * v                                                    fp32
+//   acc = cx * x + cs * xs + c0 * g + c1 * hist[h1_slot] + c2 * hist[h2_slot]   fp32, left to right
+//   x1  = bf16(acc)                                                          (BLEND: then blend_euler_kernel's tail on x1)
+// Every product and every sum is rounded to fp32 on its own: plain * and + under `fp contract(off)` stay unfused (HIP's __fmul_rn /
+// __fadd_rn are inline * / + compiled with contraction allowed, and may fuse once inlined: not used here).  A term whose coefficient is exactly
+// 0.0f or whose slot is negative is SKIPPED -- its buffer is not read, it may hold anything -- and the sum starts at the first term that
+// is present (0 when none is).  After all reads of the element: save_xs stores the pre-update x to xs, w_slot >= 0 stores g to
+// hist[w_slot] (which may be a slot just read), x' goes to img (CFG: both halves).  xs bf16 and hist fp32 [2][...] are dense like the prompt
+// half of pred; the indexing is cfg_euler_kernel's.  The row is uniform over the launch: every branch below is.
+template <bool CFG, bool PLAIN, bool BLEND>
+__global__ void __launch_bounds__(256) solver_step_kernel(u16* __restrict__ img, const u16* __restrict__ pred, u16* __restrict__ xs,
+                                                          float* __restrict__ hist, const float* __restrict__ coef, const int* __restrict__ ctl,
+                                                          const u16* __restrict__ x0, const u16* __restrict__ noise, const u16* __restrict__ mask,
+                                                          const float* __restrict__ tnext, const float* __restrict__ one_minus_tnext,
+                                                          const float* __restrict__ thr, const int* __restrict__ step,
+                                                          const float* __restrict__ scale, unsigned n_vec, unsigned vec_per_sample,
+                                                          unsigned vec_per_row, long long img_bstride, int c_in, long long img_half,
+                                                          long long pred_half) {
+#pragma clang fp contract(off)
+  const int i = step ? *step : 0;
+  const float cx = coef[8 * i], cs = coef[8 * i + 1], c0 = coef[8 * i + 2], c1 = coef[8 * i + 3], c2 = coef[8 * i + 4], ga = coef[8 * i + 5],
+              gb = coef[8 * i + 6];
+  const bool save = ctl[4 * i] != 0;
+  // a slot is -1, 0 or 1: anything above is read as 1, so that no table can index past the two slots
+  const int ws = min(ctl[4 * i + 1], 1), s1 = min(ctl[4 * i + 2], 1), s2 = min(ctl[4 * i + 3], 1);
+  const bool t_x = cx != 0.f, t_s = cs != 0.f, t_g = c0 != 0.f, t_1 = c1 != 0.f && s1 >= 0, t_2 = c2 != 0.f && s2 >= 0;
+  const bool need_g = t_g || ws >= 0;
+  const long long slot = (long long)n_vec * 8;
+  const float sc = CFG ? *scale : 0.f;
+  const float tn = BLEND ? tnext[i] : 0.f, om = BLEND ? one_minus_tnext[i] : 0.f;
+  const bool diff = BLEND && thr != nullptr;
+  const float th = diff ? thr[i] : 0.f;
+  for (unsigned v = blockIdx.x * blockDim.x + threadIdx.x; v < n_vec; v += gridDim.x * blockDim.x) {
+    long long xo = (long long)v * 8;
+    if (!PLAIN) {
+      const unsigned b = v / vec_per_sample, w = v - b * vec_per_sample, r = w / vec_per_row;
+      xo = b * img_bstride + (long long)r * c_in + (w - r * vec_per_row) * 8;
+    }
+    const long long po = (long long)v * 8;
+    const uint4 xraw = *(const uint4*)(img + xo);
+    float fx[8], fv[8], fs[8], fo[8];
+    alignas(16) float h1[8], h2[8], g[8];
+    unpack8(xraw, fx);
+    unpack8(*(const uint4*)(pred + po), fv);
+    if (CFG) {
+      float fu[8];
+      unpack8(*(const uint4*)(pred + pred_half + po), fu);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) fv[j] = rbf(fu[j] + rbf(sc * rbf(fv[j] - fu[j])));
+    }
+    if (t_s) unpack8(*(const uint4*)(xs + po), fs);
+    if (t_1) {
+      *(float4*)h1 = *(const float4*)(hist + s1 * slot + po);
+      *(float4*)(h1 + 4) = *(const float4*)(hist + s1 * slot + po + 4);
+    }
+    if (t_2) {
+      *(float4*)h2 = *(const float4*)(hist + s2 * slot + po);
+      *(float4*)(h2 + 4) = *(const float4*)(hist + s2 * slot + po + 4);
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      float gj = 0.f;
+      if (need_g) {
+        if (ga != 0.f) gj = (ga * fx[j]);
+        if (gb != 0.f) gj = ga != 0.f ? (gj + (gb * fv[j])) : (gb * fv[j]);
+      }
+      g[j] = gj;
+      float acc = 0.f;
+      bool have = false;
+      if (t_x) { acc = (cx * fx[j]); have = true; }
+      if (t_s) { const float t = (cs * fs[j]); acc = have ? (acc + t) : t; have = true; }
+      if (t_g) { const float t = (c0 * gj); acc = have ? (acc + t) : t; have = true; }
+      if (t_1) { const float t = (c1 * h1[j]); acc = have ? (acc + t) : t; have = true; }
+      if (t_2) { const float t = (c2 * h2[j]); acc = have ? (acc + t) : t; have = true; }
+      fo[j] = rbf(acc);
+    }
+    if (BLEND) {
+      float fz[8], fn[8], fm[8];
+      unpack8(*(const uint4*)(x0 + po), fz);
+      unpack8(*(const uint4*)(noise + po), fn);
+      unpack8(*(const uint4*)(mask + po), fm);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float p = rbf(rbf(tn * fn[j]) + rbf(om * fz[j]));
+        const float m = diff ? (fm[j] > th ? 1.f : 0.f) : fm[j];
+        fo[j] = rbf(rbf(m * fo[j]) + rbf(rbf(1.f - m) * p));
+      }
+    }
+    if (save) *(uint4*)(xs + po) = xraw;
+    if (ws >= 0) {
+      *(float4*)(hist + ws * slot + po) = *(const float4*)g;
+      *(float4*)(hist + ws * slot + po + 4) = *(const float4*)(g + 4);
+    }
+    const uint4 o = pack8(fo);
+    *(uint4*)(img + xo) = o;
+    if (CFG) *(uint4*)(img + img_half + xo) = o;
+  }
+}
 // per-step scalars kept on the device so that one captured graph serves every step:
 //   t_vec[b] = bf16(ts[*step]),  then ++*step happens in advance_step_kernel at the end of the step.
 __global__ void set_timestep_kernel(u16* __restrict__ t_vec, const float* __restrict__ ts, const int* __restrict__ step, int B) {
@@ -1008,6 +1109,38 @@ int fluxmi_k_blend_euler(void* img, const void* pred, const void* x0, const void
     if (plain) FLUXMI_BLEND_LAUNCH(false, true); else FLUXMI_BLEND_LAUNCH(false, false);
   }
 #undef FLUXMI_BLEND_LAUNCH
+  FLUXMI_LAUNCH_CHECK();
+  return 0;
+}
+int fluxmi_k_solver_step(void* img, const void* pred, void* xs, float* hist, const float* coef, const int* ctl, const void* x0, const void* noise,
+                         const void* mask, const float* tnext, const float* one_minus_tnext, const float* thr, const int* step,
+                         const float* scale, int B, long long img_rows, long long pred_rows, int c_in, int c_out, hipStream_t s) {
+  FLUXMI_REQUIRE(img && pred && xs && hist && coef && ctl, "solver_step: NULL argument");
+  FLUXMI_REQUIRE(!x0 || (noise && mask && tnext && one_minus_tnext), "solver_step: NULL argument (x0, noise, mask, tnext and one_minus_tnext go "
+                 "together)");
+  FLUXMI_REQUIRE(B >= 0 && c_out > 0 && c_out % 8 == 0 && c_in % 8 == 0 && c_out <= c_in && pred_rows >= 0 && pred_rows <= img_rows &&
+                     (c_in == c_out || pred_rows == img_rows),
+                 "solver_step: bad shape B=%d img_rows=%lld pred_rows=%lld c_in=%d c_out=%d (channels multiples of 8, c_out <= c_in, pred_rows <= "
+                 "img_rows, not both shorter and narrower)", B, img_rows, pred_rows, c_in, c_out);
+  const long long n_vec = (long long)B * pred_rows * (c_out / 8);
+  FLUXMI_REQUIRE(n_vec <= 0x7fffffffLL, "solver_step: %lld vectors exceed the kernel's 32-bit index", n_vec);
+  if (n_vec == 0) return 0;
+  const long long img_bstride = img_rows * c_in, img_half = (long long)B * img_bstride, pred_half = n_vec * 8;
+  const unsigned vps = (unsigned)(pred_rows * (c_out / 8));
+  const bool plain = c_in == c_out && pred_rows == img_rows;
+#define FLUXMI_SOLVER_LAUNCH(CFG, PLAIN, BLEND)                                                                                                \
+  hipLaunchKernelGGL((solver_step_kernel<CFG, PLAIN, BLEND>), dim3(grid_for(n_vec)), dim3(256), 0, s, (u16*)img, (const u16*)pred, (u16*)xs, \
+                     hist, coef, ctl, (const u16*)x0, (const u16*)noise, (const u16*)mask, tnext, one_minus_tnext, thr, step, scale,        \
+                     (unsigned)n_vec, vps, (unsigned)(c_out / 8), img_bstride, c_in, img_half, pred_half)
+#define FLUXMI_SOLVER_LAUNCH2(CFG, PLAIN) \
+  do { if (x0) FLUXMI_SOLVER_LAUNCH(CFG, PLAIN, true); else FLUXMI_SOLVER_LAUNCH(CFG, PLAIN, false); } while (0)
+  if (scale) {
+    if (plain) FLUXMI_SOLVER_LAUNCH2(true, true); else FLUXMI_SOLVER_LAUNCH2(true, false);
+  } else {
+    if (plain) FLUXMI_SOLVER_LAUNCH2(false, true); else FLUXMI_SOLVER_LAUNCH2(false, false);
+  }
+#undef FLUXMI_SOLVER_LAUNCH2
+#undef FLUXMI_SOLVER_LAUNCH
   FLUXMI_LAUNCH_CHECK();
   return 0;
 }

@@ -53,6 +53,7 @@ struct StepGraphs {
   bool masked = false;  // the attention kind: token-group masked or dense launches are baked into the pieces like the update kernel
   bool blend = false;   // the update kind, continued: the masked-latent blend kernel instead of the (guided) Euler kernel ...
   bool diff = false;    // ... and its differential form (the threshold table is a launch argument)
+  bool solver = false;  // ... and the table-driven solver update (fluxmi_engine_set_solver): WHICH solver is device data, not a kind
   unsigned gen = 0;     // fluxmi_tuning_generation() the pieces were captured under
   const void* cn = nullptr;  // the attached ControlNet whose launches (and workspace pointers) are baked into the pieces, or none ...
   unsigned long long cn_gen = 0;  // ... and the generation of its workspace / weight binding: process-wide unique, so a net created at a freed net's address never matches
@@ -146,6 +147,17 @@ struct fluxmi_engine {
   char* inp_mem = nullptr;
   size_t inp_bytes = 0;
   float *d_tnext = nullptr, *d_omt = nullptr, *d_thr = nullptr;
+  // solver program (fluxmi_engine_set_solver): the host tables of the following denoise calls, their device copies
+  // (an allocation of their own, staged through h_sched like dts), and the saved iterate / two fp32 history slots (xs bf16 | hist fp32 [2], each
+  // [B, Lpred, C_out]) made at the first solver call of a prepared shape and dropped with the workspace.  Nothing of it without a solver.
+  bool sol_on = false;
+  int sol_n = 0;
+  std::vector<float> sol_coef;     // [sol_n][8]
+  std::vector<int> sol_ctl;        // [sol_n][4]
+  float* d_sol_coef = nullptr;
+  int* d_sol_ctl = nullptr;
+  char* sol_mem = nullptr;
+  size_t sol_bytes = 0;
   // ControlNet (fluxmi_controlnet_create / fluxmi_engine_attach_controlnet).  A net is an engine of its own kind
   // (is_cn): no final layer, the controlnet_* projections behind the trunk's linears, the residuals of a forward in its workspace buffer
   // "cn_res" [Nd + Ns][B, Li, H].  The main engine holds the attached net (cn) and the conditioning scale (d_cn_scale, device data).
@@ -1101,6 +1113,9 @@ void free_ws(E* e) {
   if (e->fb_mem) { hipFree(e->fb_mem); e->fb_mem = nullptr; e->fb_bytes = 0; }
   if (e->inp_mem) { hipFree(e->inp_mem); e->inp_mem = nullptr; e->inp_bytes = 0; }
   e->inp_on = e->inp_diff = false;
+  if (e->sol_mem) { hipFree(e->sol_mem); e->sol_mem = nullptr; e->sol_bytes = 0; }
+  if (e->d_sol_coef) { hipFree(e->d_sol_coef); e->d_sol_coef = nullptr; e->d_sol_ctl = nullptr; }
+  e->sol_on = false;
   if (e->ws) { hipFree(e->ws); e->ws = nullptr; }
   e->bufs.clear();
   e->ws_bytes = 0;
@@ -1149,6 +1164,35 @@ int ensure_inp(E* e) {
   e->inp_bytes = 3 * one;
   const char* names[3] = {"inp_x0", "inp_noise", "inp_mask"};
   for (int i = 0; i < 3; ++i) e->bufs[names[i]] = Buf{e->inp_mem + i * one, one};
+  return 0;
+}
+
+// the solver's saved iterate and history slots of the prepared shape, made once a solver request arrives (like ensure_fb)
+int ensure_sol(E* e, hipStream_t s) {
+  if (e->sol_mem) return 0;
+  // the device tables (coef [MAX_STEPS][8] | ctl [MAX_STEPS][4]): constants like d_dts, but made here and not in the constants block, so
+  // that an engine that never sees a solver allocates what it allocated before; like the constants block, not counted as workspace
+  if (!e->d_sol_coef) {
+    if (hipMalloc((void**)&e->d_sol_coef, (size_t)MAX_STEPS * 12 * 4) != hipSuccess) {
+      (void)hipGetLastError();
+      e->d_sol_coef = nullptr;
+      fluxmi_set_error("engine_denoise: hipMalloc(%zu bytes) failed (solver tables)", (size_t)MAX_STEPS * 12 * 4);
+      return 2;
+    }
+    e->d_sol_ctl = (int*)(e->d_sol_coef + (size_t)MAX_STEPS * 8);
+  }
+  const size_t elems = (size_t)e->B * e->Lpred * c_out(e);
+  const size_t xs = (elems * 2 + 255) & ~(size_t)255, hist = (2 * elems * 4 + 255) & ~(size_t)255;
+  if (hipMalloc((void**)&e->sol_mem, xs + hist) != hipSuccess) {
+    (void)hipGetLastError();
+    e->sol_mem = nullptr;
+    fluxmi_set_error("engine_denoise: hipMalloc(%zu bytes) failed (solver buffers)", xs + hist);
+    return 2;
+  }
+  e->sol_bytes = xs + hist;
+  FLUXMI_CHECK_HIP(hipMemsetAsync(e->sol_mem, 0, xs + hist, s));
+  e->bufs["sol_xs"] = Buf{e->sol_mem, xs};
+  e->bufs["sol_hist"] = Buf{e->sol_mem + xs, hist};
   return 0;
 }
 
@@ -1269,8 +1313,8 @@ static int create_impl(const fluxmi_model_desc_t* desc, const fluxmi_linear_t* l
   e->d_cn_scale = (float*)(e->consts + o_cns);
   e->d_tnext = (float*)(e->consts + o_tnext); e->d_omt = (float*)(e->consts + o_omt); e->d_thr = (float*)(e->consts + o_thr);
   hipMemset(e->consts, 0, off);
-  // pinned staging for the schedule (ts | dts | tnext | 1 - tnext | thresholds) + the events (guard of the staging buffer, timing of the frozen steps)
-  if (hipHostMalloc((void**)&e->h_sched, 5 * (MAX_STEPS + 1) * sizeof(float), hipHostMallocDefault) != hipSuccess ||
+  // pinned staging for the schedule (ts | dts | tnext | 1 - tnext | thresholds | solver coef | solver ctl) + the events (guard of the staging buffer, timing of the frozen steps)
+  if (hipHostMalloc((void**)&e->h_sched, (5 * (MAX_STEPS + 1) + 12 * MAX_STEPS) * sizeof(float), hipHostMallocDefault) != hipSuccess ||
       hipEventCreateWithFlags(&e->ev_sched, hipEventDisableTiming) != hipSuccess || hipEventCreate(&e->ev_t0) != hipSuccess ||
       hipEventCreate(&e->ev_t1) != hipSuccess) {
     fluxmi_engine_destroy(e);
@@ -1496,7 +1540,7 @@ static void graphs_stale(fluxmi_engine_t* e, StepGraphs& g, bool cfg) {
   if (g.ok && g.gen != fluxmi_tuning_generation()) g.ok = g.warmed = e->qlut_valid = false;
   const bool diff = e->inp_on && e->inp_diff;
   // masked versus dense attention is a kind like guided versus plain, and so are the blend update and its differential form
-  if (g.cfg != cfg || g.masked != e->masked || g.blend != e->inp_on || g.diff != diff) g.ok = g.warmed = false;
+  if (g.cfg != cfg || g.masked != e->masked || g.blend != e->inp_on || g.diff != diff || g.solver != e->sol_on) g.ok = g.warmed = false;
   // ... and so is the attached ControlNet: its launches, weights and workspace pointers are baked into the pieces
   if (g.cn != e->cn || (e->cn && g.cn_gen != e->cn->ws_gen)) g.ok = g.warmed = false;
   g.cn = e->cn;
@@ -1505,6 +1549,7 @@ static void graphs_stale(fluxmi_engine_t* e, StepGraphs& g, bool cfg) {
   g.masked = e->masked;
   g.blend = e->inp_on;
   g.diff = diff;
+  g.solver = e->sol_on;
 }
 
 // Captures pieces[0 .. n) into g.exec[0 .. n) on a private non-blocking stream (the caller has synchronised its own).  The only place that
@@ -1704,7 +1749,19 @@ static int denoise_impl(fluxmi_engine_t* e, void* img, const void* txt, const vo
                  "(fluxmi_engine_set_inpaint takes the caller's images: the prepared batch, half of it for a guided call)", e->inp_B, cfg ? B / 2 : B);
   FLUXMI_REQUIRE(!e->inp_on || !e->inp_diff || (int)e->inp_thr.size() == n_steps, "engine_denoise: %d differential thresholds for a call of %d "
                  "steps (fluxmi_engine_set_inpaint takes one per step)", (int)e->inp_thr.size(), n_steps);
+  // With a solver program set (fluxmi_engine_set_solver) the ONE table-driven update replaces all of them, the blend included: a step is
+  // then one evaluation, and the d_dts table goes unused.
+  FLUXMI_REQUIRE(!e->sol_on || e->sol_n == n_steps, "engine_denoise: the solver program holds %d evaluations, this call runs %d "
+                 "(fluxmi_engine_set_solver takes one row per step of the call)", e->sol_n, n_steps);
+  FLUXMI_REQUIRE(!e->sol_on || !(e->fb_threshold > 0.f), "engine_denoise: a solver program does not combine with step caching (the cache "
+                 "compares consecutive evaluations; a solver may evaluate one time twice)");
+  if (e->sol_on) FLUXMI_TRY(ensure_sol(e, s));
   auto euler = [&](hipStream_t st) -> int {
+    if (e->sol_on)
+      return fluxmi_k_solver_step(buf<u16>(e, "img_s"), buf<u16>(e, "pred_s"), buf<u16>(e, "sol_xs"), buf<float>(e, "sol_hist"), e->d_sol_coef,
+                                  e->d_sol_ctl, e->inp_on ? buf<u16>(e, "inp_x0") : nullptr, e->inp_on ? buf<u16>(e, "inp_noise") : nullptr,
+                                  e->inp_on ? buf<u16>(e, "inp_mask") : nullptr, e->d_tnext, e->d_omt, e->inp_on && e->inp_diff ? e->d_thr : nullptr,
+                                  e->d_step, cfg ? e->d_cfg : nullptr, cfg ? B / 2 : B, Li, e->Lpred, C, c_out(e), st);
     if (e->inp_on)
       return fluxmi_k_blend_euler(buf<u16>(e, "img_s"), buf<u16>(e, "pred_s"), buf<u16>(e, "inp_x0"), buf<u16>(e, "inp_noise"),
                                   buf<u16>(e, "inp_mask"), e->d_dts, e->d_tnext, e->d_omt, e->inp_diff ? e->d_thr : nullptr, e->d_step,
@@ -1760,6 +1817,14 @@ static int denoise_impl(fluxmi_engine_t* e, void* img, const void* txt, const vo
     FLUXMI_CHECK_HIP(hipMemcpyAsync(e->d_tnext, h_tn, (n_steps + 1) * 4, hipMemcpyHostToDevice, s));
     FLUXMI_CHECK_HIP(hipMemcpyAsync(e->d_omt, h_om, (n_steps + 1) * 4, hipMemcpyHostToDevice, s));
     if (e->inp_diff) FLUXMI_CHECK_HIP(hipMemcpyAsync(e->d_thr, h_th, (n_steps + 1) * 4, hipMemcpyHostToDevice, s));
+  }
+  if (e->sol_on && n_steps > 0) {  // the solver's tables, through the same staging buffer
+    float* h_co = e->h_sched + 5 * (MAX_STEPS + 1);
+    int* h_ct = (int*)(h_co + 8 * MAX_STEPS);
+    memcpy(h_co, e->sol_coef.data(), (size_t)n_steps * 8 * 4);
+    memcpy(h_ct, e->sol_ctl.data(), (size_t)n_steps * 4 * 4);
+    FLUXMI_CHECK_HIP(hipMemcpyAsync(e->d_sol_coef, h_co, (size_t)n_steps * 8 * 4, hipMemcpyHostToDevice, s));
+    FLUXMI_CHECK_HIP(hipMemcpyAsync(e->d_sol_ctl, h_ct, (size_t)n_steps * 4 * 4, hipMemcpyHostToDevice, s));
   }
   FLUXMI_CHECK_HIP(hipEventRecord(e->ev_sched, s));
   e->sched_pending = true;
@@ -1900,6 +1965,34 @@ int fluxmi_engine_set_inpaint(fluxmi_engine_t* e, const void* x0, const void* no
   e->inp_diff = thresholds_host != nullptr;
   e->inp_B = batch;
   e->inp_thr.assign(thresholds_host, thresholds_host + (thresholds_host ? n_thresholds : 0));
+  return 0;
+}
+
+// The solver program of the following denoise calls (fluxmi.h): host tables only -- the buffers are made by the first denoise call that
+// needs them, the device copies travel with every call's schedule.
+int fluxmi_engine_set_solver(fluxmi_engine_t* e, const double* coef_host, const int* ctl_host, int n) {
+  FLUXMI_REQUIRE(e, "engine_set_solver: NULL engine");
+  if (!coef_host) {
+    e->sol_on = false;
+    e->sol_n = 0;
+    e->sol_coef.clear();
+    e->sol_ctl.clear();
+    return 0;
+  }
+  FLUXMI_REQUIRE(!e->is_cn, "engine_set_solver: a ControlNet engine steps nothing (set the solver on the main engine)");
+  FLUXMI_REQUIRE(e->ws, "engine_set_solver: call fluxmi_engine_prepare first (the program belongs to the prepared shape)");
+  FLUXMI_REQUIRE(ctl_host, "engine_set_solver: coef_host and ctl_host go together");
+  FLUXMI_REQUIRE(n >= 0 && n <= MAX_STEPS, "engine_set_solver: n=%d out of range (at most %d evaluations)", n, MAX_STEPS);
+  for (int i = 0; i < 8 * n; ++i)  // (checked as the device sees it: a finite double above FLT_MAX is inf in the fp32 table)
+    FLUXMI_REQUIRE(std::isfinite((float)coef_host[i]), "engine_set_solver: coefficient %d of row %d is not finite in fp32", i % 8, i / 8);
+  for (int i = 0; i < 4 * n; ++i)
+    FLUXMI_REQUIRE(i % 4 == 0 || (ctl_host[i] >= -1 && ctl_host[i] <= 1), "engine_set_solver: slot %d of row %d is %d (a slot is -1, 0 or 1)",
+                   i % 4, i / 4, ctl_host[i]);
+  e->sol_coef.resize((size_t)8 * n);
+  for (int i = 0; i < 8 * n; ++i) e->sol_coef[i] = (float)coef_host[i];
+  e->sol_ctl.assign(ctl_host, ctl_host + 4 * n);
+  e->sol_n = n;
+  e->sol_on = true;
   return 0;
 }
 
@@ -2088,7 +2181,7 @@ int fluxmi_engine_copy_buffer(fluxmi_engine_t* e, const char* name, long long of
 
 int fluxmi_engine_workspace_bytes(fluxmi_engine_t* e, long long* bytes) {
   FLUXMI_REQUIRE(e && bytes, "engine_workspace_bytes: NULL argument");
-  *bytes = (long long)(e->ws_bytes + e->pairs_bytes + e->mods_all_bytes + e->fb_bytes + e->inp_bytes);  // workspace + row-pair weight copies + modulation table + step cache + inpainting
+  *bytes = (long long)(e->ws_bytes + e->pairs_bytes + e->mods_all_bytes + e->fb_bytes + e->inp_bytes + e->sol_bytes);  // workspace + row-pair weight copies + modulation table + step cache + inpainting + solver buffers
   return 0;
 }
 

@@ -169,6 +169,11 @@ int fluxmi_k_cfg_euler(void* img, const void* pred, const float* dts, const int*
 int fluxmi_k_blend_euler(void* img, const void* pred, const void* x0, const void* noise, const void* mask, const float* dts, const float* tnext,
                          const float* one_minus_tnext, const float* thr, const int* step, const float* scale, int B, long long img_rows,
                          long long pred_rows, int c_in, int c_out, hipStream_t s);
+// the table-driven solver update (fluxmi.h, fluxmi_solver_step): row *step of coef [n][8] / ctl [n][4] decides the linear update of x from
+// x, the saved iterate xs, g = ga x + gb v and the two fp32 history slots; x0 != NULL appends blend_euler's blend, scale != NULL is the guided form
+int fluxmi_k_solver_step(void* img, const void* pred, void* xs, float* hist, const float* coef, const int* ctl, const void* x0, const void* noise,
+                         const void* mask, const float* tnext, const float* one_minus_tnext, const float* thr, const int* step,
+                         const float* scale, int B, long long img_rows, long long pred_rows, int c_in, int c_out, hipStream_t s);
 // first-block step cache (elementwise.hip): streaming passes over B samples of n bf16 elements, x side strided, cache side dense
 int fluxmi_k_fb_snapshot(const void* x, long long x_bstride, void* dst, int B, long long n, hipStream_t s);
 int fluxmi_k_fb_commit(const void* x, long long x_bstride, const void* r, void* r_ref, void* h1, int B, long long n, hipStream_t s);

@@ -28,6 +28,7 @@ import torch
 
 import lora_loading  # noqa: F401  (same import side as the reference)
 from fluxmi import dist as fdist
+from fluxmi import solvers
 from util import (ModelSpec, ModelVersion, engine_flow_dtype, into_device, into_dtype, load_config_from_path, load_controlnet,
                   load_models_from_config)
 
@@ -257,17 +258,20 @@ class FluxPipeline:
 
     @torch.inference_mode()
     def preprocess_latent(self, init_image=None, height: int = 720, width: int = 1024, num_steps: int = 20, strength: float = 1.0,
-                          generator: torch.Generator = None, num_images: int = 1, noise: Optional[torch.Tensor] = None):
+                          generator: torch.Generator = None, num_images: int = 1, noise: Optional[torch.Tensor] = None, sigmas=None,
+                          sigma_schedule=None):
         """reference flux_pipeline.py:459-523: noise + schedule; with an init image: VAE-encode it, start the schedule at
         t_idx = int((1 - strength) * num_steps) and blend x = t * noise + (1 - t) * latent."""
-        return self.preprocess_latent_parts(init_image, height, width, num_steps, strength, generator, num_images, noise)[:2]
+        return self.preprocess_latent_parts(init_image, height, width, num_steps, strength, generator, num_images, noise, sigmas, sigma_schedule)[:2]
 
     @torch.inference_mode()
     def preprocess_latent_parts(self, init_image=None, height: int = 720, width: int = 1024, num_steps: int = 20, strength: float = 1.0,
-                                generator: torch.Generator = None, num_images: int = 1, noise: Optional[torch.Tensor] = None):
+                                generator: torch.Generator = None, num_images: int = 1, noise: Optional[torch.Tensor] = None, sigmas=None,
+                                sigma_schedule=None):
         """preprocess_latent, with what it blends: -> (x, timesteps, latent, noise).  `latent` = the VAE latent of `init_image` [num_images,
         16, H/8, W/8] in the flow dtype (None without an init image: one encode per request), `noise` = the pure draw before the blend.
-        Masked-latent inpainting re-blends these two at every step (Flux.denoise)."""
+        Masked-latent inpainting re-blends these two at every step (Flux.denoise).  `sigmas` (num_steps + 1 values ending at 0) replaces
+        get_schedule's list; `sigma_schedule` ("karras" / "exponential") re-spaces either one (fluxmi.solvers.sigma_schedule)."""
         if init_image is not None:
             if self.ae is None:
                 raise RuntimeError("fluxmi: img2img needs an autoencoder (config.ae_path) -- none is attached")
@@ -279,6 +283,12 @@ class FluxPipeline:
         x = self.get_noise(num_images, height, width, generator=generator) if noise is None else noise
         x = x.to(device=self.device_flux, dtype=self.dtype)
         timesteps = self.get_schedule(num_steps, x.shape[-1] * x.shape[-2] // 4, shift=(self.name != "flux-schnell"))
+        if sigmas is not None:
+            if len(sigmas) != num_steps + 1:
+                raise ValueError(f"fluxmi: {len(sigmas)} sigmas for {num_steps} steps (one more than steps)")
+            timesteps = [float(v) for v in sigmas]
+        if sigma_schedule is not None:
+            timesteps = solvers.sigma_schedule(sigma_schedule, timesteps)
         if init_image is not None:
             t_idx = int((1 - strength) * num_steps)
             t = timesteps[t_idx]
@@ -653,7 +663,8 @@ class FluxPipeline:
                  true_cfg_interval=(0.0, 1.0), cache_threshold: float = 0.0, cache_max_hits: int = 0, regions=None,
                  regional_tokens: int = 128, inpaint_mask=None, inpaint_differential: bool = False, controlnet_image=None,
                  controlnet_conditioning_scale: float = 1.0, control_mode: Optional[int] = None, control_guidance_start: float = 0.0,
-                 control_guidance_end: float = 1.0, controlnet_cond: Optional[torch.Tensor] = None):
+                 control_guidance_end: float = 1.0, controlnet_cond: Optional[torch.Tensor] = None, sampler: str = "euler",
+                 sigma_schedule: Optional[str] = None, sigmas=None):
         """`reference_image` (FLUX.1 Kontext [dev] instruction editing): an image the prompt describes an edit of, in any form `init_image`
         takes; see prepare_kontext_reference.  Composes with `init_image` / `strength` unchanged.
         FLUX.1 Fill [dev] (a model with 320 conditioning channels): `init_image` is the image to inpaint and `mask_image` (white =
@@ -704,7 +715,30 @@ class FluxPipeline:
         or (i + 1) / n > end) -- run as consecutive denoise calls on slices of the schedule, like `true_cfg_interval`.  Composes with img2img,
         num_images, `noise=`, LoRA on the main model, Redux (the net sees the same text rows), a negative prompt (both branches are
         controlled) and `inpaint_mask`; refused with `regions`, `cache_threshold` > 0, `reference_image` and a Fill / Depth / Canny model.
-        Without it the request is today's, launch for launch."""
+        Without it the request is today's, launch for launch.
+        `sampler`: "euler" (the default: today's kernels, launch for launch), "heun" (diffusers' FlowMatchHeunDiscreteScheduler: two model
+        evaluations per step but the last), "midpoint" (RK2, two evaluations per step), "ab2" (Adams-Bashforth 2, one evaluation per step)
+        or "dpmpp_2m" (DPM-Solver++(2M), one evaluation per step); see fluxmi.solvers.  `sigmas` (diffusers' argument): the request's own
+        descending list in (0, 1], with or without a trailing 0, instead of get_schedule's -- `num_steps` then follows its length.
+        `sigma_schedule`: "karras" (rho 7) or "exponential" re-spaces the schedule between its first and last non-zero value.  The program is
+        built from the final timestep list, after the `strength` truncation; where `true_cfg_interval` or the control guidance interval
+        cuts the request into several denoise calls, each call gets the program of its own slice (a multistep solver restarts with a
+        first-order step there).  Composes with everything above except `cache_threshold` > 0, which a non-Euler sampler refuses.  Image
+        quality per sampler on real FLUX weights is not established here; no sampler or step count is recommended."""
+        if sampler not in solvers.SAMPLERS:
+            raise ValueError(f"fluxmi: sampler={sampler!r}: expected one of {solvers.SAMPLERS}")
+        if sigma_schedule not in solvers.SIGMA_SCHEDULES:
+            raise ValueError(f"fluxmi: sigma_schedule={sigma_schedule!r}: expected one of {solvers.SIGMA_SCHEDULES}")
+        if sigmas is not None:
+            sigmas = solvers.custom_sigmas(sigmas)
+        try:
+            cache_on = float(cache_threshold) > 0
+        except (TypeError, ValueError):
+            cache_on = False  # (refused below, with its own message)
+        if sampler != "euler" and cache_on:
+            raise ValueError(f"fluxmi: sampler={sampler!r} does not combine with cache_threshold > 0 (the step cache compares consecutive "
+                             "evaluations; a solver may evaluate one time twice)")
+        sched_kw = {k: v for k, v in (("sigmas", sigmas), ("sigma_schedule", sigma_schedule)) if v is not None}
         cn_on = controlnet_image is not None or controlnet_cond is not None
         if cn_on:
             if getattr(self, "controlnet", None) is None:
@@ -793,6 +827,8 @@ class FluxPipeline:
             if img_cond is None and kind == "control" and control_image is None:
                 raise ValueError("fluxmi: FLUX.1 Depth / Canny needs control_image (the depth map or edge map)")
         num_steps = 4 if self.name == "flux-schnell" else num_steps
+        if sigmas is not None:
+            num_steps = len(sigmas) - 1
         init_image = self.load_init_image_if_needed(init_image) if init_image is not None else None
         fill_image = init_image if kind == "fill" else None
         if fill_image is not None and strength == 1.0 and inpaint_mask is None:
@@ -814,10 +850,10 @@ class FluxPipeline:
         inp_mask = self.prepare_inpaint_mask(inpaint_mask, height, width, bool(inpaint_differential)) if inpaint_mask is not None else None
         if inp_mask is None:
             noise, timesteps = self.preprocess_latent(init_image=init_image, height=height, width=width, num_steps=num_steps, strength=strength,
-                                                      generator=generator, num_images=num_images, noise=noise)
+                                                      generator=generator, num_images=num_images, noise=noise, **sched_kw)
         else:
             noise, timesteps, inp_x0, inp_noise = self.preprocess_latent_parts(init_image=init_image, height=height, width=width, num_steps=num_steps,
-                                                                               strength=strength, generator=generator, num_images=num_images, noise=noise)
+                                                                               strength=strength, generator=generator, num_images=num_images, noise=noise, **sched_kw)
         img, img_ids, vec, txt, txt_ids = map(lambda x: x.contiguous(), self.prepare(noise, prompt))
         num_images = img.shape[0]  # a list prompt with num_images == 1 sizes the batch (prepare)
         inpaint = None
@@ -943,6 +979,8 @@ class FluxPipeline:
                         kw = dict(kw, inpaint_x0=x0_, inpaint_noise=noise_, inpaint_mask=mask_)
                         if thr is not None:
                             kw["inpaint_thresholds"] = thr[a:b]  # each denoise call gets its slice of the request's table
+                    if sampler != "euler":  # ... and the program of its slice of the schedule
+                        kw = dict(kw, solver=solvers.build_program(sampler, timesteps[a:b + 1]))
                     latents = self.model.denoise(latents, img_ids, txt, txt_ids, vec, timesteps[a:b + 1], guidance=guidance, use_graph=use_graph,
                                                  **cond, **kw, **cache)
         if world > 1:

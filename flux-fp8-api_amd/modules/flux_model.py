@@ -380,6 +380,16 @@ class Flux(nn.Module):
         _lib.call("fluxmi_engine_set_inpaint", self._engine, ops._p(x0), ops._p(noise), ops._p(mask), x0.shape[0], table,
                   len(thr) if thr is not None else 0, ops._stream())
 
+    def _set_solver(self, solver):
+        """after _prepare, under the lock: the solver program of this call (fluxmi.solvers.SolverProgram), or None = off"""
+        if solver is None:
+            _lib.call("fluxmi_engine_set_solver", self._engine, None, None, 0)
+            return
+        n = len(solver.coef)
+        coef = (C.c_double * max(1, 8 * n))(*[float(v) for row in solver.coef for v in row])
+        ctl = (C.c_int * max(1, 4 * n))(*[int(v) for row in solver.ctl for v in row])
+        _lib.call("fluxmi_engine_set_solver", self._engine, coef, ctl, n)
+
     @staticmethod
     def _with_reference(img, img_ids, img_cond_seq, img_cond_seq_ids):
         """FLUX.1 Kontext: the reference tokens ride behind the noisy tokens of each sample -> (stream, stream ids, Lc).  Both None: unchanged."""
@@ -621,7 +631,7 @@ class Flux(nn.Module):
                 img_cond_seq_ids: Tensor | None = None, img_cond: Tensor | None = None, neg_txt: Tensor | None = None,
                 neg_y: Tensor | None = None, cfg_scale: float = 1.0, cache_threshold: float = 0.0, cache_max_hits: int = 0,
                 attn_groups: Tensor | None = None, inpaint_x0: Tensor | None = None, inpaint_noise: Tensor | None = None,
-                inpaint_mask: Tensor | None = None, inpaint_thresholds=None, controlnet=None) -> Tensor:
+                inpaint_mask: Tensor | None = None, inpaint_thresholds=None, controlnet=None, solver=None) -> Tensor:
         """The Euler loop of FluxPipeline.generate (reference flux_pipeline.py:619-651) run natively: calibrating
         steps unfused, every later step one replay of a captured hipGraph.  Returns the final latent tokens.
         FLUX.1 Kontext: with `img_cond_seq` / `img_cond_seq_ids` the reference tokens join every step's forward and are never stepped; the
@@ -647,8 +657,28 @@ class Flux(nn.Module):
         float32(m) > float32(thresholds[i]) instead of m.  The caller's tensors are not modified.
         `controlnet`: a modules.controlnet.ControlNetCall (Flux.forward): every step runs the ControlNet, then the main model with the
         residual adds, then the update the request already had -- one captured graph per frozen step once BOTH nets are calibrated; a guided
-        request controls both branches.  Refused with a Kontext reference, attn_groups, cache_threshold > 0 and channel-conditioned models."""
-        inpaint = self._check_inpaint(img, inpaint_x0, inpaint_noise, inpaint_mask, inpaint_thresholds, len(timesteps) - 1)
+        request controls both branches.  Refused with a Kontext reference, attn_groups, cache_threshold > 0 and channel-conditioned models.
+        `solver`: a fluxmi.solvers.SolverProgram built from `timesteps` (build_program): every update -- calibrating, replayed, guided,
+        masked -- is then the table-driven kernel (csrc/elementwise.hip, solver_step_kernel) on the program's rows, one engine step per model
+        EVALUATION at `solver.times`; `inpaint_thresholds` stays one per user step and is expanded through `solver.step_of_eval`.  Refused
+        with cache_threshold > 0: the cache compares consecutive evaluations, and Heun evaluates one time twice.  None = today's call."""
+        n_user = len(timesteps) - 1
+        if solver is not None:
+            if cache_threshold and float(cache_threshold) > 0:
+                raise ValueError("fluxmi: a sampler other than euler does not combine with cache_threshold > 0 (the step cache compares "
+                                 "consecutive evaluations; a solver may evaluate one time twice)")
+            n_eval = len(solver.coef)
+            if len(solver.times) != n_eval + 1 or len(solver.ctl) != n_eval or len(solver.step_of_eval) != n_eval:
+                raise ValueError(f"solver: {len(solver.times)} times, {len(solver.ctl)} ctl rows and {len(solver.step_of_eval)} step indices for "
+                                 f"{n_eval} evaluations")
+            if (max(solver.step_of_eval) + 1 if n_eval else 0) != n_user:
+                raise ValueError(f"solver: a program of {max(solver.step_of_eval) + 1 if n_eval else 0} steps for {n_user} steps of timesteps "
+                                 f"(build it from the same list)")
+            ts_f = [float(t) for t in timesteps]
+            inside = all(ts_f[i + 1] <= float(solver.times[j]) <= ts_f[i] for j, i in enumerate(solver.step_of_eval))
+            if not inside or float(solver.times[-1]) != ts_f[-1]:
+                raise ValueError("solver: the program's evaluation times do not lie inside the steps of timesteps (build it from the same list)")
+        inpaint = self._check_inpaint(img, inpaint_x0, inpaint_noise, inpaint_mask, inpaint_thresholds, n_user)
         cache_threshold, cache_max_hits = float(cache_threshold), int(cache_max_hits)
         if not (math.isfinite(cache_threshold) and cache_threshold >= 0.0) or cache_max_hits < 0:
             raise ValueError(f"cache_threshold {cache_threshold} must be finite and >= 0 (0 = off), cache_max_hits {cache_max_hits} >= 0 (0 = no bound)")
@@ -697,10 +727,16 @@ class Flux(nn.Module):
                                 inpaint_thresholds=inpaint[3])
                 if cn is not None:
                     cond["controlnet"] = type(controlnet)(cn[0], pick(cn[1]), cn[3], cn[2])
+                if solver is not None:
+                    cond["solver"] = solver
                 o = self.denoise(pick(img), pick(img_ids), pick(txt), pick(txt_ids), pick(y), timesteps, guidance=guidance, use_graph=use_graph,
                                  cache_threshold=cache_threshold, cache_max_hits=cache_max_hits, **cond)
                 outs.append(o[:per - pad])
             return torch.cat(outs, 0)
+        if solver is not None:  # one engine step per evaluation: the program's times, the thresholds of each evaluation's user step
+            timesteps = list(solver.times)
+            if inpaint is not None and inpaint[3] is not None:
+                inpaint = inpaint[:3] + ([inpaint[3][k] for k in solver.step_of_eval],)
         Li = img.shape[1]
         img, img_ids, Lc = self._with_reference(stream, img_ids, img_cond_seq, img_cond_seq_ids)
         img = bf(img).clone()
@@ -719,6 +755,7 @@ class Flux(nn.Module):
             ts = (C.c_double * len(timesteps))(*[float(t) for t in timesteps])
             _lib.call("fluxmi_engine_set_step_cache", self._engine, cache_threshold, cache_max_hits)
             self._set_inpaint(inpaint, img.device)
+            self._set_solver(solver)
             net = self._attach_controlnet(cn, img.device)
             try:
                 if guided:
@@ -729,6 +766,8 @@ class Flux(nn.Module):
                               len(timesteps) - 1, C.byref(t_io), int(use_graph), ops._stream())
             finally:
                 self._release_controlnet(net)
+                if solver is not None:
+                    self._set_solver(None)
             if trial is not None:
                 self._advance_calibration(t_io.value)
         if self.in_channels != self.out_channels:

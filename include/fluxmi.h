@@ -399,6 +399,23 @@ int fluxmi_cfg_euler(void* img, const void* pred, const float* dts, const int* s
 int fluxmi_blend_euler(void* img, const void* pred, const void* x0, const void* noise, const void* mask, const float* dts, const float* tnext,
                        const float* one_minus_tnext, const float* thr, const int* step, const float* scale, int B, long long img_rows,
                        long long pred_rows, int c_in, int c_out, void* stream);
+/* The table-driven solver update (higher-order samplers): one linear update whose coefficients are DEVICE tables indexed
+ * by *step like dts (step NULL: row 0), so the caller's tables decide which solver runs.  img, pred, step, scale, B, img_rows, pred_rows, c_in,
+ * c_out as for fluxmi_blend_euler (scale == NULL: unguided on [B, ...]; else guided on [2B, ...], x read from the prompt half, x' written to
+ * both).  xs: bf16 [B, pred_rows, c_out], a saved iterate; hist: fp32 [2][B, pred_rows, c_out], two history slots; coef: fp32 [n][8] =
+ * {cx, cs, c0, c1, c2, ga, gb, 0}; ctl: int32 [n][4] = {save_xs, w_slot, h1_slot, h2_slot}, a slot is -1, 0 or 1.  Per predicted element:
+ *   v   = pred                          (guided: fluxmi_cfg_euler's bf16 chain d, m, p)
+ *   g   = ga * x + gb * v               fp32
+ *   acc = cx * x + cs * xs + c0 * g + c1 * hist[h1_slot] + c2 * hist[h2_slot]      fp32, left to right
+ *   x1  = bf16(acc)
+ * Every product and every sum is rounded to fp32 on its own (no fma).  A term whose coefficient is exactly 0.0f or whose slot is -1 is
+ * skipped and its buffer never read (it may hold anything); the sum starts at the first term present.  x0 != NULL (with noise, mask, tnext,
+ * one_minus_tnext, optionally thr: fluxmi_blend_euler's operands): its blend then runs on x1, same roundings, same differential compare.
+ * After all reads of the element: save_xs stores the pre-update x to xs, w_slot >= 0 stores g to hist[w_slot] (which may be a slot just
+ * read), x' goes to img.  Reference rows and conditioning channels are neither read nor written; 16-byte accesses. */
+int fluxmi_solver_step(void* img, const void* pred, void* xs, float* hist, const float* coef, const int* ctl, const void* x0, const void* noise,
+                       const void* mask, const float* tnext, const float* one_minus_tnext, const float* thr, const int* step, const float* scale,
+                       int B, long long img_rows, long long pred_rows, int c_in, int c_out, void* stream);
 
 /* ---- first-block step cache: the streaming passes --------------------------------------
  * B samples of n bf16 elements each (n = cached rows x hidden, n %% 8 == 0).  The `x` side is the residual stream: the pointer is the first
@@ -575,6 +592,17 @@ int fluxmi_engine_step_cache_log(fluxmi_engine_t* e, int* n, int* batch, float* 
  * never replay each other's graph.  A request without a mask allocates and launches nothing of this.  Call it after fluxmi_engine_prepare*. */
 int fluxmi_engine_set_inpaint(fluxmi_engine_t* e, const void* x0, const void* noise, const void* mask, int batch, const double* thresholds_host,
                               int n_thresholds, void* stream);
+/* A solver program (higher-order samplers) for the following fluxmi_engine_denoise / _denoise_cfg calls on the PREPARED
+ * shape: every update of those calls -- calibrating, graph-replayed, guided, with the inpainting state set -- is fluxmi_solver_step on the
+ * tables given here instead of the (guided / blend) Euler kernel.  coef_host: n x 8 doubles, ctl_host: n x 4 ints, the rows of
+ * fluxmi_solver_step (cast to fp32 here), n <= 1024.  An engine "step" is then one EVALUATION of the model: timesteps_host[j] is the model
+ * time of evaluation j and timesteps_host[j + 1] the time of the iterate it produces (what the blend's tnext table reads); the dts table is
+ * unused, and a denoise call whose n_steps != n is refused, as is one with step caching on.  The tables are device data carried through the
+ * pinned schedule staging like dts: solver on / off is a kind of step graph like guided versus plain, and ONE graph serves every solver and
+ * every schedule of a length.  The buffers "sol_xs" and "sol_hist" are allocated at the first solver call of a prepared shape, dropped
+ * with the workspace and counted in fluxmi_engine_workspace_bytes.  coef_host == NULL switches the feature off; a prepare that re-allocates
+ * the workspace does too.  A request without a solver allocates nothing and launches exactly what it launched before. */
+int fluxmi_engine_set_solver(fluxmi_engine_t* e, const double* coef_host, const int* ctl_host, int n);
 /* Test hook: phases [phase_from, phase_to] of ONE frozen forward on the engine's own buffers, mode 1 (fused) or 2 (unfused, frozen scales):
  *   0 img_in + txt_in on the request buffers "img_s" / "txt_s" (mode 1: the cached "txt_emb" of the last denoise call) + this step's
  *     modulation vectors out of the step-ahead table the last denoise call left (step = the request's step index, written to the device-side

@@ -14,6 +14,8 @@ Same two POST endpoints, request fields, defaults and status codes:
              inpaint_differential=None (differential diffusion: the mask is a grey change map) -- each passed on only when set;
              sampler=None ("euler" | "heun" | "midpoint" | "ab2" | "dpmpp_2m"), sigma_schedule=None ("karras" | "exponential"),
              sigmas=None (the request's own descending list in (0, 1]; num_steps follows it) -- each passed on only when set;
+             sampler also "euler_ancestral" | "dpmpp_2m_sde" (stochastic), with eta=None (0..1), s_noise=None (>= 0), noise_seed=None (the
+             key of the in-kernel noise; default the request's seed) -- each passed on only when set;
              a region with both or neither of box / mask, or a box outside 0 <= x0 < x1 <= 1, is a 422}
              ->  image/jpeg stream of FluxPipeline.generate(**args)                                               (reference api.py:54-86)
   /lora      LoraArgs{scale=1.0, path, name, action="load"|"unload"}  ->  {"status": "success"} | 400 invalid action | 500 with the
@@ -79,9 +81,12 @@ class GenerateArgs(BaseModel):
     control_mode: Optional[int] = Field(default=None, ge=0)  # ... the control mode of a Union net
     control_guidance_start: Optional[float] = Field(default=None, ge=0.0, le=1.0)  # ... the fraction of the steps at which it switches on
     control_guidance_end: Optional[float] = Field(default=None, ge=0.0, le=1.0)  # ... and off (diffusers' names)
-    sampler: Optional[Literal["euler", "heun", "midpoint", "ab2", "dpmpp_2m"]] = None  # the ODE solver (default euler; fluxmi.solvers)
+    sampler: Optional[Literal["euler", "heun", "midpoint", "ab2", "dpmpp_2m", "euler_ancestral", "dpmpp_2m_sde"]] = None  # the solver (default euler; fluxmi.solvers)
     sigma_schedule: Optional[Literal["karras", "exponential"]] = None  # re-space the schedule between its first and last non-zero sigma
     sigmas: Optional[List[float]] = Field(default=None, min_length=1)  # the request's own sigma list (diffusers' argument)
+    eta: Optional[float] = Field(default=None, ge=0.0, le=1.0)  # stochastic samplers: the share of each step's noise that is re-drawn
+    s_noise: Optional[float] = Field(default=None, ge=0.0)  # ... a factor on the drawn noise
+    noise_seed: Optional[int] = Field(default=None, ge=0, lt=2 ** 64)  # ... the key of the in-kernel noise (default: the request's seed)
 
 
 app = FastAPI(title="fluxmi")
@@ -98,7 +103,7 @@ def generate(args: GenerateArgs):
     for k in ("reference_image", "mask_image", "control_image", "redux_image", "negative_prompt", "true_cfg_scale", "true_cfg_interval",
               "cache_threshold", "cache_max_hits", "regions", "regional_tokens", "inpaint_mask", "inpaint_differential", "controlnet_image",
               "controlnet_conditioning_scale", "control_mode", "control_guidance_start", "control_guidance_end", "sampler", "sigma_schedule",
-              "sigmas"):
+              "sigmas", "eta", "s_noise", "noise_seed"):
         if kwargs.get(k) is None:
             kwargs.pop(k, None)
     if "regions" in kwargs:

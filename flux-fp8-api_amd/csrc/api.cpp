@@ -240,6 +240,16 @@ int fluxmi_solver_step(void* img, const void* pred, void* xs, float* hist, const
   return fluxmi_k_solver_step(img, pred, xs, hist, coef, ctl, x0, noise, mask, tnext, one_minus_tnext, thr, step, scale, B, img_rows, pred_rows,
                               c_in, c_out, (hipStream_t)stream);
 }
+int fluxmi_solver_step_noise(void* img, const void* pred, void* xs, float* hist, const float* coef, const int* ctl, const void* x0,
+                             const void* noise, const void* mask, const float* tnext, const float* one_minus_tnext, const float* thr, const int* step,
+                             const float* scale, int B, long long img_rows, long long pred_rows, int c_in, int c_out, const unsigned* ids,
+                             const int* eval_offset, void* stream) {
+  return fluxmi_k_solver_step_noise(img, pred, xs, hist, coef, ctl, x0, noise, mask, tnext, one_minus_tnext, thr, step, scale, B, img_rows,
+                                    pred_rows, c_in, c_out, ids, eval_offset, (hipStream_t)stream);
+}
+int fluxmi_philox_normal(void* out, const unsigned* ids, int B, long long n_per_image, unsigned eval, int raw, void* stream) {
+  return fluxmi_k_philox_normal(out, ids, B, n_per_image, eval, raw, (hipStream_t)stream);
+}
 
 int fluxmi_fb_snapshot(const void* x, long long x_bstride, void* dst, int B, long long n, void* stream) {
   return fluxmi_k_fb_snapshot(x, x_bstride, dst, B, n, (hipStream_t)stream);

@@ -645,6 +645,68 @@ __global__ void __launch_bounds__(256) blend_euler_kernel(u16* __restrict__ img,
     if (CFG) *(uint4*)(img + img_half + xo) = o;
   }
 }
+// Counter-based Gaussian noise for the stochastic samplers: Philox4x32-10 (Salmon et al., SC'11; the published
+// multipliers and key increments) and Box-Muller.  One call = one 128-bit block = four normals; counter and key are the caller's, so the
+// draw is a pure function of them -- no state, no order, the same bits from every kernel that inlines this.
+__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned w[4]) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const unsigned h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0, h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+    c0 = h1 ^ c1 ^ k0;
+    c1 = l1;
+    c2 = h0 ^ c3 ^ k1;
+    c3 = l0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  w[0] = c0; w[1] = c1; w[2] = c2; w[3] = c3;
+}
+// words -> normals: u = ((w_even >> 9) + 0.5) 2^-23 in (0, 1) and t = (w_odd >> 8) 2^-24 in [0, 1), both exact in fp32;
+// r = sqrt(-2 log u), (s, c) = sincospi(2 t); z = r c, r s from (w0, w1), then from (w2, w3).  No fast-math, no contraction.
+__device__ __forceinline__ void philox_box_muller(const unsigned w[4], float z[4]) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int p = 0; p < 2; ++p) {
+    const float u = ((float)(w[2 * p] >> 9) + 0.5f) * 0x1p-23f;
+    const float t = (float)(w[2 * p + 1] >> 8) * 0x1p-24f;
+    const float r = sqrtf(-2.f * logf(u));
+    float sn, cs;
+    sincospif(2.f * t, &sn, &cs);
+    z[2 * p] = r * cs;
+    z[2 * p + 1] = r * sn;
+  }
+}
+// the eight normals of vector `vec` (elements [8 vec, 8 vec + 8) of an image's dense block): Philox blocks q = 2 vec and 2 vec + 1 of
+// counter (q, eval, id[2], id[3]) under key (id[0], id[1])
+__device__ __forceinline__ void philox_normal8(const unsigned* __restrict__ id, unsigned vec, unsigned eval, float z[8]) {
+  const unsigned k0 = id[0], k1 = id[1], c2 = id[2], c3 = id[3];
+  unsigned w[4];
+  philox4x32_10(2 * vec, eval, c2, c3, k0, k1, w);
+  philox_box_muller(w, z);
+  philox4x32_10(2 * vec + 1, eval, c2, c3, k0, k1, w);
+  philox_box_muller(w, z + 4);
+}
+// fluxmi_philox_normal: the generator alone, for tests and tools.  out [B][vec_per_sample * 8]: RAW the uint32 words, else the fp32 normals.
+template <bool RAW>
+__global__ void __launch_bounds__(256) philox_normal_kernel(void* __restrict__ out, const unsigned* __restrict__ ids, unsigned n_vec,
+                                                            unsigned vec_per_sample, unsigned eval) {
+  for (unsigned v = blockIdx.x * blockDim.x + threadIdx.x; v < n_vec; v += gridDim.x * blockDim.x) {
+    const unsigned b = v / vec_per_sample, w = v - b * vec_per_sample;
+    const unsigned* id = ids + 4 * b;
+    if (RAW) {
+      unsigned r[4];
+      philox4x32_10(2 * w, eval, id[2], id[3], id[0], id[1], r);
+      ((uint4*)out)[2 * (size_t)v] = make_uint4(r[0], r[1], r[2], r[3]);
+      philox4x32_10(2 * w + 1, eval, id[2], id[3], id[0], id[1], r);
+      ((uint4*)out)[2 * (size_t)v + 1] = make_uint4(r[0], r[1], r[2], r[3]);
+    } else {
+      float z[8];
+      philox_normal8(id, w, eval, z);
+      ((float4*)out)[2 * (size_t)v] = make_float4(z[0], z[1], z[2], z[3]);
+      ((float4*)out)[2 * (size_t)v + 1] = make_float4(z[4], z[5], z[6], z[7]);
+    }
+  }
+}
 // The table-driven solver update (higher-order samplers): ONE linear update whose coefficients are device data, so the
 // engine never knows which solver runs.  Row j = *step of coef [n][8] = {cx, cs, c0, c1, c2, ga, gb, 0} and ctl [n][4] = {save_xs, w_slot,
 // h1_slot, h2_slot}; per predicted element, v = pred (CFG: cfg_euler_kernel's bf16 chain),
@@ -657,7 +719,11 @@ __global__ void __launch_bounds__(256) blend_euler_kernel(u16* __restrict__ img,
 // is present (0 when none is).  After all reads of the element: save_xs stores the pre-update x to xs, w_slot >= 0 stores g to
 // hist[w_slot] (which may be a slot just read), x' goes to img (CFG: both halves).  xs bf16 and hist fp32 [2][...] are dense like the prompt
 // half of pred; the indexing is cfg_euler_kernel's.  The row is uniform over the launch: every branch below is.
-template <bool CFG, bool PLAIN, bool BLEND>
+// NOISE (fluxmi_solver_step_noise; the stochastic samplers): column 7 of the row is cn, and one last term follows the c2 term,
+//   acc = acc + (cn * z),   z = philox_normal8(ids[b], vector within the image, *step + *eval_offset)
+// b the IMAGE (CFG: one draw per image, x' goes to both halves as before).  cn == 0.0f: skipped like every absent term -- ids is not
+// read, no generator work -- so the result is the NOISE = false kernel's, which ignores column 7.
+template <bool CFG, bool PLAIN, bool BLEND, bool NOISE>
 __global__ void __launch_bounds__(256) solver_step_kernel(u16* __restrict__ img, const u16* __restrict__ pred, u16* __restrict__ xs,
                                                           float* __restrict__ hist, const float* __restrict__ coef, const int* __restrict__ ctl,
                                                           const u16* __restrict__ x0, const u16* __restrict__ noise, const u16* __restrict__ mask,
@@ -665,11 +731,15 @@ __global__ void __launch_bounds__(256) solver_step_kernel(u16* __restrict__ img,
                                                           const float* __restrict__ thr, const int* __restrict__ step,
                                                           const float* __restrict__ scale, unsigned n_vec, unsigned vec_per_sample,
                                                           unsigned vec_per_row, long long img_bstride, int c_in, long long img_half,
-                                                          long long pred_half) {
+                                                          long long pred_half, const unsigned* __restrict__ ids,
+                                                          const int* __restrict__ eval_offset) {
 #pragma clang fp contract(off)
   const int i = step ? *step : 0;
   const float cx = coef[8 * i], cs = coef[8 * i + 1], c0 = coef[8 * i + 2], c1 = coef[8 * i + 3], c2 = coef[8 * i + 4], ga = coef[8 * i + 5],
               gb = coef[8 * i + 6];
+  const float cn = NOISE ? coef[8 * i + 7] : 0.f;
+  const bool t_n = NOISE && cn != 0.f;
+  const unsigned eval = NOISE ? (unsigned)i + (unsigned)(eval_offset ? *eval_offset : 0) : 0u;
   const bool save = ctl[4 * i] != 0;
   // a slot is -1, 0 or 1: anything above is read as 1, so that no table can index past the two slots
   const int ws = min(ctl[4 * i + 1], 1), s1 = min(ctl[4 * i + 2], 1), s2 = min(ctl[4 * i + 3], 1);
@@ -688,7 +758,7 @@ __global__ void __launch_bounds__(256) solver_step_kernel(u16* __restrict__ img,
     }
     const long long po = (long long)v * 8;
     const uint4 xraw = *(const uint4*)(img + xo);
-    float fx[8], fv[8], fs[8], fo[8];
+    float fx[8], fv[8], fs[8], fo[8], zn[8];
     alignas(16) float h1[8], h2[8], g[8];
     unpack8(xraw, fx);
     unpack8(*(const uint4*)(pred + po), fv);
@@ -697,6 +767,10 @@ __global__ void __launch_bounds__(256) solver_step_kernel(u16* __restrict__ img,
       unpack8(*(const uint4*)(pred + pred_half + po), fu);
 #pragma unroll
       for (int j = 0; j < 8; ++j) fv[j] = rbf(fu[j] + rbf(sc * rbf(fv[j] - fu[j])));
+    }
+    if (t_n) {
+      const unsigned b = v / vec_per_sample;
+      philox_normal8(ids + 4 * b, v - b * vec_per_sample, eval, zn);
     }
     if (t_s) unpack8(*(const uint4*)(xs + po), fs);
     if (t_1) {
@@ -722,6 +796,7 @@ __global__ void __launch_bounds__(256) solver_step_kernel(u16* __restrict__ img,
       if (t_g) { const float t = (c0 * gj); acc = have ? (acc + t) : t; have = true; }
       if (t_1) { const float t = (c1 * h1[j]); acc = have ? (acc + t) : t; have = true; }
       if (t_2) { const float t = (c2 * h2[j]); acc = have ? (acc + t) : t; have = true; }
+      if (t_n) { const float t = (cn * zn[j]); acc = have ? (acc + t) : t; have = true; }
       fo[j] = rbf(acc);
     }
     if (BLEND) {
@@ -1112,9 +1187,11 @@ int fluxmi_k_blend_euler(void* img, const void* pred, const void* x0, const void
   FLUXMI_LAUNCH_CHECK();
   return 0;
 }
-int fluxmi_k_solver_step(void* img, const void* pred, void* xs, float* hist, const float* coef, const int* ctl, const void* x0, const void* noise,
-                         const void* mask, const float* tnext, const float* one_minus_tnext, const float* thr, const int* step,
-                         const float* scale, int B, long long img_rows, long long pred_rows, int c_in, int c_out, hipStream_t s) {
+// the launcher of fluxmi_k_solver_step (ids == NULL: the deterministic kernel, column 7 ignored) and fluxmi_k_solver_step_noise
+static int solver_step_launch(void* img, const void* pred, void* xs, float* hist, const float* coef, const int* ctl, const void* x0,
+                              const void* noise, const void* mask, const float* tnext, const float* one_minus_tnext, const float* thr,
+                              const int* step, const float* scale, int B, long long img_rows, long long pred_rows, int c_in, int c_out,
+                              const unsigned* ids, const int* eval_offset, hipStream_t s) {
   FLUXMI_REQUIRE(img && pred && xs && hist && coef && ctl, "solver_step: NULL argument");
   FLUXMI_REQUIRE(!x0 || (noise && mask && tnext && one_minus_tnext), "solver_step: NULL argument (x0, noise, mask, tnext and one_minus_tnext go "
                  "together)");
@@ -1128,19 +1205,53 @@ int fluxmi_k_solver_step(void* img, const void* pred, void* xs, float* hist, con
   const long long img_bstride = img_rows * c_in, img_half = (long long)B * img_bstride, pred_half = n_vec * 8;
   const unsigned vps = (unsigned)(pred_rows * (c_out / 8));
   const bool plain = c_in == c_out && pred_rows == img_rows;
-#define FLUXMI_SOLVER_LAUNCH(CFG, PLAIN, BLEND)                                                                                                \
-  hipLaunchKernelGGL((solver_step_kernel<CFG, PLAIN, BLEND>), dim3(grid_for(n_vec)), dim3(256), 0, s, (u16*)img, (const u16*)pred, (u16*)xs, \
-                     hist, coef, ctl, (const u16*)x0, (const u16*)noise, (const u16*)mask, tnext, one_minus_tnext, thr, step, scale,        \
-                     (unsigned)n_vec, vps, (unsigned)(c_out / 8), img_bstride, c_in, img_half, pred_half)
+#define FLUXMI_SOLVER_LAUNCH(CFG, PLAIN, BLEND, NOISE)                                                                                          \
+  hipLaunchKernelGGL((solver_step_kernel<CFG, PLAIN, BLEND, NOISE>), dim3(grid_for(n_vec)), dim3(256), 0, s, (u16*)img, (const u16*)pred,       \
+                     (u16*)xs, hist, coef, ctl, (const u16*)x0, (const u16*)noise, (const u16*)mask, tnext, one_minus_tnext, thr, step, scale, \
+                     (unsigned)n_vec, vps, (unsigned)(c_out / 8), img_bstride, c_in, img_half, pred_half, ids, eval_offset)
+#define FLUXMI_SOLVER_LAUNCH3(CFG, PLAIN, BLEND) \
+  do { if (ids) FLUXMI_SOLVER_LAUNCH(CFG, PLAIN, BLEND, true); else FLUXMI_SOLVER_LAUNCH(CFG, PLAIN, BLEND, false); } while (0)
 #define FLUXMI_SOLVER_LAUNCH2(CFG, PLAIN) \
-  do { if (x0) FLUXMI_SOLVER_LAUNCH(CFG, PLAIN, true); else FLUXMI_SOLVER_LAUNCH(CFG, PLAIN, false); } while (0)
+  do { if (x0) FLUXMI_SOLVER_LAUNCH3(CFG, PLAIN, true); else FLUXMI_SOLVER_LAUNCH3(CFG, PLAIN, false); } while (0)
   if (scale) {
     if (plain) FLUXMI_SOLVER_LAUNCH2(true, true); else FLUXMI_SOLVER_LAUNCH2(true, false);
   } else {
     if (plain) FLUXMI_SOLVER_LAUNCH2(false, true); else FLUXMI_SOLVER_LAUNCH2(false, false);
   }
 #undef FLUXMI_SOLVER_LAUNCH2
+#undef FLUXMI_SOLVER_LAUNCH3
 #undef FLUXMI_SOLVER_LAUNCH
+  FLUXMI_LAUNCH_CHECK();
+  return 0;
+}
+int fluxmi_k_solver_step(void* img, const void* pred, void* xs, float* hist, const float* coef, const int* ctl, const void* x0, const void* noise,
+                         const void* mask, const float* tnext, const float* one_minus_tnext, const float* thr, const int* step,
+                         const float* scale, int B, long long img_rows, long long pred_rows, int c_in, int c_out, hipStream_t s) {
+  return solver_step_launch(img, pred, xs, hist, coef, ctl, x0, noise, mask, tnext, one_minus_tnext, thr, step, scale, B, img_rows, pred_rows,
+                            c_in, c_out, nullptr, nullptr, s);
+}
+// ids is read by the kernel only where a row's cn != 0, but which row runs is device data: the host cannot tell, so it is always required
+int fluxmi_k_solver_step_noise(void* img, const void* pred, void* xs, float* hist, const float* coef, const int* ctl, const void* x0,
+                               const void* noise, const void* mask, const float* tnext, const float* one_minus_tnext, const float* thr,
+                               const int* step, const float* scale, int B, long long img_rows, long long pred_rows, int c_in, int c_out,
+                               const unsigned* ids, const int* eval_offset, hipStream_t s) {
+  FLUXMI_REQUIRE(ids, "solver_step_noise: NULL ids (one {key_lo, key_hi, c2, c3} per image; fluxmi_solver_step is the update without noise)");
+  return solver_step_launch(img, pred, xs, hist, coef, ctl, x0, noise, mask, tnext, one_minus_tnext, thr, step, scale, B, img_rows, pred_rows,
+                            c_in, c_out, ids, eval_offset, s);
+}
+int fluxmi_k_philox_normal(void* out, const unsigned* ids, int B, long long n_per_image, unsigned eval, int raw, hipStream_t s) {
+  FLUXMI_REQUIRE(out && ids, "philox_normal: NULL argument");
+  FLUXMI_REQUIRE(B >= 0 && n_per_image >= 0 && n_per_image % 8 == 0 && (raw == 0 || raw == 1),
+                 "philox_normal: bad shape B=%d n_per_image=%lld raw=%d (n_per_image a multiple of 8, raw 0 or 1)", B, n_per_image, raw);
+  const long long n_vec = (long long)B * (n_per_image / 8);
+  FLUXMI_REQUIRE(n_vec <= 0x7fffffffLL, "philox_normal: %lld vectors exceed the kernel's 32-bit index", n_vec);
+  if (n_vec == 0) return 0;
+  if (raw)
+    hipLaunchKernelGGL((philox_normal_kernel<true>), dim3(grid_for(n_vec)), dim3(256), 0, s, out, ids, (unsigned)n_vec,
+                       (unsigned)(n_per_image / 8), eval);
+  else
+    hipLaunchKernelGGL((philox_normal_kernel<false>), dim3(grid_for(n_vec)), dim3(256), 0, s, out, ids, (unsigned)n_vec,
+                       (unsigned)(n_per_image / 8), eval);
   FLUXMI_LAUNCH_CHECK();
   return 0;
 }

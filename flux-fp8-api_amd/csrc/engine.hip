@@ -54,6 +54,7 @@ struct StepGraphs {
   bool blend = false;   // the update kind, continued: the masked-latent blend kernel instead of the (guided) Euler kernel ...
   bool diff = false;    // ... and its differential form (the threshold table is a launch argument)
   bool solver = false;  // ... and the table-driven solver update (fluxmi_engine_set_solver): WHICH solver is device data, not a kind
+  bool noise = false;   // ... and its form with the noise term (fluxmi_engine_set_solver_noise): seeds and the offset are device data
   unsigned gen = 0;     // fluxmi_tuning_generation() the pieces were captured under
   const void* cn = nullptr;  // the attached ControlNet whose launches (and workspace pointers) are baked into the pieces, or none ...
   unsigned long long cn_gen = 0;  // ... and the generation of its workspace / weight binding: process-wide unique, so a net created at a freed net's address never matches
@@ -158,6 +159,14 @@ struct fluxmi_engine {
   int* d_sol_ctl = nullptr;
   char* sol_mem = nullptr;
   size_t sol_bytes = 0;
+  // the noise of a stochastic program (fluxmi_engine_set_solver_noise): the host ids [sol_noise_B][4] and the evaluation offset of the
+  // following denoise calls; their device copy "sol_ids" (uint32 [B][4] | the offset, staged through h_sched like the tables) is made at
+  // the first noise call of a prepared shape and dropped with the workspace.  Nothing of it without noise.
+  bool sol_noise = false;
+  int sol_noise_B = 0, sol_eval_offset = 0;
+  std::vector<unsigned> sol_ids;
+  unsigned* d_sol_ids = nullptr;
+  size_t sol_ids_bytes = 0;
   // ControlNet (fluxmi_controlnet_create / fluxmi_engine_attach_controlnet).  A net is an engine of its own kind
   // (is_cn): no final layer, the controlnet_* projections behind the trunk's linears, the residuals of a forward in its workspace buffer
   // "cn_res" [Nd + Ns][B, Li, H].  The main engine holds the attached net (cn) and the conditioning scale (d_cn_scale, device data).
@@ -1115,7 +1124,8 @@ void free_ws(E* e) {
   e->inp_on = e->inp_diff = false;
   if (e->sol_mem) { hipFree(e->sol_mem); e->sol_mem = nullptr; e->sol_bytes = 0; }
   if (e->d_sol_coef) { hipFree(e->d_sol_coef); e->d_sol_coef = nullptr; e->d_sol_ctl = nullptr; }
-  e->sol_on = false;
+  if (e->d_sol_ids) { hipFree(e->d_sol_ids); e->d_sol_ids = nullptr; e->sol_ids_bytes = 0; }
+  e->sol_on = e->sol_noise = false;
   if (e->ws) { hipFree(e->ws); e->ws = nullptr; }
   e->bufs.clear();
   e->ws_bytes = 0;
@@ -1193,6 +1203,21 @@ int ensure_sol(E* e, hipStream_t s) {
   FLUXMI_CHECK_HIP(hipMemsetAsync(e->sol_mem, 0, xs + hist, s));
   e->bufs["sol_xs"] = Buf{e->sol_mem, xs};
   e->bufs["sol_hist"] = Buf{e->sol_mem + xs, hist};
+  return 0;
+}
+
+// the device copy of the noise ids and the evaluation offset, made once a request with noise arrives
+int ensure_sol_ids(E* e) {
+  if (e->d_sol_ids) return 0;
+  const size_t bytes = ((size_t)e->B * 16 + 4 + 255) & ~(size_t)255;
+  if (hipMalloc((void**)&e->d_sol_ids, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    e->d_sol_ids = nullptr;
+    fluxmi_set_error("engine_denoise: hipMalloc(%zu bytes) failed (solver noise ids)", bytes);
+    return 2;
+  }
+  e->sol_ids_bytes = bytes;
+  e->bufs["sol_ids"] = Buf{(char*)e->d_sol_ids, bytes};
   return 0;
 }
 
@@ -1313,8 +1338,8 @@ static int create_impl(const fluxmi_model_desc_t* desc, const fluxmi_linear_t* l
   e->d_cn_scale = (float*)(e->consts + o_cns);
   e->d_tnext = (float*)(e->consts + o_tnext); e->d_omt = (float*)(e->consts + o_omt); e->d_thr = (float*)(e->consts + o_thr);
   hipMemset(e->consts, 0, off);
-  // pinned staging for the schedule (ts | dts | tnext | 1 - tnext | thresholds | solver coef | solver ctl) + the events (guard of the staging buffer, timing of the frozen steps)
-  if (hipHostMalloc((void**)&e->h_sched, (5 * (MAX_STEPS + 1) + 12 * MAX_STEPS) * sizeof(float), hipHostMallocDefault) != hipSuccess ||
+  // pinned staging for the schedule (ts | dts | tnext | 1 - tnext | thresholds | solver coef | solver ctl | noise ids | eval offset) + the events (guard of the staging buffer, timing of the frozen steps)
+  if (hipHostMalloc((void**)&e->h_sched, (5 * (MAX_STEPS + 1) + 12 * MAX_STEPS + 4 * FLUXMI_ENGINE_MAX_BATCH + 1) * sizeof(float), hipHostMallocDefault) != hipSuccess ||
       hipEventCreateWithFlags(&e->ev_sched, hipEventDisableTiming) != hipSuccess || hipEventCreate(&e->ev_t0) != hipSuccess ||
       hipEventCreate(&e->ev_t1) != hipSuccess) {
     fluxmi_engine_destroy(e);
@@ -1540,7 +1565,8 @@ static void graphs_stale(fluxmi_engine_t* e, StepGraphs& g, bool cfg) {
   if (g.ok && g.gen != fluxmi_tuning_generation()) g.ok = g.warmed = e->qlut_valid = false;
   const bool diff = e->inp_on && e->inp_diff;
   // masked versus dense attention is a kind like guided versus plain, and so are the blend update and its differential form
-  if (g.cfg != cfg || g.masked != e->masked || g.blend != e->inp_on || g.diff != diff || g.solver != e->sol_on) g.ok = g.warmed = false;
+  if (g.cfg != cfg || g.masked != e->masked || g.blend != e->inp_on || g.diff != diff || g.solver != e->sol_on || g.noise != e->sol_noise)
+    g.ok = g.warmed = false;
   // ... and so is the attached ControlNet: its launches, weights and workspace pointers are baked into the pieces
   if (g.cn != e->cn || (e->cn && g.cn_gen != e->cn->ws_gen)) g.ok = g.warmed = false;
   g.cn = e->cn;
@@ -1550,6 +1576,7 @@ static void graphs_stale(fluxmi_engine_t* e, StepGraphs& g, bool cfg) {
   g.blend = e->inp_on;
   g.diff = diff;
   g.solver = e->sol_on;
+  g.noise = e->sol_noise;
 }
 
 // Captures pieces[0 .. n) into g.exec[0 .. n) on a private non-blocking stream (the caller has synchronised its own).  The only place that
@@ -1755,8 +1782,24 @@ static int denoise_impl(fluxmi_engine_t* e, void* img, const void* txt, const vo
                  "(fluxmi_engine_set_solver takes one row per step of the call)", e->sol_n, n_steps);
   FLUXMI_REQUIRE(!e->sol_on || !(e->fb_threshold > 0.f), "engine_denoise: a solver program does not combine with step caching (the cache "
                  "compares consecutive evaluations; a solver may evaluate one time twice)");
+  // A stochastic program (a non-zero cn in column 7) needs its ids (fluxmi_engine_set_solver_noise); the update is then the kernel's noise form
+  bool sol_cn = false;
+  for (int i = 0; e->sol_on && i < n_steps; ++i) sol_cn = sol_cn || e->sol_coef[(size_t)8 * i + 7] != 0.f;
+  FLUXMI_REQUIRE(!sol_cn || e->sol_noise, "engine_denoise: the solver program has a non-zero noise coefficient and no ids are set "
+                 "(fluxmi_engine_set_solver_noise after fluxmi_engine_set_solver)");
+  const bool sol_noise = e->sol_on && e->sol_noise;
+  FLUXMI_REQUIRE(!sol_noise || e->sol_noise_B == (cfg ? B / 2 : B), "engine_denoise: the solver noise holds ids of %d images, this call steps %d "
+                 "(fluxmi_engine_set_solver_noise takes the caller's images: the prepared batch, half of it for a guided call)", e->sol_noise_B,
+                 cfg ? B / 2 : B);
   if (e->sol_on) FLUXMI_TRY(ensure_sol(e, s));
+  if (sol_noise) FLUXMI_TRY(ensure_sol_ids(e));
   auto euler = [&](hipStream_t st) -> int {
+    if (sol_noise)
+      return fluxmi_k_solver_step_noise(buf<u16>(e, "img_s"), buf<u16>(e, "pred_s"), buf<u16>(e, "sol_xs"), buf<float>(e, "sol_hist"),
+                                        e->d_sol_coef, e->d_sol_ctl, e->inp_on ? buf<u16>(e, "inp_x0") : nullptr,
+                                        e->inp_on ? buf<u16>(e, "inp_noise") : nullptr, e->inp_on ? buf<u16>(e, "inp_mask") : nullptr, e->d_tnext,
+                                        e->d_omt, e->inp_on && e->inp_diff ? e->d_thr : nullptr, e->d_step, cfg ? e->d_cfg : nullptr,
+                                        cfg ? B / 2 : B, Li, e->Lpred, C, c_out(e), e->d_sol_ids, (const int*)(e->d_sol_ids + 4 * (size_t)e->B), st);
     if (e->sol_on)
       return fluxmi_k_solver_step(buf<u16>(e, "img_s"), buf<u16>(e, "pred_s"), buf<u16>(e, "sol_xs"), buf<float>(e, "sol_hist"), e->d_sol_coef,
                                   e->d_sol_ctl, e->inp_on ? buf<u16>(e, "inp_x0") : nullptr, e->inp_on ? buf<u16>(e, "inp_noise") : nullptr,
@@ -1825,6 +1868,13 @@ static int denoise_impl(fluxmi_engine_t* e, void* img, const void* txt, const vo
     memcpy(h_ct, e->sol_ctl.data(), (size_t)n_steps * 4 * 4);
     FLUXMI_CHECK_HIP(hipMemcpyAsync(e->d_sol_coef, h_co, (size_t)n_steps * 8 * 4, hipMemcpyHostToDevice, s));
     FLUXMI_CHECK_HIP(hipMemcpyAsync(e->d_sol_ctl, h_ct, (size_t)n_steps * 4 * 4, hipMemcpyHostToDevice, s));
+  }
+  if (sol_noise) {  // ... and the noise ids with the evaluation offset behind them (one copy: the offset sits at [B][4] of "sol_ids")
+    unsigned* h_id = (unsigned*)(e->h_sched + 5 * (MAX_STEPS + 1) + 12 * MAX_STEPS);
+    memset(h_id, 0, (size_t)B * 16);
+    memcpy(h_id, e->sol_ids.data(), (size_t)e->sol_noise_B * 16);
+    h_id[4 * (size_t)B] = (unsigned)e->sol_eval_offset;
+    FLUXMI_CHECK_HIP(hipMemcpyAsync(e->d_sol_ids, h_id, (size_t)B * 16 + 4, hipMemcpyHostToDevice, s));
   }
   FLUXMI_CHECK_HIP(hipEventRecord(e->ev_sched, s));
   e->sched_pending = true;
@@ -1973,10 +2023,11 @@ int fluxmi_engine_set_inpaint(fluxmi_engine_t* e, const void* x0, const void* no
 int fluxmi_engine_set_solver(fluxmi_engine_t* e, const double* coef_host, const int* ctl_host, int n) {
   FLUXMI_REQUIRE(e, "engine_set_solver: NULL engine");
   if (!coef_host) {
-    e->sol_on = false;
+    e->sol_on = e->sol_noise = false;
     e->sol_n = 0;
     e->sol_coef.clear();
     e->sol_ctl.clear();
+    e->sol_ids.clear();
     return 0;
   }
   FLUXMI_REQUIRE(!e->is_cn, "engine_set_solver: a ControlNet engine steps nothing (set the solver on the main engine)");
@@ -1993,6 +2044,24 @@ int fluxmi_engine_set_solver(fluxmi_engine_t* e, const double* coef_host, const 
   e->sol_ctl.assign(ctl_host, ctl_host + 4 * n);
   e->sol_n = n;
   e->sol_on = true;
+  e->sol_noise = false;  // a new program: its noise, if it has any, is set after it
+  e->sol_ids.clear();
+  return 0;
+}
+
+// The noise ids and evaluation offset of the program just set (fluxmi.h): host data only, like the program itself.
+int fluxmi_engine_set_solver_noise(fluxmi_engine_t* e, const unsigned* ids_host, int batch, int eval_offset) {
+  FLUXMI_REQUIRE(e && ids_host, "engine_set_solver_noise: NULL argument");
+  FLUXMI_REQUIRE(e->ws && e->sol_on, "engine_set_solver_noise: call fluxmi_engine_set_solver first (the noise belongs to its program)");
+  bool cn = false;
+  for (int i = 0; i < e->sol_n; ++i) cn = cn || e->sol_coef[(size_t)8 * i + 7] != 0.f;
+  FLUXMI_REQUIRE(cn, "engine_set_solver_noise: the solver program has no non-zero noise coefficient (column 7): it draws nothing");
+  FLUXMI_REQUIRE(batch >= 1 && batch <= e->B, "engine_set_solver_noise: batch %d outside 1..%d (the prepared batch)", batch, e->B);
+  FLUXMI_REQUIRE(eval_offset >= 0, "engine_set_solver_noise: eval_offset %d < 0", eval_offset);
+  e->sol_ids.assign(ids_host, ids_host + 4 * (size_t)batch);
+  e->sol_noise_B = batch;
+  e->sol_eval_offset = eval_offset;
+  e->sol_noise = true;
   return 0;
 }
 
@@ -2181,7 +2250,7 @@ int fluxmi_engine_copy_buffer(fluxmi_engine_t* e, const char* name, long long of
 
 int fluxmi_engine_workspace_bytes(fluxmi_engine_t* e, long long* bytes) {
   FLUXMI_REQUIRE(e && bytes, "engine_workspace_bytes: NULL argument");
-  *bytes = (long long)(e->ws_bytes + e->pairs_bytes + e->mods_all_bytes + e->fb_bytes + e->inp_bytes + e->sol_bytes);  // workspace + row-pair weight copies + modulation table + step cache + inpainting + solver buffers
+  *bytes = (long long)(e->ws_bytes + e->pairs_bytes + e->mods_all_bytes + e->fb_bytes + e->inp_bytes + e->sol_bytes + e->sol_ids_bytes);  // workspace + row-pair weight copies + modulation table + step cache + inpainting + solver buffers + noise ids
   return 0;
 }
 

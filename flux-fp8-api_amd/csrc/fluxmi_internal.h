@@ -174,6 +174,13 @@ int fluxmi_k_blend_euler(void* img, const void* pred, const void* x0, const void
 int fluxmi_k_solver_step(void* img, const void* pred, void* xs, float* hist, const float* coef, const int* ctl, const void* x0, const void* noise,
                          const void* mask, const float* tnext, const float* one_minus_tnext, const float* thr, const int* step,
                          const float* scale, int B, long long img_rows, long long pred_rows, int c_in, int c_out, hipStream_t s);
+// ... with the stochastic samplers' last term acc + cn * z (fluxmi.h, fluxmi_solver_step_noise): cn = column 7 of the row, z the Philox
+// normals of (ids[image], *step + *eval_offset, element); and the generator alone (fluxmi_philox_normal)
+int fluxmi_k_solver_step_noise(void* img, const void* pred, void* xs, float* hist, const float* coef, const int* ctl, const void* x0,
+                               const void* noise, const void* mask, const float* tnext, const float* one_minus_tnext, const float* thr,
+                               const int* step, const float* scale, int B, long long img_rows, long long pred_rows, int c_in, int c_out,
+                               const unsigned* ids, const int* eval_offset, hipStream_t s);
+int fluxmi_k_philox_normal(void* out, const unsigned* ids, int B, long long n_per_image, unsigned eval, int raw, hipStream_t s);
 // first-block step cache (elementwise.hip): streaming passes over B samples of n bf16 elements, x side strided, cache side dense
 int fluxmi_k_fb_snapshot(const void* x, long long x_bstride, void* dst, int B, long long n, hipStream_t s);
 int fluxmi_k_fb_commit(const void* x, long long x_bstride, const void* r, void* r_ref, void* h1, int B, long long n, hipStream_t s);

@@ -664,7 +664,7 @@ class FluxPipeline:
                  regional_tokens: int = 128, inpaint_mask=None, inpaint_differential: bool = False, controlnet_image=None,
                  controlnet_conditioning_scale: float = 1.0, control_mode: Optional[int] = None, control_guidance_start: float = 0.0,
                  control_guidance_end: float = 1.0, controlnet_cond: Optional[torch.Tensor] = None, sampler: str = "euler",
-                 sigma_schedule: Optional[str] = None, sigmas=None):
+                 sigma_schedule: Optional[str] = None, sigmas=None, eta: float = 1.0, s_noise: float = 1.0, noise_seed: Optional[int] = None):
         """`reference_image` (FLUX.1 Kontext [dev] instruction editing): an image the prompt describes an edit of, in any form `init_image`
         takes; see prepare_kontext_reference.  Composes with `init_image` / `strength` unchanged.
         FLUX.1 Fill [dev] (a model with 320 conditioning channels): `init_image` is the image to inpaint and `mask_image` (white =
@@ -724,9 +724,26 @@ class FluxPipeline:
         built from the final timestep list, after the `strength` truncation; where `true_cfg_interval` or the control guidance interval
         cuts the request into several denoise calls, each call gets the program of its own slice (a multistep solver restarts with a
         first-order step there).  Composes with everything above except `cache_threshold` > 0, which a non-Euler sampler refuses.  Image
-        quality per sampler on real FLUX weights is not established here; no sampler or step count is recommended."""
-        if sampler not in solvers.SAMPLERS:
-            raise ValueError(f"fluxmi: sampler={sampler!r}: expected one of {solvers.SAMPLERS}")
+        quality per sampler on real FLUX weights is not established here; no sampler or step count is recommended.
+        Stochastic samplers: `sampler` "euler_ancestral" (k-diffusion's rectified-flow ancestral step) or "dpmpp_2m_sde"
+        (SDE-DPM-Solver++(2M)), one evaluation per step, with `eta` in [0, 1] (the share of each step's noise that is re-drawn; 0 = the
+        deterministic limit) and `s_noise` >= 0 (a factor on the drawn noise).  The fresh noise is generated inside the update kernel by a
+        counter-based generator (fluxmi.solvers; fluxmi_philox_normal): image k of the request draws under ids (seed & 0xffffffff,
+        seed >> 32, k, 0), `seed` being `noise_seed` if given, else the request's seed (the integer set_seed returns; with several ranks
+        and no seed given that is each rank's own), at the evaluation's index within the whole request: a request cut by
+        `true_cfg_interval` or the control guidance interval never reuses a draw, and nothing is taken from the request's torch generator.
+        A request or slice whose program draws nothing (eta 0, s_noise 0, the lone step onto sigma 0) runs as a deterministic solver call.
+        Composes like the other samplers; `eta`, `s_noise` or `noise_seed` with a deterministic sampler is refused."""
+        stochastic = sampler in solvers.STOCHASTIC_SAMPLERS
+        if sampler not in solvers.SAMPLERS and not stochastic:
+            raise ValueError(f"fluxmi: sampler={sampler!r}: expected one of {solvers.SAMPLERS + solvers.STOCHASTIC_SAMPLERS}")
+        if not stochastic and (eta != 1.0 or s_noise != 1.0 or noise_seed is not None):
+            raise ValueError(f"fluxmi: eta / s_noise / noise_seed shape the noise of a stochastic sampler {solvers.STOCHASTIC_SAMPLERS}; "
+                             f"sampler={sampler!r} draws none")
+        if stochastic:
+            solvers.build_program(sampler, (1.0, 0.0), eta, s_noise)  # eta / s_noise out of range: refused before any work
+            if noise_seed is not None and (isinstance(noise_seed, bool) or not isinstance(noise_seed, int) or not 0 <= noise_seed < 2 ** 64):
+                raise ValueError(f"fluxmi: noise_seed={noise_seed!r}: expected an integer in [0, 2^64)")
         if sigma_schedule not in solvers.SIGMA_SCHEDULES:
             raise ValueError(f"fluxmi: sigma_schedule={sigma_schedule!r}: expected one of {solvers.SIGMA_SCHEDULES}")
         if sigmas is not None:
@@ -912,6 +929,7 @@ class FluxPipeline:
             if cn_cond.ndim != 3 or cn_cond.shape[0] not in (1, num_images) or tuple(cn_cond.shape[1:]) != tuple(img.shape[1:]):
                 raise ValueError(f"fluxmi: controlnet_cond {tuple(cn_cond.shape)}: expected [1 or {num_images}, {img.shape[1]}, {img.shape[2]}]")
             cn_cond = cn_cond.expand(num_images, -1, -1).contiguous()
+        first_image = 0  # the request's index of this rank's first image (the noise ids of a stochastic sampler count from it)
         if world > 1:
             if guided:  # the negative embeddings ride in the one broadcast, behind the prompt's
                 txt, vec = torch.cat((txt, neg_txt), 0), torch.cat((vec, neg_vec), 0)
@@ -932,6 +950,7 @@ class FluxPipeline:
                 (txt, neg_txt), (vec, neg_vec) = txt.chunk(2, 0), vec.chunk(2, 0)
             # images are sharded, not branches: both branches of an image run on the rank that owns it
             lo, hi = fdist.shard_bounds(img.shape[0], rank, world)
+            first_image = lo
             img, img_ids, vec, txt, txt_ids = (t[lo:hi].contiguous() for t in (img, img_ids, vec, txt, txt_ids))
             if guided:
                 neg_txt, neg_vec = neg_txt[lo:hi].contiguous(), neg_vec[lo:hi].contiguous()
@@ -955,6 +974,9 @@ class FluxPipeline:
                 neg["attn_groups"] = torch.stack(tab).to(self.device_flux)
             thr = self.inpaint_thresholds(n) if inpaint is not None and inpaint_differential else None
             latents = img
+            if stochastic:  # per-image ids of the noise: the request's image index, not the rank's or the pass's
+                key = int(seed if noise_seed is None else noise_seed)
+                noise_ids = [(key & 0xffffffff, (key >> 32) & 0xffffffff, first_image + k, 0) for k in range(img.shape[0])]
             segs = list(((0, g0, plain_kw), (g0, g1, neg), (g1, n, plain_kw)) if g0 < g1 else ((0, n, plain_kw),))
             if cn_cond is not None and n > 0:
                 # cut every segment where the ControlNet switches on or off (diffusers' controlnet_keep): consecutive denoise calls
@@ -979,7 +1001,11 @@ class FluxPipeline:
                         kw = dict(kw, inpaint_x0=x0_, inpaint_noise=noise_, inpaint_mask=mask_)
                         if thr is not None:
                             kw["inpaint_thresholds"] = thr[a:b]  # each denoise call gets its slice of the request's table
-                    if sampler != "euler":  # ... and the program of its slice of the schedule
+                    if stochastic:  # ... one evaluation per step: the slice's first evaluation is the request's a-th
+                        kw = dict(kw, solver=solvers.build_program(sampler, timesteps[a:b + 1], eta, s_noise))
+                        if solvers.has_noise(kw["solver"]):  # eta = 0, s_noise = 0 or a slice that is only the step onto 0 draws nothing
+                            kw["solver_noise"] = (noise_ids, a)
+                    elif sampler != "euler":  # ... and the program of its slice of the schedule
                         kw = dict(kw, solver=solvers.build_program(sampler, timesteps[a:b + 1]))
                     latents = self.model.denoise(latents, img_ids, txt, txt_ids, vec, timesteps[a:b + 1], guidance=guidance, use_graph=use_graph,
                                                  **cond, **kw, **cache)

@@ -106,6 +106,8 @@ _SIGS = {
     "fluxmi_cfg_euler": ([vp, vp, vp, vp, vp, i32, i64, i64, i32, i32, vp], i32),
     "fluxmi_blend_euler": ([vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i64, i64, i32, i32, vp], i32),
     "fluxmi_solver_step": ([vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i64, i64, i32, i32, vp], i32),
+    "fluxmi_solver_step_noise": ([vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i64, i64, i32, i32, vp, vp, vp], i32),
+    "fluxmi_philox_normal": ([vp, vp, i32, i64, C.c_uint32, i32, vp], i32),
     "fluxmi_fb_snapshot": ([vp, i64, vp, i32, i64, vp], i32),
     "fluxmi_fb_metric": ([vp, i64, vp, vp, vp, vp, vp, vp, i32, i64, vp], i32),
     "fluxmi_fb_commit": ([vp, i64, vp, vp, vp, i32, i64, vp], i32),
@@ -132,6 +134,7 @@ _SIGS = {
     "fluxmi_engine_set_attn_groups": ([vp, vp, vp], i32),
     "fluxmi_engine_set_inpaint": ([vp, vp, vp, vp, i32, C.POINTER(C.c_double), i32, vp], i32),
     "fluxmi_engine_set_solver": ([vp, C.POINTER(C.c_double), C.POINTER(i32), i32], i32),
+    "fluxmi_engine_set_solver_noise": ([vp, C.POINTER(C.c_uint32), i32, i32], i32),
     "fluxmi_engine_step_cache_log": ([vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(f32), C.POINTER(C.c_ubyte), i32], i32),
     "fluxmi_engine_run_phase": ([vp, i32, i32, i32, i32, vp], i32),
     "fluxmi_controlnet_num_linears": ([C.POINTER(ModelDesc)], i32),

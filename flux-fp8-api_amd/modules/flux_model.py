@@ -25,7 +25,7 @@ import torch
 from pydantic import BaseModel, Field
 from torch import Tensor, nn
 
-from fluxmi import _lib, ops
+from fluxmi import _lib, ops, solvers
 
 if TYPE_CHECKING:
     from util import ModelSpec
@@ -390,6 +390,36 @@ class Flux(nn.Module):
         ctl = (C.c_int * max(1, 4 * n))(*[int(v) for row in solver.ctl for v in row])
         _lib.call("fluxmi_engine_set_solver", self._engine, coef, ctl, n)
 
+    def _set_solver_noise(self, solver_noise):
+        """after _set_solver, under the lock: the per-image noise ids and evaluation offset of a stochastic program (_check_solver_noise)"""
+        if solver_noise is None:
+            return
+        ids, off = solver_noise
+        flat = (C.c_uint32 * (4 * len(ids)))(*[w for row in ids for w in row])
+        _lib.call("fluxmi_engine_set_solver_noise", self._engine, flat, len(ids), off)
+
+    @staticmethod
+    def _check_solver_noise(solver_noise, solver, B):
+        """-> (ids: a list of B 4-tuples of uint32 words, eval_offset) or None"""
+        if solver_noise is None:
+            if solver is not None and solvers.has_noise(solver):
+                raise ValueError("solver: the program draws noise (a non-zero cn) -- pass solver_noise=(ids [B, 4], eval_offset)")
+            return None
+        if solver is None or not solvers.has_noise(solver):
+            raise ValueError("solver_noise needs a solver program that draws noise (a non-zero cn in some row)")
+        try:
+            ids, off = solver_noise
+            ids = ids.tolist() if isinstance(ids, Tensor) else [list(r) for r in ids]
+            ids = [tuple(int(w) & 0xffffffff for w in r) for r in ids]  # (an int32 tensor holds the words' bits)
+            off = int(off)
+        except (TypeError, ValueError):
+            raise ValueError("solver_noise: expected (ids [B, 4] uint32 / int tensor or list, eval_offset)") from None
+        if len(ids) != B or any(len(r) != 4 for r in ids):
+            raise ValueError(f"solver_noise: ids of {len(ids)} images for a batch of {B} (one {{key_lo, key_hi, c2, c3}} per image)")
+        if not 0 <= off < 2 ** 31:
+            raise ValueError(f"solver_noise: eval_offset {off} outside [0, 2^31)")
+        return ids, off
+
     @staticmethod
     def _with_reference(img, img_ids, img_cond_seq, img_cond_seq_ids):
         """FLUX.1 Kontext: the reference tokens ride behind the noisy tokens of each sample -> (stream, stream ids, Lc).  Both None: unchanged."""
@@ -631,7 +661,7 @@ class Flux(nn.Module):
                 img_cond_seq_ids: Tensor | None = None, img_cond: Tensor | None = None, neg_txt: Tensor | None = None,
                 neg_y: Tensor | None = None, cfg_scale: float = 1.0, cache_threshold: float = 0.0, cache_max_hits: int = 0,
                 attn_groups: Tensor | None = None, inpaint_x0: Tensor | None = None, inpaint_noise: Tensor | None = None,
-                inpaint_mask: Tensor | None = None, inpaint_thresholds=None, controlnet=None, solver=None) -> Tensor:
+                inpaint_mask: Tensor | None = None, inpaint_thresholds=None, controlnet=None, solver=None, solver_noise=None) -> Tensor:
         """The Euler loop of FluxPipeline.generate (reference flux_pipeline.py:619-651) run natively: calibrating
         steps unfused, every later step one replay of a captured hipGraph.  Returns the final latent tokens.
         FLUX.1 Kontext: with `img_cond_seq` / `img_cond_seq_ids` the reference tokens join every step's forward and are never stepped; the
@@ -661,7 +691,11 @@ class Flux(nn.Module):
         `solver`: a fluxmi.solvers.SolverProgram built from `timesteps` (build_program): every update -- calibrating, replayed, guided,
         masked -- is then the table-driven kernel (csrc/elementwise.hip, solver_step_kernel) on the program's rows, one engine step per model
         EVALUATION at `solver.times`; `inpaint_thresholds` stays one per user step and is expanded through `solver.step_of_eval`.  Refused
-        with cache_threshold > 0: the cache compares consecutive evaluations, and Heun evaluates one time twice.  None = today's call."""
+        with cache_threshold > 0: the cache compares consecutive evaluations, and Heun evaluates one time twice.  None = today's call.
+        `solver_noise` = (ids, eval_offset) goes with a program that draws noise (fluxmi.solvers.STOCHASTIC_SAMPLERS; a non-zero cn): ids
+        [B, 4] uint32 words {key_lo, key_hi, c2, c3} per IMAGE (a tensor or a list; never per branch), eval_offset the index of this call's
+        first evaluation within the request.  Evaluation j adds cn * z in the same kernel, z generated there (Philox4x32-10 + Box-Muller) as
+        a pure function of (ids[b], j + eval_offset, element): a sample's bits depend on its ids alone, not on its batch or pass."""
         n_user = len(timesteps) - 1
         if solver is not None:
             if cache_threshold and float(cache_threshold) > 0:
@@ -678,6 +712,7 @@ class Flux(nn.Module):
             inside = all(ts_f[i + 1] <= float(solver.times[j]) <= ts_f[i] for j, i in enumerate(solver.step_of_eval))
             if not inside or float(solver.times[-1]) != ts_f[-1]:
                 raise ValueError("solver: the program's evaluation times do not lie inside the steps of timesteps (build it from the same list)")
+        solver_noise = self._check_solver_noise(solver_noise, solver, img.shape[0])
         inpaint = self._check_inpaint(img, inpaint_x0, inpaint_noise, inpaint_mask, inpaint_thresholds, n_user)
         cache_threshold, cache_max_hits = float(cache_threshold), int(cache_max_hits)
         if not (math.isfinite(cache_threshold) and cache_threshold >= 0.0) or cache_max_hits < 0:
@@ -729,6 +764,8 @@ class Flux(nn.Module):
                     cond["controlnet"] = type(controlnet)(cn[0], pick(cn[1]), cn[3], cn[2])
                 if solver is not None:
                     cond["solver"] = solver
+                if solver_noise is not None:  # picked like every per-sample tensor: a padded tail copies the last image's ids
+                    cond["solver_noise"] = (solver_noise[0][sl] + solver_noise[0][sl.stop - 1:sl.stop] * pad, solver_noise[1])
                 o = self.denoise(pick(img), pick(img_ids), pick(txt), pick(txt_ids), pick(y), timesteps, guidance=guidance, use_graph=use_graph,
                                  cache_threshold=cache_threshold, cache_max_hits=cache_max_hits, **cond)
                 outs.append(o[:per - pad])
@@ -756,6 +793,7 @@ class Flux(nn.Module):
             _lib.call("fluxmi_engine_set_step_cache", self._engine, cache_threshold, cache_max_hits)
             self._set_inpaint(inpaint, img.device)
             self._set_solver(solver)
+            self._set_solver_noise(solver_noise)
             net = self._attach_controlnet(cn, img.device)
             try:
                 if guided:

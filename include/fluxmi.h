@@ -416,6 +416,24 @@ int fluxmi_blend_euler(void* img, const void* pred, const void* x0, const void* 
 int fluxmi_solver_step(void* img, const void* pred, void* xs, float* hist, const float* coef, const int* ctl, const void* x0, const void* noise,
                        const void* mask, const float* tnext, const float* one_minus_tnext, const float* thr, const int* step, const float* scale,
                        int B, long long img_rows, long long pred_rows, int c_in, int c_out, void* stream);
+/* Counter-based Gaussian noise (stochastic samplers): Philox4x32-10 with the published constants, then Box-Muller.
+ * ids: DEVICE uint32 [B][4] = {key_lo, key_hi, c2, c3} per image.  Element e of an image belongs to Philox block q = e / 4: counter
+ * (q, eval, c2, c3), key (key_lo, key_hi) -> words w0..w3 -> four normals,
+ *   u = ((w_even >> 9) + 0.5f) * 2^-23 in (0, 1),  t = (w_odd >> 8) * 2^-24 in [0, 1)     (both exact in fp32)
+ *   r = sqrtf(-2.f * logf(u)),  (s, c) = sincospif(2.f * t),  z = r*c, r*s from (w0, w1), then r*c, r*s from (w2, w3)
+ * so a value is a pure function of (ids[b], eval, e): no state, no dependence on B or on the launch.  out: [B][n_per_image], raw = 1 the
+ * uint32 words, raw = 0 the fp32 normals; n_per_image %% 8 == 0.  The device function is the one fluxmi_solver_step_noise draws from. */
+int fluxmi_philox_normal(void* out, const unsigned* ids, int B, long long n_per_image, unsigned eval, int raw, void* stream);
+/* fluxmi_solver_step with the stochastic samplers' noise term: column 7 of the row is cn, and after the c2 term
+ *   acc = acc + (cn * z)                (product and sum each rounded to fp32; then x1 = bf16(acc), then the blend if set)
+ * z = the normal fluxmi_philox_normal gives element e of image b's dense [pred_rows, c_out] block for ids[b] at eval = *step + *eval_offset
+ * (eval_offset: DEVICE int, NULL = 0; step NULL = 0).  ids: DEVICE uint32 [B][4], per IMAGE: a guided call draws once per image and writes
+ * x' to both halves as before.  cn == 0.0f: the term is skipped like every absent term, ids is not read and nothing is generated -- the
+ * result is fluxmi_solver_step's bit for bit.  Everything else, refusals included, as for fluxmi_solver_step; NULL ids is refused. */
+int fluxmi_solver_step_noise(void* img, const void* pred, void* xs, float* hist, const float* coef, const int* ctl, const void* x0,
+                             const void* noise, const void* mask, const float* tnext, const float* one_minus_tnext, const float* thr, const int* step,
+                             const float* scale, int B, long long img_rows, long long pred_rows, int c_in, int c_out, const unsigned* ids,
+                             const int* eval_offset, void* stream);
 
 /* ---- first-block step cache: the streaming passes --------------------------------------
  * B samples of n bf16 elements each (n = cached rows x hidden, n %% 8 == 0).  The `x` side is the residual stream: the pointer is the first
@@ -603,6 +621,17 @@ int fluxmi_engine_set_inpaint(fluxmi_engine_t* e, const void* x0, const void* no
  * with the workspace and counted in fluxmi_engine_workspace_bytes.  coef_host == NULL switches the feature off; a prepare that re-allocates
  * the workspace does too.  A request without a solver allocates nothing and launches exactly what it launched before. */
 int fluxmi_engine_set_solver(fluxmi_engine_t* e, const double* coef_host, const int* ctl_host, int n);
+/* The noise of a stochastic solver program (column 7, cn, non-zero in some row): valid only after such a fluxmi_engine_set_solver, for the
+ * denoise calls that program serves.  ids_host: batch x 4 uint32 = {key_lo, key_hi, c2, c3} per image (fluxmi_philox_normal); batch = the
+ * caller's images -- the prepared batch, half of it for a guided call; the denoise call checks it, like fluxmi_engine_set_inpaint's.
+ * eval_offset >= 0: evaluation j of the call draws at eval = j + eval_offset, so a request cut into several denoise calls draws what the
+ * uncut one draws.  Every update of the call is then fluxmi_solver_step_noise.  ids and the offset are device data ("sol_ids": uint32
+ * [prepared batch][4], then the offset) staged with the call's schedule like the coefficient tables: solver-with-noise is a kind of step graph
+ * of its own, and ONE graph serves every seed and every offset.  "sol_ids" is allocated at the first such call of a prepared shape, counted
+ * in fluxmi_engine_workspace_bytes and dropped with the workspace.  fluxmi_engine_set_solver (a new program, or NULL) and a prepare that
+ * re-allocates the workspace switch the noise off; a denoise call whose program has a non-zero cn and no ids set is refused.  A deterministic
+ * solver request and a request without a solver allocate and launch exactly what they did before. */
+int fluxmi_engine_set_solver_noise(fluxmi_engine_t* e, const unsigned* ids_host, int batch, int eval_offset);
 /* Test hook: phases [phase_from, phase_to] of ONE frozen forward on the engine's own buffers, mode 1 (fused) or 2 (unfused, frozen scales):
  *   0 img_in + txt_in on the request buffers "img_s" / "txt_s" (mode 1: the cached "txt_emb" of the last denoise call) + this step's
  *     modulation vectors out of the step-ahead table the last denoise call left (step = the request's step index, written to the device-side

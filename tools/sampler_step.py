@@ -1,7 +1,8 @@
 """Time per EVALUATION of a frozen, graph-replayed denoise under a solver program (higher-order samplers) against the plain Euler one: full
 Flux-dev geometry (19 + 38 blocks, hidden 3072) with synthetic weights made on the device, fp8 flow, a 1024^2 image (Li 4096, Lt 512), B 1.
-One engine, four request kinds that ALTERNATE round after round in one process: plain Euler (today's kernels), ab2 (one evaluation per step),
-heun (two per step but the last), heun + guided (true CFG: two samples in the engine).  The meter is the engine's own hipEvent pair around the
+One engine, five request kinds that ALTERNATE round after round in one process: plain Euler (today's kernels), ab2 (one evaluation per step),
+heun (two per step but the last), heun + guided (true CFG: two samples in the engine), euler_ancestral (one evaluation per step, the noise
+generated in the update kernel).  The meter is the engine's own hipEvent pair around the
 graph replays (fluxmi_engine_last_timing), divided by the evaluations it brackets; calibration, the modulation table, the warm step and the
 capture are outside it.  Printed per kind: every round's ms per evaluation, the median and the spread (max - min), and for the solver kinds
 the distance from the plain median next to the plain kind's own spread.
@@ -9,7 +10,7 @@ the distance from the plain median next to the plain kind's own spread.
 Kernel times come from ONE separate run under the profiler (own process, no counters), summarised by this tool:
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/sampler_step.py --rounds 1 --steps 10
     python tools/sampler_step.py --summarize DIR
-which prints the update kernels (euler_kernel, solver_step_kernel plain and guided) side by side (calls, mean, the ratio to euler_kernel)
+which prints the update kernels (euler_kernel, solver_step_kernel plain, guided and with noise) side by side (calls, mean, the ratio to euler_kernel)
 and the launch count per frozen evaluation of each kind (evaluations are delimited by advance_step_kernel; an evaluation's kind is its
 update kernel), and fails unless a solver evaluation launches as many kernels as a plain step.
 Prints one JSON line per measurement."""
@@ -18,19 +19,22 @@ import csv
 import glob
 import json
 import os
+import re
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "flux-fp8-api_amd"))
 sys.path.insert(0, ROOT)
 
-UPDATE_KERNELS = {"euler_kernel(": "plain", "solver_step_kernel<false": "solver", "solver_step_kernel<true": "solver + guided"}
+SOLVER_KERNEL = re.compile(r"(?:^|[\s:])solver_step_kernel<\s*(\w+)\s*,\s*\w+\s*,\s*\w+\s*,\s*(\w+)\s*>")  # <CFG, PLAIN, BLEND, NOISE>
 
 
 def update_kind(name):
-    for key, kind in UPDATE_KERNELS.items():
-        if "::" + key in name or name.startswith(key) or " " + key in name:
-            return kind
+    m = SOLVER_KERNEL.search(name)
+    if m:
+        return "solver" + (" + guided" if m.group(1) in ("true", "1") else "") + (" + noise" if m.group(2) in ("true", "1") else "")
+    if re.search(r"(?:^|[\s:])euler_kernel\(", name):
+        return "plain"
     return None
 
 
@@ -75,6 +79,12 @@ def summarize(path):
                               equal=same)))
         if not same:
             sys.exit("the solver evaluation launches %d kernels, the plain step %d" % (per_step["solver"], per_step["plain"]))
+    if "plain" in per_step and "solver + noise" in per_step:  # ... and so must one with noise: the generator adds no launch
+        same = per_step["plain"] == per_step["solver + noise"]
+        print(json.dumps(dict(what="solver evaluation with noise launches as many kernels as the plain step", plain=per_step["plain"],
+                              noise=per_step["solver + noise"], equal=same)))
+        if not same:
+            sys.exit("the noise evaluation launches %d kernels, the plain step %d" % (per_step["solver + noise"], per_step["plain"]))
 
 
 def main():
@@ -114,11 +124,14 @@ def main():
             kw = dict(neg_txt=neg["txt"], neg_y=neg["y"], cfg_scale=args.scale) if guided else {}
             if sampler is not None:
                 kw["solver"] = solvers.build_program(sampler, ts)
+            if sampler in solvers.STOCHASTIC_SAMPLERS:
+                kw["solver_noise"] = ([(1234, 0, 0, 0)], 0)
             return model.denoise(inp["img"], inp["img_ids"], inp["txt"], inp["txt_ids"], inp["y"], ts, guidance=3.5, use_graph=True, **kw)
 
         run(sched(13), None, False)  # calibration: 13 unfused steps freeze every F8Linear input scale
         assert model.calibration_state()[0]
-        kinds = (("plain", None, False), ("ab2", "ab2", False), ("heun", "heun", False), ("heun + guided", "heun", True))
+        kinds = (("plain", None, False), ("ab2", "ab2", False), ("heun", "heun", False), ("heun + guided", "heun", True),
+                 ("euler_ancestral", "euler_ancestral", False))
         per = {name: [] for name, _, _ in kinds}
         evals = {}
         finite = True
@@ -138,7 +151,7 @@ def main():
                        engine_batch=2 if guided else 1, Li=Li, Lt=Lt, steps_per_request=args.steps, timed_evaluations=evals[name],
                        ms_per_evaluation_each_round=[round(t, 3) for t in v], ms_per_evaluation_median=round(med(v), 3),
                        spread_ms=round(max(v) - min(v), 3))
-            if name in ("ab2", "heun"):
+            if name in ("ab2", "heun", "euler_ancestral"):
                 rec.update(minus_plain_median_ms=round(med(v) - med(per["plain"]), 3),
                            plain_spread_ms=round(max(per["plain"]) - min(per["plain"]), 3))
             print(json.dumps(rec), flush=True)

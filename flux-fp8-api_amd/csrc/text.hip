@@ -91,6 +91,8 @@ __global__ void __launch_bounds__(256) act_mul_kernel(const u16* __restrict__ in
 // ---- self-attention, head width D = 64 (T5, CLIP) or 96 (SigLIP's 72, zero-padded per head) --------------------------------------
 // Per image b (blockIdx.z): q, k, vt, out are offset by b times their batch strides.  Zero q / k columns add nothing to q.k, and zero
 // V^T rows (with zero v_bias entries) give zero output columns, so a padded head computes exactly what the unpadded one does.
+// Padding rows >= L of q / k and padding columns >= L of V^T never reach the output (masked scores, P = 0), but they must hold FINITE
+// values: a masked key still goes through the P V MFMA as 0 * v, and 0 * inf is NaN.
 struct TextAttnArgs {
   const u16* q; const u16* k; long long ld_qk;   // [Lp, ld_qk], head h at columns h*D ..
   const u16* vt; long long ld_vt;                // [H*D, ld_vt]: V transposed (row h*D + d, column = key)

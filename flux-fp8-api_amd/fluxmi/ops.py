@@ -474,7 +474,8 @@ def act_mul(x: torch.Tensor, gated: bool) -> torch.Tensor:
 
 def text_attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, L: int, heads: int, scale: float = 1.0, causal: bool = False,
                    rel_bias: Optional[torch.Tensor] = None, v_bias: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """q, k [Lp, >= heads*64] (views with the same row stride), vt [heads*64, Lp] -> out [Lp, heads*64]; see include/fluxmi.h."""
+    """q, k [Lp, >= heads*64] (views with the same row stride), vt [heads*64, Lp] -> out [Lp, heads*64]; see include/fluxmi.h.
+    Rows >= L of q and k and columns >= L of vt are padding the result does not depend on, but they must be FINITE (0 * inf is NaN in P V)."""
     _req(q, torch.bfloat16, "q")
     _req(k, torch.bfloat16, "k")
     _req(vt, torch.bfloat16, "vt")

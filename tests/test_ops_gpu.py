@@ -17,7 +17,7 @@ import torch.nn.functional as F
 
 import attention_ref as ar
 import flux_oracle as fo
-from parity_util import assert_bf16_close, assert_close_mag, assert_f8_close, f8_ulp_diff, round_fp64_to_bf16, ulp_diff
+from parity_util import accum_noise, assert_bf16_close, assert_close_mag, assert_f8_close, f8_ulp_diff, round_fp64_to_bf16, ulp_diff
 
 pytestmark = pytest.mark.gpu
 
@@ -252,17 +252,6 @@ def test_gemm_split_k(ops, dev, case):
         else:
             ex = assert_close_mag(runs[0][gi], h, mag=noise, ulps=1.05, min_exact=0.98, what=f"split-K {case} group {gi}")
         print(f"split-K {case} group {gi} (M={out.shape[0]}): bit-exact vs fp64 {ex:.5f}")
-
-
-def accum_noise(a, w, s):
-    """Magnitude (already in 'bf16-ulp units', i.e. multiplied by 2^7) of fp32 accumulation-order noise:
-    16*sqrt(K)*2^-24 * sum_k|a||w| * s  (worst case is K*2^-24; the MX MFMA also aligns the 64 products of a block to
-    a common exponent before adding).  Passed as `mag` so that assert_close_mag allows 1 bf16 ulp OR this noise;
-    the bit-exact-fraction requirement is what keeps the test sharp."""
-    S = (a.double().abs() @ w.double().abs().T) * float(s)
-    # floor at K = 256: a single 32x32x64 MX MFMA aligns its 64 products to the block's largest exponent before adding, so
-    # even one K-step carries that much truncation (measured on gfx950: K = 64 reaches 1.85x the sqrt(K) model)
-    return 16.0 * math.sqrt(max(a.shape[1], 256)) * 2.0 ** -24 * S * 2.0 ** 7
 
 
 @pytest.mark.parametrize("cfg", [2, 13, 15, 100])

@@ -5,6 +5,9 @@ Same two POST endpoints, request fields, defaults and status codes:
              init_image=None (path or base64), reference_image=None (FLUX.1 Kontext edit; path or base64, passed on only when set),
              mask_image=None (FLUX.1 Fill: white = regenerate), control_image=None (FLUX.1 Depth / Canny: the depth or edge map),
              redux_image=None (FLUX.1 Redux image prompt) -- path or base64, each passed on only when set;
+             ip_adapter_image=None (FLUX IP-Adapter image prompt: a path / base64 string or a list), ip_adapter_image_embeds=None ([n][768]),
+             ip_adapter_scale=None (a float or one per double block), negative_ip_adapter_image=None, negative_ip_adapter_scale=None -- each
+             passed on only when set;
              negative_prompt=None, true_cfg_scale=None, true_cfg_interval=None ([lo, hi]) -- true classifier-free guidance
              (FluxPipeline.generate), each passed on only when set;
              cache_threshold=None, cache_max_hits=None -- first-block step caching (FluxPipeline.generate), each passed on only when set;
@@ -26,7 +29,7 @@ engine access with its own lock (modules/flux_model.py), so concurrent requests 
 from __future__ import annotations
 
 import random
-from typing import List, Literal, Optional, Tuple
+from typing import List, Literal, Optional, Tuple, Union
 
 from fastapi import FastAPI
 from fastapi.responses import JSONResponse, StreamingResponse
@@ -78,6 +81,11 @@ class GenerateArgs(BaseModel):
     inpaint_differential: Optional[bool] = None  # differential diffusion: inpaint_mask is a grey change map (lighter = changed more)
     controlnet_image: Optional[str] = None  # FLUX ControlNet (config controlnet_path): the edge map / depth map / pose to follow, path or base64
     controlnet_conditioning_scale: Optional[float] = None  # ... the strength of its residuals (default 1.0)
+    ip_adapter_image: Optional[Union[str, List[str]]] = None  # FLUX IP-Adapter (config ip_adapter_path / clip_vision_path): image prompt(s), path or base64
+    ip_adapter_image_embeds: Optional[List[List[float]]] = None  # ... or the CLIP image_embeds [n][768] already computed
+    ip_adapter_scale: Optional[Union[float, List[float]]] = None  # ... its strength: a float, or one float per double block (default 1.0)
+    negative_ip_adapter_image: Optional[Union[str, List[str]]] = None  # ... the negative branch's image(s) (default: black), with a negative prompt
+    negative_ip_adapter_scale: Optional[Union[float, List[float]]] = None  # ... and its strength
     control_mode: Optional[int] = Field(default=None, ge=0)  # ... the control mode of a Union net
     control_guidance_start: Optional[float] = Field(default=None, ge=0.0, le=1.0)  # ... the fraction of the steps at which it switches on
     control_guidance_end: Optional[float] = Field(default=None, ge=0.0, le=1.0)  # ... and off (diffusers' names)
@@ -98,14 +106,20 @@ def generate(args: GenerateArgs):
     `reference_image` selects a FLUX.1 Kontext edit of that image, `mask_image` a FLUX.1 Fill inpainting of `init_image`, `control_image` a
     FLUX.1 Depth / Canny generation, `redux_image` a FLUX.1 Redux image prompt; `negative_prompt` + `true_cfg_scale` (+ `true_cfg_interval`)
     select true classifier-free guidance, `cache_threshold` (+ `cache_max_hits`) first-block step caching, `controlnet_image` (+ `controlnet_conditioning_scale`,
-    `control_mode`, `control_guidance_start` / `_end`) a FLUX ControlNet.  Without them the call is exactly the reference's."""
+    `control_mode`, `control_guidance_start` / `_end`) a FLUX ControlNet, `ip_adapter_image` / `ip_adapter_image_embeds` (+ `ip_adapter_scale`,
+    `negative_ip_adapter_image`, `negative_ip_adapter_scale`) a FLUX IP-Adapter.  Without them the call is exactly the reference's."""
     kwargs = args.model_dump()
     for k in ("reference_image", "mask_image", "control_image", "redux_image", "negative_prompt", "true_cfg_scale", "true_cfg_interval",
               "cache_threshold", "cache_max_hits", "regions", "regional_tokens", "inpaint_mask", "inpaint_differential", "controlnet_image",
               "controlnet_conditioning_scale", "control_mode", "control_guidance_start", "control_guidance_end", "sampler", "sigma_schedule",
-              "sigmas", "eta", "s_noise", "noise_seed"):
+              "sigmas", "eta", "s_noise", "noise_seed", "ip_adapter_image", "ip_adapter_image_embeds", "ip_adapter_scale",
+              "negative_ip_adapter_image", "negative_ip_adapter_scale"):
         if kwargs.get(k) is None:
             kwargs.pop(k, None)
+    if "ip_adapter_image_embeds" in kwargs:
+        import torch
+
+        kwargs["ip_adapter_image_embeds"] = torch.tensor(kwargs["ip_adapter_image_embeds"], dtype=torch.float32)
     if "regions" in kwargs:
         regs = []
         for r in kwargs["regions"]:

@@ -270,5 +270,11 @@ int fluxmi_fb_apply(void* x, long long x_bstride, const void* h1, long long h1_b
 int fluxmi_add_scaled(void* x, long long x_bstride, const void* r, long long r_bstride, const float* scale, int B, long long n, void* stream) {
   return fluxmi_k_add_scaled(x, x_bstride, r, r_bstride, scale, B, n, (hipStream_t)stream);
 }
+int fluxmi_ip_attention(const void* qkv, long long ld_qkv, long long qkv_bstride, const void* qn_scale, const void* k_ip, const void* v_ip,
+                        long long kv_bstride, void* out, long long ld_o, long long o_bstride, const float* scale, long long scale_bstride, int B,
+                        int rows, int heads, int Nk, void* stream) {
+  return fluxmi_k_ip_attention(qkv, ld_qkv, qkv_bstride, qn_scale, k_ip, v_ip, kv_bstride, out, ld_o, o_bstride, scale, scale_bstride, B, rows, heads,
+                               Nk, (hipStream_t)stream);
+}
 
 }  // extern "C"

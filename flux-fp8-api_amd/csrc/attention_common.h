@@ -88,6 +88,30 @@ constexpr int V_BYTES = 128 * KT * 2;  // 16 KiB
 constexpr int A_STAGE = K_BYTES + V_BYTES;
 
 
+// QKNorm of one raw query row of a head (flux_model.py:158-176), shared by attention's raw-Q mode and the IP-Adapter term
+// (ip_attention.hip) so that both see the same query bits.  Lanes l and l ^ 32 hold the row: raw[c] = elements d = c*16 + hi*8 + [0,8) of
+// lane half hi.  Unpacks them into x, returns 1 / rms: each lane sums its 64 squares in (c, j) order, the two halves are added.
+__device__ __forceinline__ float qknorm_rinv(const uint4 (&raw)[8], float (&x)[8][8]) {
+  float ss = 0.f;
+#pragma unroll
+  for (int c = 0; c < 8; ++c) {
+    unpack8(raw[c], x[c]);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) ss += x[c][j] * x[c][j];
+  }
+  {  // the other 64 values of the row sit in lane ^ 32
+    const unsigned u = __float_as_uint(ss);
+    const auto sw2 = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+    ss = __uint_as_float(sw2[0]) + __uint_as_float(sw2[1]);
+  }
+  return 1.0f / sqrtf(ss * (1.0f / 128.0f) + 1e-6f);
+}
+// ... and the normalised values, rounded to bf16: x[j] = bf16((x[j] / rms) * w[j]) for the eight elements of one 16-byte piece
+__device__ __forceinline__ void qknorm_apply(float (&x)[8], float rinv, const float (&w)[8]) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) x[j] = rbf((x[j] * rinv) * w[j]);
+}
+
 // Q fragments (MFMA B operand): 8 x (8 bf16); lane (l31, hi) holds d = c*16 + hi*8 + [0,8) of query row `qld` of (b, h).
 // raw-Q mode (a.Q == nullptr): the row comes straight from the qkv GEMM output and QKNorm + RoPE are applied here
 // (flux_model.py:158-176,60-65), so the normalised / rotated Q tensor never exists in HBM.
@@ -126,26 +150,13 @@ __device__ __forceinline__ void load_q_frags(const AttnArgs& a, int b, int h, in
       rcs[c] = *(const uint4*)(pp + c * 16);
     }
     float x[8][8];
-    float ss = 0.f;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      unpack8(raw[c], x[c]);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) ss += x[c][j] * x[c][j];
-    }
-    {  // the other 64 values of the row sit in lane ^ 32
-      const unsigned u = __float_as_uint(ss);
-      const auto sw2 = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-      ss = __uint_as_float(sw2[0]) + __uint_as_float(sw2[1]);
-    }
-    const float rinv = 1.0f / sqrtf(ss * (1.0f / 128.0f) + 1e-6f);
+    const float rinv = qknorm_rinv(raw, x);
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
       float w[8], cs[8], y[8];
       unpack8(rw[c], w);
       unpack8(rcs[c], cs);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) x[c][j] = rbf((x[c][j] * rinv) * w[j]);
+      qknorm_apply(x[c], rinv, w);
 #pragma unroll
       for (int p = 0; p < 4; ++p) {
         const float cc = cs[2 * p], sn = cs[2 * p + 1];

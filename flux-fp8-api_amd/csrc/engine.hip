@@ -58,6 +58,9 @@ struct StepGraphs {
   unsigned gen = 0;     // fluxmi_tuning_generation() the pieces were captured under
   const void* cn = nullptr;  // the attached ControlNet whose launches (and workspace pointers) are baked into the pieces, or none ...
   unsigned long long cn_gen = 0;  // ... and the generation of its workspace / weight binding: process-wide unique, so a net created at a freed net's address never matches
+  const void* ip = nullptr;  // the IP-Adapter's K / V buffer baked into the pieces (null: no adapter launches), its Nk ...
+  int ip_nk = 0;
+  unsigned long long ip_gen = 0;  // ... and the buffer's generation (an allocation at a freed buffer's address never matches)
   void drop() {
     for (hipGraphExec_t& g : exec)
       if (g) { hipGraphExecDestroy(g); g = nullptr; }
@@ -183,6 +186,16 @@ struct fluxmi_engine {
   fluxmi_engine* cn_owner = nullptr;  // net: the main engine it is attached to
   int cn_batch = 0;                // main: the caller's images the attached cond holds
   float* d_cn_scale = nullptr;
+  // IP-Adapter (fluxmi_engine_set_ip_adapter): the step-invariant keys / values of every double block and the
+  // per-sample, per-block scales in ONE engine-owned allocation (k | v, each bf16 [depth][B][Nk][H], then scales fp32 [B][depth]) made by the
+  // set call -- never inside a capture -- kept while it is large enough and dropped with the workspace.  Contents are device data; on / off,
+  // the buffer and Nk are a kind of step graph.  Nothing of it without an adapter.
+  bool ip_on = false;
+  int ip_nk = 0, ip_B = 0;
+  char* ip_mem = nullptr;
+  size_t ip_bytes = 0;
+  unsigned long long ip_gen = 0;
+  std::vector<float> ip_scales_h;  // the staged scales' host copy (alive until the next set call: the source of an asynchronous copy)
 };
 
 namespace {
@@ -964,6 +977,18 @@ int cn_add(E* e, int slot, hipStream_t s) {
                              e->d_cn_scale, e->B, one, s);
 }
 
+// IP-Adapter: x_img = bf16(x_img + bf16(o_i * scale[b][i])) behind double block i, o_i from the block's raw image q still in "qkv" (all
+// L - Lt image-stream rows: Kontext reference rows included)
+int ip_add(E* e, int i, hipStream_t s) {
+  const int H = e->d.hidden, B = e->B, nk = e->ip_nk;
+  const long long kv = (long long)e->d.depth * B * nk * H;  // elements of k (and of v)
+  const u16* k = (const u16*)e->ip_mem + (long long)i * B * nk * H;
+  const float* sc = (const float*)(e->ip_mem + (size_t)kv * 4) + i;
+  return fluxmi_k_ip_attention(buf<u16>(e, "qkv") + (long long)e->Lt * 3 * H, 3 * H, (long long)e->L * 3 * H, e->norm[i * 4], k, k + kv,
+                               (long long)nk * H, buf<u16>(e, "x") + (long long)e->Lt * H, H, (long long)e->L * H, sc, e->d.depth, B, e->Li,
+                               e->d.heads, nk, s);
+}
+
 // Every block linear (the modulation linears apart) is F8Linear: what the fused path needs.  Otherwise *blk is the first block that has a
 // bf16 one: double block *blk, or single block *blk - depth.
 bool all_block_linears_f8(E* e, int* blk = nullptr) {
@@ -1037,6 +1062,7 @@ int forward_impl(E* e, const u16* img, const u16* txt, const u16* y, const u16* 
     if (ph >= p0 && ph <= p1) {
       FLUXMI_TRY(double_block(e, ctx, i, mode, trial, 0, DOUBLE_STAGES - 1, s));
       if (e->is_cn) FLUXMI_TRY(cn_project(e, e->i_cn_d0 + i, i, s));
+      if (e->ip_on) FLUXMI_TRY(ip_add(e, i, s));  // block, adapter term, ControlNet residual
       if (e->cn) FLUXMI_TRY(cn_add(e, i / ((e->d.depth + e->cn->d.depth - 1) / e->cn->d.depth), s));
     }
   }
@@ -1126,6 +1152,8 @@ void free_ws(E* e) {
   if (e->d_sol_coef) { hipFree(e->d_sol_coef); e->d_sol_coef = nullptr; e->d_sol_ctl = nullptr; }
   if (e->d_sol_ids) { hipFree(e->d_sol_ids); e->d_sol_ids = nullptr; e->sol_ids_bytes = 0; }
   e->sol_on = e->sol_noise = false;
+  if (e->ip_mem) { hipFree(e->ip_mem); e->ip_mem = nullptr; e->ip_bytes = 0; }
+  e->ip_on = false;
   if (e->ws) { hipFree(e->ws); e->ws = nullptr; }
   e->bufs.clear();
   e->ws_bytes = 0;
@@ -1515,6 +1543,14 @@ static int cn_usable(fluxmi_engine_t* e) {
   return 0;
 }
 
+// what a set IP-Adapter excludes, checked by every call that runs it (the state may have been set after the adapter)
+static int ip_usable(fluxmi_engine_t* e) {
+  FLUXMI_REQUIRE(!e->masked, "IP-Adapter: a token-group attention table is set on this engine (regional prompts do not combine with an IP-Adapter)");
+  FLUXMI_REQUIRE(!(e->fb_threshold > 0.f), "IP-Adapter: step caching is on (it does not combine with an IP-Adapter)");
+  FLUXMI_REQUIRE(e->ip_mem && e->ip_B == e->B, "IP-Adapter: the adapter holds %d samples, the prepared batch is %d", e->ip_B, e->B);
+  return 0;
+}
+
 int fluxmi_engine_forward(fluxmi_engine_t* e, const void* img, const void* txt, const void* y, const void* timesteps,
                           const void* guidance, void* pred, int mode, int trial_index, void* stream) {
   FLUXMI_REQUIRE(e && e->ws, "engine_forward: call fluxmi_engine_prepare first");
@@ -1526,6 +1562,7 @@ int fluxmi_engine_forward(fluxmi_engine_t* e, const void* img, const void* txt, 
   if (mode == 1) FLUXMI_TRY(build_qluts(e, (hipStream_t)stream));
   SplitkScope splitk(e);
   FLUXMI_TRY(ensure_pairs(e, (hipStream_t)stream));
+  if (e->ip_on) FLUXMI_TRY(ip_usable(e));
   if (fluxmi_engine_t* n = e->cn) {  // the attached ControlNet first: calibrating on its own counter, else frozen like the main model
     FLUXMI_TRY(cn_usable(e));
     const bool ncal = any_f8(n) && n->cn_trial <= n->d.num_trials;
@@ -1571,6 +1608,12 @@ static void graphs_stale(fluxmi_engine_t* e, StepGraphs& g, bool cfg) {
   if (g.cn != e->cn || (e->cn && g.cn_gen != e->cn->ws_gen)) g.ok = g.warmed = false;
   g.cn = e->cn;
   g.cn_gen = e->cn ? e->cn->ws_gen : 0;
+  // ... and the IP-Adapter: its launches, its buffer and Nk are baked in (K / V contents and scales are device data)
+  const void* ip = e->ip_on ? e->ip_mem : nullptr;
+  if (g.ip != ip || (ip && (g.ip_nk != e->ip_nk || g.ip_gen != e->ip_gen))) g.ok = g.warmed = false;
+  g.ip = ip;
+  g.ip_nk = ip ? e->ip_nk : 0;
+  g.ip_gen = ip ? e->ip_gen : 0;
   g.cfg = cfg;
   g.masked = e->masked;
   g.blend = e->inp_on;
@@ -1817,6 +1860,7 @@ static int denoise_impl(fluxmi_engine_t* e, void* img, const void* txt, const vo
     return fluxmi_k_euler_rows(buf<u16>(e, "img_s"), buf<u16>(e, "pred_s"), e->d_dts, e->d_step, B, Li, e->Lpred, C, st);
   };
   const bool main_f8 = any_f8(e);
+  if (e->ip_on) FLUXMI_TRY(ip_usable(e));
   // the attached ControlNet: its own scratch / weight copies, the request's schedule and step counter shared with the main engine
   fluxmi_engine_t* const cn = e->cn;
   if (cn) {
@@ -2133,6 +2177,53 @@ int fluxmi_controlnet_trial(fluxmi_engine_t* cn, int* trial_index) {
   return 0;
 }
 
+// The IP-Adapter of the prepared shape (fluxmi.h): K / V are copied into the engine's own buffer on `stream`, in order with the forward /
+// denoise call that follows on it; the scales are staged behind them.
+int fluxmi_engine_set_ip_adapter(fluxmi_engine_t* e, const void* k_ip, const void* v_ip, int Nk, int batch, const float* scales_host, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  FLUXMI_REQUIRE(e, "engine_set_ip_adapter: NULL engine");
+  if (!k_ip) {
+    e->ip_on = false;
+    return 0;
+  }
+  FLUXMI_REQUIRE(!e->is_cn, "engine_set_ip_adapter: a ControlNet engine takes no IP-Adapter (set it on the main engine)");
+  FLUXMI_REQUIRE(e->ws, "engine_set_ip_adapter: call fluxmi_engine_prepare first (the adapter belongs to the prepared shape)");
+  FLUXMI_REQUIRE(v_ip && scales_host, "engine_set_ip_adapter: NULL v_ip / scales_host");
+  FLUXMI_REQUIRE(Nk >= 1 && Nk <= 64, "engine_set_ip_adapter: Nk = %d outside 1..64", Nk);
+  FLUXMI_REQUIRE(batch == e->B, "engine_set_ip_adapter: K / V for %d samples on a prepared batch of %d (a guided request carries both branches)",
+                 batch, e->B);
+  FLUXMI_REQUIRE(e->d.depth >= 1 && e->d.hidden == e->d.heads * 128, "engine_set_ip_adapter: the adapter needs double blocks and head_dim 128");
+  FLUXMI_REQUIRE(!e->masked, "engine_set_ip_adapter: a token-group attention table is set (regional prompts do not combine with an IP-Adapter)");
+  FLUXMI_REQUIRE(!(e->fb_threshold > 0.f), "engine_set_ip_adapter: step caching is on (it does not combine with an IP-Adapter)");
+  const size_t kv = (size_t)e->d.depth * batch * Nk * e->d.hidden * 2, sc = (size_t)batch * e->d.depth * 4, total = 2 * kv + sc;
+  if (!e->ip_mem || e->ip_bytes < total) {
+    e->ip_on = false;
+    if (e->ip_mem) {  // a captured graph may hold the old buffer: never free it under a replay in flight
+      FLUXMI_CHECK_HIP(hipDeviceSynchronize());
+      hipFree(e->ip_mem);
+      e->ip_mem = nullptr; e->ip_bytes = 0;
+    }
+    if (hipMalloc((void**)&e->ip_mem, total) != hipSuccess) {
+      (void)hipGetLastError();
+      e->ip_mem = nullptr;
+      fluxmi_set_error("engine_set_ip_adapter: hipMalloc(%zu bytes) failed", total);
+      return 2;
+    }
+    e->ip_bytes = total;
+    e->ip_gen = next_generation();
+  }
+  // the layout follows Nk (k | v | scales packed for THIS Nk): Nk is part of the graph key
+  FLUXMI_CHECK_HIP(hipMemcpyAsync(e->ip_mem, k_ip, kv, hipMemcpyDeviceToDevice, s));
+  FLUXMI_CHECK_HIP(hipMemcpyAsync(e->ip_mem + kv, v_ip, kv, hipMemcpyDeviceToDevice, s));
+  FLUXMI_CHECK_HIP(hipStreamSynchronize(s));  // (the previous staging copy, if any, has left ip_scales_h)
+  e->ip_scales_h.assign(scales_host, scales_host + (size_t)batch * e->d.depth);
+  FLUXMI_CHECK_HIP(hipMemcpyAsync(e->ip_mem + 2 * kv, e->ip_scales_h.data(), sc, hipMemcpyHostToDevice, s));
+  e->ip_nk = Nk;
+  e->ip_B = batch;
+  e->ip_on = true;
+  return 0;
+}
+
 int fluxmi_engine_set_step_cache(fluxmi_engine_t* e, float threshold, int max_consecutive_hits) {
   FLUXMI_REQUIRE(e, "engine_set_step_cache: NULL engine");
   FLUXMI_REQUIRE(threshold >= 0.f, "engine_set_step_cache: threshold %g must be >= 0 and not NaN (0 = off)", (double)threshold);
@@ -2162,6 +2253,7 @@ int fluxmi_engine_run_phase(fluxmi_engine_t* e, int mode, int phase_from, int ph
                  "engine_run_phase: step %d is outside the modulation table of the last denoise call (from step %d)", step, e->mods_step0);
   FLUXMI_REQUIRE(mode == 2 || phase_from > PH_EMBED || e->txt_emb_valid, "engine_run_phase: no embedded text from a denoise call on this shape");
   FLUXMI_REQUIRE(!e->cn && !e->is_cn, "engine_run_phase: a ControlNet is attached (the phases are the main model's alone: detach it first)");
+  FLUXMI_REQUIRE(!e->ip_on, "engine_run_phase: an IP-Adapter is set (the phases are the plain model's alone: clear it first)");
   SplitkScope splitk(e);
   FLUXMI_TRY(ensure_pairs(e, s));
   if (mode == 1) {
@@ -2250,7 +2342,7 @@ int fluxmi_engine_copy_buffer(fluxmi_engine_t* e, const char* name, long long of
 
 int fluxmi_engine_workspace_bytes(fluxmi_engine_t* e, long long* bytes) {
   FLUXMI_REQUIRE(e && bytes, "engine_workspace_bytes: NULL argument");
-  *bytes = (long long)(e->ws_bytes + e->pairs_bytes + e->mods_all_bytes + e->fb_bytes + e->inp_bytes + e->sol_bytes + e->sol_ids_bytes);  // workspace + row-pair weight copies + modulation table + step cache + inpainting + solver buffers + noise ids
+  *bytes = (long long)(e->ws_bytes + e->pairs_bytes + e->mods_all_bytes + e->fb_bytes + e->inp_bytes + e->sol_bytes + e->sol_ids_bytes + e->ip_bytes);  // workspace + row-pair weight copies + modulation table + step cache + inpainting + solver buffers + noise ids
   return 0;
 }
 

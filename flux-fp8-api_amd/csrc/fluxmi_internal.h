@@ -190,6 +190,10 @@ int fluxmi_k_fb_store(const void* x, long long x_bstride, const void* h1, void* 
 int fluxmi_k_fb_apply(void* x, long long x_bstride, const void* h1, long long h1_bstride, const void* R, int B, long long n, hipStream_t s);
 // ControlNet residual hand-over: x[b, j] = bf16(x[b, j] + bf16(r[b, j] * *s_dev)), B samples of n elements, batch strides in elements
 int fluxmi_k_add_scaled(void* x, long long x_bstride, const void* r, long long r_bstride, const float* s_dev, int B, long long n, hipStream_t s);
+// IP-Adapter term of a double block (ip_attention.hip; include/fluxmi.h, fluxmi_ip_attention): scale == NULL writes o, else x += bf16(o * scale[b])
+int fluxmi_k_ip_attention(const void* qkv, long long ld_qkv, long long qkv_bstride, const void* qn_scale, const void* k_ip, const void* v_ip,
+                          long long kv_bstride, void* out, long long ld_o, long long o_bstride, const float* scale, long long scale_bstride,
+                          int B, int rows, int heads, int Nk, hipStream_t s);
 int fluxmi_k_set_timestep(void* t_vec, const float* ts, const int* step, int B, hipStream_t s);
 int fluxmi_k_advance_step(int* step, hipStream_t s);
 int fluxmi_k_clock_sample(unsigned long long* out2, hipStream_t s);

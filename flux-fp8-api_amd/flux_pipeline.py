@@ -29,7 +29,7 @@ import torch
 import lora_loading  # noqa: F401  (same import side as the reference)
 from fluxmi import dist as fdist
 from fluxmi import solvers
-from util import (ModelSpec, ModelVersion, engine_flow_dtype, into_device, into_dtype, load_config_from_path, load_controlnet,
+from util import (ModelSpec, ModelVersion, engine_flow_dtype, into_device, into_dtype, load_config_from_path, load_controlnet, load_ip_adapter,
                   load_models_from_config)
 
 MAX_RAND = 2**32 - 1
@@ -152,7 +152,7 @@ class FluxPipeline:
     def __init__(self, name: str, offload: bool = False, clip=None, t5=None, model=None, ae=None,
                  dtype: torch.dtype = torch.float16, verbose: bool = False, flux_device="cuda:0", ae_device="cuda:1",
                  clip_device="cuda:1", t5_device="cuda:1", config: ModelSpec = None, debug: bool = False, redux=None,
-                 controlnet=None):
+                 controlnet=None, ip_adapter=None):
         if config is None:
             raise ValueError("ModelSpec config is required!")
         self.debug, self.name, self.verbose, self.offload = debug, name, verbose, offload
@@ -162,6 +162,7 @@ class FluxPipeline:
         self.clip, self.t5, self.model, self.ae = clip, t5, model, ae
         self.redux = redux  # FLUX.1 Redux image encoder (modules/image_embedders.ReduxImageEncoder) or None
         self.controlnet = controlnet  # FLUX ControlNet (modules/controlnet.FluxControlNet, config.controlnet_path) or None
+        self.ip_adapter = ip_adapter  # FLUX IP-Adapter (modules/ip_adapter.IPAdapter, config.ip_adapter_path / clip_vision_path) or None
         self.rng = torch.Generator(device="cpu")
         self.ae_dtype = torch.bfloat16
         self.config = config
@@ -466,6 +467,34 @@ class FluxPipeline:
             raise RuntimeError("fluxmi: controlnet_image needs an autoencoder (config.ae_path) -- none is attached; pass controlnet_cond")
         return self.prepare_control_conditioning(controlnet_image, height, width, num_images=num_images, generator=generator)
 
+    # ---- FLUX IP-Adapter image prompts ---------------------------------------------------------------------------------------------------
+    def prepare_ip_adapter(self, images, image_embeds, scale, negative_image, negative_scale, guided: bool):
+        """-> (call, guided_call): the `ip_adapter=` arguments of Flux.denoise for the unguided steps (the prompt branch's K / V, [depth, 1,
+        Nk, H]) and, for a guided request, for the guided steps ([depth, 2, Nk, H]: prompt branch, then negative branch with its own K / V
+        and scale; else None).  The negative branch defaults to black images, one per prompt image (XLabs); a float tensor [n, 768] is
+        taken as embeds."""
+        from modules.ip_adapter import IPAdapterCall
+
+        ad = self.ip_adapter
+        emb = ad.embed(images) if image_embeds is None else image_embeds
+        k, v = ad.kv(emb)
+        call = IPAdapterCall(k, v, scale)
+        if not guided:
+            return call, None
+        if isinstance(negative_image, torch.Tensor) and negative_image.is_floating_point():
+            nemb = negative_image
+        else:
+            n = emb.shape[0]
+            if negative_image is None:
+                S = ad.clip.cfg["image_size"] if ad.clip is not None else 224
+                negative_image = [np.zeros((S, S, 3), dtype=np.uint8)] * n
+            nemb = ad.embed(negative_image)
+        if nemb.shape[0] != emb.shape[0]:
+            raise ValueError(f"fluxmi: negative_ip_adapter_image holds {nemb.shape[0]} images, ip_adapter_image {emb.shape[0]} (both branches "
+                             "run in one batch: the same number of image tokens)")
+        nk, nv = ad.kv(nemb)
+        return call, IPAdapterCall(torch.cat((k, nk), 1), torch.cat((v, nv), 1), torch.cat((scale, negative_scale), 0))
+
     # ---- FLUX.1 Redux image prompts ------------------------------------------------------------------------------------------------------
     def _require_redux(self):
         if self.redux is None:
@@ -664,7 +693,9 @@ class FluxPipeline:
                  regional_tokens: int = 128, inpaint_mask=None, inpaint_differential: bool = False, controlnet_image=None,
                  controlnet_conditioning_scale: float = 1.0, control_mode: Optional[int] = None, control_guidance_start: float = 0.0,
                  control_guidance_end: float = 1.0, controlnet_cond: Optional[torch.Tensor] = None, sampler: str = "euler",
-                 sigma_schedule: Optional[str] = None, sigmas=None, eta: float = 1.0, s_noise: float = 1.0, noise_seed: Optional[int] = None):
+                 sigma_schedule: Optional[str] = None, sigmas=None, eta: float = 1.0, s_noise: float = 1.0, noise_seed: Optional[int] = None,
+                 ip_adapter_image=None, ip_adapter_image_embeds: Optional[torch.Tensor] = None, ip_adapter_scale=1.0,
+                 negative_ip_adapter_image=None, negative_ip_adapter_scale=1.0):
         """`reference_image` (FLUX.1 Kontext [dev] instruction editing): an image the prompt describes an edit of, in any form `init_image`
         takes; see prepare_kontext_reference.  Composes with `init_image` / `strength` unchanged.
         FLUX.1 Fill [dev] (a model with 320 conditioning channels): `init_image` is the image to inpaint and `mask_image` (white =
@@ -733,7 +764,17 @@ class FluxPipeline:
         and no seed given that is each rank's own), at the evaluation's index within the whole request: a request cut by
         `true_cfg_interval` or the control guidance interval never reuses a draw, and nothing is taken from the request's torch generator.
         A request or slice whose program draws nothing (eta 0, s_noise 0, the lone step onto sigma 0) runs as a deterministic solver call.
-        Composes like the other samplers; `eta`, `s_noise` or `noise_seed` with a deterministic sampler is refused."""
+        Composes like the other samplers; `eta`, `s_noise` or `noise_seed` with a deterministic sampler is refused.
+        `ip_adapter_image` (a FLUX IP-Adapter in the XLabs format, config.ip_adapter_path + clip_vision_path; modules/ip_adapter.py): an
+        image prompt in any form `init_image` takes, or a list -- several images concatenate their tokens (Nk = T n <= 64; an extension of
+        XLabs, as the image list is for Redux) -- or `ip_adapter_image_embeds`, the CLIP image_embeds [n, 768] already computed (the tower is
+        skipped).  Unlike Redux it does not lengthen the text stream: every double block adds `ip_adapter_scale` (a float, or one float
+        per double block) times a small cross-attention of its image queries over the image tokens.  With a negative prompt the negative
+        branch gets `negative_ip_adapter_image` (default: a black image, as XLabs does; the same number of images; a [n, 768] tensor is
+        taken as embeds) at `negative_ip_adapter_scale`.  Composes with img2img, num_images, LoRA, Redux, a Kontext reference, Fill /
+        Depth / Canny, a negative prompt, `inpaint_mask`, every sampler and a ControlNet; refused with `regions`, `cache_threshold` > 0 and
+        under a process group.  Parity with XLabs' code is unpinned and image quality on real weights is not established here (README).
+        Without it the request is today's, launch for launch."""
         stochastic = sampler in solvers.STOCHASTIC_SAMPLERS
         if sampler not in solvers.SAMPLERS and not stochastic:
             raise ValueError(f"fluxmi: sampler={sampler!r}: expected one of {solvers.SAMPLERS + solvers.STOCHASTIC_SAMPLERS}")
@@ -787,6 +828,31 @@ class FluxPipeline:
                                  f"end <= 1 and a finite controlnet_conditioning_scale")
             if fdist.world_size() > 1:
                 raise ValueError("fluxmi: a ControlNet request under a process group is not supported")
+        ip_on = ip_adapter_image is not None or ip_adapter_image_embeds is not None
+        if ip_on:
+            from modules.ip_adapter import scale_table
+
+            if getattr(self, "ip_adapter", None) is None:
+                raise ValueError("fluxmi: ip_adapter_image needs an IP-Adapter: set config.ip_adapter_path (a local XLabs-format "
+                                 "flux-ip-adapter checkpoint) and config.clip_vision_path (the CLIP ViT-L/14 vision tower)")
+            if ip_adapter_image is not None and ip_adapter_image_embeds is not None:
+                raise ValueError("fluxmi: pass ip_adapter_image or ip_adapter_image_embeds, not both")
+            if regions is not None:
+                raise ValueError("fluxmi: regions do not combine with an IP-Adapter")
+            if cache_on:
+                raise ValueError("fluxmi: cache_threshold > 0 (step caching) does not combine with an IP-Adapter")
+            if fdist.world_size() > 1:
+                raise ValueError("fluxmi: an IP-Adapter request under a process group is not supported")
+            depth = self.ip_adapter.depth
+            if depth != len(self.model.double_blocks) or self.ip_adapter.hidden != self.model.hidden_size:
+                raise ValueError(f"fluxmi: the IP-Adapter has {depth} double blocks of hidden {self.ip_adapter.hidden}, the flow model "
+                                 f"{len(self.model.double_blocks)} of {self.model.hidden_size}")
+            try:
+                ip_scales = (scale_table(ip_adapter_scale, depth, 1), scale_table(negative_ip_adapter_scale, depth, 1))
+            except (TypeError, ValueError) as e:
+                raise ValueError(f"fluxmi: ip_adapter_scale / negative_ip_adapter_scale: {e}") from None
+        elif negative_ip_adapter_image is not None:
+            raise ValueError("fluxmi: negative_ip_adapter_image goes with ip_adapter_image / ip_adapter_image_embeds")
         if inpaint_mask is None and inpaint_differential:
             raise ValueError("fluxmi: inpaint_differential needs an inpaint_mask (the change map)")
         if inpaint_mask is not None and init_image is None:
@@ -929,6 +995,10 @@ class FluxPipeline:
             if cn_cond.ndim != 3 or cn_cond.shape[0] not in (1, num_images) or tuple(cn_cond.shape[1:]) != tuple(img.shape[1:]):
                 raise ValueError(f"fluxmi: controlnet_cond {tuple(cn_cond.shape)}: expected [1 or {num_images}, {img.shape[1]}, {img.shape[2]}]")
             cn_cond = cn_cond.expand(num_images, -1, -1).contiguous()
+        ip_calls = None
+        if ip_on:
+            ip_calls = self.prepare_ip_adapter(ip_adapter_image, ip_adapter_image_embeds, ip_scales[0],
+                                               negative_ip_adapter_image if guided else None, ip_scales[1], guided)
         first_image = 0  # the request's index of this rank's first image (the noise ids of a stochastic sampler count from it)
         if world > 1:
             if guided:  # the negative embeddings ride in the one broadcast, behind the prompt's
@@ -972,6 +1042,9 @@ class FluxPipeline:
                 tab = [build_region_groups(n_base, regional_tokens, region_grids, n_ref=n_ref, negative=ng) for ng in ((False, True) if guided else (False,))]
                 plain_kw = dict(attn_groups=tab[0][None].to(self.device_flux))
                 neg["attn_groups"] = torch.stack(tab).to(self.device_flux)
+            if ip_calls is not None:  # the prompt branch's tables for the unguided steps, both branches' for the guided ones
+                plain_kw = dict(plain_kw, ip_adapter=ip_calls[0])
+                neg["ip_adapter"] = ip_calls[1]
             thr = self.inpaint_thresholds(n) if inpaint is not None and inpaint_differential else None
             latents = img
             if stochastic:  # per-image ids of the noise: the request's image index, not the rank's or the pass's
@@ -1082,4 +1155,4 @@ class FluxPipeline:
         return cls(name=config.version, clip=models.clip, t5=models.t5, model=flow_model, ae=models.ae, dtype=flux_dtype, verbose=False,
                    flux_device=flux_device, ae_device=into_device(config.ae_device), clip_device=into_device(config.text_enc_device),
                    t5_device=into_device(config.text_enc_device), config=config, debug=debug, redux=redux,
-                   controlnet=load_controlnet(config, device=flux_device))
+                   controlnet=load_controlnet(config, device=flux_device), ip_adapter=load_ip_adapter(config, device=flux_device))

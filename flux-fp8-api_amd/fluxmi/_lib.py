@@ -141,6 +141,8 @@ _SIGS = {
     "fluxmi_controlnet_create": ([C.POINTER(ModelDesc), C.POINTER(Linear), i32, C.POINTER(vp), i32, vp, i32, C.POINTER(vp)], i32),
     "fluxmi_engine_attach_controlnet": ([vp, vp, vp, i32, i32, f32, i32, vp], i32),
     "fluxmi_controlnet_trial": ([vp, C.POINTER(i32)], i32),
+    "fluxmi_ip_attention": ([vp, i64, i64, vp, vp, vp, i64, vp, i64, i64, vp, i64, i32, i32, i32, i32, vp], i32),
+    "fluxmi_engine_set_ip_adapter": ([vp, vp, vp, i32, i32, C.POINTER(f32), vp], i32),
 }
 AMAX_HOOK = C.CFUNCTYPE(i32, vp, i32, i32, vp)
 EXPORTS = sorted(list(_SIGS) + ["fluxmi_last_error"])

@@ -547,3 +547,37 @@ def add_scaled(x: torch.Tensor, r: torch.Tensor, scale) -> torch.Tensor:
     rs = r.stride(0) if B > 1 else n
     _lib.call("fluxmi_add_scaled", _p(x), xs, _p(r), rs, _p(s), B, n, _stream())
     return x
+
+
+def ip_attention(qkv: torch.Tensor, qn_scale: torch.Tensor, k_ip: torch.Tensor, v_ip: torch.Tensor, heads: int, nk: Optional[int] = None,
+                 x: Optional[torch.Tensor] = None, scale=None) -> torch.Tensor:
+    """The IP-Adapter term of a double block (fluxmi_ip_attention).  qkv: bf16 [B, rows, >= heads * 128] view of the image rows of a qkv GEMM
+    output (q in the leading heads * 128 columns; row and batch strides are taken from the view); qn_scale: bf16 [128]; k_ip, v_ip: bf16
+    [B, >= nk, heads * 128], of which rows [0, nk) are read (nk defaults to all).  x is None: returns o = bf16 [B, rows, heads * 128].  Else the
+    fused form, in place: x = bf16(x + bf16(o * scale[b])), x a bf16 [B, rows, heads * 128] view (strided like qkv), scale a float or an fp32
+    device tensor [B]."""
+    for t, nm in ((qkv, "qkv"), (qn_scale, "qn_scale"), (k_ip, "k_ip"), (v_ip, "v_ip")):
+        _req(t, torch.bfloat16, nm)
+    hd = heads * 128
+    if qkv.ndim != 3 or qkv.shape[-1] < hd or qkv.stride(-1) != 1 or qn_scale.numel() != 128 or not qn_scale.is_contiguous():
+        raise ValueError(f"ip_attention: qkv {tuple(qkv.shape)} / qn_scale {tuple(qn_scale.shape)} for {heads} heads of 128")
+    B, rows = qkv.shape[0], qkv.shape[1]
+    nk = k_ip.shape[1] if nk is None else int(nk)
+    if k_ip.shape != v_ip.shape or k_ip.ndim != 3 or k_ip.shape[0] != B or k_ip.shape[2] != hd or k_ip.shape[1] < nk or k_ip.stride() != v_ip.stride() \
+            or k_ip.stride(2) != 1 or k_ip.stride(1) != hd:
+        raise ValueError(f"ip_attention: k_ip {tuple(k_ip.shape)} / v_ip {tuple(v_ip.shape)} for B = {B}, nk = {nk}, {heads} heads")
+    if x is None:
+        out = torch.empty((B, rows, hd), dtype=torch.bfloat16, device=qkv.device)
+        s, ss = None, 0
+    else:
+        out = _req(x, torch.bfloat16, "x")
+        if out.shape != (B, rows, hd) or out.stride(-1) != 1:
+            raise ValueError(f"ip_attention: x {tuple(out.shape)} vs [{B}, {rows}, {hd}]")
+        s = scale if isinstance(scale, torch.Tensor) else torch.full((B,), float(scale), dtype=torch.float32, device=qkv.device)
+        _req(s, torch.float32, "scale")
+        if s.numel() != B:
+            raise ValueError(f"ip_attention: {s.numel()} scales for {B} samples")
+        ss = s.stride(0) if s.ndim else 0
+    _lib.call("fluxmi_ip_attention", _p(qkv), qkv.stride(1), qkv.stride(0), _p(qn_scale), _p(k_ip), _p(v_ip), k_ip.stride(0), _p(out), out.stride(1),
+              out.stride(0), _p(s), ss, B, rows, heads, nk, _stream())
+    return out

@@ -121,3 +121,55 @@ def make_controlnet_state_dict(params, num_double: int, num_single: int, num_mod
     if num_mode:
         sd["controlnet_mode_embedder.weight"] = torch.randn(num_mode, H, generator=gen, device=device, dtype=torch.float32).to(dtype)
     return sd
+
+
+def make_ip_adapter_state_dict(hidden: int, depth: int, num_tokens: int = 4, seed: int = 0, dtype=torch.bfloat16, device="cpu",
+                               kv_gain: float = 4.0) -> Dict[str, torch.Tensor]:
+    """A synthetic XLabs-format FLUX IP-Adapter (modules.ip_adapter): ip_adapter_proj_model.{proj, norm} and, per double block, the
+    processor's ip_adapter_double_stream_{k,v}_proj.  `kv_gain` makes keys / values as large as a normalised query row (unit rms x 4), so
+    the softmax is not flat and the term is as large as the stream it joins: a parity test cannot pass by ignoring it."""
+    gen = torch.Generator(device=device).manual_seed(seed + 15485863)
+    sd: Dict[str, torch.Tensor] = {}
+    L = lambda *a, **k: _linear(sd, *a, gen=gen, device=device, dtype=dtype, **k)
+    L("ip_adapter_proj_model.proj", num_tokens * 4096, 768, outliers=False)
+    sd["ip_adapter_proj_model.norm.weight"] = (1.0 + 0.1 * torch.randn(4096, generator=gen, device=device)).to(dtype)
+    sd["ip_adapter_proj_model.norm.bias"] = (0.1 * torch.randn(4096, generator=gen, device=device)).to(dtype)
+    for i in range(depth):
+        for kv in ("k", "v"):
+            L(f"double_blocks.{i}.processor.ip_adapter_double_stream_{kv}_proj", hidden, 4096, gain=kv_gain, outliers=False)
+    return sd
+
+
+def make_clip_vision_state_dict(config: dict, seed: int = 0, dtype=torch.float32) -> Dict[str, torch.Tensor]:
+    """A synthetic transformers CLIPVisionModelWithProjection state dict for a CLIPVisionConfig dict (hidden_size, intermediate_size,
+    num_hidden_layers, num_attention_heads, image_size, patch_size, projection_dim): weights drawn so that activations stay O(1) through
+    the depth (LayerNorm gains around 1, linears at 1 / sqrt(fan_in))."""
+    gen = torch.Generator().manual_seed(seed + 32452843)
+    D, Fd, P, S = config["hidden_size"], config["intermediate_size"], config["patch_size"], config["image_size"]
+    n_pos = (S // P) ** 2 + 1
+    rn = lambda *shape, s=1.0: (s * torch.randn(*shape, generator=gen)).to(dtype)
+    sd = {"vision_model.embeddings.class_embedding": rn(D, s=0.5),
+          "vision_model.embeddings.patch_embedding.weight": rn(D, config.get("num_channels", 3), P, P, s=1.0 / math.sqrt(3 * P * P)),
+          "vision_model.embeddings.position_embedding.weight": rn(n_pos, D, s=0.1)}
+
+    def ln(name):
+        sd[name + ".weight"] = (1.0 + 0.1 * torch.randn(D, generator=gen)).to(dtype)
+        sd[name + ".bias"] = rn(D, s=0.05)
+
+    def lin(name, n_out, n_in, bias=True):
+        sd[name + ".weight"] = rn(n_out, n_in, s=1.0 / math.sqrt(n_in))
+        if bias:
+            sd[name + ".bias"] = rn(n_out, s=0.05)
+
+    ln("vision_model.pre_layrnorm")
+    for i in range(config["num_hidden_layers"]):
+        p = f"vision_model.encoder.layers.{i}"
+        for n in ("q_proj", "k_proj", "v_proj", "out_proj"):
+            lin(f"{p}.self_attn.{n}", D, D)
+        ln(p + ".layer_norm1")
+        ln(p + ".layer_norm2")
+        lin(p + ".mlp.fc1", Fd, D)
+        lin(p + ".mlp.fc2", D, Fd)
+    ln("vision_model.post_layernorm")
+    lin("visual_projection", config["projection_dim"], D, bias=False)
+    return sd

@@ -502,6 +502,47 @@ class Flux(nn.Module):
         if net is not None:
             net._detach(self._engine)
 
+    def _check_ip_adapter(self, ip_adapter, B_engine: int, attn_groups, cache_threshold: float = 0.0):
+        """the `ip_adapter=` argument (modules.ip_adapter.IPAdapterCall) validated before any device work -> None or (k_ip, v_ip, scales) for
+        the B_engine samples of the engine pass (both branches of a guided call): k_ip, v_ip [depth, B_engine, Nk, hidden], scales a
+        [B_engine, depth] float32 CPU tensor"""
+        if ip_adapter is None:
+            return None
+        if attn_groups is not None:
+            raise ValueError("ip_adapter: regional prompts (attn_groups) do not combine with an IP-Adapter")
+        if cache_threshold > 0.0:
+            raise ValueError("ip_adapter: step caching (cache_threshold > 0) does not combine with an IP-Adapter")
+        k, v = ip_adapter.k_ip, ip_adapter.v_ip
+        depth = len(self.double_blocks)
+        if not (isinstance(k, torch.Tensor) and isinstance(v, torch.Tensor)) or k.ndim != 4 or k.shape != v.shape or k.shape[0] != depth \
+                or k.shape[1] not in (1, B_engine) or k.shape[3] != self.hidden_size:
+            raise ValueError(f"ip_adapter: k_ip / v_ip {tuple(getattr(k, 'shape', ()))} / {tuple(getattr(v, 'shape', ()))}: expected two tensors "
+                             f"[{depth}, 1 or {B_engine}, Nk, {self.hidden_size}]")
+        if not 1 <= k.shape[2] <= 64:
+            raise ValueError(f"ip_adapter: Nk = {k.shape[2]} image tokens outside 1..64")
+        if self.hidden_size != self.num_heads * 128:
+            raise ValueError("ip_adapter: the adapter kernel needs heads of 128")
+        from modules.ip_adapter import scale_table
+
+        return k.expand(-1, B_engine, -1, -1), v.expand(-1, B_engine, -1, -1), scale_table(ip_adapter.scale, depth, B_engine)
+
+    def _set_ip_adapter(self, ip, device):
+        """after _prepare, under the lock: hand the call's adapter tables to the engine (it copies them), or nothing: no adapter is set
+        between calls (_clear_ip_adapter), so a plain call makes the host calls it always made"""
+        if ip is None:
+            return False
+        k, v, sc = ip
+        k = k.to(device=device, dtype=torch.bfloat16).contiguous()
+        v = v.to(device=device, dtype=torch.bfloat16).contiguous()
+        sc = sc.contiguous()
+        _lib.call("fluxmi_engine_set_ip_adapter", self._engine, ops._p(k), ops._p(v), int(k.shape[2]), int(k.shape[1]),
+                  sc.numpy().ctypes.data_as(C.POINTER(C.c_float)), ops._stream())
+        return True
+
+    def _clear_ip_adapter(self, was_set):
+        if was_set:
+            _lib.call("fluxmi_engine_set_ip_adapter", self._engine, None, None, 0, 0, None, ops._stream())
+
     # ---- batch-sharded calibration (SURVEY.md 8e-3) ------------------------------------------------------------------
     def enable_amax_exchange(self, reduce_fn=None):
         """Keep the F8Linear input scales of batch-sharded replicas IDENTICAL to those of the whole batch on one GPU: the reference
@@ -600,7 +641,7 @@ class Flux(nn.Module):
     def forward(self, img: Tensor, img_ids: Tensor, txt: Tensor, txt_ids: Tensor, timesteps: Tensor, y: Tensor,
                 guidance: Tensor | None = None, mode: Optional[int] = None, img_cond_seq: Tensor | None = None,
                 img_cond_seq_ids: Tensor | None = None, img_cond: Tensor | None = None, attn_groups: Tensor | None = None,
-                controlnet=None) -> Tensor:
+                controlnet=None, ip_adapter=None) -> Tensor:
         """One denoise-step evaluation (reference flux_model.py:672-716).  mode=None picks what the reference would do:
         calibrating (unfused) while any F8Linear still has trials to record, fused once frozen.
         FLUX.1 Kontext: `img_cond_seq` [B, Lc, C] / `img_cond_seq_ids` [B, Lc, 3] (flux_pipeline.prepare_kontext_reference) run through every
@@ -611,7 +652,10 @@ class Flux(nn.Module):
         every attention of the forward then runs F.scaled_dot_product_attention(q, k, v, attn_mask=allowed) instead of the dense one.
         `controlnet`: a modules.controlnet.ControlNetCall -- the ControlNet runs first on the same inputs and its per-block residuals, times
         the conditioning scale, are added to the image stream behind the main blocks (diffusers' FluxControlNetModel / FluxTransformer2DModel);
-        it calibrates on its own counter.  None = today's call."""
+        it calibrates on its own counter.  None = today's call.
+        `ip_adapter`: a modules.ip_adapter.IPAdapterCall -- behind every double block the image stream gains ip_scale times the decoupled
+        cross-attention of the block's image query over the adapter's image tokens (csrc/ip_attention.hip), before a ControlNet's residual.
+        Refused with attn_groups.  None = today's call."""
         if img.ndim != 3 or txt.ndim != 3:
             raise ValueError("Input img and txt tensors must have 3 dimensions.")
         if self.params.guidance_embed and guidance is None:
@@ -619,6 +663,7 @@ class Flux(nn.Module):
         bf = lambda t: t.to(torch.bfloat16).contiguous()
         Li = img.shape[1]
         cn = self._check_controlnet(controlnet, img, img.shape[0], img_cond_seq is not None or img_cond_seq_ids is not None, attn_groups)
+        ip = self._check_ip_adapter(ip_adapter, img.shape[0], attn_groups)
         img = self._with_channels(img, img_cond, img_cond_seq)
         img, img_ids, Lc = self._with_reference(img, img_ids, img_cond_seq, img_cond_seq_ids)
         img, txt, y, timesteps = bf(img), bf(txt), bf(y), bf(timesteps)
@@ -638,8 +683,12 @@ class Flux(nn.Module):
             pred = torch.empty(img.shape[0], Li, self.out_channels, dtype=torch.bfloat16, device=img.device)
             net = self._attach_controlnet(cn, img.device)
             try:
-                _lib.call("fluxmi_engine_forward", self._engine, ops._p(img), ops._p(txt), ops._p(y), ops._p(timesteps), ops._p(guidance),
-                          ops._p(pred), mode, trial if mode == 0 else 0, ops._stream())
+                ip_set = self._set_ip_adapter(ip, img.device)
+                try:
+                    _lib.call("fluxmi_engine_forward", self._engine, ops._p(img), ops._p(txt), ops._p(y), ops._p(timesteps), ops._p(guidance),
+                              ops._p(pred), mode, trial if mode == 0 else 0, ops._stream())
+                finally:
+                    self._clear_ip_adapter(ip_set)
             finally:
                 self._release_controlnet(net)
             if mode == 0:
@@ -661,7 +710,8 @@ class Flux(nn.Module):
                 img_cond_seq_ids: Tensor | None = None, img_cond: Tensor | None = None, neg_txt: Tensor | None = None,
                 neg_y: Tensor | None = None, cfg_scale: float = 1.0, cache_threshold: float = 0.0, cache_max_hits: int = 0,
                 attn_groups: Tensor | None = None, inpaint_x0: Tensor | None = None, inpaint_noise: Tensor | None = None,
-                inpaint_mask: Tensor | None = None, inpaint_thresholds=None, controlnet=None, solver=None, solver_noise=None) -> Tensor:
+                inpaint_mask: Tensor | None = None, inpaint_thresholds=None, controlnet=None, solver=None, solver_noise=None,
+                ip_adapter=None) -> Tensor:
         """The Euler loop of FluxPipeline.generate (reference flux_pipeline.py:619-651) run natively: calibrating
         steps unfused, every later step one replay of a captured hipGraph.  Returns the final latent tokens.
         FLUX.1 Kontext: with `img_cond_seq` / `img_cond_seq_ids` the reference tokens join every step's forward and are never stepped; the
@@ -695,7 +745,11 @@ class Flux(nn.Module):
         `solver_noise` = (ids, eval_offset) goes with a program that draws noise (fluxmi.solvers.STOCHASTIC_SAMPLERS; a non-zero cn): ids
         [B, 4] uint32 words {key_lo, key_hi, c2, c3} per IMAGE (a tensor or a list; never per branch), eval_offset the index of this call's
         first evaluation within the request.  Evaluation j adds cn * z in the same kernel, z generated there (Philox4x32-10 + Box-Muller) as
-        a pure function of (ids[b], j + eval_offset, element): a sample's bits depend on its ids alone, not on its batch or pass."""
+        a pure function of (ids[b], j + eval_offset, element): a sample's bits depend on its ids alone, not on its batch or pass.
+        `ip_adapter`: a modules.ip_adapter.IPAdapterCall (Flux.forward): every step adds the adapter term behind every double block, in the
+        calibrating and the graph-replayed steps alike; K / V and the scales are device data of ONE captured graph.  Its tensors hold 1 or B
+        samples, a guided call's 2 or 2B: the prompt branches' tables, then the negative branches'.  Refused with attn_groups and
+        cache_threshold > 0."""
         n_user = len(timesteps) - 1
         if solver is not None:
             if cache_threshold and float(cache_threshold) > 0:
@@ -721,6 +775,12 @@ class Flux(nn.Module):
         kontext = img_cond_seq is not None or img_cond_seq_ids is not None
         guided = neg_txt is not None or neg_y is not None
         cn = self._check_controlnet(controlnet, img, img.shape[0], kontext, attn_groups, cache_threshold)
+        if ip_adapter is not None and guided and ip_adapter.k_ip.ndim == 4 and ip_adapter.k_ip.shape[1] == 2 and img.shape[0] > 1:
+            rep = lambda t: t.repeat_interleave(img.shape[0], 1)  # [pos, neg] -> B x pos, B x neg
+            sc = ip_adapter.scale
+            ip_adapter = type(ip_adapter)(rep(ip_adapter.k_ip), rep(ip_adapter.v_ip),
+                                          sc.repeat_interleave(img.shape[0], 0) if isinstance(sc, torch.Tensor) and sc.ndim == 2 else sc)
+        ip = self._check_ip_adapter(ip_adapter, img.shape[0] * (2 if guided else 1), attn_groups, cache_threshold)
         if guided:
             if neg_txt is None or neg_y is None:
                 raise ValueError("neg_txt and neg_y go together (the negative prompt's T5 sequence and pooled CLIP vector)")
@@ -762,6 +822,9 @@ class Flux(nn.Module):
                                 inpaint_thresholds=inpaint[3])
                 if cn is not None:
                     cond["controlnet"] = type(controlnet)(cn[0], pick(cn[1]), cn[3], cn[2])
+                if ip is not None:  # per sample along dim 1 (scales: dim 0); a guided call's halves are picked separately
+                    pick_b = lambda t, dim: torch.cat([pick(h.transpose(0, dim)).transpose(0, dim) for h in t.chunk(2 if guided else 1, dim)], dim)
+                    cond["ip_adapter"] = type(ip_adapter)(pick_b(ip[0], 1), pick_b(ip[1], 1), pick_b(ip[2], 0))
                 if solver is not None:
                     cond["solver"] = solver
                 if solver_noise is not None:  # picked like every per-sample tensor: a padded tail copies the last image's ids
@@ -795,7 +858,9 @@ class Flux(nn.Module):
             self._set_solver(solver)
             self._set_solver_noise(solver_noise)
             net = self._attach_controlnet(cn, img.device)
+            ip_set = False
             try:
+                ip_set = self._set_ip_adapter(ip, img.device)
                 if guided:
                     _lib.call("fluxmi_engine_denoise_cfg", self._engine, ops._p(img), ops._p(txt), ops._p(y), float(guidance), float(cfg_scale), ts,
                               len(timesteps) - 1, C.byref(t_io), int(use_graph), ops._stream())
@@ -803,6 +868,7 @@ class Flux(nn.Module):
                     _lib.call("fluxmi_engine_denoise", self._engine, ops._p(img), ops._p(txt), ops._p(y), float(guidance), ts,
                               len(timesteps) - 1, C.byref(t_io), int(use_graph), ops._stream())
             finally:
+                self._clear_ip_adapter(ip_set)
                 self._release_controlnet(net)
                 if solver is not None:
                     self._set_solver(None)

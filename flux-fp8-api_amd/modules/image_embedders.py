@@ -354,3 +354,188 @@ def read_siglip(path: str) -> SiglipVisionNative:
     if missing:
         raise RuntimeError(f"fluxmi: SigLIP checkpoint is missing weights: {missing[:4]} ...")
     return m
+
+
+# ---- CLIP vision tower (the IP-Adapter's image encoder; modules/ip_adapter.py) -----------------------------------------------------------
+# openai/clip-vit-large-patch14's vision_config; keys left out of a config mean CLIPVisionConfig's defaults, as transformers reads them
+CLIP_VIT_L14 = dict(hidden_size=1024, intermediate_size=4096, num_hidden_layers=24, num_attention_heads=16, num_channels=3, image_size=224,
+                    patch_size=14, hidden_act="quick_gelu", layer_norm_eps=1e-5, projection_dim=768)
+_CLIP_VISION_DEFAULTS = dict(hidden_size=768, intermediate_size=3072, num_hidden_layers=12, num_attention_heads=12, num_channels=3,
+                             image_size=224, patch_size=32, hidden_act="quick_gelu", layer_norm_eps=1e-5, projection_dim=512)
+
+
+class _ClipVisionTransformer(nn.Module):
+    def __init__(self, c):
+        super().__init__()
+        D, Fd, C, P = c["hidden_size"], c["intermediate_size"], c["num_channels"], c["patch_size"]
+        self.embeddings = nn.Module()
+        self.embeddings.class_embedding = nn.Parameter(torch.zeros(D))
+        self.embeddings.patch_embedding = nn.Conv2d(C, D, kernel_size=P, stride=P, bias=False)
+        self.embeddings.position_embedding = _Weight((c["image_size"] // P) ** 2 + 1, D)
+        self.pre_layrnorm = nn.LayerNorm(D, eps=c["layer_norm_eps"])  # (transformers' spelling: it is the state-dict key)
+        self.encoder = nn.Module()
+        self.encoder.layers = nn.ModuleList()
+        for _ in range(c["num_hidden_layers"]):
+            lay = nn.Module()
+            lay.self_attn = nn.Module()
+            for n in ("q_proj", "k_proj", "v_proj", "out_proj"):
+                setattr(lay.self_attn, n, _lin(D, D, True))
+            lay.layer_norm1, lay.layer_norm2 = nn.LayerNorm(D, eps=c["layer_norm_eps"]), nn.LayerNorm(D, eps=c["layer_norm_eps"])
+            lay.mlp = nn.Module()
+            lay.mlp.fc1, lay.mlp.fc2 = _lin(D, Fd, True), _lin(Fd, D, True)
+            self.encoder.layers.append(lay)
+        self.post_layernorm = nn.LayerNorm(D, eps=c["layer_norm_eps"])
+        self.requires_grad_(False)
+
+
+class ClipVisionNative(nn.Module):
+    """transformers' CLIPVisionModelWithProjection on libfluxmi, built from the kernels the SigLIP tower runs on (no kernel of its own):
+    class token + stride-P "valid" Conv2d without bias (fluxmi_patchify + GEMM) + position embedding; pre_layrnorm; pre-LN encoder layers
+    (LayerNorm eps 1e-5 with bias; q / k / v / out projections with bias, heads of 64, non-causal, scale 64^-1/2 through
+    fluxmi_vision_attention; fc1, quick_gelu = `ops.act_mul(x, gated=False)`, fc2; both residual adds in bf16); post_layernorm on the class
+    token; visual_projection without bias -> image_embeds.  State-dict keys: vision_model.embeddings.{class_embedding, patch_embedding,
+    position_embedding}, vision_model.pre_layrnorm, vision_model.encoder.layers.{i}.*, vision_model.post_layernorm, visual_projection.  A
+    full CLIPModel checkpoint loads too: text_model.*, text_projection and logit_scale are ignored.
+    A sequence of grid^2 + 1 tokens (257 for ViT-L/14) is padded to a multiple of 256 rows (512), fc1 / fc2 to a multiple of 256 and the
+    patch matrix's K to a multiple of 64, as for SigLIP (zeros: exact).
+    `config`: a CLIPVisionConfig dict or a CLIPModel config.json (its `vision_config` + `projection_dim`); None = openai/clip-vit-large-patch14."""
+
+    def __init__(self, config: Optional[dict] = None):
+        super().__init__()
+        c = dict(_CLIP_VISION_DEFAULTS)
+        if config is None:
+            c.update(CLIP_VIT_L14)
+        elif "vision_config" in config:
+            c.update(config.get("vision_config") or {})
+            if "projection_dim" in config:
+                c["projection_dim"] = config["projection_dim"]
+        else:
+            c.update(config)
+        if c["hidden_act"] != "quick_gelu":
+            raise ValueError(f"fluxmi: the native CLIP vision tower covers quick_gelu MLPs, got {c['hidden_act']!r}")
+        D, H = c["hidden_size"], c["num_attention_heads"]
+        if D % H or D % 8 or D // H > 64:
+            raise ValueError(f"fluxmi: CLIP vision hidden_size {D} must be a multiple of 8 and of the head count {H}, with heads of at most 64")
+        self.cfg = c
+        self.head_dim = D // H
+        self.head_pad = padded_head_dim(self.head_dim)
+        self.grid = c["image_size"] // c["patch_size"]
+        self.num_tokens = self.grid ** 2 + 1
+        self.vision_model = _ClipVisionTransformer(c)
+        self.visual_projection = _lin(D, c["projection_dim"], False)
+        self._cache = _Cache()
+
+    def load_state_dict(self, sd, strict=True, assign=False):
+        sd = {k: v for k, v in sd.items() if not k.startswith(("text_model.", "text_projection", "logit_scale")) and not k.endswith("position_ids")}
+        return super().load_state_dict(sd, strict=strict, assign=assign)
+
+    @property
+    def device(self):
+        return self.vision_model.post_layernorm.weight.device
+
+    @property
+    def seq_pad(self) -> int:
+        return _round_up(self.num_tokens, 256)
+
+    @property
+    def mlp_pad(self) -> int:
+        return _round_up(self.cfg["intermediate_size"], 256)
+
+    @property
+    def patch_k(self) -> int:
+        c = self.cfg
+        return _round_up(c["num_channels"] * c["patch_size"] ** 2, 64)
+
+    def padded_weights(self, i) -> dict:
+        """bf16 weights of layer i (or i = "embed") as the kernels take them, built once"""
+        vm, ck = self.vision_model, self._cache
+        H, hd, hp = self.cfg["num_attention_heads"], self.head_dim, self.head_pad
+        if i == "embed":
+            em = vm.embeddings
+            pe, pos = em.patch_embedding, em.position_embedding.weight
+            return dict(
+                w=ck.get("patch_w", [pe.weight], lambda: _pad_to(_bf(pe.weight).reshape(pe.weight.shape[0], -1), self.patch_k, 1).contiguous()),
+                pos=ck.get("pos", [pos], lambda: _bf(pos)),
+                # the class row: bf16(class_embedding + position_embedding[0]) on bf16 tensors, as transformers adds them
+                cls=ck.get("cls", [em.class_embedding, pos], lambda: (_bf(em.class_embedding) + _bf(pos)[0]).contiguous()))
+        lay = vm.encoder.layers[i]
+        sa, mlp = lay.self_attn, lay.mlp
+        ph = lambda t, dim=0: pad_heads(_bf(t), H, hd, hp, dim).contiguous()  # noqa: E731
+        p = dict(
+            wqk=ck.get(("wqk", i), [sa.q_proj.weight, sa.k_proj.weight], lambda: torch.cat([ph(sa.q_proj.weight), ph(sa.k_proj.weight)], 0)),
+            bqk=ck.get(("bqk", i), [sa.q_proj.bias, sa.k_proj.bias], lambda: torch.cat([ph(sa.q_proj.bias), ph(sa.k_proj.bias)], 0)),
+            wv=ck.get(("wv", i), [sa.v_proj.weight], lambda: ph(sa.v_proj.weight)),
+            bv=ck.get(("bv", i), [sa.v_proj.bias], lambda: ph(sa.v_proj.bias)),
+            wo=ck.get(("wo", i), [sa.out_proj.weight], lambda: ph(sa.out_proj.weight, 1)),
+            bo=ck.get(("bo", i), [sa.out_proj.bias], lambda: _bf(sa.out_proj.bias)),
+            w1=ck.get(("w1", i), [mlp.fc1.weight], lambda: _pad_to(_bf(mlp.fc1.weight), self.mlp_pad, 0).contiguous()),
+            b1=ck.get(("b1", i), [mlp.fc1.bias], lambda: _pad_to(_bf(mlp.fc1.bias), self.mlp_pad, 0).contiguous()),
+            w2=ck.get(("w2", i), [mlp.fc2.weight], lambda: _pad_to(_bf(mlp.fc2.weight), self.mlp_pad, 1).contiguous()),
+            b2=ck.get(("b2", i), [mlp.fc2.bias], lambda: _bf(mlp.fc2.bias)))
+        for name, t in (("g1", lay.layer_norm1.weight), ("e1", lay.layer_norm1.bias), ("g2", lay.layer_norm2.weight), ("e2", lay.layer_norm2.bias)):
+            p[name] = ck.get((name, i), [t], lambda t=t: _bf(t))
+        return p
+
+    @torch.inference_mode()
+    def forward(self, pixel_values: Tensor, **_) -> dict:
+        """pixel_values [B, C, image_size, image_size] -> {"image_embeds": bf16 [B, projection_dim], "last_hidden_state": bf16
+        [B, grid^2 + 1, hidden] (before post_layernorm, as transformers returns it)}"""
+        from fluxmi import _lib, ops
+
+        dev = self.device
+        if dev.type != "cuda":
+            raise RuntimeError("fluxmi: the CLIP vision encoder needs the GPU (libfluxmi has no CPU path)")
+        c, ck, vm = self.cfg, self._cache, self.vision_model
+        D, H, eps, P, S = c["hidden_size"], c["num_attention_heads"], c["layer_norm_eps"], c["patch_size"], c["image_size"]
+        pix = pixel_values.to(device=dev, dtype=torch.bfloat16)
+        if pix.dim() != 4 or pix.shape[1] != c["num_channels"] or tuple(pix.shape[-2:]) != (S, S):
+            raise ValueError(f"fluxmi: CLIP takes pixel_values [B, {c['num_channels']}, {S}, {S}], got {tuple(pix.shape)}")
+        B, L, Lp, hp, G = pix.shape[0], self.num_tokens, self.seq_pad, self.head_pad, self.grid ** 2
+        ones = ck.get("ones", [vm.post_layernorm.weight], lambda: torch.ones(D, dtype=torch.bfloat16, device=dev))
+        ln = lambda x, mod, tag: ops.row_norm(x, ck.get((tag, "g"), [mod.weight], lambda: _bf(mod.weight)),  # noqa: E731
+                                              ck.get((tag, "e"), [mod.bias], lambda: _bf(mod.bias)), eps=eps, rms=False)
+        # row 0 of each image's Lp-row slab: the class row; rows 1 .. G: bf16(pos + bf16(conv)); the rest zero (finite through every layer)
+        e = self.padded_weights("embed")
+        patches = ops.patchify(pix, P, self.grid, self.patch_k)
+        x = torch.zeros(B, Lp, D, dtype=torch.bfloat16, device=dev)
+        _linear_groups([patches[b * G:(b + 1) * G] for b in range(B)], e["w"], [x[b, 1:L] for b in range(B)], None,
+                       resid_rows=[e["pos"][1:]] * B, ones=ones)
+        x[:, 0] = e["cls"]
+        x = ln(x.view(B * Lp, D), vm.pre_layrnorm, "pre")
+        for i in range(len(vm.encoder.layers)):
+            p = self.padded_weights(i)
+            h = ops.row_norm(x, p["g1"], p["e1"], eps=eps, rms=False)
+            qk = ops.linear(h, p["wqk"], p["bqk"]).view(B, Lp, 2 * H * hp)
+            vt = torch.empty(B, H * hp, Lp, dtype=torch.bfloat16, device=dev)
+            for b in range(B):  # V^T = W_v . h_b^T per image (the SigLIP tower's scheme)
+                ops.linear(p["wv"], h[b * Lp:(b + 1) * Lp], out=vt[b])
+            o = ops.vision_attention(qk[:, :, : H * hp], qk[:, :, H * hp:], vt, L, H, hp, self.head_dim ** -0.5, v_bias=p["bv"])
+            x = ops.linear(o.view(B * Lp, H * hp), p["wo"], p["bo"], epilogue=_lib.EPI_GATE_RESID, gate=ones, resid=x, out=torch.empty_like(x))
+            h = ops.row_norm(x, p["g2"], p["e2"], eps=eps, rms=False)
+            f = ops.act_mul(ops.linear(h, p["w1"], p["b1"]), gated=False)
+            x = ops.linear(f, p["w2"], p["b2"], epilogue=_lib.EPI_GATE_RESID, gate=ones, resid=x, out=torch.empty_like(x))
+        x = x.view(B, Lp, D)
+        pooled = ln(x[:, 0].contiguous(), vm.post_layernorm, "post")
+        wp = ck.get("proj", [self.visual_projection.weight], lambda: _bf(self.visual_projection.weight))
+        return {"image_embeds": ops.linear(pooled, wp), "last_hidden_state": x[:, :L].contiguous()}
+
+
+def read_clip_vision(path: str) -> ClipVisionNative:
+    """a local HF directory (config.json + *.safetensors of CLIPVisionModelWithProjection or CLIPModel) or one .safetensors file (the
+    ViT-L/14 geometry) -> ClipVisionNative with its weights (host memory)"""
+    from safetensors.torch import load_file
+
+    if os.path.isdir(path):
+        cfg = None
+        cj = os.path.join(path, "config.json")
+        if os.path.exists(cj):
+            with open(cj) as f:
+                cfg = json.load(f)
+        sd = _read_dir_weights(path)
+    else:
+        cfg, sd = None, load_file(path, device="cpu")
+    m = ClipVisionNative(cfg)
+    missing, _ = m.load_state_dict(sd, strict=False)
+    if missing:
+        raise RuntimeError(f"fluxmi: CLIP vision checkpoint is missing weights: {missing[:4]} ...")
+    return m

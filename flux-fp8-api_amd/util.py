@@ -73,6 +73,10 @@ class ModelSpec(BaseModel):  # reference util.py:38-79 (unknown JSON keys are ig
     # FLUX ControlNet: a LOCAL diffusers-format FluxControlNetModel checkpoint (InstantX / Shakker-Labs Canny, Depth, Union ...), a
     # .safetensors file or a directory holding diffusion_pytorch_model.safetensors.  Nothing is downloaded.
     controlnet_path: str | None = None
+    # FLUX IP-Adapter: a LOCAL XLabs-format checkpoint (flux-ip-adapter / -v2 .safetensors) and the CLIP ViT-L/14 vision tower
+    # (CLIPVisionModelWithProjection: a local HF directory or .safetensors file).  Nothing is downloaded.
+    ip_adapter_path: str | None = None
+    clip_vision_path: str | None = None
 
     model_config: ConfigDict = {"arbitrary_types_allowed": True, "use_enum_values": True}
 
@@ -334,6 +338,22 @@ def load_controlnet(config: ModelSpec, device=None, state_dict=None):
                                                           quantize_modulation=config.quantize_modulation,
                                                           quantize_flow_embedder_layers=config.quantize_flow_embedder_layers)
     return net
+
+
+def load_ip_adapter(config: ModelSpec, device=None):
+    """The FLUX IP-Adapter of config.ip_adapter_path with its CLIP vision tower (modules/ip_adapter.IPAdapter) in bf16 on `device`, or None
+    unless config.ip_adapter_path is a local file and config.clip_vision_path a local directory or file.  Nothing is downloaded.  A
+    checkpoint that is not in the XLabs format is refused by name (modules.ip_adapter.check_state_dict)."""
+    import os
+
+    from modules.image_embedders import read_clip_vision
+    from modules.ip_adapter import read_ip_adapter
+
+    ip, clip = getattr(config, "ip_adapter_path", None), getattr(config, "clip_vision_path", None)
+    if not (isinstance(ip, str) and os.path.isfile(ip) and isinstance(clip, str) and os.path.exists(clip)):
+        return None
+    m = read_ip_adapter(ip, read_clip_vision(clip))
+    return m.to(device=into_device(device if device is not None else config.flux_device), dtype=torch.bfloat16)
 
 
 def load_models_from_config(config: ModelSpec, state_dict=None, ae_state_dict=None, clip_kwargs=None, t5_kwargs=None) -> LoadedModels:

@@ -682,6 +682,38 @@ int fluxmi_engine_attach_controlnet(fluxmi_engine_t* e, fluxmi_engine_t* cn, con
                                     void* stream);
 int fluxmi_controlnet_trial(fluxmi_engine_t* cn, int* trial_index);
 
+/* ---- IP-Adapter: decoupled image attention (XLabs IPDoubleStreamBlockProcessor, restated) -------------------------------
+ * For every sample b < B, image row r < rows and head h < heads (head_dim 128 only):
+ *   qn   = QKNorm of the raw query  qkv[b * qkv_bstride + r * ld_qkv + h * 128 + d]  with the learnable scale qn_scale (bf16 [128]): formed by
+ *          the helper fluxmi_attention_rawq uses (csrc/attention_common.h, qknorm_rinv / qknorm_apply: fp32 rms over the 128 columns, eps 1e-6,
+ *          bf16((x / rms) * w)), BEFORE RoPE -- attention and the adapter see the same query bits
+ *   t_j  = (qn . k_ip[b, j, h]) * (128^-1/2 * log2 e),  j < Nk      fp32 products and sums
+ *   p_j  = exp2(t_j - max_j t_j),  acc_d = sum_j p_j * v_ip[b, j, h, d],  o_d = bf16(acc_d * (1 / sum_j p_j))      all fp32, one rounding
+ * scale == NULL (out-of-place):  out[b * o_bstride + r * ld_o + h * 128 + d] = o_d
+ * scale != NULL (fused):         x = bf16(x + bf16(o_d * scale[b * scale_bstride]))  at the same address of `out` (the residual stream): bit
+ *                                for bit the out-of-place form followed by fluxmi_add_scaled.  scale is DEVICE fp32, one value per sample.
+ * k_ip, v_ip: bf16, row j of sample b at b * kv_bstride + j * heads * 128; rows at or beyond Nk are never read.  1 <= Nk <= 64.  Strides in
+ * elements, multiples of 8, every pointer 16-byte aligned.  A sample's result depends on its own rows only; nothing outside the addressed
+ * [rows, heads * 128] window of each sample is written.  VALU kernel, no MFMA: it is bound by the bytes of q and x. */
+int fluxmi_ip_attention(const void* qkv, long long ld_qkv, long long qkv_bstride, const void* qn_scale, const void* k_ip, const void* v_ip,
+                        long long kv_bstride, void* out, long long ld_o, long long o_bstride, const float* scale, long long scale_bstride, int B,
+                        int rows, int heads, int Nk, void* stream);
+/* The adapter of the following fluxmi_engine_forward / _denoise / _denoise_cfg calls on the PREPARED shape (call it after fluxmi_engine_prepare*):
+ *   k_ip, v_ip   device bf16 [depth][batch][Nk][hidden]: the step-invariant keys / values of every double block (computed once per request by
+ *                the caller).  Copied into an engine-owned buffer allocated here -- never inside a capture -- so a captured graph never holds
+ *                the caller's pointers; counted in fluxmi_engine_workspace_bytes; re-used while it is large enough
+ *   batch        must equal the prepared batch: both branches of a guided request carry their own K / V and scales
+ *   scales_host  [batch][depth] floats (ip_scale per sample and block), staged as device data: one captured graph serves every scale
+ * With an adapter set, every forward launches fluxmi_ip_attention (fused form) once behind each double block, on all L - Lt image-stream
+ * rows (Kontext reference rows included), reading the block's raw image q that still sits in the qkv workspace; with a ControlNet attached
+ * the order is block, adapter term, ControlNet residual.  Calibrating, unfused, frozen and graph-replayed steps alike.  Adapter on / off is a
+ * kind of step graph (Nk and the buffer are baked in: another Nk or a re-allocated buffer re-captures; other K / V contents or scales
+ * replay the same graph).  k_ip == NULL switches it off (the other arguments are ignored); so does a prepare that re-allocates the workspace.
+ * A request without an adapter allocates and launches exactly what it did before.  Refused: Nk outside 1..64, batch != the prepared one,
+ * a token-group attention table, step caching on (both also by the forward / denoise call if set afterwards), a ControlNet engine as the
+ * target; fluxmi_engine_run_phase is refused while an adapter is set. */
+int fluxmi_engine_set_ip_adapter(fluxmi_engine_t* e, const void* k_ip, const void* v_ip, int Nk, int batch, const float* scales_host, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,6 +19,9 @@ Same two POST endpoints, request fields, defaults and status codes:
              sigmas=None (the request's own descending list in (0, 1]; num_steps follows it) -- each passed on only when set;
              sampler also "euler_ancestral" | "dpmpp_2m_sde" (stochastic), with eta=None (0..1), s_noise=None (>= 0), noise_seed=None (the
              key of the in-kernel noise; default the request's seed) -- each passed on only when set;
+             guidance_mode=None ("cfg" | "apg" | "cfg_zero_star"), guidance_rescale=None (0..1), apg_eta=None, apg_norm_threshold=None (>= 0),
+             apg_momentum=None, zero_init_steps=None (>= 0) -- guidance shaping of true classifier-free guidance (FluxPipeline.generate; needs
+             negative_prompt and true_cfg_scale > 1), each passed on only when set;
              a region with both or neither of box / mask, or a box outside 0 <= x0 < x1 <= 1, is a 422}
              ->  image/jpeg stream of FluxPipeline.generate(**args)                                               (reference api.py:54-86)
   /lora      LoraArgs{scale=1.0, path, name, action="load"|"unload"}  ->  {"status": "success"} | 400 invalid action | 500 with the
@@ -95,6 +98,12 @@ class GenerateArgs(BaseModel):
     eta: Optional[float] = Field(default=None, ge=0.0, le=1.0)  # stochastic samplers: the share of each step's noise that is re-drawn
     s_noise: Optional[float] = Field(default=None, ge=0.0)  # ... a factor on the drawn noise
     noise_seed: Optional[int] = Field(default=None, ge=0, lt=2 ** 64)  # ... the key of the in-kernel noise (default: the request's seed)
+    guidance_mode: Optional[Literal["cfg", "apg", "cfg_zero_star"]] = None  # true CFG's combination rule (default cfg; FluxPipeline.generate)
+    guidance_rescale: Optional[float] = Field(default=None, ge=0.0, le=1.0)  # ... CFG rescale (diffusers' name): 0 = off
+    apg_eta: Optional[float] = None  # ... APG: the weight of the part of the guidance parallel to the prompt prediction (default 1)
+    apg_norm_threshold: Optional[float] = Field(default=None, ge=0.0)  # ... APG: clip the guidance difference to this norm (0 = off)
+    apg_momentum: Optional[float] = None  # ... APG: the running difference's momentum (0 = off)
+    zero_init_steps: Optional[int] = Field(default=None, ge=0)  # ... CFG-Zero*'s zero-init: the first k model evaluations predict 0
 
 
 app = FastAPI(title="fluxmi")
@@ -107,13 +116,15 @@ def generate(args: GenerateArgs):
     FLUX.1 Depth / Canny generation, `redux_image` a FLUX.1 Redux image prompt; `negative_prompt` + `true_cfg_scale` (+ `true_cfg_interval`)
     select true classifier-free guidance, `cache_threshold` (+ `cache_max_hits`) first-block step caching, `controlnet_image` (+ `controlnet_conditioning_scale`,
     `control_mode`, `control_guidance_start` / `_end`) a FLUX ControlNet, `ip_adapter_image` / `ip_adapter_image_embeds` (+ `ip_adapter_scale`,
-    `negative_ip_adapter_image`, `negative_ip_adapter_scale`) a FLUX IP-Adapter.  Without them the call is exactly the reference's."""
+    `negative_ip_adapter_image`, `negative_ip_adapter_scale`) a FLUX IP-Adapter, `guidance_mode` / `guidance_rescale` / `apg_*` /
+    `zero_init_steps` guidance shaping of a guided request.  Without them the call is exactly the reference's."""
     kwargs = args.model_dump()
     for k in ("reference_image", "mask_image", "control_image", "redux_image", "negative_prompt", "true_cfg_scale", "true_cfg_interval",
               "cache_threshold", "cache_max_hits", "regions", "regional_tokens", "inpaint_mask", "inpaint_differential", "controlnet_image",
               "controlnet_conditioning_scale", "control_mode", "control_guidance_start", "control_guidance_end", "sampler", "sigma_schedule",
               "sigmas", "eta", "s_noise", "noise_seed", "ip_adapter_image", "ip_adapter_image_embeds", "ip_adapter_scale",
-              "negative_ip_adapter_image", "negative_ip_adapter_scale"):
+              "negative_ip_adapter_image", "negative_ip_adapter_scale", "guidance_mode", "guidance_rescale", "apg_eta", "apg_norm_threshold",
+              "apg_momentum", "zero_init_steps"):
         if kwargs.get(k) is None:
             kwargs.pop(k, None)
     if "ip_adapter_image_embeds" in kwargs:

@@ -270,6 +270,13 @@ int fluxmi_fb_apply(void* x, long long x_bstride, const void* h1, long long h1_b
 int fluxmi_add_scaled(void* x, long long x_bstride, const void* r, long long r_bstride, const float* scale, int B, long long n, void* stream) {
   return fluxmi_k_add_scaled(x, x_bstride, r, r_bstride, scale, B, n, (hipStream_t)stream);
 }
+int fluxmi_guidance_moments(const void* pred, const float* r, float* part, int B, long long N, void* stream) {
+  return fluxmi_k_guidance_moments(pred, r, part, B, N, (hipStream_t)stream);
+}
+int fluxmi_guidance_combine(void* pred, float* r, const float* part, const float* params, const int* step, const int* step_offset,
+                            float* coef_out, int B, long long N, void* stream) {
+  return fluxmi_k_guidance_combine(pred, r, part, params, step, step_offset, coef_out, B, N, (hipStream_t)stream);
+}
 int fluxmi_ip_attention(const void* qkv, long long ld_qkv, long long qkv_bstride, const void* qn_scale, const void* k_ip, const void* v_ip,
                         long long kv_bstride, void* out, long long ld_o, long long o_bstride, const float* scale, long long scale_bstride, int B,
                         int rows, int heads, int Nk, void* stream) {

@@ -55,6 +55,7 @@ struct StepGraphs {
   bool diff = false;    // ... and its differential form (the threshold table is a launch argument)
   bool solver = false;  // ... and the table-driven solver update (fluxmi_engine_set_solver): WHICH solver is device data, not a kind
   bool noise = false;   // ... and its form with the noise term (fluxmi_engine_set_solver_noise): seeds and the offset are device data
+  bool shaped = false;  // guidance shaping (fluxmi_engine_set_guidance): two launches in front of the guided update; mode and values are device data
   unsigned gen = 0;     // fluxmi_tuning_generation() the pieces were captured under
   const void* cn = nullptr;  // the attached ControlNet whose launches (and workspace pointers) are baked into the pieces, or none ...
   unsigned long long cn_gen = 0;  // ... and the generation of its workspace / weight binding: process-wide unique, so a net created at a freed net's address never matches
@@ -170,6 +171,16 @@ struct fluxmi_engine {
   std::vector<unsigned> sol_ids;
   unsigned* d_sol_ids = nullptr;
   size_t sol_ids_bytes = 0;
+  // guidance shaping (fluxmi_engine_set_guidance): the host parameters and step offset of the following guided denoise
+  // calls; their device copy "gd_params" (float [8] | the offset, staged through h_sched like the schedule), the moments' partials "gd_part",
+  // the last step's coefficients "gd_coef" and APG's running difference "gd_r" (fp32 [B / 2][Lpred * C_out]) are one allocation made at the
+  // first shaped call of a prepared shape and dropped with the workspace.  Nothing of it without shaping.
+  bool gd_on = false;
+  bool gd_zero_r = false;          // a set call came in: the next guided denoise call zeroes "gd_r" on its stream
+  float gd_params[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  int gd_offset = 0;
+  char* gd_mem = nullptr;
+  size_t gd_bytes = 0;
   // ControlNet (fluxmi_controlnet_create / fluxmi_engine_attach_controlnet).  A net is an engine of its own kind
   // (is_cn): no final layer, the controlnet_* projections behind the trunk's linears, the residuals of a forward in its workspace buffer
   // "cn_res" [Nd + Ns][B, Li, H].  The main engine holds the attached net (cn) and the conditioning scale (d_cn_scale, device data).
@@ -1152,6 +1163,8 @@ void free_ws(E* e) {
   if (e->d_sol_coef) { hipFree(e->d_sol_coef); e->d_sol_coef = nullptr; e->d_sol_ctl = nullptr; }
   if (e->d_sol_ids) { hipFree(e->d_sol_ids); e->d_sol_ids = nullptr; e->sol_ids_bytes = 0; }
   e->sol_on = e->sol_noise = false;
+  if (e->gd_mem) { hipFree(e->gd_mem); e->gd_mem = nullptr; e->gd_bytes = 0; }
+  e->gd_on = e->gd_zero_r = false;
   if (e->ip_mem) { hipFree(e->ip_mem); e->ip_mem = nullptr; e->ip_bytes = 0; }
   e->ip_on = false;
   if (e->ws) { hipFree(e->ws); e->ws = nullptr; }
@@ -1246,6 +1259,31 @@ int ensure_sol_ids(E* e) {
   }
   e->sol_ids_bytes = bytes;
   e->bufs["sol_ids"] = Buf{(char*)e->d_sol_ids, bytes};
+  return 0;
+}
+
+// the guidance-shaping buffers of the prepared shape, made once a shaped guided request arrives (like ensure_fb); Bh = the caller's images
+constexpr long long GD_CHUNK_ELEMS = 16384;  // elements per workgroup of the moments pass (guidance.hip, GD_CHUNK vectors)
+int ensure_gd(E* e, hipStream_t s) {
+  if (e->gd_mem) return 0;
+  const size_t Bh = (size_t)e->B / 2, n = (size_t)e->Lpred * c_out(e), chunks = (n + GD_CHUNK_ELEMS - 1) / GD_CHUNK_ELEMS;
+  struct Item { const char* name; size_t bytes; };
+  const Item items[] = {{"gd_params", 9 * 4}, {"gd_part", Bh * chunks * 9 * 4}, {"gd_coef", Bh * 4 * 4}, {"gd_r", Bh * n * 4}};
+  size_t total = 0;
+  for (auto& it : items) total += (it.bytes + 255) & ~(size_t)255;
+  if (hipMalloc((void**)&e->gd_mem, total) != hipSuccess) {
+    (void)hipGetLastError();
+    e->gd_mem = nullptr;
+    fluxmi_set_error("engine_denoise: hipMalloc(%zu bytes) failed (guidance shaping)", total);
+    return 2;
+  }
+  e->gd_bytes = total;
+  FLUXMI_CHECK_HIP(hipMemsetAsync(e->gd_mem, 0, total, s));
+  size_t off = 0;
+  for (auto& it : items) {
+    e->bufs[it.name] = Buf{e->gd_mem + off, it.bytes};
+    off += (it.bytes + 255) & ~(size_t)255;
+  }
   return 0;
 }
 
@@ -1367,7 +1405,7 @@ static int create_impl(const fluxmi_model_desc_t* desc, const fluxmi_linear_t* l
   e->d_tnext = (float*)(e->consts + o_tnext); e->d_omt = (float*)(e->consts + o_omt); e->d_thr = (float*)(e->consts + o_thr);
   hipMemset(e->consts, 0, off);
   // pinned staging for the schedule (ts | dts | tnext | 1 - tnext | thresholds | solver coef | solver ctl | noise ids | eval offset) + the events (guard of the staging buffer, timing of the frozen steps)
-  if (hipHostMalloc((void**)&e->h_sched, (5 * (MAX_STEPS + 1) + 12 * MAX_STEPS + 4 * FLUXMI_ENGINE_MAX_BATCH + 1) * sizeof(float), hipHostMallocDefault) != hipSuccess ||
+  if (hipHostMalloc((void**)&e->h_sched, (5 * (MAX_STEPS + 1) + 12 * MAX_STEPS + 4 * FLUXMI_ENGINE_MAX_BATCH + 1 + 9) * sizeof(float), hipHostMallocDefault) != hipSuccess ||
       hipEventCreateWithFlags(&e->ev_sched, hipEventDisableTiming) != hipSuccess || hipEventCreate(&e->ev_t0) != hipSuccess ||
       hipEventCreate(&e->ev_t1) != hipSuccess) {
     fluxmi_engine_destroy(e);
@@ -1602,7 +1640,9 @@ static void graphs_stale(fluxmi_engine_t* e, StepGraphs& g, bool cfg) {
   if (g.ok && g.gen != fluxmi_tuning_generation()) g.ok = g.warmed = e->qlut_valid = false;
   const bool diff = e->inp_on && e->inp_diff;
   // masked versus dense attention is a kind like guided versus plain, and so are the blend update and its differential form
-  if (g.cfg != cfg || g.masked != e->masked || g.blend != e->inp_on || g.diff != diff || g.solver != e->sol_on || g.noise != e->sol_noise)
+  const bool shaped = cfg && e->gd_on;  // ... and guidance shaping; an unguided request does not consult the state
+  if (g.cfg != cfg || g.masked != e->masked || g.blend != e->inp_on || g.diff != diff || g.solver != e->sol_on || g.noise != e->sol_noise ||
+      g.shaped != shaped)
     g.ok = g.warmed = false;
   // ... and so is the attached ControlNet: its launches, weights and workspace pointers are baked into the pieces
   if (g.cn != e->cn || (e->cn && g.cn_gen != e->cn->ws_gen)) g.ok = g.warmed = false;
@@ -1620,6 +1660,7 @@ static void graphs_stale(fluxmi_engine_t* e, StepGraphs& g, bool cfg) {
   g.diff = diff;
   g.solver = e->sol_on;
   g.noise = e->sol_noise;
+  g.shaped = shaped;
 }
 
 // Captures pieces[0 .. n) into g.exec[0 .. n) on a private non-blocking stream (the caller has synchronised its own).  The only place that
@@ -1836,7 +1877,18 @@ static int denoise_impl(fluxmi_engine_t* e, void* img, const void* txt, const vo
                  cfg ? B / 2 : B);
   if (e->sol_on) FLUXMI_TRY(ensure_sol(e, s));
   if (sol_noise) FLUXMI_TRY(ensure_sol_ids(e));
+  // Guidance shaping (fluxmi_engine_set_guidance): moments and combine on pred_s in front of whichever guided update runs; both halves of
+  // pred_s then hold the shaped prediction v, and the update's own chain d = bf16(v - v) = 0, m = 0, p = v steps with v unchanged.
+  const bool shaped = cfg && e->gd_on;
+  if (shaped) FLUXMI_TRY(ensure_gd(e, s));
   auto euler = [&](hipStream_t st) -> int {
+    if (shaped) {
+      const long long n_pred = (long long)e->Lpred * c_out(e);
+      float* gp = buf<float>(e, "gd_params");
+      FLUXMI_TRY(fluxmi_k_guidance_moments(buf<u16>(e, "pred_s"), buf<float>(e, "gd_r"), buf<float>(e, "gd_part"), B / 2, n_pred, st));
+      FLUXMI_TRY(fluxmi_k_guidance_combine(buf<u16>(e, "pred_s"), buf<float>(e, "gd_r"), buf<float>(e, "gd_part"), gp, e->d_step,
+                                           (const int*)(gp + 8), buf<float>(e, "gd_coef"), B / 2, n_pred, st));
+    }
     if (sol_noise)
       return fluxmi_k_solver_step_noise(buf<u16>(e, "img_s"), buf<u16>(e, "pred_s"), buf<u16>(e, "sol_xs"), buf<float>(e, "sol_hist"),
                                         e->d_sol_coef, e->d_sol_ctl, e->inp_on ? buf<u16>(e, "inp_x0") : nullptr,
@@ -1919,6 +1971,14 @@ static int denoise_impl(fluxmi_engine_t* e, void* img, const void* txt, const vo
     memcpy(h_id, e->sol_ids.data(), (size_t)e->sol_noise_B * 16);
     h_id[4 * (size_t)B] = (unsigned)e->sol_eval_offset;
     FLUXMI_CHECK_HIP(hipMemcpyAsync(e->d_sol_ids, h_id, (size_t)B * 16 + 4, hipMemcpyHostToDevice, s));
+  }
+  if (shaped) {  // ... and the shaping parameters with the step offset behind them; a new request's running difference starts at 0
+    float* h_gd = e->h_sched + 5 * (MAX_STEPS + 1) + 12 * MAX_STEPS + 4 * FLUXMI_ENGINE_MAX_BATCH + 1;
+    memcpy(h_gd, e->gd_params, 32);
+    memcpy(h_gd + 8, &e->gd_offset, 4);
+    FLUXMI_CHECK_HIP(hipMemcpyAsync(buf<float>(e, "gd_params"), h_gd, 36, hipMemcpyHostToDevice, s));
+    if (e->gd_zero_r) FLUXMI_CHECK_HIP(hipMemsetAsync(buf<float>(e, "gd_r"), 0, (size_t)(B / 2) * e->Lpred * c_out(e) * 4, s));
+    e->gd_zero_r = false;
   }
   FLUXMI_CHECK_HIP(hipEventRecord(e->ev_sched, s));
   e->sched_pending = true;
@@ -2106,6 +2166,28 @@ int fluxmi_engine_set_solver_noise(fluxmi_engine_t* e, const unsigned* ids_host,
   e->sol_noise_B = batch;
   e->sol_eval_offset = eval_offset;
   e->sol_noise = true;
+  return 0;
+}
+
+// The guidance-shaping state of the following guided denoise calls (fluxmi.h): host data only, like the solver program.
+int fluxmi_engine_set_guidance(fluxmi_engine_t* e, const float* params_host, int step_offset) {
+  FLUXMI_REQUIRE(e, "engine_set_guidance: NULL engine");
+  if (!params_host) {
+    e->gd_on = e->gd_zero_r = false;
+    return 0;
+  }
+  FLUXMI_REQUIRE(!e->is_cn, "engine_set_guidance: a ControlNet engine steps nothing (set the shaping on the main engine)");
+  FLUXMI_REQUIRE(e->ws, "engine_set_guidance: call fluxmi_engine_prepare first (the state belongs to the prepared shape)");
+  for (int i = 0; i < 8; ++i) FLUXMI_REQUIRE(std::isfinite(params_host[i]), "engine_set_guidance: parameter %d is not finite", i);
+  const float phi = params_host[1], rho = params_host[3], mode = params_host[5], zi = params_host[6];
+  FLUXMI_REQUIRE(mode == 0.f || mode == 1.f || mode == 2.f, "engine_set_guidance: mode %g (0 = CFG, 1 = APG, 2 = CFG-Zero*)", (double)mode);
+  FLUXMI_REQUIRE(phi >= 0.f && phi <= 1.f, "engine_set_guidance: phi %g outside [0, 1] (the rescale blend)", (double)phi);
+  FLUXMI_REQUIRE(rho >= 0.f && zi >= 0.f, "engine_set_guidance: rho %g, zero_init %g must be >= 0 (0 = off)", (double)rho, (double)zi);
+  FLUXMI_REQUIRE(step_offset >= 0, "engine_set_guidance: step_offset %d < 0", step_offset);
+  memcpy(e->gd_params, params_host, 32);
+  e->gd_params[7] = 0.f;
+  e->gd_offset = step_offset;
+  e->gd_on = e->gd_zero_r = true;
   return 0;
 }
 
@@ -2342,7 +2424,7 @@ int fluxmi_engine_copy_buffer(fluxmi_engine_t* e, const char* name, long long of
 
 int fluxmi_engine_workspace_bytes(fluxmi_engine_t* e, long long* bytes) {
   FLUXMI_REQUIRE(e && bytes, "engine_workspace_bytes: NULL argument");
-  *bytes = (long long)(e->ws_bytes + e->pairs_bytes + e->mods_all_bytes + e->fb_bytes + e->inp_bytes + e->sol_bytes + e->sol_ids_bytes + e->ip_bytes);  // workspace + row-pair weight copies + modulation table + step cache + inpainting + solver buffers + noise ids
+  *bytes = (long long)(e->ws_bytes + e->pairs_bytes + e->mods_all_bytes + e->fb_bytes + e->inp_bytes + e->sol_bytes + e->sol_ids_bytes + e->ip_bytes + e->gd_bytes);  // workspace + row-pair weight copies + modulation table + step cache + inpainting + solver buffers + noise ids + adapter + guidance shaping
   return 0;
 }
 

@@ -188,6 +188,11 @@ int fluxmi_k_fb_metric(const void* x, long long x_bstride, const void* h0, void*
                        float* numden, int B, long long n, hipStream_t s);
 int fluxmi_k_fb_store(const void* x, long long x_bstride, const void* h1, void* R, int B, long long n, hipStream_t s);
 int fluxmi_k_fb_apply(void* x, long long x_bstride, const void* h1, long long h1_bstride, const void* R, int B, long long n, hipStream_t s);
+// guidance shaping of true CFG (guidance.hip; include/fluxmi.h, fluxmi_guidance_moments / _combine): nine per-image sums over (c, u, r) as
+// per-workgroup partials, then p = alpha c + beta u + gamma r with fp64-derived per-image coefficients written to both halves of pred
+int fluxmi_k_guidance_moments(const void* pred, const float* r, float* part, int B, long long N, hipStream_t s);
+int fluxmi_k_guidance_combine(void* pred, float* r, const float* part, const float* params, const int* step, const int* step_offset,
+                              float* coef_out, int B, long long N, hipStream_t s);
 // ControlNet residual hand-over: x[b, j] = bf16(x[b, j] + bf16(r[b, j] * *s_dev)), B samples of n elements, batch strides in elements
 int fluxmi_k_add_scaled(void* x, long long x_bstride, const void* r, long long r_bstride, const float* s_dev, int B, long long n, hipStream_t s);
 // IP-Adapter term of a double block (ip_attention.hip; include/fluxmi.h, fluxmi_ip_attention): scale == NULL writes o, else x += bf16(o * scale[b])

@@ -33,6 +33,7 @@ from util import (ModelSpec, ModelVersion, engine_flow_dtype, into_device, into_
                   load_models_from_config)
 
 MAX_RAND = 2**32 - 1
+GUIDANCE_MODES = ("cfg", "apg", "cfg_zero_star")  # generate(guidance_mode=...): the rule that combines the two branches of true CFG
 
 # FLUX.1 Kontext's preferred reference resolutions, (width, height) (BFL flux, src/flux/sampling.py)
 KONTEXT_PREFERRED_RESOLUTIONS = [
@@ -695,7 +696,8 @@ class FluxPipeline:
                  control_guidance_end: float = 1.0, controlnet_cond: Optional[torch.Tensor] = None, sampler: str = "euler",
                  sigma_schedule: Optional[str] = None, sigmas=None, eta: float = 1.0, s_noise: float = 1.0, noise_seed: Optional[int] = None,
                  ip_adapter_image=None, ip_adapter_image_embeds: Optional[torch.Tensor] = None, ip_adapter_scale=1.0,
-                 negative_ip_adapter_image=None, negative_ip_adapter_scale=1.0):
+                 negative_ip_adapter_image=None, negative_ip_adapter_scale=1.0, guidance_mode: str = "cfg", guidance_rescale: float = 0.0,
+                 apg_eta: float = 1.0, apg_norm_threshold: float = 0.0, apg_momentum: float = 0.0, zero_init_steps: int = 0):
         """`reference_image` (FLUX.1 Kontext [dev] instruction editing): an image the prompt describes an edit of, in any form `init_image`
         takes; see prepare_kontext_reference.  Composes with `init_image` / `strength` unchanged.
         FLUX.1 Fill [dev] (a model with 320 conditioning channels): `init_image` is the image to inpaint and `mask_image` (white =
@@ -774,7 +776,46 @@ class FluxPipeline:
         taken as embeds) at `negative_ip_adapter_scale`.  Composes with img2img, num_images, LoRA, Redux, a Kontext reference, Fill /
         Depth / Canny, a negative prompt, `inpaint_mask`, every sampler and a ControlNet; refused with `regions`, `cache_threshold` > 0 and
         under a process group.  Parity with XLabs' code is unpinned and image quality on real weights is not established here (README).
-        Without it the request is today's, launch for launch."""
+        Without it the request is today's, launch for launch.
+        Guidance shaping of true CFG (a guided request only; Flux.denoise `guidance_shaping`, csrc/guidance.hip): `guidance_mode` "cfg" (the
+        default), "apg" (adaptive projected guidance, Sadat et al. 2024: the guidance difference is split along the prompt prediction,
+        `apg_eta` scales the parallel part, `apg_norm_threshold` > 0 clips the difference's norm, `apg_momentum` (usually negative) keeps a
+        running difference) or "cfg_zero_star" (Fan et al. 2025: the negative branch is rescaled by the optimised s* = <c, u> / <u, u>);
+        `guidance_rescale` in [0, 1] (Lin et al. 2023 section 3.4; diffusers' name) pulls the guided prediction's standard deviation back
+        to the prompt branch's; `zero_init_steps` replaces the prediction of the request's first k model EVALUATIONS by zero (CFG-Zero*'s
+        zero-init; Heun and midpoint evaluate twice per step, and an evaluation outside `true_cfg_interval` counts but is never zeroed).
+        Shaping runs iff the request is guided and (guidance_mode != "cfg" or guidance_rescale > 0 or zero_init_steps > 0): two more
+        launches per evaluation, statistics per image; otherwise the request is today's, launch for launch.  Any non-default value
+        without guidance (no negative prompt, or true_cfg_scale <= 1) is refused.  APG's running difference starts at 0 in front of every
+        guided denoise call (one per request unless a ControlNet interval cuts the guided slice) and advances once per evaluation.
+        Composes with everything a negative prompt composes with, step caching included.  Parity with diffusers' code is unpinned (the
+        formulas of include/fluxmi.h are the definition) and image quality on real FLUX weights is NOT established here."""
+        if guidance_mode not in GUIDANCE_MODES:
+            raise ValueError(f"fluxmi: guidance_mode={guidance_mode!r}: expected one of {GUIDANCE_MODES}")
+        try:
+            guidance_rescale, apg_eta, apg_norm_threshold, apg_momentum = (float(v) for v in (guidance_rescale, apg_eta, apg_norm_threshold, apg_momentum))
+            if isinstance(zero_init_steps, bool) or int(zero_init_steps) != zero_init_steps:
+                raise ValueError
+            zero_init_steps = int(zero_init_steps)
+        except (TypeError, ValueError):
+            raise ValueError("fluxmi: guidance_rescale / apg_eta / apg_norm_threshold / apg_momentum take floats, zero_init_steps an integer") from None
+        if not all(math.isfinite(v) for v in (guidance_rescale, apg_eta, apg_norm_threshold, apg_momentum)):
+            raise ValueError("fluxmi: guidance_rescale / apg_eta / apg_norm_threshold / apg_momentum must be finite")
+        if not 0.0 <= guidance_rescale <= 1.0:
+            raise ValueError(f"fluxmi: guidance_rescale={guidance_rescale}: expected a value in [0, 1]")
+        if apg_norm_threshold < 0 or zero_init_steps < 0:
+            raise ValueError(f"fluxmi: apg_norm_threshold={apg_norm_threshold} and zero_init_steps={zero_init_steps} must be >= 0")
+        shaping_asked = (guidance_mode != "cfg" or guidance_rescale > 0 or zero_init_steps > 0 or apg_eta != 1.0 or apg_norm_threshold != 0.0
+                         or apg_momentum != 0.0)
+        if shaping_asked and not (negative_prompt is not None and true_cfg_scale > 1):
+            raise ValueError("fluxmi: guidance_mode / guidance_rescale / apg_* / zero_init_steps shape true classifier-free guidance: they need a "
+                             "negative_prompt and true_cfg_scale > 1")
+        if guidance_mode != "apg" and (apg_eta != 1.0 or apg_norm_threshold != 0.0 or apg_momentum != 0.0):
+            raise ValueError(f"fluxmi: apg_eta / apg_norm_threshold / apg_momentum belong to guidance_mode=\"apg\", not {guidance_mode!r}")
+        shaping = None
+        if guidance_mode != "cfg" or guidance_rescale > 0 or zero_init_steps > 0:
+            shaping = dict(mode=guidance_mode, rescale=guidance_rescale, eta=apg_eta, norm_threshold=apg_norm_threshold, momentum=apg_momentum,
+                           zero_init_steps=zero_init_steps)
         stochastic = sampler in solvers.STOCHASTIC_SAMPLERS
         if sampler not in solvers.SAMPLERS and not stochastic:
             raise ValueError(f"fluxmi: sampler={sampler!r}: expected one of {solvers.SAMPLERS + solvers.STOCHASTIC_SAMPLERS}")
@@ -1067,8 +1108,11 @@ class FluxPipeline:
                         cut.append((i, j, dict(kw, controlnet=call) if keep[i] else kw))
                         i = j
                 segs = cut
+            evals_done = 0  # model evaluations of the request in front of the segment (zero_init_steps counts them)
             for a, b, kw in segs:
                 if a < b or n == 0:
+                    if shaping is not None and "neg_txt" in kw:
+                        kw = dict(kw, guidance_shaping=dict(shaping, step_offset=evals_done))
                     if inpaint is not None:
                         x0_, noise_, mask_ = inpaint.chunk(3, -1)
                         kw = dict(kw, inpaint_x0=x0_, inpaint_noise=noise_, inpaint_mask=mask_)
@@ -1082,6 +1126,7 @@ class FluxPipeline:
                         kw = dict(kw, solver=solvers.build_program(sampler, timesteps[a:b + 1]))
                     latents = self.model.denoise(latents, img_ids, txt, txt_ids, vec, timesteps[a:b + 1], guidance=guidance, use_graph=use_graph,
                                                  **cond, **kw, **cache)
+                    evals_done += len(kw["solver"].coef) if "solver" in kw else b - a
         if world > 1:
             latents = fdist.gather_latents(latents, num_images, dst=0)
             if latents is None:  # only the gather rank decodes / returns the images

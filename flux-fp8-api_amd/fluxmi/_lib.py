@@ -114,6 +114,8 @@ _SIGS = {
     "fluxmi_fb_store": ([vp, i64, vp, vp, i32, i64, vp], i32),
     "fluxmi_fb_apply": ([vp, i64, vp, i64, vp, i32, i64, vp], i32),
     "fluxmi_add_scaled": ([vp, i64, vp, i64, vp, i32, i64, vp], i32),
+    "fluxmi_guidance_moments": ([vp, vp, vp, i32, i64, vp], i32),
+    "fluxmi_guidance_combine": ([vp, vp, vp, vp, vp, vp, vp, i32, i64, vp], i32),
     "fluxmi_engine_num_linears": ([C.POINTER(ModelDesc)], i32),
     "fluxmi_engine_create": ([C.POINTER(ModelDesc), C.POINTER(Linear), i32, C.POINTER(vp), i32, C.POINTER(vp)], i32),
     "fluxmi_engine_destroy": ([vp], i32),
@@ -135,6 +137,7 @@ _SIGS = {
     "fluxmi_engine_set_inpaint": ([vp, vp, vp, vp, i32, C.POINTER(C.c_double), i32, vp], i32),
     "fluxmi_engine_set_solver": ([vp, C.POINTER(C.c_double), C.POINTER(i32), i32], i32),
     "fluxmi_engine_set_solver_noise": ([vp, C.POINTER(C.c_uint32), i32, i32], i32),
+    "fluxmi_engine_set_guidance": ([vp, C.POINTER(f32), i32], i32),
     "fluxmi_engine_step_cache_log": ([vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(f32), C.POINTER(C.c_ubyte), i32], i32),
     "fluxmi_engine_run_phase": ([vp, i32, i32, i32, i32, vp], i32),
     "fluxmi_controlnet_num_linears": ([C.POINTER(ModelDesc)], i32),

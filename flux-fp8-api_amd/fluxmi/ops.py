@@ -581,3 +581,82 @@ def ip_attention(qkv: torch.Tensor, qn_scale: torch.Tensor, k_ip: torch.Tensor, 
     _lib.call("fluxmi_ip_attention", _p(qkv), qkv.stride(1), qkv.stride(0), _p(qn_scale), _p(k_ip), _p(v_ip), k_ip.stride(0), _p(out), out.stride(1),
               out.stride(0), _p(s), ss, B, rows, heads, nk, _stream())
     return out
+
+
+# ---- guidance shaping of true CFG (fluxmi_guidance_moments / _combine; include/fluxmi.h) ---------------------------------------------------
+GUIDANCE_MODES = {"cfg": 0, "apg": 1, "cfg_zero_star": 2}
+GUIDANCE_CHUNK = 16384  # elements per workgroup of the moments pass
+
+
+def guidance_params(s: float, mode="cfg", phi: float = 0.0, eta: float = 1.0, rho: float = 0.0, mu: float = 0.0, zero_init: int = 0):
+    """The 8 floats {s, phi, eta, rho, mu, mode, zero_init, 0} the combine stage reads (a plain list; mode by name or number)."""
+    m = GUIDANCE_MODES[mode] if isinstance(mode, str) else int(mode)
+    return [float(s), float(phi), float(eta), float(rho), float(mu), float(m), float(zero_init), 0.0]
+
+
+def _guidance_shape(pred: torch.Tensor, r: Optional[torch.Tensor]):
+    _req(pred, torch.bfloat16, "pred")
+    if pred.ndim < 2 or pred.shape[0] % 2 or not pred.is_contiguous():
+        raise ValueError(f"guidance: pred {tuple(pred.shape)} must be contiguous [2B, ...]: prompt branches first, then the negative branches")
+    B = pred.shape[0] // 2
+    N = pred[0].numel()
+    if r is not None:
+        _req(r, torch.float32, "r")
+        if r.numel() != B * N or not r.is_contiguous():
+            raise ValueError(f"guidance: r {tuple(r.shape)} must be contiguous fp32 [{B}, {N}]")
+    return B, N
+
+
+def guidance_moments(pred: torch.Tensor, r: Optional[torch.Tensor] = None, part: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """part[b][g] = the nine fp32 sums (Sc, Su, Sr, cc, uu, rr, cu, cr, ur) over elements [16384 g, 16384 (g + 1)) of image b; pred bf16
+    [2B, ...] (c = pred[b], u = pred[B + b]), r fp32 [B, N] or None (its sums are 0)."""
+    B, N = _guidance_shape(pred, r)
+    G = -(-N // GUIDANCE_CHUNK)
+    if part is None:
+        part = torch.empty((B, G, 9), dtype=torch.float32, device=pred.device)
+    _req(part, torch.float32, "part")
+    if part.numel() != B * G * 9 or not part.is_contiguous():
+        raise ValueError(f"guidance_moments: part {tuple(part.shape)} must be contiguous fp32 [{B}, {G}, 9]")
+    call("fluxmi_guidance_moments", _p(pred), _p(r), _p(part), B, N, _stream())
+    return part
+
+
+def guidance_combine(pred: torch.Tensor, part: torch.Tensor, params, r: Optional[torch.Tensor] = None, step=None, step_offset=None,
+                     coef_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """In place: both halves of pred = bf16((alpha c + beta u) + gamma r) with the per-image coefficients of `params` (guidance_params, or an
+    fp32 device tensor [8]) on the partial sums `part`; mu != 0 also advances r.  step / step_offset: ints or int32 device scalars (zero-init
+    compares their sum with params[6]).  Returns coef_out, fp32 [B, 4] = {alpha, beta, gamma, f} per image."""
+    B, N = _guidance_shape(pred, r)
+    dev = pred.device
+    prm = params if isinstance(params, torch.Tensor) else torch.tensor([float(v) for v in params], dtype=torch.float32, device=dev)
+    _req(prm, torch.float32, "params")
+    if prm.numel() != 8 or not prm.is_contiguous():
+        raise ValueError("guidance_combine: params holds 8 floats {s, phi, eta, rho, mu, mode, zero_init, 0}")
+    _req(part, torch.float32, "part")
+    if part.numel() != B * (-(-N // GUIDANCE_CHUNK)) * 9 or not part.is_contiguous():
+        raise ValueError(f"guidance_combine: part {tuple(part.shape)} is not guidance_moments' [B, ceil(N / {GUIDANCE_CHUNK}), 9]")
+    ints = []
+    for v in (step, step_offset):
+        t = v if v is None or isinstance(v, torch.Tensor) else torch.tensor([int(v)], dtype=torch.int32, device=dev)
+        ints.append(None if t is None else _req(t, torch.int32, "step"))
+    if coef_out is None:
+        coef_out = torch.empty((B, 4), dtype=torch.float32, device=dev)
+    _req(coef_out, torch.float32, "coef_out")
+    if coef_out.numel() != 4 * B or not coef_out.is_contiguous():
+        raise ValueError(f"guidance_combine: coef_out {tuple(coef_out.shape)} must be contiguous fp32 [{B}, 4]")
+    call("fluxmi_guidance_combine", _p(pred), _p(r), _p(part), _p(prm), _p(ints[0]), _p(ints[1]), _p(coef_out), B, N, _stream())
+    return coef_out
+
+
+def cfg_euler(img: torch.Tensor, pred: torch.Tensor, dt: float, scale: float) -> torch.Tensor:
+    """In place, the guided Euler update (fluxmi_cfg_euler): img bf16 [2B, img_rows, c_in], pred bf16 [2B, pred_rows, c_out]; both halves of
+    img get x + dt * (u + scale * (c - u)) on bf16 tensors, x read from the prompt half."""
+    _req(img, torch.bfloat16, "img")
+    _req(pred, torch.bfloat16, "pred")
+    if img.ndim != 3 or pred.ndim != 3 or img.shape[0] != pred.shape[0] or img.shape[0] % 2 or not (img.is_contiguous() and pred.is_contiguous()):
+        raise ValueError(f"cfg_euler: img {tuple(img.shape)} / pred {tuple(pred.shape)} must be contiguous [2B, rows, channels]")
+    dts = torch.tensor([float(dt)], dtype=torch.float32, device=img.device)
+    sc = torch.tensor([float(scale)], dtype=torch.float32, device=img.device)
+    call("fluxmi_cfg_euler", _p(img), _p(pred), _p(dts), None, _p(sc), img.shape[0] // 2, img.shape[1], pred.shape[1], img.shape[2], pred.shape[2],
+         _stream())
+    return img

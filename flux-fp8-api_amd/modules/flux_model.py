@@ -398,6 +398,38 @@ class Flux(nn.Module):
         flat = (C.c_uint32 * (4 * len(ids)))(*[w for row in ids for w in row])
         _lib.call("fluxmi_engine_set_solver_noise", self._engine, flat, len(ids), off)
 
+    GUIDANCE_SHAPING_KEYS = ("mode", "rescale", "eta", "norm_threshold", "momentum", "zero_init_steps", "step_offset")
+
+    @classmethod
+    def _check_guidance_shaping(cls, shaping, guided, cfg_scale):
+        """`guidance_shaping` of denoise -> (the 8 floats of fluxmi_guidance_combine, step_offset), or None"""
+        if shaping is None:
+            return None
+        if not guided:
+            raise ValueError("guidance_shaping needs a negative prompt (neg_txt / neg_y): it shapes the true-CFG combination of the two branches")
+        if not isinstance(shaping, dict) or set(shaping) - set(cls.GUIDANCE_SHAPING_KEYS):
+            raise ValueError(f"guidance_shaping: expected a dict with keys out of {cls.GUIDANCE_SHAPING_KEYS}, got {shaping!r}")
+        mode = shaping.get("mode", "cfg")
+        if mode not in ops.GUIDANCE_MODES:
+            raise ValueError(f"guidance_shaping: unknown mode {mode!r} (one of {sorted(ops.GUIDANCE_MODES)})")
+        phi, eta, rho, mu = (float(shaping.get(k, d)) for k, d in (("rescale", 0.0), ("eta", 1.0), ("norm_threshold", 0.0), ("momentum", 0.0)))
+        zi, off = int(shaping.get("zero_init_steps", 0)), int(shaping.get("step_offset", 0))
+        if not all(math.isfinite(v) for v in (phi, eta, rho, mu, float(cfg_scale))):
+            raise ValueError("guidance_shaping: every value (and cfg_scale) must be finite")
+        if not 0.0 <= phi <= 1.0:
+            raise ValueError(f"guidance_shaping: rescale {phi} outside [0, 1]")
+        if rho < 0.0 or zi < 0 or off < 0:
+            raise ValueError(f"guidance_shaping: norm_threshold {rho}, zero_init_steps {zi} and step_offset {off} must be >= 0")
+        return ops.guidance_params(cfg_scale, mode, phi, eta, rho, mu, zi), off
+
+    def _set_guidance(self, shaping):
+        """after _prepare, under the lock: the shaping state of this call (_check_guidance_shaping), or None = off.  Every set call with a
+        state starts APG's running difference at 0."""
+        if shaping is None:
+            _lib.call("fluxmi_engine_set_guidance", self._engine, None, 0)
+            return
+        _lib.call("fluxmi_engine_set_guidance", self._engine, (C.c_float * 8)(*shaping[0]), shaping[1])
+
     @staticmethod
     def _check_solver_noise(solver_noise, solver, B):
         """-> (ids: a list of B 4-tuples of uint32 words, eval_offset) or None"""
@@ -711,7 +743,7 @@ class Flux(nn.Module):
                 neg_y: Tensor | None = None, cfg_scale: float = 1.0, cache_threshold: float = 0.0, cache_max_hits: int = 0,
                 attn_groups: Tensor | None = None, inpaint_x0: Tensor | None = None, inpaint_noise: Tensor | None = None,
                 inpaint_mask: Tensor | None = None, inpaint_thresholds=None, controlnet=None, solver=None, solver_noise=None,
-                ip_adapter=None) -> Tensor:
+                ip_adapter=None, guidance_shaping: dict | None = None) -> Tensor:
         """The Euler loop of FluxPipeline.generate (reference flux_pipeline.py:619-651) run natively: calibrating
         steps unfused, every later step one replay of a captured hipGraph.  Returns the final latent tokens.
         FLUX.1 Kontext: with `img_cond_seq` / `img_cond_seq_ids` the reference tokens join every step's forward and are never stepped; the
@@ -749,7 +781,16 @@ class Flux(nn.Module):
         `ip_adapter`: a modules.ip_adapter.IPAdapterCall (Flux.forward): every step adds the adapter term behind every double block, in the
         calibrating and the graph-replayed steps alike; K / V and the scales are device data of ONE captured graph.  Its tensors hold 1 or B
         samples, a guided call's 2 or 2B: the prompt branches' tables, then the negative branches'.  Refused with attn_groups and
-        cache_threshold > 0."""
+        cache_threshold > 0.
+        `guidance_shaping` (a guided call only): a dict out of {mode: "cfg" | "apg" | "cfg_zero_star", rescale, eta, norm_threshold,
+        momentum, zero_init_steps, step_offset}.  Every step then runs two more launches in front of its update (csrc/guidance.hip): per-image
+        moments of (c, u, r), and p = alpha c + beta u + gamma r written over both branches' predictions, with `cfg_scale` as s -- CFG
+        rescale (`rescale` = phi), adaptive projected guidance (`eta`, `norm_threshold` = rho, `momentum` = mu; the running difference r
+        starts at 0 in every call and pass and advances once per model evaluation) and CFG-Zero* (the optimised scale s*; `zero_init_steps`
+        = the number of leading model EVALUATIONS of the request whose prediction is replaced by 0, counted from `step_offset` for a call
+        that continues a request; Heun and midpoint evaluate twice per step).  The formulas are those of include/fluxmi.h
+        (fluxmi_guidance_combine).  The values are device data of one captured graph; shaped versus unshaped is a graph kind.  None =
+        today's call, launch for launch."""
         n_user = len(timesteps) - 1
         if solver is not None:
             if cache_threshold and float(cache_threshold) > 0:
@@ -767,6 +808,7 @@ class Flux(nn.Module):
             if not inside or float(solver.times[-1]) != ts_f[-1]:
                 raise ValueError("solver: the program's evaluation times do not lie inside the steps of timesteps (build it from the same list)")
         solver_noise = self._check_solver_noise(solver_noise, solver, img.shape[0])
+        shaping = self._check_guidance_shaping(guidance_shaping, neg_txt is not None or neg_y is not None, cfg_scale)
         inpaint = self._check_inpaint(img, inpaint_x0, inpaint_noise, inpaint_mask, inpaint_thresholds, n_user)
         cache_threshold, cache_max_hits = float(cache_threshold), int(cache_max_hits)
         if not (math.isfinite(cache_threshold) and cache_threshold >= 0.0) or cache_max_hits < 0:
@@ -829,6 +871,8 @@ class Flux(nn.Module):
                     cond["solver"] = solver
                 if solver_noise is not None:  # picked like every per-sample tensor: a padded tail copies the last image's ids
                     cond["solver_noise"] = (solver_noise[0][sl] + solver_noise[0][sl.stop - 1:sl.stop] * pad, solver_noise[1])
+                if guidance_shaping is not None:
+                    cond["guidance_shaping"] = guidance_shaping
                 o = self.denoise(pick(img), pick(img_ids), pick(txt), pick(txt_ids), pick(y), timesteps, guidance=guidance, use_graph=use_graph,
                                  cache_threshold=cache_threshold, cache_max_hits=cache_max_hits, **cond)
                 outs.append(o[:per - pad])
@@ -857,6 +901,7 @@ class Flux(nn.Module):
             self._set_inpaint(inpaint, img.device)
             self._set_solver(solver)
             self._set_solver_noise(solver_noise)
+            self._set_guidance(shaping)
             net = self._attach_controlnet(cn, img.device)
             ip_set = False
             try:
@@ -872,6 +917,8 @@ class Flux(nn.Module):
                 self._release_controlnet(net)
                 if solver is not None:
                     self._set_solver(None)
+                if shaping is not None:
+                    self._set_guidance(None)
             if trial is not None:
                 self._advance_calibration(t_io.value)
         if self.in_channels != self.out_channels:

@@ -435,6 +435,42 @@ int fluxmi_solver_step_noise(void* img, const void* pred, void* xs, float* hist,
                              const float* scale, int B, long long img_rows, long long pred_rows, int c_in, int c_out, const unsigned* ids,
                              const int* eval_offset, void* stream);
 
+/* ---- guidance shaping of true classifier-free guidance: CFG rescale, APG, CFG-Zero*  ------------------------------
+ * Operands as for fluxmi_cfg_euler: pred bf16, dense [2B][N], N = pred_rows * c_out, N %% 8 == 0; sample b is c (the prompt branch), sample
+ * B + b is u (the negative branch).  r: fp32, dense [B][N], APG's running difference (NULL: no r; its sums are 0, it is never touched and mu
+ * counts as 0).  params: DEVICE float[8] = {s, phi, eta, rho, mu, mode, zero_init, 0}; mode 0 = CFG, 1 = APG, 2 = CFG-Zero*.
+ *
+ * moments: grid (ceil(N / 16384), B); workgroup g of image b owns elements [16384 g, 16384 (g + 1)) (fluxmi_fb_metric's rule) and writes the
+ * nine fp32 sums  Sc, Su, Sr, cc, uu, rr, cu, cr, ur  (plain sums, then sums of products) over them to part[b][g][9].  256 threads, 16-byte
+ * loads; a thread adds its vectors in ascending order (at most 64 adds per sum), then a fixed 8-level tree over the 256 threads (wave64
+ * butterfly, (w0 + w1) + (w2 + w3) through LDS); every product and every sum is rounded on its own; no atomics.  An image's partials depend
+ * on its own N elements only: the same bits alone, in any batch, at every launch.
+ *
+ * combine: grid (ceil(N / 16384), B).  Every workgroup of image b adds part[b][0..] in fp64 in ascending g, evaluates in fp64
+ *   CFG:        alpha = s,  beta = 1 - s,  gamma = 0
+ *   CFG-Zero*:  s* = cu / uu (1 if uu == 0);  alpha = s,  beta = s* (1 - s),  gamma = 0                    [ = s* u + s (c - s* u) ]
+ *   APG:        p = c + (s - 1)(d_perp + eta d_par),  d = c - u + mu r  projected on c:
+ *               dd = cc + uu + mu^2 rr - 2 cu + 2 mu cr - 2 mu ur;  dc = cc - cu + mu cr
+ *               tau = min(1, rho / sqrt(dd)) if rho > 0 and dd > 0, else 1;  k = tau dc / cc (0 if cc == 0)
+ *               alpha = 1 + (s - 1)(tau + (eta - 1) k);  beta = -(s - 1) tau;  gamma = (s - 1) tau mu
+ *   rescale (phi > 0, on whichever coefficients resulted):
+ *               mean_p = (alpha Sc + beta Su + gamma Sr) / N
+ *               E[p^2] = (alpha^2 cc + beta^2 uu + gamma^2 rr + 2 alpha beta cu + 2 alpha gamma cr + 2 beta gamma ur) / N
+ *               var_p = E[p^2] - mean_p^2;  var_c = max(0, cc / N - (Sc / N)^2)
+ *               f = phi sqrt(var_c / var_p) + (1 - phi)  (1 if var_p <= 0);  alpha, beta, gamma *= f
+ *   zero-init:  *step + *step_offset < zero_init (step, step_offset: DEVICE ints, NULL = 0):  alpha = beta = gamma = 0
+ * and casts alpha, beta, gamma to fp32: all workgroups of an image hold the same bits.  Workgroup 0 writes coef_out[b] = {alpha, beta,
+ * gamma, f} (fp32 [B][4], may be NULL; f as computed, zero-init or not).  Then per element, in fp32, every product and sum rounded on its
+ * own (no fma):
+ *   v = bf16((alpha c + beta u) + gamma r)  -> pred[b] AND pred[B + b]
+ *   mu != 0:  r' = (c - u) + mu r  -> r, stored behind all reads of the element           (mu == 0: r is neither read nor written)
+ * A term whose coefficient is exactly 0.0f is skipped and its buffer not read (fluxmi_solver_step's rule); the sum starts at the first term
+ * present, 0 when none.  With v in both halves every guided update kernel (fluxmi_cfg_euler, guided fluxmi_blend_euler / _solver_step) computes
+ * d = bf16(v - v) = 0, m = 0, p = v and steps with v as it is, for every finite scale.  part: float [B][ceil(N / 16384)][9]. */
+int fluxmi_guidance_moments(const void* pred, const float* r, float* part, int B, long long N, void* stream);
+int fluxmi_guidance_combine(void* pred, float* r, const float* part, const float* params, const int* step, const int* step_offset,
+                            float* coef_out, int B, long long N, void* stream);
+
 /* ---- first-block step cache: the streaming passes --------------------------------------
  * B samples of n bf16 elements each (n = cached rows x hidden, n %% 8 == 0).  The `x` side is the residual stream: the pointer is the first
  * cached row of sample 0, x_bstride the batch stride in elements; every other tensor is dense [B, n].  16-byte accesses; workgroup c of a
@@ -632,6 +668,19 @@ int fluxmi_engine_set_solver(fluxmi_engine_t* e, const double* coef_host, const 
  * re-allocates the workspace switch the noise off; a denoise call whose program has a non-zero cn and no ids set is refused.  A deterministic
  * solver request and a request without a solver allocate and launch exactly what they did before. */
 int fluxmi_engine_set_solver_noise(fluxmi_engine_t* e, const unsigned* ids_host, int batch, int eval_offset);
+/* Guidance shaping (fluxmi_guidance_moments / _combine) for the following fluxmi_engine_denoise_cfg calls on the PREPARED
+ * shape: every step of those calls -- calibrating, graph-replayed, both tails of a step-cached step -- launches moments and combine on
+ * "pred_s" immediately in front of the update kernel the request already had (guided Euler, blend, solver, with or without noise), which
+ * then steps with the shaped prediction.  params_host: the 8 floats of fluxmi_guidance_combine (finite; mode 0, 1 or 2; phi in [0, 1];
+ * rho, zero_init >= 0), step_offset >= 0: evaluation j of the call counts as j + step_offset against zero_init, so a request cut into
+ * several denoise calls zero-initialises what the uncut one does.  Both are device data staged with the call's schedule ("gd_params": float
+ * [8] | the offset): shaped versus unshaped is a kind of step graph like guided versus plain, and ONE graph serves every mode and value.
+ * The engine owns "gd_part", "gd_coef" (the last step's {alpha, beta, gamma, f} per image) and "gd_r" (fp32 [B / 2][Lpred * C_out]), made at
+ * the first shaped call of a prepared shape, dropped with the workspace and counted in fluxmi_engine_workspace_bytes; EVERY set call with
+ * params zeroes "gd_r" behind the next denoise call's staging, so a request starts APG's running difference at 0.  An unguided
+ * fluxmi_engine_denoise call does not consult the state.  params_host == NULL switches it off; a prepare that re-allocates the workspace
+ * does too.  A request without shaping allocates and launches exactly what it did before. */
+int fluxmi_engine_set_guidance(fluxmi_engine_t* e, const float* params_host, int step_offset);
 /* Test hook: phases [phase_from, phase_to] of ONE frozen forward on the engine's own buffers, mode 1 (fused) or 2 (unfused, frozen scales):
  *   0 img_in + txt_in on the request buffers "img_s" / "txt_s" (mode 1: the cached "txt_emb" of the last denoise call) + this step's
  *     modulation vectors out of the step-ahead table the last denoise call left (step = the request's step index, written to the device-side

@@ -22,8 +22,16 @@ Same two POST endpoints, request fields, defaults and status codes:
              guidance_mode=None ("cfg" | "apg" | "cfg_zero_star"), guidance_rescale=None (0..1), apg_eta=None, apg_norm_threshold=None (>= 0),
              apg_momentum=None, zero_init_steps=None (>= 0) -- guidance shaping of true classifier-free guidance (FluxPipeline.generate; needs
              negative_prompt and true_cfg_scale > 1), each passed on only when set;
+             stream=None, preview_every=None (>= 0) -- progress, live previews and cancellation, see below;
              a region with both or neither of box / mask, or a box outside 0 <= x0 < x1 <= 1, is a 422}
              ->  image/jpeg stream of FluxPipeline.generate(**args)                                               (reference api.py:54-86)
+             With stream=true the response is application/x-ndjson instead, one JSON object per line: for every model evaluation
+               {"event": "progress", "evaluation", "num_evaluations", "step", "preview": <base64 JPEG at latent resolution, or null>}
+             (a preview at every preview_every-th evaluation; none with preview_every unset or 0), then ONE final line
+               {"event": "result", "image": <base64 JPEG>}  |  {"event": "cancelled"}  |  {"event": "error", "message"}.
+             The request runs in a worker thread that feeds a queue; closing the response -- a client that disconnected -- sets a flag
+             that the next on_step turns into a cancel, so an abandoned request frees its GPU within two model evaluations.
+             preview_every without stream is a 422.
   /lora      LoraArgs{scale=1.0, path, name, action="load"|"unload"}  ->  {"status": "success"} | 400 invalid action | 500 with the
              exception text; unload uses `name` when given, else `path`                                         (reference api.py:89-122)
 The app holds one pipeline in `app.state.model`; FastAPI runs these sync handlers on its threadpool, and the pipeline serialises
@@ -31,7 +39,12 @@ engine access with its own lock (modules/flux_model.py), so concurrent requests 
 """
 from __future__ import annotations
 
+import base64
+import io
+import json
+import queue
 import random
+import threading
 from typing import List, Literal, Optional, Tuple, Union
 
 from fastapi import FastAPI
@@ -104,9 +117,60 @@ class GenerateArgs(BaseModel):
     apg_norm_threshold: Optional[float] = Field(default=None, ge=0.0)  # ... APG: clip the guidance difference to this norm (0 = off)
     apg_momentum: Optional[float] = None  # ... APG: the running difference's momentum (0 = off)
     zero_init_steps: Optional[int] = Field(default=None, ge=0)  # ... CFG-Zero*'s zero-init: the first k model evaluations predict 0
+    stream: Optional[bool] = None  # answer with application/x-ndjson progress lines and a final result line instead of the JPEG
+    preview_every: Optional[int] = Field(default=None, ge=0)  # ... with a latent-resolution preview at every k-th model evaluation (0 = none)
 
 
 app = FastAPI(title="fluxmi")
+
+
+def _preview_jpeg(preview) -> str:
+    """uint8 [num_images, h, w, 3] -> base64 JPEG, the images stacked vertically like FluxPipeline.into_bytes"""
+    import numpy as np
+    from PIL import Image
+
+    buf = io.BytesIO()
+    Image.fromarray(np.vstack(list(preview))).save(buf, format="JPEG", quality=90)
+    return base64.b64encode(buf.getvalue()).decode("ascii")
+
+
+def stream_events(model, kwargs):
+    """The NDJSON lines of one streamed request (a generator of bytes).  `model.generate(**kwargs, on_step=...)` runs in a worker thread
+    and feeds a queue; closing this generator -- what the server does when the client went away -- sets the flag that the next on_step
+    turns into a cancel (it returns False), and the worker's remaining lines are dropped."""
+    lines: "queue.Queue" = queue.Queue()
+    gone = threading.Event()
+
+    def on_step(info):
+        if gone.is_set():
+            return False
+        pv = info.get("preview")
+        lines.put({"event": "progress", "evaluation": int(info["evaluation"]), "num_evaluations": int(info["num_evaluations"]),
+                   "step": int(info["step"]), "preview": None if pv is None else _preview_jpeg(pv)})
+        return True
+
+    def work():
+        try:
+            result = model.generate(**kwargs, on_step=on_step)
+            data = result.getvalue() if hasattr(result, "getvalue") else bytes(result)
+            lines.put({"event": "result", "image": base64.b64encode(data).decode("ascii")})
+        except Exception as e:
+            from fluxmi import GenerationCancelled
+
+            lines.put({"event": "cancelled"} if isinstance(e, GenerationCancelled) else {"event": "error", "message": str(e)})
+        finally:
+            lines.put(None)
+
+    worker = threading.Thread(target=work, name="fluxmi-stream", daemon=True)
+    worker.start()
+    try:
+        while True:
+            line = lines.get()
+            if line is None:
+                return
+            yield (json.dumps(line) + "\n").encode("utf-8")
+    finally:
+        gone.set()
 
 
 @app.post("/generate")
@@ -119,6 +183,11 @@ def generate(args: GenerateArgs):
     `negative_ip_adapter_image`, `negative_ip_adapter_scale`) a FLUX IP-Adapter, `guidance_mode` / `guidance_rescale` / `apg_*` /
     `zero_init_steps` guidance shaping of a guided request.  Without them the call is exactly the reference's."""
     kwargs = args.model_dump()
+    stream = bool(kwargs.pop("stream", None))
+    if kwargs.get("preview_every") is None:
+        kwargs.pop("preview_every", None)
+    elif not stream:
+        return JSONResponse(status_code=422, content={"status": "error", "message": "preview_every needs stream=true"})
     for k in ("reference_image", "mask_image", "control_image", "redux_image", "negative_prompt", "true_cfg_scale", "true_cfg_interval",
               "cache_threshold", "cache_max_hits", "regions", "regional_tokens", "inpaint_mask", "inpaint_differential", "controlnet_image",
               "controlnet_conditioning_scale", "control_mode", "control_guidance_start", "control_guidance_end", "sampler", "sigma_schedule",
@@ -144,6 +213,8 @@ def generate(args: GenerateArgs):
             else:
                 regs.append({"prompt": r["prompt"], "mask": r["mask"]})
         kwargs["regions"] = regs
+    if stream:
+        return StreamingResponse(stream_events(app.state.model, kwargs), media_type="application/x-ndjson")
     result = app.state.model.generate(**kwargs)
     return StreamingResponse(result, media_type="image/jpeg")
 

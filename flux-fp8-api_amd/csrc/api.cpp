@@ -277,6 +277,11 @@ int fluxmi_guidance_combine(void* pred, float* r, const float* part, const float
                             float* coef_out, int B, long long N, void* stream) {
   return fluxmi_k_guidance_combine(pred, r, part, params, step, step_offset, coef_out, B, N, (hipStream_t)stream);
 }
+int fluxmi_latent_preview(const void* x, const void* pred, const float* ts, const int* step, const float* scale, const float* proj,
+                          const int* ctl, void* out, int B, long long img_rows, long long pred_rows, int c_in, int c_out, int h, int w,
+                          void* stream) {
+  return fluxmi_k_latent_preview(x, pred, ts, step, scale, proj, ctl, out, B, img_rows, pred_rows, c_in, c_out, h, w, (hipStream_t)stream);
+}
 int fluxmi_ip_attention(const void* qkv, long long ld_qkv, long long qkv_bstride, const void* qn_scale, const void* k_ip, const void* v_ip,
                         long long kv_bstride, void* out, long long ld_o, long long o_bstride, const float* scale, long long scale_bstride, int B,
                         int rows, int heads, int Nk, void* stream) {

@@ -56,6 +56,8 @@ struct StepGraphs {
   bool solver = false;  // ... and the table-driven solver update (fluxmi_engine_set_solver): WHICH solver is device data, not a kind
   bool noise = false;   // ... and its form with the noise term (fluxmi_engine_set_solver_noise): seeds and the offset are device data
   bool shaped = false;  // guidance shaping (fluxmi_engine_set_guidance): two launches in front of the guided update; mode and values are device data
+  bool previewed = false;  // the preview launch in front of the update (fluxmi_engine_set_preview, every > 0): cadence, offset and factors are device data ...
+  int pv_h = 0, pv_w = 0;  // ... the token grid is a launch argument
   unsigned gen = 0;     // fluxmi_tuning_generation() the pieces were captured under
   const void* cn = nullptr;  // the attached ControlNet whose launches (and workspace pointers) are baked into the pieces, or none ...
   unsigned long long cn_gen = 0;  // ... and the generation of its workspace / weight binding: process-wide unique, so a net created at a freed net's address never matches
@@ -207,6 +209,25 @@ struct fluxmi_engine {
   size_t ip_bytes = 0;
   unsigned long long ip_gen = 0;
   std::vector<float> ip_scales_h;  // the staged scales' host copy (alive until the next set call: the source of an asynchronous copy)
+  // progress, previews and cancellation (fluxmi_engine_set_preview): the host state of the following denoise calls.  The
+  // device buffers ("pv_proj" float [51] | "pv_ctl" int {every, eval_offset} | "pv_out" uint8 [SLOTS][B][2 h][2 w][3]) are one allocation made at
+  // the first previewed call of a prepared shape and dropped with the workspace; proj and ctl are staged through h_sched like the schedule.
+  // The pinned delivery buffer, the private copy stream and the event ring are made by the first set call with a hook and live as long as
+  // the engine.  Nothing of it without a hook; with every = 0 only the events.
+  fluxmi_step_hook_t pv_hook = nullptr;
+  void* pv_user = nullptr;
+  int pv_every = 0, pv_offset = 0, pv_n = 0, pv_h = 0, pv_w = 0;
+  float pv_proj[51];
+  char* pv_mem = nullptr;
+  size_t pv_bytes = 0;
+  unsigned char* pv_host = nullptr;
+  size_t pv_host_bytes = 0;
+  hipStream_t pv_stream = nullptr;
+  hipEvent_t pv_ev[FLUXMI_PREVIEW_DEPTH + 1] = {};
+  // ... and the state of the running call: evaluations launched / delivered to the hook, the caller's images, whether the hook said stop
+  int pv_launched = 0, pv_delivered = 0, pv_images = 0;
+  bool pv_cancelled = false;
+  long long captures = 0;          // graph captures since create (fluxmi_engine_preview_stats: read-only, for tests)
 };
 
 namespace {
@@ -1167,6 +1188,9 @@ void free_ws(E* e) {
   e->gd_on = e->gd_zero_r = false;
   if (e->ip_mem) { hipFree(e->ip_mem); e->ip_mem = nullptr; e->ip_bytes = 0; }
   e->ip_on = false;
+  if (e->pv_mem) { hipFree(e->pv_mem); e->pv_mem = nullptr; e->pv_bytes = 0; }
+  e->pv_hook = nullptr;
+  e->pv_every = 0;
   if (e->ws) { hipFree(e->ws); e->ws = nullptr; }
   e->bufs.clear();
   e->ws_bytes = 0;
@@ -1282,6 +1306,29 @@ int ensure_gd(E* e, hipStream_t s) {
   size_t off = 0;
   for (auto& it : items) {
     e->bufs[it.name] = Buf{e->gd_mem + off, it.bytes};
+    off += (it.bytes + 255) & ~(size_t)255;
+  }
+  return 0;
+}
+
+// the preview buffers of the prepared shape, made once a previewed request arrives (like ensure_fb): room for a plain call's B images
+int ensure_pv(E* e, hipStream_t s) {
+  if (e->pv_mem) return 0;
+  struct Item { const char* name; size_t bytes; };
+  const Item items[] = {{"pv_proj", 51 * 4}, {"pv_ctl", 2 * 4}, {"pv_out", (size_t)FLUXMI_PREVIEW_SLOTS * e->B * e->Lpred * 4 * 3}};
+  size_t total = 0;
+  for (auto& it : items) total += (it.bytes + 255) & ~(size_t)255;
+  if (hipMalloc((void**)&e->pv_mem, total) != hipSuccess) {
+    (void)hipGetLastError();
+    e->pv_mem = nullptr;
+    fluxmi_set_error("engine_denoise: hipMalloc(%zu bytes) failed (preview)", total);
+    return 2;
+  }
+  e->pv_bytes = total;
+  FLUXMI_CHECK_HIP(hipMemsetAsync(e->pv_mem, 0, total, s));
+  size_t off = 0;
+  for (auto& it : items) {
+    e->bufs[it.name] = Buf{e->pv_mem + off, it.bytes};
     off += (it.bytes + 255) & ~(size_t)255;
   }
   return 0;
@@ -1405,7 +1452,7 @@ static int create_impl(const fluxmi_model_desc_t* desc, const fluxmi_linear_t* l
   e->d_tnext = (float*)(e->consts + o_tnext); e->d_omt = (float*)(e->consts + o_omt); e->d_thr = (float*)(e->consts + o_thr);
   hipMemset(e->consts, 0, off);
   // pinned staging for the schedule (ts | dts | tnext | 1 - tnext | thresholds | solver coef | solver ctl | noise ids | eval offset) + the events (guard of the staging buffer, timing of the frozen steps)
-  if (hipHostMalloc((void**)&e->h_sched, (5 * (MAX_STEPS + 1) + 12 * MAX_STEPS + 4 * FLUXMI_ENGINE_MAX_BATCH + 1 + 9) * sizeof(float), hipHostMallocDefault) != hipSuccess ||
+  if (hipHostMalloc((void**)&e->h_sched, (5 * (MAX_STEPS + 1) + 12 * MAX_STEPS + 4 * FLUXMI_ENGINE_MAX_BATCH + 1 + 9 + 53) * sizeof(float), hipHostMallocDefault) != hipSuccess ||
       hipEventCreateWithFlags(&e->ev_sched, hipEventDisableTiming) != hipSuccess || hipEventCreate(&e->ev_t0) != hipSuccess ||
       hipEventCreate(&e->ev_t1) != hipSuccess) {
     fluxmi_engine_destroy(e);
@@ -1428,6 +1475,10 @@ int fluxmi_engine_destroy(fluxmi_engine_t* e) {
   if (e->ev_t1) hipEventDestroy(e->ev_t1);
   if (e->h_ratio) hipHostFree(e->h_ratio);
   if (e->ev_fb) hipEventDestroy(e->ev_fb);
+  if (e->pv_host) hipHostFree(e->pv_host);
+  if (e->pv_stream) hipStreamDestroy(e->pv_stream);
+  for (hipEvent_t ev : e->pv_ev)
+    if (ev) hipEventDestroy(ev);
   delete e;
   return 0;
 }
@@ -1644,6 +1695,12 @@ static void graphs_stale(fluxmi_engine_t* e, StepGraphs& g, bool cfg) {
   if (g.cfg != cfg || g.masked != e->masked || g.blend != e->inp_on || g.diff != diff || g.solver != e->sol_on || g.noise != e->sol_noise ||
       g.shaped != shaped)
     g.ok = g.warmed = false;
+  // ... and the preview launch with its token grid (cadence, offset and factors are device data: they never re-capture)
+  const bool previewed = e->pv_hook && e->pv_every > 0;
+  if (g.previewed != previewed || (previewed && (g.pv_h != e->pv_h || g.pv_w != e->pv_w))) g.ok = g.warmed = false;
+  g.previewed = previewed;
+  g.pv_h = previewed ? e->pv_h : 0;
+  g.pv_w = previewed ? e->pv_w : 0;
   // ... and so is the attached ControlNet: its launches, weights and workspace pointers are baked into the pieces
   if (g.cn != e->cn || (e->cn && g.cn_gen != e->cn->ws_gen)) g.ok = g.warmed = false;
   g.cn = e->cn;
@@ -1687,6 +1744,41 @@ static int capture_pieces(StepGraphs& g, const StepPiece* pieces, int n) {
   return 0;
 }
 
+// ---- the throttled loop of a hooked call (fluxmi.h, fluxmi_engine_set_preview) ---------------------------------------------------------------
+// Evaluation k of the call goes to the hook: waits on the event recorded behind it, copies its preview slot -- if it has one -- to the pinned
+// buffer on the private stream, waits for that copy, calls the hook on the caller's thread.  A non-zero return sets pv_cancelled.
+static int pv_deliver(fluxmi_engine_t* e, int k) {
+  FLUXMI_CHECK_HIP(hipEventSynchronize(e->pv_ev[k % (FLUXMI_PREVIEW_DEPTH + 1)]));
+  const long long g = (long long)e->pv_offset + k;
+  const unsigned char* rgb = nullptr;
+  if (e->pv_every > 0 && g % e->pv_every == 0) {
+    const size_t bytes = (size_t)e->pv_images * e->pv_h * e->pv_w * 4 * 3;
+    const size_t slot = (size_t)((g / e->pv_every) % FLUXMI_PREVIEW_SLOTS);
+    FLUXMI_CHECK_HIP(hipMemcpyAsync(e->pv_host, buf<unsigned char>(e, "pv_out") + slot * bytes, bytes, hipMemcpyDeviceToHost, e->pv_stream));
+    FLUXMI_CHECK_HIP(hipStreamSynchronize(e->pv_stream));
+    rgb = e->pv_host;
+  }
+  e->pv_delivered = k + 1;
+  if (e->pv_hook(e->pv_user, (int)g, e->pv_n, rgb, e->pv_images, 2 * e->pv_h, 2 * e->pv_w) != 0) e->pv_cancelled = true;
+  return 0;
+}
+// One evaluation of a denoise call, `run`, under the look-ahead rule: the ONE helper of the calibrating loop and of frozen_steps.  Without a
+// hook it is `run` alone.  With one: before launching evaluation i >= DEPTH, every evaluation up to i - DEPTH not yet delivered is delivered,
+// in order; a cancel there returns FLUXMI_CANCELLED with nothing further launched.  Behind the launch the evaluation's event is recorded: slot
+// i % (DEPTH + 1) of the ring, last used by evaluation i - DEPTH - 1, which has been delivered.
+static int pv_eval(fluxmi_engine_t* e, hipStream_t s, const std::function<int()>& run) {
+  if (!e->pv_hook) return run();
+  const int i = e->pv_launched;
+  while (e->pv_delivered <= i - FLUXMI_PREVIEW_DEPTH) {
+    FLUXMI_TRY(pv_deliver(e, e->pv_delivered));
+    if (e->pv_cancelled) return FLUXMI_CANCELLED;
+  }
+  FLUXMI_TRY(run());
+  FLUXMI_CHECK_HIP(hipEventRecord(e->pv_ev[i % (FLUXMI_PREVIEW_DEPTH + 1)], s));
+  e->pv_launched = i + 1;
+  return 0;
+}
+
 // The modulation vectors of up to MODS_STEPS steps are produced ahead (one pass over the 3.2 GB of modulation weights per window); the table
 // address and the device-side window origin never change, so ONE set of captured pieces serves every step of every request.  The first frozen
 // step of a shape and update kind runs eagerly, so that every lazy one-time init (function attributes) happens outside capture; the steps
@@ -1711,13 +1803,14 @@ static int frozen_steps(fluxmi_engine_t* e, const Stepper& st, int mode, bool cf
     if (use_graph && !g.ok) {
       if (!g.warmed) {
         if (st.pre_warm) FLUXMI_TRY(st.pre_warm());
-        FLUXMI_TRY(st.step(false));
+        FLUXMI_TRY(pv_eval(e, s, [&]() { return st.step(false); }));
         ++step;
         g.warmed = true;
       }
       if (step < win_end) {
         FLUXMI_CHECK_HIP(hipStreamSynchronize(s));  // one-time, at graph capture only
         FLUXMI_TRY(capture_pieces(g, st.piece, st.n_pieces));
+        ++e->captures;
       }
     }
     Range r(st.range);
@@ -1729,13 +1822,15 @@ static int frozen_steps(fluxmi_engine_t* e, const Stepper& st, int mode, bool cf
       t0 = true;
     }
     const bool graph = use_graph && g.ok;
-    for (; step < win_end; ++step) FLUXMI_TRY(st.step(graph));
+    int rc = 0;  // (a cancelled call leaves through here as well: what was replayed wrote the buffers)
+    for (; step < win_end && !rc; ++step) rc = pv_eval(e, s, [&]() { return st.step(graph); });
     if (graph) {
       // the host code of the step ran at capture only: the replayed pieces wrote the activation buffers in the layout they were captured
       // with (a tuning change since the capture re-captures above)
       const bool ap = act_pairs(e, mode == 1);
       for (bool& b : e->act_in_pairs) b = ap;
     }
+    FLUXMI_TRY(rc);
   }
   return 0;
 }
@@ -1881,6 +1976,17 @@ static int denoise_impl(fluxmi_engine_t* e, void* img, const void* txt, const vo
   // pred_s then hold the shaped prediction v, and the update's own chain d = bf16(v - v) = 0, m = 0, p = v steps with v unchanged.
   const bool shaped = cfg && e->gd_on;
   if (shaped) FLUXMI_TRY(ensure_gd(e, s));
+  // Progress / previews / cancellation (fluxmi_engine_set_preview): the preview launch goes in front of whichever update runs, behind the
+  // shaping -- both halves of pred_s then hold v, and the guided formula u + s (v - v) still gives v
+  const bool hooked = e->pv_hook != nullptr, previewed = hooked && e->pv_every > 0;
+  FLUXMI_REQUIRE(!hooked || !e->amax_hook, "engine_denoise: a step hook and an amax-exchange hook are both set (previews, progress and "
+                 "cancellation are refused under a process group: the host waits would stall its collectives)");
+  FLUXMI_REQUIRE(!previewed || ((long long)e->pv_h * e->pv_w == e->Lpred && c_out(e) == 64), "engine_denoise: the preview state's token grid "
+                 "%d x %d does not cover the %d stepped rows of the prepared shape (or C_out = %d != 64)", e->pv_h, e->pv_w, e->Lpred, c_out(e));
+  if (previewed) FLUXMI_TRY(ensure_pv(e, s));
+  e->pv_launched = e->pv_delivered = 0;
+  e->pv_cancelled = false;
+  e->pv_images = cfg ? B / 2 : B;
   auto euler = [&](hipStream_t st) -> int {
     if (shaped) {
       const long long n_pred = (long long)e->Lpred * c_out(e);
@@ -1889,6 +1995,10 @@ static int denoise_impl(fluxmi_engine_t* e, void* img, const void* txt, const vo
       FLUXMI_TRY(fluxmi_k_guidance_combine(buf<u16>(e, "pred_s"), buf<float>(e, "gd_r"), buf<float>(e, "gd_part"), gp, e->d_step,
                                            (const int*)(gp + 8), buf<float>(e, "gd_coef"), B / 2, n_pred, st));
     }
+    if (previewed)
+      FLUXMI_TRY(fluxmi_k_latent_preview(buf<u16>(e, "img_s"), buf<u16>(e, "pred_s"), e->d_ts, e->d_step, cfg ? e->d_cfg : nullptr,
+                                         buf<float>(e, "pv_proj"), buf<int>(e, "pv_ctl"), buf<unsigned char>(e, "pv_out"), cfg ? B / 2 : B, Li,
+                                         e->Lpred, C, c_out(e), e->pv_h, e->pv_w, st));
     if (sol_noise)
       return fluxmi_k_solver_step_noise(buf<u16>(e, "img_s"), buf<u16>(e, "pred_s"), buf<u16>(e, "sol_xs"), buf<float>(e, "sol_hist"),
                                         e->d_sol_coef, e->d_sol_ctl, e->inp_on ? buf<u16>(e, "inp_x0") : nullptr,
@@ -1980,6 +2090,14 @@ static int denoise_impl(fluxmi_engine_t* e, void* img, const void* txt, const vo
     if (e->gd_zero_r) FLUXMI_CHECK_HIP(hipMemsetAsync(buf<float>(e, "gd_r"), 0, (size_t)(B / 2) * e->Lpred * c_out(e) * 4, s));
     e->gd_zero_r = false;
   }
+  if (previewed) {  // ... and the projection with the control word {every, eval_offset} behind it (one copy: "pv_ctl" follows "pv_proj" at +256)
+    float* h_pv = e->h_sched + 5 * (MAX_STEPS + 1) + 12 * MAX_STEPS + 4 * FLUXMI_ENGINE_MAX_BATCH + 1 + 9;
+    memcpy(h_pv, e->pv_proj, 51 * 4);
+    const int ctl[2] = {e->pv_every, e->pv_offset};
+    memcpy(h_pv + 51, ctl, 8);
+    FLUXMI_CHECK_HIP(hipMemcpyAsync(buf<float>(e, "pv_proj"), h_pv, 51 * 4, hipMemcpyHostToDevice, s));
+    FLUXMI_CHECK_HIP(hipMemcpyAsync(buf<int>(e, "pv_ctl"), h_pv + 51, 8, hipMemcpyHostToDevice, s));
+  }
   FLUXMI_CHECK_HIP(hipEventRecord(e->ev_sched, s));
   e->sched_pending = true;
   u16 *gvec = buf<u16>(e, "gvec"), *tvec = buf<u16>(e, "tvec");
@@ -2006,7 +2124,7 @@ static int denoise_impl(fluxmi_engine_t* e, void* img, const void* txt, const vo
     // (with a ControlNet attached: while EITHER net has trials left -- that net in mode 0, the other in its frozen mode, eagerly)
     auto main_cal = [&]() { return main_f8 && trial <= e->d.num_trials; };
     auto cn_cal = [&]() { return cn_f8 && cn->cn_trial <= cn->d.num_trials; };
-    while (step < n_steps && (main_cal() || cn_cal())) {
+    auto cal_step = [&]() -> int {
       FLUXMI_TRY(fluxmi_k_set_timestep(tvec, e->d_ts, e->d_step, B, s));
       if (cn) {
         const int nmode = cn_cal() ? 0 : (all_block_linears_f8(cn) ? 1 : 2);
@@ -2023,13 +2141,19 @@ static int denoise_impl(fluxmi_engine_t* e, void* img, const void* txt, const vo
       FLUXMI_TRY(fluxmi_k_advance_step(e->d_step, s));
       if (mmode == 0) ++trial;
       ++step;
+      return 0;
+    };
+    while (step < n_steps && (main_cal() || cn_cal())) {
+      const int rc = pv_eval(e, s, cal_step);
+      if (rc == FLUXMI_CANCELLED && e->pv_cancelled) break;
+      FLUXMI_TRY(rc);
     }
   }
   // -- frozen steps -------------------------------------------------------------------------------------------
   e->timed_steps = 0;
   e->fb_log_ratio.clear();
   e->fb_log_hit.clear();
-  if (step < n_steps) {
+  if (step < n_steps && !e->pv_cancelled) {
     const int mode = all_block_linears_f8(e) ? 1 : 2;  // any bf16 block linear -> the fused path is unavailable, run unfused-frozen
     if (mode == 1) {
       FLUXMI_TRY(embed_txt(e, txt_s, false, 0, buf<u16>(e, "txt_emb"), (long long)Lt * e->d.hidden, s));
@@ -2048,12 +2172,22 @@ static int denoise_impl(fluxmi_engine_t* e, void* img, const void* txt, const vo
     }
     // plain, or with first-block step caching: the same steps cut into head / body / skip pieces with a host decision in between
     int first_timed = n_steps;  // the first step behind ev_t0, which the loop records: ev_t0 .. ev_t1 brackets steps [first_timed, n_steps)
-    FLUXMI_TRY((e->fb_threshold > 0.f ? cached_steps : plain_steps)(e, mode, cfg, step, n_steps, g_arg, use_graph, euler, &first_timed, s));
+    const int rc = (e->fb_threshold > 0.f ? cached_steps : plain_steps)(e, mode, cfg, step, n_steps, g_arg, use_graph, euler, &first_timed, s);
+    if (!(rc == FLUXMI_CANCELLED && e->pv_cancelled)) FLUXMI_TRY(rc);
     FLUXMI_CHECK_HIP(hipEventRecord(e->ev_t1, s));
-    e->timed_steps = n_steps - first_timed;
+    e->timed_steps = e->pv_cancelled ? std::max(0, e->pv_launched - first_timed) : n_steps - first_timed;
   }
+  // a hooked call drains: the evaluations still in flight are waited for and delivered, so the call is synchronous.  A cancelled one delivers
+  // nothing further and waits for what it launched
+  while (hooked && !e->pv_cancelled && e->pv_delivered < e->pv_launched) FLUXMI_TRY(pv_deliver(e, e->pv_delivered));
+  if (e->pv_cancelled && e->pv_launched > 0)
+    FLUXMI_CHECK_HIP(hipEventSynchronize(e->pv_ev[(e->pv_launched - 1) % (FLUXMI_PREVIEW_DEPTH + 1)]));
   FLUXMI_CHECK_HIP(hipMemcpyAsync(img, img_s, n_img * 2, hipMemcpyDeviceToDevice, s));
   *trial_index_inout = trial;
+  if (e->pv_cancelled) {
+    fluxmi_set_error("engine_denoise: cancelled by the step hook after %d of %d evaluations", e->pv_launched, n_steps);
+    return FLUXMI_CANCELLED;
+  }
   return 0;
 }
 
@@ -2188,6 +2322,55 @@ int fluxmi_engine_set_guidance(fluxmi_engine_t* e, const float* params_host, int
   e->gd_params[7] = 0.f;
   e->gd_offset = step_offset;
   e->gd_on = e->gd_zero_r = true;
+  return 0;
+}
+
+// The progress / preview / cancellation state of the following denoise calls (fluxmi.h): host data only, like the solver program; the pinned
+// delivery buffer, the private copy stream and the event ring are made here, never inside a denoise call.
+int fluxmi_engine_set_preview(fluxmi_engine_t* e, const float* proj51_host, int h, int w, int every, int eval_offset, int n_evaluations,
+                              fluxmi_step_hook_t hook, void* user) {
+  FLUXMI_REQUIRE(e, "engine_set_preview: NULL engine");
+  if (!hook) {
+    e->pv_hook = nullptr; e->pv_user = nullptr; e->pv_every = 0;
+    return 0;
+  }
+  FLUXMI_REQUIRE(!e->is_cn, "engine_set_preview: a ControlNet engine steps nothing (set the hook on the main engine)");
+  FLUXMI_REQUIRE(e->ws, "engine_set_preview: call fluxmi_engine_prepare first (the state belongs to the prepared shape)");
+  FLUXMI_REQUIRE(!e->amax_hook, "engine_set_preview: an amax-exchange hook is attached (previews, progress and cancellation are refused under a "
+                 "process group: the host waits would stall its collectives)");
+  FLUXMI_REQUIRE(every >= 0, "engine_set_preview: every %d < 0 (0 = progress and cancellation only)", every);
+  FLUXMI_REQUIRE(eval_offset >= 0 && n_evaluations >= 0, "engine_set_preview: eval_offset %d, n_evaluations %d must be >= 0", eval_offset, n_evaluations);
+  if (every > 0) {
+    FLUXMI_REQUIRE(proj51_host, "engine_set_preview: every > 0 needs the 51 projection floats");
+    for (int i = 0; i < 51; ++i) FLUXMI_REQUIRE(std::isfinite(proj51_host[i]), "engine_set_preview: projection value %d is not finite", i);
+    FLUXMI_REQUIRE(c_out(e) == 64, "engine_set_preview: the model predicts %d channels per token (a preview needs 16 latent channels x 4 sub-pixels)", c_out(e));
+    FLUXMI_REQUIRE(h >= 1 && w >= 1 && (long long)h * w == e->Lpred, "engine_set_preview: a token grid of %d x %d for the %d stepped rows of the "
+                   "prepared shape", h, w, e->Lpred);
+    const size_t need = (size_t)e->B * e->Lpred * 4 * 3;
+    if (e->pv_host_bytes < need) {
+      if (e->pv_host) { hipHostFree(e->pv_host); e->pv_host = nullptr; e->pv_host_bytes = 0; }
+      FLUXMI_CHECK_HIP(hipHostMalloc((void**)&e->pv_host, need, hipHostMallocDefault));
+      e->pv_host_bytes = need;
+    }
+    if (!e->pv_stream) FLUXMI_CHECK_HIP(hipStreamCreateWithFlags(&e->pv_stream, hipStreamNonBlocking));
+    memcpy(e->pv_proj, proj51_host, 51 * 4);
+  }
+  for (hipEvent_t& ev : e->pv_ev)
+    if (!ev) FLUXMI_CHECK_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+  e->pv_h = every > 0 ? h : 0;
+  e->pv_w = every > 0 ? w : 0;
+  e->pv_every = every;
+  e->pv_offset = eval_offset;
+  e->pv_n = n_evaluations;
+  e->pv_hook = hook;
+  e->pv_user = user;
+  return 0;
+}
+
+int fluxmi_engine_preview_stats(fluxmi_engine_t* e, long long* captures, int* evaluations_run) {
+  FLUXMI_REQUIRE(e && captures && evaluations_run, "engine_preview_stats: NULL argument");
+  *captures = e->captures;
+  *evaluations_run = e->pv_launched;
   return 0;
 }
 
@@ -2363,6 +2546,7 @@ int fluxmi_engine_set_amax_exchange(fluxmi_engine_t* e, float* amax_dev, int n, 
     e->d_amax = e->d_amax_own;
     return 0;
   }
+  FLUXMI_REQUIRE(!e->pv_hook, "engine_set_amax_exchange: a step hook is set (fluxmi_engine_set_preview is refused under a process group)");
   FLUXMI_REQUIRE(amax_dev && n >= (int)e->lin.size(), "engine_set_amax_exchange: need a device array of >= %d floats", (int)e->lin.size());
   e->amax_hook = hook; e->amax_user = user; e->amax_ext = amax_dev; e->d_amax = amax_dev;
   return 0;
@@ -2424,7 +2608,7 @@ int fluxmi_engine_copy_buffer(fluxmi_engine_t* e, const char* name, long long of
 
 int fluxmi_engine_workspace_bytes(fluxmi_engine_t* e, long long* bytes) {
   FLUXMI_REQUIRE(e && bytes, "engine_workspace_bytes: NULL argument");
-  *bytes = (long long)(e->ws_bytes + e->pairs_bytes + e->mods_all_bytes + e->fb_bytes + e->inp_bytes + e->sol_bytes + e->sol_ids_bytes + e->ip_bytes + e->gd_bytes);  // workspace + row-pair weight copies + modulation table + step cache + inpainting + solver buffers + noise ids + adapter + guidance shaping
+  *bytes = (long long)(e->ws_bytes + e->pairs_bytes + e->mods_all_bytes + e->fb_bytes + e->inp_bytes + e->sol_bytes + e->sol_ids_bytes + e->ip_bytes + e->gd_bytes + e->pv_bytes);  // workspace + row-pair weight copies + modulation table + step cache + inpainting + solver buffers + noise ids + adapter + guidance shaping + preview ring
   return 0;
 }
 

@@ -193,6 +193,11 @@ int fluxmi_k_fb_apply(void* x, long long x_bstride, const void* h1, long long h1
 int fluxmi_k_guidance_moments(const void* pred, const float* r, float* part, int B, long long N, hipStream_t s);
 int fluxmi_k_guidance_combine(void* pred, float* r, const float* part, const float* params, const int* step, const int* step_offset,
                               float* coef_out, int B, long long N, hipStream_t s);
+// latent preview (preview.hip; include/fluxmi.h, fluxmi_latent_preview): x0 = x - t v of one evaluation projected 16 -> 3 into a ring slot chosen
+// on the device from *step and ctl = {every, eval_offset}
+int fluxmi_k_latent_preview(const void* x, const void* pred, const float* ts, const int* step, const float* scale, const float* proj,
+                            const int* ctl, void* out, int B, long long img_rows, long long pred_rows, int c_in, int c_out, int h, int w,
+                            hipStream_t s);
 // ControlNet residual hand-over: x[b, j] = bf16(x[b, j] + bf16(r[b, j] * *s_dev)), B samples of n elements, batch strides in elements
 int fluxmi_k_add_scaled(void* x, long long x_bstride, const void* r, long long r_bstride, const float* s_dev, int B, long long n, hipStream_t s);
 // IP-Adapter term of a double block (ip_attention.hip; include/fluxmi.h, fluxmi_ip_attention): scale == NULL writes o, else x += bf16(o * scale[b])

@@ -697,7 +697,8 @@ class FluxPipeline:
                  sigma_schedule: Optional[str] = None, sigmas=None, eta: float = 1.0, s_noise: float = 1.0, noise_seed: Optional[int] = None,
                  ip_adapter_image=None, ip_adapter_image_embeds: Optional[torch.Tensor] = None, ip_adapter_scale=1.0,
                  negative_ip_adapter_image=None, negative_ip_adapter_scale=1.0, guidance_mode: str = "cfg", guidance_rescale: float = 0.0,
-                 apg_eta: float = 1.0, apg_norm_threshold: float = 0.0, apg_momentum: float = 0.0, zero_init_steps: int = 0):
+                 apg_eta: float = 1.0, apg_norm_threshold: float = 0.0, apg_momentum: float = 0.0, zero_init_steps: int = 0,
+                 on_step=None, preview_every: int = 0, preview_factors=None):
         """`reference_image` (FLUX.1 Kontext [dev] instruction editing): an image the prompt describes an edit of, in any form `init_image`
         takes; see prepare_kontext_reference.  Composes with `init_image` / `strength` unchanged.
         FLUX.1 Fill [dev] (a model with 320 conditioning channels): `init_image` is the image to inpaint and `mask_image` (white =
@@ -789,7 +790,31 @@ class FluxPipeline:
         without guidance (no negative prompt, or true_cfg_scale <= 1) is refused.  APG's running difference starts at 0 in front of every
         guided denoise call (one per request unless a ControlNet interval cuts the guided slice) and advances once per evaluation.
         Composes with everything a negative prompt composes with, step caching included.  Parity with diffusers' code is unpinned (the
-        formulas of include/fluxmi.h are the definition) and image quality on real FLUX weights is NOT established here."""
+        formulas of include/fluxmi.h are the definition) and image quality on real FLUX weights is NOT established here.
+        `on_step(info)`: progress, live previews and cancellation.  Called once per model evaluation, in order, from this thread, behind the
+        GPU's work on that evaluation, with info = {"evaluation", "num_evaluations", "step", "preview"}: `step` is the request's step the
+        evaluation belongs to (a sampler's step_of_eval; Heun and midpoint evaluate twice per step) and `preview` a uint8 array
+        [num_images, height / 8, width / 8, 3] -- the denoised estimate x - t v of that evaluation projected 16 -> 3 by one more launch in
+        front of the update (csrc/preview.hip) -- at the evaluations with evaluation % preview_every == 0, None elsewhere (always None
+        with preview_every = 0).  The numbering continues across the denoise calls `true_cfg_interval` or a ControlNet interval cuts the
+        request into.  Returning False cancels: the engine stops launching (at most two evaluations run on), and generate raises
+        fluxmi.GenerationCancelled, which carries the evaluations run; an exception raised in on_step surfaces here the same way.
+        `preview_factors` = ([16][3], [3]) in decoded-latent space; default: the config's preview_factors / preview_bias, else a least-squares
+        fit against this pipeline's VAE, made on first use and cached (util.fit_preview_factors).  preview_every > 0 without on_step is
+        refused, both are refused under a process group and for more images than one engine pass holds.  Without them the request is
+        today's, launch for launch.  Composes with everything else."""
+        if isinstance(preview_every, bool) or not isinstance(preview_every, int) or preview_every < 0:
+            raise ValueError(f"fluxmi: preview_every={preview_every!r}: expected an integer >= 0 (0 = no previews)")
+        if on_step is not None and not callable(on_step):
+            raise ValueError("fluxmi: on_step must be callable")
+        if preview_every > 0 and on_step is None:
+            raise ValueError("fluxmi: preview_every > 0 needs on_step (the callback that receives the previews)")
+        if preview_factors is not None and preview_every == 0:
+            raise ValueError("fluxmi: preview_factors given with preview_every = 0")
+        if on_step is not None and fdist.world_size() > 1:
+            raise ValueError("fluxmi: on_step / preview_every are refused under a process group (the per-evaluation host waits would stall its "
+                             "collectives)")
+        preview_proj = self.preview_projection(preview_factors) if preview_every > 0 else None
         if guidance_mode not in GUIDANCE_MODES:
             raise ValueError(f"fluxmi: guidance_mode={guidance_mode!r}: expected one of {GUIDANCE_MODES}")
         try:
@@ -1109,6 +1134,7 @@ class FluxPipeline:
                         i = j
                 segs = cut
             evals_done = 0  # model evaluations of the request in front of the segment (zero_init_steps counts them)
+            plan = []  # the denoise calls of the request: (a, b, keywords), every keyword but those that count evaluations
             for a, b, kw in segs:
                 if a < b or n == 0:
                     if shaping is not None and "neg_txt" in kw:
@@ -1124,9 +1150,13 @@ class FluxPipeline:
                             kw["solver_noise"] = (noise_ids, a)
                     elif sampler != "euler":  # ... and the program of its slice of the schedule
                         kw = dict(kw, solver=solvers.build_program(sampler, timesteps[a:b + 1]))
-                    latents = self.model.denoise(latents, img_ids, txt, txt_ids, vec, timesteps[a:b + 1], guidance=guidance, use_graph=use_graph,
-                                                 **cond, **kw, **cache)
+                    plan.append((a, b, kw, evals_done))
                     evals_done += len(kw["solver"].coef) if "solver" in kw else b - a
+            for a, b, kw, off in plan:
+                if on_step is not None:  # the request's numbering continues across its denoise calls
+                    kw = dict(kw, preview=self._preview_call(on_step, preview_proj, preview_every, height, width, a, off, evals_done, kw.get("solver")))
+                latents = self.model.denoise(latents, img_ids, txt, txt_ids, vec, timesteps[a:b + 1], guidance=guidance, use_graph=use_graph,
+                                             **cond, **kw, **cache)
         if world > 1:
             latents = fdist.gather_latents(latents, num_images, dst=0)
             if latents is None:  # only the gather rank decodes / returns the images
@@ -1138,6 +1168,44 @@ class FluxPipeline:
         # output_type "uint8": the [B, H, W, 3] array into_bytes hands to the JPEG encoder (the pixel-parity tests compare it)
         out = self.to_uint8(img_px) if output_type == "uint8" else self.into_bytes(img_px, jpeg_quality=jpeg_quality)
         return (out, seed) if return_seed else out
+
+    def _preview_call(self, on_step, proj, every: int, height: int, width: int, step0: int, eval_offset: int, n_evaluations: int, solver):
+        """the PreviewCall of one denoise call of a request: evaluation numbers are the request's, `step` goes through the slice's solver"""
+        from modules.flux_model import PreviewCall
+
+        def callback(evaluation, num_evaluations, rgb):
+            j = evaluation - eval_offset
+            step = step0 + (int(solver.step_of_eval[j]) if solver is not None else j)
+            return on_step({"evaluation": evaluation, "num_evaluations": num_evaluations, "step": step, "preview": rgb})
+
+        return PreviewCall(proj, (math.ceil(height / 16), math.ceil(width / 16)), every, eval_offset, n_evaluations, callback)
+
+    def preview_projection(self, preview_factors=None) -> list:
+        """The 51 floats the engine's preview launch reads, for the model's latent: `preview_factors` = (M [16][3], bias [3]) in
+        decoded-latent space, else the config's, else the cached least-squares fit against this pipeline's VAE; the VAE's scale_factor /
+        shift_factor are folded in (util.fold_preview_factors)."""
+        from util import fit_preview_factors, fold_preview_factors
+
+        ae = self.config.ae_params
+        if preview_factors is None and getattr(self.config, "preview_factors", None) is not None:
+            preview_factors = (self.config.preview_factors, self.config.preview_bias or [0.0, 0.0, 0.0])
+        if preview_factors is None:
+            if getattr(self, "_preview_fit", None) is None:
+                if self.ae is None:
+                    raise ValueError("fluxmi: preview_every > 0 needs preview_factors (or the config's) when no autoencoder is loaded")
+                # a few seeded N(0, 1) latents through the native decoder, area-averaged 8 x 8 to latent resolution
+                g = torch.Generator().manual_seed(0)
+                z = torch.randn(4, ae.z_channels, 16, 16, generator=g).to(self.device_ae)
+                with torch.autocast(device_type=self.device_ae.type, dtype=torch.bfloat16, cache_enabled=False):
+                    px = self.ae.decode(z).float()
+                f = px.shape[-1] // z.shape[-1]
+                self._preview_fit = fit_preview_factors(z.float() / ae.scale_factor + ae.shift_factor, torch.nn.functional.avg_pool2d(px, f))
+            preview_factors = self._preview_fit
+        try:
+            m, b = preview_factors
+            return fold_preview_factors(m, b, ae.scale_factor, ae.shift_factor)
+        except (TypeError, ValueError):
+            raise ValueError("fluxmi: preview_factors: expected ([16][3], [3]): the matrix and the bias in decoded-latent space") from None
 
     def vae_decode(self, x: torch.Tensor, height: int, width: int) -> torch.Tensor:
         x = self.unpack(x.to(self.device_ae).float(), height, width)

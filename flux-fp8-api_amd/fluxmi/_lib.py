@@ -138,6 +138,9 @@ _SIGS = {
     "fluxmi_engine_set_solver": ([vp, C.POINTER(C.c_double), C.POINTER(i32), i32], i32),
     "fluxmi_engine_set_solver_noise": ([vp, C.POINTER(C.c_uint32), i32, i32], i32),
     "fluxmi_engine_set_guidance": ([vp, C.POINTER(f32), i32], i32),
+    "fluxmi_latent_preview": ([vp, vp, vp, vp, vp, vp, vp, vp, i32, i64, i64, i32, i32, i32, i32, vp], i32),
+    "fluxmi_engine_set_preview": ([vp, C.POINTER(f32), i32, i32, i32, i32, i32, vp, vp], i32),
+    "fluxmi_engine_preview_stats": ([vp, C.POINTER(i64), C.POINTER(i32)], i32),
     "fluxmi_engine_step_cache_log": ([vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(f32), C.POINTER(C.c_ubyte), i32], i32),
     "fluxmi_engine_run_phase": ([vp, i32, i32, i32, i32, vp], i32),
     "fluxmi_controlnet_num_linears": ([C.POINTER(ModelDesc)], i32),
@@ -148,6 +151,10 @@ _SIGS = {
     "fluxmi_engine_set_ip_adapter": ([vp, vp, vp, i32, i32, C.POINTER(f32), vp], i32),
 }
 AMAX_HOOK = C.CFUNCTYPE(i32, vp, i32, i32, vp)
+STEP_HOOK = C.CFUNCTYPE(i32, vp, i32, i32, vp, i32, i32, i32)  # fluxmi_step_hook_t: user, evaluation, n_evaluations, rgb, images, height, width
+PREVIEW_DEPTH = 2           # FLUXMI_PREVIEW_DEPTH
+PREVIEW_SLOTS = PREVIEW_DEPTH + 1
+CANCELLED = 3               # FLUXMI_CANCELLED
 EXPORTS = sorted(list(_SIGS) + ["fluxmi_last_error"])
 
 lib.fluxmi_last_error.restype = C.c_char_p

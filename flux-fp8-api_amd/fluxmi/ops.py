@@ -660,3 +660,51 @@ def cfg_euler(img: torch.Tensor, pred: torch.Tensor, dt: float, scale: float) ->
     call("fluxmi_cfg_euler", _p(img), _p(pred), _p(dts), None, _p(sc), img.shape[0] // 2, img.shape[1], pred.shape[1], img.shape[2], pred.shape[2],
          _stream())
     return img
+
+
+# ---- latent preview (fluxmi_latent_preview; include/fluxmi.h) ---------------------------------------------------------------------------
+def preview_proj(factors, bias=None) -> list:
+    """The 51 floats the kernel reads: M[16][3] row-major, then bias[3] (zeros when None)."""
+    m = [[float(v) for v in row] for row in factors]
+    b = [0.0, 0.0, 0.0] if bias is None else [float(v) for v in bias]
+    if len(m) != 16 or any(len(r) != 3 for r in m) or len(b) != 3:
+        raise ValueError("preview_proj: factors [16][3] and bias [3]")
+    return [v for r in m for v in r] + b
+
+
+def latent_preview(x: torch.Tensor, pred: torch.Tensor, t, proj, grid, scale=None, step=None, ctl=None,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The denoised estimate x - t v of one evaluation projected to RGB (fluxmi_latent_preview): x bf16 [B (2B guided), img_rows, c_in],
+    pred bf16 [B (2B guided), pred_rows, 64], `grid` = (h, w) tokens, proj = the 51 floats (a list or an fp32 device tensor).  `t`: a float,
+    or an fp32 device table indexed by `step` (an int32 device scalar; None = entry 0).  `scale` (a float or an fp32 device scalar) selects
+    the guided form.  `ctl` = (every, eval_offset) or an int32 device tensor [2]; None = (1, 0): every evaluation, slot = step % PREVIEW_SLOTS.
+    Returns `out`, uint8 [PREVIEW_SLOTS, B, 2 h, 2 w, 3]: only the slot the launch selects is written."""
+    _req(x, torch.bfloat16, "x")
+    _req(pred, torch.bfloat16, "pred")
+    if x.ndim != 3 or pred.ndim != 3 or x.shape[0] != pred.shape[0] or not (x.is_contiguous() and pred.is_contiguous()):
+        raise ValueError(f"latent_preview: x {tuple(x.shape)} / pred {tuple(pred.shape)} must be contiguous [B, rows, channels] of one batch")
+    dev = x.device
+    guided = scale is not None
+    if guided and x.shape[0] % 2:
+        raise ValueError("latent_preview: a guided call takes [2B, ...]: prompt branches first, then the negative branches")
+    B = x.shape[0] // 2 if guided else x.shape[0]
+    h, w = int(grid[0]), int(grid[1])
+    f32t = lambda v, name: _req(v if isinstance(v, torch.Tensor) else torch.tensor([float(u) for u in (v if isinstance(v, (list, tuple)) else [v])],
+                                                                                    dtype=torch.float32, device=dev), torch.float32, name)
+    ts, prj = f32t(t, "t"), f32t(proj, "proj")
+    if prj.numel() != 51 or not prj.is_contiguous():
+        raise ValueError("latent_preview: proj holds 51 floats: M[16][3], then bias[3]")
+    sc = f32t(scale, "scale") if guided else None
+    st = None if step is None else _req(step if isinstance(step, torch.Tensor) else torch.tensor([int(step)], dtype=torch.int32, device=dev),
+                                        torch.int32, "step")
+    ct = None if ctl is None else _req(ctl if isinstance(ctl, torch.Tensor) else torch.tensor([int(v) for v in ctl], dtype=torch.int32, device=dev),
+                                       torch.int32, "ctl")
+    if ct is not None and ct.numel() != 2:
+        raise ValueError("latent_preview: ctl holds {every, eval_offset}")
+    if out is None:
+        out = torch.zeros((_lib.PREVIEW_SLOTS, B, 2 * h, 2 * w, 3), dtype=torch.uint8, device=dev)
+    _req(out, torch.uint8, "out")
+    if out.numel() != _lib.PREVIEW_SLOTS * B * 4 * h * w * 3 or not out.is_contiguous():
+        raise ValueError(f"latent_preview: out {tuple(out.shape)} must be contiguous uint8 [{_lib.PREVIEW_SLOTS}, {B}, {2 * h}, {2 * w}, 3]")
+    call("fluxmi_latent_preview", _p(x), _p(pred), _p(ts), _p(st), _p(sc), _p(prj), _p(ct), _p(out), B, x.shape[1], pred.shape[1], x.shape[2], pred.shape[2], h, w, _stream())
+    return out

@@ -25,10 +25,17 @@ import torch
 from pydantic import BaseModel, Field
 from torch import Tensor, nn
 
-from fluxmi import _lib, ops, solvers
+from fluxmi import GenerationCancelled, _lib, ops, solvers
 
 if TYPE_CHECKING:
     from util import ModelSpec
+
+
+# Progress, previews and cancellation of one Flux.denoise call (include/fluxmi.h, fluxmi_engine_set_preview).  proj: the 51 floats of
+# ops.preview_proj (None with every = 0); grid: (h, w) tokens of the stepped rows; every: 0 = progress and cancellation only, k > 0 = a preview
+# at every evaluation g with g % k == 0; eval_offset / n_evaluations: this call's first evaluation within the request and the request's
+# total; callback(evaluation, n_evaluations, rgb) with rgb a uint8 numpy array [images, 2 h, 2 w, 3] or None -- returning False cancels.
+PreviewCall = namedtuple("PreviewCall", ["proj", "grid", "every", "eval_offset", "n_evaluations", "callback"])
 
 
 class FluxParams(BaseModel):  # reference flux_model.py:24-36
@@ -422,6 +429,59 @@ class Flux(nn.Module):
             raise ValueError(f"guidance_shaping: norm_threshold {rho}, zero_init_steps {zi} and step_offset {off} must be >= 0")
         return ops.guidance_params(cfg_scale, mode, phi, eta, rho, mu, zi), off
 
+    @staticmethod
+    def _check_preview(preview):
+        if preview is None:
+            return None
+        if not callable(preview.callback):
+            raise ValueError("preview: callback must be callable")
+        every, off, n = int(preview.every), int(preview.eval_offset), int(preview.n_evaluations)
+        if every < 0 or off < 0 or n < 0:
+            raise ValueError(f"preview: every {every}, eval_offset {off} and n_evaluations {n} must be >= 0")
+        proj = None
+        if every > 0:
+            proj = [float(v) for v in preview.proj]
+            if len(proj) != 51 or not all(math.isfinite(v) for v in proj):
+                raise ValueError("preview: proj holds 51 finite floats (ops.preview_proj)")
+            if len(preview.grid) != 2:
+                raise ValueError("preview: grid = (h, w) tokens")
+        return PreviewCall(proj, tuple(int(v) for v in preview.grid) if every > 0 else (0, 0), every, off, n, preview.callback)
+
+    def _set_preview(self, preview):
+        """after _prepare, under the lock: the step hook of this call (_check_preview) -> the state that keeps the ctypes callback alive and
+        carries an exception out of it (ctypes would swallow it), or None"""
+        if preview is None:
+            return None
+        import numpy as np
+
+        state = {"error": None, "cb": None}
+
+        def hook(user, evaluation, n_evaluations, rgb, images, height, width):
+            try:
+                arr = None
+                if rgb:
+                    buf = (C.c_ubyte * (images * height * width * 3)).from_address(rgb)
+                    arr = np.frombuffer(buf, dtype=np.uint8).reshape(images, height, width, 3).copy()  # the pinned buffer is the engine's
+                return 1 if preview.callback(evaluation, n_evaluations, arr) is False else 0
+            except BaseException as e:  # an exception must not cross the C ABI: cancel, re-raise behind the engine call
+                state["error"] = e
+                return 1
+
+        state["cb"] = _lib.STEP_HOOK(hook)
+        proj = (C.c_float * 51)(*preview.proj) if preview.proj is not None else None
+        _lib.call("fluxmi_engine_set_preview", self._engine, proj, preview.grid[0], preview.grid[1], preview.every, preview.eval_offset,
+                  preview.n_evaluations, state["cb"], None)
+        return state
+
+    def preview_stats(self):
+        """(graph captures of the engine since it was created, evaluations the last denoise call launched): read-only, for tests"""
+        if self._engine is None:
+            return 0, 0
+        with self._lock:
+            cap, ran = C.c_longlong(0), C.c_int(0)
+            _lib.call("fluxmi_engine_preview_stats", self._engine, C.byref(cap), C.byref(ran))
+        return cap.value, ran.value
+
     def _set_guidance(self, shaping):
         """after _prepare, under the lock: the shaping state of this call (_check_guidance_shaping), or None = off.  Every set call with a
         state starts APG's running difference at 0."""
@@ -743,7 +803,7 @@ class Flux(nn.Module):
                 neg_y: Tensor | None = None, cfg_scale: float = 1.0, cache_threshold: float = 0.0, cache_max_hits: int = 0,
                 attn_groups: Tensor | None = None, inpaint_x0: Tensor | None = None, inpaint_noise: Tensor | None = None,
                 inpaint_mask: Tensor | None = None, inpaint_thresholds=None, controlnet=None, solver=None, solver_noise=None,
-                ip_adapter=None, guidance_shaping: dict | None = None) -> Tensor:
+                ip_adapter=None, guidance_shaping: dict | None = None, preview: PreviewCall | None = None) -> Tensor:
         """The Euler loop of FluxPipeline.generate (reference flux_pipeline.py:619-651) run natively: calibrating
         steps unfused, every later step one replay of a captured hipGraph.  Returns the final latent tokens.
         FLUX.1 Kontext: with `img_cond_seq` / `img_cond_seq_ids` the reference tokens join every step's forward and are never stepped; the
@@ -790,8 +850,18 @@ class Flux(nn.Module):
         = the number of leading model EVALUATIONS of the request whose prediction is replaced by 0, counted from `step_offset` for a call
         that continues a request; Heun and midpoint evaluate twice per step).  The formulas are those of include/fluxmi.h
         (fluxmi_guidance_combine).  The values are device data of one captured graph; shaped versus unshaped is a graph kind.  None =
-        today's call, launch for launch."""
+        today's call, launch for launch.
+        `preview`: a PreviewCall.  Its callback is called once per model evaluation, in order, from this thread, behind the GPU's work on
+        that evaluation; with `every` > 0 one more launch in front of every update (csrc/preview.hip) projects the denoised estimate
+        x - t v to uint8 RGB at latent resolution, and the callback receives it at the evaluations `every` selects.  The host loop then
+        stays at most two evaluations ahead of the GPU and the call is synchronous.  Returning False from the callback stops the launches:
+        the engine finishes what it launched (cancelling at evaluation k runs min(n, k + 2)), the calibration counters advance by what
+        ran, and GenerationCancelled is raised; an exception raised in the callback cancels the same way and is re-raised.  Refused when
+        the batch needs more than one engine pass and under an amax exchange (a process group).  None = today's call, launch for launch."""
         n_user = len(timesteps) - 1
+        preview = self._check_preview(preview)
+        if preview is not None and getattr(self, "_amax_xchg", None) is not None:
+            raise ValueError("fluxmi: preview / progress / cancellation are refused under an amax exchange (a process group)")
         if solver is not None:
             if cache_threshold and float(cache_threshold) > 0:
                 raise ValueError("fluxmi: a sampler other than euler does not combine with cache_threshold > 0 (the step cache compares "
@@ -836,6 +906,8 @@ class Flux(nn.Module):
             neg_y = neg_y.to(device=y.device).expand(B, -1)
         cap = self.MAX_ENGINE_BATCH // 2 if guided else self.MAX_ENGINE_BATCH
         stream = self._with_channels(img, img_cond, img_cond_seq) if img.shape[0] <= cap else None
+        if img.shape[0] > cap and preview is not None:
+            raise ValueError(f"fluxmi: preview / progress / cancellation need a batch that runs in one engine pass (at most {cap} images here)")
         if img.shape[0] > cap:
             # the engine takes at most 32 samples per pass (workspace / modulation-table size); the reference has no num_images limit, so
             # larger batches run as consecutive passes (samples never interact).  EQUAL passes: the engine re-allocates its workspace and
@@ -904,15 +976,25 @@ class Flux(nn.Module):
             self._set_guidance(shaping)
             net = self._attach_controlnet(cn, img.device)
             ip_set = False
+            pv, rc, ran = None, 0, 0
             try:
                 ip_set = self._set_ip_adapter(ip, img.device)
+                pv = self._set_preview(preview)
                 if guided:
-                    _lib.call("fluxmi_engine_denoise_cfg", self._engine, ops._p(img), ops._p(txt), ops._p(y), float(guidance), float(cfg_scale), ts,
-                              len(timesteps) - 1, C.byref(t_io), int(use_graph), ops._stream())
+                    rc = _lib.lib.fluxmi_engine_denoise_cfg(self._engine, ops._p(img), ops._p(txt), ops._p(y), float(guidance), float(cfg_scale), ts,
+                                                            len(timesteps) - 1, C.byref(t_io), int(use_graph), ops._stream())
                 else:
-                    _lib.call("fluxmi_engine_denoise", self._engine, ops._p(img), ops._p(txt), ops._p(y), float(guidance), ts,
-                              len(timesteps) - 1, C.byref(t_io), int(use_graph), ops._stream())
+                    rc = _lib.lib.fluxmi_engine_denoise(self._engine, ops._p(img), ops._p(txt), ops._p(y), float(guidance), ts,
+                                                        len(timesteps) - 1, C.byref(t_io), int(use_graph), ops._stream())
+                if rc != _lib.CANCELLED or pv is None:
+                    _lib.check(rc)
+                else:
+                    cap_ran = (C.c_longlong(0), C.c_int(0))
+                    _lib.call("fluxmi_engine_preview_stats", self._engine, C.byref(cap_ran[0]), C.byref(cap_ran[1]))
+                    ran = cap_ran[1].value
             finally:
+                if pv is not None:
+                    _lib.call("fluxmi_engine_set_preview", self._engine, None, 0, 0, 0, 0, 0, None, None)
                 self._clear_ip_adapter(ip_set)
                 self._release_controlnet(net)
                 if solver is not None:
@@ -921,6 +1003,10 @@ class Flux(nn.Module):
                     self._set_guidance(None)
             if trial is not None:
                 self._advance_calibration(t_io.value)
+        if pv is not None and pv["error"] is not None:
+            raise pv["error"]
+        if rc == _lib.CANCELLED:
+            raise GenerationCancelled(preview.eval_offset + ran, preview.n_evaluations)
         if self.in_channels != self.out_channels:
             return img[..., :self.out_channels].contiguous()
         return img[:, :Li].contiguous() if Lc else img

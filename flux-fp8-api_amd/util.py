@@ -77,8 +77,37 @@ class ModelSpec(BaseModel):  # reference util.py:38-79 (unknown JSON keys are ig
     # (CLIPVisionModelWithProjection: a local HF directory or .safetensors file).  Nothing is downloaded.
     ip_adapter_path: str | None = None
     clip_vision_path: str | None = None
+    # live previews (FluxPipeline.generate(preview_every=...)): the 16 -> 3 projection of the decoded latent, [16][3] and [3]; None = fitted
+    # once per pipeline against the loaded VAE (fit_preview_factors)
+    preview_factors: Optional[list] = None
+    preview_bias: Optional[list] = None
 
     model_config: ConfigDict = {"arbitrary_types_allowed": True, "use_enum_values": True}
+
+
+def fit_preview_factors(latents, rgb):
+    """Least-squares 16 -> 3 projection of a latent to the RGB its decoder gives: latents [N, 16, h, w] (the decoded-latent space, z /
+    scale_factor + shift_factor), rgb [N, 3, h, w] (the decoder's output area-averaged to latent resolution) -> (M [16][3], bias [3]) as
+    nested lists, minimising |bias + M^T z - rgb|^2 over all pixels; float64 on the host."""
+    import numpy as np
+
+    z = np.asarray(torch.as_tensor(latents).detach().double().cpu().numpy(), dtype=np.float64)
+    y = np.asarray(torch.as_tensor(rgb).detach().double().cpu().numpy(), dtype=np.float64)
+    if z.ndim != 4 or y.ndim != 4 or z.shape[1] != 16 or y.shape[1] != 3 or z.shape[0] != y.shape[0] or z.shape[2:] != y.shape[2:]:
+        raise ValueError(f"fit_preview_factors: latents {z.shape} / rgb {y.shape}: expected [N, 16, h, w] and [N, 3, h, w]")
+    A = np.concatenate([z.transpose(0, 2, 3, 1).reshape(-1, 16), np.ones((z.shape[0] * z.shape[2] * z.shape[3], 1))], 1)
+    sol, *_ = np.linalg.lstsq(A, y.transpose(0, 2, 3, 1).reshape(-1, 3), rcond=None)
+    return sol[:16].tolist(), sol[16].tolist()
+
+
+def fold_preview_factors(factors, bias, scale_factor: float, shift_factor: float) -> list:
+    """(M, bias) in decoded-latent space -> the 51 fp32-bound floats the engine reads for the MODEL's latent z (decoded = z / scale_factor +
+    shift_factor):  M' = M / scale_factor,  bias' = bias + shift_factor * sum_c M[c]; M' row-major, then bias'."""
+    m = [[float(v) for v in row] for row in factors]
+    b = [float(v) for v in bias]
+    if len(m) != 16 or any(len(r) != 3 for r in m) or len(b) != 3:
+        raise ValueError("preview factors: expected a [16][3] matrix and a [3] bias")
+    return [v / float(scale_factor) for r in m for v in r] + [b[k] + float(shift_factor) * sum(r[k] for r in m) for k in range(3)]
 
 
 def parse_device(device) -> torch.device:

@@ -471,6 +471,33 @@ int fluxmi_guidance_moments(const void* pred, const float* r, float* part, int B
 int fluxmi_guidance_combine(void* pred, float* r, const float* part, const float* params, const int* step, const int* step_offset,
                             float* coef_out, int B, long long N, void* stream);
 
+/* ---- latent preview -------------------------------------------------------------------
+ * The denoised estimate of ONE model evaluation, projected to RGB at latent resolution (csrc/preview.hip).  x: bf16 [B (2B guided), img_rows,
+ * c_in], the model input of the evaluation -- only the leading pred_rows rows of each sample and the leading c_out = 64 channels of a row are
+ * read (Kontext's reference rows and Fill / Depth / Canny's conditioning channels trail them).  pred: bf16, dense [B (2B guided), pred_rows,
+ * 64]; scale != NULL (DEVICE fp32 scalar) is the guided form: sample b is c (the prompt branch), sample B + b is u, and only the B prompt
+ * samples produce images.  ts: DEVICE fp32 table, step: DEVICE int (NULL = 0); t = ts[*step].  proj: DEVICE float [51] = M[16][3], then
+ * bias[3].  ctl: DEVICE int [2] = {every, eval_offset} (NULL = {1, 0}).  out: uint8 [FLUXMI_PREVIEW_SLOTS][B][2 h][2 w][3].
+ *
+ * For image b, token r = ty * w + tx of the h x w token grid (h * w == pred_rows), sub-pixel sub = py * 2 + px and latent channel c in 0..15
+ * the packed column is c * 4 + sub (FluxPipeline.unpack's layout).  In fp32, every operation rounded once, fma = one fused multiply-add:
+ *   v    = pred                                  plain
+ *   v    = fma(s, c - u, u)                      guided: the subtraction rounded on its own, s = *scale
+ *   x0_c = fma(-t, v, x)
+ *   a_k  = bias_k;  a_k = fma(M[c][k], x0_c, a_k)  for c = 0, 1, .., 15 in this order            (k = 0, 1, 2)
+ *   q    = rint(fma(0.5, a_k, 0.5) * 255)        the product rounded on its own, rint = round half to even
+ *   out[slot][b][2 ty + py][2 tx + px][k] = uint8(q > 0 ? (q < 255 ? q : 255) : 0)               NaN -> 0
+ * With g = eval_offset + *step the launch writes nothing unless every > 0 and g % every == 0, and then writes slot
+ * (g / every) % FLUXMI_PREVIEW_SLOTS; every other slot keeps its bytes.  every and eval_offset are device data: one captured graph serves
+ * every cadence and every slice of a request.  One thread per token, sixteen (guided: twenty-four) 16-byte loads -- the token's 128 contiguous
+ * bytes of x and of pred -- and twelve byte stores; no LDS, no atomics.  An image's bytes depend on its own tokens only.
+ * Refused: c_out != 64, h * w != pred_rows, img_rows < pred_rows, c_in < 64 or no multiple of 8, x / pred not 16-byte aligned. */
+#define FLUXMI_PREVIEW_DEPTH 2                          /* evaluations the host loop of a hooked denoise call may be ahead of the GPU */
+#define FLUXMI_PREVIEW_SLOTS (FLUXMI_PREVIEW_DEPTH + 1) /* slots of the preview ring (fluxmi_engine_set_preview has the argument) */
+int fluxmi_latent_preview(const void* x, const void* pred, const float* ts, const int* step, const float* scale, const float* proj,
+                          const int* ctl, void* out, int B, long long img_rows, long long pred_rows, int c_in, int c_out, int h, int w,
+                          void* stream);
+
 /* ---- first-block step cache: the streaming passes --------------------------------------
  * B samples of n bf16 elements each (n = cached rows x hidden, n %% 8 == 0).  The `x` side is the residual stream: the pointer is the first
  * cached row of sample 0, x_bstride the batch stride in elements; every other tensor is dense [B, n].  16-byte accesses; workgroup c of a
@@ -681,6 +708,43 @@ int fluxmi_engine_set_solver_noise(fluxmi_engine_t* e, const unsigned* ids_host,
  * fluxmi_engine_denoise call does not consult the state.  params_host == NULL switches it off; a prepare that re-allocates the workspace
  * does too.  A request without shaping allocates and launches exactly what it did before. */
 int fluxmi_engine_set_guidance(fluxmi_engine_t* e, const float* params_host, int step_offset);
+/* Progress, live previews and cancellation for the following fluxmi_engine_denoise / _denoise_cfg calls on the PREPARED
+ * shape, until cleared.  hook(user, evaluation, n_evaluations, rgb, images, height, width) is called on the caller's thread once per model
+ * evaluation of those calls, in order, AFTER the GPU has finished that evaluation: evaluation = eval_offset + the call's step index,
+ * n_evaluations as given here (the whole request's, so a request cut into several denoise calls continues its numbering like
+ * fluxmi_engine_set_solver_noise's eval_offset), rgb = uint8 [images][height = 2 h][width = 2 w][3] in an engine-owned pinned buffer that is
+ * valid until the hook returns, or NULL at an evaluation without a preview.  images = the caller's images (the prepared batch, half of it
+ * for a guided call).  h x w is the token grid of the stepped rows; proj51_host = the 51 floats of fluxmi_latent_preview.
+ *   every > 0: fluxmi_latent_preview is launched in front of whatever update the evaluation has -- behind guidance shaping, in the calibrating
+ *              steps, the eager warm step, the plain piece and both tails of a step-cached step alike -- and evaluation g has a preview iff
+ *              g % every == 0.  Previewed versus not is a kind of step graph like guided versus plain; every, eval_offset and the factors
+ *              are device data, so ONE graph serves every cadence and every slice of a request.
+ *   every = 0: progress and cancellation only: nothing is allocated, captured or launched beyond events.
+ *   hook = NULL clears the state (the other arguments are ignored); a prepare that re-allocates the workspace does too.  A request without
+ *   the state allocates, captures and launches exactly what it did before.
+ * Look-ahead: with a hook set the host loop stays at most FLUXMI_PREVIEW_DEPTH evaluations ahead of the GPU.  Before launching evaluation
+ * i >= DEPTH it waits on the event recorded behind evaluation i - DEPTH and delivers every evaluation up to i - DEPTH not yet delivered; after
+ * the last launch it waits for and delivers the rest.  A HOOKED DENOISE CALL IS THEREFORE SYNCHRONOUS: when it returns, every evaluation has
+ * finished and been delivered (the copy of the latent back into img is still only enqueued on the caller's stream).  Delivery copies the slot
+ * to the pinned buffer on a private stream and waits for that copy.  Since the delivery of evaluation k precedes the launch of k + DEPTH, at
+ * most the previews of evaluations k + 1 .. k + DEPTH can be written while k's is unread: FLUXMI_PREVIEW_SLOTS = DEPTH + 1 slots suffice for
+ * every cadence.  Device and pinned memory: SLOTS (pinned: 1) x images x 4 h w x 3 bytes, independent of the step count, counted in
+ * fluxmi_engine_workspace_bytes.
+ * Cancellation: a non-zero hook return stops the launches.  The engine waits for what was launched, copies the latent out as usual, updates
+ * *trial_index_inout for the calibrating steps that ran, delivers nothing further and returns FLUXMI_CANCELLED; fluxmi_last_error names the evaluations run.
+ * Cancelling at evaluation k of a call of n runs exactly min(n, k + DEPTH) of them (offsets aside).  There is no device-side abort.  The
+ * engine is fully usable afterwards: the next request computes what it computes on a fresh engine.
+ * Refused: on a ControlNet engine, under an attached amax-exchange hook (the host waits would stall a process group's collectives),
+ * every < 0, eval_offset < 0, h * w != the prepared shape's stepped rows, a model whose C_out != 64.  The state speaks of the prepared batch:
+ * the host wrapper refuses a batch that needs more than one engine pass.
+ * fluxmi_engine_preview_stats is read-only, for tests: *captures = the graph captures the engine has made since it was created,
+ * *evaluations_run = the evaluations the last denoise call launched (what a cancelled call ran; 0 after a call without a hook). */
+#define FLUXMI_CANCELLED 3
+typedef int (*fluxmi_step_hook_t)(void* user, int evaluation, int n_evaluations, const unsigned char* rgb /* NULL: no preview at this evaluation */,
+                                  int images, int height, int width);
+int fluxmi_engine_set_preview(fluxmi_engine_t* e, const float* proj51_host, int h, int w, int every, int eval_offset, int n_evaluations,
+                              fluxmi_step_hook_t hook, void* user);
+int fluxmi_engine_preview_stats(fluxmi_engine_t* e, long long* captures, int* evaluations_run);
 /* Test hook: phases [phase_from, phase_to] of ONE frozen forward on the engine's own buffers, mode 1 (fused) or 2 (unfused, frozen scales):
  *   0 img_in + txt_in on the request buffers "img_s" / "txt_s" (mode 1: the cached "txt_emb" of the last denoise call) + this step's
  *     modulation vectors out of the step-ahead table the last denoise call left (step = the request's step index, written to the device-side

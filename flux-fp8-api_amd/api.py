@@ -22,6 +22,9 @@ Same two POST endpoints, request fields, defaults and status codes:
              guidance_mode=None ("cfg" | "apg" | "cfg_zero_star"), guidance_rescale=None (0..1), apg_eta=None, apg_norm_threshold=None (>= 0),
              apg_momentum=None, zero_init_steps=None (>= 0) -- guidance shaping of true classifier-free guidance (FluxPipeline.generate; needs
              negative_prompt and true_cfg_scale > 1), each passed on only when set;
+             source_prompt=None (FlowEdit: the prompt that describes init_image; `prompt` is then the target), source_guidance=None,
+             edit_n_max=None (>= 0), edit_n_min=None (>= 0), edit_n_avg=None (>= 1) -- text-guided editing of init_image
+             (FluxPipeline.generate), each passed on only when set;
              stream=None, preview_every=None (>= 0) -- progress, live previews and cancellation, see below;
              a region with both or neither of box / mask, or a box outside 0 <= x0 < x1 <= 1, is a 422}
              ->  image/jpeg stream of FluxPipeline.generate(**args)                                               (reference api.py:54-86)
@@ -117,6 +120,11 @@ class GenerateArgs(BaseModel):
     apg_norm_threshold: Optional[float] = Field(default=None, ge=0.0)  # ... APG: clip the guidance difference to this norm (0 = off)
     apg_momentum: Optional[float] = None  # ... APG: the running difference's momentum (0 = off)
     zero_init_steps: Optional[int] = Field(default=None, ge=0)  # ... CFG-Zero*'s zero-init: the first k model evaluations predict 0
+    source_prompt: Optional[str] = None  # FlowEdit: the prompt that describes init_image; `prompt` is then the target prompt (FluxPipeline.generate)
+    source_guidance: Optional[float] = None  # ... the distilled guidance of the source branch (default: guidance, which the target branch takes)
+    edit_n_max: Optional[int] = Field(default=None, ge=0)  # ... the last edit_n_max steps are edited (default: every step)
+    edit_n_min: Optional[int] = Field(default=None, ge=0)  # ... the last edit_n_min of them as a plain Euler tail on the target prompt (default 0)
+    edit_n_avg: Optional[int] = Field(default=None, ge=1)  # ... model evaluations averaged per step (default 1)
     stream: Optional[bool] = None  # answer with application/x-ndjson progress lines and a final result line instead of the JPEG
     preview_every: Optional[int] = Field(default=None, ge=0)  # ... with a latent-resolution preview at every k-th model evaluation (0 = none)
 
@@ -181,7 +189,8 @@ def generate(args: GenerateArgs):
     select true classifier-free guidance, `cache_threshold` (+ `cache_max_hits`) first-block step caching, `controlnet_image` (+ `controlnet_conditioning_scale`,
     `control_mode`, `control_guidance_start` / `_end`) a FLUX ControlNet, `ip_adapter_image` / `ip_adapter_image_embeds` (+ `ip_adapter_scale`,
     `negative_ip_adapter_image`, `negative_ip_adapter_scale`) a FLUX IP-Adapter, `guidance_mode` / `guidance_rescale` / `apg_*` /
-    `zero_init_steps` guidance shaping of a guided request.  Without them the call is exactly the reference's."""
+    `zero_init_steps` guidance shaping of a guided request, `source_prompt` (+ `source_guidance`, `edit_n_max` / `_min` / `_avg`) a FlowEdit edit of
+    `init_image` towards `prompt`.  Without them the call is exactly the reference's."""
     kwargs = args.model_dump()
     stream = bool(kwargs.pop("stream", None))
     if kwargs.get("preview_every") is None:
@@ -193,7 +202,7 @@ def generate(args: GenerateArgs):
               "controlnet_conditioning_scale", "control_mode", "control_guidance_start", "control_guidance_end", "sampler", "sigma_schedule",
               "sigmas", "eta", "s_noise", "noise_seed", "ip_adapter_image", "ip_adapter_image_embeds", "ip_adapter_scale",
               "negative_ip_adapter_image", "negative_ip_adapter_scale", "guidance_mode", "guidance_rescale", "apg_eta", "apg_norm_threshold",
-              "apg_momentum", "zero_init_steps"):
+              "apg_momentum", "zero_init_steps", "source_prompt", "source_guidance", "edit_n_max", "edit_n_min", "edit_n_avg"):
         if kwargs.get(k) is None:
             kwargs.pop(k, None)
     if "ip_adapter_image_embeds" in kwargs:

@@ -251,6 +251,29 @@ int fluxmi_philox_normal(void* out, const unsigned* ids, int B, long long n_per_
   return fluxmi_k_philox_normal(out, ids, B, n_per_image, eval, raw, (hipStream_t)stream);
 }
 
+int fluxmi_flowedit_couple(void* img, const void* z, const void* x0, float t, float one_minus_t, const unsigned* ids, unsigned eval, int B,
+                           long long img_rows, long long pred_rows, int c_in, int c_out, void* stream) {
+  return fluxmi_k_flowedit_couple(img, z, x0, t, one_minus_t, ids, eval, B, img_rows, pred_rows, c_in, c_out, (hipStream_t)stream);
+}
+// acc == NULL is legal only for a row with first and apply set, and which row runs is device data: this entry (tests and tools; the engine
+// knows its program and calls the launcher) then reads *step and the row back -- two small synchronising copies -- before it launches
+int fluxmi_flowedit_step(void* img, const void* pred, void* z, float* acc, const void* x0, const float* coef, const int* ctl, const int* step,
+                         const unsigned* ids, const int* eval_offset, int B, long long img_rows, long long pred_rows, int c_in, int c_out,
+                         void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (!acc && ctl && ids && B > 0 && pred_rows > 0) {
+    int i = 0, row[2] = {0, 0};
+    if (step) FLUXMI_CHECK_HIP(hipMemcpyAsync(&i, step, 4, hipMemcpyDeviceToHost, s));
+    if (step) FLUXMI_CHECK_HIP(hipStreamSynchronize(s));
+    FLUXMI_REQUIRE(i >= 0, "flowedit_step: *step = %d < 0", i);
+    FLUXMI_CHECK_HIP(hipMemcpyAsync(row, ctl + 2 * (size_t)i, 8, hipMemcpyDeviceToHost, s));
+    FLUXMI_CHECK_HIP(hipStreamSynchronize(s));
+    FLUXMI_REQUIRE(row[0] != 0 && row[1] != 0, "flowedit_step: NULL acc, and row %d has first = %d, apply = %d (the fp32 accumulator is "
+                   "stored by a row without apply and read by a row without first)", i, row[0], row[1]);
+  }
+  return fluxmi_k_flowedit_step(img, pred, z, acc, x0, coef, ctl, step, ids, eval_offset, B, img_rows, pred_rows, c_in, c_out, s);
+}
+
 int fluxmi_fb_snapshot(const void* x, long long x_bstride, void* dst, int B, long long n, void* stream) {
   return fluxmi_k_fb_snapshot(x, x_bstride, dst, B, n, (hipStream_t)stream);
 }

@@ -55,6 +55,8 @@ struct StepGraphs {
   bool diff = false;    // ... and its differential form (the threshold table is a launch argument)
   bool solver = false;  // ... and the table-driven solver update (fluxmi_engine_set_solver): WHICH solver is device data, not a kind
   bool noise = false;   // ... and its form with the noise term (fluxmi_engine_set_solver_noise): seeds and the offset are device data
+  bool edit = false;    // ... and FlowEdit's update (fluxmi_engine_denoise_edit): tables, ids, offset and the guidance pair are device data ...
+  const void* fe_acc = nullptr;  // ... its fp32 accumulator is a launch argument: null until a program that averages has made the buffer
   bool shaped = false;  // guidance shaping (fluxmi_engine_set_guidance): two launches in front of the guided update; mode and values are device data
   bool previewed = false;  // the preview launch in front of the update (fluxmi_engine_set_preview, every > 0): cadence, offset and factors are device data ...
   int pv_h = 0, pv_w = 0;  // ... the token grid is a launch argument
@@ -183,6 +185,19 @@ struct fluxmi_engine {
   int gd_offset = 0;
   char* gd_mem = nullptr;
   size_t gd_bytes = 0;
+  // FlowEdit (fluxmi_engine_set_flow_edit / _denoise_edit): the host tables, ids, offset and guidance pair of the following
+  // edit calls.  Device side, three allocations dropped with the workspace: fe_mem = "fe_x0" (bf16 [B / 2, Lpred, C_out], filled by the set
+  // call) | "fe_tab" (coef fp32 [MAX_STEPS][4] | ctl int [MAX_STEPS][2] | ids uint32 [FLUXMI_ENGINE_MAX_BATCH][4] | the offset, staged through h_sched like the
+  // solver's), fe_zmem = "fe_z" made by the first edit call of a prepared shape, fe_accmem = "fe_acc" (fp32) made by the first edit call whose
+  // program has a row without first or apply.  Nothing of it without an edit request.  fe_call: the running denoise call is an edit call.
+  bool fe_on = false, fe_call = false, fe_need_acc = false;
+  int fe_B = 0, fe_n = 0, fe_eval_offset = 0;
+  float fe_gs = 0.f, fe_gt = 0.f;
+  std::vector<float> fe_coef;      // [fe_n][4]
+  std::vector<int> fe_ctl;         // [fe_n][2]
+  std::vector<unsigned> fe_ids;    // [fe_B][4]
+  char *fe_mem = nullptr, *fe_zmem = nullptr, *fe_accmem = nullptr;
+  size_t fe_bytes = 0, fe_zbytes = 0, fe_accbytes = 0;
   // ControlNet (fluxmi_controlnet_create / fluxmi_engine_attach_controlnet).  A net is an engine of its own kind
   // (is_cn): no final layer, the controlnet_* projections behind the trunk's linears, the residuals of a forward in its workspace buffer
   // "cn_res" [Nd + Ns][B, Li, H].  The main engine holds the attached net (cn) and the conditioning scale (d_cn_scale, device data).
@@ -1184,6 +1199,10 @@ void free_ws(E* e) {
   if (e->d_sol_coef) { hipFree(e->d_sol_coef); e->d_sol_coef = nullptr; e->d_sol_ctl = nullptr; }
   if (e->d_sol_ids) { hipFree(e->d_sol_ids); e->d_sol_ids = nullptr; e->sol_ids_bytes = 0; }
   e->sol_on = e->sol_noise = false;
+  if (e->fe_mem) { hipFree(e->fe_mem); e->fe_mem = nullptr; e->fe_bytes = 0; }
+  if (e->fe_zmem) { hipFree(e->fe_zmem); e->fe_zmem = nullptr; e->fe_zbytes = 0; }
+  if (e->fe_accmem) { hipFree(e->fe_accmem); e->fe_accmem = nullptr; e->fe_accbytes = 0; }
+  e->fe_on = false;
   if (e->gd_mem) { hipFree(e->gd_mem); e->gd_mem = nullptr; e->gd_bytes = 0; }
   e->gd_on = e->gd_zero_r = false;
   if (e->ip_mem) { hipFree(e->ip_mem); e->ip_mem = nullptr; e->ip_bytes = 0; }
@@ -1284,6 +1303,45 @@ int ensure_sol_ids(E* e) {
   e->sol_ids_bytes = bytes;
   e->bufs["sol_ids"] = Buf{(char*)e->d_sol_ids, bytes};
   return 0;
+}
+
+// FlowEdit's buffers of the prepared shape (like ensure_fb), for the B / 2 images an edit call of this shape steps: the init latent and the
+// device tables (made by the set call, which fills x0), the edit state, and the fp32 accumulator of a program that averages
+constexpr size_t FE_TAB_BYTES = (size_t)MAX_STEPS * 6 * 4 + (size_t)FLUXMI_ENGINE_MAX_BATCH * 16 + 4;
+int fe_alloc(E* e, char** mem, size_t* bytes, const char* const* names, const size_t* sizes, int n, bool zero, hipStream_t s) {
+  if (*mem) return 0;
+  size_t total = 0;
+  for (int i = 0; i < n; ++i) total += (sizes[i] + 255) & ~(size_t)255;
+  if (hipMalloc((void**)mem, total) != hipSuccess) {
+    (void)hipGetLastError();
+    *mem = nullptr;
+    fluxmi_set_error("engine_flow_edit: hipMalloc(%zu bytes) failed (%s)", total, names[0]);
+    return 2;
+  }
+  *bytes = total;
+  if (zero) FLUXMI_CHECK_HIP(hipMemsetAsync(*mem, 0, total, s));
+  size_t off = 0;
+  for (int i = 0; i < n; ++i) {
+    e->bufs[names[i]] = Buf{*mem + off, sizes[i]};
+    off += (sizes[i] + 255) & ~(size_t)255;
+  }
+  return 0;
+}
+size_t fe_elems(const E* e) { return (size_t)std::max(1, e->B / 2) * e->Lpred * c_out(e); }
+int ensure_fe_x0(E* e, hipStream_t s) {
+  const char* names[2] = {"fe_x0", "fe_tab"};
+  const size_t sizes[2] = {fe_elems(e) * 2, FE_TAB_BYTES};
+  return fe_alloc(e, &e->fe_mem, &e->fe_bytes, names, sizes, 2, true, s);
+}
+int ensure_fe_z(E* e, hipStream_t s) {
+  const char* names[1] = {"fe_z"};
+  const size_t sizes[1] = {fe_elems(e) * 2};
+  return fe_alloc(e, &e->fe_zmem, &e->fe_zbytes, names, sizes, 1, true, s);
+}
+int ensure_fe_acc(E* e, hipStream_t s) {
+  const char* names[1] = {"fe_acc"};
+  const size_t sizes[1] = {fe_elems(e) * 4};
+  return fe_alloc(e, &e->fe_accmem, &e->fe_accbytes, names, sizes, 1, true, s);
 }
 
 // the guidance-shaping buffers of the prepared shape, made once a shaped guided request arrives (like ensure_fb); Bh = the caller's images
@@ -1452,7 +1510,7 @@ static int create_impl(const fluxmi_model_desc_t* desc, const fluxmi_linear_t* l
   e->d_tnext = (float*)(e->consts + o_tnext); e->d_omt = (float*)(e->consts + o_omt); e->d_thr = (float*)(e->consts + o_thr);
   hipMemset(e->consts, 0, off);
   // pinned staging for the schedule (ts | dts | tnext | 1 - tnext | thresholds | solver coef | solver ctl | noise ids | eval offset) + the events (guard of the staging buffer, timing of the frozen steps)
-  if (hipHostMalloc((void**)&e->h_sched, (5 * (MAX_STEPS + 1) + 12 * MAX_STEPS + 4 * FLUXMI_ENGINE_MAX_BATCH + 1 + 9 + 53) * sizeof(float), hipHostMallocDefault) != hipSuccess ||
+  if (hipHostMalloc((void**)&e->h_sched, (5 * (MAX_STEPS + 1) + 12 * MAX_STEPS + 4 * FLUXMI_ENGINE_MAX_BATCH + 1 + 9 + 53 + 6 * MAX_STEPS + 4 * FLUXMI_ENGINE_MAX_BATCH + 1) * sizeof(float), hipHostMallocDefault) != hipSuccess ||
       hipEventCreateWithFlags(&e->ev_sched, hipEventDisableTiming) != hipSuccess || hipEventCreate(&e->ev_t0) != hipSuccess ||
       hipEventCreate(&e->ev_t1) != hipSuccess) {
     fluxmi_engine_destroy(e);
@@ -1692,8 +1750,9 @@ static void graphs_stale(fluxmi_engine_t* e, StepGraphs& g, bool cfg) {
   const bool diff = e->inp_on && e->inp_diff;
   // masked versus dense attention is a kind like guided versus plain, and so are the blend update and its differential form
   const bool shaped = cfg && e->gd_on;  // ... and guidance shaping; an unguided request does not consult the state
+  const void* fe_acc = e->fe_call ? e->fe_accmem : nullptr;  // (once made, the buffer rides in every edit launch: a row with first and apply ignores it)
   if (g.cfg != cfg || g.masked != e->masked || g.blend != e->inp_on || g.diff != diff || g.solver != e->sol_on || g.noise != e->sol_noise ||
-      g.shaped != shaped)
+      g.shaped != shaped || g.edit != e->fe_call || g.fe_acc != fe_acc)
     g.ok = g.warmed = false;
   // ... and the preview launch with its token grid (cadence, offset and factors are device data: they never re-capture)
   const bool previewed = e->pv_hook && e->pv_every > 0;
@@ -1718,6 +1777,8 @@ static void graphs_stale(fluxmi_engine_t* e, StepGraphs& g, bool cfg) {
   g.solver = e->sol_on;
   g.noise = e->sol_noise;
   g.shaped = shaped;
+  g.edit = e->fe_call;  // ... and FlowEdit's update: an edit request never replays a plain or guided request's pieces, nor they its
+  g.fe_acc = fe_acc;
 }
 
 // Captures pieces[0 .. n) into g.exec[0 .. n) on a private non-blocking stream (the caller has synchronised its own).  The only place that
@@ -1935,15 +1996,47 @@ static int cached_steps(fluxmi_engine_t* e, int mode, bool cfg, int step, int n_
 // the denoise loop, plain or guided (cfg: true classifier-free guidance).  Guided: the prepared batch B is 2 Bh, samples [0, Bh) the prompt
 // branch and [Bh, B) the negative branch of the caller's Bh images; the caller's img [Bh, ...] is copied into both halves of the stream, every
 // forward runs on the B samples, and the update is fluxmi_k_cfg_euler, which keeps the halves bit-identical.
+// edit (fluxmi_engine_denoise_edit): the third kind.  The batch is 2 Bh as for a guided call -- samples [0, Bh) the source branches, [Bh, B)
+// the target branches -- but the halves hold different latents, `img` is the caller's edit state z [Bh, ...], and the update is
+// fluxmi_k_flowedit_step on the engine's "fe_z" / "fe_x0": the stream only carries the two model inputs the kernel rebuilds.
 static int denoise_impl(fluxmi_engine_t* e, void* img, const void* txt, const void* y, float guidance, bool cfg, float cfg_scale,
-                        const double* timesteps_host, int n_steps, int* trial_index_inout, int use_graph, void* stream) {
+                        const double* timesteps_host, int n_steps, int* trial_index_inout, int use_graph, void* stream, bool edit = false) {
   hipStream_t s = (hipStream_t)stream;
+  if (e) e->fe_call = false;
   FLUXMI_REQUIRE(e && e->ws, "engine_denoise: call fluxmi_engine_prepare first");
   FLUXMI_REQUIRE(!e->is_cn, "engine_denoise: a ControlNet engine runs attached to a main engine (fluxmi_engine_attach_controlnet)");
   FLUXMI_REQUIRE(!cfg || e->B % 2 == 0, "engine_denoise_cfg: the prepared batch (%d) must be even: prompt branches first, then the negative "
                  "branches of the same images (2B <= %d)", e->B, FLUXMI_ENGINE_MAX_BATCH);
   FLUXMI_REQUIRE(img && txt && y && timesteps_host && trial_index_inout, "engine_denoise: NULL argument");
   FLUXMI_REQUIRE(n_steps >= 0 && n_steps <= MAX_STEPS, "engine_denoise: n_steps=%d out of range", n_steps);
+  if (edit) {
+    FLUXMI_REQUIRE(e->fe_on, "engine_denoise_edit: no FlowEdit state is set (fluxmi_engine_set_flow_edit)");
+    FLUXMI_REQUIRE(e->B % 2 == 0, "engine_denoise_edit: the prepared batch (%d) must be even: source branches first, then the target branches "
+                   "of the same images (2B <= %d)", e->B, FLUXMI_ENGINE_MAX_BATCH);
+    FLUXMI_REQUIRE(e->Lpred == e->Li && c_out(e) == e->d.in_channels, "engine_denoise_edit: %d reference rows, %d input and %d predicted "
+                   "channels: FlowEdit steps the whole stream (no Kontext reference, no Fill / Depth / Canny model)", e->Li - e->Lpred,
+                   e->d.in_channels, c_out(e));
+    FLUXMI_REQUIRE(e->fe_B == e->B / 2, "engine_denoise_edit: the FlowEdit state holds %d images, this call steps %d (half the prepared batch)",
+                   e->fe_B, e->B / 2);
+    FLUXMI_REQUIRE(e->fe_n == n_steps, "engine_denoise_edit: the FlowEdit program holds %d evaluations, this call runs %d "
+                   "(fluxmi_engine_set_flow_edit takes one row per evaluation of the call)", e->fe_n, n_steps);
+    FLUXMI_REQUIRE(!e->inp_on, "engine_denoise_edit: an inpainting state is set (FlowEdit edits the whole image: no mask)");
+    FLUXMI_REQUIRE(!e->sol_on, "engine_denoise_edit: a solver program is set (FlowEdit's update is its own: sampler euler only)");
+    FLUXMI_REQUIRE(!(e->fb_threshold > 0.f), "engine_denoise_edit: step caching is on (every evaluation runs on a fresh draw: consecutive "
+                   "evaluations are not comparable)");
+    FLUXMI_REQUIRE(!e->masked, "engine_denoise_edit: an attention-group table is set (regional prompts do not combine with FlowEdit)");
+    FLUXMI_REQUIRE(!e->cn, "engine_denoise_edit: a ControlNet is attached (not combined with FlowEdit)");
+    FLUXMI_REQUIRE(!e->ip_on, "engine_denoise_edit: an IP-Adapter is set (not combined with FlowEdit)");
+    FLUXMI_REQUIRE(!(e->pv_hook && e->pv_every > 0), "engine_denoise_edit: previews (every = %d > 0) are refused: the stream holds the two "
+                   "coupled model inputs, not a latent to preview (a hook with every = 0 reports progress and cancels)", e->pv_every);
+    FLUXMI_TRY(ensure_fe_z(e, s));
+    if (e->fe_need_acc) FLUXMI_TRY(ensure_fe_acc(e, s));
+    e->fe_call = true;
+  }
+  struct EditCallScope {  // fe_call speaks of the running call only: off again on every way out
+    fluxmi_engine_t* e;
+    ~EditCallScope() { e->fe_call = false; }
+  } edit_scope{e};
   Range whole("fluxmi_engine_denoise");
   SplitkScope splitk(e);
   FLUXMI_TRY(ensure_pairs(e, s));
@@ -1986,8 +2079,16 @@ static int denoise_impl(fluxmi_engine_t* e, void* img, const void* txt, const vo
   if (previewed) FLUXMI_TRY(ensure_pv(e, s));
   e->pv_launched = e->pv_delivered = 0;
   e->pv_cancelled = false;
-  e->pv_images = cfg ? B / 2 : B;
+  e->pv_images = cfg || edit ? B / 2 : B;
   auto euler = [&](hipStream_t st) -> int {
+    if (edit) {
+      const char* tab = buf<char>(e, "fe_tab");
+      return fluxmi_k_flowedit_step(buf<u16>(e, "img_s"), buf<u16>(e, "pred_s"), buf<u16>(e, "fe_z"), buf<float>(e, "fe_acc"),
+                                    buf<u16>(e, "fe_x0"), (const float*)tab, (const int*)(tab + (size_t)MAX_STEPS * 16), e->d_step,
+                                    (const unsigned*)(tab + (size_t)MAX_STEPS * 24),
+                                    (const int*)(tab + (size_t)MAX_STEPS * 24 + (size_t)FLUXMI_ENGINE_MAX_BATCH * 16), B / 2, Li, e->Lpred, C,
+                                    c_out(e), st);
+    }
     if (shaped) {
       const long long n_pred = (long long)e->Lpred * c_out(e);
       float* gp = buf<float>(e, "gd_params");
@@ -2050,8 +2151,9 @@ static int denoise_impl(fluxmi_engine_t* e, void* img, const void* txt, const vo
   // (long finished) copy: wait on that copy's event, never on the stream.
   if (e->sched_pending) FLUXMI_CHECK_HIP(hipEventSynchronize(e->ev_sched));
   float *h_ts = e->h_sched, *h_dts = e->h_sched + (MAX_STEPS + 1);
-  for (int i = 0; i <= n_steps; ++i) h_ts[i] = (float)timesteps_host[i];
-  for (int i = 0; i < n_steps; ++i) h_dts[i] = (float)(timesteps_host[i + 1] - timesteps_host[i]);
+  // (an edit call: timesteps_host holds the n_steps evaluation times and nothing behind them; the dts table goes unused)
+  for (int i = 0; i <= n_steps; ++i) h_ts[i] = edit && i == n_steps ? 0.f : (float)timesteps_host[i];
+  for (int i = 0; i < n_steps; ++i) h_dts[i] = edit ? 0.f : (float)(timesteps_host[i + 1] - timesteps_host[i]);
   h_dts[n_steps] = 0.f;
   FLUXMI_CHECK_HIP(hipMemcpyAsync(e->d_ts, h_ts, (n_steps + 1) * 4, hipMemcpyHostToDevice, s));
   FLUXMI_CHECK_HIP(hipMemcpyAsync(e->d_dts, h_dts, (n_steps + 1) * 4, hipMemcpyHostToDevice, s));
@@ -2098,14 +2200,44 @@ static int denoise_impl(fluxmi_engine_t* e, void* img, const void* txt, const vo
     FLUXMI_CHECK_HIP(hipMemcpyAsync(buf<float>(e, "pv_proj"), h_pv, 51 * 4, hipMemcpyHostToDevice, s));
     FLUXMI_CHECK_HIP(hipMemcpyAsync(buf<int>(e, "pv_ctl"), h_pv + 51, 8, hipMemcpyHostToDevice, s));
   }
+  if (edit) {  // ... and FlowEdit's tables, ids and offset: behind every earlier region of the staging buffer, one copy each into "fe_tab"
+    float* h_fe = e->h_sched + 5 * (MAX_STEPS + 1) + 12 * MAX_STEPS + 4 * FLUXMI_ENGINE_MAX_BATCH + 1 + 9 + 53;
+    int* h_ct = (int*)(h_fe + 4 * MAX_STEPS);
+    unsigned* h_id = (unsigned*)(h_fe + 6 * MAX_STEPS);
+    char* tab = buf<char>(e, "fe_tab");
+    memcpy(h_fe, e->fe_coef.data(), (size_t)n_steps * 16);
+    memcpy(h_ct, e->fe_ctl.data(), (size_t)n_steps * 8);
+    memset(h_id, 0, (size_t)FLUXMI_ENGINE_MAX_BATCH * 16);
+    memcpy(h_id, e->fe_ids.data(), (size_t)e->fe_B * 16);
+    h_id[4 * FLUXMI_ENGINE_MAX_BATCH] = (unsigned)e->fe_eval_offset;
+    if (n_steps > 0) {
+      FLUXMI_CHECK_HIP(hipMemcpyAsync(tab, h_fe, (size_t)n_steps * 16, hipMemcpyHostToDevice, s));
+      FLUXMI_CHECK_HIP(hipMemcpyAsync(tab + (size_t)MAX_STEPS * 16, h_ct, (size_t)n_steps * 8, hipMemcpyHostToDevice, s));
+    }
+    FLUXMI_CHECK_HIP(hipMemcpyAsync(tab + (size_t)MAX_STEPS * 24, h_id, (size_t)FLUXMI_ENGINE_MAX_BATCH * 16 + 4, hipMemcpyHostToDevice, s));
+  }
   FLUXMI_CHECK_HIP(hipEventRecord(e->ev_sched, s));
   e->sched_pending = true;
   u16 *gvec = buf<u16>(e, "gvec"), *tvec = buf<u16>(e, "tvec");
-  FLUXMI_TRY(fluxmi_k_fill_bf16(gvec, guidance, B, s));  // guidance arrives in the flow dtype (flux_pipeline.py:619-623)
+  if (edit) {  // a distilled-guidance value per branch: the source half, then the target half
+    FLUXMI_TRY(fluxmi_k_fill_bf16(gvec, e->fe_gs, B / 2, s));
+    FLUXMI_TRY(fluxmi_k_fill_bf16(gvec + B / 2, e->fe_gt, B / 2, s));
+  } else {
+    FLUXMI_TRY(fluxmi_k_fill_bf16(gvec, guidance, B, s));  // guidance arrives in the flow dtype (flux_pipeline.py:619-623)
+  }
   FLUXMI_CHECK_HIP(hipMemsetAsync(e->d_step, 0, 4, s));
   u16 *img_s = buf<u16>(e, "img_s"), *txt_s = buf<u16>(e, "txt_s"), *y_s = buf<u16>(e, "y_s"), *pred_s = buf<u16>(e, "pred_s");
-  const long long n_img = (long long)(cfg ? B / 2 : B) * Li * C;  // the caller's samples
-  FLUXMI_CHECK_HIP(hipMemcpyAsync(img_s, img, n_img * 2, hipMemcpyDeviceToDevice, s));
+  const long long n_img = (long long)(cfg || edit ? B / 2 : B) * Li * C;  // the caller's samples
+  if (edit) {  // the caller's edit state goes beside the stream; the first coupling, at the first evaluation's time, fills both halves of it
+    u16* fz = buf<u16>(e, "fe_z");
+    FLUXMI_CHECK_HIP(hipMemcpyAsync(fz, img, n_img * 2, hipMemcpyDeviceToDevice, s));
+    if (n_steps > 0)
+      FLUXMI_TRY(fluxmi_k_flowedit_couple(img_s, fz, buf<u16>(e, "fe_x0"), (float)timesteps_host[0], (float)(1.0 - timesteps_host[0]),
+                                          (const unsigned*)(buf<char>(e, "fe_tab") + (size_t)MAX_STEPS * 24), (unsigned)e->fe_eval_offset, B / 2, Li,
+                                          e->Lpred, C, c_out(e), s));
+  } else {
+    FLUXMI_CHECK_HIP(hipMemcpyAsync(img_s, img, n_img * 2, hipMemcpyDeviceToDevice, s));
+  }
   if (cfg) {
     FLUXMI_CHECK_HIP(hipMemcpyAsync(img_s + n_img, img, n_img * 2, hipMemcpyDeviceToDevice, s));
     unsigned bits;
@@ -2182,7 +2314,7 @@ static int denoise_impl(fluxmi_engine_t* e, void* img, const void* txt, const vo
   while (hooked && !e->pv_cancelled && e->pv_delivered < e->pv_launched) FLUXMI_TRY(pv_deliver(e, e->pv_delivered));
   if (e->pv_cancelled && e->pv_launched > 0)
     FLUXMI_CHECK_HIP(hipEventSynchronize(e->pv_ev[(e->pv_launched - 1) % (FLUXMI_PREVIEW_DEPTH + 1)]));
-  FLUXMI_CHECK_HIP(hipMemcpyAsync(img, img_s, n_img * 2, hipMemcpyDeviceToDevice, s));
+  FLUXMI_CHECK_HIP(hipMemcpyAsync(img, edit ? buf<u16>(e, "fe_z") : img_s, n_img * 2, hipMemcpyDeviceToDevice, s));
   *trial_index_inout = trial;
   if (e->pv_cancelled) {
     fluxmi_set_error("engine_denoise: cancelled by the step hook after %d of %d evaluations", e->pv_launched, n_steps);
@@ -2199,6 +2331,54 @@ int fluxmi_engine_denoise(fluxmi_engine_t* e, void* img, const void* txt, const 
 int fluxmi_engine_denoise_cfg(fluxmi_engine_t* e, void* img, const void* txt, const void* y, float guidance, float cfg_scale,
                               const double* timesteps_host, int n_steps, int* trial_index_inout, int use_graph, void* stream) {
   return denoise_impl(e, img, txt, y, guidance, true, cfg_scale, timesteps_host, n_steps, trial_index_inout, use_graph, stream);
+}
+
+int fluxmi_engine_denoise_edit(fluxmi_engine_t* e, void* z, const void* txt, const void* y, const double* timesteps_host, int n_evals,
+                               int* trial_index_inout, int use_graph, void* stream) {
+  return denoise_impl(e, z, txt, y, 0.f, false, 1.f, timesteps_host, n_evals, trial_index_inout, use_graph, stream, true);
+}
+
+// The FlowEdit state of the following edit calls (fluxmi.h): host tables like the solver program's; x0 is copied into the engine's own buffer
+// on `stream`, in order with the denoise_edit call that follows on it.
+int fluxmi_engine_set_flow_edit(fluxmi_engine_t* e, const void* x0_dev, int batch, const double* coef_host, const int* ctl_host, int n,
+                                const unsigned* ids_host, int eval_offset, float source_guidance, float target_guidance, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  FLUXMI_REQUIRE(e, "engine_set_flow_edit: NULL engine");
+  if (!x0_dev) {
+    e->fe_on = false;
+    e->fe_n = 0;
+    e->fe_coef.clear();
+    e->fe_ctl.clear();
+    e->fe_ids.clear();
+    return 0;
+  }
+  FLUXMI_REQUIRE(!e->is_cn, "engine_set_flow_edit: a ControlNet engine steps nothing (set the state on the main engine)");
+  FLUXMI_REQUIRE(e->ws, "engine_set_flow_edit: call fluxmi_engine_prepare first (the state belongs to the prepared shape)");
+  FLUXMI_REQUIRE(coef_host && ctl_host && ids_host, "engine_set_flow_edit: x0, coef_host, ctl_host and ids_host go together");
+  FLUXMI_REQUIRE(n >= 0 && n <= MAX_STEPS, "engine_set_flow_edit: n=%d out of range (at most %d evaluations)", n, MAX_STEPS);
+  FLUXMI_REQUIRE(batch >= 1 && 2 * batch <= std::max(2, e->B), "engine_set_flow_edit: batch %d outside 1..%d (half the prepared batch: "
+                 "the source and the target branch of every image)", batch, std::max(1, e->B / 2));
+  FLUXMI_REQUIRE(eval_offset >= 0, "engine_set_flow_edit: eval_offset %d < 0", eval_offset);
+  FLUXMI_REQUIRE(std::isfinite(source_guidance) && std::isfinite(target_guidance), "engine_set_flow_edit: guidance values must be finite");
+  for (int i = 0; i < 4 * n; ++i)
+    FLUXMI_REQUIRE(std::isfinite((float)coef_host[i]), "engine_set_flow_edit: coefficient %d of row %d is not finite in fp32", i % 4, i / 4);
+  bool need_acc = false;
+  for (int i = 0; i < n; ++i) need_acc = need_acc || !ctl_host[2 * i] || !ctl_host[2 * i + 1];
+  FLUXMI_TRY(ensure_fe_x0(e, s));
+  FLUXMI_CHECK_HIP(hipMemcpyAsync(buf<void>(e, "fe_x0"), x0_dev, (size_t)batch * e->Lpred * c_out(e) * 2, hipMemcpyDeviceToDevice, s));
+  e->fe_coef.resize((size_t)4 * n);
+  for (int i = 0; i < 4 * n; ++i) e->fe_coef[i] = (float)coef_host[i];
+  e->fe_ctl.resize((size_t)2 * n);
+  for (int i = 0; i < 2 * n; ++i) e->fe_ctl[i] = ctl_host[i] != 0;
+  e->fe_ids.assign(ids_host, ids_host + 4 * (size_t)batch);
+  e->fe_B = batch;
+  e->fe_n = n;
+  e->fe_eval_offset = eval_offset;
+  e->fe_gs = source_guidance;
+  e->fe_gt = target_guidance;
+  e->fe_need_acc = need_acc;
+  e->fe_on = true;
+  return 0;
 }
 
 // Token-group attention mask of the prepared shape: `table` = [B, L] descriptors on the device (L = Lt + Li: text rows, then image rows, as
@@ -2608,7 +2788,7 @@ int fluxmi_engine_copy_buffer(fluxmi_engine_t* e, const char* name, long long of
 
 int fluxmi_engine_workspace_bytes(fluxmi_engine_t* e, long long* bytes) {
   FLUXMI_REQUIRE(e && bytes, "engine_workspace_bytes: NULL argument");
-  *bytes = (long long)(e->ws_bytes + e->pairs_bytes + e->mods_all_bytes + e->fb_bytes + e->inp_bytes + e->sol_bytes + e->sol_ids_bytes + e->ip_bytes + e->gd_bytes + e->pv_bytes);  // workspace + row-pair weight copies + modulation table + step cache + inpainting + solver buffers + noise ids + adapter + guidance shaping + preview ring
+  *bytes = (long long)(e->ws_bytes + e->pairs_bytes + e->mods_all_bytes + e->fb_bytes + e->inp_bytes + e->sol_bytes + e->sol_ids_bytes + e->ip_bytes + e->gd_bytes + e->pv_bytes + e->fe_bytes + e->fe_zbytes + e->fe_accbytes);  // workspace + row-pair weight copies + modulation table + step cache + inpainting + solver buffers + noise ids + adapter + guidance shaping + preview ring + FlowEdit state
   return 0;
 }
 

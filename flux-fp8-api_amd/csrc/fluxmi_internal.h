@@ -181,6 +181,15 @@ int fluxmi_k_solver_step_noise(void* img, const void* pred, void* xs, float* his
                                const int* step, const float* scale, int B, long long img_rows, long long pred_rows, int c_in, int c_out,
                                const unsigned* ids, const int* eval_offset, hipStream_t s);
 int fluxmi_k_philox_normal(void* out, const unsigned* ids, int B, long long n_per_image, unsigned eval, int raw, hipStream_t s);
+// FlowEdit (flowedit.hip; include/fluxmi.h, fluxmi_flowedit_couple / _step): the coupling alone at host scalars (t, 1 - t, eval), and the update
+// of the edit state z from row *step of coef [n][4] / ctl [n][2] followed by the next coupling; img / pred [2B, rows, C], source branches first,
+// z / x0 bf16 and acc fp32 dense [B, rows, C].  The step launcher does not see the row: a caller that passes acc == NULL vouches that every
+// row it runs has first and apply set
+int fluxmi_k_flowedit_couple(void* img, const void* z, const void* x0, float t, float one_minus_t, const unsigned* ids, unsigned eval, int B,
+                             long long img_rows, long long pred_rows, int c_in, int c_out, hipStream_t s);
+int fluxmi_k_flowedit_step(void* img, const void* pred, void* z, float* acc, const void* x0, const float* coef, const int* ctl, const int* step,
+                           const unsigned* ids, const int* eval_offset, int B, long long img_rows, long long pred_rows, int c_in, int c_out,
+                           hipStream_t s);
 // first-block step cache (elementwise.hip): streaming passes over B samples of n bf16 elements, x side strided, cache side dense
 int fluxmi_k_fb_snapshot(const void* x, long long x_bstride, void* dst, int B, long long n, hipStream_t s);
 int fluxmi_k_fb_commit(const void* x, long long x_bstride, const void* r, void* r_ref, void* h1, int B, long long n, hipStream_t s);

@@ -698,7 +698,8 @@ class FluxPipeline:
                  ip_adapter_image=None, ip_adapter_image_embeds: Optional[torch.Tensor] = None, ip_adapter_scale=1.0,
                  negative_ip_adapter_image=None, negative_ip_adapter_scale=1.0, guidance_mode: str = "cfg", guidance_rescale: float = 0.0,
                  apg_eta: float = 1.0, apg_norm_threshold: float = 0.0, apg_momentum: float = 0.0, zero_init_steps: int = 0,
-                 on_step=None, preview_every: int = 0, preview_factors=None):
+                 on_step=None, preview_every: int = 0, preview_factors=None, source_prompt=None, source_guidance: Optional[float] = None,
+                 edit_n_max: Optional[int] = None, edit_n_min: int = 0, edit_n_avg: int = 1):
         """`reference_image` (FLUX.1 Kontext [dev] instruction editing): an image the prompt describes an edit of, in any form `init_image`
         takes; see prepare_kontext_reference.  Composes with `init_image` / `strength` unchanged.
         FLUX.1 Fill [dev] (a model with 320 conditioning channels): `init_image` is the image to inpaint and `mask_image` (white =
@@ -802,7 +803,24 @@ class FluxPipeline:
         `preview_factors` = ([16][3], [3]) in decoded-latent space; default: the config's preview_factors / preview_bias, else a least-squares
         fit against this pipeline's VAE, made on first use and cached (util.fit_preview_factors).  preview_every > 0 without on_step is
         refused, both are refused under a process group and for more images than one engine pass holds.  Without them the request is
-        today's, launch for launch.  Composes with everything else."""
+        today's, launch for launch.  Composes with everything else.
+        `source_prompt` (FlowEdit, Kulikov et al. 2024: inversion-free text-guided editing on a plain text-to-image checkpoint): a prompt
+        that DESCRIBES `init_image`, in any form `prompt` takes and of its sequence length; `prompt` is then the target prompt and the
+        result is `init_image` under it -- no mask, no extra weights, no inversion pass.  It runs iff `source_prompt is not None` and needs
+        `init_image`, strength 1.0 and sampler "euler".  Of the request's `num_steps` steps the last `edit_n_max` (None = all) are edited;
+        the last `edit_n_min` of those are a plain Euler tail on the target prompt (0 = none), the others are coupled steps: `edit_n_avg`
+        model evaluations each, on both prompts at once (one forward on two samples per image; Flux.denoise_edit, fluxmi.flowedit).
+        `guidance` is the target branch's distilled guidance, `source_guidance` the source branch's (None = `guidance`).  The noise of
+        the couplings is generated in the update kernel from `noise_seed` (None = the request's seed): nothing is drawn from the request's
+        torch generator, and image k of the request draws under ids (seed & 0xffffffff, seed >> 32, k, 1).  Composes with LoRA,
+        `num_images` (at most 16), `sigmas` / `sigma_schedule` and `on_step` (progress and cancellation; no previews); refused with a
+        negative prompt at a scale > 1, `inpaint_mask`, `reference_image`, a Fill / Depth / Canny model, `regions`, `cache_threshold` > 0,
+        a ControlNet, an IP-Adapter, `redux_image`, `preview_every` > 0 and under a process group.  Without `source_prompt` the request is
+        today's, launch for launch, and `source_guidance` / `edit_*` are refused."""
+        edit = self._check_edit(locals())
+        if edit is not None:
+            return self._generate_edit(edit, prompt, source_prompt, width, height, num_steps, guidance, seed, init_image, silent, num_images,
+                                       return_seed, jpeg_quality, output_type, use_graph, sigma_schedule, sigmas, noise_seed, on_step)
         if isinstance(preview_every, bool) or not isinstance(preview_every, int) or preview_every < 0:
             raise ValueError(f"fluxmi: preview_every={preview_every!r}: expected an integer >= 0 (0 = no previews)")
         if on_step is not None and not callable(on_step):
@@ -1166,6 +1184,143 @@ class FluxPipeline:
             return (out, seed) if return_seed else out
         img_px = self.vae_decode(latents, height, width)
         # output_type "uint8": the [B, H, W, 3] array into_bytes hands to the JPEG encoder (the pixel-parity tests compare it)
+        out = self.to_uint8(img_px) if output_type == "uint8" else self.into_bytes(img_px, jpeg_quality=jpeg_quality)
+        return (out, seed) if return_seed else out
+
+    # ---- FlowEdit (fluxmi.flowedit; Flux.denoise_edit) ---------------------------------------------------------------------------------------
+    def _check_edit(self, a: dict):
+        """generate's arguments -> None (no source_prompt: today's request) or (source_guidance, n_max, n_min, n_avg); every refusal of an
+        edit request is raised here, before any encoder or engine work"""
+        from fluxmi import flowedit
+
+        if a["source_prompt"] is None:
+            if a["source_guidance"] is not None or a["edit_n_max"] is not None or a["edit_n_min"] != 0 or a["edit_n_avg"] != 1:
+                raise ValueError("fluxmi: source_guidance / edit_n_max / edit_n_min / edit_n_avg belong to a FlowEdit request: they need source_prompt")
+            return None
+        no = lambda what: ValueError(f"fluxmi: source_prompt (FlowEdit) does not combine with {what}")
+        if a["init_image"] is None:
+            raise ValueError("fluxmi: source_prompt (FlowEdit) needs init_image (the image the source prompt describes)")
+        if a["strength"] != 1.0:
+            raise ValueError(f"fluxmi: source_prompt (FlowEdit) needs strength 1.0, not {a['strength']} (edit_n_max bounds how far the edit goes)")
+        if a["sampler"] != "euler" or a["eta"] != 1.0 or a["s_noise"] != 1.0:
+            raise ValueError(f"fluxmi: source_prompt (FlowEdit) needs sampler \"euler\" (got {a['sampler']!r}) and takes no eta / s_noise")
+        if a["negative_prompt"] is not None and a["true_cfg_scale"] > 1:
+            raise no("a negative_prompt at true_cfg_scale > 1 (four branches per image)")
+        for name in ("inpaint_mask", "reference_image", "regions", "redux_image", "mask_image", "control_image", "img_cond"):
+            if a[name] is not None:
+                raise no(name)
+        if a["controlnet_image"] is not None or a["controlnet_cond"] is not None:
+            raise no("a ControlNet")
+        if a["ip_adapter_image"] is not None or a["ip_adapter_image_embeds"] is not None:
+            raise no("an IP-Adapter")
+        try:
+            cache_on = float(a["cache_threshold"]) > 0
+        except (TypeError, ValueError):
+            cache_on = True
+        if cache_on:
+            raise no("cache_threshold > 0 (every evaluation runs on a fresh draw)")
+        pe = a["preview_every"]
+        if isinstance(pe, bool) or not isinstance(pe, int) or pe != 0:
+            raise no("preview_every > 0 (there are no previews of the edit state; on_step reports progress and cancels)")
+        if a["on_step"] is not None and not callable(a["on_step"]):
+            raise ValueError("fluxmi: on_step must be callable")
+        if fdist.world_size() > 1:
+            raise no("a process group")
+        if self.conditioning_kind() is not None:
+            raise no("a FLUX.1 Fill / Depth / Canny model")
+        sg = a["guidance"] if a["source_guidance"] is None else a["source_guidance"]
+        try:
+            sg = float(sg)
+            if not math.isfinite(sg):
+                raise ValueError
+        except (TypeError, ValueError):
+            raise ValueError(f"fluxmi: source_guidance={a['source_guidance']!r}: expected a finite number") from None
+        ns = a["noise_seed"]
+        if ns is not None and (isinstance(ns, bool) or not isinstance(ns, int) or not 0 <= ns < 2 ** 64):
+            raise ValueError(f"fluxmi: noise_seed={ns!r}: expected an integer in [0, 2^64)")
+        if a["sigma_schedule"] not in solvers.SIGMA_SCHEDULES:
+            raise ValueError(f"fluxmi: sigma_schedule={a['sigma_schedule']!r}: expected one of {solvers.SIGMA_SCHEDULES}")
+        if isinstance(a["num_images"], bool) or not 1 <= a["num_images"] <= flowedit.MAX_IMAGES:
+            raise ValueError(f"fluxmi: source_prompt (FlowEdit) takes 1..{flowedit.MAX_IMAGES} images per request, not {a['num_images']}")
+        steps = 4 if self.name == "flux-schnell" else a["num_steps"]
+        if a["sigmas"] is not None:
+            steps = len(solvers.custom_sigmas(a["sigmas"])) - 1
+        flowedit.build_program((1.0, 0.0), a["edit_n_avg"])  # edit_n_avg < 1: refused here
+        flowedit.split_steps(steps, a["edit_n_max"], a["edit_n_min"])  # 0 <= edit_n_min <= edit_n_max <= num_steps, or refused
+        return sg, a["edit_n_max"], a["edit_n_min"], a["edit_n_avg"]
+
+    @torch.inference_mode()
+    def prepare_edit(self, init_image, height: int, width: int, num_steps: int, num_images: int = 1, sigmas=None, sigma_schedule=None):
+        """-> (the VAE latent of `init_image` [num_images, 16, height / 8, width / 8] in the flow dtype, the request's schedule): what
+        preprocess_latent_parts does with an init image at strength 1, without any draw: no noise (FlowEdit draws nothing from the
+        generator) and the encoder's mean instead of a sample of its Gaussian"""
+        if self.ae is None:
+            raise RuntimeError("fluxmi: FlowEdit needs an autoencoder (config.ae_path) -- none is attached")
+        if isinstance(init_image, np.ndarray):
+            init_image = torch.from_numpy(init_image)
+        px = init_image.permute(2, 0, 1).contiguous().to(self.device_ae, dtype=self.ae_dtype).div(127.5).sub(1)[None, ...]
+        px = self.resize_center_crop(px, height, width)
+        # x0 is the MEAN of the encoder's Gaussian (its mode, as the FlowEdit authors take it), not a sample: the edit starts from the photo
+        # itself, and the same request gives the same bits without a draw
+        mean = torch.chunk(self.ae.encode_moments(px), 2, dim=self.ae.reg.chunk_dim)[0].float()
+        latent = (self.ae.scale_factor * (mean - self.ae.shift_factor)).to(dtype=self.dtype, device=self.device_flux).repeat(num_images, 1, 1, 1)
+        timesteps = self.get_schedule(num_steps, latent.shape[-1] * latent.shape[-2] // 4, shift=(self.name != "flux-schnell"))
+        if sigmas is not None:
+            timesteps = [float(v) for v in sigmas]
+        if sigma_schedule is not None:
+            timesteps = solvers.sigma_schedule(sigma_schedule, timesteps)
+        return latent, timesteps
+
+    def _generate_edit(self, edit, prompt, source_prompt, width, height, num_steps, guidance, seed, init_image, silent, num_images, return_seed,
+                       jpeg_quality, output_type, use_graph, sigma_schedule, sigmas, noise_seed, on_step):
+        """the FlowEdit request of generate (its docstring): skipped steps | coupled steps (Flux.denoise_edit) | Euler tail (Flux.denoise)"""
+        from fluxmi import flowedit, ops
+        from modules.flux_model import PreviewCall
+
+        source_guidance, n_max, n_min, n_avg = edit
+        num_steps = 4 if self.name == "flux-schnell" else num_steps
+        if sigmas is not None:
+            sigmas = solvers.custom_sigmas(sigmas)
+            num_steps = len(sigmas) - 1
+        height, width = 16 * (height // 16), 16 * (width // 16)
+        _, seed = self.set_seed(seed)
+        init_image = self.load_init_image_if_needed(init_image)
+        latent, timesteps = self.prepare_edit(init_image, height, width, num_steps, num_images, sigmas, sigma_schedule)
+        x0, img_ids, vec, txt, txt_ids = map(lambda t: t.contiguous(), self.prepare(latent, prompt))
+        _, _, src_vec, src_txt, _ = self.prepare(latent, source_prompt)
+        if tuple(src_txt.shape[1:]) != tuple(txt.shape[1:]) or src_txt.shape[0] not in (1, txt.shape[0]):
+            raise ValueError(f"fluxmi: source_prompt embeddings {tuple(src_txt.shape)} do not match the prompt's {tuple(txt.shape)}: both branches "
+                             f"run in one batch, so they need the same sequence length")
+        B = x0.shape[0]
+        if B > flowedit.MAX_IMAGES:
+            raise ValueError(f"fluxmi: source_prompt (FlowEdit) takes 1..{flowedit.MAX_IMAGES} images per request, not {B}")
+        a, b = flowedit.split_steps(len(timesteps) - 1, n_max, n_min)
+        ids = flowedit.edit_ids(seed if noise_seed is None else noise_seed, B)
+        n_coupled, n_total = (b - a) * n_avg, (b - a) * n_avg + (len(timesteps) - 1 - b)
+
+        def hook(eval_offset, step_of):  # the request's numbering continues from the coupled steps into the tail
+            if on_step is None:
+                return None
+            cb = lambda evaluation, num_evaluations, rgb: on_step({"evaluation": evaluation, "num_evaluations": num_evaluations,
+                                                                   "step": step_of(evaluation - eval_offset), "preview": None})
+            return PreviewCall(None, (0, 0), 0, eval_offset, n_total, cb)
+
+        z = x0
+        if b > a:
+            z = self.model.denoise_edit(x0, img_ids, src_txt, src_vec, txt, vec, txt_ids, timesteps[a:b + 1], n_avg=n_avg, ids=ids, eval_offset=0,
+                                        source_guidance=source_guidance, guidance=guidance, use_graph=use_graph,
+                                        preview=hook(0, lambda j: a + j // n_avg), x0=x0)
+        latents = z
+        if b < len(timesteps) - 1:
+            # the tail: one coupling at the tail's first time with the next draw index -- n_coupled, the index a continuing edit call would
+            # start at -- whose target half is an ordinary noisy latent of the edited image
+            zt = ops.flowedit_couple(z.to(torch.bfloat16).contiguous(), x0.to(torch.bfloat16).contiguous(), timesteps[b], ids, n_coupled)[B:]
+            latents = self.model.denoise(zt.to(x0.dtype), img_ids, txt, txt_ids, vec, timesteps[b:], guidance=guidance, use_graph=use_graph,
+                                         **({} if on_step is None else dict(preview=hook(n_coupled, lambda j: b + j))))
+        if output_type == "latent" or self.ae is None:
+            out = self.unpack(latents.float(), height, width)
+            return (out, seed) if return_seed else out
+        img_px = self.vae_decode(latents, height, width)
         out = self.to_uint8(img_px) if output_type == "uint8" else self.into_bytes(img_px, jpeg_quality=jpeg_quality)
         return (out, seed) if return_seed else out
 

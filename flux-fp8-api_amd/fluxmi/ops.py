@@ -662,6 +662,58 @@ def cfg_euler(img: torch.Tensor, pred: torch.Tensor, dt: float, scale: float) ->
     return img
 
 
+# ---- FlowEdit (fluxmi_flowedit_couple / _step; include/fluxmi.h, fluxmi/flowedit.py) ----------------------------------------------------------
+def _flowedit_ids(ids, B: int, dev) -> torch.Tensor:
+    """ids [B, 4] (a list of uint32 words, or a tensor) -> int32 device tensor holding the same 32-bit words"""
+    t = ids if isinstance(ids, torch.Tensor) else torch.tensor([[int(w) for w in row] for row in ids], dtype=torch.int64).reshape(-1, 4)
+    if tuple(t.shape) != (B, 4):
+        raise ValueError(f"flowedit: ids {tuple(t.shape)}: expected [{B}, 4] uint32 words {{key_lo, key_hi, c2, c3}} per image")
+    if t.dtype == torch.uint32:
+        t = t.view(torch.int32)
+    elif t.dtype != torch.int32:
+        t = (((t.to(torch.int64) & 0xffffffff) + 2 ** 31) % 2 ** 32 - 2 ** 31).to(torch.int32)
+    return t.to(dev).contiguous()
+
+
+def flowedit_couple(z: torch.Tensor, x0: torch.Tensor, t: float, ids, eval_index: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """FlowEdit's coupling alone (fluxmi_flowedit_couple): z, x0 bf16 [B, rows, C] -> out bf16 [2B, rows, C] with zs = (1 - t) * x0 + t * n in
+    the first half and zt = z + zs - x0 in the second, on bf16 tensors, n the Philox normals of (ids[b], eval_index) rounded to bf16.  1 - t is
+    subtracted here, in double."""
+    _req(z, torch.bfloat16, "z")
+    _req(x0, torch.bfloat16, "x0")
+    if z.ndim != 3 or z.shape != x0.shape or not (z.is_contiguous() and x0.is_contiguous()):
+        raise ValueError(f"flowedit_couple: z {tuple(z.shape)} / x0 {tuple(x0.shape)} must be contiguous [B, rows, channels] of one shape")
+    B, R, Cc = z.shape
+    d_ids = _flowedit_ids(ids, B, z.device)
+    if out is None:
+        out = torch.empty((2 * B, R, Cc), dtype=torch.bfloat16, device=z.device)
+    _req(out, torch.bfloat16, "out")
+    if tuple(out.shape) != (2 * B, R, Cc) or not out.is_contiguous():
+        raise ValueError(f"flowedit_couple: out {tuple(out.shape)} must be contiguous [{2 * B}, {R}, {Cc}]")
+    call("fluxmi_flowedit_couple", _p(out), _p(z), _p(x0), float(t), float(1.0 - float(t)), _p(d_ids), int(eval_index), B, R, R, Cc, Cc, _stream())
+    return out
+
+
+def flowedit_step(img: torch.Tensor, pred: torch.Tensor, z: torch.Tensor, x0: torch.Tensor, coef: torch.Tensor, ctl: torch.Tensor, ids,
+                  acc: Optional[torch.Tensor] = None, step: Optional[torch.Tensor] = None, eval_offset: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """In place, FlowEdit's update and the next coupling (fluxmi_flowedit_step): img / pred bf16 [2B, rows, C], z / x0 bf16 [B, rows, C], coef
+    fp32 [n, 4] and ctl int32 [n, 2] on the device, `step` / `eval_offset` int32 device scalars (None = 0), acc fp32 [B, rows, C] or None."""
+    for name, t_ in (("img", img), ("pred", pred), ("z", z), ("x0", x0)):
+        _req(t_, torch.bfloat16, name)
+    _req(coef, torch.float32, "coef")
+    _req(ctl, torch.int32, "ctl")
+    if acc is not None:
+        _req(acc, torch.float32, "acc")
+    B, R, Cc = z.shape
+    if tuple(img.shape) != (2 * B, R, Cc) or pred.shape != img.shape or x0.shape != z.shape or (acc is not None and acc.shape != z.shape) or \
+            not all(t_.is_contiguous() for t_ in (img, pred, z, x0, coef, ctl) + ((acc,) if acc is not None else ())):
+        raise ValueError(f"flowedit_step: img {tuple(img.shape)} / pred {tuple(pred.shape)} [2B, rows, C] and z {tuple(z.shape)} / x0 / acc [B, rows, C], contiguous")
+    d_ids = _flowedit_ids(ids, B, z.device)
+    call("fluxmi_flowedit_step", _p(img), _p(pred), _p(z), _p(acc), _p(x0), _p(coef), _p(ctl), _p(step), _p(d_ids), _p(eval_offset), B, R, R, Cc, Cc,
+         _stream())
+    return z
+
+
 # ---- latent preview (fluxmi_latent_preview; include/fluxmi.h) ---------------------------------------------------------------------------
 def preview_proj(factors, bias=None) -> list:
     """The 51 floats the kernel reads: M[16][3] row-major, then bias[3] (zeros when None)."""

@@ -1011,6 +1011,95 @@ class Flux(nn.Module):
             return img[..., :self.out_channels].contiguous()
         return img[:, :Li].contiguous() if Lc else img
 
+    MAX_EDIT_IMAGES = 16  # fluxmi.flowedit.MAX_IMAGES: the source and the target branch of every image share one engine pass
+
+    def denoise_edit(self, z: Tensor, img_ids: Tensor, src_txt: Tensor, src_y: Tensor, tar_txt: Tensor, tar_y: Tensor, txt_ids: Tensor,
+                     timesteps: List[float], n_avg: int = 1, ids=None, eval_offset: int = 0, source_guidance: float = 1.5,
+                     guidance: float = 5.5, use_graph: bool = True, preview: PreviewCall | None = None, x0: Tensor | None = None) -> Tensor:
+        """FlowEdit's coupled steps (fluxmi.flowedit; Kulikov et al. 2024, Algorithm 1) run natively: the loop of `denoise` -- calibrating
+        steps unfused, every later evaluation one replay of a captured hipGraph -- on 2B samples, sample b the SOURCE branch of image b
+        (`src_txt` / `src_y`, distilled guidance `source_guidance`) and sample B + b its TARGET branch (`tar_txt` / `tar_y`, `guidance`).
+        `z` [B, Li, C]: the edit state; `x0` the init image's latent tokens (None: `z` is x0, the start of an edit).  Every step of
+        `timesteps` is coupled: `n_avg` evaluations at its time, each on a fresh coupling zs = (1 - t) x0 + t n, zt = z + zs - x0 written to
+        the two halves of the stream, then z moves by dt times the average of (v_target - v_source) (csrc/flowedit.hip: update and next
+        coupling in one launch).  `ids` [B, 4] uint32 words per IMAGE (fluxmi.flowedit.edit_ids); the call's first coupling draws at
+        `eval_offset`, evaluation j's at eval_offset + j + 1, so a request cut into several calls draws what the uncut one draws.  Returns
+        the new z; neither `z` nor `x0` is modified.  `preview`: progress and cancellation only (every = 0), `evaluation` counting model
+        evaluations.  At most 16 images; refused under an amax exchange (a process group)."""
+        from fluxmi import flowedit
+
+        if getattr(self, "_amax_xchg", None) is not None:
+            raise ValueError("fluxmi: FlowEdit is refused under an amax exchange (a process group)")
+        preview = self._check_preview(preview)
+        if preview is not None and preview.every > 0:
+            raise ValueError("fluxmi: FlowEdit has no previews of the edit state (preview.every must be 0: progress and cancellation only)")
+        B = z.shape[0]
+        if z.ndim != 3 or not 1 <= B <= self.MAX_EDIT_IMAGES:
+            raise ValueError(f"fluxmi: FlowEdit takes z [1..{self.MAX_EDIT_IMAGES}, Li, C] (both branches of every image share one engine pass), got "
+                             f"{tuple(z.shape)}")
+        if self.in_channels != self.out_channels or z.shape[2] != self.in_channels:
+            raise ValueError(f"fluxmi: FlowEdit needs a text-to-image model ({self.in_channels} input and {self.out_channels} predicted channels; z has "
+                             f"{z.shape[2]})")
+        if x0 is None:
+            x0 = z
+        if tuple(x0.shape) != tuple(z.shape):
+            raise ValueError(f"fluxmi: x0 {tuple(x0.shape)} does not match z {tuple(z.shape)}")
+        for name, t, want in (("src_txt", src_txt, None), ("tar_txt", tar_txt, tuple(src_txt.shape[1:])), ("src_y", src_y, None),
+                              ("tar_y", tar_y, tuple(src_y.shape[1:]))):
+            if t.shape[0] not in (1, B) or (want is not None and tuple(t.shape[1:]) != want):
+                raise ValueError(f"fluxmi: {name} {tuple(t.shape)}: expected [1 or {B}, ...] with the other branch's sequence length (both "
+                                 f"branches run in one batch)")
+        program = flowedit.build_program(timesteps, n_avg)
+        n = len(program.coef)
+        if isinstance(eval_offset, bool) or int(eval_offset) != eval_offset or eval_offset < 0:
+            raise ValueError(f"fluxmi: eval_offset={eval_offset!r}: expected an integer >= 0")
+        ids = [[int(w) & 0xffffffff for w in row] for row in (ids.tolist() if isinstance(ids, torch.Tensor) else ids or ())]
+        if len(ids) != B or any(len(row) != 4 for row in ids):
+            raise ValueError(f"fluxmi: ids: expected {B} rows of 4 uint32 words, one row per image (fluxmi.flowedit.edit_ids)")
+        bf = lambda t: t.to(device=z.device, dtype=torch.bfloat16).contiguous()
+        ex = lambda t: t.to(z.device).expand(B, *t.shape[1:])
+        txt, y = bf(torch.cat((ex(src_txt), ex(tar_txt)), 0)), bf(torch.cat((ex(src_y), ex(tar_y)), 0))
+        ids2, tids2 = torch.cat((img_ids, img_ids), 0), torch.cat((ex(txt_ids), ex(txt_ids)), 0)
+        z, x0 = bf(z).clone(), bf(x0)
+        self._ensure_engine(z.device)
+        with self._lock:
+            self._prepare(z, ids2, tids2, txt, 0)
+            self._set_attn_groups(None, txt.shape[0], txt.shape[1] + z.shape[1], z.device)
+            _lib.call("fluxmi_engine_set_step_cache", self._engine, 0.0, 0)
+            self._set_inpaint(None, z.device)
+            self._set_solver(None)
+            self._set_guidance(None)
+            trial = self._trial_counter()
+            t_io = C.c_int(trial if trial is not None else 0)
+            coef = (C.c_double * max(1, 4 * n))(*[float(v) for row in program.coef for v in row])
+            ctl = (C.c_int * max(1, 2 * n))(*[int(v) for row in program.ctl for v in row])
+            flat = (C.c_uint32 * (4 * B))(*[w for row in ids for w in row])
+            ts = (C.c_double * max(1, n))(*program.times)
+            _lib.call("fluxmi_engine_set_flow_edit", self._engine, ops._p(x0), B, coef, ctl, n, flat, int(eval_offset), float(source_guidance),
+                      float(guidance), ops._stream())
+            pv, rc, ran = None, 0, 0
+            try:
+                pv = self._set_preview(preview)
+                rc = _lib.lib.fluxmi_engine_denoise_edit(self._engine, ops._p(z), ops._p(txt), ops._p(y), ts, n, C.byref(t_io), int(use_graph),
+                                                         ops._stream())
+                if rc != _lib.CANCELLED or pv is None:
+                    _lib.check(rc)
+                else:
+                    cap_ran = (C.c_longlong(0), C.c_int(0))
+                    _lib.call("fluxmi_engine_preview_stats", self._engine, C.byref(cap_ran[0]), C.byref(cap_ran[1]))
+                    ran = cap_ran[1].value
+            finally:
+                if pv is not None:
+                    _lib.call("fluxmi_engine_set_preview", self._engine, None, 0, 0, 0, 0, 0, None, None)
+                _lib.call("fluxmi_engine_set_flow_edit", self._engine, None, 0, None, None, 0, None, 0, 0.0, 0.0, None)
+            if trial is not None:
+                self._advance_calibration(t_io.value)
+        if pv is not None and pv["error"] is not None:
+            raise pv["error"]
+        if rc == _lib.CANCELLED:
+            raise GenerationCancelled(preview.eval_offset + ran, preview.n_evaluations)
+        return z
+
     def step_cache_log(self):
         """What first-block step caching did in the last `denoise` call (the last pass of a chunked batch): `(ratios, hits)` with
         `ratios` a float32 tensor [frozen steps, samples of the pass] (inf where no reference existed yet: the first frozen step) and `hits` a

@@ -435,6 +435,31 @@ int fluxmi_solver_step_noise(void* img, const void* pred, void* xs, float* hist,
                              const float* scale, int B, long long img_rows, long long pred_rows, int c_in, int c_out, const unsigned* ids,
                              const int* eval_offset, void* stream);
 
+/* ---- FlowEdit: inversion-free text-guided editing of an init image (Kulikov et al. 2024, Algorithm 1) --------------
+ * img / pred: bf16 [2B, rows, C]; sample b is the SOURCE branch of image b, sample B + b its TARGET branch.  z (the edit state) and x0 (the
+ * init image's latent tokens, never modified): bf16, dense [B, rows, C].  ids: DEVICE uint32 [B][4] per image, as for fluxmi_philox_normal.
+ * Coupling at time t and draw index ev, with n = bf16(the normal fluxmi_philox_normal gives element e of image b for ids[b] at eval = ev):
+ *   zs = bf16( bf16((1 - t) * x0) + bf16(t * n) )  -> img[b]          zt = bf16( bf16(z + zs) - x0 )  -> img[B + b]
+ * one bf16 rounding per operation, t and 1 - t fp32 (one_minus_t is the caller's: subtracted in double).  fluxmi_flowedit_couple is the
+ * coupling alone at HOST scalars; z is only read.
+ * fluxmi_flowedit_step: the update after an evaluation, then the next coupling.  coef: DEVICE fp32 [n][4] = {w, dt, tn, 1 - tn}, ctl: DEVICE
+ * int32 [n][2] = {first, apply}; row j = *step (step: DEVICE int, NULL = 0), vs = pred[b], vt = pred[B + b]:
+ *   d   = bf16(vt - vs)
+ *   acc = (first ? 0 : acc) + w * float(d)            fp32, the product and the sum each rounded (never fused)
+ *   apply:  D = bf16(acc);  m = bf16(dt * D);  z' = bf16(float(z) + float(m)), stored to z;        else acc is stored
+ *   then the coupling at t = tn with ev = *step + 1 + *eval_offset (eval_offset: DEVICE int, NULL = 0) on z' (z without apply).
+ * acc: fp32, dense [B, rows, C]: stored by a row without apply, read by a row without first.  A row with first AND apply (one evaluation per
+ * step) neither reads nor writes it and acc may be NULL; NULL acc with any other row is refused (this entry then reads *step and the row
+ * back, which synchronises the stream: the engine, which knows its program, does not).  pred and x0 are never written; every read of an
+ * element precedes its writes; 16-byte accesses, one thread per 8 elements (two Philox blocks).
+ * Refused: c_in != c_out or pred_rows != img_rows (v1 steps the whole stream: no Kontext rows, no conditioning channels), NULL ids,
+ * c_out %% 8 != 0, more than 2^31 - 1 vectors. */
+int fluxmi_flowedit_couple(void* img, const void* z, const void* x0, float t, float one_minus_t, const unsigned* ids, unsigned eval, int B,
+                           long long img_rows, long long pred_rows, int c_in, int c_out, void* stream);
+int fluxmi_flowedit_step(void* img, const void* pred, void* z, float* acc, const void* x0, const float* coef, const int* ctl, const int* step,
+                         const unsigned* ids, const int* eval_offset, int B, long long img_rows, long long pred_rows, int c_in, int c_out,
+                         void* stream);
+
 /* ---- guidance shaping of true classifier-free guidance: CFG rescale, APG, CFG-Zero*  ------------------------------
  * Operands as for fluxmi_cfg_euler: pred bf16, dense [2B][N], N = pred_rows * c_out, N %% 8 == 0; sample b is c (the prompt branch), sample
  * B + b is u (the negative branch).  r: fp32, dense [B][N], APG's running difference (NULL: no r; its sums are 0, it is never touched and mu
@@ -695,6 +720,27 @@ int fluxmi_engine_set_solver(fluxmi_engine_t* e, const double* coef_host, const 
  * re-allocates the workspace switch the noise off; a denoise call whose program has a non-zero cn and no ids set is refused.  A deterministic
  * solver request and a request without a solver allocate and launch exactly what they did before. */
 int fluxmi_engine_set_solver_noise(fluxmi_engine_t* e, const unsigned* ids_host, int batch, int eval_offset);
+/* FlowEdit state (fluxmi_flowedit_step) for the following fluxmi_engine_denoise_edit calls on the PREPARED shape (2 x batch
+ * samples: source branches first).  x0_dev: bf16 [batch, Li, C] on the device, copied into the engine-owned "fe_x0" on `stream`; coef_host:
+ * n x 4 doubles, ctl_host: n x 2 ints, the rows of fluxmi_flowedit_step (cast to fp32 here), n <= 1024; ids_host: batch x 4 uint32 per image;
+ * eval_offset >= 0: the call's first coupling draws at eval_offset and evaluation j's update at eval_offset + j + 1, so a request cut into
+ * several calls draws what the uncut one draws.  source_guidance / target_guidance: the distilled-guidance value of each half of the batch.
+ * Tables, ids and the offset are device data staged with the call's schedule; "fe_z" and -- only when some row lacks first or apply --
+ * "fe_acc" are made at the first edit call of a prepared shape.  All of it is counted in fluxmi_engine_workspace_bytes and dropped with the
+ * workspace.  x0_dev == NULL switches the state off; a prepare that re-allocates the workspace does too.  fluxmi_engine_denoise and
+ * _denoise_cfg do not consult the state: a request without it allocates and launches exactly what it did before. */
+int fluxmi_engine_set_flow_edit(fluxmi_engine_t* e, const void* x0_dev, int batch, const double* coef_host, const int* ctl_host, int n,
+                                const unsigned* ids_host, int eval_offset, float source_guidance, float target_guidance, void* stream);
+/* The edit loop: fluxmi_engine_denoise's loop -- calibrating steps, then frozen steps replayed from ONE captured graph -- on the 2 x batch
+ * samples, with fluxmi_flowedit_step as every update.  z: bf16 [batch, Li, C], the edit state, in and out; txt [2 batch, Lt, ctx] and y
+ * [2 batch, vec]: the source branches, then the target branches; timesteps_host[j], j < n_evals: the model time of evaluation j.  z is copied
+ * to "fe_z", one coupling at (timesteps_host[0], eval_offset) fills the stream, and at the end "fe_z" is copied back.  Edit versus not is a
+ * kind of step graph: seeds, offset, guidance pair and schedule are device data.  Refused: no state set, n_evals != its n, a batch other than
+ * half the (even) prepared batch, reference rows or conditioning channels, an inpainting state, a solver program, step caching, an
+ * attention-group table, an attached ControlNet, an IP-Adapter, and a step hook with every > 0 (a hook with every = 0 works: evaluation
+ * counts model evaluations). */
+int fluxmi_engine_denoise_edit(fluxmi_engine_t* e, void* z, const void* txt, const void* y, const double* timesteps_host, int n_evals,
+                               int* trial_index_inout, int use_graph, void* stream);
 /* Guidance shaping (fluxmi_guidance_moments / _combine) for the following fluxmi_engine_denoise_cfg calls on the PREPARED
  * shape: every step of those calls -- calibrating, graph-replayed, both tails of a step-cached step -- launches moments and combine on
  * "pred_s" immediately in front of the update kernel the request already had (guided Euler, blend, solver, with or without noise), which

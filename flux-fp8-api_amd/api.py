@@ -25,6 +25,8 @@ Same two POST endpoints, request fields, defaults and status codes:
              source_prompt=None (FlowEdit: the prompt that describes init_image; `prompt` is then the target), source_guidance=None,
              edit_n_max=None (>= 0), edit_n_min=None (>= 0), edit_n_avg=None (>= 1) -- text-guided editing of init_image
              (FluxPipeline.generate), each passed on only when set;
+             tile_size=None (an int or [height, width] in pixels), tile_overlap=None (>= 0, pixels), tile_weight=None ("cosine" | "uniform")
+             -- tiled generation: a large canvas stepped from overlapping windows (FluxPipeline.generate), each passed on only when set;
              stream=None, preview_every=None (>= 0) -- progress, live previews and cancellation, see below;
              a region with both or neither of box / mask, or a box outside 0 <= x0 < x1 <= 1, is a 422}
              ->  image/jpeg stream of FluxPipeline.generate(**args)                                               (reference api.py:54-86)
@@ -125,6 +127,9 @@ class GenerateArgs(BaseModel):
     edit_n_max: Optional[int] = Field(default=None, ge=0)  # ... the last edit_n_max steps are edited (default: every step)
     edit_n_min: Optional[int] = Field(default=None, ge=0)  # ... the last edit_n_min of them as a plain Euler tail on the target prompt (default 0)
     edit_n_avg: Optional[int] = Field(default=None, ge=1)  # ... model evaluations averaged per step (default 1)
+    tile_size: Optional[Union[int, Tuple[int, int]]] = None  # tiled generation: the window in pixels, an int (square) or [height, width] (FluxPipeline.generate)
+    tile_overlap: Optional[int] = Field(default=None, ge=0)  # ... the overlap of neighbouring windows in pixels (default: a quarter of the tile)
+    tile_weight: Optional[str] = None  # ... "cosine" (default) | "uniform": how overlapping windows are blended
     stream: Optional[bool] = None  # answer with application/x-ndjson progress lines and a final result line instead of the JPEG
     preview_every: Optional[int] = Field(default=None, ge=0)  # ... with a latent-resolution preview at every k-th model evaluation (0 = none)
 
@@ -190,7 +195,7 @@ def generate(args: GenerateArgs):
     `control_mode`, `control_guidance_start` / `_end`) a FLUX ControlNet, `ip_adapter_image` / `ip_adapter_image_embeds` (+ `ip_adapter_scale`,
     `negative_ip_adapter_image`, `negative_ip_adapter_scale`) a FLUX IP-Adapter, `guidance_mode` / `guidance_rescale` / `apg_*` /
     `zero_init_steps` guidance shaping of a guided request, `source_prompt` (+ `source_guidance`, `edit_n_max` / `_min` / `_avg`) a FlowEdit edit of
-    `init_image` towards `prompt`.  Without them the call is exactly the reference's."""
+    `init_image` towards `prompt`, `tile_size` (+ `tile_overlap`, `tile_weight`) tiled generation of a large canvas.  Without them the call is exactly the reference's."""
     kwargs = args.model_dump()
     stream = bool(kwargs.pop("stream", None))
     if kwargs.get("preview_every") is None:
@@ -202,7 +207,8 @@ def generate(args: GenerateArgs):
               "controlnet_conditioning_scale", "control_mode", "control_guidance_start", "control_guidance_end", "sampler", "sigma_schedule",
               "sigmas", "eta", "s_noise", "noise_seed", "ip_adapter_image", "ip_adapter_image_embeds", "ip_adapter_scale",
               "negative_ip_adapter_image", "negative_ip_adapter_scale", "guidance_mode", "guidance_rescale", "apg_eta", "apg_norm_threshold",
-              "apg_momentum", "zero_init_steps", "source_prompt", "source_guidance", "edit_n_max", "edit_n_min", "edit_n_avg"):
+              "apg_momentum", "zero_init_steps", "source_prompt", "source_guidance", "edit_n_max", "edit_n_min", "edit_n_avg", "tile_size",
+              "tile_overlap", "tile_weight"):
         if kwargs.get(k) is None:
             kwargs.pop(k, None)
     if "ip_adapter_image_embeds" in kwargs:

@@ -5,6 +5,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <vector>
+
 #include "fluxmi_internal.h"
 
 static thread_local char g_err[1024] = "";
@@ -272,6 +274,37 @@ int fluxmi_flowedit_step(void* img, const void* pred, void* z, float* acc, const
                    "stored by a row without apply and read by a row without first)", i, row[0], row[1]);
   }
   return fluxmi_k_flowedit_step(img, pred, z, acc, x0, coef, ctl, step, ids, eval_offset, B, img_rows, pred_rows, c_in, c_out, s);
+}
+
+// The tables are device data and the placement rules speak of their contents: these entries (tests and tools; the engine is given host
+// tables and calls the launchers) read row0 / col0 back -- one synchronising copy each -- before they launch
+static int window_tables_ok(const char* who, const int* row0, const int* col0, int Hc, int Wc, int h, int w, int ny, int nx, hipStream_t s) {
+  FLUXMI_REQUIRE(ny >= 1 && nx >= 1 && ny <= 65536 && nx <= 65536, "%s: window grid %d x %d out of range", who, ny, nx);
+  std::vector<int> r((size_t)ny), c((size_t)nx);
+  FLUXMI_CHECK_HIP(hipMemcpyAsync(r.data(), row0, (size_t)ny * 4, hipMemcpyDeviceToHost, s));
+  FLUXMI_CHECK_HIP(hipMemcpyAsync(c.data(), col0, (size_t)nx * 4, hipMemcpyDeviceToHost, s));
+  FLUXMI_CHECK_HIP(hipStreamSynchronize(s));
+  return fluxmi_window_check_tables(who, r.data(), c.data(), Hc, Wc, h, w, ny, nx);
+}
+int fluxmi_window_gather(const void* canvas, void* img, const int* row0, const int* col0, int N, int Hc, int Wc, int h, int w, int ny, int nx,
+                         int C, int guided, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  FLUXMI_REQUIRE(row0 && col0, "window_gather: NULL tables (row0 int32 [ny], col0 int32 [nx] on the device)");
+  FLUXMI_REQUIRE(C > 0 && C % 8 == 0 && Hc >= 1 && Wc >= 1 && h >= 1 && w >= 1 && h <= Hc && w <= Wc, "window_gather: C=%d (C %% 8 == 0), "
+                 "window %d x %d inside the canvas %d x %d", C, h, w, Hc, Wc);
+  FLUXMI_TRY(window_tables_ok("window_gather", row0, col0, Hc, Wc, h, w, ny, nx, s));
+  return fluxmi_k_window_gather(canvas, img, row0, col0, N, Hc, Wc, h, w, ny, nx, C, guided, s);
+}
+int fluxmi_window_step(void* canvas, void* img, const void* pred, const float* dts, const int* step, const float* scale, const int* row0,
+                       const int* col0, const float* Ny, const float* Nx, int N, int Hc, int Wc, int h, int w, int ny, int nx, int C,
+                       void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  FLUXMI_REQUIRE(row0 && col0 && Ny && Nx, "window_step: NULL tables (row0 int32 [ny], col0 int32 [nx], Ny fp32 [ny][Hc], Nx fp32 [nx][Wc] on "
+                 "the device)");
+  FLUXMI_REQUIRE(C > 0 && C % 8 == 0 && Hc >= 1 && Wc >= 1 && h >= 1 && w >= 1 && h <= Hc && w <= Wc, "window_step: C=%d (C %% 8 == 0), "
+                 "window %d x %d inside the canvas %d x %d", C, h, w, Hc, Wc);
+  FLUXMI_TRY(window_tables_ok("window_step", row0, col0, Hc, Wc, h, w, ny, nx, s));
+  return fluxmi_k_window_step(canvas, img, pred, dts, step, scale, row0, col0, Ny, Nx, N, Hc, Wc, h, w, ny, nx, C, s);
 }
 
 int fluxmi_fb_snapshot(const void* x, long long x_bstride, void* dst, int B, long long n, void* stream) {

@@ -57,6 +57,9 @@ struct StepGraphs {
   bool noise = false;   // ... and its form with the noise term (fluxmi_engine_set_solver_noise): seeds and the offset are device data
   bool edit = false;    // ... and FlowEdit's update (fluxmi_engine_denoise_edit): tables, ids, offset and the guidance pair are device data ...
   const void* fe_acc = nullptr;  // ... its fp32 accumulator is a launch argument: null until a program that averages has made the buffer
+  bool win = false;     // ... and the windowed update (fluxmi_engine_denoise_windows): tables and scale are device data; the canvas geometry, which
+  int win_geo[7] = {0, 0, 0, 0, 0, 0, 0};  // ... is a launch argument, and the canvas's address are part of the key
+  const void* win_x = nullptr;
   bool shaped = false;  // guidance shaping (fluxmi_engine_set_guidance): two launches in front of the guided update; mode and values are device data
   bool previewed = false;  // the preview launch in front of the update (fluxmi_engine_set_preview, every > 0): cadence, offset and factors are device data ...
   int pv_h = 0, pv_w = 0;  // ... the token grid is a launch argument
@@ -198,6 +201,15 @@ struct fluxmi_engine {
   std::vector<unsigned> fe_ids;    // [fe_B][4]
   char *fe_mem = nullptr, *fe_zmem = nullptr, *fe_accmem = nullptr;
   size_t fe_bytes = 0, fe_zbytes = 0, fe_accbytes = 0;
+  // Tiled generation (fluxmi_engine_set_windows / _denoise_windows): the geometry {N, Hc, Wc, h, w, ny, nx} of the
+  // following windowed calls.  Device side, one allocation dropped with the workspace: win_mem = "win_x" (the canvas, bf16 [N, Hc, Wc, C]) |
+  // "win_tab" (row0 int [ny] | col0 int [nx] | Ny fp32 [ny][Hc] | Nx fp32 [nx][Wc], each 256-byte aligned, filled by the set call).  Nothing
+  // of it without a windowed request.  win_call: the running denoise call is a windowed call.
+  bool win_on = false, win_call = false;
+  int win_geo[7] = {0, 0, 0, 0, 0, 0, 0};
+  size_t win_off[4] = {0, 0, 0, 0};  // the four tables' offsets in "win_tab"
+  char* win_mem = nullptr;
+  size_t win_bytes = 0;
   // ControlNet (fluxmi_controlnet_create / fluxmi_engine_attach_controlnet).  A net is an engine of its own kind
   // (is_cn): no final layer, the controlnet_* projections behind the trunk's linears, the residuals of a forward in its workspace buffer
   // "cn_res" [Nd + Ns][B, Li, H].  The main engine holds the attached net (cn) and the conditioning scale (d_cn_scale, device data).
@@ -1203,6 +1215,8 @@ void free_ws(E* e) {
   if (e->fe_zmem) { hipFree(e->fe_zmem); e->fe_zmem = nullptr; e->fe_zbytes = 0; }
   if (e->fe_accmem) { hipFree(e->fe_accmem); e->fe_accmem = nullptr; e->fe_accbytes = 0; }
   e->fe_on = false;
+  if (e->win_mem) { hipFree(e->win_mem); e->win_mem = nullptr; e->win_bytes = 0; e->bufs.erase("win_x"); e->bufs.erase("win_tab"); }
+  e->win_on = false;
   if (e->gd_mem) { hipFree(e->gd_mem); e->gd_mem = nullptr; e->gd_bytes = 0; }
   e->gd_on = e->gd_zero_r = false;
   if (e->ip_mem) { hipFree(e->ip_mem); e->ip_mem = nullptr; e->ip_bytes = 0; }
@@ -1754,6 +1768,12 @@ static void graphs_stale(fluxmi_engine_t* e, StepGraphs& g, bool cfg) {
   if (g.cfg != cfg || g.masked != e->masked || g.blend != e->inp_on || g.diff != diff || g.solver != e->sol_on || g.noise != e->sol_noise ||
       g.shaped != shaped || g.edit != e->fe_call || g.fe_acc != fe_acc)
     g.ok = g.warmed = false;
+  // ... and the windowed update with its canvas: a windowed request never replays a plain or guided request's pieces, nor they its
+  const void* win_x = e->win_call ? e->win_mem : nullptr;
+  if (g.win != e->win_call || g.win_x != win_x || (e->win_call && memcmp(g.win_geo, e->win_geo, sizeof g.win_geo) != 0)) g.ok = g.warmed = false;
+  g.win = e->win_call;
+  g.win_x = win_x;
+  if (e->win_call) memcpy(g.win_geo, e->win_geo, sizeof g.win_geo); else memset(g.win_geo, 0, sizeof g.win_geo);
   // ... and the preview launch with its token grid (cadence, offset and factors are device data: they never re-capture)
   const bool previewed = e->pv_hook && e->pv_every > 0;
   if (g.previewed != previewed || (previewed && (g.pv_h != e->pv_h || g.pv_w != e->pv_w))) g.ok = g.warmed = false;
@@ -2000,9 +2020,10 @@ static int cached_steps(fluxmi_engine_t* e, int mode, bool cfg, int step, int n_
 // the target branches -- but the halves hold different latents, `img` is the caller's edit state z [Bh, ...], and the update is
 // fluxmi_k_flowedit_step on the engine's "fe_z" / "fe_x0": the stream only carries the two model inputs the kernel rebuilds.
 static int denoise_impl(fluxmi_engine_t* e, void* img, const void* txt, const void* y, float guidance, bool cfg, float cfg_scale,
-                        const double* timesteps_host, int n_steps, int* trial_index_inout, int use_graph, void* stream, bool edit = false) {
+                        const double* timesteps_host, int n_steps, int* trial_index_inout, int use_graph, void* stream, bool edit = false,
+                        bool win = false) {
   hipStream_t s = (hipStream_t)stream;
-  if (e) e->fe_call = false;
+  if (e) e->fe_call = e->win_call = false;
   FLUXMI_REQUIRE(e && e->ws, "engine_denoise: call fluxmi_engine_prepare first");
   FLUXMI_REQUIRE(!e->is_cn, "engine_denoise: a ControlNet engine runs attached to a main engine (fluxmi_engine_attach_controlnet)");
   FLUXMI_REQUIRE(!cfg || e->B % 2 == 0, "engine_denoise_cfg: the prepared batch (%d) must be even: prompt branches first, then the negative "
@@ -2033,9 +2054,30 @@ static int denoise_impl(fluxmi_engine_t* e, void* img, const void* txt, const vo
     if (e->fe_need_acc) FLUXMI_TRY(ensure_fe_acc(e, s));
     e->fe_call = true;
   }
-  struct EditCallScope {  // fe_call speaks of the running call only: off again on every way out
+  if (win) {
+    const int *g = e->win_geo, S = g[0] * g[5] * g[6];
+    FLUXMI_REQUIRE(e->win_on, "engine_denoise_windows: no window state is set (fluxmi_engine_set_windows)");
+    FLUXMI_REQUIRE(e->B == (cfg ? 2 * S : S) && e->Li == g[3] * g[4], "engine_denoise_windows: the window state holds %d images x %d x %d "
+                   "windows of %d x %d tokens, the prepared shape %d samples of %d rows (%s: %d samples of %d)", g[0], g[5], g[6], g[3], g[4],
+                   e->B, e->Li, cfg ? "guided" : "unguided", cfg ? 2 * S : S, g[3] * g[4]);
+    FLUXMI_REQUIRE(e->Lpred == e->Li && c_out(e) == e->d.in_channels, "engine_denoise_windows: %d reference rows, %d input and %d predicted "
+                   "channels: a windowed call steps the whole stream (no Kontext reference, no Fill / Depth / Canny model)", e->Li - e->Lpred,
+                   e->d.in_channels, c_out(e));
+    FLUXMI_REQUIRE(!e->inp_on, "engine_denoise_windows: an inpainting state is set (windows are not combined with a mask)");
+    FLUXMI_REQUIRE(!e->sol_on, "engine_denoise_windows: a solver program is set (the windowed update is its own: sampler euler only)");
+    FLUXMI_REQUIRE(!(e->fb_threshold > 0.f), "engine_denoise_windows: step caching is on (not combined with windows)");
+    FLUXMI_REQUIRE(!e->masked, "engine_denoise_windows: an attention-group table is set (regional prompts do not combine with windows)");
+    FLUXMI_REQUIRE(!e->cn, "engine_denoise_windows: a ControlNet is attached (not combined with windows)");
+    FLUXMI_REQUIRE(!e->ip_on, "engine_denoise_windows: an IP-Adapter is set (not combined with windows)");
+    FLUXMI_REQUIRE(!e->fe_on, "engine_denoise_windows: a FlowEdit state is set (not combined with windows)");
+    FLUXMI_REQUIRE(!(cfg && e->gd_on), "engine_denoise_windows: guidance shaping is set (a guided windowed call is unshaped)");
+    FLUXMI_REQUIRE(!(e->pv_hook && e->pv_every > 0), "engine_denoise_windows: previews (every = %d > 0) are refused: the stream holds windows, "
+                   "not the canvas (a hook with every = 0 reports progress and cancels)", e->pv_every);
+    e->win_call = true;
+  }
+  struct EditCallScope {  // fe_call and win_call speak of the running call only: off again on every way out
     fluxmi_engine_t* e;
-    ~EditCallScope() { e->fe_call = false; }
+    ~EditCallScope() { e->fe_call = e->win_call = false; }
   } edit_scope{e};
   Range whole("fluxmi_engine_denoise");
   SplitkScope splitk(e);
@@ -2079,8 +2121,16 @@ static int denoise_impl(fluxmi_engine_t* e, void* img, const void* txt, const vo
   if (previewed) FLUXMI_TRY(ensure_pv(e, s));
   e->pv_launched = e->pv_delivered = 0;
   e->pv_cancelled = false;
-  e->pv_images = cfg || edit ? B / 2 : B;
+  e->pv_images = win ? e->win_geo[0] : (cfg || edit ? B / 2 : B);
   auto euler = [&](hipStream_t st) -> int {
+    if (win) {
+      const int* g = e->win_geo;
+      const char* tab = buf<char>(e, "win_tab");
+      return fluxmi_k_window_step(buf<u16>(e, "win_x"), buf<u16>(e, "img_s"), buf<u16>(e, "pred_s"), e->d_dts, e->d_step,
+                                  cfg ? e->d_cfg : nullptr, (const int*)(tab + e->win_off[0]), (const int*)(tab + e->win_off[1]),
+                                  (const float*)(tab + e->win_off[2]), (const float*)(tab + e->win_off[3]), g[0], g[1], g[2], g[3], g[4], g[5],
+                                  g[6], C, st);
+    }
     if (edit) {
       const char* tab = buf<char>(e, "fe_tab");
       return fluxmi_k_flowedit_step(buf<u16>(e, "img_s"), buf<u16>(e, "pred_s"), buf<u16>(e, "fe_z"), buf<float>(e, "fe_acc"),
@@ -2227,8 +2277,16 @@ static int denoise_impl(fluxmi_engine_t* e, void* img, const void* txt, const vo
   }
   FLUXMI_CHECK_HIP(hipMemsetAsync(e->d_step, 0, 4, s));
   u16 *img_s = buf<u16>(e, "img_s"), *txt_s = buf<u16>(e, "txt_s"), *y_s = buf<u16>(e, "y_s"), *pred_s = buf<u16>(e, "pred_s");
-  const long long n_img = (long long)(cfg || edit ? B / 2 : B) * Li * C;  // the caller's samples
-  if (edit) {  // the caller's edit state goes beside the stream; the first coupling, at the first evaluation's time, fills both halves of it
+  const long long n_img = win ? (long long)e->win_geo[0] * e->win_geo[1] * e->win_geo[2] * C  // (a windowed call: the caller's canvas)
+                              : (long long)(cfg || edit ? B / 2 : B) * Li * C;                 // the caller's samples
+  if (win) {  // the caller's canvas goes beside the stream; one gather fills every window of it (guided: both halves)
+    const int* g = e->win_geo;
+    const char* tab = buf<char>(e, "win_tab");
+    u16* wx = buf<u16>(e, "win_x");
+    FLUXMI_CHECK_HIP(hipMemcpyAsync(wx, img, n_img * 2, hipMemcpyDeviceToDevice, s));
+    FLUXMI_TRY(fluxmi_k_window_gather(wx, img_s, (const int*)(tab + e->win_off[0]), (const int*)(tab + e->win_off[1]), g[0], g[1], g[2], g[3],
+                                      g[4], g[5], g[6], C, cfg ? 1 : 0, s));
+  } else if (edit) {  // the caller's edit state goes beside the stream; the first coupling, at the first evaluation's time, fills both halves of it
     u16* fz = buf<u16>(e, "fe_z");
     FLUXMI_CHECK_HIP(hipMemcpyAsync(fz, img, n_img * 2, hipMemcpyDeviceToDevice, s));
     if (n_steps > 0)
@@ -2239,7 +2297,7 @@ static int denoise_impl(fluxmi_engine_t* e, void* img, const void* txt, const vo
     FLUXMI_CHECK_HIP(hipMemcpyAsync(img_s, img, n_img * 2, hipMemcpyDeviceToDevice, s));
   }
   if (cfg) {
-    FLUXMI_CHECK_HIP(hipMemcpyAsync(img_s + n_img, img, n_img * 2, hipMemcpyDeviceToDevice, s));
+    if (!win) FLUXMI_CHECK_HIP(hipMemcpyAsync(img_s + n_img, img, n_img * 2, hipMemcpyDeviceToDevice, s));
     unsigned bits;
     memcpy(&bits, &cfg_scale, 4);
     FLUXMI_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)e->d_cfg, (int)bits, 1, s));
@@ -2314,7 +2372,7 @@ static int denoise_impl(fluxmi_engine_t* e, void* img, const void* txt, const vo
   while (hooked && !e->pv_cancelled && e->pv_delivered < e->pv_launched) FLUXMI_TRY(pv_deliver(e, e->pv_delivered));
   if (e->pv_cancelled && e->pv_launched > 0)
     FLUXMI_CHECK_HIP(hipEventSynchronize(e->pv_ev[(e->pv_launched - 1) % (FLUXMI_PREVIEW_DEPTH + 1)]));
-  FLUXMI_CHECK_HIP(hipMemcpyAsync(img, edit ? buf<u16>(e, "fe_z") : img_s, n_img * 2, hipMemcpyDeviceToDevice, s));
+  FLUXMI_CHECK_HIP(hipMemcpyAsync(img, win ? buf<u16>(e, "win_x") : (edit ? buf<u16>(e, "fe_z") : img_s), n_img * 2, hipMemcpyDeviceToDevice, s));
   *trial_index_inout = trial;
   if (e->pv_cancelled) {
     fluxmi_set_error("engine_denoise: cancelled by the step hook after %d of %d evaluations", e->pv_launched, n_steps);
@@ -2336,6 +2394,73 @@ int fluxmi_engine_denoise_cfg(fluxmi_engine_t* e, void* img, const void* txt, co
 int fluxmi_engine_denoise_edit(fluxmi_engine_t* e, void* z, const void* txt, const void* y, const double* timesteps_host, int n_evals,
                                int* trial_index_inout, int use_graph, void* stream) {
   return denoise_impl(e, z, txt, y, 0.f, false, 1.f, timesteps_host, n_evals, trial_index_inout, use_graph, stream, true);
+}
+
+int fluxmi_engine_denoise_windows(fluxmi_engine_t* e, void* canvas, const void* txt, const void* y, float guidance, int guided, float cfg_scale,
+                                  const double* timesteps_host, int n_steps, int* trial_index_inout, int use_graph, void* stream) {
+  return denoise_impl(e, canvas, txt, y, guidance, guided != 0, cfg_scale, timesteps_host, n_steps, trial_index_inout, use_graph, stream, false,
+                      true);
+}
+
+// The window state of the following windowed calls (fluxmi.h): the geometry, and the four host tables copied into the engine's own buffer
+// on `stream` (the call returns behind one stream synchronisation: the host tables are the caller's).
+int fluxmi_engine_set_windows(fluxmi_engine_t* e, int n_images, int Hc, int Wc, int h, int w, int ny, int nx, const int* row0_host,
+                              const int* col0_host, const float* Ny_host, const float* Nx_host, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  FLUXMI_REQUIRE(e, "engine_set_windows: NULL engine");
+  if (!row0_host) {
+    e->win_on = false;
+    return 0;
+  }
+  FLUXMI_REQUIRE(!e->is_cn, "engine_set_windows: a ControlNet engine steps nothing (set the state on the main engine)");
+  FLUXMI_REQUIRE(e->ws, "engine_set_windows: call fluxmi_engine_prepare first (the state belongs to the prepared shape)");
+  FLUXMI_REQUIRE(col0_host && Ny_host && Nx_host, "engine_set_windows: row0_host, col0_host, Ny_host and Nx_host go together");
+  FLUXMI_REQUIRE(n_images >= 1 && Hc >= 1 && Wc >= 1 && h >= 1 && w >= 1 && ny >= 1 && nx >= 1 && h <= Hc && w <= Wc,
+                 "engine_set_windows: bad geometry: %d images, canvas %d x %d, windows %d x %d on a %d x %d grid", n_images, Hc, Wc, h, w, ny, nx);
+  FLUXMI_REQUIRE((long long)n_images * ny * nx <= FLUXMI_ENGINE_MAX_BATCH && (long long)n_images * ny * nx <= e->B,
+                 "engine_set_windows: %d images x %d x %d windows do not fit the prepared batch of %d samples (one pass: at most %d, half of it "
+                 "for a guided call)", n_images, ny, nx, e->B, FLUXMI_ENGINE_MAX_BATCH);
+  FLUXMI_REQUIRE(h * w == e->Li, "engine_set_windows: a window of %d x %d tokens is not the prepared shape's %d image rows", h, w, e->Li);
+  FLUXMI_REQUIRE((double)n_images * Hc * Wc * (c_out(e) / 8) <= 2147483647.0, "engine_set_windows: the canvas exceeds the kernel's 32-bit index");
+  FLUXMI_TRY(fluxmi_window_check_tables("engine_set_windows", row0_host, col0_host, Hc, Wc, h, w, ny, nx));
+  for (long long i = 0; i < (long long)ny * Hc; ++i)
+    FLUXMI_REQUIRE(std::isfinite(Ny_host[i]), "engine_set_windows: Ny[%lld][%lld] is not finite", i / Hc, i % Hc);
+  for (long long i = 0; i < (long long)nx * Wc; ++i)
+    FLUXMI_REQUIRE(std::isfinite(Nx_host[i]), "engine_set_windows: Nx[%lld][%lld] is not finite", i / Wc, i % Wc);
+  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t x_bytes = (size_t)n_images * Hc * Wc * c_out(e) * 2;
+  const size_t sz[4] = {(size_t)ny * 4, (size_t)nx * 4, (size_t)ny * Hc * 4, (size_t)nx * Wc * 4};
+  size_t off[4], tab_bytes = 0;
+  for (int i = 0; i < 4; ++i) { off[i] = tab_bytes; tab_bytes += up(sz[i]); }
+  const size_t total = up(x_bytes) + tab_bytes;
+  if (e->win_mem && e->win_bytes != total) {  // another geometry: pieces captured on the old canvas go stale by the key (graphs_stale)
+    FLUXMI_CHECK_HIP(hipStreamSynchronize(s));
+    hipFree(e->win_mem);
+    e->win_mem = nullptr;
+    e->win_bytes = 0;
+    e->win_on = false;
+  }
+  if (!e->win_mem) {
+    if (hipMalloc((void**)&e->win_mem, total) != hipSuccess) {
+      (void)hipGetLastError();
+      e->win_mem = nullptr;
+      fluxmi_set_error("engine_set_windows: hipMalloc(%zu bytes) failed (win_x)", total);
+      return 2;
+    }
+    e->win_bytes = total;
+    FLUXMI_CHECK_HIP(hipMemsetAsync(e->win_mem, 0, total, s));
+  }
+  e->bufs["win_x"] = Buf{e->win_mem, x_bytes};
+  e->bufs["win_tab"] = Buf{e->win_mem + up(x_bytes), tab_bytes};
+  char* tab = e->win_mem + up(x_bytes);
+  const void* src[4] = {row0_host, col0_host, Ny_host, Nx_host};
+  for (int i = 0; i < 4; ++i) FLUXMI_CHECK_HIP(hipMemcpyAsync(tab + off[i], src[i], sz[i], hipMemcpyHostToDevice, s));
+  FLUXMI_CHECK_HIP(hipStreamSynchronize(s));
+  const int geo[7] = {n_images, Hc, Wc, h, w, ny, nx};
+  memcpy(e->win_geo, geo, sizeof geo);
+  memcpy(e->win_off, off, sizeof off);
+  e->win_on = true;
+  return 0;
 }
 
 // The FlowEdit state of the following edit calls (fluxmi.h): host tables like the solver program's; x0 is copied into the engine's own buffer
@@ -2788,7 +2913,7 @@ int fluxmi_engine_copy_buffer(fluxmi_engine_t* e, const char* name, long long of
 
 int fluxmi_engine_workspace_bytes(fluxmi_engine_t* e, long long* bytes) {
   FLUXMI_REQUIRE(e && bytes, "engine_workspace_bytes: NULL argument");
-  *bytes = (long long)(e->ws_bytes + e->pairs_bytes + e->mods_all_bytes + e->fb_bytes + e->inp_bytes + e->sol_bytes + e->sol_ids_bytes + e->ip_bytes + e->gd_bytes + e->pv_bytes + e->fe_bytes + e->fe_zbytes + e->fe_accbytes);  // workspace + row-pair weight copies + modulation table + step cache + inpainting + solver buffers + noise ids + adapter + guidance shaping + preview ring + FlowEdit state
+  *bytes = (long long)(e->ws_bytes + e->pairs_bytes + e->mods_all_bytes + e->fb_bytes + e->inp_bytes + e->sol_bytes + e->sol_ids_bytes + e->ip_bytes + e->gd_bytes + e->pv_bytes + e->fe_bytes + e->fe_zbytes + e->fe_accbytes + e->win_bytes);  // (+ the window canvas and tables) workspace + row-pair weight copies + modulation table + step cache + inpainting + solver buffers + noise ids + adapter + guidance shaping + preview ring + FlowEdit state
   return 0;
 }
 

@@ -190,6 +190,15 @@ int fluxmi_k_flowedit_couple(void* img, const void* z, const void* x0, float t, 
 int fluxmi_k_flowedit_step(void* img, const void* pred, void* z, float* acc, const void* x0, const float* coef, const int* ctl, const int* step,
                            const unsigned* ids, const int* eval_offset, int B, long long img_rows, long long pred_rows, int c_in, int c_out,
                            hipStream_t s);
+// Tiled generation (window_step.hip; include/fluxmi.h, fluxmi_window_gather / _step): the canvas bf16 [N, Hc, Wc, C] beside a stream of
+// N * ny * nx windows of h x w tokens (2x when guided: scale != NULL / guided != 0), row0 / col0 / Ny / Nx DEVICE tables.  The launchers do not
+// see the tables (the kernel never leaves the stream whatever they hold): fluxmi_window_check_tables applies the placement rules to HOST copies
+int fluxmi_k_window_gather(const void* canvas, void* img, const int* row0, const int* col0, int N, int Hc, int Wc, int h, int w, int ny, int nx,
+                           int C, int guided, hipStream_t s);
+int fluxmi_k_window_step(void* canvas, void* img, const void* pred, const float* dts, const int* step, const float* scale, const int* row0,
+                         const int* col0, const float* Ny, const float* Nx, int N, int Hc, int Wc, int h, int w, int ny, int nx, int C,
+                         hipStream_t s);
+int fluxmi_window_check_tables(const char* who, const int* row0, const int* col0, int Hc, int Wc, int h, int w, int ny, int nx);
 // first-block step cache (elementwise.hip): streaming passes over B samples of n bf16 elements, x side strided, cache side dense
 int fluxmi_k_fb_snapshot(const void* x, long long x_bstride, void* dst, int B, long long n, hipStream_t s);
 int fluxmi_k_fb_commit(const void* x, long long x_bstride, const void* r, void* r_ref, void* h1, int B, long long n, hipStream_t s);

@@ -261,19 +261,21 @@ class FluxPipeline:
     @torch.inference_mode()
     def preprocess_latent(self, init_image=None, height: int = 720, width: int = 1024, num_steps: int = 20, strength: float = 1.0,
                           generator: torch.Generator = None, num_images: int = 1, noise: Optional[torch.Tensor] = None, sigmas=None,
-                          sigma_schedule=None):
+                          sigma_schedule=None, image_seq_len: Optional[int] = None):
         """reference flux_pipeline.py:459-523: noise + schedule; with an init image: VAE-encode it, start the schedule at
         t_idx = int((1 - strength) * num_steps) and blend x = t * noise + (1 - t) * latent."""
-        return self.preprocess_latent_parts(init_image, height, width, num_steps, strength, generator, num_images, noise, sigmas, sigma_schedule)[:2]
+        return self.preprocess_latent_parts(init_image, height, width, num_steps, strength, generator, num_images, noise, sigmas, sigma_schedule,
+                                            image_seq_len)[:2]
 
     @torch.inference_mode()
     def preprocess_latent_parts(self, init_image=None, height: int = 720, width: int = 1024, num_steps: int = 20, strength: float = 1.0,
                                 generator: torch.Generator = None, num_images: int = 1, noise: Optional[torch.Tensor] = None, sigmas=None,
-                                sigma_schedule=None):
+                                sigma_schedule=None, image_seq_len: Optional[int] = None):
         """preprocess_latent, with what it blends: -> (x, timesteps, latent, noise).  `latent` = the VAE latent of `init_image` [num_images,
         16, H/8, W/8] in the flow dtype (None without an init image: one encode per request), `noise` = the pure draw before the blend.
         Masked-latent inpainting re-blends these two at every step (Flux.denoise).  `sigmas` (num_steps + 1 values ending at 0) replaces
-        get_schedule's list; `sigma_schedule` ("karras" / "exponential") re-spaces either one (fluxmi.solvers.sigma_schedule)."""
+        get_schedule's list; `sigma_schedule` ("karras" / "exponential") re-spaces either one (fluxmi.solvers.sigma_schedule).
+        `image_seq_len`: the sequence length the schedule's shift follows (None: the latent's own; a tiled request passes its window's)."""
         if init_image is not None:
             if self.ae is None:
                 raise RuntimeError("fluxmi: img2img needs an autoencoder (config.ae_path) -- none is attached")
@@ -284,7 +286,8 @@ class FluxPipeline:
             init_image = self.ae.encode(init_image).to(dtype=self.dtype, device=self.device_flux).repeat(num_images, 1, 1, 1)
         x = self.get_noise(num_images, height, width, generator=generator) if noise is None else noise
         x = x.to(device=self.device_flux, dtype=self.dtype)
-        timesteps = self.get_schedule(num_steps, x.shape[-1] * x.shape[-2] // 4, shift=(self.name != "flux-schnell"))
+        timesteps = self.get_schedule(num_steps, x.shape[-1] * x.shape[-2] // 4 if image_seq_len is None else int(image_seq_len),
+                                      shift=(self.name != "flux-schnell"))
         if sigmas is not None:
             if len(sigmas) != num_steps + 1:
                 raise ValueError(f"fluxmi: {len(sigmas)} sigmas for {num_steps} steps (one more than steps)")
@@ -699,7 +702,8 @@ class FluxPipeline:
                  negative_ip_adapter_image=None, negative_ip_adapter_scale=1.0, guidance_mode: str = "cfg", guidance_rescale: float = 0.0,
                  apg_eta: float = 1.0, apg_norm_threshold: float = 0.0, apg_momentum: float = 0.0, zero_init_steps: int = 0,
                  on_step=None, preview_every: int = 0, preview_factors=None, source_prompt=None, source_guidance: Optional[float] = None,
-                 edit_n_max: Optional[int] = None, edit_n_min: int = 0, edit_n_avg: int = 1):
+                 edit_n_max: Optional[int] = None, edit_n_min: int = 0, edit_n_avg: int = 1, tile_size=None, tile_overlap: Optional[int] = None,
+                 tile_weight: str = "cosine"):
         """`reference_image` (FLUX.1 Kontext [dev] instruction editing): an image the prompt describes an edit of, in any form `init_image`
         takes; see prepare_kontext_reference.  Composes with `init_image` / `strength` unchanged.
         FLUX.1 Fill [dev] (a model with 320 conditioning channels): `init_image` is the image to inpaint and `mask_image` (white =
@@ -816,7 +820,29 @@ class FluxPipeline:
         `num_images` (at most 16), `sigmas` / `sigma_schedule` and `on_step` (progress and cancellation; no previews); refused with a
         negative prompt at a scale > 1, `inpaint_mask`, `reference_image`, a Fill / Depth / Canny model, `regions`, `cache_threshold` > 0,
         a ControlNet, an IP-Adapter, `redux_image`, `preview_every` > 0 and under a process group.  Without `source_prompt` the request is
-        today's, launch for launch, and `source_guidance` / `edit_*` are refused."""
+        today's, launch for launch, and `source_guidance` / `edit_*` are refused.
+        `tile_size` (tiled generation; MultiDiffusion, Bar-Tal et al. 2023, known as tiled diffusion): an int (a square window) or (height,
+        width) in pixels, multiples of 16, at most the request's size.  The request's latent is then one large canvas and every step runs
+        the model on overlapping windows of that size -- each a stand-alone image to the model, all of them samples of one engine batch --
+        blends their predictions where they overlap (`tile_weight`: "cosine", a Hann profile over the window, or "uniform") and steps the
+        canvas once (Flux.denoise_windows, fluxmi.windows, csrc/window_step.hip): cost linear in area.  `tile_overlap` in pixels, a multiple
+        of 16 with 0 <= overlap < tile, is the overlap of neighbouring windows (None: a quarter of the tile, rounded down to a multiple of
+        16); the last window of an axis snaps to the canvas edge.  Noise is drawn at canvas size from the request's generator, `init_image`
+        / `strength` run at canvas size as for any request (img2img upscaling), the schedule's shift follows the WINDOW's sequence length,
+        text and `y` are shared by all windows, and the result is decoded at canvas size by the same VAE -- whose mid-block attention is
+        quadratic in the canvas: beyond 46340 latent pixels (about 1720 x 1720 px) a request that decodes or encodes is refused, and
+        output_type="latent" is what remains.  Composes with a negative prompt at `true_cfg_scale` > 1 (unshaped), `true_cfg_interval`,
+        `init_image` / `strength`, LoRA, `num_images`, `sigmas` / `sigma_schedule`, `noise=` and `on_step` with preview_every = 0, while
+        num_images x windows (twice that when guided) fit one engine pass of 32 samples.  Refused with any sampler but "euler", guidance
+        shaping, `inpaint_mask`, `reference_image`, a Fill / Depth / Canny model, `redux_image`, `regions`, `cache_threshold` > 0, a
+        ControlNet, an IP-Adapter, `source_prompt`, `preview_every` > 0 and under a process group.  `tile_size=None`, or a tile of the
+        request's size with no other tile argument, is today's request, launch for launch; `tile_overlap` / `tile_weight` without
+        `tile_size` are refused.  Image quality on real FLUX weights is not established here; no tile size or overlap is recommended."""
+        tiles = self._check_tiles(locals())
+        if tiles is not None:
+            return self._generate_tiled(tiles, prompt, width, height, num_steps, guidance, seed, init_image, strength, num_images, return_seed,
+                                        jpeg_quality, output_type, noise, use_graph, negative_prompt, true_cfg_scale, true_cfg_interval,
+                                        sigma_schedule, sigmas, on_step)
         edit = self._check_edit(locals())
         if edit is not None:
             return self._generate_edit(edit, prompt, source_prompt, width, height, num_steps, guidance, seed, init_image, silent, num_images,
@@ -1184,6 +1210,146 @@ class FluxPipeline:
             return (out, seed) if return_seed else out
         img_px = self.vae_decode(latents, height, width)
         # output_type "uint8": the [B, H, W, 3] array into_bytes hands to the JPEG encoder (the pixel-parity tests compare it)
+        out = self.to_uint8(img_px) if output_type == "uint8" else self.into_bytes(img_px, jpeg_quality=jpeg_quality)
+        return (out, seed) if return_seed else out
+
+    # ---- tiled generation (fluxmi.windows; Flux.denoise_windows) -------------------------------------------------------------------------------
+    VAE_MAX_LATENT_PIXELS = 46340  # the VAE's mid-block attention scores [P, P] bf16 behind a 32-bit GEMM descriptor: 2 P^2 bytes < 4 GiB
+
+    def _check_tiles(self, a: dict):
+        """generate's arguments -> None (no tile_size, or one tile of the request's size and nothing else asked: today's request) or the
+        fluxmi.windows.WindowPlan of the request; every refusal of a tiled request is raised here, before any encoder or engine work"""
+        from fluxmi import windows
+        from modules.flux_model import Flux
+
+        ts, ov, prof = a["tile_size"], a["tile_overlap"], a["tile_weight"]
+        if ts is None:
+            if ov is not None or prof != "cosine":
+                raise ValueError("fluxmi: tile_overlap / tile_weight belong to a tiled request: they need tile_size")
+            return None
+        is_int = lambda v: isinstance(v, int) and not isinstance(v, bool)
+        if is_int(ts):
+            ts = (ts, ts)
+        if not isinstance(ts, (tuple, list)) or len(ts) != 2 or not all(is_int(v) for v in ts):
+            raise ValueError(f"fluxmi: tile_size={a['tile_size']!r}: expected an int or (height, width) in pixels")
+        th, tw = ts
+        height, width = 16 * (a["height"] // 16), 16 * (a["width"] // 16)
+        if th < 16 or tw < 16 or th % 16 or tw % 16 or th > height or tw > width:
+            raise ValueError(f"fluxmi: tile_size={a['tile_size']!r}: expected multiples of 16, at least 16 and at most the request's {height} x "
+                             f"{width} (height x width)")
+        if prof not in windows.PROFILES:
+            raise ValueError(f"fluxmi: tile_weight={prof!r}: expected one of {windows.PROFILES}")
+        if ov is not None and (not is_int(ov) or ov < 0 or ov % 16 or ov >= min(th, tw)):
+            raise ValueError(f"fluxmi: tile_overlap={ov!r}: expected a multiple of 16 with 0 <= overlap < tile ({min(th, tw)})")
+        if (th, tw) == (height, width) and ov is None and prof == "cosine":
+            return None
+        no = lambda what: ValueError(f"fluxmi: tile_size (tiled generation) does not combine with {what}")
+        if a["sampler"] != "euler" or a["eta"] != 1.0 or a["s_noise"] != 1.0 or a["noise_seed"] is not None:
+            raise no(f"sampler={a['sampler']!r} / eta / s_noise / noise_seed (the windowed update is an Euler step: sampler \"euler\" only)")
+        if (a["guidance_mode"] != "cfg" or a["guidance_rescale"] != 0.0 or a["zero_init_steps"] != 0 or a["apg_eta"] != 1.0
+                or a["apg_norm_threshold"] != 0.0 or a["apg_momentum"] != 0.0):
+            raise no("guidance shaping (guidance_mode / guidance_rescale / apg_* / zero_init_steps: a guided tiled request is unshaped)")
+        for name, what in (("inpaint_mask", "inpaint_mask"), ("reference_image", "a Kontext reference_image"), ("redux_image", "redux_image"),
+                           ("regions", "regions"), ("source_prompt", "source_prompt (FlowEdit)"), ("mask_image", "mask_image (FLUX.1 Fill)"),
+                           ("control_image", "control_image (FLUX.1 Depth / Canny)"), ("img_cond", "img_cond (FLUX.1 Fill / Depth / Canny)")):
+            if a[name] is not None:
+                raise no(what)
+        if a["inpaint_differential"]:
+            raise no("inpaint_differential")
+        if a["controlnet_image"] is not None or a["controlnet_cond"] is not None:
+            raise no("a ControlNet")
+        if a["ip_adapter_image"] is not None or a["ip_adapter_image_embeds"] is not None or a["negative_ip_adapter_image"] is not None:
+            raise no("an IP-Adapter")
+        try:
+            cache_on = float(a["cache_threshold"]) > 0
+        except (TypeError, ValueError):
+            cache_on = True
+        if cache_on:
+            raise no("cache_threshold > 0 (step caching)")
+        pe = a["preview_every"]
+        if isinstance(pe, bool) or not isinstance(pe, int) or pe != 0 or a["preview_factors"] is not None:
+            raise no("preview_every > 0 (the stream holds windows, not the canvas; on_step reports progress and cancels)")
+        if a["on_step"] is not None and not callable(a["on_step"]):
+            raise ValueError("fluxmi: on_step must be callable")
+        if fdist.world_size() > 1:
+            raise no("a process group")
+        if self.conditioning_kind() is not None:
+            raise no("a FLUX.1 Fill / Depth / Canny model")
+        if a["sigma_schedule"] not in solvers.SIGMA_SCHEDULES:
+            raise ValueError(f"fluxmi: sigma_schedule={a['sigma_schedule']!r}: expected one of {solvers.SIGMA_SCHEDULES}")
+        if a["negative_prompt"] is None and a["true_cfg_scale"] > 1:
+            raise ValueError(f"fluxmi: true_cfg_scale={a['true_cfg_scale']} needs a negative_prompt")
+        try:
+            lo, hi = (float(v) for v in a["true_cfg_interval"])
+        except (TypeError, ValueError):
+            raise ValueError(f"fluxmi: true_cfg_interval={a['true_cfg_interval']!r}: expected (lo, hi)") from None
+        if not 0.0 <= lo <= hi <= 1.0:
+            raise ValueError(f"fluxmi: true_cfg_interval={a['true_cfg_interval']!r}: expected 0 <= lo <= hi <= 1")
+        ovh, ovw = (16 * (th // 64), 16 * (tw // 64)) if ov is None else (ov, ov)
+        plan = windows.plan(height // 16, width // 16, th // 16, tw // 16, (th - ovh) // 16, (tw - ovw) // 16, prof)
+        n_img = a["num_images"]
+        if isinstance(n_img, bool) or not isinstance(n_img, int) or n_img < 1:
+            raise ValueError(f"fluxmi: num_images={n_img!r}: expected an integer >= 1")
+        if isinstance(a["prompt"], (list, tuple)) and n_img == 1:
+            n_img = max(1, len(a["prompt"]))
+        guided = a["negative_prompt"] is not None and a["true_cfg_scale"] > 1
+        cap = Flux.MAX_ENGINE_BATCH // 2 if guided else Flux.MAX_ENGINE_BATCH
+        if n_img * plan.ny * plan.nx > cap:
+            raise no(f"num_images={n_img} at this size: {n_img} x {plan.ny} x {plan.nx} windows do not fit one engine pass of {cap} samples"
+                     f"{' (half the pass: a negative prompt doubles them)' if guided else ''}; use a larger tile_size or a smaller tile_overlap")
+        decodes = not (a["output_type"] == "latent" or self.ae is None)
+        if (decodes or a["init_image"] is not None) and (height // 8) * (width // 8) > self.VAE_MAX_LATENT_PIXELS:
+            raise no(f"{'init_image' if a['init_image'] is not None else 'a decoded output'} at {height} x {width}: the VAE's mid-block attention "
+                     f"holds a [P, P] bf16 score matrix of the canvas's P = {(height // 8) * (width // 8)} latent pixels behind a 32-bit GEMM "
+                     f"descriptor (P <= {self.VAE_MAX_LATENT_PIXELS}); a text-to-image request can return output_type=\"latent\"")
+        return plan
+
+    def _generate_tiled(self, plan, prompt, width, height, num_steps, guidance, seed, init_image, strength, num_images, return_seed, jpeg_quality,
+                        output_type, noise, use_graph, negative_prompt, true_cfg_scale, true_cfg_interval, sigma_schedule, sigmas, on_step):
+        """the tiled request of generate (its docstring): today's noise / img2img / text at canvas size, then Flux.denoise_windows on the
+        canvas -- one call, or up to three where true_cfg_interval cuts the request"""
+        from modules.flux_model import Flux, PreviewCall
+
+        num_steps = 4 if self.name == "flux-schnell" else num_steps
+        if sigmas is not None:
+            sigmas = solvers.custom_sigmas(sigmas)
+            num_steps = len(sigmas) - 1
+        sched_kw = {k: v for k, v in (("sigmas", sigmas), ("sigma_schedule", sigma_schedule)) if v is not None}
+        init_image = self.load_init_image_if_needed(init_image) if init_image is not None else None
+        height, width = 16 * (height // 16), 16 * (width // 16)
+        generator, seed = self.set_seed(seed)
+        # the schedule's shift follows the WINDOW's sequence length: that is the image the model sees
+        x, timesteps = self.preprocess_latent(init_image=init_image, height=height, width=width, num_steps=num_steps, strength=strength,
+                                              generator=generator, num_images=num_images, noise=noise, image_seq_len=plan.h * plan.w, **sched_kw)
+        img, _, vec, txt, txt_ids = map(lambda t: t.contiguous(), self.prepare(x, prompt))
+        N = img.shape[0]  # a list prompt with num_images == 1 sizes the batch (prepare)
+        guided = negative_prompt is not None and true_cfg_scale > 1
+        cap = Flux.MAX_ENGINE_BATCH // 2 if guided else Flux.MAX_ENGINE_BATCH
+        if N * plan.ny * plan.nx > cap:
+            raise ValueError(f"fluxmi: tile_size (tiled generation): {N} images x {plan.ny} x {plan.nx} windows do not fit one engine pass of {cap} samples")
+        neg = {}
+        if guided:
+            neg_vec, neg_txt = self._prepare_negative(negative_prompt, x, N, txt)
+            neg = dict(neg_txt=neg_txt, neg_y=neg_vec, cfg_scale=true_cfg_scale)
+        win_ids = self.make_img_ids(1, plan.h, plan.w, self.device_flux, self.dtype)
+        canvas = img.reshape(N, plan.Hc, plan.Wc, img.shape[2])  # pack() is row-major over the token grid
+        n = len(timesteps) - 1
+        cfg_lo, cfg_hi = (float(v) for v in true_cfg_interval)
+        g0, g1 = (min(n, math.ceil(cfg_lo * n)), min(n, math.ceil(cfg_hi * n))) if guided else (n, n)
+        segs = list(((0, g0, {}), (g0, g1, neg), (g1, n, {})) if g0 < g1 else ((0, n, {}),))
+        for a, b, kw in segs:
+            if a < b or n == 0:
+                if on_step is not None:  # the request's numbering continues across its denoise calls
+                    cb = lambda evaluation, num_evaluations, rgb, a=a: on_step({"evaluation": evaluation, "num_evaluations": num_evaluations,
+                                                                                "step": evaluation, "preview": None})
+                    kw = dict(kw, preview=PreviewCall(None, (0, 0), 0, a, n, cb))
+                canvas = self.model.denoise_windows(canvas, plan, win_ids, txt, txt_ids, vec, timesteps[a:b + 1], guidance=guidance,
+                                                    use_graph=use_graph, **kw)
+        latents = canvas.reshape(N, plan.Hc * plan.Wc, -1).to(img.dtype)
+        if output_type == "latent" or self.ae is None:
+            out = self.unpack(latents.float(), height, width)
+            return (out, seed) if return_seed else out
+        img_px = self.vae_decode(latents, height, width)
         out = self.to_uint8(img_px) if output_type == "uint8" else self.into_bytes(img_px, jpeg_quality=jpeg_quality)
         return (out, seed) if return_seed else out
 

@@ -110,6 +110,8 @@ _SIGS = {
     "fluxmi_philox_normal": ([vp, vp, i32, i64, C.c_uint32, i32, vp], i32),
     "fluxmi_flowedit_couple": ([vp, vp, vp, f32, f32, vp, C.c_uint32, i32, i64, i64, i32, i32, vp], i32),
     "fluxmi_flowedit_step": ([vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i64, i64, i32, i32, vp], i32),
+    "fluxmi_window_gather": ([vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp], i32),
+    "fluxmi_window_step": ([vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp], i32),
     "fluxmi_fb_snapshot": ([vp, i64, vp, i32, i64, vp], i32),
     "fluxmi_fb_metric": ([vp, i64, vp, vp, vp, vp, vp, vp, i32, i64, vp], i32),
     "fluxmi_fb_commit": ([vp, i64, vp, vp, vp, i32, i64, vp], i32),
@@ -142,6 +144,8 @@ _SIGS = {
     "fluxmi_engine_set_guidance": ([vp, C.POINTER(f32), i32], i32),
     "fluxmi_engine_set_flow_edit": ([vp, vp, i32, C.POINTER(C.c_double), C.POINTER(i32), i32, C.POINTER(C.c_uint32), i32, f32, f32, vp], i32),
     "fluxmi_engine_denoise_edit": ([vp, vp, vp, vp, C.POINTER(C.c_double), i32, C.POINTER(i32), i32, vp], i32),
+    "fluxmi_engine_set_windows": ([vp, i32, i32, i32, i32, i32, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(f32), C.POINTER(f32), vp], i32),
+    "fluxmi_engine_denoise_windows": ([vp, vp, vp, vp, f32, i32, f32, C.POINTER(C.c_double), i32, C.POINTER(i32), i32, vp], i32),
     "fluxmi_latent_preview": ([vp, vp, vp, vp, vp, vp, vp, vp, i32, i64, i64, i32, i32, i32, i32, vp], i32),
     "fluxmi_engine_set_preview": ([vp, C.POINTER(f32), i32, i32, i32, i32, i32, vp, vp], i32),
     "fluxmi_engine_preview_stats": ([vp, C.POINTER(i64), C.POINTER(i32)], i32),

@@ -714,6 +714,62 @@ def flowedit_step(img: torch.Tensor, pred: torch.Tensor, z: torch.Tensor, x0: to
     return z
 
 
+# ---- tiled generation (fluxmi_window_gather / _step; include/fluxmi.h, fluxmi/windows.py) ---------------------------------------------------
+def _window_shapes(who: str, canvas: torch.Tensor, img: torch.Tensor, row0, col0, h: int, w: int, guided: bool):
+    """canvas bf16 [N, Hc, Wc, C], img bf16 [S or 2S, h * w, C] with S = N * ny * nx, contiguous -> (N, Hc, Wc, ny, nx, C).  What the tables
+    hold, and C % 8, is the library's to refuse."""
+    _req(canvas, torch.bfloat16, "canvas")
+    _req(img, torch.bfloat16, "img")
+    for name, t in (("row0", row0), ("col0", col0)):
+        if t is not None:
+            _req(t, torch.int32, name)
+    if canvas.ndim != 4 or img.ndim != 3 or not (canvas.is_contiguous() and img.is_contiguous()):
+        raise ValueError(f"{who}: canvas {tuple(canvas.shape)} must be contiguous [N, Hc, Wc, C] and img {tuple(img.shape)} contiguous [S, h * w, C]")
+    N, Hc, Wc, Cc = canvas.shape
+    ny, nx = (1 if row0 is None else row0.numel()), (1 if col0 is None else col0.numel())
+    S = N * ny * nx * (2 if guided else 1)
+    if tuple(img.shape) != (S, int(h) * int(w), Cc):
+        raise ValueError(f"{who}: img {tuple(img.shape)}: expected [{S}, {int(h) * int(w)}, {Cc}] ({N} images x {ny} x {nx} windows"
+                         f"{', both branches' if guided else ''})")
+    return N, Hc, Wc, ny, nx, Cc
+
+
+def window_gather(canvas: torch.Tensor, img: torch.Tensor, row0: torch.Tensor, col0: torch.Tensor, h: int, w: int, guided: bool = False) -> torch.Tensor:
+    """Fills the stream from the canvas (fluxmi_window_gather): canvas bf16 [N, Hc, Wc, C]; img bf16 [S, h * w, C], S = N * ny * nx, sample
+    (n * ny + a) * nx + b window (a, b) of image n at canvas token (row0[a], col0[b]); `guided`: img holds 2S samples and both halves are
+    filled.  row0 / col0: int32 device tensors.  Returns img."""
+    N, Hc, Wc, ny, nx, Cc = _window_shapes("window_gather", canvas, img, row0, col0, h, w, guided)
+    call("fluxmi_window_gather", _p(canvas), _p(img), _p(row0), _p(col0), N, Hc, Wc, int(h), int(w), ny, nx, Cc, int(bool(guided)), _stream())
+    return img
+
+
+def window_step(canvas: torch.Tensor, img: torch.Tensor, pred: torch.Tensor, dts: torch.Tensor, row0: torch.Tensor, col0: torch.Tensor,
+                Ny: torch.Tensor, Nx: torch.Tensor, h: int, w: int, step: Optional[torch.Tensor] = None,
+                scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """In place, the windowed update (fluxmi_window_step): the canvas moves by dts[*step] times the blend of the windows' predictions
+    (`scale`, an fp32 device scalar: of their guided predictions, pred / img then hold 2S samples) and every window of img is rebuilt from
+    it.  dts fp32, `step` an int32 device scalar (None = 0), Ny fp32 [ny, Hc] / Nx fp32 [nx, Wc] (fluxmi.windows.window_weights) on the
+    device.  Returns the canvas."""
+    guided = scale is not None
+    N, Hc, Wc, ny, nx, Cc = _window_shapes("window_step", canvas, img, row0, col0, h, w, guided)
+    _req(pred, torch.bfloat16, "pred")
+    _req(dts, torch.float32, "dts")
+    if pred.shape != img.shape or not pred.is_contiguous():
+        raise ValueError(f"window_step: pred {tuple(pred.shape)} must be contiguous like img {tuple(img.shape)}")
+    for name, t, want in (("Ny", Ny, (ny, Hc)), ("Nx", Nx, (nx, Wc))):
+        if t is not None:
+            _req(t, torch.float32, name)
+            if tuple(t.shape) != want or not t.is_contiguous():
+                raise ValueError(f"window_step: {name} {tuple(t.shape)} must be contiguous fp32 {list(want)}")
+    if step is not None:
+        _req(step, torch.int32, "step")
+    if guided:
+        _req(scale, torch.float32, "scale")
+    call("fluxmi_window_step", _p(canvas), _p(img), _p(pred), _p(dts), _p(step), _p(scale), _p(row0), _p(col0), _p(Ny), _p(Nx), N, Hc, Wc, int(h),
+         int(w), ny, nx, Cc, _stream())
+    return canvas
+
+
 # ---- latent preview (fluxmi_latent_preview; include/fluxmi.h) ---------------------------------------------------------------------------
 def preview_proj(factors, bias=None) -> list:
     """The 51 floats the kernel reads: M[16][3] row-major, then bias[3] (zeros when None)."""

@@ -1100,6 +1100,94 @@ class Flux(nn.Module):
             raise GenerationCancelled(preview.eval_offset + ran, preview.n_evaluations)
         return z
 
+    def denoise_windows(self, canvas: Tensor, plan, img_ids: Tensor, txt: Tensor, txt_ids: Tensor, y: Tensor, timesteps: List[float],
+                        guidance: float = 3.5, use_graph: bool = True, neg_txt: Tensor | None = None, neg_y: Tensor | None = None,
+                        cfg_scale: float = 1.0, preview: PreviewCall | None = None) -> Tensor:
+        """Tiled generation (fluxmi.windows; MultiDiffusion, Bar-Tal et al. 2023) run natively: the loop of `denoise` -- calibrating steps
+        unfused, every later step one replay of a captured hipGraph -- on the S = N * ny * nx windows of `canvas` [N, Hc, Wc, C] (the token
+        grid of the packed latent) that `plan` (a fluxmi.windows.WindowPlan) lays out, sample (n * ny + a) * nx + b window (a, b) of image
+        n.  Every window is a stand-alone image to the model: `img_ids` [1, h * w, 3] are the WINDOW's position ids, `txt` / `y` [1 or N,
+        ...] are broadcast to an image's windows.  After every evaluation one kernel (csrc/window_step.hip) blends the windows'
+        predictions with the plan's weights, steps the canvas once and rebuilds every window from it.  `neg_txt` / `neg_y` (both or
+        neither): true classifier-free guidance, 2S samples, `cfg_scale` taken as given and unshaped.  S (guided: 2S) must fit one engine
+        pass.  Returns the new canvas; `canvas` is not modified.  `preview`: progress and cancellation only (every = 0).  Refused under an
+        amax exchange (a process group)."""
+        if getattr(self, "_amax_xchg", None) is not None:
+            raise ValueError("fluxmi: tiled generation is refused under an amax exchange (a process group)")
+        preview = self._check_preview(preview)
+        if preview is not None and preview.every > 0:
+            raise ValueError("fluxmi: tiled generation has no previews of the canvas (preview.every must be 0: progress and cancellation only)")
+        guided = neg_txt is not None or neg_y is not None
+        if guided and (neg_txt is None or neg_y is None):
+            raise ValueError("neg_txt and neg_y go together (the negative prompt's T5 sequence and pooled CLIP vector)")
+        if canvas.ndim != 4 or tuple(canvas.shape[1:3]) != (plan.Hc, plan.Wc):
+            raise ValueError(f"fluxmi: canvas {tuple(canvas.shape)}: expected [N, {plan.Hc}, {plan.Wc}, C] (the plan's token grid)")
+        if self.in_channels != self.out_channels or canvas.shape[3] != self.in_channels:
+            raise ValueError(f"fluxmi: tiled generation needs a text-to-image model ({self.in_channels} input and {self.out_channels} predicted "
+                             f"channels; the canvas has {canvas.shape[3]})")
+        N, per = canvas.shape[0], plan.ny * plan.nx
+        S, Li = N * per, plan.h * plan.w
+        cap = self.MAX_ENGINE_BATCH // 2 if guided else self.MAX_ENGINE_BATCH
+        if not 1 <= S <= cap:
+            raise ValueError(f"fluxmi: {N} images x {plan.ny} x {plan.nx} windows = {S} samples do not fit one engine pass (at most {cap}"
+                             f"{' with a negative prompt' if guided else ''})")
+        if img_ids.ndim != 3 or img_ids.shape[0] != 1 or img_ids.shape[1] != Li:
+            raise ValueError(f"fluxmi: img_ids {tuple(img_ids.shape)}: expected [1, {Li}, axes], the position ids of ONE window")
+        for name, t in (("txt", txt), ("y", y)) + ((("neg_txt", neg_txt), ("neg_y", neg_y)) if guided else ()):
+            if t.shape[0] not in (1, N):
+                raise ValueError(f"fluxmi: {name} {tuple(t.shape)}: expected [1 or {N}, ...] (one row per image, broadcast to its windows)")
+        if guided and (tuple(neg_txt.shape[1:]) != tuple(txt.shape[1:]) or tuple(neg_y.shape[1:]) != tuple(y.shape[1:])):
+            raise ValueError(f"fluxmi: neg_txt {tuple(neg_txt.shape)} / neg_y {tuple(neg_y.shape)} must have the prompt's sequence length "
+                             f"({tuple(txt.shape)} / {tuple(y.shape)}): both branches run in one batch")
+        dev = canvas.device
+        bf = lambda t: t.to(device=dev, dtype=torch.bfloat16).contiguous()
+        ex = lambda t: t.to(dev).expand(N, *t.shape[1:]).repeat_interleave(per, 0)  # one row per image -> one per window
+        B = 2 * S if guided else S
+        txt_s, y_s = (torch.cat((ex(txt), ex(neg_txt)), 0), torch.cat((ex(y), ex(neg_y)), 0)) if guided else (ex(txt), ex(y))
+        txt_s, y_s = bf(txt_s), bf(y_s)
+        ids_s, tids_s = img_ids.to(dev).expand(B, -1, -1), txt_ids[:1].to(dev).expand(B, -1, -1)
+        canvas = bf(canvas).clone()
+        stream_like = canvas.new_empty((B, Li, canvas.shape[3]))  # (shape only: the engine owns the stream)
+        row0 = (C.c_int * plan.ny)(*plan.row0)
+        col0 = (C.c_int * plan.nx)(*plan.col0)
+        wy = (C.c_float * (plan.ny * plan.Hc))(*plan.Ny.reshape(-1).tolist())
+        wx = (C.c_float * (plan.nx * plan.Wc))(*plan.Nx.reshape(-1).tolist())
+        self._ensure_engine(dev)
+        with self._lock:
+            self._prepare(stream_like, ids_s, tids_s, txt_s, 0)
+            self._set_attn_groups(None, B, txt_s.shape[1] + Li, dev)
+            _lib.call("fluxmi_engine_set_step_cache", self._engine, 0.0, 0)
+            self._set_inpaint(None, dev)
+            self._set_solver(None)
+            self._set_guidance(None)
+            trial = self._trial_counter()
+            t_io = C.c_int(trial if trial is not None else 0)
+            ts = (C.c_double * len(timesteps))(*[float(t) for t in timesteps])
+            _lib.call("fluxmi_engine_set_windows", self._engine, N, plan.Hc, plan.Wc, plan.h, plan.w, plan.ny, plan.nx, row0, col0, wy, wx,
+                      ops._stream())
+            pv, rc, ran = None, 0, 0
+            try:
+                pv = self._set_preview(preview)
+                rc = _lib.lib.fluxmi_engine_denoise_windows(self._engine, ops._p(canvas), ops._p(txt_s), ops._p(y_s), float(guidance), int(guided),
+                                                            float(cfg_scale), ts, len(timesteps) - 1, C.byref(t_io), int(use_graph), ops._stream())
+                if rc != _lib.CANCELLED or pv is None:
+                    _lib.check(rc)
+                else:
+                    cap_ran = (C.c_longlong(0), C.c_int(0))
+                    _lib.call("fluxmi_engine_preview_stats", self._engine, C.byref(cap_ran[0]), C.byref(cap_ran[1]))
+                    ran = cap_ran[1].value
+            finally:
+                if pv is not None:
+                    _lib.call("fluxmi_engine_set_preview", self._engine, None, 0, 0, 0, 0, 0, None, None)
+                _lib.call("fluxmi_engine_set_windows", self._engine, 0, 0, 0, 0, 0, 0, 0, None, None, None, None, None)
+            if trial is not None:
+                self._advance_calibration(t_io.value)
+        if pv is not None and pv["error"] is not None:
+            raise pv["error"]
+        if rc == _lib.CANCELLED:
+            raise GenerationCancelled(preview.eval_offset + ran, preview.n_evaluations)
+        return canvas
+
     def step_cache_log(self):
         """What first-block step caching did in the last `denoise` call (the last pass of a chunked batch): `(ratios, hits)` with
         `ratios` a float32 tensor [frozen steps, samples of the pass] (inf where no reference existed yet: the first frozen step) and `hits` a

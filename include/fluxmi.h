@@ -460,6 +460,32 @@ int fluxmi_flowedit_step(void* img, const void* pred, void* z, float* acc, const
                          const unsigned* ids, const int* eval_offset, int B, long long img_rows, long long pred_rows, int c_in, int c_out,
                          void* stream);
 
+/* ---- tiled generation: a canvas stepped from overlapping windows (MultiDiffusion, Bar-Tal et al. 2023) -------------
+ * canvas x: bf16, dense [N, Hc, Wc, C], the token grid of the packed latent, row-major.  img / pred: bf16 [S, h * w, C], S = N * ny * nx, or
+ * [2S, ...] when guided (the negative branches behind the prompt branches).  Sample s = (n * ny + a) * nx + b is window (a, b) of image n; its
+ * token i * w + j is canvas token (row0[a] + i, col0[b] + j).  Windows sit on a Cartesian grid, so placement and blend weights are separable.
+ * DEVICE tables: row0 int32 [ny], col0 int32 [nx], Ny fp32 [ny][Hc], Nx fp32 [nx][Wc]; the weight tables are normalised per canvas position
+ * by the caller (fluxmi/windows.py) and zero outside their window.  A window (a, b) COVERS canvas token (r, c) when row0[a] <= r < row0[a] + h
+ * and col0[b] <= c < col0[b] + w.  fluxmi_window_step, per canvas element, with dt = dts[*step] (dts: DEVICE fp32; step: DEVICE int, NULL = 0):
+ *   v_k  = pred[s_k]                                                                unguided (scale == NULL)
+ *          d = bf16(c - u); m = bf16(s * d); p = bf16(u + m)  (fluxmi_cfg_euler's chain) on c = pred[s_k], u = pred[S + s_k], s = *scale (DEVICE)
+ *   wgt  = Ny[a][r] * Nx[b][c]                                                       fp32, rounded
+ *   num  = sum over the covering windows, ascending (a, b), of wgt * v_k             fp32, the product and the sum each rounded (never fused)
+ *   vbar = bf16(num)
+ *   x'   = bf16(float(x) + float(bf16(dt * vbar)))                                   (fluxmi_euler's last operation)
+ *   canvas <- x';  img[s_k] (and img[S + s_k] when guided) <- x' for every covering window
+ * fluxmi_window_gather is the last line alone with x' = x: it fills the stream from the canvas before the first evaluation (guided != 0: both
+ * halves); the canvas is only read.  pred and the tables are never written; every read of a vector precedes its writes; 16-byte accesses, one
+ * thread per 8 channels of one canvas token; a stream element maps to exactly one canvas token.  No LDS, no atomics.
+ * Refused: C %% 8 != 0, a window that leaves the canvas (h > Hc, w > Wc, row0[a] outside [0, Hc - h], col0[b] outside [0, Wc - w]), a canvas row
+ * or column that no window covers, NULL tables, more than 2^31 - 1 vectors in the canvas or in the stream.  The placement rules speak of the
+ * tables' contents: these entries read row0 / col0 back, which synchronises the stream (the engine, which is given host tables, does not). */
+int fluxmi_window_gather(const void* canvas, void* img, const int* row0, const int* col0, int N, int Hc, int Wc, int h, int w, int ny, int nx,
+                         int C, int guided, void* stream);
+int fluxmi_window_step(void* canvas, void* img, const void* pred, const float* dts, const int* step, const float* scale, const int* row0,
+                       const int* col0, const float* Ny, const float* Nx, int N, int Hc, int Wc, int h, int w, int ny, int nx, int C,
+                       void* stream);
+
 /* ---- guidance shaping of true classifier-free guidance: CFG rescale, APG, CFG-Zero*  ------------------------------
  * Operands as for fluxmi_cfg_euler: pred bf16, dense [2B][N], N = pred_rows * c_out, N %% 8 == 0; sample b is c (the prompt branch), sample
  * B + b is u (the negative branch).  r: fp32, dense [B][N], APG's running difference (NULL: no r; its sums are 0, it is never touched and mu
@@ -741,6 +767,26 @@ int fluxmi_engine_set_flow_edit(fluxmi_engine_t* e, const void* x0_dev, int batc
  * counts model evaluations). */
 int fluxmi_engine_denoise_edit(fluxmi_engine_t* e, void* z, const void* txt, const void* y, const double* timesteps_host, int n_evals,
                                int* trial_index_inout, int use_graph, void* stream);
+/* Window state (fluxmi_window_step) for the following fluxmi_engine_denoise_windows calls on the PREPARED shape: S =
+ * n_images * ny * nx samples (2S for a guided call) of Li = h * w rows with ONE set of window-local position ids, so that every window looks
+ * like a stand-alone image to the model.  row0_host [ny], col0_host [nx], Ny_host [ny][Hc], Nx_host [nx][Wc]: the tables of
+ * fluxmi_window_step on the HOST, checked here (placement rules, finite weights) and copied into the engine-owned "win_tab" on `stream`; the
+ * call returns behind one stream synchronisation.  "win_x" (the canvas, bf16 [n_images, Hc, Wc, C]) is made with it.  Both are counted in
+ * fluxmi_engine_workspace_bytes and dropped with the workspace.  Refused: S > the prepared batch (or > 32, one pass), h * w != Li.
+ * row0_host == NULL switches the state off; a prepare that re-allocates the workspace does too.  fluxmi_engine_denoise and _denoise_cfg do
+ * not consult the state: a request without windows allocates and launches exactly what it did before. */
+int fluxmi_engine_set_windows(fluxmi_engine_t* e, int n_images, int Hc, int Wc, int h, int w, int ny, int nx, const int* row0_host,
+                              const int* col0_host, const float* Ny_host, const float* Nx_host, void* stream);
+/* The windowed loop: fluxmi_engine_denoise's loop -- calibrating steps, then frozen steps replayed from ONE captured graph -- on the S (guided
+ * != 0: 2S) samples, with fluxmi_window_step as every update after one fluxmi_window_gather up front.  canvas: bf16 [n_images, Hc, Wc, C], in
+ * and out (copied to "win_x" and back); txt [S or 2S, Lt, ctx] and y [S or 2S, vec]: one row per SAMPLE (guided: the negative branches in the
+ * second half); guidance, cfg_scale, timesteps_host (n_steps + 1 times), trial_index_inout, use_graph as for fluxmi_engine_denoise_cfg.
+ * Windowed versus not is a kind of step graph and the canvas geometry is part of its key; tables, scale and schedule are device data.
+ * Refused: no state set, a prepared batch other than S (guided: 2S), reference rows or conditioning channels, an inpainting state, a solver
+ * program, step caching, an attention-group table, an attached ControlNet, an IP-Adapter, a FlowEdit state, guidance shaping (guided), and a
+ * step hook with every > 0 (a hook with every = 0 works: progress and cancellation). */
+int fluxmi_engine_denoise_windows(fluxmi_engine_t* e, void* canvas, const void* txt, const void* y, float guidance, int guided, float cfg_scale,
+                                  const double* timesteps_host, int n_steps, int* trial_index_inout, int use_graph, void* stream);
 /* Guidance shaping (fluxmi_guidance_moments / _combine) for the following fluxmi_engine_denoise_cfg calls on the PREPARED
  * shape: every step of those calls -- calibrating, graph-replayed, both tails of a step-cached step -- launches moments and combine on
  * "pred_s" immediately in front of the update kernel the request already had (guided Euler, blend, solver, with or without noise), which

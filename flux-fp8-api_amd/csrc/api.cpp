@@ -110,6 +110,12 @@ int fluxmi_ln_modulate(const void* x, long long ldx, void* out, long long ldo, c
   return fluxmi_k_ln_modulate(x, ldx, (long long)L * ldx, out, ldo, (long long)L * ldo, shift0, scale0, shift1, scale1, mod_bstride,
                               q_scale0, q_scale1, B, L, split, H, out_fp8, fmt, (hipStream_t)stream);
 }
+int fluxmi_ln_modulate_pairs(const void* x, long long ldx, void* out, long long ldo, const void* shift0, const void* scale0,
+                             const void* shift1, const void* scale1, long long mod_bstride, const float* q_scale0, const float* q_scale1,
+                             int B, int L, int split, int H, int out_fp8, int fmt, int out_pairs, void* stream) {
+  return fluxmi_k_ln_modulate(x, ldx, (long long)L * ldx, out, ldo, (long long)L * ldo, shift0, scale0, shift1, scale1, mod_bstride,
+                              q_scale0, q_scale1, B, L, split, H, out_fp8, fmt, (hipStream_t)stream, out_pairs != 0);
+}
 int fluxmi_act(const void* x, void* y, int rows, int cols, long long ld_in, long long ld_out, int mode, void* stream) {
   return fluxmi_k_act(x, y, rows, cols, ld_in, ld_out, mode, (hipStream_t)stream);
 }
@@ -119,6 +125,9 @@ int fluxmi_gate_residual(const void* x, const void* y, const void* gate, void* o
 }
 int fluxmi_add(const void* a, const void* b, void* z, long long n, void* stream) {
   return fluxmi_k_add(a, b, z, n, (hipStream_t)stream);
+}
+int fluxmi_add_bcast(const void* a, const void* b, void* z, long long rows, int nb, int cols, void* stream) {
+  return fluxmi_k_add_bcast(a, b, z, rows, nb, cols, (hipStream_t)stream);
 }
 int fluxmi_rope_table(const void* ids, const float* omega, const int* axis, void* pe, long long rows, int n_axes, int pairs,
                       void* stream) {

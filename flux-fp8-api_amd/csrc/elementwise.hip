@@ -353,7 +353,10 @@ __global__ void __launch_bounds__(512) ln_modulate_stream_kernel(const LnModArgs
       t.s[0] = *(const float4*)(tsft + 512 * k); t.s[1] = *(const float4*)(tsft + 512 * k + 4);
       return t;
     };
-    Tab tc = tab_read(0);
+    // chunk 0 is guarded like the others: at H < 512 the lanes past H would read beyond the 16 * H bytes of LDS the launch asked for
+    // (FULL: tab_ok is constant true, the code is unchanged)
+    Tab tc = {};
+    if (tab_ok(0)) tc = tab_read(0);
 #pragma unroll
     for (int k = 0; k < NCH; ++k) {
       const int c = (lane + 64 * k) * 8;

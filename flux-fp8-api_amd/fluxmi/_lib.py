@@ -78,9 +78,11 @@ _SIGS = {
     "fluxmi_lora_fuse_f8": ([vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp], i32),
     "fluxmi_dequant": ([vp, vp, vp, i64, i32, vp], i32),
     "fluxmi_ln_modulate": ([vp, i64, vp, i64, vp, vp, vp, vp, i64, vp, vp, i32, i32, i32, i32, i32, i32, vp], i32),
+    "fluxmi_ln_modulate_pairs": ([vp, i64, vp, i64, vp, vp, vp, vp, i64, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp], i32),
     "fluxmi_act": ([vp, vp, i32, i32, i64, i64, i32, vp], i32),
     "fluxmi_gate_residual": ([vp, vp, vp, vp, i32, i32, i32, i64, i64, i64, i64, vp], i32),
     "fluxmi_add": ([vp, vp, vp, i64, vp], i32),
+    "fluxmi_add_bcast": ([vp, vp, vp, i64, i32, i32, vp], i32),
     "fluxmi_rope_table": ([vp, vp, vp, vp, i64, i32, i32, vp], i32),
     "fluxmi_qkv_rope": ([vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp], i32),
     "fluxmi_build_quant_lut": ([vp, i32, i32, vp, vp], i32),

@@ -181,37 +181,68 @@ def gemv(x, W, bias=None, in_scale=None, sa_recip=None, sb_recip=None, pre_silu=
 
 
 # ---- block elementwise ---------------------------------------------------------------------------------
-def ln_modulate(x, shift0, scale0, shift1=None, scale1=None, split=None, q_scale0=None, q_scale1=None, fmt=E5M2):
-    """x [B,L,H] bf16; shift/scale [B,H] (row stride = mod_bstride).  fp8 output iff q_scale0 is given."""
+def ln_modulate(x, shift0, scale0, shift1=None, scale1=None, split=None, q_scale0=None, q_scale1=None, fmt=E5M2, out=None, out_pairs=False):
+    """x [B,L,H] bf16; shift/scale [B,H] (row stride = mod_bstride).  fp8 output iff q_scale0 is given.  x and `out` [B,L,H] may be column
+    slices of wider [B,L,W] buffers (batch stride = L * row stride).  out_pairs: the fp8 output in the row-pair layout (pair_rows) over
+    the B * L rows; the library refuses it where the streaming kernel cannot write it (fluxmi_ln_modulate_pairs)."""
     B, L, H = x.shape
     split = L if split is None else split
     shift1 = shift0 if shift1 is None else shift1
     scale1 = scale0 if scale1 is None else scale1
     out_fp8 = q_scale0 is not None
     q_scale1 = q_scale0 if q_scale1 is None else q_scale1
-    out = torch.empty((B, L, H), dtype=dtype_of(fmt) if out_fp8 else torch.bfloat16, device=x.device)
-    call("fluxmi_ln_modulate", _p(x), x.stride(1), _p(out), H, _p(shift0), _p(scale0), _p(shift1), _p(scale1), shift0.stride(0),
-         _p(q_scale0), _p(q_scale1), B, L, split, H, int(out_fp8), fmt, _stream())
+    if out is None:
+        out = torch.empty((B, L, H), dtype=dtype_of(fmt) if out_fp8 else torch.bfloat16, device=x.device)
+    for t, name in ((x, "x"), (out, "out")):
+        if tuple(t.shape) != (B, L, H) or t.stride(2) != 1 or (B > 1 and t.stride(0) != L * t.stride(1)):
+            raise ValueError(f"ln_modulate: {name} must be [B, L, H] with unit column stride and batch stride L * row stride")
+    args = (_p(x), x.stride(1), _p(out), out.stride(1), _p(shift0), _p(scale0), _p(shift1), _p(scale1), shift0.stride(0),
+            _p(q_scale0), _p(q_scale1), B, L, split, H, int(out_fp8), fmt)
+    if out_pairs:
+        call("fluxmi_ln_modulate_pairs", *args, 1, _stream())
+    else:
+        call("fluxmi_ln_modulate", *args, _stream())
     return out
 
 
-def act(x, mode: int):
+def act(x, mode: int, out=None):
+    """out: a preallocated [rows, cols] bf16 tensor (a column slice of a wider buffer is fine), returned as it is"""
     x2 = x.reshape(-1, x.shape[-1])
-    y = torch.empty_like(x2)
+    y = torch.empty(x2.shape, dtype=x.dtype, device=x.device) if out is None else out
     call("fluxmi_act", _p(x2), _p(y), x2.shape[0], x2.shape[1], x2.stride(0), y.stride(0), mode, _stream())
-    return y.view(x.shape)
+    return y.view(x.shape) if out is None else out
 
 
-def gate_residual(x, y, gate):
+def _rows3(t, name):
+    """[B, L, H], unit column stride, rows of all batch elements at one stride (dense, or a column slice of a wider [B, L, W] buffer)"""
+    B, L, _ = t.shape
+    if t.stride(2) != 1 or (B > 1 and t.stride(0) != L * t.stride(1)):
+        raise ValueError(f"gate_residual: {name} must be [B, L, H] with unit column stride and batch stride L * row stride")
+    return t.stride(1)
+
+
+def gate_residual(x, y, gate, out=None):
+    """out = x + gate[b] * y.  x, y, out [B,L,H] may be column slices of wider buffers; gate [B,H] with any batch stride."""
     B, L, H = x.shape
-    out = torch.empty_like(x)
-    call("fluxmi_gate_residual", _p(x), _p(y), _p(gate), _p(out), B, L, H, H, H, H, gate.stride(0), _stream())
+    if out is None:
+        out = torch.empty((B, L, H), dtype=x.dtype, device=x.device)
+    call("fluxmi_gate_residual", _p(x), _p(y), _p(gate), _p(out), B, L, H, _rows3(x, "x"), _rows3(y, "y"), _rows3(out, "out"),
+         gate.stride(0), _stream())
     return out
 
 
-def add(a, b):
-    z = torch.empty_like(a)
+def add(a, b, out=None):
+    z = torch.empty_like(a) if out is None else out
     call("fluxmi_add", _p(a), _p(b), _p(z), a.numel(), _stream())
+    return z
+
+
+def add_bcast(a, b, out=None):
+    """z[r, :] = a[r, :] + b[r % nb, :]: a [rows, cols], b [nb, cols], both dense bf16"""
+    assert a.dim() == 2 and b.dim() == 2 and a.is_contiguous() and b.is_contiguous() and a.shape[1] == b.shape[1]
+    z = torch.empty_like(a) if out is None else out
+    assert z.is_contiguous() and z.shape == a.shape
+    call("fluxmi_add_bcast", _p(a), _p(b), _p(z), a.shape[0], b.shape[0], a.shape[1], _stream())
     return z
 
 
@@ -242,17 +273,27 @@ def rope_table(ids: torch.Tensor, axes_dim, theta) -> torch.Tensor:
     return pe
 
 
-def qkv_rope(qkv, pe, q_scale0, k_scale0, q_scale1=None, k_scale1=None, split=None, heads=None, skip_q=False, k_f16=False):
+def qkv_rope(qkv, pe, q_scale0, k_scale0, q_scale1=None, k_scale1=None, split=None, heads=None, skip_q=False, k_f16=False, out=None):
     """qkv bf16 [B,L,>=3*H*128] -> Q,K [B,H,L,128], VT [B,H,128,Lp].  skip_q: only K and VT (Q is returned as None).
-    k_f16: K is returned as float16 (the operand format of the attention kernel's folded schedule; pass it on to attention*)."""
+    k_f16: K is returned as float16 (the operand format of the attention kernel's folded schedule; pass it on to attention*).
+    out: preallocated contiguous (Q, K, VT) of those shapes and dtypes (Q ignored under skip_q; VT's last dimension is taken as Lp)."""
     B, L, _ = qkv.shape
     split = L if split is None else split
     q_scale1 = q_scale0 if q_scale1 is None else q_scale1
     k_scale1 = k_scale0 if k_scale1 is None else k_scale1
     Lp = (L + 63) // 64 * 64
-    K = torch.empty((B, heads, L, 128), dtype=torch.float16 if k_f16 else torch.bfloat16, device=qkv.device)
-    Q = None if skip_q else torch.empty((B, heads, L, 128), dtype=torch.bfloat16, device=qkv.device)
-    VT = torch.empty((B, heads, 128, Lp), dtype=torch.bfloat16, device=qkv.device)
+    if out is not None:
+        Q, K, VT = out
+        Q = None if skip_q else Q
+        Lp = VT.shape[-1]
+        for t, shape, dt in ((Q, (B, heads, L, 128), torch.bfloat16), (K, (B, heads, L, 128), torch.float16 if k_f16 else torch.bfloat16),
+                             (VT, (B, heads, 128, Lp), torch.bfloat16)):
+            if t is not None and (tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous()):
+                raise ValueError(f"qkv_rope: out tensors must be contiguous {shape} {dt}, got {tuple(t.shape)} {t.dtype}")
+    else:
+        K = torch.empty((B, heads, L, 128), dtype=torch.float16 if k_f16 else torch.bfloat16, device=qkv.device)
+        Q = None if skip_q else torch.empty((B, heads, L, 128), dtype=torch.bfloat16, device=qkv.device)
+        VT = torch.empty((B, heads, 128, Lp), dtype=torch.bfloat16, device=qkv.device)
     call("fluxmi_qkv_rope", _p(qkv), qkv.stride(1), _p(pe), _p(q_scale0), _p(k_scale0), _p(q_scale1), _p(k_scale1), _p(Q), _p(K),
          _p(VT), B, L, Lp, heads, split, int(k_f16), _stream())
     return Q, K, VT

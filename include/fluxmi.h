@@ -242,12 +242,19 @@ int fluxmi_dequant(const void* q, float* out, const float* scale_recip, long lon
 int fluxmi_ln_modulate(const void* x, long long ldx, void* out, long long ldo, const void* shift0, const void* scale0,
                        const void* shift1, const void* scale1, long long mod_bstride, const float* q_scale0,
                        const float* q_scale1, int B, int L, int split, int H, int out_fp8, int fmt, void* stream);
+/* the same with out_pairs: != 0 stores the fp8 output in the row-pair layout of fluxmi_pair_rows over the B * L rows (needs fp8 output,
+ * ldo == H, H % 64 == 0, H <= 3072, B * L even and fluxmi_tuning_t.ln_variant >= 2; refused otherwise); 0 is fluxmi_ln_modulate */
+int fluxmi_ln_modulate_pairs(const void* x, long long ldx, void* out, long long ldo, const void* shift0, const void* scale0,
+                             const void* shift1, const void* scale1, long long mod_bstride, const float* q_scale0,
+                             const float* q_scale1, int B, int L, int split, int H, int out_fp8, int fmt, int out_pairs, void* stream);
 /* mode 0: GELU(tanh), 1: SiLU (bf16 -> bf16)                                     flux_model.py:301,139 */
 int fluxmi_act(const void* x, void* y, int rows, int cols, long long ld_in, long long ld_out, int mode, void* stream);
 /* out = x + gate[b] * y                                                           flux_model.py:387-396,484 */
 int fluxmi_gate_residual(const void* x, const void* y, const void* gate, void* out, int B, int L, int H, long long ldx,
                          long long ldy, long long ldo, long long gate_bstride, void* stream);
 int fluxmi_add(const void* a, const void* b, void* z, long long n, void* stream);
+/* z[r, :] = a[r, :] + b[r % nb, :] over dense rows of `cols` bf16 (cols % 8 == 0, nb >= 1) */
+int fluxmi_add_bcast(const void* a, const void* b, void* z, long long rows, int nb, int cols, void* stream);
 
 /* lut[b] for every bf16 bit pattern b: the fp8 byte of  to_fp8_saturated(act(bf16 b), *scale)  (act: 0 none, 1 gelu-tanh, 2 silu),
  * rounded at the same points as the fused epilogues.  65536 bytes.                      float8_quantize.py:217-218 */

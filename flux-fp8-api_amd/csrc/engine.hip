@@ -1,5 +1,6 @@
 // fluxmi -- the Flux denoise engine: Flux.forward (reference modules/flux_model.py:672-716) and the Euler
-// loop of FluxPipeline.generate (flux_pipeline.py:619-651) sequenced natively over the HIP kernels.
+// loop of FluxPipeline.generate (flux_pipeline.py:619-651) sequenced natively over the HIP kernels.  This file: create, prepare, the
+// forward and its blocks, ControlNet / IP-Adapter plumbing, diagnostics; engine_denoise.hip: the request state and the loop; engine_state.h: the state.
 //
 // Two execution modes share every kernel:
 //   unfused (mode 0 calibrating / mode 2 frozen): producer -> bf16 -> [amax -> scale update] -> quantise -> GEMM,
@@ -21,258 +22,16 @@
 //   Q,K    bf16 [B, heads, L, 128];  VT bf16 [B, heads, 128, Lp]  (attention operands)
 //   attn8  fp8  [B, L, H];  h8 fp8 [B, L, 4H];  cat8 fp8 [B, L, 5H]  (single block: attn | gelu(mlp))
 //   mod    bf16 [B, 12H*depth + 3H*single + 2H]   all modulation vectors of the step
-#include <dlfcn.h>
 #include <limits.h>
 #include <stdlib.h>
-#include <string.h>
 #include <math.h>
 #include <algorithm>
 #include <atomic>
-#include <functional>
-#include <map>
-#include <string>
-#include <vector>
 
-#include "common.h"
-#include "fluxmi_internal.h"
+#include "engine_state.h"
 #include "gemm_cfg.h"
 
 namespace {
-constexpr int MAX_STEPS = 1024;
-// samples per engine pass: bounds the workspace (1.1 GB per 1024x1024 sample) and the step-ahead modulation table (2.1 MB per step and
-// sample); the host wrapper runs larger batches as equal consecutive passes
-constexpr int FLUXMI_ENGINE_MAX_BATCH = 32;
-struct Buf { void* p; size_t n; };
-// The captured pieces of one kind of frozen step (plain: the whole step; cached: head, body, skip) and what they were captured for.  Kernel
-// choices and the update kernel are baked into a captured piece, so the set is keyed on the tuning generation and the update kind.
-struct StepGraphs {
-  hipGraphExec_t exec[3] = {nullptr, nullptr, nullptr};
-  bool ok = false;      // exec[] is instantiated and replayable
-  bool warmed = false;  // one frozen step of this kind, shape and update kind has run eagerly (lazy one-time inits done): the next call may capture at once
-  bool cfg = false;     // the update kind (`warmed` and the pieces): guided or plain -- the two never share a graph
-  bool masked = false;  // the attention kind: token-group masked or dense launches are baked into the pieces like the update kernel
-  bool blend = false;   // the update kind, continued: the masked-latent blend kernel instead of the (guided) Euler kernel ...
-  bool diff = false;    // ... and its differential form (the threshold table is a launch argument)
-  bool solver = false;  // ... and the table-driven solver update (fluxmi_engine_set_solver): WHICH solver is device data, not a kind
-  bool noise = false;   // ... and its form with the noise term (fluxmi_engine_set_solver_noise): seeds and the offset are device data
-  bool edit = false;    // ... and FlowEdit's update (fluxmi_engine_denoise_edit): tables, ids, offset and the guidance pair are device data ...
-  const void* fe_acc = nullptr;  // ... its fp32 accumulator is a launch argument: null until a program that averages has made the buffer
-  bool win = false;     // ... and the windowed update (fluxmi_engine_denoise_windows): tables and scale are device data; the canvas geometry, which
-  int win_geo[7] = {0, 0, 0, 0, 0, 0, 0};  // ... is a launch argument, and the canvas's address are part of the key
-  const void* win_x = nullptr;
-  bool shaped = false;  // guidance shaping (fluxmi_engine_set_guidance): two launches in front of the guided update; mode and values are device data
-  bool previewed = false;  // the preview launch in front of the update (fluxmi_engine_set_preview, every > 0): cadence, offset and factors are device data ...
-  int pv_h = 0, pv_w = 0;  // ... the token grid is a launch argument
-  unsigned gen = 0;     // fluxmi_tuning_generation() the pieces were captured under
-  const void* cn = nullptr;  // the attached ControlNet whose launches (and workspace pointers) are baked into the pieces, or none ...
-  unsigned long long cn_gen = 0;  // ... and the generation of its workspace / weight binding: process-wide unique, so a net created at a freed net's address never matches
-  const void* ip = nullptr;  // the IP-Adapter's K / V buffer baked into the pieces (null: no adapter launches), its Nk ...
-  int ip_nk = 0;
-  unsigned long long ip_gen = 0;  // ... and the buffer's generation (an allocation at a freed buffer's address never matches)
-  void drop() {
-    for (hipGraphExec_t& g : exec)
-      if (g) { hipGraphExecDestroy(g); g = nullptr; }
-    ok = warmed = false;
-  }
-};
-}  // namespace
-
-struct fluxmi_engine {
-  fluxmi_model_desc_t d;
-  std::vector<fluxmi_linear_t> lin;
-  std::vector<const void*> norm;
-  int i_img_in, i_time_in, i_vec_in, i_guid_in, i_txt_in, i_double0, i_single0, i_final_mod, i_final_lin;
-  int B = 0, Li = 0, Lt = 0, L = 0, Lp = 0;
-  int Lpred = 0;  // predicted (and stepped) rows per sample: the leading rows of the image stream; Li - Lpred = Lc reference rows (Kontext)
-  long long mod_cols = 0;
-  char* ws = nullptr;
-  size_t ws_bytes = 0;
-  std::map<std::string, Buf> bufs;
-  // persistent small device state
-  char* consts = nullptr;
-  float *d_freqs, *d_omega, *d_ts, *d_dts, *d_amax, *d_amax_own;
-  int *d_axis, *d_step;
-  FluxmiCalibLayer* d_calib;
-  FluxmiGemvLayer* d_gemv = nullptr;
-  std::vector<FluxmiGemvLayer> h_gemv;
-  std::vector<FluxmiCalibLayer> h_calib_mod;  // modulation layers that share silu(vec)
-  FluxmiCalibLayer* d_calib_mod = nullptr;
-  int gemv_blocks = 0, gemv_maxK = 0;
-  // step-ahead modulation table (frozen scales): every modulation vector of every remaining step of a request, computed
-  // before the loop in batches of 8 steps so that the 3.2 GB of modulation weights are streamed once per 8 steps, not per step
-  char* mods_all = nullptr;
-  size_t mods_all_bytes = 0;
-  int mods_step0 = 0;
-  bool mods_table = false;  // the step being sequenced takes its modulations from the table
-  bool qlut_valid = false;  // the quantising-epilogue tables reflect the current input scales
-  // the frozen step's graphs: the plain step (one piece) and the step-cache step (head, body, skip).  Separate sets, so that plain and cached
-  // requests alternating on one shape never re-capture; both go stale by ONE rule (graphs_stale) and run through ONE loop (frozen_steps)
-  StepGraphs step_graphs, fb_graphs;
-  bool txt_emb_valid = false;
-  // row-pair copies of the F8Linear weights the persistent GEMM launches read (fluxmi_gemm_group_t.W_pairs): one allocation, offsets per linear
-  // (-1 = none); rebuilt on the first launch after create / rebind (the weights may have been rewritten: LoRA fuse)
-  char* pairs = nullptr;
-  size_t pairs_bytes = 0;
-  std::vector<long long> pairs_off;
-  bool pairs_dirty = true;
-  bool pairs_skipped = false;      // the copies were wanted and did not fit (ensure_pairs): retried at the next prepare
-  unsigned pairs_gen = 0;          // fluxmi_tuning_generation() the copies were built under (fluxmi_tuning_t.w_pairs may have changed)
-  float* d_cfg = nullptr;          // true-CFG scale (device scalar, like d_dts: one guided graph serves every scale)
-  // token-group attention mask (fluxmi_engine_set_attn_groups): every attention launch of a forward reads the [B, L] descriptors in the
-  // workspace buffer "attn_groups".  The CONTENTS are device data -- one set of graphs serves every table of a prepared shape -- masked
-  // versus dense is a graph kind (graphs_stale).  Cleared when the workspace is re-allocated: a table belongs to a shape
-  bool masked = false;
-  int* d_step0 = nullptr;          // first step of the modulation table (device scalar: the captured graph reads it)
-  // the layout each fp8 activation buffer (ACT_A8 .. ACT_CAT8) was last written in: true = row pairs (fused mode, act_pairs), false = plain
-  // rows.  Set by the stages that write them (and by a replayed step graph); fluxmi_engine_copy_buffer converts by it
-  bool act_in_pairs[4] = {false, false, false, false};
-  int mods_rows_cap = 0;           // rows (steps x B) the table holds; sized in engine_prepare, never inside denoise
-  // pinned host staging for the per-request schedule (ts | dts), guarded by an event so that engine_denoise never waits on the stream
-  float* h_sched = nullptr;
-  hipEvent_t ev_sched = nullptr;
-  bool sched_pending = false;
-  // hipEvent timing of the frozen (graph-replayed) part of the last denoise call, read back by fluxmi_engine_last_timing
-  hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;
-  int timed_steps = 0;
-  // multi-GPU calibration: caller-owned amax array + host hook called between the amax reduction of a layer and its scale update
-  float* amax_ext = nullptr;
-  fluxmi_amax_hook_t amax_hook = nullptr;
-  void* amax_user = nullptr;
-  // first-block step cache (fluxmi_engine_set_step_cache).  Threshold, hit counter and log are HOST state: one set of
-  // graphs (fb_graphs) serves every threshold.  The buffers (h0 | r, h1, r_ref, R, partial sums, ratios) are one allocation made at the first cached
-  // call of a prepared shape and dropped with the workspace; a plain request never allocates, captures or launches any of this.
-  float fb_threshold = 0.f;
-  int fb_max_hits = 0;
-  char* fb_mem = nullptr;
-  size_t fb_bytes = 0;
-  float* h_ratio = nullptr;        // pinned: the B ratios of the step, copied out behind the head piece
-  hipEvent_t ev_fb = nullptr;      // ... and the event the host waits on before it decides
-  int fb_log_B = 0;
-  std::vector<float> fb_log_ratio;          // [frozen steps of the last call][B]
-  std::vector<unsigned char> fb_log_hit;    // [frozen steps of the last call]
-  // masked-latent inpainting (fluxmi_engine_set_inpaint).  The buffers (x0 | noise | mask, each bf16 [B, Lpred, C_out]: room
-  // for a plain call's B images) are one allocation made at the first masked call of a prepared shape and dropped with the workspace; the
-  // per-step tables ride in the constants block and the pinned schedule staging.  A request without a mask allocates and launches none of it.
-  bool inp_on = false, inp_diff = false;
-  int inp_B = 0;                   // the caller's images the buffers hold
-  std::vector<double> inp_thr;     // differential thresholds, one per step of the following denoise call
-  char* inp_mem = nullptr;
-  size_t inp_bytes = 0;
-  float *d_tnext = nullptr, *d_omt = nullptr, *d_thr = nullptr;
-  // solver program (fluxmi_engine_set_solver): the host tables of the following denoise calls, their device copies
-  // (an allocation of their own, staged through h_sched like dts), and the saved iterate / two fp32 history slots (xs bf16 | hist fp32 [2], each
-  // [B, Lpred, C_out]) made at the first solver call of a prepared shape and dropped with the workspace.  Nothing of it without a solver.
-  bool sol_on = false;
-  int sol_n = 0;
-  std::vector<float> sol_coef;     // [sol_n][8]
-  std::vector<int> sol_ctl;        // [sol_n][4]
-  float* d_sol_coef = nullptr;
-  int* d_sol_ctl = nullptr;
-  char* sol_mem = nullptr;
-  size_t sol_bytes = 0;
-  // the noise of a stochastic program (fluxmi_engine_set_solver_noise): the host ids [sol_noise_B][4] and the evaluation offset of the
-  // following denoise calls; their device copy "sol_ids" (uint32 [B][4] | the offset, staged through h_sched like the tables) is made at
-  // the first noise call of a prepared shape and dropped with the workspace.  Nothing of it without noise.
-  bool sol_noise = false;
-  int sol_noise_B = 0, sol_eval_offset = 0;
-  std::vector<unsigned> sol_ids;
-  unsigned* d_sol_ids = nullptr;
-  size_t sol_ids_bytes = 0;
-  // guidance shaping (fluxmi_engine_set_guidance): the host parameters and step offset of the following guided denoise
-  // calls; their device copy "gd_params" (float [8] | the offset, staged through h_sched like the schedule), the moments' partials "gd_part",
-  // the last step's coefficients "gd_coef" and APG's running difference "gd_r" (fp32 [B / 2][Lpred * C_out]) are one allocation made at the
-  // first shaped call of a prepared shape and dropped with the workspace.  Nothing of it without shaping.
-  bool gd_on = false;
-  bool gd_zero_r = false;          // a set call came in: the next guided denoise call zeroes "gd_r" on its stream
-  float gd_params[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  int gd_offset = 0;
-  char* gd_mem = nullptr;
-  size_t gd_bytes = 0;
-  // FlowEdit (fluxmi_engine_set_flow_edit / _denoise_edit): the host tables, ids, offset and guidance pair of the following
-  // edit calls.  Device side, three allocations dropped with the workspace: fe_mem = "fe_x0" (bf16 [B / 2, Lpred, C_out], filled by the set
-  // call) | "fe_tab" (coef fp32 [MAX_STEPS][4] | ctl int [MAX_STEPS][2] | ids uint32 [FLUXMI_ENGINE_MAX_BATCH][4] | the offset, staged through h_sched like the
-  // solver's), fe_zmem = "fe_z" made by the first edit call of a prepared shape, fe_accmem = "fe_acc" (fp32) made by the first edit call whose
-  // program has a row without first or apply.  Nothing of it without an edit request.  fe_call: the running denoise call is an edit call.
-  bool fe_on = false, fe_call = false, fe_need_acc = false;
-  int fe_B = 0, fe_n = 0, fe_eval_offset = 0;
-  float fe_gs = 0.f, fe_gt = 0.f;
-  std::vector<float> fe_coef;      // [fe_n][4]
-  std::vector<int> fe_ctl;         // [fe_n][2]
-  std::vector<unsigned> fe_ids;    // [fe_B][4]
-  char *fe_mem = nullptr, *fe_zmem = nullptr, *fe_accmem = nullptr;
-  size_t fe_bytes = 0, fe_zbytes = 0, fe_accbytes = 0;
-  // Tiled generation (fluxmi_engine_set_windows / _denoise_windows): the geometry {N, Hc, Wc, h, w, ny, nx} of the
-  // following windowed calls.  Device side, one allocation dropped with the workspace: win_mem = "win_x" (the canvas, bf16 [N, Hc, Wc, C]) |
-  // "win_tab" (row0 int [ny] | col0 int [nx] | Ny fp32 [ny][Hc] | Nx fp32 [nx][Wc], each 256-byte aligned, filled by the set call).  Nothing
-  // of it without a windowed request.  win_call: the running denoise call is a windowed call.
-  bool win_on = false, win_call = false;
-  int win_geo[7] = {0, 0, 0, 0, 0, 0, 0};
-  size_t win_off[4] = {0, 0, 0, 0};  // the four tables' offsets in "win_tab"
-  char* win_mem = nullptr;
-  size_t win_bytes = 0;
-  // ControlNet (fluxmi_controlnet_create / fluxmi_engine_attach_controlnet).  A net is an engine of its own kind
-  // (is_cn): no final layer, the controlnet_* projections behind the trunk's linears, the residuals of a forward in its workspace buffer
-  // "cn_res" [Nd + Ns][B, Li, H].  The main engine holds the attached net (cn) and the conditioning scale (d_cn_scale, device data).
-  bool is_cn = false;
-  int i_cn_x = -1, i_cn_d0 = -1, i_cn_s0 = -1;   // controlnet_x_embedder, controlnet_blocks[0], controlnet_single_blocks[0]
-  const void* cn_mode_table = nullptr;           // controlnet_mode_embedder.weight bf16 [cn_num_mode, H] (Union), or none
-  int cn_num_mode = 0;
-  int txt_extra = 0;               // 1: row 0 of the text stream is the mode embedding (Lt = the request's text rows + 1)
-  int cn_trial = 0;                // the net's own calibration counter
-  // a number no other engine state of this process ever had (next_generation): renewed at create, when the workspace is dropped and when the
-  // weights are re-bound.  Step graphs that baked a net in are keyed on it, never on the net's address alone (the allocator reuses addresses)
-  unsigned long long ws_gen = 0;
-  fluxmi_engine* cn = nullptr;        // main: the attached net
-  fluxmi_engine* cn_owner = nullptr;  // net: the main engine it is attached to
-  int cn_batch = 0;                // main: the caller's images the attached cond holds
-  float* d_cn_scale = nullptr;
-  // IP-Adapter (fluxmi_engine_set_ip_adapter): the step-invariant keys / values of every double block and the
-  // per-sample, per-block scales in ONE engine-owned allocation (k | v, each bf16 [depth][B][Nk][H], then scales fp32 [B][depth]) made by the
-  // set call -- never inside a capture -- kept while it is large enough and dropped with the workspace.  Contents are device data; on / off,
-  // the buffer and Nk are a kind of step graph.  Nothing of it without an adapter.
-  bool ip_on = false;
-  int ip_nk = 0, ip_B = 0;
-  char* ip_mem = nullptr;
-  size_t ip_bytes = 0;
-  unsigned long long ip_gen = 0;
-  std::vector<float> ip_scales_h;  // the staged scales' host copy (alive until the next set call: the source of an asynchronous copy)
-  // progress, previews and cancellation (fluxmi_engine_set_preview): the host state of the following denoise calls.  The
-  // device buffers ("pv_proj" float [51] | "pv_ctl" int {every, eval_offset} | "pv_out" uint8 [SLOTS][B][2 h][2 w][3]) are one allocation made at
-  // the first previewed call of a prepared shape and dropped with the workspace; proj and ctl are staged through h_sched like the schedule.
-  // The pinned delivery buffer, the private copy stream and the event ring are made by the first set call with a hook and live as long as
-  // the engine.  Nothing of it without a hook; with every = 0 only the events.
-  fluxmi_step_hook_t pv_hook = nullptr;
-  void* pv_user = nullptr;
-  int pv_every = 0, pv_offset = 0, pv_n = 0, pv_h = 0, pv_w = 0;
-  float pv_proj[51];
-  char* pv_mem = nullptr;
-  size_t pv_bytes = 0;
-  unsigned char* pv_host = nullptr;
-  size_t pv_host_bytes = 0;
-  hipStream_t pv_stream = nullptr;
-  hipEvent_t pv_ev[FLUXMI_PREVIEW_DEPTH + 1] = {};
-  // ... and the state of the running call: evaluations launched / delivered to the hook, the caller's images, whether the hook said stop
-  int pv_launched = 0, pv_delivered = 0, pv_images = 0;
-  bool pv_cancelled = false;
-  long long captures = 0;          // graph captures since create (fluxmi_engine_preview_stats: read-only, for tests)
-};
-
-namespace {
-
-typedef fluxmi_engine E;
-
-template <class T> T* buf(E* e, const char* name) {
-  auto it = e->bufs.find(name);
-  return it == e->bufs.end() ? nullptr : (T*)it->second.p;
-}
-
-static u16 host_f2bf(double v) {
-  float f = (float)v;
-  unsigned u;
-  memcpy(&u, &f, 4);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (u16)(u >> 16);
-}
 
 // fluxmi_tuning_t.fuse_kv (FLUXMI_FUSE_KV): 0 = K / V^T by the relayout kernel, 1 = V^T from the qkv GEMM epilogue, 2 (default) = K and V^T
 // from the epilogue: no relayout launch at all.  Round 1 (profiles/r01_fuse_kv_ab.txt: 52.23 / 51.50 / 51.70 ms per step) had K's
@@ -287,17 +46,8 @@ const void* attn_groups(E* e) { return e->masked ? buf<void>(e, "attn_groups") :
 // folded arithmetic (softmax scale in Q, running max in the accumulator init; include/fluxmi.h, fluxmi_attention).  0 = bf16 K, the unfolded kernel.
 int attn_f16k() { return fluxmi_tuning().attn_f16k; }
 
-// weight prefetch riding on launches with idle CUs (fluxmi_internal.h, FluxmiPrefetch): the fp8 weights of up to six linears, for the next
-// launch that supports it; `wgs` = the CUs that launch leaves idle in its last round
-void set_pf(fluxmi_engine* e, std::initializer_list<int> lins, int wgs);
-const void* pairs_of(fluxmi_engine* e, int li);
-
 int lin_count(const fluxmi_model_desc_t& d) { return 6 + (d.guidance_embed ? 2 : 0) + d.depth * 10 + d.depth_single * 3 + 2; }
 // a ControlNet: the trunk without its final layer + controlnet_x_embedder + one projection per block
-unsigned long long next_generation() {
-  static std::atomic<unsigned long long> g{0};
-  return ++g;
-}
 int cn_lin_count(const fluxmi_model_desc_t& d) { return lin_count(d) - 2 + 1 + d.depth + d.depth_single; }
 
 // double-block linear slots / single-block linear slots
@@ -309,6 +59,13 @@ const fluxmi_linear_t& SL(E* e, int blk, int slot) { return e->lin[e->i_single0 
 int DLi(E* e, int blk, int slot) { return e->i_double0 + blk * 10 + slot; }
 int SLi(E* e, int blk, int slot) { return e->i_single0 + blk * 3 + slot; }
 
+// the row-pair copy of linear li's weight, or nullptr
+const void* pairs_of(E* e, int li) {
+  if (!e->pairs || e->pairs_dirty || !fluxmi_tuning().w_pairs || li < 0 || li >= (int)e->pairs_off.size() || e->pairs_off[li] < 0) return nullptr;
+  return e->pairs + e->pairs_off[li];
+}
+// weight prefetch riding on launches with idle CUs (fluxmi_internal.h, FluxmiPrefetch): the fp8 weights of up to six linears, for the next
+// launch that supports it; `wgs` = the CUs that launch leaves idle in its last round
 void set_pf(fluxmi_engine* e, std::initializer_list<int> lins, int wgs) {
   FluxmiPrefetch pf;
   memset(&pf, 0, sizeof(pf));
@@ -327,85 +84,6 @@ void set_pf(fluxmi_engine* e, std::initializer_list<int> lins, int wgs) {
 }
 int idle_cus(long long wgs) { return (int)((256 - wgs % 256) % 256); }
 
-// the row-pair copy of linear li's weight, or nullptr
-const void* pairs_of(E* e, int li) {
-  if (!e->pairs || e->pairs_dirty || !fluxmi_tuning().w_pairs || li < 0 || li >= (int)e->pairs_off.size() || e->pairs_off[li] < 0) return nullptr;
-  return e->pairs + e->pairs_off[li];
-}
-// ACTIVATIONS in the row-pair layout (round 6; fluxmi_gemm_group_t.a_pairs / c8_pairs, fluxmi_tuning_t.a_pairs): in FUSED mode the fp8
-// activation buffers a8 / attn8 / h8 / cat8 -- written by LayerNorm, attention and the quantising GEMM epilogues, read as the A operand of
-// the block linears -- keep the 64-byte K-steps of rows 2r and 2r + 1 in one 128-byte line, so an A panel's lines cross L2 -> CU once per
-// tile instead of twice (what W_pairs does for the weights).  Needs every row offset of a group to be even: L and Lt even, hidden % 64 == 0.
-// The unfused / calibrating modes keep plain rows (their producers are the standalone quantise kernels).
-// Every producer and consumer of the step must handle the layout: the LayerNorm kernel writes it only from its streaming form (hidden <= 3072,
-// ln_variant >= 2: fluxmi_ln_pairs_ok), and the generic GEMM kernel -- the fallback of a launch no tile config fits, e.g. a single block's
-// split column 3H that is no multiple of a 256-column tile -- reads and writes plain rows only; otherwise the step keeps plain rows (same bits).
-bool act_pairs(const E* e, bool fused) {
-  const int H = e->d.hidden, Hm = e->d.mlp_hidden;
-  return fused && fluxmi_tuning().a_pairs && e->L % 2 == 0 && e->Lt % 2 == 0 && fluxmi_ln_pairs_ok(H) && Hm % 128 == 0 && (3 * H) % 256 == 0;
-}
-// fp8 activation buffers whose layout is recorded (fluxmi_engine::act_in_pairs)
-enum { ACT_A8 = 0, ACT_ATTN8 = 1, ACT_H8 = 2, ACT_CAT8 = 3 };
-// Linears whose launches go through the kernels that honour W_pairs at Flux geometry: the persistent kernel (double blocks' qkv and mlp.0,
-// single blocks' linear1) and the one-wave-per-SIMD kernel (mlp.2, linear2).  +8 GB at Flux-dev.  Built lazily on the caller's stream:
-// create / rebind have none, and a rebind follows weight surgery.
-int ensure_pairs(E* e, hipStream_t s) {
-  if (!e->pairs_dirty && e->pairs_gen == fluxmi_tuning_generation()) return 0;
-  e->pairs_gen = fluxmi_tuning_generation();
-  const int n = (int)e->lin.size();
-  std::vector<long long> off(n, -1);
-  size_t total = 0;
-  if (fluxmi_tuning().w_pairs) {
-    auto want = [&](int li) {
-      const fluxmi_linear_t& l = e->lin[li];
-      // fp8 weights only.  (The kernels read row-pair copies of BF16 weights as well since round 6 -- tests/test_ops_gpu.py::
-      // test_gemm_bf16_row_pair_weights -- but for the bf16 flow they measured +1 %: Flux-schnell 256^2, 15.06 / 14.99 ms per step with copies,
-      // 15.21 / 15.17 without, for 23.8 GB of copies; its M = 512 launches are bound by the A side and by latency, DESIGN.md section 9.)
-      const size_t eb = 1;
-      if (l.kind != 1 || !l.weight || l.N % 2 || (l.K * eb) % 64) return;
-      off[li] = (long long)total;
-      total += ((size_t)l.N * l.K * eb + 255) & ~(size_t)255;
-    };
-    // (proj: the ping-pong kernel, tile config 13, honours W_pairs since round 6, but copies of the proj weights measured nothing in the step --
-    // 38.71 / 38.74 / 38.76 ms with, 38.71 / 38.75 / 38.71 without, profiles/r06_act_pairs.txt -- so they are not made)
-    for (int i = 0; i < e->d.depth; ++i)
-      for (int sl : {D_IMG_QKV, D_TXT_QKV, D_IMG_MLP0, D_TXT_MLP0, D_IMG_MLP2, D_TXT_MLP2}) want(DLi(e, i, sl));
-    for (int i = 0; i < e->d.depth_single; ++i) { want(SLi(e, i, S_LIN1)); want(SLi(e, i, S_LIN2)); }
-  }
-  if (total == 0 && e->pairs) {  // switched off (fluxmi_tuning_t.w_pairs = 0): give the memory back
-    FLUXMI_CHECK_HIP(hipStreamSynchronize(s));
-    hipFree(e->pairs);
-    e->pairs = nullptr; e->pairs_bytes = 0;
-  }
-  if (total > e->pairs_bytes) {
-    if (e->pairs) hipFree(e->pairs);
-    e->pairs = nullptr; e->pairs_bytes = 0;
-    // The copies are an optimisation (same results without them): they must not take the memory the caller still needs -- the torch
-    // allocator's next block, the VAE's 5.9 GB of patch matrices -- so they are only made while at least as much again (and 4 GiB) stays free
-    size_t free_b = 0, total_b = 0;
-    const bool room = hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b >= 2 * total + ((size_t)4 << 30);
-    if (!room || hipMalloc((void**)&e->pairs, total) != hipSuccess) {
-      // no room for the copies: run without them (same results, ~3 % slower steps) -- said once per engine, and tried again at the next
-      // fluxmi_engine_prepare (the caller's allocator may have given memory back by then); hipMemGetInfo does not see what the torch
-      // allocator holds cached, so this depends on the allocator's state at the first launch
-      (void)hipGetLastError();
-      if (!e->pairs_skipped)
-        fprintf(stderr, "fluxmi: row-pair weight copies skipped (%.1f GB wanted, %.1f GB free of %.1f): the GEMMs read the plain weights\n",
-                total / 1e9, free_b / 1e9, total_b / 1e9);
-      e->pairs_skipped = true;
-      e->pairs_off.assign(n, -1);
-      e->pairs_dirty = false;
-      return 0;
-    }
-    e->pairs_skipped = false;
-    e->pairs_bytes = total;
-  }
-  for (int li = 0; li < n; ++li)
-    if (off[li] >= 0) FLUXMI_TRY(fluxmi_k_pair_rows(e->lin[li].weight, e->pairs + off[li], e->lin[li].N, (long long)e->lin[li].K * (e->lin[li].kind == 1 ? 1 : 2), s));
-  e->pairs_off = off;
-  e->pairs_dirty = false;
-  return 0;
-}
 
 FluxmiGemmGroup mk_group(const fluxmi_linear_t& l, const void* A, long long lda, void* C, long long ldc, int M) {
   FluxmiGemmGroup g;
@@ -608,6 +286,86 @@ int compute_vec_and_mods(E* e, const u16* t_vec, const u16* g_vec, const u16* y,
   const size_t a8_stride = ((size_t)B * e->gemv_maxK + 255) & ~(size_t)255;
   return mods_gemm(e, svec, B, buf<u16>(e, "mod"), buf<uint8_t>(e, "mods_a8"), a8_stride, s);
 }
+}  // namespace
+
+unsigned long long next_generation() {
+  static std::atomic<unsigned long long> g{0};
+  return ++g;
+}
+// ACTIVATIONS in the row-pair layout (round 6; fluxmi_gemm_group_t.a_pairs / c8_pairs, fluxmi_tuning_t.a_pairs): in FUSED mode the fp8
+// activation buffers a8 / attn8 / h8 / cat8 -- written by LayerNorm, attention and the quantising GEMM epilogues, read as the A operand of
+// the block linears -- keep the 64-byte K-steps of rows 2r and 2r + 1 in one 128-byte line, so an A panel's lines cross L2 -> CU once per
+// tile instead of twice (what W_pairs does for the weights).  Needs every row offset of a group to be even: L and Lt even, hidden % 64 == 0.
+// The unfused / calibrating modes keep plain rows (their producers are the standalone quantise kernels).
+// Every producer and consumer of the step must handle the layout: the LayerNorm kernel writes it only from its streaming form (hidden <= 3072,
+// ln_variant >= 2: fluxmi_ln_pairs_ok), and the generic GEMM kernel -- the fallback of a launch no tile config fits, e.g. a single block's
+// split column 3H that is no multiple of a 256-column tile -- reads and writes plain rows only; otherwise the step keeps plain rows (same bits).
+bool act_pairs(const E* e, bool fused) {
+  const int H = e->d.hidden, Hm = e->d.mlp_hidden;
+  return fused && fluxmi_tuning().a_pairs && e->L % 2 == 0 && e->Lt % 2 == 0 && fluxmi_ln_pairs_ok(H) && Hm % 128 == 0 && (3 * H) % 256 == 0;
+}
+// fp8 activation buffers whose layout is recorded (fluxmi_engine::act_in_pairs)
+enum { ACT_A8 = 0, ACT_ATTN8 = 1, ACT_H8 = 2, ACT_CAT8 = 3 };
+// Linears whose launches go through the kernels that honour W_pairs at Flux geometry: the persistent kernel (double blocks' qkv and mlp.0,
+// single blocks' linear1) and the one-wave-per-SIMD kernel (mlp.2, linear2).  +8 GB at Flux-dev.  Built lazily on the caller's stream:
+// create / rebind have none, and a rebind follows weight surgery.
+int ensure_pairs(E* e, hipStream_t s) {
+  if (!e->pairs_dirty && e->pairs_gen == fluxmi_tuning_generation()) return 0;
+  e->pairs_gen = fluxmi_tuning_generation();
+  const int n = (int)e->lin.size();
+  std::vector<long long> off(n, -1);
+  size_t total = 0;
+  if (fluxmi_tuning().w_pairs) {
+    auto want = [&](int li) {
+      const fluxmi_linear_t& l = e->lin[li];
+      // fp8 weights only.  (The kernels read row-pair copies of BF16 weights as well since round 6 -- tests/test_ops_gpu.py::
+      // test_gemm_bf16_row_pair_weights -- but for the bf16 flow they measured +1 %: Flux-schnell 256^2, 15.06 / 14.99 ms per step with copies,
+      // 15.21 / 15.17 without, for 23.8 GB of copies; its M = 512 launches are bound by the A side and by latency, DESIGN.md section 9.)
+      const size_t eb = 1;
+      if (l.kind != 1 || !l.weight || l.N % 2 || (l.K * eb) % 64) return;
+      off[li] = (long long)total;
+      total += ((size_t)l.N * l.K * eb + 255) & ~(size_t)255;
+    };
+    // (proj: the ping-pong kernel, tile config 13, honours W_pairs since round 6, but copies of the proj weights measured nothing in the step --
+    // 38.71 / 38.74 / 38.76 ms with, 38.71 / 38.75 / 38.71 without, profiles/r06_act_pairs.txt -- so they are not made)
+    for (int i = 0; i < e->d.depth; ++i)
+      for (int sl : {D_IMG_QKV, D_TXT_QKV, D_IMG_MLP0, D_TXT_MLP0, D_IMG_MLP2, D_TXT_MLP2}) want(DLi(e, i, sl));
+    for (int i = 0; i < e->d.depth_single; ++i) { want(SLi(e, i, S_LIN1)); want(SLi(e, i, S_LIN2)); }
+  }
+  if (total == 0 && e->pairs) {  // switched off (fluxmi_tuning_t.w_pairs = 0): give the memory back
+    FLUXMI_CHECK_HIP(hipStreamSynchronize(s));
+    hipFree(e->pairs);
+    e->pairs = nullptr; e->pairs_bytes = 0;
+  }
+  if (total > e->pairs_bytes) {
+    if (e->pairs) hipFree(e->pairs);
+    e->pairs = nullptr; e->pairs_bytes = 0;
+    // The copies are an optimisation (same results without them): they must not take the memory the caller still needs -- the torch
+    // allocator's next block, the VAE's 5.9 GB of patch matrices -- so they are only made while at least as much again (and 4 GiB) stays free
+    size_t free_b = 0, total_b = 0;
+    const bool room = hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b >= 2 * total + ((size_t)4 << 30);
+    if (!room || hipMalloc((void**)&e->pairs, total) != hipSuccess) {
+      // no room for the copies: run without them (same results, ~3 % slower steps) -- said once per engine, and tried again at the next
+      // fluxmi_engine_prepare (the caller's allocator may have given memory back by then); hipMemGetInfo does not see what the torch
+      // allocator holds cached, so this depends on the allocator's state at the first launch
+      (void)hipGetLastError();
+      if (!e->pairs_skipped)
+        fprintf(stderr, "fluxmi: row-pair weight copies skipped (%.1f GB wanted, %.1f GB free of %.1f): the GEMMs read the plain weights\n",
+                total / 1e9, free_b / 1e9, total_b / 1e9);
+      e->pairs_skipped = true;
+      e->pairs_off.assign(n, -1);
+      e->pairs_dirty = false;
+      return 0;
+    }
+    e->pairs_skipped = false;
+    e->pairs_bytes = total;
+  }
+  for (int li = 0; li < n; ++li)
+    if (off[li] >= 0) FLUXMI_TRY(fluxmi_k_pair_rows(e->lin[li].weight, e->pairs + off[li], e->lin[li].N, (long long)e->lin[li].K * (e->lin[li].kind == 1 ? 1 : 2), s));
+  e->pairs_off = off;
+  e->pairs_dirty = false;
+  return 0;
+}
 
 int embed_txt(E* e, const u16* txt, bool calib, int trial, u16* dst, long long dst_bstride, hipStream_t s) {
   // (a Union ControlNet: row 0 of the text stream is the mode embedding, put_mode_row; txt_in's rows follow it)
@@ -640,8 +398,7 @@ int put_mode_row(E* e, u16* dst, long long dst_bstride, hipStream_t s) {
 // so the table is bit-identical to what compute_vec_and_mods produces step by step), 8 rows per weight pass.
 // ---------------------------------------------------------------------------------------------------------
 // table geometry for `rows` rows: [table | t | temb | hidden | vec_t | vec | silu(vec) | per-group quantised activations]
-constexpr int MODS_STEPS = 64;  // steps per table window; a longer request rebuilds the table every MODS_STEPS steps
-size_t mods_table_bytes(E* e, size_t rows) {
+static size_t mods_table_bytes(E* e, size_t rows) {
   auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
   const size_t H = e->d.hidden;
   return al(rows * e->mod_cols * 2) + al(rows * 2) + al(rows * 512) + 4 * al(rows * H * 2) + FLUXMI_MAX_GROUPS * al(rows * (size_t)e->gemv_maxK);
@@ -707,7 +464,7 @@ int precompute_mods(E* e, int step0, int step_end, const u16* g_vec, const u16* 
 // per stream, single-block linear1 -> linear2), see fluxmi_gemm_group_t.q_lut.  Rebuilt (77 tiny launches) whenever a fused
 // sequence starts, so they always reflect the current input scales.  fluxmi_tuning_t.qlut = 0 turns them off.
 // ---------------------------------------------------------------------------------------------------------
-bool qlut_enabled() { return fluxmi_tuning().qlut != 0; }
+static bool qlut_enabled() { return fluxmi_tuning().qlut != 0; }
 int build_qluts(E* e, hipStream_t s) {
   uint8_t* lut = buf<uint8_t>(e, "qlut");
   if (!lut || !qlut_enabled() || e->qlut_valid) return 0;
@@ -723,6 +480,8 @@ int build_qluts(E* e, hipStream_t s) {
   }
   return 0;
 }
+
+namespace {
 
 // Workspace pointers of one forward pass (looked up once).
 struct Ctx {
@@ -1012,12 +771,13 @@ int final_layer(E* e, u16* pred, int s0, int s1, hipStream_t s) {
   }
   return 0;
 }
+}  // namespace
 
 // the channels the model predicts: final_layer.linear's N (== in_channels but for channel-conditioned models, see fluxmi_engine_create)
 int c_out(const E* e) { return e->is_cn ? e->d.in_channels : e->lin[e->i_final_lin].N; }
 
 // ControlNet: r_k = bf16(proj(x_img)) of the image rows of the stream after block k (slot k < Nd: double, Nd + k: single) -> "cn_res"[slot]
-int cn_project(E* e, int li, int slot, hipStream_t s) {
+static int cn_project(E* e, int li, int slot, hipStream_t s) {
   const int H = e->d.hidden, B = e->B, Li = e->Li;
   const long long XB = (long long)e->L * H;
   u16* x = buf<u16>(e, "x") + (long long)e->Lt * H;
@@ -1028,7 +788,7 @@ int cn_project(E* e, int li, int slot, hipStream_t s) {
   return run_gemm(gs, H, H, 0, 0, FLUXMI_EPI_BF16, s);
 }
 // main engine with a net attached: x_img = bf16(x_img + bf16(r_slot * scale)) after a controlled block
-int cn_add(E* e, int slot, hipStream_t s) {
+static int cn_add(E* e, int slot, hipStream_t s) {
   const E* n = e->cn;
   const int H = e->d.hidden;
   const long long one = (long long)e->Li * H;
@@ -1038,11 +798,12 @@ int cn_add(E* e, int slot, hipStream_t s) {
 
 // IP-Adapter: x_img = bf16(x_img + bf16(o_i * scale[b][i])) behind double block i, o_i from the block's raw image q still in "qkv" (all
 // L - Lt image-stream rows: Kontext reference rows included)
-int ip_add(E* e, int i, hipStream_t s) {
+static int ip_add(E* e, int i, hipStream_t s) {
   const int H = e->d.hidden, B = e->B, nk = e->ip_nk;
   const long long kv = (long long)e->d.depth * B * nk * H;  // elements of k (and of v)
-  const u16* k = (const u16*)e->ip_mem + (long long)i * B * nk * H;
-  const float* sc = (const float*)(e->ip_mem + (size_t)kv * 4) + i;
+  const char* mem = e->side[SB_IP].p;
+  const u16* k = (const u16*)mem + (long long)i * B * nk * H;
+  const float* sc = (const float*)(mem + (size_t)kv * 4) + i;
   return fluxmi_k_ip_attention(buf<u16>(e, "qkv") + (long long)e->Lt * 3 * H, 3 * H, (long long)e->L * 3 * H, e->norm[i * 4], k, k + kv,
                                (long long)nk * H, buf<u16>(e, "x") + (long long)e->Lt * H, H, (long long)e->L * H, sc, e->d.depth, B, e->Li,
                                e->d.heads, nk, s);
@@ -1050,7 +811,7 @@ int ip_add(E* e, int i, hipStream_t s) {
 
 // Every block linear (the modulation linears apart) is F8Linear: what the fused path needs.  Otherwise *blk is the first block that has a
 // bf16 one: double block *blk, or single block *blk - depth.
-bool all_block_linears_f8(E* e, int* blk = nullptr) {
+bool all_block_linears_f8(E* e, int* blk) {
   int bad = -1;
   for (int i = 0; i < e->d.depth && bad < 0; ++i)
     for (int sl : {D_IMG_QKV, D_IMG_PROJ, D_IMG_MLP0, D_IMG_MLP2, D_TXT_QKV, D_TXT_PROJ, D_TXT_MLP0, D_TXT_MLP2})
@@ -1060,7 +821,7 @@ bool all_block_linears_f8(E* e, int* blk = nullptr) {
   if (blk) *blk = bad;
   return bad < 0;
 }
-int require_all_f8(E* e) {
+static int require_all_f8(E* e) {
   int blk;
   if (all_block_linears_f8(e, &blk)) return 0;
   if (blk < e->d.depth) fluxmi_set_error("fused mode needs every block linear to be F8Linear (double block %d)", blk);
@@ -1068,20 +829,14 @@ int require_all_f8(E* e) {
   return 1;
 }
 
-// ---------------------------------------------------------------------------------------------------------
-// Phases [p0, p1] of the forward: 0 = embedders + modulation vectors, 1 = double block 0, 2 = every later block, 3 = final layer.  The step
-// cache cuts the frozen step between them (head = 0..1, body = 2..3, skip = 3); every other caller runs 0..3, the launches it always ran.
-enum { PH_EMBED = 0, PH_BLOCK0 = 1, PH_BLOCKS = 2, PH_FINAL = 3 };
+// The phases [p0, p1] (engine_state.h, PH_*) of the forward.
 int forward_impl(E* e, const u16* img, const u16* txt, const u16* y, const u16* t_vec, const u16* g_vec, u16* pred, int mode,
-                 int trial, bool txt_cached, hipStream_t s, int p0 = PH_EMBED, int p1 = PH_FINAL) {
+                 int trial, bool txt_cached, hipStream_t s, int p0, int p1) {
   const int H = e->d.hidden, Hm = e->d.mlp_hidden, B = e->B, L = e->L, Lt = e->Lt, Li = e->Li, heads = e->d.heads;
   const bool fused = mode == 1, calib = mode == 0;
   const long long XB = (long long)L * H;  // batch stride of x
   u16* x = buf<u16>(e, "x");
-  u16 *mod = buf<u16>(e, "mod"), *qkv = buf<u16>(e, "qkv"), *Q = buf<u16>(e, "Q"), *K = buf<u16>(e, "K"), *VT = buf<u16>(e, "VT");
-  u16 *pe = buf<u16>(e, "pe"), *abf = buf<u16>(e, "abf"), *catbf = buf<u16>(e, "catbf"), *hbf = buf<u16>(e, "hbf");
-  u16 *attnbf = buf<u16>(e, "attnbf"), *fin = buf<u16>(e, "fin");
-  uint8_t *a8 = buf<uint8_t>(e, "a8"), *attn8 = buf<uint8_t>(e, "attn8"), *h8 = buf<uint8_t>(e, "h8"), *cat8 = buf<uint8_t>(e, "cat8");
+  u16* mod = buf<u16>(e, "mod");
   uint8_t* in8 = buf<uint8_t>(e, "in8");
   const long long MC = e->mod_cols;
 
@@ -1138,28 +893,11 @@ int forward_impl(E* e, const u16* img, const u16* txt, const u16* y, const u16* 
   return 0;
 }
 
-int cn_forward(E* e, const u16* img, const u16* txt, const u16* y, const u16* t_vec, const u16* g_vec, int mode, int trial, bool table,
-               hipStream_t s);
-// Phases [p0, p1] of a frozen step's forward: the engine's static request buffers, the modulations from the step-ahead table
-int frozen_forward(E* e, int mode, const u16* g_arg, int p0, int p1, hipStream_t s) {
-  if (e->cn && p0 <= PH_EMBED)
-    FLUXMI_TRY(cn_forward(e, buf<u16>(e, "img_s"), buf<u16>(e, "txt_s"), buf<u16>(e, "y_s"), buf<u16>(e, "tvec"), buf<u16>(e, "gvec"),
-                          all_block_linears_f8(e->cn) ? 1 : 2, 0, true, s));
-  e->mods_table = true;
-  const int rc = forward_impl(e, buf<u16>(e, "img_s"), buf<u16>(e, "txt_s"), buf<u16>(e, "y_s"), buf<u16>(e, "tvec"), g_arg, buf<u16>(e, "pred_s"),
-                              mode, 0, mode == 1, s, p0, p1);
-  e->mods_table = false;
-  return rc;
-}
-
-bool needs_splitk(E* e) {
+static bool needs_splitk(E* e) {
   for (const fluxmi_linear_t& l : e->lin)
     if (!l.kind && (long long)l.K * 2 / 64 >= 192) return true;
   return false;
 }
-// the engine's split-K scratch for every launch of this thread while an engine entry point runs
-// ... and its scratch for attention's balanced grid; a prefetch left pending by an error return between set_pf and the launch that
-// would have consumed it is dropped here, on entry and on exit (it points into weights the caller may free afterwards)
 void scope_set(E* e) {
   auto it = e->bufs.find("splitk");
   fluxmi_set_splitk_scratch(it != e->bufs.end() && it->second.n >= FLUXMI_SPLITK_WS_BYTES ? (float*)it->second.p : nullptr);
@@ -1168,15 +906,6 @@ void scope_set(E* e) {
   fluxmi_set_prefetch(nullptr);
   fluxmi_gemm_set_batch(e->B);
 }
-struct SplitkScope {
-  explicit SplitkScope(E* e) { scope_set(e); }
-  ~SplitkScope() {
-    fluxmi_gemm_set_batch(1);
-    fluxmi_set_splitk_scratch(nullptr);
-    fluxmi_set_attn_scratch(nullptr);
-    fluxmi_set_prefetch(nullptr);
-  }
-};
 
 // One forward of the ControlNet attached to `e` (no final layer: phases 0 .. 2) on the buffers given -- the residuals land in the net's
 // "cn_res" -- under the net's own scratch scope; e's scope is restored behind it.  table: modulations from the net's step-ahead table.
@@ -1190,13 +919,24 @@ int cn_forward(E* e, const u16* img, const u16* txt, const u16* y, const u16* t_
   scope_set(e);
   return rc;
 }
+// Phases [p0, p1] of a frozen step's forward: the engine's static request buffers, the modulations from the step-ahead table
+int frozen_forward(E* e, int mode, const u16* g_arg, int p0, int p1, hipStream_t s) {
+  if (e->cn && p0 <= PH_EMBED)
+    FLUXMI_TRY(cn_forward(e, buf<u16>(e, "img_s"), buf<u16>(e, "txt_s"), buf<u16>(e, "y_s"), buf<u16>(e, "tvec"), buf<u16>(e, "gvec"),
+                          all_block_linears_f8(e->cn) ? 1 : 2, 0, true, s));
+  e->mods_table = true;
+  const int rc = forward_impl(e, buf<u16>(e, "img_s"), buf<u16>(e, "txt_s"), buf<u16>(e, "y_s"), buf<u16>(e, "tvec"), g_arg, buf<u16>(e, "pred_s"),
+                              mode, 0, mode == 1, s, p0, p1);
+  e->mods_table = false;
+  return rc;
+}
 bool any_f8(const E* e) {
   for (auto& l : e->lin)
     if (l.kind != 0) return true;
   return false;
 }
 
-void free_ws(E* e) {
+static void free_ws(E* e) {
   e->ws_gen = next_generation();
   // an attachment belongs to a prepared shape: dropped with the workspace of either side
   if (e->cn) { e->cn->cn_owner = nullptr; e->cn = nullptr; }
@@ -1204,24 +944,15 @@ void free_ws(E* e) {
   e->step_graphs.drop();
   e->fb_graphs.drop();
   e->qlut_valid = false;
-  if (e->fb_mem) { hipFree(e->fb_mem); e->fb_mem = nullptr; e->fb_bytes = 0; }
-  if (e->inp_mem) { hipFree(e->inp_mem); e->inp_mem = nullptr; e->inp_bytes = 0; }
+  for (SideBuf& sb : e->side) sb.drop(e);
+  e->sol_tab.drop(e);
+  e->d_sol_coef = nullptr; e->d_sol_ctl = nullptr;
   e->inp_on = e->inp_diff = false;
-  if (e->sol_mem) { hipFree(e->sol_mem); e->sol_mem = nullptr; e->sol_bytes = 0; }
-  if (e->d_sol_coef) { hipFree(e->d_sol_coef); e->d_sol_coef = nullptr; e->d_sol_ctl = nullptr; }
-  if (e->d_sol_ids) { hipFree(e->d_sol_ids); e->d_sol_ids = nullptr; e->sol_ids_bytes = 0; }
   e->sol_on = e->sol_noise = false;
-  if (e->fe_mem) { hipFree(e->fe_mem); e->fe_mem = nullptr; e->fe_bytes = 0; }
-  if (e->fe_zmem) { hipFree(e->fe_zmem); e->fe_zmem = nullptr; e->fe_zbytes = 0; }
-  if (e->fe_accmem) { hipFree(e->fe_accmem); e->fe_accmem = nullptr; e->fe_accbytes = 0; }
   e->fe_on = false;
-  if (e->win_mem) { hipFree(e->win_mem); e->win_mem = nullptr; e->win_bytes = 0; e->bufs.erase("win_x"); e->bufs.erase("win_tab"); }
   e->win_on = false;
-  if (e->gd_mem) { hipFree(e->gd_mem); e->gd_mem = nullptr; e->gd_bytes = 0; }
   e->gd_on = e->gd_zero_r = false;
-  if (e->ip_mem) { hipFree(e->ip_mem); e->ip_mem = nullptr; e->ip_bytes = 0; }
   e->ip_on = false;
-  if (e->pv_mem) { hipFree(e->pv_mem); e->pv_mem = nullptr; e->pv_bytes = 0; }
   e->pv_hook = nullptr;
   e->pv_every = 0;
   if (e->ws) { hipFree(e->ws); e->ws = nullptr; }
@@ -1230,236 +961,26 @@ void free_ws(E* e) {
   e->masked = false;
 }
 
-// the step cache's buffers for the prepared shape, made once a cached request arrives (a plain request's workspace stays what it was)
-constexpr long long FB_CHUNK_ELEMS = 16384;  // elements per workgroup of the metric pass (elementwise.hip, FB_CHUNK vectors)
-int ensure_fb(E* e, hipStream_t s) {
-  if (!e->h_ratio) FLUXMI_CHECK_HIP(hipHostMalloc((void**)&e->h_ratio, FLUXMI_ENGINE_MAX_BATCH * sizeof(float), hipHostMallocDefault));
-  if (!e->ev_fb) FLUXMI_CHECK_HIP(hipEventCreateWithFlags(&e->ev_fb, hipEventDisableTiming));
-  if (e->fb_mem) return 0;
-  const size_t n = (size_t)e->Lpred * e->d.hidden, rows = (size_t)e->B * n * 2;
-  const size_t chunks = (n + FB_CHUNK_ELEMS - 1) / FB_CHUNK_ELEMS;
-  struct Item { const char* name; size_t bytes; };
-  const Item items[] = {{"fb_h0", rows}, {"fb_h1", rows}, {"fb_rref", rows}, {"fb_R", rows}, {"fb_part", (size_t)e->B * chunks * 8},
-                        {"fb_ratio", (size_t)e->B * 3 * 4}};
-  size_t total = 0;
-  for (auto& it : items) total += (it.bytes + 255) & ~(size_t)255;
-  if (hipMalloc((void**)&e->fb_mem, total) != hipSuccess) {
-    (void)hipGetLastError();
-    e->fb_mem = nullptr;
-    fluxmi_set_error("engine_denoise: hipMalloc(%zu bytes) failed (step cache)", total);
-    return 2;
-  }
-  e->fb_bytes = total;
-  FLUXMI_CHECK_HIP(hipMemsetAsync(e->fb_mem, 0, total, s));
-  size_t off = 0;
-  for (auto& it : items) {
-    e->bufs[it.name] = Buf{e->fb_mem + off, it.bytes};
-    off += (it.bytes + 255) & ~(size_t)255;
-  }
+// what an attached ControlNet excludes, checked again by every call that runs it (the state may have been set after the attach)
+int cn_usable(E* e) {
+  FLUXMI_REQUIRE(!e->masked, "ControlNet: a token-group attention table is set on this engine (regional prompts do not combine with a ControlNet)");
+  FLUXMI_REQUIRE(!(e->fb_threshold > 0.f), "ControlNet: step caching is on (it does not combine with a ControlNet)");
+  FLUXMI_REQUIRE(e->cn->ws && e->cn->B == e->B && e->cn->Li == e->Li && e->cn->Lt == e->Lt + e->cn->txt_extra,
+                 "ControlNet: the attached net is not prepared for this engine's shape (attach it after fluxmi_engine_prepare)");
   return 0;
 }
 
-// the inpainting buffers of the prepared shape, made once a masked request arrives (like ensure_fb)
-int ensure_inp(E* e) {
-  if (e->inp_mem) return 0;
-  const size_t one = ((size_t)e->B * e->Lpred * c_out(e) * 2 + 255) & ~(size_t)255;
-  if (hipMalloc((void**)&e->inp_mem, 3 * one) != hipSuccess) {
-    (void)hipGetLastError();
-    e->inp_mem = nullptr;
-    fluxmi_set_error("engine_set_inpaint: hipMalloc(%zu bytes) failed", 3 * one);
-    return 2;
-  }
-  e->inp_bytes = 3 * one;
-  const char* names[3] = {"inp_x0", "inp_noise", "inp_mask"};
-  for (int i = 0; i < 3; ++i) e->bufs[names[i]] = Buf{e->inp_mem + i * one, one};
+// what a set IP-Adapter excludes, checked by every call that runs it (the state may have been set after the adapter)
+int ip_usable(E* e) {
+  FLUXMI_REQUIRE(!e->masked, "IP-Adapter: a token-group attention table is set on this engine (regional prompts do not combine with an IP-Adapter)");
+  FLUXMI_REQUIRE(!(e->fb_threshold > 0.f), "IP-Adapter: step caching is on (it does not combine with an IP-Adapter)");
+  FLUXMI_REQUIRE(e->side[SB_IP].p && e->ip_B == e->B, "IP-Adapter: the adapter holds %d samples, the prepared batch is %d", e->ip_B, e->B);
   return 0;
 }
-
-// the solver's saved iterate and history slots of the prepared shape, made once a solver request arrives (like ensure_fb)
-int ensure_sol(E* e, hipStream_t s) {
-  if (e->sol_mem) return 0;
-  // the device tables (coef [MAX_STEPS][8] | ctl [MAX_STEPS][4]): constants like d_dts, but made here and not in the constants block, so
-  // that an engine that never sees a solver allocates what it allocated before; like the constants block, not counted as workspace
-  if (!e->d_sol_coef) {
-    if (hipMalloc((void**)&e->d_sol_coef, (size_t)MAX_STEPS * 12 * 4) != hipSuccess) {
-      (void)hipGetLastError();
-      e->d_sol_coef = nullptr;
-      fluxmi_set_error("engine_denoise: hipMalloc(%zu bytes) failed (solver tables)", (size_t)MAX_STEPS * 12 * 4);
-      return 2;
-    }
-    e->d_sol_ctl = (int*)(e->d_sol_coef + (size_t)MAX_STEPS * 8);
-  }
-  const size_t elems = (size_t)e->B * e->Lpred * c_out(e);
-  const size_t xs = (elems * 2 + 255) & ~(size_t)255, hist = (2 * elems * 4 + 255) & ~(size_t)255;
-  if (hipMalloc((void**)&e->sol_mem, xs + hist) != hipSuccess) {
-    (void)hipGetLastError();
-    e->sol_mem = nullptr;
-    fluxmi_set_error("engine_denoise: hipMalloc(%zu bytes) failed (solver buffers)", xs + hist);
-    return 2;
-  }
-  e->sol_bytes = xs + hist;
-  FLUXMI_CHECK_HIP(hipMemsetAsync(e->sol_mem, 0, xs + hist, s));
-  e->bufs["sol_xs"] = Buf{e->sol_mem, xs};
-  e->bufs["sol_hist"] = Buf{e->sol_mem + xs, hist};
-  return 0;
-}
-
-// the device copy of the noise ids and the evaluation offset, made once a request with noise arrives
-int ensure_sol_ids(E* e) {
-  if (e->d_sol_ids) return 0;
-  const size_t bytes = ((size_t)e->B * 16 + 4 + 255) & ~(size_t)255;
-  if (hipMalloc((void**)&e->d_sol_ids, bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    e->d_sol_ids = nullptr;
-    fluxmi_set_error("engine_denoise: hipMalloc(%zu bytes) failed (solver noise ids)", bytes);
-    return 2;
-  }
-  e->sol_ids_bytes = bytes;
-  e->bufs["sol_ids"] = Buf{(char*)e->d_sol_ids, bytes};
-  return 0;
-}
-
-// FlowEdit's buffers of the prepared shape (like ensure_fb), for the B / 2 images an edit call of this shape steps: the init latent and the
-// device tables (made by the set call, which fills x0), the edit state, and the fp32 accumulator of a program that averages
-constexpr size_t FE_TAB_BYTES = (size_t)MAX_STEPS * 6 * 4 + (size_t)FLUXMI_ENGINE_MAX_BATCH * 16 + 4;
-int fe_alloc(E* e, char** mem, size_t* bytes, const char* const* names, const size_t* sizes, int n, bool zero, hipStream_t s) {
-  if (*mem) return 0;
-  size_t total = 0;
-  for (int i = 0; i < n; ++i) total += (sizes[i] + 255) & ~(size_t)255;
-  if (hipMalloc((void**)mem, total) != hipSuccess) {
-    (void)hipGetLastError();
-    *mem = nullptr;
-    fluxmi_set_error("engine_flow_edit: hipMalloc(%zu bytes) failed (%s)", total, names[0]);
-    return 2;
-  }
-  *bytes = total;
-  if (zero) FLUXMI_CHECK_HIP(hipMemsetAsync(*mem, 0, total, s));
-  size_t off = 0;
-  for (int i = 0; i < n; ++i) {
-    e->bufs[names[i]] = Buf{*mem + off, sizes[i]};
-    off += (sizes[i] + 255) & ~(size_t)255;
-  }
-  return 0;
-}
-size_t fe_elems(const E* e) { return (size_t)std::max(1, e->B / 2) * e->Lpred * c_out(e); }
-int ensure_fe_x0(E* e, hipStream_t s) {
-  const char* names[2] = {"fe_x0", "fe_tab"};
-  const size_t sizes[2] = {fe_elems(e) * 2, FE_TAB_BYTES};
-  return fe_alloc(e, &e->fe_mem, &e->fe_bytes, names, sizes, 2, true, s);
-}
-int ensure_fe_z(E* e, hipStream_t s) {
-  const char* names[1] = {"fe_z"};
-  const size_t sizes[1] = {fe_elems(e) * 2};
-  return fe_alloc(e, &e->fe_zmem, &e->fe_zbytes, names, sizes, 1, true, s);
-}
-int ensure_fe_acc(E* e, hipStream_t s) {
-  const char* names[1] = {"fe_acc"};
-  const size_t sizes[1] = {fe_elems(e) * 4};
-  return fe_alloc(e, &e->fe_accmem, &e->fe_accbytes, names, sizes, 1, true, s);
-}
-
-// the guidance-shaping buffers of the prepared shape, made once a shaped guided request arrives (like ensure_fb); Bh = the caller's images
-constexpr long long GD_CHUNK_ELEMS = 16384;  // elements per workgroup of the moments pass (guidance.hip, GD_CHUNK vectors)
-int ensure_gd(E* e, hipStream_t s) {
-  if (e->gd_mem) return 0;
-  const size_t Bh = (size_t)e->B / 2, n = (size_t)e->Lpred * c_out(e), chunks = (n + GD_CHUNK_ELEMS - 1) / GD_CHUNK_ELEMS;
-  struct Item { const char* name; size_t bytes; };
-  const Item items[] = {{"gd_params", 9 * 4}, {"gd_part", Bh * chunks * 9 * 4}, {"gd_coef", Bh * 4 * 4}, {"gd_r", Bh * n * 4}};
-  size_t total = 0;
-  for (auto& it : items) total += (it.bytes + 255) & ~(size_t)255;
-  if (hipMalloc((void**)&e->gd_mem, total) != hipSuccess) {
-    (void)hipGetLastError();
-    e->gd_mem = nullptr;
-    fluxmi_set_error("engine_denoise: hipMalloc(%zu bytes) failed (guidance shaping)", total);
-    return 2;
-  }
-  e->gd_bytes = total;
-  FLUXMI_CHECK_HIP(hipMemsetAsync(e->gd_mem, 0, total, s));
-  size_t off = 0;
-  for (auto& it : items) {
-    e->bufs[it.name] = Buf{e->gd_mem + off, it.bytes};
-    off += (it.bytes + 255) & ~(size_t)255;
-  }
-  return 0;
-}
-
-// the preview buffers of the prepared shape, made once a previewed request arrives (like ensure_fb): room for a plain call's B images
-int ensure_pv(E* e, hipStream_t s) {
-  if (e->pv_mem) return 0;
-  struct Item { const char* name; size_t bytes; };
-  const Item items[] = {{"pv_proj", 51 * 4}, {"pv_ctl", 2 * 4}, {"pv_out", (size_t)FLUXMI_PREVIEW_SLOTS * e->B * e->Lpred * 4 * 3}};
-  size_t total = 0;
-  for (auto& it : items) total += (it.bytes + 255) & ~(size_t)255;
-  if (hipMalloc((void**)&e->pv_mem, total) != hipSuccess) {
-    (void)hipGetLastError();
-    e->pv_mem = nullptr;
-    fluxmi_set_error("engine_denoise: hipMalloc(%zu bytes) failed (preview)", total);
-    return 2;
-  }
-  e->pv_bytes = total;
-  FLUXMI_CHECK_HIP(hipMemsetAsync(e->pv_mem, 0, total, s));
-  size_t off = 0;
-  for (auto& it : items) {
-    e->bufs[it.name] = Buf{e->pv_mem + off, it.bytes};
-    off += (it.bytes + 255) & ~(size_t)255;
-  }
-  return 0;
-}
-
-}  // namespace
-
-// roctx ranges (rocprofv3 --marker-trace) around the phases of a denoise call, resolved at run time so that the library has no
-// hard dependency on the profiler: fluxmi_tuning_t.roctx (FLUXMI_ROCTX=1) turns them on.
-namespace {
-struct Roctx {
-  int (*push)(const char*) = nullptr;
-  int (*pop)() = nullptr;
-  Roctx() {
-    if (!fluxmi_tuning().roctx) return;
-    void* h = dlopen("libroctx64.so", RTLD_NOW | RTLD_GLOBAL);
-    if (!h) h = dlopen("librocprofiler-sdk-roctx.so", RTLD_NOW | RTLD_GLOBAL);
-    if (!h) return;
-    push = (int (*)(const char*))dlsym(h, "roctxRangePushA");
-    pop = (int (*)())dlsym(h, "roctxRangePop");
-    if (!push || !pop) push = nullptr, pop = nullptr;
-  }
-};
-Roctx& roctx() { static Roctx r; return r; }
-struct Range {
-  Range(const char* name) { if (roctx().push) roctx().push(name); }
-  ~Range() { if (roctx().pop) roctx().pop(); }
-};
-}  // namespace
 
 extern "C" {
 
 int fluxmi_engine_num_linears(const fluxmi_model_desc_t* desc) { return desc ? lin_count(*desc) : -1; }
-
-static int create_impl(const fluxmi_model_desc_t* desc, const fluxmi_linear_t* linears, int n_linears, const void* const* norm_scales,
-                       int n_norm_scales, bool cn, const void* mode_table, int num_mode, fluxmi_engine_t** out);
-int fluxmi_engine_create(const fluxmi_model_desc_t* desc, const fluxmi_linear_t* linears, int n_linears,
-                         const void* const* norm_scales, int n_norm_scales, fluxmi_engine_t** out) {
-  return create_impl(desc, linears, n_linears, norm_scales, n_norm_scales, false, nullptr, 0, out);
-}
-
-int fluxmi_controlnet_num_linears(const fluxmi_model_desc_t* desc) { return desc ? cn_lin_count(*desc) : -1; }
-
-int fluxmi_controlnet_create(const fluxmi_model_desc_t* desc, const fluxmi_linear_t* linears, int n_linears, const void* const* norm_scales,
-                             int n_norm_scales, const void* mode_table, int num_mode, fluxmi_engine_t** out) {
-  FLUXMI_REQUIRE(desc && linears, "controlnet_create: NULL argument");
-  FLUXMI_REQUIRE(desc->depth >= 1 && desc->depth_single >= 0, "controlnet_create: a ControlNet has at least one double block (got %d + %d)",
-                 desc->depth, desc->depth_single);
-  FLUXMI_REQUIRE((mode_table != nullptr) == (num_mode > 0) && num_mode >= 0, "controlnet_create: mode_table and num_mode (%d) go together", num_mode);
-  FLUXMI_REQUIRE(n_linears == cn_lin_count(*desc), "controlnet_create: expected %d linears, got %d", cn_lin_count(*desc), n_linears);
-  const int first = lin_count(*desc) - 2, H = desc->hidden;
-  for (int i = first; i < n_linears; ++i) {
-    const int K = i == first ? desc->in_channels : H;
-    FLUXMI_REQUIRE(linears[i].kind == 0 && linears[i].weight && linears[i].N == H && linears[i].K == K,
-                   "controlnet_create: linear %d (controlnet_%s) must be a bf16 nn.Linear [%d, %d] (kind %d, [%d, %d])", i,
-                   i == first ? "x_embedder" : "blocks / controlnet_single_blocks", H, K, linears[i].kind, linears[i].N, linears[i].K);
-  }
-  return create_impl(desc, linears, n_linears, norm_scales, n_norm_scales, true, mode_table, num_mode, out);
-}
 
 static int create_impl(const fluxmi_model_desc_t* desc, const fluxmi_linear_t* linears, int n_linears, const void* const* norm_scales,
                        int n_norm_scales, bool cn, const void* mode_table, int num_mode, fluxmi_engine_t** out) {
@@ -1523,8 +1044,8 @@ static int create_impl(const fluxmi_model_desc_t* desc, const fluxmi_linear_t* l
   e->d_cn_scale = (float*)(e->consts + o_cns);
   e->d_tnext = (float*)(e->consts + o_tnext); e->d_omt = (float*)(e->consts + o_omt); e->d_thr = (float*)(e->consts + o_thr);
   hipMemset(e->consts, 0, off);
-  // pinned staging for the schedule (ts | dts | tnext | 1 - tnext | thresholds | solver coef | solver ctl | noise ids | eval offset) + the events (guard of the staging buffer, timing of the frozen steps)
-  if (hipHostMalloc((void**)&e->h_sched, (5 * (MAX_STEPS + 1) + 12 * MAX_STEPS + 4 * FLUXMI_ENGINE_MAX_BATCH + 1 + 9 + 53 + 6 * MAX_STEPS + 4 * FLUXMI_ENGINE_MAX_BATCH + 1) * sizeof(float), hipHostMallocDefault) != hipSuccess ||
+  // pinned staging for the tables of a denoise call (engine_state.h, SchedStaging) + the events (guard of the staging buffer, timing of the frozen steps)
+  if (hipHostMalloc((void**)&e->h_sched, sizeof(SchedStaging), hipHostMallocDefault) != hipSuccess ||
       hipEventCreateWithFlags(&e->ev_sched, hipEventDisableTiming) != hipSuccess || hipEventCreate(&e->ev_t0) != hipSuccess ||
       hipEventCreate(&e->ev_t1) != hipSuccess) {
     fluxmi_engine_destroy(e);
@@ -1533,6 +1054,30 @@ static int create_impl(const fluxmi_model_desc_t* desc, const fluxmi_linear_t* l
   }
   *out = e;
   return 0;
+}
+
+int fluxmi_engine_create(const fluxmi_model_desc_t* desc, const fluxmi_linear_t* linears, int n_linears,
+                         const void* const* norm_scales, int n_norm_scales, fluxmi_engine_t** out) {
+  return create_impl(desc, linears, n_linears, norm_scales, n_norm_scales, false, nullptr, 0, out);
+}
+
+int fluxmi_controlnet_num_linears(const fluxmi_model_desc_t* desc) { return desc ? cn_lin_count(*desc) : -1; }
+
+int fluxmi_controlnet_create(const fluxmi_model_desc_t* desc, const fluxmi_linear_t* linears, int n_linears, const void* const* norm_scales,
+                             int n_norm_scales, const void* mode_table, int num_mode, fluxmi_engine_t** out) {
+  FLUXMI_REQUIRE(desc && linears, "controlnet_create: NULL argument");
+  FLUXMI_REQUIRE(desc->depth >= 1 && desc->depth_single >= 0, "controlnet_create: a ControlNet has at least one double block (got %d + %d)",
+                 desc->depth, desc->depth_single);
+  FLUXMI_REQUIRE((mode_table != nullptr) == (num_mode > 0) && num_mode >= 0, "controlnet_create: mode_table and num_mode (%d) go together", num_mode);
+  FLUXMI_REQUIRE(n_linears == cn_lin_count(*desc), "controlnet_create: expected %d linears, got %d", cn_lin_count(*desc), n_linears);
+  const int first = lin_count(*desc) - 2, H = desc->hidden;
+  for (int i = first; i < n_linears; ++i) {
+    const int K = i == first ? desc->in_channels : H;
+    FLUXMI_REQUIRE(linears[i].kind == 0 && linears[i].weight && linears[i].N == H && linears[i].K == K,
+                   "controlnet_create: linear %d (controlnet_%s) must be a bf16 nn.Linear [%d, %d] (kind %d, [%d, %d])", i,
+                   i == first ? "x_embedder" : "blocks / controlnet_single_blocks", H, K, linears[i].kind, linears[i].N, linears[i].K);
+  }
+  return create_impl(desc, linears, n_linears, norm_scales, n_norm_scales, true, mode_table, num_mode, out);
 }
 
 int fluxmi_engine_destroy(fluxmi_engine_t* e) {
@@ -1593,16 +1138,6 @@ int fluxmi_engine_prepare(fluxmi_engine_t* e, int B, int Li, int Lt, const void*
   return fluxmi_engine_prepare_cond(e, B, Li, 0, Lt, img_ids, txt_ids, stream);
 }
 
-// Li_pred noisy rows + Lc reference rows per sample (FLUX.1 Kontext): the engine's image stream is Li = Li_pred + Lc rows long.  The split is
-// part of the workspace key: the same (B, Li, Lt) with another split re-allocates, which drops the captured step graph (its final layer and
-// Euler update are sized by the split).
-static int prepare_impl(fluxmi_engine_t* e, int B, int Li_pred, int Lc, int Lt, const void* img_ids, const void* txt_ids, const fluxmi_engine_t* ids_from,
-                        hipStream_t s);
-int fluxmi_engine_prepare_cond(fluxmi_engine_t* e, int B, int Li_pred, int Lc, int Lt, const void* img_ids, const void* txt_ids, void* stream) {
-  FLUXMI_REQUIRE(e && !e->is_cn, "engine_prepare: a ControlNet engine is prepared by fluxmi_engine_attach_controlnet");
-  FLUXMI_REQUIRE(img_ids && (Lt == 0 || txt_ids), "engine_prepare: NULL ids");
-  return prepare_impl(e, B, Li_pred, Lc, Lt, img_ids, txt_ids, nullptr, (hipStream_t)stream);
-}
 // ids_from: (a ControlNet) the main engine whose position ids this shape shares -- its text rows (behind a copy of the first of them for the
 // mode row of a Union net: Lt counts that row), then its image rows
 static int prepare_impl(fluxmi_engine_t* e, int B, int Li_pred, int Lc, int Lt, const void* img_ids, const void* txt_ids, const fluxmi_engine_t* ids_from,
@@ -1695,21 +1230,13 @@ static int prepare_impl(fluxmi_engine_t* e, int B, int Li_pred, int Lc, int Lt, 
   return 0;
 }
 
-// what an attached ControlNet excludes, checked again by every call that runs it (the state may have been set after the attach)
-static int cn_usable(fluxmi_engine_t* e) {
-  FLUXMI_REQUIRE(!e->masked, "ControlNet: a token-group attention table is set on this engine (regional prompts do not combine with a ControlNet)");
-  FLUXMI_REQUIRE(!(e->fb_threshold > 0.f), "ControlNet: step caching is on (it does not combine with a ControlNet)");
-  FLUXMI_REQUIRE(e->cn->ws && e->cn->B == e->B && e->cn->Li == e->Li && e->cn->Lt == e->Lt + e->cn->txt_extra,
-                 "ControlNet: the attached net is not prepared for this engine's shape (attach it after fluxmi_engine_prepare)");
-  return 0;
-}
-
-// what a set IP-Adapter excludes, checked by every call that runs it (the state may have been set after the adapter)
-static int ip_usable(fluxmi_engine_t* e) {
-  FLUXMI_REQUIRE(!e->masked, "IP-Adapter: a token-group attention table is set on this engine (regional prompts do not combine with an IP-Adapter)");
-  FLUXMI_REQUIRE(!(e->fb_threshold > 0.f), "IP-Adapter: step caching is on (it does not combine with an IP-Adapter)");
-  FLUXMI_REQUIRE(e->ip_mem && e->ip_B == e->B, "IP-Adapter: the adapter holds %d samples, the prepared batch is %d", e->ip_B, e->B);
-  return 0;
+// Li_pred noisy rows + Lc reference rows per sample (FLUX.1 Kontext): the engine's image stream is Li = Li_pred + Lc rows long.  The split is
+// part of the workspace key: the same (B, Li, Lt) with another split re-allocates, which drops the captured step graph (its final layer and
+// Euler update are sized by the split).
+int fluxmi_engine_prepare_cond(fluxmi_engine_t* e, int B, int Li_pred, int Lc, int Lt, const void* img_ids, const void* txt_ids, void* stream) {
+  FLUXMI_REQUIRE(e && !e->is_cn, "engine_prepare: a ControlNet engine is prepared by fluxmi_engine_attach_controlnet");
+  FLUXMI_REQUIRE(img_ids && (Lt == 0 || txt_ids), "engine_prepare: NULL ids");
+  return prepare_impl(e, B, Li_pred, Lc, Lt, img_ids, txt_ids, nullptr, (hipStream_t)stream);
 }
 
 int fluxmi_engine_forward(fluxmi_engine_t* e, const void* img, const void* txt, const void* y, const void* timesteps,
@@ -1737,946 +1264,6 @@ int fluxmi_engine_forward(fluxmi_engine_t* e, const void* img, const void* txt, 
   }
   return forward_impl(e, (const u16*)img, (const u16*)txt, (const u16*)y, (const u16*)timesteps, (const u16*)guidance, (u16*)pred,
                       mode, trial_index, false, (hipStream_t)stream);
-}
-
-
-// ---------------------------------------------------------------------------------------------------------
-// The frozen steps [step, n_steps) of a request: ONE loop (frozen_steps) for the plain step and for the step with first-block caching.  The
-// two differ only in their Stepper: the pieces a step is cut into -- each piece is one captured graph -- and how a step is sequenced from them.
-// ---------------------------------------------------------------------------------------------------------
-typedef std::function<int(hipStream_t)> StepFn;
-struct StepPiece { const char* name; StepFn run; };
-struct Stepper {
-  StepGraphs* g;
-  const char* range;                    // roctx range around the steps
-  int n_pieces;
-  StepPiece piece[3];
-  std::function<int(bool graph)> step;  // one step on the caller's stream: the pieces replayed (graph) or run eagerly
-  std::function<int()> pre_warm;        // what precedes the eager warm step (may be empty)
-};
-
-// The ONE staleness rule of both graph sets.  Kernel choices are baked into a captured piece: never replay one captured under other knobs
-// (the quantising-epilogue tables follow the knobs too).  The update kernel is baked in as well, and `warmed` speaks of one update kind: a
-// plain and a guided request of one shape never share a graph or a warm step, whether or not a graph exists yet.  The old pieces stay
-// allocated until the re-capture replaces them (behind its stream synchronisation).
-static void graphs_stale(fluxmi_engine_t* e, StepGraphs& g, bool cfg) {
-  if (g.ok && g.gen != fluxmi_tuning_generation()) g.ok = g.warmed = e->qlut_valid = false;
-  const bool diff = e->inp_on && e->inp_diff;
-  // masked versus dense attention is a kind like guided versus plain, and so are the blend update and its differential form
-  const bool shaped = cfg && e->gd_on;  // ... and guidance shaping; an unguided request does not consult the state
-  const void* fe_acc = e->fe_call ? e->fe_accmem : nullptr;  // (once made, the buffer rides in every edit launch: a row with first and apply ignores it)
-  if (g.cfg != cfg || g.masked != e->masked || g.blend != e->inp_on || g.diff != diff || g.solver != e->sol_on || g.noise != e->sol_noise ||
-      g.shaped != shaped || g.edit != e->fe_call || g.fe_acc != fe_acc)
-    g.ok = g.warmed = false;
-  // ... and the windowed update with its canvas: a windowed request never replays a plain or guided request's pieces, nor they its
-  const void* win_x = e->win_call ? e->win_mem : nullptr;
-  if (g.win != e->win_call || g.win_x != win_x || (e->win_call && memcmp(g.win_geo, e->win_geo, sizeof g.win_geo) != 0)) g.ok = g.warmed = false;
-  g.win = e->win_call;
-  g.win_x = win_x;
-  if (e->win_call) memcpy(g.win_geo, e->win_geo, sizeof g.win_geo); else memset(g.win_geo, 0, sizeof g.win_geo);
-  // ... and the preview launch with its token grid (cadence, offset and factors are device data: they never re-capture)
-  const bool previewed = e->pv_hook && e->pv_every > 0;
-  if (g.previewed != previewed || (previewed && (g.pv_h != e->pv_h || g.pv_w != e->pv_w))) g.ok = g.warmed = false;
-  g.previewed = previewed;
-  g.pv_h = previewed ? e->pv_h : 0;
-  g.pv_w = previewed ? e->pv_w : 0;
-  // ... and so is the attached ControlNet: its launches, weights and workspace pointers are baked into the pieces
-  if (g.cn != e->cn || (e->cn && g.cn_gen != e->cn->ws_gen)) g.ok = g.warmed = false;
-  g.cn = e->cn;
-  g.cn_gen = e->cn ? e->cn->ws_gen : 0;
-  // ... and the IP-Adapter: its launches, its buffer and Nk are baked in (K / V contents and scales are device data)
-  const void* ip = e->ip_on ? e->ip_mem : nullptr;
-  if (g.ip != ip || (ip && (g.ip_nk != e->ip_nk || g.ip_gen != e->ip_gen))) g.ok = g.warmed = false;
-  g.ip = ip;
-  g.ip_nk = ip ? e->ip_nk : 0;
-  g.ip_gen = ip ? e->ip_gen : 0;
-  g.cfg = cfg;
-  g.masked = e->masked;
-  g.blend = e->inp_on;
-  g.diff = diff;
-  g.solver = e->sol_on;
-  g.noise = e->sol_noise;
-  g.shaped = shaped;
-  g.edit = e->fe_call;  // ... and FlowEdit's update: an edit request never replays a plain or guided request's pieces, nor they its
-  g.fe_acc = fe_acc;
-}
-
-// Captures pieces[0 .. n) into g.exec[0 .. n) on a private non-blocking stream (the caller has synchronised its own).  The only place that
-// captures and instantiates; the stream sits behind a guard, so that no error path keeps it.
-static int capture_pieces(StepGraphs& g, const StepPiece* pieces, int n) {
-  struct CaptureStream {
-    hipStream_t s = nullptr;
-    ~CaptureStream() { if (s) hipStreamDestroy(s); }
-  } cs;
-  FLUXMI_CHECK_HIP(hipStreamCreateWithFlags(&cs.s, hipStreamNonBlocking));
-  for (int p = 0; p < n; ++p) {
-    hipGraph_t graph = nullptr;
-    hipError_t ce = hipStreamBeginCapture(cs.s, hipStreamCaptureModeThreadLocal);
-    const int rc = ce == hipSuccess ? pieces[p].run(cs.s) : 0;
-    if (ce == hipSuccess) ce = hipStreamEndCapture(cs.s, &graph);  // ends the capture of a failed piece as well
-    if (g.exec[p]) { hipGraphExecDestroy(g.exec[p]); g.exec[p] = nullptr; }
-    if (!rc && ce == hipSuccess) ce = hipGraphInstantiate(&g.exec[p], graph, nullptr, nullptr, 0);
-    if (graph) hipGraphDestroy(graph);
-    if (!rc && ce != hipSuccess) fluxmi_set_error("engine_denoise: capturing %s failed: %s", pieces[p].name, hipGetErrorString(ce));
-    if (rc || ce != hipSuccess) return rc ? rc : 2;
-  }
-  g.ok = true;
-  g.gen = fluxmi_tuning_generation();
-  return 0;
-}
-
-// ---- the throttled loop of a hooked call (fluxmi.h, fluxmi_engine_set_preview) ---------------------------------------------------------------
-// Evaluation k of the call goes to the hook: waits on the event recorded behind it, copies its preview slot -- if it has one -- to the pinned
-// buffer on the private stream, waits for that copy, calls the hook on the caller's thread.  A non-zero return sets pv_cancelled.
-static int pv_deliver(fluxmi_engine_t* e, int k) {
-  FLUXMI_CHECK_HIP(hipEventSynchronize(e->pv_ev[k % (FLUXMI_PREVIEW_DEPTH + 1)]));
-  const long long g = (long long)e->pv_offset + k;
-  const unsigned char* rgb = nullptr;
-  if (e->pv_every > 0 && g % e->pv_every == 0) {
-    const size_t bytes = (size_t)e->pv_images * e->pv_h * e->pv_w * 4 * 3;
-    const size_t slot = (size_t)((g / e->pv_every) % FLUXMI_PREVIEW_SLOTS);
-    FLUXMI_CHECK_HIP(hipMemcpyAsync(e->pv_host, buf<unsigned char>(e, "pv_out") + slot * bytes, bytes, hipMemcpyDeviceToHost, e->pv_stream));
-    FLUXMI_CHECK_HIP(hipStreamSynchronize(e->pv_stream));
-    rgb = e->pv_host;
-  }
-  e->pv_delivered = k + 1;
-  if (e->pv_hook(e->pv_user, (int)g, e->pv_n, rgb, e->pv_images, 2 * e->pv_h, 2 * e->pv_w) != 0) e->pv_cancelled = true;
-  return 0;
-}
-// One evaluation of a denoise call, `run`, under the look-ahead rule: the ONE helper of the calibrating loop and of frozen_steps.  Without a
-// hook it is `run` alone.  With one: before launching evaluation i >= DEPTH, every evaluation up to i - DEPTH not yet delivered is delivered,
-// in order; a cancel there returns FLUXMI_CANCELLED with nothing further launched.  Behind the launch the evaluation's event is recorded: slot
-// i % (DEPTH + 1) of the ring, last used by evaluation i - DEPTH - 1, which has been delivered.
-static int pv_eval(fluxmi_engine_t* e, hipStream_t s, const std::function<int()>& run) {
-  if (!e->pv_hook) return run();
-  const int i = e->pv_launched;
-  while (e->pv_delivered <= i - FLUXMI_PREVIEW_DEPTH) {
-    FLUXMI_TRY(pv_deliver(e, e->pv_delivered));
-    if (e->pv_cancelled) return FLUXMI_CANCELLED;
-  }
-  FLUXMI_TRY(run());
-  FLUXMI_CHECK_HIP(hipEventRecord(e->pv_ev[i % (FLUXMI_PREVIEW_DEPTH + 1)], s));
-  e->pv_launched = i + 1;
-  return 0;
-}
-
-// The modulation vectors of up to MODS_STEPS steps are produced ahead (one pass over the 3.2 GB of modulation weights per window); the table
-// address and the device-side window origin never change, so ONE set of captured pieces serves every step of every request.  The first frozen
-// step of a shape and update kind runs eagerly, so that every lazy one-time init (function attributes) happens outside capture; the steps
-// behind it are replayed (use_graph) or run eagerly.  *first_timed = the first step behind ev_t0.
-static int frozen_steps(fluxmi_engine_t* e, const Stepper& st, int mode, bool cfg, int step, int n_steps, const u16* g_arg, int use_graph,
-                        int* first_timed, hipStream_t s) {
-  StepGraphs& g = *st.g;
-  bool t0 = false;
-  while (step < n_steps) {
-    const int win_end = std::min(n_steps, step + MODS_STEPS);
-    {
-      Range r("step-ahead modulation table");
-      FLUXMI_TRY(precompute_mods(e, step, win_end, g_arg, buf<u16>(e, "y_s"), s));
-      if (e->cn) {  // the attached ControlNet's own table, from the same schedule, guidance and y
-        scope_set(e->cn);
-        const int rc = precompute_mods(e->cn, step, win_end, e->cn->d.guidance_embed ? buf<u16>(e, "gvec") : nullptr, buf<u16>(e, "y_s"), s);
-        scope_set(e);
-        FLUXMI_TRY(rc);
-      }
-    }
-    graphs_stale(e, g, cfg);
-    if (use_graph && !g.ok) {
-      if (!g.warmed) {
-        if (st.pre_warm) FLUXMI_TRY(st.pre_warm());
-        FLUXMI_TRY(pv_eval(e, s, [&]() { return st.step(false); }));
-        ++step;
-        g.warmed = true;
-      }
-      if (step < win_end) {
-        FLUXMI_CHECK_HIP(hipStreamSynchronize(s));  // one-time, at graph capture only
-        FLUXMI_TRY(capture_pieces(g, st.piece, st.n_pieces));
-        ++e->captures;
-      }
-    }
-    Range r(st.range);
-    // ev_t0 .. ev_t1 (fluxmi_engine_last_timing) brackets frozen STEPS only: recorded behind the first window's modulation table, the eager
-    // warm step and the graph capture of a new shape (a request longer than MODS_STEPS steps includes its later table builds)
-    if (!t0) {
-      FLUXMI_CHECK_HIP(hipEventRecord(e->ev_t0, s));
-      *first_timed = step;
-      t0 = true;
-    }
-    const bool graph = use_graph && g.ok;
-    int rc = 0;  // (a cancelled call leaves through here as well: what was replayed wrote the buffers)
-    for (; step < win_end && !rc; ++step) rc = pv_eval(e, s, [&]() { return st.step(graph); });
-    if (graph) {
-      // the host code of the step ran at capture only: the replayed pieces wrote the activation buffers in the layout they were captured
-      // with (a tuning change since the capture re-captures above)
-      const bool ap = act_pairs(e, mode == 1);
-      for (bool& b : e->act_in_pairs) b = ap;
-    }
-    FLUXMI_TRY(rc);
-  }
-  return 0;
-}
-
-// The plain step: one piece -- the forward, the update, the step counter -- and one hipGraphLaunch per replayed step.
-static int plain_steps(fluxmi_engine_t* e, int mode, bool cfg, int step, int n_steps, const u16* g_arg, int use_graph, const StepFn& euler,
-                       int* first_timed, hipStream_t s) {
-  Stepper st;
-  st.g = &e->step_graphs;
-  st.range = "frozen steps (hipGraph replay)";
-  st.n_pieces = 1;
-  st.piece[0] = {"the step", [&](hipStream_t t) -> int {
-                   FLUXMI_TRY(frozen_forward(e, mode, g_arg, PH_EMBED, PH_FINAL, t));
-                   FLUXMI_TRY(euler(t));
-                   return fluxmi_k_advance_step(e->d_step, t);
-                 }};
-  st.step = [&](bool graph) -> int {
-    if (!graph) return st.piece[0].run(s);
-    FLUXMI_CHECK_HIP(hipGraphLaunch(st.g->exec[0], s));
-    return 0;
-  };
-  return frozen_steps(e, st, mode, cfg, step, n_steps, g_arg, use_graph, first_timed, s);
-}
-
-// The step with first-block caching (fluxmi.h, fluxmi_engine_set_step_cache): three pieces with a host decision between them
-//   head: img_in, txt rows, select_step | h0 = x rows | double block 0 | r = bf16(x - h0) over h0, ratios -> pinned host
-//   host: waits for the head, reads the B ratios, decides
-//   body (miss): r_ref = r, h1 = x | blocks 1 .. | R = bf16(x - h1) | final layer, update, advance
-//   skip (hit):  x = bf16(x + R) (x still holds this step's h1) | final layer, update, advance
-// on the rows the final layer reads.  The rule's host state (have_full, consec) and the log live here; a plain request never comes here, so it
-// never allocates, captures or launches anything of the cache.
-static int cached_steps(fluxmi_engine_t* e, int mode, bool cfg, int step, int n_steps, const u16* g_arg, int use_graph, const StepFn& euler,
-                        int* first_timed, hipStream_t s) {
-  FLUXMI_REQUIRE(e->d.depth >= 1, "engine_denoise: step caching needs at least one double block");
-  FLUXMI_TRY(ensure_fb(e, s));
-  const int B = e->B, H = e->d.hidden;
-  const long long XB = (long long)e->L * H, n = (long long)e->Lpred * H;
-  u16* xr = buf<u16>(e, "x") + (long long)e->Lt * H;  // the rows the final layer reads: Lpred rows behind the text rows of each sample
-  u16 *h0 = buf<u16>(e, "fb_h0"), *h1 = buf<u16>(e, "fb_h1"), *rref = buf<u16>(e, "fb_rref"), *R = buf<u16>(e, "fb_R");
-  float *part = buf<float>(e, "fb_part"), *ratio = buf<float>(e, "fb_ratio");
-  auto fwd = [&](int p0, int p1, hipStream_t t) -> int { return frozen_forward(e, mode, g_arg, p0, p1, t); };
-  auto tail = [&](hipStream_t t) -> int {
-    FLUXMI_TRY(fwd(PH_FINAL, PH_FINAL, t));
-    FLUXMI_TRY(euler(t));
-    return fluxmi_k_advance_step(e->d_step, t);
-  };
-  Stepper st;
-  st.g = &e->fb_graphs;
-  st.range = "frozen steps (step cache)";
-  st.n_pieces = 3;
-  st.piece[0] = {"step-cache piece 0 (head)", [&](hipStream_t t) -> int {
-                   FLUXMI_TRY(fwd(PH_EMBED, PH_EMBED, t));
-                   FLUXMI_TRY(fluxmi_k_fb_snapshot(xr, XB, h0, B, n, t));
-                   FLUXMI_TRY(fwd(PH_BLOCK0, PH_BLOCK0, t));
-                   FLUXMI_TRY(fluxmi_k_fb_metric(xr, XB, h0, h0, rref, part, ratio, ratio + B, B, n, t));
-                   FLUXMI_CHECK_HIP(hipMemcpyAsync(e->h_ratio, ratio, (size_t)B * 4, hipMemcpyDeviceToHost, t));
-                   return 0;
-                 }};
-  st.piece[1] = {"step-cache piece 1 (body)", [&](hipStream_t t) -> int {
-                   FLUXMI_TRY(fluxmi_k_fb_commit(xr, XB, h0, rref, h1, B, n, t));
-                   FLUXMI_TRY(fwd(PH_BLOCKS, PH_BLOCKS, t));
-                   FLUXMI_TRY(fluxmi_k_fb_store(xr, XB, h1, R, B, n, t));
-                   return tail(t);
-                 }};
-  st.piece[2] = {"step-cache piece 2 (skip)", [&](hipStream_t t) -> int {
-                   FLUXMI_TRY(fluxmi_k_fb_apply(xr, XB, xr, XB, R, B, n, t));
-                   return tail(t);
-                 }};
-  // host state of the rule
-  bool have_full = false;  // a full step has run in THIS call: every call starts with an empty cache
-  int consec = 0;
-  e->fb_log_B = B;
-  auto run = [&](int p, bool graph) -> int {
-    if (!graph) return st.piece[p].run(s);
-    FLUXMI_CHECK_HIP(hipGraphLaunch(st.g->exec[p], s));
-    return 0;
-  };
-  st.step = [&](bool graph) -> int {
-    FLUXMI_TRY(run(0, graph));
-    FLUXMI_CHECK_HIP(hipEventRecord(e->ev_fb, s));
-    FLUXMI_CHECK_HIP(hipEventSynchronize(e->ev_fb));
-    bool hit = have_full && (e->fb_max_hits <= 0 || consec < e->fb_max_hits);
-    for (int b = 0; b < B; ++b) {
-      const float r = have_full ? e->h_ratio[b] : INFINITY;  // no reference yet: the step misses whatever r_ref still holds
-      e->fb_log_ratio.push_back(r);
-      hit = hit && r < e->fb_threshold;  // NaN and +inf (den == 0) are misses
-    }
-    e->fb_log_hit.push_back(hit ? 1 : 0);
-    consec = hit ? consec + 1 : 0;
-    have_full = have_full || !hit;
-    return run(hit ? 2 : 1, graph);
-  };
-  // lazy one-time inits happen outside capture: the warm step runs head and body eagerly -- it is the first frozen step of a call and
-  // misses -- and the skip piece's own kernel is launched once before it on x's image rows, which are dead here (img_in rewrites them next)
-  st.pre_warm = [&]() -> int {
-    FLUXMI_REQUIRE(!have_full, "engine_denoise: step-cache warm-up behind a full step");
-    return fluxmi_k_fb_apply(xr, XB, xr, XB, R, B, n, s);
-  };
-  return frozen_steps(e, st, mode, cfg, step, n_steps, g_arg, use_graph, first_timed, s);
-}
-
-// the denoise loop, plain or guided (cfg: true classifier-free guidance).  Guided: the prepared batch B is 2 Bh, samples [0, Bh) the prompt
-// branch and [Bh, B) the negative branch of the caller's Bh images; the caller's img [Bh, ...] is copied into both halves of the stream, every
-// forward runs on the B samples, and the update is fluxmi_k_cfg_euler, which keeps the halves bit-identical.
-// edit (fluxmi_engine_denoise_edit): the third kind.  The batch is 2 Bh as for a guided call -- samples [0, Bh) the source branches, [Bh, B)
-// the target branches -- but the halves hold different latents, `img` is the caller's edit state z [Bh, ...], and the update is
-// fluxmi_k_flowedit_step on the engine's "fe_z" / "fe_x0": the stream only carries the two model inputs the kernel rebuilds.
-static int denoise_impl(fluxmi_engine_t* e, void* img, const void* txt, const void* y, float guidance, bool cfg, float cfg_scale,
-                        const double* timesteps_host, int n_steps, int* trial_index_inout, int use_graph, void* stream, bool edit = false,
-                        bool win = false) {
-  hipStream_t s = (hipStream_t)stream;
-  if (e) e->fe_call = e->win_call = false;
-  FLUXMI_REQUIRE(e && e->ws, "engine_denoise: call fluxmi_engine_prepare first");
-  FLUXMI_REQUIRE(!e->is_cn, "engine_denoise: a ControlNet engine runs attached to a main engine (fluxmi_engine_attach_controlnet)");
-  FLUXMI_REQUIRE(!cfg || e->B % 2 == 0, "engine_denoise_cfg: the prepared batch (%d) must be even: prompt branches first, then the negative "
-                 "branches of the same images (2B <= %d)", e->B, FLUXMI_ENGINE_MAX_BATCH);
-  FLUXMI_REQUIRE(img && txt && y && timesteps_host && trial_index_inout, "engine_denoise: NULL argument");
-  FLUXMI_REQUIRE(n_steps >= 0 && n_steps <= MAX_STEPS, "engine_denoise: n_steps=%d out of range", n_steps);
-  if (edit) {
-    FLUXMI_REQUIRE(e->fe_on, "engine_denoise_edit: no FlowEdit state is set (fluxmi_engine_set_flow_edit)");
-    FLUXMI_REQUIRE(e->B % 2 == 0, "engine_denoise_edit: the prepared batch (%d) must be even: source branches first, then the target branches "
-                   "of the same images (2B <= %d)", e->B, FLUXMI_ENGINE_MAX_BATCH);
-    FLUXMI_REQUIRE(e->Lpred == e->Li && c_out(e) == e->d.in_channels, "engine_denoise_edit: %d reference rows, %d input and %d predicted "
-                   "channels: FlowEdit steps the whole stream (no Kontext reference, no Fill / Depth / Canny model)", e->Li - e->Lpred,
-                   e->d.in_channels, c_out(e));
-    FLUXMI_REQUIRE(e->fe_B == e->B / 2, "engine_denoise_edit: the FlowEdit state holds %d images, this call steps %d (half the prepared batch)",
-                   e->fe_B, e->B / 2);
-    FLUXMI_REQUIRE(e->fe_n == n_steps, "engine_denoise_edit: the FlowEdit program holds %d evaluations, this call runs %d "
-                   "(fluxmi_engine_set_flow_edit takes one row per evaluation of the call)", e->fe_n, n_steps);
-    FLUXMI_REQUIRE(!e->inp_on, "engine_denoise_edit: an inpainting state is set (FlowEdit edits the whole image: no mask)");
-    FLUXMI_REQUIRE(!e->sol_on, "engine_denoise_edit: a solver program is set (FlowEdit's update is its own: sampler euler only)");
-    FLUXMI_REQUIRE(!(e->fb_threshold > 0.f), "engine_denoise_edit: step caching is on (every evaluation runs on a fresh draw: consecutive "
-                   "evaluations are not comparable)");
-    FLUXMI_REQUIRE(!e->masked, "engine_denoise_edit: an attention-group table is set (regional prompts do not combine with FlowEdit)");
-    FLUXMI_REQUIRE(!e->cn, "engine_denoise_edit: a ControlNet is attached (not combined with FlowEdit)");
-    FLUXMI_REQUIRE(!e->ip_on, "engine_denoise_edit: an IP-Adapter is set (not combined with FlowEdit)");
-    FLUXMI_REQUIRE(!(e->pv_hook && e->pv_every > 0), "engine_denoise_edit: previews (every = %d > 0) are refused: the stream holds the two "
-                   "coupled model inputs, not a latent to preview (a hook with every = 0 reports progress and cancels)", e->pv_every);
-    FLUXMI_TRY(ensure_fe_z(e, s));
-    if (e->fe_need_acc) FLUXMI_TRY(ensure_fe_acc(e, s));
-    e->fe_call = true;
-  }
-  if (win) {
-    const int *g = e->win_geo, S = g[0] * g[5] * g[6];
-    FLUXMI_REQUIRE(e->win_on, "engine_denoise_windows: no window state is set (fluxmi_engine_set_windows)");
-    FLUXMI_REQUIRE(e->B == (cfg ? 2 * S : S) && e->Li == g[3] * g[4], "engine_denoise_windows: the window state holds %d images x %d x %d "
-                   "windows of %d x %d tokens, the prepared shape %d samples of %d rows (%s: %d samples of %d)", g[0], g[5], g[6], g[3], g[4],
-                   e->B, e->Li, cfg ? "guided" : "unguided", cfg ? 2 * S : S, g[3] * g[4]);
-    FLUXMI_REQUIRE(e->Lpred == e->Li && c_out(e) == e->d.in_channels, "engine_denoise_windows: %d reference rows, %d input and %d predicted "
-                   "channels: a windowed call steps the whole stream (no Kontext reference, no Fill / Depth / Canny model)", e->Li - e->Lpred,
-                   e->d.in_channels, c_out(e));
-    FLUXMI_REQUIRE(!e->inp_on, "engine_denoise_windows: an inpainting state is set (windows are not combined with a mask)");
-    FLUXMI_REQUIRE(!e->sol_on, "engine_denoise_windows: a solver program is set (the windowed update is its own: sampler euler only)");
-    FLUXMI_REQUIRE(!(e->fb_threshold > 0.f), "engine_denoise_windows: step caching is on (not combined with windows)");
-    FLUXMI_REQUIRE(!e->masked, "engine_denoise_windows: an attention-group table is set (regional prompts do not combine with windows)");
-    FLUXMI_REQUIRE(!e->cn, "engine_denoise_windows: a ControlNet is attached (not combined with windows)");
-    FLUXMI_REQUIRE(!e->ip_on, "engine_denoise_windows: an IP-Adapter is set (not combined with windows)");
-    FLUXMI_REQUIRE(!e->fe_on, "engine_denoise_windows: a FlowEdit state is set (not combined with windows)");
-    FLUXMI_REQUIRE(!(cfg && e->gd_on), "engine_denoise_windows: guidance shaping is set (a guided windowed call is unshaped)");
-    FLUXMI_REQUIRE(!(e->pv_hook && e->pv_every > 0), "engine_denoise_windows: previews (every = %d > 0) are refused: the stream holds windows, "
-                   "not the canvas (a hook with every = 0 reports progress and cancels)", e->pv_every);
-    e->win_call = true;
-  }
-  struct EditCallScope {  // fe_call and win_call speak of the running call only: off again on every way out
-    fluxmi_engine_t* e;
-    ~EditCallScope() { e->fe_call = e->win_call = false; }
-  } edit_scope{e};
-  Range whole("fluxmi_engine_denoise");
-  SplitkScope splitk(e);
-  FLUXMI_TRY(ensure_pairs(e, s));
-  const int B = e->B, Li = e->Li, Lt = e->Lt, C = e->d.in_channels;
-  // the Euler update: the whole stream, or (Kontext) the leading Lpred rows of each sample -- the reference rows never move -- or (Fill /
-  // Depth / Canny) the leading C_out channels of every row -- the conditioning channels never move (no row split then: prepare_cond)
-  // With an inpainting state set (fluxmi_engine_set_inpaint) the ONE blend kernel replaces whichever of them it would have been.
-  FLUXMI_REQUIRE(!e->inp_on || e->inp_B == (cfg ? B / 2 : B), "engine_denoise: the inpainting state holds %d images, this call steps %d "
-                 "(fluxmi_engine_set_inpaint takes the caller's images: the prepared batch, half of it for a guided call)", e->inp_B, cfg ? B / 2 : B);
-  FLUXMI_REQUIRE(!e->inp_on || !e->inp_diff || (int)e->inp_thr.size() == n_steps, "engine_denoise: %d differential thresholds for a call of %d "
-                 "steps (fluxmi_engine_set_inpaint takes one per step)", (int)e->inp_thr.size(), n_steps);
-  // With a solver program set (fluxmi_engine_set_solver) the ONE table-driven update replaces all of them, the blend included: a step is
-  // then one evaluation, and the d_dts table goes unused.
-  FLUXMI_REQUIRE(!e->sol_on || e->sol_n == n_steps, "engine_denoise: the solver program holds %d evaluations, this call runs %d "
-                 "(fluxmi_engine_set_solver takes one row per step of the call)", e->sol_n, n_steps);
-  FLUXMI_REQUIRE(!e->sol_on || !(e->fb_threshold > 0.f), "engine_denoise: a solver program does not combine with step caching (the cache "
-                 "compares consecutive evaluations; a solver may evaluate one time twice)");
-  // A stochastic program (a non-zero cn in column 7) needs its ids (fluxmi_engine_set_solver_noise); the update is then the kernel's noise form
-  bool sol_cn = false;
-  for (int i = 0; e->sol_on && i < n_steps; ++i) sol_cn = sol_cn || e->sol_coef[(size_t)8 * i + 7] != 0.f;
-  FLUXMI_REQUIRE(!sol_cn || e->sol_noise, "engine_denoise: the solver program has a non-zero noise coefficient and no ids are set "
-                 "(fluxmi_engine_set_solver_noise after fluxmi_engine_set_solver)");
-  const bool sol_noise = e->sol_on && e->sol_noise;
-  FLUXMI_REQUIRE(!sol_noise || e->sol_noise_B == (cfg ? B / 2 : B), "engine_denoise: the solver noise holds ids of %d images, this call steps %d "
-                 "(fluxmi_engine_set_solver_noise takes the caller's images: the prepared batch, half of it for a guided call)", e->sol_noise_B,
-                 cfg ? B / 2 : B);
-  if (e->sol_on) FLUXMI_TRY(ensure_sol(e, s));
-  if (sol_noise) FLUXMI_TRY(ensure_sol_ids(e));
-  // Guidance shaping (fluxmi_engine_set_guidance): moments and combine on pred_s in front of whichever guided update runs; both halves of
-  // pred_s then hold the shaped prediction v, and the update's own chain d = bf16(v - v) = 0, m = 0, p = v steps with v unchanged.
-  const bool shaped = cfg && e->gd_on;
-  if (shaped) FLUXMI_TRY(ensure_gd(e, s));
-  // Progress / previews / cancellation (fluxmi_engine_set_preview): the preview launch goes in front of whichever update runs, behind the
-  // shaping -- both halves of pred_s then hold v, and the guided formula u + s (v - v) still gives v
-  const bool hooked = e->pv_hook != nullptr, previewed = hooked && e->pv_every > 0;
-  FLUXMI_REQUIRE(!hooked || !e->amax_hook, "engine_denoise: a step hook and an amax-exchange hook are both set (previews, progress and "
-                 "cancellation are refused under a process group: the host waits would stall its collectives)");
-  FLUXMI_REQUIRE(!previewed || ((long long)e->pv_h * e->pv_w == e->Lpred && c_out(e) == 64), "engine_denoise: the preview state's token grid "
-                 "%d x %d does not cover the %d stepped rows of the prepared shape (or C_out = %d != 64)", e->pv_h, e->pv_w, e->Lpred, c_out(e));
-  if (previewed) FLUXMI_TRY(ensure_pv(e, s));
-  e->pv_launched = e->pv_delivered = 0;
-  e->pv_cancelled = false;
-  e->pv_images = win ? e->win_geo[0] : (cfg || edit ? B / 2 : B);
-  auto euler = [&](hipStream_t st) -> int {
-    if (win) {
-      const int* g = e->win_geo;
-      const char* tab = buf<char>(e, "win_tab");
-      return fluxmi_k_window_step(buf<u16>(e, "win_x"), buf<u16>(e, "img_s"), buf<u16>(e, "pred_s"), e->d_dts, e->d_step,
-                                  cfg ? e->d_cfg : nullptr, (const int*)(tab + e->win_off[0]), (const int*)(tab + e->win_off[1]),
-                                  (const float*)(tab + e->win_off[2]), (const float*)(tab + e->win_off[3]), g[0], g[1], g[2], g[3], g[4], g[5],
-                                  g[6], C, st);
-    }
-    if (edit) {
-      const char* tab = buf<char>(e, "fe_tab");
-      return fluxmi_k_flowedit_step(buf<u16>(e, "img_s"), buf<u16>(e, "pred_s"), buf<u16>(e, "fe_z"), buf<float>(e, "fe_acc"),
-                                    buf<u16>(e, "fe_x0"), (const float*)tab, (const int*)(tab + (size_t)MAX_STEPS * 16), e->d_step,
-                                    (const unsigned*)(tab + (size_t)MAX_STEPS * 24),
-                                    (const int*)(tab + (size_t)MAX_STEPS * 24 + (size_t)FLUXMI_ENGINE_MAX_BATCH * 16), B / 2, Li, e->Lpred, C,
-                                    c_out(e), st);
-    }
-    if (shaped) {
-      const long long n_pred = (long long)e->Lpred * c_out(e);
-      float* gp = buf<float>(e, "gd_params");
-      FLUXMI_TRY(fluxmi_k_guidance_moments(buf<u16>(e, "pred_s"), buf<float>(e, "gd_r"), buf<float>(e, "gd_part"), B / 2, n_pred, st));
-      FLUXMI_TRY(fluxmi_k_guidance_combine(buf<u16>(e, "pred_s"), buf<float>(e, "gd_r"), buf<float>(e, "gd_part"), gp, e->d_step,
-                                           (const int*)(gp + 8), buf<float>(e, "gd_coef"), B / 2, n_pred, st));
-    }
-    if (previewed)
-      FLUXMI_TRY(fluxmi_k_latent_preview(buf<u16>(e, "img_s"), buf<u16>(e, "pred_s"), e->d_ts, e->d_step, cfg ? e->d_cfg : nullptr,
-                                         buf<float>(e, "pv_proj"), buf<int>(e, "pv_ctl"), buf<unsigned char>(e, "pv_out"), cfg ? B / 2 : B, Li,
-                                         e->Lpred, C, c_out(e), e->pv_h, e->pv_w, st));
-    if (sol_noise)
-      return fluxmi_k_solver_step_noise(buf<u16>(e, "img_s"), buf<u16>(e, "pred_s"), buf<u16>(e, "sol_xs"), buf<float>(e, "sol_hist"),
-                                        e->d_sol_coef, e->d_sol_ctl, e->inp_on ? buf<u16>(e, "inp_x0") : nullptr,
-                                        e->inp_on ? buf<u16>(e, "inp_noise") : nullptr, e->inp_on ? buf<u16>(e, "inp_mask") : nullptr, e->d_tnext,
-                                        e->d_omt, e->inp_on && e->inp_diff ? e->d_thr : nullptr, e->d_step, cfg ? e->d_cfg : nullptr,
-                                        cfg ? B / 2 : B, Li, e->Lpred, C, c_out(e), e->d_sol_ids, (const int*)(e->d_sol_ids + 4 * (size_t)e->B), st);
-    if (e->sol_on)
-      return fluxmi_k_solver_step(buf<u16>(e, "img_s"), buf<u16>(e, "pred_s"), buf<u16>(e, "sol_xs"), buf<float>(e, "sol_hist"), e->d_sol_coef,
-                                  e->d_sol_ctl, e->inp_on ? buf<u16>(e, "inp_x0") : nullptr, e->inp_on ? buf<u16>(e, "inp_noise") : nullptr,
-                                  e->inp_on ? buf<u16>(e, "inp_mask") : nullptr, e->d_tnext, e->d_omt, e->inp_on && e->inp_diff ? e->d_thr : nullptr,
-                                  e->d_step, cfg ? e->d_cfg : nullptr, cfg ? B / 2 : B, Li, e->Lpred, C, c_out(e), st);
-    if (e->inp_on)
-      return fluxmi_k_blend_euler(buf<u16>(e, "img_s"), buf<u16>(e, "pred_s"), buf<u16>(e, "inp_x0"), buf<u16>(e, "inp_noise"),
-                                  buf<u16>(e, "inp_mask"), e->d_dts, e->d_tnext, e->d_omt, e->inp_diff ? e->d_thr : nullptr, e->d_step,
-                                  cfg ? e->d_cfg : nullptr, cfg ? B / 2 : B, Li, e->Lpred, C, c_out(e), st);
-    if (cfg)
-      return fluxmi_k_cfg_euler(buf<u16>(e, "img_s"), buf<u16>(e, "pred_s"), e->d_dts, e->d_step, e->d_cfg, B / 2, Li, e->Lpred, C, c_out(e), st);
-    if (c_out(e) != C)
-      return fluxmi_k_euler_cols(buf<u16>(e, "img_s"), buf<u16>(e, "pred_s"), e->d_dts, e->d_step, (long long)B * Li, C, c_out(e), st);
-    if (e->Lpred == Li) return fluxmi_k_euler(buf<u16>(e, "img_s"), buf<u16>(e, "pred_s"), e->d_dts, e->d_step, (long long)B * Li * C, st);
-    return fluxmi_k_euler_rows(buf<u16>(e, "img_s"), buf<u16>(e, "pred_s"), e->d_dts, e->d_step, B, Li, e->Lpred, C, st);
-  };
-  const bool main_f8 = any_f8(e);
-  if (e->ip_on) FLUXMI_TRY(ip_usable(e));
-  // the attached ControlNet: its own scratch / weight copies, the request's schedule and step counter shared with the main engine
-  fluxmi_engine_t* const cn = e->cn;
-  if (cn) {
-    FLUXMI_TRY(cn_usable(e));
-    FLUXMI_REQUIRE(e->cn_batch == (cfg ? e->B / 2 : e->B), "engine_denoise: the attached ControlNet's cond holds %d images, this call steps %d",
-                   e->cn_batch, cfg ? e->B / 2 : e->B);
-    FLUXMI_TRY(ensure_pairs(cn, s));
-  }
-  // for the length of this call the net reads the request's schedule and step counter from the main engine's constants; its own pointers
-  // are back on every way out
-  struct SharedSchedule {
-    fluxmi_engine_t* n;
-    float* ts;
-    int* step;
-    SharedSchedule(fluxmi_engine_t* n_, fluxmi_engine_t* m) : n(n_), ts(n_ ? n_->d_ts : nullptr), step(n_ ? n_->d_step : nullptr) {
-      if (n) { n->d_ts = m->d_ts; n->d_step = m->d_step; }
-    }
-    ~SharedSchedule() {
-      if (n) { n->d_ts = ts; n->d_step = step; }
-    }
-  } shared_schedule(cn, e);
-  const bool cn_f8 = cn && any_f8(cn);
-
-  // schedule -> device through the engine's pinned staging buffer.  The buffer may still be the source of the previous request's
-  // (long finished) copy: wait on that copy's event, never on the stream.
-  if (e->sched_pending) FLUXMI_CHECK_HIP(hipEventSynchronize(e->ev_sched));
-  float *h_ts = e->h_sched, *h_dts = e->h_sched + (MAX_STEPS + 1);
-  // (an edit call: timesteps_host holds the n_steps evaluation times and nothing behind them; the dts table goes unused)
-  for (int i = 0; i <= n_steps; ++i) h_ts[i] = edit && i == n_steps ? 0.f : (float)timesteps_host[i];
-  for (int i = 0; i < n_steps; ++i) h_dts[i] = edit ? 0.f : (float)(timesteps_host[i + 1] - timesteps_host[i]);
-  h_dts[n_steps] = 0.f;
-  FLUXMI_CHECK_HIP(hipMemcpyAsync(e->d_ts, h_ts, (n_steps + 1) * 4, hipMemcpyHostToDevice, s));
-  FLUXMI_CHECK_HIP(hipMemcpyAsync(e->d_dts, h_dts, (n_steps + 1) * 4, hipMemcpyHostToDevice, s));
-  if (e->inp_on) {  // the blend's tables: the NEXT time of every step and its complement (subtracted in double), the thresholds
-    float *h_tn = e->h_sched + 2 * (MAX_STEPS + 1), *h_om = e->h_sched + 3 * (MAX_STEPS + 1), *h_th = e->h_sched + 4 * (MAX_STEPS + 1);
-    for (int i = 0; i < n_steps; ++i) {
-      h_tn[i] = (float)timesteps_host[i + 1];
-      h_om[i] = (float)(1.0 - timesteps_host[i + 1]);
-      h_th[i] = e->inp_diff ? (float)e->inp_thr[i] : 0.f;
-    }
-    h_tn[n_steps] = h_om[n_steps] = h_th[n_steps] = 0.f;
-    FLUXMI_CHECK_HIP(hipMemcpyAsync(e->d_tnext, h_tn, (n_steps + 1) * 4, hipMemcpyHostToDevice, s));
-    FLUXMI_CHECK_HIP(hipMemcpyAsync(e->d_omt, h_om, (n_steps + 1) * 4, hipMemcpyHostToDevice, s));
-    if (e->inp_diff) FLUXMI_CHECK_HIP(hipMemcpyAsync(e->d_thr, h_th, (n_steps + 1) * 4, hipMemcpyHostToDevice, s));
-  }
-  if (e->sol_on && n_steps > 0) {  // the solver's tables, through the same staging buffer
-    float* h_co = e->h_sched + 5 * (MAX_STEPS + 1);
-    int* h_ct = (int*)(h_co + 8 * MAX_STEPS);
-    memcpy(h_co, e->sol_coef.data(), (size_t)n_steps * 8 * 4);
-    memcpy(h_ct, e->sol_ctl.data(), (size_t)n_steps * 4 * 4);
-    FLUXMI_CHECK_HIP(hipMemcpyAsync(e->d_sol_coef, h_co, (size_t)n_steps * 8 * 4, hipMemcpyHostToDevice, s));
-    FLUXMI_CHECK_HIP(hipMemcpyAsync(e->d_sol_ctl, h_ct, (size_t)n_steps * 4 * 4, hipMemcpyHostToDevice, s));
-  }
-  if (sol_noise) {  // ... and the noise ids with the evaluation offset behind them (one copy: the offset sits at [B][4] of "sol_ids")
-    unsigned* h_id = (unsigned*)(e->h_sched + 5 * (MAX_STEPS + 1) + 12 * MAX_STEPS);
-    memset(h_id, 0, (size_t)B * 16);
-    memcpy(h_id, e->sol_ids.data(), (size_t)e->sol_noise_B * 16);
-    h_id[4 * (size_t)B] = (unsigned)e->sol_eval_offset;
-    FLUXMI_CHECK_HIP(hipMemcpyAsync(e->d_sol_ids, h_id, (size_t)B * 16 + 4, hipMemcpyHostToDevice, s));
-  }
-  if (shaped) {  // ... and the shaping parameters with the step offset behind them; a new request's running difference starts at 0
-    float* h_gd = e->h_sched + 5 * (MAX_STEPS + 1) + 12 * MAX_STEPS + 4 * FLUXMI_ENGINE_MAX_BATCH + 1;
-    memcpy(h_gd, e->gd_params, 32);
-    memcpy(h_gd + 8, &e->gd_offset, 4);
-    FLUXMI_CHECK_HIP(hipMemcpyAsync(buf<float>(e, "gd_params"), h_gd, 36, hipMemcpyHostToDevice, s));
-    if (e->gd_zero_r) FLUXMI_CHECK_HIP(hipMemsetAsync(buf<float>(e, "gd_r"), 0, (size_t)(B / 2) * e->Lpred * c_out(e) * 4, s));
-    e->gd_zero_r = false;
-  }
-  if (previewed) {  // ... and the projection with the control word {every, eval_offset} behind it (one copy: "pv_ctl" follows "pv_proj" at +256)
-    float* h_pv = e->h_sched + 5 * (MAX_STEPS + 1) + 12 * MAX_STEPS + 4 * FLUXMI_ENGINE_MAX_BATCH + 1 + 9;
-    memcpy(h_pv, e->pv_proj, 51 * 4);
-    const int ctl[2] = {e->pv_every, e->pv_offset};
-    memcpy(h_pv + 51, ctl, 8);
-    FLUXMI_CHECK_HIP(hipMemcpyAsync(buf<float>(e, "pv_proj"), h_pv, 51 * 4, hipMemcpyHostToDevice, s));
-    FLUXMI_CHECK_HIP(hipMemcpyAsync(buf<int>(e, "pv_ctl"), h_pv + 51, 8, hipMemcpyHostToDevice, s));
-  }
-  if (edit) {  // ... and FlowEdit's tables, ids and offset: behind every earlier region of the staging buffer, one copy each into "fe_tab"
-    float* h_fe = e->h_sched + 5 * (MAX_STEPS + 1) + 12 * MAX_STEPS + 4 * FLUXMI_ENGINE_MAX_BATCH + 1 + 9 + 53;
-    int* h_ct = (int*)(h_fe + 4 * MAX_STEPS);
-    unsigned* h_id = (unsigned*)(h_fe + 6 * MAX_STEPS);
-    char* tab = buf<char>(e, "fe_tab");
-    memcpy(h_fe, e->fe_coef.data(), (size_t)n_steps * 16);
-    memcpy(h_ct, e->fe_ctl.data(), (size_t)n_steps * 8);
-    memset(h_id, 0, (size_t)FLUXMI_ENGINE_MAX_BATCH * 16);
-    memcpy(h_id, e->fe_ids.data(), (size_t)e->fe_B * 16);
-    h_id[4 * FLUXMI_ENGINE_MAX_BATCH] = (unsigned)e->fe_eval_offset;
-    if (n_steps > 0) {
-      FLUXMI_CHECK_HIP(hipMemcpyAsync(tab, h_fe, (size_t)n_steps * 16, hipMemcpyHostToDevice, s));
-      FLUXMI_CHECK_HIP(hipMemcpyAsync(tab + (size_t)MAX_STEPS * 16, h_ct, (size_t)n_steps * 8, hipMemcpyHostToDevice, s));
-    }
-    FLUXMI_CHECK_HIP(hipMemcpyAsync(tab + (size_t)MAX_STEPS * 24, h_id, (size_t)FLUXMI_ENGINE_MAX_BATCH * 16 + 4, hipMemcpyHostToDevice, s));
-  }
-  FLUXMI_CHECK_HIP(hipEventRecord(e->ev_sched, s));
-  e->sched_pending = true;
-  u16 *gvec = buf<u16>(e, "gvec"), *tvec = buf<u16>(e, "tvec");
-  if (edit) {  // a distilled-guidance value per branch: the source half, then the target half
-    FLUXMI_TRY(fluxmi_k_fill_bf16(gvec, e->fe_gs, B / 2, s));
-    FLUXMI_TRY(fluxmi_k_fill_bf16(gvec + B / 2, e->fe_gt, B / 2, s));
-  } else {
-    FLUXMI_TRY(fluxmi_k_fill_bf16(gvec, guidance, B, s));  // guidance arrives in the flow dtype (flux_pipeline.py:619-623)
-  }
-  FLUXMI_CHECK_HIP(hipMemsetAsync(e->d_step, 0, 4, s));
-  u16 *img_s = buf<u16>(e, "img_s"), *txt_s = buf<u16>(e, "txt_s"), *y_s = buf<u16>(e, "y_s"), *pred_s = buf<u16>(e, "pred_s");
-  const long long n_img = win ? (long long)e->win_geo[0] * e->win_geo[1] * e->win_geo[2] * C  // (a windowed call: the caller's canvas)
-                              : (long long)(cfg || edit ? B / 2 : B) * Li * C;                 // the caller's samples
-  if (win) {  // the caller's canvas goes beside the stream; one gather fills every window of it (guided: both halves)
-    const int* g = e->win_geo;
-    const char* tab = buf<char>(e, "win_tab");
-    u16* wx = buf<u16>(e, "win_x");
-    FLUXMI_CHECK_HIP(hipMemcpyAsync(wx, img, n_img * 2, hipMemcpyDeviceToDevice, s));
-    FLUXMI_TRY(fluxmi_k_window_gather(wx, img_s, (const int*)(tab + e->win_off[0]), (const int*)(tab + e->win_off[1]), g[0], g[1], g[2], g[3],
-                                      g[4], g[5], g[6], C, cfg ? 1 : 0, s));
-  } else if (edit) {  // the caller's edit state goes beside the stream; the first coupling, at the first evaluation's time, fills both halves of it
-    u16* fz = buf<u16>(e, "fe_z");
-    FLUXMI_CHECK_HIP(hipMemcpyAsync(fz, img, n_img * 2, hipMemcpyDeviceToDevice, s));
-    if (n_steps > 0)
-      FLUXMI_TRY(fluxmi_k_flowedit_couple(img_s, fz, buf<u16>(e, "fe_x0"), (float)timesteps_host[0], (float)(1.0 - timesteps_host[0]),
-                                          (const unsigned*)(buf<char>(e, "fe_tab") + (size_t)MAX_STEPS * 24), (unsigned)e->fe_eval_offset, B / 2, Li,
-                                          e->Lpred, C, c_out(e), s));
-  } else {
-    FLUXMI_CHECK_HIP(hipMemcpyAsync(img_s, img, n_img * 2, hipMemcpyDeviceToDevice, s));
-  }
-  if (cfg) {
-    if (!win) FLUXMI_CHECK_HIP(hipMemcpyAsync(img_s + n_img, img, n_img * 2, hipMemcpyDeviceToDevice, s));
-    unsigned bits;
-    memcpy(&bits, &cfg_scale, 4);
-    FLUXMI_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)e->d_cfg, (int)bits, 1, s));
-  }
-  FLUXMI_CHECK_HIP(hipMemcpyAsync(txt_s, txt, (size_t)B * Lt * e->d.ctx_in * 2, hipMemcpyDeviceToDevice, s));
-  FLUXMI_CHECK_HIP(hipMemcpyAsync(y_s, y, (size_t)B * e->d.vec_in * 2, hipMemcpyDeviceToDevice, s));
-
-  int trial = *trial_index_inout;
-  int step = 0;
-  const u16* g_arg = e->d.guidance_embed ? gvec : nullptr;
-  // -- calibrating steps: the reference's first num_trials+1 calls of every F8Linear ----------------------
-  {
-    Range r("calibrating steps (unfused)");
-    // (with a ControlNet attached: while EITHER net has trials left -- that net in mode 0, the other in its frozen mode, eagerly)
-    auto main_cal = [&]() { return main_f8 && trial <= e->d.num_trials; };
-    auto cn_cal = [&]() { return cn_f8 && cn->cn_trial <= cn->d.num_trials; };
-    auto cal_step = [&]() -> int {
-      FLUXMI_TRY(fluxmi_k_set_timestep(tvec, e->d_ts, e->d_step, B, s));
-      if (cn) {
-        const int nmode = cn_cal() ? 0 : (all_block_linears_f8(cn) ? 1 : 2);
-        if (nmode == 0) cn->qlut_valid = false;
-        if (nmode == 1) FLUXMI_TRY(build_qluts(cn, s));
-        FLUXMI_TRY(cn_forward(e, img_s, txt_s, y_s, tvec, gvec, nmode, cn->cn_trial, false, s));
-        if (nmode == 0) ++cn->cn_trial;
-      }
-      const int mmode = main_cal() ? 0 : (all_block_linears_f8(e) ? 1 : 2);
-      if (mmode == 0) e->qlut_valid = false;
-      if (mmode == 1) FLUXMI_TRY(build_qluts(e, s));
-      FLUXMI_TRY(forward_impl(e, img_s, txt_s, y_s, tvec, g_arg, pred_s, mmode, trial, false, s));
-      FLUXMI_TRY(euler(s));
-      FLUXMI_TRY(fluxmi_k_advance_step(e->d_step, s));
-      if (mmode == 0) ++trial;
-      ++step;
-      return 0;
-    };
-    while (step < n_steps && (main_cal() || cn_cal())) {
-      const int rc = pv_eval(e, s, cal_step);
-      if (rc == FLUXMI_CANCELLED && e->pv_cancelled) break;
-      FLUXMI_TRY(rc);
-    }
-  }
-  // -- frozen steps -------------------------------------------------------------------------------------------
-  e->timed_steps = 0;
-  e->fb_log_ratio.clear();
-  e->fb_log_hit.clear();
-  if (step < n_steps && !e->pv_cancelled) {
-    const int mode = all_block_linears_f8(e) ? 1 : 2;  // any bf16 block linear -> the fused path is unavailable, run unfused-frozen
-    if (mode == 1) {
-      FLUXMI_TRY(embed_txt(e, txt_s, false, 0, buf<u16>(e, "txt_emb"), (long long)Lt * e->d.hidden, s));
-      e->txt_emb_valid = true;
-      FLUXMI_TRY(build_qluts(e, s));
-    }
-    if (cn && all_block_linears_f8(cn)) {  // the net's embedded text (behind its mode row) and quantising tables, once per request
-      scope_set(cn);
-      u16* te = buf<u16>(cn, "txt_emb");
-      int rc = embed_txt(cn, txt_s, false, 0, te, (long long)cn->Lt * cn->d.hidden, s);
-      if (!rc) rc = put_mode_row(cn, te, (long long)cn->Lt * cn->d.hidden, s);
-      if (!rc) rc = build_qluts(cn, s);
-      scope_set(e);
-      FLUXMI_TRY(rc);
-      cn->txt_emb_valid = true;
-    }
-    // plain, or with first-block step caching: the same steps cut into head / body / skip pieces with a host decision in between
-    int first_timed = n_steps;  // the first step behind ev_t0, which the loop records: ev_t0 .. ev_t1 brackets steps [first_timed, n_steps)
-    const int rc = (e->fb_threshold > 0.f ? cached_steps : plain_steps)(e, mode, cfg, step, n_steps, g_arg, use_graph, euler, &first_timed, s);
-    if (!(rc == FLUXMI_CANCELLED && e->pv_cancelled)) FLUXMI_TRY(rc);
-    FLUXMI_CHECK_HIP(hipEventRecord(e->ev_t1, s));
-    e->timed_steps = e->pv_cancelled ? std::max(0, e->pv_launched - first_timed) : n_steps - first_timed;
-  }
-  // a hooked call drains: the evaluations still in flight are waited for and delivered, so the call is synchronous.  A cancelled one delivers
-  // nothing further and waits for what it launched
-  while (hooked && !e->pv_cancelled && e->pv_delivered < e->pv_launched) FLUXMI_TRY(pv_deliver(e, e->pv_delivered));
-  if (e->pv_cancelled && e->pv_launched > 0)
-    FLUXMI_CHECK_HIP(hipEventSynchronize(e->pv_ev[(e->pv_launched - 1) % (FLUXMI_PREVIEW_DEPTH + 1)]));
-  FLUXMI_CHECK_HIP(hipMemcpyAsync(img, win ? buf<u16>(e, "win_x") : (edit ? buf<u16>(e, "fe_z") : img_s), n_img * 2, hipMemcpyDeviceToDevice, s));
-  *trial_index_inout = trial;
-  if (e->pv_cancelled) {
-    fluxmi_set_error("engine_denoise: cancelled by the step hook after %d of %d evaluations", e->pv_launched, n_steps);
-    return FLUXMI_CANCELLED;
-  }
-  return 0;
-}
-
-int fluxmi_engine_denoise(fluxmi_engine_t* e, void* img, const void* txt, const void* y, float guidance,
-                          const double* timesteps_host, int n_steps, int* trial_index_inout, int use_graph, void* stream) {
-  return denoise_impl(e, img, txt, y, guidance, false, 1.f, timesteps_host, n_steps, trial_index_inout, use_graph, stream);
-}
-
-int fluxmi_engine_denoise_cfg(fluxmi_engine_t* e, void* img, const void* txt, const void* y, float guidance, float cfg_scale,
-                              const double* timesteps_host, int n_steps, int* trial_index_inout, int use_graph, void* stream) {
-  return denoise_impl(e, img, txt, y, guidance, true, cfg_scale, timesteps_host, n_steps, trial_index_inout, use_graph, stream);
-}
-
-int fluxmi_engine_denoise_edit(fluxmi_engine_t* e, void* z, const void* txt, const void* y, const double* timesteps_host, int n_evals,
-                               int* trial_index_inout, int use_graph, void* stream) {
-  return denoise_impl(e, z, txt, y, 0.f, false, 1.f, timesteps_host, n_evals, trial_index_inout, use_graph, stream, true);
-}
-
-int fluxmi_engine_denoise_windows(fluxmi_engine_t* e, void* canvas, const void* txt, const void* y, float guidance, int guided, float cfg_scale,
-                                  const double* timesteps_host, int n_steps, int* trial_index_inout, int use_graph, void* stream) {
-  return denoise_impl(e, canvas, txt, y, guidance, guided != 0, cfg_scale, timesteps_host, n_steps, trial_index_inout, use_graph, stream, false,
-                      true);
-}
-
-// The window state of the following windowed calls (fluxmi.h): the geometry, and the four host tables copied into the engine's own buffer
-// on `stream` (the call returns behind one stream synchronisation: the host tables are the caller's).
-int fluxmi_engine_set_windows(fluxmi_engine_t* e, int n_images, int Hc, int Wc, int h, int w, int ny, int nx, const int* row0_host,
-                              const int* col0_host, const float* Ny_host, const float* Nx_host, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  FLUXMI_REQUIRE(e, "engine_set_windows: NULL engine");
-  if (!row0_host) {
-    e->win_on = false;
-    return 0;
-  }
-  FLUXMI_REQUIRE(!e->is_cn, "engine_set_windows: a ControlNet engine steps nothing (set the state on the main engine)");
-  FLUXMI_REQUIRE(e->ws, "engine_set_windows: call fluxmi_engine_prepare first (the state belongs to the prepared shape)");
-  FLUXMI_REQUIRE(col0_host && Ny_host && Nx_host, "engine_set_windows: row0_host, col0_host, Ny_host and Nx_host go together");
-  FLUXMI_REQUIRE(n_images >= 1 && Hc >= 1 && Wc >= 1 && h >= 1 && w >= 1 && ny >= 1 && nx >= 1 && h <= Hc && w <= Wc,
-                 "engine_set_windows: bad geometry: %d images, canvas %d x %d, windows %d x %d on a %d x %d grid", n_images, Hc, Wc, h, w, ny, nx);
-  FLUXMI_REQUIRE((long long)n_images * ny * nx <= FLUXMI_ENGINE_MAX_BATCH && (long long)n_images * ny * nx <= e->B,
-                 "engine_set_windows: %d images x %d x %d windows do not fit the prepared batch of %d samples (one pass: at most %d, half of it "
-                 "for a guided call)", n_images, ny, nx, e->B, FLUXMI_ENGINE_MAX_BATCH);
-  FLUXMI_REQUIRE(h * w == e->Li, "engine_set_windows: a window of %d x %d tokens is not the prepared shape's %d image rows", h, w, e->Li);
-  FLUXMI_REQUIRE((double)n_images * Hc * Wc * (c_out(e) / 8) <= 2147483647.0, "engine_set_windows: the canvas exceeds the kernel's 32-bit index");
-  FLUXMI_TRY(fluxmi_window_check_tables("engine_set_windows", row0_host, col0_host, Hc, Wc, h, w, ny, nx));
-  for (long long i = 0; i < (long long)ny * Hc; ++i)
-    FLUXMI_REQUIRE(std::isfinite(Ny_host[i]), "engine_set_windows: Ny[%lld][%lld] is not finite", i / Hc, i % Hc);
-  for (long long i = 0; i < (long long)nx * Wc; ++i)
-    FLUXMI_REQUIRE(std::isfinite(Nx_host[i]), "engine_set_windows: Nx[%lld][%lld] is not finite", i / Wc, i % Wc);
-  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t x_bytes = (size_t)n_images * Hc * Wc * c_out(e) * 2;
-  const size_t sz[4] = {(size_t)ny * 4, (size_t)nx * 4, (size_t)ny * Hc * 4, (size_t)nx * Wc * 4};
-  size_t off[4], tab_bytes = 0;
-  for (int i = 0; i < 4; ++i) { off[i] = tab_bytes; tab_bytes += up(sz[i]); }
-  const size_t total = up(x_bytes) + tab_bytes;
-  if (e->win_mem && e->win_bytes != total) {  // another geometry: pieces captured on the old canvas go stale by the key (graphs_stale)
-    FLUXMI_CHECK_HIP(hipStreamSynchronize(s));
-    hipFree(e->win_mem);
-    e->win_mem = nullptr;
-    e->win_bytes = 0;
-    e->win_on = false;
-  }
-  if (!e->win_mem) {
-    if (hipMalloc((void**)&e->win_mem, total) != hipSuccess) {
-      (void)hipGetLastError();
-      e->win_mem = nullptr;
-      fluxmi_set_error("engine_set_windows: hipMalloc(%zu bytes) failed (win_x)", total);
-      return 2;
-    }
-    e->win_bytes = total;
-    FLUXMI_CHECK_HIP(hipMemsetAsync(e->win_mem, 0, total, s));
-  }
-  e->bufs["win_x"] = Buf{e->win_mem, x_bytes};
-  e->bufs["win_tab"] = Buf{e->win_mem + up(x_bytes), tab_bytes};
-  char* tab = e->win_mem + up(x_bytes);
-  const void* src[4] = {row0_host, col0_host, Ny_host, Nx_host};
-  for (int i = 0; i < 4; ++i) FLUXMI_CHECK_HIP(hipMemcpyAsync(tab + off[i], src[i], sz[i], hipMemcpyHostToDevice, s));
-  FLUXMI_CHECK_HIP(hipStreamSynchronize(s));
-  const int geo[7] = {n_images, Hc, Wc, h, w, ny, nx};
-  memcpy(e->win_geo, geo, sizeof geo);
-  memcpy(e->win_off, off, sizeof off);
-  e->win_on = true;
-  return 0;
-}
-
-// The FlowEdit state of the following edit calls (fluxmi.h): host tables like the solver program's; x0 is copied into the engine's own buffer
-// on `stream`, in order with the denoise_edit call that follows on it.
-int fluxmi_engine_set_flow_edit(fluxmi_engine_t* e, const void* x0_dev, int batch, const double* coef_host, const int* ctl_host, int n,
-                                const unsigned* ids_host, int eval_offset, float source_guidance, float target_guidance, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  FLUXMI_REQUIRE(e, "engine_set_flow_edit: NULL engine");
-  if (!x0_dev) {
-    e->fe_on = false;
-    e->fe_n = 0;
-    e->fe_coef.clear();
-    e->fe_ctl.clear();
-    e->fe_ids.clear();
-    return 0;
-  }
-  FLUXMI_REQUIRE(!e->is_cn, "engine_set_flow_edit: a ControlNet engine steps nothing (set the state on the main engine)");
-  FLUXMI_REQUIRE(e->ws, "engine_set_flow_edit: call fluxmi_engine_prepare first (the state belongs to the prepared shape)");
-  FLUXMI_REQUIRE(coef_host && ctl_host && ids_host, "engine_set_flow_edit: x0, coef_host, ctl_host and ids_host go together");
-  FLUXMI_REQUIRE(n >= 0 && n <= MAX_STEPS, "engine_set_flow_edit: n=%d out of range (at most %d evaluations)", n, MAX_STEPS);
-  FLUXMI_REQUIRE(batch >= 1 && 2 * batch <= std::max(2, e->B), "engine_set_flow_edit: batch %d outside 1..%d (half the prepared batch: "
-                 "the source and the target branch of every image)", batch, std::max(1, e->B / 2));
-  FLUXMI_REQUIRE(eval_offset >= 0, "engine_set_flow_edit: eval_offset %d < 0", eval_offset);
-  FLUXMI_REQUIRE(std::isfinite(source_guidance) && std::isfinite(target_guidance), "engine_set_flow_edit: guidance values must be finite");
-  for (int i = 0; i < 4 * n; ++i)
-    FLUXMI_REQUIRE(std::isfinite((float)coef_host[i]), "engine_set_flow_edit: coefficient %d of row %d is not finite in fp32", i % 4, i / 4);
-  bool need_acc = false;
-  for (int i = 0; i < n; ++i) need_acc = need_acc || !ctl_host[2 * i] || !ctl_host[2 * i + 1];
-  FLUXMI_TRY(ensure_fe_x0(e, s));
-  FLUXMI_CHECK_HIP(hipMemcpyAsync(buf<void>(e, "fe_x0"), x0_dev, (size_t)batch * e->Lpred * c_out(e) * 2, hipMemcpyDeviceToDevice, s));
-  e->fe_coef.resize((size_t)4 * n);
-  for (int i = 0; i < 4 * n; ++i) e->fe_coef[i] = (float)coef_host[i];
-  e->fe_ctl.resize((size_t)2 * n);
-  for (int i = 0; i < 2 * n; ++i) e->fe_ctl[i] = ctl_host[i] != 0;
-  e->fe_ids.assign(ids_host, ids_host + 4 * (size_t)batch);
-  e->fe_B = batch;
-  e->fe_n = n;
-  e->fe_eval_offset = eval_offset;
-  e->fe_gs = source_guidance;
-  e->fe_gt = target_guidance;
-  e->fe_need_acc = need_acc;
-  e->fe_on = true;
-  return 0;
-}
-
-// Token-group attention mask of the prepared shape: `table` = [B, L] descriptors on the device (L = Lt + Li: text rows, then image rows, as
-// the joint sequence is laid out), copied into the engine's own buffer; NULL = dense.  Self-admission is checked here on a host copy (one
-// stream synchronisation per call, none per step).
-int fluxmi_engine_set_attn_groups(fluxmi_engine_t* e, const unsigned* table, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  FLUXMI_REQUIRE(e, "engine_set_attn_groups: NULL engine");
-  if (!table) {
-    e->masked = false;
-    return 0;
-  }
-  FLUXMI_REQUIRE(e->ws, "engine_set_attn_groups: call fluxmi_engine_prepare first (the table is [B, L] of the prepared shape)");
-  const size_t n = (size_t)e->B * e->L;
-  std::vector<unsigned> h(n);
-  FLUXMI_CHECK_HIP(hipMemcpyAsync(h.data(), table, n * 4, hipMemcpyDeviceToHost, s));
-  FLUXMI_CHECK_HIP(hipStreamSynchronize(s));
-  for (size_t i = 0; i < n; ++i) {
-    FLUXMI_REQUIRE((h[i] & 0xFFF0u) == 0, "engine_set_attn_groups: descriptor %zu = 0x%08x has bits 4-15 set", i, h[i]);
-    FLUXMI_REQUIRE((h[i] >> (16 + (h[i] & 15u))) & 1u, "engine_set_attn_groups: token %zu (sample %zu, row %zu) does not admit its own key group %u: "
-                   "its softmax row would be empty", i, i / e->L, i % e->L, h[i] & 15u);
-  }
-  FLUXMI_CHECK_HIP(hipMemcpyAsync(buf<unsigned>(e, "attn_groups"), table, n * 4, hipMemcpyDeviceToDevice, s));
-  e->masked = true;
-  return 0;
-}
-
-// Masked-latent inpainting state of the prepared shape (fluxmi.h): the caller's tensors are copied into the engine's own buffers on `stream`,
-// in order with the denoise call that follows on it.
-int fluxmi_engine_set_inpaint(fluxmi_engine_t* e, const void* x0, const void* noise, const void* mask, int batch, const double* thresholds_host,
-                              int n_thresholds, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  FLUXMI_REQUIRE(e, "engine_set_inpaint: NULL engine");
-  if (!x0) {
-    e->inp_on = e->inp_diff = false;
-    e->inp_thr.clear();
-    return 0;
-  }
-  FLUXMI_REQUIRE(e->ws, "engine_set_inpaint: call fluxmi_engine_prepare first (the tensors are [batch, Li, C_out] of the prepared shape)");
-  FLUXMI_REQUIRE(noise && mask, "engine_set_inpaint: x0, noise and mask go together");
-  FLUXMI_REQUIRE(batch >= 1 && batch <= e->B, "engine_set_inpaint: batch %d outside 1..%d (the prepared batch)", batch, e->B);
-  FLUXMI_REQUIRE(!thresholds_host ? n_thresholds == 0 : (n_thresholds >= 0 && n_thresholds <= MAX_STEPS),
-                 "engine_set_inpaint: n_thresholds %d (0 without a table, at most %d with one)", n_thresholds, MAX_STEPS);
-  for (int i = 0; i < n_thresholds; ++i)
-    FLUXMI_REQUIRE(thresholds_host[i] == thresholds_host[i], "engine_set_inpaint: threshold %d is NaN", i);
-  FLUXMI_TRY(ensure_inp(e));
-  const size_t bytes = (size_t)batch * e->Lpred * c_out(e) * 2;
-  FLUXMI_CHECK_HIP(hipMemcpyAsync(buf<void>(e, "inp_x0"), x0, bytes, hipMemcpyDeviceToDevice, s));
-  FLUXMI_CHECK_HIP(hipMemcpyAsync(buf<void>(e, "inp_noise"), noise, bytes, hipMemcpyDeviceToDevice, s));
-  FLUXMI_CHECK_HIP(hipMemcpyAsync(buf<void>(e, "inp_mask"), mask, bytes, hipMemcpyDeviceToDevice, s));
-  e->inp_on = true;
-  e->inp_diff = thresholds_host != nullptr;
-  e->inp_B = batch;
-  e->inp_thr.assign(thresholds_host, thresholds_host + (thresholds_host ? n_thresholds : 0));
-  return 0;
-}
-
-// The solver program of the following denoise calls (fluxmi.h): host tables only -- the buffers are made by the first denoise call that
-// needs them, the device copies travel with every call's schedule.
-int fluxmi_engine_set_solver(fluxmi_engine_t* e, const double* coef_host, const int* ctl_host, int n) {
-  FLUXMI_REQUIRE(e, "engine_set_solver: NULL engine");
-  if (!coef_host) {
-    e->sol_on = e->sol_noise = false;
-    e->sol_n = 0;
-    e->sol_coef.clear();
-    e->sol_ctl.clear();
-    e->sol_ids.clear();
-    return 0;
-  }
-  FLUXMI_REQUIRE(!e->is_cn, "engine_set_solver: a ControlNet engine steps nothing (set the solver on the main engine)");
-  FLUXMI_REQUIRE(e->ws, "engine_set_solver: call fluxmi_engine_prepare first (the program belongs to the prepared shape)");
-  FLUXMI_REQUIRE(ctl_host, "engine_set_solver: coef_host and ctl_host go together");
-  FLUXMI_REQUIRE(n >= 0 && n <= MAX_STEPS, "engine_set_solver: n=%d out of range (at most %d evaluations)", n, MAX_STEPS);
-  for (int i = 0; i < 8 * n; ++i)  // (checked as the device sees it: a finite double above FLT_MAX is inf in the fp32 table)
-    FLUXMI_REQUIRE(std::isfinite((float)coef_host[i]), "engine_set_solver: coefficient %d of row %d is not finite in fp32", i % 8, i / 8);
-  for (int i = 0; i < 4 * n; ++i)
-    FLUXMI_REQUIRE(i % 4 == 0 || (ctl_host[i] >= -1 && ctl_host[i] <= 1), "engine_set_solver: slot %d of row %d is %d (a slot is -1, 0 or 1)",
-                   i % 4, i / 4, ctl_host[i]);
-  e->sol_coef.resize((size_t)8 * n);
-  for (int i = 0; i < 8 * n; ++i) e->sol_coef[i] = (float)coef_host[i];
-  e->sol_ctl.assign(ctl_host, ctl_host + 4 * n);
-  e->sol_n = n;
-  e->sol_on = true;
-  e->sol_noise = false;  // a new program: its noise, if it has any, is set after it
-  e->sol_ids.clear();
-  return 0;
-}
-
-// The noise ids and evaluation offset of the program just set (fluxmi.h): host data only, like the program itself.
-int fluxmi_engine_set_solver_noise(fluxmi_engine_t* e, const unsigned* ids_host, int batch, int eval_offset) {
-  FLUXMI_REQUIRE(e && ids_host, "engine_set_solver_noise: NULL argument");
-  FLUXMI_REQUIRE(e->ws && e->sol_on, "engine_set_solver_noise: call fluxmi_engine_set_solver first (the noise belongs to its program)");
-  bool cn = false;
-  for (int i = 0; i < e->sol_n; ++i) cn = cn || e->sol_coef[(size_t)8 * i + 7] != 0.f;
-  FLUXMI_REQUIRE(cn, "engine_set_solver_noise: the solver program has no non-zero noise coefficient (column 7): it draws nothing");
-  FLUXMI_REQUIRE(batch >= 1 && batch <= e->B, "engine_set_solver_noise: batch %d outside 1..%d (the prepared batch)", batch, e->B);
-  FLUXMI_REQUIRE(eval_offset >= 0, "engine_set_solver_noise: eval_offset %d < 0", eval_offset);
-  e->sol_ids.assign(ids_host, ids_host + 4 * (size_t)batch);
-  e->sol_noise_B = batch;
-  e->sol_eval_offset = eval_offset;
-  e->sol_noise = true;
-  return 0;
-}
-
-// The guidance-shaping state of the following guided denoise calls (fluxmi.h): host data only, like the solver program.
-int fluxmi_engine_set_guidance(fluxmi_engine_t* e, const float* params_host, int step_offset) {
-  FLUXMI_REQUIRE(e, "engine_set_guidance: NULL engine");
-  if (!params_host) {
-    e->gd_on = e->gd_zero_r = false;
-    return 0;
-  }
-  FLUXMI_REQUIRE(!e->is_cn, "engine_set_guidance: a ControlNet engine steps nothing (set the shaping on the main engine)");
-  FLUXMI_REQUIRE(e->ws, "engine_set_guidance: call fluxmi_engine_prepare first (the state belongs to the prepared shape)");
-  for (int i = 0; i < 8; ++i) FLUXMI_REQUIRE(std::isfinite(params_host[i]), "engine_set_guidance: parameter %d is not finite", i);
-  const float phi = params_host[1], rho = params_host[3], mode = params_host[5], zi = params_host[6];
-  FLUXMI_REQUIRE(mode == 0.f || mode == 1.f || mode == 2.f, "engine_set_guidance: mode %g (0 = CFG, 1 = APG, 2 = CFG-Zero*)", (double)mode);
-  FLUXMI_REQUIRE(phi >= 0.f && phi <= 1.f, "engine_set_guidance: phi %g outside [0, 1] (the rescale blend)", (double)phi);
-  FLUXMI_REQUIRE(rho >= 0.f && zi >= 0.f, "engine_set_guidance: rho %g, zero_init %g must be >= 0 (0 = off)", (double)rho, (double)zi);
-  FLUXMI_REQUIRE(step_offset >= 0, "engine_set_guidance: step_offset %d < 0", step_offset);
-  memcpy(e->gd_params, params_host, 32);
-  e->gd_params[7] = 0.f;
-  e->gd_offset = step_offset;
-  e->gd_on = e->gd_zero_r = true;
-  return 0;
-}
-
-// The progress / preview / cancellation state of the following denoise calls (fluxmi.h): host data only, like the solver program; the pinned
-// delivery buffer, the private copy stream and the event ring are made here, never inside a denoise call.
-int fluxmi_engine_set_preview(fluxmi_engine_t* e, const float* proj51_host, int h, int w, int every, int eval_offset, int n_evaluations,
-                              fluxmi_step_hook_t hook, void* user) {
-  FLUXMI_REQUIRE(e, "engine_set_preview: NULL engine");
-  if (!hook) {
-    e->pv_hook = nullptr; e->pv_user = nullptr; e->pv_every = 0;
-    return 0;
-  }
-  FLUXMI_REQUIRE(!e->is_cn, "engine_set_preview: a ControlNet engine steps nothing (set the hook on the main engine)");
-  FLUXMI_REQUIRE(e->ws, "engine_set_preview: call fluxmi_engine_prepare first (the state belongs to the prepared shape)");
-  FLUXMI_REQUIRE(!e->amax_hook, "engine_set_preview: an amax-exchange hook is attached (previews, progress and cancellation are refused under a "
-                 "process group: the host waits would stall its collectives)");
-  FLUXMI_REQUIRE(every >= 0, "engine_set_preview: every %d < 0 (0 = progress and cancellation only)", every);
-  FLUXMI_REQUIRE(eval_offset >= 0 && n_evaluations >= 0, "engine_set_preview: eval_offset %d, n_evaluations %d must be >= 0", eval_offset, n_evaluations);
-  if (every > 0) {
-    FLUXMI_REQUIRE(proj51_host, "engine_set_preview: every > 0 needs the 51 projection floats");
-    for (int i = 0; i < 51; ++i) FLUXMI_REQUIRE(std::isfinite(proj51_host[i]), "engine_set_preview: projection value %d is not finite", i);
-    FLUXMI_REQUIRE(c_out(e) == 64, "engine_set_preview: the model predicts %d channels per token (a preview needs 16 latent channels x 4 sub-pixels)", c_out(e));
-    FLUXMI_REQUIRE(h >= 1 && w >= 1 && (long long)h * w == e->Lpred, "engine_set_preview: a token grid of %d x %d for the %d stepped rows of the "
-                   "prepared shape", h, w, e->Lpred);
-    const size_t need = (size_t)e->B * e->Lpred * 4 * 3;
-    if (e->pv_host_bytes < need) {
-      if (e->pv_host) { hipHostFree(e->pv_host); e->pv_host = nullptr; e->pv_host_bytes = 0; }
-      FLUXMI_CHECK_HIP(hipHostMalloc((void**)&e->pv_host, need, hipHostMallocDefault));
-      e->pv_host_bytes = need;
-    }
-    if (!e->pv_stream) FLUXMI_CHECK_HIP(hipStreamCreateWithFlags(&e->pv_stream, hipStreamNonBlocking));
-    memcpy(e->pv_proj, proj51_host, 51 * 4);
-  }
-  for (hipEvent_t& ev : e->pv_ev)
-    if (!ev) FLUXMI_CHECK_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-  e->pv_h = every > 0 ? h : 0;
-  e->pv_w = every > 0 ? w : 0;
-  e->pv_every = every;
-  e->pv_offset = eval_offset;
-  e->pv_n = n_evaluations;
-  e->pv_hook = hook;
-  e->pv_user = user;
-  return 0;
-}
-
-int fluxmi_engine_preview_stats(fluxmi_engine_t* e, long long* captures, int* evaluations_run) {
-  FLUXMI_REQUIRE(e && captures && evaluations_run, "engine_preview_stats: NULL argument");
-  *captures = e->captures;
-  *evaluations_run = e->pv_launched;
-  return 0;
 }
 
 // Attach a ControlNet to the prepared shape of `e` (fluxmi.h): prepares the net for that shape (its own workspace; the position ids come from
@@ -2744,72 +1331,6 @@ int fluxmi_engine_attach_controlnet(fluxmi_engine_t* e, fluxmi_engine_t* cn, con
 int fluxmi_controlnet_trial(fluxmi_engine_t* cn, int* trial_index) {
   FLUXMI_REQUIRE(cn && cn->is_cn && trial_index, "controlnet_trial: not a ControlNet engine / NULL argument");
   *trial_index = cn->cn_trial;
-  return 0;
-}
-
-// The IP-Adapter of the prepared shape (fluxmi.h): K / V are copied into the engine's own buffer on `stream`, in order with the forward /
-// denoise call that follows on it; the scales are staged behind them.
-int fluxmi_engine_set_ip_adapter(fluxmi_engine_t* e, const void* k_ip, const void* v_ip, int Nk, int batch, const float* scales_host, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  FLUXMI_REQUIRE(e, "engine_set_ip_adapter: NULL engine");
-  if (!k_ip) {
-    e->ip_on = false;
-    return 0;
-  }
-  FLUXMI_REQUIRE(!e->is_cn, "engine_set_ip_adapter: a ControlNet engine takes no IP-Adapter (set it on the main engine)");
-  FLUXMI_REQUIRE(e->ws, "engine_set_ip_adapter: call fluxmi_engine_prepare first (the adapter belongs to the prepared shape)");
-  FLUXMI_REQUIRE(v_ip && scales_host, "engine_set_ip_adapter: NULL v_ip / scales_host");
-  FLUXMI_REQUIRE(Nk >= 1 && Nk <= 64, "engine_set_ip_adapter: Nk = %d outside 1..64", Nk);
-  FLUXMI_REQUIRE(batch == e->B, "engine_set_ip_adapter: K / V for %d samples on a prepared batch of %d (a guided request carries both branches)",
-                 batch, e->B);
-  FLUXMI_REQUIRE(e->d.depth >= 1 && e->d.hidden == e->d.heads * 128, "engine_set_ip_adapter: the adapter needs double blocks and head_dim 128");
-  FLUXMI_REQUIRE(!e->masked, "engine_set_ip_adapter: a token-group attention table is set (regional prompts do not combine with an IP-Adapter)");
-  FLUXMI_REQUIRE(!(e->fb_threshold > 0.f), "engine_set_ip_adapter: step caching is on (it does not combine with an IP-Adapter)");
-  const size_t kv = (size_t)e->d.depth * batch * Nk * e->d.hidden * 2, sc = (size_t)batch * e->d.depth * 4, total = 2 * kv + sc;
-  if (!e->ip_mem || e->ip_bytes < total) {
-    e->ip_on = false;
-    if (e->ip_mem) {  // a captured graph may hold the old buffer: never free it under a replay in flight
-      FLUXMI_CHECK_HIP(hipDeviceSynchronize());
-      hipFree(e->ip_mem);
-      e->ip_mem = nullptr; e->ip_bytes = 0;
-    }
-    if (hipMalloc((void**)&e->ip_mem, total) != hipSuccess) {
-      (void)hipGetLastError();
-      e->ip_mem = nullptr;
-      fluxmi_set_error("engine_set_ip_adapter: hipMalloc(%zu bytes) failed", total);
-      return 2;
-    }
-    e->ip_bytes = total;
-    e->ip_gen = next_generation();
-  }
-  // the layout follows Nk (k | v | scales packed for THIS Nk): Nk is part of the graph key
-  FLUXMI_CHECK_HIP(hipMemcpyAsync(e->ip_mem, k_ip, kv, hipMemcpyDeviceToDevice, s));
-  FLUXMI_CHECK_HIP(hipMemcpyAsync(e->ip_mem + kv, v_ip, kv, hipMemcpyDeviceToDevice, s));
-  FLUXMI_CHECK_HIP(hipStreamSynchronize(s));  // (the previous staging copy, if any, has left ip_scales_h)
-  e->ip_scales_h.assign(scales_host, scales_host + (size_t)batch * e->d.depth);
-  FLUXMI_CHECK_HIP(hipMemcpyAsync(e->ip_mem + 2 * kv, e->ip_scales_h.data(), sc, hipMemcpyHostToDevice, s));
-  e->ip_nk = Nk;
-  e->ip_B = batch;
-  e->ip_on = true;
-  return 0;
-}
-
-int fluxmi_engine_set_step_cache(fluxmi_engine_t* e, float threshold, int max_consecutive_hits) {
-  FLUXMI_REQUIRE(e, "engine_set_step_cache: NULL engine");
-  FLUXMI_REQUIRE(threshold >= 0.f, "engine_set_step_cache: threshold %g must be >= 0 and not NaN (0 = off)", (double)threshold);
-  FLUXMI_REQUIRE(max_consecutive_hits >= 0, "engine_set_step_cache: max_consecutive_hits %d must be >= 0 (0 = unbounded)", max_consecutive_hits);
-  e->fb_threshold = threshold;
-  e->fb_max_hits = max_consecutive_hits;
-  return 0;
-}
-
-int fluxmi_engine_step_cache_log(fluxmi_engine_t* e, int* n, int* batch, float* ratios, unsigned char* hit, int cap) {
-  FLUXMI_REQUIRE(e && n && batch && cap >= 0 && (cap == 0 || (ratios && hit)), "engine_step_cache_log: bad arguments");
-  const int steps = (int)e->fb_log_hit.size(), m = std::min(steps, cap);
-  *n = steps;
-  *batch = steps ? e->fb_log_B : 0;
-  for (int i = 0; i < m; ++i) hit[i] = e->fb_log_hit[i];
-  for (long long i = 0; i < (long long)m * e->fb_log_B; ++i) ratios[i] = e->fb_log_ratio[i];
   return 0;
 }
 
@@ -2913,7 +1434,8 @@ int fluxmi_engine_copy_buffer(fluxmi_engine_t* e, const char* name, long long of
 
 int fluxmi_engine_workspace_bytes(fluxmi_engine_t* e, long long* bytes) {
   FLUXMI_REQUIRE(e && bytes, "engine_workspace_bytes: NULL argument");
-  *bytes = (long long)(e->ws_bytes + e->pairs_bytes + e->mods_all_bytes + e->fb_bytes + e->inp_bytes + e->sol_bytes + e->sol_ids_bytes + e->ip_bytes + e->gd_bytes + e->pv_bytes + e->fe_bytes + e->fe_zbytes + e->fe_accbytes + e->win_bytes);  // (+ the window canvas and tables) workspace + row-pair weight copies + modulation table + step cache + inpainting + solver buffers + noise ids + adapter + guidance shaping + preview ring + FlowEdit state
+  *bytes = (long long)(e->ws_bytes + e->pairs_bytes + e->mods_all_bytes);  // workspace + row-pair weight copies + modulation table ...
+  for (const SideBuf& sb : e->side) *bytes += (long long)sb.bytes;         // ... + every feature's side allocation
   return 0;
 }
 

@@ -9,7 +9,7 @@ img_in, txt_in, time_in, vector_in, guidance_in, pe_embedder), the BFL state-dic
 `Flux.forward(img, img_ids, txt, txt_ids, timesteps, y, guidance)` and the LoRA bookkeeping methods.
 
 Different by design: the modules hold weights only.  `Flux.forward` hands raw device pointers to the C++
-engine (csrc/engine.hip), which runs the whole step on hand-written gfx950 kernels -- fused and
+engine (csrc/engine.hip, csrc/engine_denoise.hip), which runs the whole step on hand-written gfx950 kernels -- fused and
 hipGraph-captured once every F8Linear input scale is frozen, unfused (reference op order) while the
 12-trial calibration of float8_quantize.py:220-246 is still running.
 """
@@ -167,7 +167,7 @@ class LastLayer(nn.Module):  # reference flux_model.py:488-503
 class Flux(nn.Module):
     """Transformer model for flow matching on sequences (reference flux_model.py:506-734)."""
 
-    MAX_ENGINE_BATCH = 32  # samples per engine pass (csrc/engine.hip FLUXMI_ENGINE_MAX_BATCH)
+    MAX_ENGINE_BATCH = 32  # samples per engine pass (csrc/engine_state.h FLUXMI_ENGINE_MAX_BATCH)
 
     def __init__(self, config: "ModelSpec", dtype: torch.dtype = torch.float16):
         super().__init__()

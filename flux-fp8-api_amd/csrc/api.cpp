@@ -188,6 +188,10 @@ int fluxmi_vision_attention(const void* q, const void* k, long long ld_qk, long 
                             void* stream) {
   return fluxmi_k_vision_attention(q, k, ld_qk, bs_qk, vt, ld_vt, bs_vt, out, ld_out, bs_out, v_bias, scale, head_dim, L, Lp, H, B, (hipStream_t)stream);
 }
+int fluxmi_vae_attention(const void* q, const void* k, long long ld_qk, long long bs_qk, const void* vt, long long ld_vt, long long bs_vt,
+                         void* out, long long ld_out, long long bs_out, const void* v_bias, int D, int P, int Pp, int B, void* stream) {
+  return fluxmi_k_vae_attention(q, k, ld_qk, bs_qk, vt, ld_vt, bs_vt, out, ld_out, bs_out, v_bias, D, P, Pp, B, (hipStream_t)stream);
+}
 int fluxmi_patchify(const void* pix, void* out, int B, int C, int H, int W, int patch, int grid, int Kp, void* stream) {
   return fluxmi_k_patchify(pix, out, B, C, H, W, patch, grid, Kp, (hipStream_t)stream);
 }

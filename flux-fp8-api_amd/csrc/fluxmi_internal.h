@@ -234,6 +234,8 @@ int fluxmi_k_row_norm(const void* x, const void* w, const void* b, void* y, int 
 int fluxmi_k_act_mul(const void* in, void* out, int rows, int F, long long ld_in, long long ld_out, int mode, hipStream_t s);
 int fluxmi_k_text_attention(const void* q, const void* k, long long ld_qk, const void* vt, long long ld_vt, void* out, long long ld_out,
                             const float* rel_bias, int bias_ld, const void* v_bias, float scale, int causal, int L, int Lp, int H, hipStream_t s);
+int fluxmi_k_vae_attention(const void* q, const void* k, long long ld_qk, long long bs_qk, const void* vt, long long ld_vt, long long bs_vt,
+                           void* out, long long ld_out, long long bs_out, const void* v_bias, int D, int P, int Pp, int B, hipStream_t s);
 int fluxmi_k_vision_attention(const void* q, const void* k, long long ld_qk, long long bs_qk, const void* vt, long long ld_vt, long long bs_vt,
                               void* out, long long ld_out, long long bs_out, const void* v_bias, float scale, int head_dim, int L, int Lp, int H,
                               int B, hipStream_t s);

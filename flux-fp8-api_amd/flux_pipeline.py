@@ -29,6 +29,7 @@ import torch
 import lora_loading  # noqa: F401  (same import side as the reference)
 from fluxmi import dist as fdist
 from fluxmi import solvers
+from modules.autoencoder import check_attention_mode
 from util import (ModelSpec, ModelVersion, engine_flow_dtype, into_device, into_dtype, load_config_from_path, load_controlnet, load_ip_adapter,
                   load_models_from_config)
 
@@ -161,6 +162,9 @@ class FluxPipeline:
         self.device_ae, self.device_clip, self.device_t5 = into_device(ae_device), into_device(clip_device), into_device(t5_device)
         self.dtype = into_dtype(dtype)
         self.clip, self.t5, self.model, self.ae = clip, t5, model, ae
+        self.vae_attention = check_attention_mode(getattr(config, "vae_attention", "gemm"))
+        if ae is not None:
+            ae.attention = self.vae_attention
         self.redux = redux  # FLUX.1 Redux image encoder (modules/image_embedders.ReduxImageEncoder) or None
         self.controlnet = controlnet  # FLUX ControlNet (modules/controlnet.FluxControlNet, config.controlnet_path) or None
         self.ip_adapter = ip_adapter  # FLUX IP-Adapter (modules/ip_adapter.IPAdapter, config.ip_adapter_path / clip_vision_path) or None
@@ -1215,6 +1219,11 @@ class FluxPipeline:
 
     # ---- tiled generation (fluxmi.windows; Flux.denoise_windows) -------------------------------------------------------------------------------
     VAE_MAX_LATENT_PIXELS = 46340  # the VAE's mid-block attention scores [P, P] bf16 behind a 32-bit GEMM descriptor: 2 P^2 bytes < 4 GiB
+    # vae_attention="streaming" has no score matrix.  What is left behind a 32-bit descriptor is the A operand of the 1x1-convolution GEMMs:
+    # the widest at full resolution is 64 P pixels x 256 channels x 2 bytes < 4 GiB, i.e. P < 131072 per image (DESIGN.md section 7;
+    # AutoEncoder decodes / encodes batches above that image by image)
+    VAE_MAX_LATENT_PIXELS_STREAMING = 131071
+    vae_attention = "gemm"  # the config's ModelSpec.vae_attention, carried to self.ae.attention by the constructor
 
     def _check_tiles(self, a: dict):
         """generate's arguments -> None (no tile_size, or one tile of the request's size and nothing else asked: today's request) or the
@@ -1298,10 +1307,17 @@ class FluxPipeline:
             raise no(f"num_images={n_img} at this size: {n_img} x {plan.ny} x {plan.nx} windows do not fit one engine pass of {cap} samples"
                      f"{' (half the pass: a negative prompt doubles them)' if guided else ''}; use a larger tile_size or a smaller tile_overlap")
         decodes = not (a["output_type"] == "latent" or self.ae is None)
-        if (decodes or a["init_image"] is not None) and (height // 8) * (width // 8) > self.VAE_MAX_LATENT_PIXELS:
+        if check_attention_mode(self.vae_attention) == "streaming":
+            if (decodes or a["init_image"] is not None) and (height // 8) * (width // 8) > self.VAE_MAX_LATENT_PIXELS_STREAMING:
+                raise no(f"{'init_image' if a['init_image'] is not None else 'a decoded output'} at {height} x {width}: the VAE's full-resolution "
+                         f"activations of the canvas's P = {(height // 8) * (width // 8)} latent pixels sit behind 32-bit GEMM descriptors "
+                         f"(P <= {self.VAE_MAX_LATENT_PIXELS_STREAMING} with vae_attention=\"streaming\"); a text-to-image request can return "
+                         f"output_type=\"latent\"")
+        elif (decodes or a["init_image"] is not None) and (height // 8) * (width // 8) > self.VAE_MAX_LATENT_PIXELS:
             raise no(f"{'init_image' if a['init_image'] is not None else 'a decoded output'} at {height} x {width}: the VAE's mid-block attention "
                      f"holds a [P, P] bf16 score matrix of the canvas's P = {(height // 8) * (width // 8)} latent pixels behind a 32-bit GEMM "
-                     f"descriptor (P <= {self.VAE_MAX_LATENT_PIXELS}); a text-to-image request can return output_type=\"latent\"")
+                     f"descriptor (P <= {self.VAE_MAX_LATENT_PIXELS}); the config's vae_attention=\"streaming\" has no such matrix, and a "
+                     f"text-to-image request can return output_type=\"latent\"")
         return plan
 
     def _generate_tiled(self, plan, prompt, width, height, num_steps, guidance, seed, init_image, strength, num_images, return_seed, jpeg_quality,

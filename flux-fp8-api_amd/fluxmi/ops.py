@@ -560,6 +560,42 @@ def vision_attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, L: int,
     return out
 
 
+def vae_attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, P: int, v_bias: Optional[torch.Tensor] = None,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """q, k [B, Pp, D] (views with the same strides, e.g. two column windows of one fused projection), vt [B, D, >= Pp] = V transposed ->
+    out [B, P, D] = softmax(q k^T / sqrt D) v + v_bias: the autoencoder's single-head mid-block attention in ONE launch with no [P, P]
+    matrix (fluxmi_vae_attention; include/fluxmi.h has the arithmetic).  D = 64 or 512; Pp = P rounded up to 64; rows >= P of q / k and
+    columns >= P of vt are padding no output depends on (finite values).  Only rows < P of `out` are written."""
+    _req(q, torch.bfloat16, "q")
+    _req(k, torch.bfloat16, "k")
+    _req(vt, torch.bfloat16, "vt")
+    if q.ndim != 3 or k.ndim != 3 or vt.ndim != 3:
+        raise ValueError("vae_attention: q, k [B, Pp, D] and vt [B, D, Pp] must be 3-d")
+    B, Pp, D = q.shape
+    P = int(P)
+    if q.stride() != k.stride() or q.stride(2) != 1 or vt.stride(2) != 1 or tuple(k.shape) != (B, Pp, D):
+        raise ValueError("vae_attention: q and k must share shape and strides; innermost strides must be 1")
+    if D not in (64, 512):
+        raise ValueError(f"vae_attention: head width D={D} must be 64 or 512")
+    if P < 1 or Pp % 64 or Pp < P:
+        raise ValueError(f"vae_attention: q / k must hold Pp rows, a multiple of 64 that is >= P (P={P}, Pp={Pp})")
+    if vt.shape[0] != B or vt.shape[1] != D or vt.shape[2] < Pp:
+        raise ValueError(f"vae_attention: vt must be [B, D, >= Pp] = [{B}, {D}, >= {Pp}], got {tuple(vt.shape)}")
+    if out is None:
+        out = torch.empty((B, P, D), dtype=torch.bfloat16, device=q.device)
+    else:
+        _req(out, torch.bfloat16, "out")
+        if out.ndim != 3 or out.shape[0] != B or out.shape[1] < P or out.shape[2] != D or out.stride(2) != 1:
+            raise ValueError(f"vae_attention: out must be [B, >= P, D] with innermost stride 1, got {tuple(out.shape)}")
+    if v_bias is not None:
+        _req(v_bias, torch.bfloat16, "v_bias")
+        if v_bias.numel() != D or not v_bias.is_contiguous():
+            raise ValueError(f"vae_attention: v_bias needs D = {D} contiguous entries")
+    call("fluxmi_vae_attention", _p(q), _p(k), q.stride(1), q.stride(0), _p(vt), vt.stride(1), vt.stride(0), _p(out), out.stride(1),
+         out.stride(0), _p(v_bias), D, P, Pp, B, _stream())
+    return out
+
+
 def patchify(pix: torch.Tensor, patch: int, grid: int, k_pad: int) -> torch.Tensor:
     """pix bf16 [B, C, H, W] -> patch rows [B*grid*grid, k_pad], column order (c, ky, kx), zero past C*patch*patch (fluxmi_patchify)."""
     _req(pix, torch.bfloat16, "pix")

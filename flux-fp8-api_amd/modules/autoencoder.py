@@ -12,6 +12,9 @@ run natively:
     (flux_pipeline.py:431-434): convolutions / SDPA in bf16, GroupNorm and the swish behind it in fp32;
   * the single 512-wide attention head of mid.attn_1: S = Q K^T (GEMM) -> fp32 row softmax (`fluxmi_softmax_rows`) -> P V (GEMM against
     V^T, which the v-projection GEMM produces directly by swapping its operands; v's bias is added after P V, rows of P sum to 1).
+    That is `AutoEncoder.attention = "gemm"`, the default.  `"streaming"` runs the same head as ONE launch of `fluxmi_vae_attention`
+    for all images (running row maximum over 64-key tiles, no [P, P] matrix; q and k come from one GEMM on concatenated weights): the
+    path for canvases whose score matrix does not fit a 32-bit descriptor (P > 46340), and 1 GiB less peak memory at 1024^2.
 
   * Downsample (encoder): the stride-2 window with zero pad on the right/bottom only is one more gather mode of `fluxmi_im2col3x3`;
   * DiagonalGaussian: mean + exp(logvar/2) * noise on the [B, 2z, h, w] moments (a 128 KB tensor at 1024^2 -- torch elementwise).
@@ -136,7 +139,21 @@ class Decoder(nn.Module):  # reference :203-259 (module tree / state-dict keys)
         self.conv_out = nn.Conv2d(block_in, out_ch, kernel_size=3, stride=1, padding=1)
 
 
+ATTENTION_MODES = ("gemm", "streaming")
+
+
+def check_attention_mode(mode) -> str:
+    if mode not in ATTENTION_MODES:
+        raise ValueError(f"fluxmi: vae_attention={mode!r}: expected one of {ATTENTION_MODES}")
+    return mode
+
+
 class AutoEncoder(nn.Module):
+    # latent pixels (over all images) one decode / encode launch sequence takes: the widest full-resolution activation, 64 pixels per
+    # latent pixel x 256 channels x 2 bytes, is the A operand of a 1x1-convolution GEMM behind a 32-bit buffer descriptor (< 4 GiB);
+    # batches above it run image by image
+    MAX_LATENT_PIXELS_PER_PASS = 131071
+
     def __init__(self, params: AutoEncoderParams):
         super().__init__()
         self.params = params
@@ -149,6 +166,16 @@ class AutoEncoder(nn.Module):
         self.encoder_loaded = True  # util.load_autoencoder clears it for decoder-only checkpoints
         self._wcache = {}
         self.implicit_conv = True  # 3x3 convolutions as implicit GEMMs (fluxmi_conv3x3); False = im2col + GEMM (same bits, tests)
+        self._attention = "gemm"
+
+    @property
+    def attention(self) -> str:
+        """mid-block attention: "gemm" (three launches around a [P, P] score matrix) or "streaming" (fluxmi_vae_attention, one launch)"""
+        return self._attention
+
+    @attention.setter
+    def attention(self, mode):
+        self._attention = check_attention_mode(mode)
 
     # ---- weight preparation (once per module): conv weight -> GEMM weight [N, K] bf16, K ordered (dy, dx, cin) --------------------
     def _w(self, conv: nn.Conv2d):
@@ -235,6 +262,8 @@ class AutoEncoder(nn.Module):
     def _attn(self, x: Tensor, blk: AttnBlock) -> Tensor:  # reference :37-52
         from fluxmi import ops
 
+        if self._attention == "streaming":
+            return self._attn_streaming(x, blk)
         B, H, W, C = x.shape
         P = H * W
         hn = self._norm(x, blk.norm, False).view(B, P, C)
@@ -256,11 +285,53 @@ class AutoEncoder(nn.Module):
             out[b] = ops.linear(Pm, vt, bv)[:P]                 # [P, C] = P V + b_v
         return self._conv1(out.view(B, H, W, C), blk.proj_out, resid=x)
 
+    def _wqk(self, blk: AttnBlock):
+        """[Wq; Wk] [2C, C] and [bq; bk] for the streaming path's single q / k projection"""
+        key = ("qk", id(blk))
+        ent = self._wcache.get(key)
+        if ent is None or ent[0] is not blk.q.weight or ent[1] is not blk.k.weight or ent[2].device != blk.q.weight.device:
+            (wq, bq, _), (wk, bk, _) = self._w(blk.q), self._w(blk.k)
+            ent = (blk.q.weight, blk.k.weight, torch.cat((wq, wk), 0).contiguous(), torch.cat((bq, bk), 0).contiguous())
+            self._wcache[key] = ent
+        return ent[2], ent[3]
+
+    def _attn_streaming(self, x: Tensor, blk: AttnBlock) -> Tensor:
+        """_attn without the [P, P] matrix: one fused q / k projection over all images, V^T per image from the operand-swapped GEMM, then
+        ONE fluxmi_vae_attention launch.  P is padded to Pp = a multiple of 64 with zero pixel rows: their q / k rows are the projection
+        biases (finite), their V^T columns Wv . 0 = 0; the kernel gives keys >= P weight exactly 0 and writes no row >= P."""
+        from fluxmi import ops
+
+        B, H, W, C = x.shape
+        P = H * W
+        if C not in (64, 512):
+            raise ValueError(f"fluxmi: AutoEncoder.attention=\"streaming\" runs a mid block of width 64 or 512 (fluxmi_vae_attention); this "
+                             f"autoencoder's is {C} wide: use attention=\"gemm\"")
+        hn = self._norm(x, blk.norm, False).view(B, P, C)
+        Pp = -(-P // 64) * 64
+        xp = hn if Pp == P else torch.cat((hn, hn.new_zeros(B, Pp - P, C)), 1)
+        wqk, bqk = self._wqk(blk)
+        wv, bv, _ = self._w(blk.v)
+        qk = ops.linear(xp.view(B * Pp, C), wqk, bqk).view(B, Pp, 2 * C)   # [q | k]
+        vt = torch.empty(B, C, Pp, dtype=hn.dtype, device=hn.device)
+        for b in range(B):
+            ops.linear(wv, xp[b], None, out=vt[b])                         # [C, Pp] = Wv . Xn^T = V^T (bias added after P V)
+        out = ops.vae_attention(qk[:, :, :C], qk[:, :, C:], vt, P, v_bias=bv)
+        return self._conv1(out.view(B, H, W, C), blk.proj_out, resid=x)
+
+    def _per_image(self, fn, t: Tensor, latent_pixels: int):
+        """fn(t) image by image when the batch's rows would pass a 32-bit descriptor (MAX_LATENT_PIXELS_PER_PASS), else None"""
+        if t.shape[0] > 1 and t.shape[0] * latent_pixels > self.MAX_LATENT_PIXELS_PER_PASS:
+            return torch.cat([fn(t[i : i + 1]) for i in range(t.shape[0])], 0)
+        return None
+
     @torch.inference_mode()
     def decode(self, z: Tensor) -> Tensor:
         """z [B, z_channels, h, w] -> image [B, out_ch, 8h, 8w] (bf16), reference :330-332 + :261-283 under autocast(bf16)."""
         if not z.is_cuda:
             raise RuntimeError("fluxmi: AutoEncoder.decode needs the GPU (libfluxmi has no CPU path)")
+        split = self._per_image(self.decode, z, z.shape[-2] * z.shape[-1])
+        if split is not None:
+            return split
         d = self.decoder
         h = (z.float() / self.scale_factor + self.shift_factor).permute(0, 2, 3, 1).to(torch.bfloat16).contiguous()  # NHWC
         h = self._conv3(h, d.conv_in)
@@ -286,6 +357,9 @@ class AutoEncoder(nn.Module):
         n_down = e.num_resolutions - 1
         if x.shape[-2] % (1 << n_down) or x.shape[-1] % (1 << n_down):
             raise ValueError(f"fluxmi: AutoEncoder.encode needs H and W to be multiples of {1 << n_down}")
+        split = self._per_image(self.encode_moments, x, (x.shape[-2] >> n_down) * (x.shape[-1] >> n_down))
+        if split is not None:
+            return split
         h = x.permute(0, 2, 3, 1).to(torch.bfloat16).contiguous()  # NHWC
         h = self._conv3(h, e.conv_in)
         for i_level in range(e.num_resolutions):

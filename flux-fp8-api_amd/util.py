@@ -81,6 +81,9 @@ class ModelSpec(BaseModel):  # reference util.py:38-79 (unknown JSON keys are ig
     # once per pipeline against the loaded VAE (fit_preview_factors)
     preview_factors: Optional[list] = None
     preview_bias: Optional[list] = None
+    # the VAE's mid-block attention: "gemm" (three launches around a [P, P] score matrix; decodes / encodes up to 46340 latent pixels) or
+    # "streaming" (fluxmi_vae_attention: one launch, no score matrix; what a tiled 2048 x 2048 request needs to be decoded)
+    vae_attention: str = "gemm"
 
     model_config: ConfigDict = {"arbitrary_types_allowed": True, "use_enum_values": True}
 
@@ -288,6 +291,7 @@ def load_autoencoder(config: ModelSpec, state_dict=None):
 
         state_dict = load_sft(path, device="cpu")
     ae = AutoEncoder(config.ae_params)
+    ae.attention = getattr(config, "vae_attention", "gemm")
     missing, unexpected = ae.load_state_dict(state_dict, strict=False)
     if any(k.startswith("decoder.") for k in missing):
         raise RuntimeError(f"autoencoder checkpoint is missing decoder weights: {[k for k in missing if k.startswith('decoder.')][:4]} ...")

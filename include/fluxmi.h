@@ -375,6 +375,24 @@ int fluxmi_text_attention(const void* q, const void* k, long long ld_qk, const v
 int fluxmi_vision_attention(const void* q, const void* k, long long ld_qk, long long bs_qk, const void* vt, long long ld_vt, long long bs_vt,
                             void* out, long long ld_out, long long bs_out, const void* v_bias, float scale, int head_dim, int L, int Lp, int H, int B,
                             void* stream);
+/* Streaming attention of the autoencoder's mid block: ONE head of width D = 64 or 512, non-causal, B images in one launch, no [P, P] matrix.
+ *   q, k   bf16 [B][Pp][D], row stride ld_qk, batch stride bs_qk (both: two column windows of one fused projection output are fine)
+ *   vt     bf16 [B][D][Pp] = V transposed (row = channel, column = key), row stride ld_vt, batch stride bs_vt
+ *   out    bf16 [B][P][D], row stride ld_out, batch stride bs_out; rows >= P and everything outside the addressed window are not written
+ *   v_bias bf16 [D] or NULL
+ * Pp is a multiple of 64 that is >= P (P rounded up to 64).  Rows >= P of q and k and columns >= P of vt may hold arbitrary FINITE values; no
+ * output depends on them.  Arithmetic, with c = fp32(log2 e / sqrt D) and the keys walked in tiles of FLUXMI_VAE_ATTN_KEY_TILE:
+ *   s_ij = fp32 MFMA sum of the bf16 products q_i . k_j;   t_ij = s_ij * c in fp32
+ *   per tile: m' = max(m, max_j t_ij), exact;  O and l are multiplied by exp2(m - m') in fp32 when the maximum grew;
+ *             p_ij = exp2(t_ij - m') in fp32;  l += sum_j p_ij in fp32;  O += bf16(p) V on the matrix pipe with fp32 accumulation
+ *   out = bf16(O / l + v_bias[d])  -- the only rounding of the output
+ * P is rounded to bf16 once, after its tile's maximum is final; there is no deferred maximum.  Keys >= P have weight exactly 0.  A sample's
+ * bits depend on that sample alone, and results are deterministic (no atomics, fixed summation order).
+ * Returns non-zero before any launch for: D other than 64 / 512; P < 1; Pp %% 64 != 0 or Pp < P; B outside 1..65535; a stride that is no
+ * multiple of 8 (or too short for its operand); a pointer that is not 16-byte aligned.  All stride arithmetic is 64-bit. */
+#define FLUXMI_VAE_ATTN_KEY_TILE 64
+int fluxmi_vae_attention(const void* q, const void* k, long long ld_qk, long long bs_qk, const void* vt, long long ld_vt, long long bs_vt,
+                         void* out, long long ld_out, long long bs_out, const void* v_bias, int D, int P, int Pp, int B, void* stream);
 /* Patch rows of a stride-`patch` "valid" convolution: pix bf16 [B, C, H, W] (NCHW, contiguous) -> out bf16 [B*grid*grid, Kp], row
  * (b, gy, gx), column c*patch*patch + ky*patch + kx (the order of a Conv2d weight [N, C, patch, patch] flattened), columns >= C*patch*patch
  * zero.  Pixels past grid*patch are not read.  Kp %% 8 == 0; grid*patch <= H, W.  SigLIP-so400m: C 3, patch 14, grid 27, Kp 640. */

@@ -27,6 +27,8 @@ Same two POST endpoints, request fields, defaults and status codes:
              (FluxPipeline.generate), each passed on only when set;
              tile_size=None (an int or [height, width] in pixels), tile_overlap=None (>= 0, pixels), tile_weight=None ("cosine" | "uniform")
              -- tiled generation: a large canvas stepped from overlapping windows (FluxPipeline.generate), each passed on only when set;
+             upscale=false, init_upscale=false -- the configured ESRGAN-family upscaler on the decoded pixels / on init_image
+             (FluxPipeline.generate; needs config.upscaler_path), each passed on only when true;
              stream=None, preview_every=None (>= 0) -- progress, live previews and cancellation, see below;
              a region with both or neither of box / mask, or a box outside 0 <= x0 < x1 <= 1, is a 422}
              ->  image/jpeg stream of FluxPipeline.generate(**args)                                               (reference api.py:54-86)
@@ -130,6 +132,8 @@ class GenerateArgs(BaseModel):
     tile_size: Optional[Union[int, Tuple[int, int]]] = None  # tiled generation: the window in pixels, an int (square) or [height, width] (FluxPipeline.generate)
     tile_overlap: Optional[int] = Field(default=None, ge=0)  # ... the overlap of neighbouring windows in pixels (default: a quarter of the tile)
     tile_weight: Optional[str] = None  # ... "cosine" (default) | "uniform": how overlapping windows are blended
+    upscale: Optional[bool] = False  # run the decoded pixels through the configured ESRGAN-family upscaler (config.upscaler_path): scale x the size
+    init_upscale: Optional[bool] = False  # run init_image through it before the resize to width x height (the upscale + img2img workflow)
     stream: Optional[bool] = None  # answer with application/x-ndjson progress lines and a final result line instead of the JPEG
     preview_every: Optional[int] = Field(default=None, ge=0)  # ... with a latent-resolution preview at every k-th model evaluation (0 = none)
 
@@ -195,7 +199,8 @@ def generate(args: GenerateArgs):
     `control_mode`, `control_guidance_start` / `_end`) a FLUX ControlNet, `ip_adapter_image` / `ip_adapter_image_embeds` (+ `ip_adapter_scale`,
     `negative_ip_adapter_image`, `negative_ip_adapter_scale`) a FLUX IP-Adapter, `guidance_mode` / `guidance_rescale` / `apg_*` /
     `zero_init_steps` guidance shaping of a guided request, `source_prompt` (+ `source_guidance`, `edit_n_max` / `_min` / `_avg`) a FlowEdit edit of
-    `init_image` towards `prompt`, `tile_size` (+ `tile_overlap`, `tile_weight`) tiled generation of a large canvas.  Without them the call is exactly the reference's."""
+    `init_image` towards `prompt`, `tile_size` (+ `tile_overlap`, `tile_weight`) tiled generation of a large canvas, `upscale` / `init_upscale` the
+    configured super-resolution network on the output / on `init_image`.  Without them the call is exactly the reference's."""
     kwargs = args.model_dump()
     stream = bool(kwargs.pop("stream", None))
     if kwargs.get("preview_every") is None:
@@ -210,6 +215,9 @@ def generate(args: GenerateArgs):
               "apg_momentum", "zero_init_steps", "source_prompt", "source_guidance", "edit_n_max", "edit_n_min", "edit_n_avg", "tile_size",
               "tile_overlap", "tile_weight"):
         if kwargs.get(k) is None:
+            kwargs.pop(k, None)
+    for k in ("upscale", "init_upscale"):  # passed on only when asked for
+        if not kwargs.get(k):
             kwargs.pop(k, None)
     if "ip_adapter_image_embeds" in kwargs:
         import torch

@@ -192,6 +192,11 @@ int fluxmi_vae_attention(const void* q, const void* k, long long ld_qk, long lon
                          void* out, long long ld_out, long long bs_out, const void* v_bias, int D, int P, int Pp, int B, void* stream) {
   return fluxmi_k_vae_attention(q, k, ld_qk, bs_qk, vt, ld_vt, bs_vt, out, ld_out, bs_out, v_bias, D, P, Pp, B, (hipStream_t)stream);
 }
+int fluxmi_conv3x3_dense(const void* x, long long ldx, int Cin, const void* w2, const void* bias, void* out, long long ldo, int Cout,
+                         const void* r1, long long ldr1, float a1, const void* r2, long long ldr2, float a2, float slope, int act,
+                         int upsample, int B, int H, int W, void* stream) {
+  return fluxmi_k_conv3x3_dense(x, ldx, Cin, w2, bias, out, ldo, Cout, r1, ldr1, a1, r2, ldr2, a2, slope, act, upsample, B, H, W, (hipStream_t)stream);
+}
 int fluxmi_patchify(const void* pix, void* out, int B, int C, int H, int W, int patch, int grid, int Kp, void* stream) {
   return fluxmi_k_patchify(pix, out, B, C, H, W, patch, grid, Kp, (hipStream_t)stream);
 }

@@ -236,6 +236,9 @@ int fluxmi_k_text_attention(const void* q, const void* k, long long ld_qk, const
                             const float* rel_bias, int bias_ld, const void* v_bias, float scale, int causal, int L, int Lp, int H, hipStream_t s);
 int fluxmi_k_vae_attention(const void* q, const void* k, long long ld_qk, long long bs_qk, const void* vt, long long ld_vt, long long bs_vt,
                            void* out, long long ld_out, long long bs_out, const void* v_bias, int D, int P, int Pp, int B, hipStream_t s);
+int fluxmi_k_conv3x3_dense(const void* x, long long ldx, int Cin, const void* w2, const void* bias, void* out, long long ldo, int Cout,
+                           const void* r1, long long ldr1, float a1, const void* r2, long long ldr2, float a2, float slope, int act,
+                           int upsample, int B, int H, int W, hipStream_t s);
 int fluxmi_k_vision_attention(const void* q, const void* k, long long ld_qk, long long bs_qk, const void* vt, long long ld_vt, long long bs_vt,
                               void* out, long long ld_out, long long bs_out, const void* v_bias, float scale, int head_dim, int L, int Lp, int H,
                               int B, hipStream_t s);

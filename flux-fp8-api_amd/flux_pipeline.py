@@ -30,7 +30,7 @@ import lora_loading  # noqa: F401  (same import side as the reference)
 from fluxmi import dist as fdist
 from fluxmi import solvers
 from modules.autoencoder import check_attention_mode
-from util import (ModelSpec, ModelVersion, engine_flow_dtype, into_device, into_dtype, load_config_from_path, load_controlnet, load_ip_adapter,
+from util import (ModelSpec, ModelVersion, engine_flow_dtype, into_device, into_dtype, load_config_from_path, load_controlnet, load_ip_adapter, load_upscaler,
                   load_models_from_config)
 
 MAX_RAND = 2**32 - 1
@@ -154,7 +154,7 @@ class FluxPipeline:
     def __init__(self, name: str, offload: bool = False, clip=None, t5=None, model=None, ae=None,
                  dtype: torch.dtype = torch.float16, verbose: bool = False, flux_device="cuda:0", ae_device="cuda:1",
                  clip_device="cuda:1", t5_device="cuda:1", config: ModelSpec = None, debug: bool = False, redux=None,
-                 controlnet=None, ip_adapter=None):
+                 controlnet=None, ip_adapter=None, upscaler=None):
         if config is None:
             raise ValueError("ModelSpec config is required!")
         self.debug, self.name, self.verbose, self.offload = debug, name, verbose, offload
@@ -168,6 +168,7 @@ class FluxPipeline:
         self.redux = redux  # FLUX.1 Redux image encoder (modules/image_embedders.ReduxImageEncoder) or None
         self.controlnet = controlnet  # FLUX ControlNet (modules/controlnet.FluxControlNet, config.controlnet_path) or None
         self.ip_adapter = ip_adapter  # FLUX IP-Adapter (modules/ip_adapter.IPAdapter, config.ip_adapter_path / clip_vision_path) or None
+        self.upscaler = upscaler  # ESRGAN-family super-resolution network (modules/upscaler.RRDBNet, config.upscaler_path) or None
         self.rng = torch.Generator(device="cpu")
         self.ae_dtype = torch.bfloat16
         self.config = config
@@ -707,7 +708,7 @@ class FluxPipeline:
                  apg_eta: float = 1.0, apg_norm_threshold: float = 0.0, apg_momentum: float = 0.0, zero_init_steps: int = 0,
                  on_step=None, preview_every: int = 0, preview_factors=None, source_prompt=None, source_guidance: Optional[float] = None,
                  edit_n_max: Optional[int] = None, edit_n_min: int = 0, edit_n_avg: int = 1, tile_size=None, tile_overlap: Optional[int] = None,
-                 tile_weight: str = "cosine"):
+                 tile_weight: str = "cosine", upscale: bool = False, init_upscale: bool = False):
         """`reference_image` (FLUX.1 Kontext [dev] instruction editing): an image the prompt describes an edit of, in any form `init_image`
         takes; see prepare_kontext_reference.  Composes with `init_image` / `strength` unchanged.
         FLUX.1 Fill [dev] (a model with 320 conditioning channels): `init_image` is the image to inpaint and `mask_image` (white =
@@ -841,16 +842,27 @@ class FluxPipeline:
         shaping, `inpaint_mask`, `reference_image`, a Fill / Depth / Canny model, `redux_image`, `regions`, `cache_threshold` > 0, a
         ControlNet, an IP-Adapter, `source_prompt`, `preview_every` > 0 and under a process group.  `tile_size=None`, or a tile of the
         request's size with no other tile argument, is today's request, launch for launch; `tile_overlap` / `tile_weight` without
-        `tile_size` are refused.  Image quality on real FLUX weights is not established here; no tile size or overlap is recommended."""
+        `tile_size` are refused.  Image quality on real FLUX weights is not established here; no tile size or overlap is recommended.
+        `upscale` / `init_upscale` (an ESRGAN-family RRDBNet, config.upscaler_path; modules/upscaler.py, FluxPipeline.upscale): with
+        `upscale=True` the request's uint8 pixels go through the network before they are returned or JPEG-encoded, so the result is
+        `upscaler.scale` times `width` x `height` -- for every request kind that returns pixels, tiled and FlowEdit ones included; with
+        `init_upscale=True` `init_image` goes through it before the resize to `width` x `height` that the request already does, e.g.
+        generate(prompt, init_image=photo, init_upscale=True, width=4096, height=4096, strength=0.3, tile_size=1024) on a
+        vae_attention="streaming" config.  Refused up front: either flag without a configured upscaler, `upscale` with
+        output_type="latent" (or no VAE), `init_upscale` without `init_image`, an image the network's kernel or the device's free memory
+        cannot take.  Both False (the default) is today's request, launch for launch."""
+        if upscale or init_upscale:
+            init_image = self._check_upscale(upscale, init_upscale, output_type, init_image, width, height, num_images)
         tiles = self._check_tiles(locals())
         if tiles is not None:
             return self._generate_tiled(tiles, prompt, width, height, num_steps, guidance, seed, init_image, strength, num_images, return_seed,
                                         jpeg_quality, output_type, noise, use_graph, negative_prompt, true_cfg_scale, true_cfg_interval,
-                                        sigma_schedule, sigmas, on_step)
+                                        sigma_schedule, sigmas, on_step, upscale=upscale)
         edit = self._check_edit(locals())
         if edit is not None:
             return self._generate_edit(edit, prompt, source_prompt, width, height, num_steps, guidance, seed, init_image, silent, num_images,
-                                       return_seed, jpeg_quality, output_type, use_graph, sigma_schedule, sigmas, noise_seed, on_step)
+                                       return_seed, jpeg_quality, output_type, use_graph, sigma_schedule, sigmas, noise_seed, on_step,
+                                       upscale=upscale)
         if isinstance(preview_every, bool) or not isinstance(preview_every, int) or preview_every < 0:
             raise ValueError(f"fluxmi: preview_every={preview_every!r}: expected an integer >= 0 (0 = no previews)")
         if on_step is not None and not callable(on_step):
@@ -1214,7 +1226,7 @@ class FluxPipeline:
             return (out, seed) if return_seed else out
         img_px = self.vae_decode(latents, height, width)
         # output_type "uint8": the [B, H, W, 3] array into_bytes hands to the JPEG encoder (the pixel-parity tests compare it)
-        out = self.to_uint8(img_px) if output_type == "uint8" else self.into_bytes(img_px, jpeg_quality=jpeg_quality)
+        out = self._pixels_out(img_px, output_type, jpeg_quality, upscale)
         return (out, seed) if return_seed else out
 
     # ---- tiled generation (fluxmi.windows; Flux.denoise_windows) -------------------------------------------------------------------------------
@@ -1321,7 +1333,8 @@ class FluxPipeline:
         return plan
 
     def _generate_tiled(self, plan, prompt, width, height, num_steps, guidance, seed, init_image, strength, num_images, return_seed, jpeg_quality,
-                        output_type, noise, use_graph, negative_prompt, true_cfg_scale, true_cfg_interval, sigma_schedule, sigmas, on_step):
+                        output_type, noise, use_graph, negative_prompt, true_cfg_scale, true_cfg_interval, sigma_schedule, sigmas, on_step,
+                        upscale=False):
         """the tiled request of generate (its docstring): today's noise / img2img / text at canvas size, then Flux.denoise_windows on the
         canvas -- one call, or up to three where true_cfg_interval cuts the request"""
         from modules.flux_model import Flux, PreviewCall
@@ -1366,7 +1379,7 @@ class FluxPipeline:
             out = self.unpack(latents.float(), height, width)
             return (out, seed) if return_seed else out
         img_px = self.vae_decode(latents, height, width)
-        out = self.to_uint8(img_px) if output_type == "uint8" else self.into_bytes(img_px, jpeg_quality=jpeg_quality)
+        out = self._pixels_out(img_px, output_type, jpeg_quality, upscale)
         return (out, seed) if return_seed else out
 
     # ---- FlowEdit (fluxmi.flowedit; Flux.denoise_edit) ---------------------------------------------------------------------------------------
@@ -1454,7 +1467,7 @@ class FluxPipeline:
         return latent, timesteps
 
     def _generate_edit(self, edit, prompt, source_prompt, width, height, num_steps, guidance, seed, init_image, silent, num_images, return_seed,
-                       jpeg_quality, output_type, use_graph, sigma_schedule, sigmas, noise_seed, on_step):
+                       jpeg_quality, output_type, use_graph, sigma_schedule, sigmas, noise_seed, on_step, upscale=False):
         """the FlowEdit request of generate (its docstring): skipped steps | coupled steps (Flux.denoise_edit) | Euler tail (Flux.denoise)"""
         from fluxmi import flowedit, ops
         from modules.flux_model import PreviewCall
@@ -1503,7 +1516,7 @@ class FluxPipeline:
             out = self.unpack(latents.float(), height, width)
             return (out, seed) if return_seed else out
         img_px = self.vae_decode(latents, height, width)
-        out = self.to_uint8(img_px) if output_type == "uint8" else self.into_bytes(img_px, jpeg_quality=jpeg_quality)
+        out = self._pixels_out(img_px, output_type, jpeg_quality, upscale)
         return (out, seed) if return_seed else out
 
     def _preview_call(self, on_step, proj, every: int, height: int, width: int, step0: int, eval_offset: int, n_evaluations: int, solver):
@@ -1555,9 +1568,56 @@ class FluxPipeline:
         return x.clamp(-1, 1).add(1.0).mul(127.5).clamp(0, 255).permute(0, 2, 3, 1).contiguous().to(torch.uint8).cpu()
 
     def into_bytes(self, x: torch.Tensor, jpeg_quality: int = 99) -> io.BytesIO:
+        return self._jpeg(self.to_uint8(x), jpeg_quality)
+
+    # ---- super-resolution (modules/upscaler.RRDBNet on fluxmi_conv3x3_dense) ---------------------------------------------------------------
+    def _require_upscaler(self):
+        if getattr(self, "upscaler", None) is None:
+            raise ValueError("fluxmi: upscaling needs an ESRGAN-family checkpoint: set config.upscaler_path to a local RRDBNet .safetensors / "
+                             ".pth file (nothing is downloaded)")
+        return self.upscaler
+
+    def upscale(self, image) -> torch.Tensor:
+        """One image in any form `init_image` takes (path, base64 / data-URL, PIL image, HWC uint8 array or tensor), or a uint8 batch
+        [B, H, W, 3] -> uint8 [B, scale H, scale W, 3] on the host through the configured RRDBNet: / 255 -> bf16 -> network -> clamp [0, 1]
+        -> * 255, round half even.  An input the kernel's addressing or the free memory cannot take is refused by name; the network is
+        not tiled."""
+        net = self._require_upscaler()
+        px = self.load_init_image_if_needed(image)
+        if not isinstance(px, torch.Tensor) or px.dtype != torch.uint8:
+            raise ValueError("fluxmi: upscale takes uint8 pixels (an image, or a [B, H, W, 3] uint8 batch)")
+        if px.ndim == 2:
+            px = px[..., None].expand(-1, -1, 3)
+        if px.ndim == 3:
+            px = px[None]
+        if px.ndim != 4 or px.shape[-1] not in (3, 4):
+            raise ValueError(f"fluxmi: upscale takes RGB pixels [H, W, 3] or [B, H, W, 3], got {tuple(px.shape)}")
+        return net.upscale_uint8(px[..., :3].contiguous())
+
+    def _check_upscale(self, upscale, init_upscale, output_type, init_image, width, height, num_images):
+        """every refusal of generate's `upscale` / `init_upscale`, before any other work; -> init_image (upscaled when asked)"""
+        net = self._require_upscaler()
+        if upscale and (output_type == "latent" or self.ae is None):
+            raise ValueError("fluxmi: upscale=True works on pixels: it cannot be combined with output_type=\"latent\" (or a pipeline without a VAE)")
+        if init_upscale and init_image is None:
+            raise ValueError("fluxmi: init_upscale=True needs init_image (the image to super-resolve before img2img)")
+        if upscale:
+            net.check_input(max(1, int(num_images)), 16 * (height // 16), 16 * (width // 16))
+        if init_upscale:
+            init_image = self.upscale(init_image)[0]
+        return init_image
+
+    def _pixels_out(self, img_px: torch.Tensor, output_type: str, jpeg_quality: int, upscale: bool = False):
+        """decoded pixels -> what the request returns: the uint8 array or its JPEG, through the upscaler first when asked"""
+        px = self.to_uint8(img_px)
+        if upscale:
+            px = self.upscale(px)
+        return px if output_type == "uint8" else self._jpeg(px, jpeg_quality)
+
+    @staticmethod
+    def _jpeg(px: torch.Tensor, jpeg_quality: int = 99) -> io.BytesIO:
         from PIL import Image
 
-        px = self.to_uint8(x)
         imgs = [px[i].numpy() for i in range(px.shape[0])]
         im = imgs[0] if len(imgs) == 1 else np.vstack(imgs)
         buf = io.BytesIO()
@@ -1605,4 +1665,5 @@ class FluxPipeline:
         return cls(name=config.version, clip=models.clip, t5=models.t5, model=flow_model, ae=models.ae, dtype=flux_dtype, verbose=False,
                    flux_device=flux_device, ae_device=into_device(config.ae_device), clip_device=into_device(config.text_enc_device),
                    t5_device=into_device(config.text_enc_device), config=config, debug=debug, redux=redux,
-                   controlnet=load_controlnet(config, device=flux_device), ip_adapter=load_ip_adapter(config, device=flux_device))
+                   controlnet=load_controlnet(config, device=flux_device), ip_adapter=load_ip_adapter(config, device=flux_device),
+                   upscaler=load_upscaler(config, device=into_device(config.ae_device)))

@@ -455,6 +455,55 @@ def conv3x3(x: torch.Tensor, w2: torch.Tensor, bias=None, upsample: int = 1, res
     return out
 
 
+CONV_DENSE_TILE = 16  # include/fluxmi.h FLUXMI_CONV_DENSE_TILE: the kernel's pixel tile edge
+
+
+def _pixel_stride(t: torch.Tensor, name: str) -> int:
+    """t: a [B, H, W, C] channel window of an NHWC pixel buffer -> its pixel stride in elements"""
+    if t.ndim != 4 or t.stride(3) != 1:
+        raise ValueError(f"conv3x3_dense: {name} must be a [B, H, W, C] view with channel stride 1, got {tuple(t.shape)} / {t.stride()}")
+    B, H, W, _ = t.shape
+    ld = t.stride(2) if W > 1 else (t.stride(1) if H > 1 else (t.stride(0) if B > 1 else t.shape[3] + (-t.shape[3]) % 8))
+    ok = (W == 1 or t.stride(2) == ld) and (H == 1 or t.stride(1) == W * ld) and (B == 1 or t.stride(0) == H * W * ld)
+    if not ok:
+        raise ValueError(f"conv3x3_dense: {name} must address its pixels densely ([B][H][W] with ONE pixel stride), got strides {t.stride()}")
+    return ld
+
+
+def conv3x3_dense(x: torch.Tensor, w2: torch.Tensor, bias: Optional[torch.Tensor], out: torch.Tensor, r1: Optional[torch.Tensor] = None,
+                  a1: float = 1.0, r2: Optional[torch.Tensor] = None, a2: float = 1.0, slope: float = 0.2, act: bool = False,
+                  upsample: int = 1) -> torch.Tensor:
+    """The dense-block 3x3 convolution (fluxmi_conv3x3_dense; include/fluxmi.h has the arithmetic) on CHANNEL WINDOWS of NHWC bf16 pixel
+    buffers: x [B, Hi, Wi, Cin] and out [B, H, W, Cout] are views such as buf[..., :Cin] and buf[..., Cin:Cin + Cout] (the same buffer is
+    fine when the windows do not meet), r1 / r2 [B, H, W, Cout] likewise.  w2 [Cout32, 3, 3, Cin] (Cout32 = Cout rounded up to 32, extra
+    rows zero), bias [Cout32] or None.  out = bf16(a2 * (a1 * lrelu(conv(x) + bias) + r1) + r2), each stage optional; H = upsample * Hi."""
+    _req(x, torch.bfloat16, "x")
+    _req(w2, torch.bfloat16, "w2")
+    _req(out, torch.bfloat16, "out")
+    ldx, ldo = _pixel_stride(x, "x"), _pixel_stride(out, "out")
+    B, Hi, Wi, Cin = x.shape
+    Bo, H, W, Cout = out.shape
+    if upsample not in (1, 2) or (Bo, H, W) != (B, Hi * upsample, Wi * upsample):
+        raise ValueError(f"conv3x3_dense: out {tuple(out.shape)} does not match x {tuple(x.shape)} at upsample={upsample}")
+    c32 = (Cout + 31) // 32 * 32
+    if not w2.is_contiguous() or w2.numel() != c32 * 9 * Cin or w2.shape[0] != c32:
+        raise ValueError(f"conv3x3_dense: w2 must be contiguous [Cout32 = {c32}, 3, 3, Cin = {Cin}], got {tuple(w2.shape)}")
+    if bias is not None:
+        _req(bias, torch.bfloat16, "bias")
+        if bias.numel() != c32 or not bias.is_contiguous():
+            raise ValueError(f"conv3x3_dense: bias needs Cout32 = {c32} contiguous entries")
+    ld_r = [0, 0]
+    for i, r in enumerate((r1, r2)):
+        if r is not None:
+            _req(r, torch.bfloat16, f"r{i + 1}")
+            if tuple(r.shape) != (B, H, W, Cout):
+                raise ValueError(f"conv3x3_dense: r{i + 1} must be {(B, H, W, Cout)}, got {tuple(r.shape)}")
+            ld_r[i] = _pixel_stride(r, f"r{i + 1}")
+    call("fluxmi_conv3x3_dense", _p(x), ldx, Cin, _p(w2), _p(bias), _p(out), ldo, Cout, _p(r1), ld_r[0], float(a1), _p(r2), ld_r[1], float(a2),
+         float(slope), int(bool(act)), upsample, B, H, W, _stream())
+    return out
+
+
 def im2col3x3(x: torch.Tensor, upsample: int = 1) -> torch.Tensor:
     """x [B, Hin, Win, C] bf16 -> patch matrix [B*H*W, 9*C], column order (dy, dx, c).  upsample = 1: H = Hin; 2: nearest 2x upsample
     first (H = 2*Hin); -2: stride-2 window with zero pad on the right/bottom only (H = Hin/2, the reference's Downsample)."""

@@ -173,3 +173,46 @@ def make_clip_vision_state_dict(config: dict, seed: int = 0, dtype=torch.float32
     ln("vision_model.post_layernorm")
     lin("visual_projection", config["projection_dim"], D, bias=False)
     return sd
+
+
+def make_rrdbnet_state_dict(num_block: int = 2, nf: int = 64, gc: int = 32, scale: int = 4, seed: int = 0,
+                            layout: str = "new") -> Dict[str, torch.Tensor]:
+    """A seeded RRDBNet checkpoint (modules/upscaler.py) for tests and tools: Conv2d weights [Cout, Cin, 3, 3] and biases as fp32 tensors that
+    hold bf16 values.  He-style gains keep the activations O(1) through a few blocks, so no branch can be ignored by a test: std 1.4 /
+    sqrt(9 Cin) on the trunk's convolutions (the dense blocks, conv_body, conv_up1 / 2, conv_hr), 1.0 / sqrt(9 Cin) on conv_first and
+    conv_last; biases N(0, 0.1).  `scale` 4 / 2 / 1 gives conv_first 3 / 12 / 48 input channels (Real-ESRGAN's pixel_unshuffle heads).
+    `layout`: "new" (BasicSR keys) or "old" (the original ESRGAN x4 keys: model.0, model.1.sub.{i}.RDB{j}.conv{k}.0, model.1.sub.{n},
+    model.3 / 6 / 8 / 10; scale 4 only)."""
+    if scale not in (4, 2, 1):
+        raise ValueError(f"make_rrdbnet_state_dict: scale={scale} must be 4, 2 or 1")
+    if layout not in ("new", "old") or (layout == "old" and scale != 4):
+        raise ValueError(f"make_rrdbnet_state_dict: layout={layout!r} must be 'new' or 'old' (old: scale 4 only)")
+    gen = torch.Generator().manual_seed(1000 + seed)
+    in_ch = {4: 3, 2: 12, 1: 48}[scale]
+    sd: Dict[str, torch.Tensor] = {}
+
+    def conv(name, co, ci, gain):
+        sd[name + ".weight"] = (torch.randn(co, ci, 3, 3, generator=gen) * (gain / math.sqrt(9 * ci))).bfloat16().float()
+        sd[name + ".bias"] = (0.1 * torch.randn(co, generator=gen)).bfloat16().float()
+
+    conv("conv_first", nf, in_ch, 1.0)
+    for i in range(num_block):
+        for j in (1, 2, 3):
+            for k in (1, 2, 3, 4, 5):
+                conv(f"body.{i}.rdb{j}.conv{k}", nf if k == 5 else gc, nf + (k - 1) * gc, 1.4)
+    for name in ("conv_body", "conv_up1", "conv_up2", "conv_hr"):
+        conv(name, nf, nf, 1.4)
+    conv("conv_last", 3, nf, 1.0)
+    if layout == "new":
+        return sd
+    fixed = {"conv_first": "model.0", "conv_body": f"model.1.sub.{num_block}", "conv_up1": "model.3", "conv_up2": "model.6", "conv_hr": "model.8",
+             "conv_last": "model.10"}
+    old = {}
+    for k, v in sd.items():
+        base, leaf = k.rsplit(".", 1)
+        if base in fixed:
+            old[f"{fixed[base]}.{leaf}"] = v
+        else:
+            _, i, rdb, cv = base.split(".")
+            old[f"model.1.sub.{i}.RDB{rdb[3:]}.conv{cv[4:]}.0.{leaf}"] = v
+    return old

@@ -84,6 +84,9 @@ class ModelSpec(BaseModel):  # reference util.py:38-79 (unknown JSON keys are ig
     # the VAE's mid-block attention: "gemm" (three launches around a [P, P] score matrix; decodes / encodes up to 46340 latent pixels) or
     # "streaming" (fluxmi_vae_attention: one launch, no score matrix; what a tiled 2048 x 2048 request needs to be decoded)
     vae_attention: str = "gemm"
+    # an ESRGAN-family super-resolution network (RRDBNet: ESRGAN, Real-ESRGAN x4plus / x2plus, 4x-UltraSharp ...; modules/upscaler.py): a
+    # LOCAL .safetensors or .pth file.  Nothing is downloaded; FluxPipeline.upscaler is None unless the file exists
+    upscaler_path: str | None = None
 
     model_config: ConfigDict = {"arbitrary_types_allowed": True, "use_enum_values": True}
 
@@ -387,6 +390,19 @@ def load_ip_adapter(config: ModelSpec, device=None):
         return None
     m = read_ip_adapter(ip, read_clip_vision(clip))
     return m.to(device=into_device(device if device is not None else config.flux_device), dtype=torch.bfloat16)
+
+
+def load_upscaler(config: ModelSpec, device=None):
+    """The RRDBNet of config.upscaler_path (modules/upscaler.RRDBNet) on `device`, or None unless the path is a local file.  Nothing is
+    downloaded.  A checkpoint of another architecture is refused by name (modules.upscaler.normalize_state_dict)."""
+    import os
+
+    path = getattr(config, "upscaler_path", None)
+    if not (isinstance(path, str) and os.path.isfile(path)):
+        return None
+    from modules.upscaler import read_upscaler
+
+    return read_upscaler(path, device=into_device(device if device is not None else config.ae_device))
 
 
 def load_models_from_config(config: ModelSpec, state_dict=None, ae_state_dict=None, clip_kwargs=None, t5_kwargs=None) -> LoadedModels:

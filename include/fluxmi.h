@@ -393,6 +393,31 @@ int fluxmi_vision_attention(const void* q, const void* k, long long ld_qk, long 
 #define FLUXMI_VAE_ATTN_KEY_TILE 64
 int fluxmi_vae_attention(const void* q, const void* k, long long ld_qk, long long bs_qk, const void* vt, long long ld_vt, long long bs_vt,
                          void* out, long long ld_out, long long bs_out, const void* v_bias, int D, int P, int Pp, int B, void* stream);
+/* The 3x3 convolution of RRDBNet (ESRGAN family; modules/upscaler.py): stride 1, zero pad 1, NHWC bf16, reading and writing CHANNEL WINDOWS
+ * of strided pixel buffers, so a residual dense block is five launches on one [B, H, W, nf + 4 gc] buffer with no concatenation copy.
+ *   x      bf16 [B][Hi][Wi] pixels, pixel stride ldx elements; channels [0, Cin) of each pixel are read.  (H, W) is the OUTPUT grid:
+ *          upsample 1: Hi = H, Wi = W;  upsample 2: Hi = H/2, Wi = W/2, the nearest 2x upsample folded into the gather (output pixel
+ *          (y, x) of the upsampled image is input pixel (y/2, x/2); the zero pad surrounds the UPSAMPLED image) -- fluxmi_conv3x3's convention
+ *   w2     bf16 [Cout32][3][3][Cin], Cout32 = Cout rounded up to 32; the caller zero-pads rows >= Cout
+ *   bias   bf16 [Cout32] or NULL
+ *   out    bf16 [B][H][W] pixels, pixel stride ldo; channels [0, Cout) at `out` are written and NOTHING else is (the caller points `out`
+ *          at the first channel of the window)
+ *   r1, r2 optional bf16 residuals, channels [0, Cout) of [B][H][W] pixels with pixel strides ldr1, ldr2 (r2 needs r1)
+ * Arithmetic, all fp32 until the store:
+ *   acc = MFMA (v_mfma_f32_32x32x16_bf16) sum of the bf16 products over input-channel chunks of 64, then (dy, dx), then 16-channel steps
+ *   y = acc + bias;   act = 1: y = y < 0 ? slope * y : y;   r1: y = a1 * y + r1;   r2: y = a2 * y + r2;   out = bf16(y)
+ * Each scale-and-add is TWO operations (a rounded product, then a rounded sum), not an fma.  The store is the only bf16 rounding.
+ * One workgroup computes a FLUXMI_CONV_DENSE_TILE x FLUXMI_CONV_DENSE_TILE pixel tile of one image.
+ * Aliasing: `out` may lie in the same buffer as x iff its channel window does not meet [0, Cin); r1 and r2 may alias x; `out` overlaps
+ * neither residual.  Deterministic (no atomics, fixed summation order); a sample's bits depend on that sample alone.  All address
+ * arithmetic is 64-bit.
+ * Returns non-zero before any launch (text in fluxmi_last_error) for: Cin not a multiple of 16 in 16..256; Cout outside 1..64; upsample
+ * other than 1 / 2, or 2 with odd H or W; act other than 0 / 1; B, H or W < 1; B or ceil(H / tile) above 65535 (the launch grid);
+ * a stride that is no multiple of 8 or shorter than its channels; a pointer that is not 16-byte aligned; r2 without r1; out == r1 or r2. */
+#define FLUXMI_CONV_DENSE_TILE 16
+int fluxmi_conv3x3_dense(const void* x, long long ldx, int Cin, const void* w2, const void* bias, void* out, long long ldo, int Cout,
+                         const void* r1, long long ldr1, float a1, const void* r2, long long ldr2, float a2, float slope, int act,
+                         int upsample, int B, int H, int W, void* stream);
 /* Patch rows of a stride-`patch` "valid" convolution: pix bf16 [B, C, H, W] (NCHW, contiguous) -> out bf16 [B*grid*grid, Kp], row
  * (b, gy, gx), column c*patch*patch + ky*patch + kx (the order of a Conv2d weight [N, C, patch, patch] flattened), columns >= C*patch*patch
  * zero.  Pixels past grid*patch are not read.  Kp %% 8 == 0; grid*patch <= H, W.  SigLIP-so400m: C 3, patch 14, grid 27, Kp 640. */

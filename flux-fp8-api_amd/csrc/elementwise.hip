@@ -4,7 +4,7 @@
 // reference's bf16 rounding points (common.h).  Reference sites are cited per kernel.
 #include "common.h"
 #include "fluxmi_internal.h"
-#include "philox.h"
+#include "stream_view.h"  // grid_for
 
 namespace {
 
@@ -510,280 +510,6 @@ __global__ void rope_table_kernel(const u16* __restrict__ ids, const float* __re
   pe[i * 2 + 1] = f2bf(sinf(ang));
 }
 
-// Euler step of the flow ODE:  img = bf16( img + bf16(dt * pred) ),  dt = dts[*step]       flux_pipeline.py:651
-__global__ void __launch_bounds__(256) euler_kernel(u16* __restrict__ img, const u16* __restrict__ pred, const float* __restrict__ dts,
-                                                    const int* __restrict__ step, long long n) {
-  const float dt = dts[step ? *step : 0];
-  for (long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 8; i < n; i += (long long)gridDim.x * blockDim.x * 8) {
-    float fi[8], fp[8];
-    unpack8(*(const uint4*)(img + i), fi);
-    unpack8(*(const uint4*)(pred + i), fp);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) fi[j] += rbf(dt * fp[j]);
-    *(uint4*)(img + i) = pack8(fi);
-  }
-}
-// The Euler step of an image stream LONGER than the prediction (FLUX.1 Kontext: the reference-image rows ride behind the noisy rows of each
-// sample and are never stepped): rows [0, pred_rows) of every sample of img [B, img_rows, C] += bf16(dt * pred), pred [B, pred_rows, C].
-// Same arithmetic as euler_kernel, 16-byte accesses (C % 8 == 0: a vector never straddles a row); the reference rows are not touched.
-__global__ void __launch_bounds__(256) euler_rows_kernel(u16* __restrict__ img, const u16* __restrict__ pred, const float* __restrict__ dts,
-                                                         const int* __restrict__ step, long long n, long long pred_bstride, long long img_bstride) {
-  const float dt = dts[*step];
-  for (long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 8; i < n; i += (long long)gridDim.x * blockDim.x * 8) {
-    const long long b = i / pred_bstride;
-    u16* x = img + b * img_bstride + (i - b * pred_bstride);
-    float fi[8], fp[8];
-    unpack8(*(const uint4*)x, fi);
-    unpack8(*(const uint4*)(pred + i), fp);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) fi[j] += rbf(dt * fp[j]);
-    *(uint4*)x = pack8(fi);
-  }
-}
-// The Euler step of an image stream WIDER than the prediction (FLUX.1 Fill / Depth / Canny: step-invariant conditioning channels ride behind
-// the noisy channels of every token and are never stepped): channels [0, c_out) of every row of img [rows, c_in] += bf16(dt * pred),
-// pred [rows, c_out].  Same arithmetic as euler_kernel.  One thread per 16-byte vector, vectors numbered along pred (dense): the c_out / 8
-// lanes of one row read one contiguous c_out * 2-byte segment of img (128 B at c_out = 64) and the next row's segment starts c_in * 2 bytes
-// further on, so every wave touches 8 full segments and pred in one contiguous KiB.  The conditioning channels are neither read nor written.
-__global__ void __launch_bounds__(256) euler_cols_kernel(u16* __restrict__ img, const u16* __restrict__ pred, const float* __restrict__ dts,
-                                                         const int* __restrict__ step, long long n_vec, int vec_per_row, int c_in) {
-  const float dt = dts[*step];
-  for (long long v = (long long)blockIdx.x * blockDim.x + threadIdx.x; v < n_vec; v += (long long)gridDim.x * blockDim.x) {
-    const long long r = v / vec_per_row;
-    u16* x = img + r * c_in + (v - r * vec_per_row) * 8;
-    float fi[8], fp[8];
-    unpack8(*(const uint4*)x, fi);
-    unpack8(*(const uint4*)(pred + v * 8), fp);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) fi[j] += rbf(dt * fp[j]);
-    *(uint4*)x = pack8(fi);
-  }
-}
-// The guided Euler step (true classifier-free guidance): the image stream holds 2B samples, sample b the prompt branch and sample B + b the
-// negative branch of the same image.  With c = pred[b], u = pred[B + b], x = img[b], s = *scale, dt = dts[*step]:
-//   d = bf16(c - u);  m = bf16(s * d);  p = bf16(u + m);  x' = bf16(x + bf16(dt * p));  img[b] = img[B + b] = x'
-// -- the torch expression x + dt * (u + s * (c - u)) on bf16 tensors, one rounding per operation; the last operation is euler_kernel's.  x is
-// read from the prompt half only and x' is written to both, so the halves stay bit-identical.  One thread per 16-byte vector, vectors numbered
-// along the prompt half of pred (dense).  PLAIN: the prediction is as long and as wide as the stream and the vector index is the offset; else
-// (Kontext: img_bstride > vec_per_sample rows' worth; Fill / Depth / Canny: c_in > 8 * vec_per_row) the sample and the row are divided out
-// in 32 bits, and neither the reference rows nor the conditioning channels are read or written.
-template <bool PLAIN>
-__global__ void __launch_bounds__(256) cfg_euler_kernel(u16* __restrict__ img, const u16* __restrict__ pred, const float* __restrict__ dts,
-                                                        const int* __restrict__ step, const float* __restrict__ scale, unsigned n_vec,
-                                                        unsigned vec_per_sample, unsigned vec_per_row, long long img_bstride, int c_in,
-                                                        long long img_half, long long pred_half) {
-  const float dt = dts[step ? *step : 0], sc = *scale;
-  for (unsigned v = blockIdx.x * blockDim.x + threadIdx.x; v < n_vec; v += gridDim.x * blockDim.x) {
-    long long xo = (long long)v * 8;
-    if (!PLAIN) {
-      const unsigned b = v / vec_per_sample, w = v - b * vec_per_sample, r = w / vec_per_row;
-      xo = b * img_bstride + (long long)r * c_in + (w - r * vec_per_row) * 8;
-    }
-    float fx[8], fc[8], fu[8];
-    unpack8(*(const uint4*)(img + xo), fx);
-    unpack8(*(const uint4*)(pred + (long long)v * 8), fc);
-    unpack8(*(const uint4*)(pred + pred_half + (long long)v * 8), fu);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float m = rbf(sc * rbf(fc[j] - fu[j]));
-      fx[j] += rbf(dt * rbf(fu[j] + m));
-    }
-    const uint4 o = pack8(fx);
-    *(uint4*)(img + xo) = o;
-    *(uint4*)(img + img_half + xo) = o;
-  }
-}
-// The masked-latent (inpainting) update: the Euler step (CFG: the guided one, cfg_euler_kernel's arithmetic) followed by the blend with the
-// init latent re-noised to the NEXT time.  With i = *step, dt = dts[i], tn = tnext[i], om = one_minus_tnext[i]:
-//   x1 = bf16(x + bf16(dt * v))                                      (CFG: v = bf16(u + bf16(s * bf16(c - u))))
-//   p  = bf16(bf16(tn * noise) + bf16(om * x0))
-//   x' = bf16(bf16(bf16(1 - m) * p) + bf16(m * x1))
-// -- the torch expressions x + dt * v; tn * noise + om * x0; (1 - m) * p + m * x1 on bf16 tensors, one rounding per operation, scalars fp32.
-// thr != nullptr (differential diffusion): m is replaced by (float(m) > thr[i] ? 1 : 0), compared in fp32.  x0 / noise / mask are dense like
-// the prompt half of pred; the indexing is cfg_euler_kernel's (one thread per 16-byte vector numbered along pred; PLAIN: the vector index is
-// the stream offset).  CFG: x is read from the prompt half and x' written to both; reference rows and conditioning channels are never touched.
-template <bool CFG, bool PLAIN>
-__global__ void __launch_bounds__(256) blend_euler_kernel(u16* __restrict__ img, const u16* __restrict__ pred, const u16* __restrict__ x0,
-                                                          const u16* __restrict__ noise, const u16* __restrict__ mask,
-                                                          const float* __restrict__ dts, const float* __restrict__ tnext,
-                                                          const float* __restrict__ one_minus_tnext, const float* __restrict__ thr,
-                                                          const int* __restrict__ step, const float* __restrict__ scale, unsigned n_vec,
-                                                          unsigned vec_per_sample, unsigned vec_per_row, long long img_bstride, int c_in,
-                                                          long long img_half, long long pred_half) {
-  // Every product below is rounded to bf16 BEFORE it is added.  Two of them have two bf16-valued factors (m * x1, (1 - m) * p), which the
-  // compiler may narrow to a bf16 multiply and then, contracting, fuse into the following add as an fma on the unrounded product (it did:
-  // one operand of the last sum lost its rounding).  No contraction in this kernel.
-#pragma clang fp contract(off)
-  const int i = step ? *step : 0;
-  const float dt = dts[i], tn = tnext[i], om = one_minus_tnext[i], sc = CFG ? *scale : 0.f;
-  const bool diff = thr != nullptr;
-  const float th = diff ? thr[i] : 0.f;
-  for (unsigned v = blockIdx.x * blockDim.x + threadIdx.x; v < n_vec; v += gridDim.x * blockDim.x) {
-    long long xo = (long long)v * 8;
-    if (!PLAIN) {
-      const unsigned b = v / vec_per_sample, w = v - b * vec_per_sample, r = w / vec_per_row;
-      xo = b * img_bstride + (long long)r * c_in + (w - r * vec_per_row) * 8;
-    }
-    const long long po = (long long)v * 8;
-    float fx[8], fc[8], fz[8], fn[8], fm[8];
-    unpack8(*(const uint4*)(img + xo), fx);
-    unpack8(*(const uint4*)(pred + po), fc);
-    unpack8(*(const uint4*)(x0 + po), fz);
-    unpack8(*(const uint4*)(noise + po), fn);
-    unpack8(*(const uint4*)(mask + po), fm);
-    if (CFG) {
-      float fu[8];
-      unpack8(*(const uint4*)(pred + pred_half + po), fu);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) fc[j] = rbf(fu[j] + rbf(sc * rbf(fc[j] - fu[j])));
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float x1 = rbf(fx[j] + rbf(dt * fc[j]));
-      const float p = rbf(rbf(tn * fn[j]) + rbf(om * fz[j]));
-      const float m = diff ? (fm[j] > th ? 1.f : 0.f) : fm[j];
-      fx[j] = rbf(rbf(m * x1) + rbf(rbf(1.f - m) * p));
-    }
-    const uint4 o = pack8(fx);
-    *(uint4*)(img + xo) = o;
-    if (CFG) *(uint4*)(img + img_half + xo) = o;
-  }
-}
-// fluxmi_philox_normal: the generator alone, for tests and tools.  out [B][vec_per_sample * 8]: RAW the uint32 words, else the fp32 normals.
-template <bool RAW>
-__global__ void __launch_bounds__(256) philox_normal_kernel(void* __restrict__ out, const unsigned* __restrict__ ids, unsigned n_vec,
-                                                            unsigned vec_per_sample, unsigned eval) {
-  for (unsigned v = blockIdx.x * blockDim.x + threadIdx.x; v < n_vec; v += gridDim.x * blockDim.x) {
-    const unsigned b = v / vec_per_sample, w = v - b * vec_per_sample;
-    const unsigned* id = ids + 4 * b;
-    if (RAW) {
-      unsigned r[4];
-      philox4x32_10(2 * w, eval, id[2], id[3], id[0], id[1], r);
-      ((uint4*)out)[2 * (size_t)v] = make_uint4(r[0], r[1], r[2], r[3]);
-      philox4x32_10(2 * w + 1, eval, id[2], id[3], id[0], id[1], r);
-      ((uint4*)out)[2 * (size_t)v + 1] = make_uint4(r[0], r[1], r[2], r[3]);
-    } else {
-      float z[8];
-      philox_normal8(id, w, eval, z);
-      ((float4*)out)[2 * (size_t)v] = make_float4(z[0], z[1], z[2], z[3]);
-      ((float4*)out)[2 * (size_t)v + 1] = make_float4(z[4], z[5], z[6], z[7]);
-    }
-  }
-}
-// The table-driven solver update (higher-order samplers): ONE linear update whose coefficients are device data, so the
-// engine never knows which solver runs.  Row j = *step of coef [n][8] = {cx, cs, c0, c1, c2, ga, gb, 0} and ctl [n][4] = {save_xs, w_slot,
-// h1_slot, h2_slot}; per predicted element, v = pred (CFG: cfg_euler_kernel's bf16 chain),
-//   g   = ga * x + gb * v                                                    fp32
-//   acc = cx * x + cs * xs + c0 * g + c1 * hist[h1_slot] + c2 * hist[h2_slot]   fp32, left to right
-//   x1  = bf16(acc)                                                          (BLEND: then blend_euler_kernel's tail on x1)
-// Every product and every sum is rounded to fp32 on its own: plain * and + under `fp contract(off)` stay unfused (HIP's __fmul_rn /
-// __fadd_rn are inline * / + compiled with contraction allowed, and may fuse once inlined: not used here).  A term whose coefficient is exactly
-// 0.0f or whose slot is negative is SKIPPED -- its buffer is not read, it may hold anything -- and the sum starts at the first term that
-// is present (0 when none is).  After all reads of the element: save_xs stores the pre-update x to xs, w_slot >= 0 stores g to
-// hist[w_slot] (which may be a slot just read), x' goes to img (CFG: both halves).  xs bf16 and hist fp32 [2][...] are dense like the prompt
-// half of pred; the indexing is cfg_euler_kernel's.  The row is uniform over the launch: every branch below is.
-// NOISE (fluxmi_solver_step_noise; the stochastic samplers): column 7 of the row is cn, and one last term follows the c2 term,
-//   acc = acc + (cn * z),   z = philox_normal8(ids[b], vector within the image, *step + *eval_offset)
-// b the IMAGE (CFG: one draw per image, x' goes to both halves as before).  cn == 0.0f: skipped like every absent term -- ids is not
-// read, no generator work -- so the result is the NOISE = false kernel's, which ignores column 7.
-template <bool CFG, bool PLAIN, bool BLEND, bool NOISE>
-__global__ void __launch_bounds__(256) solver_step_kernel(u16* __restrict__ img, const u16* __restrict__ pred, u16* __restrict__ xs,
-                                                          float* __restrict__ hist, const float* __restrict__ coef, const int* __restrict__ ctl,
-                                                          const u16* __restrict__ x0, const u16* __restrict__ noise, const u16* __restrict__ mask,
-                                                          const float* __restrict__ tnext, const float* __restrict__ one_minus_tnext,
-                                                          const float* __restrict__ thr, const int* __restrict__ step,
-                                                          const float* __restrict__ scale, unsigned n_vec, unsigned vec_per_sample,
-                                                          unsigned vec_per_row, long long img_bstride, int c_in, long long img_half,
-                                                          long long pred_half, const unsigned* __restrict__ ids,
-                                                          const int* __restrict__ eval_offset) {
-#pragma clang fp contract(off)
-  const int i = step ? *step : 0;
-  const float cx = coef[8 * i], cs = coef[8 * i + 1], c0 = coef[8 * i + 2], c1 = coef[8 * i + 3], c2 = coef[8 * i + 4], ga = coef[8 * i + 5],
-              gb = coef[8 * i + 6];
-  const float cn = NOISE ? coef[8 * i + 7] : 0.f;
-  const bool t_n = NOISE && cn != 0.f;
-  const unsigned eval = NOISE ? (unsigned)i + (unsigned)(eval_offset ? *eval_offset : 0) : 0u;
-  const bool save = ctl[4 * i] != 0;
-  // a slot is -1, 0 or 1: anything above is read as 1, so that no table can index past the two slots
-  const int ws = min(ctl[4 * i + 1], 1), s1 = min(ctl[4 * i + 2], 1), s2 = min(ctl[4 * i + 3], 1);
-  const bool t_x = cx != 0.f, t_s = cs != 0.f, t_g = c0 != 0.f, t_1 = c1 != 0.f && s1 >= 0, t_2 = c2 != 0.f && s2 >= 0;
-  const bool need_g = t_g || ws >= 0;
-  const long long slot = (long long)n_vec * 8;
-  const float sc = CFG ? *scale : 0.f;
-  const float tn = BLEND ? tnext[i] : 0.f, om = BLEND ? one_minus_tnext[i] : 0.f;
-  const bool diff = BLEND && thr != nullptr;
-  const float th = diff ? thr[i] : 0.f;
-  for (unsigned v = blockIdx.x * blockDim.x + threadIdx.x; v < n_vec; v += gridDim.x * blockDim.x) {
-    long long xo = (long long)v * 8;
-    if (!PLAIN) {
-      const unsigned b = v / vec_per_sample, w = v - b * vec_per_sample, r = w / vec_per_row;
-      xo = b * img_bstride + (long long)r * c_in + (w - r * vec_per_row) * 8;
-    }
-    const long long po = (long long)v * 8;
-    const uint4 xraw = *(const uint4*)(img + xo);
-    float fx[8], fv[8], fs[8], fo[8], zn[8];
-    alignas(16) float h1[8], h2[8], g[8];
-    unpack8(xraw, fx);
-    unpack8(*(const uint4*)(pred + po), fv);
-    if (CFG) {
-      float fu[8];
-      unpack8(*(const uint4*)(pred + pred_half + po), fu);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) fv[j] = rbf(fu[j] + rbf(sc * rbf(fv[j] - fu[j])));
-    }
-    if (t_n) {
-      const unsigned b = v / vec_per_sample;
-      philox_normal8(ids + 4 * b, v - b * vec_per_sample, eval, zn);
-    }
-    if (t_s) unpack8(*(const uint4*)(xs + po), fs);
-    if (t_1) {
-      *(float4*)h1 = *(const float4*)(hist + s1 * slot + po);
-      *(float4*)(h1 + 4) = *(const float4*)(hist + s1 * slot + po + 4);
-    }
-    if (t_2) {
-      *(float4*)h2 = *(const float4*)(hist + s2 * slot + po);
-      *(float4*)(h2 + 4) = *(const float4*)(hist + s2 * slot + po + 4);
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float gj = 0.f;
-      if (need_g) {
-        if (ga != 0.f) gj = (ga * fx[j]);
-        if (gb != 0.f) gj = ga != 0.f ? (gj + (gb * fv[j])) : (gb * fv[j]);
-      }
-      g[j] = gj;
-      float acc = 0.f;
-      bool have = false;
-      if (t_x) { acc = (cx * fx[j]); have = true; }
-      if (t_s) { const float t = (cs * fs[j]); acc = have ? (acc + t) : t; have = true; }
-      if (t_g) { const float t = (c0 * gj); acc = have ? (acc + t) : t; have = true; }
-      if (t_1) { const float t = (c1 * h1[j]); acc = have ? (acc + t) : t; have = true; }
-      if (t_2) { const float t = (c2 * h2[j]); acc = have ? (acc + t) : t; have = true; }
-      if (t_n) { const float t = (cn * zn[j]); acc = have ? (acc + t) : t; have = true; }
-      fo[j] = rbf(acc);
-    }
-    if (BLEND) {
-      float fz[8], fn[8], fm[8];
-      unpack8(*(const uint4*)(x0 + po), fz);
-      unpack8(*(const uint4*)(noise + po), fn);
-      unpack8(*(const uint4*)(mask + po), fm);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float p = rbf(rbf(tn * fn[j]) + rbf(om * fz[j]));
-        const float m = diff ? (fm[j] > th ? 1.f : 0.f) : fm[j];
-        fo[j] = rbf(rbf(m * fo[j]) + rbf(rbf(1.f - m) * p));
-      }
-    }
-    if (save) *(uint4*)(xs + po) = xraw;
-    if (ws >= 0) {
-      *(float4*)(hist + ws * slot + po) = *(const float4*)g;
-      *(float4*)(hist + ws * slot + po + 4) = *(const float4*)(g + 4);
-    }
-    const uint4 o = pack8(fo);
-    *(uint4*)(img + xo) = o;
-    if (CFG) *(uint4*)(img + img_half + xo) = o;
-  }
-}
 // per-step scalars kept on the device so that one captured graph serves every step:
 //   t_vec[b] = bf16(ts[*step]),  then ++*step happens in advance_step_kernel at the end of the step.
 __global__ void set_timestep_kernel(u16* __restrict__ t_vec, const float* __restrict__ ts, const int* __restrict__ step, int B) {
@@ -821,12 +547,6 @@ __global__ void __launch_bounds__(256) lora_delta_kernel(const float* __restrict
   acc *= scale;
   float* d = delta + (long long)n * K + k;
   *d = accumulate ? (*d + acc) : acc;
-}
-
-inline int grid_for(long long work_items, int block = 256, int cap = 256 * 16) {
-  long long g = (work_items + block - 1) / block;
-  if (g < 1) g = 1;
-  return (int)(g > cap ? cap : g);
 }
 
 }  // namespace
@@ -1075,149 +795,6 @@ int fluxmi_k_rope_table(const void* ids, const float* omega, const int* axis, vo
   return 0;
 }
 
-int fluxmi_k_euler(void* img, const void* pred, const float* dts, const int* step, long long n, hipStream_t s) {
-  FLUXMI_REQUIRE(n % 8 == 0, "euler: n must be a multiple of 8");
-  if (n == 0) return 0;
-  hipLaunchKernelGGL(euler_kernel, dim3(grid_for(n / 8)), dim3(256), 0, s, (u16*)img, (const u16*)pred, dts, step, n);
-  FLUXMI_LAUNCH_CHECK();
-  return 0;
-}
-int fluxmi_k_euler_rows(void* img, const void* pred, const float* dts, const int* step, int B, long long img_rows, long long pred_rows, int C,
-                        hipStream_t s) {
-  FLUXMI_REQUIRE(step && B >= 0 && C > 0 && C % 8 == 0 && pred_rows >= 0 && pred_rows <= img_rows,
-                 "euler_rows: bad shape B=%d img_rows=%lld pred_rows=%lld C=%d (C %% 8 == 0, pred_rows <= img_rows)", B, img_rows, pred_rows, C);
-  const long long n = (long long)B * pred_rows * C;
-  if (n == 0) return 0;
-  hipLaunchKernelGGL(euler_rows_kernel, dim3(grid_for(n / 8)), dim3(256), 0, s, (u16*)img, (const u16*)pred, dts, step, n, pred_rows * C,
-                     img_rows * C);
-  FLUXMI_LAUNCH_CHECK();
-  return 0;
-}
-int fluxmi_k_euler_cols(void* img, const void* pred, const float* dts, const int* step, long long rows, int c_in, int c_out, hipStream_t s) {
-  FLUXMI_REQUIRE(step && rows >= 0 && c_out > 0 && c_out % 8 == 0 && c_in % 8 == 0 && c_out <= c_in,
-                 "euler_cols: bad shape rows=%lld c_in=%d c_out=%d (multiples of 8, c_out <= c_in)", rows, c_in, c_out);
-  const long long n_vec = rows * (c_out / 8);
-  if (n_vec == 0) return 0;
-  hipLaunchKernelGGL(euler_cols_kernel, dim3(grid_for(n_vec)), dim3(256), 0, s, (u16*)img, (const u16*)pred, dts, step, n_vec, c_out / 8, c_in);
-  FLUXMI_LAUNCH_CHECK();
-  return 0;
-}
-int fluxmi_k_cfg_euler(void* img, const void* pred, const float* dts, const int* step, const float* scale, int B, long long img_rows,
-                       long long pred_rows, int c_in, int c_out, hipStream_t s) {
-  FLUXMI_REQUIRE(img && pred && dts && scale, "cfg_euler: NULL argument");
-  FLUXMI_REQUIRE(B >= 0 && c_out > 0 && c_out % 8 == 0 && c_in % 8 == 0 && c_out <= c_in && pred_rows >= 0 && pred_rows <= img_rows &&
-                     (c_in == c_out || pred_rows == img_rows),
-                 "cfg_euler: bad shape B=%d img_rows=%lld pred_rows=%lld c_in=%d c_out=%d (channels multiples of 8, c_out <= c_in, pred_rows <= "
-                 "img_rows, not both shorter and narrower)", B, img_rows, pred_rows, c_in, c_out);
-  const long long n_vec = (long long)B * pred_rows * (c_out / 8);
-  FLUXMI_REQUIRE(n_vec <= 0x7fffffffLL, "cfg_euler: %lld vectors exceed the kernel's 32-bit index", n_vec);
-  if (n_vec == 0) return 0;
-  const long long img_bstride = img_rows * c_in, img_half = (long long)B * img_bstride, pred_half = n_vec * 8;
-  const unsigned vps = (unsigned)(pred_rows * (c_out / 8));
-  if (c_in == c_out && pred_rows == img_rows)
-    hipLaunchKernelGGL(cfg_euler_kernel<true>, dim3(grid_for(n_vec)), dim3(256), 0, s, (u16*)img, (const u16*)pred, dts, step, scale,
-                       (unsigned)n_vec, vps, (unsigned)(c_out / 8), img_bstride, c_in, img_half, pred_half);
-  else
-    hipLaunchKernelGGL(cfg_euler_kernel<false>, dim3(grid_for(n_vec)), dim3(256), 0, s, (u16*)img, (const u16*)pred, dts, step, scale,
-                       (unsigned)n_vec, vps, (unsigned)(c_out / 8), img_bstride, c_in, img_half, pred_half);
-  FLUXMI_LAUNCH_CHECK();
-  return 0;
-}
-int fluxmi_k_blend_euler(void* img, const void* pred, const void* x0, const void* noise, const void* mask, const float* dts, const float* tnext,
-                         const float* one_minus_tnext, const float* thr, const int* step, const float* scale, int B, long long img_rows,
-                         long long pred_rows, int c_in, int c_out, hipStream_t s) {
-  FLUXMI_REQUIRE(img && pred && x0 && noise && mask && dts && tnext && one_minus_tnext, "blend_euler: NULL argument");
-  FLUXMI_REQUIRE(B >= 0 && c_out > 0 && c_out % 8 == 0 && c_in % 8 == 0 && c_out <= c_in && pred_rows >= 0 && pred_rows <= img_rows &&
-                     (c_in == c_out || pred_rows == img_rows),
-                 "blend_euler: bad shape B=%d img_rows=%lld pred_rows=%lld c_in=%d c_out=%d (channels multiples of 8, c_out <= c_in, pred_rows <= "
-                 "img_rows, not both shorter and narrower)", B, img_rows, pred_rows, c_in, c_out);
-  const long long n_vec = (long long)B * pred_rows * (c_out / 8);
-  FLUXMI_REQUIRE(n_vec <= 0x7fffffffLL, "blend_euler: %lld vectors exceed the kernel's 32-bit index", n_vec);
-  if (n_vec == 0) return 0;
-  const long long img_bstride = img_rows * c_in, img_half = (long long)B * img_bstride, pred_half = n_vec * 8;
-  const unsigned vps = (unsigned)(pred_rows * (c_out / 8));
-  const bool plain = c_in == c_out && pred_rows == img_rows;
-#define FLUXMI_BLEND_LAUNCH(CFG, PLAIN)                                                                                                       \
-  hipLaunchKernelGGL((blend_euler_kernel<CFG, PLAIN>), dim3(grid_for(n_vec)), dim3(256), 0, s, (u16*)img, (const u16*)pred, (const u16*)x0, \
-                     (const u16*)noise, (const u16*)mask, dts, tnext, one_minus_tnext, thr, step, scale, (unsigned)n_vec, vps,                \
-                     (unsigned)(c_out / 8), img_bstride, c_in, img_half, pred_half)
-  if (scale) {
-    if (plain) FLUXMI_BLEND_LAUNCH(true, true); else FLUXMI_BLEND_LAUNCH(true, false);
-  } else {
-    if (plain) FLUXMI_BLEND_LAUNCH(false, true); else FLUXMI_BLEND_LAUNCH(false, false);
-  }
-#undef FLUXMI_BLEND_LAUNCH
-  FLUXMI_LAUNCH_CHECK();
-  return 0;
-}
-// the launcher of fluxmi_k_solver_step (ids == NULL: the deterministic kernel, column 7 ignored) and fluxmi_k_solver_step_noise
-static int solver_step_launch(void* img, const void* pred, void* xs, float* hist, const float* coef, const int* ctl, const void* x0,
-                              const void* noise, const void* mask, const float* tnext, const float* one_minus_tnext, const float* thr,
-                              const int* step, const float* scale, int B, long long img_rows, long long pred_rows, int c_in, int c_out,
-                              const unsigned* ids, const int* eval_offset, hipStream_t s) {
-  FLUXMI_REQUIRE(img && pred && xs && hist && coef && ctl, "solver_step: NULL argument");
-  FLUXMI_REQUIRE(!x0 || (noise && mask && tnext && one_minus_tnext), "solver_step: NULL argument (x0, noise, mask, tnext and one_minus_tnext go "
-                 "together)");
-  FLUXMI_REQUIRE(B >= 0 && c_out > 0 && c_out % 8 == 0 && c_in % 8 == 0 && c_out <= c_in && pred_rows >= 0 && pred_rows <= img_rows &&
-                     (c_in == c_out || pred_rows == img_rows),
-                 "solver_step: bad shape B=%d img_rows=%lld pred_rows=%lld c_in=%d c_out=%d (channels multiples of 8, c_out <= c_in, pred_rows <= "
-                 "img_rows, not both shorter and narrower)", B, img_rows, pred_rows, c_in, c_out);
-  const long long n_vec = (long long)B * pred_rows * (c_out / 8);
-  FLUXMI_REQUIRE(n_vec <= 0x7fffffffLL, "solver_step: %lld vectors exceed the kernel's 32-bit index", n_vec);
-  if (n_vec == 0) return 0;
-  const long long img_bstride = img_rows * c_in, img_half = (long long)B * img_bstride, pred_half = n_vec * 8;
-  const unsigned vps = (unsigned)(pred_rows * (c_out / 8));
-  const bool plain = c_in == c_out && pred_rows == img_rows;
-#define FLUXMI_SOLVER_LAUNCH(CFG, PLAIN, BLEND, NOISE)                                                                                          \
-  hipLaunchKernelGGL((solver_step_kernel<CFG, PLAIN, BLEND, NOISE>), dim3(grid_for(n_vec)), dim3(256), 0, s, (u16*)img, (const u16*)pred,       \
-                     (u16*)xs, hist, coef, ctl, (const u16*)x0, (const u16*)noise, (const u16*)mask, tnext, one_minus_tnext, thr, step, scale, \
-                     (unsigned)n_vec, vps, (unsigned)(c_out / 8), img_bstride, c_in, img_half, pred_half, ids, eval_offset)
-#define FLUXMI_SOLVER_LAUNCH3(CFG, PLAIN, BLEND) \
-  do { if (ids) FLUXMI_SOLVER_LAUNCH(CFG, PLAIN, BLEND, true); else FLUXMI_SOLVER_LAUNCH(CFG, PLAIN, BLEND, false); } while (0)
-#define FLUXMI_SOLVER_LAUNCH2(CFG, PLAIN) \
-  do { if (x0) FLUXMI_SOLVER_LAUNCH3(CFG, PLAIN, true); else FLUXMI_SOLVER_LAUNCH3(CFG, PLAIN, false); } while (0)
-  if (scale) {
-    if (plain) FLUXMI_SOLVER_LAUNCH2(true, true); else FLUXMI_SOLVER_LAUNCH2(true, false);
-  } else {
-    if (plain) FLUXMI_SOLVER_LAUNCH2(false, true); else FLUXMI_SOLVER_LAUNCH2(false, false);
-  }
-#undef FLUXMI_SOLVER_LAUNCH2
-#undef FLUXMI_SOLVER_LAUNCH3
-#undef FLUXMI_SOLVER_LAUNCH
-  FLUXMI_LAUNCH_CHECK();
-  return 0;
-}
-int fluxmi_k_solver_step(void* img, const void* pred, void* xs, float* hist, const float* coef, const int* ctl, const void* x0, const void* noise,
-                         const void* mask, const float* tnext, const float* one_minus_tnext, const float* thr, const int* step,
-                         const float* scale, int B, long long img_rows, long long pred_rows, int c_in, int c_out, hipStream_t s) {
-  return solver_step_launch(img, pred, xs, hist, coef, ctl, x0, noise, mask, tnext, one_minus_tnext, thr, step, scale, B, img_rows, pred_rows,
-                            c_in, c_out, nullptr, nullptr, s);
-}
-// ids is read by the kernel only where a row's cn != 0, but which row runs is device data: the host cannot tell, so it is always required
-int fluxmi_k_solver_step_noise(void* img, const void* pred, void* xs, float* hist, const float* coef, const int* ctl, const void* x0,
-                               const void* noise, const void* mask, const float* tnext, const float* one_minus_tnext, const float* thr,
-                               const int* step, const float* scale, int B, long long img_rows, long long pred_rows, int c_in, int c_out,
-                               const unsigned* ids, const int* eval_offset, hipStream_t s) {
-  FLUXMI_REQUIRE(ids, "solver_step_noise: NULL ids (one {key_lo, key_hi, c2, c3} per image; fluxmi_solver_step is the update without noise)");
-  return solver_step_launch(img, pred, xs, hist, coef, ctl, x0, noise, mask, tnext, one_minus_tnext, thr, step, scale, B, img_rows, pred_rows,
-                            c_in, c_out, ids, eval_offset, s);
-}
-int fluxmi_k_philox_normal(void* out, const unsigned* ids, int B, long long n_per_image, unsigned eval, int raw, hipStream_t s) {
-  FLUXMI_REQUIRE(out && ids, "philox_normal: NULL argument");
-  FLUXMI_REQUIRE(B >= 0 && n_per_image >= 0 && n_per_image % 8 == 0 && (raw == 0 || raw == 1),
-                 "philox_normal: bad shape B=%d n_per_image=%lld raw=%d (n_per_image a multiple of 8, raw 0 or 1)", B, n_per_image, raw);
-  const long long n_vec = (long long)B * (n_per_image / 8);
-  FLUXMI_REQUIRE(n_vec <= 0x7fffffffLL, "philox_normal: %lld vectors exceed the kernel's 32-bit index", n_vec);
-  if (n_vec == 0) return 0;
-  if (raw)
-    hipLaunchKernelGGL((philox_normal_kernel<true>), dim3(grid_for(n_vec)), dim3(256), 0, s, out, ids, (unsigned)n_vec,
-                       (unsigned)(n_per_image / 8), eval);
-  else
-    hipLaunchKernelGGL((philox_normal_kernel<false>), dim3(grid_for(n_vec)), dim3(256), 0, s, out, ids, (unsigned)n_vec,
-                       (unsigned)(n_per_image / 8), eval);
-  FLUXMI_LAUNCH_CHECK();
-  return 0;
-}
 int fluxmi_k_set_timestep(void* t_vec, const float* ts, const int* step, int B, hipStream_t s) {
   FLUXMI_REQUIRE(B <= 64, "set_timestep: batch %d > 64", B);
   hipLaunchKernelGGL(set_timestep_kernel, dim3(1), dim3(64), 0, s, (u16*)t_vec, ts, step, B);

@@ -350,9 +350,8 @@ int update_launch(E* e, const Request& rq, hipStream_t st) {
     return fluxmi_k_blend_euler(img_s, pred_s, ix0, inoise, imask, e->d_dts, e->d_tnext, e->d_omt, thr, e->d_step, scale, rq.images, Li, e->Lpred, C,
                                 Co, st);
   if (rq.cfg()) return fluxmi_k_cfg_euler(img_s, pred_s, e->d_dts, e->d_step, e->d_cfg, rq.images, Li, e->Lpred, C, Co, st);
-  if (Co != C) return fluxmi_k_euler_cols(img_s, pred_s, e->d_dts, e->d_step, (long long)B * Li, C, Co, st);
-  if (e->Lpred == Li) return fluxmi_k_euler(img_s, pred_s, e->d_dts, e->d_step, (long long)B * Li * C, st);
-  return fluxmi_k_euler_rows(img_s, pred_s, e->d_dts, e->d_step, B, Li, e->Lpred, C, st);
+  return fluxmi_k_euler_step("euler", img_s, pred_s, nullptr, nullptr, nullptr, e->d_dts, nullptr, nullptr, nullptr, e->d_step, nullptr, B, Li,
+                             e->Lpred, C, Co, st);
 }
 
 // The plain step: one piece -- the forward, the update, the step counter -- and one hipGraphLaunch per replayed step.

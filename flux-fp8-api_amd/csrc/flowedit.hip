@@ -17,13 +17,9 @@
 #include "common.h"
 #include "fluxmi_internal.h"
 #include "philox.h"
+#include "stream_view.h"
 
 namespace {
-
-inline int fe_grid(long long n_vec) {
-  const long long g = (n_vec + 255) / 256;
-  return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
-}
 
 template <bool STEP>
 __global__ void __launch_bounds__(256) flowedit_kernel(u16* __restrict__ img, const u16* __restrict__ pred, u16* __restrict__ z,
@@ -32,7 +28,7 @@ __global__ void __launch_bounds__(256) flowedit_kernel(u16* __restrict__ img, co
                                                        const unsigned* __restrict__ ids, const int* __restrict__ eval_offset, float t_arg,
                                                        float omt_arg, unsigned eval_arg, unsigned n_vec, unsigned vec_per_sample,
                                                        long long half) {
-  // every product is rounded before it is added (blend_euler_kernel has the story of the fused bf16 multiply-add): no contraction here
+  // every product is rounded before it is added (euler_kernel has the story of the fused bf16 multiply-add): no contraction here
 #pragma clang fp contract(off)
   float w = 0.f, dt = 0.f, t = t_arg, omt = omt_arg;
   bool first = true, apply = true;
@@ -109,7 +105,7 @@ int fluxmi_k_flowedit_couple(void* img, const void* z, const void* x0, float t, 
   unsigned vps;
   FLUXMI_TRY(fe_shape("flowedit_couple", B, img_rows, pred_rows, c_in, c_out, &n_vec, &vps));
   if (n_vec == 0) return 0;
-  hipLaunchKernelGGL((flowedit_kernel<false>), dim3(fe_grid(n_vec)), dim3(256), 0, s, (u16*)img, (const u16*)nullptr, (u16*)z, (float*)nullptr,
+  hipLaunchKernelGGL((flowedit_kernel<false>), dim3(grid_for(n_vec)), dim3(256), 0, s, (u16*)img, (const u16*)nullptr, (u16*)z, (float*)nullptr,
                      (const u16*)x0, (const float*)nullptr, (const int*)nullptr, (const int*)nullptr, ids, (const int*)nullptr, t, one_minus_t,
                      eval, (unsigned)n_vec, vps, n_vec * 8);
   FLUXMI_LAUNCH_CHECK();
@@ -125,7 +121,7 @@ int fluxmi_k_flowedit_step(void* img, const void* pred, void* z, float* acc, con
   unsigned vps;
   FLUXMI_TRY(fe_shape("flowedit_step", B, img_rows, pred_rows, c_in, c_out, &n_vec, &vps));
   if (n_vec == 0) return 0;
-  hipLaunchKernelGGL((flowedit_kernel<true>), dim3(fe_grid(n_vec)), dim3(256), 0, s, (u16*)img, (const u16*)pred, (u16*)z, acc, (const u16*)x0,
+  hipLaunchKernelGGL((flowedit_kernel<true>), dim3(grid_for(n_vec)), dim3(256), 0, s, (u16*)img, (const u16*)pred, (u16*)z, acc, (const u16*)x0,
                      coef, ctl, step, ids, eval_offset, 0.f, 0.f, 0u, (unsigned)n_vec, vps, n_vec * 8);
   FLUXMI_LAUNCH_CHECK();
   return 0;

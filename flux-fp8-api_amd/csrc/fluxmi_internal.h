@@ -152,13 +152,15 @@ int fluxmi_k_timestep_rows(void* t_rows, const float* ts, int step0, int B, int 
 int fluxmi_k_fill_bf16(void* dst, float v, int n, hipStream_t s);
 int fluxmi_k_timestep_embedding(const void* t, const float* freqs, void* out, int B, int half, float time_factor, hipStream_t s);
 int fluxmi_k_rope_table(const void* ids, const float* omega, const int* axis, void* pe, long long rows, int n_axes, int pairs, hipStream_t s);
+// The update kernels (update_step.hip).  The flat Euler step img [n] += bf16(dts[*step] * pred [n]), any n % 8 == 0
 int fluxmi_k_euler(void* img, const void* pred, const float* dts, const int* step, long long n, hipStream_t s);
-// rows [0, pred_rows) of each sample of img [B, img_rows, C] += bf16(dts[*step] * pred [B, pred_rows, C]) (FLUX.1 Kontext: the reference rows stay)
-int fluxmi_k_euler_rows(void* img, const void* pred, const float* dts, const int* step, int B, long long img_rows, long long pred_rows, int C,
-                        hipStream_t s);
-// channels [0, c_out) of every row of img [rows, c_in] += bf16(dts[*step] * pred [rows, c_out]) (FLUX.1 Fill / Depth / Canny: the conditioning
-// channels stay)
-int fluxmi_k_euler_cols(void* img, const void* pred, const float* dts, const int* step, long long rows, int c_in, int c_out, hipStream_t s);
+// ... and every Euler step of a shaped stream, ONE kernel: the leading pred_rows rows of each sample (FLUX.1 Kontext: the reference rows
+// stay) and the leading c_out channels of every row (Fill / Depth / Canny: the conditioning channels stay) of img [B, img_rows, c_in] +=
+// bf16(dts[*step] * v), v = pred [B, pred_rows, c_out].  scale != NULL is the guided step and x0 != NULL appends the inpainting blend, both as
+// below; `who` names the caller in a refusal.  The two entries below are this one behind their own NULL-argument checks
+int fluxmi_k_euler_step(const char* who, void* img, const void* pred, const void* x0, const void* noise, const void* mask, const float* dts,
+                        const float* tnext, const float* one_minus_tnext, const float* thr, const int* step, const float* scale, int B,
+                        long long img_rows, long long pred_rows, int c_in, int c_out, hipStream_t s);
 // the guided Euler step (true CFG): img [2B, img_rows, c_in], pred [2B, pred_rows, c_out], prompt branch first; both halves of img get
 // x + bf16(dt * (u + s (c - u))) with one bf16 rounding per operation, s = *scale (device), dt = dts[*step]
 int fluxmi_k_cfg_euler(void* img, const void* pred, const float* dts, const int* step, const float* scale, int B, long long img_rows,

@@ -1,4 +1,4 @@
-// fluxmi -- the counter-based Gaussian generator shared by every kernel that draws noise (elementwise.hip: the stochastic samplers'
+// fluxmi -- the counter-based Gaussian generator shared by every kernel that draws noise (update_step.hip: the stochastic samplers'
 // solver update and fluxmi_philox_normal; flowedit.hip: FlowEdit's coupling).  Device functions only: each includer inlines the same code,
 // so the bits are the same from every kernel.
 #pragma once

@@ -7,7 +7,7 @@
 // Cartesian grid, so placement and blend weights are separable: Ny fp32 [ny][Hc], Nx fp32 [nx][Wc], normalised per canvas position by the host
 // (fluxmi/windows.py) and zero outside their window.  Per canvas element, with dt = dts[*step]:
 //   v_k  = pred[s_k]                                                            unguided
-//          cfg_euler_kernel's bf16 chain d, m, p on (pred[s_k], pred[S + s_k])   guided (scale != NULL)
+//          guided_chain8 (stream_view.h) of (pred[s_k], pred[S + s_k])           guided (scale != NULL)
 //   wgt  = Ny[a][r] * Nx[b][c]                                                   fp32, rounded
 //   num  = sum over the covering windows, ascending (a, b), of wgt * v_k         fp32, product and sum each rounded (no fma)
 //   vbar = bf16(num);   x' = bf16(x + bf16(dt * vbar))                           (euler_kernel's last operation)
@@ -17,13 +17,9 @@
 // no two threads touch one address.  No LDS, no atomics.
 #include "common.h"
 #include "fluxmi_internal.h"
+#include "stream_view.h"
 
 namespace {
-
-inline int win_grid(long long n_vec) {
-  const long long g = (n_vec + 255) / 256;
-  return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
-}
 
 template <bool STEP>
 __global__ void __launch_bounds__(256) window_step_kernel(u16* __restrict__ x, u16* __restrict__ img, const u16* __restrict__ pred,
@@ -32,7 +28,7 @@ __global__ void __launch_bounds__(256) window_step_kernel(u16* __restrict__ x, u
                                                           const int* __restrict__ col0, const float* __restrict__ Ny,
                                                           const float* __restrict__ Nx, unsigned n_vec, int Hc, int Wc, int h, int w, int ny,
                                                           int nx, int vec_per_tok, long long half, bool guided) {
-  // every product is rounded before it is added (blend_euler_kernel has the story of the fused bf16 multiply-add): no contraction here
+  // every product is rounded before it is added (euler_kernel has the story of the fused bf16 multiply-add): no contraction here
 #pragma clang fp contract(off)
   float dt = 0.f, sc = 0.f;
   if (STEP) {
@@ -63,8 +59,7 @@ __global__ void __launch_bounds__(256) window_step_kernel(u16* __restrict__ x, u
           if (guided) {
             float fu[8];
             unpack8(*(const uint4*)(pred + half + po), fu);
-#pragma unroll
-            for (int k = 0; k < 8; ++k) fv[k] = rbf(fu[k] + rbf(sc * rbf(fv[k] - fu[k])));
+            guided_chain8(fv, fu, sc);
           }
 #pragma unroll
           for (int k = 0; k < 8; ++k) {
@@ -116,7 +111,7 @@ int fluxmi_k_window_gather(const void* canvas, void* img, const int* row0, const
   long long n_vec, half;
   FLUXMI_TRY(win_shape("window_gather", N, Hc, Wc, h, w, ny, nx, C, guided != 0, &n_vec, &half));
   if (n_vec == 0) return 0;
-  hipLaunchKernelGGL((window_step_kernel<false>), dim3(win_grid(n_vec)), dim3(256), 0, s, (u16*)canvas, (u16*)img, (const u16*)nullptr,
+  hipLaunchKernelGGL((window_step_kernel<false>), dim3(grid_for(n_vec)), dim3(256), 0, s, (u16*)canvas, (u16*)img, (const u16*)nullptr,
                      (const float*)nullptr, (const int*)nullptr, (const float*)nullptr, row0, col0, (const float*)nullptr, (const float*)nullptr,
                      (unsigned)n_vec, Hc, Wc, h, w, ny, nx, C / 8, half, guided != 0);
   FLUXMI_LAUNCH_CHECK();
@@ -132,7 +127,7 @@ int fluxmi_k_window_step(void* canvas, void* img, const void* pred, const float*
   long long n_vec, half;
   FLUXMI_TRY(win_shape("window_step", N, Hc, Wc, h, w, ny, nx, C, scale != nullptr, &n_vec, &half));
   if (n_vec == 0) return 0;
-  hipLaunchKernelGGL((window_step_kernel<true>), dim3(win_grid(n_vec)), dim3(256), 0, s, (u16*)canvas, (u16*)img, (const u16*)pred, dts, step,
+  hipLaunchKernelGGL((window_step_kernel<true>), dim3(grid_for(n_vec)), dim3(256), 0, s, (u16*)canvas, (u16*)img, (const u16*)pred, dts, step,
                      scale, row0, col0, Ny, Nx, (unsigned)n_vec, Hc, Wc, h, w, ny, nx, C / 8, half, scale != nullptr);
   FLUXMI_LAUNCH_CHECK();
   return 0;

@@ -1,4 +1,4 @@
-"""Higher-order samplers as PROGRAMS for the engine's table-driven update (csrc/elementwise.hip, solver_step_kernel).
+"""Higher-order samplers as PROGRAMS for the engine's table-driven update (csrc/update_step.hip, solver_step_kernel).
 
 The engine knows one linear update per model evaluation j,
 

@@ -812,7 +812,7 @@ class Flux(nn.Module):
         token and is never stepped; the return value is the stepped [B, Li, out_channels] tokens.
         True classifier-free guidance: with `neg_txt` [1 or B, Lt, ctx] / `neg_y` [1 or B, vec] (both or neither; the prompt's Lt) every step
         predicts both branches in ONE forward on 2B samples (prompt branches first, ids and conditioning duplicated) and steps the shared
-        latent with `u + cfg_scale * (c - u)` (csrc/elementwise.hip, cfg_euler_kernel); any `cfg_scale` is taken as given.  At most 16 images
+        latent with `u + cfg_scale * (c - u)` (csrc/update_step.hip, the guided arm of euler_kernel); any `cfg_scale` is taken as given.  At most 16 images
         per pass then, more run as equal passes (frozen scales only); the two branches of an image always share a pass.
         First-block step caching: `cache_threshold` > 0 lets a frozen step whose first double block's residual moved by less than that
         (relative L1, per sample; every sample of the pass must agree) reuse the remaining blocks' residual of the last full step instead of
@@ -822,7 +822,7 @@ class Flux(nn.Module):
         call takes [2 or 2B, ...]: the tables of the prompt branches, then those of the negative branches.  None = dense, today's call.
         Masked-latent inpainting: `inpaint_x0` (the init image's latent tokens) and `inpaint_noise` (the request's pure noise draw), both
         [B, Li, out_channels], and `inpaint_mask` [1 or B, Li, out_channels] (1 = regenerate, 0 = keep), all three or none.  Every step's
-        update -- calibrating, replayed, cached, guided -- is then followed, in the same kernel (csrc/elementwise.hip, blend_euler_kernel), by
+        update -- calibrating, replayed, cached, guided -- is then followed, in the same kernel (csrc/update_step.hip, the BLEND arms of euler_kernel), by
             p = t_next * noise + (1.0 - t_next) * x0;  x' = (1 - m) * p + m * x1
         on bf16 tensors, t_next = timesteps[i + 1]: with a schedule that ends at 0 the kept elements of the result are x0 bit for bit.
         `inpaint_thresholds` (differential diffusion): one float per step of THIS call; step i blends with the binary mask
@@ -831,7 +831,7 @@ class Flux(nn.Module):
         residual adds, then the update the request already had -- one captured graph per frozen step once BOTH nets are calibrated; a guided
         request controls both branches.  Refused with a Kontext reference, attn_groups, cache_threshold > 0 and channel-conditioned models.
         `solver`: a fluxmi.solvers.SolverProgram built from `timesteps` (build_program): every update -- calibrating, replayed, guided,
-        masked -- is then the table-driven kernel (csrc/elementwise.hip, solver_step_kernel) on the program's rows, one engine step per model
+        masked -- is then the table-driven kernel (csrc/update_step.hip, solver_step_kernel) on the program's rows, one engine step per model
         EVALUATION at `solver.times`; `inpaint_thresholds` stays one per user step and is expanded through `solver.step_of_eval`.  Refused
         with cache_threshold > 0: the cache compares consecutive evaluations, and Heun evaluates one time twice.  None = today's call.
         `solver_noise` = (ids, eval_offset) goes with a program that draws noise (fluxmi.solvers.STOCHASTIC_SAMPLERS; a non-zero cn): ids

@@ -5,7 +5,7 @@
     x' = (1 - m) * p + m * x1
 
 on bf16 tensors with python scalars (every operation rounds to bf16 once, the scalars enter as fp32), and the same thing as an explicit fp32
-model with the roundings written out (csrc/elementwise.hip, blend_euler_kernel)."""
+model with the roundings written out (csrc/update_step.hip, the BLEND arms of euler_kernel)."""
 import torch
 
 

@@ -9,7 +9,7 @@ A term whose coefficient is exactly 0 (as the arithmetic sees it) or whose slot 
 the first term present.  Then save_xs stores the PRE-update x to xs, w_slot >= 0 stores g to hist[w_slot], and x' = acc.
 
 exact=True: float64 tensors, no rounding -- the mathematics of the program.
-exact=False: the kernel's arithmetic (csrc/elementwise.hip, solver_step_kernel) restated: x, v, xs bf16, hist fp32, the coefficients cast to
+exact=False: the kernel's arithmetic (csrc/update_step.hip, solver_step_kernel) restated: x, v, xs bf16, hist fp32, the coefficients cast to
 fp32; torch.mul and torch.add on fp32 tensors are separate operations, one rounding each (no fma); x1 = bf16(acc).  The guided chain and the
 blend tail are inpaint_util.blend_step's expressions (bf16 tensors, python scalars)."""
 import torch

@@ -7,7 +7,7 @@ image b's dense block belongs to block q = e // 4: counter (q, eval, ids[b][2], 
     u = ((w_even >> 9) + 0.5) * 2^-23 in (0, 1),   t = (w_odd >> 8) * 2^-24 in [0, 1)         (both exact in fp32)
     r = sqrt(-2 log u),   z = r cos(2 pi t), r sin(2 pi t)   from (w0, w1), then from (w2, w3)
 
-apply_row restates solver_step_kernel's NOISE form (csrc/elementwise.hip): fp32 products and sums one by one, left to right, the noise term
+apply_row restates solver_step_kernel's NOISE form (csrc/update_step.hip): fp32 products and sums one by one, left to right, the noise term
 cn * z last, one bf16 store, then the blend."""
 import numpy as np
 import torch

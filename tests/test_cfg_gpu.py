@@ -3,7 +3,7 @@ first and the negative branches of the same images behind them; every step is on
 
     x' = x + (t_prev - t_curr) * (u + s * (c - u))          c = pred[:B], u = pred[B:], every operation rounded to bf16 once,
 
-written to both halves (csrc/elementwise.hip, cfg_euler_kernel).  The oracle needs no change: a guided step is FluxOracle.forward on the 2B
+written to both halves (csrc/update_step.hip, the guided arm of euler_kernel).  The oracle needs no change: a guided step is FluxOracle.forward on the 2B
 batch followed by that torch expression.  Helpers are those of tests/test_fill_gpu.py / tests/test_kontext_gpu.py, copied."""
 import ctypes as C
 import io
@@ -192,6 +192,38 @@ def test_cfg_euler_kernel_bit_exact(dev, layout, B):
     assert torch.equal(img[:B, :Rp, :Co], want)
     with pytest.raises(RuntimeError, match="cfg_euler: bad shape"):
         _lib.call("fluxmi_cfg_euler", ops._p(img), ops._p(pred), ops._p(d_dts), None, ops._p(d_scale), B, Rp, R + 1, Ci, Co, ops._stream())
+
+
+@pytest.mark.parametrize("guided", [False, True])
+def test_euler_kernel_second_grid_trip(dev, guided):
+    """The grid is capped at 4096 workgroups of 256 threads = 1 048 576 vectors; 131073 rows of 64 channels are 1 048 584, so eight threads
+    take the grid-stride loop's second trip.  fluxmi_euler and the plain fluxmi_cfg_euler (B = 1) against the torch bf16 expression, bit for
+    bit, with a NaN-pattern guard region behind the stream that must come back untouched."""
+    from fluxmi import _lib, ops
+
+    R, C, GUARD, halves = 131073, 64, 4096, 2 if guided else 1
+    g = torch.Generator().manual_seed(29)
+    n = halves * R * C
+    store = torch.full((n + GUARD,), 0x7FC1, dtype=torch.int16).view(torch.bfloat16).to(dev)  # a quiet NaN with a payload no kernel writes
+    guard_before = store[n:].view(torch.int16).clone()
+    store[:n] = torch.randn(n, generator=g).to(torch.bfloat16).to(dev)
+    img = store[:n].view(halves, R, C)
+    pred = torch.randn(halves, R, C, generator=g).to(torch.bfloat16).to(dev)
+    dts = torch.tensor([0.0471, -0.03173828125], dtype=torch.float32)
+    d_dts, d_step = dts.to(dev), torch.tensor([1], dtype=torch.int32, device=dev)
+    if guided:
+        c, u = pred[:1], pred[1:]
+        want = img[:1] + float(dts[1]) * (u + SCALE * (c - u))
+        d_scale = torch.tensor([SCALE], dtype=torch.float32, device=dev)
+        _lib.call("fluxmi_cfg_euler", ops._p(img), ops._p(pred), ops._p(d_dts), ops._p(d_step), ops._p(d_scale), 1, R, R, C, C, ops._stream())
+    else:
+        want = img + float(dts[1]) * pred
+        _lib.call("fluxmi_euler", ops._p(img), ops._p(pred), ops._p(d_dts), ops._p(d_step), R * C, ops._stream())
+    torch.cuda.synchronize()
+    assert want.dtype == torch.bfloat16
+    for h in range(halves):
+        assert torch.equal(img[h], want[0]), f"half {h}: {(img[h] != want[0]).sum().item()} elements differ, {(img[h, -1] != want[0, -1]).sum().item()} in the last row"
+    assert torch.equal(store[n:].view(torch.int16), guard_before), "the guard region behind the stream changed"
 
 
 # ---- 2. guided denoise: graph == eager == python loop; 7. tuning knobs ----------------------------------------------------------------------

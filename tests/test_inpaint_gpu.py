@@ -1,5 +1,5 @@
-"""Masked-latent inpainting and differential diffusion on the GPU.  Every update of a masked request is ONE kernel (csrc/elementwise.hip,
-blend_euler_kernel): the Euler (or guided Euler) step followed by
+"""Masked-latent inpainting and differential diffusion on the GPU.  Every update of a masked request is ONE kernel (csrc/update_step.hip,
+the BLEND arms of euler_kernel): the Euler (or guided Euler) step followed by
 
     p  = t_next * noise + (1.0 - t_next) * x0
     x' = (1 - m) * p + m * x1                        every operation rounded to bf16 once, python scalars as fp32

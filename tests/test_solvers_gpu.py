@@ -1,4 +1,4 @@
-"""Higher-order samplers on the GPU.  Every update of a solver request is ONE kernel (csrc/elementwise.hip, solver_step_kernel) driven by
+"""Higher-order samplers on the GPU.  Every update of a solver request is ONE kernel (csrc/update_step.hip, solver_step_kernel) driven by
 device tables: row j of the program (fluxmi/solvers.py) says how evaluation j combines x, the saved iterate, g = ga x + gb v and two fp32
 history slots.  The kernel and the engine are compared bit for bit with the interpreter of tests/solver_util.py (exact=False: fp32 products
 and sums rounded one by one, no fma, one bf16 store).  Model helpers are those of tests/test_cfg_gpu.py and tests/test_inpaint_gpu.py."""

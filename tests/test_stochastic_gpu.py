@@ -1,5 +1,5 @@
 """Stochastic samplers on the GPU.  The fresh noise of euler_ancestral / dpmpp_2m_sde is generated INSIDE the update kernel
-(csrc/elementwise.hip: Philox4x32-10 + Box-Muller, solver_step_kernel's NOISE form) as a pure function of (ids of the image, evaluation index,
+(csrc/update_step.hip: Philox4x32-10 + Box-Muller, solver_step_kernel's NOISE form) as a pure function of (ids of the image, evaluation index,
 element).  The words are compared bit for bit with the numpy reference of tests/stochastic_util.py, the normals with float64 Box-Muller of
 the same words, and kernel and engine bit for bit with the interpreter fed the normals fluxmi_philox_normal returns.  Model helpers are those
 of tests/test_cfg_gpu.py, tests/test_inpaint_gpu.py and tests/test_solvers_gpu.py."""

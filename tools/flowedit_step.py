@@ -1,6 +1,6 @@
 """Time per step of a frozen, graph-replayed FlowEdit evaluation (source_prompt: fluxmi.flowedit, Flux.denoise_edit) against the guided step
 (negative prompt): full Flux-dev geometry (19 + 38 blocks, hidden 3072) with synthetic weights made on the device, fp8 flow, one 1024^2
-image (Li 4096, Lt 512).  Both are ONE forward on two samples followed by one update launch -- cfg_euler_kernel there, flowedit_kernel here --
+image (Li 4096, Lt 512).  Both are ONE forward on two samples followed by one update launch -- euler_kernel's guided arm there, flowedit_kernel here --
 so the edit step is expected inside the guided step's run-to-run spread.  One engine, the two request kinds ALTERNATING (--requests rounds)
 so that clock and thermal drift hit both alike.  The meter is the engine's own hipEvent pair around the graph replays
 (fluxmi_engine_last_timing); calibration, the modulation table and the capture are outside it.
@@ -29,7 +29,7 @@ from fluxmi import _lib, flowedit, synth
 
 
 UPDATE_KERNELS = (("flowedit", re.compile(r"flowedit_kernel<(?:true|1)>")), ("flowedit couple", re.compile(r"flowedit_kernel<(?:false|0)>")),
-                  ("guided", re.compile(r"cfg_euler_kernel")), ("guided solver + noise", re.compile(r"solver_step_kernel<(?:true|1),.*(?:true|1)>")))
+                  ("guided", re.compile(r"(?<![a-z_])euler_kernel<(?:true|1),\s*\w+,\s*(?:false|0)>")), ("guided solver + noise", re.compile(r"solver_step_kernel<(?:true|1),.*(?:true|1)>")))
 
 
 def summarize(path):

@@ -8,7 +8,7 @@ distance from the plain median next to the plain kind's own spread.
 Kernel times come from ONE separate run under the profiler (own process, no counters), summarised by this tool:
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/inpaint_step.py --rounds 1 --steps 10 --with-guided
     python tools/inpaint_step.py --summarize DIR
-which prints the update kernels (euler_kernel, cfg_euler_kernel, blend_euler_kernel) side by side (calls, mean, the ratio to euler_kernel) and the launch count per frozen step of each
+which prints the arms of euler_kernel<CFG, PLAIN, BLEND> (plain, guided, masked, masked + guided) side by side (calls, mean, the ratio to the plain arm) and the launch count per frozen step of each
 kind (steps are delimited by advance_step_kernel; a step's kind is its update kernel), and fails unless a masked step launches as many
 kernels as a plain one.
 Prints one JSON line per measurement."""
@@ -17,20 +17,20 @@ import csv
 import glob
 import json
 import os
+import re
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "flux-fp8-api_amd"))
 sys.path.insert(0, ROOT)
 
-UPDATE_KERNELS = {"euler_kernel(": "plain", "cfg_euler_kernel<": "guided (no mask)", "blend_euler_kernel<false": "masked", "blend_euler_kernel<true": "masked + guided"}
+EULER_KERNEL = re.compile(r"(?:^|[\s:])euler_kernel<\s*(\w+)\s*,\s*\w+\s*,\s*(\w+)\s*>")  # <CFG, PLAIN, BLEND>
+UPDATE_KERNELS = {(False, False): "plain", (True, False): "guided (no mask)", (False, True): "masked", (True, True): "masked + guided"}
 
 
 def update_kind(name):
-    for key, kind in UPDATE_KERNELS.items():
-        if "::" + key in name:
-            return kind
-    return None
+    m = EULER_KERNEL.search(name)
+    return UPDATE_KERNELS[(m.group(1) in ("true", "1"), m.group(2) in ("true", "1"))] if m else None
 
 
 def summarize(path):
@@ -85,7 +85,7 @@ def main():
     ap.add_argument("--width", type=int, default=1024)
     ap.add_argument("--scale", type=float, default=3.5)
     ap.add_argument("--differential", action="store_true", help="the masked kinds run the differential form (a threshold per step)")
-    ap.add_argument("--with-guided", action="store_true", help="a fourth kind, guided without a mask: puts cfg_euler_kernel into a profiler trace")
+    ap.add_argument("--with-guided", action="store_true", help="a fourth kind, guided without a mask: puts the guided arm of euler_kernel into a profiler trace")
     ap.add_argument("--summarize", default=None, help="a directory (or file) with a rocprofv3 *kernel_trace.csv of this tool: print the summary and exit")
     args = ap.parse_args()
     if args.summarize:

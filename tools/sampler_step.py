@@ -27,13 +27,15 @@ sys.path.insert(0, os.path.join(ROOT, "flux-fp8-api_amd"))
 sys.path.insert(0, ROOT)
 
 SOLVER_KERNEL = re.compile(r"(?:^|[\s:])solver_step_kernel<\s*(\w+)\s*,\s*\w+\s*,\s*\w+\s*,\s*(\w+)\s*>")  # <CFG, PLAIN, BLEND, NOISE>
+EULER_KERNEL = re.compile(r"(?:^|[\s:])euler_kernel<\s*(\w+)\s*,\s*\w+\s*,\s*(\w+)\s*>")  # <CFG, PLAIN, BLEND>
 
 
 def update_kind(name):
     m = SOLVER_KERNEL.search(name)
     if m:
         return "solver" + (" + guided" if m.group(1) in ("true", "1") else "") + (" + noise" if m.group(2) in ("true", "1") else "")
-    if re.search(r"(?:^|[\s:])euler_kernel\(", name):
+    m = EULER_KERNEL.search(name)
+    if m and m.group(1) not in ("true", "1") and m.group(2) not in ("true", "1"):
         return "plain"
     return None
 

@@ -6,7 +6,7 @@ engine, the two request kinds ALTERNATING (--requests rounds) so that clock and 
 hipEvent pair around the graph replays (fluxmi_engine_last_timing); calibration, the modulation table and the capture are outside it.
     python tools/window_step.py [--steps 10] [--requests 3] [--canvas 2048x1024] [--tile 1024] [--overlap 0] [--guided]
 --canvas is width x height in pixels; 2048x1024 at overlap 0 gives S = 2, 2048x2048 at overlap 512 gives S = 9.  Prints one JSON line per
-kind.  --guided adds the guided kinds (cfg_euler_kernel against the guided windowed update, 2 S samples) for a kernel trace:
+kind.  --guided adds the guided kinds (euler_kernel's guided arm against the guided windowed update, 2 S samples) for a kernel trace:
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/window_step.py --requests 1 --steps 6 --guided
     python tools/window_step.py --summarize DIR"""
 import argparse
@@ -29,7 +29,8 @@ from fluxmi import _lib, synth, windows
 
 
 UPDATE_KERNELS = (("windowed", re.compile(r"window_step_kernel<(?:true|1)>")), ("window gather", re.compile(r"window_step_kernel<(?:false|0)>")),
-                  ("guided", re.compile(r"cfg_euler_kernel")), ("plain", re.compile(r"(?<![a-z_])euler_kernel")))
+                  ("guided", re.compile(r"(?<![a-z_])euler_kernel<(?:true|1),\s*\w+,\s*(?:false|0)>")),
+                  ("plain", re.compile(r"(?<![a-z_])euler_kernel<(?:false|0),\s*\w+,\s*(?:false|0)>")))  # <CFG, PLAIN, BLEND>
 
 
 def summarize(path):
@@ -72,7 +73,7 @@ def main():
     ap.add_argument("--canvas", default="2048x1024", help="width x height of the canvas in pixels")
     ap.add_argument("--tile", type=int, default=1024)
     ap.add_argument("--overlap", type=int, default=0)
-    ap.add_argument("--guided", action="store_true", help="also the guided kinds (2 S samples): cfg_euler_kernel and the guided windowed update")
+    ap.add_argument("--guided", action="store_true", help="also the guided kinds (2 S samples): euler_kernel's guided arm and the guided windowed update")
     ap.add_argument("--summarize", default=None, help="a directory (or file) with a rocprofv3 *kernel_trace.csv of this tool: print the summary and exit")
     args = ap.parse_args()
     if args.summarize:

@@ -197,6 +197,29 @@ int fluxmi_conv3x3_dense(const void* x, long long ldx, int Cin, const void* w2, 
                          int upsample, int B, int H, int W, void* stream) {
   return fluxmi_k_conv3x3_dense(x, ldx, Cin, w2, bias, out, ldo, Cout, r1, ldr1, a1, r2, ldr2, a2, slope, act, upsample, B, H, W, (hipStream_t)stream);
 }
+int fluxmi_canny_classify(const void* rgb, long long ld, long long bs, void* state, long long state_ld, long long state_bs, int B, int H, int W,
+                          int low, int high, int l2, void* stream) {
+  return fluxmi_k_canny_classify(rgb, ld, bs, state, state_ld, state_bs, B, H, W, low, high, l2, (hipStream_t)stream);
+}
+int fluxmi_canny_hysteresis_round(void* state, long long state_ld, long long state_bs, int B, int H, int W, int* changed_flag, void* stream) {
+  return fluxmi_k_canny_hysteresis_round(state, state_ld, state_bs, B, H, W, changed_flag, (hipStream_t)stream);
+}
+int fluxmi_canny_hysteresis(void* state, long long state_ld, long long state_bs, void* edges, long long edges_ld, long long edges_bs, int* flags,
+                            int B, int H, int W, int* rounds_out, void* stream) {
+  return fluxmi_k_canny_hysteresis(state, state_ld, state_bs, edges, edges_ld, edges_bs, flags, B, H, W, rounds_out, (hipStream_t)stream);
+}
+int fluxmi_canny(const void* rgb, long long ld, long long bs, void* edges, long long edges_ld, long long edges_bs, void* work,
+                 long long work_bytes, int B, int H, int W, int low, int high, int l2, int* rounds_out, void* stream) {
+  return fluxmi_k_canny(rgb, ld, bs, edges, edges_ld, edges_bs, work, work_bytes, B, H, W, low, high, l2, rounds_out, (hipStream_t)stream);
+}
+int fluxmi_rgb_to_gray(const void* rgb, long long ld, long long bs, void* gray, long long gray_ld, long long gray_bs, int B, int H, int W,
+                       void* stream) {
+  return fluxmi_k_rgb_to_gray(rgb, ld, bs, gray, gray_ld, gray_bs, B, H, W, (hipStream_t)stream);
+}
+int fluxmi_gaussian_blur(const void* src, long long ld, long long bs, void* dst, long long dst_ld, long long dst_bs, void* work,
+                         long long work_bytes, int B, int H, int W, int C, float sigma, void* stream) {
+  return fluxmi_k_gaussian_blur(src, ld, bs, dst, dst_ld, dst_bs, work, work_bytes, B, H, W, C, sigma, (hipStream_t)stream);
+}
 int fluxmi_patchify(const void* pix, void* out, int B, int C, int H, int W, int patch, int grid, int Kp, void* stream) {
   return fluxmi_k_patchify(pix, out, B, C, H, W, patch, grid, Kp, (hipStream_t)stream);
 }

@@ -241,6 +241,19 @@ int fluxmi_k_vae_attention(const void* q, const void* k, long long ld_qk, long l
 int fluxmi_k_conv3x3_dense(const void* x, long long ldx, int Cin, const void* w2, const void* bias, void* out, long long ldo, int Cout,
                            const void* r1, long long ldr1, float a1, const void* r2, long long ldr2, float a2, float slope, int act,
                            int upsample, int B, int H, int W, hipStream_t s);
+// control-map preprocessors (preprocess.hip; include/fluxmi.h, fluxmi_canny* / fluxmi_rgb_to_gray / fluxmi_gaussian_blur): uint8 NHWC images with
+// row and image strides in bytes
+int fluxmi_k_canny_classify(const void* rgb, long long ld, long long bs, void* state, long long sld, long long sbs, int B, int H, int W,
+                            int low, int high, int l2, hipStream_t s);
+int fluxmi_k_canny_hysteresis_round(void* state, long long sld, long long sbs, int B, int H, int W, int* changed_flag, hipStream_t s);
+int fluxmi_k_canny_hysteresis(void* state, long long sld, long long sbs, void* edges, long long eld, long long ebs, int* flags, int B, int H,
+                              int W, int* rounds_out, hipStream_t s);
+int fluxmi_k_canny(const void* rgb, long long ld, long long bs, void* edges, long long eld, long long ebs, void* work, long long work_bytes,
+                   int B, int H, int W, int low, int high, int l2, int* rounds_out, hipStream_t s);
+int fluxmi_k_rgb_to_gray(const void* rgb, long long ld, long long bs, void* gray, long long gld, long long gbs, int B, int H, int W,
+                         hipStream_t s);
+int fluxmi_k_gaussian_blur(const void* src, long long ld, long long bs, void* dst, long long dld, long long dbs, void* work, long long work_bytes,
+                           int B, int H, int W, int C, float sigma, hipStream_t s);
 int fluxmi_k_vision_attention(const void* q, const void* k, long long ld_qk, long long bs_qk, const void* vt, long long ld_vt, long long bs_vt,
                               void* out, long long ld_out, long long bs_out, const void* v_bias, float scale, int head_dim, int L, int Lp, int H,
                               int B, hipStream_t s);

@@ -28,12 +28,13 @@ import torch
 
 import lora_loading  # noqa: F401  (same import side as the reference)
 from fluxmi import dist as fdist
-from fluxmi import solvers
+from fluxmi import ops, solvers
 from modules.autoencoder import check_attention_mode
 from util import (ModelSpec, ModelVersion, engine_flow_dtype, into_device, into_dtype, load_config_from_path, load_controlnet, load_ip_adapter, load_upscaler,
                   load_models_from_config)
 
 MAX_RAND = 2**32 - 1
+CONTROL_PREPROCESSORS = ("canny", "gray", "blur")  # generate(control_preprocess=...) / preprocess_control: the maps made from a photo
 GUIDANCE_MODES = ("cfg", "apg", "cfg_zero_star")  # generate(guidance_mode=...): the rule that combines the two branches of true CFG
 
 # FLUX.1 Kontext's preferred reference resolutions, (width, height) (BFL flux, src/flux/sampling.py)
@@ -454,8 +455,9 @@ class FluxPipeline:
                                      generator: torch.Generator = None) -> torch.Tensor:
         """FLUX.1 Depth / Canny [dev] -> img_cond bf16 [num_images, Li, 64] on the flow device (BFL's prepare_control, src/flux/sampling.py):
         the RGB control image is resized to (width, height) with PIL LANCZOS, goes to float / 127.5 - 1, is VAE-encoded with its Gaussian
-        sample (drawn from `generator` after the noise, as in prepare_fill_conditioning), cast to bf16 and packed 2 x 2.  The caller passes the
-        depth map or edge map itself: BFL's preprocessors (Depth Anything, OpenCV Canny) are not part of this project."""
+        sample (drawn from `generator` after the noise, as in prepare_fill_conditioning), cast to bf16 and packed 2 x 2.  `control_image` is
+        the depth map or edge map itself.  An edge map can be made from a photo by preprocess_control(photo, "canny") (generate's
+        `control_preprocess`: a native Canny, where BFL calls OpenCV's); BFL's depth preprocessor (Depth Anything) is not part of this project."""
         from PIL import Image
 
         if self.ae is None:
@@ -470,11 +472,63 @@ class FluxPipeline:
                                         generator: torch.Generator = None) -> torch.Tensor:
         """A ControlNet's `cond` bf16 [num_images, Li, 64] on the flow device (diffusers' FluxControlNetPipeline.prepare_image + the latent
         handling of its __call__): the control image, in any form `init_image` takes, is resized like `control_image`, VAE-encoded (its
-        Gaussian sample drawn from `generator` after the noise), shifted and scaled, cast to bf16 and packed 2 x 2.  The caller passes the
-        edge map / depth map / pose itself; no preprocessor is part of this project."""
+        Gaussian sample drawn from `generator` after the noise), shifted and scaled, cast to bf16 and packed 2 x 2.  `controlnet_image` is
+        the edge map / depth map / pose itself.  The classical maps -- Canny edges, gray, blur -- can be made from a photo by
+        preprocess_control (generate's `control_preprocess`); preprocessors that need weights (depth, pose) are not part of this project."""
         if self.ae is None:
             raise RuntimeError("fluxmi: controlnet_image needs an autoencoder (config.ae_path) -- none is attached; pass controlnet_cond")
         return self.prepare_control_conditioning(controlnet_image, height, width, num_images=num_images, generator=generator)
+
+    # ---- control-map preprocessors (csrc/preprocess.hip) ---------------------------------------------------------------------------------
+    @staticmethod
+    def _check_control_preprocess(kind, canny_low=100, canny_high=200, canny_l2=False, blur_sigma=8.0):
+        """the arguments of preprocess_control, refused by name before any work"""
+        if kind not in CONTROL_PREPROCESSORS:
+            raise ValueError(f"fluxmi: control_preprocess={kind!r}: expected one of {CONTROL_PREPROCESSORS} (depth, pose and the other maps that "
+                             "need weights are not part of this project: pass the map itself)")
+        try:
+            ops.canny_thresholds(canny_low, canny_high)
+        except ValueError as e:
+            raise ValueError(f"fluxmi: canny_low={canny_low!r} / canny_high={canny_high!r}: expected integers >= 0 ({e})") from None
+        if not isinstance(canny_l2, bool):
+            raise ValueError(f"fluxmi: canny_l2={canny_l2!r}: expected a bool")
+        try:
+            ops.blur_radius(blur_sigma)
+        except ValueError:
+            raise ValueError(f"fluxmi: blur_sigma={blur_sigma!r}: expected a number whose radius ceil(3 sigma) lies in 1..{ops.BLUR_MAX_RADIUS}, "
+                             f"i.e. 0 < blur_sigma <= {ops.BLUR_MAX_RADIUS / 3:.2f}") from None
+
+    @torch.inference_mode()
+    def preprocess_control(self, image, kind: str, width: Optional[int] = None, height: Optional[int] = None, canny_low: int = 100,
+                           canny_high: int = 200, canny_l2: bool = False, blur_sigma: float = 8.0) -> torch.Tensor:
+        """A photo -> the control map a FLUX.1 Canny [dev] checkpoint or a ControlNet follows: uint8 [H, W, 3] on the host.  `image`: any form
+        `init_image` takes.  It is first resized to (width, height) with PIL LANCZOS, exactly as prepare_control_conditioning resizes a map
+        (BFL runs its Canny after the resize too; None keeps the image's own size), then goes to the autoencoder's device and through one
+        of the kernels of csrc/preprocess.hip (fluxmi.ops):
+          "canny"  edges 0 / 255 of the Canny detector defined in include/fluxmi.h: integer arithmetic, exact and deterministic.  It follows
+                   the well-known algorithm, but parity with an OpenCV binary is NOT pinned (none is available to the tests).  The defaults
+                   100 / 200 are the thresholds of diffusers' ControlNet examples; BFL's FLUX.1 Canny pipeline uses 50 / 200.  Those are
+                   theirs -- no threshold is recommended here.  `canny_l2`: squared-gradient magnitudes (OpenCV's L2gradient).
+          "gray"   PIL's convert("L"), bit for bit
+          "blur"   a Gaussian blur of standard deviation `blur_sigma` pixels (radius ceil(3 sigma) <= 64), replicated border
+        A one-channel result is repeated to three channels.  Depth, pose, tile and low-quality maps are not made here."""
+        from PIL import Image
+
+        self._check_control_preprocess(kind, canny_low, canny_high, canny_l2, blur_sigma)
+        pil = self._rgb_uint8(image).convert("RGB")
+        size = (pil.width if width is None else int(width), pil.height if height is None else int(height))
+        if size != pil.size:
+            pil = pil.resize(size, Image.LANCZOS)
+        dev = self.device_ae if getattr(self, "ae", None) is not None else self.device_flux
+        x = torch.from_numpy(np.array(pil)).to(dev)[None].contiguous()
+        if kind == "canny":
+            y = ops.canny(x, canny_low, canny_high, canny_l2)
+        elif kind == "gray":
+            y = ops.rgb_to_gray(x)
+        else:
+            y = ops.gaussian_blur(x, blur_sigma)
+        y = y[0] if y.ndim == 4 else y[0][..., None].expand(-1, -1, 3)
+        return y.contiguous().cpu()
 
     # ---- FLUX IP-Adapter image prompts ---------------------------------------------------------------------------------------------------
     def prepare_ip_adapter(self, images, image_embeds, scale, negative_image, negative_scale, guided: bool):
@@ -708,7 +762,8 @@ class FluxPipeline:
                  apg_eta: float = 1.0, apg_norm_threshold: float = 0.0, apg_momentum: float = 0.0, zero_init_steps: int = 0,
                  on_step=None, preview_every: int = 0, preview_factors=None, source_prompt=None, source_guidance: Optional[float] = None,
                  edit_n_max: Optional[int] = None, edit_n_min: int = 0, edit_n_avg: int = 1, tile_size=None, tile_overlap: Optional[int] = None,
-                 tile_weight: str = "cosine", upscale: bool = False, init_upscale: bool = False):
+                 tile_weight: str = "cosine", upscale: bool = False, init_upscale: bool = False, control_preprocess: Optional[str] = None,
+                 canny_low: int = 100, canny_high: int = 200, canny_l2: bool = False, blur_sigma: float = 8.0):
         """`reference_image` (FLUX.1 Kontext [dev] instruction editing): an image the prompt describes an edit of, in any form `init_image`
         takes; see prepare_kontext_reference.  Composes with `init_image` / `strength` unchanged.
         FLUX.1 Fill [dev] (a model with 320 conditioning channels): `init_image` is the image to inpaint and `mask_image` (white =
@@ -850,7 +905,27 @@ class FluxPipeline:
         generate(prompt, init_image=photo, init_upscale=True, width=4096, height=4096, strength=0.3, tile_size=1024) on a
         vae_attention="streaming" config.  Refused up front: either flag without a configured upscaler, `upscale` with
         output_type="latent" (or no VAE), `init_upscale` without `init_image`, an image the network's kernel or the device's free memory
-        cannot take.  Both False (the default) is today's request, launch for launch."""
+        cannot take.  Both False (the default) is today's request, launch for launch.
+        `control_preprocess` ("canny" | "gray" | "blur"; preprocess_control): `control_image` (FLUX.1 Depth / Canny) or `controlnet_image` (a
+        ControlNet) -- whichever the request carries -- is a PHOTO, and the control map is made from it on the device, after the resize to
+        `width` x `height`, by a native Canny edge detector (`canny_low` / `canny_high` / `canny_l2`), PIL's luma, or a Gaussian blur
+        (`blur_sigma`); the conditioning call then sees a correctly sized map.  The Canny is the integer definition of include/fluxmi.h:
+        exact and deterministic, but parity with OpenCV's binary is unpinned.  100 / 200 are diffusers' example thresholds, BFL's
+        pipeline uses 50 / 200; neither is a recommendation.  Refused up front: `control_preprocess` without `control_image` /
+        `controlnet_image`, with `img_cond` / `controlnet_cond` (already-encoded maps), an unknown kind, thresholds that are not integers
+        >= 0, a `blur_sigma` whose radius ceil(3 sigma) is outside 1..64.  None (the default) is today's request, launch for launch, and
+        then refuses non-default `canny_*` / `blur_sigma`."""
+        if control_preprocess is not None:
+            if img_cond is not None or controlnet_cond is not None:
+                raise ValueError("fluxmi: control_preprocess works on an image: it does not combine with img_cond / controlnet_cond (maps that "
+                                 "are already encoded)")
+            if control_image is None and controlnet_image is None:
+                raise ValueError("fluxmi: control_preprocess needs control_image (FLUX.1 Depth / Canny) or controlnet_image (a ControlNet): "
+                                 "the photo to make the map from")
+            self._check_control_preprocess(control_preprocess, canny_low, canny_high, canny_l2, blur_sigma)
+        elif (canny_low, canny_high, canny_l2, blur_sigma) != (100, 200, False, 8.0):
+            raise ValueError("fluxmi: canny_low / canny_high / canny_l2 / blur_sigma belong to control_preprocess, which is not set")
+        prep_kw = dict(canny_low=canny_low, canny_high=canny_high, canny_l2=canny_l2, blur_sigma=blur_sigma)
         if upscale or init_upscale:
             init_image = self._check_upscale(upscale, init_upscale, output_type, init_image, width, height, num_images)
         tiles = self._check_tiles(locals())
@@ -1107,6 +1182,8 @@ class FluxPipeline:
             if img_cond is None and kind == "fill":
                 img_cond = self.prepare_fill_conditioning(fill_image, mask_image, height, width, num_images=1, generator=generator)
             elif img_cond is None:
+                if control_preprocess is not None:
+                    control_image = self.preprocess_control(control_image, control_preprocess, width, height, **prep_kw)
                 img_cond = self.prepare_control_conditioning(control_image, height, width, num_images=1, generator=generator)
             img_cond = img_cond.to(device=self.device_flux, dtype=torch.bfloat16)
             if img_cond.shape[0] == 1 and num_images > 1:
@@ -1116,6 +1193,8 @@ class FluxPipeline:
         if cn_on:
             # drawn from the request's generator after the noise, like a Kontext reference
             if controlnet_cond is None:
+                if control_preprocess is not None:
+                    controlnet_image = self.preprocess_control(controlnet_image, control_preprocess, width, height, **prep_kw)
                 controlnet_cond = self.prepare_controlnet_conditioning(controlnet_image, height, width, num_images=1, generator=generator)
             cn_cond = controlnet_cond.to(device=self.device_flux, dtype=torch.bfloat16)
             if cn_cond.ndim != 3 or cn_cond.shape[0] not in (1, num_images) or tuple(cn_cond.shape[1:]) != tuple(img.shape[1:]):

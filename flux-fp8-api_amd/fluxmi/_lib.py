@@ -98,6 +98,12 @@ _SIGS = {
     "fluxmi_vision_attention": ([vp, vp, i64, i64, vp, i64, i64, vp, i64, i64, vp, C.c_float, i32, i32, i32, i32, i32, vp], i32),
     "fluxmi_vae_attention": ([vp, vp, i64, i64, vp, i64, i64, vp, i64, i64, vp, i32, i32, i32, i32, vp], i32),
     "fluxmi_conv3x3_dense": ([vp, i64, i32, vp, vp, vp, i64, i32, vp, i64, C.c_float, vp, i64, C.c_float, C.c_float, i32, i32, i32, i32, i32, vp], i32),
+    "fluxmi_canny_classify": ([vp, i64, i64, vp, i64, i64, i32, i32, i32, i32, i32, i32, vp], i32),
+    "fluxmi_canny_hysteresis_round": ([vp, i64, i64, i32, i32, i32, vp, vp], i32),
+    "fluxmi_canny_hysteresis": ([vp, i64, i64, vp, i64, i64, vp, i32, i32, i32, C.POINTER(i32), vp], i32),
+    "fluxmi_canny": ([vp, i64, i64, vp, i64, i64, vp, i64, i32, i32, i32, i32, i32, i32, C.POINTER(i32), vp], i32),
+    "fluxmi_rgb_to_gray": ([vp, i64, i64, vp, i64, i64, i32, i32, i32, vp], i32),
+    "fluxmi_gaussian_blur": ([vp, i64, i64, vp, i64, i64, vp, i64, i32, i32, i32, i32, f32, vp], i32),
     "fluxmi_patchify": ([vp, vp, i32, i32, i32, i32, i32, i32, i32, vp], i32),
     "fluxmi_attention": ([vp, vp, vp, vp, i64, i32, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp], i32),
     "fluxmi_attention_grouped": ([vp, vp, vp, vp, i64, i32, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp], i32),

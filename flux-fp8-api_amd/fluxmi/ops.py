@@ -942,3 +942,120 @@ def latent_preview(x: torch.Tensor, pred: torch.Tensor, t, proj, grid, scale=Non
         raise ValueError(f"latent_preview: out {tuple(out.shape)} must be contiguous uint8 [{_lib.PREVIEW_SLOTS}, {B}, {2 * h}, {2 * w}, 3]")
     call("fluxmi_latent_preview", _p(x), _p(pred), _p(ts), _p(st), _p(sc), _p(prj), _p(ct), _p(out), B, x.shape[1], pred.shape[1], x.shape[2], pred.shape[2], h, w, _stream())
     return out
+
+
+# ---- control-map preprocessors (csrc/preprocess.hip; include/fluxmi.h has the arithmetic) ----------------------------------------------
+CANNY_TILE = 32          # FLUXMI_CANNY_TILE: the pixel tile edge of the classify and the hysteresis kernel
+CANNY_ROUND_GROUP = 4    # FLUXMI_CANNY_ROUND_GROUP: hysteresis rounds launched per flag read-back
+BLUR_MAX_RADIUS = 64     # FLUXMI_BLUR_MAX_RADIUS
+
+
+def _u8_image(t: torch.Tensor, who: str, name: str, channels: int):
+    """t: uint8 [B, H, W, channels] (or [B, H, W] for channels == 1), pixels and channels adjacent, any row / image stride that keeps rows
+    apart (a window of a larger buffer is fine) -> (B, H, W, row stride, image stride) in bytes"""
+    _req(t, torch.uint8, f"{who}: {name}")
+    shape = tuple(t.shape) + (1,) if t.ndim == 3 and channels == 1 else tuple(t.shape)
+    strides = tuple(t.stride()) + (1,) if t.ndim == 3 and channels == 1 else tuple(t.stride())
+    if len(shape) != 4 or shape[3] != channels or min(shape) < 1:
+        want = f"[B, H, W, {channels}]" + (" or [B, H, W]" if channels == 1 else "")
+        raise ValueError(f"{who}: {name} must be uint8 {want} with B, H, W >= 1, got {tuple(t.shape)}")
+    B, H, W, C = shape
+    ld = strides[1] if H > 1 else W * C
+    bs = strides[0] if B > 1 else H * ld
+    if (C > 1 and strides[3] != 1) or (W > 1 and strides[2] != C) or ld < W * C or bs < H * ld:
+        raise ValueError(f"{who}: {name} must keep channels and pixels adjacent, rows >= W * C = {W * C} bytes apart and images >= H rows "
+                         f"apart, got strides {tuple(t.stride())} for shape {tuple(t.shape)}")
+    return B, H, W, ld, bs
+
+
+def _u8_out(out: Optional[torch.Tensor], shape, like: torch.Tensor, who: str, name: str, channels: int):
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=like.device)
+    geo = _u8_image(out, who, name, channels)
+    if out.device != like.device or geo[:3] != tuple(shape[:3]):
+        raise ValueError(f"{who}: {name} {tuple(out.shape)} on {out.device} does not match the input's {tuple(shape)} on {like.device}")
+    return out, geo[3], geo[4]
+
+
+def canny_thresholds(low, high):
+    """Canny's two thresholds as the kernel takes them: integers >= 0 (bools and fractions are refused by name), in either order."""
+    for name, v in (("low", low), ("high", high)):
+        if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v < 2 ** 31:
+            raise ValueError(f"canny: {name}={v!r}: expected an integer in [0, 2^31)")
+    return int(low), int(high)
+
+
+def blur_radius(sigma) -> int:
+    """ceil(3 sigma) with sigma rounded to fp32 first, as fluxmi_gaussian_blur computes it; refuses a sigma whose radius is outside
+    1..BLUR_MAX_RADIUS"""
+    import math
+
+    try:
+        s = float(torch.tensor(float(sigma), dtype=torch.float32))
+    except (TypeError, ValueError):
+        raise ValueError(f"gaussian_blur: sigma={sigma!r}: expected a number (the radius is ceil(3 sigma))") from None
+    r = math.ceil(3.0 * s) if math.isfinite(s) and s > 0 else 0
+    if isinstance(sigma, bool) or not 1 <= r <= BLUR_MAX_RADIUS:
+        raise ValueError(f"gaussian_blur: sigma={sigma!r}: the radius ceil(3 sigma) must lie in 1..{BLUR_MAX_RADIUS}")
+    return r
+
+
+def rgb_to_gray(rgb: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """rgb uint8 [B, H, W, 3] -> uint8 [B, H, W]: L = (19595 R + 38470 G + 7471 B + 32768) >> 16, PIL's convert("L") bit for bit"""
+    B, H, W, ld, bs = _u8_image(rgb, "rgb_to_gray", "rgb", 3)
+    out, old, obs = _u8_out(out, (B, H, W), rgb, "rgb_to_gray", "out", 1)
+    call("fluxmi_rgb_to_gray", _p(rgb), ld, bs, _p(out), old, obs, B, H, W, _stream())
+    return out
+
+
+def canny_classify(rgb: torch.Tensor, low: int, high: int, l2: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The first half of Canny (fluxmi_canny_classify): rgb uint8 [B, H, W, 3] -> state uint8 [B, H, W], 0 = no edge, 1 = weak (kept by
+    non-maximum suppression, above min(low, high)), 2 = strong (above max(low, high)).  l2: squared-gradient magnitudes against squared thresholds."""
+    low, high = canny_thresholds(low, high)
+    B, H, W, ld, bs = _u8_image(rgb, "canny_classify", "rgb", 3)
+    out, old, obs = _u8_out(out, (B, H, W), rgb, "canny_classify", "out", 1)
+    call("fluxmi_canny_classify", _p(rgb), ld, bs, _p(out), old, obs, B, H, W, low, high, int(bool(l2)), _stream())
+    return out
+
+
+def canny_hysteresis(state: torch.Tensor, out: Optional[torch.Tensor] = None):
+    """The second half (fluxmi_canny_hysteresis): state uint8 [B, H, W] of 0 / 1 / 2 -> (edges, rounds); edges uint8 [B, H, W] is 255 on every
+    strong pixel and every weak pixel 8-connected to one through weak pixels, 0 elsewhere; `rounds` = kernel rounds run, the last of which
+    changed nothing.  `state` is left as it is (the rounds run on a copy).  Reads flags back: synchronises the current stream."""
+    B, H, W, _, _ = _u8_image(state, "canny_hysteresis", "state", 1)
+    out, old, obs = _u8_out(out, (B, H, W), state, "canny_hysteresis", "out", 1)
+    work = state.reshape(B, H, W).clone(memory_format=torch.contiguous_format)
+    flags = torch.zeros(CANNY_ROUND_GROUP, dtype=torch.int32, device=state.device)
+    rounds = C.c_int(0)
+    call("fluxmi_canny_hysteresis", _p(work), W, H * W, _p(out), old, obs, _p(flags), B, H, W, C.byref(rounds), _stream())
+    return out, rounds.value
+
+
+def canny(rgb: torch.Tensor, low: int, high: int, l2: bool = False, out: Optional[torch.Tensor] = None, return_rounds: bool = False):
+    """The Canny edge detector (fluxmi_canny = classify + hysteresis): rgb uint8 [B, H, W, 3] -> edges uint8 [B, H, W] of 0 / 255.  Integer
+    arithmetic throughout; include/fluxmi.h is the definition (parity with an OpenCV binary is not pinned).  Synchronises the current stream."""
+    low, high = canny_thresholds(low, high)
+    B, H, W, ld, bs = _u8_image(rgb, "canny", "rgb", 3)
+    out, old, obs = _u8_out(out, (B, H, W), rgb, "canny", "out", 1)
+    nbytes = B * H * ((W + 3) // 4 * 4) + 4 * CANNY_ROUND_GROUP  # FLUXMI_CANNY_WORK_BYTES
+    work = torch.empty(nbytes, dtype=torch.uint8, device=rgb.device)
+    rounds = C.c_int(0)
+    call("fluxmi_canny", _p(rgb), ld, bs, _p(out), old, obs, _p(work), nbytes, B, H, W, low, high, int(bool(l2)), C.byref(rounds), _stream())
+    return (out, rounds.value) if return_rounds else out
+
+
+def gaussian_blur(img: torch.Tensor, sigma: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Separable Gaussian blur (fluxmi_gaussian_blur) of img uint8 [B, H, W, C], C in {1, 3} ([B, H, W] counts as C = 1): radius
+    ceil(3 sigma) in 1..64, replicated border, fp32 accumulation over an fp32 intermediate, one rounding at the store."""
+    blur_radius(sigma)
+    ch = 1 if img.ndim == 3 else img.shape[-1]
+    if ch not in (1, 3):
+        raise ValueError(f"gaussian_blur: img {tuple(img.shape)}: expected 1 or 3 channels")
+    B, H, W, ld, bs = _u8_image(img, "gaussian_blur", "img", ch)
+    out, old, obs = _u8_out(out, tuple(img.shape), img, "gaussian_blur", "out", ch)
+    if out.data_ptr() == img.data_ptr():
+        raise ValueError("gaussian_blur: out must not be img")
+    nbytes = B * H * ((W * ch + 3) // 4 * 4) * 4  # FLUXMI_BLUR_WORK_BYTES
+    work = torch.empty(nbytes, dtype=torch.uint8, device=img.device)
+    call("fluxmi_gaussian_blur", _p(img), ld, bs, _p(out), old, obs, _p(work), nbytes, B, H, W, ch, float(sigma), _stream())
+    return out

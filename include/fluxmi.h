@@ -423,6 +423,67 @@ int fluxmi_conv3x3_dense(const void* x, long long ldx, int Cin, const void* w2, 
  * zero.  Pixels past grid*patch are not read.  Kp %% 8 == 0; grid*patch <= H, W.  SigLIP-so400m: C 3, patch 14, grid 27, Kp 640. */
 int fluxmi_patchify(const void* pix, void* out, int B, int C, int H, int W, int patch, int grid, int Kp, void* stream);
 
+/* ---- control-map preprocessors (csrc/preprocess.hip): photo -> edge map / luma / blurred image ---------------------------------------
+ * Images are uint8 [B][H][W][C], channels adjacent, with a ROW stride `ld` and an IMAGE stride `bs` in bytes (ld >= W * C; bs >= H * ld
+ * when B > 1), so an operand may be a window of a larger buffer: nothing outside the W * C bytes of a row is read or written.  Pointers
+ * need no alignment; 4-byte accesses are used on rows whose address is a multiple of 4.  B, H <= 65535, W <= 2^24.  A sample's bits depend
+ * on that sample alone, and every function here is deterministic.
+ *
+ * Canny.  Everything is integer arithmetic and the text below IS the definition: the kernels match it bit for bit.  It follows the steps
+ * and constants of the widely used open-source implementation (3 x 3 Sobel, the channel of largest magnitude, 22.5-degree sectors by the
+ * fixed-point tan 13573 / 2^15, hysteresis over 8-neighbours), but parity with an OpenCV binary is NOT pinned: none is available to the tests.
+ *
+ * fluxmi_canny_classify: rgb [B][H][W][3] -> state [B][H][W] in {0, 1 (weak), 2 (strong)}, one launch.
+ *   per channel c, with p(y, x) read at indices clamped to the image (the border is replicated):
+ *     dx = (p(y-1,x+1) + 2 p(y,x+1) + p(y+1,x+1)) - (p(y-1,x-1) + 2 p(y,x-1) + p(y+1,x-1))          rows [-1 0 1; -2 0 2; -1 0 1]
+ *     dy = (p(y+1,x-1) + 2 p(y+1,x) + p(y+1,x+1)) - (p(y-1,x-1) + 2 p(y-1,x) + p(y-1,x+1))          its transpose
+ *     m  = |dx| + |dy|   (l2 = 0)      or      dx dx + dy dy   (l2 = 1; low and high are then squared here, saturating at 2^31 - 1)
+ *   the pixel takes (dx, dy, m) of the channel with the largest m; a later channel replaces an earlier one only when strictly greater.
+ *   The magnitude of a position outside the image is 0.  lo = min(low, high), hi = max(low, high), both >= 0.
+ *   m <= lo: state 0.  Otherwise non-maximum suppression, with x = |dx|, y = |dy| << 15, t22 = x * 13573, t67 = t22 + (x << 16):
+ *     y < t22:   kept iff m >  m(y, x-1)  and m >= m(y, x+1)
+ *     y > t67:   kept iff m >  m(y-1, x)  and m >= m(y+1, x)
+ *     otherwise: s = -1 if dx and dy have opposite signs, else +1;  kept iff m > m(y-1, x-s) and m > m(y+1, x+s)
+ *   not kept: state 0;  kept: state 2 if m > hi, else 1.
+ *   Example: a vertical step of height h between columns c - 1 and c gives dx = 4 h, dy = 0 in both columns; the tie keeps the LEFT one
+ *   (m > left, m >= right), so the edge is the single column c - 1 (likewise the upper row of a horizontal step), and h <= lo / 4 gives none.
+ *   One workgroup owns a FLUXMI_CANNY_TILE x FLUXMI_CANNY_TILE pixel tile; its 2-pixel input halo is staged in LDS once and every magnitude
+ *   of the tile + 1 is computed once.
+ * fluxmi_canny_hysteresis_round: one round on a state map of values 0 / 1 / 2, in place.  Each workgroup loads its FLUXMI_CANNY_TILE^2 tile
+ *   and a 1-pixel halo (0 outside the image), promotes 1 -> 2 wherever one of the 8 neighbours is 2 until the tile stops changing, stores
+ *   the promoted pixels of its own tile and sets *changed_flag = 1 (device int; never cleared here) if it promoted any.  A halo pixel may be
+ *   read before or after its owner's store of the same round; the update is monotone, so repeated rounds reach the one closure -- the set
+ *   of weak pixels 8-connected to a strong one -- whatever the interleaving.  No workgroup waits on another.
+ * fluxmi_canny_hysteresis: rounds until one changes nothing, then edges [B][H][W] = 255 where state == 2, else 0.  Rounds are launched in
+ *   groups of FLUXMI_CANNY_ROUND_GROUP, each with its own zeroed slot of `flags` (that many device ints); the group's flags are read back
+ *   (this call synchronises the stream) and *rounds_out = the rounds up to and including the first that changed nothing (those launched
+ *   behind it in its group did nothing).  Every other round promotes a pixel, so H * W + 1 rounds suffice: beyond that an error is
+ *   returned.  `state` is modified (it ends as the closure).  rounds_out may be NULL.
+ * fluxmi_canny = classify into `work`, then fluxmi_canny_hysteresis.  work: 16-byte aligned, FLUXMI_CANNY_WORK_BYTES(B, H, W) bytes. */
+#define FLUXMI_CANNY_TILE 32
+#define FLUXMI_CANNY_ROUND_GROUP 4
+#define FLUXMI_CANNY_WORK_BYTES(B, H, W) ((long long)(B) * (H) * (((long long)(W) + 3) & ~3LL) + 4 * FLUXMI_CANNY_ROUND_GROUP)
+int fluxmi_canny_classify(const void* rgb, long long ld, long long bs, void* state, long long state_ld, long long state_bs, int B, int H, int W,
+                          int low, int high, int l2, void* stream);
+int fluxmi_canny_hysteresis_round(void* state, long long state_ld, long long state_bs, int B, int H, int W, int* changed_flag, void* stream);
+int fluxmi_canny_hysteresis(void* state, long long state_ld, long long state_bs, void* edges, long long edges_ld, long long edges_bs, int* flags,
+                            int B, int H, int W, int* rounds_out, void* stream);
+int fluxmi_canny(const void* rgb, long long ld, long long bs, void* edges, long long edges_ld, long long edges_bs, void* work,
+                 long long work_bytes, int B, int H, int W, int low, int high, int l2, int* rounds_out, void* stream);
+/* gray [B][H][W] = (19595 R + 38470 G + 7471 B + 32768) >> 16 of rgb [B][H][W][3]: PIL's convert("L"), bit for bit. */
+int fluxmi_rgb_to_gray(const void* rgb, long long ld, long long bs, void* gray, long long gray_ld, long long gray_bs, int B, int H, int W,
+                       void* stream);
+/* Separable Gaussian blur of src [B][H][W][C], C in {1, 3}, into dst (not src): radius r = ceil(3 sigma) (sigma as fp32, the product in
+ * fp64), 1 <= r <= FLUXMI_BLUR_MAX_RADIUS; taps w[i] = exp(-i^2 / (2 sigma^2)), i = -r .. r, divided by their sum in fp64 and rounded to
+ * fp32 once (handed to both passes as fp32 kernel-argument data).  Indices are clamped to the image (the border is replicated).
+ *   t(y, x, c)   = sum_i w[i] src(y, x + i, c)      horizontal pass, fp32: acc = fma(w[i], value, acc) from 0, i ascending; NOT rounded to uint8
+ *   dst(y, x, c) = sum_i w[i] t(y + i, x, c)        vertical pass, the same way; then rint (to nearest, ties to even) and clamp to 0..255
+ * work: 16-byte aligned, FLUXMI_BLUR_WORK_BYTES(B, H, W, C) bytes (the fp32 intermediate). */
+#define FLUXMI_BLUR_MAX_RADIUS 64
+#define FLUXMI_BLUR_WORK_BYTES(B, H, W, C) ((long long)(B) * (H) * ((((long long)(W) * (C)) + 3) & ~3LL) * 4)
+int fluxmi_gaussian_blur(const void* src, long long ld, long long bs, void* dst, long long dst_ld, long long dst_bs, void* work,
+                         long long work_bytes, int B, int H, int W, int C, float sigma, void* stream);
+
 /* ---- step scalars -------------------------------------------------------------------------------------- */
 /* timestep_embedding(t, 2*half) with host-provided frequency table                 flux_model.py:95-116 */
 int fluxmi_timestep_embedding(const void* t, const float* freqs, void* out, int B, int half, float time_factor, void* stream);

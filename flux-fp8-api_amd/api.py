@@ -29,10 +29,11 @@ Same two POST endpoints, request fields, defaults and status codes:
              -- tiled generation: a large canvas stepped from overlapping windows (FluxPipeline.generate), each passed on only when set;
              upscale=false, init_upscale=false -- the configured ESRGAN-family upscaler on the decoded pixels / on init_image
              (FluxPipeline.generate; needs config.upscaler_path), each passed on only when true;
-             control_preprocess=None ("canny" | "gray" | "blur"), canny_low=None (>= 0), canny_high=None (>= 0), canny_l2=None,
-             blur_sigma=None (> 0) -- control_image / controlnet_image is a PHOTO and the control map is made from it on the device
-             (FluxPipeline.preprocess_control: a native Canny whose parity with OpenCV's is unpinned, PIL's luma, a Gaussian blur), each
-             passed on only when set;
+             control_preprocess=None ("canny" | "gray" | "blur" | "depth_anything"), canny_low=None (>= 0), canny_high=None (>= 0),
+             canny_l2=None, blur_sigma=None (> 0), depth_resolution=None (14..1036), depth_normalize=None ("minmax" | "raw") --
+             control_image / controlnet_image is a PHOTO and the control map is made from it on the device
+             (FluxPipeline.preprocess_control: a native Canny whose parity with OpenCV's is unpinned, PIL's luma, a Gaussian blur, the
+             depth map of the Depth Anything estimator of config.depth_path), each passed on only when set;
              stream=None, preview_every=None (>= 0) -- progress, live previews and cancellation, see below;
              a region with both or neither of box / mask, or a box outside 0 <= x0 < x1 <= 1, is a 422}
              ->  image/jpeg stream of FluxPipeline.generate(**args)                                               (reference api.py:54-86)
@@ -138,11 +139,13 @@ class GenerateArgs(BaseModel):
     tile_weight: Optional[str] = None  # ... "cosine" (default) | "uniform": how overlapping windows are blended
     upscale: Optional[bool] = False  # run the decoded pixels through the configured ESRGAN-family upscaler (config.upscaler_path): scale x the size
     init_upscale: Optional[bool] = False  # run init_image through it before the resize to width x height (the upscale + img2img workflow)
-    control_preprocess: Optional[Literal["canny", "gray", "blur"]] = None  # control_image / controlnet_image is a photo: make the map from it (FluxPipeline.preprocess_control)
+    control_preprocess: Optional[Literal["canny", "gray", "blur", "depth_anything"]] = None  # control_image / controlnet_image is a photo: make the map from it (FluxPipeline.preprocess_control)
     canny_low: Optional[int] = Field(default=None, ge=0)  # ... Canny's thresholds (defaults 100 / 200, diffusers' example values; BFL uses 50 / 200)
     canny_high: Optional[int] = Field(default=None, ge=0)
     canny_l2: Optional[bool] = None  # ... squared-gradient magnitudes instead of |dx| + |dy|
     blur_sigma: Optional[float] = Field(default=None, gt=0.0)  # ... the Gaussian's standard deviation in pixels (default 8; radius ceil(3 sigma) <= 64)
+    depth_resolution: Optional[int] = Field(default=None, ge=14, le=1036)  # ... "depth_anything": the side the estimator sees (default 518)
+    depth_normalize: Optional[Literal["minmax", "raw"]] = None  # ... its depth -> 0..255: each image's min..max (default) or clamp(depth, 0, 255)
     stream: Optional[bool] = None  # answer with application/x-ndjson progress lines and a final result line instead of the JPEG
     preview_every: Optional[int] = Field(default=None, ge=0)  # ... with a latent-resolution preview at every k-th model evaluation (0 = none)
 
@@ -210,8 +213,9 @@ def generate(args: GenerateArgs):
     `zero_init_steps` guidance shaping of a guided request, `source_prompt` (+ `source_guidance`, `edit_n_max` / `_min` / `_avg`) a FlowEdit edit of
     `init_image` towards `prompt`, `tile_size` (+ `tile_overlap`, `tile_weight`) tiled generation of a large canvas, `upscale` / `init_upscale` the
     configured super-resolution network on the output / on `init_image`, `control_preprocess` (+ `canny_low` / `canny_high` / `canny_l2`,
-    `blur_sigma`) the control map made on the device from a photo given as `control_image` / `controlnet_image` (a native Canny edge detector:
-    exact integer arithmetic, parity with OpenCV's binary unpinned; PIL's luma; a Gaussian blur).  Without them the call is exactly the reference's."""
+    `blur_sigma`, `depth_resolution` / `depth_normalize`) the control map made on the device from a photo given as `control_image` /
+    `controlnet_image` (a native Canny edge detector: exact integer arithmetic, parity with OpenCV's binary unpinned; PIL's luma; a Gaussian
+    blur; a Depth Anything depth map, parity with BFL's post-processing unpinned).  Without them the call is exactly the reference's."""
     kwargs = args.model_dump()
     stream = bool(kwargs.pop("stream", None))
     if kwargs.get("preview_every") is None:
@@ -224,7 +228,8 @@ def generate(args: GenerateArgs):
               "sigmas", "eta", "s_noise", "noise_seed", "ip_adapter_image", "ip_adapter_image_embeds", "ip_adapter_scale",
               "negative_ip_adapter_image", "negative_ip_adapter_scale", "guidance_mode", "guidance_rescale", "apg_eta", "apg_norm_threshold",
               "apg_momentum", "zero_init_steps", "source_prompt", "source_guidance", "edit_n_max", "edit_n_min", "edit_n_avg", "tile_size",
-              "tile_overlap", "tile_weight", "control_preprocess", "canny_low", "canny_high", "canny_l2", "blur_sigma"):
+              "tile_overlap", "tile_weight", "control_preprocess", "canny_low", "canny_high", "canny_l2", "blur_sigma", "depth_resolution",
+              "depth_normalize"):
         if kwargs.get(k) is None:
             kwargs.pop(k, None)
     for k in ("upscale", "init_upscale"):  # passed on only when asked for

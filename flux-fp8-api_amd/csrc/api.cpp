@@ -223,6 +223,26 @@ int fluxmi_gaussian_blur(const void* src, long long ld, long long bs, void* dst,
 int fluxmi_patchify(const void* pix, void* out, int B, int C, int H, int W, int patch, int grid, int Kp, void* stream) {
   return fluxmi_k_patchify(pix, out, B, C, H, W, patch, grid, Kp, (hipStream_t)stream);
 }
+int fluxmi_unary(const void* x, void* y, long long rows, int cols, long long ld_in, long long ld_out, int kind, void* stream) {
+  return fluxmi_k_unary(x, y, rows, cols, ld_in, ld_out, kind, (hipStream_t)stream);
+}
+int fluxmi_resize_bilinear(const void* x, long long ldx, void* out, long long ldo, const void* add, long long lda, int B, int Hi, int Wi, int Ho,
+                           int Wo, int C, void* stream) {
+  return fluxmi_k_resize_bilinear(x, ldx, out, ldo, add, lda, B, Hi, Wi, Ho, Wo, C, (hipStream_t)stream);
+}
+int fluxmi_patchify_rect(const void* pix, void* out, int B, int C, int H, int W, int patch, int grid_h, int grid_w, int Kp, void* stream) {
+  return fluxmi_k_patchify_rect(pix, out, B, C, H, W, patch, grid_h, grid_w, Kp, (hipStream_t)stream);
+}
+int fluxmi_im2col3x3_s2(const void* x, void* col, int B, int Hi, int Wi, int C, void* stream) {
+  return fluxmi_k_im2col3x3_s2(x, col, B, Hi, Wi, C, (hipStream_t)stream);
+}
+int fluxmi_depth_head(const void* x, long long ldx, int C, const void* w, const void* bias, float* out, long long n, void* stream) {
+  return fluxmi_k_depth_head(x, ldx, C, w, bias, out, n, (hipStream_t)stream);
+}
+int fluxmi_depth_to_map(const float* depth, long long ld, long long bs, void* out, long long out_ld, long long out_bs, float* work,
+                        long long work_bytes, int B, int h, int w, int H, int W, int normalize, void* stream) {
+  return fluxmi_k_depth_to_map(depth, ld, bs, out, out_ld, out_bs, work, work_bytes, B, h, w, H, W, normalize, (hipStream_t)stream);
+}
 int fluxmi_build_quant_lut(const float* scale, int fmt, int act, void* lut, void* stream) {
   return fluxmi_k_build_qlut(scale, fmt, act, lut, (hipStream_t)stream);
 }

@@ -258,6 +258,15 @@ int fluxmi_k_vision_attention(const void* q, const void* k, long long ld_qk, lon
                               void* out, long long ld_out, long long bs_out, const void* v_bias, float scale, int head_dim, int L, int Lp, int H,
                               int B, hipStream_t s);
 int fluxmi_k_patchify(const void* pix, void* out, int B, int C, int H, int W, int P, int G, int Kp, hipStream_t s);
+// the Depth Anything estimator's own kernels (depth.hip; include/fluxmi.h has the arithmetic): NHWC bf16 maps behind one pixel stride
+int fluxmi_k_unary(const void* x, void* y, long long rows, int cols, long long ld_in, long long ld_out, int kind, hipStream_t s);
+int fluxmi_k_resize_bilinear(const void* x, long long ldx, void* out, long long ldo, const void* add, long long lda, int B, int Hi, int Wi,
+                             int Ho, int Wo, int C, hipStream_t s);
+int fluxmi_k_patchify_rect(const void* pix, void* out, int B, int C, int H, int W, int P, int Gh, int Gw, int Kp, hipStream_t s);
+int fluxmi_k_im2col3x3_s2(const void* x, void* col, int B, int Hi, int Wi, int C, hipStream_t s);
+int fluxmi_k_depth_head(const void* x, long long ldx, int C, const void* w, const void* bias, float* out, long long n, hipStream_t s);
+int fluxmi_k_depth_to_map(const float* depth, long long ld, long long bs, void* out, long long out_ld, long long out_bs, float* work,
+                          long long work_bytes, int B, int h, int w, int H, int W, int normalize, hipStream_t s);
 int fluxmi_k_qkv_rope(const void* qkv, long long ld, const void* pe, const void* q_scale0, const void* k_scale0,
                       const void* q_scale1, const void* k_scale1, void* Q, void* K, void* VT, int B, int L, int Lp, int H,
                       int split, int k_f16, hipStream_t s);

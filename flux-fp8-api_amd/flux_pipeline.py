@@ -30,11 +30,11 @@ import lora_loading  # noqa: F401  (same import side as the reference)
 from fluxmi import dist as fdist
 from fluxmi import ops, solvers
 from modules.autoencoder import check_attention_mode
-from util import (ModelSpec, ModelVersion, engine_flow_dtype, into_device, into_dtype, load_config_from_path, load_controlnet, load_ip_adapter, load_upscaler,
+from util import (ModelSpec, ModelVersion, engine_flow_dtype, into_device, into_dtype, load_config_from_path, load_controlnet, load_depth_model, load_ip_adapter, load_upscaler,
                   load_models_from_config)
 
 MAX_RAND = 2**32 - 1
-CONTROL_PREPROCESSORS = ("canny", "gray", "blur")  # generate(control_preprocess=...) / preprocess_control: the maps made from a photo
+CONTROL_PREPROCESSORS = ("canny", "gray", "blur", "depth_anything")  # generate(control_preprocess=...) / preprocess_control: the maps made from a photo
 GUIDANCE_MODES = ("cfg", "apg", "cfg_zero_star")  # generate(guidance_mode=...): the rule that combines the two branches of true CFG
 
 # FLUX.1 Kontext's preferred reference resolutions, (width, height) (BFL flux, src/flux/sampling.py)
@@ -155,7 +155,7 @@ class FluxPipeline:
     def __init__(self, name: str, offload: bool = False, clip=None, t5=None, model=None, ae=None,
                  dtype: torch.dtype = torch.float16, verbose: bool = False, flux_device="cuda:0", ae_device="cuda:1",
                  clip_device="cuda:1", t5_device="cuda:1", config: ModelSpec = None, debug: bool = False, redux=None,
-                 controlnet=None, ip_adapter=None, upscaler=None):
+                 controlnet=None, ip_adapter=None, upscaler=None, depth_model=None):
         if config is None:
             raise ValueError("ModelSpec config is required!")
         self.debug, self.name, self.verbose, self.offload = debug, name, verbose, offload
@@ -170,6 +170,7 @@ class FluxPipeline:
         self.controlnet = controlnet  # FLUX ControlNet (modules/controlnet.FluxControlNet, config.controlnet_path) or None
         self.ip_adapter = ip_adapter  # FLUX IP-Adapter (modules/ip_adapter.IPAdapter, config.ip_adapter_path / clip_vision_path) or None
         self.upscaler = upscaler  # ESRGAN-family super-resolution network (modules/upscaler.RRDBNet, config.upscaler_path) or None
+        self.depth_model = depth_model  # Depth Anything depth estimator (modules/depth.DepthAnythingNative, config.depth_path) or None
         self.rng = torch.Generator(device="cpu")
         self.ae_dtype = torch.bfloat16
         self.config = config
@@ -456,8 +457,8 @@ class FluxPipeline:
         """FLUX.1 Depth / Canny [dev] -> img_cond bf16 [num_images, Li, 64] on the flow device (BFL's prepare_control, src/flux/sampling.py):
         the RGB control image is resized to (width, height) with PIL LANCZOS, goes to float / 127.5 - 1, is VAE-encoded with its Gaussian
         sample (drawn from `generator` after the noise, as in prepare_fill_conditioning), cast to bf16 and packed 2 x 2.  `control_image` is
-        the depth map or edge map itself.  An edge map can be made from a photo by preprocess_control(photo, "canny") (generate's
-        `control_preprocess`: a native Canny, where BFL calls OpenCV's); BFL's depth preprocessor (Depth Anything) is not part of this project."""
+        the depth map or edge map itself.  Either can be made from a photo by preprocess_control (generate's `control_preprocess`):
+        "canny", a native Canny where BFL calls OpenCV's, and "depth_anything", the native Depth Anything estimator of config.depth_path."""
         from PIL import Image
 
         if self.ae is None:
@@ -473,19 +474,38 @@ class FluxPipeline:
         """A ControlNet's `cond` bf16 [num_images, Li, 64] on the flow device (diffusers' FluxControlNetPipeline.prepare_image + the latent
         handling of its __call__): the control image, in any form `init_image` takes, is resized like `control_image`, VAE-encoded (its
         Gaussian sample drawn from `generator` after the noise), shifted and scaled, cast to bf16 and packed 2 x 2.  `controlnet_image` is
-        the edge map / depth map / pose itself.  The classical maps -- Canny edges, gray, blur -- can be made from a photo by
-        preprocess_control (generate's `control_preprocess`); preprocessors that need weights (depth, pose) are not part of this project."""
+        the edge map / depth map / pose itself.  Canny edges, gray, blur and a Depth Anything depth map (config.depth_path) can be made from
+        a photo by preprocess_control (generate's `control_preprocess`); a pose preprocessor is not part of this project."""
         if self.ae is None:
             raise RuntimeError("fluxmi: controlnet_image needs an autoencoder (config.ae_path) -- none is attached; pass controlnet_cond")
         return self.prepare_control_conditioning(controlnet_image, height, width, num_images=num_images, generator=generator)
 
     # ---- control-map preprocessors (csrc/preprocess.hip) ---------------------------------------------------------------------------------
-    @staticmethod
-    def _check_control_preprocess(kind, canny_low=100, canny_high=200, canny_l2=False, blur_sigma=8.0):
+    def _check_control_preprocess(self, kind, canny_low=100, canny_high=200, canny_l2=False, blur_sigma=8.0, depth_resolution=518,
+                                  depth_normalize="minmax", width=None, height=None):
         """the arguments of preprocess_control, refused by name before any work"""
         if kind not in CONTROL_PREPROCESSORS:
-            raise ValueError(f"fluxmi: control_preprocess={kind!r}: expected one of {CONTROL_PREPROCESSORS} (depth, pose and the other maps that "
-                             "need weights are not part of this project: pass the map itself)")
+            raise ValueError(f"fluxmi: control_preprocess={kind!r}: expected one of {CONTROL_PREPROCESSORS} (a depth map comes from "
+                             "\"depth_anything\", the Depth Anything estimator of config.depth_path; pose and the other maps that need weights are "
+                             "not part of this project: pass the map itself)")
+        if kind == "depth_anything":
+            from modules import depth as da
+
+            if getattr(self, "depth_model", None) is None:
+                raise ValueError("fluxmi: control_preprocess=\"depth_anything\" needs the Depth Anything estimator: set config.depth_path to a local "
+                                 "directory holding config.json and the weights of DepthAnythingForDepthEstimation (nothing is downloaded)")
+            if isinstance(depth_resolution, bool) or not isinstance(depth_resolution, int) or not da.DEPTH_RES_MIN <= depth_resolution <= da.DEPTH_RES_MAX:
+                raise ValueError(f"fluxmi: depth_resolution={depth_resolution!r}: expected an integer in {da.DEPTH_RES_MIN}..{da.DEPTH_RES_MAX} (the side "
+                                 "the estimator sees, rounded to a multiple of 14)")
+            if depth_normalize not in ops.DEPTH_NORMALIZE:
+                raise ValueError(f"fluxmi: depth_normalize={depth_normalize!r}: expected one of {tuple(ops.DEPTH_NORMALIZE)}")
+            if width is not None and height is not None:
+                w, h = da.depth_input_size(int(width), int(height), depth_resolution)
+                if (w // da.PATCH) * (h // da.PATCH) + 1 > da.MAX_TOKENS:
+                    raise ValueError(f"fluxmi: depth_resolution={depth_resolution} on a {width} x {height} image is a {h // da.PATCH} x {w // da.PATCH} "
+                                     f"patch grid, above the {da.MAX_TOKENS} tokens the estimator is checked at (74 x 74 + 1): lower depth_resolution")
+        elif (depth_resolution, depth_normalize) != (518, "minmax"):
+            raise ValueError("fluxmi: depth_resolution / depth_normalize belong to control_preprocess=\"depth_anything\"")
         try:
             ops.canny_thresholds(canny_low, canny_high)
         except ValueError as e:
@@ -500,7 +520,8 @@ class FluxPipeline:
 
     @torch.inference_mode()
     def preprocess_control(self, image, kind: str, width: Optional[int] = None, height: Optional[int] = None, canny_low: int = 100,
-                           canny_high: int = 200, canny_l2: bool = False, blur_sigma: float = 8.0) -> torch.Tensor:
+                           canny_high: int = 200, canny_l2: bool = False, blur_sigma: float = 8.0, depth_resolution: int = 518,
+                           depth_normalize: str = "minmax") -> torch.Tensor:
         """A photo -> the control map a FLUX.1 Canny [dev] checkpoint or a ControlNet follows: uint8 [H, W, 3] on the host.  `image`: any form
         `init_image` takes.  It is first resized to (width, height) with PIL LANCZOS, exactly as prepare_control_conditioning resizes a map
         (BFL runs its Canny after the resize too; None keeps the image's own size), then goes to the autoencoder's device and through one
@@ -511,14 +532,22 @@ class FluxPipeline:
                    theirs -- no threshold is recommended here.  `canny_l2`: squared-gradient magnitudes (OpenCV's L2gradient).
           "gray"   PIL's convert("L"), bit for bit
           "blur"   a Gaussian blur of standard deviation `blur_sigma` pixels (radius ceil(3 sigma) <= 64), replicated border
-        A one-channel result is repeated to three channels.  Depth, pose, tile and low-quality maps are not made here."""
+          "depth_anything"  the depth map of the Depth Anything estimator of config.depth_path (modules/depth.py; near = bright): the resized
+                   image goes through DPTImageProcessor's steps as the checkpoints configure them (PIL bicubic to the size of
+                   modules.depth.depth_input_size for `depth_resolution` -- the side closer to it becomes it, both sides multiples of 14 --,
+                   x / 255, ImageNet mean / std), the model, and fluxmi_depth_to_map back to the image's size: `depth_normalize` "minmax"
+                   maps the image's own min..max to 0..255 (the form diffusers' and the ControlNet annotators' depth maps take), "raw"
+                   writes clamp(depth, 0, 255).  Parity with BFL's DepthImageEncoder post-processing is NOT pinned.
+        A one-channel result is repeated to three channels.  Pose, tile and low-quality maps are not made here."""
         from PIL import Image
 
-        self._check_control_preprocess(kind, canny_low, canny_high, canny_l2, blur_sigma)
+        self._check_control_preprocess(kind, canny_low, canny_high, canny_l2, blur_sigma, depth_resolution, depth_normalize, width, height)
         pil = self._rgb_uint8(image).convert("RGB")
         size = (pil.width if width is None else int(width), pil.height if height is None else int(height))
         if size != pil.size:
             pil = pil.resize(size, Image.LANCZOS)
+        if kind == "depth_anything":
+            return self.depth_model.depth_map(pil, (size[1], size[0]), depth_resolution, depth_normalize).cpu()
         dev = self.device_ae if getattr(self, "ae", None) is not None else self.device_flux
         x = torch.from_numpy(np.array(pil)).to(dev)[None].contiguous()
         if kind == "canny":
@@ -763,7 +792,8 @@ class FluxPipeline:
                  on_step=None, preview_every: int = 0, preview_factors=None, source_prompt=None, source_guidance: Optional[float] = None,
                  edit_n_max: Optional[int] = None, edit_n_min: int = 0, edit_n_avg: int = 1, tile_size=None, tile_overlap: Optional[int] = None,
                  tile_weight: str = "cosine", upscale: bool = False, init_upscale: bool = False, control_preprocess: Optional[str] = None,
-                 canny_low: int = 100, canny_high: int = 200, canny_l2: bool = False, blur_sigma: float = 8.0):
+                 canny_low: int = 100, canny_high: int = 200, canny_l2: bool = False, blur_sigma: float = 8.0, depth_resolution: int = 518,
+                 depth_normalize: str = "minmax"):
         """`reference_image` (FLUX.1 Kontext [dev] instruction editing): an image the prompt describes an edit of, in any form `init_image`
         takes; see prepare_kontext_reference.  Composes with `init_image` / `strength` unchanged.
         FLUX.1 Fill [dev] (a model with 320 conditioning channels): `init_image` is the image to inpaint and `mask_image` (white =
@@ -906,7 +936,7 @@ class FluxPipeline:
         vae_attention="streaming" config.  Refused up front: either flag without a configured upscaler, `upscale` with
         output_type="latent" (or no VAE), `init_upscale` without `init_image`, an image the network's kernel or the device's free memory
         cannot take.  Both False (the default) is today's request, launch for launch.
-        `control_preprocess` ("canny" | "gray" | "blur"; preprocess_control): `control_image` (FLUX.1 Depth / Canny) or `controlnet_image` (a
+        `control_preprocess` ("canny" | "gray" | "blur" | "depth_anything"; preprocess_control): `control_image` (FLUX.1 Depth / Canny) or `controlnet_image` (a
         ControlNet) -- whichever the request carries -- is a PHOTO, and the control map is made from it on the device, after the resize to
         `width` x `height`, by a native Canny edge detector (`canny_low` / `canny_high` / `canny_l2`), PIL's luma, or a Gaussian blur
         (`blur_sigma`); the conditioning call then sees a correctly sized map.  The Canny is the integer definition of include/fluxmi.h:
@@ -914,7 +944,14 @@ class FluxPipeline:
         pipeline uses 50 / 200; neither is a recommendation.  Refused up front: `control_preprocess` without `control_image` /
         `controlnet_image`, with `img_cond` / `controlnet_cond` (already-encoded maps), an unknown kind, thresholds that are not integers
         >= 0, a `blur_sigma` whose radius ceil(3 sigma) is outside 1..64.  None (the default) is today's request, launch for launch, and
-        then refuses non-default `canny_*` / `blur_sigma`."""
+        then refuses non-default `canny_*` / `blur_sigma`.
+        `control_preprocess="depth_anything"` (+ `depth_resolution`, `depth_normalize`): the map is the depth map of the Depth Anything
+        estimator of config.depth_path (modules/depth.py; preprocess_control has the steps), e.g. generate(prompt, control_image=photo,
+        control_preprocess="depth_anything") on a FLUX.1 Depth [dev] model, or the same on `controlnet_image` with a Union ControlNet's depth
+        mode.  `depth_resolution` (default 518, DPTImageProcessor's) is the side the estimator sees, `depth_normalize` "minmax" (default) or
+        "raw".  Refused up front: the kind without a depth model (naming `depth_path`), a `depth_resolution` outside 14..1036, a patch grid
+        above 74 x 74 + 1 tokens (the longest sequence the estimator's attention is checked at), an unknown `depth_normalize`, and either
+        argument without the kind.  `control_preprocess="depth"` stays refused: the kind is named after its model."""
         if control_preprocess is not None:
             if img_cond is not None or controlnet_cond is not None:
                 raise ValueError("fluxmi: control_preprocess works on an image: it does not combine with img_cond / controlnet_cond (maps that "
@@ -922,10 +959,15 @@ class FluxPipeline:
             if control_image is None and controlnet_image is None:
                 raise ValueError("fluxmi: control_preprocess needs control_image (FLUX.1 Depth / Canny) or controlnet_image (a ControlNet): "
                                  "the photo to make the map from")
-            self._check_control_preprocess(control_preprocess, canny_low, canny_high, canny_l2, blur_sigma)
+            self._check_control_preprocess(control_preprocess, canny_low, canny_high, canny_l2, blur_sigma, depth_resolution, depth_normalize,
+                                           width, height)
         elif (canny_low, canny_high, canny_l2, blur_sigma) != (100, 200, False, 8.0):
             raise ValueError("fluxmi: canny_low / canny_high / canny_l2 / blur_sigma belong to control_preprocess, which is not set")
+        elif (depth_resolution, depth_normalize) != (518, "minmax"):
+            raise ValueError("fluxmi: depth_resolution / depth_normalize belong to control_preprocess=\"depth_anything\", which is not set")
         prep_kw = dict(canny_low=canny_low, canny_high=canny_high, canny_l2=canny_l2, blur_sigma=blur_sigma)
+        if control_preprocess == "depth_anything":  # the other kinds keep the call they always made
+            prep_kw.update(depth_resolution=depth_resolution, depth_normalize=depth_normalize)
         if upscale or init_upscale:
             init_image = self._check_upscale(upscale, init_upscale, output_type, init_image, width, height, num_images)
         tiles = self._check_tiles(locals())
@@ -1745,4 +1787,5 @@ class FluxPipeline:
                    flux_device=flux_device, ae_device=into_device(config.ae_device), clip_device=into_device(config.text_enc_device),
                    t5_device=into_device(config.text_enc_device), config=config, debug=debug, redux=redux,
                    controlnet=load_controlnet(config, device=flux_device), ip_adapter=load_ip_adapter(config, device=flux_device),
-                   upscaler=load_upscaler(config, device=into_device(config.ae_device)))
+                   upscaler=load_upscaler(config, device=into_device(config.ae_device)),
+                   depth_model=load_depth_model(config, device=into_device(config.ae_device)))

@@ -105,6 +105,12 @@ _SIGS = {
     "fluxmi_rgb_to_gray": ([vp, i64, i64, vp, i64, i64, i32, i32, i32, vp], i32),
     "fluxmi_gaussian_blur": ([vp, i64, i64, vp, i64, i64, vp, i64, i32, i32, i32, i32, f32, vp], i32),
     "fluxmi_patchify": ([vp, vp, i32, i32, i32, i32, i32, i32, i32, vp], i32),
+    "fluxmi_unary": ([vp, vp, i64, i32, i64, i64, i32, vp], i32),
+    "fluxmi_resize_bilinear": ([vp, i64, vp, i64, vp, i64, i32, i32, i32, i32, i32, i32, vp], i32),
+    "fluxmi_patchify_rect": ([vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp], i32),
+    "fluxmi_im2col3x3_s2": ([vp, vp, i32, i32, i32, i32, vp], i32),
+    "fluxmi_depth_head": ([vp, i64, i32, vp, vp, vp, i64, vp], i32),
+    "fluxmi_depth_to_map": ([vp, i64, i64, vp, i64, i64, vp, i64, i32, i32, i32, i32, i32, i32, vp], i32),
     "fluxmi_attention": ([vp, vp, vp, vp, i64, i32, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp], i32),
     "fluxmi_attention_grouped": ([vp, vp, vp, vp, i64, i32, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp], i32),
     "fluxmi_attention_rawq_grouped": ([vp, i64, vp, vp, vp, vp, vp, vp, i64, i32, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp], i32),

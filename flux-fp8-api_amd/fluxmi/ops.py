@@ -1059,3 +1059,150 @@ def gaussian_blur(img: torch.Tensor, sigma: float, out: Optional[torch.Tensor] =
     work = torch.empty(nbytes, dtype=torch.uint8, device=img.device)
     call("fluxmi_gaussian_blur", _p(img), ld, bs, _p(out), old, obs, _p(work), nbytes, B, H, W, ch, float(sigma), _stream())
     return out
+
+
+# ---- depth estimator pieces (csrc/depth.hip; NHWC bf16 maps behind one pixel stride) ------------------------------------------------------
+UNARY_KINDS = {"gelu": 0, "relu": 1}            # FLUXMI_UNARY_GELU_ERF / FLUXMI_UNARY_RELU
+DEPTH_NORMALIZE = {"minmax": 0, "raw": 1}       # FLUXMI_DEPTH_MINMAX / FLUXMI_DEPTH_RAW
+
+
+def unary(x: torch.Tensor, kind: str, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out = bf16(f(x)) elementwise in fp32 with one rounding (fluxmi_unary): kind "gelu" = the exact GELU 0.5 x (1 + erf(x / sqrt 2)),
+    "relu".  x bf16 [..., cols] whose leading dims collapse to rows of ONE stride (a column window of a wider buffer is fine), any cols;
+    `out`: a tensor of x's shape under the same rule (default: a new dense one; may be x)."""
+    _req(x, torch.bfloat16, "x")
+    if kind not in UNARY_KINDS:
+        raise ValueError(f"unary: kind={kind!r}: expected one of {tuple(UNARY_KINDS)}")
+    if out is None:
+        out = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
+    _req(out, torch.bfloat16, "out")
+    if tuple(out.shape) != tuple(x.shape):
+        raise ValueError(f"unary: out {tuple(out.shape)} does not match x {tuple(x.shape)}")
+    if x.numel() == 0:
+        return out
+
+    def rows_of(t, name):
+        cols = t.shape[-1]
+        if t.ndim < 1 or (cols > 1 and t.stride(-1) != 1):
+            raise ValueError(f"unary: {name} must have unit stride along its last dim, got strides {t.stride()}")
+        lead = [(n, s) for n, s in zip(t.shape[:-1], t.stride()[:-1]) if n > 1]
+        ld = lead[-1][1] if lead else cols
+        want = ld
+        for n, s in reversed(lead):
+            if s != want:
+                raise ValueError(f"unary: the rows of {name} must lie at ONE stride, got shape {tuple(t.shape)} / strides {t.stride()}")
+            want *= n
+        return ld
+
+    ldx, ldo = rows_of(x, "x"), rows_of(out, "out")
+    cols = x.shape[-1]
+    call("fluxmi_unary", _p(x), _p(out), x.numel() // cols, cols, ldx, ldo, UNARY_KINDS[kind], _stream())
+    return out
+
+
+def _depth_pixels(t: torch.Tensor, who: str, name: str):
+    """t: a bf16 [B, H, W, C] channel window of an NHWC pixel buffer with ONE pixel stride -> that stride in elements"""
+    _req(t, torch.bfloat16, f"{who}: {name}")
+    if t.ndim != 4 or min(t.shape) < 1 or t.stride(3) != 1:
+        raise ValueError(f"{who}: {name} must be a bf16 [B, H, W, C] view with channel stride 1, got {tuple(t.shape)} / {t.stride()}")
+    B, H, W, Cc = t.shape
+    ld = t.stride(2) if W > 1 else (t.stride(1) if H > 1 else (t.stride(0) if B > 1 else Cc + (-Cc) % 8))
+    if not ((W == 1 or t.stride(2) == ld) and (H == 1 or t.stride(1) == W * ld) and (B == 1 or t.stride(0) == H * W * ld)):
+        raise ValueError(f"{who}: {name} must address its pixels densely ([B][H][W] with ONE pixel stride), got strides {t.stride()}")
+    return ld
+
+
+def resize_bilinear(x: torch.Tensor, size, add: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x bf16 [B, Hi, Wi, C] (NHWC, or a channel window of a wider pixel buffer) -> [B, Ho, Wo, C], size = (Ho, Wo): the bilinear resize
+    with align_corners=True as torch computes it (fluxmi_resize_bilinear; include/fluxmi.h has the arithmetic), any sizes >= 1, C % 8 == 0.
+    `add` [B, Ho, Wo, C]: out = bf16(bf16(resize(x)) + add).  `out`: a [B, Ho, Wo, C] view to write (default: a new dense tensor)."""
+    ldx = _depth_pixels(x, "resize_bilinear", "x")
+    B, Hi, Wi, Cc = x.shape
+    Ho, Wo = int(size[0]), int(size[1])
+    if Ho < 1 or Wo < 1 or Cc % 8:
+        raise ValueError(f"resize_bilinear: size {tuple(size)} must be >= 1 x 1 and C = {Cc} a multiple of 8")
+    if out is None:
+        out = torch.empty((B, Ho, Wo, Cc), dtype=torch.bfloat16, device=x.device)
+    if tuple(out.shape) != (B, Ho, Wo, Cc):
+        raise ValueError(f"resize_bilinear: out {tuple(out.shape)} does not match {(B, Ho, Wo, Cc)}")
+    ldo = _depth_pixels(out, "resize_bilinear", "out")
+    lda = 0
+    if add is not None:
+        if tuple(add.shape) != (B, Ho, Wo, Cc):
+            raise ValueError(f"resize_bilinear: add {tuple(add.shape)} does not match {(B, Ho, Wo, Cc)}")
+        lda = _depth_pixels(add, "resize_bilinear", "add")
+    call("fluxmi_resize_bilinear", _p(x), ldx, _p(out), ldo, _p(add), lda, B, Hi, Wi, Ho, Wo, Cc, _stream())
+    return out
+
+
+def patchify_rect(pix: torch.Tensor, patch: int, grid_h: int, grid_w: int, k_pad: int) -> torch.Tensor:
+    """pix bf16 [B, C, H, W] -> patch rows [B*grid_h*grid_w, k_pad], column order (c, ky, kx), zero past C*patch*patch (fluxmi_patchify_rect)."""
+    _req(pix, torch.bfloat16, "pix")
+    pix = pix.contiguous()
+    B, Cc, H, W = pix.shape
+    out = torch.empty((B * grid_h * grid_w, k_pad), dtype=torch.bfloat16, device=pix.device)
+    call("fluxmi_patchify_rect", _p(pix), _p(out), B, Cc, H, W, int(patch), int(grid_h), int(grid_w), int(k_pad), _stream())
+    return out
+
+
+def conv3x3_s2_hw(Hi: int, Wi: int):
+    """the output grid of Conv2d(kernel 3, stride 2, padding 1)"""
+    return (Hi - 1) // 2 + 1, (Wi - 1) // 2 + 1
+
+
+def im2col3x3_s2(x: torch.Tensor) -> torch.Tensor:
+    """x bf16 [B, Hi, Wi, C] -> the patch matrix [B*Ho*Wo, 9*C] of Conv2d(kernel 3, stride 2, padding 1), column order (dy, dx, c), at odd
+    and even sizes (fluxmi_im2col3x3_s2)."""
+    _req(x, torch.bfloat16, "x")
+    x = x.contiguous()
+    B, Hi, Wi, Cc = x.shape
+    Ho, Wo = conv3x3_s2_hw(Hi, Wi)
+    col = torch.empty((B * Ho * Wo, 9 * Cc), dtype=torch.bfloat16, device=x.device)
+    call("fluxmi_im2col3x3_s2", _p(x), _p(col), B, Hi, Wi, Cc, _stream())
+    return col
+
+
+def conv3x3_s2(x: torch.Tensor, w2: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Conv2d(kernel 3, stride 2, padding 1) on NHWC bf16: x [B, Hi, Wi, C], w2 [Cout, 9*C] with K ordered (dy, dx, c) -> [B, Ho, Wo, Cout]:
+    the symmetric-pad stride-2 patch matrix, then the bf16 GEMM."""
+    B, Hi, Wi, _ = x.shape
+    Ho, Wo = conv3x3_s2_hw(Hi, Wi)
+    return linear(im2col3x3_s2(x), w2, bias).view(B, Ho, Wo, w2.shape[0])
+
+
+def depth_head(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x bf16 [B, H, W, C] (a channel window is fine), w bf16 [C], bias bf16 [1] -> fp32 [B, H, W] = relu(x . w + bias), accumulated and
+    stored in fp32 (fluxmi_depth_head: the head's last 1x1 convolution + ReLU)."""
+    ldx = _depth_pixels(x, "depth_head", "x")
+    _req(w, torch.bfloat16, "w")
+    B, H, W, Cc = x.shape
+    if w.numel() != Cc or not w.is_contiguous() or Cc % 8:
+        raise ValueError(f"depth_head: w needs C = {Cc} contiguous entries, C a multiple of 8")
+    out = torch.empty((B, H, W), dtype=torch.float32, device=x.device)
+    call("fluxmi_depth_head", _p(x), ldx, Cc, _p(w), _p(bias), _p(out), B * H * W, _stream())
+    return out
+
+
+def depth_to_map(depth: torch.Tensor, size, normalize: str = "minmax", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """depth fp32 [B, h, w] -> uint8 [B, H, W, 3], size = (H, W): half-pixel bilinear resize, normalisation, floor(v + 0.5) clamped to
+    0..255, written to all three channels (fluxmi_depth_to_map).  normalize "minmax": each image's own min..max of the SOURCE depth -> 0..255
+    (a constant image gives 0), from a deterministic two-launch reduction; "raw": clamp(depth, 0, 255).  `out`: a uint8 [B, H, W, 3] view
+    with adjacent pixels (a window of a larger buffer is fine)."""
+    _req(depth, torch.float32, "depth")
+    if normalize not in DEPTH_NORMALIZE:
+        raise ValueError(f"depth_to_map: normalize={normalize!r}: expected one of {tuple(DEPTH_NORMALIZE)}")
+    if depth.ndim != 3 or min(depth.shape) < 1 or (depth.shape[2] > 1 and depth.stride(2) != 1):
+        raise ValueError(f"depth_to_map: depth must be fp32 [B, h, w] with unit column stride, got {tuple(depth.shape)} / {depth.stride()}")
+    B, h, w = depth.shape
+    H, W = int(size[0]), int(size[1])
+    if H < 1 or W < 1:
+        raise ValueError(f"depth_to_map: size {tuple(size)} must be >= 1 x 1")
+    ld = depth.stride(1) if h > 1 else w
+    bs = depth.stride(0) if B > 1 else h * ld
+    if ld < w or bs < h * ld:
+        raise ValueError(f"depth_to_map: depth rows / images overlap (strides {depth.stride()})")
+    out, old, obs = _u8_out(out, (B, H, W, 3), depth, "depth_to_map", "out", 3)
+    nbytes = B * ((h * w + 4095) // 4096 + 1) * 8  # FLUXMI_DEPTH_MAP_WORK_BYTES
+    work = torch.empty(nbytes // 4, dtype=torch.float32, device=depth.device)
+    call("fluxmi_depth_to_map", _p(depth), ld, bs, _p(out), old, obs, _p(work), nbytes, B, h, w, H, W, DEPTH_NORMALIZE[normalize], _stream())
+    return out

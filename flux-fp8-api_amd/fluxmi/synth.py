@@ -216,3 +216,93 @@ def make_rrdbnet_state_dict(num_block: int = 2, nf: int = 64, gc: int = 32, scal
             _, i, rdb, cv = base.split(".")
             old[f"model.1.sub.{i}.RDB{rdb[3:]}.conv{cv[4:]}.0.{leaf}"] = v
     return old
+
+
+# the Depth Anything geometries of the three released sizes (LiheYoung/depth-anything-{small,base,large}-hf and the V2 checkpoints)
+DEPTH_ANYTHING_SIZES = {
+    "small": dict(hidden_size=384, num_attention_heads=6, num_hidden_layers=12, out_indices=[3, 6, 9, 12], neck_hidden_sizes=[48, 96, 192, 384],
+                  fusion_hidden_size=64),
+    "base": dict(hidden_size=768, num_attention_heads=12, num_hidden_layers=12, out_indices=[3, 6, 9, 12], neck_hidden_sizes=[96, 192, 384, 768],
+                 fusion_hidden_size=128),
+    "large": dict(hidden_size=1024, num_attention_heads=16, num_hidden_layers=24, out_indices=[5, 12, 18, 24],
+                  neck_hidden_sizes=[256, 512, 1024, 1024], fusion_hidden_size=256),
+}
+
+
+def depth_anything_config(size: str = "large", **over) -> dict:
+    """the config.json of a Depth Anything checkpoint of that size, as a dict (DepthAnythingConfig with an inline Dinov2Config)"""
+    g = dict(DEPTH_ANYTHING_SIZES[size])
+    g.update(over)
+    bc = dict(model_type="dinov2", hidden_size=g["hidden_size"], num_attention_heads=g["num_attention_heads"],
+              num_hidden_layers=g["num_hidden_layers"], image_size=518, patch_size=14, out_indices=list(g["out_indices"]), apply_layernorm=True,
+              reshape_hidden_states=False, mlp_ratio=4, layerscale_value=1.0)
+    return dict(model_type="depth_anything", backbone_config=bc, reassemble_hidden_size=g["hidden_size"], reassemble_factors=[4, 2, 1, 0.5],
+                neck_hidden_sizes=list(g["neck_hidden_sizes"]), fusion_hidden_size=g["fusion_hidden_size"], head_hidden_size=g.get("head_hidden_size", 32),
+                patch_size=14, depth_estimation_type="relative")
+
+
+def make_depth_anything_state_dict(config: dict, seed: int = 0, dtype=torch.float32) -> Dict[str, torch.Tensor]:
+    """A synthetic transformers DepthAnythingForDepthEstimation state dict for a config.json dict (depth_anything_config; the tests' tiny
+    geometry).  transformers' own initialisation (std 0.02 everywhere) gives a depth of about 4e-5 that the last ReLU mostly zeroes; here
+    every layer preserves variance instead, so that each branch reaches the output at O(1): linears and 1 x 1 convolutions at 1 /
+    sqrt(fan_in), convolutions in front of a ReLU'd consumer at sqrt(2 / fan_in), LayerNorm gains around 1, LayerScale 0.3 +- 0.1 (non-zero:
+    both residual branches count), and a head whose last convolution has non-negative weights and a positive bias, so that the depth is
+    positive nearly everywhere and still varies over the image."""
+    gen = torch.Generator().manual_seed(seed + 49979687)
+    bc = config["backbone_config"]
+    D, P = bc["hidden_size"], bc.get("patch_size", 14)
+    Fd, n_pos = int(D * bc.get("mlp_ratio", 4)), (bc.get("image_size", 518) // P) ** 2 + 1
+    Fh, Hh = config["fusion_hidden_size"], config.get("head_hidden_size", 32)
+    rn = lambda *shape, s=1.0: (s * torch.randn(*shape, generator=gen)).to(dtype)  # noqa: E731
+    sd = {}
+
+    def ln(name):
+        sd[name + ".weight"] = (1.0 + 0.1 * torch.randn(D, generator=gen)).to(dtype)
+        sd[name + ".bias"] = rn(D, s=0.05)
+
+    def lin(name, n_out, n_in):
+        sd[name + ".weight"] = rn(n_out, n_in, s=1.0 / math.sqrt(n_in))
+        sd[name + ".bias"] = rn(n_out, s=0.05)
+
+    def conv(name, n_out, n_in, k, gain=1.0, bias=True):
+        sd[name + ".weight"] = rn(n_out, n_in, k, k, s=gain / math.sqrt(n_in * k * k))
+        if bias:
+            sd[name + ".bias"] = rn(n_out, s=0.05)
+
+    e = "backbone.embeddings."
+    sd[e + "cls_token"] = rn(1, 1, D, s=0.5)
+    sd[e + "mask_token"] = torch.zeros(1, D, dtype=dtype)
+    sd[e + "position_embeddings"] = rn(1, n_pos, D, s=0.1)
+    conv(e + "patch_embeddings.projection", D, 3, P)
+    for i in range(bc["num_hidden_layers"]):
+        p = f"backbone.encoder.layer.{i}."
+        ln(p + "norm1")
+        for n in ("query", "key", "value"):
+            lin(p + f"attention.attention.{n}", D, D)
+        lin(p + "attention.output.dense", D, D)
+        sd[p + "layer_scale1.lambda1"] = (0.3 + 0.1 * torch.randn(D, generator=gen)).to(dtype)
+        ln(p + "norm2")
+        lin(p + "mlp.fc1", Fd, D)
+        lin(p + "mlp.fc2", D, Fd)
+        sd[p + "layer_scale2.lambda1"] = (0.3 + 0.1 * torch.randn(D, generator=gen)).to(dtype)
+    ln("backbone.layernorm")
+    g2 = math.sqrt(2.0)
+    for i, (ch, f) in enumerate(zip(config["neck_hidden_sizes"], config.get("reassemble_factors", [4, 2, 1, 0.5]))):
+        p = f"neck.reassemble_stage.layers.{i}."
+        conv(p + "projection", ch, D, 1)
+        if f > 1:  # ConvTranspose2d weight [Cin, Cout, f, f]: every output pixel sums Cin products
+            sd[p + "resize.weight"] = rn(ch, ch, int(f), int(f), s=1.0 / math.sqrt(ch))
+            sd[p + "resize.bias"] = rn(ch, s=0.05)
+        elif f < 1:
+            conv(p + "resize", ch, ch, 3)
+        conv(f"neck.convs.{i}", Fh, ch, 3, bias=False)
+        q = f"neck.fusion_stage.layers.{i}."
+        conv(q + "projection", Fh, Fh, 1)
+        for n in ("residual_layer1", "residual_layer2"):
+            conv(f"{q}{n}.convolution1", Fh, Fh, 3, gain=g2)   # reads relu(x)
+            conv(f"{q}{n}.convolution2", Fh, Fh, 3, gain=0.5 * g2)  # the residual branch at half the stream's size
+    conv("head.conv1", Fh // 2, Fh, 3)
+    conv("head.conv2", Hh, Fh // 2, 3)
+    sd["head.conv3.weight"] = (torch.rand(1, Hh, 1, 1, generator=gen) * (2.0 / Hh)).to(dtype)
+    sd["head.conv3.bias"] = torch.full((1,), 0.25, dtype=dtype)
+    return sd

@@ -87,6 +87,10 @@ class ModelSpec(BaseModel):  # reference util.py:38-79 (unknown JSON keys are ig
     # an ESRGAN-family super-resolution network (RRDBNet: ESRGAN, Real-ESRGAN x4plus / x2plus, 4x-UltraSharp ...; modules/upscaler.py): a
     # LOCAL .safetensors or .pth file.  Nothing is downloaded; FluxPipeline.upscaler is None unless the file exists
     upscaler_path: str | None = None
+    # the Depth Anything depth estimator of control_preprocess="depth_anything" (modules/depth.py): a LOCAL directory in the HF layout
+    # (config.json + model.safetensors / *.bin of DepthAnythingForDepthEstimation, e.g. a copy of LiheYoung/depth-anything-large-hf).
+    # Nothing is downloaded; FluxPipeline.depth_model is None unless the directory exists
+    depth_path: str | None = None
 
     model_config: ConfigDict = {"arbitrary_types_allowed": True, "use_enum_values": True}
 
@@ -403,6 +407,19 @@ def load_upscaler(config: ModelSpec, device=None):
     from modules.upscaler import read_upscaler
 
     return read_upscaler(path, device=into_device(device if device is not None else config.ae_device))
+
+
+def load_depth_model(config: ModelSpec, device=None):
+    """The Depth Anything estimator of config.depth_path (modules/depth.DepthAnythingNative) in bf16 on `device`, or None unless the path is
+    a local directory.  Nothing is downloaded.  A config the native model does not cover is refused by name (modules.depth.resolve_config)."""
+    import os
+
+    path = getattr(config, "depth_path", None)
+    if not (isinstance(path, str) and os.path.isdir(path)):
+        return None
+    from modules.depth import read_depth_anything
+
+    return read_depth_anything(path).to(device=into_device(device if device is not None else config.ae_device), dtype=torch.bfloat16)
 
 
 def load_models_from_config(config: ModelSpec, state_dict=None, ae_state_dict=None, clip_kwargs=None, t5_kwargs=None) -> LoadedModels:

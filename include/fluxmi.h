@@ -484,6 +484,54 @@ int fluxmi_rgb_to_gray(const void* rgb, long long ld, long long bs, void* gray, 
 int fluxmi_gaussian_blur(const void* src, long long ld, long long bs, void* dst, long long dst_ld, long long dst_bs, void* work,
                          long long work_bytes, int B, int H, int W, int C, float sigma, void* stream);
 
+/* ---- depth estimator pieces (csrc/depth.hip; modules/depth.py: Depth Anything = a DINOv2 tower + a DPT decoder) -----------------------
+ * The tower runs on the vision-encoder entry points above, the decoder's stride-1 convolutions on fluxmi_conv3x3 / fluxmi_conv3x3_dense; what
+ * those do not cover is here.  Maps are NHWC bf16: [B][H][W] pixels addressed densely with ONE pixel stride `ld` in elements (ld >= C,
+ * ld %% 8 == 0, 16-byte aligned pointers), so an operand may be a channel window of a wider buffer; channels outside [0, C) of a pixel are
+ * neither read nor written.  Every function is deterministic (no atomics, fixed order), a sample's bits depend on that sample alone, and
+ * all address arithmetic is 64-bit.
+ *
+ * fluxmi_unary: y[r][c] = bf16(f(x[r][c])) for rows of `cols` bf16 values with row strides ld_in, ld_out (>= cols), f in fp32, ONE rounding:
+ *   FLUXMI_UNARY_GELU_ERF  0.5 x (1 + erf(x * 0.70710678118654752440f))   (torch's exact GELU; fluxmi_act's mode 0 is the tanh form)
+ *   FLUXMI_UNARY_RELU      x > 0 ? x : 0                                   (a NaN gives 0)
+ *   Any cols >= 1: full groups of 8 columns move as 16 bytes when both pointers are 16-byte aligned and both strides multiples of 8, the
+ *   tail (and everything otherwise) element by element.  y may be x.
+ * fluxmi_resize_bilinear: x [B][Hi][Wi] -> out [B][Ho][Wo], C channels (C %% 8 == 0), align_corners=True, any sizes >= 1.  Per axis, as
+ *   torch computes it:  scale = fp32(in - 1) / fp32(out - 1) (0 when out == 1);  src = scale * fp32(o), in fp32;  i0 = (int)src, clamped to
+ *   in - 1;  i1 = i0 + 1 unless i0 == in - 1, then i0;  l = src - i0;  h = 1 - l.  With a, b = x(y0, x0), x(y0, x1) and c, d = x(y1, x0), x(y1, x1):
+ *     top = hx * a + lx * b;   bot = hx * c + lx * d;   v = hy * top + ly * bot        each product and sum rounded to fp32 (no fma contraction
+ *   is relied on: the gate of tests/test_depth_gpu.py covers either);  out = bf16(v).  Equal sizes give scale 1 and l = 0: out == x exactly.
+ *   With `add` ([B][Ho][Wo] pixels, stride add_ld; NULL = none):  out = bf16(fp32(bf16(v)) + add)  -- torch's bf16 tensor sum.  out != x.
+ * fluxmi_patchify_rect: fluxmi_patchify for a grid_h x grid_w grid: row (b, gy, gx), column c*patch*patch + ky*patch + kx, zero past C*patch*patch.
+ * fluxmi_im2col3x3_s2: x [B, Hi, Wi, C] dense -> col [B*Ho*Wo, 9*C], Ho = (Hi - 1) / 2 + 1, Wo likewise, column (dy*3+dx)*C + c = input pixel
+ *   (2 yo + dy - 1, 2 xo + dx - 1), zero outside the image: the patch matrix of Conv2d(kernel 3, stride 2, padding 1) at odd and even sizes
+ *   (fluxmi_im2col3x3's -2 mode pads right / bottom only and needs even sizes).  The convolution is then the bf16 GEMM.  C %% 8 == 0.
+ * fluxmi_depth_head: out[p] = max(0, sum_c x[p][c] * w[c] + bias[0]) for n pixels (stride ldx), fp32: acc = fma(x_c, w_c, acc) from 0 with c
+ *   ascending, then + bias, then the ReLU; out fp32 [n], NOT rounded to bf16.  w bf16 [C], bias bf16 [1] or NULL, C %% 8 == 0 (the caller
+ *   zero-pads).  This is the head's last 1x1 convolution + ReLU of a relative-depth model.
+ * fluxmi_depth_to_map: depth fp32 [B][h][w] (row stride ld, image stride bs, in elements) -> out uint8 [B][H][W][3] (row stride out_ld, image
+ *   stride out_bs, in bytes; out_ld >= 3 W), the value written to all three channels.  Half-pixel bilinear (align_corners=False), per axis as
+ *   torch computes it:  scale = fp32(in) / fp32(out);  src = max(scale * (o + 0.5) - 0.5, 0);  i0, i1, l, h and the four-tap blend v as above.
+ *     FLUXMI_DEPTH_MINMAX  t = (v - mn) * s, with mn / mx the minimum / maximum of THIS image's SOURCE depth (not the resized one) and
+ *                          s = 255 / (mx - mn) in fp32, s = 0 for a constant image (which therefore gives 0 everywhere)
+ *     FLUXMI_DEPTH_RAW     t = v
+ *   byte = clamp(floor(t + 0.5), 0, 255) (a NaN gives 0).  The minimum and maximum come from two launches -- per-chunk partials of 4096
+ *   elements, then one workgroup per image over the partials, each a fixed tree -- into `work` (fp32, 4-byte aligned,
+ *   FLUXMI_DEPTH_MAP_WORK_BYTES(B, h, w) bytes; unused and may be NULL for FLUXMI_DEPTH_RAW).  B, H <= 65535. */
+#define FLUXMI_UNARY_GELU_ERF 0
+#define FLUXMI_UNARY_RELU 1
+#define FLUXMI_DEPTH_MINMAX 0
+#define FLUXMI_DEPTH_RAW 1
+#define FLUXMI_DEPTH_MAP_WORK_BYTES(B, h, w) ((long long)(B) * ((((long long)(h) * (w) + 4095) / 4096) + 1) * 8)
+int fluxmi_unary(const void* x, void* y, long long rows, int cols, long long ld_in, long long ld_out, int kind, void* stream);
+int fluxmi_resize_bilinear(const void* x, long long ldx, void* out, long long ldo, const void* add, long long add_ld, int B, int Hi, int Wi, int Ho,
+                           int Wo, int C, void* stream);
+int fluxmi_patchify_rect(const void* pix, void* out, int B, int C, int H, int W, int patch, int grid_h, int grid_w, int Kp, void* stream);
+int fluxmi_im2col3x3_s2(const void* x, void* col, int B, int Hi, int Wi, int C, void* stream);
+int fluxmi_depth_head(const void* x, long long ldx, int C, const void* w, const void* bias, float* out, long long n, void* stream);
+int fluxmi_depth_to_map(const float* depth, long long ld, long long bs, void* out, long long out_ld, long long out_bs, float* work,
+                        long long work_bytes, int B, int h, int w, int H, int W, int normalize, void* stream);
+
 /* ---- step scalars -------------------------------------------------------------------------------------- */
 /* timestep_embedding(t, 2*half) with host-provided frequency table                 flux_model.py:95-116 */
 int fluxmi_timestep_embedding(const void* t, const float* freqs, void* out, int B, int half, float time_factor, void* stream);

@@ -1,14 +1,13 @@
 // fluxmi -- the kernels of the Depth Anything depth estimator (gfx950; modules/depth.py) that the ViT / VAE / upscaler kernels do not cover:
-// the DPT decoder's align-corners bilinear resampling on odd-sized NHWC maps, exact GELU / ReLU, the patch rows of a rectangular grid, the
-// symmetric-pad stride-2 gather of the last reassemble layer, the head's 1x1 convolution to one fp32 channel, and depth -> uint8 control map.
+// the DPT decoder's align-corners bilinear resampling on odd-sized NHWC maps, exact GELU / ReLU, the head's 1x1 convolution to one fp32
+// channel, and depth -> uint8 control map.  (The patch rows of its rectangular grid are text.hip's fluxmi_patchify_rect, the symmetric-pad
+// stride-2 gather of the last reassemble layer vae.hip's fluxmi_im2col3x3_s2.)
 // The arithmetic of every function is stated in include/fluxmi.h.  All of them are bandwidth-sized: one thread moves 16 bytes along C, a
 // 1-D grid-stride loop with 64-bit indices walks the output, nothing is staged in LDS except the block reductions of the min / max.
 //
 // unary_kernel            8 columns per thread; a row's tail (cols % 8) and rows whose address or stride is not 16-byte aligned go element
 //                         by element.  Nothing outside [0, cols) of a row is read or written.
 // resize_bilinear_kernel  one output pixel x 8 channels per thread: four 16-byte loads, the blend in fp32, one 16-byte store.
-// patchify_rect_kernel    fluxmi_patchify's gather for a gh x gw grid.
-// im2col_s2_kernel        fluxmi_im2col3x3's gather with stride 2 and one zero row / column on EVERY side (Conv2d(stride=2, padding=1)).
 // depth_head_kernel       one pixel per thread: dot of its C channels with the weight in fp32, + bias, ReLU, an fp32 store.
 // minmax_partial_kernel / minmax_final_kernel   per-image min / max of the depth: fixed chunks, a fixed tree, no atomics.
 // depth_to_map_kernel     four output pixels (12 bytes) per thread: half-pixel bilinear source, normalise, round, three equal channels.
@@ -104,49 +103,6 @@ __global__ void __launch_bounds__(256) resize_bilinear_kernel(const u16* __restr
       for (int j = 0; j < 8; ++j) o[j] = rbf(o[j]) + e[j];
     }
     *(uint4*)(out + pix * ldo + cc * 8) = pack8(o);
-  }
-}
-
-__global__ void __launch_bounds__(256) patchify_rect_kernel(const u16* __restrict__ pix, u16* __restrict__ out, int B, int C, int H, int W, int P,
-                                                            int Gh, int Gw, int Kp) {
-  const int k8 = Kp >> 3, kc = C * P * P;
-  const long long total = (long long)B * Gh * Gw * k8;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-    const long long row = i / k8;
-    const int c0 = (int)(i % k8) * 8;
-    const int b = (int)(row / (Gh * Gw)), t = (int)(row % (Gh * Gw)), gy = t / Gw, gx = t % Gw;
-    unsigned short v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int col = c0 + j;
-      v[j] = 0;
-      if (col < kc) {
-        const int c = col / (P * P), r = col % (P * P), ky = r / P, kx = r % P;
-        v[j] = pix[(((long long)b * C + c) * H + gy * P + ky) * W + gx * P + kx];
-      }
-    }
-    *(uint4*)(out + row * Kp + c0) = make_uint4(v[0] | (unsigned)v[1] << 16, v[2] | (unsigned)v[3] << 16, v[4] | (unsigned)v[5] << 16,
-                                                v[6] | (unsigned)v[7] << 16);
-  }
-}
-
-__global__ void __launch_bounds__(256) im2col_s2_kernel(const u16* __restrict__ x, u16* __restrict__ col, int B, int Hi, int Wi, int Ho, int Wo,
-                                                        int C) {
-  const int c8 = C >> 3;
-  const long long total = (long long)B * Ho * Wo * 9 * c8;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-    const int cc = (int)(i % c8);
-    long long r = i / c8;
-    const int tap = (int)(r % 9);
-    r /= 9;
-    const int xo = (int)(r % Wo);
-    r /= Wo;
-    const int yo = (int)(r % Ho);
-    const long long b = r / Ho;
-    const int yy = 2 * yo + tap / 3 - 1, xx = 2 * xo + tap % 3 - 1;
-    uint4 v = make_uint4(0, 0, 0, 0);
-    if (yy >= 0 && yy < Hi && xx >= 0 && xx < Wi) v = *(const uint4*)(x + ((b * Hi + yy) * Wi + xx) * C + cc * 8);
-    *(uint4*)(col + i * 8) = v;
   }
 }
 
@@ -305,28 +261,6 @@ int fluxmi_k_resize_bilinear(const void* x, long long ldx, void* out, long long 
   const float sy = Ho > 1 ? (float)(Hi - 1) / (float)(Ho - 1) : 0.f, sx = Wo > 1 ? (float)(Wi - 1) / (float)(Wo - 1) : 0.f;
   hipLaunchKernelGGL(resize_bilinear_kernel, dim3(grid_for((long long)B * Ho * Wo * (C / 8))), dim3(256), 0, s, (const u16*)x, ldx, (u16*)out,
                      ldo, (const u16*)add, lda, B, Hi, Wi, Ho, Wo, C, sy, sx);
-  FLUXMI_LAUNCH_CHECK();
-  return 0;
-}
-
-int fluxmi_k_patchify_rect(const void* pix, void* out, int B, int C, int H, int W, int P, int Gh, int Gw, int Kp, hipStream_t s) {
-  FLUXMI_REQUIRE(pix && out && B > 0 && C > 0 && P > 0 && Gh > 0 && Gw > 0 && Gh * P <= H && Gw * P <= W,
-                 "patchify_rect: a %dx%d grid of %d-pixel patches needs H >= %d, W >= %d (got %dx%d)", Gh, Gw, P, Gh * P, Gw * P, H, W);
-  FLUXMI_REQUIRE(Kp % 8 == 0 && Kp >= C * P * P && aligned16(out), "patchify_rect: Kp=%d must be a multiple of 8 and >= C*P*P=%d, out 16-byte "
-                 "aligned", Kp, C * P * P);
-  hipLaunchKernelGGL(patchify_rect_kernel, dim3(grid_for((long long)B * Gh * Gw * (Kp / 8))), dim3(256), 0, s, (const u16*)pix, (u16*)out, B, C,
-                     H, W, P, Gh, Gw, Kp);
-  FLUXMI_LAUNCH_CHECK();
-  return 0;
-}
-
-int fluxmi_k_im2col3x3_s2(const void* x, void* col, int B, int Hi, int Wi, int C, hipStream_t s) {
-  FLUXMI_REQUIRE(B >= 1 && Hi >= 1 && Wi >= 1 && C >= 8 && C % 8 == 0, "im2col3x3_s2: B=%d, Hi=%d, Wi=%d must be >= 1 and C=%d a multiple of 8",
-                 B, Hi, Wi, C);
-  FLUXMI_REQUIRE(x && col && aligned16(x) && aligned16(col), "im2col3x3_s2: x and col must be 16-byte aligned device pointers");
-  const int Ho = (Hi - 1) / 2 + 1, Wo = (Wi - 1) / 2 + 1;
-  hipLaunchKernelGGL(im2col_s2_kernel, dim3(grid_for((long long)B * Ho * Wo * 9 * (C / 8))), dim3(256), 0, s, (const u16*)x, (u16*)col, B, Hi, Wi,
-                     Ho, Wo, C);
   FLUXMI_LAUNCH_CHECK();
   return 0;
 }

@@ -228,6 +228,7 @@ int fluxmi_k_set_timestep(void* t_vec, const float* ts, const int* step, int B, 
 int fluxmi_k_advance_step(int* step, hipStream_t s);
 int fluxmi_k_clock_sample(unsigned long long* out2, hipStream_t s);
 int fluxmi_k_im2col3x3(const void* x, void* col, int B, int H, int W, int C, int up, hipStream_t s);
+int fluxmi_k_im2col3x3_s2(const void* x, void* col, int B, int Hi, int Wi, int C, hipStream_t s);
 int fluxmi_k_groupnorm(const void* x, const void* gamma, const void* beta, void* y, float* work, int B, int P, int C, int swish, float eps,
                        hipStream_t s);
 int fluxmi_k_softmax_rows(const void* S, void* P, int rows, int cols, long long ld, float scale, hipStream_t s);
@@ -258,12 +259,11 @@ int fluxmi_k_vision_attention(const void* q, const void* k, long long ld_qk, lon
                               void* out, long long ld_out, long long bs_out, const void* v_bias, float scale, int head_dim, int L, int Lp, int H,
                               int B, hipStream_t s);
 int fluxmi_k_patchify(const void* pix, void* out, int B, int C, int H, int W, int P, int G, int Kp, hipStream_t s);
+int fluxmi_k_patchify_rect(const void* pix, void* out, int B, int C, int H, int W, int P, int Gh, int Gw, int Kp, hipStream_t s);
 // the Depth Anything estimator's own kernels (depth.hip; include/fluxmi.h has the arithmetic): NHWC bf16 maps behind one pixel stride
 int fluxmi_k_unary(const void* x, void* y, long long rows, int cols, long long ld_in, long long ld_out, int kind, hipStream_t s);
 int fluxmi_k_resize_bilinear(const void* x, long long ldx, void* out, long long ldo, const void* add, long long lda, int B, int Hi, int Wi,
                              int Ho, int Wo, int C, hipStream_t s);
-int fluxmi_k_patchify_rect(const void* pix, void* out, int B, int C, int H, int W, int P, int Gh, int Gw, int Kp, hipStream_t s);
-int fluxmi_k_im2col3x3_s2(const void* x, void* col, int B, int Hi, int Wi, int C, hipStream_t s);
 int fluxmi_k_depth_head(const void* x, long long ldx, int C, const void* w, const void* bias, float* out, long long n, hipStream_t s);
 int fluxmi_k_depth_to_map(const float* depth, long long ld, long long bs, void* out, long long out_ld, long long out_bs, float* work,
                           long long work_bytes, int B, int h, int w, int H, int W, int normalize, hipStream_t s);

@@ -8,7 +8,8 @@
 //   * text_attention self-attention for head_dim 64, L <= 1024: bf16 MFMA, fp32 softmax, additive relative-position bias (T5: a
 //                    function of key - query only, so the [H, L, L] tensor is never built) or causal mask + scale (CLIP);
 //   * vision_attention the same kernel over a batch of images, also at head width 96 (SigLIP-so400m's 72, zero-padded per head at load
-//                    time by modules/image_embedders.py), and patchify, the im2col of SigLIP's stride-14 patch embedding.
+//                    time by modules/encoder_common.py), and patchify / patchify_rect, the im2col of the vision towers' stride-P patch
+//                    embedding: one gather kernel for a Gh x Gw grid, the square entry point passing Gh = Gw = G.
 // The attention kernel needs no LDS: with the "swapped" product S^T = K . Q^T a lane owns one query and 16 of a tile's 32 keys, the
 // bf16 P values it produces are exactly a B operand of O^T += V^T . P^T once the contraction index of that MFMA is taken in the
 // lane's own key order -- and V^T (which the v-projection GEMM writes directly by swapping its operands) then supplies the matching
@@ -208,16 +209,16 @@ __global__ void __launch_bounds__(256) text_attention_kernel(const TextAttnArgs 
 }
 
 // ---- patch embedding: NCHW pixels -> patch rows ----------------------------------------------------------------------------------
-// row (b, gy, gx) of out [B*G*G, Kp], column c*P*P + ky*P + kx = pix[b][c][gy*P + ky][gx*P + kx] (a Conv2d weight [N, C, P, P] flattened
-// row-major); columns C*P*P .. Kp-1 are zero.  Pixels past G*P (a "valid" convolution's unread border) are never read.
-__global__ void __launch_bounds__(256) patchify_kernel(const u16* __restrict__ pix, u16* __restrict__ out, int B, int C, int H, int W, int P,
-                                                       int G, int Kp) {
+// row (b, gy, gx) of out [B*Gh*Gw, Kp], column c*P*P + ky*P + kx = pix[b][c][gy*P + ky][gx*P + kx] (a Conv2d weight [N, C, P, P] flattened
+// row-major); columns C*P*P .. Kp-1 are zero.  Pixels past Gh*P, Gw*P (a "valid" convolution's unread border) are never read.
+__global__ void __launch_bounds__(256) patchify_rect_kernel(const u16* __restrict__ pix, u16* __restrict__ out, int B, int C, int H, int W, int P,
+                                                            int Gh, int Gw, int Kp) {
   const int k8 = Kp >> 3, kc = C * P * P;
-  const long long total = (long long)B * G * G * k8;
+  const long long total = (long long)B * Gh * Gw * k8;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
     const long long row = i / k8;
     const int c0 = (int)(i % k8) * 8;
-    const int b = (int)(row / (G * G)), t = (int)(row % (G * G)), gy = t / G, gx = t % G;
+    const int b = (int)(row / (Gh * Gw)), t = (int)(row % (Gh * Gw)), gy = t / Gw, gx = t % Gw;
     unsigned short v[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
@@ -296,11 +297,24 @@ int fluxmi_k_vision_attention(const void* q, const void* k, long long ld_qk, lon
   return launch_attention(a, head_dim, H, B, 1, s);
 }
 
+static int launch_patchify(const void* pix, void* out, int B, int C, int H, int W, int P, int Gh, int Gw, int Kp, hipStream_t s) {
+  hipLaunchKernelGGL(patchify_rect_kernel, dim3(grid1d((long long)B * Gh * Gw * (Kp / 8))), dim3(256), 0, s, (const u16*)pix, (u16*)out, B, C, H, W,
+                     P, Gh, Gw, Kp);
+  FLUXMI_LAUNCH_CHECK();
+  return 0;
+}
+
 int fluxmi_k_patchify(const void* pix, void* out, int B, int C, int H, int W, int P, int G, int Kp, hipStream_t s) {
   FLUXMI_REQUIRE(B > 0 && C > 0 && P > 0 && G > 0 && G * P <= H && G * P <= W, "patchify: a %dx%d grid of %d-pixel patches needs H, W >= %d (got %dx%d)",
                  G, G, P, G * P, H, W);
   FLUXMI_REQUIRE(Kp % 8 == 0 && Kp >= C * P * P, "patchify: Kp=%d must be a multiple of 8 and >= C*P*P=%d", Kp, C * P * P);
-  hipLaunchKernelGGL(patchify_kernel, dim3(grid1d((long long)B * G * G * (Kp / 8))), dim3(256), 0, s, (const u16*)pix, (u16*)out, B, C, H, W, P, G, Kp);
-  FLUXMI_LAUNCH_CHECK();
-  return 0;
+  return launch_patchify(pix, out, B, C, H, W, P, G, G, Kp, s);
+}
+
+int fluxmi_k_patchify_rect(const void* pix, void* out, int B, int C, int H, int W, int P, int Gh, int Gw, int Kp, hipStream_t s) {
+  FLUXMI_REQUIRE(pix && out && B > 0 && C > 0 && P > 0 && Gh > 0 && Gw > 0 && Gh * P <= H && Gw * P <= W,
+                 "patchify_rect: a %dx%d grid of %d-pixel patches needs H >= %d, W >= %d (got %dx%d)", Gh, Gw, P, Gh * P, Gw * P, H, W);
+  FLUXMI_REQUIRE(Kp % 8 == 0 && Kp >= C * P * P && ((uintptr_t)out & 15) == 0, "patchify_rect: Kp=%d must be a multiple of 8 and >= C*P*P=%d, "
+                 "out 16-byte aligned", Kp, C * P * P);
+  return launch_patchify(pix, out, B, C, H, W, P, Gh, Gw, Kp, s);
 }

@@ -22,6 +22,7 @@ namespace {
 //   up = 1 : stride 1, pad 1                                   (Hi = H)
 //   up = 2 : nearest 2x upsample, then stride 1, pad 1          (Hi = H/2;  Upsample.forward, reference :117-119)
 //   up = -2: stride 2, zero pad (0,1,0,1) = right/bottom only   (Hi = 2H;   Downsample.forward, reference :103-107)
+//   fluxmi_im2col3x3_s2: stride 2, pad 1 on every side          (H = (Hi - 1) / 2 + 1, any Hi;  Conv2d(stride=2, padding=1), modules/depth.py)
 // i.e. source row = (yo*stride + dy - pad) / rep, zero outside [0, Hi*rep).
 __global__ void __launch_bounds__(256) im2col3x3_kernel(const u16* __restrict__ x, u16* __restrict__ col, int B, int H, int W, int C, int Hi, int Wi,
                                                         int stride, int pad, int rep) {
@@ -212,6 +213,17 @@ int fluxmi_k_im2col3x3(const void* x, void* col, int B, int H, int W, int C, int
   const int Hi = up == 2 ? H / 2 : up == -2 ? H * 2 : H, Wi = up == 2 ? W / 2 : up == -2 ? W * 2 : W;
   const int stride = up == -2 ? 2 : 1, pad = up == -2 ? 0 : 1, rep = up == 2 ? 2 : 1;
   hipLaunchKernelGGL(im2col3x3_kernel, dim3(grid1d(total)), dim3(256), 0, s, (const u16*)x, (u16*)col, B, H, W, C, Hi, Wi, stride, pad, rep);
+  FLUXMI_LAUNCH_CHECK();
+  return 0;
+}
+
+int fluxmi_k_im2col3x3_s2(const void* x, void* col, int B, int Hi, int Wi, int C, hipStream_t s) {
+  FLUXMI_REQUIRE(B >= 1 && Hi >= 1 && Wi >= 1 && C >= 8 && C % 8 == 0, "im2col3x3_s2: B=%d, Hi=%d, Wi=%d must be >= 1 and C=%d a multiple of 8",
+                 B, Hi, Wi, C);
+  FLUXMI_REQUIRE(x && col && (((uintptr_t)x | (uintptr_t)col) & 15) == 0, "im2col3x3_s2: x and col must be 16-byte aligned device pointers");
+  const int Ho = (Hi - 1) / 2 + 1, Wo = (Wi - 1) / 2 + 1;
+  hipLaunchKernelGGL(im2col3x3_kernel, dim3(grid1d((long long)B * Ho * Wo * 9 * (C / 8))), dim3(256), 0, s, (const u16*)x, (u16*)col, B, Ho, Wo, C,
+                     Hi, Wi, 2, 1, 1);
   FLUXMI_LAUNCH_CHECK();
   return 0;
 }

@@ -25,41 +25,11 @@ from typing import Optional
 import torch
 from torch import Tensor, nn
 
+from modules.encoder_common import CLIP_LAYER, _bf, _Cache, _lin, _Weight, clip_encoder_layers, encoder_layer, layer_weights, text_attend
+
 
 def _pad32(n: int) -> int:
     return (n + 31) // 32 * 32
-
-
-class _Weight(nn.Module):
-    """A module that only owns `weight` (T5LayerNorm / relative_attention_bias / embeddings keep the HF key names)."""
-
-    def __init__(self, *shape):
-        super().__init__()
-        self.weight = nn.Parameter(torch.ones(*shape), requires_grad=False)
-
-
-def _lin(i, o, bias):
-    m = nn.Linear(i, o, bias=bias)
-    m.requires_grad_(False)
-    return m
-
-
-class _Cache:
-    """Fused / derived weights, rebuilt when the source parameter object or device changes."""
-
-    def __init__(self):
-        self._d = {}
-
-    def get(self, key, srcs, fn):
-        ent = self._d.get(key)
-        if ent is None or any(a is not b for a, b in zip(ent[0], srcs)) or ent[1].device != srcs[0].device:
-            ent = (tuple(srcs), fn())
-            self._d[key] = ent
-        return ent[1]
-
-
-def _bf(t: Tensor) -> Tensor:
-    return t.detach().to(torch.bfloat16).contiguous()
 
 
 def _gemm(a, w, bias=None, resid=None, ones=None):
@@ -184,16 +154,7 @@ class _ClipTextTransformer(nn.Module):
         self.embeddings.token_embedding = _Weight(c["vocab_size"], D)
         self.embeddings.position_embedding = _Weight(c.get("max_position_embeddings", 77), D)
         self.encoder = nn.Module()
-        self.encoder.layers = nn.ModuleList()
-        for _ in range(c["num_hidden_layers"]):
-            lay = nn.Module()
-            lay.self_attn = nn.Module()
-            for n in ("q_proj", "k_proj", "v_proj", "out_proj"):
-                setattr(lay.self_attn, n, _lin(D, D, True))
-            lay.layer_norm1, lay.layer_norm2 = nn.LayerNorm(D), nn.LayerNorm(D)
-            lay.mlp = nn.Module()
-            lay.mlp.fc1, lay.mlp.fc2 = _lin(D, Fd, True), _lin(Fd, D, True)
-            self.encoder.layers.append(lay)
+        self.encoder.layers = clip_encoder_layers(c["num_hidden_layers"], D, Fd, c["layer_norm_eps"])
         self.final_layer_norm = nn.LayerNorm(D)
         self.requires_grad_(False)
 
@@ -229,6 +190,11 @@ class ClipTextNative(nn.Module):
     def device(self):
         return self.text_model.final_layer_norm.weight.device
 
+    def padded_weights(self, i) -> dict:
+        """bf16 weights of layer i as the kernels take them (q | k fused), built once; heads of 64 and the MLP need no padding"""
+        c = self.cfg
+        return layer_weights(self._cache, self.text_model.encoder.layers[i], CLIP_LAYER, i, c["num_attention_heads"], 64, 64, c["intermediate_size"])
+
     @torch.inference_mode()
     def forward(self, input_ids: Tensor, attention_mask=None, output_hidden_states: bool = False, **_):
         from fluxmi import ops
@@ -246,27 +212,13 @@ class ClipTextNative(nn.Module):
         tok = ck.get("tok", [tm.embeddings.token_embedding.weight], lambda: _bf(tm.embeddings.token_embedding.weight))
         pos = ck.get("pos", [tm.embeddings.position_embedding.weight], lambda: _bf(tm.embeddings.position_embedding.weight))
         ones = ck.get("ones", [tm.final_layer_norm.weight], lambda: torch.ones(D, dtype=torch.bfloat16, device=dev))
+        attend, quick_gelu = text_attend(L, H), lambda f: ops.act_mul(f, gated=False)  # noqa: E731
         hid, pooled = [], []
         for b in range(B):
             x = torch.zeros(Lp, D, dtype=torch.bfloat16, device=dev)
             x[:L] = tok[input_ids[b]] + pos[:L]
-            for i, lay in enumerate(tm.encoder.layers):
-                sa, mlp = lay.self_attn, lay.mlp
-                wqk = ck.get(("qk", i), [sa.q_proj.weight, sa.k_proj.weight], lambda: torch.cat([_bf(sa.q_proj.weight), _bf(sa.k_proj.weight)], 0))
-                bqk = ck.get(("bqk", i), [sa.q_proj.bias, sa.k_proj.bias], lambda: torch.cat([_bf(sa.q_proj.bias), _bf(sa.k_proj.bias)], 0))
-                p = {}
-                for name, t in (("wv", sa.v_proj.weight), ("bv", sa.v_proj.bias), ("wo", sa.out_proj.weight), ("bo", sa.out_proj.bias),
-                                ("w1", mlp.fc1.weight), ("b1", mlp.fc1.bias), ("w2", mlp.fc2.weight), ("b2", mlp.fc2.bias),
-                                ("g1", lay.layer_norm1.weight), ("e1", lay.layer_norm1.bias), ("g2", lay.layer_norm2.weight),
-                                ("e2", lay.layer_norm2.bias)):
-                    p[name] = ck.get((name, i), [t], lambda t=t: _bf(t))
-                h = ops.row_norm(x, p["g1"], p["e1"], eps=eps, rms=False)
-                qk = _gemm(h, wqk, bqk)
-                vt = _gemm(p["wv"], h)                                # V^T without its bias: rows of P sum to 1 -> added after P V
-                o = ops.text_attention(qk[:, :D], qk[:, D:], vt, L, H, scale=64 ** -0.5, causal=True, v_bias=p["bv"])
-                x = _gemm(o, p["wo"], p["bo"], resid=x, ones=ones)
-                h = ops.row_norm(x, p["g2"], p["e2"], eps=eps, rms=False)
-                x = _gemm(ops.act_mul(_gemm(h, p["w1"], p["b1"]), gated=False), p["w2"], p["b2"], resid=x, ones=ones)
+            for i in range(len(tm.encoder.layers)):
+                x = encoder_layer(x, self.padded_weights(i), attend, quick_gelu, eps, ones, ones)
             g, e = (ck.get((n, "fin"), [t], lambda t=t: _bf(t)) for n, t in (("g", tm.final_layer_norm.weight), ("e", tm.final_layer_norm.bias)))
             x = ops.row_norm(x, g, e, eps=eps, rms=False)[:L]
             ids = input_ids[b].to(torch.int)

@@ -18,7 +18,7 @@ The model is transformers' `DepthAnythingForDepthEstimation`, kept here in one p
   4. head: 3 x 3 convolution to fusion / 2 at 8g, bilinear align_corners=True to (14 gh, 14 gw), 3 x 3 convolution to head_hidden_size +
      ReLU, 1 x 1 convolution to one channel + ReLU -> predicted_depth [B, 14 gh, 14 gw] (times max_depth = 1).
 
-On libfluxmi: the tower is the SigLIP / CLIP towers' scheme (modules/image_embedders.py: fluxmi_patchify_rect + the bf16 GEMM,
+On libfluxmi: the tower is the SigLIP / CLIP towers' scheme (modules/encoder_common.py: fluxmi_patchify_rect + the bf16 GEMM,
 fluxmi_row_norm, q | k as one GEMM, V^T from the swapped v-projection, fluxmi_vision_attention at head width 64) with LayerScale as the gate
 of the GEMM's gate * y + x epilogue, where those towers pass ones, and fluxmi_unary for the exact GELU.  The decoder is NHWC bf16 throughout:
 1 x 1 convolutions are GEMMs on the pixel rows; a ConvTranspose with kernel = stride = f is a GEMM to f * f * C' columns (row order
@@ -46,7 +46,8 @@ import torch.nn.functional as F
 from torch import Tensor, nn
 
 from modules.conditioner import _bf, _Cache, _lin, _read_dir_weights
-from modules.image_embedders import _pad_to, _round_up, pad_heads, to_pil
+from modules.encoder_common import DINOV2_LAYER, encoder_layer, layer_weights, normalize_image, patch_embed, vision_attend
+from modules.image_embedders import _pad_to, _round_up, to_pil
 
 PATCH = 14
 IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)  # DPTImageProcessor's image_mean / image_std of the checkpoints
@@ -225,7 +226,6 @@ class DepthAnythingNative(nn.Module):
         self.head.conv3 = nn.Conv2d(c["head_hidden_size"], 1, 1)
         self.requires_grad_(False)
         self._cache = _Cache()
-        self._decoder = None
 
     def load_state_dict(self, sd, strict=True, assign=False):
         return super().load_state_dict({k: v for k, v in sd.items() if not k.endswith("embeddings.mask_token")}, strict=strict, assign=assign)
@@ -290,7 +290,6 @@ class DepthAnythingNative(nn.Module):
 
     def _kernel_weights(self) -> dict:
         """bf16 weights of the neck and the head in the layouts the kernels take, from padded_state_dict(), built once"""
-        srcs = [p for p in list(self.neck.parameters()) + list(self.head.parameters())]
 
         def build():
             sd = self.padded_state_dict()
@@ -318,40 +317,17 @@ class DepthAnythingNative(nn.Module):
             k["ones"] = torch.ones(self.padded_sizes()["fusion"], dtype=torch.bfloat16, device=sd["head.conv3.bias"].device)
             return k
 
-        # (a dict, so _Cache's rule is restated here: rebuilt when a parameter object or the device changes)
-        ent = self._decoder
-        if ent is None or len(ent[0]) != len(srcs) or any(a is not b for a, b in zip(ent[0], srcs)) or ent[1] != srcs[0].device:
-            ent = self._decoder = (tuple(srcs), srcs[0].device, build())
-        return ent[2]
+        return self._cache.get("decoder", list(self.neck.parameters()) + list(self.head.parameters()), build)
 
     def layer_weights(self, i) -> dict:
         """bf16 weights of backbone layer i (or i = "embed") as the kernels take them, built once"""
         bb, ck = self.backbone, self._cache
         bc = self.cfg["backbone_config"]
-        H, hd, hp = bc["num_attention_heads"], self.head_dim, 64
         if i == "embed":
             pe = bb.embeddings.patch_embeddings.projection
             return dict(w=ck.get("patch_w", [pe.weight], lambda: _pad_to(_bf(pe.weight).reshape(pe.weight.shape[0], -1), self.patch_k, 1).contiguous()),
                         b=ck.get("patch_b", [pe.bias], lambda: _bf(pe.bias)))
-        lay = bb.encoder.layer[i]
-        sa, mlp = lay.attention.attention, lay.mlp
-        ph = lambda t, dim=0: pad_heads(_bf(t), H, hd, hp, dim).contiguous()  # noqa: E731
-        od = lay.attention.output.dense
-        p = dict(
-            wqk=ck.get(("wqk", i), [sa.query.weight, sa.key.weight], lambda: torch.cat([ph(sa.query.weight), ph(sa.key.weight)], 0)),
-            bqk=ck.get(("bqk", i), [sa.query.bias, sa.key.bias], lambda: torch.cat([ph(sa.query.bias), ph(sa.key.bias)], 0)),
-            wv=ck.get(("wv", i), [sa.value.weight], lambda: ph(sa.value.weight)),
-            bv=ck.get(("bv", i), [sa.value.bias], lambda: ph(sa.value.bias)),
-            wo=ck.get(("wo", i), [od.weight], lambda: ph(od.weight, 1)),
-            bo=ck.get(("bo", i), [od.bias], lambda: _bf(od.bias)),
-            w1=ck.get(("w1", i), [mlp.fc1.weight], lambda: _pad_to(_bf(mlp.fc1.weight), self.mlp_pad, 0).contiguous()),
-            b1=ck.get(("b1", i), [mlp.fc1.bias], lambda: _pad_to(_bf(mlp.fc1.bias), self.mlp_pad, 0).contiguous()),
-            w2=ck.get(("w2", i), [mlp.fc2.weight], lambda: _pad_to(_bf(mlp.fc2.weight), self.mlp_pad, 1).contiguous()),
-            b2=ck.get(("b2", i), [mlp.fc2.bias], lambda: _bf(mlp.fc2.bias)))
-        for name, t in (("g1", lay.norm1.weight), ("e1", lay.norm1.bias), ("g2", lay.norm2.weight), ("e2", lay.norm2.bias),
-                        ("l1", lay.layer_scale1.lambda1), ("l2", lay.layer_scale2.lambda1)):
-            p[name] = ck.get((name, i), [t], lambda t=t: _bf(t))
-        return p
+        return layer_weights(ck, bb.encoder.layer[i], DINOV2_LAYER, i, bc["num_attention_heads"], self.head_dim, 64, self.mlp_pad)
 
     def position_rows(self, gh: int, gw: int):
         """(class row bf16 [D] = bf16(cls_token + pos[0]), patch rows bf16 [gh gw, D]) on the model's device; interpolated once per grid on the
@@ -369,20 +345,18 @@ class DepthAnythingNative(nn.Module):
     @torch.inference_mode()
     def features(self, pixel_values: Tensor) -> list:
         """the backbone: pixel_values [B, 3, 14 gh, 14 gw] -> the tapped hidden states, each bf16 [B, gh, gw, D] (NHWC, dense)"""
-        from fluxmi import _lib, ops
-
-        from modules.image_embedders import _linear_groups
+        from fluxmi import ops
 
         dev = self.device
         if dev.type != "cuda":
             raise RuntimeError("fluxmi: the Depth Anything estimator needs the GPU (libfluxmi has no CPU path)")
         bc, ck, bb = self.cfg["backbone_config"], self._cache, self.backbone
-        D, H, eps, hp = bc["hidden_size"], bc["num_attention_heads"], bc["layer_norm_eps"], 64
+        D, H, eps = bc["hidden_size"], bc["num_attention_heads"], bc["layer_norm_eps"]
         pix = pixel_values.to(device=dev, dtype=torch.bfloat16)
         if pix.dim() != 4 or pix.shape[1] != 3 or pix.shape[2] < PATCH or pix.shape[3] < PATCH or pix.shape[2] % PATCH or pix.shape[3] % PATCH:
             raise ValueError(f"fluxmi: Depth Anything takes pixel_values [B, 3, 14 gh, 14 gw] with gh, gw >= 1, got {tuple(pixel_values.shape)}")
         B, gh, gw = pix.shape[0], pix.shape[2] // PATCH, pix.shape[3] // PATCH
-        G, L, Lp = gh * gw, gh * gw + 1, self.seq_pad(gh, gw)
+        L, Lp = gh * gw + 1, self.seq_pad(gh, gw)
         if L > MAX_TOKENS:
             raise ValueError(f"fluxmi: a {gh} x {gw} patch grid is {L} tokens, above the {MAX_TOKENS} the estimator is checked at (74 x 74 + 1): "
                              "lower the resolution")
@@ -390,28 +364,14 @@ class DepthAnythingNative(nn.Module):
         cls_row, pos_rows = self.position_rows(gh, gw)
         # row 0 of each image's Lp-row slab: the class row; rows 1 .. G: bf16(pos + bf16(conv)); the rest zero (finite through every layer)
         e = self.layer_weights("embed")
-        patches = ops.patchify_rect(pix, PATCH, gh, gw, self.patch_k)
-        x = torch.zeros(B, Lp, D, dtype=torch.bfloat16, device=dev)
-        _linear_groups([patches[b * G:(b + 1) * G] for b in range(B)], e["w"], [x[b, 1:L] for b in range(B)], e["b"],
-                       resid_rows=[pos_rows] * B, ones=ones)
-        x[:, 0] = cls_row
-        x = x.view(B * Lp, D)
+        x = patch_embed(pix, PATCH, gh, gw, self.patch_k, e["w"], e["b"], pos_rows, cls_row, Lp, ones)
         g_f, e_f = (ck.get((n, "final"), [t], lambda t=t: _bf(t)) for n, t in (("g", bb.layernorm.weight), ("e", bb.layernorm.bias)))
+        attend, gelu = vision_attend(B, L, Lp, H, self.head_dim, 64), lambda f: ops.unary(f, "gelu", out=f)  # noqa: E731
         taps = []
         for i in range(max(bc["out_indices"])):
             p = self.layer_weights(i)
-            h = ops.row_norm(x, p["g1"], p["e1"], eps=eps, rms=False)
-            qk = ops.linear(h, p["wqk"], p["bqk"]).view(B, Lp, 2 * H * hp)
-            vt = torch.empty(B, H * hp, Lp, dtype=torch.bfloat16, device=dev)
-            for b in range(B):  # V^T = W_v . h_b^T per image (the SigLIP tower's scheme); its bias is added after P V
-                ops.linear(p["wv"], h[b * Lp:(b + 1) * Lp], out=vt[b])
-            o = ops.vision_attention(qk[:, :, : H * hp], qk[:, :, H * hp:], vt, L, H, hp, self.head_dim ** -0.5, v_bias=p["bv"])
-            # LayerScale: x + lambda * (o W^T + b) is the gate * y + x epilogue with the gate lambda
-            x = ops.linear(o.view(B * Lp, H * hp), p["wo"], p["bo"], epilogue=_lib.EPI_GATE_RESID, gate=p["l1"], resid=x, out=torch.empty_like(x))
-            h = ops.row_norm(x, p["g2"], p["e2"], eps=eps, rms=False)
-            f = ops.linear(h, p["w1"], p["b1"])
-            ops.unary(f, "gelu", out=f)
-            x = ops.linear(f, p["w2"], p["b2"], epilogue=_lib.EPI_GATE_RESID, gate=p["l2"], resid=x, out=torch.empty_like(x))
+            # LayerScale: x + lambda * (y W^T + b) is the gate * y + x epilogue with the gate lambda
+            x = encoder_layer(x, p, attend, gelu, eps, p["l1"], p["l2"])
             if i + 1 in bc["out_indices"]:
                 y = ops.row_norm(x, g_f, e_f, eps=eps, rms=False) if bc["apply_layernorm"] else x
                 taps.append(y.view(B, Lp, D)[:, 1:L].reshape(B, gh, gw, D))
@@ -477,9 +437,7 @@ class DepthAnythingNative(nn.Module):
         size = depth_input_size(pil.width, pil.height, resolution)
         if size != pil.size:
             pil = pil.resize(size, resample=Image.BICUBIC)
-        a = (np.asarray(pil).astype(np.float64) * (1 / 255)).astype(np.float32)
-        a = (a - np.array(IMAGENET_MEAN, dtype=np.float32)) / np.array(IMAGENET_STD, dtype=np.float32)
-        return torch.from_numpy(np.ascontiguousarray(a.transpose(2, 0, 1)))[None]
+        return normalize_image(np.asarray(pil), IMAGENET_MEAN, IMAGENET_STD)
 
     @torch.inference_mode()
     def depth_map(self, image, size=None, resolution: int = 518, normalize: str = "minmax") -> Tensor:

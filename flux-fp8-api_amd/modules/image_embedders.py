@@ -13,8 +13,8 @@ What Redux computes (BFL `ReduxImageEncoder.__call__` + `prepare_redux`, src/flu
 
 The encoder runs on libfluxmi: every Linear on the bf16 MFMA GEMM (residual adds and the position embedding in its gate*y+x epilogue
 with a ones gate), LayerNorm = `fluxmi_row_norm`, gelu_tanh / silu = `fluxmi_act`, attention = `fluxmi_vision_attention` (all images of a
-call in one launch), the patch embedding = `fluxmi_patchify` + the GEMM.  So that every GEMM takes a tiled config, weights are padded
-once at load time (exact: the pads are zeros):
+call in one launch), the patch embedding = `fluxmi_patchify_rect` + the GEMM; modules/encoder_common.py has the layer, shared with the
+other towers.  So that every GEMM takes a tiled config, weights are padded once at load time (exact: the pads are zeros):
   * heads of 72 -> 96: q / k / v weight rows and biases per head, out_proj's columns per head.  Zero q / k columns add nothing to q.k,
     zero V^T rows and v_bias entries give zero output columns, and out_proj's zero columns drop them;
   * fc1 rows / bias and fc2 columns to a multiple of 256 (4304 -> 4352): gelu_tanh(0) = 0;
@@ -33,7 +33,10 @@ import numpy as np
 import torch
 from torch import Tensor, nn
 
-from modules.conditioner import _bf, _Cache, _lin, _read_dir_weights, _Weight
+from modules.conditioner import _read_dir_weights
+from modules.encoder_common import (CLIP_LAYER, _bf, _Cache, _lin, _linear_groups, _pad_to, _round_up, _Weight,  # noqa: F401  (re-exported)
+                                    clip_encoder_layers, encoder_layer, layer_weights, normalize_image, pad_heads, padded_head_dim, patch_embed,
+                                    unpad_heads, vision_attend)
 
 # google/siglip-so400m-patch14-384 (the vision tower FLUX.1 Redux was trained on); keys left out of a config mean SiglipVisionConfig's
 # defaults, as transformers reads them
@@ -41,65 +44,6 @@ SIGLIP_SO400M_384 = dict(hidden_size=1152, intermediate_size=4304, num_hidden_la
                          image_size=384, patch_size=14, hidden_act="gelu_pytorch_tanh", layer_norm_eps=1e-6)
 _SIGLIP_DEFAULTS = dict(hidden_size=768, intermediate_size=3072, num_hidden_layers=12, num_attention_heads=12, num_channels=3,
                         image_size=224, patch_size=16, hidden_act="gelu_pytorch_tanh", layer_norm_eps=1e-6)
-
-
-def _round_up(n: int, m: int) -> int:
-    return (n + m - 1) // m * m
-
-
-def padded_head_dim(head_dim: int) -> int:
-    """the head width fluxmi_vision_attention runs a head of `head_dim` at (64 or 96; SigLIP-so400m's 72 -> 96)"""
-    if head_dim <= 64:
-        return 64
-    if head_dim <= 96:
-        return 96
-    raise ValueError(f"fluxmi: vision attention covers head_dim <= 96, got {head_dim}")
-
-
-def pad_heads(t: Tensor, heads: int, hd: int, hp: int, dim: int = 0) -> Tensor:
-    """rows (dim 0) or columns (dim 1) of H heads of hd -> H heads of hp, zero-filled per head"""
-    if dim == 0:
-        x = t.reshape(heads, hd, *t.shape[1:])
-        out = x.new_zeros((heads, hp) + tuple(x.shape[2:]))
-        out[:, :hd] = x
-        return out.reshape(heads * hp, *t.shape[1:])
-    x = t.reshape(t.shape[0], heads, hd)
-    out = x.new_zeros(t.shape[0], heads, hp)
-    out[:, :, :hd] = x
-    return out.reshape(t.shape[0], heads * hp)
-
-
-def unpad_heads(t: Tensor, heads: int, hd: int, hp: int, dim: int = 0) -> Tensor:
-    if dim == 0:
-        return t.reshape(heads, hp, *t.shape[1:])[:, :hd].reshape(heads * hd, *t.shape[1:])
-    return t.reshape(t.shape[0], heads, hp)[:, :, :hd].reshape(t.shape[0], heads * hd)
-
-
-def _pad_to(t: Tensor, n: int, dim: int = 0) -> Tensor:
-    if t.shape[dim] == n:
-        return t
-    shape = list(t.shape)
-    shape[dim] = n
-    out = t.new_zeros(shape)
-    out.narrow(dim, 0, t.shape[dim]).copy_(t)
-    return out
-
-
-def _linear_groups(rows_a, w, out_rows, bias=None, resid_rows=None, ones=None):
-    """One GEMM launch over groups (<= 16 per launch): out_rows[i] = rows_a[i] . w^T (+ bias) (+ resid_rows[i], through the gate*y+x
-    epilogue with a ones gate).  Each item is a 2-D view with unit column stride."""
-    from fluxmi import _lib, ops
-
-    N, K = w.shape
-    epi = _lib.EPI_BF16 if resid_rows is None else _lib.EPI_GATE_RESID
-    for i0 in range(0, len(rows_a), 16):
-        gs = []
-        for i in range(i0, min(i0 + 16, len(rows_a))):
-            a, c = rows_a[i], out_rows[i]
-            r = None if resid_rows is None else resid_rows[i]
-            gs.append(ops.make_group(ops._p(a), ops._p(w), ops._p(bias), None, None, ops._p(c), a.shape[0], a.stride(0), c.stride(0),
-                                     gate=ops._p(ones), resid=ops._p(r), ldr=r.stride(0) if r is not None else 0))
-        ops.gemm_grouped(gs, N, K, False, _lib.E5M2, epi)
 
 
 # ---- SigLIP vision tower ------------------------------------------------------------------------------------------------------------
@@ -111,16 +55,7 @@ class _SiglipVisionTransformer(nn.Module):
         self.embeddings.patch_embedding = nn.Conv2d(C, D, kernel_size=P, stride=P)
         self.embeddings.position_embedding = _Weight((c["image_size"] // P) ** 2, D)
         self.encoder = nn.Module()
-        self.encoder.layers = nn.ModuleList()
-        for _ in range(c["num_hidden_layers"]):
-            lay = nn.Module()
-            lay.self_attn = nn.Module()
-            for n in ("q_proj", "k_proj", "v_proj", "out_proj"):
-                setattr(lay.self_attn, n, _lin(D, D, True))
-            lay.layer_norm1, lay.layer_norm2 = nn.LayerNorm(D, eps=c["layer_norm_eps"]), nn.LayerNorm(D, eps=c["layer_norm_eps"])
-            lay.mlp = nn.Module()
-            lay.mlp.fc1, lay.mlp.fc2 = _lin(D, Fd, True), _lin(Fd, D, True)
-            self.encoder.layers.append(lay)
+        self.encoder.layers = clip_encoder_layers(c["num_hidden_layers"], D, Fd, c["layer_norm_eps"])
         self.post_layernorm = nn.LayerNorm(D, eps=c["layer_norm_eps"])
         self.requires_grad_(False)
 
@@ -180,36 +115,19 @@ class SiglipVisionNative(nn.Module):
 
     def padded_weights(self, i) -> dict:
         """bf16 weights of layer i (or i = "embed") as the kernels take them, built once (see the module docstring for the padding)"""
-        vm, ck = self.vision_model, self._cache
-        H, hd, hp = self.cfg["num_attention_heads"], self.head_dim, self.head_pad
+        vm, ck, c = self.vision_model, self._cache, self.cfg
         if i == "embed":
             pe = vm.embeddings.patch_embedding
             return dict(
                 w=ck.get("patch_w", [pe.weight], lambda: _pad_to(_bf(pe.weight).reshape(pe.weight.shape[0], -1), self.patch_k, 1).contiguous()),
                 b=ck.get("patch_b", [pe.bias], lambda: _bf(pe.bias)),
                 pos=ck.get("pos", [vm.embeddings.position_embedding.weight], lambda: _bf(vm.embeddings.position_embedding.weight)))
-        lay = vm.encoder.layers[i]
-        sa, mlp = lay.self_attn, lay.mlp
-        ph = lambda t, dim=0: pad_heads(_bf(t), H, hd, hp, dim).contiguous()  # noqa: E731
-        p = dict(
-            wqk=ck.get(("wqk", i), [sa.q_proj.weight, sa.k_proj.weight], lambda: torch.cat([ph(sa.q_proj.weight), ph(sa.k_proj.weight)], 0)),
-            bqk=ck.get(("bqk", i), [sa.q_proj.bias, sa.k_proj.bias], lambda: torch.cat([ph(sa.q_proj.bias), ph(sa.k_proj.bias)], 0)),
-            wv=ck.get(("wv", i), [sa.v_proj.weight], lambda: ph(sa.v_proj.weight)),
-            bv=ck.get(("bv", i), [sa.v_proj.bias], lambda: ph(sa.v_proj.bias)),
-            wo=ck.get(("wo", i), [sa.out_proj.weight], lambda: ph(sa.out_proj.weight, 1)),
-            bo=ck.get(("bo", i), [sa.out_proj.bias], lambda: _bf(sa.out_proj.bias)),
-            w1=ck.get(("w1", i), [mlp.fc1.weight], lambda: _pad_to(_bf(mlp.fc1.weight), self.mlp_pad, 0).contiguous()),
-            b1=ck.get(("b1", i), [mlp.fc1.bias], lambda: _pad_to(_bf(mlp.fc1.bias), self.mlp_pad, 0).contiguous()),
-            w2=ck.get(("w2", i), [mlp.fc2.weight], lambda: _pad_to(_bf(mlp.fc2.weight), self.mlp_pad, 1).contiguous()),
-            b2=ck.get(("b2", i), [mlp.fc2.bias], lambda: _bf(mlp.fc2.bias)))
-        for name, t in (("g1", lay.layer_norm1.weight), ("e1", lay.layer_norm1.bias), ("g2", lay.layer_norm2.weight), ("e2", lay.layer_norm2.bias)):
-            p[name] = ck.get((name, i), [t], lambda t=t: _bf(t))
-        return p
+        return layer_weights(ck, vm.encoder.layers[i], CLIP_LAYER, i, c["num_attention_heads"], self.head_dim, self.head_pad, self.mlp_pad)
 
     @torch.inference_mode()
     def forward(self, pixel_values: Tensor, **_) -> dict:
         """pixel_values [B, C, image_size, image_size] -> {"last_hidden_state": bf16 [B, grid^2, hidden]}"""
-        from fluxmi import _lib, ops
+        from fluxmi import ops
 
         dev = self.device
         if dev.type != "cuda":
@@ -223,24 +141,10 @@ class SiglipVisionNative(nn.Module):
         ones = ck.get("ones", [vm.post_layernorm.weight], lambda: torch.ones(D, dtype=torch.bfloat16, device=dev))
         # patch embedding + position embedding: bf16(pos + bf16(conv)), written into the first L rows of each image's Lp-row slab
         e = self.padded_weights("embed")
-        patches = ops.patchify(pix, P, self.grid, self.patch_k)
-        x = torch.zeros(B, Lp, D, dtype=torch.bfloat16, device=dev)
-        _linear_groups([patches[b * L:(b + 1) * L] for b in range(B)], e["w"], [x[b, :L] for b in range(B)], e["b"],
-                       resid_rows=[e["pos"]] * B, ones=ones)
-        x = x.view(B * Lp, D)
+        x = patch_embed(pix, P, self.grid, self.grid, self.patch_k, e["w"], e["b"], e["pos"], None, Lp, ones)
+        attend, gelu_tanh = vision_attend(B, L, Lp, H, self.head_dim, hp), lambda f: ops.act(f, 0)  # noqa: E731
         for i in range(len(vm.encoder.layers)):
-            p = self.padded_weights(i)
-            h = ops.row_norm(x, p["g1"], p["e1"], eps=eps, rms=False)
-            qk = ops.linear(h, p["wqk"], p["bqk"]).view(B, Lp, 2 * H * hp)
-            vt = torch.empty(B, H * hp, Lp, dtype=torch.bfloat16, device=dev)
-            # V^T = W_v . h_b^T per image: the weight is the "A" operand, the image's rows the "W" operand (one launch per image)
-            for b in range(B):
-                ops.linear(p["wv"], h[b * Lp:(b + 1) * Lp], out=vt[b])
-            o = ops.vision_attention(qk[:, :, : H * hp], qk[:, :, H * hp:], vt, L, H, hp, self.head_dim ** -0.5, v_bias=p["bv"])
-            x = ops.linear(o.view(B * Lp, H * hp), p["wo"], p["bo"], epilogue=_lib.EPI_GATE_RESID, gate=ones, resid=x, out=torch.empty_like(x))
-            h = ops.row_norm(x, p["g2"], p["e2"], eps=eps, rms=False)
-            f = ops.act(ops.linear(h, p["w1"], p["b1"]), 0)
-            x = ops.linear(f, p["w2"], p["b2"], epilogue=_lib.EPI_GATE_RESID, gate=ones, resid=x, out=torch.empty_like(x))
+            x = encoder_layer(x, self.padded_weights(i), attend, gelu_tanh, eps, ones, ones)
         g, e2 = (ck.get((n, "post"), [t], lambda t=t: _bf(t)) for n, t in (("g", vm.post_layernorm.weight), ("e", vm.post_layernorm.bias)))
         y = ops.row_norm(x, g, e2, eps=eps, rms=False).view(B, Lp, D)[:, :L]
         return {"last_hidden_state": y.contiguous()}
@@ -310,9 +214,7 @@ class ReduxImageEncoder(nn.Module):
         from PIL import Image
 
         pil = to_pil(image).convert("RGB").resize((self.image_size, self.image_size), resample=Image.BICUBIC)
-        a = (np.asarray(pil).astype(np.float64) * (1 / 255)).astype(np.float32)
-        a = (a - np.float32(0.5)) / np.float32(0.5)
-        return torch.from_numpy(np.ascontiguousarray(a.transpose(2, 0, 1)))[None]
+        return normalize_image(np.asarray(pil), np.float32(0.5), np.float32(0.5))
 
     @torch.inference_mode()
     def project(self, hidden: Tensor) -> Tensor:
@@ -335,25 +237,30 @@ class ReduxImageEncoder(nn.Module):
         return self.project(self.siglip(pix)["last_hidden_state"])
 
 
-def read_siglip(path: str) -> SiglipVisionNative:
-    """a local HF directory (config.json + *.safetensors of SiglipVisionModel or SiglipModel) or one .safetensors file (the
-    so400m-patch14-384 geometry) -> SiglipVisionNative with its weights (host memory)"""
+def _read_tower(path: str, cls, what: str):
+    """a local HF directory (config.json + *.safetensors) or one .safetensors file (cls's default geometry) -> cls with its weights (host memory)"""
     from safetensors.torch import load_file
 
+    cfg = None
     if os.path.isdir(path):
-        cfg = None
         cj = os.path.join(path, "config.json")
         if os.path.exists(cj):
             with open(cj) as f:
                 cfg = json.load(f)
         sd = _read_dir_weights(path)
     else:
-        cfg, sd = None, load_file(path, device="cpu")
-    m = SiglipVisionNative(cfg)
+        sd = load_file(path, device="cpu")
+    m = cls(cfg)
     missing, _ = m.load_state_dict(sd, strict=False)
     if missing:
-        raise RuntimeError(f"fluxmi: SigLIP checkpoint is missing weights: {missing[:4]} ...")
+        raise RuntimeError(f"fluxmi: {what} checkpoint is missing weights: {missing[:4]} ...")
     return m
+
+
+def read_siglip(path: str) -> SiglipVisionNative:
+    """a local HF directory (config.json + *.safetensors of SiglipVisionModel or SiglipModel) or one .safetensors file (the
+    so400m-patch14-384 geometry) -> SiglipVisionNative with its weights (host memory)"""
+    return _read_tower(path, SiglipVisionNative, "SigLIP")
 
 
 # ---- CLIP vision tower (the IP-Adapter's image encoder; modules/ip_adapter.py) -----------------------------------------------------------
@@ -374,23 +281,14 @@ class _ClipVisionTransformer(nn.Module):
         self.embeddings.position_embedding = _Weight((c["image_size"] // P) ** 2 + 1, D)
         self.pre_layrnorm = nn.LayerNorm(D, eps=c["layer_norm_eps"])  # (transformers' spelling: it is the state-dict key)
         self.encoder = nn.Module()
-        self.encoder.layers = nn.ModuleList()
-        for _ in range(c["num_hidden_layers"]):
-            lay = nn.Module()
-            lay.self_attn = nn.Module()
-            for n in ("q_proj", "k_proj", "v_proj", "out_proj"):
-                setattr(lay.self_attn, n, _lin(D, D, True))
-            lay.layer_norm1, lay.layer_norm2 = nn.LayerNorm(D, eps=c["layer_norm_eps"]), nn.LayerNorm(D, eps=c["layer_norm_eps"])
-            lay.mlp = nn.Module()
-            lay.mlp.fc1, lay.mlp.fc2 = _lin(D, Fd, True), _lin(Fd, D, True)
-            self.encoder.layers.append(lay)
+        self.encoder.layers = clip_encoder_layers(c["num_hidden_layers"], D, Fd, c["layer_norm_eps"])
         self.post_layernorm = nn.LayerNorm(D, eps=c["layer_norm_eps"])
         self.requires_grad_(False)
 
 
 class ClipVisionNative(nn.Module):
     """transformers' CLIPVisionModelWithProjection on libfluxmi, built from the kernels the SigLIP tower runs on (no kernel of its own):
-    class token + stride-P "valid" Conv2d without bias (fluxmi_patchify + GEMM) + position embedding; pre_layrnorm; pre-LN encoder layers
+    class token + stride-P "valid" Conv2d without bias (fluxmi_patchify_rect + GEMM) + position embedding; pre_layrnorm; pre-LN encoder layers
     (LayerNorm eps 1e-5 with bias; q / k / v / out projections with bias, heads of 64, non-causal, scale 64^-1/2 through
     fluxmi_vision_attention; fc1, quick_gelu = `ops.act_mul(x, gated=False)`, fc2; both residual adds in bf16); post_layernorm on the class
     token; visual_projection without bias -> image_embeds.  State-dict keys: vision_model.embeddings.{class_embedding, patch_embedding,
@@ -448,8 +346,7 @@ class ClipVisionNative(nn.Module):
 
     def padded_weights(self, i) -> dict:
         """bf16 weights of layer i (or i = "embed") as the kernels take them, built once"""
-        vm, ck = self.vision_model, self._cache
-        H, hd, hp = self.cfg["num_attention_heads"], self.head_dim, self.head_pad
+        vm, ck, c = self.vision_model, self._cache, self.cfg
         if i == "embed":
             em = vm.embeddings
             pe, pos = em.patch_embedding, em.position_embedding.weight
@@ -458,29 +355,13 @@ class ClipVisionNative(nn.Module):
                 pos=ck.get("pos", [pos], lambda: _bf(pos)),
                 # the class row: bf16(class_embedding + position_embedding[0]) on bf16 tensors, as transformers adds them
                 cls=ck.get("cls", [em.class_embedding, pos], lambda: (_bf(em.class_embedding) + _bf(pos)[0]).contiguous()))
-        lay = vm.encoder.layers[i]
-        sa, mlp = lay.self_attn, lay.mlp
-        ph = lambda t, dim=0: pad_heads(_bf(t), H, hd, hp, dim).contiguous()  # noqa: E731
-        p = dict(
-            wqk=ck.get(("wqk", i), [sa.q_proj.weight, sa.k_proj.weight], lambda: torch.cat([ph(sa.q_proj.weight), ph(sa.k_proj.weight)], 0)),
-            bqk=ck.get(("bqk", i), [sa.q_proj.bias, sa.k_proj.bias], lambda: torch.cat([ph(sa.q_proj.bias), ph(sa.k_proj.bias)], 0)),
-            wv=ck.get(("wv", i), [sa.v_proj.weight], lambda: ph(sa.v_proj.weight)),
-            bv=ck.get(("bv", i), [sa.v_proj.bias], lambda: ph(sa.v_proj.bias)),
-            wo=ck.get(("wo", i), [sa.out_proj.weight], lambda: ph(sa.out_proj.weight, 1)),
-            bo=ck.get(("bo", i), [sa.out_proj.bias], lambda: _bf(sa.out_proj.bias)),
-            w1=ck.get(("w1", i), [mlp.fc1.weight], lambda: _pad_to(_bf(mlp.fc1.weight), self.mlp_pad, 0).contiguous()),
-            b1=ck.get(("b1", i), [mlp.fc1.bias], lambda: _pad_to(_bf(mlp.fc1.bias), self.mlp_pad, 0).contiguous()),
-            w2=ck.get(("w2", i), [mlp.fc2.weight], lambda: _pad_to(_bf(mlp.fc2.weight), self.mlp_pad, 1).contiguous()),
-            b2=ck.get(("b2", i), [mlp.fc2.bias], lambda: _bf(mlp.fc2.bias)))
-        for name, t in (("g1", lay.layer_norm1.weight), ("e1", lay.layer_norm1.bias), ("g2", lay.layer_norm2.weight), ("e2", lay.layer_norm2.bias)):
-            p[name] = ck.get((name, i), [t], lambda t=t: _bf(t))
-        return p
+        return layer_weights(ck, vm.encoder.layers[i], CLIP_LAYER, i, c["num_attention_heads"], self.head_dim, self.head_pad, self.mlp_pad)
 
     @torch.inference_mode()
     def forward(self, pixel_values: Tensor, **_) -> dict:
         """pixel_values [B, C, image_size, image_size] -> {"image_embeds": bf16 [B, projection_dim], "last_hidden_state": bf16
         [B, grid^2 + 1, hidden] (before post_layernorm, as transformers returns it)}"""
-        from fluxmi import _lib, ops
+        from fluxmi import ops
 
         dev = self.device
         if dev.type != "cuda":
@@ -490,30 +371,16 @@ class ClipVisionNative(nn.Module):
         pix = pixel_values.to(device=dev, dtype=torch.bfloat16)
         if pix.dim() != 4 or pix.shape[1] != c["num_channels"] or tuple(pix.shape[-2:]) != (S, S):
             raise ValueError(f"fluxmi: CLIP takes pixel_values [B, {c['num_channels']}, {S}, {S}], got {tuple(pix.shape)}")
-        B, L, Lp, hp, G = pix.shape[0], self.num_tokens, self.seq_pad, self.head_pad, self.grid ** 2
+        B, L, Lp, hp = pix.shape[0], self.num_tokens, self.seq_pad, self.head_pad
         ones = ck.get("ones", [vm.post_layernorm.weight], lambda: torch.ones(D, dtype=torch.bfloat16, device=dev))
         ln = lambda x, mod, tag: ops.row_norm(x, ck.get((tag, "g"), [mod.weight], lambda: _bf(mod.weight)),  # noqa: E731
                                               ck.get((tag, "e"), [mod.bias], lambda: _bf(mod.bias)), eps=eps, rms=False)
         # row 0 of each image's Lp-row slab: the class row; rows 1 .. G: bf16(pos + bf16(conv)); the rest zero (finite through every layer)
         e = self.padded_weights("embed")
-        patches = ops.patchify(pix, P, self.grid, self.patch_k)
-        x = torch.zeros(B, Lp, D, dtype=torch.bfloat16, device=dev)
-        _linear_groups([patches[b * G:(b + 1) * G] for b in range(B)], e["w"], [x[b, 1:L] for b in range(B)], None,
-                       resid_rows=[e["pos"][1:]] * B, ones=ones)
-        x[:, 0] = e["cls"]
-        x = ln(x.view(B * Lp, D), vm.pre_layrnorm, "pre")
+        x = ln(patch_embed(pix, P, self.grid, self.grid, self.patch_k, e["w"], None, e["pos"][1:], e["cls"], Lp, ones), vm.pre_layrnorm, "pre")
+        attend, quick_gelu = vision_attend(B, L, Lp, H, self.head_dim, hp), lambda f: ops.act_mul(f, gated=False)  # noqa: E731
         for i in range(len(vm.encoder.layers)):
-            p = self.padded_weights(i)
-            h = ops.row_norm(x, p["g1"], p["e1"], eps=eps, rms=False)
-            qk = ops.linear(h, p["wqk"], p["bqk"]).view(B, Lp, 2 * H * hp)
-            vt = torch.empty(B, H * hp, Lp, dtype=torch.bfloat16, device=dev)
-            for b in range(B):  # V^T = W_v . h_b^T per image (the SigLIP tower's scheme)
-                ops.linear(p["wv"], h[b * Lp:(b + 1) * Lp], out=vt[b])
-            o = ops.vision_attention(qk[:, :, : H * hp], qk[:, :, H * hp:], vt, L, H, hp, self.head_dim ** -0.5, v_bias=p["bv"])
-            x = ops.linear(o.view(B * Lp, H * hp), p["wo"], p["bo"], epilogue=_lib.EPI_GATE_RESID, gate=ones, resid=x, out=torch.empty_like(x))
-            h = ops.row_norm(x, p["g2"], p["e2"], eps=eps, rms=False)
-            f = ops.act_mul(ops.linear(h, p["w1"], p["b1"]), gated=False)
-            x = ops.linear(f, p["w2"], p["b2"], epilogue=_lib.EPI_GATE_RESID, gate=ones, resid=x, out=torch.empty_like(x))
+            x = encoder_layer(x, self.padded_weights(i), attend, quick_gelu, eps, ones, ones)
         x = x.view(B, Lp, D)
         pooled = ln(x[:, 0].contiguous(), vm.post_layernorm, "post")
         wp = ck.get("proj", [self.visual_projection.weight], lambda: _bf(self.visual_projection.weight))
@@ -523,19 +390,4 @@ class ClipVisionNative(nn.Module):
 def read_clip_vision(path: str) -> ClipVisionNative:
     """a local HF directory (config.json + *.safetensors of CLIPVisionModelWithProjection or CLIPModel) or one .safetensors file (the
     ViT-L/14 geometry) -> ClipVisionNative with its weights (host memory)"""
-    from safetensors.torch import load_file
-
-    if os.path.isdir(path):
-        cfg = None
-        cj = os.path.join(path, "config.json")
-        if os.path.exists(cj):
-            with open(cj) as f:
-                cfg = json.load(f)
-        sd = _read_dir_weights(path)
-    else:
-        cfg, sd = None, load_file(path, device="cpu")
-    m = ClipVisionNative(cfg)
-    missing, _ = m.load_state_dict(sd, strict=False)
-    if missing:
-        raise RuntimeError(f"fluxmi: CLIP vision checkpoint is missing weights: {missing[:4]} ...")
-    return m
+    return _read_tower(path, ClipVisionNative, "CLIP vision")

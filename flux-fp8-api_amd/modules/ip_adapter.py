@@ -67,7 +67,7 @@ def clip_preprocess(image, size: int = 224) -> Tensor:
     to `size` (the long edge int(size * long / short)), centre crop, x * (1 / 255) in float64 then float32, (x - mean) / std in float32."""
     from PIL import Image
 
-    from modules.image_embedders import to_pil
+    from modules.image_embedders import normalize_image, to_pil
 
     pil = to_pil(image).convert("RGB")
     w, h = pil.size
@@ -77,10 +77,7 @@ def clip_preprocess(image, size: int = 224) -> Tensor:
     pil = pil.resize((nw, nh), resample=Image.BICUBIC)
     a = np.asarray(pil)
     top, left = (nh - size) // 2, (nw - size) // 2
-    a = a[top:top + size, left:left + size]
-    a = (a.astype(np.float64) * (1 / 255)).astype(np.float32)
-    a = (a - np.array(CLIP_MEAN, dtype=np.float32)) / np.array(CLIP_STD, dtype=np.float32)
-    return torch.from_numpy(np.ascontiguousarray(a.transpose(2, 0, 1)))[None]
+    return normalize_image(a[top:top + size, left:left + size], CLIP_MEAN, CLIP_STD)
 
 
 def check_state_dict(sd) -> tuple:

@@ -502,10 +502,12 @@ int fluxmi_gaussian_blur(const void* src, long long ld, long long bs, void* dst,
  *     top = hx * a + lx * b;   bot = hx * c + lx * d;   v = hy * top + ly * bot        each product and sum rounded to fp32 (no fma contraction
  *   is relied on: the gate of tests/test_depth_gpu.py covers either);  out = bf16(v).  Equal sizes give scale 1 and l = 0: out == x exactly.
  *   With `add` ([B][Ho][Wo] pixels, stride add_ld; NULL = none):  out = bf16(fp32(bf16(v)) + add)  -- torch's bf16 tensor sum.  out != x.
- * fluxmi_patchify_rect: fluxmi_patchify for a grid_h x grid_w grid: row (b, gy, gx), column c*patch*patch + ky*patch + kx, zero past C*patch*patch.
+ * fluxmi_patchify_rect: fluxmi_patchify for a grid_h x grid_w grid: row (b, gy, gx), column c*patch*patch + ky*patch + kx, zero past C*patch*patch
+ *   (one gather kernel serves both, csrc/text.hip: fluxmi_patchify is the grid_h = grid_w case).
  * fluxmi_im2col3x3_s2: x [B, Hi, Wi, C] dense -> col [B*Ho*Wo, 9*C], Ho = (Hi - 1) / 2 + 1, Wo likewise, column (dy*3+dx)*C + c = input pixel
  *   (2 yo + dy - 1, 2 xo + dx - 1), zero outside the image: the patch matrix of Conv2d(kernel 3, stride 2, padding 1) at odd and even sizes
- *   (fluxmi_im2col3x3's -2 mode pads right / bottom only and needs even sizes).  The convolution is then the bf16 GEMM.  C %% 8 == 0.
+ *   (fluxmi_im2col3x3's -2 mode pads right / bottom only and needs even sizes; the same kernel, csrc/vae.hip, at stride 2 and pad 1).  The
+ *   convolution is then the bf16 GEMM.  C %% 8 == 0.
  * fluxmi_depth_head: out[p] = max(0, sum_c x[p][c] * w[c] + bias[0]) for n pixels (stride ldx), fp32: acc = fma(x_c, w_c, acc) from 0 with c
  *   ascending, then + bias, then the ReLU; out fp32 [n], NOT rounded to bf16.  w bf16 [C], bias bf16 [1] or NULL, C %% 8 == 0 (the caller
  *   zero-pads).  This is the head's last 1x1 convolution + ReLU of a relative-depth model.

@@ -193,6 +193,35 @@ def test_patchify_rect_equals_the_definition(ops, dev):
             assert torch.equal(bits(got), bits(ops.patchify(pix.to(dev), 14, gh, 640).cpu()))
 
 
+# an unread border and a padded K;  K exactly C P P;  one patch per image and a pad of a single 8-vector
+SQUARE_PATCH_CASES = [(2, 3, 31, 30, 14, 2, 640), (1, 2, 4, 4, 2, 2, 8), (3, 3, 14, 14, 14, 1, 592)]
+
+
+@pytest.mark.parametrize("case", SQUARE_PATCH_CASES, ids=vr.case_id)
+def test_patchify_square_equals_rect_and_the_definition(ops, dev, case):
+    """fluxmi_patchify is fluxmi_patchify_rect's gather at grid_h = grid_w"""
+    B, C, H, W, P, G, Kp = case
+    pix = torch.randn(B, C, H, W, generator=torch.Generator().manual_seed(hr.seed_of("patchify", case))).bfloat16()
+    kc = C * P * P
+    want = F.unfold(pix[:, :, :G * P, :G * P].float(), kernel_size=P, stride=P).transpose(1, 2).reshape(B * G * G, kc).bfloat16()
+    sq, rect = ops.patchify(pix.to(dev), P, G, Kp).cpu(), ops.patchify_rect(pix.to(dev), P, G, G, Kp).cpu()
+    assert tuple(sq.shape) == tuple(rect.shape) == (B * G * G, Kp)
+    assert torch.equal(bits(sq), bits(rect))
+    assert torch.equal(bits(sq[:, :kc]), bits(want)) and not bits(sq[:, kc:]).any()
+
+
+@pytest.mark.parametrize("B", [1, 3])
+@pytest.mark.parametrize("hw", [(1, 1), (2, 3), (5, 7)], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_stride2_gather_equals_the_definition(ops, dev, hw, B):
+    """conv3x3_s2's patch matrix at the narrowest channel count (one 8-vector per tap), odd and even sizes"""
+    Hi, Wi = hw
+    x = torch.randn(B, Hi, Wi, 8, generator=torch.Generator().manual_seed(hr.seed_of("s2 gather", hw, B))).bfloat16()
+    Ho, Wo = ops.conv3x3_s2_hw(Hi, Wi)
+    col = ops.im2col3x3_s2(x.to(dev)).cpu()
+    assert tuple(col.shape) == (B * Ho * Wo, 72)
+    assert torch.equal(bits(col), bits(s2_patch64(x).bfloat16()))
+
+
 S2_CASES = [(2, 1, 1, 64, 128), (2, 3, 5, 64, 128), (1, 4, 4, 128, 256), (1, 37, 37, 128, 128)]
 
 

@@ -99,7 +99,7 @@ int fluxmi_lora_fuse_f8(void* w_fp8, float* w_scale, float* w_scale_recip, const
   float* delta = work_f32 + n;
   FLUXMI_TRY(fluxmi_k_dequant(w_fp8, w32, w_scale_recip, n, FLUXMI_E4M3, s));
   for (int c = 0; c < n_chunks; ++c)
-    FLUXMI_TRY(fluxmi_k_lora_delta(lora_B, lora_A + (long long)c * R * K, delta, N, K, R, lora_scale, c > 0, s));
+    FLUXMI_TRY(fluxmi_k_lora_delta(lora_B, lora_A + (long long)c * R * K, delta, N, K, R, lora_scale, c > 0 ? 1 : (n_chunks > 1 ? 2 : 0), s));
   FLUXMI_TRY(fluxmi_k_axpy_f32(w32, delta, 1.0f, n, s));
   return fluxmi_k_requantize_f32(w32, w_fp8, amax_tmp, w_scale, w_scale_recip, n, FLUXMI_E4M3, s);
 }

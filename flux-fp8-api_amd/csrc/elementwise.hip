@@ -546,7 +546,10 @@ __global__ void __launch_bounds__(256) lora_delta_kernel(const float* __restrict
   for (int r = 0; r < R; ++r) acc = fmaf(Bm[(long long)n * R + r], A[(long long)r * K + k], acc);
   acc *= scale;
   float* d = delta + (long long)n * K + k;
-  *d = accumulate ? (*d + acc) : acc;
+  // accumulate: 0 store, 1 add to *d, 2 the first term of a chunk sum, which the reference starts from zeros (lora_loading.py:509-544):
+  // +0 + acc turns a -0 product (lora_scale = 0) into +0, and a -0 weight then re-quantises to +0 as it does there
+  const float base = accumulate == 1 ? *d : 0.f;
+  *d = accumulate ? base + acc : acc;
 }
 
 }  // namespace

@@ -224,7 +224,9 @@ int fluxmi_gemv(const void* x, long long ldx, const void* W, const void* bias, c
 /* q = fp8(clamp(bf16(x*scale)))                                                float8_quantize.py:217-218,274-276 */
 int fluxmi_quantize_act(const void* x, void* q, const float* scale, int rows, int cols, long long ld_in, long long ld_out,
                         int fmt, void* stream);
-/* *amax = max(*amax, max|x|)  (caller zeroes *amax first)                      float8_quantize.py:227 */
+/* *amax = max(*amax, max|x|)  (caller zeroes *amax first)                      float8_quantize.py:227
+ * An inf element gives inf; a NaN element is SKIPPED (fmaxf drops it), where torch.max would return NaN: the maximum is taken over the
+ * other elements, and a tensor of NaNs alone leaves *amax as it was (tests/test_quant_kernels_gpu.py pins this). */
 int fluxmi_amax(const void* x, float* amax, int rows, int cols, long long ld, void* stream);
 /* one call of F8Linear.quantize_input's scale logic for trial `trial_index`     float8_quantize.py:220-246 */
 int fluxmi_calib_update(const float* amax, float* trials, float* scale, float* scale_recip, int trial_index, int num_trials,

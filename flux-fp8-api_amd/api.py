@@ -34,6 +34,8 @@ Same two POST endpoints, request fields, defaults and status codes:
              control_image / controlnet_image is a PHOTO and the control map is made from it on the device
              (FluxPipeline.preprocess_control: a native Canny whose parity with OpenCV's is unpinned, PIL's luma, a Gaussian blur, the
              depth map of the Depth Anything estimator of config.depth_path), each passed on only when set;
+             jpeg_encoder=None ("pil" | "native") -- who writes the response's JPEG: Pillow on the host, or the native encoder on the device
+             (FluxPipeline.generate); passed on only when set, and unset means the config JSON's "jpeg_encoder" ("pil" unless given there);
              stream=None, preview_every=None (>= 0) -- progress, live previews and cancellation, see below;
              a region with both or neither of box / mask, or a box outside 0 <= x0 < x1 <= 1, is a 422}
              ->  image/jpeg stream of FluxPipeline.generate(**args)                                               (reference api.py:54-86)
@@ -146,6 +148,9 @@ class GenerateArgs(BaseModel):
     blur_sigma: Optional[float] = Field(default=None, gt=0.0)  # ... the Gaussian's standard deviation in pixels (default 8; radius ceil(3 sigma) <= 64)
     depth_resolution: Optional[int] = Field(default=None, ge=14, le=1036)  # ... "depth_anything": the side the estimator sees (default 518)
     depth_normalize: Optional[Literal["minmax", "raw"]] = None  # ... its depth -> 0..255: each image's min..max (default) or clamp(depth, 0, 255)
+    # who writes the response's JPEG: "pil" (Pillow on the host) or "native" (the device encoder, fluxmi.ops.jpeg_encode: the pixels never
+    # leave the device uncompressed); unset = the configuration's jpeg_encoder ("pil" unless set there).  Previews stay on Pillow
+    jpeg_encoder: Optional[Literal["pil", "native"]] = None
     stream: Optional[bool] = None  # answer with application/x-ndjson progress lines and a final result line instead of the JPEG
     preview_every: Optional[int] = Field(default=None, ge=0)  # ... with a latent-resolution preview at every k-th model evaluation (0 = none)
 
@@ -229,7 +234,7 @@ def generate(args: GenerateArgs):
               "negative_ip_adapter_image", "negative_ip_adapter_scale", "guidance_mode", "guidance_rescale", "apg_eta", "apg_norm_threshold",
               "apg_momentum", "zero_init_steps", "source_prompt", "source_guidance", "edit_n_max", "edit_n_min", "edit_n_avg", "tile_size",
               "tile_overlap", "tile_weight", "control_preprocess", "canny_low", "canny_high", "canny_l2", "blur_sigma", "depth_resolution",
-              "depth_normalize"):
+              "depth_normalize", "jpeg_encoder"):
         if kwargs.get(k) is None:
             kwargs.pop(k, None)
     for k in ("upscale", "init_upscale"):  # passed on only when asked for

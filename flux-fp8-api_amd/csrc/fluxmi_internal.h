@@ -255,6 +255,22 @@ int fluxmi_k_rgb_to_gray(const void* rgb, long long ld, long long bs, void* gray
                          hipStream_t s);
 int fluxmi_k_gaussian_blur(const void* src, long long ld, long long bs, void* dst, long long dld, long long dbs, void* work, long long work_bytes,
                            int B, int H, int W, int C, float sigma, hipStream_t s);
+// the baseline JPEG encoder (include/fluxmi.h, fluxmi_jpeg_*): the host's plan of one encode (jpeg_host.cpp: geometry, the layout of `work`,
+// the scaled quantisation tables, the header bytes) and the launches that run it (jpeg.hip)
+struct FluxmiJpegPlan {
+  int H, Hs, W, ss, bpm;       // image rows, stacked rows B * H, columns, FLUXMI_JPEG_420 / _444, blocks per MCU (6 / 3)
+  int mw, mh, nbw, nbh;        // MCUs across / down, 8 x 8 blocks that hold image pixels across / down
+  int R;                       // MCUs per interval as run: `restart`, or every MCU when restart = 0
+  long long n_mcu, n_int;      // MCUs, intervals = ceil(n_mcu / R)
+  long long stride;            // bytes of one interval's slot
+  long long off_sizes, off_offs, off_slots, work_bytes, out_cap;
+  int hdr_bytes;
+  unsigned char hdr[640];      // SOI .. SOS
+  unsigned char q[2][64];      // the scaled tables, ZIGZAG order: [0] luminance, [1] chrominance
+};
+int fluxmi_jpeg_plan(const char* who, int B, int H, int W, int quality, int subsampling, int restart, FluxmiJpegPlan* p);
+int fluxmi_k_jpeg_encode(const FluxmiJpegPlan& p, const void* rgb, long long ld, long long bs, void* work, void* out, long long out_cap,
+                         void* n_bytes_dev, hipStream_t s);
 int fluxmi_k_vision_attention(const void* q, const void* k, long long ld_qk, long long bs_qk, const void* vt, long long ld_vt, long long bs_vt,
                               void* out, long long ld_out, long long bs_out, const void* v_bias, float scale, int head_dim, int L, int Lp, int H,
                               int B, hipStream_t s);

@@ -35,6 +35,7 @@ from util import (ModelSpec, ModelVersion, engine_flow_dtype, into_device, into_
 
 MAX_RAND = 2**32 - 1
 CONTROL_PREPROCESSORS = ("canny", "gray", "blur", "depth_anything")  # generate(control_preprocess=...) / preprocess_control: the maps made from a photo
+JPEG_ENCODERS = ("pil", "native")  # generate(jpeg_encoder=...) / ModelSpec.jpeg_encoder: Pillow on the host, or fluxmi.ops.jpeg_encode on the device
 GUIDANCE_MODES = ("cfg", "apg", "cfg_zero_star")  # generate(guidance_mode=...): the rule that combines the two branches of true CFG
 
 # FLUX.1 Kontext's preferred reference resolutions, (width, height) (BFL flux, src/flux/sampling.py)
@@ -793,7 +794,7 @@ class FluxPipeline:
                  edit_n_max: Optional[int] = None, edit_n_min: int = 0, edit_n_avg: int = 1, tile_size=None, tile_overlap: Optional[int] = None,
                  tile_weight: str = "cosine", upscale: bool = False, init_upscale: bool = False, control_preprocess: Optional[str] = None,
                  canny_low: int = 100, canny_high: int = 200, canny_l2: bool = False, blur_sigma: float = 8.0, depth_resolution: int = 518,
-                 depth_normalize: str = "minmax"):
+                 depth_normalize: str = "minmax", jpeg_encoder: Optional[str] = None):
         """`reference_image` (FLUX.1 Kontext [dev] instruction editing): an image the prompt describes an edit of, in any form `init_image`
         takes; see prepare_kontext_reference.  Composes with `init_image` / `strength` unchanged.
         FLUX.1 Fill [dev] (a model with 320 conditioning channels): `init_image` is the image to inpaint and `mask_image` (white =
@@ -951,7 +952,14 @@ class FluxPipeline:
         mode.  `depth_resolution` (default 518, DPTImageProcessor's) is the side the estimator sees, `depth_normalize` "minmax" (default) or
         "raw".  Refused up front: the kind without a depth model (naming `depth_path`), a `depth_resolution` outside 14..1036, a patch grid
         above 74 x 74 + 1 tokens (the longest sequence the estimator's attention is checked at), an unknown `depth_normalize`, and either
-        argument without the kind.  `control_preprocess="depth"` stays refused: the kind is named after its model."""
+        argument without the kind.  `control_preprocess="depth"` stays refused: the kind is named after its model.
+        `jpeg_encoder` ("pil" | "native"; None = config.jpeg_encoder, "pil" unless configured): who writes the JPEG of output_type="jpeg".
+        "pil" is today's path, byte for byte: pixels to the host, Pillow at `jpeg_quality`.  "native" keeps the pixels on the device from the
+        VAE (and the upscaler) to fluxmi.ops.jpeg_encode -- a baseline JFIF file, 4:2:0, the Annex K tables at `jpeg_quality`, restart markers
+        every 4 MCUs: libjpeg's integer pipeline (include/fluxmi.h), so it decodes to the pixels Pillow's file decodes to; the bytes differ
+        only by the restart markers -- and two copies come back, the length and that many bytes.  It serves the plain, the tiled and the
+        FlowEdit request and into_bytes; with another output_type it is ignored.  Refused by name: an unknown encoder, and with "native" a
+        `jpeg_quality` outside 1..100 or an image beyond 65535 x 65535 (num_images stack vertically)."""
         if control_preprocess is not None:
             if img_cond is not None or controlnet_cond is not None:
                 raise ValueError("fluxmi: control_preprocess works on an image: it does not combine with img_cond / controlnet_cond (maps that "
@@ -970,16 +978,20 @@ class FluxPipeline:
             prep_kw.update(depth_resolution=depth_resolution, depth_normalize=depth_normalize)
         if upscale or init_upscale:
             init_image = self._check_upscale(upscale, init_upscale, output_type, init_image, width, height, num_images)
+        jpeg_encoder = self._jpeg_encoder(jpeg_encoder)
+        if jpeg_encoder == "native" and output_type == "jpeg" and self.ae is not None:
+            up = self.upscaler.scale if upscale else 1
+            self._check_jpeg_native(num_images, up * 16 * (height // 16), up * 16 * (width // 16), jpeg_quality)
         tiles = self._check_tiles(locals())
         if tiles is not None:
             return self._generate_tiled(tiles, prompt, width, height, num_steps, guidance, seed, init_image, strength, num_images, return_seed,
                                         jpeg_quality, output_type, noise, use_graph, negative_prompt, true_cfg_scale, true_cfg_interval,
-                                        sigma_schedule, sigmas, on_step, upscale=upscale)
+                                        sigma_schedule, sigmas, on_step, upscale=upscale, jpeg_encoder=jpeg_encoder)
         edit = self._check_edit(locals())
         if edit is not None:
             return self._generate_edit(edit, prompt, source_prompt, width, height, num_steps, guidance, seed, init_image, silent, num_images,
                                        return_seed, jpeg_quality, output_type, use_graph, sigma_schedule, sigmas, noise_seed, on_step,
-                                       upscale=upscale)
+                                       upscale=upscale, jpeg_encoder=jpeg_encoder)
         if isinstance(preview_every, bool) or not isinstance(preview_every, int) or preview_every < 0:
             raise ValueError(f"fluxmi: preview_every={preview_every!r}: expected an integer >= 0 (0 = no previews)")
         if on_step is not None and not callable(on_step):
@@ -1347,7 +1359,7 @@ class FluxPipeline:
             return (out, seed) if return_seed else out
         img_px = self.vae_decode(latents, height, width)
         # output_type "uint8": the [B, H, W, 3] array into_bytes hands to the JPEG encoder (the pixel-parity tests compare it)
-        out = self._pixels_out(img_px, output_type, jpeg_quality, upscale)
+        out = self._pixels_out(img_px, output_type, jpeg_quality, upscale, jpeg_encoder)
         return (out, seed) if return_seed else out
 
     # ---- tiled generation (fluxmi.windows; Flux.denoise_windows) -------------------------------------------------------------------------------
@@ -1455,7 +1467,7 @@ class FluxPipeline:
 
     def _generate_tiled(self, plan, prompt, width, height, num_steps, guidance, seed, init_image, strength, num_images, return_seed, jpeg_quality,
                         output_type, noise, use_graph, negative_prompt, true_cfg_scale, true_cfg_interval, sigma_schedule, sigmas, on_step,
-                        upscale=False):
+                        upscale=False, jpeg_encoder="pil"):
         """the tiled request of generate (its docstring): today's noise / img2img / text at canvas size, then Flux.denoise_windows on the
         canvas -- one call, or up to three where true_cfg_interval cuts the request"""
         from modules.flux_model import Flux, PreviewCall
@@ -1500,7 +1512,7 @@ class FluxPipeline:
             out = self.unpack(latents.float(), height, width)
             return (out, seed) if return_seed else out
         img_px = self.vae_decode(latents, height, width)
-        out = self._pixels_out(img_px, output_type, jpeg_quality, upscale)
+        out = self._pixels_out(img_px, output_type, jpeg_quality, upscale, jpeg_encoder)
         return (out, seed) if return_seed else out
 
     # ---- FlowEdit (fluxmi.flowedit; Flux.denoise_edit) ---------------------------------------------------------------------------------------
@@ -1588,7 +1600,8 @@ class FluxPipeline:
         return latent, timesteps
 
     def _generate_edit(self, edit, prompt, source_prompt, width, height, num_steps, guidance, seed, init_image, silent, num_images, return_seed,
-                       jpeg_quality, output_type, use_graph, sigma_schedule, sigmas, noise_seed, on_step, upscale=False):
+                       jpeg_quality, output_type, use_graph, sigma_schedule, sigmas, noise_seed, on_step, upscale=False,
+                       jpeg_encoder="pil"):
         """the FlowEdit request of generate (its docstring): skipped steps | coupled steps (Flux.denoise_edit) | Euler tail (Flux.denoise)"""
         from fluxmi import flowedit, ops
         from modules.flux_model import PreviewCall
@@ -1637,7 +1650,7 @@ class FluxPipeline:
             out = self.unpack(latents.float(), height, width)
             return (out, seed) if return_seed else out
         img_px = self.vae_decode(latents, height, width)
-        out = self._pixels_out(img_px, output_type, jpeg_quality, upscale)
+        out = self._pixels_out(img_px, output_type, jpeg_quality, upscale, jpeg_encoder)
         return (out, seed) if return_seed else out
 
     def _preview_call(self, on_step, proj, every: int, height: int, width: int, step0: int, eval_offset: int, n_evaluations: int, solver):
@@ -1688,8 +1701,41 @@ class FluxPipeline:
         """[B, 3, H, W] in [-1, 1] -> [B, H, W, 3] uint8 on the host (reference flux_pipeline.py:385-393)"""
         return x.clamp(-1, 1).add(1.0).mul(127.5).clamp(0, 255).permute(0, 2, 3, 1).contiguous().to(torch.uint8).cpu()
 
-    def into_bytes(self, x: torch.Tensor, jpeg_quality: int = 99) -> io.BytesIO:
+    @staticmethod
+    def to_uint8_device(x: torch.Tensor) -> torch.Tensor:
+        """to_uint8's arithmetic without the copy to the host: [B, 3, H, W] in [-1, 1] -> [B, H, W, 3] uint8 where x lives"""
+        return x.clamp(-1, 1).add(1.0).mul(127.5).clamp(0, 255).permute(0, 2, 3, 1).contiguous().to(torch.uint8)
+
+    def into_bytes(self, x: torch.Tensor, jpeg_quality: int = 99, jpeg_encoder: Optional[str] = None) -> io.BytesIO:
+        if self._jpeg_encoder(jpeg_encoder) == "native":
+            return self._jpeg_native(self.to_uint8_device(x), jpeg_quality)
         return self._jpeg(self.to_uint8(x), jpeg_quality)
+
+    def _jpeg_encoder(self, jpeg_encoder: Optional[str]) -> str:
+        """the request's encoder: its own `jpeg_encoder`, else the configuration's (ModelSpec.jpeg_encoder, "pil" when absent); an unknown
+        value is refused by name"""
+        enc = jpeg_encoder if jpeg_encoder is not None else getattr(getattr(self, "config", None), "jpeg_encoder", "pil")
+        if enc not in JPEG_ENCODERS:
+            raise ValueError(f"fluxmi: jpeg_encoder={enc!r}: expected one of {JPEG_ENCODERS}")
+        return enc
+
+    @staticmethod
+    def _check_jpeg_native(num_images: int, height: int, width: int, jpeg_quality):
+        """the native encoder's refusals, by name, before any other work of the request (fluxmi.ops.jpeg_params)"""
+        from fluxmi import ops
+
+        ops.jpeg_params(max(1, int(num_images)), height, width, jpeg_quality)
+
+    @staticmethod
+    def _jpeg_native(px: torch.Tensor, jpeg_quality: int = 99) -> io.BytesIO:
+        """_jpeg on the device (fluxmi.ops.jpeg_encode): uint8 [B, H, W, 3] where the VAE left it -> the file, the batch stacked vertically;
+        4:2:0 and the Annex K tables at `jpeg_quality`, which is what _jpeg's Pillow call picks, so both decode to the same pixels"""
+        from fluxmi import ops
+
+        with torch.cuda.device(px.device):  # the encoder launches on the current stream: make it the pixels' device's
+            buf = io.BytesIO(ops.jpeg_encode(px, quality=jpeg_quality))
+        buf.seek(0)
+        return buf
 
     # ---- super-resolution (modules/upscaler.RRDBNet on fluxmi_conv3x3_dense) ---------------------------------------------------------------
     def _require_upscaler(self):
@@ -1728,8 +1774,14 @@ class FluxPipeline:
             init_image = self.upscale(init_image)[0]
         return init_image
 
-    def _pixels_out(self, img_px: torch.Tensor, output_type: str, jpeg_quality: int, upscale: bool = False):
-        """decoded pixels -> what the request returns: the uint8 array or its JPEG, through the upscaler first when asked"""
+    def _pixels_out(self, img_px: torch.Tensor, output_type: str, jpeg_quality: int, upscale: bool = False, jpeg_encoder: str = "pil"):
+        """decoded pixels -> what the request returns: the uint8 array or its JPEG, through the upscaler first when asked.  jpeg_encoder
+        "native" (an encoder name already checked; ignored unless a JPEG is returned): the pixels stay on the device up to the encoder."""
+        if jpeg_encoder == "native" and output_type == "jpeg":
+            px = self.to_uint8_device(img_px)
+            if upscale:
+                px = self._require_upscaler().upscale_uint8_device(px)
+            return self._jpeg_native(px, jpeg_quality)
         px = self.to_uint8(img_px)
         if upscale:
             px = self.upscale(px)

@@ -173,6 +173,10 @@ _SIGS = {
     "fluxmi_controlnet_trial": ([vp, C.POINTER(i32)], i32),
     "fluxmi_ip_attention": ([vp, i64, i64, vp, vp, vp, i64, vp, i64, i64, vp, i64, i32, i32, i32, i32, vp], i32),
     "fluxmi_engine_set_ip_adapter": ([vp, vp, vp, i32, i32, C.POINTER(f32), vp], i32),
+    "fluxmi_jpeg_workspace_bytes": ([i32, i32, i32, i32, i32, C.POINTER(i64), C.POINTER(i64)], i32),
+    "fluxmi_jpeg_encode": ([vp, i64, i64, i32, i32, i32, i32, i32, i32, vp, vp, i64, vp, vp], i32),
+    "fluxmi_jpeg_finish": ([vp, i64, C.POINTER(i64), vp], i32),
+    "fluxmi_jpeg_header": ([i32, i32, i32, i32, i32, i32, vp, i64, C.POINTER(i64)], i32),
 }
 AMAX_HOOK = C.CFUNCTYPE(i32, vp, i32, i32, vp)
 STEP_HOOK = C.CFUNCTYPE(i32, vp, i32, i32, vp, i32, i32, i32)  # fluxmi_step_hook_t: user, evaluation, n_evaluations, rgb, images, height, width

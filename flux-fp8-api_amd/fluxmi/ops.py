@@ -1061,6 +1061,98 @@ def gaussian_blur(img: torch.Tensor, sigma: float, out: Optional[torch.Tensor] =
     return out
 
 
+# ---- baseline JPEG encoder (csrc/jpeg.hip, csrc/jpeg_host.cpp; include/fluxmi.h has the definition) -----------------------------------------
+JPEG_SUBSAMPLING = {"4:2:0": 0, "4:4:4": 1}             # FLUXMI_JPEG_420 / FLUXMI_JPEG_444
+JPEG_DEFAULT_RESTART = {"4:2:0": 4, "4:4:4": 8}         # FLUXMI_JPEG_RESTART_420 / _444: MCUs per interval, 24 blocks either way
+JPEG_MAX_DIM = 65535
+
+
+def jpeg_params(B: int, H: int, W: int, quality=99, subsampling="4:2:0", restart_interval=None):
+    """every refusal of a JPEG request that needs no device, by name -> (quality, FLUXMI_JPEG_* code, MCUs per interval); restart_interval
+    None = JPEG_DEFAULT_RESTART[subsampling], 0 = no restart markers (one workgroup codes the whole image: slow)"""
+    if subsampling not in JPEG_SUBSAMPLING:
+        raise ValueError(f"jpeg_encode: subsampling={subsampling!r}: expected one of {tuple(JPEG_SUBSAMPLING)}")
+    if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
+        raise ValueError(f"jpeg_encode: quality={quality!r}: expected an integer in 1..100")
+    if restart_interval is None:
+        restart_interval = JPEG_DEFAULT_RESTART[subsampling]
+    if isinstance(restart_interval, bool) or not isinstance(restart_interval, int) or not 0 <= restart_interval <= 65535:
+        raise ValueError(f"jpeg_encode: restart_interval={restart_interval!r}: expected an integer in 0..65535 (MCUs per interval; 0 = no "
+                         f"restart markers, None = {JPEG_DEFAULT_RESTART[subsampling]})")
+    if W > JPEG_MAX_DIM or B * H > JPEG_MAX_DIM:
+        raise ValueError(f"jpeg_encode: a JPEG holds at most {JPEG_MAX_DIM} x {JPEG_MAX_DIM} pixels: width {W}, height {B} x {H} = {B * H} "
+                         f"(a batch is one image, stacked vertically)")
+    return quality, JPEG_SUBSAMPLING[subsampling], restart_interval
+
+
+def jpeg_workspace_bytes(B: int, H: int, W: int, subsampling="4:2:0", restart_interval=None):
+    """(bytes of `work`, bytes of an `out` no stream can exceed) for jpeg_encode_into (fluxmi_jpeg_workspace_bytes)"""
+    _, ss, R = jpeg_params(B, H, W, 99, subsampling, restart_interval)
+    work, cap = C.c_longlong(0), C.c_longlong(0)
+    call("fluxmi_jpeg_workspace_bytes", B, H, W, ss, R, C.byref(work), C.byref(cap))
+    return work.value, cap.value
+
+
+def jpeg_header(B: int, H: int, W: int, quality=99, subsampling="4:2:0", restart_interval=None) -> bytes:
+    """the header (SOI .. SOS) of the file jpeg_encode writes for such an input, from the host (fluxmi_jpeg_header)"""
+    q, ss, R = jpeg_params(B, H, W, quality, subsampling, restart_interval)
+    buf, n = C.create_string_buffer(1024), C.c_longlong(0)
+    call("fluxmi_jpeg_header", B, H, W, q, ss, R, buf, 1024, C.byref(n))
+    return buf.raw[:n.value]
+
+
+def _jpeg_run(px: torch.Tensor, work: torch.Tensor, out: torch.Tensor, quality, subsampling, restart_interval) -> int:
+    """the launches and the 8-byte read-back -> the stream's length, which exceeds out.numel() when the stream did not fit (`out` then holds
+    its first bytes and nothing beyond `out` was written)"""
+    B, H, W, ld, bs = _u8_image(px, "jpeg_encode", "px", 3)
+    q, ss, R = jpeg_params(B, H, W, quality, subsampling, restart_interval)
+    for name, t in (("work", work), ("out", out)):
+        _req(t, torch.uint8, f"jpeg_encode: {name}")
+        if t.ndim != 1 or not t.is_contiguous() or t.device != px.device:
+            raise ValueError(f"jpeg_encode: {name} must be a flat contiguous uint8 buffer on {px.device}")
+    need, _ = jpeg_workspace_bytes(B, H, W, subsampling, R)
+    if work.numel() < need:
+        raise ValueError(f"jpeg_encode: work holds {work.numel()} bytes, jpeg_workspace_bytes gives {need}")
+    n_dev = torch.zeros(1, dtype=torch.int64, device=px.device)
+    call("fluxmi_jpeg_encode", _p(px), ld, bs, B, H, W, q, ss, R, _p(work), _p(out), out.numel(), _p(n_dev), _stream())
+    n = C.c_longlong(0)
+    rc = _lib.lib.fluxmi_jpeg_finish(_p(n_dev), out.numel(), C.byref(n), _stream())
+    if rc != 0 and n.value <= out.numel():  # anything but "did not fit"
+        _lib.check(rc)
+    return n.value
+
+
+def jpeg_encode_into(px: torch.Tensor, work: torch.Tensor, out: torch.Tensor, quality=99, subsampling="4:2:0", restart_interval=None) -> int:
+    """px uint8 [B, H, W, 3] on the device (any row / image stride, as _u8_image takes them) -> the JPEG file in out[:n], n returned.  work
+    (256-byte aligned) and out are flat uint8 device buffers; work holds jpeg_workspace_bytes(...)[0] bytes, out any number: a stream that
+    does not fit is refused by name (RuntimeError) and nothing beyond out is written.  One small device-to-host copy (the length)."""
+    n = _jpeg_run(px, work, out, quality, subsampling, restart_interval)
+    if n > out.numel():
+        raise RuntimeError("fluxmi: " + _lib.lib.fluxmi_last_error().decode("utf-8", "replace"))
+    return n
+
+
+def jpeg_encode(px: torch.Tensor, quality: int = 99, subsampling: str = "4:2:0", restart_interval: Optional[int] = None) -> bytes:
+    """px uint8 [B, H, W, 3] on the device -> the bytes of a baseline JFIF file (fluxmi_jpeg_encode; include/fluxmi.h is the definition,
+    libjpeg's integer pipeline at its defaults).  A batch is ONE image of height B * H.  Two device-to-host copies: the length, then exactly
+    that many bytes.  Synchronises the current stream."""
+    B, H, W, _, _ = _u8_image(px, "jpeg_encode", "px", 3)
+    nwork, cap = jpeg_workspace_bytes(B, H, W, subsampling, restart_interval)
+    work = torch.empty(nwork, dtype=torch.uint8, device=px.device)
+    # `cap` is the worst case (every coefficient at its longest code, every byte stuffed): 9.75 or 19.5 bytes per pixel.  The raw size is tried
+    # first -- only noise at the highest qualities exceeds it -- and a stream that did not fit is coded again into the worst case
+    first = min(cap, 1024 + 3 * B * H * W)
+    out = torch.empty(first, dtype=torch.uint8, device=px.device)
+    n = _jpeg_run(px, work, out, quality, subsampling, restart_interval)
+    if n > first:
+        out = torch.empty(cap, dtype=torch.uint8, device=px.device)
+        n = jpeg_encode_into(px, work, out, quality, subsampling, restart_interval)
+    host = torch.empty(n, dtype=torch.uint8, pin_memory=True)  # torch caches pinned blocks: no allocation once warm
+    host.copy_(out[:n], non_blocking=True)
+    torch.cuda.current_stream().synchronize()
+    return host.numpy().tobytes()
+
+
 # ---- depth estimator pieces (csrc/depth.hip; NHWC bf16 maps behind one pixel stride) ------------------------------------------------------
 UNARY_KINDS = {"gelu": 0, "relu": 1}            # FLUXMI_UNARY_GELU_ERF / FLUXMI_UNARY_RELU
 DEPTH_NORMALIZE = {"minmax": 0, "raw": 1}       # FLUXMI_DEPTH_MINMAX / FLUXMI_DEPTH_RAW

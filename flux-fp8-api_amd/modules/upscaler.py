@@ -216,6 +216,13 @@ class RRDBNet:
         y = self(px.to(self.device).float().div(255.0).to(torch.bfloat16))
         return y.float().clamp(0.0, 1.0).mul(255.0).round().to(torch.uint8).cpu().contiguous()
 
+    def upscale_uint8_device(self, px: torch.Tensor) -> torch.Tensor:
+        """upscale_uint8's arithmetic with the result left on the network's device (contiguous): what the native JPEG encoder reads"""
+        if px.dtype != torch.uint8 or px.ndim != 4 or px.shape[-1] != 3:
+            raise ValueError(f"upscaler: expected uint8 [B, H, W, 3], got {tuple(px.shape)} {px.dtype}")
+        y = self(px.to(self.device).float().div(255.0).to(torch.bfloat16))
+        return y.float().clamp(0.0, 1.0).mul(255.0).round().to(torch.uint8).contiguous()
+
 
 def read_upscaler(path: str, device="cuda:0") -> RRDBNet:
     """a LOCAL .safetensors or .pth (torch.load(weights_only=True)) file -> RRDBNet; nothing is downloaded"""

@@ -91,6 +91,9 @@ class ModelSpec(BaseModel):  # reference util.py:38-79 (unknown JSON keys are ig
     # (config.json + model.safetensors / *.bin of DepthAnythingForDepthEstimation, e.g. a copy of LiheYoung/depth-anything-large-hf).
     # Nothing is downloaded; FluxPipeline.depth_model is None unless the directory exists
     depth_path: str | None = None
+    # who writes the JPEG of an output_type="jpeg" request that does not say (generate(jpeg_encoder=...)): "pil" (Pillow on the host, the
+    # reference's path) or "native" (fluxmi.ops.jpeg_encode on the device: the same decoded pixels, restart markers in the stream)
+    jpeg_encoder: str = "pil"
 
     model_config: ConfigDict = {"arbitrary_types_allowed": True, "use_enum_values": True}
 

@@ -486,6 +486,60 @@ int fluxmi_rgb_to_gray(const void* rgb, long long ld, long long bs, void* gray, 
 int fluxmi_gaussian_blur(const void* src, long long ld, long long bs, void* dst, long long dst_ld, long long dst_bs, void* work,
                          long long work_bytes, int B, int H, int W, int C, float sigma, void* stream);
 
+/* ---- baseline JPEG encoder (csrc/jpeg.hip, csrc/jpeg_host.cpp): device pixels -> the bytes of a JFIF file --------------------------------
+ * A baseline sequential (SOF0) Huffman-coded JPEG of rgb uint8 [B][H][W][3] (row stride ld, image stride bs, in bytes, as above).  Everything
+ * is integer arithmetic and the text below IS the definition: the kernels and tests/jpeg_ref.py match it byte for byte.  It is libjpeg's
+ * integer pipeline at its defaults (the "islow" DCT, the Annex K tables), so a stream decodes to what that library's own stream decodes to;
+ * tests/test_jpeg_cpu.py pins byte equality of the entropy-coded segment with Pillow on libjpeg-turbo.
+ *   Input.   A batch is ONE image of B * H rows: image b's row r is row b * H + r.  W <= 65535 and B * H <= 65535, any H, W >= 1.
+ *   Colour.  Y  = ( 19595 R + 38470 G +  7471 B + 32768) >> 16
+ *            Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16        (>> is arithmetic)
+ *            Cr = ( 32768 R - 27439 G -  5329 B + (128 << 16) + 32767) >> 16
+ *   Subsampling.  FLUXMI_JPEG_420: 16 x 16 MCUs, blocks Y00 Y01 Y10 Y11 Cb Cr, chroma sample (i, j) = (a + b + c + d + bias) >> 2 of the
+ *            2 x 2 box at (2i, 2j), bias = 1 for even j and 2 for odd j.  FLUXMI_JPEG_444: 8 x 8 MCUs, blocks Y Cb Cr.
+ *   Edges.   MCUs run left to right, top to bottom over ceil(W / m) x ceil(B H / m) MCUs (m = 16 or 8).  A sample right of the image repeats
+ *            the last column, a sample below it the last row -- of ITS OWN plane: below a 4:2:0 image the last CHROMA row repeats (the box
+ *            of rows B H - 2 and B H - 1 when B H is even), which is how libjpeg pads.  A Y block of a 4:2:0 MCU that holds no image pixel
+ *            at all (block column >= ceil(W / 8) or block row >= ceil(B H / 8)) is libjpeg's dummy block: no AC levels, and the DC LEVEL
+ *            of the block before it in the MCU (which may itself be a dummy block).
+ *   DCT.     Samples - 128, then the accurate integer forward DCT: rows, then columns, each the 12-multiply butterfly with 13-bit
+ *            constants (2446 3196 4433 6270 7373 9633 12299 15137 16069 16819 20995 25172); the row pass keeps 2 extra bits (outputs 0 and
+ *            4 shifted left by 2, the others descaled by 11 bits), the column pass removes them (by 2 and by 15 bits); descale(x, n) =
+ *            (x + (1 << (n - 1))) >> n.  The result is the DCT scaled by 8.
+ *   Quantisation.  Annex K.1's tables, entry t -> clamp((t s + 50) / 100, 1, 255) with s = 5000 / quality below 50 and 200 - 2 quality
+ *            from 50 (quality 1..100, integer division).  Level of coefficient c: sign(c) ((|c| + 4 t) / (8 t)).
+ *   Entropy coding.  Annex K.3's four Huffman tables, canonical codes; per block the DC difference against the previous block of the same
+ *            component (category + magnitude bits, a negative value v as v - 1 in `category` bits), then (run, size) symbols for the
+ *            non-zero AC levels in zigzag order, ZRL (0xF0) for every 16 zeros of a run, EOB unless level 63 is non-zero; bits most
+ *            significant first, a byte 0xFF followed by 0x00.
+ *   Restarts.  restart = R in 1..65535: a DRI segment; after every R MCUs (but the last) the stream is padded with 1-bits to a byte, RSTm
+ *            with m = k mod 8 for the k-th marker follows, and the DC predictions restart at 0.  R = 0: no DRI, no markers; the device then
+ *            codes the whole image as one interval in one workgroup -- correct and slow.  FLUXMI_JPEG_RESTART_420 / _444 (24 blocks per
+ *            interval either way) are what fluxmi.ops picks when not told: ~2.5 bytes per interval, 0.1 - 0.6 % of a quality-99 file.
+ *   Header.  SOI, APP0 (JFIF 1.01, aspect 1:1), DQT 0, DQT 1, SOF0, DHT (DC 0, AC 0, DC 1, AC 1), DRI when R > 0, SOS; EOI ends the file.
+ * Three launches and no host wait: (1) one workgroup per 16 x 16 pixels converts, downsamples, transforms and quantises into int16 levels,
+ * zigzag order, MCU by MCU; (2) one workgroup per interval codes its blocks, one wave per block (a ballot gives the non-zero mask, each
+ * lane its run, code and length, a wave prefix sum the bit positions), assembles the bits in LDS, stuffs them and writes them to the
+ * interval's own slot of `work` -- FLUXMI_JPEG_SLOT_BYTES_PER_BLOCK bytes per block, twice the worst case of 1660 bits, so no slot can
+ * overflow -- and records the byte count; (3) a prefix sum of the counts, then each slot is copied behind the header with its marker.
+ * An interval's bytes are written by its own workgroup alone: the same input gives the same bytes, run to run.
+ * fluxmi_jpeg_workspace_bytes: *work_bytes = the size of `work` (256-byte aligned), *out_cap = a size of `out` no stream can exceed.
+ * fluxmi_jpeg_encode: asynchronous.  Writes the file to out[0 .. n) and n (int64) to *n_bytes_dev, a DEVICE address.  No byte at or beyond
+ *   out + out_cap is written whatever n is; n > out_cap means the file did not fit and `out` holds a truncated stream.  An out_cap below the
+ *   header + EOI is refused here.
+ * fluxmi_jpeg_finish: the one small read-back: *n_bytes = *n_bytes_dev after synchronising `stream`; n > out_cap is an error.
+ * fluxmi_jpeg_header: host only: the header bytes (SOI .. SOS) of such a file into buf[0 .. cap), *n_bytes = their count. */
+#define FLUXMI_JPEG_420 0
+#define FLUXMI_JPEG_444 1
+#define FLUXMI_JPEG_RESTART_420 4
+#define FLUXMI_JPEG_RESTART_444 8
+#define FLUXMI_JPEG_SLOT_BYTES_PER_BLOCK 416
+int fluxmi_jpeg_workspace_bytes(int B, int H, int W, int subsampling, int restart, long long* work_bytes, long long* out_cap);
+int fluxmi_jpeg_encode(const void* rgb, long long ld, long long bs, int B, int H, int W, int quality, int subsampling, int restart, void* work,
+                       void* out, long long out_cap, void* n_bytes_dev, void* stream);
+int fluxmi_jpeg_finish(const void* n_bytes_dev, long long out_cap, long long* n_bytes, void* stream);
+int fluxmi_jpeg_header(int B, int H, int W, int quality, int subsampling, int restart, void* buf, long long cap, long long* n_bytes);
+
 /* ---- depth estimator pieces (csrc/depth.hip; modules/depth.py: Depth Anything = a DINOv2 tower + a DPT decoder) -----------------------
  * The tower runs on the vision-encoder entry points above, the decoder's stride-1 convolutions on fluxmi_conv3x3 / fluxmi_conv3x3_dense; what
  * those do not cover is here.  Maps are NHWC bf16: [B][H][W] pixels addressed densely with ONE pixel stride `ld` in elements (ld >= C,

@@ -23,6 +23,35 @@ extern "C" {
 const char* fluxmi_last_error(void) { return g_err; }
 int fluxmi_abi_version(void) { return FLUXMI_ABI_VERSION; }
 
+// The alignment contract of fluxmi_gemm_group_t (include/fluxmi.h): every kernel fetches A and W in 16-byte pieces (LDS-DMA, uint4 loads), and
+// the tiled and split-K kernels read bias / gate / resid and store C / C2 as 8- or 16-byte vectors at columns that are multiples of 8 (bf16) or
+// 16 (fp8).  The generic kernel touches its outputs one element at a time: where only it can run (tile_cfg 100, or an N no tile divides) the
+// outputs need no more than their element's alignment.
+static int gemm_check_alignment(const fluxmi_gemm_group_t& g, int i, int N, int is_fp8, int epilogue, int tile_cfg) {
+  auto al16 = [](const void* p) { return ((unsigned long long)p & 15) == 0; };
+  const long long eb = is_fp8 ? 1 : 2;
+  FLUXMI_REQUIRE(al16(g.A), "gemm_grouped: group %d: A=%p must be 16-byte aligned", i, g.A);
+  FLUXMI_REQUIRE(al16(g.W), "gemm_grouped: group %d: W=%p must be 16-byte aligned", i, g.W);
+  FLUXMI_REQUIRE(g.lda * eb % 16 == 0, "gemm_grouped: group %d: lda=%lld: a row of A must be a multiple of 16 bytes", i, g.lda);
+  if (tile_cfg == 100 || N % 64 != 0) return 0;
+  const bool q_out = epilogue == FLUXMI_EPI_GELU_QUANT || epilogue == FLUXMI_EPI_QUANT || epilogue == FLUXMI_EPI_SILU_QUANT;
+  FLUXMI_REQUIRE(al16(g.C), "gemm_grouped: group %d: C=%p must be 16-byte aligned", i, g.C);
+  FLUXMI_REQUIRE(g.ldc * (q_out ? 1 : 2) % 16 == 0, "gemm_grouped: group %d: ldc=%lld: a row of C must be a multiple of 16 bytes", i, g.ldc);
+  FLUXMI_REQUIRE(al16(g.bias), "gemm_grouped: group %d: bias=%p must be 16-byte aligned", i, g.bias);
+  if (epilogue == FLUXMI_EPI_GATE_RESID) {
+    FLUXMI_REQUIRE(al16(g.gate), "gemm_grouped: group %d: gate=%p must be 16-byte aligned", i, g.gate);
+    FLUXMI_REQUIRE(al16(g.resid), "gemm_grouped: group %d: resid=%p must be 16-byte aligned", i, g.resid);
+    FLUXMI_REQUIRE(g.ldr * 2 % 16 == 0, "gemm_grouped: group %d: ldr=%lld: a row of resid must be a multiple of 16 bytes", i, g.ldr);
+  }
+  if (epilogue == FLUXMI_EPI_SPLIT) {
+    FLUXMI_REQUIRE(al16(g.C2), "gemm_grouped: group %d: C2=%p must be 16-byte aligned", i, g.C2);
+    FLUXMI_REQUIRE(g.ldc2 % 16 == 0, "gemm_grouped: group %d: ldc2=%lld: a row of C2 must be a multiple of 16 bytes", i, g.ldc2);
+    FLUXMI_REQUIRE(g.c2_col0 % 16 == 0, "gemm_grouped: group %d: c2_col0=%d must be a multiple of 16", i, g.c2_col0);
+    FLUXMI_REQUIRE(g.split_n % 16 == 0, "gemm_grouped: group %d: split_n=%d must be a multiple of 16", i, g.split_n);
+  }
+  return 0;
+}
+
 int fluxmi_gemm_grouped(const fluxmi_gemm_group_t* groups, int n_groups, int N, int K, int is_fp8, int act_fmt, int epilogue,
                         int tile_cfg, void* stream) {
   FLUXMI_REQUIRE(groups && n_groups >= 1 && n_groups <= FLUXMI_MAX_GROUPS, "gemm_grouped: n_groups=%d (1..%d)", n_groups, FLUXMI_MAX_GROUPS);
@@ -33,6 +62,7 @@ int fluxmi_gemm_grouped(const fluxmi_gemm_group_t* groups, int n_groups, int N, 
     p.g[i] = groups[i];
     FLUXMI_REQUIRE(groups[i].M >= 0, "gemm_grouped: group %d has M=%d", i, groups[i].M);
     FLUXMI_REQUIRE(groups[i].M == 0 || (groups[i].A && groups[i].W && groups[i].C), "gemm_grouped: group %d has NULL A/W/C", i);
+    if (groups[i].M > 0) FLUXMI_TRY(gemm_check_alignment(groups[i], i, N, is_fp8, epilogue, tile_cfg));  // before any launch: a refused call has done nothing
   }
   p.n_groups = n_groups; p.N = N; p.K = K; p.epi = epilogue;
   if (tile_cfg == 100) return fluxmi_launch_gemm_generic(p, is_fp8, act_fmt, (hipStream_t)stream);

@@ -48,7 +48,20 @@ enum {
   FLUXMI_EPI_SILU_QUANT = 5  /* C(fp8)  = q(bf16(silu(h)), q_scale)           flux_model.py:154-155 */
 };
 
-/* one problem of a (grouped) linear: out[M,N] = epilogue(A[M,K] . W[N,K]^T) */
+/* one problem of a (grouped) linear: out[M,N] = epilogue(A[M,K] . W[N,K]^T)
+ *
+ * Strides and alignment.  lda, ldc, ldr count ELEMENTS of their buffer (fp8: bytes; bf16: 2 bytes each; ldc of a quantising epilogue:
+ * bytes), ldc2 and c2_col0 count bytes of the fp8 output C2, split_n counts columns of N.  Operands and outputs may be views of wider
+ * buffers (lda > K, ldc > N, ldr != ldc, resid == C); nothing outside rows [0, M) x the view's columns is written.
+ *   - A, W: 16-byte aligned, and a row of A (lda elements) a multiple of 16 bytes -- every kernel fetches them in 16-byte pieces.  The
+ *     one-wave-per-SIMD and persistent kernels address A through a buffer descriptor of M * lda elements from A: a view's last row is
+ *     followed by up to lda - K elements that lie inside the descriptor and may be FETCHED (never used), so they must be readable.
+ *   - C, C2, bias, gate, resid: 16-byte aligned; rows of C, C2 and resid (ldc, ldc2, ldr) multiples of 16 bytes; c2_col0 and split_n
+ *     multiples of 16 (a tile config also needs split_n to be a multiple of its N tile).  The tiled and split-K kernels load and store these as
+ *     8- and 16-byte vectors.  The generic kernel (tile_cfg 100, and every N that is not a multiple of 64) touches them one element at
+ *     a time: there they need only their element's alignment.
+ * fluxmi_gemm_grouped refuses a group that violates this, by field name, before it launches anything.  Groups with M == 0 are allowed
+ * anywhere in a launch: they get no tile and none of their pointers is followed. */
 typedef struct fluxmi_gemm_group {
   const void* A;          /* activations [M,K]: fp8 bytes (F8Linear) or bf16 (nn.Linear) */
   const void* W;          /* weight [N,K] row-major = F8Linear.float8_data / nn.Linear.weight */

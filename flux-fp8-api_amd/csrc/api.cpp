@@ -246,6 +246,12 @@ int fluxmi_rgb_to_gray(const void* rgb, long long ld, long long bs, void* gray, 
                        void* stream) {
   return fluxmi_k_rgb_to_gray(rgb, ld, bs, gray, gray_ld, gray_bs, B, H, W, (hipStream_t)stream);
 }
+int fluxmi_resample_u8(const void* src, long long ld, long long bs, void* dst, long long dst_ld, long long dst_bs, void* work,
+                       long long work_bytes, int B, int H, int W, int C, int h, int w, int filter, const int* bounds_x, const int* kk_x,
+                       const int* bounds_y, const int* kk_y, void* stream) {
+  return fluxmi_k_resample_u8(src, ld, bs, dst, dst_ld, dst_bs, work, work_bytes, B, H, W, C, h, w, filter, bounds_x, kk_x, bounds_y, kk_y,
+                              (hipStream_t)stream);
+}
 int fluxmi_gaussian_blur(const void* src, long long ld, long long bs, void* dst, long long dst_ld, long long dst_bs, void* work,
                          long long work_bytes, int B, int H, int W, int C, float sigma, void* stream) {
   return fluxmi_k_gaussian_blur(src, ld, bs, dst, dst_ld, dst_bs, work, work_bytes, B, H, W, C, sigma, (hipStream_t)stream);

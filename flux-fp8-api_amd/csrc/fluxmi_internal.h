@@ -271,6 +271,23 @@ struct FluxmiJpegPlan {
 int fluxmi_jpeg_plan(const char* who, int B, int H, int W, int quality, int subsampling, int restart, FluxmiJpegPlan* p);
 int fluxmi_k_jpeg_encode(const FluxmiJpegPlan& p, const void* rgb, long long ld, long long bs, void* work, void* out, long long out_cap,
                          void* n_bytes_dev, hipStream_t s);
+// the image resampler (include/fluxmi.h, fluxmi_resample_*): one axis' geometry and the plan of one resize (resample_host.cpp), and the
+// launches that run it (resample.hip)
+struct FluxmiResampleAxis {
+  int n_in, ksize;
+  double scale, support, ss;  // in / out, filter support x max(scale, 1), 1 / max(scale, 1)
+};
+struct FluxmiResamplePlan {
+  FluxmiResampleAxis ax, ay;
+  int do_x, do_y, fused;       // the width changes, the height changes, both passes run in one launch
+  long long pitch, work_bytes; // row pitch of the two-launch path's intermediate [B][H][pitch], its size (0 when not needed)
+};
+FluxmiResampleAxis fluxmi_resample_axis(int n_in, int n_out, int filter);
+void fluxmi_resample_bounds(const FluxmiResampleAxis& a, int xx, int* xmin, int* n);
+int fluxmi_resample_make_plan(const char* who, int B, int H, int W, int C, int h, int w, int filter, FluxmiResamplePlan* p);
+int fluxmi_k_resample_u8(const void* src, long long ld, long long bs, void* dst, long long dld, long long dbs, void* work, long long work_bytes,
+                         int B, int H, int W, int C, int h, int w, int filter, const int* bounds_x, const int* kk_x, const int* bounds_y,
+                         const int* kk_y, hipStream_t s);
 int fluxmi_k_vision_attention(const void* q, const void* k, long long ld_qk, long long bs_qk, const void* vt, long long ld_vt, long long bs_vt,
                               void* out, long long ld_out, long long bs_out, const void* v_bias, float scale, int head_dim, int L, int Lp, int H,
                               int B, hipStream_t s);

@@ -35,6 +35,7 @@ from util import (ModelSpec, ModelVersion, engine_flow_dtype, into_device, into_
 
 MAX_RAND = 2**32 - 1
 CONTROL_PREPROCESSORS = ("canny", "gray", "blur", "depth_anything")  # generate(control_preprocess=...) / preprocess_control: the maps made from a photo
+IMAGE_RESIZERS = ("pil", "native")  # generate(image_resize=...) / ModelSpec.image_resize: Pillow on the host, or fluxmi.ops.resize_u8 on the device
 JPEG_ENCODERS = ("pil", "native")  # generate(jpeg_encoder=...) / ModelSpec.jpeg_encoder: Pillow on the host, or fluxmi.ops.jpeg_encode on the device
 GUIDANCE_MODES = ("cfg", "apg", "cfg_zero_star")  # generate(guidance_mode=...): the rule that combines the two branches of true CFG
 
@@ -342,7 +343,8 @@ class FluxPipeline:
 
     # ---- FLUX.1 Kontext reference image ------------------------------------------------------------------------------------------------
     @torch.inference_mode()
-    def prepare_kontext_reference(self, reference_image, num_images: int = 1, generator: torch.Generator = None):
+    def prepare_kontext_reference(self, reference_image, num_images: int = 1, generator: torch.Generator = None,
+                                  image_resize: Optional[str] = None):
         """The reference image of an instruction edit (FLUX.1 Kontext [dev]) -> (img_cond_seq [num_images, Lc, 64], img_cond_seq_ids
         [num_images, Lc, 3]) in the flow dtype on the flow device.  The semantics of BFL's prepare_kontext / denoise (src/flux/sampling.py),
         kept here in one place:
@@ -363,15 +365,14 @@ class FluxPipeline:
             raise RuntimeError("fluxmi: a Kontext reference image needs an autoencoder (config.ae_path) -- none is attached")
         ref = self.load_init_image_if_needed(reference_image)
         if isinstance(ref, torch.Tensor):
-            ref = ref.detach().cpu()
             if ref.dtype != torch.uint8:
                 raise TypeError(f"fluxmi: a reference image tensor must be uint8 HWC, got {ref.dtype}")
-            ref = ref.numpy()
-        pil = Image.fromarray(np.asarray(ref)).convert("RGB")
-        width, height = pil.size
+            if not ref.is_cuda:
+                ref = ref.detach().numpy()
+        src = self._rgb_source(ref if isinstance(ref, torch.Tensor) else Image.fromarray(np.asarray(ref)), image_resize)
+        width, height = self._rgb_size(src)
         _, _, w_l, h_l = kontext_reference_size(width, height)
-        pil = pil.resize((8 * w_l, 8 * h_l), Image.LANCZOS)
-        x = torch.from_numpy(np.array(pil)).permute(2, 0, 1).float().div(127.5).sub(1.0)[None]
+        x = self._unit_range(self._resize_rgb(src, (8 * w_l, 8 * h_l), "lanczos"))
         x = x.to(self.device_ae, dtype=self.ae_dtype)
         f = 1 << (self.ae.encoder.num_resolutions - 1)  # the encoder's downsampling (8 for every Flux autoencoder)
         z_ch = self.ae.encoder.conv_out.out_channels // 2
@@ -405,6 +406,64 @@ class FluxPipeline:
                 raise TypeError(f"fluxmi: a conditioning image tensor must be uint8 HWC, got {im.dtype}")
             im = im.numpy()
         return im if isinstance(im, Image.Image) else Image.fromarray(np.asarray(im))
+
+    # ---- the request's image resizes: Pillow on the host ("pil"), or fluxmi.ops.resize_u8 on the device ("native") -------------------------
+    def _image_resize(self, image_resize: Optional[str]) -> str:
+        """the request's resizer: its own `image_resize`, else the configuration's (ModelSpec.image_resize, "pil" when absent); an unknown
+        value is refused by name"""
+        mode = image_resize if image_resize is not None else getattr(getattr(self, "config", None), "image_resize", "pil")
+        if mode not in IMAGE_RESIZERS:
+            raise ValueError(f"fluxmi: image_resize={mode!r}: expected one of {IMAGE_RESIZERS}")
+        return mode
+
+    def _rgb_source(self, image, image_resize: Optional[str] = None):
+        """an image in any form `init_image` takes, or a uint8 [H, W, 3] tensor already on a device -> what the request's resizes work on:
+        "pil": the PIL RGB image, as before; "native": uint8 [H, W, 3] on the autoencoder's device -- the ONE upload, at the image's own
+        size; every later _resize_rgb of it stays there."""
+        mode = self._image_resize(image_resize)
+        if mode == "native" and isinstance(image, torch.Tensor) and image.is_cuda and image.dtype == torch.uint8 and image.ndim == 3 \
+                and image.shape[-1] == 3:
+            return image  # already where the resizes run; any other tensor takes the host's conversion to RGB below, as it always did
+        pil = self._rgb_uint8(image).convert("RGB")
+        if mode == "pil":
+            return pil
+        dev = self.device_ae if getattr(self, "ae", None) is not None else self.device_flux
+        return torch.from_numpy(np.array(pil)).to(dev)
+
+    @staticmethod
+    def _rgb_size(src):
+        """(width, height) of what _rgb_source returned"""
+        return (src.shape[1], src.shape[0]) if isinstance(src, torch.Tensor) else src.size
+
+    @staticmethod
+    def _resize_rgb(src, size, filter: str = "lanczos"):
+        """what _rgb_source returned -> the same kind at size = (width, height): exactly Image.resize(size, filter) for a PIL image, and
+        fluxmi.ops.resize_u8 -- the same bytes -- for pixels on the device"""
+        from PIL import Image
+
+        if not isinstance(src, torch.Tensor):
+            return src.resize(size, {"lanczos": Image.LANCZOS, "bicubic": Image.BICUBIC}[filter])
+        with torch.cuda.device(src.device):  # the kernel launches on the current stream: make it the pixels' device's
+            return ops.resize_u8(src[None], size, filter)[0]
+
+    @staticmethod
+    def _unit_range(src) -> torch.Tensor:
+        """what _rgb_source / _resize_rgb returned -> fp32 [1, 3, H, W] in [-1, 1] where it lives: v / 127.5 - 1.  On the device the 256
+        possible values are computed on the host, as for a PIL image, and looked up, so both kinds give the same bits."""
+        if not isinstance(src, torch.Tensor):
+            return torch.from_numpy(np.array(src)).float().div(127.5).sub(1.0).permute(2, 0, 1)[None]
+        lut = torch.arange(256, dtype=torch.uint8).float().div(127.5).sub(1.0).to(src.device)
+        return lut[src.long()].permute(2, 0, 1)[None]
+
+    @torch.inference_mode()
+    def resize(self, image, width: int, height: int, filter: str = "lanczos", image_resize: Optional[str] = "native") -> torch.Tensor:
+        """`image` (any form `init_image` takes) resized to width x height alone -> uint8 [height, width, 3] on the host: PIL's
+        Image.resize(size, filter) of the RGB image, byte for byte, computed on the device (fluxmi.ops.resize_u8; "lanczos" or "bicubic")
+        unless image_resize="pil" asks for Pillow itself."""
+        if filter not in ("lanczos", "bicubic"):
+            raise ValueError(f"fluxmi: resize filter={filter!r}: expected \"lanczos\" or \"bicubic\" (fluxmi.ops.resize_u8 has the others)")
+        out = self._resize_rgb(self._rgb_source(image, image_resize), (int(width), int(height)), filter)
+        return out.cpu() if isinstance(out, torch.Tensor) else torch.from_numpy(np.array(out))
 
     def _encode_sampled(self, x: torch.Tensor, generator: torch.Generator = None) -> torch.Tensor:
         """VAE-encode x [1, 3, H, W] in [-1, 1] with the Gaussian sample [1, z_channels, H/8, W/8] drawn from `generator` -> bf16 latents"""
@@ -454,7 +513,7 @@ class FluxPipeline:
 
     @torch.inference_mode()
     def prepare_control_conditioning(self, control_image, height: int, width: int, num_images: int = 1,
-                                     generator: torch.Generator = None) -> torch.Tensor:
+                                     generator: torch.Generator = None, image_resize: Optional[str] = None) -> torch.Tensor:
         """FLUX.1 Depth / Canny [dev] -> img_cond bf16 [num_images, Li, 64] on the flow device (BFL's prepare_control, src/flux/sampling.py):
         the RGB control image is resized to (width, height) with PIL LANCZOS, goes to float / 127.5 - 1, is VAE-encoded with its Gaussian
         sample (drawn from `generator` after the noise, as in prepare_fill_conditioning), cast to bf16 and packed 2 x 2.  `control_image` is
@@ -464,14 +523,13 @@ class FluxPipeline:
 
         if self.ae is None:
             raise RuntimeError("fluxmi: FLUX.1 Depth / Canny conditioning needs an autoencoder (config.ae_path) -- none is attached")
-        pil = self._rgb_uint8(control_image).convert("RGB").resize((width, height), Image.LANCZOS)
-        x = torch.from_numpy(np.array(pil)).float().div(127.5).sub(1.0).permute(2, 0, 1)[None]
+        x = self._unit_range(self._resize_rgb(self._rgb_source(control_image, image_resize), (width, height), "lanczos"))
         cond = self.pack(self._encode_sampled(x, generator))
         return cond.to(self.device_flux).repeat(num_images, 1, 1).contiguous()
 
     @torch.inference_mode()
     def prepare_controlnet_conditioning(self, controlnet_image, height: int, width: int, num_images: int = 1,
-                                        generator: torch.Generator = None) -> torch.Tensor:
+                                        generator: torch.Generator = None, image_resize: Optional[str] = None) -> torch.Tensor:
         """A ControlNet's `cond` bf16 [num_images, Li, 64] on the flow device (diffusers' FluxControlNetPipeline.prepare_image + the latent
         handling of its __call__): the control image, in any form `init_image` takes, is resized like `control_image`, VAE-encoded (its
         Gaussian sample drawn from `generator` after the noise), shifted and scaled, cast to bf16 and packed 2 x 2.  `controlnet_image` is
@@ -479,7 +537,8 @@ class FluxPipeline:
         a photo by preprocess_control (generate's `control_preprocess`); a pose preprocessor is not part of this project."""
         if self.ae is None:
             raise RuntimeError("fluxmi: controlnet_image needs an autoencoder (config.ae_path) -- none is attached; pass controlnet_cond")
-        return self.prepare_control_conditioning(controlnet_image, height, width, num_images=num_images, generator=generator)
+        return self.prepare_control_conditioning(controlnet_image, height, width, num_images=num_images, generator=generator,
+                                                 image_resize=image_resize)
 
     # ---- control-map preprocessors (csrc/preprocess.hip) ---------------------------------------------------------------------------------
     def _check_control_preprocess(self, kind, canny_low=100, canny_high=200, canny_l2=False, blur_sigma=8.0, depth_resolution=518,
@@ -522,7 +581,7 @@ class FluxPipeline:
     @torch.inference_mode()
     def preprocess_control(self, image, kind: str, width: Optional[int] = None, height: Optional[int] = None, canny_low: int = 100,
                            canny_high: int = 200, canny_l2: bool = False, blur_sigma: float = 8.0, depth_resolution: int = 518,
-                           depth_normalize: str = "minmax") -> torch.Tensor:
+                           depth_normalize: str = "minmax", image_resize: Optional[str] = None, on_device: bool = False) -> torch.Tensor:
         """A photo -> the control map a FLUX.1 Canny [dev] checkpoint or a ControlNet follows: uint8 [H, W, 3] on the host.  `image`: any form
         `init_image` takes.  It is first resized to (width, height) with PIL LANCZOS, exactly as prepare_control_conditioning resizes a map
         (BFL runs its Canny after the resize too; None keeps the image's own size), then goes to the autoencoder's device and through one
@@ -539,18 +598,20 @@ class FluxPipeline:
                    x / 255, ImageNet mean / std), the model, and fluxmi_depth_to_map back to the image's size: `depth_normalize` "minmax"
                    maps the image's own min..max to 0..255 (the form diffusers' and the ControlNet annotators' depth maps take), "raw"
                    writes clamp(depth, 0, 255).  Parity with BFL's DepthImageEncoder post-processing is NOT pinned.
-        A one-channel result is repeated to three channels.  Pose, tile and low-quality maps are not made here."""
-        from PIL import Image
-
+        A one-channel result is repeated to three channels.  Pose, tile and low-quality maps are not made here.
+        `image_resize` (None = the configuration's): "native" uploads the photo once at its own size and resizes it on the device
+        (fluxmi.ops.resize_u8: the same bytes as PIL's), the estimator's bicubic resize included.  `on_device`: leave the map where it was made."""
         self._check_control_preprocess(kind, canny_low, canny_high, canny_l2, blur_sigma, depth_resolution, depth_normalize, width, height)
-        pil = self._rgb_uint8(image).convert("RGB")
-        size = (pil.width if width is None else int(width), pil.height if height is None else int(height))
-        if size != pil.size:
-            pil = pil.resize(size, Image.LANCZOS)
+        src = self._rgb_source(image, image_resize)
+        own = self._rgb_size(src)
+        size = (own[0] if width is None else int(width), own[1] if height is None else int(height))
+        if size != own:
+            src = self._resize_rgb(src, size, "lanczos")
         if kind == "depth_anything":
-            return self.depth_model.depth_map(pil, (size[1], size[0]), depth_resolution, depth_normalize).cpu()
+            y = self.depth_model.depth_map(src, (size[1], size[0]), depth_resolution, depth_normalize)
+            return y if on_device else y.cpu()
         dev = self.device_ae if getattr(self, "ae", None) is not None else self.device_flux
-        x = torch.from_numpy(np.array(pil)).to(dev)[None].contiguous()
+        x = (src if isinstance(src, torch.Tensor) else torch.from_numpy(np.array(src)).to(dev))[None].contiguous()
         if kind == "canny":
             y = ops.canny(x, canny_low, canny_high, canny_l2)
         elif kind == "gray":
@@ -558,10 +619,11 @@ class FluxPipeline:
         else:
             y = ops.gaussian_blur(x, blur_sigma)
         y = y[0] if y.ndim == 4 else y[0][..., None].expand(-1, -1, 3)
-        return y.contiguous().cpu()
+        return y.contiguous() if on_device else y.contiguous().cpu()
 
     # ---- FLUX IP-Adapter image prompts ---------------------------------------------------------------------------------------------------
-    def prepare_ip_adapter(self, images, image_embeds, scale, negative_image, negative_scale, guided: bool):
+    def prepare_ip_adapter(self, images, image_embeds, scale, negative_image, negative_scale, guided: bool,
+                           image_resize: Optional[str] = None):
         """-> (call, guided_call): the `ip_adapter=` arguments of Flux.denoise for the unguided steps (the prompt branch's K / V, [depth, 1,
         Nk, H]) and, for a guided request, for the guided steps ([depth, 2, Nk, H]: prompt branch, then negative branch with its own K / V
         and scale; else None).  The negative branch defaults to black images, one per prompt image (XLabs); a float tensor [n, 768] is
@@ -569,7 +631,8 @@ class FluxPipeline:
         from modules.ip_adapter import IPAdapterCall
 
         ad = self.ip_adapter
-        emb = ad.embed(images) if image_embeds is None else image_embeds
+        rs_kw = {} if self._image_resize(image_resize) == "pil" else dict(image_resize="native")  # CLIP's bicubic resize on the device
+        emb = ad.embed(images, **rs_kw) if image_embeds is None else image_embeds
         k, v = ad.kv(emb)
         call = IPAdapterCall(k, v, scale)
         if not guided:
@@ -581,7 +644,7 @@ class FluxPipeline:
             if negative_image is None:
                 S = ad.clip.cfg["image_size"] if ad.clip is not None else 224
                 negative_image = [np.zeros((S, S, 3), dtype=np.uint8)] * n
-            nemb = ad.embed(negative_image)
+            nemb = ad.embed(negative_image, **rs_kw)
         if nemb.shape[0] != emb.shape[0]:
             raise ValueError(f"fluxmi: negative_ip_adapter_image holds {nemb.shape[0]} images, ip_adapter_image {emb.shape[0]} (both branches "
                              "run in one batch: the same number of image tokens)")
@@ -599,13 +662,14 @@ class FluxPipeline:
         return list(redux_image) if isinstance(redux_image, (list, tuple)) else [redux_image]
 
     @torch.inference_mode()
-    def prepare_redux_tokens(self, images, num_images: int = 1, txt: Optional[torch.Tensor] = None):
+    def prepare_redux_tokens(self, images, num_images: int = 1, txt: Optional[torch.Tensor] = None, image_resize: Optional[str] = None):
         """FLUX.1 Redux [dev]: steps 1-4 of modules/image_embedders.py's docstring.  `images`: one image in any form `init_image` takes,
         or a list of them (729 tokens per image, in list order).  Returns the Redux tokens [num_images, 729 n, 4096] in the flow dtype on
         the flow device; with `txt` [num_images, Lt5, 4096] (the T5 states), returns (txt, txt_ids) with the tokens appended behind the T5
         tokens and txt_ids = zeros [num_images, Lt5 + 729 n, 3], as BFL's prepare_redux builds them."""
         self._require_redux()
-        tok = self.redux(self._redux_list(images)).to(device=self.device_flux, dtype=torch.bfloat16)
+        rs_kw = {} if self._image_resize(image_resize) == "pil" else dict(image_resize="native")  # SigLIP's bicubic resize on the device
+        tok = self.redux(self._redux_list(images), **rs_kw).to(device=self.device_flux, dtype=torch.bfloat16)
         tok = tok.reshape(1, -1, tok.shape[-1]).to(self.dtype).repeat(num_images, 1, 1)
         if txt is None:
             return tok
@@ -794,7 +858,7 @@ class FluxPipeline:
                  edit_n_max: Optional[int] = None, edit_n_min: int = 0, edit_n_avg: int = 1, tile_size=None, tile_overlap: Optional[int] = None,
                  tile_weight: str = "cosine", upscale: bool = False, init_upscale: bool = False, control_preprocess: Optional[str] = None,
                  canny_low: int = 100, canny_high: int = 200, canny_l2: bool = False, blur_sigma: float = 8.0, depth_resolution: int = 518,
-                 depth_normalize: str = "minmax", jpeg_encoder: Optional[str] = None):
+                 depth_normalize: str = "minmax", jpeg_encoder: Optional[str] = None, image_resize: Optional[str] = None):
         """`reference_image` (FLUX.1 Kontext [dev] instruction editing): an image the prompt describes an edit of, in any form `init_image`
         takes; see prepare_kontext_reference.  Composes with `init_image` / `strength` unchanged.
         FLUX.1 Fill [dev] (a model with 320 conditioning channels): `init_image` is the image to inpaint and `mask_image` (white =
@@ -953,6 +1017,10 @@ class FluxPipeline:
         "raw".  Refused up front: the kind without a depth model (naming `depth_path`), a `depth_resolution` outside 14..1036, a patch grid
         above 74 x 74 + 1 tokens (the longest sequence the estimator's attention is checked at), an unknown `depth_normalize`, and either
         argument without the kind.  `control_preprocess="depth"` stays refused: the kind is named after its model.
+        `image_resize` ("pil" | "native"; None = config.image_resize, "pil" unless configured): who resizes the request's images -- the
+        Kontext reference, a control image / ControlNet image, the photo of `control_preprocess` (its estimator's bicubic resize included).
+        "pil" is Pillow on the host, the calls this method always made.  "native" uploads each image once at its own size and resizes it on
+        the device (fluxmi.ops.resize_u8: Pillow's integer resampler, the same bytes), so the latents are the same bit for bit.
         `jpeg_encoder` ("pil" | "native"; None = config.jpeg_encoder, "pil" unless configured): who writes the JPEG of output_type="jpeg".
         "pil" is today's path, byte for byte: pixels to the host, Pillow at `jpeg_quality`.  "native" keeps the pixels on the device from the
         VAE (and the upscaler) to fluxmi.ops.jpeg_encode -- a baseline JFIF file, 4:2:0, the Annex K tables at `jpeg_quality`, restart markers
@@ -978,6 +1046,7 @@ class FluxPipeline:
             prep_kw.update(depth_resolution=depth_resolution, depth_normalize=depth_normalize)
         if upscale or init_upscale:
             init_image = self._check_upscale(upscale, init_upscale, output_type, init_image, width, height, num_images)
+        image_resize = self._image_resize(image_resize)
         jpeg_encoder = self._jpeg_encoder(jpeg_encoder)
         if jpeg_encoder == "native" and output_type == "jpeg" and self.ae is not None:
             up = self.upscaler.scale if upscale else 1
@@ -1209,7 +1278,8 @@ class FluxPipeline:
                 txt = torch.cat((txt, txt.new_zeros(txt.shape[0], n_tok, txt.shape[2])), dim=-2)
                 txt_ids = txt_ids.new_zeros(txt.shape[0], txt.shape[1], 3)
             else:
-                txt, txt_ids = self.prepare_redux_tokens(redux_image, num_images=num_images, txt=txt)
+                txt, txt_ids = self.prepare_redux_tokens(redux_image, num_images=num_images, txt=txt,
+                                                         **({} if image_resize == "pil" else dict(image_resize=image_resize)))
             txt, txt_ids = txt.contiguous(), txt_ids.contiguous()
             if guided:  # the same image tokens behind the negative prompt's T5 tokens
                 neg_txt = torch.cat((neg_txt, txt[:, neg_txt.shape[1]:]), dim=-2).contiguous()
@@ -1227,9 +1297,12 @@ class FluxPipeline:
             if guided:  # the same rows in the negative branch, where the table hides them from every other token
                 neg_txt = torch.cat((neg_txt, rows), 1).contiguous()
         cond = {}
+        # a request on Pillow makes the calls it always made; "native" names itself and keeps a control map where it was made
+        rs_kw = {} if image_resize == "pil" else dict(image_resize=image_resize)
+        dev_kw = {} if image_resize == "pil" else dict(on_device=True)
         if reference_image is not None:
             # drawn from the request's generator after the noise (the order is part of what a seed reproduces)
-            c_seq, c_ids = self.prepare_kontext_reference(reference_image, num_images=num_images, generator=generator)
+            c_seq, c_ids = self.prepare_kontext_reference(reference_image, num_images=num_images, generator=generator, **rs_kw)
             cond = dict(img_cond_seq=c_seq, img_cond_seq_ids=c_ids)
         if kind is not None:
             # drawn from the request's generator after the noise, like a Kontext reference
@@ -1237,8 +1310,8 @@ class FluxPipeline:
                 img_cond = self.prepare_fill_conditioning(fill_image, mask_image, height, width, num_images=1, generator=generator)
             elif img_cond is None:
                 if control_preprocess is not None:
-                    control_image = self.preprocess_control(control_image, control_preprocess, width, height, **prep_kw)
-                img_cond = self.prepare_control_conditioning(control_image, height, width, num_images=1, generator=generator)
+                    control_image = self.preprocess_control(control_image, control_preprocess, width, height, **prep_kw, **rs_kw, **dev_kw)
+                img_cond = self.prepare_control_conditioning(control_image, height, width, num_images=1, generator=generator, **rs_kw)
             img_cond = img_cond.to(device=self.device_flux, dtype=torch.bfloat16)
             if img_cond.shape[0] == 1 and num_images > 1:
                 img_cond = img_cond.repeat(num_images, 1, 1)
@@ -1248,8 +1321,10 @@ class FluxPipeline:
             # drawn from the request's generator after the noise, like a Kontext reference
             if controlnet_cond is None:
                 if control_preprocess is not None:
-                    controlnet_image = self.preprocess_control(controlnet_image, control_preprocess, width, height, **prep_kw)
-                controlnet_cond = self.prepare_controlnet_conditioning(controlnet_image, height, width, num_images=1, generator=generator)
+                    controlnet_image = self.preprocess_control(controlnet_image, control_preprocess, width, height, **prep_kw, **rs_kw,
+                                                               **dev_kw)
+                controlnet_cond = self.prepare_controlnet_conditioning(controlnet_image, height, width, num_images=1, generator=generator,
+                                                                       **rs_kw)
             cn_cond = controlnet_cond.to(device=self.device_flux, dtype=torch.bfloat16)
             if cn_cond.ndim != 3 or cn_cond.shape[0] not in (1, num_images) or tuple(cn_cond.shape[1:]) != tuple(img.shape[1:]):
                 raise ValueError(f"fluxmi: controlnet_cond {tuple(cn_cond.shape)}: expected [1 or {num_images}, {img.shape[1]}, {img.shape[2]}]")
@@ -1257,7 +1332,8 @@ class FluxPipeline:
         ip_calls = None
         if ip_on:
             ip_calls = self.prepare_ip_adapter(ip_adapter_image, ip_adapter_image_embeds, ip_scales[0],
-                                               negative_ip_adapter_image if guided else None, ip_scales[1], guided)
+                                               negative_ip_adapter_image if guided else None, ip_scales[1], guided,
+                                               **({} if image_resize == "pil" else dict(image_resize=image_resize)))
         first_image = 0  # the request's index of this rank's first image (the noise ids of a stochastic sampler count from it)
         if world > 1:
             if guided:  # the negative embeddings ride in the one broadcast, behind the prompt's

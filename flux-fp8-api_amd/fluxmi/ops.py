@@ -1153,6 +1153,81 @@ def jpeg_encode(px: torch.Tensor, quality: int = 99, subsampling: str = "4:2:0",
     return host.numpy().tobytes()
 
 
+# ---- image resampler (csrc/resample.hip, csrc/resample_host.cpp; include/fluxmi.h has the definition: Pillow's 8-bit resize) -------------
+RESAMPLE_FILTERS = {"box": 0, "bilinear": 1, "hamming": 2, "bicubic": 3, "lanczos": 4}  # FLUXMI_RESAMPLE_BOX .. FLUXMI_RESAMPLE_LANCZOS
+RESAMPLE_TILE_BYTES = 256        # FLUXMI_RESAMPLE_TILE_BYTES: output bytes (pixels x channels) of one workgroup's tile
+RESAMPLE_TILE_ROWS = 16          # FLUXMI_RESAMPLE_TILE_ROWS
+RESAMPLE_LDS_IN_BYTES = 16384    # FLUXMI_RESAMPLE_LDS_IN_BYTES: the stage of input rows
+RESAMPLE_LDS_MID_BYTES = 32768   # FLUXMI_RESAMPLE_LDS_MID_BYTES: the uint8 intermediate; more input rows under one tile than
+#                                  LDS_MID_BYTES / TILE_BYTES = 128 and the resize runs as two launches through a workspace
+_resample_tables: dict = {}
+
+
+def resample_filter(filter) -> int:
+    """the FLUXMI_RESAMPLE_* code of a filter name; anything else -- "nearest" (a different routine in Pillow) included -- is refused by name"""
+    if not isinstance(filter, str) or filter not in RESAMPLE_FILTERS:
+        raise ValueError(f"resize_u8: filter={filter!r}: expected one of {tuple(RESAMPLE_FILTERS)} (\"nearest\" is not provided)")
+    return RESAMPLE_FILTERS[filter]
+
+
+def resample_coeffs(n_in: int, n_out: int, filter: str):
+    """one axis of Pillow's resampler on the host (fluxmi_resample_coeffs; needs no GPU) -> (bounds int32 [n_out, 2] of (xmin, n),
+    kk int32 [n_out, ksize], zero-padded)"""
+    f = resample_filter(filter)
+    ksize = C.c_int(0)
+    call("fluxmi_resample_ksize", int(n_in), int(n_out), f, C.byref(ksize))
+    bounds = torch.empty(n_out, 2, dtype=torch.int32)
+    kk = torch.empty(n_out, ksize.value, dtype=torch.int32)
+    call("fluxmi_resample_coeffs", int(n_in), int(n_out), f, _p(bounds), _p(kk))
+    return bounds, kk
+
+
+def resample_plan(B: int, H: int, W: int, channels: int, h: int, w: int, filter: str):
+    """(fused, workspace bytes) of a resize (fluxmi_resample_plan; needs no GPU): fused = one launch runs both passes; the workspace is
+    needed only when both axes change and a tile's intermediate does not fit RESAMPLE_LDS_MID_BYTES"""
+    fused, nbytes = C.c_int(0), C.c_longlong(0)
+    call("fluxmi_resample_plan", B, H, W, channels, h, w, resample_filter(filter), C.byref(fused), C.byref(nbytes))
+    return bool(fused.value), nbytes.value
+
+
+def _resample_device_tables(n_in: int, n_out: int, filter: str, device):
+    key = (n_in, n_out, filter, str(device))
+    if key not in _resample_tables:
+        if len(_resample_tables) >= 64:  # a server sees few sizes; an adversarial stream of them must not grow this without bound
+            _resample_tables.pop(next(iter(_resample_tables)))
+        _resample_tables[key] = tuple(t.to(device) for t in resample_coeffs(n_in, n_out, filter))
+    return _resample_tables[key]
+
+
+def resize_u8(px: torch.Tensor, size, filter: str = "lanczos", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """px uint8 [B, H, W, 3] or [B, H, W] on the device -> [B, h, w, 3] / [B, h, w] for size = (w, h): PIL.Image.resize(size, filter) of every
+    image, byte for byte (fluxmi_resample_u8; include/fluxmi.h is the definition: integer taps, a uint8 image between the horizontal and the
+    vertical pass).  Any row / image stride, as _u8_image takes them.  The coefficient tables come from the host once per (in, out, filter)
+    and stay on the device; a workspace is allocated only when the resize runs as two launches (resample_plan)."""
+    f = resample_filter(filter)
+    ch = 1 if px.ndim == 3 else px.shape[-1] if px.ndim == 4 else 0
+    if ch not in (1, 3):
+        raise ValueError(f"resize_u8: px {tuple(px.shape)}: expected uint8 [B, H, W, 3] or [B, H, W] (a 4-channel image is not provided: Pillow "
+                         "premultiplies its alpha)")
+    try:
+        w, h = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise ValueError(f"resize_u8: size={size!r}: expected (width, height)") from None
+    if w < 1 or h < 1:
+        raise ValueError(f"resize_u8: size={size!r}: width and height must be >= 1")
+    B, H, W, ld, bs = _u8_image(px, "resize_u8", "px", ch)
+    out, old, obs = _u8_out(out, (B, h, w) if px.ndim == 3 else (B, h, w, ch), px, "resize_u8", "out", ch)
+    _, nwork = resample_plan(B, H, W, ch, h, w, filter)
+    work = torch.empty(nwork, dtype=torch.uint8, device=px.device) if nwork else None
+    bx, kx = _resample_device_tables(W, w, filter, px.device) if w != W else (None, None)
+    by, ky = _resample_device_tables(H, h, filter, px.device) if h != H else (None, None)
+    for t in (bx, kx, by, ky):  # a cached table may be evicted while this stream's launch still reads it: the allocator must wait for it
+        if t is not None:
+            t.record_stream(torch.cuda.current_stream())
+    call("fluxmi_resample_u8", _p(px), ld, bs, _p(out), old, obs, _p(work), nwork, B, H, W, ch, h, w, f, _p(bx), _p(kx), _p(by), _p(ky), _stream())
+    return out
+
+
 # ---- depth estimator pieces (csrc/depth.hip; NHWC bf16 maps behind one pixel stride) ------------------------------------------------------
 UNARY_KINDS = {"gelu": 0, "relu": 1}            # FLUXMI_UNARY_GELU_ERF / FLUXMI_UNARY_RELU
 DEPTH_NORMALIZE = {"minmax": 0, "raw": 1}       # FLUXMI_DEPTH_MINMAX / FLUXMI_DEPTH_RAW

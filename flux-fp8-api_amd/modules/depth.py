@@ -433,6 +433,15 @@ class DepthAnythingNative(nn.Module):
         depth_input_size, x / 255, ImageNet mean / std.  `image`: anything to_pil takes."""
         from PIL import Image
 
+        if isinstance(image, torch.Tensor) and image.is_cuda:
+            # uint8 [H, W, 3] already on a device (the pipeline's image_resize="native"): the bicubic resize runs there too
+            # (fluxmi.ops.resize_u8: the bytes PIL gives); the small result is normalised on the host like a PIL image's, bit for bit
+            from fluxmi import ops
+
+            size = depth_input_size(image.shape[1], image.shape[0], resolution)
+            with torch.cuda.device(image.device):
+                px = ops.resize_u8(image[None], size, "bicubic")[0] if size != (image.shape[1], image.shape[0]) else image
+            return normalize_image(px.cpu().numpy(), IMAGENET_MEAN, IMAGENET_STD)
         pil = to_pil(image).convert("RGB")
         size = depth_input_size(pil.width, pil.height, resolution)
         if size != pil.size:
@@ -445,8 +454,9 @@ class DepthAnythingNative(nn.Module):
         take): preprocess, the model, fluxmi_depth_to_map to size = (H, W) (default: the photo's own)."""
         from fluxmi import ops
 
-        pil = to_pil(image)
-        H, W = (pil.height, pil.width) if size is None else (int(size[0]), int(size[1]))
+        pil = image if isinstance(image, torch.Tensor) and image.is_cuda else to_pil(image)
+        own = (pil.shape[0], pil.shape[1]) if isinstance(pil, torch.Tensor) else (pil.height, pil.width)
+        H, W = own if size is None else (int(size[0]), int(size[1]))
         depth = self(self.preprocess(pil, resolution).to(self.device))
         return ops.depth_to_map(depth, (H, W), normalize)[0]
 

@@ -151,6 +151,20 @@ class SiglipVisionNative(nn.Module):
 
 
 # ---- FLUX.1 Redux ------------------------------------------------------------------------------------------------------------------
+def resize_rgb_u8(pil, size, filter: str, device=None) -> np.ndarray:
+    """a PIL RGB image -> uint8 [h, w, 3] on the host at size = (w, h).  device None: PIL's Image.resize.  A device: the image is uploaded at
+    its own size and resized there (fluxmi.ops.resize_u8: Pillow's integer resampler, the same bytes); the small result comes back to be
+    normalised on the host exactly as before, so the pixel values a tower sees do not depend on who resized."""
+    from PIL import Image
+
+    if device is None:
+        return np.asarray(pil.resize(size, resample={"bicubic": Image.BICUBIC, "lanczos": Image.LANCZOS}[filter]))
+    from fluxmi import ops
+
+    with torch.cuda.device(device):
+        return ops.resize_u8(torch.from_numpy(np.array(pil)).to(device)[None], size, filter)[0].cpu().numpy()
+
+
 def to_pil(image):
     """str (path, or base64 / data-URL) | PIL.Image | np.ndarray (uint8 HW / HWC) | torch.Tensor (uint8 HW / HWC) -> PIL.Image"""
     from base64 import standard_b64decode
@@ -208,13 +222,12 @@ class ReduxImageEncoder(nn.Module):
     def num_tokens(self) -> int:
         return self.siglip.num_tokens
 
-    def preprocess(self, image) -> Tensor:
+    def preprocess(self, image, resize_device=None) -> Tensor:
         """step 1 of the module docstring -> fp32 [1, 3, S, S] on the host (S = 384), bit-identical to transformers'
-        SiglipImageProcessor(size={"height": S, "width": S}).  `image`: anything to_pil takes."""
-        from PIL import Image
-
-        pil = to_pil(image).convert("RGB").resize((self.image_size, self.image_size), resample=Image.BICUBIC)
-        return normalize_image(np.asarray(pil), np.float32(0.5), np.float32(0.5))
+        SiglipImageProcessor(size={"height": S, "width": S}).  `image`: anything to_pil takes.  `resize_device`: run the bicubic resize there
+        (resize_rgb_u8: the same bytes) instead of in Pillow."""
+        px = resize_rgb_u8(to_pil(image).convert("RGB"), (self.image_size, self.image_size), "bicubic", resize_device)
+        return normalize_image(px, np.float32(0.5), np.float32(0.5))
 
     @torch.inference_mode()
     def project(self, hidden: Tensor) -> Tensor:
@@ -229,11 +242,12 @@ class ReduxImageEncoder(nn.Module):
         return ops.linear(up, wd, bd).view(n, T, -1)
 
     @torch.inference_mode()
-    def __call__(self, images) -> Tensor:
-        """one image or a list -> Redux tokens bf16 [n, 729, 4096] on the encoder's device, in list order"""
+    def __call__(self, images, image_resize: str = "pil") -> Tensor:
+        """one image or a list -> Redux tokens bf16 [n, 729, 4096] on the encoder's device, in list order; image_resize "native": the
+        bicubic resize runs on that device"""
         if not isinstance(images, (list, tuple)):
             images = [images]
-        pix = torch.cat([self.preprocess(im) for im in images], 0).to(self.device)
+        pix = torch.cat([self.preprocess(im, self.device if image_resize == "native" else None) for im in images], 0).to(self.device)
         return self.project(self.siglip(pix)["last_hidden_state"])
 
 

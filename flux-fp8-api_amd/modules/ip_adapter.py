@@ -62,20 +62,18 @@ def scale_table(scale, depth: int, batch: int) -> Tensor:
     return t.contiguous()
 
 
-def clip_preprocess(image, size: int = 224) -> Tensor:
+def clip_preprocess(image, size: int = 224, resize_device=None) -> Tensor:
     """transformers' CLIPImageProcessor defaults -> fp32 [1, 3, size, size] on the host, bit for bit: RGB, PIL bicubic resize of the SHORT edge
-    to `size` (the long edge int(size * long / short)), centre crop, x * (1 / 255) in float64 then float32, (x - mean) / std in float32."""
-    from PIL import Image
-
-    from modules.image_embedders import normalize_image, to_pil
+    to `size` (the long edge int(size * long / short)), centre crop, x * (1 / 255) in float64 then float32, (x - mean) / std in float32.
+    `resize_device`: run the bicubic resize there (image_embedders.resize_rgb_u8: the same bytes) instead of in Pillow."""
+    from modules.image_embedders import normalize_image, resize_rgb_u8, to_pil
 
     pil = to_pil(image).convert("RGB")
     w, h = pil.size
     short, long = (w, h) if w <= h else (h, w)
     new_short, new_long = size, int(size * long / short)
     nw, nh = (new_short, new_long) if w <= h else (new_long, new_short)
-    pil = pil.resize((nw, nh), resample=Image.BICUBIC)
-    a = np.asarray(pil)
+    a = resize_rgb_u8(pil, (nw, nh), "bicubic", resize_device)
     top, left = (nh - size) // 2, (nw - size) // 2
     return normalize_image(a[top:top + size, left:left + size], CLIP_MEAN, CLIP_STD)
 
@@ -195,13 +193,15 @@ class IPAdapter(nn.Module):
         return k, v
 
     @torch.inference_mode()
-    def embed(self, images) -> Tensor:
-        """step 1: one image or a list -> image_embeds bf16 [n, 768] through the CLIP vision tower"""
+    def embed(self, images, image_resize: str = "pil") -> Tensor:
+        """step 1: one image or a list -> image_embeds bf16 [n, 768] through the CLIP vision tower; image_resize "native": the bicubic
+        resize runs on the tower's device"""
         if self.clip is None:
             raise RuntimeError("fluxmi: this IP-Adapter was loaded without a CLIP vision tower (clip_vision_path): pass ip_adapter_image_embeds")
         if not isinstance(images, (list, tuple)):
             images = [images]
-        pix = torch.cat([clip_preprocess(im, self.clip.cfg["image_size"]) for im in images], 0).to(self.device)
+        dev = self.device if image_resize == "native" else None
+        pix = torch.cat([clip_preprocess(im, self.clip.cfg["image_size"], dev) for im in images], 0).to(self.device)
         return self.clip(pix)["image_embeds"]
 
     def call(self, images=None, image_embeds: Optional[Tensor] = None, scale=1.0) -> IPAdapterCall:

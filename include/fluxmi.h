@@ -553,6 +553,56 @@ int fluxmi_jpeg_encode(const void* rgb, long long ld, long long bs, int B, int H
 int fluxmi_jpeg_finish(const void* n_bytes_dev, long long out_cap, long long* n_bytes, void* stream);
 int fluxmi_jpeg_header(int B, int H, int W, int quality, int subsampling, int restart, void* buf, long long cap, long long* n_bytes);
 
+/* ---- image resampler (csrc/resample.hip, csrc/resample_host.cpp): Pillow's resize of an 8-bit image, byte for byte ----------------------
+ * uint8 [B][H][W][C] -> [B][h][w][C], C in {1, 3}, rows and images behind byte strides as for the preprocessors above.  The definition is
+ * Pillow's ImagingResample at 8 bits per channel (Image.resize of an "L" / "RGB" image, no box=, no reducing_gap=), restated here and in
+ * tests/resize_ref.py; tests/test_resize_cpu.py pins the restatement to Pillow 12.2.0, the only version compared.  Once the coefficient
+ * tables exist everything is integer arithmetic.
+ *   Coefficients of one axis, `in` samples -> `out`, filter f of support s; all in double, int() truncates toward zero:
+ *     scale = in / out;  fs = max(scale, 1);  support = s fs;  ksize = 2 ceil(support) + 1;  ss = 1 / fs
+ *     for each output index xx:  center = (xx + 0.5) scale
+ *       xmin = max(int(center - support + 0.5), 0);  xmax = min(int(center + support + 0.5), in);  n = xmax - xmin
+ *       w[x] = f((x + xmin - center + 0.5) ss) for x < n  (the division by fs IS this product with the rounded reciprocal, as Pillow has it)
+ *       ww = w[0] + w[1] + ... in ascending x;  w[x] = w[x] / ww unless ww == 0
+ *       k[x] = int(w[x] 2^22 + 0.5) for w[x] >= 0, int(w[x] 2^22 - 0.5) below;  k[x] = 0 for n <= x < ksize
+ *   Filters (x is |x| where the formula is even; sinc(0) = 1, sinc(x) = sin(pi x) / (pi x) with the product pi x rounded once):
+ *     BOX       1 on -0.5 < x <= 0.5                                                      support 0.5
+ *     BILINEAR  1 - x on x < 1                                                            support 1
+ *     HAMMING   sinc(x) (0.54f + 0.46f cos(pi x)) on x < 1, the two constants in fp32     support 1
+ *     BICUBIC   ((a + 2) x - (a + 3)) x x + 1 on x < 1, (((x - 5) x + 8) x - 4) a on x < 2, a = -0.5      support 2
+ *     LANCZOS   sinc(x) sinc(x / 3) on -3 <= x < 3                                        support 3
+ *   A pass:  out = clip(((1 << 21) + sum_x px[xmin + x] k[x]) >> 22, 0, 255), int32 accumulation, arithmetic shift.
+ *   A resize: the horizontal pass when w != W, then the vertical pass when h != H, every channel on its own; the image between the two
+ *     passes is uint8.  Equal sizes on both axes copy the image.
+ * fluxmi_resample_ksize / fluxmi_resample_coeffs: host only, no GPU: one axis' ksize; bounds[out][2] = (xmin, n) and kk[out][ksize].
+ * fluxmi_resample_plan: host only: *fused = 1 when one launch runs both passes, *work_bytes = the size of `work` (0 when none is needed).
+ * fluxmi_resample_u8: asynchronous.  bounds_x / kk_x and bounds_y / kk_y are DEVICE copies of fluxmi_resample_coeffs(W, w, filter) and
+ *   (H, h, filter); the tables of an axis whose size does not change may be NULL.  One kernel, three instantiations: a workgroup owns
+ *   FLUXMI_RESAMPLE_TILE_BYTES output bytes (pixels x channels) of FLUXMI_RESAMPLE_TILE_ROWS output rows; it stages the input rows its
+ *   vertical taps touch, cut to the columns its horizontal taps touch, through a FLUXMI_RESAMPLE_LDS_IN_BYTES buffer of LDS in 4-byte
+ *   loads, runs the horizontal pass into a uint8 intermediate in LDS (Pillow's temporary image restricted to this tile), then the vertical
+ *   pass from it, and stores 4 bytes per lane.  When a tile's intermediate would exceed FLUXMI_RESAMPLE_LDS_MID_BYTES (more than
+ *   LDS_MID_BYTES / TILE_BYTES input rows under one tile: a vertical reduction beyond about 5x with LANCZOS) the horizontal-only
+ *   instantiation writes `work` ([B][H][w C rounded up to 4], 16-byte aligned) and the vertical-only one reads it; a resize that changes one
+ *   axis is that axis' instantiation alone.  A horizontal pass whose tile needs more than LDS_IN_BYTES of one input row (a reduction beyond
+ *   about 60x with LANCZOS: the span is (tile pixels + 2 x support) x the reduction) is refused.  Out of scope and refused: NEAREST, 4-channel images, 16-bit and float samples.  dst must not overlap src. */
+#define FLUXMI_RESAMPLE_BOX 0
+#define FLUXMI_RESAMPLE_BILINEAR 1
+#define FLUXMI_RESAMPLE_HAMMING 2
+#define FLUXMI_RESAMPLE_BICUBIC 3
+#define FLUXMI_RESAMPLE_LANCZOS 4
+#define FLUXMI_RESAMPLE_PRECISION_BITS 22
+#define FLUXMI_RESAMPLE_TILE_BYTES 256
+#define FLUXMI_RESAMPLE_TILE_ROWS 16
+#define FLUXMI_RESAMPLE_LDS_IN_BYTES 16384
+#define FLUXMI_RESAMPLE_LDS_MID_BYTES 32768
+int fluxmi_resample_ksize(int n_in, int n_out, int filter, int* ksize);
+int fluxmi_resample_coeffs(int n_in, int n_out, int filter, int* bounds, int* kk);
+int fluxmi_resample_plan(int B, int H, int W, int C, int h, int w, int filter, int* fused, long long* work_bytes);
+int fluxmi_resample_u8(const void* src, long long ld, long long bs, void* dst, long long dst_ld, long long dst_bs, void* work,
+                       long long work_bytes, int B, int H, int W, int C, int h, int w, int filter, const int* bounds_x, const int* kk_x,
+                       const int* bounds_y, const int* kk_y, void* stream);
+
 /* ---- depth estimator pieces (csrc/depth.hip; modules/depth.py: Depth Anything = a DINOv2 tower + a DPT decoder) -----------------------
  * The tower runs on the vision-encoder entry points above, the decoder's stride-1 convolutions on fluxmi_conv3x3 / fluxmi_conv3x3_dense; what
  * those do not cover is here.  Maps are NHWC bf16: [B][H][W] pixels addressed densely with ONE pixel stride `ld` in elements (ld >= C,

@@ -44,7 +44,7 @@ Same two POST endpoints, request fields, defaults and status codes:
              With stream=true the response is application/x-ndjson instead, one JSON object per line: for every model evaluation
                {"event": "progress", "evaluation", "num_evaluations", "step", "preview": <base64 JPEG at latent resolution, or null>}
              (a preview at every preview_every-th evaluation; none with preview_every unset or 0), then ONE final line
-               {"event": "result", "image": <base64 JPEG>}  |  {"event": "cancelled"}  |  {"event": "error", "message"}.
+               {"event": "result", "image": <base64 JPEG, or PNG for output_type="png">}  |  {"event": "cancelled"}  |  {"event": "error", "message"}.
              The request runs in a worker thread that feeds a queue; closing the response -- a client that disconnected -- sets a flag
              that the next on_step turns into a cancel, so an abandoned request frees its GPU within two model evaluations.
              preview_every without stream is a 422.
@@ -153,6 +153,10 @@ class GenerateArgs(BaseModel):
     # who writes the response's JPEG: "pil" (Pillow on the host) or "native" (the device encoder, fluxmi.ops.jpeg_encode: the pixels never
     # leave the device uncompressed); unset = the configuration's jpeg_encoder ("pil" unless set there).  Previews stay on Pillow
     jpeg_encoder: Optional[Literal["pil", "native"]] = None
+    # "png": a lossless PNG answered as image/png instead of the JPEG (FluxPipeline.generate); unset = the JPEG, as ever.  png_encoder: who
+    # writes it, "native" (the device encoder, fluxmi.ops.png_encode) or "pil" (Pillow on the host); unset = the configuration's ("native")
+    output_type: Optional[Literal["jpeg", "png"]] = None
+    png_encoder: Optional[Literal["native", "pil"]] = None
     # who resizes the request's images (Kontext reference, control / ControlNet image, the photo of control_preprocess): "pil" (Pillow on the
     # host) or "native" (fluxmi.ops.resize_u8 on the device: the same bytes); unset = the configuration's image_resize ("pil" unless set there)
     image_resize: Optional[Literal["pil", "native"]] = None
@@ -239,7 +243,7 @@ def generate(args: GenerateArgs):
               "negative_ip_adapter_image", "negative_ip_adapter_scale", "guidance_mode", "guidance_rescale", "apg_eta", "apg_norm_threshold",
               "apg_momentum", "zero_init_steps", "source_prompt", "source_guidance", "edit_n_max", "edit_n_min", "edit_n_avg", "tile_size",
               "tile_overlap", "tile_weight", "control_preprocess", "canny_low", "canny_high", "canny_l2", "blur_sigma", "depth_resolution",
-              "depth_normalize", "jpeg_encoder", "image_resize"):
+              "depth_normalize", "jpeg_encoder", "image_resize", "output_type", "png_encoder"):
         if kwargs.get(k) is None:
             kwargs.pop(k, None)
     for k in ("upscale", "init_upscale"):  # passed on only when asked for
@@ -265,7 +269,7 @@ def generate(args: GenerateArgs):
     if stream:
         return StreamingResponse(stream_events(app.state.model, kwargs), media_type="application/x-ndjson")
     result = app.state.model.generate(**kwargs)
-    return StreamingResponse(result, media_type="image/jpeg")
+    return StreamingResponse(result, media_type="image/png" if kwargs.get("output_type") == "png" else "image/jpeg")
 
 
 @app.post("/lora", response_model=LoraLoadResponse)

@@ -271,6 +271,23 @@ struct FluxmiJpegPlan {
 int fluxmi_jpeg_plan(const char* who, int B, int H, int W, int quality, int subsampling, int restart, FluxmiJpegPlan* p);
 int fluxmi_k_jpeg_encode(const FluxmiJpegPlan& p, const void* rgb, long long ld, long long bs, void* work, void* out, long long out_cap,
                          void* n_bytes_dev, hipStream_t s);
+// the PNG encoder (include/fluxmi.h, fluxmi_png_*): the host's plan of one encode (png_host.cpp: the strip rule, the layout of `work`, the
+// bytes in front of the deflate blocks) and the launches that run it (png.hip)
+#define FLUXMI_PNG_HEAD_BYTES 43  // signature 8, IHDR 25, IDAT length + type 8, zlib header 2
+#define FLUXMI_PNG_TAIL_BYTES 20  // Adler-32 4, IDAT CRC 4, IEND 12
+struct FluxmiPngPlan {
+  int H, Hs, W, C, filter;     // image rows, stacked rows B * H, columns, channels (1 / 3), FLUXMI_PNG_FILTER_*
+  int row_bytes, rows;         // 1 + W * C, rows per strip (the strip rule)
+  int in_lds, lds_bytes;       // the strip's filtered bytes live in LDS (else in `work`), dynamic LDS of the strip kernel
+  long long n_strips;
+  long long res_stride;        // bytes between two strips' filtered bytes in `work` (0 when in_lds)
+  long long stride;            // bytes of one strip's slot: FLUXMI_PNG_STRIP_BOUND of a full strip, 16-byte aligned
+  long long off_sizes, off_offs, off_adler, off_meta, off_slots, off_res, work_bytes, out_cap;
+  unsigned char head[FLUXMI_PNG_HEAD_BYTES];  // the IDAT length left zero: the device knows it
+};
+int fluxmi_png_plan(const char* who, int B, int H, int W, int C, int filter, FluxmiPngPlan* p);
+int fluxmi_k_png_encode(const FluxmiPngPlan& p, const void* px, long long ld, long long bs, void* work, void* out, long long out_cap,
+                        void* n_bytes_dev, hipStream_t s);
 // the image resampler (include/fluxmi.h, fluxmi_resample_*): one axis' geometry and the plan of one resize (resample_host.cpp), and the
 // launches that run it (resample.hip)
 struct FluxmiResampleAxis {

@@ -36,6 +36,7 @@ from util import (ModelSpec, ModelVersion, engine_flow_dtype, into_device, into_
 MAX_RAND = 2**32 - 1
 CONTROL_PREPROCESSORS = ("canny", "gray", "blur", "depth_anything")  # generate(control_preprocess=...) / preprocess_control: the maps made from a photo
 IMAGE_RESIZERS = ("pil", "native")  # generate(image_resize=...) / ModelSpec.image_resize: Pillow on the host, or fluxmi.ops.resize_u8 on the device
+PNG_ENCODERS = ("native", "pil")   # generate(png_encoder=...) / ModelSpec.png_encoder: fluxmi.ops.png_encode on the device, or Pillow on the host
 JPEG_ENCODERS = ("pil", "native")  # generate(jpeg_encoder=...) / ModelSpec.jpeg_encoder: Pillow on the host, or fluxmi.ops.jpeg_encode on the device
 GUIDANCE_MODES = ("cfg", "apg", "cfg_zero_star")  # generate(guidance_mode=...): the rule that combines the two branches of true CFG
 
@@ -858,7 +859,8 @@ class FluxPipeline:
                  edit_n_max: Optional[int] = None, edit_n_min: int = 0, edit_n_avg: int = 1, tile_size=None, tile_overlap: Optional[int] = None,
                  tile_weight: str = "cosine", upscale: bool = False, init_upscale: bool = False, control_preprocess: Optional[str] = None,
                  canny_low: int = 100, canny_high: int = 200, canny_l2: bool = False, blur_sigma: float = 8.0, depth_resolution: int = 518,
-                 depth_normalize: str = "minmax", jpeg_encoder: Optional[str] = None, image_resize: Optional[str] = None):
+                 depth_normalize: str = "minmax", jpeg_encoder: Optional[str] = None, image_resize: Optional[str] = None,
+                 png_encoder: Optional[str] = None):
         """`reference_image` (FLUX.1 Kontext [dev] instruction editing): an image the prompt describes an edit of, in any form `init_image`
         takes; see prepare_kontext_reference.  Composes with `init_image` / `strength` unchanged.
         FLUX.1 Fill [dev] (a model with 320 conditioning channels): `init_image` is the image to inpaint and `mask_image` (white =
@@ -1027,7 +1029,13 @@ class FluxPipeline:
         every 4 MCUs: libjpeg's integer pipeline (include/fluxmi.h), so it decodes to the pixels Pillow's file decodes to; the bytes differ
         only by the restart markers -- and two copies come back, the length and that many bytes.  It serves the plain, the tiled and the
         FlowEdit request and into_bytes; with another output_type it is ignored.  Refused by name: an unknown encoder, and with "native" a
-        `jpeg_quality` outside 1..100 or an image beyond 65535 x 65535 (num_images stack vertically)."""
+        `jpeg_quality` outside 1..100 or an image beyond 65535 x 65535 (num_images stack vertically).
+        output_type="png" returns a lossless PNG (RGB, 8 bits, num_images stacked vertically) instead of the JPEG; it composes with
+        everything that returns pixels (tiled, FlowEdit, `upscale`).  `png_encoder` ("native" | "pil"; None = config.png_encoder, "native"
+        unless configured): "native" keeps the pixels on the device from the VAE (and the upscaler) to fluxmi.ops.png_encode
+        (include/fluxmi.h: adaptive filtering, one dynamic-Huffman deflate block per strip of rows, runs at distance 1); "pil" copies them
+        to the host for Pillow at compress_level=6.  Both decode to exactly the output_type="uint8" array.  With another output_type the
+        encoder is ignored; an unknown one is refused by name."""
         if control_preprocess is not None:
             if img_cond is not None or controlnet_cond is not None:
                 raise ValueError("fluxmi: control_preprocess works on an image: it does not combine with img_cond / controlnet_cond (maps that "
@@ -1047,20 +1055,29 @@ class FluxPipeline:
         if upscale or init_upscale:
             init_image = self._check_upscale(upscale, init_upscale, output_type, init_image, width, height, num_images)
         image_resize = self._image_resize(image_resize)
-        jpeg_encoder = self._jpeg_encoder(jpeg_encoder)
-        if jpeg_encoder == "native" and output_type == "jpeg" and self.ae is not None:
+        encoder = self._jpeg_encoder(jpeg_encoder)  # who writes the file this request returns, if it returns one
+        if output_type == "png":
+            encoder = self._png_encoder(png_encoder)
+            if encoder == "native" and self.ae is not None:
+                from fluxmi import ops
+
+                up = self.upscaler.scale if upscale else 1
+                ops.png_params(max(1, int(num_images)), up * 16 * (height // 16), up * 16 * (width // 16), 3)
+        elif png_encoder is not None:
+            self._png_encoder(png_encoder)
+        if encoder == "native" and output_type == "jpeg" and self.ae is not None:
             up = self.upscaler.scale if upscale else 1
             self._check_jpeg_native(num_images, up * 16 * (height // 16), up * 16 * (width // 16), jpeg_quality)
         tiles = self._check_tiles(locals())
         if tiles is not None:
             return self._generate_tiled(tiles, prompt, width, height, num_steps, guidance, seed, init_image, strength, num_images, return_seed,
                                         jpeg_quality, output_type, noise, use_graph, negative_prompt, true_cfg_scale, true_cfg_interval,
-                                        sigma_schedule, sigmas, on_step, upscale=upscale, jpeg_encoder=jpeg_encoder)
+                                        sigma_schedule, sigmas, on_step, upscale=upscale, encoder=encoder)
         edit = self._check_edit(locals())
         if edit is not None:
             return self._generate_edit(edit, prompt, source_prompt, width, height, num_steps, guidance, seed, init_image, silent, num_images,
                                        return_seed, jpeg_quality, output_type, use_graph, sigma_schedule, sigmas, noise_seed, on_step,
-                                       upscale=upscale, jpeg_encoder=jpeg_encoder)
+                                       upscale=upscale, encoder=encoder)
         if isinstance(preview_every, bool) or not isinstance(preview_every, int) or preview_every < 0:
             raise ValueError(f"fluxmi: preview_every={preview_every!r}: expected an integer >= 0 (0 = no previews)")
         if on_step is not None and not callable(on_step):
@@ -1435,7 +1452,7 @@ class FluxPipeline:
             return (out, seed) if return_seed else out
         img_px = self.vae_decode(latents, height, width)
         # output_type "uint8": the [B, H, W, 3] array into_bytes hands to the JPEG encoder (the pixel-parity tests compare it)
-        out = self._pixels_out(img_px, output_type, jpeg_quality, upscale, jpeg_encoder)
+        out = self._pixels_out(img_px, output_type, jpeg_quality, upscale, encoder)
         return (out, seed) if return_seed else out
 
     # ---- tiled generation (fluxmi.windows; Flux.denoise_windows) -------------------------------------------------------------------------------
@@ -1543,7 +1560,7 @@ class FluxPipeline:
 
     def _generate_tiled(self, plan, prompt, width, height, num_steps, guidance, seed, init_image, strength, num_images, return_seed, jpeg_quality,
                         output_type, noise, use_graph, negative_prompt, true_cfg_scale, true_cfg_interval, sigma_schedule, sigmas, on_step,
-                        upscale=False, jpeg_encoder="pil"):
+                        upscale=False, encoder="pil"):
         """the tiled request of generate (its docstring): today's noise / img2img / text at canvas size, then Flux.denoise_windows on the
         canvas -- one call, or up to three where true_cfg_interval cuts the request"""
         from modules.flux_model import Flux, PreviewCall
@@ -1588,7 +1605,7 @@ class FluxPipeline:
             out = self.unpack(latents.float(), height, width)
             return (out, seed) if return_seed else out
         img_px = self.vae_decode(latents, height, width)
-        out = self._pixels_out(img_px, output_type, jpeg_quality, upscale, jpeg_encoder)
+        out = self._pixels_out(img_px, output_type, jpeg_quality, upscale, encoder)
         return (out, seed) if return_seed else out
 
     # ---- FlowEdit (fluxmi.flowedit; Flux.denoise_edit) ---------------------------------------------------------------------------------------
@@ -1677,7 +1694,7 @@ class FluxPipeline:
 
     def _generate_edit(self, edit, prompt, source_prompt, width, height, num_steps, guidance, seed, init_image, silent, num_images, return_seed,
                        jpeg_quality, output_type, use_graph, sigma_schedule, sigmas, noise_seed, on_step, upscale=False,
-                       jpeg_encoder="pil"):
+                       encoder="pil"):
         """the FlowEdit request of generate (its docstring): skipped steps | coupled steps (Flux.denoise_edit) | Euler tail (Flux.denoise)"""
         from fluxmi import flowedit, ops
         from modules.flux_model import PreviewCall
@@ -1726,7 +1743,7 @@ class FluxPipeline:
             out = self.unpack(latents.float(), height, width)
             return (out, seed) if return_seed else out
         img_px = self.vae_decode(latents, height, width)
-        out = self._pixels_out(img_px, output_type, jpeg_quality, upscale, jpeg_encoder)
+        out = self._pixels_out(img_px, output_type, jpeg_quality, upscale, encoder)
         return (out, seed) if return_seed else out
 
     def _preview_call(self, on_step, proj, every: int, height: int, width: int, step0: int, eval_offset: int, n_evaluations: int, solver):
@@ -1782,7 +1799,12 @@ class FluxPipeline:
         """to_uint8's arithmetic without the copy to the host: [B, 3, H, W] in [-1, 1] -> [B, H, W, 3] uint8 where x lives"""
         return x.clamp(-1, 1).add(1.0).mul(127.5).clamp(0, 255).permute(0, 2, 3, 1).contiguous().to(torch.uint8)
 
-    def into_bytes(self, x: torch.Tensor, jpeg_quality: int = 99, jpeg_encoder: Optional[str] = None) -> io.BytesIO:
+    def into_bytes(self, x: torch.Tensor, jpeg_quality: int = 99, jpeg_encoder: Optional[str] = None, output_type: str = "jpeg",
+                   png_encoder: Optional[str] = None) -> io.BytesIO:
+        if output_type == "png":
+            if self._png_encoder(png_encoder) == "native":
+                return self._png_native(self.to_uint8_device(x))
+            return self._png(self.to_uint8(x))
         if self._jpeg_encoder(jpeg_encoder) == "native":
             return self._jpeg_native(self.to_uint8_device(x), jpeg_quality)
         return self._jpeg(self.to_uint8(x), jpeg_quality)
@@ -1794,6 +1816,33 @@ class FluxPipeline:
         if enc not in JPEG_ENCODERS:
             raise ValueError(f"fluxmi: jpeg_encoder={enc!r}: expected one of {JPEG_ENCODERS}")
         return enc
+
+    def _png_encoder(self, png_encoder: Optional[str]) -> str:
+        """the request's PNG encoder: its own `png_encoder`, else the configuration's (ModelSpec.png_encoder, "native" when absent)"""
+        enc = png_encoder if png_encoder is not None else getattr(getattr(self, "config", None), "png_encoder", "native")
+        if enc not in PNG_ENCODERS:
+            raise ValueError(f"fluxmi: png_encoder={enc!r}: expected one of {PNG_ENCODERS}")
+        return enc
+
+    @staticmethod
+    def _png_native(px: torch.Tensor) -> io.BytesIO:
+        """_png on the device (fluxmi.ops.png_encode): uint8 [B, H, W, 3] where the VAE left it -> the file, the batch stacked vertically"""
+        from fluxmi import ops
+
+        with torch.cuda.device(px.device):  # the encoder launches on the current stream: make it the pixels' device's
+            buf = io.BytesIO(ops.png_encode(px))
+        buf.seek(0)
+        return buf
+
+    @staticmethod
+    def _png(px: torch.Tensor) -> io.BytesIO:
+        from PIL import Image
+
+        imgs = [px[i].numpy() for i in range(px.shape[0])]
+        buf = io.BytesIO()
+        Image.fromarray(imgs[0] if len(imgs) == 1 else np.vstack(imgs)).save(buf, format="PNG", compress_level=6)
+        buf.seek(0)
+        return buf
 
     @staticmethod
     def _check_jpeg_native(num_images: int, height: int, width: int, jpeg_quality):
@@ -1850,17 +1899,20 @@ class FluxPipeline:
             init_image = self.upscale(init_image)[0]
         return init_image
 
-    def _pixels_out(self, img_px: torch.Tensor, output_type: str, jpeg_quality: int, upscale: bool = False, jpeg_encoder: str = "pil"):
-        """decoded pixels -> what the request returns: the uint8 array or its JPEG, through the upscaler first when asked.  jpeg_encoder
-        "native" (an encoder name already checked; ignored unless a JPEG is returned): the pixels stay on the device up to the encoder."""
-        if jpeg_encoder == "native" and output_type == "jpeg":
+    def _pixels_out(self, img_px: torch.Tensor, output_type: str, jpeg_quality: int, upscale: bool = False, encoder: str = "pil"):
+        """decoded pixels -> what the request returns: the uint8 array or its JPEG, through the upscaler first when asked.  `encoder`
+        "native" (an encoder name already checked; ignored unless a file is returned): the pixels stay on the device up to the encoder.
+        It names the PNG encoder for output_type "png" and the JPEG encoder otherwise (generate resolves it)."""
+        if encoder == "native" and output_type in ("jpeg", "png"):
             px = self.to_uint8_device(img_px)
             if upscale:
                 px = self._require_upscaler().upscale_uint8_device(px)
-            return self._jpeg_native(px, jpeg_quality)
+            return self._png_native(px) if output_type == "png" else self._jpeg_native(px, jpeg_quality)
         px = self.to_uint8(img_px)
         if upscale:
             px = self.upscale(px)
+        if output_type == "png":
+            return self._png(px)
         return px if output_type == "uint8" else self._jpeg(px, jpeg_quality)
 
     @staticmethod

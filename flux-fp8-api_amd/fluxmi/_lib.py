@@ -177,6 +177,11 @@ _SIGS = {
     "fluxmi_jpeg_encode": ([vp, i64, i64, i32, i32, i32, i32, i32, i32, vp, vp, i64, vp, vp], i32),
     "fluxmi_jpeg_finish": ([vp, i64, C.POINTER(i64), vp], i32),
     "fluxmi_jpeg_header": ([i32, i32, i32, i32, i32, i32, vp, i64, C.POINTER(i64)], i32),
+    "fluxmi_png_workspace_bytes": ([i32, i32, i32, i32, C.POINTER(i64), C.POINTER(i64)], i32),
+    "fluxmi_png_encode": ([vp, i64, i64, i32, i32, i32, i32, i32, vp, i64, vp, i64, vp, vp], i32),
+    "fluxmi_png_finish": ([vp, i64, C.POINTER(i64), vp], i32),
+    "fluxmi_png_header": ([i32, i32, i32, i32, vp, i64, C.POINTER(i64)], i32),
+    "fluxmi_png_seal": ([vp, i64, C.POINTER(C.c_double)], i32),
     "fluxmi_resample_ksize": ([i32, i32, i32, C.POINTER(i32)], i32),
     "fluxmi_resample_coeffs": ([i32, i32, i32, vp, vp], i32),
     "fluxmi_resample_plan": ([i32, i32, i32, i32, i32, i32, i32, C.POINTER(i32), C.POINTER(i64)], i32),

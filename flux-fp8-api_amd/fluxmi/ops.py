@@ -1153,6 +1153,94 @@ def jpeg_encode(px: torch.Tensor, quality: int = 99, subsampling: str = "4:2:0",
     return host.numpy().tobytes()
 
 
+# ---- PNG encoder (csrc/png.hip, csrc/png_host.cpp; include/fluxmi.h has the definition) --------------------------------------------------
+PNG_FILTERS = {"none": 0, "sub": 1, "up": 2, "average": 3, "paeth": 4, "adaptive": 5}  # FLUXMI_PNG_FILTER_*
+PNG_STRIP_TARGET, PNG_STRIP_ROWS = 67584, 16   # FLUXMI_PNG_STRIP_TARGET, FLUXMI_PNG_STRIP_ROWS
+PNG_FRAME_BYTES = 63                           # signature, IHDR, the IDAT's framing, zlib header, Adler-32, IEND
+
+
+def png_strip_bound(n: int) -> int:
+    """FLUXMI_PNG_STRIP_BOUND: the most bytes a strip of n filtered bytes takes (stored blocks + the empty block that ends it)"""
+    return n + 5 * ((n + 65534) // 65535) + 5
+
+
+def png_params(B: int, H: int, W: int, C_: int = 3, filter="adaptive"):
+    """every refusal of a PNG request that needs no device, by name -> (FLUXMI_PNG_FILTER_* code, rows per strip)"""
+    if filter not in PNG_FILTERS:
+        raise ValueError(f"png_encode: filter={filter!r}: expected one of {tuple(PNG_FILTERS)}")
+    if C_ not in (1, 3):
+        raise ValueError(f"png_encode: {C_} channels: expected 3 (RGB) or 1 (grey)")
+    if min(B, H, W) < 1 or B * H > 2 ** 31 - 1 or W * C_ >= 2 ** 30:
+        raise ValueError(f"png_encode: B * H = {B} * {H} rows must lie in 1..2^31 - 1 and a row's W * C = {W} * {C_} bytes in 1..2^30 - 1 (a "
+                         f"batch is one image, stacked vertically)")
+    rows = max(1, min(PNG_STRIP_ROWS, PNG_STRIP_TARGET // (1 + W * C_)))
+    if -(-B * H // rows) > (2 ** 32 - 1) // 256:
+        raise ValueError(f"png_encode: {B * H} rows in strips of {rows} are beyond the {(2 ** 32 - 1) // 256} strips one launch holds")
+    full, tail = divmod(B * H, rows)
+    if 6 + full * png_strip_bound(rows * (1 + W * C_)) + (png_strip_bound(tail * (1 + W * C_)) if tail else 0) > 2 ** 31 - 1:
+        raise ValueError(f"png_encode: {B * H} x {W} x {C_} may not fit one IDAT chunk of 2^31 - 1 bytes")
+    return PNG_FILTERS[filter], rows
+
+
+def png_workspace_bytes(B: int, H: int, W: int, C_: int = 3):
+    """(bytes of `work`, bytes of an `out` no file can exceed) for png_encode_into (fluxmi_png_workspace_bytes)"""
+    png_params(B, H, W, C_)
+    work, cap = C.c_longlong(0), C.c_longlong(0)
+    call("fluxmi_png_workspace_bytes", B, H, W, C_, C.byref(work), C.byref(cap))
+    return work.value, cap.value
+
+
+def _png_image(px: torch.Tensor):
+    if px.ndim not in (3, 4) or (px.ndim == 4 and px.shape[-1] not in (1, 3)):
+        raise ValueError(f"png_encode: px must be uint8 [B, H, W, 3] (RGB) or [B, H, W] / [B, H, W, 1] (grey), got {tuple(px.shape)}")
+    ch = 1 if px.ndim == 3 else px.shape[-1]
+    return (ch,) + _u8_image(px, "png_encode", "px", ch)
+
+
+def png_encode_into(px: torch.Tensor, work: torch.Tensor, out: torch.Tensor, filter="adaptive") -> int:
+    """px uint8 [B, H, W, 3] or [B, H, W] on the device (any row / image stride, as _u8_image takes them) -> the PNG file in out[:n], n
+    returned, its IDAT CRC field still zero (png_seal fills it in on the host's copy).  work (256-byte aligned) and out are flat uint8
+    device buffers; a file that does not fit is refused by name (RuntimeError) and nothing beyond out is written."""
+    ch, B, H, W, ld, bs = _png_image(px)
+    f, _ = png_params(B, H, W, ch, filter)
+    for name, t in (("work", work), ("out", out)):
+        _req(t, torch.uint8, f"png_encode: {name}")
+        if t.ndim != 1 or not t.is_contiguous() or t.device != px.device:
+            raise ValueError(f"png_encode: {name} must be a flat contiguous uint8 buffer on {px.device}")
+    n_dev = torch.zeros(1, dtype=torch.int64, device=px.device)
+    call("fluxmi_png_encode", _p(px), ld, bs, B, H, W, ch, f, _p(work), work.numel(), _p(out), out.numel(), _p(n_dev), _stream())
+    n = C.c_longlong(0)
+    call("fluxmi_png_finish", _p(n_dev), out.numel(), C.byref(n), _stream())
+    return n.value
+
+
+def png_seal(data) -> float:
+    """the IDAT CRC-32 of a file of png_encode_into, in place in a writable host buffer (bytearray / uint8 array); -> milliseconds taken"""
+    buf = (C.c_ubyte * len(data)).from_buffer(data)
+    ms = C.c_double(0.0)
+    call("fluxmi_png_seal", buf, len(data), C.byref(ms))
+    return ms.value
+
+
+def png_encode(px: torch.Tensor, filter: str = "adaptive", profile: Optional[dict] = None) -> bytes:
+    """px uint8 [B, H, W, 3] (RGB) or [B, H, W] (grey) on the device -> the bytes of a PNG file (fluxmi_png_encode; include/fluxmi.h is the
+    definition).  Lossless; a batch is ONE image of height B * H.  Two device-to-host copies -- the length, then exactly that many bytes --
+    and one pass of the host over them for the IDAT's CRC-32 (its milliseconds land in profile["crc_ms"]).  Synchronises the current stream."""
+    ch, B, H, W, _, _ = _png_image(px)
+    nwork, cap = png_workspace_bytes(B, H, W, ch)
+    work = torch.empty(nwork, dtype=torch.uint8, device=px.device)
+    out = torch.empty(cap, dtype=torch.uint8, device=px.device)
+    n = png_encode_into(px, work, out, filter)
+    host = torch.empty(n, dtype=torch.uint8, pin_memory=True)  # torch caches pinned blocks: no allocation once warm
+    host.copy_(out[:n], non_blocking=True)
+    torch.cuda.current_stream().synchronize()
+    arr = host.numpy()
+    ms = png_seal(arr)
+    if profile is not None:
+        profile.update(crc_ms=ms, work_bytes=nwork, out_cap=cap)
+    return arr.tobytes()
+
+
 # ---- image resampler (csrc/resample.hip, csrc/resample_host.cpp; include/fluxmi.h has the definition: Pillow's 8-bit resize) -------------
 RESAMPLE_FILTERS = {"box": 0, "bilinear": 1, "hamming": 2, "bicubic": 3, "lanczos": 4}  # FLUXMI_RESAMPLE_BOX .. FLUXMI_RESAMPLE_LANCZOS
 RESAMPLE_TILE_BYTES = 256        # FLUXMI_RESAMPLE_TILE_BYTES: output bytes (pixels x channels) of one workgroup's tile

@@ -94,6 +94,9 @@ class ModelSpec(BaseModel):  # reference util.py:38-79 (unknown JSON keys are ig
     # who writes the JPEG of an output_type="jpeg" request that does not say (generate(jpeg_encoder=...)): "pil" (Pillow on the host, the
     # reference's path) or "native" (fluxmi.ops.jpeg_encode on the device: the same decoded pixels, restart markers in the stream)
     jpeg_encoder: str = "pil"
+    # who writes the PNG of an output_type="png" request that does not say (generate(png_encoder=...)): "native" (fluxmi.ops.png_encode on the
+    # device) or "pil" (Pillow on the host at compress_level=6: the same decoded pixels)
+    png_encoder: str = "native"
     # who resizes a request's images when it does not say (generate(image_resize=...)): "pil" (Pillow on the host, the reference's path) or
     # "native" (fluxmi.ops.resize_u8 on the device: Pillow's integer resampler, the same bytes, so the same latents)
     image_resize: str = "pil"

@@ -553,6 +553,67 @@ int fluxmi_jpeg_encode(const void* rgb, long long ld, long long bs, int B, int H
 int fluxmi_jpeg_finish(const void* n_bytes_dev, long long out_cap, long long* n_bytes, void* stream);
 int fluxmi_jpeg_header(int B, int H, int W, int quality, int subsampling, int restart, void* buf, long long cap, long long* n_bytes);
 
+/* ---- PNG encoder (csrc/png.hip, csrc/png_host.cpp): device pixels -> the bytes of a PNG file, lossless ------------------------------------
+ * px uint8 [B][H][W][C], C = 3 (colour type 2, RGB) or 1 (colour type 0, grey), bit depth 8, no interlace; row stride ld, image stride bs,
+ * in bytes, as above.  The file is signature, IHDR, ONE IDAT, IEND; the IDAT holds one zlib stream: 78 01, deflate blocks, Adler-32.  The
+ * text below IS the definition: the same pixels and arguments give the same bytes, run to run (integer arithmetic, and LDS atomics that
+ * commute: histogram adds, bit ORs).  zlib and Pillow are the decoders of record; tests/png_ref.py restates the filter and strip rules.
+ *   Input.   A batch is ONE image of B * H rows: image b's row r is row b * H + r.  B * H <= 2^31 - 1 and W * C < 2^30.
+ *   Filtering.  A scanline is a filter byte and W * C residual bytes (x - prediction) mod 256 with a = the byte C to the left, b = the byte
+ *            above, c = the byte above a; bytes left of the row and the row above row 0 are zero, and for B > 1 row 0 of image b predicts
+ *            from the last row of image b - 1.  NONE 0: 0; SUB 1: a; UP 2: b; AVERAGE 3: (a + b) >> 1; PAETH 4: with p = a + b - c the one
+ *            of a, b, c nearest to p, ties in that order.  Filters read raw pixels only, so rows do not depend on each other.
+ *            FLUXMI_PNG_FILTER_ADAPTIVE picks, per row, the filter whose residual row has the smallest sum of min(v, 256 - v); ties go to
+ *            the lowest filter number.
+ *   Strips.  rows = clamp(FLUXMI_PNG_STRIP_TARGET / (1 + W C), 1, FLUXMI_PNG_STRIP_ROWS) (integer division): a function of (W, C) alone.
+ *            Strip s is scanlines s rows .. min((s + 1) rows, B H) and compresses with no reference to any other strip.  The target, 66
+ *            KiB, is what lets two workgroups (12 KiB of static LDS each) hold their strips in a compute unit's 160 KiB of LDS; a single
+ *            scanline beyond it is a strip of one row whose bytes live in the workspace instead.
+ *   Tokens.  Literals, and matches at distance 1 of length 3..258.  A maximal run of n equal bytes of the strip (filter bytes included) is
+ *            one literal, then floor((n - 1) / 258) matches of length 258, then the remainder r = (n - 1) mod 258: a match of length r
+ *            when r >= 3, r literals when r is 1 or 2.
+ *   Codes.   Each strip is one dynamic-Huffman block (BTYPE 10).  The literal/length code is the Huffman code of the strip's symbol counts
+ *            plus one end-of-block -- two-queue merge over the symbols sorted by (count, symbol), a leaf before an internal node of equal
+ *            weight -- limited to 15 bits by zlib's rule (every node deeper than 15 is moved to 15 and counted; per two counted, one leaf
+ *            of the deepest level above 15 that has one becomes an internal node over itself and a leaf taken from level 15; lengths then
+ *            go to the symbols from the rarest up, longest first) and numbered canonically (RFC 1951 3.2.2).  HLIT covers the highest
+ *            symbol in use.  HDIST = 2: distance codes 0 and 1 of one bit each are always sent -- a complete code, matches or not -- and
+ *            a match's distance is the one bit 0.  The code-length code is built the same way over the lengths 0..15 of those HLIT + 2
+ *            entries, limited to 7 bits; the repeat symbols 16..18 are not used.
+ *   Stored.  The dynamic block's exact size (header + counts x lengths + extra bits) is known before a bit is written; when it is not
+ *            below 8 n + 40 ceil(n / 65535) bits, the strip's n bytes go out as stored blocks of at most 65535 bytes instead.
+ *   End.     Every strip ends with an empty stored block (BFINAL set in the last strip's), which byte-aligns it.  So a strip takes at
+ *            most FLUXMI_PNG_STRIP_BOUND(n) bytes -- the size of its slot in `work` -- and a file at most 57 + 6 + the sum of the bounds.
+ *   CRC.     The IDAT's CRC-32 is NOT computed on the device: fluxmi_png_encode leaves those four bytes zero, and fluxmi_png_seal fills
+ *            them in over the host's copy of the file (per-strip IDAT chunks with device CRCs would remove that pass).
+ * Three launches and no host wait: (1) one workgroup per strip filters (one wave per row, wave reductions cost the five filters), counts
+ * symbols and the Adler-32 partial, builds both codes (a bitonic sort, one lane's tree merge), decides, and emits through an LDS bit window
+ * into its slot; (2) a prefix sum of the strip sizes and the composition of the Adler partials; (3) each slot is copied behind the head.
+ * fluxmi_png_workspace_bytes: *work_bytes = the size of `work` (256-byte aligned), *out_cap = a size of `out` no file can exceed.
+ * fluxmi_png_encode: asynchronous.  Writes the file (CRC field zero) to out[0 .. n) and n (int64) to *n_bytes_dev, a DEVICE address.  No
+ *   byte at or beyond out + out_cap is written whatever n is; n > out_cap means the file did not fit.  Refused by name before any launch:
+ *   C other than 1 or 3, sizes below 1, B * H or W * C beyond the limits above, more than 16 777 215 strips (one launch's workgroups of
+ *   256 threads), a file that may exceed one IDAT's 2^31 - 1 bytes, an
+ *   unknown filter, strides shorter than a row / an image, a NULL or misaligned or too small `work`, an `out` below the 63 framing bytes.
+ * fluxmi_png_finish: the one small read-back: *n_bytes = *n_bytes_dev after synchronising `stream`; n > out_cap is an error.
+ * fluxmi_png_header: host only: the 43 bytes in front of the deflate blocks (IDAT length zero) into buf[0 .. cap).
+ * fluxmi_png_seal: host only: the IDAT CRC-32 of the n_bytes of such a file at `file` (host memory), in place; *crc_ms = the time it took. */
+#define FLUXMI_PNG_FILTER_NONE 0
+#define FLUXMI_PNG_FILTER_SUB 1
+#define FLUXMI_PNG_FILTER_UP 2
+#define FLUXMI_PNG_FILTER_AVERAGE 3
+#define FLUXMI_PNG_FILTER_PAETH 4
+#define FLUXMI_PNG_FILTER_ADAPTIVE 5
+#define FLUXMI_PNG_STRIP_TARGET 67584
+#define FLUXMI_PNG_STRIP_ROWS 16
+#define FLUXMI_PNG_STRIP_BOUND(n) ((long long)(n) + 5 * (((long long)(n) + 65534) / 65535) + 5)
+int fluxmi_png_workspace_bytes(int B, int H, int W, int C, long long* work_bytes, long long* out_cap);
+int fluxmi_png_encode(const void* px, long long ld, long long bs, int B, int H, int W, int C, int filter, void* work, long long work_bytes,
+                      void* out, long long out_cap, void* n_bytes_dev, void* stream);
+int fluxmi_png_finish(const void* n_bytes_dev, long long out_cap, long long* n_bytes, void* stream);
+int fluxmi_png_header(int B, int H, int W, int C, void* buf, long long cap, long long* n_bytes);
+int fluxmi_png_seal(void* file, long long n_bytes, double* crc_ms);
+
 /* ---- image resampler (csrc/resample.hip, csrc/resample_host.cpp): Pillow's resize of an 8-bit image, byte for byte ----------------------
  * uint8 [B][H][W][C] -> [B][h][w][C], C in {1, 3}, rows and images behind byte strides as for the preprocessors above.  The definition is
  * Pillow's ImagingResample at 8 bits per channel (Image.resize of an "L" / "RGB" image, no box=, no reducing_gap=), restated here and in

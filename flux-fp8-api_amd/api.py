@@ -50,6 +50,7 @@ Same two POST endpoints, request fields, defaults and status codes:
              preview_every without stream is a 422.
   /lora      LoraArgs{scale=1.0, path, name, action="load"|"unload"}  ->  {"status": "success"} | 400 invalid action | 500 with the
              exception text; unload uses `name` when given, else `path`                                         (reference api.py:89-122)
+             + adapters=[{path, scale=1.0, name}] on a load: all of them fused at once, one fp8 re-quantisation per layer (no counterpart)
 The app holds one pipeline in `app.state.model`; FastAPI runs these sync handlers on its threadpool, and the pipeline serialises
 engine access with its own lock (modules/flux_model.py), so concurrent requests queue instead of interleaving.
 """
@@ -70,11 +71,18 @@ from pydantic import BaseModel, Field
 MAX_RAND = 2**32 - 1
 
 
+class AdapterArgs(BaseModel):
+    path: str
+    scale: float = 1.0
+    name: Optional[str] = None
+
+
 class LoraArgs(BaseModel):
     scale: Optional[float] = 1.0
     path: Optional[str] = None
     name: Optional[str] = None
     action: Optional[Literal["load", "unload"]] = "load"
+    adapters: Optional[List[AdapterArgs]] = None  # load only: several adapters fused in one pass (one re-quantisation per layer)
 
 
 class LoraLoadResponse(BaseModel):
@@ -276,7 +284,9 @@ def generate(args: GenerateArgs):
 def lora_action(args: LoraArgs):
     """Fuse (`load`) or subtract-and-requantise (`unload`) a LoRA into the fp8 flow weights."""
     try:
-        if args.action == "load":
+        if args.action == "load" and args.adapters:
+            app.state.model.load_loras([(a.path, a.scale, a.name) for a in args.adapters])
+        elif args.action == "load":
             app.state.model.load_lora(args.path, args.scale, args.name)
         elif args.action == "unload":
             app.state.model.unload_lora(args.name if args.name else args.path)

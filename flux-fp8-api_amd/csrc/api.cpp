@@ -134,6 +134,30 @@ int fluxmi_lora_fuse_f8(void* w_fp8, float* w_scale, float* w_scale_recip, const
   return fluxmi_k_requantize_f32(w32, w_fp8, amax_tmp, w_scale, w_scale_recip, n, FLUXMI_E4M3, s);
 }
 
+// W' = requant( bf16( dequant(W) + sum_t d_t ) ) in place, no workspace (adapter_fuse.hip).  Everything is checked here, before any
+// launch: a refused call has done nothing.
+int fluxmi_adapter_fuse_f8(void* w_fp8, float* w_scale, float* w_scale_recip, const fluxmi_delta_term_t* terms, int n_terms, int N, int K,
+                           float* amax_tmp, void* stream) {
+  FLUXMI_REQUIRE(n_terms >= 1 && n_terms <= FLUXMI_MAX_DELTA_TERMS, "adapter_fuse: n_terms=%d outside 1..%d", n_terms, FLUXMI_MAX_DELTA_TERMS);
+  FLUXMI_REQUIRE(w_fp8 && w_scale && w_scale_recip && terms && amax_tmp, "adapter_fuse: null weight, scale, terms or amax_tmp pointer");
+  FLUXMI_REQUIRE(N >= 1 && K >= 16 && K % 16 == 0, "adapter_fuse: N=%d must be >= 1 and K=%d a multiple of 16 (K %% 16 != 0)", N, K);
+  FLUXMI_REQUIRE(((unsigned long long)w_fp8 & 3) == 0, "adapter_fuse: w_fp8=%p must be 4-byte aligned", w_fp8);
+  for (int t = 0; t < n_terms; ++t) {
+    const fluxmi_delta_term_t& T = terms[t];
+    FLUXMI_REQUIRE(T.kind >= FLUXMI_DELTA_LORA && T.kind <= FLUXMI_DELTA_FULL, "adapter_fuse: term %d: unknown kind %d", t, T.kind);
+    const int n_ptrs = T.kind == FLUXMI_DELTA_LOHA ? 4 : T.kind == FLUXMI_DELTA_FULL ? 1 : 2;
+    const float* p[4] = {T.p0, T.p1, T.p2, T.p3};
+    for (int i = 0; i < n_ptrs; ++i) FLUXMI_REQUIRE(p[i], "adapter_fuse: term %d: null factor pointer p%d", t, i);
+    if (T.kind == FLUXMI_DELTA_LORA || T.kind == FLUXMI_DELTA_LOHA)
+      FLUXMI_REQUIRE(T.rank >= 1 && T.rank <= 128, "adapter_fuse: term %d: rank=%d outside 1..128", t, T.rank);
+    if (T.kind == FLUXMI_DELTA_LORA) FLUXMI_REQUIRE(T.n_chunks >= 1, "adapter_fuse: term %d: n_chunks=%d must be >= 1", t, T.n_chunks);
+    if (T.kind == FLUXMI_DELTA_LOKR)
+      FLUXMI_REQUIRE(T.kn >= 1 && T.kk >= 1 && N % T.kn == 0 && K % T.kk == 0, "adapter_fuse: term %d: LOKR block kn=%d kk=%d must divide N=%d K=%d", t,
+                     T.kn, T.kk, N, K);
+  }
+  return fluxmi_k_adapter_fuse(w_fp8, w_scale, w_scale_recip, terms, n_terms, N, K, amax_tmp, (hipStream_t)stream);
+}
+
 int fluxmi_ln_modulate(const void* x, long long ldx, void* out, long long ldo, const void* shift0, const void* scale0,
                        const void* shift1, const void* scale1, long long mod_bstride, const float* q_scale0, const float* q_scale1,
                        int B, int L, int split, int H, int out_fp8, int fmt, void* stream) {

@@ -135,6 +135,9 @@ int fluxmi_k_dequant(const void* q, float* out, const float* recip, long long n,
 int fluxmi_k_requantize_f32(const float* w32, void* q, float* amax_tmp, float* scale, float* recip, long long n, int fmt, hipStream_t s);
 int fluxmi_k_lora_delta(const float* Bm, const float* A, float* delta, int N, int K, int R, float scale, int accumulate, hipStream_t s);
 int fluxmi_k_axpy_f32(float* w, const float* d, float alpha, long long n, hipStream_t s);
+// adapter_fuse.hip: the two passes of fluxmi_adapter_fuse_f8 (terms already validated; amax_tmp: four floats)
+int fluxmi_k_adapter_fuse(void* w_fp8, float* w_scale, float* w_scale_recip, const fluxmi_delta_term_t* terms, int n_terms, int N, int K,
+                          float* amax_tmp, hipStream_t s);
 int fluxmi_ln_pairs_ok(int H);  // elementwise.hip: fluxmi_k_ln_modulate can write the row-pair layout at this hidden size / ln_variant
 int fluxmi_k_ln_modulate(const void* x, long long ldx, long long x_bstride, void* out, long long ldo, long long out_bstride,
                          const void* shift0, const void* scale0, const void* shift1, const void* scale1, long long mod_bstride,

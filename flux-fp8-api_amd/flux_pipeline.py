@@ -771,6 +771,10 @@ class FluxPipeline:
     def load_lora(self, lora_path, scale: float, name: Optional[str] = None):
         self.model.load_lora(path=lora_path, scale=scale, name=name)
 
+    def load_loras(self, loras):
+        """[(path, scale, name)]: several adapters (LoRA, LoHa, LoKr, full delta) fused with one re-quantisation per layer."""
+        self.model.load_loras(loras)
+
     def unload_lora(self, path_or_identifier: str):
         self.model.unload_lora(path_or_identifier=path_or_identifier)
 

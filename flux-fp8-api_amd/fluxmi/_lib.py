@@ -61,6 +61,14 @@ class ModelDesc(C.Structure):
     ]
 
 
+class DeltaTerm(C.Structure):
+    """fluxmi_delta_term_t (include/fluxmi.h): one delta term of fluxmi_adapter_fuse_f8."""
+    _fields_ = [("kind", i32), ("rank", i32), ("n_chunks", i32), ("kn", i32), ("kk", i32), ("scale", f32), ("p0", vp), ("p1", vp), ("p2", vp), ("p3", vp)]
+
+
+DELTA_LORA, DELTA_LOHA, DELTA_LOKR, DELTA_FULL = range(4)
+MAX_DELTA_TERMS = 8
+
 _SIGS = {
     "fluxmi_abi_version": ([], i32),
     "fluxmi_get_tuning": ([C.POINTER(Tuning)], i32),
@@ -76,6 +84,7 @@ _SIGS = {
     "fluxmi_calib_update": ([vp, vp, vp, vp, i32, i32, f32, vp], i32),
     "fluxmi_quantize_weight": ([vp, vp, vp, vp, vp, i32, i32, i32, vp], i32),
     "fluxmi_lora_fuse_f8": ([vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp], i32),
+    "fluxmi_adapter_fuse_f8": ([vp, vp, vp, C.POINTER(DeltaTerm), i32, i32, i32, vp, vp], i32),
     "fluxmi_dequant": ([vp, vp, vp, i64, i32, vp], i32),
     "fluxmi_ln_modulate": ([vp, i64, vp, i64, vp, vp, vp, vp, i64, vp, vp, i32, i32, i32, i32, i32, i32, vp], i32),
     "fluxmi_ln_modulate_pairs": ([vp, i64, vp, i64, vp, vp, vp, vp, i64, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp], i32),

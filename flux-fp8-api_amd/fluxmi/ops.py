@@ -6,6 +6,7 @@ PyTorch is plumbing only (device memory + current stream).  Every function launc
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 from typing import Optional, Sequence
 
 import torch
@@ -96,6 +97,70 @@ def lora_fuse_f8(w8: torch.Tensor, w_scale: torch.Tensor, w_scale_recip: torch.T
         raise TypeError(f"fluxmi: LoRA fuse needs float8_e4m3fn weights (the GEMM kernels fix the weight operand format), got {w8.dtype}")
     call("fluxmi_lora_fuse_f8", _p(w8), _p(w_scale), _p(w_scale_recip), _p(lora_B.float().contiguous()),
          _p(lora_A.float().contiguous()), N, K, R, n_chunks, float(lora_scale), _p(work), _p(tmp), _stream())
+
+
+@dataclasses.dataclass
+class Delta:
+    """One delta term of adapter_fuse_f8 (fluxmi_delta_term_t).  factors, fp32 on the weight's device:
+    lora (B [N, R], A [n_chunks * R, K]) | loha (w1_a [N, R], w1_b [R, K], w2_a [N, R], w2_b [R, K]) | lokr (w1 [N / kn, K / kk], w2 [kn, kk]) |
+    full (D [N, K])."""
+    kind: str
+    factors: tuple
+    scale: float = 1.0
+    n_chunks: int = 1
+
+    def scaled(self, s: float) -> "Delta":
+        return dataclasses.replace(self, scale=self.scale * s)
+
+    def dense(self) -> torch.Tensor:
+        """the delta as a dense fp32 matrix in plain torch: weight surgery on un-quantised layers (plumbing), and what the tests restate"""
+        f = [t.float() for t in self.factors]
+        if self.kind == "lora":
+            return sum(self.scale * torch.mm(f[0], c) for c in f[1].chunk(self.n_chunks, dim=0))
+        if self.kind == "loha":
+            return torch.mm(f[0], f[1]) * torch.mm(f[2], f[3]) * self.scale
+        return (torch.kron(f[0], f[1]) if self.kind == "lokr" else f[0]) * self.scale
+
+
+MAX_DELTA_TERMS = _lib.MAX_DELTA_TERMS
+_DELTA_KINDS = {"lora": (_lib.DELTA_LORA, 2), "loha": (_lib.DELTA_LOHA, 4), "lokr": (_lib.DELTA_LOKR, 2), "full": (_lib.DELTA_FULL, 1)}
+
+
+def delta_terms(terms: Sequence[Delta], N: int, K: int, device):
+    """-> (ctypes array of fluxmi_delta_term_t, the device tensors it points into, which the caller keeps alive over the call)"""
+    arr = (_lib.DeltaTerm * max(len(terms), 1))()
+    keep = []
+    for d, t in zip(arr, terms):
+        if t.kind not in _DELTA_KINDS or len(t.factors) != _DELTA_KINDS[t.kind][1]:
+            raise ValueError(f"fluxmi: adapter term {t.kind!r} with {len(t.factors)} factors (kinds and factor counts: {_DELTA_KINDS})")
+        f = [x.to(device=device, dtype=torch.float32).contiguous() for x in t.factors]
+        keep.append(f)
+        d.kind, d.scale, d.n_chunks = _DELTA_KINDS[t.kind][0], float(t.scale), int(t.n_chunks)
+        want = {"lora": lambda r: [(N, r), (t.n_chunks * r, K)], "loha": lambda r: [(N, r), (r, K)] * 2, "full": lambda r: [(N, K)]}
+        if t.kind == "lokr":
+            d.kn, d.kk = f[1].shape
+            shapes = [(N // max(d.kn, 1), K // max(d.kk, 1)), tuple(f[1].shape)]
+        else:
+            d.rank = f[0].shape[1] if t.kind != "full" else 0
+            shapes = want[t.kind](d.rank)
+        if [tuple(x.shape) for x in f] != shapes:
+            raise ValueError(f"fluxmi: {t.kind} term for a [{N}, {K}] weight needs factors {shapes}, got {[tuple(x.shape) for x in f]}")
+        for name, x in zip(("p0", "p1", "p2", "p3"), f):
+            setattr(d, name, x.data_ptr())
+    return arr, keep
+
+
+def adapter_fuse_f8(w8: torch.Tensor, w_scale: torch.Tensor, w_scale_recip: torch.Tensor, terms: Sequence[Delta]) -> None:
+    """In-place fuse of up to 8 delta terms (LoRA, LoHa, LoKr, full) + ONE re-quantise of an e4m3 weight, no fp32 workspace
+    (fluxmi_adapter_fuse_f8; the arithmetic is stated in include/fluxmi.h)."""
+    _req(w8, torch.float8_e4m3fn, "w8")
+    N, K = w8.shape
+    arr, keep = delta_terms(terms, N, K, w8.device)
+    tmp = torch.empty(4, dtype=torch.float32, device=w8.device)
+    if not w8.is_contiguous():
+        raise ValueError("fluxmi: adapter fuse needs a contiguous weight")
+    call("fluxmi_adapter_fuse_f8", _p(w8), _p(w_scale), _p(w_scale_recip), arr, len(terms), N, K, _p(tmp), _stream())
+    del keep  # (alive until the launches were queued; same stream, so the allocator cannot hand the factors out before they run)
 
 
 # ---- linear ----------------------------------------------------------------------------------------

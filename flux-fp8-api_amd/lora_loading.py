@@ -6,6 +6,11 @@ In scope: dequantise fp8 -> fp32, dW = scale * (alpha/ra
 re-quantise with a fresh amax/scale (F8Linear.set_weight_tensor semantics) -- all on the GPU via
 libfluxmi (fluxmi_lora_fuse_f8).  Input scales are NOT recalibrated, exactly like the reference.
 
+Beside plain LoRA a module may carry a LyCORIS LoHa (`hada_w1_a / hada_w1_b / hada_w2_a / hada_w2_b`), LoKr (`lokr_w1` or `lokr_w1_a` +
+`lokr_w1_b`, `lokr_w2` or `lokr_w2_a` + `lokr_w2_b`) or full delta (`diff`), each with `alpha`; these, and every load of several adapters at
+once, go through fluxmi_adapter_fuse_f8: all terms of a module in one pass over its fp8 bytes and ONE re-quantisation.  The reference has
+no counterpart.  Tucker factors and `diff_b` are refused by name, `dora_scale` is ignored with a warning.
+
 Accepted inputs: a dict with BFL-dotted keys `<module>.lora_A.weight / .lora_B.weight / .alpha`
 (lora_loading.py:608-612 skips conversion for dicts), a LoraWeights, or a safetensors path holding such
 keys, kohya `lora_unet_*` keys, or diffusers `transformer.*` keys (both converted below; the diffusers
@@ -15,6 +20,7 @@ tests/golden/g12_lora_diffusers.safetensors, quirks included).
 from __future__ import annotations
 
 import re
+import warnings
 from typing import Optional, OrderedDict, Tuple, TypeAlias, Union
 
 import torch
@@ -24,6 +30,11 @@ from float8_quantize import F8Linear
 from fluxmi import ops
 
 path_regex = re.compile(r"/|\\")
+# LyCORIS leaves beside `lora_A / lora_B / alpha` (public LyCORIS / ComfyUI key conventions; no real checkpoint has been available to pin them)
+_REFUSED_LEAVES = ("hada_t1", "hada_t2", "lokr_t2", "diff_b")
+_ADAPTER_LEAVES = ("hada_w1_a", "hada_w1_b", "hada_w2_a", "hada_w2_b", "lokr_w1", "lokr_w1_a", "lokr_w1_b", "lokr_w2", "lokr_w2_a", "lokr_w2_b",
+                   "diff") + _REFUSED_LEAVES
+_LEAF_RE = re.compile(r"\.(?:" + "|".join(_ADAPTER_LEAVES + ("dora_scale",)) + r")$")
 StateDict: TypeAlias = OrderedDict[str, torch.Tensor]
 
 
@@ -148,12 +159,12 @@ def resolve_lora_state_dict(lora_weights: dict, has_guidance: bool = True):
     if any(k.startswith("transformer.") for k in lora_weights):
         lora_weights = convert_diffusers_to_flux_transformer_checkpoint(dict(lora_weights), 19, 38, has_guidance=has_guidance, prefix="transformer.")
     else:
-        lora_weights = _kohya_to_bfl({k: v for k, v in lora_weights.items() if "lora" in k})
+        lora_weights = _kohya_to_bfl({k: v for k, v in lora_weights.items() if "lora" in k or _LEAF_RE.search(k)})
     return _keys_without_ab(lora_weights), lora_weights
 
 
 def _keys_without_ab(lora_weights: dict):
-    return sorted({k.replace(".lora_A.weight", "").replace(".lora_B.weight", "").replace(".lora_A", "").replace(".lora_B", "")
+    return sorted({_LEAF_RE.sub("", k).replace(".lora_A.weight", "").replace(".lora_B.weight", "").replace(".lora_A", "").replace(".lora_B", "")
                    .replace(".alpha", "") for k in lora_weights.keys()})
 
 
@@ -180,49 +191,106 @@ def _prescaled_A(lora_A, lora_B, alpha, device):
     return a.contiguous(), chunks, rank
 
 
+def get_adapter_for_key(key: str, lora_weights: dict, device=None) -> Optional[ops.Delta]:
+    """The delta term of module `key` at adapter scale 1, or None when the dict holds no adapter for it.  Plain LoRA keeps the reference's
+    arithmetic (alpha / rank folded into lora_A).  LoHa / LoKr / full deltas follow the LyCORIS key layout and ComfyUI's loading rule: the
+    factor scale is alpha / rank when a decomposed factor gives a rank, else 1; decomposed LoKr factors are multiplied out here."""
+    for leaf in _REFUSED_LEAVES:
+        if f"{key}.{leaf}" in lora_weights:
+            raise ValueError(f"adapter key {key}.{leaf}: Tucker-decomposed factors (hada_t1 / hada_t2 / lokr_t2) and bias deltas (diff_b) are not supported")
+    if f"{key}.dora_scale" in lora_weights:
+        warnings.warn(f"adapter key {key}.dora_scale is ignored: DoRA is not supported, the module is fused without its magnitude vector")
+
+    def get(leaf):
+        t = lora_weights.get(f"{key}.{leaf}")
+        return None if t is None else t.to(dtype=torch.float32, device=device)
+
+    alpha = lora_weights.get(f"{key}.alpha")
+    alpha = None if alpha is None else float(alpha)
+    lora_sd = get_lora_for_key(key, lora_weights)
+    if lora_sd is not None:
+        a, chunks, _ = _prescaled_A(lora_sd[0], lora_sd[1], lora_sd[2], device)
+        return ops.Delta("lora", (lora_sd[1].to(dtype=torch.float32, device=device), a), 1.0, chunks)
+    hada = [get(leaf) for leaf in ("hada_w1_a", "hada_w1_b", "hada_w2_a", "hada_w2_b")]
+    if all(t is not None for t in hada):
+        rank = hada[1].shape[0]
+        return ops.Delta("loha", tuple(hada), alpha / rank if alpha is not None else 1.0)
+    kron, rank = [], None
+    for w in ("lokr_w1", "lokr_w2"):
+        full, fa, fb = get(w), get(w + "_a"), get(w + "_b")
+        if full is None and fa is not None and fb is not None:
+            full, rank = torch.mm(fa, fb), fb.shape[0]
+        kron.append(full)
+    if all(t is not None for t in kron):
+        return ops.Delta("lokr", tuple(kron), alpha / rank if alpha is not None and rank is not None else 1.0)
+    diff = get("diff")
+    return None if diff is None else ops.Delta("full", (diff,), 1.0)
+
+
 @torch.inference_mode()
-def _fuse_into(module: nn.Module, lora_sd, lora_scale: float):
-    lora_A, lora_B, alpha = lora_sd
+def _fuse_terms(module: nn.Module, terms) -> None:
+    """every term of one module in ONE re-quantisation (eight terms per call: FLUXMI_MAX_DELTA_TERMS)"""
     if isinstance(module, F8Linear):
-        dev = module.float8_data.device
-        a, chunks, _ = _prescaled_A(lora_A, lora_B, alpha, dev)
-        b = lora_B.to(dtype=torch.float32, device=dev).contiguous()
-        ops.lora_fuse_f8(module.float8_data, module.scale, module.scale_reciprocal, b, a, lora_scale, n_chunks=chunks)
+        if len(terms) == 1 and terms[0].kind == "lora":  # a plain LoRA on its own keeps the reference-shaped path and its bits
+            d = terms[0]
+            ops.lora_fuse_f8(module.float8_data, module.scale, module.scale_reciprocal, d.factors[0].contiguous(), d.factors[1], d.scale, n_chunks=d.n_chunks)
+            return
+        for i in range(0, len(terms), ops.MAX_DELTA_TERMS):
+            ops.adapter_fuse_f8(module.float8_data, module.scale, module.scale_reciprocal, terms[i:i + ops.MAX_DELTA_TERMS])
     else:  # un-quantised nn.Linear: one-off weight surgery in fp32 on the device (plumbing, not hot path)
         w = module.weight.data
-        a, chunks, _ = _prescaled_A(lora_A, lora_B, alpha, w.device)
-        b = lora_B.to(dtype=torch.float32, device=w.device)
-        delta = sum(lora_scale * torch.mm(b, c) for c in a.chunk(chunks, dim=0))
-        module.weight.data = (w.float() + delta).to(w.dtype)
+        module.weight.data = (w.float() + sum(d.dense() for d in terms)).to(w.dtype)
+
+
+def _module_device(module: nn.Module):
+    return module.float8_data.device if isinstance(module, F8Linear) else module.weight.device
+
+
+@torch.inference_mode()
+def fuse_adapters(model, adapters) -> None:
+    """adapters: [(BFL-keyed weights, scale)].  Gathers, per module, the terms of every adapter and fuses them together."""
+    per_module = {}
+    for lora_weights, scale in adapters:
+        for key in _keys_without_ab(lora_weights):
+            if get_lora_for_key(key, lora_weights) is None and not any(f"{key}.{leaf}" in lora_weights for leaf in _ADAPTER_LEAVES):
+                continue  # (before the module lookup: converted files carry keys of no module, as in the reference)
+            module = get_module_for_key(key, model)
+            d = get_adapter_for_key(key, lora_weights, _module_device(module))
+            if d is not None:
+                per_module.setdefault(key, (module, []))[1].append(d.scaled(scale))
+    for module, terms in per_module.values():
+        _fuse_terms(module, terms)
+    if hasattr(model, "rebind_weights"):
+        model.rebind_weights()
+
+
+def _guidance(model) -> bool:
+    return bool(getattr(getattr(model, "params", None), "guidance_embed", True))
 
 
 @torch.inference_mode()
 def apply_lora_to_model(model, lora_path, lora_scale: float = 1.0, return_lora_resolved: bool = False):
     """reference lora_loading.py:634-693."""
-    lora_weights, _ = _resolve(lora_path, bool(getattr(getattr(model, "params", None), "guidance_embed", True)))
-    for key in _keys_without_ab(lora_weights):
-        lora_sd = get_lora_for_key(key, lora_weights)
-        if lora_sd is None:
-            continue
-        _fuse_into(get_module_for_key(key, model), lora_sd, lora_scale)
-    if hasattr(model, "rebind_weights"):
-        model.rebind_weights()
+    lora_weights, _ = _resolve(lora_path, _guidance(model))
+    fuse_adapters(model, [(lora_weights, lora_scale)])
     if return_lora_resolved:
         return model, lora_weights
     return model
 
 
 @torch.inference_mode()
+def apply_loras_to_model(model, loras):
+    """loras: [(path or dict, scale)] -> the resolved weights of each, after ONE fuse per module over all of them"""
+    resolved = [(_resolve(path, _guidance(model))[0], scale) for path, scale in loras]
+    fuse_adapters(model, resolved)
+    return [w for w, _ in resolved]
+
+
+@torch.inference_mode()
 def remove_lora_from_module(model, lora_path, lora_scale: float = 1.0):
     """reference lora_loading.py:696-753: subtract the same delta and re-quantise (lossy through fp8, as there)."""
-    lora_weights, stored_scale = _resolve(lora_path, bool(getattr(getattr(model, "params", None), "guidance_embed", True)))
+    lora_weights, stored_scale = _resolve(lora_path, _guidance(model))
     if stored_scale is not None:
         lora_scale = stored_scale
-    for key in _keys_without_ab(lora_weights):
-        lora_sd = get_lora_for_key(key, lora_weights)
-        if lora_sd is None:
-            continue
-        _fuse_into(get_module_for_key(key, model), lora_sd, -lora_scale)
-    if hasattr(model, "rebind_weights"):
-        model.rebind_weights()
+    fuse_adapters(model, [(lora_weights, -lora_scale)])
     return model

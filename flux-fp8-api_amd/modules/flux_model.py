@@ -717,6 +717,21 @@ class Flux(nn.Module):
             self.loras.append(LoraWeights(lora, path if isinstance(path, str) else (name or "lora"), name, scale))
         self.rebind_weights()
 
+    def load_loras(self, loras):
+        """loras: [(path or state dict, scale, name)].  Every module takes the terms of ALL the adapters in one fuse: one fp8 re-quantisation
+        per layer however many adapters there are (load_lora one by one re-quantises per adapter).  Each member is recorded, so
+        unload_lora(name) works as after load_lora."""
+        from lora_loading import LoraWeights, apply_loras_to_model
+
+        loras = [(path, scale, name) for path, scale, name in loras]
+        for path, _, name in loras:
+            if self.has_lora(path) or (name and self.has_lora(name)):
+                raise ValueError(f"load_loras: {name or path!r} is already loaded; unload it first or use load_lora to change its scale")
+        resolved = apply_loras_to_model(self, [(path, scale) for path, scale, _ in loras])
+        for (path, scale, name), weights in zip(loras, resolved):
+            self.loras.append(LoraWeights(weights, path if isinstance(path, str) else (name or "lora"), name, scale))
+        self.rebind_weights()
+
     def unload_lora(self, path_or_identifier: str):
         from lora_loading import remove_lora_from_module
 

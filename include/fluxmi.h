@@ -252,6 +252,36 @@ int fluxmi_lora_fuse_f8(void* w_fp8, float* w_scale, float* w_scale_recip, const
                         int R, int n_chunks, float lora_scale, float* work_f32, float* amax_tmp, void* stream);
 int fluxmi_dequant(const void* q, float* out, const float* scale_recip, long long n, int fmt, void* stream);
 
+/* Adapter fuse: W' = requant(bf16(dequant(W) + sum_t d_t)) for 1 .. FLUXMI_MAX_DELTA_TERMS delta terms, in place on the e4m3 bytes, with
+ * no fp32 workspace and ONE re-quantisation however many terms there are.  LyCORIS forms (LoHa, LoKr, full delta) beside plain LoRA; the
+ * reference has no counterpart beyond LoRA (lora_loading.py:509-577).  Every factor is fp32, dense, row-major, on the device; `terms` is a
+ * HOST array.  csrc/adapter_fuse.hip: one tiled kernel run twice (measure the amax, then write), rank products on the fp32 matrix pipe.
+ *   w    = fp32(e4m3) * *w_scale_recip                                             as fluxmi_dequant
+ *   LORA   P = sum_r B[n][r] * A[c * R + r][k] in fp32 on the matrix pipe (v_mfma_f32_32x32x2_f32 chained over ascending rank pairs: a
+ *          fixed order); d_c = fl(P * scale); one chunk: d = d_0, more: d = fl(fl(fl(+0 + d_0) + d_1) + ...), as fluxmi_lora_fuse_f8
+ *   LOHA   d = fl(fl(P1 * P2) * scale), P1 = w1_a @ w1_b and P2 = w2_a @ w2_b summed as above
+ *   LOKR   d = fl(fl(w1[n / kn][k / kk] * w2[n % kn][k % kk]) * scale)              torch.kron(w1, w2) * scale
+ *   FULL   d = fl(D[n][k] * scale)
+ *   acc = w; acc = fl(acc + d_t) in term order; v = bf16(acc), round to nearest even; amax = max |v| (a NaN is skipped, as fluxmi_amax)
+ *   *w_scale = min(fl(fl(1 / max(amax, 1e-12)) * 448), 448); *w_scale_recip = fl(1 / *w_scale)       as fluxmi_quantize_weight
+ *   byte = e4m3(clamp(bf16(fl(v * *w_scale)), +-448)), round to nearest even          as fluxmi_lora_fuse_f8's last pass
+ * A product and its scale are two roundings, never an fma with the add.  N >= 1, K % 16 == 0; nothing outside the N * K bytes at w_fp8
+ * (4-byte aligned) is written.  amax_tmp: FOUR floats of device scratch.  Refused by name before any launch: n_terms outside
+ * 1 .. FLUXMI_MAX_DELTA_TERMS, an unknown kind, a null factor pointer, rank outside 1 .. 128 or n_chunks < 1 (LORA, LOHA), LOKR with
+ * N % kn or K % kk non-zero, K % 16 != 0. */
+#define FLUXMI_DELTA_LORA 0 /* p0 = B [N][R], p1 = A [n_chunks * R][K] */
+#define FLUXMI_DELTA_LOHA 1 /* p0 = w1_a [N][R], p1 = w1_b [R][K], p2 = w2_a [N][R], p3 = w2_b [R][K] */
+#define FLUXMI_DELTA_LOKR 2 /* p0 = w1 [N / kn][K / kk], p1 = w2 [kn][kk] */
+#define FLUXMI_DELTA_FULL 3 /* p0 = D [N][K] */
+#define FLUXMI_MAX_DELTA_TERMS 8
+typedef struct {
+  int kind, rank, n_chunks, kn, kk; /* rank, n_chunks: LORA / LOHA (n_chunks: LORA); kn, kk: LOKR */
+  float scale;
+  const float *p0, *p1, *p2, *p3;
+} fluxmi_delta_term_t;
+int fluxmi_adapter_fuse_f8(void* w_fp8, float* w_scale, float* w_scale_recip, const fluxmi_delta_term_t* terms, int n_terms, int N, int K,
+                           float* amax_tmp, void* stream);
+
 /* ---- block elementwise ----------------------------------------------------------------------------- */
 /* y = (1+scale)*LayerNorm(x)+shift (+fp8 quantise); rows [B][L], rows l<split use set 0   flux_model.py:367-368,389,469-470,501 */
 int fluxmi_ln_modulate(const void* x, long long ldx, void* out, long long ldo, const void* shift0, const void* scale0,

@@ -4,6 +4,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <cmath>
 
 #include <vector>
 
@@ -136,8 +137,8 @@ int fluxmi_lora_fuse_f8(void* w_fp8, float* w_scale, float* w_scale_recip, const
 
 // W' = requant( bf16( dequant(W) + sum_t d_t ) ) in place, no workspace (adapter_fuse.hip).  Everything is checked here, before any
 // launch: a refused call has done nothing.
-int fluxmi_adapter_fuse_f8(void* w_fp8, float* w_scale, float* w_scale_recip, const fluxmi_delta_term_t* terms, int n_terms, int N, int K,
-                           float* amax_tmp, void* stream) {
+static int adapter_fuse_check(const void* w_fp8, const float* w_scale, const float* w_scale_recip, const fluxmi_delta_term_t* terms, int n_terms,
+                             int N, int K, const float* amax_tmp) {
   FLUXMI_REQUIRE(n_terms >= 1 && n_terms <= FLUXMI_MAX_DELTA_TERMS, "adapter_fuse: n_terms=%d outside 1..%d", n_terms, FLUXMI_MAX_DELTA_TERMS);
   FLUXMI_REQUIRE(w_fp8 && w_scale && w_scale_recip && terms && amax_tmp, "adapter_fuse: null weight, scale, terms or amax_tmp pointer");
   FLUXMI_REQUIRE(N >= 1 && K >= 16 && K % 16 == 0, "adapter_fuse: N=%d must be >= 1 and K=%d a multiple of 16 (K %% 16 != 0)", N, K);
@@ -155,7 +156,29 @@ int fluxmi_adapter_fuse_f8(void* w_fp8, float* w_scale, float* w_scale_recip, co
       FLUXMI_REQUIRE(T.kn >= 1 && T.kk >= 1 && N % T.kn == 0 && K % T.kk == 0, "adapter_fuse: term %d: LOKR block kn=%d kk=%d must divide N=%d K=%d", t,
                      T.kn, T.kk, N, K);
   }
+  return 0;
+}
+int fluxmi_adapter_fuse_f8(void* w_fp8, float* w_scale, float* w_scale_recip, const fluxmi_delta_term_t* terms, int n_terms, int N, int K,
+                           float* amax_tmp, void* stream) {
+  FLUXMI_TRY(adapter_fuse_check(w_fp8, w_scale, w_scale_recip, terms, n_terms, N, K, amax_tmp));
   return fluxmi_k_adapter_fuse(w_fp8, w_scale, w_scale_recip, terms, n_terms, N, K, amax_tmp, (hipStream_t)stream);
+}
+
+// DoRA: W' = requant( bf16( a_i * dequant(W) + b_i * sum_t d_t ) ), (a_i, b_i) from the magnitude and the norm of W + sum_t d_t along `axis`
+// (APPLY), or from the inverse of the pair an APPLY left in `factors` (REMOVE).  Checked here, before any launch.
+long long fluxmi_adapter_dora_work_bytes(int N, int K, int axis) {
+  return N >= 1 && K >= 1 && (axis == 0 || axis == 1) ? fluxmi_k_adapter_dora_work_bytes(N, K, axis) : 0;
+}
+int fluxmi_adapter_fuse_dora_f8(void* w_fp8, float* w_scale, float* w_scale_recip, const fluxmi_delta_term_t* terms, int n_terms, int N, int K,
+                                int axis, const float* magnitude, float strength, int mode, float* factors, float* work, float* amax_tmp,
+                                void* stream) {
+  FLUXMI_TRY(adapter_fuse_check(w_fp8, w_scale, w_scale_recip, terms, n_terms, N, K, amax_tmp));
+  FLUXMI_REQUIRE(axis == 0 || axis == 1, "adapter_fuse_dora: axis=%d must be 0 (output rows) or 1 (input columns)", axis);
+  FLUXMI_REQUIRE(mode == FLUXMI_DORA_APPLY || mode == FLUXMI_DORA_REMOVE, "adapter_fuse_dora: unknown mode %d", mode);
+  FLUXMI_REQUIRE(factors && work && (magnitude || mode == FLUXMI_DORA_REMOVE), "adapter_fuse_dora: null magnitude, factors or work pointer");
+  FLUXMI_REQUIRE(std::isfinite(strength), "adapter_fuse_dora: strength must be finite");
+  return fluxmi_k_adapter_fuse_dora(w_fp8, w_scale, w_scale_recip, terms, n_terms, N, K, axis, magnitude, strength, mode == FLUXMI_DORA_REMOVE,
+                                    factors, work, amax_tmp, (hipStream_t)stream);
 }
 
 int fluxmi_ln_modulate(const void* x, long long ldx, void* out, long long ldo, const void* shift0, const void* scale0,

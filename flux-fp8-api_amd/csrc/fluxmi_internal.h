@@ -138,6 +138,11 @@ int fluxmi_k_axpy_f32(float* w, const float* d, float alpha, long long n, hipStr
 // adapter_fuse.hip: the two passes of fluxmi_adapter_fuse_f8 (terms already validated; amax_tmp: four floats)
 int fluxmi_k_adapter_fuse(void* w_fp8, float* w_scale, float* w_scale_recip, const fluxmi_delta_term_t* terms, int n_terms, int N, int K,
                           float* amax_tmp, hipStream_t s);
+// the passes of fluxmi_adapter_fuse_dora_f8 (everything already validated; remove: 0 APPLY writes factors, 1 REMOVE reads them)
+int fluxmi_k_adapter_fuse_dora(void* w_fp8, float* w_scale, float* w_scale_recip, const fluxmi_delta_term_t* terms, int n_terms, int N, int K,
+                               int axis, const float* magnitude, float strength, int remove, float* factors, float* work, float* amax_tmp,
+                               hipStream_t s);
+long long fluxmi_k_adapter_dora_work_bytes(int N, int K, int axis);
 int fluxmi_ln_pairs_ok(int H);  // elementwise.hip: fluxmi_k_ln_modulate can write the row-pair layout at this hidden size / ln_variant
 int fluxmi_k_ln_modulate(const void* x, long long ldx, long long x_bstride, void* out, long long ldo, long long out_bstride,
                          const void* shift0, const void* scale0, const void* shift1, const void* scale1, long long mod_bstride,

@@ -68,6 +68,7 @@ class DeltaTerm(C.Structure):
 
 DELTA_LORA, DELTA_LOHA, DELTA_LOKR, DELTA_FULL = range(4)
 MAX_DELTA_TERMS = 8
+DORA_APPLY, DORA_REMOVE = 0, 1
 
 _SIGS = {
     "fluxmi_abi_version": ([], i32),
@@ -85,6 +86,8 @@ _SIGS = {
     "fluxmi_quantize_weight": ([vp, vp, vp, vp, vp, i32, i32, i32, vp], i32),
     "fluxmi_lora_fuse_f8": ([vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp], i32),
     "fluxmi_adapter_fuse_f8": ([vp, vp, vp, C.POINTER(DeltaTerm), i32, i32, i32, vp, vp], i32),
+    "fluxmi_adapter_fuse_dora_f8": ([vp, vp, vp, C.POINTER(DeltaTerm), i32, i32, i32, i32, vp, f32, i32, vp, vp, vp, vp], i32),
+    "fluxmi_adapter_dora_work_bytes": ([i32, i32, i32], i64),
     "fluxmi_dequant": ([vp, vp, vp, i64, i32, vp], i32),
     "fluxmi_ln_modulate": ([vp, i64, vp, i64, vp, vp, vp, vp, i64, vp, vp, i32, i32, i32, i32, i32, i32, vp], i32),
     "fluxmi_ln_modulate_pairs": ([vp, i64, vp, i64, vp, vp, vp, vp, i64, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp], i32),

@@ -163,6 +163,42 @@ def adapter_fuse_f8(w8: torch.Tensor, w_scale: torch.Tensor, w_scale_recip: torc
     del keep  # (alive until the launches were queued; same stream, so the allocator cannot hand the factors out before they run)
 
 
+def _dora_call(w8, w_scale, w_scale_recip, terms, axis, magnitude, strength, mode, factors):
+    _req(w8, torch.float8_e4m3fn, "w8")
+    N, K = w8.shape
+    if axis not in (0, 1):
+        raise ValueError(f"fluxmi: DoRA axis {axis!r} must be 0 (one magnitude per output row) or 1 (one per input column)")
+    n = (N, K)[axis]
+    for name, t, shape in (("magnitude", magnitude, (n,)), ("factors", factors, (2, n))):
+        if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32 or t.device != w8.device or not t.is_contiguous()):
+            raise ValueError(f"fluxmi: DoRA {name} for a [{N}, {K}] weight on axis {axis} must be contiguous fp32 {shape} on {w8.device}")
+    if not w8.is_contiguous():
+        raise ValueError("fluxmi: adapter fuse needs a contiguous weight")
+    arr, keep = delta_terms(terms, N, K, w8.device)
+    work = torch.empty(max(_lib.lib.fluxmi_adapter_dora_work_bytes(N, K, axis) // 4, 1), dtype=torch.float32, device=w8.device)
+    tmp = torch.empty(4, dtype=torch.float32, device=w8.device)
+    call("fluxmi_adapter_fuse_dora_f8", _p(w8), _p(w_scale), _p(w_scale_recip), arr, len(terms), N, K, axis, _p(magnitude), float(strength), mode,
+         _p(factors), _p(work), _p(tmp), _stream())
+    del keep
+
+
+def adapter_fuse_dora_f8(w8: torch.Tensor, w_scale: torch.Tensor, w_scale_recip: torch.Tensor, terms: Sequence[Delta], magnitude: torch.Tensor,
+                         axis: int = 0, strength: float = 1.0) -> torch.Tensor:
+    """In-place DoRA fuse of an e4m3 weight: the delta terms of adapter_fuse_f8 and a magnitude vector ([N] for axis 0, [K] for axis 1), three
+    tile passes over the fp8 bytes and no fp32 copy of W (fluxmi_adapter_fuse_dora_f8; include/fluxmi.h states the arithmetic).  Returns the
+    factors [2, N or K] that adapter_unfuse_dora_f8 needs to take the adapter out again."""
+    magnitude = magnitude.to(device=w8.device, dtype=torch.float32).contiguous()
+    factors = torch.empty(2, w8.shape[axis] if axis in (0, 1) else 0, dtype=torch.float32, device=w8.device)
+    _dora_call(w8, w_scale, w_scale_recip, terms, axis, magnitude, strength, _lib.DORA_APPLY, factors)
+    return factors
+
+
+def adapter_unfuse_dora_f8(w8: torch.Tensor, w_scale: torch.Tensor, w_scale_recip: torch.Tensor, terms: Sequence[Delta], factors: torch.Tensor,
+                           axis: int = 0) -> None:
+    """The inverse of adapter_fuse_dora_f8 up to the fp8 re-quantisation: the same terms (at the same scales) and the factors it returned."""
+    _dora_call(w8, w_scale, w_scale_recip, terms, axis, None, 1.0, _lib.DORA_REMOVE, factors)
+
+
 # ---- linear ----------------------------------------------------------------------------------------
 def make_group(A, W, bias, sa_recip, sb_recip, Cout, M, lda, ldc, *, C2=None, ldc2=0, gate=None, resid=None, ldr=0,
                q_scale=None, split_n=0, c2_col0=0, vt_out=None, vt_ld=0, tok0=0, vt_rows=0, kv_col0=0, heads=0, k_out=None, pe=None,

@@ -9,7 +9,14 @@ libfluxmi (fluxmi_lora_fuse_f8).  Input scales are NOT recalibrated, exactly lik
 Beside plain LoRA a module may carry a LyCORIS LoHa (`hada_w1_a / hada_w1_b / hada_w2_a / hada_w2_b`), LoKr (`lokr_w1` or `lokr_w1_a` +
 `lokr_w1_b`, `lokr_w2` or `lokr_w2_a` + `lokr_w2_b`) or full delta (`diff`), each with `alpha`; these, and every load of several adapters at
 once, go through fluxmi_adapter_fuse_f8: all terms of a module in one pass over its fp8 bytes and ONE re-quantisation.  The reference has
-no counterpart.  Tucker factors and `diff_b` are refused by name, `dora_scale` is ignored with a warning.
+no counterpart.  Tucker factors and `diff_b` are refused by name.
+
+DoRA: a module that also carries `dora_scale` (shape [N, 1] or [N]: one magnitude per output row, axis 0; [1, K]: per input column, axis 1;
+anything else is refused by name) is not an additive delta.  The fuse path rescales every row or column of W + dW to its magnitude through
+fluxmi_adapter_fuse_dora_f8, in a call of its own, and keeps the factor pair of that call on the LoraWeights record (`.dora`): unloading
+inverts with the stored factors, "the same terms, scale negated" would be wrong.  DoRA does not commute with later fuses, so such an adapter
+unloads only as the most recently loaded one (check_unload_order).  get_adapter_for_key still returns the delta alone and warns about the
+magnitude it leaves out.  No real DoRA checkpoint has been available: the key layout is the public kohya / LyCORIS convention.
 
 Accepted inputs: a dict with BFL-dotted keys `<module>.lora_A.weight / .lora_B.weight / .alpha`
 (lora_loading.py:608-612 skips conversion for dicts), a LoraWeights, or a safetensors path holding such
@@ -44,6 +51,7 @@ class LoraWeights:  # reference lora_loading.py:21-32
         self.weights = weights
         self.name = name if name else path_regex.split(path)[-1]
         self.scale = scale
+        self.dora = {}  # module key -> (factors [2, N or K], axis) of the DoRA fuse that is in the weights now (fuse_adapters)
 
 
 def get_module_for_key(key: str, model) -> nn.Module:
@@ -195,11 +203,15 @@ def get_adapter_for_key(key: str, lora_weights: dict, device=None) -> Optional[o
     """The delta term of module `key` at adapter scale 1, or None when the dict holds no adapter for it.  Plain LoRA keeps the reference's
     arithmetic (alpha / rank folded into lora_A).  LoHa / LoKr / full deltas follow the LyCORIS key layout and ComfyUI's loading rule: the
     factor scale is alpha / rank when a decomposed factor gives a rank, else 1; decomposed LoKr factors are multiplied out here."""
+    if f"{key}.dora_scale" in lora_weights:
+        warnings.warn(f"adapter key {key}.dora_scale is ignored: DoRA is not supported, the module is fused without its magnitude vector")
+    return _delta_for_key(key, lora_weights, device)
+
+
+def _delta_for_key(key: str, lora_weights: dict, device=None) -> Optional[ops.Delta]:
     for leaf in _REFUSED_LEAVES:
         if f"{key}.{leaf}" in lora_weights:
             raise ValueError(f"adapter key {key}.{leaf}: Tucker-decomposed factors (hada_t1 / hada_t2 / lokr_t2) and bias deltas (diff_b) are not supported")
-    if f"{key}.dora_scale" in lora_weights:
-        warnings.warn(f"adapter key {key}.dora_scale is ignored: DoRA is not supported, the module is fused without its magnitude vector")
 
     def get(leaf):
         t = lora_weights.get(f"{key}.{leaf}")
@@ -227,6 +239,26 @@ def get_adapter_for_key(key: str, lora_weights: dict, device=None) -> Optional[o
     return None if diff is None else ops.Delta("full", (diff,), 1.0)
 
 
+def get_dora_for_key(key: str, lora_weights: dict, N: int, K: int, device=None):
+    """What the fuse path takes for module `key` ([N, K]): (delta at adapter scale 1, magnitude, axis); magnitude and axis are None for a module
+    without `dora_scale`.  [N, 1] or [N] is one magnitude per output row (axis 0, also a 1-D vector with N == K), [1, K] one per input column."""
+    d = _delta_for_key(key, lora_weights, device)
+    m = lora_weights.get(f"{key}.dora_scale")
+    if m is None:
+        return d, None, None
+    if d is None:
+        raise ValueError(f"adapter key {key}.dora_scale: a magnitude vector without a delta for its module")
+    shape = tuple(m.shape)
+    if shape in ((N, 1), (N,)):
+        axis = 0
+    elif shape == (1, K):
+        axis = 1
+    else:
+        raise ValueError(f"adapter key {key}.dora_scale: shape {list(shape)} is neither [{N}, 1] / [{N}] (one magnitude per output row) nor [1, {K}] "
+                         f"(one per input column) of the [{N}, {K}] weight")
+    return d, m.to(dtype=torch.float32, device=device).reshape(-1).contiguous(), axis
+
+
 @torch.inference_mode()
 def _fuse_terms(module: nn.Module, terms) -> None:
     """every term of one module in ONE re-quantisation (eight terms per call: FLUXMI_MAX_DELTA_TERMS)"""
@@ -242,26 +274,67 @@ def _fuse_terms(module: nn.Module, terms) -> None:
         module.weight.data = (w.float() + sum(d.dense() for d in terms)).to(w.dtype)
 
 
+@torch.inference_mode()
+def _fuse_dora(module: nn.Module, term, magnitude, axis: int, strength: float, factors=None):
+    """one DoRA call on one module: APPLY (factors None) -> the factor pair [2, N or K]; REMOVE with the pair an APPLY returned"""
+    if isinstance(module, F8Linear):
+        if factors is None:
+            return ops.adapter_fuse_dora_f8(module.float8_data, module.scale, module.scale_reciprocal, [term], magnitude, axis, strength)
+        ops.adapter_unfuse_dora_f8(module.float8_data, module.scale, module.scale_reciprocal, [term], factors, axis)
+        return factors
+    w, D = module.weight.data.float(), term.dense()  # un-quantised nn.Linear: include/fluxmi.h's formula as fp32 surgery (plumbing)
+    if factors is None:
+        b = strength * (magnitude / ((w + D).norm(dim=1 - axis) + 2.0 ** -23))
+        a, b = (1.0 - strength) + b, b
+        factors = torch.stack([a, b])
+    else:
+        a, b = 1.0 / factors[0], -(factors[1] / factors[0])
+    a, b = (a[:, None], b[:, None]) if axis == 0 else (a[None, :], b[None, :])
+    module.weight.data = (a * w + b * D).to(module.weight.dtype)
+    return factors
+
+
 def _module_device(module: nn.Module):
     return module.float8_data.device if isinstance(module, F8Linear) else module.weight.device
 
 
 @torch.inference_mode()
-def fuse_adapters(model, adapters) -> None:
-    """adapters: [(BFL-keyed weights, scale)].  Gathers, per module, the terms of every adapter and fuses them together."""
-    per_module = {}
-    for lora_weights, scale in adapters:
+def fuse_adapters(model, adapters, dora_remove=None):
+    """adapters: [(BFL-keyed weights, scale)].  Gathers, per module, the terms of every adapter and fuses them together: ONE re-quantisation
+    for the additive terms.  A module with a magnitude vector (DoRA) is fused in a call of its own, in adapter list order, with the adapter's
+    scale as the strength: DoRA does not add, so a list re-quantises such a module once per DoRA adapter, plus once for the additive terms on
+    either side of it.  Returns, per adapter, {module key: (factors, axis)} of its DoRA calls.  dora_remove (the same structure, or None per
+    adapter): the DoRA modules of that adapter are taken OUT with the stored factors instead (its additive modules take `scale` as given)."""
+    per_module, out = {}, [{} for _ in adapters]
+    for i, (lora_weights, scale) in enumerate(adapters):
         for key in _keys_without_ab(lora_weights):
             if get_lora_for_key(key, lora_weights) is None and not any(f"{key}.{leaf}" in lora_weights for leaf in _ADAPTER_LEAVES):
                 continue  # (before the module lookup: converted files carry keys of no module, as in the reference)
             module = get_module_for_key(key, model)
-            d = get_adapter_for_key(key, lora_weights, _module_device(module))
-            if d is not None:
-                per_module.setdefault(key, (module, []))[1].append(d.scaled(scale))
-    for module, terms in per_module.values():
-        _fuse_terms(module, terms)
+            N, K = (module.float8_data if isinstance(module, F8Linear) else module.weight).shape
+            d, magnitude, axis = get_dora_for_key(key, lora_weights, N, K, _module_device(module))
+            if d is None:
+                continue
+            calls = per_module.setdefault(key, (module, []))[1]
+            if magnitude is not None:
+                stored = (dora_remove[i] or {}).get(key) if dora_remove else None
+                if dora_remove and stored is None:
+                    raise ValueError(f"adapter key {key}.dora_scale: a DoRA module is taken out with the factors its fuse returned, and none are recorded")
+                calls.append((i, key, d, magnitude, axis, scale, stored))
+            elif calls and isinstance(calls[-1], list):
+                calls[-1].append(d.scaled(scale))
+            else:
+                calls.append([d.scaled(scale)])
+    for module, calls in per_module.values():
+        for call in calls:
+            if isinstance(call, list):
+                _fuse_terms(module, call)
+            else:
+                i, key, d, magnitude, axis, scale, stored = call
+                out[i][key] = (_fuse_dora(module, d, magnitude, axis, scale, None if stored is None else stored[0]), axis)
     if hasattr(model, "rebind_weights"):
         model.rebind_weights()
+    return out
 
 
 def _guidance(model) -> bool:
@@ -272,7 +345,9 @@ def _guidance(model) -> bool:
 def apply_lora_to_model(model, lora_path, lora_scale: float = 1.0, return_lora_resolved: bool = False):
     """reference lora_loading.py:634-693."""
     lora_weights, _ = _resolve(lora_path, _guidance(model))
-    fuse_adapters(model, [(lora_weights, lora_scale)])
+    dora = fuse_adapters(model, [(lora_weights, lora_scale)])[0]
+    if isinstance(lora_path, LoraWeights):
+        lora_path.dora = dora  # (a DoRA adapter unloads only through its record: remove_lora_from_module)
     if return_lora_resolved:
         return model, lora_weights
     return model
@@ -280,17 +355,43 @@ def apply_lora_to_model(model, lora_path, lora_scale: float = 1.0, return_lora_r
 
 @torch.inference_mode()
 def apply_loras_to_model(model, loras):
-    """loras: [(path or dict, scale)] -> the resolved weights of each, after ONE fuse per module over all of them"""
+    """loras: [(path, dict or LoraWeights, scale)] -> the resolved weights of each, after ONE fuse per module over all their additive terms
+    (fuse_adapters: DoRA modules take a call of their own; a LoraWeights member records their factors)"""
     resolved = [(_resolve(path, _guidance(model))[0], scale) for path, scale in loras]
-    fuse_adapters(model, resolved)
+    for (path, _), dora in zip(loras, fuse_adapters(model, resolved)):
+        if isinstance(path, LoraWeights):
+            path.dora = dora
     return [w for w, _ in resolved]
 
 
 @torch.inference_mode()
 def remove_lora_from_module(model, lora_path, lora_scale: float = 1.0):
-    """reference lora_loading.py:696-753: subtract the same delta and re-quantise (lossy through fp8, as there)."""
+    """reference lora_loading.py:696-753: subtract the same delta and re-quantise (lossy through fp8, as there).  The DoRA modules of a
+    LoraWeights record are inverted with the factors their fuse left on it; a stored factor a_i that is zero or not finite (a row scaled to
+    nothing cannot be scaled back) refuses the whole unload by name, before anything is touched: one device-to-host check."""
     lora_weights, stored_scale = _resolve(lora_path, _guidance(model))
     if stored_scale is not None:
         lora_scale = stored_scale
-    fuse_adapters(model, [(lora_weights, -lora_scale)])
+    dora = dict(getattr(lora_path, "dora", None) or {})
+    if dora:
+        bad = torch.stack([((f[0] == 0) | ~torch.isfinite(f[0])).any() for f, _ in dora.values()]).cpu()
+        if bool(bad.any()):
+            keys = [k for k, x in zip(dora, bad.tolist()) if x]
+            raise ValueError(f"unload of {getattr(lora_path, 'name', 'the adapter')!r}: the stored DoRA factors of {keys} hold a zero or non-finite "
+                             "scale, which has no inverse")
+    fuse_adapters(model, [(lora_weights, -lora_scale)], dora_remove=[dora])
+    if isinstance(lora_path, LoraWeights):
+        lora_path.dora = {}
     return model
+
+
+def check_unload_order(loras, idx: int) -> None:
+    """DoRA does not commute with later fuses: raises a ValueError that names the adapter to unload first when loras[idx] (a list of
+    LoraWeights in load order) is a DoRA adapter with anything loaded after it, or shares a module with a DoRA adapter loaded after it."""
+    rec, later = loras[idx], loras[idx + 1:]
+    if rec.dora and later:
+        raise ValueError(f"{rec.name!r} is a DoRA adapter and not the most recently loaded one: unload {later[-1].name!r} first")
+    mine = set(_keys_without_ab(rec.weights))
+    for other in reversed(later):
+        if other.dora and mine & set(_keys_without_ab(other.weights)):
+            raise ValueError(f"{rec.name!r} was loaded before the DoRA adapter {other.name!r}, which rescaled modules they share: unload {other.name!r} first")

@@ -704,40 +704,48 @@ class Flux(nn.Module):
         return self.get_lora(identifier) is not None
 
     def load_lora(self, path: str, scale: float, name: str = None):
-        from lora_loading import LoraWeights, apply_lora_to_model, remove_lora_from_module
+        """A DoRA file (modules with `dora_scale`) loads like any other; its record keeps the factors of every DoRA module (about 8 N bytes
+        each), which unload_lora and a load_lora at another scale need: both take the adapter out with them, under check_unload_order."""
+        from lora_loading import LoraWeights, _guidance, _resolve, apply_lora_to_model, check_unload_order, remove_lora_from_module
 
         if self.has_lora(path):
             lora = self.get_lora(path)
             if lora.scale != scale:
+                check_unload_order(self.loras, self.loras.index(lora))
                 remove_lora_from_module(self, lora, lora.scale)
-                apply_lora_to_model(self, lora, scale)
                 lora.scale = scale
+                apply_lora_to_model(self, lora, scale)
         else:
-            _, lora = apply_lora_to_model(self, path, scale, return_lora_resolved=True)
-            self.loras.append(LoraWeights(lora, path if isinstance(path, str) else (name or "lora"), name, scale))
+            lora = LoraWeights(_resolve(path, _guidance(self))[0], path if isinstance(path, str) else (name or "lora"), name, scale)
+            apply_lora_to_model(self, lora, scale)
+            self.loras.append(lora)
         self.rebind_weights()
 
     def load_loras(self, loras):
-        """loras: [(path or state dict, scale, name)].  Every module takes the terms of ALL the adapters in one fuse: one fp8 re-quantisation
-        per layer however many adapters there are (load_lora one by one re-quantises per adapter).  Each member is recorded, so
-        unload_lora(name) works as after load_lora."""
-        from lora_loading import LoraWeights, apply_loras_to_model
+        """loras: [(path or state dict, scale, name)].  Every module takes the additive terms of ALL the adapters in one fuse: one fp8
+        re-quantisation per layer however many adapters there are (load_lora one by one re-quantises per adapter).  DoRA does not add: a module
+        with a magnitude vector is fused in a call of its own, in list order, so it is re-quantised once per DoRA adapter plus once for the
+        additive terms on either side.  Each member is recorded, so unload_lora(name) works as after load_lora."""
+        from lora_loading import LoraWeights, _guidance, _resolve, apply_loras_to_model
 
         loras = [(path, scale, name) for path, scale, name in loras]
         for path, _, name in loras:
             if self.has_lora(path) or (name and self.has_lora(name)):
                 raise ValueError(f"load_loras: {name or path!r} is already loaded; unload it first or use load_lora to change its scale")
-        resolved = apply_loras_to_model(self, [(path, scale) for path, scale, _ in loras])
-        for (path, scale, name), weights in zip(loras, resolved):
-            self.loras.append(LoraWeights(weights, path if isinstance(path, str) else (name or "lora"), name, scale))
+        records = [LoraWeights(_resolve(path, _guidance(self))[0], path if isinstance(path, str) else (name or "lora"), name, scale) for path, scale, name in loras]
+        apply_loras_to_model(self, [(rec, rec.scale) for rec in records])
+        self.loras.extend(records)
         self.rebind_weights()
 
     def unload_lora(self, path_or_identifier: str):
-        from lora_loading import remove_lora_from_module
+        """Raises a ValueError naming the adapter to unload first, with nothing touched, when a DoRA adapter is not the most recently loaded
+        one or the adapter shares a module with a DoRA adapter loaded after it (DoRA does not commute with later fuses)."""
+        from lora_loading import check_unload_order, remove_lora_from_module
 
         for idx, lora_ in enumerate(list(self.loras)):
             if lora_.path == path_or_identifier or lora_.name == path_or_identifier:
-                remove_lora_from_module(self, lora_.weights, lora_.scale)
+                check_unload_order(self.loras, idx)
+                remove_lora_from_module(self, lora_, lora_.scale)
                 self.loras.pop(idx)
                 self.rebind_weights()
                 return True

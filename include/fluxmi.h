@@ -282,6 +282,30 @@ typedef struct {
 int fluxmi_adapter_fuse_f8(void* w_fp8, float* w_scale, float* w_scale_recip, const fluxmi_delta_term_t* terms, int n_terms, int N, int K,
                            float* amax_tmp, void* stream);
 
+/* DoRA fuse (Liu et al. 2024): the delta terms of fluxmi_adapter_fuse_f8 plus a learned magnitude vector m.  Not an additive delta: every
+ * row (axis 0: m has N entries, the norm runs over K) or column (axis 1: m has K entries, the norm runs over N) of W + sum_t d_t is rescaled
+ * to the magnitude m_i.  csrc/adapter_fuse.hip: APPLY is three tile passes over the fp8 bytes (NORM, MEASURE, WRITE), no fp32 copy of W.
+ *   w and every d_t exactly as fluxmi_adapter_fuse_f8;  D = d_0, D = fl(D + d_t) in term order;  v = fl(w + D)
+ *   ss_i = sum v^2 along the axis: fp32 inside a 128 x 128 tile in a fixed order (axis 0: a lane's eight columns ascending, then the row's 16
+ *          lanes as a butterfly; axis 1: a lane's four rows ascending, then the tile's 32 row groups ascending); each tile writes its partials
+ *          to work ([N][ceil(K / 128)] for axis 0, [ceil(N / 128)][K] for axis 1); the tiles are summed in fp64 by ascending tile index.  No
+ *          atomics: the result is a pure function of the input, run to run.
+ *   n_i = (float)sqrt(ss_i);  g_i = fl(m_i / fl(n_i + 2^-23));  b_i = fl(s * g_i);  a_i = fl(fl(1 - s) + b_i)          s: strength
+ *          W' = W + s (g (.) (W + dW) - W): ComfyUI's weight_decompose as far as it is known here, the paper's form at s = 1
+ *   out = bf16(fl(fl(a_i * w) + fl(b_i * D))): two products and one add, each rounded, never an fma; amax, the new scale pair and the e4m3
+ *          byte follow exactly as in fluxmi_adapter_fuse_f8 (NaN skipped, the same scale rule, the same final rounding)
+ * APPLY writes factors = [2][N or K] (a, then b).  REMOVE reads the pair an APPLY wrote and runs the same out formula with a'_i = fl(1 / a_i),
+ * b'_i = -fl(b_i / a_i), without a norm pass (magnitude, strength unused): the inverse of APPLY up to the fp8 re-quantisation.
+ * work: fluxmi_adapter_dora_work_bytes(N, K, axis) bytes (0 for a bad axis); amax_tmp: four floats.  Nothing outside the N * K weight bytes
+ * and those extents is written.  Refused by name before any launch: everything fluxmi_adapter_fuse_f8 refuses, an axis outside 0 / 1, a null
+ * magnitude (APPLY), factors or work, an unknown mode, a non-finite strength. */
+#define FLUXMI_DORA_APPLY 0
+#define FLUXMI_DORA_REMOVE 1
+long long fluxmi_adapter_dora_work_bytes(int N, int K, int axis);
+int fluxmi_adapter_fuse_dora_f8(void* w_fp8, float* w_scale, float* w_scale_recip, const fluxmi_delta_term_t* terms, int n_terms, int N, int K,
+                                int axis, const float* magnitude, float strength, int mode, float* factors, float* work, float* amax_tmp,
+                                void* stream);
+
 /* ---- block elementwise ----------------------------------------------------------------------------- */
 /* y = (1+scale)*LayerNorm(x)+shift (+fp8 quantise); rows [B][L], rows l<split use set 0   flux_model.py:367-368,389,469-470,501 */
 int fluxmi_ln_modulate(const void* x, long long ldx, void* out, long long ldo, const void* shift0, const void* scale0,

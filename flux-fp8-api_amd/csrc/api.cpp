@@ -269,6 +269,14 @@ int fluxmi_vae_attention(const void* q, const void* k, long long ld_qk, long lon
                          void* out, long long ld_out, long long bs_out, const void* v_bias, int D, int P, int Pp, int B, void* stream) {
   return fluxmi_k_vae_attention(q, k, ld_qk, bs_qk, vt, ld_vt, bs_vt, out, ld_out, bs_out, v_bias, D, P, Pp, B, (hipStream_t)stream);
 }
+int fluxmi_window_attention(const void* qkv, long long ld, const float* bias_table, void* out, long long ldo, int B, int H, int W, int heads,
+                            int shift, float scale, void* stream) {
+  return fluxmi_k_window_attention(qkv, ld, bias_table, out, ldo, B, H, W, heads, shift, scale, (hipStream_t)stream);
+}
+int fluxmi_channel_norm(const void* x, long long ldx, const void* weight, const void* bias, void* y, long long ldy, long long rows, int D,
+                        float eps, void* stream) {
+  return fluxmi_k_channel_norm(x, ldx, weight, bias, y, ldy, rows, D, eps, (hipStream_t)stream);
+}
 int fluxmi_conv3x3_dense(const void* x, long long ldx, int Cin, const void* w2, const void* bias, void* out, long long ldo, int Cout,
                          const void* r1, long long ldr1, float a1, const void* r2, long long ldr2, float a2, float slope, int act,
                          int upsample, int B, int H, int W, void* stream) {

@@ -999,7 +999,8 @@ class FluxPipeline:
         ControlNet, an IP-Adapter, `source_prompt`, `preview_every` > 0 and under a process group.  `tile_size=None`, or a tile of the
         request's size with no other tile argument, is today's request, launch for launch; `tile_overlap` / `tile_weight` without
         `tile_size` are refused.  Image quality on real FLUX weights is not established here; no tile size or overlap is recommended.
-        `upscale` / `init_upscale` (an ESRGAN-family RRDBNet, config.upscaler_path; modules/upscaler.py, FluxPipeline.upscale): with
+        `upscale` / `init_upscale` (config.upscaler_path: an ESRGAN-family RRDBNet, modules/upscaler.py, or a SwinIR "nearest+conv" x2 / x4
+        model, modules/swinir.py -- chosen by the file's keys; FluxPipeline.upscale): with
         `upscale=True` the request's uint8 pixels go through the network before they are returned or JPEG-encoded, so the result is
         `upscaler.scale` times `width` x `height` -- for every request kind that returns pixels, tiled and FlowEdit ones included; with
         `init_upscale=True` `init_image` goes through it before the resize to `width` x `height` that the request already does, e.g.
@@ -1869,8 +1870,8 @@ class FluxPipeline:
     # ---- super-resolution (modules/upscaler.RRDBNet on fluxmi_conv3x3_dense) ---------------------------------------------------------------
     def _require_upscaler(self):
         if getattr(self, "upscaler", None) is None:
-            raise ValueError("fluxmi: upscaling needs an ESRGAN-family checkpoint: set config.upscaler_path to a local RRDBNet .safetensors / "
-                             ".pth file (nothing is downloaded)")
+            raise ValueError("fluxmi: upscaling needs an ESRGAN-family (RRDBNet) or SwinIR checkpoint: set config.upscaler_path to a local "
+                             ".safetensors / .pth file of one of the two (nothing is downloaded)")
         return self.upscaler
 
     def upscale(self, image) -> torch.Tensor:

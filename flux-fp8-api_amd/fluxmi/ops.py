@@ -746,6 +746,57 @@ def vae_attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, P: int, v_
     return out
 
 
+WINDOW = 8            # include/fluxmi.h FLUXMI_WINDOW: the attention window's edge
+WINDOW_HEAD_PAD = 32  # the width every head is padded to in qkv and out
+
+
+def window_attention(qkv: torch.Tensor, bias_table: torch.Tensor, heads: int, shift: int, scale: float,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Swin's shifted-window attention in ONE launch (fluxmi_window_attention; include/fluxmi.h has the layout and the arithmetic).
+    qkv bf16 [B, H, W, 3 * heads * 32]: q | k | v per pixel, head h at columns h * 32 .. of each, narrower heads zero-padded (a column
+    window of a wider pixel buffer is fine); bias_table fp32 [225, heads]; shift 0 or 4; H, W multiples of 8.  -> out bf16
+    [B, H, W, heads * 32] (default: a new dense tensor; else a view under the same rule that does not overlap qkv)."""
+    _req(qkv, torch.bfloat16, "qkv")
+    _req(bias_table, torch.float32, "bias_table")
+    heads = int(heads)
+    Cw = heads * WINDOW_HEAD_PAD
+    if qkv.ndim != 4 or qkv.shape[3] != 3 * Cw:
+        raise ValueError(f"window_attention: qkv must be [B, H, W, 3 * heads * 32 = {3 * Cw}], got {tuple(qkv.shape)}")
+    B, H, W, _ = qkv.shape
+    if tuple(bias_table.shape) != ((2 * WINDOW - 1) ** 2, heads) or not bias_table.is_contiguous():
+        raise ValueError(f"window_attention: bias_table must be contiguous [{(2 * WINDOW - 1) ** 2}, heads = {heads}], got {tuple(bias_table.shape)}")
+    if out is None:
+        out = torch.empty((B, H, W, Cw), dtype=torch.bfloat16, device=qkv.device)
+    _req(out, torch.bfloat16, "out")
+    if tuple(out.shape) != (B, H, W, Cw):
+        raise ValueError(f"window_attention: out must be {(B, H, W, Cw)}, got {tuple(out.shape)}")
+    ld, ldo = _depth_pixels(qkv, "window_attention", "qkv"), _depth_pixels(out, "window_attention", "out")
+    call("fluxmi_window_attention", _p(qkv), ld, _p(bias_table), _p(out), ldo, B, H, W, heads, int(shift), float(scale), _stream())
+    return out
+
+
+def channel_norm(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, D: int, eps: float = 1e-5,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """LayerNorm over the first D channels of padded rows (fluxmi_channel_norm): x bf16 [rows, >= D8] with row stride % 8 == 0, D8 = D
+    rounded up to 8, any D in 1..512; weight, bias bf16 [D8], zero past D.  -> out (default: zeros of x's shape) with columns [0, D8)
+    written, the ones past D as zeros."""
+    _req(x, torch.bfloat16, "x")
+    _req(weight, torch.bfloat16, "weight")
+    _req(bias, torch.bfloat16, "bias")
+    D8 = (int(D) + 7) // 8 * 8
+    if x.ndim != 2 or x.stride(1) != 1 or x.shape[1] < D8:
+        raise ValueError(f"channel_norm: x must be [rows, >= {D8}] with unit column stride, got {tuple(x.shape)} / {x.stride()}")
+    if weight.numel() != D8 or bias.numel() != D8 or not weight.is_contiguous() or not bias.is_contiguous():
+        raise ValueError(f"channel_norm: weight and bias need D8 = {D8} contiguous entries")
+    if out is None:
+        out = torch.zeros(x.shape, dtype=torch.bfloat16, device=x.device)
+    _req(out, torch.bfloat16, "out")
+    if out.ndim != 2 or out.stride(1) != 1 or out.shape[0] != x.shape[0] or out.shape[1] < D8:
+        raise ValueError(f"channel_norm: out must be [{x.shape[0]}, >= {D8}] with unit column stride, got {tuple(out.shape)}")
+    call("fluxmi_channel_norm", _p(x), x.stride(0), _p(weight), _p(bias), _p(out), out.stride(0), x.shape[0], int(D), float(eps), _stream())
+    return out
+
+
 def patchify(pix: torch.Tensor, patch: int, grid: int, k_pad: int) -> torch.Tensor:
     """pix bf16 [B, C, H, W] -> patch rows [B*grid*grid, k_pad], column order (c, ky, kx), zero past C*patch*patch (fluxmi_patchify)."""
     _req(pix, torch.bfloat16, "pix")

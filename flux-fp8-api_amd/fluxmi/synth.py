@@ -306,3 +306,56 @@ def make_depth_anything_state_dict(config: dict, seed: int = 0, dtype=torch.floa
     sd["head.conv3.weight"] = (torch.rand(1, Hh, 1, 1, generator=gen) * (2.0 / Hh)).to(dtype)
     sd["head.conv3.bias"] = torch.full((1,), 0.25, dtype=dtype)
     return sd
+
+
+def make_swinir_state_dict(embed_dim: int = 60, depths=(2, 2), heads=(2, 2), mlp_ratio: float = 2.0, resi: str = "1conv", scale: int = 4,
+                           num_feat: int = 64, seed: int = 0, wrap: str | None = None) -> Dict[str, torch.Tensor]:
+    """A seeded SwinIR "nearest+conv" checkpoint (modules/swinir.py) in KAIR's key layout for tests and tools: fp32 tensors that hold bf16
+    values.  Linear weights N(0, 1 / fan_in), convolutions N(0, 1 / (9 Cin)), LayerNorm weights 1 + N(0, 0.1), biases N(0, 0.1), bias
+    tables N(0, 0.5): activations stay O(1) and the logits within a few units, so no branch can be ignored by a test.  The
+    relative_position_index buffer the loaders ignore is included, as a real file has it.  SwinIR-M x4 is (180, (6,) * 6, (6,) * 6, 2.0,
+    "1conv"), SwinIR-L (240, (6,) * 9, (8,) * 9, 2.0, "3conv").  `wrap`: "params_ema" / "params" nests the dict as BasicSR saves it."""
+    if scale not in (2, 4) or resi not in ("1conv", "3conv") or len(depths) != len(heads):
+        raise ValueError("make_swinir_state_dict: scale 2 / 4, resi '1conv' / '3conv', one head count per layer")
+    gen = torch.Generator().manual_seed(3000 + seed)
+    C, hidden = embed_dim, int(embed_dim * mlp_ratio)
+    sd: Dict[str, torch.Tensor] = {}
+    rn = lambda *shape, std=1.0: (std * torch.randn(*shape, generator=gen)).bfloat16().float()  # noqa: E731
+
+    def conv(name, co, ci, k=3):
+        sd[name + ".weight"], sd[name + ".bias"] = rn(co, ci, k, k, std=1.0 / math.sqrt(k * k * ci)), rn(co, std=0.1)
+
+    def linear(name, co, ci):
+        sd[name + ".weight"], sd[name + ".bias"] = rn(co, ci, std=1.0 / math.sqrt(ci)), rn(co, std=0.1)
+
+    def norm(name):
+        sd[name + ".weight"], sd[name + ".bias"] = (1.0 + rn(C, std=0.1)).bfloat16().float(), rn(C, std=0.1)
+
+    def body_conv(name):
+        if resi == "1conv":
+            conv(name, C, C)
+        else:
+            conv(name + ".0", C // 4, C), conv(name + ".2", C // 4, C // 4, 1), conv(name + ".4", C, C // 4)
+
+    conv("conv_first", C, 3)
+    norm("patch_embed.norm")
+    co = torch.stack(torch.meshgrid(torch.arange(8), torch.arange(8), indexing="ij")).flatten(1)
+    rel = (co[:, :, None] - co[:, None, :]).permute(1, 2, 0) + 7
+    for i, (d, h) in enumerate(zip(depths, heads)):
+        for j in range(d):
+            p = f"layers.{i}.residual_group.blocks.{j}."
+            norm(p + "norm1")
+            sd[p + "attn.relative_position_bias_table"] = rn(225, h, std=0.5)
+            sd[p + "attn.relative_position_index"] = rel[..., 0] * 15 + rel[..., 1]
+            linear(p + "attn.qkv", 3 * C, C), linear(p + "attn.proj", C, C)
+            norm(p + "norm2")
+            linear(p + "mlp.fc1", hidden, C), linear(p + "mlp.fc2", C, hidden)
+        body_conv(f"layers.{i}.conv")
+    norm("norm")
+    body_conv("conv_after_body")
+    conv("conv_before_upsample.0", num_feat, C)
+    for n in ("conv_up1", "conv_up2", "conv_hr"):
+        if n != "conv_up2" or scale == 4:
+            conv(n, num_feat, num_feat)
+    conv("conv_last", 3, num_feat)
+    return {wrap: sd} if wrap else sd

@@ -224,8 +224,9 @@ class RRDBNet:
         return y.float().clamp(0.0, 1.0).mul(255.0).round().to(torch.uint8).contiguous()
 
 
-def read_upscaler(path: str, device="cuda:0") -> RRDBNet:
-    """a LOCAL .safetensors or .pth (torch.load(weights_only=True)) file -> RRDBNet; nothing is downloaded"""
+def read_upscaler(path: str, device="cuda:0"):
+    """a LOCAL .safetensors or .pth (torch.load(weights_only=True)) file -> RRDBNet, or modules.swinir.SwinIR when the keys are a Swin
+    transformer's (which refuses Swin2SR / HAT and the SwinIR variants it does not cover by name); nothing is downloaded"""
     if str(path).endswith(".safetensors"):
         from safetensors.torch import load_file
 
@@ -234,4 +235,8 @@ def read_upscaler(path: str, device="cuda:0") -> RRDBNet:
         sd = torch.load(str(path), map_location="cpu", weights_only=True)
     if not isinstance(sd, dict):
         raise UpscalerFormatError(f"upscaler: {path} does not hold a state dict")
+    from modules import swinir
+
+    if swinir.is_swin_family(sd):
+        return swinir.SwinIR(sd, device=device)
     return RRDBNet(sd, device=device)

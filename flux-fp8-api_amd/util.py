@@ -85,7 +85,8 @@ class ModelSpec(BaseModel):  # reference util.py:38-79 (unknown JSON keys are ig
     # "streaming" (fluxmi_vae_attention: one launch, no score matrix; what a tiled 2048 x 2048 request needs to be decoded)
     vae_attention: str = "gemm"
     # an ESRGAN-family super-resolution network (RRDBNet: ESRGAN, Real-ESRGAN x4plus / x2plus, 4x-UltraSharp ...; modules/upscaler.py): a
-    # LOCAL .safetensors or .pth file.  Nothing is downloaded; FluxPipeline.upscaler is None unless the file exists
+    # LOCAL .safetensors or .pth file, or a SwinIR "nearest+conv" x2 / x4 model (the real-world SwinIR-M / L; modules/swinir.py), told apart
+    # by the keys.  Nothing is downloaded; FluxPipeline.upscaler is None unless the file exists
     upscaler_path: str | None = None
     # the Depth Anything depth estimator of control_preprocess="depth_anything" (modules/depth.py): a LOCAL directory in the HF layout
     # (config.json + model.safetensors / *.bin of DepthAnythingForDepthEstimation, e.g. a copy of LiheYoung/depth-anything-large-hf).
@@ -406,8 +407,8 @@ def load_ip_adapter(config: ModelSpec, device=None):
 
 
 def load_upscaler(config: ModelSpec, device=None):
-    """The RRDBNet of config.upscaler_path (modules/upscaler.RRDBNet) on `device`, or None unless the path is a local file.  Nothing is
-    downloaded.  A checkpoint of another architecture is refused by name (modules.upscaler.normalize_state_dict)."""
+    """The network of config.upscaler_path on `device` -- modules/upscaler.RRDBNet or modules/swinir.SwinIR, by the file's keys -- or None
+    unless the path is a local file.  Nothing is downloaded.  A checkpoint of another architecture is refused by name."""
     import os
 
     path = getattr(config, "upscaler_path", None)

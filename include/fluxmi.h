@@ -487,6 +487,40 @@ int fluxmi_vae_attention(const void* q, const void* k, long long ld_qk, long lon
 int fluxmi_conv3x3_dense(const void* x, long long ldx, int Cin, const void* w2, const void* bias, void* out, long long ldo, int Cout,
                          const void* r1, long long ldr1, float a1, const void* r2, long long ldr2, float a2, float slope, int act,
                          int upsample, int B, int H, int W, void* stream);
+/* Shifted-window attention with a 2-D relative-position bias: the core of SwinIR's block (modules/swinir.py; csrc/window_attention.hip),
+ * window FLUXMI_WINDOW = 8 (64 tokens), heads padded to 32 columns.  ONE launch does, for all images, windows and heads, what Swin's
+ * roll -> window_partition -> WindowAttention core -> window_reverse -> roll back does: the partition, both rolls and the reverse are address
+ * arithmetic; no [N, N] score matrix and no permuted copy reaches memory.
+ *   qkv         bf16 [B][H][W] pixels, pixel stride ld elements.  Each pixel holds q | k | v, each heads * 32 columns wide, head h at columns
+ *               h * 32 ..; a head narrower than 32 (SwinIR: 30) is followed by zeros -- the caller permutes and zero-pads the rows of the
+ *               fused qkv weight and bias, the kernel never sees an unpadded head
+ *   bias_table  fp32 [(2 * 8 - 1)^2 = 225][heads]
+ *   out         bf16 [B][H][W] pixels, pixel stride ldo; heads * 32 columns are written per pixel (a head's pad columns as zero) and NOTHING else
+ *   shift       0 or 4;  scale fp32;  H, W multiples of 8
+ * Rolled coordinates: rolled pixel (i, j) is source pixel ((i + shift) mod H, (j + shift) mod W).  Window (wy, wx) holds rolled pixels
+ * 8 wy .. 8 wy + 7, 8 wx .. 8 wx + 7, tokens in row-major order; the result for a rolled pixel is stored at its source pixel.
+ * Bias: for query token (ya, xa) and key token (yb, xb) of a window, bias = bias_table[(ya - yb + 7) * 15 + (xa - xb + 7)][h].
+ * Shift mask, only when shift > 0: the region of a rolled row i is 0 if i < H - 8, 1 if i < H - 4, else 2; columns use W the same way; a
+ * pixel's id is 3 * row_region + col_region, and a (query, key) pair with different ids gets -100 ADDED to its logit (the model's constant,
+ * not -inf).  H = 8 or W = 8 is no special case of that rule.
+ * Arithmetic:  s = fp32 MFMA sum of the bf16 products q . k over the 32 columns;  t = s * scale + bias (+ -100) in fp32;  m = max_j t, exact
+ * (the whole 64-key row is in registers: no running maximum);  p = exp(t - m) and l = sum p in fp32;  O = sum bf16(p) v on the matrix pipe
+ * with fp32 accumulation;  out = bf16(O / l) -- the only rounding of the output.
+ * Deterministic (no atomics, fixed summation order); a sample's bits depend on that sample alone.  All address arithmetic is 64-bit.
+ * Returns non-zero before any launch (text in fluxmi_last_error) for: H or W not a positive multiple of 8; shift other than 0 / 4; heads
+ * outside 1..16; B above 65535 or more than 2^31 - 1 windows per image (the launch grid); a stride that is no multiple of 8 or shorter than
+ * its columns (3 * heads * 32, heads * 32); qkv or out not 16-byte aligned; out overlapping qkv. */
+#define FLUXMI_WINDOW 8
+int fluxmi_window_attention(const void* qkv, long long ld, const float* bias_table, void* out, long long ldo, int B, int H, int W, int heads,
+                            int shift, float scale, void* stream);
+/* LayerNorm over the first D channels of `rows` padded pixel rows, for a D that is no multiple of 8 (SwinIR's 180 / 60; fluxmi_row_norm
+ * needs D %% 8 == 0):  y[r][c] = bf16((x[r][c] - mean_r) * rstd_r * weight[c] + bias[c]) for c < D, mean and the centred variance in fp32
+ * over channels < D only, rstd = 1 / sqrt(var + eps); the columns [D, D8), D8 = D rounded up to 8, are stored as zeros and nothing past D8
+ * is read or written.  x, y bf16 with row strides ldx, ldy (multiples of 8, >= D8); weight, bias bf16 [D8].  D in 1..512.  Deterministic;
+ * a row's bits depend on that row alone.  Returns non-zero before any launch for a D outside 1..512, a stride that is no multiple of 8 or
+ * shorter than D8, or a pointer that is not 16-byte aligned. */
+int fluxmi_channel_norm(const void* x, long long ldx, const void* weight, const void* bias, void* y, long long ldy, long long rows, int D,
+                        float eps, void* stream);
 /* Patch rows of a stride-`patch` "valid" convolution: pix bf16 [B, C, H, W] (NCHW, contiguous) -> out bf16 [B*grid*grid, Kp], row
  * (b, gy, gx), column c*patch*patch + ky*patch + kx (the order of a Conv2d weight [N, C, patch, patch] flattened), columns >= C*patch*patch
  * zero.  Pixels past grid*patch are not read.  Kp %% 8 == 0; grid*patch <= H, W.  SigLIP-so400m: C 3, patch 14, grid 27, Kp 640. */

@@ -39,6 +39,8 @@ Same two POST endpoints, request fields, defaults and status codes:
              image_resize=None ("pil" | "native") -- who resizes the request's images: Pillow on the host, or the native resampler on the
              device (the same bytes); passed on only when set, and unset means the config JSON's "image_resize" ("pil" unless given there);
              stream=None, preview_every=None (>= 0) -- progress, live previews and cancellation, see below;
+             decoder=None ("vae" | "tiny": who decodes the final latents), preview_decoder=None ("latent" | "tiny": what the previews
+             are; "tiny" = the estimate through the tiny autoencoder of config.tiny_ae_path at full resolution) -- each passed on only when set;
              a region with both or neither of box / mask, or a box outside 0 <= x0 < x1 <= 1, is a 422}
              ->  image/jpeg stream of FluxPipeline.generate(**args)                                               (reference api.py:54-86)
              With stream=true the response is application/x-ndjson instead, one JSON object per line: for every model evaluation
@@ -168,6 +170,12 @@ class GenerateArgs(BaseModel):
     # who resizes the request's images (Kontext reference, control / ControlNet image, the photo of control_preprocess): "pil" (Pillow on the
     # host) or "native" (fluxmi.ops.resize_u8 on the device: the same bytes); unset = the configuration's image_resize ("pil" unless set there)
     image_resize: Optional[Literal["pil", "native"]] = None
+    # who decodes the final latents: "vae" (the autoencoder) or "tiny" (the TAEF1 decoder of config.tiny_ae_path: a fast approximate decode);
+    # unset = "vae", the request as ever
+    decoder: Optional[Literal["vae", "tiny"]] = None
+    # what a streamed request's previews are: "latent" (the projection at latent resolution) or "tiny" (the estimate through the tiny
+    # decoder, at full resolution; needs preview_every > 0); unset = "latent"
+    preview_decoder: Optional[Literal["latent", "tiny"]] = None
     stream: Optional[bool] = None  # answer with application/x-ndjson progress lines and a final result line instead of the JPEG
     preview_every: Optional[int] = Field(default=None, ge=0)  # ... with a latent-resolution preview at every k-th model evaluation (0 = none)
 
@@ -251,7 +259,7 @@ def generate(args: GenerateArgs):
               "negative_ip_adapter_image", "negative_ip_adapter_scale", "guidance_mode", "guidance_rescale", "apg_eta", "apg_norm_threshold",
               "apg_momentum", "zero_init_steps", "source_prompt", "source_guidance", "edit_n_max", "edit_n_min", "edit_n_avg", "tile_size",
               "tile_overlap", "tile_weight", "control_preprocess", "canny_low", "canny_high", "canny_l2", "blur_sigma", "depth_resolution",
-              "depth_normalize", "jpeg_encoder", "image_resize", "output_type", "png_encoder"):
+              "depth_normalize", "jpeg_encoder", "image_resize", "output_type", "png_encoder", "decoder", "preview_decoder"):
         if kwargs.get(k) is None:
             kwargs.pop(k, None)
     for k in ("upscale", "init_upscale"):  # passed on only when asked for

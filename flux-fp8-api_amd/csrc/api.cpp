@@ -282,6 +282,10 @@ int fluxmi_conv3x3_dense(const void* x, long long ldx, int Cin, const void* w2, 
                          int upsample, int B, int H, int W, void* stream) {
   return fluxmi_k_conv3x3_dense(x, ldx, Cin, w2, bias, out, ldo, Cout, r1, ldr1, a1, r2, ldr2, a2, slope, act, upsample, B, H, W, (hipStream_t)stream);
 }
+int fluxmi_conv3x3_block(const void* x, long long ldx, const void* w, const void* bias, void* out, long long ldo, int B, int H, int W,
+                         void* stream) {
+  return fluxmi_k_conv3x3_block(x, ldx, w, bias, out, ldo, B, H, W, (hipStream_t)stream);
+}
 int fluxmi_canny_classify(const void* rgb, long long ld, long long bs, void* state, long long state_ld, long long state_bs, int B, int H, int W,
                           int low, int high, int l2, void* stream) {
   return fluxmi_k_canny_classify(rgb, ld, bs, state, state_ld, state_bs, B, H, W, low, high, l2, (hipStream_t)stream);
@@ -489,6 +493,12 @@ int fluxmi_latent_preview(const void* x, const void* pred, const float* ts, cons
                           const int* ctl, void* out, int B, long long img_rows, long long pred_rows, int c_in, int c_out, int h, int w,
                           void* stream) {
   return fluxmi_k_latent_preview(x, pred, ts, step, scale, proj, ctl, out, B, img_rows, pred_rows, c_in, c_out, h, w, (hipStream_t)stream);
+}
+int fluxmi_latent_preview_x0(const void* x, const void* pred, const float* ts, const int* step, const float* scale, const float* proj,
+                             const int* ctl, void* out, void* x0_out, int B, long long img_rows, long long pred_rows, int c_in, int c_out,
+                             int h, int w, void* stream) {
+  return fluxmi_k_latent_preview_x0(x, pred, ts, step, scale, proj, ctl, out, x0_out, B, img_rows, pred_rows, c_in, c_out, h, w,
+                                    (hipStream_t)stream);
 }
 int fluxmi_ip_attention(const void* qkv, long long ld_qkv, long long qkv_bstride, const void* qn_scale, const void* k_ip, const void* v_ip,
                         long long kv_bstride, void* out, long long ld_o, long long o_bstride, const float* scale, long long scale_bstride, int B,

@@ -163,6 +163,7 @@ void step_key(const E* e, const Request& rq, StepKey& k) {
   k.shaped = rq.shaped;
   k.previewed = rq.previewed;
   if (rq.previewed) { k.pv_h = e->pv_h; k.pv_w = e->pv_w; }
+  if (rq.previewed && e->pv_x0) k.pv_x0 = e->side[SB_PV_X0].p;
   k.cn = e->cn;
   if (e->cn) k.cn_gen = e->cn->ws_gen;
   if (e->ip_on && e->side[SB_IP].p) {
@@ -331,7 +332,11 @@ int update_launch(E* e, const Request& rq, hipStream_t st) {
     FLUXMI_TRY(fluxmi_k_guidance_combine(pred_s, buf<float>(e, "gd_r"), buf<float>(e, "gd_part"), gp, e->d_step, (const int*)(gp + 8),
                                          buf<float>(e, "gd_coef"), rq.images, n_pred, st));
   }
-  if (rq.previewed)
+  if (rq.previewed && e->pv_x0)
+    FLUXMI_TRY(fluxmi_k_latent_preview_x0(img_s, pred_s, e->d_ts, e->d_step, scale, buf<float>(e, "pv_proj"), buf<int>(e, "pv_ctl"),
+                                          buf<unsigned char>(e, "pv_out"), e->side[SB_PV_X0].p, rq.images, Li, e->Lpred, C, Co, e->pv_h,
+                                          e->pv_w, st));
+  else if (rq.previewed)
     FLUXMI_TRY(fluxmi_k_latent_preview(img_s, pred_s, e->d_ts, e->d_step, scale, buf<float>(e, "pv_proj"), buf<int>(e, "pv_ctl"),
                                        buf<unsigned char>(e, "pv_out"), rq.images, Li, e->Lpred, C, Co, e->pv_h, e->pv_w, st));
   const u16 *ix0 = e->inp_on ? buf<u16>(e, "inp_x0") : nullptr, *inoise = e->inp_on ? buf<u16>(e, "inp_noise") : nullptr;
@@ -1054,6 +1059,7 @@ int fluxmi_engine_set_guidance(fluxmi_engine_t* e, const float* params_host, int
 int fluxmi_engine_set_preview(fluxmi_engine_t* e, const float* proj51_host, int h, int w, int every, int eval_offset, int n_evaluations,
                               fluxmi_step_hook_t hook, void* user) {
   FLUXMI_REQUIRE(e, "engine_set_preview: NULL engine");
+  e->pv_x0 = false;
   if (!hook) {
     e->pv_hook = nullptr; e->pv_user = nullptr; e->pv_every = 0;
     return 0;
@@ -1088,6 +1094,17 @@ int fluxmi_engine_set_preview(fluxmi_engine_t* e, const float* proj51_host, int 
   e->pv_n = n_evaluations;
   e->pv_hook = hook;
   e->pv_user = user;
+  return 0;
+}
+
+// The previewed step of the state just set also keeps its estimate (fluxmi.h): the ring is a side allocation of the prepared shape.
+int fluxmi_engine_set_preview_latents(fluxmi_engine_t* e, int on) {
+  FLUXMI_REQUIRE(e, "engine_set_preview_latents: NULL engine");
+  FLUXMI_REQUIRE(!on || (e->pv_hook && e->pv_every > 0), "engine_set_preview_latents: call fluxmi_engine_set_preview with a hook and every > 0 first");
+  if (on)
+    FLUXMI_TRY(e->side[SB_PV_X0].ensure(e, {{"preview_x0", (size_t)FLUXMI_PREVIEW_SLOTS * e->B * e->Lpred * 64 * 2}}, false, nullptr,
+                                        "engine_set_preview_latents", " (preview estimates)"));
+  e->pv_x0 = on != 0;
   return 0;
 }
 

@@ -36,6 +36,7 @@ struct StepKey {
   bool shaped;     // guidance shaping (fluxmi_engine_set_guidance) on a guided call: two launches in front of the guided update; mode and values are device data
   bool previewed;  // the preview launch in front of the update (fluxmi_engine_set_preview, every > 0): cadence, offset and factors are device data ...
   int pv_h, pv_w;  // ... the token grid is a launch argument (zero unless previewed)
+  const void* pv_x0;  // ... and the estimate ring of fluxmi_engine_set_preview_latents: the launch takes its _x0 form (null: the plain form)
   const void* cn;  // the attached ControlNet whose launches (and workspace pointers) are baked into the pieces, or none ...
   unsigned long long cn_gen;  // ... and the generation of its workspace / weight binding: process-wide unique, so a net created at a freed net's address never matches
   const void* ip;  // the IP-Adapter's K / V buffer baked into the pieces (null: no adapter launches), its Nk ...
@@ -73,7 +74,7 @@ struct SideBuf {
   void drop(E* e);  // frees the memory and erases its names
 };
 // (the comments beside the engine's feature state say what each one holds)
-enum { SB_FB = 0, SB_INP, SB_SOL, SB_SOL_IDS, SB_GD, SB_PV, SB_FE, SB_FE_Z, SB_FE_ACC, SB_WIN, SB_IP, SB_COUNT };
+enum { SB_FB = 0, SB_INP, SB_SOL, SB_SOL_IDS, SB_GD, SB_PV, SB_FE, SB_FE_Z, SB_FE_ACC, SB_WIN, SB_IP, SB_PV_X0, SB_COUNT };
 
 // FlowEdit's device tables, the workspace buffer "fe_tab": the program's rows, then the noise ids of the B / 2 images with the evaluation
 // offset behind them (one copy).  Staged through SchedStaging::fe, which is the same layout.
@@ -255,6 +256,7 @@ struct fluxmi_engine {
   fluxmi_step_hook_t pv_hook = nullptr;
   void* pv_user = nullptr;
   int pv_every = 0, pv_offset = 0, pv_n = 0, pv_h = 0, pv_w = 0;
+  bool pv_x0 = false;  // fluxmi_engine_set_preview_latents: the previewed step also keeps bf16 x0 in "preview_x0" (SB_PV_X0); every set_preview clears it
   float pv_proj[51];
   unsigned char* pv_host = nullptr;
   size_t pv_host_bytes = 0;

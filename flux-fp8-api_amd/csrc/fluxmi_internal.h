@@ -226,6 +226,9 @@ int fluxmi_k_guidance_combine(void* pred, float* r, const float* part, const flo
 int fluxmi_k_latent_preview(const void* x, const void* pred, const float* ts, const int* step, const float* scale, const float* proj,
                             const int* ctl, void* out, int B, long long img_rows, long long pred_rows, int c_in, int c_out, int h, int w,
                             hipStream_t s);
+int fluxmi_k_latent_preview_x0(const void* x, const void* pred, const float* ts, const int* step, const float* scale, const float* proj,
+                               const int* ctl, void* out, void* x0_out, int B, long long img_rows, long long pred_rows, int c_in, int c_out,
+                               int h, int w, hipStream_t s);
 // ControlNet residual hand-over: x[b, j] = bf16(x[b, j] + bf16(r[b, j] * *s_dev)), B samples of n elements, batch strides in elements
 int fluxmi_k_add_scaled(void* x, long long x_bstride, const void* r, long long r_bstride, const float* s_dev, int B, long long n, hipStream_t s);
 // IP-Adapter term of a double block (ip_attention.hip; include/fluxmi.h, fluxmi_ip_attention): scale == NULL writes o, else x += bf16(o * scale[b])
@@ -254,6 +257,8 @@ int fluxmi_k_channel_norm(const void* x, long long ldx, const void* weight, cons
 int fluxmi_k_conv3x3_dense(const void* x, long long ldx, int Cin, const void* w2, const void* bias, void* out, long long ldo, int Cout,
                            const void* r1, long long ldr1, float a1, const void* r2, long long ldr2, float a2, float slope, int act,
                            int upsample, int B, int H, int W, hipStream_t s);
+int fluxmi_k_conv3x3_block(const void* x, long long ldx, const void* w, const void* bias, void* out, long long ldo, int B, int H, int W,
+                           hipStream_t s);
 // control-map preprocessors (preprocess.hip; include/fluxmi.h, fluxmi_canny* / fluxmi_rgb_to_gray / fluxmi_gaussian_blur): uint8 NHWC images with
 // row and image strides in bytes
 int fluxmi_k_canny_classify(const void* rgb, long long ld, long long bs, void* state, long long sld, long long sbs, int B, int H, int W,

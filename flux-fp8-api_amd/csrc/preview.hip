@@ -8,17 +8,20 @@
 // One thread per token: the token's 64 stepped channels are 128 contiguous bytes of x and of pred -- eight 16-byte loads each, every thread a
 // whole line -- and its four pixels are two runs of six bytes.  No LDS, no atomics; ~1 MB of traffic per image at 1024^2, so the kernel is
 // launch-latency sized like euler_kernel.
+//
+// X0 (fluxmi_latent_preview_x0): the same kernel also stores bf16(x0_c) of the token's 64 packed columns -- eight 16-byte stores -- into the
+// same slot of a second ring, for a decoder that wants the estimate itself (the tiny autoencoder's previews).  The RGB code is shared.
 #include "common.h"
 #include "fluxmi_internal.h"
 
 namespace {
 // vector j of a token holds packed columns 8 j .. 8 j + 7 = latent channels 2 j and 2 j + 1, each with its four sub-pixels (column c * 4 + sub)
-template <bool GUIDED>
+template <bool GUIDED, bool X0>
 __global__ void __launch_bounds__(256) latent_preview_kernel(const u16* __restrict__ x, const u16* __restrict__ pred, const float* __restrict__ ts,
                                                              const int* __restrict__ step, const float* __restrict__ scale,
                                                              const float* __restrict__ proj, const int* __restrict__ ctl,
-                                                             unsigned char* __restrict__ out, int B, long long img_rows, long long pred_rows,
-                                                             int c_in, int h, int w) {
+                                                             unsigned char* __restrict__ out, u16* __restrict__ x0_out, int B, long long img_rows,
+                                                             long long pred_rows, int c_in, int h, int w) {
 #pragma clang fp contract(off)
   const int st = step ? *step : 0;
   const int every = ctl ? ctl[0] : 1;
@@ -40,7 +43,7 @@ __global__ void __launch_bounds__(256) latent_preview_kernel(const u16* __restri
     for (int k = 0; k < 3; ++k) acc[sub][k] = proj[48 + k];
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
-    float fx[8], fc[8], fu[8];
+    float fx[8], fc[8], fu[8], f0[8];
     unpack8(*(const uint4*)(xp + 8 * j), fx);
     unpack8(*(const uint4*)(cp + 8 * j), fc);
     if (GUIDED) unpack8(*(const uint4*)(up + 8 * j), fu);
@@ -49,9 +52,11 @@ __global__ void __launch_bounds__(256) latent_preview_kernel(const u16* __restri
       const int c = 2 * j + (i >> 2), sub = i & 3;
       const float v = GUIDED ? __builtin_fmaf(s, fc[i] - fu[i], fu[i]) : fc[i];
       const float x0 = __builtin_fmaf(-t, v, fx[i]);
+      if (X0) f0[i] = x0;
 #pragma unroll
       for (int k = 0; k < 3; ++k) acc[sub][k] = __builtin_fmaf(proj[3 * c + k], x0, acc[sub][k]);
     }
+    if (X0) *(uint4*)(x0_out + ((((long long)slot * B + b) * pred_rows + r) * 64 + 8 * j)) = pack8(f0);
   }
   const int ty = (int)(r / w), tx = (int)(r % w);
   unsigned char* ob = out + ((long long)slot * B + b) * (4LL * h * w * 3);
@@ -66,11 +71,16 @@ __global__ void __launch_bounds__(256) latent_preview_kernel(const u16* __restri
     }
   }
 }
-}  // namespace
+template <bool GUIDED, bool X0>
+void launch(dim3 grid, hipStream_t s, const void* x, const void* pred, const float* ts, const int* step, const float* scale, const float* proj,
+            const int* ctl, void* out, void* x0_out, int B, long long img_rows, long long pred_rows, int c_in, int h, int w) {
+  hipLaunchKernelGGL((latent_preview_kernel<GUIDED, X0>), grid, dim3(256), 0, s, (const u16*)x, (const u16*)pred, ts, step, scale, proj, ctl,
+                     (unsigned char*)out, (u16*)x0_out, B, img_rows, pred_rows, c_in, h, w);
+}
 
-int fluxmi_k_latent_preview(const void* x, const void* pred, const float* ts, const int* step, const float* scale, const float* proj,
-                            const int* ctl, void* out, int B, long long img_rows, long long pred_rows, int c_in, int c_out, int h, int w,
-                            hipStream_t s) {
+// x0_out == nullptr: fluxmi_latent_preview, the instantiations without the second store
+int preview_launch(const void* x, const void* pred, const float* ts, const int* step, const float* scale, const float* proj, const int* ctl,
+                   void* out, void* x0_out, int B, long long img_rows, long long pred_rows, int c_in, int c_out, int h, int w, hipStream_t s) {
   FLUXMI_REQUIRE(x && pred && ts && proj && out, "latent_preview: NULL argument");
   FLUXMI_REQUIRE(c_out == 64, "latent_preview: c_out = %d (the projection reads 16 latent channels x 4 sub-pixels = 64 packed columns)", c_out);
   FLUXMI_REQUIRE(h >= 1 && w >= 1 && (long long)h * w == pred_rows, "latent_preview: a token grid of %d x %d for %lld predicted rows (h * w must "
@@ -78,14 +88,29 @@ int fluxmi_k_latent_preview(const void* x, const void* pred, const float* ts, co
   FLUXMI_REQUIRE(B >= 1 && B <= 32767 && img_rows >= pred_rows && pred_rows <= 0x7fffffffLL / 256 && c_in >= c_out && c_in % 8 == 0,
                  "latent_preview: bad shape B=%d img_rows=%lld pred_rows=%lld c_in=%d (1 <= B <= 32767, img_rows >= pred_rows, c_in >= 64 and a "
                  "multiple of 8)", B, img_rows, pred_rows, c_in);
-  FLUXMI_REQUIRE(((uintptr_t)x | (uintptr_t)pred) % 16 == 0, "latent_preview: x and pred must be 16-byte aligned");
+  FLUXMI_REQUIRE(((uintptr_t)x | (uintptr_t)pred | (uintptr_t)x0_out) % 16 == 0, "latent_preview: x, pred and x0_out must be 16-byte aligned");
   const dim3 grid((unsigned)((pred_rows + 255) / 256), (unsigned)B);
-  if (scale)
-    hipLaunchKernelGGL(latent_preview_kernel<true>, grid, dim3(256), 0, s, (const u16*)x, (const u16*)pred, ts, step, scale, proj, ctl,
-                       (unsigned char*)out, B, img_rows, pred_rows, c_in, h, w);
-  else
-    hipLaunchKernelGGL(latent_preview_kernel<false>, grid, dim3(256), 0, s, (const u16*)x, (const u16*)pred, ts, step, scale, proj, ctl,
-                       (unsigned char*)out, B, img_rows, pred_rows, c_in, h, w);
+  if (x0_out) {
+    if (scale) launch<true, true>(grid, s, x, pred, ts, step, scale, proj, ctl, out, x0_out, B, img_rows, pred_rows, c_in, h, w);
+    else launch<false, true>(grid, s, x, pred, ts, step, scale, proj, ctl, out, x0_out, B, img_rows, pred_rows, c_in, h, w);
+  } else {
+    if (scale) launch<true, false>(grid, s, x, pred, ts, step, scale, proj, ctl, out, nullptr, B, img_rows, pred_rows, c_in, h, w);
+    else launch<false, false>(grid, s, x, pred, ts, step, scale, proj, ctl, out, nullptr, B, img_rows, pred_rows, c_in, h, w);
+  }
   FLUXMI_LAUNCH_CHECK();
   return 0;
+}
+}  // namespace
+
+int fluxmi_k_latent_preview(const void* x, const void* pred, const float* ts, const int* step, const float* scale, const float* proj,
+                            const int* ctl, void* out, int B, long long img_rows, long long pred_rows, int c_in, int c_out, int h, int w,
+                            hipStream_t s) {
+  return preview_launch(x, pred, ts, step, scale, proj, ctl, out, nullptr, B, img_rows, pred_rows, c_in, c_out, h, w, s);
+}
+
+int fluxmi_k_latent_preview_x0(const void* x, const void* pred, const float* ts, const int* step, const float* scale, const float* proj,
+                               const int* ctl, void* out, void* x0_out, int B, long long img_rows, long long pred_rows, int c_in, int c_out,
+                               int h, int w, hipStream_t s) {
+  FLUXMI_REQUIRE(x0_out, "latent_preview_x0: x0_out must not be NULL");
+  return preview_launch(x, pred, ts, step, scale, proj, ctl, out, x0_out, B, img_rows, pred_rows, c_in, c_out, h, w, s);
 }

@@ -30,7 +30,7 @@ import lora_loading  # noqa: F401  (same import side as the reference)
 from fluxmi import dist as fdist
 from fluxmi import ops, solvers
 from modules.autoencoder import check_attention_mode
-from util import (ModelSpec, ModelVersion, engine_flow_dtype, into_device, into_dtype, load_config_from_path, load_controlnet, load_depth_model, load_ip_adapter, load_upscaler,
+from util import (ModelSpec, ModelVersion, engine_flow_dtype, into_device, into_dtype, load_config_from_path, load_controlnet, load_depth_model, load_ip_adapter, load_tiny_ae, load_upscaler,
                   load_models_from_config)
 
 MAX_RAND = 2**32 - 1
@@ -38,6 +38,8 @@ CONTROL_PREPROCESSORS = ("canny", "gray", "blur", "depth_anything")  # generate(
 IMAGE_RESIZERS = ("pil", "native")  # generate(image_resize=...) / ModelSpec.image_resize: Pillow on the host, or fluxmi.ops.resize_u8 on the device
 PNG_ENCODERS = ("native", "pil")   # generate(png_encoder=...) / ModelSpec.png_encoder: fluxmi.ops.png_encode on the device, or Pillow on the host
 JPEG_ENCODERS = ("pil", "native")  # generate(jpeg_encoder=...) / ModelSpec.jpeg_encoder: Pillow on the host, or fluxmi.ops.jpeg_encode on the device
+PREVIEW_DECODERS = ("latent", "tiny")  # generate(preview_decoder=...): the 16 -> 3 projection, or the tiny autoencoder on the kept estimate
+DECODERS = ("vae", "tiny")         # generate(decoder=...): the autoencoder's decoder, or the tiny autoencoder's (config.tiny_ae_path)
 GUIDANCE_MODES = ("cfg", "apg", "cfg_zero_star")  # generate(guidance_mode=...): the rule that combines the two branches of true CFG
 
 # FLUX.1 Kontext's preferred reference resolutions, (width, height) (BFL flux, src/flux/sampling.py)
@@ -158,7 +160,7 @@ class FluxPipeline:
     def __init__(self, name: str, offload: bool = False, clip=None, t5=None, model=None, ae=None,
                  dtype: torch.dtype = torch.float16, verbose: bool = False, flux_device="cuda:0", ae_device="cuda:1",
                  clip_device="cuda:1", t5_device="cuda:1", config: ModelSpec = None, debug: bool = False, redux=None,
-                 controlnet=None, ip_adapter=None, upscaler=None, depth_model=None):
+                 controlnet=None, ip_adapter=None, upscaler=None, depth_model=None, tiny_ae=None):
         if config is None:
             raise ValueError("ModelSpec config is required!")
         self.debug, self.name, self.verbose, self.offload = debug, name, verbose, offload
@@ -173,6 +175,7 @@ class FluxPipeline:
         self.controlnet = controlnet  # FLUX ControlNet (modules/controlnet.FluxControlNet, config.controlnet_path) or None
         self.ip_adapter = ip_adapter  # FLUX IP-Adapter (modules/ip_adapter.IPAdapter, config.ip_adapter_path / clip_vision_path) or None
         self.upscaler = upscaler  # ESRGAN-family super-resolution network (modules/upscaler.RRDBNet, config.upscaler_path) or None
+        self.tiny_ae = tiny_ae  # the tiny autoencoder's decoder (modules/tiny_vae.TinyDecoder, config.tiny_ae_path) or None
         self.depth_model = depth_model  # Depth Anything depth estimator (modules/depth.DepthAnythingNative, config.depth_path) or None
         self.rng = torch.Generator(device="cpu")
         self.ae_dtype = torch.bfloat16
@@ -864,7 +867,7 @@ class FluxPipeline:
                  tile_weight: str = "cosine", upscale: bool = False, init_upscale: bool = False, control_preprocess: Optional[str] = None,
                  canny_low: int = 100, canny_high: int = 200, canny_l2: bool = False, blur_sigma: float = 8.0, depth_resolution: int = 518,
                  depth_normalize: str = "minmax", jpeg_encoder: Optional[str] = None, image_resize: Optional[str] = None,
-                 png_encoder: Optional[str] = None):
+                 png_encoder: Optional[str] = None, decoder: str = "vae", preview_decoder: str = "latent"):
         """`reference_image` (FLUX.1 Kontext [dev] instruction editing): an image the prompt describes an edit of, in any form `init_image`
         takes; see prepare_kontext_reference.  Composes with `init_image` / `strength` unchanged.
         FLUX.1 Fill [dev] (a model with 320 conditioning channels): `init_image` is the image to inpaint and `mask_image` (white =
@@ -1040,7 +1043,15 @@ class FluxPipeline:
         unless configured): "native" keeps the pixels on the device from the VAE (and the upscaler) to fluxmi.ops.png_encode
         (include/fluxmi.h: adaptive filtering, one dynamic-Huffman deflate block per strip of rows, runs at distance 1); "pil" copies them
         to the host for Pillow at compress_level=6.  Both decode to exactly the output_type="uint8" array.  With another output_type the
-        encoder is ignored; an unknown one is refused by name."""
+        encoder is ignored; an unknown one is refused by name.
+        `decoder` ("vae" | "tiny"): who turns the final latents into pixels.  "vae" is the autoencoder, launch for launch what it always was;
+        "tiny" is the TAEF1 decoder of config.tiny_ae_path (modules/tiny_vae.py: ten fused residual-block launches of fluxmi_conv3x3_block),
+        a fast approximate decode whose pixels enter the JPEG / PNG encoders, `upscale` and a tiled request's output exactly where the
+        VAE's do.  "tiny" without a configured file is refused before any other work.
+        `preview_decoder` ("latent" | "tiny"): what `on_step` receives as info["preview"] at a previewed evaluation.  "latent" is the 16 -> 3
+        projection at latent resolution, as ever.  "tiny": the engine also keeps the evaluation's estimate (fluxmi_engine_set_preview_latents)
+        and the preview is that estimate through the tiny decoder on a side stream: uint8 [num_images, height, width, 3], to_uint8's
+        rounding.  It needs preview_every > 0 and config.tiny_ae_path, and is refused wherever preview_every > 0 is."""
         if control_preprocess is not None:
             if img_cond is not None or controlnet_cond is not None:
                 raise ValueError("fluxmi: control_preprocess works on an image: it does not combine with img_cond / controlnet_cond (maps that "
@@ -1057,6 +1068,16 @@ class FluxPipeline:
         prep_kw = dict(canny_low=canny_low, canny_high=canny_high, canny_l2=canny_l2, blur_sigma=blur_sigma)
         if control_preprocess == "depth_anything":  # the other kinds keep the call they always made
             prep_kw.update(depth_resolution=depth_resolution, depth_normalize=depth_normalize)
+        if decoder not in DECODERS:
+            raise ValueError(f"fluxmi: decoder={decoder!r}: expected one of {DECODERS}")
+        if decoder == "tiny":
+            self._require_tiny_ae().check_input(max(1, int(num_images)), 2 * (height // 16), 2 * (width // 16))
+        if preview_decoder not in PREVIEW_DECODERS:
+            raise ValueError(f"fluxmi: preview_decoder={preview_decoder!r}: expected one of {PREVIEW_DECODERS}")
+        if preview_decoder == "tiny":
+            if isinstance(preview_every, bool) or not isinstance(preview_every, int) or preview_every <= 0:
+                raise ValueError("fluxmi: preview_decoder=\"tiny\" needs preview_every > 0 (it decodes the previews)")
+            self._require_tiny_ae().check_input(max(1, int(num_images)), 2 * (height // 16), 2 * (width // 16))
         if upscale or init_upscale:
             init_image = self._check_upscale(upscale, init_upscale, output_type, init_image, width, height, num_images)
         image_resize = self._image_resize(image_resize)
@@ -1077,12 +1098,12 @@ class FluxPipeline:
         if tiles is not None:
             return self._generate_tiled(tiles, prompt, width, height, num_steps, guidance, seed, init_image, strength, num_images, return_seed,
                                         jpeg_quality, output_type, noise, use_graph, negative_prompt, true_cfg_scale, true_cfg_interval,
-                                        sigma_schedule, sigmas, on_step, upscale=upscale, encoder=encoder)
+                                        sigma_schedule, sigmas, on_step, upscale=upscale, encoder=encoder, decoder=decoder)
         edit = self._check_edit(locals())
         if edit is not None:
             return self._generate_edit(edit, prompt, source_prompt, width, height, num_steps, guidance, seed, init_image, silent, num_images,
                                        return_seed, jpeg_quality, output_type, use_graph, sigma_schedule, sigmas, noise_seed, on_step,
-                                       upscale=upscale, encoder=encoder)
+                                       upscale=upscale, encoder=encoder, decoder=decoder)
         if isinstance(preview_every, bool) or not isinstance(preview_every, int) or preview_every < 0:
             raise ValueError(f"fluxmi: preview_every={preview_every!r}: expected an integer >= 0 (0 = no previews)")
         if on_step is not None and not callable(on_step):
@@ -1445,17 +1466,18 @@ class FluxPipeline:
                     evals_done += len(kw["solver"].coef) if "solver" in kw else b - a
             for a, b, kw, off in plan:
                 if on_step is not None:  # the request's numbering continues across its denoise calls
-                    kw = dict(kw, preview=self._preview_call(on_step, preview_proj, preview_every, height, width, a, off, evals_done, kw.get("solver")))
+                    kw = dict(kw, preview=self._preview_call(on_step, preview_proj, preview_every, height, width, a, off, evals_done, kw.get("solver"),
+                                                             preview_decoder))
                 latents = self.model.denoise(latents, img_ids, txt, txt_ids, vec, timesteps[a:b + 1], guidance=guidance, use_graph=use_graph,
                                              **cond, **kw, **cache)
         if world > 1:
             latents = fdist.gather_latents(latents, num_images, dst=0)
             if latents is None:  # only the gather rank decodes / returns the images
                 return (None, seed) if return_seed else None
-        if output_type == "latent" or self.ae is None:
+        if output_type == "latent" or (self.ae is None and decoder != "tiny"):
             out = self.unpack(latents.float(), height, width) if latents is not None else None
             return (out, seed) if return_seed else out
-        img_px = self.vae_decode(latents, height, width)
+        img_px = self._decode(latents, height, width, decoder)
         # output_type "uint8": the [B, H, W, 3] array into_bytes hands to the JPEG encoder (the pixel-parity tests compare it)
         out = self._pixels_out(img_px, output_type, jpeg_quality, upscale, encoder)
         return (out, seed) if return_seed else out
@@ -1565,7 +1587,7 @@ class FluxPipeline:
 
     def _generate_tiled(self, plan, prompt, width, height, num_steps, guidance, seed, init_image, strength, num_images, return_seed, jpeg_quality,
                         output_type, noise, use_graph, negative_prompt, true_cfg_scale, true_cfg_interval, sigma_schedule, sigmas, on_step,
-                        upscale=False, encoder="pil"):
+                        upscale=False, encoder="pil", decoder="vae"):
         """the tiled request of generate (its docstring): today's noise / img2img / text at canvas size, then Flux.denoise_windows on the
         canvas -- one call, or up to three where true_cfg_interval cuts the request"""
         from modules.flux_model import Flux, PreviewCall
@@ -1606,10 +1628,10 @@ class FluxPipeline:
                 canvas = self.model.denoise_windows(canvas, plan, win_ids, txt, txt_ids, vec, timesteps[a:b + 1], guidance=guidance,
                                                     use_graph=use_graph, **kw)
         latents = canvas.reshape(N, plan.Hc * plan.Wc, -1).to(img.dtype)
-        if output_type == "latent" or self.ae is None:
+        if output_type == "latent" or (self.ae is None and decoder != "tiny"):
             out = self.unpack(latents.float(), height, width)
             return (out, seed) if return_seed else out
-        img_px = self.vae_decode(latents, height, width)
+        img_px = self._decode(latents, height, width, decoder)
         out = self._pixels_out(img_px, output_type, jpeg_quality, upscale, encoder)
         return (out, seed) if return_seed else out
 
@@ -1699,7 +1721,7 @@ class FluxPipeline:
 
     def _generate_edit(self, edit, prompt, source_prompt, width, height, num_steps, guidance, seed, init_image, silent, num_images, return_seed,
                        jpeg_quality, output_type, use_graph, sigma_schedule, sigmas, noise_seed, on_step, upscale=False,
-                       encoder="pil"):
+                       encoder="pil", decoder="vae"):
         """the FlowEdit request of generate (its docstring): skipped steps | coupled steps (Flux.denoise_edit) | Euler tail (Flux.denoise)"""
         from fluxmi import flowedit, ops
         from modules.flux_model import PreviewCall
@@ -1744,14 +1766,15 @@ class FluxPipeline:
             zt = ops.flowedit_couple(z.to(torch.bfloat16).contiguous(), x0.to(torch.bfloat16).contiguous(), timesteps[b], ids, n_coupled)[B:]
             latents = self.model.denoise(zt.to(x0.dtype), img_ids, txt, txt_ids, vec, timesteps[b:], guidance=guidance, use_graph=use_graph,
                                          **({} if on_step is None else dict(preview=hook(n_coupled, lambda j: b + j))))
-        if output_type == "latent" or self.ae is None:
+        if output_type == "latent" or (self.ae is None and decoder != "tiny"):
             out = self.unpack(latents.float(), height, width)
             return (out, seed) if return_seed else out
-        img_px = self.vae_decode(latents, height, width)
+        img_px = self._decode(latents, height, width, decoder)
         out = self._pixels_out(img_px, output_type, jpeg_quality, upscale, encoder)
         return (out, seed) if return_seed else out
 
-    def _preview_call(self, on_step, proj, every: int, height: int, width: int, step0: int, eval_offset: int, n_evaluations: int, solver):
+    def _preview_call(self, on_step, proj, every: int, height: int, width: int, step0: int, eval_offset: int, n_evaluations: int, solver,
+                      preview_decoder: str = "latent"):
         """the PreviewCall of one denoise call of a request: evaluation numbers are the request's, `step` goes through the slice's solver"""
         from modules.flux_model import PreviewCall
 
@@ -1760,7 +1783,10 @@ class FluxPipeline:
             step = step0 + (int(solver.step_of_eval[j]) if solver is not None else j)
             return on_step({"evaluation": evaluation, "num_evaluations": num_evaluations, "step": step, "preview": rgb})
 
-        return PreviewCall(proj, (math.ceil(height / 16), math.ceil(width / 16)), every, eval_offset, n_evaluations, callback)
+        decode = None
+        if preview_decoder == "tiny" and every > 0:  # x0: the packed estimate [images, tokens, 64] -> pixels as a finished request's would be
+            decode = lambda x0: self.to_uint8(self.tiny_decode(self.unpack(x0.float(), height, width))).numpy()
+        return PreviewCall(proj, (math.ceil(height / 16), math.ceil(width / 16)), every, eval_offset, n_evaluations, callback, decode)
 
     def preview_projection(self, preview_factors=None) -> list:
         """The 51 floats the engine's preview launch reads, for the model's latent: `preview_factors` = (M [16][3], bias [3]) in
@@ -1793,6 +1819,24 @@ class FluxPipeline:
         x = self.unpack(x.to(self.device_ae).float(), height, width)
         with torch.autocast(device_type=self.device_ae.type, dtype=torch.bfloat16, cache_enabled=False):
             return self.ae.decode(x)
+
+    # ---- the tiny autoencoder (modules/tiny_vae.TinyDecoder on fluxmi_conv3x3_block) -----------------------------------------------------
+    def _require_tiny_ae(self):
+        if getattr(self, "tiny_ae", None) is None:
+            raise ValueError("fluxmi: decoder=\"tiny\" needs a TAEF1 decoder: set config.tiny_ae_path to a local .safetensors / .pth file "
+                             "(nothing is downloaded)")
+        return self.tiny_ae
+
+    def tiny_decode(self, latents: torch.Tensor) -> torch.Tensor:
+        """The model's latent [B, 16, h, w] (an output_type="latent" result) -> [B, 3, 8 h, 8 w] fp32 in [-1, 1] through the tiny decoder,
+        where vae_decode would put it: to_uint8 / _pixels_out take either."""
+        return self._require_tiny_ae().decode(latents)
+
+    def _decode(self, x: torch.Tensor, height: int, width: int, decoder: str = "vae") -> torch.Tensor:
+        """the packed latents of a finished request -> pixels through the request's decoder"""
+        if decoder == "tiny":
+            return self.tiny_decode(self.unpack(x.float(), height, width))
+        return self.vae_decode(x, height, width)
 
     @staticmethod
     def to_uint8(x: torch.Tensor) -> torch.Tensor:
@@ -1973,4 +2017,5 @@ class FluxPipeline:
                    t5_device=into_device(config.text_enc_device), config=config, debug=debug, redux=redux,
                    controlnet=load_controlnet(config, device=flux_device), ip_adapter=load_ip_adapter(config, device=flux_device),
                    upscaler=load_upscaler(config, device=into_device(config.ae_device)),
+                   tiny_ae=load_tiny_ae(config, device=into_device(config.ae_device)),
                    depth_model=load_depth_model(config, device=into_device(config.ae_device)))

@@ -112,6 +112,7 @@ _SIGS = {
     "fluxmi_window_attention": ([vp, i64, vp, vp, i64, i32, i32, i32, i32, i32, C.c_float, vp], i32),
     "fluxmi_channel_norm": ([vp, i64, vp, vp, vp, i64, i64, i32, C.c_float, vp], i32),
     "fluxmi_conv3x3_dense": ([vp, i64, i32, vp, vp, vp, i64, i32, vp, i64, C.c_float, vp, i64, C.c_float, C.c_float, i32, i32, i32, i32, i32, vp], i32),
+    "fluxmi_conv3x3_block": ([vp, i64, vp, vp, vp, i64, i32, i32, i32, vp], i32),
     "fluxmi_canny_classify": ([vp, i64, i64, vp, i64, i64, i32, i32, i32, i32, i32, i32, vp], i32),
     "fluxmi_canny_hysteresis_round": ([vp, i64, i64, i32, i32, i32, vp, vp], i32),
     "fluxmi_canny_hysteresis": ([vp, i64, i64, vp, i64, i64, vp, i32, i32, i32, C.POINTER(i32), vp], i32),
@@ -177,7 +178,9 @@ _SIGS = {
     "fluxmi_engine_set_windows": ([vp, i32, i32, i32, i32, i32, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(f32), C.POINTER(f32), vp], i32),
     "fluxmi_engine_denoise_windows": ([vp, vp, vp, vp, f32, i32, f32, C.POINTER(C.c_double), i32, C.POINTER(i32), i32, vp], i32),
     "fluxmi_latent_preview": ([vp, vp, vp, vp, vp, vp, vp, vp, i32, i64, i64, i32, i32, i32, i32, vp], i32),
+    "fluxmi_latent_preview_x0": ([vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i64, i64, i32, i32, i32, i32, vp], i32),
     "fluxmi_engine_set_preview": ([vp, C.POINTER(f32), i32, i32, i32, i32, i32, vp, vp], i32),
+    "fluxmi_engine_set_preview_latents": ([vp, i32], i32),
     "fluxmi_engine_preview_stats": ([vp, C.POINTER(i64), C.POINTER(i32)], i32),
     "fluxmi_engine_step_cache_log": ([vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(f32), C.POINTER(C.c_ubyte), i32], i32),
     "fluxmi_engine_run_phase": ([vp, i32, i32, i32, i32, vp], i32),

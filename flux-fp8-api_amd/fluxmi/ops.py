@@ -605,6 +605,22 @@ def conv3x3_dense(x: torch.Tensor, w2: torch.Tensor, bias: Optional[torch.Tensor
     return out
 
 
+def conv3x3_block(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """The tiny autoencoder's fused residual block (fluxmi_conv3x3_block; include/fluxmi.h has the arithmetic):
+    out = relu(conv3(relu(conv2(relu(conv1(x))))) + x) on 64-channel windows x, out [B, H, W, 64] of NHWC bf16 pixel buffers that do not
+    overlap.  w [3, 64, 3, 3, 64] (conv, cout, dy, dx, cin), bias [3, 64], both contiguous."""
+    for t, name in ((x, "x"), (w, "w"), (bias, "bias"), (out, "out")):
+        _req(t, torch.bfloat16, name)
+    ldx, ldo = _pixel_stride(x, "x"), _pixel_stride(out, "out")
+    B, H, W, Cc = x.shape
+    if Cc != 64 or tuple(out.shape) != (B, H, W, 64):
+        raise ValueError(f"conv3x3_block: x {tuple(x.shape)} and out {tuple(out.shape)} must both be [B, H, W, 64]")
+    if tuple(w.shape) != (3, 64, 3, 3, 64) or not w.is_contiguous() or tuple(bias.shape) != (3, 64) or not bias.is_contiguous():
+        raise ValueError(f"conv3x3_block: w must be contiguous [3, 64, 3, 3, 64] and bias [3, 64], got {tuple(w.shape)} / {tuple(bias.shape)}")
+    call("fluxmi_conv3x3_block", _p(x), ldx, _p(w), _p(bias), _p(out), ldo, B, H, W, _stream())
+    return out
+
+
 def im2col3x3(x: torch.Tensor, upsample: int = 1) -> torch.Tensor:
     """x [B, Hin, Win, C] bf16 -> patch matrix [B*H*W, 9*C], column order (dy, dx, c).  upsample = 1: H = Hin; 2: nearest 2x upsample
     first (H = 2*Hin); -2: stride-2 window with zero pad on the right/bottom only (H = Hin/2, the reference's Downsample)."""
@@ -1059,12 +1075,13 @@ def preview_proj(factors, bias=None) -> list:
 
 
 def latent_preview(x: torch.Tensor, pred: torch.Tensor, t, proj, grid, scale=None, step=None, ctl=None,
-                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   out: Optional[torch.Tensor] = None, x0_out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The denoised estimate x - t v of one evaluation projected to RGB (fluxmi_latent_preview): x bf16 [B (2B guided), img_rows, c_in],
     pred bf16 [B (2B guided), pred_rows, 64], `grid` = (h, w) tokens, proj = the 51 floats (a list or an fp32 device tensor).  `t`: a float,
     or an fp32 device table indexed by `step` (an int32 device scalar; None = entry 0).  `scale` (a float or an fp32 device scalar) selects
     the guided form.  `ctl` = (every, eval_offset) or an int32 device tensor [2]; None = (1, 0): every evaluation, slot = step % PREVIEW_SLOTS.
-    Returns `out`, uint8 [PREVIEW_SLOTS, B, 2 h, 2 w, 3]: only the slot the launch selects is written."""
+    Returns `out`, uint8 [PREVIEW_SLOTS, B, 2 h, 2 w, 3]: only the slot the launch selects is written.  `x0_out` (bf16 [PREVIEW_SLOTS, B,
+    pred_rows, 64], contiguous) selects fluxmi_latent_preview_x0: the same slot of it also receives the estimate's 64 packed columns."""
     _req(x, torch.bfloat16, "x")
     _req(pred, torch.bfloat16, "pred")
     if x.ndim != 3 or pred.ndim != 3 or x.shape[0] != pred.shape[0] or not (x.is_contiguous() and pred.is_contiguous()):
@@ -1092,6 +1109,13 @@ def latent_preview(x: torch.Tensor, pred: torch.Tensor, t, proj, grid, scale=Non
     _req(out, torch.uint8, "out")
     if out.numel() != _lib.PREVIEW_SLOTS * B * 4 * h * w * 3 or not out.is_contiguous():
         raise ValueError(f"latent_preview: out {tuple(out.shape)} must be contiguous uint8 [{_lib.PREVIEW_SLOTS}, {B}, {2 * h}, {2 * w}, 3]")
+    if x0_out is not None:
+        _req(x0_out, torch.bfloat16, "x0_out")
+        if tuple(x0_out.shape) != (_lib.PREVIEW_SLOTS, B, pred.shape[1], 64) or not x0_out.is_contiguous():
+            raise ValueError(f"latent_preview: x0_out {tuple(x0_out.shape)} must be contiguous bf16 [{_lib.PREVIEW_SLOTS}, {B}, {pred.shape[1]}, 64]")
+        call("fluxmi_latent_preview_x0", _p(x), _p(pred), _p(ts), _p(st), _p(sc), _p(prj), _p(ct), _p(out), _p(x0_out), B, x.shape[1], pred.shape[1],
+             x.shape[2], pred.shape[2], h, w, _stream())
+        return out
     call("fluxmi_latent_preview", _p(x), _p(pred), _p(ts), _p(st), _p(sc), _p(prj), _p(ct), _p(out), B, x.shape[1], pred.shape[1], x.shape[2], pred.shape[2], h, w, _stream())
     return out
 

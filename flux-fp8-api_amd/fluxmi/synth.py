@@ -218,6 +218,33 @@ def make_rrdbnet_state_dict(num_block: int = 2, nf: int = 64, gc: int = 32, scal
     return old
 
 
+def make_taef1_state_dict(seed: int = 0, prefix: str = "") -> Dict[str, torch.Tensor]:
+    """A seeded TAEF1 decoder checkpoint (modules/tiny_vae.py) for tests and tools, under the original's bare Sequential keys ("1.weight",
+    "3.conv.0.weight", ..) behind `prefix` ("", "decoder."), or with prefix "decoder.layers." numbered from the stem (index 0), the other
+    published layout.  fp32 tensors that hold bf16 values; std 1.4 / sqrt(9 Cin) on the 64 -> 64 convolutions of the blocks, 0.7 on their
+    third (the skip adds to it), 1.0 elsewhere; biases N(0, 0.1), the last convolution's around 0.5 so the RGB is not all clipped."""
+    gen = torch.Generator().manual_seed(2000 + seed)
+    shift = 1 if prefix == "decoder.layers." else 0
+    sd: Dict[str, torch.Tensor] = {}
+
+    def conv(name, co, ci, gain, bias=0.0):
+        idx, _, rest = name.partition(".")
+        key = f"{prefix}{int(idx) - shift}" + (f".{rest}" if rest else "")
+        sd[key + ".weight"] = (torch.randn(co, ci, 3, 3, generator=gen) * (gain / math.sqrt(9 * ci))).bfloat16().float()
+        if bias is not None:
+            sd[key + ".bias"] = (bias + 0.1 * torch.randn(co, generator=gen)).bfloat16().float()
+
+    conv("1", 64, 16, 1.0)
+    for i in range(3, 19):
+        if i in (7, 12, 17):
+            conv(str(i), 64, 64, 1.0, bias=None)
+        elif i not in (6, 11, 16):
+            for s, gain in ((0, 1.4), (2, 1.4), (4, 0.7)):
+                conv(f"{i}.conv.{s}", 64, 64, gain)
+    conv("19", 3, 64, 1.0, bias=0.5)
+    return sd
+
+
 # the Depth Anything geometries of the three released sizes (LiheYoung/depth-anything-{small,base,large}-hf and the V2 checkpoints)
 DEPTH_ANYTHING_SIZES = {
     "small": dict(hidden_size=384, num_attention_heads=6, num_hidden_layers=12, out_indices=[3, 6, 9, 12], neck_hidden_sizes=[48, 96, 192, 384],

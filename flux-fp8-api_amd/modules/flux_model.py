@@ -35,7 +35,10 @@ if TYPE_CHECKING:
 # ops.preview_proj (None with every = 0); grid: (h, w) tokens of the stepped rows; every: 0 = progress and cancellation only, k > 0 = a preview
 # at every evaluation g with g % k == 0; eval_offset / n_evaluations: this call's first evaluation within the request and the request's
 # total; callback(evaluation, n_evaluations, rgb) with rgb a uint8 numpy array [images, 2 h, 2 w, 3] or None -- returning False cancels.
-PreviewCall = namedtuple("PreviewCall", ["proj", "grid", "every", "eval_offset", "n_evaluations", "callback"])
+# decode (optional, every > 0 only): the engine also keeps the estimate (fluxmi_engine_set_preview_latents) and the callback's third argument
+# is decode(x0) instead of the projected RGB, x0 = the evaluation's packed estimate, bf16 [images, h w, 64] on the engine's device; it is
+# called on a side stream and returns what the callback is to receive.
+PreviewCall = namedtuple("PreviewCall", ["proj", "grid", "every", "eval_offset", "n_evaluations", "callback", "decode"], defaults=(None,))
 
 
 class FluxParams(BaseModel):  # reference flux_model.py:24-36
@@ -445,9 +448,12 @@ class Flux(nn.Module):
                 raise ValueError("preview: proj holds 51 finite floats (ops.preview_proj)")
             if len(preview.grid) != 2:
                 raise ValueError("preview: grid = (h, w) tokens")
-        return PreviewCall(proj, tuple(int(v) for v in preview.grid) if every > 0 else (0, 0), every, off, n, preview.callback)
+        decode = getattr(preview, "decode", None)
+        if decode is not None and (every == 0 or not callable(decode)):
+            raise ValueError("preview: decode must be callable and needs every > 0")
+        return PreviewCall(proj, tuple(int(v) for v in preview.grid) if every > 0 else (0, 0), every, off, n, preview.callback, decode)
 
-    def _set_preview(self, preview):
+    def _set_preview(self, preview, device=None):
         """after _prepare, under the lock: the step hook of this call (_check_preview) -> the state that keeps the ctypes callback alive and
         carries an exception out of it (ctypes would swallow it), or None"""
         if preview is None:
@@ -455,11 +461,26 @@ class Flux(nn.Module):
         import numpy as np
 
         state = {"error": None, "cb": None}
+        side = torch.cuda.Stream(device=device) if preview.decode is not None else None
+
+        def decoded(evaluation, images):
+            """the estimate of this evaluation out of its ring slot (valid until the hook returns: fluxmi.h's look-ahead argument), decoded"""
+            rows = preview.grid[0] * preview.grid[1]
+            x0 = torch.empty(images, rows, 64, dtype=torch.bfloat16, device=device)
+            slot = (evaluation // preview.every) % _lib.PREVIEW_SLOTS
+            with torch.cuda.stream(side):
+                _lib.call("fluxmi_engine_copy_buffer", self._engine, b"preview_x0", slot * x0.numel() * 2, ops._p(x0), x0.numel() * 2, 0,
+                          C.c_void_p(side.cuda_stream))
+                out = preview.decode(x0)
+            side.synchronize()
+            return out
 
         def hook(user, evaluation, n_evaluations, rgb, images, height, width):
             try:
                 arr = None
-                if rgb:
+                if rgb and preview.decode is not None:
+                    arr = decoded(evaluation, images)
+                elif rgb:
                     buf = (C.c_ubyte * (images * height * width * 3)).from_address(rgb)
                     arr = np.frombuffer(buf, dtype=np.uint8).reshape(images, height, width, 3).copy()  # the pinned buffer is the engine's
                 return 1 if preview.callback(evaluation, n_evaluations, arr) is False else 0
@@ -471,6 +492,8 @@ class Flux(nn.Module):
         proj = (C.c_float * 51)(*preview.proj) if preview.proj is not None else None
         _lib.call("fluxmi_engine_set_preview", self._engine, proj, preview.grid[0], preview.grid[1], preview.every, preview.eval_offset,
                   preview.n_evaluations, state["cb"], None)
+        if preview.decode is not None:
+            _lib.call("fluxmi_engine_set_preview_latents", self._engine, 1)
         return state
 
     def preview_stats(self):
@@ -1002,7 +1025,7 @@ class Flux(nn.Module):
             pv, rc, ran = None, 0, 0
             try:
                 ip_set = self._set_ip_adapter(ip, img.device)
-                pv = self._set_preview(preview)
+                pv = self._set_preview(preview, img.device)
                 if guided:
                     rc = _lib.lib.fluxmi_engine_denoise_cfg(self._engine, ops._p(img), ops._p(txt), ops._p(y), float(guidance), float(cfg_scale), ts,
                                                             len(timesteps) - 1, C.byref(t_io), int(use_graph), ops._stream())

@@ -88,6 +88,9 @@ class ModelSpec(BaseModel):  # reference util.py:38-79 (unknown JSON keys are ig
     # LOCAL .safetensors or .pth file, or a SwinIR "nearest+conv" x2 / x4 model (the real-world SwinIR-M / L; modules/swinir.py), told apart
     # by the keys.  Nothing is downloaded; FluxPipeline.upscaler is None unless the file exists
     upscaler_path: str | None = None
+    # the tiny autoencoder's decoder (TAEF1; modules/tiny_vae.py) behind generate(decoder="tiny") and preview_decoder="tiny": a LOCAL
+    # .safetensors or .pth file.  Nothing is downloaded; FluxPipeline.tiny_ae is None unless the file exists
+    tiny_ae_path: str | None = None
     # the Depth Anything depth estimator of control_preprocess="depth_anything" (modules/depth.py): a LOCAL directory in the HF layout
     # (config.json + model.safetensors / *.bin of DepthAnythingForDepthEstimation, e.g. a copy of LiheYoung/depth-anything-large-hf).
     # Nothing is downloaded; FluxPipeline.depth_model is None unless the directory exists
@@ -417,6 +420,21 @@ def load_upscaler(config: ModelSpec, device=None):
     from modules.upscaler import read_upscaler
 
     return read_upscaler(path, device=into_device(device if device is not None else config.ae_device))
+
+
+def load_tiny_ae(config: ModelSpec, device=None):
+    """The TAEF1 decoder of config.tiny_ae_path (modules/tiny_vae.TinyDecoder) on `device`, fed through the VAE's scale_factor /
+    shift_factor, or None unless the path is a local file.  Nothing is downloaded.  Another geometry is refused by name."""
+    import os
+
+    path = getattr(config, "tiny_ae_path", None)
+    if not (isinstance(path, str) and os.path.isfile(path)):
+        return None
+    from modules.tiny_vae import read_tiny_ae
+
+    ae = config.ae_params
+    return read_tiny_ae(path, device=into_device(device if device is not None else config.ae_device), scale_factor=ae.scale_factor,
+                        shift_factor=ae.shift_factor)
 
 
 def load_depth_model(config: ModelSpec, device=None):

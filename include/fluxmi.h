@@ -487,6 +487,27 @@ int fluxmi_vae_attention(const void* q, const void* k, long long ld_qk, long lon
 int fluxmi_conv3x3_dense(const void* x, long long ldx, int Cin, const void* w2, const void* bias, void* out, long long ldo, int Cout,
                          const void* r1, long long ldr1, float a1, const void* r2, long long ldr2, float a2, float slope, int act,
                          int upsample, int B, int H, int W, void* stream);
+/* The residual block of the tiny autoencoder (TAEF1; modules/tiny_vae.py): three 3x3 convolutions of 64 -> 64 channels (stride 1, zero pad 1,
+ * NHWC bf16) with their ReLUs and the skip in ONE kernel (csrc/tiny_vae.hip) that reads its input once and writes its output once.
+ *   x      bf16 [B][H][W] pixels, pixel stride ldx elements; channels [0, 64) of each pixel are read
+ *   w      bf16 [3][64][3][3][64]: per convolution fluxmi_conv3x3_dense's w2 at Cin = Cout = 64 ([cout][dy][dx][cin])
+ *   bias   bf16 [3][64]
+ *   out    bf16 [B][H][W] pixels, pixel stride ldo; channels [0, 64) at `out` are written and NOTHING else is
+ * Arithmetic, with zero padding of 1 at EVERY convolution (an m1 / m2 pixel outside the image is zero, not what the convolution before it
+ * would compute there):
+ *   m1  = bf16(relu(conv1(x) + b1))      m2 = bf16(relu(conv2(m1) + b2))
+ *   y   = (conv3(m2) + b3) + x           in fp32, two rounded sums
+ *   out = bf16(relu(y))
+ * Every conv is the fp32 MFMA (v_mfma_f32_32x32x16_bf16) sum of the bf16 products over (dy, dx), then 16-channel steps.  The two intermediate
+ * roundings and the store are the only bf16 roundings; relu(NaN) = NaN.  One workgroup computes a FLUXMI_CONV_BLOCK_TILE x
+ * FLUXMI_CONV_BLOCK_TILE pixel tile of one image from a (TILE + 6)^2 input halo held in LDS; m1 and m2 never reach memory.
+ * Deterministic (no atomics, fixed summation order); a sample's bits depend on that sample alone.  All address arithmetic is 64-bit.
+ * Returns non-zero before any launch (text in fluxmi_last_error) for: a NULL pointer; B, H or W < 1; B or ceil(H / tile) above 65535 (the
+ * launch grid); a stride that is no multiple of 8 or shorter than 64; a pointer that is not 16-byte aligned; address ranges of x and out
+ * that meet. */
+#define FLUXMI_CONV_BLOCK_TILE 16
+int fluxmi_conv3x3_block(const void* x, long long ldx, const void* w, const void* bias, void* out, long long ldo, int B, int H, int W,
+                         void* stream);
 /* Shifted-window attention with a 2-D relative-position bias: the core of SwinIR's block (modules/swinir.py; csrc/window_attention.hip),
  * window FLUXMI_WINDOW = 8 (64 tokens), heads padded to 32 columns.  ONE launch does, for all images, windows and heads, what Swin's
  * roll -> window_partition -> WindowAttention core -> window_reverse -> roll back does: the partition, both rolls and the reverse are address
@@ -977,6 +998,13 @@ int fluxmi_guidance_combine(void* pred, float* r, const float* part, const float
 int fluxmi_latent_preview(const void* x, const void* pred, const float* ts, const int* step, const float* scale, const float* proj,
                           const int* ctl, void* out, int B, long long img_rows, long long pred_rows, int c_in, int c_out, int h, int w,
                           void* stream);
+/* fluxmi_latent_preview that ALSO keeps the estimate: x0_out bf16 [FLUXMI_PREVIEW_SLOTS][B][pred_rows][64], 16-byte aligned, not NULL.  The
+ * same kernel template; whenever it writes the RGB of slot s it additionally stores bf16(x0_c) of every token's 64 packed columns (column
+ * c * 4 + sub, the layout of pred) into slot s of x0_out, eight 16-byte stores per token; every other slot of x0_out keeps its bytes.  The
+ * RGB bytes are those of fluxmi_latent_preview on the same inputs.  For a decoder that wants the estimate itself (modules/tiny_vae.py). */
+int fluxmi_latent_preview_x0(const void* x, const void* pred, const float* ts, const int* step, const float* scale, const float* proj,
+                             const int* ctl, void* out, void* x0_out, int B, long long img_rows, long long pred_rows, int c_in, int c_out,
+                             int h, int w, void* stream);
 
 /* ---- first-block step cache: the streaming passes --------------------------------------
  * B samples of n bf16 elements each (n = cached rows x hidden, n %% 8 == 0).  The `x` side is the residual stream: the pointer is the first
@@ -1266,6 +1294,16 @@ typedef int (*fluxmi_step_hook_t)(void* user, int evaluation, int n_evaluations,
 int fluxmi_engine_set_preview(fluxmi_engine_t* e, const float* proj51_host, int h, int w, int every, int eval_offset, int n_evaluations,
                               fluxmi_step_hook_t hook, void* user);
 int fluxmi_engine_preview_stats(fluxmi_engine_t* e, long long* captures, int* evaluations_run);
+/* Previews through a decoder that wants the estimate itself (modules/tiny_vae.py).  Called AFTER a fluxmi_engine_set_preview with a hook and
+ * every > 0 (anything else is refused); every fluxmi_engine_set_preview call switches it off again.  on != 0:
+ *   - allocates "preview_x0", bf16 [FLUXMI_PREVIEW_SLOTS][B][stepped rows][64] for the prepared batch B, once per prepared shape; counted in
+ *     fluxmi_engine_workspace_bytes, found by fluxmi_engine_get_buffer / read with fluxmi_engine_copy_buffer, dropped with the workspace;
+ *   - the previewed step launches fluxmi_latent_preview_x0 instead of fluxmi_latent_preview: one more kind of step graph (the ring's
+ *     address is part of the key), the same RGB bytes and hook arguments.
+ * The hook of evaluation g with a preview finds its estimate in slot (g / every) % FLUXMI_PREVIEW_SLOTS, sample stride images x rows x 64;
+ * by the look-ahead argument above the slot is not rewritten before the hook returns.  A request without it allocates, captures and
+ * launches exactly what it did before. */
+int fluxmi_engine_set_preview_latents(fluxmi_engine_t* e, int on);
 /* Test hook: phases [phase_from, phase_to] of ONE frozen forward on the engine's own buffers, mode 1 (fused) or 2 (unfused, frozen scales):
  *   0 img_in + txt_in on the request buffers "img_s" / "txt_s" (mode 1: the cached "txt_emb" of the last denoise call) + this step's
  *     modulation vectors out of the step-ahead table the last denoise call left (step = the request's step index, written to the device-side

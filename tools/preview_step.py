@@ -7,6 +7,8 @@ round, so that drift of the device shows in every kind alike:
              ahead of the GPU, one event wait per evaluation) and no launch of its own
     every1   a preview at every evaluation: one more launch per step, one 393 KB device-to-host copy per delivery
     every4   a preview at every fourth evaluation: the same launches (the kernel returns at once on the others), a quarter of the copies
+    tiny1    (not in the default kinds) a preview at every evaluation through the tiny autoencoder (modules/tiny_vae.py, synthetic weights):
+             the launch also keeps the estimate, and each delivery decodes it to full resolution on a side stream and copies 3 MB to the host
 Two meters per request: the host's wall clock around the whole Flux.denoise call, stream-synchronised on both sides (what a caller waits
 for; a hooked call is synchronous anyway), and the engine's own hipEvent pair around the graph replays (fluxmi_engine_last_timing).  Every
 timed request follows an untimed one of its kind, which absorbs the warm step and the capture of a switch between previewed and not.
@@ -30,7 +32,8 @@ from float8_quantize import quantize_flow_transformer_and_dispatch_float8
 from fluxmi import _lib, synth
 from modules.flux_model import PreviewCall
 
-KINDS = {"plain": None, "hook": 0, "every1": 1, "every4": 4}
+KINDS = {"plain": None, "hook": 0, "every1": 1, "every4": 4, "tiny1": 1}
+DEFAULT_KINDS = "plain,hook,every1,every4"
 
 
 def main():
@@ -39,7 +42,7 @@ def main():
     ap.add_argument("--requests", type=int, default=5)
     ap.add_argument("--height", type=int, default=1024)
     ap.add_argument("--width", type=int, default=1024)
-    ap.add_argument("--kinds", default=",".join(KINDS), help="comma-separated, out of " + ", ".join(KINDS))
+    ap.add_argument("--kinds", default=DEFAULT_KINDS, help="comma-separated, out of " + ", ".join(KINDS))
     args = ap.parse_args()
     kinds = [k for k in args.kinds.split(",") if k]
     for k in kinds:
@@ -61,6 +64,16 @@ def main():
         proj = (0.1 * torch.randn(51, generator=g)).tolist()
         grid = (args.height // 16, args.width // 16)
         delivered = {k: 0 for k in kinds}
+        tiny = None
+        if "tiny1" in kinds:
+            from modules.tiny_vae import TinyDecoder
+
+            tiny = TinyDecoder(synth.make_taef1_state_dict(seed=0), device=dev, scale_factor=cfg.ae_params.scale_factor,
+                               shift_factor=cfg.ae_params.shift_factor)
+
+        def tiny_pixels(x0):  # FluxPipeline.unpack, tiny_decode and to_uint8 of the packed estimate [1, h w, 64]
+            z = x0.float().view(-1, grid[0], grid[1], 16, 2, 2).permute(0, 3, 1, 4, 2, 5).reshape(-1, 16, 2 * grid[0], 2 * grid[1])
+            return tiny.decode(z).clamp(-1, 1).add(1.0).mul(127.5).clamp(0, 255).permute(0, 2, 3, 1).contiguous().to(torch.uint8).cpu().numpy()
 
         def run(n, kind):
             every = KINDS[kind]
@@ -70,7 +83,7 @@ def main():
                     delivered[kind] += rgb is not None
                     return True
 
-                pv = PreviewCall(proj if every else None, grid, every, 0, n, cb)
+                pv = PreviewCall(proj if every else None, grid, every, 0, n, cb, tiny_pixels if kind == "tiny1" else None)
             return model.denoise(inp["img"], inp["img_ids"], inp["txt"], inp["txt_ids"], inp["y"], util_schedule(n, Li), guidance=3.5, use_graph=True,
                                  preview=pv)
 

@@ -254,6 +254,12 @@ int fluxmi_k_window_attention(const void* qkv, long long ld, const float* bias_t
                               int shift, float scale, hipStream_t s);
 int fluxmi_k_channel_norm(const void* x, long long ldx, const void* weight, const void* bias, void* y, long long ldy, long long rows, int D,
                           float eps, hipStream_t s);
+int fluxmi_k_window_attention16(const void* qkv, long long ld, const float* table, int table_rows, const int* index, void* out, long long ldo,
+                                int B, int H, int W, int heads, int shift, int overlap, float scale, hipStream_t s);
+int fluxmi_k_channel_mean(const void* x, long long ld, float* mean, float* work, long long work_bytes, int B, long long P, int C, hipStream_t s);
+int fluxmi_k_channel_combine(const void* a, long long lda, const void* b, long long ldb, const void* y, long long ldy, const float* mean,
+                             const float* w1, const float* b1, const float* w2, const float* b2, void* out, long long ldo, int B, long long P,
+                             int C, int Cs, float scale, hipStream_t s);
 int fluxmi_k_conv3x3_dense(const void* x, long long ldx, int Cin, const void* w2, const void* bias, void* out, long long ldo, int Cout,
                            const void* r1, long long ldr1, float a1, const void* r2, long long ldr2, float a2, float slope, int act,
                            int upsample, int B, int H, int W, hipStream_t s);

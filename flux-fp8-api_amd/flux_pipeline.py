@@ -1914,8 +1914,8 @@ class FluxPipeline:
     # ---- super-resolution (modules/upscaler.RRDBNet on fluxmi_conv3x3_dense) ---------------------------------------------------------------
     def _require_upscaler(self):
         if getattr(self, "upscaler", None) is None:
-            raise ValueError("fluxmi: upscaling needs an ESRGAN-family (RRDBNet) or SwinIR checkpoint: set config.upscaler_path to a local "
-                             ".safetensors / .pth file of one of the two (nothing is downloaded)")
+            raise ValueError("fluxmi: upscaling needs an ESRGAN-family (RRDBNet), SwinIR or HAT checkpoint: set config.upscaler_path to a local "
+                             ".safetensors / .pth file of one of them (nothing is downloaded)")
         return self.upscaler
 
     def upscale(self, image) -> torch.Tensor:

@@ -111,6 +111,9 @@ _SIGS = {
     "fluxmi_vae_attention": ([vp, vp, i64, i64, vp, i64, i64, vp, i64, i64, vp, i32, i32, i32, i32, vp], i32),
     "fluxmi_window_attention": ([vp, i64, vp, vp, i64, i32, i32, i32, i32, i32, C.c_float, vp], i32),
     "fluxmi_channel_norm": ([vp, i64, vp, vp, vp, i64, i64, i32, C.c_float, vp], i32),
+    "fluxmi_window_attention16": ([vp, i64, vp, i32, vp, vp, i64, i32, i32, i32, i32, i32, i32, C.c_float, vp], i32),
+    "fluxmi_channel_mean": ([vp, i64, vp, vp, i64, i32, i64, i32, vp], i32),
+    "fluxmi_channel_combine": ([vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, i64, i32, i64, i32, i32, C.c_float, vp], i32),
     "fluxmi_conv3x3_dense": ([vp, i64, i32, vp, vp, vp, i64, i32, vp, i64, C.c_float, vp, i64, C.c_float, C.c_float, i32, i32, i32, i32, i32, vp], i32),
     "fluxmi_conv3x3_block": ([vp, i64, vp, vp, vp, i64, i32, i32, i32, vp], i32),
     "fluxmi_canny_classify": ([vp, i64, i64, vp, i64, i64, i32, i32, i32, i32, i32, i32, vp], i32),

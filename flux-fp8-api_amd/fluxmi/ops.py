@@ -813,6 +813,86 @@ def channel_norm(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, D: i
     return out
 
 
+WINDOW16 = 16         # include/fluxmi.h FLUXMI_WINDOW16: HAT's attention window
+WINDOW16_OVERLAP = 4  # the one overlap fluxmi_window_attention16 takes besides 0: OCAB's 24 x 24 key neighbourhood
+
+
+def check_bias_index(index: torch.Tensor, table_rows: int, who: str = "window_attention16") -> None:
+    """the range check fluxmi_window_attention16 leaves to its caller: every entry in 0 .. table_rows - 1 (it reads the device: do it once)"""
+    lo, hi = (int(v) for v in torch.aminmax(index))
+    if lo < 0 or hi >= table_rows:
+        raise ValueError(f"{who}: the bias index holds entries in {lo}..{hi}, outside the table's rows 0..{table_rows - 1}")
+
+
+def window_attention16(qkv: torch.Tensor, table: torch.Tensor, index: torch.Tensor, heads: int, shift: int, overlap: int, scale: float,
+                       out: Optional[torch.Tensor] = None, check_index: bool = True) -> torch.Tensor:
+    """HAT's 16 x 16 window attention in ONE launch (fluxmi_window_attention16; include/fluxmi.h has the layout and the arithmetic).
+    qkv bf16 [B, H, W, 3 * heads * 32] as for window_attention; overlap 0: window self-attention over 256 keys, shift 0 or 8; overlap 4:
+    the overlapping cross-attention over the 24 x 24 = 576 pixels around each window (zero k / v outside the image), shift 0.  table fp32
+    [rows <= 1521, heads]; index int32 [256, Nk]: bias(a, b, h) = table[index[a, b], h].  H, W multiples of 16.  `check_index`: verify the
+    index against the table's rows first (a device read); a caller that did so when it loaded the index passes False.
+    -> out bf16 [B, H, W, heads * 32] (default: a new dense tensor; else a view under the same rule that does not overlap qkv)."""
+    _req(qkv, torch.bfloat16, "qkv")
+    _req(table, torch.float32, "table")
+    _req(index, torch.int32, "index")
+    heads = int(heads)
+    Cw = heads * WINDOW_HEAD_PAD
+    if qkv.ndim != 4 or qkv.shape[3] != 3 * Cw:
+        raise ValueError(f"window_attention16: qkv must be [B, H, W, 3 * heads * 32 = {3 * Cw}], got {tuple(qkv.shape)}")
+    B, H, W, _ = qkv.shape
+    Nk = (WINDOW16 + 2 * int(overlap)) ** 2
+    if table.ndim != 2 or table.shape[1] != heads or not table.is_contiguous():
+        raise ValueError(f"window_attention16: table must be contiguous [rows, heads = {heads}], got {tuple(table.shape)}")
+    if tuple(index.shape) != (WINDOW16 ** 2, Nk) or not index.is_contiguous():
+        raise ValueError(f"window_attention16: index must be contiguous [{WINDOW16 ** 2}, {Nk}] at overlap={overlap}, got {tuple(index.shape)}")
+    if check_index:
+        check_bias_index(index, table.shape[0])
+    if out is None:
+        out = torch.empty((B, H, W, Cw), dtype=torch.bfloat16, device=qkv.device)
+    _req(out, torch.bfloat16, "out")
+    if tuple(out.shape) != (B, H, W, Cw):
+        raise ValueError(f"window_attention16: out must be {(B, H, W, Cw)}, got {tuple(out.shape)}")
+    ld, ldo = _depth_pixels(qkv, "window_attention16", "qkv"), _depth_pixels(out, "window_attention16", "out")
+    call("fluxmi_window_attention16", _p(qkv), ld, _p(table), table.shape[0], _p(index), _p(out), ldo, B, H, W, heads, int(shift), int(overlap),
+         float(scale), _stream())
+    return out
+
+
+def channel_mean(x: torch.Tensor) -> torch.Tensor:
+    """x bf16 [B, H, W, C] (a channel window of an NHWC pixel buffer is fine; C % 8 == 0, <= 512) -> fp32 [B, C], the mean over H x W of
+    every channel, summed in fp32 in one fixed order (fluxmi_channel_mean: two launches, no atomics)."""
+    ld = _depth_pixels(x, "channel_mean", "x")
+    B, H, W, Cc = x.shape
+    P = H * W
+    work = torch.empty(B * ((P + 255) // 256) * Cc, dtype=torch.float32, device=x.device)
+    mean = torch.empty((B, Cc), dtype=torch.float32, device=x.device)
+    call("fluxmi_channel_mean", _p(x), ld, _p(mean), _p(work), work.numel() * 4, B, P, Cc, _stream())
+    return mean
+
+
+def channel_combine(a: torch.Tensor, b: torch.Tensor, y: torch.Tensor, mean: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor,
+                    w2: torch.Tensor, b2: torch.Tensor, scale: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """HAT's channel-attention gate and block sum in ONE launch (fluxmi_channel_combine): g = sigmoid(w2 relu(w1 mean + b1) + b2) per image
+    in fp32, out = bf16(a + b + scale * y * g).  a, b, y bf16 [B, H, W, C] views; mean fp32 [B, C]; w1 [Cs, C], b1 [Cs], w2 [C, Cs], b2 [C]
+    fp32 contiguous, Cs <= 64.  `out`: a view of that shape (default: a new dense tensor; may be a, b or y)."""
+    B, H, W, Cc = a.shape
+    if out is None:
+        out = torch.empty((B, H, W, Cc), dtype=torch.bfloat16, device=a.device)
+    lds = []
+    for t, name in ((a, "a"), (b, "b"), (y, "y"), (out, "out")):
+        if tuple(t.shape) != (B, H, W, Cc):
+            raise ValueError(f"channel_combine: {name} must be {(B, H, W, Cc)}, got {tuple(t.shape)}")
+        lds.append(_depth_pixels(t, "channel_combine", name))
+    Cs = w1.shape[0]
+    for t, name, shape in ((mean, "mean", (B, Cc)), (w1, "w1", (Cs, Cc)), (b1, "b1", (Cs,)), (w2, "w2", (Cc, Cs)), (b2, "b2", (Cc,))):
+        _req(t, torch.float32, name)
+        if tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"channel_combine: {name} must be contiguous fp32 {shape}, got {tuple(t.shape)}")
+    call("fluxmi_channel_combine", _p(a), lds[0], _p(b), lds[1], _p(y), lds[2], _p(mean), _p(w1), _p(b1), _p(w2), _p(b2), _p(out), lds[3],
+         B, H * W, Cc, Cs, float(scale), _stream())
+    return out
+
+
 def patchify(pix: torch.Tensor, patch: int, grid: int, k_pad: int) -> torch.Tensor:
     """pix bf16 [B, C, H, W] -> patch rows [B*grid*grid, k_pad], column order (c, ky, kx), zero past C*patch*patch (fluxmi_patchify)."""
     _req(pix, torch.bfloat16, "pix")

@@ -386,3 +386,58 @@ def make_swinir_state_dict(embed_dim: int = 60, depths=(2, 2), heads=(2, 2), mlp
             conv(n, num_feat, num_feat)
     conv("conv_last", 3, num_feat)
     return {wrap: sd} if wrap else sd
+
+
+def make_hat_state_dict(embed_dim: int = 60, depths=(2, 2), heads=(2, 2), mlp_ratio: float = 2.0, compress: int = 3, squeeze: int = 30,
+                        scale: int = 4, num_feat: int = 64, seed: int = 0, wrap: str | None = None, with_index: bool = True) -> Dict[str, torch.Tensor]:
+    """A seeded HAT checkpoint (modules/hat.py) in hat_arch.py's key layout for tests and tools, drawn like make_swinir_state_dict: fp32
+    tensors that hold bf16 values, activations O(1), bias tables N(0, 0.5) of 961 (window attention) and 1521 (overlapping attention) rows.
+    `with_index`: include the relative_position_index_SA / _OCA buffers a real file carries (modules/hat.py's formulas, the negative
+    entries of the OCA index as they are).  HAT-M x4 is (180, (6,) * 6, (6,) * 6), HAT-L (180, (6,) * 12, (6,) * 12)."""
+    from modules import hat
+
+    if scale not in (2, 4) or len(depths) != len(heads):
+        raise ValueError("make_hat_state_dict: scale 2 / 4, one head count per layer")
+    gen = torch.Generator().manual_seed(4000 + seed)
+    C, hidden, Cc, Cs = embed_dim, int(embed_dim * mlp_ratio), embed_dim // compress, embed_dim // squeeze
+    sd: Dict[str, torch.Tensor] = {}
+    rn = lambda *shape, std=1.0: (std * torch.randn(*shape, generator=gen)).bfloat16().float()  # noqa: E731
+
+    def conv(name, co, ci, k=3):
+        sd[name + ".weight"], sd[name + ".bias"] = rn(co, ci, k, k, std=1.0 / math.sqrt(k * k * ci)), rn(co, std=0.1)
+
+    def linear(name, co, ci):
+        sd[name + ".weight"], sd[name + ".bias"] = rn(co, ci, std=1.0 / math.sqrt(ci)), rn(co, std=0.1)
+
+    def norm(name):
+        sd[name + ".weight"], sd[name + ".bias"] = (1.0 + rn(C, std=0.1)).bfloat16().float(), rn(C, std=0.1)
+
+    def attention(p, a, rows, h, hid):
+        norm(p + "norm1")
+        sd[p + a + "relative_position_bias_table"] = rn(rows, h, std=0.5)
+        linear(p + a + "qkv", 3 * C, C), linear(p + a + "proj", C, C)
+        norm(p + "norm2")
+        linear(p + "mlp.fc1", hid, C), linear(p + "mlp.fc2", C, hid)
+
+    conv("conv_first", C, 3)
+    norm("patch_embed.norm")
+    if with_index:
+        sd["relative_position_index_SA"], sd["relative_position_index_OCA"] = hat.index_sa(), hat.index_oca()
+    for i, (d, h) in enumerate(zip(depths, heads)):
+        for j in range(d):
+            p = f"layers.{i}.residual_group.blocks.{j}."
+            attention(p, "attn.", hat.SA_ROWS, h, hidden)
+            conv(p + "conv_block.cab.0", Cc, C), conv(p + "conv_block.cab.2", C, Cc)
+            # the squeeze sees channel means (small): a unit-gain first layer keeps the gate away from a constant 1 / 2
+            sd[p + "conv_block.cab.3.attention.1.weight"], sd[p + "conv_block.cab.3.attention.1.bias"] = rn(Cs, C, 1, 1, std=1.0), rn(Cs, std=0.1)
+            conv(p + "conv_block.cab.3.attention.3", C, Cs, 1)
+        attention(f"layers.{i}.residual_group.overlap_attn.", "", hat.OCA_ROWS, h, hidden)
+        conv(f"layers.{i}.conv", C, C)
+    norm("norm")
+    conv("conv_after_body", C, C)
+    conv("conv_before_upsample.0", num_feat, C)
+    conv("upsample.0", 4 * num_feat, num_feat)
+    if scale == 4:
+        conv("upsample.2", 4 * num_feat, num_feat)
+    conv("conv_last", 3, num_feat)
+    return {wrap: sd} if wrap else sd

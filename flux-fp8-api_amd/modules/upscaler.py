@@ -226,7 +226,8 @@ class RRDBNet:
 
 def read_upscaler(path: str, device="cuda:0"):
     """a LOCAL .safetensors or .pth (torch.load(weights_only=True)) file -> RRDBNet, or modules.swinir.SwinIR when the keys are a Swin
-    transformer's (which refuses Swin2SR / HAT and the SwinIR variants it does not cover by name); nothing is downloaded"""
+    transformer's (which refuses Swin2SR and the SwinIR variants it does not cover by name), or modules.hat.HAT when they hold HAT's
+    overlapping cross-attention / channel-attention blocks (looked for first); nothing is downloaded"""
     if str(path).endswith(".safetensors"):
         from safetensors.torch import load_file
 
@@ -235,8 +236,10 @@ def read_upscaler(path: str, device="cuda:0"):
         sd = torch.load(str(path), map_location="cpu", weights_only=True)
     if not isinstance(sd, dict):
         raise UpscalerFormatError(f"upscaler: {path} does not hold a state dict")
-    from modules import swinir
+    from modules import hat, swinir
 
+    if hat.is_hat(sd):
+        return hat.HAT(sd, device=device)
     if swinir.is_swin_family(sd):
         return swinir.SwinIR(sd, device=device)
     return RRDBNet(sd, device=device)

@@ -410,7 +410,7 @@ def load_ip_adapter(config: ModelSpec, device=None):
 
 
 def load_upscaler(config: ModelSpec, device=None):
-    """The network of config.upscaler_path on `device` -- modules/upscaler.RRDBNet or modules/swinir.SwinIR, by the file's keys -- or None
+    """The network of config.upscaler_path on `device` -- modules/upscaler.RRDBNet, modules/swinir.SwinIR or modules/hat.HAT, by the file's keys -- or None
     unless the path is a local file.  Nothing is downloaded.  A checkpoint of another architecture is refused by name."""
     import os
 

@@ -542,6 +542,44 @@ int fluxmi_window_attention(const void* qkv, long long ld, const float* bias_tab
  * shorter than D8, or a pointer that is not 16-byte aligned. */
 int fluxmi_channel_norm(const void* x, long long ldx, const void* weight, const void* bias, void* y, long long ldy, long long rows, int D,
                         float eps, void* stream);
+/* 16 x 16 window attention with an INDEXED relative-position bias: the attention of HAT (modules/hat.py; csrc/window_attention16.hip), window
+ * FLUXMI_WINDOW16 = 16 (256 queries), heads padded to 32 columns, with fluxmi_window_attention's conventions for qkv, out, ld, ldo, the rolled
+ * coordinates and the write-back at the source pixel.  One launch per call; no score matrix, unfolded copy or permuted copy reaches memory.
+ *   overlap 0   HAT's window self-attention: the keys are the window's own 256 tokens (Nk = 256); shift 0 or 8.  Shift mask, only when
+ *               shift > 0: the region of a rolled row i is 0 if i < H - 16, 1 if i < H - 8, else 2, columns with W likewise, and a (query,
+ *               key) pair whose ids 3 * row_region + col_region differ gets -100 added to its logit.
+ *   overlap 4   HAT's overlapping cross-attention (OCAB), shift 0 only: for query window (wy, wx) the keys are the 24 x 24 pixels
+ *               16 wy - 4 .. 16 wy + 19, 16 wx - 4 .. 16 wx + 19 in row-major order (Nk = 576).  A key position outside the image is a key
+ *               whose k and v are exactly zero -- what nn.Unfold(24, stride 16, padding 4) makes of it after the qkv linear: it still takes
+ *               part in the softmax with its bias as its logit, and adds nothing to the numerator.  Such keys are never read from memory.
+ *   table       fp32 [table_rows][heads] (HAT: 961 rows for self-attention, 1521 for OCAB; at most 1521)
+ *   index       int32 [256][Nk]: bias(query token a, key b, head h) = table[index[a * Nk + b]][h].  The index is DATA (HAT's
+ *               relative_position_index_SA / _OCA buffers), not a formula of this library.  Every entry must lie in 0 .. table_rows - 1:
+ *               the CALLER checks that (once, when it loads the index); this call trusts it.
+ * Arithmetic:  s = fp32 MFMA sum of the bf16 products q . k over the 32 columns;  t = s * scale + bias (+ -100 where masked) in fp32;  the
+ * softmax is STREAMED over key tiles of 32 with a running maximum m per query: entering a tile, l and O are multiplied by
+ * exp(m_old - m_new);  p = exp(t - m) and l += p in fp32;  O += bf16(p) v on the matrix pipe with fp32 accumulation;  out = bf16(O / l) --
+ * the only rounding of the output.  Deterministic (no atomics, fixed order); a sample's bits depend on that sample alone; addresses are 64-bit.
+ * Returns non-zero before any launch (text in fluxmi_last_error) for: H or W not a positive multiple of 16; overlap other than 0 / 4; shift
+ * other than 0 / 8, or a shift with an overlap; heads outside 1..16; table_rows outside 1..1521; B above 65535 or more than 2^31 - 1 windows
+ * (the launch grid); a stride that is no multiple of 8 or shorter than its columns; qkv, out or index not 16-byte aligned; out overlapping qkv. */
+#define FLUXMI_WINDOW16 16
+int fluxmi_window_attention16(const void* qkv, long long ld, const float* table, int table_rows, const int* index, void* out, long long ldo,
+                              int B, int H, int W, int heads, int shift, int overlap, float scale, void* stream);
+/* Channel attention of HAT's CAB, in two calls.
+ * fluxmi_channel_mean: mean[b][c] = (sum over the P pixels of image b of x[b][p][c]) / P for c < C.  x bf16 [B][P] pixels with stride ld;
+ * mean fp32 [B][C]; work fp32, FLUXMI_CHANNEL_MEAN_WORK_BYTES(B, P, C) bytes.  Two launches, no atomics: blocks of 256 pixels are summed in
+ * fp32 in one fixed order into `work`, then the blocks in one fixed order (16 interleaved runs, then the runs); one division by P at the end.  C a multiple of 8 in 8..512.
+ * fluxmi_channel_combine: g[b][c] = sigmoid(b2[c] + sum_j w2[c][j] relu(b1[j] + sum_c' w1[j][c'] mean[b][c'])) in fp32 (w1 [Cs][C], b1 [Cs],
+ * w2 [C][Cs], b2 [C], all fp32; Cs in 1..64), then  out = bf16(a + b + scale * y * g[b][c])  in fp32 with that ONE rounding; a, b, y, out
+ * bf16 [B][P] pixels with their own strides, out may be a, b or y.  One launch.  Both are deterministic, a sample's bits depend on that
+ * sample alone, and both return non-zero before any launch for a C, Cs, B or P outside those ranges, a stride that is no multiple of 8 or
+ * shorter than C, a short `work`, or a bf16 pointer that is not 16-byte aligned. */
+#define FLUXMI_CHANNEL_MEAN_WORK_BYTES(B, P, C) ((long long)(B) * (((long long)(P) + 255) / 256) * (C) * 4)
+int fluxmi_channel_mean(const void* x, long long ld, float* mean, float* work, long long work_bytes, int B, long long P, int C, void* stream);
+int fluxmi_channel_combine(const void* a, long long lda, const void* b, long long ldb, const void* y, long long ldy, const float* mean,
+                           const float* w1, const float* b1, const float* w2, const float* b2, void* out, long long ldo, int B, long long P,
+                           int C, int Cs, float scale, void* stream);
 /* Patch rows of a stride-`patch` "valid" convolution: pix bf16 [B, C, H, W] (NCHW, contiguous) -> out bf16 [B*grid*grid, Kp], row
  * (b, gy, gx), column c*patch*patch + ky*patch + kx (the order of a Conv2d weight [N, C, patch, patch] flattened), columns >= C*patch*patch
  * zero.  Pixels past grid*patch are not read.  Kp %% 8 == 0; grid*patch <= H, W.  SigLIP-so400m: C 3, patch 14, grid 27, Kp 640. */
